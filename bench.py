@@ -6,7 +6,7 @@ semantics (src/heightmap.cpp:130-187): build_arrays + enable_glaciate + eval of 
 mesh_freq_filter 1 -> start_eval_sin 10), min(vals), apply_erosion(vals, N, N, min, 1000 droplets), all device resident.
 The z grid never leaves HBM inside the timed region (there is no input grid; parameters are a few hundred bytes).
 
-  python bench.py [--gpus N --steps K --warmup W --size 16384 --mode sine --droplets 1000]   (N > 1: starts N ranks itself through torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W --size 16384 --mode sine --droplets 1000] [--full] [--dump-outputs DIR]   (N > 1: starts N ranks itself through torch.distributed.run)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...      (one rank per GPU; WORLD_SIZE must equal --gpus)
 
 `value` (the headline):
@@ -17,7 +17,8 @@ The z grid never leaves HBM inside the timed region (there is no input grid; par
           noise runs everywhere (3dworld_amd/dist.py::OneHeightmapPipeline).  Bit-identical to the single-GPU heightmap.  The independent-regions number of round 1-3 (every
           rank its own N x N region, no collective, weak scaling) is measured in the same run and printed as `value_weak` / detail.regions.
 
-The same run also measures, under `detail` (incl. `dense_erosion`: 10^6 droplets on the bench grid and on BASELINE config 3's 4096^2 map) (all ranks take part, rank 0 reports; switch off with --no-extras):
+A plain run sets up, warms up, times the K steps of the headline, writes its outputs (--dump-outputs) and prints the line: nothing else.
+With --full the same run also measures, under `detail` (incl. `dense_erosion`: 10^6 droplets on the bench grid and on BASELINE config 3's 4096^2 map) (all ranks take part, rank 0 reports; --full --no-extras leaves them out):
   single   one heightmap in flight (no overlap of a map's erosion with the next map's noise): the latency of one map
   strips   the noise + min part of the one-grid line alone: rank r evaluates rows [r*N/W, (r+1)*N/W) (terra_gen_grid_rows_minmax_dev, bit-identical to the
            full grid), min(vals) = one float through all_reduce(min) over RCCL; no erosion
@@ -27,8 +28,12 @@ The same run also measures, under `detail` (incl. `dense_erosion`: 10^6 droplets
   modes    the same 16384^2 step with simplex / Perlin / domain-warp noise (rank 0)
 `--workload onegrid|regions|strips|tiles` makes one of those the headline `value` instead (for a scaling sweep of that mode alone; onegrid also at N = 1).
 
-Prints ONE JSON line on rank 0.  `roofline` = dominant kernel, measured with HIP events on the library's stream;
-`cpu_baseline` = the reference's own CPU code (oracle/_ref) or the C restatement (oracle/) timed on this host, rank 0, N=1.
+Prints ONE JSON line on rank 0.  With --full also: `roofline` = dominant kernel, measured with HIP events on the library's stream (per-kernel times under `detail`);
+`cpu_baseline` = the reference's own CPU code (oracle/_ref) or the C restatement (oracle/) timed on this host, rank 0, N=1; at N = 1 the one-rank RCCL group and the one-grid line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the headline's last step computed (its heightmap after erosion, and the {min, max} its noise kernel left in
+device memory) as float32 .npy files under DIR: the whole grid when it takes at most 48 MiB, otherwise a fixed seeded sample of cells plus a fixed seeded set of whole rows.
+The inputs are synthetic and fixed by the arguments, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import importlib
@@ -78,9 +83,37 @@ def parse():
     p.add_argument("--no-rccl-world1", action="store_true", help="N = 1: do not create the one-rank RCCL group (the collectives of the sharded paths are then skipped)")
     p.add_argument("--clock-warmup-ms", type=float, default=150.0, help="untimed steps run for this long right before every timed region so that it runs at the chip's sustained clock (a cold MI355X needs ~30 ms of load to get there, an idle gap of 5 ms already costs 12 %%: profiles/r04_clock_ramp.txt); 0 = only the W warm-up steps")
     p.add_argument("--cpu-size", type=int, default=0, help="grid edge of the CPU sample (default: the benchmark's own size)")
+    p.add_argument("--full", action="store_true", help="also every secondary measurement of the run: the `detail` extras, the one-grid line at N = 1, the one-rank RCCL group, per-kernel "
+                   "times and the roofline, the CPU baseline (off: a plain run times the headline alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument("--simulate-world", type=int, default=8, help="detail.onegrid_rank_floor: what one rank of the one-grid line does per step at this world size (its 1/W row strip of noise + the "
                    "all_reduce(min) + every W-th step an erosion), measured on this GPU: the floor of the N = W step and the prediction that follows from it")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.no_extras = args.no_cpu_baseline = args.no_rccl_world1 = True
+    return args
+
+
+DUMP_WHOLE_BYTES = 48 << 20   # a grid up to this size is written whole
+DUMP_CELLS = 1 << 23          # otherwise: this many cells at seeded positions (32 MiB) ...
+DUMP_ROWS = 256               # ... and this many seeded whole rows (16 MiB at 16384^2)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, torch, z, n, mm=None):
+    """the heightmap of the headline's last step (a device tensor of n * n float32) and its {min, max}, as float32 .npy files under out_dir (see the module docstring)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if z.numel() * 4 <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(out_dir, "heightmap.npy"), z.view(n, n).cpu().numpy())
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        cells = np.unique(rng.integers(0, z.numel(), DUMP_CELLS))
+        rows = np.sort(rng.choice(n, min(DUMP_ROWS, n), replace=False))
+        np.save(os.path.join(out_dir, "heightmap_cells.npy"), z[torch.from_numpy(cells).to(z.device)].cpu().numpy())
+        np.save(os.path.join(out_dir, "heightmap_rows.npy"), z.view(n, n)[torch.from_numpy(rows).to(z.device)].cpu().numpy())
+    if mm is not None:
+        np.save(os.path.join(out_dir, "heightmap_minmax.npy"), mm.cpu().numpy())
 
 
 def cpu_baseline(args, mode):
@@ -302,6 +335,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and not (args.workload == "regions" or (args.workload == "heightmap" and args.gpus == 1)):
+        raise SystemExit("--dump-outputs: only the heightmaps of the heightmap (N = 1) / regions headline are written")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus)  # does not return
     import torch
@@ -413,11 +448,14 @@ def main():
             noise_done.set()
         c.apply_erosion_dev(zz.data_ptr(), N, N, mn, args.droplets, pkg.ERODE_MINZ_IS_MIN)
 
+    last_pipe = [0]  # the pipeline that ran the last step of the last run_steps() call
+
     def run_steps(k, npipe):
         """k steps in total on npipe pipelines (one host thread each: the library calls release the GIL)."""
         if npipe == 1:
             for _ in range(k):
                 step(0)
+            last_pipe[0] = 0
             return
         # the pipelines start one noise phase apart (worker p issues its first step when worker p-1's first noise call has returned): started together
         # they run in lockstep -- four noise kernels sharing the chip, then four erosions leaving it idle -- and only drift into an overlapping
@@ -427,11 +465,13 @@ def main():
         first_noise_done = [threading.Event() for _ in range(npipe)]
         lock = threading.Lock()
         left = [k]
-        def take():
+        def take(p):
             with lock:
                 if left[0] <= 0:
                     return False
                 left[0] -= 1
+                if left[0] == 0:
+                    last_pipe[0] = p
                 return True
         errs = []
 
@@ -440,7 +480,7 @@ def main():
             try:
                 if p > 0:
                     first_noise_done[p - 1].wait()
-                while not errs and take():
+                while not errs and take(p):
                     step(p, first_noise_done[p] if first else None)
                     first = False
             except Exception as e:  # noqa: BLE001 -- reported by the caller's thread; nobody is left waiting for this worker
@@ -534,6 +574,9 @@ def main():
             dt = timed(lambda k: run_steps(k, P), K, max(W, 2 * P))  # at least two untimed steps per pipeline: first-use allocations, graph captures and clocks settle
             value_weak = world * cells * K / dt / 1e9
             value, scaling, workload, par = value_weak, "weak", workload_w, par_w
+            if args.dump_outputs and rank == 0:  # before anything else runs on these grids
+                lp = last_pipe[0]
+                dump_outputs(args.dump_outputs, torch, zs[lp], N, mms[lp] if args.handoff == "event" else None)
         if pipe is not None:
             dts = timed(lambda k: pipe.run(k), K, max(W, 2), "onegrid")
             value_strong = cells * K / dts / 1e9
@@ -596,7 +639,7 @@ def main():
         bench_detail.sharded(env, detail, run_steps)
 
     # ---- per-kernel times, live, HIP events on the library's stream (rank 0 only; the other ranks wait at the barrier below)
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = max(3, min(K, 16))
         t_s = time.perf_counter()
         while (time.perf_counter() - t_s) * 1e3 < args.clock_warmup_ms:  # the kernel times below are quoted at the sustained clock, like the headline
@@ -637,35 +680,37 @@ def main():
         # dominant kernel by time: the noise grid kernel (k_sine_grid / k_noise_grid).  It is fp32-VALU bound (45 flop per byte written), so the
         # roofline is the flop one: achieved = SURVEY 8(d)'s flops per cell x cells / kernel time, peak = the chip's fp32 vector peak.  The HBM side
         # (4 B written per cell) is reported beside it.
-        ms_k = detail["ms_grid_kernel"]
-        fl = flops_per_cell(mode, args.octaves)
-        tflops = fl * cells / (ms_k * 1e-3) / 1e12
-        hbm = 4.0 * cells / (ms_k * 1e-3) / 1e9
-        traffic = None  # HBM bytes per launch from the PMC passes (2 x FETCH_SIZE + WRITE_SIZE, profiles/*_pmc_traffic.json), only for the configuration they were taken on
-        traffic_source = None
-        for fn in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
-            try:
-                pm = json.load(open(os.path.join(ROOT, "profiles", fn)))["kernels"]["k_sine_grid"]
-                if mode == 0 and N == 16384 and args.octaves == 8:
-                    traffic = pm["hbm_bytes_per_launch"]
-                    traffic_source = f"profiles/{fn} (2 x FETCH_SIZE + WRITE_SIZE of separate rocprofv3 --pmc passes over tools/prof_driver.py: a recorded constant of this configuration, not measured in this run)"
-                    break
-            except Exception:
-                pass
-        roof = {"bound": "valu", "kernel": "k_sine_grid (+table kernels)" if mode == 0 else f"k_noise_grid<{args.mode}>", "achieved": round(tflops, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(tflops / FP32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source, "algorithmic_flops": fl * cells, "algorithmic_bytes": 4 * cells,
-                "hbm_achieved_gbs": round(hbm, 2), "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": round(hbm / HBM_PEAK_GBS, 4),
-                "nofma_peak_tops": VALU_NOFMA_TOPS, "nofma_frac": round(tflops / VALU_NOFMA_TOPS, 4), "operative_ceiling": "nofma_frac (bit parity forbids the fused multiply-add the fp32 peak counts)",
-                "note": "fp32 VALU bound; the peak counts fused multiply-adds at 2.4 GHz.  Bit-parity with the FMA-free CPU reference forbids fusing (mul and add issue separately): nofma_frac is the "
-                        "fraction of that rate; and the chip sustains ~1.94 GHz under this kernel (GRBM_GUI_ACTIVE / duration, profiles/r04_clock_ramp.txt): at the clock it gets, its ~6000 "
-                        "VALU instructions per wave (5120 of them the sum) keep the vector ALUs issuing ~90 % of the time (profiles/r04_pmc_summary.txt); the f32 matrix instructions share that datapath "
-                        "(profiles/r04_sine_matrix_pipe.txt)"}
+        roof = None  # per-kernel times and the roofline: --full
+        if args.full:
+            ms_k = detail["ms_grid_kernel"]
+            fl = flops_per_cell(mode, args.octaves)
+            tflops = fl * cells / (ms_k * 1e-3) / 1e12
+            hbm = 4.0 * cells / (ms_k * 1e-3) / 1e9
+            traffic = None  # HBM bytes per launch from the PMC passes (2 x FETCH_SIZE + WRITE_SIZE, profiles/*_pmc_traffic.json), only for the configuration they were taken on
+            traffic_source = None
+            for fn in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
+                try:
+                    pm = json.load(open(os.path.join(ROOT, "profiles", fn)))["kernels"]["k_sine_grid"]
+                    if mode == 0 and N == 16384 and args.octaves == 8:
+                        traffic = pm["hbm_bytes_per_launch"]
+                        traffic_source = f"profiles/{fn} (2 x FETCH_SIZE + WRITE_SIZE of separate rocprofv3 --pmc passes over tools/prof_driver.py: a recorded constant of this configuration, not measured in this run)"
+                        break
+                except Exception:
+                    pass
+            roof = {"bound": "valu", "kernel": "k_sine_grid (+table kernels)" if mode == 0 else f"k_noise_grid<{args.mode}>", "achieved": round(tflops, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(tflops / FP32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source, "algorithmic_flops": fl * cells, "algorithmic_bytes": 4 * cells,
+                    "hbm_achieved_gbs": round(hbm, 2), "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": round(hbm / HBM_PEAK_GBS, 4),
+                    "nofma_peak_tops": VALU_NOFMA_TOPS, "nofma_frac": round(tflops / VALU_NOFMA_TOPS, 4), "operative_ceiling": "nofma_frac (bit parity forbids the fused multiply-add the fp32 peak counts)",
+                    "note": "fp32 VALU bound; the peak counts fused multiply-adds at 2.4 GHz.  Bit-parity with the FMA-free CPU reference forbids fusing (mul and add issue separately): nofma_frac is the "
+                            "fraction of that rate; and the chip sustains ~1.94 GHz under this kernel (GRBM_GUI_ACTIVE / duration, profiles/r04_clock_ramp.txt): at the clock it gets, its ~6000 "
+                            "VALU instructions per wave (5120 of them the sum) keep the vector ALUs issuing ~90 % of the time (profiles/r04_pmc_summary.txt); the f32 matrix instructions share that datapath "
+                            "(profiles/r04_sine_matrix_pipe.txt)"}
         out = {"metric": "heightmap Gcells/sec (noise+erosion), 16384^2 grid", "value": round(value, 4), "unit": "Gcells/s", "n_gpus": world, "steps": K, "warmup": W,
                "value_strong": None if value_strong is None else round(value_strong, 4), "value_weak": None if value_weak is None else round(value_weak, 4),
                "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": workload, "mesh_gen_mode": mode, "octaves": args.octaves, "droplets": args.droplets, "grid": N, "pipelines_per_gpu": P if (args.workload in ("heightmap", "regions") and scaling == "weak") else 1, "handoff": args.handoff, "parallelism": par},
                "latency_ms_single": detail.get("single", {}).get("latency_ms_single", round(ms_step, 4) if P == 1 else None),
-               "roofline": roof, "detail": dict(detail, erosion=rep, rccl=rccl_note,
+               **({"roofline": roof} if roof is not None else {}), "detail": dict(detail, erosion=rep, rccl=rccl_note,
                                                   clock_warmup={"ms": args.clock_warmup_ms, "untimed_steps_run": spin_log,
                                                                 "why": "a cold MI355X reaches its sustained clock after ~30 ms of load and loses it again within ~5 ms of idling (profiles/r04_clock_ramp.txt); every timed region is preceded by untimed steps of the same kind for this long, with < 1 ms between them and the timed steps"})}
         if not args.no_cpu_baseline and world == 1:

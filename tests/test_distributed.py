@@ -256,7 +256,7 @@ def test_bench_world1_runs_its_collectives_through_rccl():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TERRA_BENCH_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--size", "2048", "--no-cpu-baseline", "--workload", "strips"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--size", "2048", "--full", "--no-cpu-baseline", "--workload", "strips"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _last_json_line(r.stdout)

@@ -37,8 +37,8 @@ tests)
 	;;
 bench)
 	if [ $# -eq 0 ]; then
-		timeout 900 python bench.py > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"; echo "bench rc $?"
-		timeout 600 python bench.py --pipelines 1 --no-extras --no-cpu-baseline > "$OUT/bench_pipelines1_line.json" 2> "$OUT/bench_p1.err"; echo "bench p1 rc $?"
+		timeout 900 python bench.py --full > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"; echo "bench rc $?"
+		timeout 600 python bench.py --full --pipelines 1 --no-extras --no-cpu-baseline > "$OUT/bench_pipelines1_line.json" 2> "$OUT/bench_p1.err"; echo "bench p1 rc $?"
 		python - <<PY
 import json
 for f in ("bench_default_line.json", "bench_pipelines1_line.json"):
@@ -52,8 +52,8 @@ profile)
 	WHAT=${*:-bench p1 tiles tile_erosion weights ao voxels noise erosion}
 	for w in $WHAT; do
 		case $w in
-		bench) prof bench_default python "$ROOT/bench.py" --no-cpu-baseline --no-extras --no-rccl-world1 ;;
-		p1) prof bench_pipelines1 python "$ROOT/bench.py" --no-cpu-baseline --no-extras --no-rccl-world1 --pipelines 1 ;;
+		bench) prof bench_default python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --no-rccl-world1 ;;
+		p1) prof bench_pipelines1 python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --no-rccl-world1 --pipelines 1 ;;
 		tiles) prof tiles python "$ROOT/tools/prof_tiles.py" ;;
 		tile_erosion) prof tile_erosion python "$ROOT/tools/prof_tile_erosion.py" 1000 2 ;;
 		weights) prof weights python "$ROOT/tools/prof_weights.py" 3 ;;
@@ -82,7 +82,7 @@ erosion)
 	cut -c1-150 "$OUT/erosion_timings.txt"
 	;;
 multirank)
-	TERRA_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 8 --warmup 2 --size 4096 --no-cpu-baseline > "$OUT/bench_2rank_gloo.json" 2> "$OUT/bench_2rank_gloo.err"; echo "bench2 rc $?"
+	TERRA_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 8 --warmup 2 --size 4096 --full --no-cpu-baseline > "$OUT/bench_2rank_gloo.json" 2> "$OUT/bench_2rank_gloo.err"; echo "bench2 rc $?"
 	for w in strips tiles; do TERRA_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 8 --warmup 2 --workload $w --no-cpu-baseline --no-extras > "$OUT/bench_2rank_$w.json" 2> "$OUT/bench_2rank_$w.err"; echo "$w rc $?"; done
 	python - <<PY
 import json
