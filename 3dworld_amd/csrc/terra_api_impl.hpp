@@ -564,6 +564,7 @@ int terra_tiles_create_weights(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 	TERRA_CHECK_CTX if (n && (!tile_xy || !h_zvals || !h_weights)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
+		ctx->eng.require_tile_128("tiles_create_weights"); // (before the zvals are read: they are 130^2 floats a tile)
 		auto &be = ctx->eng.be;
 		size_t const zb = (size_t)n*130*130*4, wb = (size_t)n*129*129*4, gb = (size_t)n*32*32*sizeof(terra_grass_block), hb = ((size_t)n + 3) & ~(size_t)3;
 		uint8_t *d = (uint8_t *)be.alloc(zb + wb + gb + hb);
@@ -586,7 +587,8 @@ int terra_tiles_ao_lighting(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
 		auto &be = ctx->eng.be;
-		size_t const zb = (size_t)n*130*130*4, ab = (size_t)n*129*129;
+		ctx->eng.require_scene(); ctx->eng.require_tile_size();
+		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, ab = (size_t)n*(S + 1)*(S + 1);
 		uint8_t *d = (uint8_t *)be.alloc(zb + ab);
 		try {
 			be.h2d(d, h_zvals, zb);
@@ -619,7 +621,8 @@ int terra_tiles_mesh_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
 		auto &be = ctx->eng.be;
-		size_t const zb = (size_t)n*130*130*4, sb = (size_t)n*130*130;
+		ctx->eng.require_scene(); ctx->eng.require_tile_size();
+		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*(S + 2)*(S + 2);
 		uint8_t *d = (uint8_t *)be.alloc(zb + sb);
 		try {
 			be.h2d(d, h_zvals, zb);
@@ -642,7 +645,8 @@ int terra_tiles_post(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const f
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
 		auto &be = ctx->eng.be;
-		size_t const zb = (size_t)n*130*130*4, sb = (size_t)n*sizeof(terra_tile_stats), nb = (size_t)n*129*129*4, mb = (size_t)n*4;
+		ctx->eng.require_scene(); ctx->eng.require_tile_size();
+		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*sizeof(terra_tile_stats), nb = (size_t)n*(S + 1)*(S + 1)*4, mb = (size_t)n*4;
 		uint8_t *d = (uint8_t *)be.alloc(zb + sb + nb + mb + 1024);
 		float *dz = (float *)d; terra_tile_stats *ds = (terra_tile_stats *)(d + zb); uint8_t *dn = d + zb + sb; float *dm = (float *)(d + zb + sb + nb);
 		try {
@@ -660,7 +664,8 @@ int terra_tiles_create_zvals(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
 		auto &be = ctx->eng.be;
-		size_t const zb = (size_t)n*130*130*4, sb = (size_t)n*sizeof(terra_tile_stats), nb = (size_t)n*129*129*4, mb = (size_t)n*4;
+		ctx->eng.require_scene(); ctx->eng.require_tile_size();
+		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*sizeof(terra_tile_stats), nb = (size_t)n*(S + 1)*(S + 1)*4, mb = (size_t)n*4;
 		uint8_t *d = (uint8_t *)be.alloc(zb + sb + nb + mb + 1024);
 		float *dz = (float *)d; terra_tile_stats *ds = (terra_tile_stats *)(d + zb); uint8_t *dn = d + zb + sb; float *dm = (float *)(d + zb + sb + nb);
 		try {
@@ -672,6 +677,11 @@ int terra_tiles_create_zvals(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 		} catch (...) {be.free(d); throw;}
 		be.free(d);
 	TERRA_CATCH
+}
+
+int terra_tile_size(terra_ctx *ctx, uint32_t *size) {
+	TERRA_CHECK_CTX if (!size) return terra::fail(TERRA_ERR_ARG, "null out");
+	TERRA_TRY ctx->eng.require_scene(); ctx->eng.require_tile_size(); *size = ctx->eng.tile_size(); TERRA_CATCH
 }
 
 int terra_selftest_hot_sqrt(terra_ctx *ctx, uint32_t stride, uint64_t *mismatches) {

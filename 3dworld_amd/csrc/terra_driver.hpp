@@ -134,7 +134,8 @@ TERRA_HD bool shadow_line_clip(shadow_pt_t &v1, shadow_pt_t &v2, float const d[3
 // OUT::shadow(x, y) sets the MESH_SHADOW bit; OUT::out_x / out_y(index, order, value) record an outgoing edge height -- `order` grows with the
 // sequential execution order (sweep, then step), the writer with the highest order must win.
 // IN::x(ix) / IN::y(iy): incoming edge heights (MESH_MIN_Z = none)
-template<class IN, class OUT> TERRA_HD void shadow_trace_path(shadow_consts_t const &c, float const *mh, IN const &in, unsigned p, OUT &out) {
+// OSTRIDE: orders per sweep, more than the longest sweep's steps (1024 for tiles of 130 cells; the tiles of other sizes take 4096: up to 1026 cells, 4 x 1026 sweeps < 2^31 / 4096)
+template<uint32_t OSTRIDE = 1024u, class IN, class OUT> TERRA_HD void shadow_trace_path(shadow_consts_t const &c, float const *mh, IN const &in, unsigned p, OUT &out) {
 	shadow_pt_t v1;
 	if (p < 2u*(unsigned)c.ysize) {v1.x = c.xval((c.dirx > 0) ? 0 : c.xsize); v1.y = (float)((double)-c.Y_SCENE_SIZE + 0.5*(double)c.DY_VAL*(double)(int)p); v1.z = 0.0f;}
 	else {int const xx = (int)(p - 2u*(unsigned)c.ysize); v1.x = (float)((double)-c.X_SCENE_SIZE + 0.5*(double)c.DX_VAL*(double)xx); v1.y = c.yval((c.diry > 0) ? 0 : c.ysize); v1.z = 0.0f;}
@@ -168,7 +169,7 @@ template<class IN, class OUT> TERRA_HD void shadow_trace_path(shadow_consts_t co
 			float const shadow_z = (float)((double)(pt_d - cur_d)*dir_ratio + (double)cur_z);
 			if (inited && shadow_z > pt_z) {
 				out.shadow(x, y);
-				uint32_t const order = p*1024u + (uint32_t)i + 1u; // sweeps are at most ~2*130 steps long
+				uint32_t const order = p*OSTRIDE + (uint32_t)i + 1u; // sweeps are at most ~2*130 steps long at 130 cells
 				if (x == xb) {out.out_y(y, order, shadow_z);}
 				if (y == yb) {out.out_x(x, order, shadow_z);}
 			}
@@ -330,6 +331,11 @@ TERRA_HD void tile_normal_v(float zc, float zr, float zd, float dxv, float dyv, 
 }
 TERRA_HD void tile_normal(float const *z, unsigned x, unsigned y, float dxv, float dyv, float dxy, float nv[3]) {
 	unsigned const zv = 130, ix2 = y*zv + x;
+	tile_normal_v(z[ix2], z[ix2 + 1], z[ix2 + zv], dxv, dyv, dxy, nv);
+}
+// ... for tiles of zv = S + 2 cells a side
+TERRA_HD void tile_normal_zv(float const *z, unsigned zv, unsigned x, unsigned y, float dxv, float dyv, float dxy, float nv[3]) {
+	unsigned const ix2 = y*zv + x;
 	tile_normal_v(z[ix2], z[ix2 + 1], z[ix2 + zv], dxv, dyv, dxy, nv);
 }
 
@@ -1423,6 +1429,19 @@ template<class BE> struct terra_engine {
 	}
 
 	// ================================================================ tiles (a10, a13, K6, K7)
+	// The tile size S is get_tile_size() = MESH_X_SIZE (src/tiled_mesh.cpp:142): a tile (tx, ty) starts at cell (tx*S, ty*S) and owns (S + 2)^2 zvals, (S + 1)^2 normals /
+	// AO texels and an (S + 73)^2 AO context.  S = 128 takes the tuned kernels of the backend; every other size takes the backend's *_sized methods.
+	uint32_t tile_size() const {return (uint32_t)cfg.mesh_x;}
+	void require_tile_size() const {
+		int const S = cfg.mesh_x;
+		if (S == 128) return;
+		if (S < 16 || S > 1024) throw std::invalid_argument("tiles: the tile size (mesh_x) must be 16 .. 1024");
+		if (cfg.mesh_y != S) throw std::invalid_argument("tiles: at a tile size other than 128 mesh_x and mesh_y must be equal (the reference asserts it in tiled mode)");
+		if ((S & 3) == 2) throw std::invalid_argument("tiles: a tile size of the form 4k + 2 is not supported (the reference's sub-block loop would read row and column S + 2, past the zvals)");
+	}
+	void require_tile_128(char const *what) const { // the entry points that have no size-general form yet
+		if (cfg.mesh_x != 128) throw std::invalid_argument(std::string(what) + ": only at the tile size 128 (mesh_x = 128)");
+	}
 	// One height field of tw x tw cells per tile, origin (tile*128 - shift) cells: setup_height_gen_async(height_gen, x1 - shift, y1 - shift, tw, tw)
 	// + the eval_index loop (src/tiled_mesh.cpp:458-464,480-488,494-505).  tw = 130, shift = 0: the tile's zvals; tw = 201, shift = 36: its AO context.
 	// Returns the device copy of the tile references (valid until the next tile call of this context).
@@ -1430,7 +1449,7 @@ template<class BE> struct terra_engine {
 		bool glac = true, bool force_sine = false, int min_start_sin = 0, // enable_glaciate() after build_arrays; build_arrays' force_sine_mode; eval_index's min_start_sin
 		tile_band_t const *band = nullptr, bool *band_used = nullptr)         // band: only these cells of every tile's field, if the backend can (*band_used); else the whole fields
 	{
-		uint32_t const size = 128, zv = tw;
+		uint32_t const size = tile_size(), zv = tw;
 		if (band_used) {*band_used = false;}
 		float const fdx = xy_scale*DX_VAL, fdy = xy_scale*DY_VAL; // setup_height_gen_async: build_arrays(..., xy_scale*DX_VAL, xy_scale*DY_VAL, ...)
 		// a tile's X table depends only on its tile x, its Y table only on its tile y: build each distinct one once
@@ -1513,6 +1532,7 @@ template<class BE> struct terra_engine {
 	}
 
 	static constexpr uint32_t AO_DIRS = 8, AO_STEPS = 8, AO_RAY_LEN = AO_STEPS*(AO_STEPS + 1)/2, AO_CTX = 129 + 2*AO_RAY_LEN; // src/tiled_mesh.cpp:41-43: 36, 201
+	uint32_t ao_ctx_size() const {return tile_size() + 1 + 2*AO_RAY_LEN;} // context_sz = stride + 2*AO_RAY_LEN: AO_CTX at S = 128
 	// enable_tiled_mesh_ao with the GL noise modes: create_zvals clips the zvals from the AO context grid (src/tiled_mesh.cpp:478-488,505)
 	bool ao_context_zvals() const {return tiled_mesh_ao && mode >= MGEN_SIMPLEX_GPU;}
 
@@ -1531,10 +1551,11 @@ template<class BE> struct terra_engine {
 		bool const add_detail = using_hmap_with_detail();
 		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, tw, shift, d_out, add_detail ? 16.0f : 0.0f); // HMAP_DETAIL_SCALE (src/heightmap.h:8)
 		hmap_view_t const hv = hmap_view();
+		int const S = (int)tile_size();
 		be.launch((size_t)n*tw*tw, [=] TERRA_LAMBDA (size_t i) {
 			unsigned const t = (unsigned)(i / ((size_t)tw*tw)), p = (unsigned)(i % ((size_t)tw*tw)), y = p / tw, x = p % tw;
 			tile_ref_pod_t const r = d_refs[t];
-			float zval = hv.clamped_height(r.tx*128 - shift + (int)x, r.ty*128 - shift + (int)y);
+			float zval = hv.clamped_height(r.tx*S - shift + (int)x, r.ty*S - shift + (int)y);
 			if (add_detail) {zval += 0.01f*d_out[i];} // HMAP_DETAIL_MAG (src/heightmap.h:9)
 			d_out[i] = zval;
 		});
@@ -1543,14 +1564,15 @@ template<class BE> struct terra_engine {
 
 	void tiles_create_zvals_dev(int32_t const *tile_xy, uint32_t n, uint32_t iters_tt, float *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz) {
 		require_scene();
+		require_tile_size();
 		if (n == 0) return;
-		uint32_t const size = 128, zv = 130;
+		uint32_t const size = tile_size(), zv = size + 2;
 		tile_ref_pod_t const *d_refs;
 		if (using_hmap()) {d_refs = tile_hmap_fields_dev(tile_xy, n, zv, 0, d_zvals); iters_tt = 0;} // "heightmap is eroded during load" (src/tiled_mesh.cpp:515)
 		else if (ao_context_zvals()) {
-			float *d_ctx = scratch<float>(s_ao, (size_t)n*AO_CTX*AO_CTX);
-			d_refs = tile_fields_dev(tile_xy, n, AO_CTX, (int)AO_RAY_LEN, d_ctx);
-			uint32_t const cs = AO_CTX, rl = AO_RAY_LEN;
+			uint32_t const cs = ao_ctx_size(), rl = AO_RAY_LEN;
+			float *d_ctx = scratch<float>(s_ao, (size_t)n*cs*cs);
+			d_refs = tile_fields_dev(tile_xy, n, cs, (int)AO_RAY_LEN, d_ctx);
 			be.launch((size_t)n*zv*zv, [=] TERRA_LAMBDA (size_t i) {
 				unsigned const t = (unsigned)(i / (zv*zv)), p = (unsigned)(i % (zv*zv)), y = p / zv, x = p % zv;
 				d_zvals[i] = d_ctx[(size_t)t*cs*cs + (size_t)(y + rl)*cs + (x + rl)];
@@ -1558,7 +1580,7 @@ template<class BE> struct terra_engine {
 		}
 		else {d_refs = tile_fields_dev(tile_xy, n, zv, 0, d_zvals);}
 		float const dxv = DX_VAL, dyv = DY_VAL;
-		// erosion: every tile alone on its clamp-padded 138x138 copy, droplets in order (src/tiled_mesh.cpp:515)
+		// erosion: every tile alone on its clamp-padded (zv + 8)^2 copy, droplets in order (src/tiled_mesh.cpp:515); tile_erosion takes its sizes from ec
 		if (iters_tt > 0 && erode_amount > 0.0f) {
 			check_erosion_iters(iters_tt);
 			erosion_consts_t const ec = make_erosion_consts((int)zv, (int)zv, zmin);
@@ -1568,17 +1590,22 @@ template<class BE> struct terra_engine {
 		if (d_stats || d_normals) {
 			float const wpz_max = get_max_sea_level();
 			float const rad_c = (dxv*dxv + dyv*dyv)*size*size;
-			be.tile_post(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxdy);
+			if (size == 128) {be.tile_post(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxdy);}
+			else {be.tile_post_sized(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxdy, size);}
 		}
 	}
 
 	// the post pass alone over the caller's zvals (terra_tiles_post_dev)
 	void tiles_post_dev(int32_t const *tile_xy, uint32_t n, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz) {
 		require_scene();
+		require_tile_size();
 		if (n == 0 || !(d_stats || d_normals)) return;
-		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, 130, 0, nullptr, 0.0f); // (only the tile references)
-		float const dxv = DX_VAL, dyv = DY_VAL, rad_c = (dxv*dxv + dyv*dyv)*128*128;
-		be.tile_post(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, get_max_sea_level(), rad_c, dxv, dyv, dxdy);
+		uint32_t const size = tile_size();
+		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, size + 2, 0, nullptr, 0.0f); // (only the tile references)
+		float const dxv = DX_VAL, dyv = DY_VAL;
+		if (size == 128) {float const rad_c = (dxv*dxv + dyv*dyv)*128*128; be.tile_post(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, get_max_sea_level(), rad_c, dxv, dyv, dxdy); return;}
+		float const rad_c = (dxv*dxv + dyv*dyv)*size*size;
+		be.tile_post_sized(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, get_max_sea_level(), rad_c, dxv, dyv, dxdy, size);
 	}
 
 	// tile_t::calc_shadows_for_light + calc_mesh_shadows (src/tiled_mesh.cpp:664-692, src/visibility.cpp:510-520) for a batch and one directional light:
@@ -1593,8 +1620,10 @@ template<class BE> struct terra_engine {
 		float const *edge_in = nullptr, uint8_t const *edge_in_present = nullptr, float *edge_out = nullptr, float const *d_edge_in = nullptr, float *d_edge_out = nullptr)
 	{
 		require_scene();
+		require_tile_size();
+		if (tile_size() != 128 && (edge_in || edge_in_present || edge_out || d_edge_in || d_edge_out)) require_tile_128("tiles_mesh_shadows with halo edges");
 		if (n == 0) return;
-		uint32_t const zv = 130;
+		uint32_t const size = tile_size(), zv = size + 2;
 		if (edge_in && d_edge_in) throw std::invalid_argument("tiles_mesh_shadows: incoming edges either on the host or on the device");
 		if (edge_out) {for (size_t i = 0; i < (size_t)n*2*zv; ++i) edge_out[i] = -1.0E6f;} // sh_out[l][d].resize(zvsize, MESH_MIN_Z)
 		if (d_edge_out) {float *eo = d_edge_out; be.launch((size_t)n*2*zv, [=] TERRA_LAMBDA (size_t i) {eo[i] = -1.0E6f;});}
@@ -1695,11 +1724,12 @@ template<class BE> struct terra_engine {
 		}
 		uint32_t const npaths = 4*zv;
 		uint32_t *d_sync = (uint32_t *)((uint8_t *)d_out + (((size_t)2*nslots*zv*8 + 255) & ~(size_t)255)); // the ticket counter of the dataflow launch
-		if (be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync)) {} // one launch; tiles start as their two upstream tiles publish
-		else for (uint32_t first = 0; first < n;) { // "shadows.levels" / cross-check kernels / the emulator: one launch per dependency level
+		if (size == 128 && be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync)) {} // one launch; tiles start as their two upstream tiles publish
+		else for (uint32_t first = 0; first < n;) { // "shadows.levels" / cross-check kernels / the emulator / other tile sizes: one launch per dependency level
 			uint32_t last = first;
 			while (last < n && level[order[last]] == level[order[first]]) ++last;
-			be.tile_shadows(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);
+			if (size == 128) {be.tile_shadows(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);}
+			else {be.tile_shadows_sized(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);}
 			first = last;
 		}
 		if (d_edge_out) { // the tiles' own outgoing edges, decoded on the device
@@ -1729,8 +1759,9 @@ template<class BE> struct terra_engine {
 	// enable_tiled_mesh_ao and a GL noise mode it is the context grid everywhere (ao_zvals kept by create_zvals).
 	void tiles_ao_lighting_dev(int32_t const *tile_xy, uint32_t n, float const *d_zvals, uint8_t *d_ao) {
 		require_scene();
+		require_tile_size();
 		if (n == 0) return;
-		uint32_t const zv = 130, cs = AO_CTX, rl = AO_RAY_LEN;
+		uint32_t const size = tile_size(), zv = size + 2, cs = ao_ctx_size(), rl = AO_RAY_LEN;
 		float *d_ctx = scratch<float>(s_ao, (size_t)n*cs*cs);
 		// inside the tile the context is the tile's own zvals (src/tiled_mesh.cpp:622): the kernel takes those cells from d_zvals while it stages the context (a copy pass
 		// into d_ctx first was 168 us for 4096 tiles)
@@ -1741,11 +1772,12 @@ template<class BE> struct terra_engine {
 			// (a cell's value does not depend on its neighbours: the same bits), as two launches: the rows above and below the tile, then the columns beside it
 			tile_band_t const rows_band = {cs, cs - zv, cs, 0xFFFFFFFFu, 0u, rl, zv}, cols_band = {cs - zv, zv, cs, rl, zv, 0u, rl};
 			bool banded = false;
-			tile_fields_dev(tile_xy, n, cs, (int)rl, d_ctx, 1.0f, true, false, 0, (own && opt.ao_bands) ? &rows_band : nullptr, &banded);
+			tile_fields_dev(tile_xy, n, cs, (int)rl, d_ctx, 1.0f, true, false, 0, (own && opt.ao_bands && size == 128) ? &rows_band : nullptr, &banded);
 			if (banded) {tile_fields_dev(tile_xy, n, cs, (int)rl, d_ctx, 1.0f, true, false, 0, &cols_band, &banded);}
 		}
 		float const dz = (float)(0.5*(double)HALF_DXY);
-		be.tile_ao(n, d_zvals, d_ctx, d_ao, dz, own);
+		if (size == 128) {be.tile_ao(n, d_zvals, d_ctx, d_ao, dz, own);}
+		else {be.tile_ao_sized(n, d_zvals, d_ctx, d_ao, dz, own, size);}
 	}
 
 	// ================================================================ height edits of the heightmap texture and the map exporter (rest of f4)
@@ -1883,6 +1915,7 @@ template<class BE> struct terra_engine {
 	}
 	void tiles_terrain_params(int32_t const *tile_xy, uint32_t n, float *h_params) {
 		require_scene();
+		require_tile_128("tiles_terrain_params");
 		if (n == 0) return;
 		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, WT_TEX, 0, nullptr, 0.0f);
 		float *d_params = scratch<float>(s_ao, (size_t)n*12);
@@ -1909,6 +1942,7 @@ template<class BE> struct terra_engine {
 	// d_weights n x 129x129 RGBA8, d_blocks n x 32x32 grass blocks (or null), d_has_grass n bytes (or null)
 	void tiles_create_weights_dev(int32_t const *tile_xy, uint32_t n, float const *d_zvals, uint8_t *d_weights, grass_block_pod_t *d_blocks, uint8_t *d_has_grass) {
 		require_scene();
+		require_tile_128("tiles_create_weights");
 		if (n == 0) return;
 		uint32_t const ts = WT_TEX, zv = WT_ZV;
 		size_t const ntex = (size_t)n*ts*ts;

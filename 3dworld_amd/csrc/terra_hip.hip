@@ -448,6 +448,24 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		hipLaunchKernelGGL(terra::k_tile_post_final, dim3((n + 255)/256), dim3(256), 0, stream, refs, n, st, mnz, tile_acc, rad_c, dxy, nm ? 1 : 0);
 		TERRA_HIP_CHECK(hipGetLastError());
 	}
+	// the post pass at a tile size other than 128 (terra_kernels.hpp: k_tile_post_sized); the same preconditions as tile_post's kernel
+	void tile_post_sized(uint32_t n, terra::tile_ref_pod_t const *refs, float const *z, terra_tile_stats *st, uint8_t *nm, float *mnz, float wpz, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {
+		float const c2 = dxy*dxy;
+		bool const normalized = !(sqrtf(c2) < 1.0E-12f) && dxy > 0.0f;
+		if (simple_kernels || ((uintptr_t)nm & 3) || !normalized || (uint64_t)n*4 > 0x7FFFFFFFull) {simple_paths::tile_post_sized(n, refs, z, st, nm, mnz, wpz, rad_c, dxv, dyv, dxy, S); return;}
+		use();
+		uint32_t flat_word;
+		{
+			float nv[3]; terra::tile_normal_v(0.0f, 0.0f, 0.0f, dxv, dyv, dxy, nv);
+			flat_word = (uint32_t)(uint8_t)(127.0*((double)nv[0] + 1.0)) | ((uint32_t)(uint8_t)(127.0*((double)nv[1] + 1.0)) << 8) | ((uint32_t)(uint8_t)(127.0*((double)nv[2] + 1.0)) << 16);
+		}
+		size_t const bytes = (size_t)n*terra::TP_ACC*sizeof(uint32_t);
+		if (bytes > tile_acc_bytes) {if (tile_acc) {sync(); (void)hipFree(tile_acc);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_acc, bytes)); tile_acc_bytes = bytes;}
+		hipLaunchKernelGGL(terra::k_tile_post_init, dim3((n*terra::TP_ACC + 255)/256), dim3(256), 0, stream, tile_acc, n);
+		hipLaunchKernelGGL(terra::k_tile_post_sized, dim3(n*4), dim3(terra::TPS_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word, S);
+		hipLaunchKernelGGL(terra::k_tile_post_final_sized, dim3((n + 255)/256), dim3(256), 0, stream, refs, n, st, mnz, tile_acc, rad_c, dxy, nm ? 1 : 0, S);
+		TERRA_HIP_CHECK(hipGetLastError());
+	}
 	void tile_erosion(uint32_t n, float *zvals, terra::erosion_consts_t const &ec, uint32_t iters) {
 		use();
 		size_t const lds = (size_t)ec.NX*ec.NY*sizeof(float);

@@ -598,6 +598,104 @@ __global__ __launch_bounds__(256) void k_tile_post_final(tile_ref_pod_t const *_
 	}
 }
 
+// ---- the post pass at a tile size S other than 128 (zv = S + 2, stride = S + 1, block_size bs = zv/4): one block per (tile, sub-block row yy).  The block owns the
+// stats rows [yy*bs, (yy + 1)*bs] (the shared row (yy + 1)*bs counts in both bands, as in the reference) and the texel rows [yy*bs, (yy + 1)*bs) -- the last band
+// through row S.  A wave walks every TPS_WAVES-th row, a lane every 64th column; the rows are read through the caches (no LDS staging: a band of a 1024-cell tile
+// is 1 MB).  The texel words are tp_word_fast / tp_word_exact's, by the same wave-uniform decision as k_tile_post; the tile's totals go through the same per-tile
+// accumulators to k_tile_post_final_sized.
+constexpr unsigned TPS_THREADS = 512, TPS_WAVES = TPS_THREADS/64;
+__global__ __launch_bounds__(TPS_THREADS) void k_tile_post_sized(tile_ref_pod_t const *__restrict__ refs, float const *__restrict__ zvals, terra_tile_stats *__restrict__ stats,
+	uint8_t *__restrict__ normals, uint32_t *__restrict__ acc, float wpz_max, float dxv, float dyv, float dxy, float c2, uint32_t flat_word, unsigned S)
+{
+	__shared__ uint32_t s_lo[4], s_hi[4], s_smax;
+	__shared__ int s_bb[4];
+	unsigned const t = blockIdx.x >> 2, yy = blockIdx.x & 3u, tid = threadIdx.x, zv = S + 2, stride = S + 1, bs = zv/4, lim = 4*bs;
+	unsigned const srow0 = yy*bs, srow1 = (yy + 1)*bs;              // stats rows [srow0, srow1]
+	unsigned const nrow0 = yy*bs, nrow1 = (yy == 3) ? stride : srow1; // texel rows [nrow0, nrow1)
+	unsigned const rowN = (srow1 + 1 > nrow1) ? srow1 + 1 : nrow1;    // rows this band visits: [srow0, rowN)
+	tile_ref_pod_t const r = refs[t];
+	int const x1 = r.tx*(int)S, y1 = r.ty*(int)S;
+	if (tid < 4) {s_lo[tid] = f2ord(100.0f); s_hi[tid] = ~f2ord(-100.0f);} // folds start at szmin = FAR_DISTANCE, szmax = -FAR_DISTANCE
+	if (tid == 0) {s_smax = 0u; s_bb[0] = x1 + (int)S; s_bb[1] = y1 + (int)S; s_bb[2] = x1; s_bb[3] = y1;} // water bbox starts denormalized
+	__syncthreads();
+	unsigned const w = (unsigned)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+	float const *z = zvals + (size_t)t*zv*zv;
+	uint32_t *nout = normals ? (uint32_t *)(normals + (size_t)t*stride*stride*4) : nullptr;
+	bool const want_stats = stats != nullptr;
+	uint32_t lo[4] = {f2ord(100.0f), f2ord(100.0f), f2ord(100.0f), f2ord(100.0f)}, hi[4] = {~f2ord(-100.0f), ~f2ord(-100.0f), ~f2ord(-100.0f), ~f2ord(-100.0f)};
+	int wx0 = 0x7FFFFFFF, wx1 = -1, wy0 = 0x7FFFFFFF, wy1 = -1;
+	float smax = 0.0f;
+	for (unsigned y = srow0 + w; y < rowN; y += TPS_WAVES) { // (wave-uniform)
+		float const *row = z + (size_t)y*zv;
+		bool const srow = y <= srow1, nrow = nout && y >= nrow0 && y < nrow1;
+		for (unsigned x0 = 0; x0 < zv; x0 += 64) {
+			unsigned const x = x0 + lane;
+			bool const in = x < zv;
+			float const zc = row[in ? x : 0u];
+			if (want_stats && srow) {
+				if (in && x <= lim && zc == zc) { // sub-block xx covers columns [xx*bs, (xx + 1)*bs]: a column on a block border counts on both sides; a NaN never wins
+					uint32_t const o = f2ord(zc);
+#pragma unroll
+					for (unsigned k = 0; k < 4; ++k) {
+						if (x >= k*bs && x <= k*bs + bs) {lo[k] = (o < lo[k]) ? o : lo[k]; hi[k] = (~o < hi[k]) ? ~o : hi[k];}
+					}
+				}
+				if (in && x <= lim && zc < wpz_max) {wx0 = (wx0 < (int)x) ? wx0 : (int)x; wx1 = (wx1 > (int)x) ? wx1 : (int)x; wy0 = (wy0 < (int)y) ? wy0 : (int)y; wy1 = (int)y;}
+			}
+			if (nrow && x0 < stride) { // (wave-uniform)
+				bool const tx = x < stride;
+				float const zr = row[tx ? x + 1 : 0u], zd = row[(tx ? x : 0u) + zv];
+				uint32_t wd; float sv;
+				bool const ok = tp_word_fast(zc, zr, zd, dxv, dyv, dxy, c2, flat_word, wd, sv);
+				if (__builtin_amdgcn_ballot_w64(tx && !ok) != 0) {wd = tp_word_exact(zc, zr, zd, dxv, dyv, dxy);}
+				if (tx) {__builtin_nontemporal_store(wd, &nout[(size_t)y*stride + x]); smax = __builtin_fmaxf(smax, sv);}
+			}
+		}
+	}
+	if (want_stats) {
+#pragma unroll
+		for (unsigned k = 0; k < 4; ++k) {uint32_t const a = wave_min_u32(lo[k]), b = wave_min_u32(hi[k]); if (lane == 0) {atomicMin(&s_lo[k], a); atomicMin(&s_hi[k], b);}}
+		int const ax0 = wave_min_i32(wx0), ay0 = wave_min_i32(wy0), ax1 = -wave_min_i32(-wx1), ay1 = -wave_min_i32(-wy1);
+		if (lane == 0 && ax1 >= 0) {atomicMin(&s_bb[0], x1 + ax0); atomicMin(&s_bb[1], y1 + ay0); atomicMax(&s_bb[2], x1 + ax1); atomicMax(&s_bb[3], y1 + ay1);}
+	}
+	if (nout) { // s >= 0: positive floats order like their bit patterns
+		uint32_t u; memcpy(&u, &smax, 4);
+#pragma unroll
+		for (int off = 32; off > 0; off >>= 1) {uint32_t const o = __shfl_xor(u, off, 64); u = (o > u) ? o : u;}
+		if (lane == 0) {atomicMax(&s_smax, u);}
+	}
+	__syncthreads();
+	if (tid == 0) {
+		uint32_t *a = acc + (size_t)t*TP_ACC;
+		if (want_stats) {
+			for (int k = 0; k < 4; ++k) {stats[t].sub_zmin[yy*4 + k] = ord2f(s_lo[k]); stats[t].sub_zmax[yy*4 + k] = ord2f(~s_hi[k]);}
+			atomicMin((int *)&a[2], s_bb[0]); atomicMin((int *)&a[3], s_bb[1]); atomicMax((int *)&a[4], s_bb[2]); atomicMax((int *)&a[5], s_bb[3]);
+		}
+		if (nout) {atomicMax(&a[6], s_smax);}
+	}
+}
+__global__ __launch_bounds__(256) void k_tile_post_final_sized(tile_ref_pod_t const *__restrict__ refs, uint32_t n, terra_tile_stats *__restrict__ stats, float *__restrict__ min_nz, uint32_t const *__restrict__ acc,
+	float rad_c, float dxy, int have_normals, unsigned S)
+{
+	uint32_t const t = blockIdx.x*blockDim.x + threadIdx.x;
+	if (t >= n) return;
+	uint32_t const *a = acc + (size_t)t*TP_ACC;
+	if (stats) {
+		tile_ref_pod_t const r = refs[t];
+		int const x1 = r.tx*(int)S, y1 = r.ty*(int)S;
+		float mzmin = 100.0f, mzmax = -100.0f;
+		for (int k = 0; k < 16; ++k) {mzmin = min_std(mzmin, stats[t].sub_zmin[k]); mzmax = max_std(mzmax, stats[t].sub_zmax[k]);}
+		stats[t].mzmin = mzmin; stats[t].mzmax = mzmax;
+		stats[t].radius = (float)(0.5*sqrt((double)(rad_c + (mzmax - mzmin)*(mzmax - mzmin))));
+		stats[t].wx1 = imin((int)a[2], x1 + (int)S); stats[t].wy1 = imin((int)a[3], y1 + (int)S); stats[t].wx2 = imax((int)a[4], x1); stats[t].wy2 = imax((int)a[5], y1);
+	}
+	if (min_nz && have_normals) {
+		float smax; uint32_t const u = a[6]; memcpy(&smax, &u, 4);
+		float const nz = dxy/sqrtf(smax);
+		min_nz[t] = (nz < 1.0f) ? nz : 1.0f;
+	}
+}
+
 // ------------------------------------------------------------------ row f1: tile AO lighting (tile_t::calc_mesh_ao_lighting, src/tiled_mesh.cpp:634-659)
 // One block = one band of AO_BAND texel rows of one tile (33: four bands cover the 129 rows; with 32 a fifth block staged 74 context rows for one texel row).  The context rows the rays of the band can reach are staged in LDS in two passes:
 // rays going up or sideways need context rows [y0, y0 + band + 35], rays going down rows [y0 + 36, y0 + band + 71] (context coordinates =

@@ -290,8 +290,9 @@ int terra_multi_tiles_create_zvals(terra_multi *m, const int32_t *tile_xy, uint3
 	return terra::multi_run(m, [&](uint32_t i) {
 		uint32_t first, cnt; terra::multi_block(n, P, i, first, cnt);
 		if (cnt == 0) return;
-		int const rc = terra_tiles_create_zvals(m->ctxs[i], tile_xy + 2*(size_t)first, cnt, iters_tt, h_zvals + (size_t)first*130*130, h_stats ? h_stats + first : nullptr,
-			h_normals ? h_normals + (size_t)first*129*129*4 : nullptr, (h_normals && h_min_nz) ? h_min_nz + first : nullptr);
+		size_t const S = m->ctxs[i]->eng.tile_size(); // (every context has the same scene)
+		int const rc = terra_tiles_create_zvals(m->ctxs[i], tile_xy + 2*(size_t)first, cnt, iters_tt, h_zvals + (size_t)first*(S + 2)*(S + 2), h_stats ? h_stats + first : nullptr,
+			h_normals ? h_normals + (size_t)first*(S + 1)*(S + 1)*4 : nullptr, (h_normals && h_min_nz) ? h_min_nz + first : nullptr);
 		if (rc != TERRA_OK) throw std::runtime_error(terra_last_error());
 	});
 }
@@ -334,8 +335,14 @@ int terra_multi_voxel_fill_dev(terra_multi *m, float *const *d_out, uint32_t nx,
 		m->ctxs[i]->eng.voxel_fill_dev(d_out[i], nx, ny, nz, lo, vsz, off, mag, freq, rs1, rs2, gen_mode, zscale, normalize, first, cnt);
 	});
 }
+// the multi-context mesh shadows hand 130-float edges between strips: only at the tile size 128 for now
+static int multi_tile_128(terra_multi *m, char const *what) {
+	for (terra_ctx *c : m->ctxs) {if (c->eng.scene_ready && c->eng.tile_size() != 128) return terra::fail(TERRA_ERR_ARG, (std::string(what) + ": only at the tile size 128 (mesh_x = 128)").c_str());}
+	return TERRA_OK;
+}
 int terra_multi_shadow_layout(terra_multi *m, const int32_t *tile_xy, uint32_t n, const float light_pos[3], uint32_t *ctx_of_tile, uint32_t *pos_in_ctx, uint32_t *tiles_per_ctx) {
 	TERRA_CHECK_MULTI if (n && (!tile_xy || !light_pos)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	if (multi_tile_128(m, "terra_multi_shadow_layout") != TERRA_OK) return TERRA_ERR_ARG;
 	try {
 		terra::shadow_layout_t L;
 		if (!terra::shadow_layout((uint32_t)m->ctxs.size(), tile_xy, n, light_pos, L)) return terra::fail(TERRA_ERR_ARG, "terra_multi_shadow_layout: a tile is named twice");
@@ -346,6 +353,7 @@ int terra_multi_shadow_layout(terra_multi *m, const int32_t *tile_xy, uint32_t n
 }
 int terra_multi_tiles_mesh_shadows_dev(terra_multi *m, const int32_t *tile_xy, uint32_t n, float *const *d_zvals, const float light_pos[3], uint8_t *const *d_smask) {
 	TERRA_CHECK_MULTI if (n && (!tile_xy || !d_zvals || !d_smask || !light_pos)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	if (multi_tile_128(m, "terra_multi_tiles_mesh_shadows_dev") != TERRA_OK) return TERRA_ERR_ARG;
 	try {
 		terra::shadow_layout_t L;
 		if (!terra::shadow_layout((uint32_t)m->ctxs.size(), tile_xy, n, light_pos, L)) return terra::fail(TERRA_ERR_ARG, "terra_multi_tiles_mesh_shadows_dev: a tile is named twice");
@@ -355,6 +363,7 @@ int terra_multi_tiles_mesh_shadows_dev(terra_multi *m, const int32_t *tile_xy, u
 }
 int terra_multi_tiles_mesh_shadows(terra_multi *m, const int32_t *tile_xy, uint32_t n, const float *h_zvals, const float light_pos[3], uint8_t *h_smask) {
 	TERRA_CHECK_MULTI if (n && (!tile_xy || !h_zvals || !h_smask || !light_pos)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	if (multi_tile_128(m, "terra_multi_tiles_mesh_shadows") != TERRA_OK) return TERRA_ERR_ARG;
 	try {return terra::multi_tiles_mesh_shadows(m, tile_xy, n, h_zvals, light_pos, h_smask);}
 	catch (std::exception const &e) {return terra::fail(TERRA_ERR_HIP, e.what());}
 }

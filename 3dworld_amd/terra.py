@@ -190,6 +190,7 @@ _PROTOS = {
     "terra_tiles_post_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_post": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_create_zvals": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "terra_tile_size": (_i32, [_vp, C.POINTER(_u32)]),
     "terra_selftest_hot_sqrt": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64)]),
     "terra_voxel_fill_dev": (_i32, [_vp, _vp, _u32, _u32, _u32, _f3, _f3, _f3, _f, _f, _i32, _i32, _i32, _f, _i32]),
     "terra_voxel_fill_slab_dev": (_i32, [_vp, _vp, _u32, _u32, _u32, _f3, _f3, _f3, _f, _f, _i32, _i32, _i32, _f, _i32, _u32, _u32]),
@@ -415,12 +416,20 @@ class Terra:
         self._ck(self.lib.terra_get_erosion_report(self.ctx, C.byref(r)))
         return r
 
+    @property
+    def tile_size(self):
+        """S = the scene's mesh_x (get_tile_size): tiles hold (S+2)^2 zvals, (S+1)^2 normals / AO texels (include/terra.h)"""
+        s = _u32()
+        self._ck(self.lib.terra_tile_size(self.ctx, C.byref(s)))
+        return s.value
+
     def tiles_create_zvals(self, tile_xy, iters_tt=0, stats=True, normals=True):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
-        z = np.empty((n, 130, 130), np.float32)
+        S = self.tile_size
+        z = np.empty((n, S + 2, S + 2), np.float32)
         st = (TileStats * n)() if stats else None
-        nm = np.empty((n, 129, 129, 4), np.uint8) if normals else None
+        nm = np.empty((n, S + 1, S + 1, 4), np.uint8) if normals else None
         mnz = np.empty(n, np.float32) if normals else None
         self._ck(self.lib.terra_tiles_create_zvals(self.ctx, txy.ctypes.data, n, iters_tt, z.ctypes.data,
                                                     C.addressof(st) if stats else None, nm.ctypes.data if normals else None,
@@ -466,8 +475,9 @@ class Terra:
     def tiles_mesh_shadows(self, tile_xy, zvals, light_pos):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
-        z = np.ascontiguousarray(zvals, np.float32).reshape(n, 130, 130)
-        sm = np.empty((n, 130, 130), np.uint8)
+        zv = self.tile_size + 2
+        z = np.ascontiguousarray(zvals, np.float32).reshape(n, zv, zv)
+        sm = np.empty((n, zv, zv), np.uint8)
         lp = (C.c_float * 3)(*light_pos)
         self._ck(self.lib.terra_tiles_mesh_shadows(self.ctx, txy.ctypes.data, n, z.ctypes.data, lp, sm.ctypes.data))
         return sm
@@ -573,8 +583,9 @@ class Terra:
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
-        z = np.ascontiguousarray(zvals, np.float32).reshape(n, 130, 130)
-        ao = np.empty((n, 129, 129), np.uint8)
+        S = self.tile_size
+        z = np.ascontiguousarray(zvals, np.float32).reshape(n, S + 2, S + 2)
+        ao = np.empty((n, S + 1, S + 1), np.uint8)
         self._ck(self.lib.terra_tiles_ao_lighting(self.ctx, txy.ctypes.data, n, z.ctypes.data, ao.ctypes.data))
         return ao
 
@@ -805,7 +816,10 @@ class TerraMulti:
     def tiles_create_zvals(self, tile_xy, iters_tt=0):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
-        z = np.empty((n, 130, 130), np.float32); st = (TileStats * n)(); nm = np.empty((n, 129, 129, 4), np.uint8); mnz = np.empty(n, np.float32)
+        s = _u32()
+        self._ck(self.lib.terra_tile_size(self.lib.terra_multi_ctx(self.m, 0), C.byref(s)))  # (every context has the same scene)
+        S = s.value
+        z = np.empty((n, S + 2, S + 2), np.float32); st = (TileStats * n)(); nm = np.empty((n, S + 1, S + 1, 4), np.uint8); mnz = np.empty(n, np.float32)
         self._ck(self.lib.terra_multi_tiles_create_zvals(self.m, txy.ctypes.data, n, iters_tt, z.ctypes.data, C.addressof(st), nm.ctypes.data, mnz.ctypes.data))
         return z, st, nm, mnz
 

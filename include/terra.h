@@ -334,9 +334,22 @@ int  terra_heightmap_postprocess_dev(terra_ctx *ctx, uint8_t *d_pixels, uint32_t
 int  terra_read_mesh(terra_ctx *ctx, const char *filename, float zmm, float *h_mesh, uint32_t nx, uint32_t ny, float *h_zbottom_ztop);
 int  terra_write_mesh(const char *filename, const float *h_mesh, uint32_t nx, uint32_t ny);
 
-/* ---- tiles: tile_t::create_zvals batch, size = 128 (zvsize 130, stride 129).
- * tile_xy: n pairs (tile x, tile y) on the HOST.  d_zvals: n*130*130 floats.  d_stats: n terra_tile_stats (optional).
- * d_normals: n*129*129*4 bytes RGBA8 with A = 0 (optional); d_min_normal_z: n floats (optional). */
+/* ---- tiles: tile_t::create_zvals batch.  The tile size S is get_tile_size() = MESH_X_SIZE = the scene's mesh_x (src/tiled_mesh.cpp:142); every tile buffer is
+ * sized from it (the numbers in brackets are S = 128, the size every call supports):
+ *   zvals  [n][S+2][S+2] floats         ([n][130][130])    tile (tx, ty) covers cells x1 = tx*S .. x1 + S + 1, y1 = ty*S .., field origin x1 - mesh_x/2, y1 - mesh_y/2
+ *   normals [n][S+1][S+1][4] bytes      ([n][129][129][4]) RGBA8, A = 0
+ *   AO     [n][S+1][S+1] bytes          ([n][129][129])    from an (S+73)^2 context at (x1 - 36, y1 - 36) (201^2)
+ *   smask  [n][S+2][S+2] bytes          ([n][130][130])
+ *   stats: 4 x 4 sub-blocks of block_size = (S+2)/4 cells (32), radius from (DX^2 + DY^2)*S*S.
+ * Supported: 16 <= S <= 1024; S other than 128 also needs mesh_x == mesh_y (the reference asserts it in tiled mode) and S != 4k + 2 (the reference's sub-block
+ * loop would read past the zvals there); otherwise every tile call is TERRA_ERR_ARG.  At S != 128 these entry points follow S: terra_tiles_create_zvals[_dev]
+ * (all three field sources: procedural, the AO-context clip, the heightmap texture), terra_tiles_post[_dev], terra_tiles_ao_lighting[_dev],
+ * terra_tiles_mesh_shadows[_dev] and terra_multi_tiles_create_zvals[_dev].  These are TERRA_ERR_ARG at S != 128 for now: terra_tiles_terrain_params,
+ * terra_tiles_create_weights[_dev], terra_tiles_mesh_shadows_halo_dev / _edges_dev, terra_multi_tiles_mesh_shadows[_dev] and terra_multi_shadow_layout.
+ * terra_tile_size: *size = S of the scene in force (TERRA_ERR_ARG when the scene's S is not supported, TERRA_ERR_STATE before terra_init_scene).
+ * tile_xy: n pairs (tile x, tile y) on the HOST.  d_zvals: n zvals.  d_stats: n terra_tile_stats (optional).
+ * d_normals: n normals (optional); d_min_normal_z: n floats (optional). */
+int  terra_tile_size(terra_ctx *ctx, uint32_t *size);
 int  terra_tiles_create_zvals_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, uint32_t erosion_iters_tt,
                                   float *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_normal_z);
 int  terra_tiles_create_zvals(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, uint32_t erosion_iters_tt,
@@ -391,9 +404,9 @@ int  terra_hmap_read_mod(const char *path, terra_hmap_mod *mods, uint32_t mods_c
 int  terra_export_heightmap_dev(terra_ctx *ctx, float xstart, float ystart, uint32_t width, uint32_t height, float *d_vals, uint8_t *d_pixels16, float *h_min_z_dz);
 int  terra_write_map_mode_heightmap_image(terra_ctx *ctx, const char *path, float xstart, float ystart, uint32_t width, uint32_t height);
 
-/* ---- tile ambient-occlusion lighting: tile_t::calc_mesh_ao_lighting (src/tiled_mesh.cpp:586-661).  zvals: [n][130][130] exactly as
- * terra_tiles_create_zvals left them (eroded or not); ao: [n][129][129] bytes = (unsigned char)(255*(1 - atten/64)).  The 201 x 201 context
- * around each tile is generated internally (setup_height_gen_async(x1 - 36, y1 - 36, 201, 201)).
+/* ---- tile ambient-occlusion lighting: tile_t::calc_mesh_ao_lighting (src/tiled_mesh.cpp:586-661).  zvals: [n][S+2][S+2] exactly as
+ * terra_tiles_create_zvals left them (eroded or not); ao: [n][S+1][S+1] bytes = (unsigned char)(255*(1 - atten/64)).  The (S+73)^2 context
+ * around each tile is generated internally (setup_height_gen_async(x1 - 36, y1 - 36, S+73, S+73); 201 at S = 128).
  * terra_set_tiled_mesh_ao = the config key enable_tiled_mesh_ao (src/3DWorld.cpp:1778; scene_config/config.txt turns it on): with mesh_gen_mode >= 3 the
  * reference clips a tile's zvals out of that context grid instead of a 130 x 130 grid of its own (src/tiled_mesh.cpp:478-488,505), which changes
  * their low bits; terra_tiles_create_zvals follows the flag. */
@@ -401,7 +414,7 @@ int  terra_set_tiled_mesh_ao(terra_ctx *ctx, int enable);
 int  terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao);
 int  terra_tiles_ao_lighting(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *h_zvals, uint8_t *h_ao);
 
-/* ---- landscape weights texture of a tile: tile_t::create_texture (src/tiled_mesh.cpp:1071-1240) with update_terrain_params (:321-343), get_tids /
+/* ---- landscape weights texture of a tile (tile size 128 only): tile_t::create_texture (src/tiled_mesh.cpp:1071-1240) with update_terrain_params (:321-343), get_tids /
  * update_lttex_ix (src/Textures.cpp:1289-1316) and add_grass_block_at (src/tiled_mesh.cpp:1354-1371).  Terrain-only branch: the city, tunnel and building
  * queries and the tree map come from subsystems outside this library (their texels are the caller's to overwrite afterwards, as the reference does).
  * zvals: [n][130][130]; weights: [n][129][129][4] bytes RGBA = {sand, dirt, grass, rock}, snow = remainder; grass_blocks: [n][32][32] or NULL;
@@ -414,7 +427,7 @@ int  terra_tiles_create_weights_dev(terra_ctx *ctx, const int32_t *tile_xy, uint
 int  terra_tiles_create_weights(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *h_zvals, uint8_t *h_weights, terra_grass_block *h_grass_blocks, uint8_t *h_has_any_grass);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
- * src/visibility.cpp:411-520).  zvals: [n][130][130]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][130][130] bytes, 0 or
+ * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or
  * MESH_SHADOW (0x02).  Shadows cross tile borders: a tile starts its sweeps from the edge heights left by its neighbours toward the light when those are
  * part of the batch (sh_out -> sh_in), otherwise from nothing, exactly like a tile whose neighbour does not exist.  Order of evaluation = the
  * reference's single-threaded order (its two OpenMP sections race). */

@@ -79,7 +79,8 @@ inline void heightmap_proc_gen(unsigned width, unsigned height, unsigned erosion
 	min_z = range[0]; dz = range[1];
 }
 
-// tile_t::create_zvals for a batch of tiles (src/tiled_mesh.cpp:467-546): zvals n*130*130, stats n, normals n*129*129*4 (optional)
+// tile_t::create_zvals for a batch of tiles (src/tiled_mesh.cpp:467-546) at the tile size S = MESH_X_SIZE (terra_tile_size): zvals n*(S+2)*(S+2), stats n,
+// normals n*(S+1)*(S+1)*4 (optional) -- 130 / 129 at S = 128
 // ---- eval_mesh_sin_terms (src/mesh_gen.cpp:797-805): point query, evaluated on the host
 inline float eval_mesh_sin_terms(float xv, float yv) {
 	float z = 0.0f;
