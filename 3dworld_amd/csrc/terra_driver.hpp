@@ -134,8 +134,8 @@ TERRA_HD bool shadow_line_clip(shadow_pt_t &v1, shadow_pt_t &v2, float const d[3
 // OUT::shadow(x, y) sets the MESH_SHADOW bit; OUT::out_x / out_y(index, order, value) record an outgoing edge height -- `order` grows with the
 // sequential execution order (sweep, then step), the writer with the highest order must win.
 // IN::x(ix) / IN::y(iy): incoming edge heights (MESH_MIN_Z = none)
-// OSTRIDE: orders per sweep, more than the longest sweep's steps (1024 for tiles of 130 cells; the tiles of other sizes take 4096: up to 1026 cells, 4 x 1026 sweeps < 2^31 / 4096)
-template<uint32_t OSTRIDE = 1024u, class IN, class OUT> TERRA_HD void shadow_trace_path(shadow_consts_t const &c, float const *mh, IN const &in, unsigned p, OUT &out) {
+// A sweep's orders are p*4096 + step + 1: 4096 is more than the longest sweep's steps at every tile size (up to 1026 cells a side), and 4 x 1026 sweeps x 4096 < 2^31
+template<class IN, class OUT> TERRA_HD void shadow_trace_path(shadow_consts_t const &c, float const *mh, IN const &in, unsigned p, OUT &out) {
 	shadow_pt_t v1;
 	if (p < 2u*(unsigned)c.ysize) {v1.x = c.xval((c.dirx > 0) ? 0 : c.xsize); v1.y = (float)((double)-c.Y_SCENE_SIZE + 0.5*(double)c.DY_VAL*(double)(int)p); v1.z = 0.0f;}
 	else {int const xx = (int)(p - 2u*(unsigned)c.ysize); v1.x = (float)((double)-c.X_SCENE_SIZE + 0.5*(double)c.DX_VAL*(double)xx); v1.y = c.yval((c.diry > 0) ? 0 : c.ysize); v1.z = 0.0f;}
@@ -169,7 +169,7 @@ template<uint32_t OSTRIDE = 1024u, class IN, class OUT> TERRA_HD void shadow_tra
 			float const shadow_z = (float)((double)(pt_d - cur_d)*dir_ratio + (double)cur_z);
 			if (inited && shadow_z > pt_z) {
 				out.shadow(x, y);
-				uint32_t const order = p*OSTRIDE + (uint32_t)i + 1u; // sweeps are at most ~2*130 steps long at 130 cells
+				uint32_t const order = p*4096u + (uint32_t)i + 1u;
 				if (x == xb) {out.out_y(y, order, shadow_z);}
 				if (y == yb) {out.out_x(x, order, shadow_z);}
 			}
@@ -329,11 +329,7 @@ TERRA_HD void tile_normal_v(float zc, float zr, float zd, float dxv, float dyv, 
 	float const mag = sqrtf(nv[0]*nv[0] + nv[1]*nv[1] + nv[2]*nv[2]);
 	if (!(mag < 1.0E-12f)) {nv[0] /= mag; nv[1] /= mag; nv[2] /= mag;}
 }
-TERRA_HD void tile_normal(float const *z, unsigned x, unsigned y, float dxv, float dyv, float dxy, float nv[3]) {
-	unsigned const zv = 130, ix2 = y*zv + x;
-	tile_normal_v(z[ix2], z[ix2 + 1], z[ix2 + zv], dxv, dyv, dxy, nv);
-}
-// ... for tiles of zv = S + 2 cells a side
+// ... at cell (x, y) of a tile of zv = S + 2 cells a side
 TERRA_HD void tile_normal_zv(float const *z, unsigned zv, unsigned x, unsigned y, float dxv, float dyv, float dxy, float nv[3]) {
 	unsigned const ix2 = y*zv + x;
 	tile_normal_v(z[ix2], z[ix2 + 1], z[ix2 + zv], dxv, dyv, dxy, nv);
@@ -1430,7 +1426,7 @@ template<class BE> struct terra_engine {
 
 	// ================================================================ tiles (a10, a13, K6, K7)
 	// The tile size S is get_tile_size() = MESH_X_SIZE (src/tiled_mesh.cpp:142): a tile (tx, ty) starts at cell (tx*S, ty*S) and owns (S + 2)^2 zvals, (S + 1)^2 normals /
-	// AO texels and an (S + 73)^2 AO context.  S = 128 takes the tuned kernels of the backend; every other size takes the backend's *_sized methods.
+	// AO texels and an (S + 73)^2 AO context.  The backend's tile passes take S and choose their kernels themselves.
 	uint32_t tile_size() const {return (uint32_t)cfg.mesh_x;}
 	void require_tile_size() const {
 		int const S = cfg.mesh_x;
@@ -1589,9 +1585,7 @@ template<class BE> struct terra_engine {
 		// sub-block z ranges + water bbox (src/tiled_mesh.cpp:517-541) and normals (src/tiled_mesh.h:281-284, src/tiled_mesh.cpp:865-880)
 		if (d_stats || d_normals) {
 			float const wpz_max = get_max_sea_level();
-			float const rad_c = (dxv*dxv + dyv*dyv)*size*size;
-			if (size == 128) {be.tile_post(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxdy);}
-			else {be.tile_post_sized(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxdy, size);}
+			be.tile_post_pass(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, (dxv*dxv + dyv*dyv)*size*size, dxv, dyv, dxdy, size);
 		}
 	}
 
@@ -1603,9 +1597,7 @@ template<class BE> struct terra_engine {
 		uint32_t const size = tile_size();
 		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, size + 2, 0, nullptr, 0.0f); // (only the tile references)
 		float const dxv = DX_VAL, dyv = DY_VAL;
-		if (size == 128) {float const rad_c = (dxv*dxv + dyv*dyv)*128*128; be.tile_post(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, get_max_sea_level(), rad_c, dxv, dyv, dxdy); return;}
-		float const rad_c = (dxv*dxv + dyv*dyv)*size*size;
-		be.tile_post_sized(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, get_max_sea_level(), rad_c, dxv, dyv, dxdy, size);
+		be.tile_post_pass(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, get_max_sea_level(), (dxv*dxv + dyv*dyv)*size*size, dxv, dyv, dxdy, size);
 	}
 
 	// tile_t::calc_shadows_for_light + calc_mesh_shadows (src/tiled_mesh.cpp:664-692, src/visibility.cpp:510-520) for a batch and one directional light:
@@ -1724,12 +1716,11 @@ template<class BE> struct terra_engine {
 		}
 		uint32_t const npaths = 4*zv;
 		uint32_t *d_sync = (uint32_t *)((uint8_t *)d_out + (((size_t)2*nslots*zv*8 + 255) & ~(size_t)255)); // the ticket counter of the dataflow launch
-		if (size == 128 && be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync)) {} // one launch; tiles start as their two upstream tiles publish
+		if (be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync)) {} // one launch; tiles start as their two upstream tiles publish
 		else for (uint32_t first = 0; first < n;) { // "shadows.levels" / cross-check kernels / the emulator / other tile sizes: one launch per dependency level
 			uint32_t last = first;
 			while (last < n && level[order[last]] == level[order[first]]) ++last;
-			if (size == 128) {be.tile_shadows(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);}
-			else {be.tile_shadows_sized(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);}
+			be.tile_shadows(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);
 			first = last;
 		}
 		if (d_edge_out) { // the tiles' own outgoing edges, decoded on the device
@@ -1776,8 +1767,7 @@ template<class BE> struct terra_engine {
 			if (banded) {tile_fields_dev(tile_xy, n, cs, (int)rl, d_ctx, 1.0f, true, false, 0, &cols_band, &banded);}
 		}
 		float const dz = (float)(0.5*(double)HALF_DXY);
-		if (size == 128) {be.tile_ao(n, d_zvals, d_ctx, d_ao, dz, own);}
-		else {be.tile_ao_sized(n, d_zvals, d_ctx, d_ao, dz, own, size);}
+		be.tile_ao_pass(n, d_zvals, d_ctx, d_ao, dz, own, size);
 	}
 
 	// ================================================================ height edits of the heightmap texture and the map exporter (rest of f4)

@@ -394,10 +394,14 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		lanes = lanes_cached;
 		return lanes_ok;
 	}
+	// The LDS kernels: their layout is for tiles of 130 cells a side (S = 128), the block ORs its mask out a word at a time.  Every level of a batch must take the same
+	// path (the LDS kernels order a sweep's edge writes with stride 1024, tile_shadows_simple with 4096): the choice depends only on the batch's constants
+	bool shadow_kernels_ok(terra::shadow_consts_t const &c, uint8_t const *sm, uint32_t np, terra::shadow_lanes_t &lanes) {
+		return !simple_kernels && c.xsize == 130 && !((uintptr_t)sm & 3) && shadow_lanes(c, np, lanes);
+	}
 	bool tile_shadows_flow(terra::shadow_consts_t const &c, uint32_t ntiles, uint32_t nslots, uint32_t const *ord, int32_t const *adj, float const *z, unsigned long long *out, uint8_t *sm, uint32_t np, uint32_t *sync_words) {
-		if (simple_kernels || ((uintptr_t)sm & 3) || (opt && opt->shadows_levels)) return false;
 		terra::shadow_lanes_t lanes;
-		if (!shadow_lanes(c, np, lanes)) return false;
+		if ((opt && opt->shadows_levels) || !shadow_kernels_ok(c, sm, np, lanes)) return false;
 		use();
 		fill32(sync_words, 0u, 1); // the ticket (the edge arrays were zeroed by the caller: no stale `published` bit)
 		unsigned const grid = std::min<unsigned>(ntiles, (unsigned)(2*num_cus));
@@ -407,14 +411,14 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	}
 	void tile_shadows(terra::shadow_consts_t const &c, uint32_t cnt, uint32_t const *ord, int32_t const *adj, uint32_t n, float const *z, unsigned long long *out, uint8_t *sm, uint32_t np) {
 		terra::shadow_lanes_t lanes;
-		if (simple_kernels || ((uintptr_t)sm & 3) || !shadow_lanes(c, np, lanes)) {tile_shadows_simple(c, cnt, ord, adj, n, z, out, sm, np); return;} // the block ORs its mask out a word at a time
+		if (!shadow_kernels_ok(c, sm, np, lanes)) {tile_shadows_simple(c, cnt, ord, adj, n, z, out, sm, np); return;}
 		use();
 		hipLaunchKernelGGL(terra::k_tile_shadows_level, dim3(cnt), dim3(terra::SH_LEVEL_THREADS), terra::SH_LEVEL_LDS, stream, c, n, ord, adj, z, out, sm, np, lanes);
 		TERRA_HIP_CHECK(hipGetLastError());
 	}
 	bool ao_tile_ok = false;
-	void tile_ao(uint32_t n, float const *z, float const *ctx, uint8_t *ao, float dz, bool own) {
-		if (simple_kernels) {tile_ao_simple(n, z, ctx, ao, dz, own); return;}
+	void tile_ao_pass(uint32_t n, float const *z, float const *ctx, uint8_t *ao, float dz, bool own, uint32_t S) {
+		if (simple_kernels || S != 128) {tile_ao_simple(n, z, ctx, ao, dz, own, S); return;} // (the kernels' LDS layout is for 130-cell tiles)
 		use();
 		if (ao_tile_ok && (!opt || opt->ao_whole)) { // one workgroup per tile, the context staged once
 			unsigned const grid = std::min<unsigned>(n, (unsigned)num_cus); // persistent: a CU holds one of these workgroups
@@ -430,11 +434,14 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 	}
 	uint32_t *tile_acc = nullptr; size_t tile_acc_bytes = 0; // k_tile_post's per-tile accumulators
-	void tile_post(uint32_t n, terra::tile_ref_pod_t const *refs, float const *z, terra_tile_stats *st, uint8_t *nm, float *mnz, float wpz, float rad_c, float dxv, float dyv, float dxy) {
+	// k_tile_post (S = 128, LDS-staged: the zvals 16-byte aligned), else k_tile_post_sized, else tile_post_simple; both kernels store texels as words
+	void tile_post_pass(uint32_t n, terra::tile_ref_pod_t const *refs, float const *z, terra_tile_stats *st, uint8_t *nm, float *mnz, float wpz, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {
 		float const c2 = dxy*dxy;
-		// k_tile_post takes min_normal_z from the largest |n|^2 and never looks at get_norm's "mag < TOLERANCE" branch: a texel's mag is >= sqrtf(dxdy*dxdy) (a sum that only grows, monotone roundings)
+		// the kernels take min_normal_z from the largest |n|^2 and never look at get_norm's "mag < TOLERANCE" branch: a texel's mag is >= sqrtf(dxdy*dxdy) (a sum that only grows, monotone roundings)
 		bool const normalized = !(sqrtf(c2) < 1.0E-12f) && dxy > 0.0f;
-		if (simple_kernels || ((uintptr_t)z & 15) || ((uintptr_t)nm & 3) || !normalized) {tile_post_simple(n, refs, z, st, nm, mnz, wpz, rad_c, dxv, dyv, dxy); return;} // the LDS staging reads 16 bytes at a time, texels are stored as words
+		bool const kernels = !simple_kernels && !((uintptr_t)nm & 3) && normalized;
+		bool const tuned = kernels && S == 128 && !((uintptr_t)z & 15), sized = kernels && (uint64_t)n*4 <= 0x7FFFFFFFull;
+		if (!tuned && !sized) {tile_post_simple(n, refs, z, st, nm, mnz, wpz, rad_c, dxv, dyv, dxy, S); return;}
 		use();
 		uint32_t flat_word; // the texel of a flat cell (n = (+-0, +-0, dxdy): the ocean floor), by the reference's statements
 		{
@@ -444,26 +451,9 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		size_t const bytes = (size_t)n*terra::TP_ACC*sizeof(uint32_t);
 		if (bytes > tile_acc_bytes) {if (tile_acc) {sync(); (void)hipFree(tile_acc);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_acc, bytes)); tile_acc_bytes = bytes;}
 		hipLaunchKernelGGL(terra::k_tile_post_init, dim3((n*terra::TP_ACC + 255)/256), dim3(256), 0, stream, tile_acc, n);
-		hipLaunchKernelGGL(terra::k_tile_post, dim3(n*4), dim3(terra::TP_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word);
-		hipLaunchKernelGGL(terra::k_tile_post_final, dim3((n + 255)/256), dim3(256), 0, stream, refs, n, st, mnz, tile_acc, rad_c, dxy, nm ? 1 : 0);
-		TERRA_HIP_CHECK(hipGetLastError());
-	}
-	// the post pass at a tile size other than 128 (terra_kernels.hpp: k_tile_post_sized); the same preconditions as tile_post's kernel
-	void tile_post_sized(uint32_t n, terra::tile_ref_pod_t const *refs, float const *z, terra_tile_stats *st, uint8_t *nm, float *mnz, float wpz, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {
-		float const c2 = dxy*dxy;
-		bool const normalized = !(sqrtf(c2) < 1.0E-12f) && dxy > 0.0f;
-		if (simple_kernels || ((uintptr_t)nm & 3) || !normalized || (uint64_t)n*4 > 0x7FFFFFFFull) {simple_paths::tile_post_sized(n, refs, z, st, nm, mnz, wpz, rad_c, dxv, dyv, dxy, S); return;}
-		use();
-		uint32_t flat_word;
-		{
-			float nv[3]; terra::tile_normal_v(0.0f, 0.0f, 0.0f, dxv, dyv, dxy, nv);
-			flat_word = (uint32_t)(uint8_t)(127.0*((double)nv[0] + 1.0)) | ((uint32_t)(uint8_t)(127.0*((double)nv[1] + 1.0)) << 8) | ((uint32_t)(uint8_t)(127.0*((double)nv[2] + 1.0)) << 16);
-		}
-		size_t const bytes = (size_t)n*terra::TP_ACC*sizeof(uint32_t);
-		if (bytes > tile_acc_bytes) {if (tile_acc) {sync(); (void)hipFree(tile_acc);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_acc, bytes)); tile_acc_bytes = bytes;}
-		hipLaunchKernelGGL(terra::k_tile_post_init, dim3((n*terra::TP_ACC + 255)/256), dim3(256), 0, stream, tile_acc, n);
-		hipLaunchKernelGGL(terra::k_tile_post_sized, dim3(n*4), dim3(terra::TPS_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word, S);
-		hipLaunchKernelGGL(terra::k_tile_post_final_sized, dim3((n + 255)/256), dim3(256), 0, stream, refs, n, st, mnz, tile_acc, rad_c, dxy, nm ? 1 : 0, S);
+		if (tuned) {hipLaunchKernelGGL(terra::k_tile_post, dim3(n*4), dim3(terra::TP_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word);}
+		else {hipLaunchKernelGGL(terra::k_tile_post_sized, dim3(n*4), dim3(terra::TPS_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word, S);}
+		hipLaunchKernelGGL(terra::k_tile_post_final, dim3((n + 255)/256), dim3(256), 0, stream, refs, n, st, mnz, tile_acc, rad_c, dxy, nm ? 1 : 0, S);
 		TERRA_HIP_CHECK(hipGetLastError());
 	}
 	void tile_erosion(uint32_t n, float *zvals, terra::erosion_consts_t const &ec, uint32_t iters) {

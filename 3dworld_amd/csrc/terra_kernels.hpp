@@ -577,19 +577,22 @@ __global__ __launch_bounds__(TP_THREADS) void k_tile_post(tile_ref_pod_t const *
 		if (nout) {atomicMax(&a[6], s_smax);}
 	}
 }
-// one thread per tile: mzmin / mzmax fold the 16 sub-block ranges in the reference's order with its std::min / std::max (src/tiled_mesh.cpp:536-538), radius, water bbox, min_normal_z
-__global__ __launch_bounds__(256) void k_tile_post_final(tile_ref_pod_t const *__restrict__ refs, uint32_t n, terra_tile_stats *__restrict__ stats, float *__restrict__ min_nz, uint32_t const *__restrict__ acc, float rad_c, float dxy, int have_normals) {
+// one thread per tile: mzmin / mzmax fold the 16 sub-block ranges in the reference's order with its std::min / std::max (src/tiled_mesh.cpp:536-538), radius, water bbox, min_normal_z,
+// after k_tile_post or k_tile_post_sized at the tile size S
+__global__ __launch_bounds__(256) void k_tile_post_final(tile_ref_pod_t const *__restrict__ refs, uint32_t n, terra_tile_stats *__restrict__ stats, float *__restrict__ min_nz, uint32_t const *__restrict__ acc,
+	float rad_c, float dxy, int have_normals, unsigned S)
+{
 	uint32_t const t = blockIdx.x*blockDim.x + threadIdx.x;
 	if (t >= n) return;
 	uint32_t const *a = acc + (size_t)t*TP_ACC;
 	if (stats) {
 		tile_ref_pod_t const r = refs[t];
-		int const x1 = r.tx*128, y1 = r.ty*128;
+		int const x1 = r.tx*(int)S, y1 = r.ty*(int)S;
 		float mzmin = 100.0f, mzmax = -100.0f;
 		for (int k = 0; k < 16; ++k) {mzmin = min_std(mzmin, stats[t].sub_zmin[k]); mzmax = max_std(mzmax, stats[t].sub_zmax[k]);}
 		stats[t].mzmin = mzmin; stats[t].mzmax = mzmax;
 		stats[t].radius = (float)(0.5*sqrt((double)(rad_c + (mzmax - mzmin)*(mzmax - mzmin))));
-		stats[t].wx1 = imin((int)a[2], x1 + 128); stats[t].wy1 = imin((int)a[3], y1 + 128); stats[t].wx2 = imax((int)a[4], x1); stats[t].wy2 = imax((int)a[5], y1);
+		stats[t].wx1 = imin((int)a[2], x1 + (int)S); stats[t].wy1 = imin((int)a[3], y1 + (int)S); stats[t].wx2 = imax((int)a[4], x1); stats[t].wy2 = imax((int)a[5], y1);
 	}
 	if (min_nz && have_normals) { // min_normal_z = min(1.0, min over texels of dxdy/mag) = dxdy / (the largest mag), both roundings monotone; a NaN never wins (src/tiled_mesh.cpp:874)
 		float smax; uint32_t const u = a[6]; memcpy(&smax, &u, 4);
@@ -598,11 +601,11 @@ __global__ __launch_bounds__(256) void k_tile_post_final(tile_ref_pod_t const *_
 	}
 }
 
-// ---- the post pass at a tile size S other than 128 (zv = S + 2, stride = S + 1, block_size bs = zv/4): one block per (tile, sub-block row yy).  The block owns the
+// ---- the post pass at any tile size S (zv = S + 2, stride = S + 1, block_size bs = zv/4): one block per (tile, sub-block row yy).  The block owns the
 // stats rows [yy*bs, (yy + 1)*bs] (the shared row (yy + 1)*bs counts in both bands, as in the reference) and the texel rows [yy*bs, (yy + 1)*bs) -- the last band
 // through row S.  A wave walks every TPS_WAVES-th row, a lane every 64th column; the rows are read through the caches (no LDS staging: a band of a 1024-cell tile
 // is 1 MB).  The texel words are tp_word_fast / tp_word_exact's, by the same wave-uniform decision as k_tile_post; the tile's totals go through the same per-tile
-// accumulators to k_tile_post_final_sized.
+// accumulators to k_tile_post_final.  It runs at S != 128 and at S = 128 where k_tile_post's 16-byte staging does not apply.
 constexpr unsigned TPS_THREADS = 512, TPS_WAVES = TPS_THREADS/64;
 __global__ __launch_bounds__(TPS_THREADS) void k_tile_post_sized(tile_ref_pod_t const *__restrict__ refs, float const *__restrict__ zvals, terra_tile_stats *__restrict__ stats,
 	uint8_t *__restrict__ normals, uint32_t *__restrict__ acc, float wpz_max, float dxv, float dyv, float dxy, float c2, uint32_t flat_word, unsigned S)
@@ -672,27 +675,6 @@ __global__ __launch_bounds__(TPS_THREADS) void k_tile_post_sized(tile_ref_pod_t 
 			atomicMin((int *)&a[2], s_bb[0]); atomicMin((int *)&a[3], s_bb[1]); atomicMax((int *)&a[4], s_bb[2]); atomicMax((int *)&a[5], s_bb[3]);
 		}
 		if (nout) {atomicMax(&a[6], s_smax);}
-	}
-}
-__global__ __launch_bounds__(256) void k_tile_post_final_sized(tile_ref_pod_t const *__restrict__ refs, uint32_t n, terra_tile_stats *__restrict__ stats, float *__restrict__ min_nz, uint32_t const *__restrict__ acc,
-	float rad_c, float dxy, int have_normals, unsigned S)
-{
-	uint32_t const t = blockIdx.x*blockDim.x + threadIdx.x;
-	if (t >= n) return;
-	uint32_t const *a = acc + (size_t)t*TP_ACC;
-	if (stats) {
-		tile_ref_pod_t const r = refs[t];
-		int const x1 = r.tx*(int)S, y1 = r.ty*(int)S;
-		float mzmin = 100.0f, mzmax = -100.0f;
-		for (int k = 0; k < 16; ++k) {mzmin = min_std(mzmin, stats[t].sub_zmin[k]); mzmax = max_std(mzmax, stats[t].sub_zmax[k]);}
-		stats[t].mzmin = mzmin; stats[t].mzmax = mzmax;
-		stats[t].radius = (float)(0.5*sqrt((double)(rad_c + (mzmax - mzmin)*(mzmax - mzmin))));
-		stats[t].wx1 = imin((int)a[2], x1 + (int)S); stats[t].wy1 = imin((int)a[3], y1 + (int)S); stats[t].wx2 = imax((int)a[4], x1); stats[t].wy2 = imax((int)a[5], y1);
-	}
-	if (min_nz && have_normals) {
-		float smax; uint32_t const u = a[6]; memcpy(&smax, &u, 4);
-		float const nz = dxy/sqrtf(smax);
-		min_nz[t] = (nz < 1.0f) ? nz : 1.0f;
 	}
 }
 
@@ -806,7 +788,7 @@ template<bool OWN> __global__ __launch_bounds__(AO_THREADS) __attribute__((amdgp
 // (2 lane, 2 lane + 1) of a row, a wave a row: the two texels' samples of a ray step are neighbours in LDS, one 8-byte read (256 B per clock against the 4-byte read's 128)
 // where the step's x offset is even; where it is odd the pair straddles two aligned 8-byte words and takes both (the 4-byte reads of a lane pair would be 2-way bank
 // conflicts at a stride of two dwords).  Per texel pair 40 + 2 x 24 eight-byte reads = 176 LDS cycles instead of 256, four waves per SIMD instead of two to hide them;
-// the compares (2 instructions per sample) are what is left.  Column 128 is a lane per row.  Same integer sums as k_tile_ao / tile_ao_simple.
+// the compares (2 instructions per sample) are what is left.  Column 128 is a lane per row.  Same integer sums as k_tile_ao / tile_ao_simple at S = 128.
 constexpr unsigned AOT_THREADS = 1024, AOT_S = 202, AOT_LDS = AO_CS*AOT_S*4;
 typedef float ao_f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float ao_lds_f;   // (the volatile reads below must know they are LDS reads: a generic volatile pointer becomes a flat load)

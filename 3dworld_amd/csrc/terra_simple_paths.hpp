@@ -39,16 +39,21 @@ template<class DERIVED> struct simple_paths {
 			zvals[i] = finish_cell(z, job, nc, L, d_sm + (size_t)r.xi*zv, d_sm + (size_t)(nux + r.yi)*zv, x, y);
 		});
 	}
+	// ---- the tile passes at the tile size S (zv = S + 2 zvals, stride = S + 1 texels a side): what the emulator runs, and what the HIP backend runs where its kernels
+	// do not apply (TERRA_SIMPLE_KERNELS=1, a precondition of a kernel not met, AO and shadows at sizes other than 128).  S defaults to 128 for backends that call the
+	// bodies with the 128-cell signatures.
 	// mesh shadows of one dependency level: one logical thread per (tile, sweep); smask bits by atomic OR on the containing word, outgoing edge
 	// heights by atomic max of (sequential order << 32 | value bits) so that the writer the single-threaded reference would see last wins
+	// a tile's mask base is t*zv^2 bytes, not always word-aligned: the MESH_SHADOW bit goes through the word that holds the byte
 	struct shadow_out_t {
 		uint8_t *sm; unsigned long long *ox, *oy; int xsize;
 		TERRA_HD void shadow(int x, int y) {
-			size_t const o = (size_t)y*xsize + x;
+			uint8_t *const b = sm + (size_t)y*xsize + x;
 #if defined(__HIP_DEVICE_COMPILE__)
-			atomicOr((unsigned int *)(sm + (o & ~(size_t)3)), 0x02u << (8u*(unsigned)(o & 3))); // tile bases are multiples of 16900 bytes: word-aligned
+			uintptr_t const a = (uintptr_t)b;
+			atomicOr((unsigned int *)(a & ~(uintptr_t)3), 0x02u << (8u*(unsigned)(a & 3)));
 #else
-			sm[o] |= 0x02;
+			*b |= 0x02;
 #endif
 		}
 		TERRA_HD static unsigned long long pack(uint32_t order, float v) {uint32_t b; memcpy(&b, &v, 4); return ((unsigned long long)order << 32) | b;}
@@ -65,7 +70,7 @@ template<class DERIVED> struct simple_paths {
 	void tile_shadows_simple(shadow_consts_t const &c, uint32_t cnt, uint32_t const *d_order, int32_t const *d_adj, uint32_t n, float const *d_zvals,
 		unsigned long long *d_out, uint8_t *d_smask, uint32_t npaths)
 	{
-		unsigned const zv = 130;
+		unsigned const zv = (unsigned)c.xsize;
 		self().launch((size_t)cnt*npaths, [=] TERRA_LAMBDA (size_t i) {
 			uint32_t const k = (uint32_t)(i / npaths), p = (uint32_t)(i % npaths), t = d_order[k];
 			int32_t const ax = d_adj[2*t], ay = d_adj[2*t + 1];
@@ -74,99 +79,9 @@ template<class DERIVED> struct simple_paths {
 			shadow_trace_path(c, d_zvals + (size_t)t*zv*zv, in, p, out);
 		});
 	}
-	// AO lighting, simple form: one logical thread per texel, context read from global memory
+	// AO lighting: one logical thread per texel, context read from global memory
 	// own: inside the tile the context is the tile's own zvals (src/tiled_mesh.cpp:622) -- read from d_zvals, whatever d_ctx holds there
-	void tile_ao_simple(uint32_t n, float const *d_zvals, float const *d_ctx, uint8_t *d_ao, float dz, bool own) {
-		unsigned const stride = 129, zv = 130, cs = 201, rl = 36;
-		self().launch((size_t)n*stride*stride, [=] TERRA_LAMBDA (size_t i) {
-			unsigned const t = (unsigned)(i / (stride*stride)), p = (unsigned)(i % (stride*stride)), y = p / stride, x = p % stride;
-			float const *c = d_ctx + (size_t)t*cs*cs, *z = d_zvals + (size_t)t*zv*zv;
-			d_ao[i] = tile_ao_texel(z[y*zv + x], (int)x, (int)y, dz, [=] TERRA_LAMBDA (int cx, int cy) {
-				bool const in = own && (unsigned)(cx - (int)rl) < zv && (unsigned)(cy - (int)rl) < zv;
-				return in ? z[(cy - (int)rl)*(int)zv + (cx - (int)rl)] : c[cy*(int)cs + cx];
-			});
-		});
-	}
-	// tile post-pass, simple form: sub-block ranges + water bbox (one logical thread per (tile, sub-block) then per tile), normals (one per texel)
-	void tile_post_simple(uint32_t n, tile_ref_pod_t const *d_refs, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz,
-		float wpz_max, float rad_c, float dxv, float dyv, float dxy)
-	{
-		unsigned const size = 128, stride = 129, zv = 130;
-		if (d_stats) {
-			self().launch((size_t)n*16, [=] TERRA_LAMBDA (size_t i) {
-				unsigned const t = (unsigned)(i >> 4), sbk = (unsigned)(i & 15), yy = sbk >> 2, xx = sbk & 3, bs = zv/4;
-				float const *z = d_zvals + (size_t)t*zv*zv;
-				float szmin = 100.0f, szmax = -100.0f; // FAR_DISTANCE (src/3DWorld.h:116)
-				for (unsigned y = yy*bs; y <= (yy+1)*bs; ++y) {
-					for (unsigned x = xx*bs; x <= (xx+1)*bs; ++x) {float const v = z[y*zv + x]; szmin = min_std(szmin, v); szmax = max_std(szmax, v);}
-				}
-				d_stats[t].sub_zmin[sbk] = szmin; d_stats[t].sub_zmax[sbk] = szmax;
-			});
-			self().launch(n, [=] TERRA_LAMBDA (size_t t) {
-				tile_ref_pod_t const r = d_refs[t];
-				int const x1 = r.tx*(int)size, y1 = r.ty*(int)size;
-				float const *z = d_zvals + (size_t)t*zv*zv;
-				terra_tile_stats &st = d_stats[t];
-				float mzmin = 100.0f, mzmax = -100.0f;
-				for (int sbk = 0; sbk < 16; ++sbk) {mzmin = min_std(mzmin, st.sub_zmin[sbk]); mzmax = max_std(mzmax, st.sub_zmax[sbk]);}
-				int wx1 = x1 + (int)size, wy1 = y1 + (int)size, wx2 = x1, wy2 = y1; // start denormalized (src/tiled_mesh.cpp:308)
-				unsigned const lim = 4*(zv/4); // cells 0..128 are visited by the 4x4 blocks; row/column 129 is skipped
-				for (unsigned y = 0; y <= lim; ++y) {
-					for (unsigned x = 0; x <= lim; ++x) {
-						if (z[y*zv + x] < wpz_max) {wx1 = imin(wx1, x1+(int)x); wy1 = imin(wy1, y1+(int)y); wx2 = imax(wx2, x1+(int)x); wy2 = imax(wy2, y1+(int)y);}
-					}
-				}
-				st.mzmin = mzmin; st.mzmax = mzmax;
-				st.radius = (float)(0.5*sqrt((double)(rad_c + (mzmax - mzmin)*(mzmax - mzmin))));
-				st.wx1 = wx1; st.wy1 = wy1; st.wx2 = wx2; st.wy2 = wy2;
-			});
-		}
-		if (d_normals) {
-			uint32_t *d_mnz = (uint32_t *)d_min_nz;
-			if (d_mnz) {self().fill32(d_mnz, 0x3F800000u /*1.0f*/, n);}
-			self().launch((size_t)n*stride*stride, [=] TERRA_LAMBDA (size_t i) {
-				unsigned const t = (unsigned)(i / (stride*stride)), p = (unsigned)(i % (stride*stride)), y = p / stride, x = p % stride;
-				float nv[3];
-				tile_normal(d_zvals + (size_t)t*zv*zv, x, y, dxv, dyv, dxy, nv);
-				uint8_t *o = d_normals + i*4;
-				o[0] = (uint8_t)(127.0*((double)nv[0] + 1.0)); o[1] = (uint8_t)(127.0*((double)nv[1] + 1.0)); o[2] = (uint8_t)(127.0*((double)nv[2] + 1.0)); o[3] = 0;
-				if (d_mnz && nv[2] < 1.0f) { // min_normal_z = min(min_normal_z, norm.z), seeded with 1.0; norm.z = dxdy/mag >= 0 so uint order == float order; NaN never wins
-					uint32_t u; memcpy(&u, &nv[2], 4);
-					TERRA_ATOMIC_MIN(&d_mnz[t], u);
-				}
-			});
-		}
-	}
-	// ---- the tile passes at a tile size S other than 128 (zv = S + 2 zvals, stride = S + 1 texels a side): the size-general forms of the three above, and what a
-	// backend without kernels of its own for them runs.  Same statements, same bytes as the 128 forms at S = 128.
-	// a tile's mask base is t*zv^2 bytes, not always word-aligned: the MESH_SHADOW bit goes through the word that holds the byte
-	struct shadow_out_sized_t {
-		uint8_t *sm; unsigned long long *ox, *oy; int xsize;
-		TERRA_HD void shadow(int x, int y) {
-			uint8_t *const b = sm + (size_t)y*xsize + x;
-#if defined(__HIP_DEVICE_COMPILE__)
-			uintptr_t const a = (uintptr_t)b;
-			atomicOr((unsigned int *)(a & ~(uintptr_t)3), 0x02u << (8u*(unsigned)(a & 3)));
-#else
-			*b |= 0x02;
-#endif
-		}
-		TERRA_HD void out_x(int ix, uint32_t order, float v) {TERRA_ATOMIC_MAX(&ox[ix], shadow_out_t::pack(order, v));}
-		TERRA_HD void out_y(int iy, uint32_t order, float v) {TERRA_ATOMIC_MAX(&oy[iy], shadow_out_t::pack(order, v));}
-	};
-	void tile_shadows_sized(shadow_consts_t const &c, uint32_t cnt, uint32_t const *d_order, int32_t const *d_adj, uint32_t n, float const *d_zvals,
-		unsigned long long *d_out, uint8_t *d_smask, uint32_t npaths)
-	{
-		unsigned const zv = (unsigned)c.xsize;
-		self().launch((size_t)cnt*npaths, [=] TERRA_LAMBDA (size_t i) {
-			uint32_t const k = (uint32_t)(i / npaths), p = (uint32_t)(i % npaths), t = d_order[k];
-			int32_t const ax = d_adj[2*t], ay = d_adj[2*t + 1];
-			shadow_in_t const in{(ay >= 0) ? d_out + ((size_t)0*n + ay)*zv : nullptr, (ax >= 0) ? d_out + ((size_t)1*n + ax)*zv : nullptr};
-			shadow_out_sized_t out{d_smask + (size_t)t*zv*zv, d_out + ((size_t)0*n + t)*zv, d_out + ((size_t)1*n + t)*zv, (int)zv};
-			shadow_trace_path<4096u>(c, d_zvals + (size_t)t*zv*zv, in, p, out);
-		});
-	}
-	void tile_ao_sized(uint32_t n, float const *d_zvals, float const *d_ctx, uint8_t *d_ao, float dz, bool own, uint32_t S) {
+	void tile_ao_simple(uint32_t n, float const *d_zvals, float const *d_ctx, uint8_t *d_ao, float dz, bool own, uint32_t S = 128) {
 		unsigned const stride = S + 1, zv = S + 2, cs = S + 73, rl = 36;
 		self().launch((size_t)n*stride*stride, [=] TERRA_LAMBDA (size_t i) {
 			unsigned const t = (unsigned)(i / ((size_t)stride*stride)), p = (unsigned)(i % ((size_t)stride*stride)), y = p / stride, x = p % stride;
@@ -177,9 +92,9 @@ template<class DERIVED> struct simple_paths {
 			});
 		});
 	}
-	// stats: one logical thread per (tile, sub-block) and then per (tile, cell row) for the water box; normals one per texel
-	void tile_post_sized(uint32_t n, tile_ref_pod_t const *d_refs, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz,
-		float wpz_max, float rad_c, float dxv, float dyv, float dxy, uint32_t S)
+	// post pass: sub-block ranges one logical thread per (tile, sub-block), the water bbox per (tile, cell row) and then per tile; normals one per texel
+	void tile_post_simple(uint32_t n, tile_ref_pod_t const *d_refs, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz,
+		float wpz_max, float rad_c, float dxv, float dyv, float dxy, uint32_t S = 128)
 	{
 		unsigned const size = S, stride = S + 1, zv = S + 2, bs = zv/4, lim = 4*bs; // block_size = zvsize/4; cells 0 .. 4*block_size are visited by the 4 x 4 blocks
 		if (d_stats) {
@@ -227,13 +142,17 @@ template<class DERIVED> struct simple_paths {
 				tile_normal_zv(d_zvals + (size_t)t*zv*zv, zv, x, y, dxv, dyv, dxy, nv);
 				uint8_t *o = d_normals + i*4;
 				o[0] = (uint8_t)(127.0*((double)nv[0] + 1.0)); o[1] = (uint8_t)(127.0*((double)nv[1] + 1.0)); o[2] = (uint8_t)(127.0*((double)nv[2] + 1.0)); o[3] = 0;
-				if (d_mnz && nv[2] < 1.0f) {
+				if (d_mnz && nv[2] < 1.0f) { // min_normal_z = min(min_normal_z, norm.z), seeded with 1.0; norm.z = dxdy/mag >= 0 so uint order == float order; NaN never wins
 					uint32_t u; memcpy(&u, &nv[2], 4);
 					TERRA_ATOMIC_MIN(&d_mnz[t], u);
 				}
 			});
 		}
 	}
+	// the driver's entry points for the post and AO passes: these bodies, unless the backend has kernels of its own (the HIP backend)
+	void tile_post_pass(uint32_t n, tile_ref_pod_t const *d_refs, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz,
+		float wpz_max, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {tile_post_simple(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxy, S);}
+	void tile_ao_pass(uint32_t n, float const *d_zvals, float const *d_ctx, uint8_t *d_ao, float dz, bool own, uint32_t S) {tile_ao_simple(n, d_zvals, d_ctx, d_ao, dz, own, S);}
 	// tile erosion, wave form: the clamp-padded copies live in HBM/L2, ONE WAVE per tile walks the droplets in order through a 32x32 LDS window
 	// (10 KB of LDS per tile instead of 76 KB: ~15 tiles per CU in flight instead of 2)
 	void tile_erosion_windowed(uint32_t n, float *zvals, erosion_consts_t const &ec, uint32_t iters, float *padded /* n*NX*NY */) {

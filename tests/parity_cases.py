@@ -362,10 +362,11 @@ def np_tile_stats(z, tx, ty, wpz_max, dxv, dyv):
     return smin, smax, mzmin, mzmax, radius, (wx1, wy1, wx2, wy2)
 
 
-def case_tiles_post_adversarial(pkg, t, orc):
+def case_tiles_post_adversarial(pkg, t, orc, zoff=0):
     """terra_tiles_post_dev on zvals the terrain generator never makes: flat tiles (the constant-word path of k_tile_post), slopes of 1e-7 (nz within an ulp of 1: the byte
     test cannot decide, the reference's statements run), |n|^2 overflowing to +inf, NaN and +-inf cells, cliffs (n_x / |n| near -1 and +1), heights around the sea level
-    (water bbox), a tile whose last row / column alone is special -- normals and min_normal_z against the oracle's tile_normals, the stats against np_tile_stats"""
+    (water bbox), a tile whose last row / column alone is special -- normals and min_normal_z against the oracle's tile_normals, the stats against np_tile_stats.
+    zoff: the zvals start that many bytes into their buffer (4: not 16-byte aligned, so the HIP backend takes k_tile_post_sized instead of k_tile_post)"""
     import ctypes as C
     pc_, oc = cfg_pair(pkg, mesh_gen_mode=0)
     st = t.init_scene(pc_); orc.init(oc)
@@ -385,12 +386,13 @@ def case_tiles_post_adversarial(pkg, t, orc):
     z[7] = f(wpz) + (rng.standard_normal((130, 130)) * 1e-3).astype(f)
     z[8] = f(0.25); z[8][128:, :] = walk(1e-2)[128:, :]; z[8][:, 128:] = walk(1e-2)[:, 128:]
     z[9] = np.nan
-    zb = t.alloc(z.nbytes).upload(z); sb = t.alloc(len(tiles) * C.sizeof(pkg.TileStats)); nb = t.alloc(len(tiles) * 129 * 129 * 4); mb = t.alloc(len(tiles) * 4)
+    zh = np.concatenate([np.full(zoff // 4, 3.0, f), z.ravel()])
+    zb = t.alloc(zh.nbytes).upload(zh); sb = t.alloc(len(tiles) * C.sizeof(pkg.TileStats)); nb = t.alloc(len(tiles) * 129 * 129 * 4); mb = t.alloc(len(tiles) * 4)
     try:
         for with_stats, with_normals in ((True, True), (True, False), (False, True)):
             nb.upload(np.full(len(tiles) * 129 * 129 * 4, 7, np.uint8)); mb.upload(np.full(len(tiles), 5.0, f)); sb.upload(np.zeros(len(tiles) * C.sizeof(pkg.TileStats), np.uint8))
-            t.tiles_post_dev(tiles, zb.ptr, sb.ptr if with_stats else None, nb.ptr if with_normals else None, mb.ptr if with_normals else None)
-            assert (zb.download(f, z.shape).view(np.uint32) == z.view(np.uint32)).all(), "the zvals are not written"
+            t.tiles_post_dev(tiles, zb.ptr + zoff, sb.ptr if with_stats else None, nb.ptr if with_normals else None, mb.ptr if with_normals else None)
+            assert (zb.download(f, zh.shape).view(np.uint32) == zh.view(np.uint32)).all(), "the zvals are not written"
             nm = nb.download(np.uint8, (len(tiles), 129, 129, 4)); mnz = mb.download(f, (len(tiles),))
             sraw = sb.download(np.uint8, (len(tiles), C.sizeof(pkg.TileStats)))
             for i, (tx, ty) in enumerate(tiles):

@@ -99,7 +99,8 @@ def test_tile_mesh_shadows_halo_interface(pkg, gpu, orc):
 
 
 def test_tiles_post_pass_on_adversarial_zvals(pkg, gpu, orc):
-    pc.case_tiles_post_adversarial(pkg, gpu, orc)
+    for zoff in (0, 4):  # 4: zvals not 16-byte aligned, the post pass at S = 128 runs k_tile_post_sized
+        pc.case_tiles_post_adversarial(pkg, gpu, orc, zoff)
 
 
 def test_tiles_from_heightmap_texture(pkg, gpu, orc):
