@@ -578,6 +578,32 @@ int terra_tiles_create_weights(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 		be.free(d);
 	TERRA_CATCH
 }
+int terra_tiles_edit_grass_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *d_zvals, const terra_tile_stats *d_stats,
+                               const uint8_t *d_is_distant, const terra_grass_brush *brush, uint8_t *d_weights, terra_grass_block *d_grass_blocks, uint8_t *d_updated, uint32_t *d_ranges) {
+	TERRA_CHECK_CTX if (!brush || (n && (!tile_xy || !d_zvals || !d_stats || !d_weights || !d_grass_blocks || !d_updated))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_edit_grass_dev(tile_xy, n, dxoff, dyoff, d_zvals, d_stats, d_is_distant, brush->pos, brush->radius, brush->add_grass != 0, brush->shape, brush->brush_weight,
+		d_weights, (terra::grass_block_pod_t *)d_grass_blocks, d_updated, d_ranges); TERRA_CATCH
+}
+int terra_tiles_edit_grass(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *h_zvals, const terra_tile_stats *h_stats,
+                           const uint8_t *h_is_distant, const terra_grass_brush *brush, uint8_t *h_weights, terra_grass_block *h_grass_blocks, uint8_t *h_updated, uint32_t *h_ranges) {
+	TERRA_CHECK_CTX if (!brush || (n && (!tile_xy || !h_zvals || !h_stats || !h_weights || !h_grass_blocks || !h_updated))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_128("tiles_edit_grass"); // (before the arrays are read: they are sized for 128)
+		if (n == 0) return TERRA_OK;
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const zb = (size_t)n*130*130*4, sb = (size_t)n*sizeof(terra_tile_stats), db = n, wb = (size_t)n*129*129*4, gb = (size_t)n*32*32*sizeof(terra_grass_block), ub = n, rb = (size_t)n*16;
+		size_t const oz = 0, os = oz + up(zb), od = os + up(sb), ow = od + up(db), og = ow + up(wb), ou = og + up(gb), orr = ou + up(ub);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(orr + up(rb));
+		be.h2d(d + oz, h_zvals, zb); be.h2d(d + os, h_stats, sb); be.h2d(d + ow, h_weights, wb); be.h2d(d + og, h_grass_blocks, gb);
+		if (h_is_distant) {be.h2d(d + od, h_is_distant, db);}
+		ctx->eng.tiles_edit_grass_dev(tile_xy, n, dxoff, dyoff, (float const *)(d + oz), (terra_tile_stats const *)(d + os), h_is_distant ? d + od : nullptr, brush->pos, brush->radius,
+			brush->add_grass != 0, brush->shape, brush->brush_weight, d + ow, (terra::grass_block_pod_t *)(d + og), d + ou, (uint32_t *)(d + orr));
+		be.d2h(h_weights, d + ow, wb); be.d2h(h_grass_blocks, d + og, gb); be.d2h(h_updated, d + ou, ub);
+		if (h_ranges) {be.d2h(h_ranges, d + orr, rb);}
+	TERRA_CATCH
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

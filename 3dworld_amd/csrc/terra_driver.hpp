@@ -1802,12 +1802,8 @@ template<class BE> struct terra_engine {
 				float const ey = ((float)yp + dy) - (float)by, ex = ((float)xp + dx) - (float)bx;
 				float const dist = sqrtf(ey*ey + ex*ex), dval = dist*r_inv;
 				if (shape != BSHAPE_CONST_SQ && shape != BSHAPE_FLAT_SQ && (double)dval > 1.0) return; // round (instead of square)
-				float mod_delta = (float)delta; // adjust_brush_weight (src/heightmap.cpp:27-33)
-				float const PI_F = 3.141592654f;
-				if      (shape == BSHAPE_LINEAR   ) {mod_delta *= 1.0f - dval;}
-				else if (shape == BSHAPE_QUADRATIC) {mod_delta *= 1.0f - dval*dval;}
-				else if (shape == BSHAPE_COSINE   ) {mod_delta *= L.COSF(0.5f*PI_F*dval);}
-				else if (shape == BSHAPE_SINE     ) {mod_delta *= 0.5f*(1.0f + L.SINF(PI_F*dval + 0.5f*PI_F));}
+				float mod_delta = (float)delta;
+				adjust_brush_weight(L, mod_delta, dval, shape);
 				int x = xp, y = yp; // modify_height_value (src/tiled_mesh.cpp:259-266)
 				hv.clamp_xy(x, y, dx, dy);
 				modify_pixel(pix, hv.ncolors, (size_t)hv.width*(unsigned)y + (unsigned)x, hmap_view_t::round_fp(mod_delta), is_delta);
@@ -1966,6 +1962,107 @@ template<class BE> struct terra_engine {
 			});
 		}
 		if (d_has_grass) {be.launch(n, [=] TERRA_LAMBDA (size_t i) {d_has_grass[i] = d_any[i];});}
+	}
+	// tile_draw_t::add_or_remove_grass_at (src/tiled_mesh.cpp:3771-3774) over a batch whose weights / grass blocks are on the device (tiles_create_weights_dev's layouts):
+	// tile_t::add_or_remove_grass_at (:3845-3948) from :3847 on, in place.  d_updated: n bytes; d_ranges (or null): n x {xl, yl, xh, yh}
+	void tiles_edit_grass_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, float const *d_zvals, terra_tile_stats const *d_stats, uint8_t const *d_distant,
+		float const pos[3], float radius, bool add, int shape, float brush_weight, uint8_t *d_weights, grass_block_pod_t *d_blocks, uint8_t *d_updated, uint32_t *d_ranges)
+	{
+		require_scene();
+		require_tile_128("tiles_edit_grass");
+		if (shape < 0 || shape >= NUM_BSHAPES) throw std::invalid_argument("tiles_edit_grass: bad brush shape");
+		if (((uintptr_t)d_weights & 3u) != 0) throw std::invalid_argument("tiles_edit_grass: d_weights must be 4-byte aligned");
+		if (n == 0) return;
+		grass_brush_consts_t g;
+		g.px = pos[0]; g.py = pos[1]; g.pz = pos[2]; g.rr = radius;
+		g.r_inv = (float)(1.0/(double)radius); g.bweight = (float)(10.0*(double)brush_weight);
+		g.xss = cfg.scene_x; g.yss = cfg.scene_y; g.DX_VAL = DX_VAL; g.DY_VAL = DY_VAL;
+		g.add = add ? 1 : 0; g.shape = shape; g.is_square = (shape == BSHAPE_CONST_SQ) ? 1 : 0; g.dxoff = dxoff; g.dyoff = dyoff;
+		g.L = lut();
+		// rradius == 0 returns at once (:3847); a negative or NaN radius passes no texel's test: only the outputs are written then
+		bool const live = radius > 0.0f;
+		auto half = [](double r, double step) {double const h = ceil(r/step) + 1.0; return (h < 200.0) ? (int)h : 200;};
+		g.hx = live ? half(radius, DX_VAL) : 0; g.hy = live ? half(radius, DY_VAL) : 0;
+		g.wx = (uint32_t)imin(2*g.hx + 1, (int)WT_TEX); g.wy = (uint32_t)imin(2*g.hy + 1, (int)WT_TEX);
+		landscape_consts_t const c = landscape_consts();
+		size_t const nwin = (size_t)g.wx*g.wy;
+		uint8_t *base = scratch<uint8_t>(s_ao, (size_t)n*(12 + 2*WT_TEX + 4)*4 + (size_t)n*nwin + 256);
+		float *d_params = (float *)base, *d_pos = d_params + (size_t)n*12;
+		if (!d_ranges) {d_ranges = (uint32_t *)(d_pos + (size_t)n*2*WT_TEX);} // (written and not returned)
+		uint8_t *d_flags = (uint8_t *)(d_pos + (size_t)n*(2*WT_TEX + 4)); // per tile and window texel: 1 = the texel set `updated`
+		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, WT_TEX, 0, nullptr, 0.0f);
+		if (live && !add) {tiles_terrain_params_dev(d_refs, n, d_params);} // the dirt scale of the remove path (:3917)
+		uint32_t *d_w32 = (uint32_t *)d_weights;
+		if (be.tile_edit_grass(g, c, d_refs, n, d_zvals, d_stats, d_distant, d_params, d_w32, d_blocks, d_flags, d_updated, d_ranges)) return;
+		// the simple form: position tables, one logical thread per window texel, per grass block, per tile
+		uint32_t const wx = g.wx, wy = g.wy;
+		if (live) {
+			// pt.x / pt.y of the texel loop advance by `+= DX_VAL` / `+= DY_VAL` from the tile's corner on, skipped rows and columns too: a serial float sum per tile and axis
+			be.launch((size_t)n*2, [=] TERRA_LAMBDA (size_t i) {
+				unsigned const t = (unsigned)(i >> 1), ax = (unsigned)(i & 1);
+				tile_ref_pod_t const r = d_refs[t];
+				float v = ax ? grass_yval(g, r.ty*(int)WT_SIZE + g.dyoff) : grass_xval(g, r.tx*(int)WT_SIZE + g.dxoff);
+				float const step = ax ? g.DY_VAL : g.DX_VAL;
+				float *o = d_pos + i*WT_TEX;
+				for (unsigned k = 0; k < WT_TEX; ++k) {o[k] = v; v += step;}
+			});
+			be.launch((size_t)n*nwin, [=] TERRA_LAMBDA (size_t i) {
+				unsigned const t = (unsigned)(i / nwin), p = (unsigned)(i % nwin);
+				tile_ref_pod_t const r = d_refs[t];
+				terra_tile_stats const &st = d_stats[t];
+				uint8_t f = 0;
+				if (grass_tile_hit(g, r.tx, r.ty, st.mzmin, st.mzmax, st.radius)) {
+					float const *px = d_pos + (size_t)t*2*WT_TEX, *py = px + WT_TEX;
+					unsigned const x = (unsigned)grass_win0(g.px, px[0], g.DX_VAL, g.hx, wx) + p % wx, y = (unsigned)grass_win0(g.py, py[0], g.DY_VAL, g.hy, wy) + p / wx;
+					f = (uint8_t)grass_texel(g, c, px[x], py[y], d_w32[((size_t)t*WT_TEX + y)*WT_TEX + x], d_zvals + (size_t)t*WT_ZV*WT_ZV, d_params + (size_t)t*12, x, y);
+				}
+				d_flags[i] = f;
+			});
+			if (add && c.gen_grass_map) {
+				uint32_t const bd = GRASS_BLOCK_DIM;
+				be.launch((size_t)n*bd*bd, [=] TERRA_LAMBDA (size_t i) {
+					unsigned const t = (unsigned)(i / (bd*bd)), b = (unsigned)(i % (bd*bd));
+					tile_ref_pod_t const r = d_refs[t];
+					terra_tile_stats const &st = d_stats[t];
+					if ((d_distant && d_distant[t]) || !grass_tile_hit(g, r.tx, r.ty, st.mzmin, st.mzmax, st.radius)) return;
+					unsigned const x0 = (unsigned)grass_win0(g.px, grass_xval(g, r.tx*(int)WT_SIZE + g.dxoff), g.DX_VAL, g.hx, wx);
+					unsigned const y0 = (unsigned)grass_win0(g.py, grass_yval(g, r.ty*(int)WT_SIZE + g.dyoff), g.DY_VAL, g.hy, wy);
+					uint8_t const *fl = d_flags + (size_t)t*nwin;
+					grass_block_pod_t gb = d_blocks[i];
+					if (grass_block_merge(c, gb, d_zvals + (size_t)t*WT_ZV*WT_ZV, r.tx*(int)WT_SIZE, r.ty*(int)WT_SIZE, b % bd, b / bd,
+						[=] TERRA_LAMBDA (unsigned x, unsigned y) {return x - x0 < wx && y - y0 < wy && (fl[(y - y0)*wx + (x - x0)] & 1u);})) {d_blocks[i] = gb;}
+				});
+			}
+		}
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			tile_ref_pod_t const r = d_refs[t];
+			terra_tile_stats const &st = d_stats[t];
+			uint32_t rg[4] = {WT_SIZE, WT_SIZE, 0u, 0u}; // xl, yl, xh, yh start denormalised (:3863)
+			bool upd = false;
+			if (live && grass_tile_hit(g, r.tx, r.ty, st.mzmin, st.mzmax, st.radius)) {
+				unsigned const x0 = (unsigned)grass_win0(g.px, grass_xval(g, r.tx*(int)WT_SIZE + g.dxoff), g.DX_VAL, g.hx, wx);
+				unsigned const y0 = (unsigned)grass_win0(g.py, grass_yval(g, r.ty*(int)WT_SIZE + g.dyoff), g.DY_VAL, g.hy, wy);
+				for (unsigned p = 0; p < nwin; ++p) {
+					if (!(d_flags[t*nwin + p] & 1u)) continue;
+					upd = true;
+					if (!add) break;
+					unsigned const x = x0 + p % wx, y = y0 + p / wx;
+					rg[0] = min_u32(rg[0], x); rg[2] = max_u32(rg[2], min_u32(x + 1, WT_SIZE));
+					rg[1] = min_u32(rg[1], y); rg[3] = max_u32(rg[3], min_u32(y + 1, WT_SIZE));
+				}
+				grass_block_pod_t *bl = d_blocks + t*GRASS_BLOCK_DIM*GRASS_BLOCK_DIM;
+				bool has_blocks = false;
+				for (unsigned b = 0; b < GRASS_BLOCK_DIM*GRASS_BLOCK_DIM && !has_blocks; ++b) {has_blocks = (bl[b].ix != 0);}
+				if (!add && upd && has_blocks) { // clear all grass blocks when there is no more grass (:3938-3945)
+					uint8_t const *wt = d_weights + t*WT_TEX*WT_TEX*4;
+					bool grass = false;
+					for (unsigned k = 0; k < WT_TEX*WT_TEX && !grass; ++k) {grass = (wt[4*k + LT_GROUND] > 0);}
+					if (!grass) {for (unsigned b = 0; b < GRASS_BLOCK_DIM*GRASS_BLOCK_DIM; ++b) {bl[b] = grass_block_pod_t{0u, 0.0f, 0.0f};}}
+				}
+			}
+			d_updated[t] = upd ? 1 : 0;
+			for (int k = 0; k < 4; ++k) {d_ranges[4*t + k] = rg[k];}
+		});
 	}
 
 	// ================================================================ voxels (a14, a15, K8, K9)

@@ -518,6 +518,18 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// the grass brush: k_grass_brush_texels over (tile, window chunk) -- only when the brush has a radius -- then k_grass_brush_tiles once per tile
+	bool tile_edit_grass(terra::grass_brush_consts_t const &g, terra::landscape_consts_t const &c, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals, terra_tile_stats const *stats,
+		uint8_t const *distant, float const *params, uint32_t *w32, terra::grass_block_pod_t *blocks, uint8_t *flags, uint8_t *updated, uint32_t *ranges)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const chunks = (g.wx*g.wy + terra::GB_CHUNK - 1)/terra::GB_CHUNK;
+		if (g.rr > 0.0f && chunks) {hipLaunchKernelGGL(terra::k_grass_brush_texels, dim3(n, chunks), dim3(terra::GB_THREADS), 0, stream, g, c, refs, zvals, stats, params, w32, flags);}
+		hipLaunchKernelGGL(terra::k_grass_brush_tiles, dim3(n), dim3(terra::GB_THREADS), 0, stream, g, c, refs, zvals, stats, distant, w32, blocks, flags, updated, ranges);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

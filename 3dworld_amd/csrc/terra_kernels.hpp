@@ -1224,6 +1224,100 @@ __global__ __launch_bounds__(256) void k_tile_weights(landscape_consts_t c, tile
 	blocks[(size_t)t*GRASS_BLOCK_DIM*GRASS_BLOCK_DIM + (size_t)(band*(WK_BAND/GRASS_BLOCK_SZ) + byl)*GRASS_BLOCK_DIM + bx] = gb;
 }
 
+// ------------------------------------------------------------------ grass brush (tile_t::add_or_remove_grass_at, src/tiled_mesh.cpp:3845-3948) on the resident weights, two launches
+// k_grass_brush_texels: one block per (tile, GB_CHUNK texels of the tile's window).  The sphere test is the whole block's (a tile outside it leaves at once); two lanes
+// build the tile's serial x / y position sums in LDS; every window texel is edited and leaves its `updated` byte in flags[tile][window texel].
+constexpr uint32_t GB_THREADS = 256, GB_CHUNK = 1024;
+__global__ __launch_bounds__(GB_THREADS) void k_grass_brush_texels(grass_brush_consts_t g, landscape_consts_t c, tile_ref_pod_t const *__restrict__ refs, float const *__restrict__ zvals,
+	terra_tile_stats const *__restrict__ stats, float const *__restrict__ params, uint32_t *__restrict__ w32, uint8_t *__restrict__ flags)
+{
+	__shared__ float s_pos[2*WT_TEX];
+	uint32_t const t = blockIdx.x;
+	tile_ref_pod_t const r = refs[t];
+	if (!grass_tile_hit(g, r.tx, r.ty, stats[t].mzmin, stats[t].mzmax, stats[t].radius)) return;
+	if (threadIdx.x < 2) { // pt.x += DX_VAL / pt.y += DY_VAL from the tile's corner on (:3865-3869)
+		uint32_t const ax = threadIdx.x;
+		float v = ax ? grass_yval(g, r.ty*(int)WT_SIZE + g.dyoff) : grass_xval(g, r.tx*(int)WT_SIZE + g.dxoff);
+		float const step = ax ? g.DY_VAL : g.DX_VAL;
+		for (uint32_t k = 0; k < WT_TEX; ++k) {s_pos[ax*WT_TEX + k] = v; v += step;}
+	}
+	__syncthreads();
+	uint32_t const x0 = (uint32_t)grass_win0(g.px, s_pos[0], g.DX_VAL, g.hx, g.wx), y0 = (uint32_t)grass_win0(g.py, s_pos[WT_TEX], g.DY_VAL, g.hy, g.wy);
+	uint32_t const nwin = g.wx*g.wy;
+	float const *zt = zvals + (size_t)t*WT_ZV*WT_ZV, *prm = params + (size_t)t*12;
+	for (uint32_t k = 0; k < GB_CHUNK/GB_THREADS; ++k) {
+		uint32_t const p = blockIdx.y*GB_CHUNK + k*GB_THREADS + threadIdx.x;
+		if (p >= nwin) break;
+		uint32_t const yy = p/g.wx, x = x0 + (p - yy*g.wx), y = y0 + yy;
+		uint32_t *wp = w32 + ((size_t)t*WT_TEX + y)*WT_TEX + x;
+		uint32_t w = *wp;
+		unsigned const f = grass_texel(g, c, s_pos[x], s_pos[WT_TEX + y], w, zt, prm, x, y);
+		if (f) {*wp = w;}
+		flags[(size_t)t*nwin + p] = (uint8_t)f;
+	}
+}
+// k_grass_brush_tiles: one block per tile.  updated / ranges as reductions over the window's flags; on the add path the grass blocks under the window, each
+// scanning its 16 texels in row-major order; after a removal the has-grass scan of the whole tile, for a tile that was updated and had grass blocks.
+__global__ __launch_bounds__(GB_THREADS) void k_grass_brush_tiles(grass_brush_consts_t g, landscape_consts_t c, tile_ref_pod_t const *__restrict__ refs, float const *__restrict__ zvals,
+	terra_tile_stats const *__restrict__ stats, uint8_t const *__restrict__ distant, uint32_t const *__restrict__ w32, grass_block_pod_t *__restrict__ blocks,
+	uint8_t const *__restrict__ flags, uint8_t *__restrict__ updated, uint32_t *__restrict__ ranges)
+{
+	__shared__ uint32_t s_red[6]; // xl, yl, xh, yh, any updated texel, any grass / block
+	uint32_t const t = blockIdx.x;
+	tile_ref_pod_t const r = refs[t];
+	bool const hit = g.rr > 0.0f && grass_tile_hit(g, r.tx, r.ty, stats[t].mzmin, stats[t].mzmax, stats[t].radius);
+	if (!hit) {
+		if (threadIdx.x < 4) {ranges[4*t + threadIdx.x] = (threadIdx.x < 2) ? WT_SIZE : 0u;}
+		if (threadIdx.x == 0) {updated[t] = 0;}
+		return;
+	}
+	if (threadIdx.x < 6) {s_red[threadIdx.x] = (threadIdx.x < 2) ? WT_SIZE : 0u;}
+	__syncthreads();
+	uint32_t const x0 = (uint32_t)grass_win0(g.px, grass_xval(g, r.tx*(int)WT_SIZE + g.dxoff), g.DX_VAL, g.hx, g.wx);
+	uint32_t const y0 = (uint32_t)grass_win0(g.py, grass_yval(g, r.ty*(int)WT_SIZE + g.dyoff), g.DY_VAL, g.hy, g.wy);
+	uint32_t const wx = g.wx, wy = g.wy, nwin = wx*wy;
+	uint8_t const *fl = flags + (size_t)t*nwin;
+	uint32_t xl = WT_SIZE, yl = WT_SIZE, xh = 0, yh = 0, any = 0;
+	for (uint32_t p = threadIdx.x; p < nwin; p += GB_THREADS) {
+		if (!(fl[p] & 1u)) continue;
+		uint32_t const yy = p/wx, x = x0 + (p - yy*wx), y = y0 + yy;
+		any = 1;
+		xl = min_u32(xl, x); xh = max_u32(xh, min_u32(x + 1, WT_SIZE));
+		yl = min_u32(yl, y); yh = max_u32(yh, min_u32(y + 1, WT_SIZE));
+	}
+	if (any) {atomicMin(&s_red[0], xl); atomicMin(&s_red[1], yl); atomicMax(&s_red[2], xh); atomicMax(&s_red[3], yh); atomicOr(&s_red[4], 1u);}
+	__syncthreads();
+	bool const upd = s_red[4] != 0;
+	if (threadIdx.x < 4) {ranges[4*t + threadIdx.x] = (g.add && upd) ? s_red[threadIdx.x] : ((threadIdx.x < 2) ? WT_SIZE : 0u);}
+	if (threadIdx.x == 0) {updated[t] = upd ? 1 : 0;}
+	if (!upd) return;
+	grass_block_pod_t *bl = blocks + (size_t)t*GRASS_BLOCK_DIM*GRASS_BLOCK_DIM;
+	float const *zt = zvals + (size_t)t*WT_ZV*WT_ZV;
+	if (g.add) {
+		if ((distant && distant[t]) || !c.gen_grass_map) return;
+		uint32_t const xe = min_u32(x0 + wx, WT_SIZE), ye = min_u32(y0 + wy, WT_SIZE); // blocks cover texels 0 .. 127 (x >= size: no block)
+		if (x0 >= xe || y0 >= ye) return;
+		uint32_t const bx0 = x0/GRASS_BLOCK_SZ, by0 = y0/GRASS_BLOCK_SZ, nbx = (xe - 1)/GRASS_BLOCK_SZ - bx0 + 1, nby = (ye - 1)/GRASS_BLOCK_SZ - by0 + 1;
+		for (uint32_t b = threadIdx.x; b < nbx*nby; b += GB_THREADS) {
+			uint32_t const by = by0 + b/nbx, bx = bx0 + (b - (b/nbx)*nbx);
+			grass_block_pod_t gb = bl[by*GRASS_BLOCK_DIM + bx];
+			if (grass_block_merge(c, gb, zt, r.tx*(int)WT_SIZE, r.ty*(int)WT_SIZE, bx, by, [=] (unsigned x, unsigned y) {return x - x0 < wx && y - y0 < wy && (fl[(y - y0)*wx + (x - x0)] & 1u);})) {
+				bl[by*GRASS_BLOCK_DIM + bx] = gb;
+			}
+		}
+		return;
+	}
+	// removal: clear every block when no texel has grass left (:3938-3945), for a tile with a non-empty block array
+	uint32_t nonempty = 0;
+	for (uint32_t b = threadIdx.x; b < GRASS_BLOCK_DIM*GRASS_BLOCK_DIM; b += GB_THREADS) {nonempty |= (bl[b].ix != 0) ? 1u : 0u;}
+	if (__syncthreads_or((int)nonempty) == 0) return;
+	uint32_t const *wt = w32 + (size_t)t*WT_TEX*WT_TEX;
+	uint32_t grass = 0;
+	for (uint32_t k = threadIdx.x; k < WT_TEX*WT_TEX; k += GB_THREADS) {grass |= ((wt[k] >> (8*LT_GROUND)) & 0xFFu) ? 1u : 0u;}
+	if (__syncthreads_or((int)grass) != 0) return;
+	for (uint32_t b = threadIdx.x; b < GRASS_BLOCK_DIM*GRASS_BLOCK_DIM; b += GB_THREADS) {bl[b] = grass_block_pod_t{0u, 0.0f, 0.0f};}
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

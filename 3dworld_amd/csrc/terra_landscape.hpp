@@ -5,6 +5,7 @@
 // Same evaluation order and float/double promotions as the reference statements (x86-64 SSE2, no FMA).
 #pragma once
 #include "terra_common.hpp"
+#include "terra_modmap.hpp"
 
 namespace terra {
 
@@ -159,6 +160,119 @@ TERRA_HD grass_block_pod_t grass_block(landscape_consts_t const &c, float const 
 		}
 	}
 	return gb;
+}
+
+// ---- grass brush: tile_t::add_or_remove_grass_at (src/tiled_mesh.cpp:3845-3948) and add_grass_block_at (:1354-1371) on a tile's weights, in place.
+// The driver (tiles_edit_grass_dev) and the HIP kernels share these bodies; the order of every float operation is the reference statement's.
+struct grass_brush_consts_t {
+	float px, py, pz;               // p_int, camera space
+	float rr, r_inv, bweight;       // rradius; r_inv(1.0/rradius) and bweight(10.0*brush_weight): double expressions narrowed to float (:3859-3860)
+	float xss, yss, DX_VAL, DY_VAL; // get_xval(i) = -X_SCENE_SIZE + DX_VAL*i (src/mesh.h:122-123)
+	int add, shape, is_square, dxoff, dyoff;
+	uint32_t wx, wy; int hx, hy;    // every tile's texel window: wx x wy texels, hx / hy texels either side of the brush centre's texel
+	sin_lut_t L;
+};
+TERRA_HD float grass_xval(grass_brush_consts_t const &g, int i) {return -g.xss + g.DX_VAL*(float)i;}
+TERRA_HD float grass_yval(grass_brush_consts_t const &g, int i) {return -g.yss + g.DY_VAL*(float)i;}
+// tile_t::mesh_sphere_intersect (:3796-3799) for the tile (tx, ty) with the stats' mzmin / mzmax / radius
+TERRA_HD bool grass_tile_hit(grass_brush_consts_t const &g, int tx, int ty, float mzmin, float mzmax, float radius) {
+	int const x1 = tx*(int)WT_SIZE, y1 = ty*(int)WT_SIZE, x2 = x1 + (int)WT_SIZE, y2 = y1 + (int)WT_SIZE;
+	// dist_less_than(pos, get_center(), radius + rradius) (src/tiled_mesh.h:229-231, src/inlines.h:176-192)
+	float const cx = grass_xval(g, ((x1 + x2) >> 1) + g.dxoff), cy = grass_yval(g, ((y1 + y2) >> 1) + g.dyoff), cz = 0.5f*(mzmin + mzmax);
+	float const ex = g.px - cx, ey = g.py - cy, ez = g.pz - cz, dv = radius + g.rr;
+	if (!(ex*ex + ey*ey + ez*ez < dv*dv)) return false;
+	// sphere_cube_intersect(pos, rradius, get_mesh_bcube()) (src/Math3d.cpp:920-935, src/tiled_mesh.h:238-241; BCUBE_ZTOLER = 1e-6, :32)
+	float const xv1 = grass_xval(g, x1 + g.dxoff), yv1 = grass_yval(g, y1 + g.dyoff);
+	float const lo[3] = {xv1, yv1, mzmin - 1.0E-6f}, hi[3] = {xv1 + (float)(x2 - x1)*g.DX_VAL, yv1 + (float)(y2 - y1)*g.DY_VAL, mzmax + 1.0E-6f}, p[3] = {g.px, g.py, g.pz};
+	float const r2 = g.rr*g.rr;
+	float dmin = 0.0f;
+	for (int i = 0; i < 3; ++i) {
+		if      (p[i] < lo[i]) {float const d = p[i] - lo[i]; dmin += d*d;}
+		else if (p[i] > hi[i]) {float const d = p[i] - hi[i]; dmin += d*d;}
+		if (dmin > r2) return false;
+	}
+	return true;
+}
+// first texel of a tile's window along one axis (llc = the axis' first texel position): the brush centre's texel less h, kept inside [0, 129 - w].  Every texel
+// outside the window fails the loop's |pt - pos| > rradius test: h = ceil(rradius/step) + 1 leaves half a texel beyond the rounding of the centre
+TERRA_HD int grass_win0(float p, float llc, float step, int h, uint32_t w) {
+	float const c = (p - llc)/step;
+	int const ci = (c > -1000.0f && c < 1000.0f) ? (int)floorf(c + 0.5f) : ((c > 0.0f) ? 1000 : -1000);
+	return imax(0, imin(ci - h, (int)WT_TEX - (int)w));
+}
+TERRA_HD uint32_t min_u32(uint32_t a, uint32_t b) {return (b < a) ? b : a;}
+TERRA_HD uint32_t max_u32(uint32_t a, uint32_t b) {return (a < b) ? b : a;}
+TERRA_HD uint8_t uchar_x86(double v) {return (uint8_t)((v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN);} // (unsigned char)double: cvttsd2si, low byte
+// the loop body (:3866-3925) for texel (x, y) at pt = (ptx, pty): w = its RGBA word (written only when the texel is updated), zv = the tile's 130 x 130 zvals,
+// prm = its 12 biome parameters (read on the remove path only).  Returns 1 when the texel sets `updated`; on the add path that is when it reaches add_grass_block_at.
+TERRA_HD unsigned grass_texel(grass_brush_consts_t const &g, landscape_consts_t const &c, float ptx, float pty, uint32_t &w, float const *zv, float const *prm, unsigned x, unsigned y) {
+	float const ex = ptx - g.px, ey = pty - g.py;
+	if (fabsf(ey) > g.rr || fabsf(ex) > g.rr) return 0;
+	float const d2 = ex*ex + ey*ey; // p2p_dist_xy_sq(pt, pos) (src/inlines.h:183-185)
+	if (!g.is_square && !(d2 < g.rr*g.rr)) return 0; // dist_xy_less_than: round shapes
+	uint8_t b[4] = {(uint8_t)w, (uint8_t)(w >> 8), (uint8_t)(w >> 16), (uint8_t)(w >> 24)}; // {sand, dirt, grass, rock}: get_texture_ixs maps the textures in LT_* order
+	uint8_t &gw = b[LT_GROUND];
+	if (gw == (g.add ? 255 : 0)) return 0; // full / no grass here
+	float delta = g.bweight;
+	adjust_brush_weight(g.L, delta, sqrtf(d2)*g.r_inv, g.shape); // p2p_dist_xy(pt, pos)*r_inv
+	if (g.add) {
+		if ((double)delta >= 0.99) {b[LT_SAND] = b[LT_DIRT] = b[LT_ROCK] = 0; gw = 255;}
+		else if ((double)delta > 0.01) {
+			uint8_t const prev = gw;
+			gw = (uint8_t)f2i_x86(min_std(255.0f, (float)gw + 255.0f*delta));
+			uint8_t added = (uint8_t)(gw - prev);
+			for (unsigned i = 0; i < 4 && added > 0; ++i) { // remove other weights until the weights are balanced
+				if (i == LT_GROUND || b[i] == 0) continue;
+				uint8_t const num = (added < b[i]) ? added : b[i];
+				b[i] -= num; added -= num;
+			}
+		}
+	}
+	else {
+		uint8_t const prev = gw;
+		gw = (uint8_t)f2i_x86(max_std(0.0f, (float)gw - 255.0f*delta));
+		uint8_t const rem = (uint8_t)(prev - gw);
+		if (rem == 0) return 0;
+		unsigned const ix = y*WT_ZV + x;
+		float const mhmax = max4_std(corner_heights_t{zv[ix], zv[ix+1], zv[ix+WT_ZV], zv[ix+WT_ZV+1]});
+		int k1 = 0, k2 = 0;
+		float t = 0.0f;
+		get_tids(c, c.relh_adj_tex + (mhmax - c.zmin)*c.dz_inv, k1, k2, &t); // (outside a blend zone t = 0, so rem2 = 0 and k2 adds nothing)
+		uint8_t const rem2 = (uint8_t)f2i_x86(t*(float)rem), rem1 = (uint8_t)(rem - rem2);
+		if (k1 == LT_GROUND) {k1 = LT_DIRT;} // replace grass with dirt
+		if (k2 == LT_GROUND) {k2 = LT_DIRT;}
+		if (k2 < 4) {b[k2] += rem2;} // not snow
+		if (k1 < 4) {b[k1] += rem1;}
+		biome_corners_t bio;
+		for (int k = 0; k < 12; ++k) {bio.v[k] = prm[k];}
+		float const dirt_scale = biome_at(bio, 2, (float)x*(1.0f/128.0f), (float)y*(1.0f/128.0f)); // BILINEAR_INTERP(params, dirt, x*xy_mult, y*xy_mult)
+		if (dirt_scale < 1.0f) { // convert dirt to sand
+			b[LT_SAND] += uchar_x86((1.0 - (double)dirt_scale)*(double)b[LT_DIRT]);
+			b[LT_DIRT] = (uint8_t)f2i_x86(dirt_scale*(float)b[LT_DIRT]);
+		}
+	}
+	w = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+	return 1;
+}
+// add_grass_block_at for the texels of block (bx, by) that reached it (reached(x, y)), in the reference's row-major order; the first one picks the ix of a block
+// whose ix was 0.  Returns whether any texel reached the block.
+template<class R> TERRA_HD bool grass_block_merge(landscape_consts_t const &c, grass_block_pod_t &gb, float const *zv, int x1, int y1, unsigned bx, unsigned by, R const &reached) {
+	bool any = false;
+	for (unsigned y = by*GRASS_BLOCK_SZ; y < (by + 1)*GRASS_BLOCK_SZ; ++y) {
+		for (unsigned x = bx*GRASS_BLOCK_SZ; x < (bx + 1)*GRASS_BLOCK_SZ; ++x) {
+			if (!reached(x, y)) continue;
+			unsigned const ix = y*WT_ZV + x;
+			corner_heights_t const h{zv[ix], zv[ix+1], zv[ix+WT_ZV], zv[ix+WT_ZV+1]};
+			float const mhmin = min4_std(h), mhmax = max4_std(h);
+			if (gb.ix == 0) {
+				gb.ix = ((((uint32_t)x1 + x) + 1567u*((uint32_t)y1 + y)) % c.num_rnd_grass_blocks) + 1; // int + unsigned: unsigned arithmetic
+				gb.zmin = mhmin; gb.zmax = mhmax;
+			}
+			else {gb.zmin = min_std(gb.zmin, mhmin); gb.zmax = max_std(gb.zmax, mhmax);}
+			any = true;
+		}
+	}
+	return any;
 }
 
 } // namespace terra

@@ -14,6 +14,13 @@ enum {BSHAPE_CONST_SQ = 0, BSHAPE_CNST_CIR, BSHAPE_LINEAR, BSHAPE_QUADRATIC, BSH
 struct hmap_brush_pod_t {int32_t x, y; uint32_t radius; int32_t delta; int16_t shape;}; // tex_mod_map_manager_t::hmap_brush_t (src/heightmap.h:71-76), 20 bytes in the file
 struct hmap_mod_pod_t {uint16_t x, y; int32_t delta;};                                  // mod_elem_t (src/heightmap.h:59-64), 8 bytes
 static_assert(sizeof(hmap_brush_pod_t) == 20 && sizeof(hmap_mod_pod_t) == 8, "mod file record layout");
+// adjust_brush_weight (src/heightmap.cpp:27-33): PI is the float 3.141592654f, SINF / COSF the table look-ups; constant shapes leave delta as it is
+TERRA_HD void adjust_brush_weight(sin_lut_t const &L, float &delta, float dval, int shape) {
+	if      (shape == BSHAPE_LINEAR   ) {delta *= 1.0f - dval;}
+	else if (shape == BSHAPE_QUADRATIC) {delta *= 1.0f - dval*dval;}
+	else if (shape == BSHAPE_COSINE   ) {delta *= L.COSF(0.5f*PI_F*dval);}
+	else if (shape == BSHAPE_SINE     ) {delta *= 0.5f*(1.0f + L.SINF(PI_F*dval + 0.5f*PI_F));}
+}
 
 // heightmap_t::modify_heightmap_value on an image other threads edit too: a compare-and-swap on the containing 32-bit word.  Within one brush every
 // delta has the sign of the brush's delta (the weights are >= 0) and saturating adds of same-signed values commute, flatten brushes store one value,

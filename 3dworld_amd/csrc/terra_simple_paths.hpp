@@ -153,6 +153,9 @@ template<class DERIVED> struct simple_paths {
 	void tile_post_pass(uint32_t n, tile_ref_pod_t const *d_refs, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz,
 		float wpz_max, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {tile_post_simple(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxy, S);}
 	void tile_ao_pass(uint32_t n, float const *d_zvals, float const *d_ctx, uint8_t *d_ao, float dz, bool own, uint32_t S) {tile_ao_simple(n, d_zvals, d_ctx, d_ao, dz, own, S);}
+	// the grass brush's kernels: none here -- the driver (tiles_edit_grass_dev) then runs its per-texel / per-block / per-tile form
+	bool tile_edit_grass(grass_brush_consts_t const &, landscape_consts_t const &, tile_ref_pod_t const *, uint32_t, float const *, terra_tile_stats const *, uint8_t const *,
+		float const *, uint32_t *, grass_block_pod_t *, uint8_t *, uint8_t *, uint32_t *) {return false;}
 	// tile erosion, wave form: the clamp-padded copies live in HBM/L2, ONE WAVE per tile walks the droplets in order through a 32x32 LDS window
 	// (10 KB of LDS per tile instead of 76 KB: ~15 tiles per CU in flight instead of 2)
 	void tile_erosion_windowed(uint32_t n, float *zvals, erosion_consts_t const &ec, uint32_t iters, float *padded /* n*NX*NY */) {

@@ -55,6 +55,15 @@ MOD_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("delta", np.int32)]) 
 GRASS_BLOCK_DTYPE = np.dtype([("ix", np.uint32), ("zmin", np.float32), ("zmax", np.float32)])  # terra_grass_block
 
 
+class GRASS_BRUSH(C.Structure):
+    """terra_grass_brush: one stroke of the fire modes "Add Grass" / "Remove Grass" (tile_t::add_or_remove_grass_at's arguments)"""
+    _fields_ = [("pos", C.c_float * 3), ("radius", C.c_float), ("add_grass", C.c_int32), ("shape", C.c_int32), ("brush_weight", C.c_float)]
+
+
+def make_grass_brush(pos, radius, add_grass, shape, brush_weight):
+    return GRASS_BRUSH((C.c_float * 3)(*pos), radius, int(bool(add_grass)), shape, brush_weight)
+
+
 class ErosionReport(C.Structure):  # terra_erosion_report
     _fields_ = [("droplets", C.c_uint32), ("windows", C.c_uint32), ("rounds", C.c_uint32), ("traces", C.c_uint32),
                 ("serial_fallbacks", C.c_uint32), ("nan_droplets", C.c_uint32), ("steps", C.c_uint64), ("traced_steps", C.c_uint64),
@@ -180,6 +189,8 @@ _PROTOS = {
     "terra_tiles_terrain_params": (_i32, [_vp, _vp, _u32, _vp]),
     "terra_tiles_create_weights_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_create_weights": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "terra_tiles_edit_grass_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_edit_grass": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -580,6 +591,21 @@ class Terra:
         self._ck(self.lib.terra_tiles_create_weights(self.ctx, txy.ctypes.data, n, z.ctypes.data, w.ctypes.data, gb.ctypes.data, hg.ctypes.data))
         return w, gb, hg.astype(bool)
 
+    def tiles_edit_grass(self, tile_xy, zvals, stats, brush, weights, blocks, dxoff=0, dyoff=0, is_distant=None):
+        """tile_t::add_or_remove_grass_at on every tile of host arrays: weights (u8 [n,129,129,4]) and blocks ([n,32,32] GRASS_BLOCK_DTYPE) are edited in place;
+        stats: the TileStats of tiles_create_zvals (a ctypes array); brush: GRASS_BRUSH.  -> (updated bool [n], ranges u32 [n,4] = xl, yl, xh, yh)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        z = np.ascontiguousarray(zvals, np.float32).reshape(n, 130, 130)
+        assert weights.flags["C_CONTIGUOUS"] and weights.dtype == np.uint8 and weights.shape == (n, 129, 129, 4)
+        assert blocks.flags["C_CONTIGUOUS"] and blocks.dtype == GRASS_BLOCK_DTYPE and blocks.shape == (n, 32, 32)
+        st = (TileStats * n).from_buffer_copy(bytes(memoryview(stats).cast("B"))[:n * C.sizeof(TileStats)])
+        dist = None if is_distant is None else np.ascontiguousarray(is_distant, np.uint8).reshape(n)
+        upd = np.empty(n, np.uint8); rg = np.empty((n, 4), np.uint32)
+        self._ck(self.lib.terra_tiles_edit_grass(self.ctx, txy.ctypes.data, n, dxoff, dyoff, z.ctypes.data, C.addressof(st), None if dist is None else dist.ctypes.data,
+                                                 C.byref(brush), weights.ctypes.data, blocks.ctypes.data, upd.ctypes.data, rg.ctypes.data))
+        return upd.astype(bool), rg
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -700,6 +726,12 @@ class Terra:
     def tiles_create_weights_dev(self, tile_xy, z_ptr, weights_ptr, blocks_ptr=None, has_grass_ptr=None):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_create_weights_dev(self.ctx, txy.ctypes.data, len(txy), z_ptr, weights_ptr, blocks_ptr, has_grass_ptr))
+
+    def tiles_edit_grass_dev(self, tile_xy, z_ptr, stats_ptr, brush, weights_ptr, blocks_ptr, updated_ptr, ranges_ptr=None, dxoff=0, dyoff=0, distant_ptr=None):
+        """the grass brush on device-resident weights / grass blocks, in place; updated_ptr: n bytes, ranges_ptr: n x 4 uint32 (or None).  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_edit_grass_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, z_ptr, stats_ptr, distant_ptr, C.byref(brush),
+                                                     weights_ptr, blocks_ptr, updated_ptr, ranges_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

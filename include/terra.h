@@ -345,7 +345,7 @@ int  terra_write_mesh(const char *filename, const float *h_mesh, uint32_t nx, ui
  * loop would read past the zvals there); otherwise every tile call is TERRA_ERR_ARG.  At S != 128 these entry points follow S: terra_tiles_create_zvals[_dev]
  * (all three field sources: procedural, the AO-context clip, the heightmap texture), terra_tiles_post[_dev], terra_tiles_ao_lighting[_dev],
  * terra_tiles_mesh_shadows[_dev] and terra_multi_tiles_create_zvals[_dev].  These are TERRA_ERR_ARG at S != 128 for now: terra_tiles_terrain_params,
- * terra_tiles_create_weights[_dev], terra_tiles_mesh_shadows_halo_dev / _edges_dev, terra_multi_tiles_mesh_shadows[_dev] and terra_multi_shadow_layout.
+ * terra_tiles_create_weights[_dev], terra_tiles_edit_grass[_dev], terra_tiles_mesh_shadows_halo_dev / _edges_dev, terra_multi_tiles_mesh_shadows[_dev] and terra_multi_shadow_layout.
  * terra_tile_size: *size = S of the scene in force (TERRA_ERR_ARG when the scene's S is not supported, TERRA_ERR_STATE before terra_init_scene).
  * tile_xy: n pairs (tile x, tile y) on the HOST.  d_zvals: n zvals.  d_stats: n terra_tile_stats (optional).
  * d_normals: n normals (optional); d_min_normal_z: n floats (optional). */
@@ -425,6 +425,29 @@ int  terra_get_landscape(terra_ctx *ctx, terra_landscape *out);
 int  terra_tiles_terrain_params(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, float *h_params);
 int  terra_tiles_create_weights_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_weights, terra_grass_block *d_grass_blocks, uint8_t *d_has_any_grass);
 int  terra_tiles_create_weights(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *h_zvals, uint8_t *h_weights, terra_grass_block *h_grass_blocks, uint8_t *h_has_any_grass);
+/* ---- grass brush on those weights (tile size 128 only): the fire modes "Add Grass" / "Remove Grass" (inf_terrain_fire_weapon, src/tiled_mesh.cpp:4004-4011) ->
+ * tile_draw_t::add_or_remove_grass_at (:3771-3774) -> tile_t::add_or_remove_grass_at (:3845-3948) on every tile of the batch, in place.  Per tile the call does
+ * everything from :3847 on: the rradius == 0 test, mesh_sphere_intersect (:3796-3799), the texel loop, add_grass_block_at (:1354-1371, with its is_distant /
+ * x >= size / gen_grass_map() early-outs) and, after a removal, the has-grass scan that clears every grass block (:3938-3945).  The caller keeps the early
+ * returns for "texture not generated" and weights_tsize != stride (city tiles) and the follow-ups flowers.update_subrange / create_or_update_weight_tex, for
+ * which updated[t] (0 / 1) and ranges[t] = {xl, yl, xh, yh} are returned (add only; they start denormalised at {128, 128, 0, 0}, as at :3863).
+ * dxoff / dyoff = xoff - xoff2 / yoff - yoff2.  stats: what terra_tiles_create_zvals returned (mzmin, mzmax and radius are read; the engine may have enlarged radius
+ * for trees).  is_distant: [n] bytes or NULL (none distant).  Layouts of terra_tiles_create_weights: weights [n][129][129][4] (4-byte aligned), grass blocks
+ * [n][32][32]: a tile whose blocks all have ix == 0 has an empty grass_blocks vector, cleared blocks become {0, 0, 0}.  has_any_grass is not touched (the
+ * reference does not touch it either).  The biome parameters of the dirt scale (:3917) are generated internally.  ranges may be NULL. */
+typedef struct terra_grass_brush {
+	float pos[3];       /* p_int, camera space */
+	float radius;       /* rradius = (bradius + 0.5)*HALF_DXY, computed by the caller */
+	int32_t add_grass;  /* FM_ADD_GRASS (1) vs FM_REM_GRASS (0) */
+	int32_t shape;      /* TERRA_BSHAPE_* */
+	float brush_weight; /* cur_brush_param.get_delta_mag() */
+} terra_grass_brush;
+int  terra_tiles_edit_grass_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff,
+                                const float *d_zvals, const terra_tile_stats *d_stats, const uint8_t *d_is_distant, const terra_grass_brush *brush,
+                                uint8_t *d_weights, terra_grass_block *d_grass_blocks, uint8_t *d_updated, uint32_t *d_ranges);
+int  terra_tiles_edit_grass(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff,
+                            const float *h_zvals, const terra_tile_stats *h_stats, const uint8_t *h_is_distant, const terra_grass_brush *brush,
+                            uint8_t *h_weights, terra_grass_block *h_grass_blocks, uint8_t *h_updated, uint32_t *h_ranges);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

@@ -181,6 +181,16 @@ inline void set_landscape(terra_landscape const &params) {check(terra_set_landsc
 inline void tiles_create_weights(int const *tile_xy, unsigned n, float const *zvals, unsigned char *mesh_weight_data, terra_grass_block *grass_blocks, unsigned char *has_any_grass) {
 	check(terra_tiles_create_weights(default_ctx(), tile_xy, n, zvals, mesh_weight_data, grass_blocks, has_any_grass), "create_texture");
 }
+// tile_draw_t::add_or_remove_grass_at (src/tiled_mesh.cpp:3771-3774): tile_t::add_or_remove_grass_at on every tile of a batch whose weights / grass blocks the
+// caller holds (tiles_create_weights' layouts), in place; dxoff / dyoff = xoff - xoff2 / yoff - yoff2; is_distant and ranges may be null.  updated[t] / ranges[t]
+// = {xl, yl, xh, yh} drive the caller's flowers.update_subrange and create_or_update_weight_tex
+inline void tiles_add_or_remove_grass_at(int const *tile_xy, unsigned n, int dxoff, int dyoff, float const *zvals, terra_tile_stats const *stats, unsigned char const *is_distant,
+	float const pos[3], float rradius, bool add_grass, int brush_shape, float brush_weight, unsigned char *mesh_weight_data, terra_grass_block *grass_blocks,
+	unsigned char *updated, unsigned *ranges = nullptr)
+{
+	terra_grass_brush const b = {{pos[0], pos[1], pos[2]}, rradius, add_grass ? 1 : 0, brush_shape, brush_weight};
+	check(terra_tiles_edit_grass(default_ctx(), tile_xy, n, dxoff, dyoff, zvals, stats, is_distant, &b, mesh_weight_data, grass_blocks, updated, ranges), "add_or_remove_grass_at");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
