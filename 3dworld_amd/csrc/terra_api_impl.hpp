@@ -604,6 +604,37 @@ int terra_tiles_edit_grass(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 		if (h_ranges) {be.d2h(h_ranges, d + orr, rb);}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_line_hit) == 32 && sizeof(terra::line_hit_pod_t) == 32, "terra_line_hit layout");
+int terra_tiles_line_intersect_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *d_zvals, const terra_tile_stats *d_stats,
+                                   const uint8_t *d_is_distant, const float *d_lines, const int32_t *d_line_tile, uint32_t nlines, terra_line_hit *d_hits) {
+	TERRA_CHECK_CTX if ((n && (!tile_xy || !d_zvals || !d_stats)) || (nlines && (!d_lines || !d_hits))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_line_intersect_dev(tile_xy, n, dxoff, dyoff, d_zvals, d_stats, d_is_distant, d_lines, d_line_tile, nlines, (terra::line_hit_pod_t *)d_hits); TERRA_CATCH
+}
+int terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *h_zvals, const terra_tile_stats *h_stats,
+                               const uint8_t *h_is_distant, const float *h_lines, const int32_t *h_line_tile, uint32_t nlines, terra_line_hit *h_hits) {
+	TERRA_CHECK_CTX if ((n && (!tile_xy || !h_zvals || !h_stats)) || (nlines && (!h_lines || !h_hits))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size(); // (before the arrays are read: they are sized by S)
+		if (h_line_tile) {
+			for (uint32_t r = 0; r < nlines; ++r) {if (h_line_tile[r] >= 0 && (uint32_t)h_line_tile[r] >= n) {return terra::fail(TERRA_ERR_ARG, "tiles_line_intersect: line_tile entry out of range");}}
+		}
+		if (nlines == 0) return TERRA_OK;
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const S = ctx->eng.tile_size();
+		size_t const zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*sizeof(terra_tile_stats), db = n, lb = (size_t)nlines*24, tb = (size_t)nlines*4, hb = (size_t)nlines*32;
+		size_t const oz = 0, os = oz + up(zb), od = os + up(sb), ol = od + up(db), ot = ol + up(lb), oh = ot + up(tb);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oh + up(hb));
+		if (n) {be.h2d(d + oz, h_zvals, zb); be.h2d(d + os, h_stats, sb);}
+		if (n && h_is_distant) {be.h2d(d + od, h_is_distant, db);}
+		be.h2d(d + ol, h_lines, lb);
+		if (h_line_tile) {be.h2d(d + ot, h_line_tile, tb);}
+		ctx->eng.tiles_line_intersect_dev(tile_xy, n, dxoff, dyoff, (float const *)(d + oz), (terra_tile_stats const *)(d + os), h_is_distant ? d + od : nullptr,
+			(float const *)(d + ol), h_line_tile ? (int32_t const *)(d + ot) : nullptr, nlines, (terra::line_hit_pod_t *)(d + oh));
+		be.d2h(h_hits, d + oh, hb);
+	TERRA_CATCH
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

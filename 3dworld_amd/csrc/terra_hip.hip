@@ -530,6 +530,23 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// the line queries: k_line_boxes once per tile, then k_line_intersect once per line, in launches of fewer than 2^32 / LI_THREADS lines (HIP's limit on the
+	// work-items of one grid dimension)
+	bool tile_line_intersect(terra::line_query_consts_t const &c, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals, terra_tile_stats const *stats,
+		uint8_t const *distant, terra::line_box_t *boxes, float const *lines, int32_t const *line_tile, uint32_t nlines, terra::line_hit_pod_t *hits)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		if (n) {hipLaunchKernelGGL(terra::k_line_boxes, dim3((n + 255)/256), dim3(256), 0, stream, c, refs, stats, distant, n, boxes);}
+		uint32_t const per = (0xFFFFFFFFu/terra::LI_THREADS) & ~255u;
+		for (uint32_t r0 = 0; r0 < nlines;) {
+			uint32_t const m = terra::min_u32(per, nlines - r0);
+			hipLaunchKernelGGL(terra::k_line_intersect, dim3(m), dim3(terra::LI_THREADS), 0, stream, c, zvals, boxes, n, lines + (size_t)6*r0, line_tile ? line_tile + r0 : nullptr, hits + r0);
+			r0 += m;
+		}
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

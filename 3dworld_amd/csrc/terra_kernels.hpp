@@ -1318,6 +1318,78 @@ __global__ __launch_bounds__(GB_THREADS) void k_grass_brush_tiles(grass_brush_co
 	for (uint32_t b = threadIdx.x; b < GRASS_BLOCK_DIM*GRASS_BLOCK_DIM; b += GB_THREADS) {bl[b] = grass_block_pod_t{0u, 0.0f, 0.0f};}
 }
 
+// ------------------------------------------------------------------ line-vs-terrain hits (tile_draw_t::line_intersect_mesh, src/tiled_mesh.cpp:3582-3605), two launches
+// k_line_boxes: every tile's get_mesh_bcube() and first cell, 32 bytes, once per call.  A distant tile gets the z range [+inf, -inf]: both ends of every finite line
+// are below it, so the clip rejects the tile (:2178).
+__global__ __launch_bounds__(256) void k_line_boxes(line_query_consts_t c, tile_ref_pod_t const *__restrict__ refs, terra_tile_stats const *__restrict__ stats,
+	uint8_t const *__restrict__ distant, uint32_t n, line_box_t *__restrict__ boxes)
+{
+	uint32_t const i = blockIdx.x*256u + threadIdx.x;
+	if (i >= n) return;
+	line_box_t b = line_tile_box(c, refs[i].tx, refs[i].ty, stats[i].mzmin, stats[i].mzmax);
+	if (distant && distant[i]) {b.d[2][0] = INFINITY; b.d[2][1] = -INFINITY;}
+	boxes[i] = b;
+}
+// k_line_intersect: one workgroup per line.  The batch is culled in rounds of LI_ROUND tiles, LI_PER exact clips per thread; the tiles that pass go to an LDS list and
+// are walked one per thread, in parallel.  (A parallel cull rather than a walk of the batch's tile grid: a batch is any list of tiles -- gaps, any order, the same
+// tile twice -- and the tie rule follows the batch index, so a grid walk would first need a per-call map from tile coordinates to batch indices.)  Each thread keeps its best (t, batch index); the workgroup takes their lexicographic minimum as one 64-bit key (hits have
+// 0 <= t <= 1, whose float bits order as the values do once -0 is read as +0), and the thread that holds it writes the record.
+constexpr uint32_t LI_THREADS = 256, LI_PER = 4, LI_ROUND = LI_THREADS*LI_PER;
+// a tile's box into registers with two 16-byte loads, before the clip's branches (which would otherwise fetch its fields one at a time)
+TERRA_D line_box_t line_box_load(line_box_t const *p) {
+	uint4 const a = ((uint4 const *)p)[0], b = ((uint4 const *)p)[1];
+	uint32_t const w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+	line_box_t r;
+	memcpy(&r, w, sizeof(r));
+	return r;
+}
+__global__ __launch_bounds__(LI_THREADS) void k_line_intersect(line_query_consts_t c, float const *__restrict__ zvals, line_box_t const *__restrict__ boxes, uint32_t n,
+	float const *__restrict__ lines, int32_t const *__restrict__ line_tile, line_hit_pod_t *__restrict__ hits)
+{
+	__shared__ uint32_t s_list[LI_ROUND];
+	__shared__ uint32_t s_cnt;
+	__shared__ unsigned long long s_best;
+	uint32_t const r = blockIdx.x;
+	float const *L = lines + (size_t)6*r;
+	shadow_pt_t const v1 = {L[0], L[1], L[2]}, v2 = {L[3], L[4], L[5]};
+	uint32_t i0, i1;
+	line_tile_range(line_tile ? line_tile[r] : -1, n, line_finite(v1, v2), i0, i1);
+	size_t const zn = (size_t)(c.S + 2)*(c.S + 2);
+	unsigned long long best = ~0ull;
+	float bt = 0.0f; int bx = 0, by = 0;
+	if (threadIdx.x == 0) {s_best = ~0ull;}
+	for (uint32_t base = i0; base < i1; base += LI_ROUND) {
+		if (threadIdx.x == 0) {s_cnt = 0;}
+		__syncthreads();
+		for (uint32_t k = 0; k < LI_PER; ++k) {
+			uint32_t const i = base + k*LI_THREADS + threadIdx.x;
+			if (i < i1 && line_box_clip(line_box_load(boxes + i), v1, v2)) {s_list[atomicAdd(&s_cnt, 1u)] = i;}
+		}
+		__syncthreads();
+		uint32_t const cnt = s_cnt;
+		for (uint32_t j = threadIdx.x; j < cnt; j += LI_THREADS) {
+			uint32_t const i = s_list[j];
+			float t = 1.0f; int ix = 0, iy = 0;
+			if (!line_tile_hit(c, line_box_load(boxes + i), v1, v2, zvals + i*zn, t, ix, iy)) continue;
+			uint32_t tb = __float_as_uint(t);
+			if (tb == 0x80000000u) {tb = 0u;}
+			unsigned long long const key = ((unsigned long long)tb << 32) | i;
+			if (key < best) {best = key; bt = t; bx = ix; by = iy;}
+		}
+		__syncthreads(); // (the next round rewrites s_cnt / s_list)
+	}
+	if (best != ~0ull) {atomicMin(&s_best, best);}
+	__syncthreads();
+	unsigned long long const win = s_best;
+	if (win == ~0ull) {
+		if (threadIdx.x == 0) {hits[r] = line_miss();}
+	}
+	else if (best == win) {
+		uint32_t const i = (uint32_t)win;
+		hits[r] = line_hit_make(v1, v2, bt, i, boxes[i], bx, by);
+	}
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

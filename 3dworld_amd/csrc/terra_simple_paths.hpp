@@ -156,6 +156,9 @@ template<class DERIVED> struct simple_paths {
 	// the grass brush's kernels: none here -- the driver (tiles_edit_grass_dev) then runs its per-texel / per-block / per-tile form
 	bool tile_edit_grass(grass_brush_consts_t const &, landscape_consts_t const &, tile_ref_pod_t const *, uint32_t, float const *, terra_tile_stats const *, uint8_t const *,
 		float const *, uint32_t *, grass_block_pod_t *, uint8_t *, uint8_t *, uint32_t *) {return false;}
+	// the line queries' kernels: none here -- the driver (tiles_line_intersect_dev) then runs its one-thread-per-line form
+	bool tile_line_intersect(line_query_consts_t const &, tile_ref_pod_t const *, uint32_t, float const *, terra_tile_stats const *, uint8_t const *, line_box_t *,
+		float const *, int32_t const *, uint32_t, line_hit_pod_t *) {return false;}
 	// tile erosion, wave form: the clamp-padded copies live in HBM/L2, ONE WAVE per tile walks the droplets in order through a 32x32 LDS window
 	// (10 KB of LDS per tile instead of 76 KB: ~15 tiles per CU in flight instead of 2)
 	void tile_erosion_windowed(uint32_t n, float *zvals, erosion_consts_t const &ec, uint32_t iters, float *padded /* n*NX*NY */) {

@@ -53,6 +53,8 @@ def make_landscape(vegetation=1.0, temperature=20.0, biome_x_offset=0.0, mesh_sc
 BRUSH_DTYPE = np.dtype({"names": ["x", "y", "radius", "delta", "shape"], "formats": [np.int32, np.int32, np.uint32, np.int32, np.int16], "itemsize": 20})  # terra_hmap_brush
 MOD_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("delta", np.int32)])  # terra_hmap_mod
 GRASS_BLOCK_DTYPE = np.dtype([("ix", np.uint32), ("zmin", np.float32), ("zmax", np.float32)])  # terra_grass_block
+LINE_HIT_DTYPE = np.dtype([("t", np.float32), ("tile", np.int32), ("xpos", np.int32), ("ypos", np.int32), ("p_int", np.float32, (3,)), ("hit", np.uint32)])  # terra_line_hit
+assert LINE_HIT_DTYPE.itemsize == 32
 
 
 class GRASS_BRUSH(C.Structure):
@@ -191,6 +193,8 @@ _PROTOS = {
     "terra_tiles_create_weights": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_edit_grass_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_edit_grass": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_line_intersect_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_line_intersect": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -606,6 +610,22 @@ class Terra:
                                                  C.byref(brush), weights.ctypes.data, blocks.ctypes.data, upd.ctypes.data, rg.ctypes.data))
         return upd.astype(bool), rg
 
+    def tiles_line_intersect(self, tile_xy, zvals, stats, lines, line_tile=None, dxoff=0, dyoff=0, is_distant=None):
+        """tile_draw_t::line_intersect_mesh (inc_trees = 0) of every line against host arrays: zvals ([n,S+2,S+2]), stats (the TileStats of tiles_create_zvals),
+        lines ([nlines,2,3] = v1, v2); line_tile ([nlines], or None): >= 0 restricts a line to that batch tile.  -> LINE_HIT_DTYPE [nlines]"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        S = self.tile_size
+        z = np.ascontiguousarray(zvals, np.float32).reshape(n, S + 2, S + 2)
+        st = (TileStats * n).from_buffer_copy(bytes(memoryview(stats).cast("B"))[:n * C.sizeof(TileStats)]) if n else None
+        ln = np.ascontiguousarray(lines, np.float32).reshape(-1, 2, 3)
+        lt = None if line_tile is None else np.ascontiguousarray(line_tile, np.int32).reshape(len(ln))
+        dist = None if is_distant is None else np.ascontiguousarray(is_distant, np.uint8).reshape(n)
+        hits = np.zeros(len(ln), LINE_HIT_DTYPE)
+        self._ck(self.lib.terra_tiles_line_intersect(self.ctx, txy.ctypes.data, n, dxoff, dyoff, z.ctypes.data, C.addressof(st) if n else None,
+                                                     None if dist is None else dist.ctypes.data, ln.ctypes.data, None if lt is None else lt.ctypes.data, len(ln), hits.ctypes.data))
+        return hits
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -732,6 +752,12 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_edit_grass_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, z_ptr, stats_ptr, distant_ptr, C.byref(brush),
                                                      weights_ptr, blocks_ptr, updated_ptr, ranges_ptr))
+
+    def tiles_line_intersect_dev(self, tile_xy, z_ptr, stats_ptr, lines_ptr, nlines, hits_ptr, line_tile_ptr=None, dxoff=0, dyoff=0, distant_ptr=None):
+        """line hits against a device-resident batch: lines_ptr [nlines][2][3] floats, hits_ptr nlines x LINE_HIT_DTYPE, line_tile_ptr [nlines] int32 (or None).  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_line_intersect_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, z_ptr, stats_ptr, distant_ptr, lines_ptr, line_tile_ptr,
+                                                         nlines, hits_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

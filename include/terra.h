@@ -344,7 +344,7 @@ int  terra_write_mesh(const char *filename, const float *h_mesh, uint32_t nx, ui
  * Supported: 16 <= S <= 1024; S other than 128 also needs mesh_x == mesh_y (the reference asserts it in tiled mode) and S != 4k + 2 (the reference's sub-block
  * loop would read past the zvals there); otherwise every tile call is TERRA_ERR_ARG.  At S != 128 these entry points follow S: terra_tiles_create_zvals[_dev]
  * (all three field sources: procedural, the AO-context clip, the heightmap texture), terra_tiles_post[_dev], terra_tiles_ao_lighting[_dev],
- * terra_tiles_mesh_shadows[_dev] and terra_multi_tiles_create_zvals[_dev].  These are TERRA_ERR_ARG at S != 128 for now: terra_tiles_terrain_params,
+ * terra_tiles_mesh_shadows[_dev], terra_tiles_line_intersect[_dev] and terra_multi_tiles_create_zvals[_dev].  These are TERRA_ERR_ARG at S != 128 for now: terra_tiles_terrain_params,
  * terra_tiles_create_weights[_dev], terra_tiles_edit_grass[_dev], terra_tiles_mesh_shadows_halo_dev / _edges_dev, terra_multi_tiles_mesh_shadows[_dev] and terra_multi_shadow_layout.
  * terra_tile_size: *size = S of the scene in force (TERRA_ERR_ARG when the scene's S is not supported, TERRA_ERR_STATE before terra_init_scene).
  * tile_xy: n pairs (tile x, tile y) on the HOST.  d_zvals: n zvals.  d_stats: n terra_tile_stats (optional).
@@ -448,6 +448,35 @@ int  terra_tiles_edit_grass_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t
 int  terra_tiles_edit_grass(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff,
                             const float *h_zvals, const terra_tile_stats *h_stats, const uint8_t *h_is_distant, const terra_grass_brush *brush,
                             uint8_t *h_weights, terra_grass_block *h_grass_blocks, uint8_t *h_updated, uint32_t *h_ranges);
+
+/* ---- line-vs-terrain hits on a tile batch (every supported tile size S): what aims the terrain fire modes (inf_terrain_fire_weapon, src/tiled_mesh.cpp:3983-4020)
+ * and serves projectiles, animals' sight lines and cars.  Per line: tile_draw_t::line_intersect_mesh (:3582-3605) with inc_trees = 0 -> tile_t::line_intersect_mesh
+ * (:2176-2213) on every tile, bit for bit; p_int = v1 + t*(v2 - v1) as line_intersect_tiled_mesh_get_tile (:3643-3648) computes it.
+ * tile_xy: n pairs on the HOST.  dxoff / dyoff = xoff - xoff2 / yoff - yoff2.  zvals [n][S+2][S+2] and stats (mzmin / mzmax are read) as terra_tiles_create_zvals
+ * returned them.  is_distant: [n] bytes or NULL (none distant); a distant tile never hits (:2178).  lines: [nlines][2][3] = v1, v2 in camera space.
+ * line_tile: [nlines] or NULL; line_tile[r] >= 0 tests line r against that batch tile alone (tile_t::line_intersect_mesh, as animals.cpp calls it), a negative entry
+ * against the whole batch.  The host form refuses an entry >= n (TERRA_ERR_ARG); the device form cannot read it up front, there such a line is a miss.
+ * hits: one record per line.  A hit: t = the winning tn, tile = its batch index, (xpos, ypos) = (x1 + ix, y1 + iy), global mesh indices without the scroll offset as
+ * the reference's, and hit = 1.  A miss: {t = 2, tile = -1, xpos = ypos = 0, p_int = {0, 0, 0}, hit = 0}.
+ * Ties: over the tiles the reference keeps the first strictly smaller tn of its unordered_map's iteration order; here equal t go to the lowest batch index, so an
+ * engine that passes its tiles in that iteration order gets the identical tile (tiles share their edge row and column: ties do happen).
+ * Where the reference asserts, a line misses: a non-finite coordinate (:2179), and steps >= 10000 in a tile (:2187), which only a line longer than 10000 cells can
+ * reach, when its clip leaves v2 where it was (tmax <= TOLERANCE).  A horizontal line never hits (its cur_t divides by v2.z - v1.z = 0), as in the reference.
+ * TERRA_ERR_STATE before terra_init_scene; TERRA_ERR_ARG for an unsupported S or a NULL required pointer (tile_xy, zvals, stats when n > 0; lines, hits when
+ * nlines > 0).  n == 0 writes misses; nlines == 0 does nothing.  The device form only enqueues. */
+typedef struct terra_line_hit {
+	float t;            /* cur_t of the winning tile, 2 on a miss */
+	int32_t tile;       /* batch index, -1 on a miss */
+	int32_t xpos, ypos; /* mesh indices of the hit cell */
+	float p_int[3];     /* v1 + t*(v2 - v1) */
+	uint32_t hit;       /* 0 / 1 */
+} terra_line_hit;       /* 32 bytes */
+int  terra_tiles_line_intersect_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff,
+                                    const float *d_zvals, const terra_tile_stats *d_stats, const uint8_t *d_is_distant,
+                                    const float *d_lines, const int32_t *d_line_tile, uint32_t nlines, terra_line_hit *d_hits);
+int  terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff,
+                                const float *h_zvals, const terra_tile_stats *h_stats, const uint8_t *h_is_distant,
+                                const float *h_lines, const int32_t *h_line_tile, uint32_t nlines, terra_line_hit *h_hits);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

@@ -12,6 +12,7 @@
 #include <cassert>
 #include <cstdio>
 #include <cstdlib>
+#include <cstddef>
 
 namespace terra_cxx {
 
@@ -190,6 +191,37 @@ inline void tiles_add_or_remove_grass_at(int const *tile_xy, unsigned n, int dxo
 {
 	terra_grass_brush const b = {{pos[0], pos[1], pos[2]}, rradius, add_grass ? 1 : 0, brush_shape, brush_weight};
 	check(terra_tiles_edit_grass(default_ctx(), tile_xy, n, dxoff, dyoff, zvals, stats, is_distant, &b, mesh_weight_data, grass_blocks, updated, ranges), "add_or_remove_grass_at");
+}
+// The engine's tile batch as the line queries read it: tile_xy on the host, zvals / stats (terra_tiles_create_zvals_dev's) and is_distant (or null) on the device
+struct tile_batch_dev_t {int const *tile_xy; unsigned n; int dxoff, dyoff; float const *d_zvals; terra_tile_stats const *d_stats; unsigned char const *d_is_distant;};
+// one line against the batch (only_tile >= 0: against that batch tile alone, tile_t::line_intersect_mesh); the line goes up and the 32-byte record comes back.
+// The staging buffer d_io is one per process, allocated on first use and never freed, like default_ctx(): the wrappers serve the engine's single-threaded
+// frame loop; threads that query concurrently call terra_tiles_line_intersect_dev with buffers of their own
+inline terra_line_hit tiles_line_intersect(tile_batch_dev_t const &b, float const v1[3], float const v2[3], int only_tile = -1) {
+	struct io_t {float line[6]; int32_t only; int32_t pad; terra_line_hit hit;};
+	static void *d_io = [] {void *p = nullptr; check(terra_malloc(default_ctx(), &p, sizeof(io_t)), "terra_malloc"); return p;}();
+	io_t const in = {{v1[0], v1[1], v1[2], v2[0], v2[1], v2[2]}, only_tile, 0, {}};
+	io_t *d = (io_t *)d_io;
+	check(terra_memcpy_h2d(default_ctx(), d, &in, offsetof(io_t, hit)), "line_intersect_mesh");
+	check(terra_tiles_line_intersect_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, b.d_zvals, b.d_stats, b.d_is_distant, d->line, &d->only, 1, &d->hit), "line_intersect_mesh");
+	terra_line_hit h;
+	check(terra_memcpy_d2h(default_ctx(), &h, &d->hit, sizeof(h)), "line_intersect_mesh");
+	return h;
+}
+// tile_draw_t::line_intersect_mesh (src/tiled_mesh.cpp:3582-3605) with inc_trees = 0: t, the batch index of the tile (for intersected_tile; -1 on a miss, as the
+// reference's nullptr) and the cell's xpos / ypos (left as they were on a miss, as the reference leaves them)
+inline bool tile_draw_line_intersect_mesh(tile_batch_dev_t const &b, float const v1[3], float const v2[3], float &t, int &tile, int &xpos, int &ypos) {
+	terra_line_hit const h = tiles_line_intersect(b, v1, v2);
+	t = h.t;
+	tile = h.tile;
+	if (h.hit) {xpos = h.xpos; ypos = h.ypos;}
+	return h.hit != 0;
+}
+// line_intersect_tiled_mesh (src/tiled_mesh.cpp:3954-3957 -> :3643-3648) with inc_trees = 0: p_int = v1 + t*(v2 - v1) on a hit
+inline bool line_intersect_tiled_mesh(tile_batch_dev_t const &b, float const v1[3], float const v2[3], float p_int[3]) {
+	terra_line_hit const h = tiles_line_intersect(b, v1, v2);
+	if (h.hit) {p_int[0] = h.p_int[0]; p_int[1] = h.p_int[1]; p_int[2] = h.p_int[2];}
+	return h.hit != 0;
 }
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
