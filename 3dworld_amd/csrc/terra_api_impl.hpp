@@ -635,6 +635,84 @@ int terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 		be.d2h(h_hits, d + oh, hb);
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_tree_splat) == 12 && sizeof(terra::tree_splat_in_t) == 12, "terra_tree_splat layout");
+int terra_tiles_tree_map_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *d_is_distant, const terra_tree_splat *d_splats,
+                             const uint32_t *h_first, int32_t reset, uint8_t *d_tree_map, uint8_t *d_updated) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !h_first || !d_tree_map)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_tree_map_dev(tile_xy, n, dxoff, dyoff, d_is_distant, (terra::tree_splat_in_t const *)d_splats, h_first, reset != 0, d_tree_map, d_updated); TERRA_CATCH
+}
+int terra_tiles_tree_map(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *h_is_distant, const terra_tree_splat *h_splats,
+                         const uint32_t *h_first, int32_t reset, uint8_t *h_tree_map, uint8_t *h_updated) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !h_first || !h_tree_map)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size(); // (before the arrays are read: they are sized by S)
+		if (n == 0) return TERRA_OK;
+		for (uint32_t t = 0; t < n; ++t) {if (h_first[t+1] < h_first[t]) {return terra::fail(TERRA_ERR_ARG, "tiles_tree_map: h_first must not decrease");}}
+		uint32_t const s0 = h_first[0], ns = h_first[n] - s0;
+		if (ns && !h_splats) return terra::fail(TERRA_ERR_ARG, "tiles_tree_map: null splat list");
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const S = ctx->eng.tile_size();
+		size_t const mb = (size_t)n*(S + 1)*(S + 1)*2, sb = (size_t)ns*sizeof(terra_tree_splat), db = n, ub = n;
+		size_t const om = 0, os = om + up(mb), od = os + up(sb), ou = od + up(db);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(ou + up(ub));
+		if (!reset) {be.h2d(d + om, h_tree_map, mb);}
+		if (ns) {be.h2d(d + os, h_splats + s0, sb);}
+		if (h_is_distant) {be.h2d(d + od, h_is_distant, db);}
+		std::vector<uint32_t> first(h_first, h_first + n + 1);
+		for (uint32_t &f : first) {f -= s0;} // (the device copy holds only the splats the lists name)
+		ctx->eng.tiles_tree_map_dev(tile_xy, n, dxoff, dyoff, h_is_distant ? d + od : nullptr, (terra::tree_splat_in_t const *)(d + os), first.data(), reset != 0, d + om, d + ou);
+		be.d2h(h_tree_map, d + om, mb);
+		if (h_updated) {be.d2h(h_updated, d + ou, ub);}
+	TERRA_CATCH
+}
+int terra_tiles_shadow_texture_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_smask_sun, const uint8_t *d_smask_moon, const uint8_t *d_ao, const uint8_t *d_tree_map,
+                                   float light_factor, int32_t mesh_shadows, uint8_t *d_shadow) {
+	TERRA_CHECK_CTX if (n && !d_shadow) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_shadow_texture_dev(n, d_smask_sun, d_smask_moon, d_ao, d_tree_map, light_factor, mesh_shadows, d_shadow); TERRA_CATCH
+}
+int terra_tiles_shadow_texture(terra_ctx *ctx, uint32_t n, const uint8_t *h_smask_sun, const uint8_t *h_smask_moon, const uint8_t *h_ao, const uint8_t *h_tree_map,
+                               float light_factor, int32_t mesh_shadows, uint8_t *h_shadow) {
+	TERRA_CHECK_CTX if (n && !h_shadow) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size();
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const S = ctx->eng.tile_size();
+		size_t const zb = (size_t)n*(S + 2)*(S + 2), ab = (size_t)n*(S + 1)*(S + 1), tb = 2*ab, ob = 4*ab;
+		size_t const o1 = 0, o2 = o1 + up(zb), oa = o2 + up(zb), ot = oa + up(ab), oo = ot + up(tb);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oo + up(ob));
+		if (n && h_smask_sun) {be.h2d(d + o1, h_smask_sun, zb);}
+		if (n && h_smask_moon) {be.h2d(d + o2, h_smask_moon, zb);}
+		if (n && h_ao) {be.h2d(d + oa, h_ao, ab);}
+		if (n && h_tree_map) {be.h2d(d + ot, h_tree_map, tb);}
+		ctx->eng.tiles_shadow_texture_dev(n, h_smask_sun ? d + o1 : nullptr, h_smask_moon ? d + o2 : nullptr, h_ao ? d + oa : nullptr, h_tree_map ? d + ot : nullptr,
+			light_factor, mesh_shadows, d + oo);
+		if (n) {be.d2h(h_shadow, d + oo, ob);}
+	TERRA_CATCH
+}
+int terra_tiles_tree_weights_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_mesh_weights, const uint8_t *d_tree_map, uint8_t *d_weights) {
+	TERRA_CHECK_CTX if (n && (!d_mesh_weights || !d_weights)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_tree_weights_dev(n, d_mesh_weights, d_tree_map, d_weights); TERRA_CATCH
+}
+int terra_tiles_tree_weights(terra_ctx *ctx, uint32_t n, const uint8_t *h_mesh_weights, const uint8_t *h_tree_map, uint8_t *h_weights) {
+	TERRA_CHECK_CTX if (n && (!h_mesh_weights || !h_weights)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_128("tiles_tree_weights"); // (before the arrays are read: they are sized for 128)
+		if (n == 0) return TERRA_OK;
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const wb = (size_t)n*129*129*4, tb = (size_t)n*129*129*2;
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(up(wb) + up(tb));
+		be.h2d(d, h_mesh_weights, wb);
+		if (h_tree_map) {be.h2d(d + up(wb), h_tree_map, tb);}
+		ctx->eng.tiles_tree_weights_dev(n, d, h_tree_map ? d + up(wb) : nullptr, d);
+		be.d2h(h_weights, d, wb);
+	TERRA_CATCH
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

@@ -12,6 +12,7 @@
 #include "terra_erosion.hpp"
 #include "terra_landscape.hpp"
 #include "terra_modmap.hpp"
+#include "terra_treemap.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
@@ -2174,6 +2175,104 @@ template<class BE> struct terra_engine {
 			}
 			d_hits[r] = h;
 		});
+	}
+	// ---- the tree map and the two textures that read it (terra_treemap.hpp)
+	// tile_t::apply_tree_ao_shadows' clear (src/tiled_mesh.cpp:824-825, `reset`) and add_tree_ao_shadow's texel loop (:751-767) for every tile's splats, in list order:
+	// tile t owns d_splats[h_first[t] .. h_first[t+1]).  d_tree_map: [n][S+1][S+1]{ao, sh}; d_updated (or null): n bytes.  A distant tile is filled under `reset`
+	// and left alone otherwise, never updated (:743, :822).  Every texel sees its splats in list order: no two logical threads share a texel.
+	void tiles_tree_map_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, uint8_t const *d_distant, tree_splat_in_t const *d_splats, uint32_t const *h_first,
+		bool reset, uint8_t *d_tree_map, uint8_t *d_updated)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		for (uint32_t t = 0; t < n; ++t) {if (h_first[t+1] < h_first[t]) throw std::invalid_argument("tiles_tree_map: h_first must not decrease");}
+		uint32_t const ns = h_first[n] - h_first[0];
+		if (ns && !d_splats) throw std::invalid_argument("tiles_tree_map: null splat list");
+		if (((uintptr_t)d_tree_map & 1u) != 0) throw std::invalid_argument("tiles_tree_map: d_tree_map must be 2-byte aligned");
+		uint32_t const S = tile_size(), W = S + 1;
+		std::vector<tree_tile_pod_t> tl(n);
+		for (uint32_t t = 0; t < n; ++t) { // xstart = get_xval(x1 + mesh_off.dxoff) (src/tiled_mesh.cpp:309), get_xval(i) = -X_SCENE_SIZE + DX_VAL*i (src/mesh.h:122-123)
+			int const x1 = (int)((uint32_t)tile_xy[2*t]*S), y1 = (int)((uint32_t)tile_xy[2*t+1]*S);
+			tl[t].xstart = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); tl[t].ystart = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
+			tl[t].first = h_first[t] - h_first[0]; tl[t].count = h_first[t+1] - h_first[t];
+		}
+		size_t const tb = ((size_t)n*sizeof(tree_tile_pod_t) + 255) & ~(size_t)255, pb = ((size_t)ns*sizeof(tree_splat_pod_t) + 255) & ~(size_t)255;
+		uint8_t *base = scratch<uint8_t>(s_ao, tb + pb + (size_t)n*W + n + 256);
+		tree_tile_pod_t *d_tiles = (tree_tile_pod_t *)base;
+		tree_splat_pod_t *d_par = (tree_splat_pod_t *)(base + tb);
+		uint8_t *d_rowf = base + tb + pb; // the simple form's per-row `updated`
+		if (!d_updated) {d_updated = d_rowf + (size_t)n*W;} // (written and not returned)
+		be.h2d_async(d_tiles, tl.data(), (size_t)n*sizeof(tree_tile_pod_t));
+		tree_splat_in_t const *sp = d_splats ? d_splats + h_first[0] : nullptr;
+		float const dxv = DX_VAL, dyv = DY_VAL;
+		uint16_t *d_map = (uint16_t *)d_tree_map;
+		if (be.tile_tree_map(d_tiles, n, S, d_distant, sp, ns, d_par, dxv, dyv, reset, d_map, d_updated)) return;
+		// the simple form: one logical thread per splat for its parameters, then one per (tile, texel row) that walks the tile's list, then one per tile
+		be.launch(ns, [=] TERRA_LAMBDA (size_t i) {
+			tree_tile_pod_t const &tt = d_tiles[tree_tile_of(d_tiles, n, (uint32_t)i)];
+			d_par[i] = tree_splat_params(sp[i], tt.xstart, tt.ystart, dxv, dyv);
+		});
+		be.launch((size_t)n*W, [=] TERRA_LAMBDA (size_t i) {
+			uint32_t const t = (uint32_t)(i / W); int const y = (int)(i % W);
+			tree_tile_pod_t const tt = d_tiles[t];
+			uint16_t *row = d_map + i*W;
+			if (reset) {for (uint32_t x = 0; x < W; ++x) {row[x] = 0xFFFFu;}}
+			bool upd = false;
+			if (!(d_distant && d_distant[t])) {
+				for (uint32_t k = 0; k < tt.count; ++k) {
+					tree_splat_pod_t const s = d_par[tt.first + k];
+					if (s.rval == 0) continue;
+					int x1, y1, x2, y2;
+					tree_window(s, (int)S, x1, y1, x2, y2);
+					if (y < y1 || y > y2) continue;
+					double const s8 = 0.8*(double)s.scale; float const rval_sq = (float)(s.rval*s.rval);
+					for (int x = x1; x <= x2; ++x) {upd |= tree_texel(s, s8, rval_sq, x, y, row[x]);}
+				}
+			}
+			d_rowf[i] = upd ? 1 : 0;
+		});
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint8_t u = 0;
+			for (uint32_t y = 0; y < W; ++y) {u |= d_rowf[t*W + y];}
+			d_updated[t] = u;
+		});
+	}
+	// tile_t::upload_shadow_map_texture (:885-911) for n tiles: smask [n][S+2][S+2] per light (read only where the lights that are up need it), ao [n][S+1][S+1] or
+	// null (170), tree map or null (empty) -> [n][S+1][S+1] RGBA8 {mesh shadow, tree shadow, ambient occlusion, 0}
+	void tiles_shadow_texture_dev(uint32_t n, uint8_t const *d_sun, uint8_t const *d_moon, uint8_t const *d_ao, uint8_t const *d_tree_map, float light_factor, int mesh_shadows, uint8_t *d_shadow) {
+		require_scene();
+		require_tile_size();
+		shadow_tex_consts_t const c = shadow_tex_consts(light_factor, mesh_shadows);
+		if (!c.has_sun && !c.has_moon) throw std::invalid_argument("tiles_shadow_texture: neither light is up (light_factor is NaN)"); // (:844 asserts)
+		if (c.mesh_shadows && ((c.has_sun && !d_sun) || (c.has_moon && !d_moon))) throw std::invalid_argument("tiles_shadow_texture: the smask of a light that is up is null"); // (:888-889)
+		if (((uintptr_t)d_shadow & 3u) != 0) throw std::invalid_argument("tiles_shadow_texture: d_shadow must be 4-byte aligned");
+		if (((uintptr_t)d_tree_map & 1u) != 0) throw std::invalid_argument("tiles_shadow_texture: d_tree_map must be 2-byte aligned");
+		if (n == 0) return;
+		uint32_t const S = tile_size(), W = S + 1, Z = S + 2;
+		uint8_t const *sun = (c.mesh_shadows && c.has_sun) ? d_sun : nullptr, *moon = (c.mesh_shadows && c.has_moon) ? d_moon : nullptr;
+		uint16_t const *tree = (uint16_t const *)d_tree_map;
+		uint32_t *out = (uint32_t *)d_shadow;
+		if (be.tile_shadow_texture(c, n, S, sun, moon, d_ao, tree, out)) return;
+		be.launch((size_t)n*W*W, [=] TERRA_LAMBDA (size_t i) {
+			size_t const t = i / ((size_t)W*W); uint32_t const p = (uint32_t)(i % ((size_t)W*W)), y = p / W, x = p % W;
+			size_t const iz = t*Z*Z + (size_t)y*Z + x;
+			out[i] = shadow_texel(c, sun ? sun[iz] : 0u, moon ? moon[iz] : 0u, d_ao ? d_ao[i] : 170u, tree != nullptr, tree ? tree[i] : 0xFFFFu);
+		});
+	}
+	// the tail of tile_t::create_texture (:1325-1348) with sz_factor == 1: weight_data = mesh_weight_data, then grass under trees becomes dirt.  d_weights may be
+	// d_mesh_weights; a null tree map (tree_map.empty()) is the plain copy
+	void tiles_tree_weights_dev(uint32_t n, uint8_t const *d_mesh_weights, uint8_t const *d_tree_map, uint8_t *d_weights) {
+		require_scene();
+		require_tile_128("tiles_tree_weights");
+		if ((((uintptr_t)d_mesh_weights | (uintptr_t)d_weights) & 3u) != 0) throw std::invalid_argument("tiles_tree_weights: the weights must be 4-byte aligned");
+		if (((uintptr_t)d_tree_map & 1u) != 0) throw std::invalid_argument("tiles_tree_weights: d_tree_map must be 2-byte aligned");
+		if (n == 0) return;
+		size_t const ntex = (size_t)n*WT_TEX*WT_TEX;
+		if (!d_tree_map) {if (d_weights != d_mesh_weights) {be.d2d(d_weights, d_mesh_weights, ntex*4);} return;}
+		uint32_t const *in = (uint32_t const *)d_mesh_weights; uint32_t *out = (uint32_t *)d_weights;
+		if (be.tile_tree_weights(ntex, in, d_tree_map, out)) return;
+		be.launch(ntex, [=] TERRA_LAMBDA (size_t i) {out[i] = tree_weights_texel(in[i], d_tree_map[2*i]);});
 	}
 
 	// ================================================================ voxels (a14, a15, K8, K9)

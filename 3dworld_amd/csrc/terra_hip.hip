@@ -547,6 +547,33 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// the tree map: k_tree_splats once per splat, then k_tree_map once per (tile, band of rows): bands of equal height that fit the kernel's LDS
+	bool tile_tree_map(terra::tree_tile_pod_t const *tiles, uint32_t n, uint32_t S, uint8_t const *distant, terra::tree_splat_in_t const *splats, uint32_t ns,
+		terra::tree_splat_pod_t *par, float dxv, float dyv, bool reset, uint16_t *map, uint8_t *updated)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const W = S + 1, rmax = terra::TM_CELLS/W, bands = (W + rmax - 1)/rmax, R = (W + bands - 1)/bands;
+		uint32_t const m = (ns > n) ? ns : n;
+		hipLaunchKernelGGL(terra::k_tree_splats, dim3((m + 255)/256), dim3(256), 0, stream, tiles, n, splats, ns, dxv, dyv, par, updated);
+		hipLaunchKernelGGL(terra::k_tree_map, dim3(n, (W + R - 1)/R), dim3(64), 0, stream, tiles, distant, par, (int)S, (int)R, reset ? 1 : 0, map, updated);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
+	bool tile_shadow_texture(terra::shadow_tex_consts_t const &c, uint32_t n, uint32_t S, uint8_t const *sun, uint8_t const *moon, uint8_t const *ao, uint16_t const *tree, uint32_t *out) {
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_shadow_texture, dim3(n, ((S + 1)*(S + 1) + 255)/256), dim3(256), 0, stream, c, S, sun, moon, ao, tree, out);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
+	bool tile_tree_weights(size_t ntex, uint32_t const *in, uint8_t const *tree, uint32_t *out) {
+		if (simple_kernels || (ntex + 255)/256 > 0x7FFFFFFFull) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_tree_weights, dim3((unsigned)((ntex + 255)/256)), dim3(256), 0, stream, ntex, in, tree, out);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

@@ -1390,6 +1390,101 @@ __global__ __launch_bounds__(LI_THREADS) void k_line_intersect(line_query_consts
 	}
 }
 
+// ------------------------------------------------------------------ tree map (tile_t::add_tree_ao_shadow, src/tiled_mesh.cpp:749-767), two launches
+// k_tree_splats: xc, yc, rval and scale of every splat, once per call (a float division per axis and a double one per splat); it also clears `updated`.
+__global__ __launch_bounds__(256) void k_tree_splats(tree_tile_pod_t const *__restrict__ tiles, uint32_t n, tree_splat_in_t const *__restrict__ splats, uint32_t ns,
+	float dxv, float dyv, tree_splat_pod_t *__restrict__ par, uint8_t *__restrict__ updated)
+{
+	uint32_t const i = blockIdx.x*256u + threadIdx.x;
+	if (i < n) {updated[i] = 0;}
+	if (i >= ns) return;
+	tree_tile_pod_t const tt = tiles[tree_tile_of(tiles, n, i)];
+	par[i] = tree_splat_params(splats[i], tt.xstart, tt.ystart, dxv, dyv);
+}
+// k_tree_map: one wave per (tile, band of R texel rows); the band lives in LDS for the length of the tile's list.  An ordered scatter with overlap and no atomics:
+// a texel belongs to one wave, and that wave applies the tile's splats one after another, in list order.  The list is read 64 splats at a time, one per lane; a
+// ballot finds those whose clipped window reaches the band and the wave takes them in lane (= list) order.  A window up to 64 texels wide is covered 64/w rows at
+// a time, a wider one row by row.  The barrier between two splats orders the LDS read-modify-writes of different lanes on one texel.
+// Cost: every band of a tile reads the tile's whole parameter list (16 bytes a splat, 64 splats per load): 5 bands at S = 128, 342 at S = 1024.  Measured at
+// S = 128 only; a long list at a large S would want the splats binned by band first.
+constexpr uint32_t TM_CELLS = 4096; // 8 KB of LDS per wave
+__global__ __launch_bounds__(64) void k_tree_map(tree_tile_pod_t const *__restrict__ tiles, uint8_t const *__restrict__ distant, tree_splat_pod_t const *__restrict__ par,
+	int S, int R, int reset, uint16_t *__restrict__ map, uint8_t *__restrict__ updated)
+{
+	__shared__ uint16_t s_map[TM_CELLS];
+	uint32_t const t = blockIdx.x, lane = threadIdx.x;
+	int const W = S + 1, r0 = (int)blockIdx.y*R, r1 = imin(r0 + R, W) - 1; // rows r0 .. r1
+	uint32_t const cells = (uint32_t)((r1 - r0 + 1)*W);
+	uint16_t *g = map + ((size_t)t*W + r0)*W;
+	tree_tile_pod_t const tt = tiles[t];
+	if ((distant && distant[t]) || tt.count == 0) { // nothing to apply: the fill of a reset, or nothing at all
+		if (reset) {for (uint32_t k = lane; k < cells; k += 64) {g[k] = 0xFFFFu;}}
+		return;
+	}
+	for (uint32_t k = lane; k < cells; k += 64) {s_map[k] = reset ? (uint16_t)0xFFFFu : g[k];}
+	__syncthreads();
+	bool any = false;
+	for (uint32_t base = 0; base < tt.count; base += 64) {
+		tree_splat_pod_t s = {0, 0, 0, 0.0f};
+		if (base + lane < tt.count) {s = par[tt.first + base + lane];}
+		int x1, y1, x2, y2;
+		tree_window(s, S, x1, y1, x2, y2);
+		unsigned long long m = __ballot(s.rval != 0 && x1 <= x2 && imax(y1, r0) <= imin(y2, r1));
+		while (m) {
+			int const j = __ffsll((long long)m) - 1;
+			m &= m - 1;
+			tree_splat_pod_t u;
+			u.xc = __shfl(s.xc, j); u.yc = __shfl(s.yc, j); u.rval = __shfl(s.rval, j); u.scale = __shfl(s.scale, j);
+			tree_window(u, S, x1, y1, x2, y2);
+			int const ya = imax(y1, r0), yb = imin(y2, r1), w = x2 - x1 + 1;
+			double const s8 = 0.8*(double)u.scale; float const rval_sq = (float)(u.rval*u.rval);
+			if (w <= 64) {
+				// lane -> (row ly, column lx) of a block of rp = 64/w rows: (lane + 0.5)/w is at least 1/128 away from an integer, far more than the float error
+				float const rcp = 1.0f/(float)w;
+				int const rp = (int)(64.5f*rcp), ly = (int)(((float)lane + 0.5f)*rcp), x = x1 + ((int)lane - ly*w);
+				if (ly < rp) {
+					for (int y = ya + ly; y <= yb; y += rp) {
+						uint16_t &c = s_map[(y - r0)*W + x];
+						uint16_t v = c;
+						if (tree_texel(u, s8, rval_sq, x, y, v)) {c = v; any = true;}
+					}
+				}
+			}
+			else {
+				for (int y = ya; y <= yb; ++y) {
+					for (int x = x1 + (int)lane; x <= x2; x += 64) {
+						uint16_t &c = s_map[(y - r0)*W + x];
+						uint16_t v = c;
+						if (tree_texel(u, s8, rval_sq, x, y, v)) {c = v; any = true;}
+					}
+				}
+			}
+			__syncthreads();
+		}
+	}
+	bool const upd = __syncthreads_or((int)any) != 0;
+	if (reset || upd) {for (uint32_t k = lane; k < cells; k += 64) {g[k] = s_map[k];}}
+	if (upd && lane == 0) {updated[t] = 1;} // (every band that multiplied a texel stores the same 1)
+}
+
+// ------------------------------------------------------------------ shadow texture (tile_t::upload_shadow_map_texture, src/tiled_mesh.cpp:885-911) and the tree pass of
+// the weights texture (tile_t::create_texture, :1325-1348): streaming, one texel and one 32-bit store per thread; a wave reads 64 consecutive bytes of each byte input
+__global__ __launch_bounds__(256) void k_shadow_texture(shadow_tex_consts_t c, uint32_t S, uint8_t const *__restrict__ sun, uint8_t const *__restrict__ moon,
+	uint8_t const *__restrict__ ao, uint16_t const *__restrict__ tree, uint32_t *__restrict__ out)
+{
+	uint32_t const t = blockIdx.x, p = blockIdx.y*256u + threadIdx.x, W = S + 1, Z = S + 2;
+	if (p >= W*W) return;
+	uint32_t const y = p/W, x = p - y*W;
+	size_t const i = (size_t)t*W*W + p, iz = (size_t)t*Z*Z + (size_t)y*Z + x;
+	out[i] = shadow_texel(c, sun ? sun[iz] : 0u, moon ? moon[iz] : 0u, ao ? ao[i] : 170u, tree != nullptr, tree ? tree[i] : 0xFFFFu);
+}
+// (in and out may be the same array: no __restrict__)
+__global__ __launch_bounds__(256) void k_tree_weights(size_t ntex, uint32_t const *in, uint8_t const *__restrict__ tree, uint32_t *out) {
+	size_t const i = (size_t)blockIdx.x*256u + threadIdx.x;
+	if (i >= ntex) return;
+	out[i] = tree_weights_texel(in[i], tree[2*i]);
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

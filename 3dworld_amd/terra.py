@@ -55,6 +55,8 @@ MOD_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("delta", np.int32)]) 
 GRASS_BLOCK_DTYPE = np.dtype([("ix", np.uint32), ("zmin", np.float32), ("zmax", np.float32)])  # terra_grass_block
 LINE_HIT_DTYPE = np.dtype([("t", np.float32), ("tile", np.int32), ("xpos", np.int32), ("ypos", np.int32), ("p_int", np.float32, (3,)), ("hit", np.uint32)])  # terra_line_hit
 assert LINE_HIT_DTYPE.itemsize == 32
+TREE_SPLAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("radius", np.float32)])  # terra_tree_splat
+assert TREE_SPLAT_DTYPE.itemsize == 12
 
 
 class GRASS_BRUSH(C.Structure):
@@ -195,6 +197,12 @@ _PROTOS = {
     "terra_tiles_edit_grass": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_line_intersect_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_line_intersect": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_tree_map_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "terra_tiles_tree_map": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "terra_tiles_shadow_texture_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _f, _i32, _vp]),
+    "terra_tiles_shadow_texture": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _f, _i32, _vp]),
+    "terra_tiles_tree_weights_dev": (_i32, [_vp, _u32, _vp, _vp, _vp]),
+    "terra_tiles_tree_weights": (_i32, [_vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -626,6 +634,50 @@ class Terra:
                                                      None if dist is None else dist.ctypes.data, ln.ctypes.data, None if lt is None else lt.ctypes.data, len(ln), hits.ctypes.data))
         return hits
 
+    @staticmethod
+    def _splat_lists(splats, first, n):
+        sp = np.ascontiguousarray(splats, TREE_SPLAT_DTYPE).reshape(-1)
+        fi = np.ascontiguousarray(first, np.uint32).reshape(-1)
+        assert len(fi) == n + 1 and (n == 0 or int(fi[-1]) <= len(sp))
+        return sp, fi
+
+    def tiles_tree_map(self, tile_xy, splats, first, reset=True, tree_map=None, dxoff=0, dyoff=0, is_distant=None):
+        """tile_t::add_tree_ao_shadow's texel loop for every tile's splat list (TREE_SPLAT_DTYPE; tile t owns splats[first[t]:first[t+1]]), in list order.
+        reset: start from an all-255 map; else continue on tree_map (u8 [n,S+1,S+1,2] = {ao, sh}, edited in place).  -> (tree_map, updated bool [n])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        S = self.tile_size
+        sp, fi = self._splat_lists(splats, first, n)
+        if tree_map is None:
+            assert reset
+            tree_map = np.empty((n, S + 1, S + 1, 2), np.uint8)
+        assert tree_map.flags["C_CONTIGUOUS"] and tree_map.dtype == np.uint8 and tree_map.shape == (n, S + 1, S + 1, 2)
+        dist = None if is_distant is None else np.ascontiguousarray(is_distant, np.uint8).reshape(n)
+        upd = np.empty(n, np.uint8)
+        self._ck(self.lib.terra_tiles_tree_map(self.ctx, txy.ctypes.data, n, dxoff, dyoff, None if dist is None else dist.ctypes.data, sp.ctypes.data if len(sp) else None,
+                                               fi.ctypes.data, int(bool(reset)), tree_map.ctypes.data, upd.ctypes.data))
+        return tree_map, upd.astype(bool)
+
+    def tiles_shadow_texture(self, n, light_factor, mesh_shadows=True, smask_sun=None, smask_moon=None, ao=None, tree_map=None):
+        """tile_t::upload_shadow_map_texture: smask_* u8 [n,S+2,S+2], ao u8 [n,S+1,S+1] (None: 170), tree_map u8 [n,S+1,S+1,2] (None: empty) -> u8 [n,S+1,S+1,4]"""
+        S = self.tile_size
+        arr = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.uint8).reshape(shape)  # noqa: E731
+        sun, moon = arr(smask_sun, (n, S + 2, S + 2)), arr(smask_moon, (n, S + 2, S + 2))
+        aov, tm = arr(ao, (n, S + 1, S + 1)), arr(tree_map, (n, S + 1, S + 1, 2))
+        out = np.empty((n, S + 1, S + 1, 4), np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self._ck(self.lib.terra_tiles_shadow_texture(self.ctx, n, ptr(sun), ptr(moon), ptr(aov), ptr(tm), light_factor, int(bool(mesh_shadows)), out.ctypes.data))
+        return out
+
+    def tiles_tree_weights(self, mesh_weights, tree_map=None):
+        """the tree pass of tile_t::create_texture: mesh_weights u8 [n,129,129,4], tree_map u8 [n,129,129,2] (None: plain copy) -> weight_data u8 [n,129,129,4]"""
+        w = np.ascontiguousarray(mesh_weights, np.uint8)
+        n = len(w)
+        tm = None if tree_map is None else np.ascontiguousarray(tree_map, np.uint8).reshape(n, 129, 129, 2)
+        out = np.empty((n, 129, 129, 4), np.uint8)
+        self._ck(self.lib.terra_tiles_tree_weights(self.ctx, n, w.ctypes.data, None if tm is None else tm.ctypes.data, out.ctypes.data))
+        return out
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -758,6 +810,23 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_line_intersect_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, z_ptr, stats_ptr, distant_ptr, lines_ptr, line_tile_ptr,
                                                          nlines, hits_ptr))
+
+    def tiles_tree_map_dev(self, tile_xy, splats_ptr, first, tree_map_ptr, updated_ptr=None, reset=True, dxoff=0, dyoff=0, distant_ptr=None):
+        """the tree map of a device-resident batch: splats_ptr = device TREE_SPLAT_DTYPE records, first = HOST [n+1] uint32, tree_map_ptr [n][S+1][S+1][2] bytes,
+        updated_ptr n bytes (or None).  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        fi = np.ascontiguousarray(first, np.uint32).reshape(-1)
+        assert len(fi) == len(txy) + 1
+        self._ck(self.lib.terra_tiles_tree_map_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, distant_ptr, splats_ptr, fi.ctypes.data, int(bool(reset)),
+                                                   tree_map_ptr, updated_ptr))
+
+    def tiles_shadow_texture_dev(self, n, light_factor, shadow_ptr, mesh_shadows=True, smask_sun_ptr=None, smask_moon_ptr=None, ao_ptr=None, tree_map_ptr=None):
+        """the shadow texture of a device-resident batch: shadow_ptr [n][S+1][S+1][4] bytes.  Only enqueues."""
+        self._ck(self.lib.terra_tiles_shadow_texture_dev(self.ctx, n, smask_sun_ptr, smask_moon_ptr, ao_ptr, tree_map_ptr, light_factor, int(bool(mesh_shadows)), shadow_ptr))
+
+    def tiles_tree_weights_dev(self, n, mesh_weights_ptr, tree_map_ptr, weights_ptr):
+        """weight_data from mesh_weight_data and the tree map on the device; weights_ptr may be mesh_weights_ptr.  Only enqueues."""
+        self._ck(self.lib.terra_tiles_tree_weights_dev(self.ctx, n, mesh_weights_ptr, tree_map_ptr, weights_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

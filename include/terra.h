@@ -345,7 +345,7 @@ int  terra_write_mesh(const char *filename, const float *h_mesh, uint32_t nx, ui
  * loop would read past the zvals there); otherwise every tile call is TERRA_ERR_ARG.  At S != 128 these entry points follow S: terra_tiles_create_zvals[_dev]
  * (all three field sources: procedural, the AO-context clip, the heightmap texture), terra_tiles_post[_dev], terra_tiles_ao_lighting[_dev],
  * terra_tiles_mesh_shadows[_dev], terra_tiles_line_intersect[_dev] and terra_multi_tiles_create_zvals[_dev].  These are TERRA_ERR_ARG at S != 128 for now: terra_tiles_terrain_params,
- * terra_tiles_create_weights[_dev], terra_tiles_edit_grass[_dev], terra_tiles_mesh_shadows_halo_dev / _edges_dev, terra_multi_tiles_mesh_shadows[_dev] and terra_multi_shadow_layout.
+ * terra_tiles_create_weights[_dev], terra_tiles_edit_grass[_dev], terra_tiles_tree_weights[_dev], terra_tiles_mesh_shadows_halo_dev / _edges_dev, terra_multi_tiles_mesh_shadows[_dev] and terra_multi_shadow_layout.
  * terra_tile_size: *size = S of the scene in force (TERRA_ERR_ARG when the scene's S is not supported, TERRA_ERR_STATE before terra_init_scene).
  * tile_xy: n pairs (tile x, tile y) on the HOST.  d_zvals: n zvals.  d_stats: n terra_tile_stats (optional).
  * d_normals: n normals (optional); d_min_normal_z: n floats (optional). */
@@ -416,7 +416,8 @@ int  terra_tiles_ao_lighting(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 
 /* ---- landscape weights texture of a tile (tile size 128 only): tile_t::create_texture (src/tiled_mesh.cpp:1071-1240) with update_terrain_params (:321-343), get_tids /
  * update_lttex_ix (src/Textures.cpp:1289-1316) and add_grass_block_at (src/tiled_mesh.cpp:1354-1371).  Terrain-only branch: the city, tunnel and building
- * queries and the tree map come from subsystems outside this library (their texels are the caller's to overwrite afterwards, as the reference does).
+ * queries come from subsystems outside this library (their texels are the caller's to overwrite afterwards, as the reference does); the tree map's texels are
+ * terra_tiles_tree_weights[_dev]'s, below: mesh_weight_data is what this call writes, weight_data what that one makes of it.
  * zvals: [n][130][130]; weights: [n][129][129][4] bytes RGBA = {sand, dirt, grass, rock}, snow = remainder; grass_blocks: [n][32][32] or NULL;
  * has_any_grass: [n] bytes or NULL.  The second noise field (build_arrays(..., 80*DX_VAL, 80*DY_VAL, 129, 129, 0, force_sine_mode=1) + eval_index(x, y, 50))
  * and the biome parameters are generated internally.  terra_tiles_terrain_params returns those parameters: [n][2][2][3] = [yp][xp]{veg, grass, dirt}. */
@@ -477,6 +478,45 @@ int  terra_tiles_line_intersect_dev(terra_ctx *ctx, const int32_t *tile_xy, uint
 int  terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff,
                                 const float *h_zvals, const terra_tile_stats *h_stats, const uint8_t *h_is_distant,
                                 const float *h_lines, const int32_t *h_line_tile, uint32_t nlines, terra_line_hit *h_hits);
+
+/* ---- tree map of a tile batch (every supported tile size S): what the fire modes "Add Trees" / "Remove Trees" (src/tiled_mesh.cpp:3998-4002) leave for the terrain
+ * to do.  tile_t::register_tree_change (:3789-3794) clears tree_map and forces the textures to be re-made; tile_t::pre_draw (:1900-1907) then runs apply_tree_ao_shadows,
+ * create_texture and check_shadow_map_and_normal_texture.  The three calls below are the terrain side of those steps; trees themselves (generation, drawing,
+ * collision) stay with the engine, which passes each tree as (pos.x, pos.y, tradius).
+ * terra_tiles_tree_map: tile t owns splats[h_first[t] .. h_first[t+1]-1]; h_first ([n+1], non-decreasing) is on the HOST in both forms.  Per tile: reset != 0 fills
+ * the map with 255 (tree_map.clear() + resize, :824-825), reset == 0 continues on the map as it is (a neighbour's push_tree_ao_shadow, :740-746); then every splat of
+ * its list is the texel loop of tile_t::add_tree_ao_shadow (:751-767), in list order, bit for bit: the order matters, (uchar)((uchar)(255*a)*b) is not
+ * (uchar)((uchar)(255*b)*a).  x, y: pos in the tile's camera-space frame (get_center() + pt_off, :791, or pos2 of :744); radius: get_ao_radius().
+ * The caller builds the lists: the own-tree loop, the eight neighbours in dy, dx order with the bounding-box cull of :793, the x_test / y_test border push of
+ * :768-778 and the trmax < min(DX_VAL, DY_VAL) shortcut stay in the engine; add_tree_ao_shadow's body becomes "append to the tile's list".
+ * tree_map: [n][S+1][S+1][2] bytes {ao, sh}, 2-byte aligned.  updated: [n] bytes or NULL; updated[t] = 1 when any texel of tile t was multiplied in this call
+ * (:765, :779).  is_distant: [n] bytes or NULL; a distant tile is filled with 255 under reset and left alone otherwise, updated = 0 (:743, :822): an all-255 map reads
+ * as the reference's empty tree_map in both consumers.  dxoff / dyoff = xoff - xoff2 / yoff - yoff2.
+ * A splat is skipped where the reference is undefined: a non-finite member, radius < 0, rval = max(int(radius/DX_VAL), int(radius/DY_VAL)) + 1 > 46340 (rval*rval
+ * overflows), |xc| or |yc| beyond 2^30.
+ * TERRA_ERR_ARG: a NULL required pointer (tile_xy, h_first, tree_map when n > 0; splats when the lists are not empty), a decreasing h_first, an unsupported S.
+ * TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing.  The device form only enqueues. */
+typedef struct terra_tree_splat {float x, y, radius;} terra_tree_splat;
+int  terra_tiles_tree_map_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *d_is_distant,
+                              const terra_tree_splat *d_splats, const uint32_t *h_first, int32_t reset, uint8_t *d_tree_map, uint8_t *d_updated);
+int  terra_tiles_tree_map(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *h_is_distant,
+                          const terra_tree_splat *h_splats, const uint32_t *h_first, int32_t reset, uint8_t *h_tree_map, uint8_t *h_updated);
+/* terra_tiles_shadow_texture: tile_t::upload_shadow_map_texture (:885-911), the RGBA8 texel {mesh shadow, tree shadow, ambient occlusion, 0} the engine uploads.
+ * smask_sun / smask_moon: [n][S+2][S+2] as terra_tiles_mesh_shadows wrote them for get_light_pos(LIGHT_SUN / LIGHT_MOON); ao: [n][S+1][S+1] or NULL (170, the
+ * reference's value without AO lighting); tree_map: as above or NULL (tree_map.empty()); shadow: [n][S+1][S+1][4], 4-byte aligned.  has_sun = light_factor >= 0.4,
+ * has_moon = light_factor <= 0.6; mesh_shadows = mesh_shadows_enabled(): 0 leaves channel 0 at 255 and reads no mask.
+ * TERRA_ERR_ARG where the reference asserts: mesh_shadows with the smask of a light that is up NULL (:888-889), neither light up (a NaN light_factor, :844);
+ * also a NULL shadow with n > 0, a misaligned pointer, an unsupported S. */
+int  terra_tiles_shadow_texture_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_smask_sun, const uint8_t *d_smask_moon, const uint8_t *d_ao, const uint8_t *d_tree_map,
+                                    float light_factor, int32_t mesh_shadows, uint8_t *d_shadow);
+int  terra_tiles_shadow_texture(terra_ctx *ctx, uint32_t n, const uint8_t *h_smask_sun, const uint8_t *h_smask_moon, const uint8_t *h_ao, const uint8_t *h_tree_map,
+                                float light_factor, int32_t mesh_shadows, uint8_t *h_shadow);
+/* terra_tiles_tree_weights (tile size 128 only): the tail of tile_t::create_texture (:1325-1348) with sz_factor == 1.  weights = mesh_weights; then, where the tree
+ * map's ao != 255 and the texel's rock byte is not 255 (a city texel), grass under trees becomes dirt.  mesh_weights / weights: [n][129][129][4] as
+ * terra_tiles_create_weights wrote them, 4-byte aligned; weights may be mesh_weights (in place), any other overlap is undefined.  tree_map: [n][129][129][2] or
+ * NULL (the plain copy). */
+int  terra_tiles_tree_weights_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_mesh_weights, const uint8_t *d_tree_map, uint8_t *d_weights);
+int  terra_tiles_tree_weights(terra_ctx *ctx, uint32_t n, const uint8_t *h_mesh_weights, const uint8_t *h_tree_map, uint8_t *h_weights);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

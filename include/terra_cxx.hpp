@@ -223,6 +223,24 @@ inline bool line_intersect_tiled_mesh(tile_batch_dev_t const &b, float const v1[
 	if (h.hit) {p_int[0] = h.p_int[0]; p_int[1] = h.p_int[1]; p_int[2] = h.p_int[2];}
 	return h.hit != 0;
 }
+// ---- the tree map of a batch and the two textures that read it (what tile_t::pre_draw runs after register_tree_change, src/tiled_mesh.cpp:1900-1907), on device
+// arrays.  tile_t::apply_tree_ao_shadows (:820-828) for every tile: the engine's add_tree_ao_shadow (:749) appends terra_tree_splat{pos.x, pos.y, tradius} to the
+// tile's list instead of looping over texels, and this runs the lists (tile t: d_splats[first[t] .. first[t+1]), first on the host).  reset = false is a later
+// push_tree_ao_shadow round on the resident map.  d_updated[t] (may be null) sets the tile's sun / moon_shadows_invalid and recalc_tree_grass_weights
+inline void tiles_apply_tree_ao_shadows(tile_batch_dev_t const &b, terra_tree_splat const *d_splats, unsigned const *first, bool reset, unsigned char *d_tree_map, unsigned char *d_updated = nullptr) {
+	check(terra_tiles_tree_map_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, b.d_is_distant, d_splats, first, reset ? 1 : 0, d_tree_map, d_updated), "apply_tree_ao_shadows");
+}
+// tile_t::upload_shadow_map_texture (:882-913) up to the texture upload: d_shadow_data [n][S+1][S+1][4]; d_ao_lighting / d_tree_map may be null (ao_lighting.empty() /
+// tree_map.empty()), a smask may be null when its light is down or mesh_shadows_enabled() is false
+inline void tiles_upload_shadow_map_texture(unsigned n, unsigned char const *d_smask_sun, unsigned char const *d_smask_moon, unsigned char const *d_ao_lighting,
+	unsigned char const *d_tree_map, float light_factor, bool mesh_shadows, unsigned char *d_shadow_data)
+{
+	check(terra_tiles_shadow_texture_dev(default_ctx(), n, d_smask_sun, d_smask_moon, d_ao_lighting, d_tree_map, light_factor, mesh_shadows ? 1 : 0, d_shadow_data), "upload_shadow_map_texture");
+}
+// the tail of tile_t::create_texture (:1325-1348): weight_data from mesh_weight_data and tree_map (null: the plain copy); d_weight_data may be d_mesh_weight_data
+inline void tiles_create_texture_tree_weights(unsigned n, unsigned char const *d_mesh_weight_data, unsigned char const *d_tree_map, unsigned char *d_weight_data) {
+	check(terra_tiles_tree_weights_dev(default_ctx(), n, d_mesh_weight_data, d_tree_map, d_weight_data), "create_texture");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
