@@ -713,6 +713,72 @@ int terra_tiles_tree_weights(terra_ctx *ctx, uint32_t n, const uint8_t *h_mesh_w
 		be.d2h(h_weights, d, wb);
 	TERRA_CATCH
 }
+int terra_set_tree_params(terra_ctx *ctx, const terra_tree_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_tree_params(*params); TERRA_CATCH
+}
+int terra_get_tree_params(terra_ctx *ctx, terra_tree_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	*out = ctx->eng.tp; return TERRA_OK;
+}
+int terra_set_height_histogram(terra_ctx *ctx, const float *h_vals, uint32_t count) {
+	TERRA_CHECK_CTX if (count && !h_vals) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_height_histogram(h_vals, count); TERRA_CATCH
+}
+int terra_get_height_histogram(terra_ctx *ctx, float *h_vals, uint32_t capacity, uint32_t *count) {
+	TERRA_CHECK_CTX if (!count) return terra::fail(TERRA_ERR_ARG, "null argument");
+	std::vector<float> const &h = ctx->eng.height_histogram;
+	*count = (uint32_t)h.size();
+	if (h_vals) {memcpy(h_vals, h.data(), std::min<size_t>(capacity, h.size())*sizeof(float));}
+	return TERRA_OK;
+}
+static_assert(sizeof(terra_tree_place) == 40 && sizeof(terra::tree_place_pod_t) == 40, "terra_tree_place layout");
+static int tiles_place_trees_impl(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *skip, const terra_tile_stats *stats,
+	const float *brush, uint32_t capacity, terra_tree_place *trees, uint32_t *counts, bool host)
+{
+	TERRA_CHECK_CTX if (n && (!tile_xy || !counts || (capacity && !trees))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		if (!host) {ctx->eng.tiles_place_trees_dev(tile_xy, n, xoff2, yoff2, skip, stats, brush, capacity, (terra::tree_place_pod_t *)trees, counts); return TERRA_OK;}
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size();
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const tb = (size_t)n*capacity*sizeof(terra_tree_place), cb = (size_t)n*4, kb = n, sb = (size_t)n*sizeof(terra_tile_stats);
+		size_t const ot = 0, oc = ot + up(tb), ok = oc + up(cb), os = ok + up(kb);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(os + up(sb));
+		if (n && skip) {be.h2d(d + ok, skip, kb);}
+		if (n && stats) {be.h2d(d + os, stats, sb);}
+		ctx->eng.tiles_place_trees_dev(tile_xy, n, xoff2, yoff2, skip ? d + ok : nullptr, stats ? (terra_tile_stats const *)(d + os) : nullptr, brush, capacity,
+			(terra::tree_place_pod_t *)(d + ot), (uint32_t *)(d + oc));
+		if (n == 0) return TERRA_OK;
+		be.d2h(counts, d + oc, cb);
+		// only the records the counts name were written: the rest of the caller's array stays as it was
+		for (uint32_t t = 0; t < n; ++t) {
+			uint32_t const m = std::min(counts[t], capacity);
+			if (m) {be.d2h(trees + (size_t)t*capacity, d + ot + (size_t)t*capacity*sizeof(terra_tree_place), (size_t)m*sizeof(terra_tree_place));}
+		}
+	TERRA_CATCH
+}
+int terra_tiles_place_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                uint32_t capacity, terra_tree_place *d_trees, uint32_t *d_counts) {
+	return tiles_place_trees_impl(ctx, tile_xy, n, xoff2, yoff2, d_skip, d_stats, nullptr, capacity, d_trees, d_counts, false);
+}
+int terra_tiles_place_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                            uint32_t capacity, terra_tree_place *h_trees, uint32_t *h_counts) {
+	return tiles_place_trees_impl(ctx, tile_xy, n, xoff2, yoff2, h_skip, h_stats, nullptr, capacity, h_trees, h_counts, true);
+}
+int terra_tiles_place_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                      const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *d_trees, uint32_t *d_counts) {
+	if (!pos) return terra::fail(TERRA_ERR_ARG, "null argument");
+	float const brush[4] = {pos[0], pos[1], radius, is_square ? 1.0f : 0.0f};
+	return tiles_place_trees_impl(ctx, tile_xy, n, xoff2, yoff2, d_skip, d_stats, brush, capacity, d_trees, d_counts, false);
+}
+int terra_tiles_place_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                                  const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *h_trees, uint32_t *h_counts) {
+	if (!pos) return terra::fail(TERRA_ERR_ARG, "null argument");
+	float const brush[4] = {pos[0], pos[1], radius, is_square ? 1.0f : 0.0f};
+	return tiles_place_trees_impl(ctx, tile_xy, n, xoff2, yoff2, h_skip, h_stats, brush, capacity, h_trees, h_counts, true);
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

@@ -13,6 +13,7 @@
 #include "terra_landscape.hpp"
 #include "terra_modmap.hpp"
 #include "terra_treemap.hpp"
+#include "terra_treeplace.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
@@ -566,6 +567,7 @@ template<class BE> struct terra_engine {
 		if (d_noise_lut) be.free(d_noise_lut);
 		if (d_noise3_lut) be.free(d_noise3_lut);
 		if (d_sinTable) be.free(d_sinTable);
+		if (d_hist) be.free(d_hist);
 	}
 
 	sin_lut_t lut() const {return sin_lut_t{d_sin_table, sscale};}
@@ -685,6 +687,28 @@ template<class BE> struct terra_engine {
 		ls = p;
 	}
 
+	// the globals small_tree_group::gen_trees reads beyond the scene and the landscape; tree_mode 1: no small trees until the engine says so
+	terra_tree_params tp = {1.0f, 1.0f, 0.55f, 0.0f, 1, -1, 0, 0, 0, 0u, 0u};
+	void set_tree_params(terra_tree_params const &p) {
+		if (!(p.sm_tree_density >= 0.0f) || !(p.tree_scale > 0.0f)) throw std::invalid_argument("terra_set_tree_params: sm_tree_density must be >= 0 and tree_scale > 0");
+		if (p.tree_mode < 0 || p.tree_mode > 3) throw std::invalid_argument("terra_set_tree_params: tree_mode must be 0 .. 3");
+		if (p.force_tree_class < -1 || p.force_tree_class > TREE_CLASS_PALM) throw std::invalid_argument("terra_set_tree_params: force_tree_class must be -1 .. 3 (TREE_CLASS_DETAILED has no small tree type)");
+		if (p.instanced && (p.num_pine_insts == 0 || p.num_palm_insts == 0 || p.num_pine_insts > (1u << 30) || p.num_palm_insts > (1u << 30))) throw std::invalid_argument("terra_set_tree_params: instanced needs 1 .. 2^30 pine and palm instances (select_inst asserts start < end)");
+		if (p.instanced && p.force_tree_class == TREE_CLASS_DECID) throw std::invalid_argument("terra_set_tree_params: instanced trees are pines and palms (maybe_add_tree asserts it)");
+		tp = p;
+	}
+	// height_histogram of estimate_zminmax (src/mesh_gen.cpp:467-480), what get_median_height reads; the device copy follows on the next placement call
+	std::vector<float> height_histogram;
+	float *d_hist = nullptr; size_t d_hist_cap = 0; bool hist_dev_valid = false;
+	void set_height_histogram(float const *v, uint32_t count) {height_histogram.assign(v, v + count); hist_dev_valid = false;}
+	float const *height_histogram_dev() {
+		size_t const nh = height_histogram.size();
+		if (nh > d_hist_cap) {if (d_hist) {be.sync(); be.free(d_hist); d_hist = nullptr; d_hist_cap = 0;} d_hist = (float *)be.alloc(nh*sizeof(float)); d_hist_cap = nh; hist_dev_valid = false;}
+		if (!hist_dev_valid && nh) {be.h2d(d_hist, height_histogram.data(), nh*sizeof(float));}
+		hist_dev_valid = true;
+		return d_hist;
+	}
+
 	// the config-file values only (no derivation): what an engine that already owns the derived globals passes before terra_set_state
 	void set_config(terra_config const &c) {
 		if (c.mesh_x <= 0 || c.mesh_y <= 0 || !(c.scene_x > 0) || !(c.scene_y > 0) || !(c.mesh_scale > 0)) throw std::invalid_argument("terra config: bad mesh/scene size");
@@ -714,13 +738,17 @@ template<class BE> struct terra_engine {
 		for (size_t i = 0; i < (size_t)MX*MY; ++i) {zmin = min_std(zmin, h[i]); zmax = max_std(zmax, h[i]);}
 		// estimate_zminmax(using_eq=1) (src/mesh_gen.cpp:447-485)
 		set_zmax_est(max_std(zmax, -zmin));
-		if (zmax == zmin) {set_zmax_est((float)((double)zmax_est + 1.0E-6));}
+		if (zmax == zmin) {set_zmax_est((float)((double)zmax_est + 1.0E-6)); set_height_histogram(nullptr, 0);}
 		else {
 			float const rm_scale = (float)(1000.0*(double)XY_SCENE_SIZE/(double)mesh_scale);
 			gen_grid_dev(0.0f, 0.0f, rm_scale, rm_scale, 128, 128, 0, 0, d);
 			be.d2h(h.data(), d, 128*128*sizeof(float));
 			float ze = zmax_est;
 			for (size_t i = 0; i < 128*128; ++i) {ze = max_std(ze, fabsf(h[i]));}
+			std::vector<float> hist; // height_histogram: 1/16 of the values, sorted (src/mesh_gen.cpp:471-480)
+			for (unsigned i = 0; i < 128; i += 4) {for (unsigned j = 0; j < 128; j += 4) {hist.push_back(h[i*128 + j]);}}
+			std::sort(hist.begin(), hist.end());
+			set_height_histogram(hist.data(), (uint32_t)hist.size());
 			if (mode != MGEN_SINE) {ze = (float)((double)ze*1.2);}
 			set_zmax_est((float)(1.1*(double)ze));
 			set_zvals();
@@ -2273,6 +2301,100 @@ template<class BE> struct terra_engine {
 		uint32_t const *in = (uint32_t const *)d_mesh_weights; uint32_t *out = (uint32_t *)d_weights;
 		if (be.tile_tree_weights(ntex, in, d_tree_map, out)) return;
 		be.launch(ntex, [=] TERRA_LAMBDA (size_t i) {out[i] = tree_weights_texel(in[i], d_tree_map[2*i]);});
+	}
+
+	// ---- pine / palm tree placement (terra_treeplace.hpp): small_tree_group::gen_trees from src/sm_tree.cpp:439 on, or gen_trees_tt_within_radius (:477-502) when
+	// `brush` = {pos.x, pos.y, radius, is_square} is given, for every tile of the batch.  false: no tile can have a tree (:439; the brush form never divides by a zero
+	// sm_tree_density either).  Throws where the reference would leave the per-cell path: see include/terra.h.
+	bool tree_place_consts(int xoff2, int yoff2, float const *brush, std::vector<float> &sums, tree_place_consts_t &c) {
+		if (using_hmap()) throw std::logic_error("tiles_place_trees: a heightmap texture is set (the texture-height branch of maybe_add_tree is not part of this call)");
+		if (tp.sm_tree_density == 0.0f || !(tp.tree_mode & 2) || (!brush && ls.vegetation == 0.0f)) return false;
+		int const S = (int)tile_size();
+		c.nc = consts(); c.L = lut(); c.st = nullptr; c.hist = nullptr; c.sums = nullptr; c.nhist = (uint32_t)height_histogram.size();
+		c.mode = mode; c.shape = shape; c.k0 = start_eval_sin;
+		c.S = S; c.xoff2 = xoff2; c.yoff2 = yoff2; c.xy_mult = cfg.mesh_x*cfg.mesh_y; c.half_x = cfg.mesh_x >> 1; c.half_y = cfg.mesh_y >> 1;
+		c.xss = cfg.scene_x; c.yss = cfg.scene_y; c.DX_VAL = DX_VAL; c.DY_VAL = DY_VAL; c.msc = mesh_scale; c.mszi = mesh_scale_z_inv; c.bxo = ls.biome_x_offset;
+		float const tscale = (cfg.scene_z*tp.tree_scale)/16.0f; // calc_tree_scale (:325)
+		c.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale;             // calc_tree_size (:326)
+		c.ntrees_mult = brush ? tp.sm_tree_density*tscale*tscale/8.0f : ls.vegetation*tp.sm_tree_density*tscale*tscale/8.0f; // (:481, :442)
+		double const sv = 1.0/(double)sqrtf(tp.sm_tree_density*tp.tree_scale); // int(1.0/(sqrt(sm_tree_density*tree_scale))): float sqrt, double quotient (:443)
+		if (!(sv < 2147483648.0)) throw std::invalid_argument("tiles_place_trees: 1/sqrt(sm_tree_density*tree_scale) does not fit an int (skip_val)");
+		c.skip_val = imax(1, (int)sv); // may exceed S: the loop then visits cell (0, 0) alone, and maybe_add_tree's offsets still scale with skip_val (:383-384)
+		c.ncell = (c.skip_val >= S) ? 1 : (S + c.skip_val - 1)/c.skip_val;
+		c.thresh = tp.tree_density_thresh; c.rand_zone = tp.tree_type_rand_zone; c.water_plane_z = water_plane_z; c.relh_adj_tex = relh_adj_tex;
+		c.glaciate_exp_inv = (float)(1.0/(double)glaciate_exp); // src/mesh_gen.cpp:393
+		float const tds = (float)((double)TREE_DIST_SCALE*((double)c.xy_mult/16384.0)); // (:447)
+		c.xscale = tds*DX_VAL*DX_VAL; c.yscale = tds*DY_VAL*DY_VAL;
+		c.tree_mode = tp.tree_mode; c.force_class = tp.force_tree_class; c.only_pine_palm = tp.only_pine_palm_trees; c.rand_gen_index = tp.rand_gen_index;
+		c.instanced = tp.instanced ? 1 : 0; c.num_pine = (int)tp.num_pine_insts; c.num_palm = (int)tp.num_palm_insts;
+		c.approx_zval = (!brush && (mode == MGEN_SINE || (double)c.ntrees_mult > 0.025)) ? 1 : 0; // (:446; world_mode == WMODE_INF_TERRAIN, no heightmap texture)
+		c.terrain_env = ls.enable_terrain_env;
+		c.brush = brush ? 1 : 0; c.bx = brush ? brush[0] : 0.0f; c.by = brush ? brush[1] : 0.0f; c.brad = brush ? brush[2] : 0.0f; c.is_square = (brush && brush[3] != 0.0f) ? 1 : 0;
+		// the running sums: xv += dxv from 0 on, once per visited column, and the same per row (dxv == dyv: x2 - x1 == y2 - y1 == S)
+		float const dxv = (float)c.skip_val/((float)S - 1.0f);
+		sums.resize(c.ncell);
+		float v = 0.0f;
+		for (int k = 0; k < c.ncell; ++k) {sums[k] = v; v += dxv;}
+		// Every cell must re-seed the generator: XY_MULT_SIZE >= 2*ntrees (:370).  ntrees = int(min(1, cur_density*ntrees_mult)*40000) grows with cur_density, and
+		// |cur_density| <= 1.001: the corners are CLIP_TO_01 values; a running sum is at most (S - 1) steps of fl(skip/(S - 1)), so it lies in [0, 1 + 1e-4] (true value
+		// <= 1, S <= 1024 roundings of 2^-24 each); then |xv*a + (1 - xv)*b| <= (xv + |1 - xv|)*max(a, b) <= 1 + 2e-4, twice, times (1 + 2^-23)^6 for the six float
+		// roundings: below 1.001.  The brush form passes ntrees_mult itself.
+		if (!(c.ntrees_mult >= 0.0f)) throw std::invalid_argument("tiles_place_trees: vegetation*sm_tree_density must not be negative");
+		int const ntrees_max = (int)(min_std(1.0f, (brush ? 1.0f : 1.001f)*c.ntrees_mult)*(float)NUM_SMALL_TREES);
+		if (c.xy_mult < 2*ntrees_max) {
+			throw std::invalid_argument("tiles_place_trees: XY_MULT_SIZE = " + std::to_string(c.xy_mult) + " < 2*ntrees = " + std::to_string(2*ntrees_max) +
+				": the reference then does not re-seed per cell (its sequence runs serially through the tile)");
+		}
+		return true;
+	}
+	void tiles_place_trees_dev(int32_t const *tile_xy, uint32_t n, int xoff2, int yoff2, uint8_t const *d_skip, terra_tile_stats const *d_stats, float const *brush,
+		uint32_t capacity, tree_place_pod_t *d_trees, uint32_t *d_counts)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		tree_place_consts_t c;
+		std::vector<float> sums;
+		bool const any = tree_place_consts(xoff2, yoff2, brush, sums, c);
+		if (capacity && !d_trees) throw std::invalid_argument("tiles_place_trees: null d_trees");
+		if (((uintptr_t)d_trees & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0) throw std::invalid_argument("tiles_place_trees: d_trees and d_counts must be 4-byte aligned");
+		if (!any) {be.fill32(d_counts, 0u, n); return;}
+		// only (tx, ty) of a tile reference is read here: no tables, no sort of the distinct columns and rows
+		std::vector<tile_ref_pod_t> refs(n);
+		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
+		size_t const sb = (sums.size()*sizeof(float) + 255) & ~(size_t)255, kb = (sizeof(tree_place_consts_t) + 255) & ~(size_t)255, rb = ((size_t)n*sizeof(tile_ref_pod_t) + 255) & ~(size_t)255;
+		uint8_t *base = scratch<uint8_t>(s_ao, sb + kb + rb + (size_t)n*4*sizeof(float));
+		float *d_sums = (float *)base, *d_dens = (float *)(base + sb + kb + rb);
+		tree_place_consts_t *d_consts = (tree_place_consts_t *)(base + sb); // the kernel reads its constants from memory: by value they fill the scalar registers
+		tile_ref_pod_t *d_refs_w = (tile_ref_pod_t *)(base + sb + kb);
+		be.h2d_async(d_refs_w, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
+		tile_ref_pod_t const *d_refs = d_refs_w;
+		be.h2d_async(d_sums, sums.data(), sums.size()*sizeof(float));
+		c.st = sinTable_dev(); c.hist = height_histogram_dev(); c.sums = d_sums;
+		tree_place_consts_t const cc = c;
+		be.h2d_async(d_consts, &cc, sizeof(cc));
+		if (!brush) {be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cc, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});}
+		if (be.tile_place_trees(d_consts, d_refs, n, d_dens, d_skip, d_stats, capacity, d_trees, d_counts)) return;
+		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			tile_ref_pod_t const r = d_refs[t];
+			float dens[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+			if (!cc.brush) {for (int k = 0; k < 4; ++k) {dens[k] = d_dens[4*t + k];}}
+			uint32_t count = 0;
+			if (tree_tile_live(cc, dens, d_skip && d_skip[t], d_stats != nullptr, d_stats ? d_stats[t].mzmin : 0.0f, d_stats ? d_stats[t].mzmax : 0.0f)) {
+				for (unsigned iy = 0; iy < (unsigned)cc.ncell; ++iy) {
+					for (unsigned ix = 0; ix < (unsigned)cc.ncell; ++ix) {
+						tree_rgen_t rg;
+						if (!tree_cell_selected(cc, dens, r.tx, r.ty, ix, iy, rg)) continue;
+						tree_place_pod_t o;
+						if (!tree_cell_finish(cc, r.tx, r.ty, ix, iy, rg, o)) continue;
+						if (count < capacity) {d_trees[(size_t)t*capacity + count] = o;}
+						++count;
+					}
+				}
+			}
+			d_counts[t] = count;
+		});
 	}
 
 	// ================================================================ voxels (a14, a15, K8, K9)

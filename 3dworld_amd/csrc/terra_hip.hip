@@ -574,6 +574,16 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// tree placement: one workgroup per tile (k_tree_place)
+	bool tile_place_trees(terra::tree_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
+		uint32_t capacity, terra::tree_place_pod_t *trees, uint32_t *counts)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_tree_place, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, dens, skip, stats, capacity, trees, counts);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

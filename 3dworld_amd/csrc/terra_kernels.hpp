@@ -1485,6 +1485,80 @@ __global__ __launch_bounds__(256) void k_tree_weights(size_t ntex, uint32_t cons
 	out[i] = tree_weights_texel(in[i], tree[2*i]);
 }
 
+// ------------------------------------------------------------------ tree placement (small_tree_group::gen_trees, src/sm_tree.cpp:439-474; terra_treeplace.hpp)
+// One workgroup per tile, so that the tile's trees come out in the reference's loop order without atomics.  The loop's cells are taken 256 at a time, row-major:
+// every thread runs the selection of get_ntrees_for_mesh_xy for its cell (three generator steps and a modulo; about one cell in fifty passes at the defaults) and
+// the survivors' cell numbers go, in order, into a ring in LDS.  Whenever the ring holds 256 of them (and once more at the end) every thread takes one and runs the
+// expensive rest -- the 80-term density field, the histogram test, maybe_add_tree with its zval -- so the lanes stay busy; the trees that come out of a batch
+// are written behind those of the batches before.  Both compactions are a ballot per wave plus a prefix over the four waves.
+// Where the time goes (kernel trace, 4096 tiles at S = 128, sine mode): the survivors, not the selection.  A survivor's two fields are 2 x 80 terms of two SINF
+// look-ups each, and a look-up is a gather from the 128 KB table that no two lanes share; four cells per thread in the selection made the kernel slower (443 us
+// against 353: one wave less per SIMD to hide those gathers behind).
+constexpr uint32_t TREEP_THREADS = 256, TREEP_RING = 512;
+// rank of the calling thread among the block's threads with `flag`, in thread order, and their number; two barriers
+__device__ __forceinline__ uint32_t tp_block_rank(bool flag, uint32_t *s_wave, uint32_t &total) {
+	uint32_t const lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	unsigned long long const m = __ballot(flag);
+	if (lane == 0) {s_wave[w] = (uint32_t)__popcll(m);}
+	__syncthreads();
+	uint32_t before = 0, all = 0;
+	for (uint32_t k = 0; k < TREEP_THREADS/64; ++k) {uint32_t const v = s_wave[k]; all += v; if (k < w) {before += v;}}
+	__syncthreads();
+	total = all;
+	return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+__global__ __launch_bounds__(TREEP_THREADS) void k_tree_place(tree_place_consts_t const *__restrict__ consts, tile_ref_pod_t const *__restrict__ tiles, float const *__restrict__ d_dens,
+	uint8_t const *__restrict__ skip, terra_tile_stats const *__restrict__ stats, uint32_t capacity, tree_place_pod_t *__restrict__ trees, uint32_t *__restrict__ counts)
+{
+	__shared__ uint32_t s_ring[TREEP_RING], s_wave[TREEP_THREADS/64];
+	tree_place_consts_t const &c = *consts;
+	uint32_t const t = blockIdx.x, tid = threadIdx.x;
+	tile_ref_pod_t const r = tiles[t];
+	float dens[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+	if (!c.brush) {for (int k = 0; k < 4; ++k) {dens[k] = d_dens[4*(size_t)t + k];}}
+	// (uniform over the block)
+	if (!tree_tile_live(c, dens, skip && skip[t], stats != nullptr, stats ? stats[t].mzmin : 0.0f, stats ? stats[t].mzmax : 0.0f)) {
+		if (tid == 0) {counts[t] = 0;}
+		return;
+	}
+	uint32_t const ncell = (uint32_t)c.ncell, ncells = ncell*ncell;
+	tree_place_pod_t *const out = trees + (size_t)t*capacity;
+	uint32_t head = 0, tail = 0, count = 0; // ring [head, tail) and the tile's trees so far: the same in every thread
+	for (uint32_t base = 0; base < ncells || head < tail; base += TREEP_THREADS) {
+		if (base < ncells) {
+			uint32_t const cell = base + tid;
+			bool sel = false;
+			if (cell < ncells) {
+				uint32_t const iy = cell/ncell, ix = cell - iy*ncell;
+				tree_rgen_t rg;
+				sel = tree_cell_selected(c, dens, r.tx, r.ty, ix, iy, rg);
+			}
+			uint32_t nsel;
+			uint32_t const rank = tp_block_rank(sel, s_wave, nsel);
+			if (sel) {s_ring[(tail + rank) & (TREEP_RING - 1)] = cell;}
+			tail += nsel;
+			__syncthreads();
+		}
+		bool const last = base + TREEP_THREADS >= ncells;
+		if (tail - head < TREEP_THREADS && !(last && head < tail)) continue; // (fewer than 256 pending and more cells to come)
+		uint32_t const nb = (tail - head < TREEP_THREADS) ? tail - head : TREEP_THREADS;
+		bool ok = false;
+		tree_place_pod_t o;
+		if (tid < nb) {
+			uint32_t const cell = s_ring[(head + tid) & (TREEP_RING - 1)], iy = cell/ncell, ix = cell - iy*ncell;
+			tree_rgen_t rg;
+			tree_cell_selected(c, dens, r.tx, r.ty, ix, iy, rg); // (the generator as the selection left it: cheaper to redo than to keep)
+			ok = tree_cell_finish(c, r.tx, r.ty, ix, iy, rg, o);
+		}
+		head += nb;
+		uint32_t ntree;
+		uint32_t const rank = tp_block_rank(ok, s_wave, ntree);
+		if (ok && count + rank < capacity) {out[count + rank] = o;}
+		count += ntree;
+	}
+	if (tid == 0) {counts[t] = count;}
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

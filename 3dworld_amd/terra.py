@@ -57,6 +57,22 @@ LINE_HIT_DTYPE = np.dtype([("t", np.float32), ("tile", np.int32), ("xpos", np.in
 assert LINE_HIT_DTYPE.itemsize == 32
 TREE_SPLAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("radius", np.float32)])  # terra_tree_splat
 assert TREE_SPLAT_DTYPE.itemsize == 12
+TREE_PLACE_DTYPE = np.dtype([("pos", np.float32, (3,)), ("type", np.int32), ("inst", np.int32), ("height", np.float32), ("width", np.float32),
+                             ("rseed1", np.int32), ("rseed2", np.int32), ("cx", np.uint16), ("cy", np.uint16)])  # terra_tree_place
+assert TREE_PLACE_DTYPE.itemsize == 40
+
+
+class TreeParams(C.Structure):  # terra_tree_params
+    _fields_ = [("sm_tree_density", C.c_float), ("tree_scale", C.c_float), ("tree_density_thresh", C.c_float), ("tree_type_rand_zone", C.c_float),
+                ("tree_mode", C.c_int32), ("force_tree_class", C.c_int32), ("only_pine_palm_trees", C.c_int32), ("rand_gen_index", C.c_int32),
+                ("instanced", C.c_int32), ("num_pine_insts", C.c_uint32), ("num_palm_insts", C.c_uint32)]
+
+
+def make_tree_params(sm_tree_density=1.0, tree_scale=1.0, tree_density_thresh=0.55, tree_type_rand_zone=0.0, tree_mode=1, force_tree_class=-1,
+                     only_pine_palm_trees=0, rand_gen_index=0, instanced=0, num_pine_insts=0, num_palm_insts=0):
+    """terra_tree_params with the reference's defaults (tree_mode 1: no small trees)."""
+    return TreeParams(sm_tree_density, tree_scale, tree_density_thresh, tree_type_rand_zone, tree_mode, force_tree_class, only_pine_palm_trees, rand_gen_index,
+                      int(bool(instanced)), num_pine_insts, num_palm_insts)
 
 
 class GRASS_BRUSH(C.Structure):
@@ -203,6 +219,14 @@ _PROTOS = {
     "terra_tiles_shadow_texture": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _f, _i32, _vp]),
     "terra_tiles_tree_weights_dev": (_i32, [_vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_tree_weights": (_i32, [_vp, _u32, _vp, _vp, _vp]),
+    "terra_set_tree_params": (_i32, [_vp, _vp]),
+    "terra_get_tree_params": (_i32, [_vp, _vp]),
+    "terra_set_height_histogram": (_i32, [_vp, _vp, _u32]),
+    "terra_get_height_histogram": (_i32, [_vp, _vp, _u32, _vp]),
+    "terra_tiles_place_trees_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _u32, _vp, _vp]),
+    "terra_tiles_place_trees": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _u32, _vp, _vp]),
+    "terra_tiles_place_trees_brush_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
+    "terra_tiles_place_trees_brush": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -678,6 +702,42 @@ class Terra:
         self._ck(self.lib.terra_tiles_tree_weights(self.ctx, n, w.ctypes.data, None if tm is None else tm.ctypes.data, out.ctypes.data))
         return out
 
+    def set_tree_params(self, tp):
+        self._ck(self.lib.terra_set_tree_params(self.ctx, C.byref(tp)))
+
+    def get_tree_params(self):
+        tp = TreeParams()
+        self._ck(self.lib.terra_get_tree_params(self.ctx, C.byref(tp)))
+        return tp
+
+    def set_height_histogram(self, vals):
+        """height_histogram (sorted, any length; empty: get_median_height returns its argument)"""
+        v = np.ascontiguousarray(vals, np.float32).reshape(-1)
+        self._ck(self.lib.terra_set_height_histogram(self.ctx, v.ctypes.data if len(v) else None, len(v)))
+
+    def get_height_histogram(self):
+        n = _u32()
+        self._ck(self.lib.terra_get_height_histogram(self.ctx, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.float32)
+        self._ck(self.lib.terra_get_height_histogram(self.ctx, out.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def tiles_place_trees(self, tile_xy, capacity, xoff2=0, yoff2=0, skip=None, stats=None, brush=None):
+        """small_tree_group::gen_trees for every tile, or gen_trees_tt_within_radius with brush = (pos[3], radius, is_square).  skip: [n] bytes (can_have_trees()
+        false), stats: the TileStats array of tiles_create_zvals.  -> (trees TREE_PLACE_DTYPE [n, capacity], counts uint32 [n]); records past counts[t] are zero"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        trees, counts = np.zeros((n, capacity), TREE_PLACE_DTYPE), np.zeros(n, np.uint32)
+        args = (self.ctx, txy.ctypes.data, n, xoff2, yoff2, None if sk is None else sk.ctypes.data, None if stats is None else C.addressof(stats))
+        tail = (capacity, trees.ctypes.data if capacity else None, counts.ctypes.data)
+        if brush is None:
+            self._ck(self.lib.terra_tiles_place_trees(*args, *tail))
+        else:
+            pos, radius, is_square = brush
+            self._ck(self.lib.terra_tiles_place_trees_brush(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), *tail))
+        return trees, counts
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -827,6 +887,17 @@ class Terra:
     def tiles_tree_weights_dev(self, n, mesh_weights_ptr, tree_map_ptr, weights_ptr):
         """weight_data from mesh_weight_data and the tree map on the device; weights_ptr may be mesh_weights_ptr.  Only enqueues."""
         self._ck(self.lib.terra_tiles_tree_weights_dev(self.ctx, n, mesh_weights_ptr, tree_map_ptr, weights_ptr))
+
+    def tiles_place_trees_dev(self, tile_xy, capacity, trees_ptr, counts_ptr, xoff2=0, yoff2=0, skip_ptr=None, stats_ptr=None, brush=None):
+        """tree placement of a device-resident batch: trees_ptr [n][capacity] TREE_PLACE_DTYPE records, counts_ptr [n] uint32, skip_ptr [n] bytes / stats_ptr [n]
+        terra_tile_stats (or None).  brush = (pos[3], radius, is_square) for the brush form.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        args = (self.ctx, txy.ctypes.data, len(txy), xoff2, yoff2, skip_ptr, stats_ptr)
+        if brush is None:
+            self._ck(self.lib.terra_tiles_place_trees_dev(*args, capacity, trees_ptr, counts_ptr))
+        else:
+            pos, radius, is_square = brush
+            self._ck(self.lib.terra_tiles_place_trees_brush_dev(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), capacity, trees_ptr, counts_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

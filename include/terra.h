@@ -518,6 +518,80 @@ int  terra_tiles_shadow_texture(terra_ctx *ctx, uint32_t n, const uint8_t *h_sma
 int  terra_tiles_tree_weights_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_mesh_weights, const uint8_t *d_tree_map, uint8_t *d_weights);
 int  terra_tiles_tree_weights(terra_ctx *ctx, uint32_t n, const uint8_t *h_mesh_weights, const uint8_t *h_tree_map, uint8_t *h_weights);
 
+/* ---- pine / palm tree placement of a tile batch (every supported tile size S): the generating half of "Add Trees" and of tile_t::init_pine_tree_draw
+ * (src/tiled_mesh.cpp:1430-1437).  The chain zvals -> tree placement -> splat lists -> tree map -> shadow texture and weights then runs without the host in between.
+ * terra_tree_params: the globals this path reads beyond the scene (water_plane_z, zmax_est, glaciate_exp, relh_adj_tex: terra_state) and the landscape (vegetation,
+ * biome_x_offset, enable_terrain_env: terra_landscape).  The defaults are the reference's; with tree_mode 1 no call places a tree.
+ * TERRA_ERR_ARG: sm_tree_density < 0, tree_scale <= 0, tree_mode outside 0 .. 3, force_tree_class outside -1 .. 3 (TREE_CLASS_DETAILED has no small tree type:
+ * get_tree_type_from_height asserts), instanced with an empty or oversized (> 2^30) instance range (select_inst asserts start < end), instanced with
+ * force_tree_class 2 (maybe_add_tree asserts pine or palm). */
+typedef struct terra_tree_params {
+	float sm_tree_density;       /* config "sm_tree_density", 1 */
+	float tree_scale;            /* config "tree_scale" (src/mesh_gen.cpp:37), 1 */
+	float tree_density_thresh;   /* config "tree_density_thresh", 0.55 */
+	float tree_type_rand_zone;   /* config "tree_type_rand_zone", 0 */
+	int32_t tree_mode;           /* 0 .. 3; bit 2 = small trees (small_trees_enabled), 3 = palms too; 1 */
+	int32_t force_tree_class;    /* -1 = by height, else TREE_CLASS_{NONE 0, PINE 1, DECID 2, PALM 3} (src/tree_3dw.h:20) */
+	int32_t only_pine_palm_trees;
+	int32_t rand_gen_index;
+	int32_t instanced;           /* what enable_instanced_pine_trees() returned (src/tiled_mesh.cpp:154-159) */
+	uint32_t num_pine_insts;     /* num_insts_per_type[T_PINE] = [0, num_pine_insts) (shared by T_SH_PINE), [T_PALM] = [num_pine_insts, num_pine_insts + num_palm_insts) */
+	uint32_t num_palm_insts;     /* (create_pine_tree_instances, src/sm_tree.cpp:342-364) */
+} terra_tree_params;
+int  terra_set_tree_params(terra_ctx *ctx, const terra_tree_params *params);
+int  terra_get_tree_params(terra_ctx *ctx, terra_tree_params *out);
+/* height_histogram (src/mesh_gen.cpp:467-480), what get_median_height (:487-491) reads: terra_init_scene keeps the 1024 sorted values of its own estimate grid
+ * (every fourth value in both directions); an engine that owns its globals (terra_set_state) passes its vector, of any length (the reference never clears it: two
+ * estimates leave 2048 values).  Every terra_init_scene REPLACES the values with those of its own estimate (none when zmax == zmin: the reference returns before
+ * the grid then) instead of appending to them: an engine that mirrors a vector grown over several estimates calls the setter after terra_init_scene.
+ * count == 0 is the empty vector: get_median_height then returns its argument.  get: *count = the length; up to `capacity` values
+ * are written when h_vals is not NULL. */
+int  terra_set_height_histogram(terra_ctx *ctx, const float *h_vals, uint32_t count);
+int  terra_get_height_histogram(terra_ctx *ctx, float *h_vals, uint32_t capacity, uint32_t *count);
+/* terra_tiles_place_trees: small_tree_group::gen_trees (src/sm_tree.cpp:407-474) from :439 on for every tile, as tile_t::init_pine_tree_draw calls it, bit for bit:
+ * the running xv / yv sums (:455-470), the bilinear cur_density over density[4] = params[..].veg (generated internally, as for terra_tiles_create_weights),
+ * get_ntrees_for_mesh_xy (:366-376), density_gen.eval_index, the get_median_height test (:466), and maybe_add_tree (:378-404) with zpos from the glaciated
+ * height_gen.eval_index when approx_zval (:446) and from get_exact_zval otherwise, get_tree_type_from_height (:527-566) and select_inst or rand_tree_height /
+ * rand_tree_width.  xoff2 / yoff2: the loop runs over the local indices x1 - xoff2 .. (ptree_off.set_from_xyoff2()), seeds and field origins use j + xoff2,
+ * get_xval(j) the local j.
+ * skip (optional): [n] bytes, non-zero = can_have_trees() is false.  stats (optional): a tile failing can_have_pine_palm_trees_in_zrange(mzmin, mzmax) (:568-578,
+ * no tree placer) gets no trees.  trees: [n][capacity] records; counts: [n].  The trees of a tile appear in the reference's loop order (rows, then columns); a tile
+ * with more than `capacity` trees gets the first `capacity` and counts[t] still reports all of them.  Records past counts[t] are not written.
+ * With the engine stay check_valid_scenery_pos and point_inside_voxel_terrain (:399, :402; they draw no random numbers, so filtering the records afterwards is
+ * identical), the tree placer block (:412-438), the small_tree constructor (for a tree that is not instanced, from the generator state in the record),
+ * postproc_trees and deciduous trees.
+ * Zero trees everywhere (:439-440): vegetation == 0, sm_tree_density == 0, bit 2 of tree_mode clear; per tile: all four density corners 0.
+ * TERRA_ERR_ARG when some cell could have XY_MULT_SIZE < 2*ntrees: the reference then does not re-seed its generator per cell (:370), the sequence runs serially
+ * through the tile and trees_this_xy can exceed 1.  The test, on the host: ntrees = int(min(1, cur_density*ntrees_mult)*40000) with cur_density = 1.001, which
+ * covers every cell (corners are CLIP_TO_01 values, a running sum stays within [0, 1 + 1e-4], six float roundings).  At the defaults ntrees <= 312 against
+ * XY_MULT_SIZE = 16384; S = 16 is refused (624 > 256).  skip_val = int(1/sqrt(sm_tree_density*tree_scale)) may exceed S: cell (0, 0) alone is visited then and
+ * the position offsets still scale with skip_val; a quotient that does not fit an int (undefined in the reference) is TERRA_ERR_ARG.
+ * Also TERRA_ERR_ARG: vegetation*sm_tree_density < 0, an unsupported S, a NULL required pointer (tile_xy,
+ * counts when n > 0; trees when capacity > 0), a misaligned pointer.
+ * TERRA_ERR_STATE before terra_init_scene, and while a heightmap texture is set (check_hmap_normal and the texture heights of get_exact_zval are not part of this
+ * call).  n == 0 does nothing once the scene and the tile size have passed: the settings are not looked at.  The device form only enqueues. */
+typedef struct terra_tree_place {
+	float pos[3];            /* xval, yval, zpos */
+	int32_t type;            /* T_PINE 0, T_DECID 1 .. 3 (force_tree_class 2 only), T_PALM 4, T_SH_PINE 5 (src/small_tree.h:9) */
+	int32_t inst;            /* select_inst's result, -1 when not instanced */
+	float height, width;     /* tsize*rand_tree_height, height*rand_tree_width; 0 when instanced */
+	int32_t rseed1, rseed2;  /* the generator where the reference constructs the small_tree */
+	uint16_t cx, cy;         /* the cell inside the tile */
+} terra_tree_place;          /* 40 bytes */
+int  terra_tiles_place_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                 uint32_t capacity, terra_tree_place *d_trees, uint32_t *d_counts);
+int  terra_tiles_place_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                             uint32_t capacity, terra_tree_place *h_trees, uint32_t *h_counts);
+/* terra_tiles_place_trees_brush: gen_trees_tt_within_radius (:477-502) as tile_t::add_new_trees (src/tiled_mesh.cpp:3805-3811) calls it, xoff2 / yoff2 = -toff.dxoff /
+ * -toff.dyoff: the same cell with ntrees_mult without vegetation, no density field, one discarded rand_float, zpos always from get_exact_zval, and the fabs /
+ * dist_xy_less_than test of the cell's centre against pos (x and y are read) and radius; is_square = (brush_shape == BSHAPE_CONST_SQ).  The caller keeps the
+ * mesh_sphere_intersect culls and the removal loop (:3822-3838).  skip / stats: can_have_pine_palm_trees() as above.  Zero trees: sm_tree_density == 0 or bit 2
+ * of tree_mode clear.  Refusals as above, the bound on ntrees taken at ntrees_mult itself. */
+int  terra_tiles_place_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                       const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *d_trees, uint32_t *d_counts);
+int  terra_tiles_place_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                                   const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *h_trees, uint32_t *h_counts);
+
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or
  * MESH_SHADOW (0x02).  Shadows cross tile borders: a tile starts its sweeps from the edge heights left by its neighbours toward the light when those are

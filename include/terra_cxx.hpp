@@ -241,6 +241,25 @@ inline void tiles_upload_shadow_map_texture(unsigned n, unsigned char const *d_s
 inline void tiles_create_texture_tree_weights(unsigned n, unsigned char const *d_mesh_weight_data, unsigned char const *d_tree_map, unsigned char *d_weight_data) {
 	check(terra_tiles_tree_weights_dev(default_ctx(), n, d_mesh_weight_data, d_tree_map, d_weight_data), "create_texture");
 }
+// ---- pine / palm tree placement of a batch on device arrays.  The globals of src/sm_tree.cpp:29-33 go in once (set_tree_globals: sm_tree_density, tree_scale,
+// tree_density_thresh, tree_type_rand_zone, tree_mode, force_tree_class, only_pine_palm_trees, rand_gen_index, enable_instanced_pine_trees() and the two ranges of
+// num_insts_per_type); an engine that owns height_histogram passes it with terra_set_height_histogram.
+inline void set_tree_globals(terra_tree_params const &p) {check(terra_set_tree_params(default_ctx(), &p), "set_tree_params");}
+// small_tree_group::gen_trees (src/sm_tree.cpp:407-474, from :439 on) for every tile as tile_t::init_pine_tree_draw (src/tiled_mesh.cpp:1430-1437) calls it: xoff2 /
+// yoff2 are the globals at that time (ptree_off.set_from_xyoff2()).  d_can_have_trees_false[t] != 0: can_have_trees() is false; b.d_stats (may be null):
+// can_have_pine_palm_trees_in_zrange(mzmin, mzmax).  d_trees [n][capacity], d_counts [n]: the engine filters each record with check_valid_scenery_pos /
+// point_inside_voxel_terrain and constructs the small_tree (instanced: from inst; else from height, width, type and the generator state rseed1 / rseed2)
+inline void tiles_gen_trees(tile_batch_dev_t const &b, int xoff2, int yoff2, unsigned char const *d_can_have_trees_false, unsigned capacity, terra_tree_place *d_trees, unsigned *d_counts) {
+	check(terra_tiles_place_trees_dev(default_ctx(), b.tile_xy, b.n, xoff2, yoff2, d_can_have_trees_false, b.d_stats, capacity, d_trees, d_counts), "gen_trees");
+}
+// small_tree_group::gen_trees_tt_within_radius (:477-502) as tile_t::add_new_trees (src/tiled_mesh.cpp:3805-3811) calls it: toff_dxoff / toff_dyoff = ptree_off's
+// members (the call runs with xoff2 = -toff.dxoff), pos = pt_pos, is_square = (brush_shape == BSHAPE_CONST_SQ)
+inline void tiles_gen_trees_tt_within_radius(tile_batch_dev_t const &b, int toff_dxoff, int toff_dyoff, unsigned char const *d_can_have_trees_false, float const pos[3], float radius,
+	bool is_square, unsigned capacity, terra_tree_place *d_trees, unsigned *d_counts)
+{
+	check(terra_tiles_place_trees_brush_dev(default_ctx(), b.tile_xy, b.n, -toff_dxoff, -toff_dyoff, d_can_have_trees_false, b.d_stats, pos, radius, is_square ? 1 : 0, capacity, d_trees, d_counts),
+		"gen_trees_tt_within_radius");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
