@@ -779,6 +779,64 @@ int terra_tiles_place_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32
 	float const brush[4] = {pos[0], pos[1], radius, is_square ? 1.0f : 0.0f};
 	return tiles_place_trees_impl(ctx, tile_xy, n, xoff2, yoff2, h_skip, h_stats, brush, capacity, h_trees, h_counts, true);
 }
+int terra_set_decid_params(terra_ctx *ctx, const terra_decid_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_decid_params(*params); TERRA_CATCH
+}
+int terra_get_decid_params(terra_ctx *ctx, terra_decid_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	*out = ctx->eng.dp; return TERRA_OK;
+}
+static_assert(sizeof(terra_decid_place) == 36 && sizeof(terra::decid_place_pod_t) == 36, "terra_decid_place layout");
+static int tiles_place_decid_trees_impl(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *skip, const terra_tile_stats *stats,
+	const float *zvals, const float *brush, uint32_t capacity, terra_decid_place *trees, uint32_t *counts, bool host)
+{
+	TERRA_CHECK_CTX if (n && (!tile_xy || !counts || (capacity && !trees))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		if (!host) {ctx->eng.tiles_place_decid_trees_dev(tile_xy, n, xoff2, yoff2, skip, stats, zvals, brush, capacity, (terra::decid_place_pod_t *)trees, counts); return TERRA_OK;}
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size();
+		if (n && stats && !zvals) throw std::invalid_argument("tiles_place_decid_trees: stats without zvals (the slope test reads the tile's heights)");
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const Z = (size_t)ctx->eng.tile_size() + 2;
+		size_t const tb = (size_t)n*capacity*sizeof(terra_decid_place), cb = (size_t)n*4, kb = n, sb = (size_t)n*sizeof(terra_tile_stats), zb = zvals ? (size_t)n*Z*Z*sizeof(float) : 0;
+		size_t const ot = 0, oc = ot + up(tb), ok = oc + up(cb), os = ok + up(kb), oz = os + up(sb);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oz + up(zb));
+		if (n && skip) {be.h2d(d + ok, skip, kb);}
+		if (n && stats) {be.h2d(d + os, stats, sb);}
+		if (n && zvals) {be.h2d(d + oz, zvals, zb);}
+		ctx->eng.tiles_place_decid_trees_dev(tile_xy, n, xoff2, yoff2, skip ? d + ok : nullptr, stats ? (terra_tile_stats const *)(d + os) : nullptr,
+			zvals ? (float const *)(d + oz) : nullptr, brush, capacity, (terra::decid_place_pod_t *)(d + ot), (uint32_t *)(d + oc));
+		if (n == 0) return TERRA_OK;
+		be.d2h(counts, d + oc, cb);
+		// only the records the counts name were written: the rest of the caller's array stays as it was
+		for (uint32_t t = 0; t < n; ++t) {
+			uint32_t const m = std::min(counts[t], capacity);
+			if (m) {be.d2h(trees + (size_t)t*capacity, d + ot + (size_t)t*capacity*sizeof(terra_decid_place), (size_t)m*sizeof(terra_decid_place));}
+		}
+	TERRA_CATCH
+}
+int terra_tiles_place_decid_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                      const float *d_zvals, uint32_t capacity, terra_decid_place *d_trees, uint32_t *d_counts) {
+	return tiles_place_decid_trees_impl(ctx, tile_xy, n, xoff2, yoff2, d_skip, d_stats, d_zvals, nullptr, capacity, d_trees, d_counts, false);
+}
+int terra_tiles_place_decid_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                                  const float *h_zvals, uint32_t capacity, terra_decid_place *h_trees, uint32_t *h_counts) {
+	return tiles_place_decid_trees_impl(ctx, tile_xy, n, xoff2, yoff2, h_skip, h_stats, h_zvals, nullptr, capacity, h_trees, h_counts, true);
+}
+int terra_tiles_place_decid_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                            const float *d_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *d_trees, uint32_t *d_counts) {
+	if (!pos) return terra::fail(TERRA_ERR_ARG, "null argument");
+	float const brush[4] = {pos[0], pos[1], radius, is_square ? 1.0f : 0.0f};
+	return tiles_place_decid_trees_impl(ctx, tile_xy, n, xoff2, yoff2, d_skip, d_stats, d_zvals, brush, capacity, d_trees, d_counts, false);
+}
+int terra_tiles_place_decid_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                                        const float *h_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *h_trees, uint32_t *h_counts) {
+	if (!pos) return terra::fail(TERRA_ERR_ARG, "null argument");
+	float const brush[4] = {pos[0], pos[1], radius, is_square ? 1.0f : 0.0f};
+	return tiles_place_decid_trees_impl(ctx, tile_xy, n, xoff2, yoff2, h_skip, h_stats, h_zvals, brush, capacity, h_trees, h_counts, true);
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

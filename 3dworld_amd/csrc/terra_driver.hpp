@@ -14,11 +14,13 @@
 #include "terra_modmap.hpp"
 #include "terra_treemap.hpp"
 #include "terra_treeplace.hpp"
+#include "terra_decidplace.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
 #include <string>
 #include <algorithm>
+#include <cmath>
 #include <stdexcept>
 #include <string.h>
 #include <stdio.h>
@@ -696,6 +698,14 @@ template<class BE> struct terra_engine {
 		if (p.instanced && (p.num_pine_insts == 0 || p.num_palm_insts == 0 || p.num_pine_insts > (1u << 30) || p.num_palm_insts > (1u << 30))) throw std::invalid_argument("terra_set_tree_params: instanced needs 1 .. 2^30 pine and palm instances (select_inst asserts start < end)");
 		if (p.instanced && p.force_tree_class == TREE_CLASS_DECID) throw std::invalid_argument("terra_set_tree_params: instanced trees are pines and palms (maybe_add_tree asserts it)");
 		tp = p;
+	}
+	// what tree_cont_t::gen_trees_tt_within_radius reads beyond terra_tree_params: num_trees, shared_tree_data.size(), tree_slope_thresh, tree_types[].branch_size
+	terra_decid_params dp = {0, 0u, 5.0f, {1.0f, 1.0f, 1.0f, 1.0f, 1.0f}};
+	void set_decid_params(terra_decid_params const &p) {
+		if (p.num_trees < 0) throw std::invalid_argument("terra_set_decid_params: num_trees must be >= 0");
+		if (!(p.tree_slope_thresh > 0.0f) || !std::isfinite(p.tree_slope_thresh)) throw std::invalid_argument("terra_set_decid_params: tree_slope_thresh must be finite and > 0");
+		for (float bs : p.branch_size) {if (!(bs > 0.0f) || !std::isfinite(bs)) throw std::invalid_argument("terra_set_decid_params: branch_size must be finite and > 0");}
+		dp = p;
 	}
 	// height_histogram of estimate_zminmax (src/mesh_gen.cpp:467-480), what get_median_height reads; the device copy follows on the next placement call
 	std::vector<float> height_histogram;
@@ -2303,17 +2313,27 @@ template<class BE> struct terra_engine {
 		be.launch(ntex, [=] TERRA_LAMBDA (size_t i) {out[i] = tree_weights_texel(in[i], d_tree_map[2*i]);});
 	}
 
+	// what both placements (pine / palm here, deciduous below) read of the scene, the landscape and terra_tree_params
+	void tree_scene_consts(int xoff2, int yoff2, float const *brush, tree_place_consts_t &c) {
+		c = tree_place_consts_t();
+		c.nc = consts(); c.L = lut(); c.st = nullptr; c.hist = nullptr; c.sums = nullptr; c.nhist = (uint32_t)height_histogram.size();
+		c.mode = mode; c.shape = shape; c.k0 = start_eval_sin;
+		c.S = (int)tile_size(); c.xoff2 = xoff2; c.yoff2 = yoff2; c.xy_mult = cfg.mesh_x*cfg.mesh_y; c.half_x = cfg.mesh_x >> 1; c.half_y = cfg.mesh_y >> 1;
+		c.xss = cfg.scene_x; c.yss = cfg.scene_y; c.DX_VAL = DX_VAL; c.DY_VAL = DY_VAL; c.msc = mesh_scale; c.mszi = mesh_scale_z_inv; c.bxo = ls.biome_x_offset;
+		c.thresh = tp.tree_density_thresh; c.rand_zone = tp.tree_type_rand_zone; c.water_plane_z = water_plane_z; c.relh_adj_tex = relh_adj_tex;
+		c.glaciate_exp_inv = (float)(1.0/(double)glaciate_exp); // src/mesh_gen.cpp:393
+		c.tree_mode = tp.tree_mode; c.force_class = tp.force_tree_class; c.only_pine_palm = tp.only_pine_palm_trees; c.rand_gen_index = tp.rand_gen_index;
+		c.terrain_env = ls.enable_terrain_env;
+		c.brush = brush ? 1 : 0; c.bx = brush ? brush[0] : 0.0f; c.by = brush ? brush[1] : 0.0f; c.brad = brush ? brush[2] : 0.0f; c.is_square = (brush && brush[3] != 0.0f) ? 1 : 0;
+	}
 	// ---- pine / palm tree placement (terra_treeplace.hpp): small_tree_group::gen_trees from src/sm_tree.cpp:439 on, or gen_trees_tt_within_radius (:477-502) when
 	// `brush` = {pos.x, pos.y, radius, is_square} is given, for every tile of the batch.  false: no tile can have a tree (:439; the brush form never divides by a zero
 	// sm_tree_density either).  Throws where the reference would leave the per-cell path: see include/terra.h.
 	bool tree_place_consts(int xoff2, int yoff2, float const *brush, std::vector<float> &sums, tree_place_consts_t &c) {
 		if (using_hmap()) throw std::logic_error("tiles_place_trees: a heightmap texture is set (the texture-height branch of maybe_add_tree is not part of this call)");
 		if (tp.sm_tree_density == 0.0f || !(tp.tree_mode & 2) || (!brush && ls.vegetation == 0.0f)) return false;
-		int const S = (int)tile_size();
-		c.nc = consts(); c.L = lut(); c.st = nullptr; c.hist = nullptr; c.sums = nullptr; c.nhist = (uint32_t)height_histogram.size();
-		c.mode = mode; c.shape = shape; c.k0 = start_eval_sin;
-		c.S = S; c.xoff2 = xoff2; c.yoff2 = yoff2; c.xy_mult = cfg.mesh_x*cfg.mesh_y; c.half_x = cfg.mesh_x >> 1; c.half_y = cfg.mesh_y >> 1;
-		c.xss = cfg.scene_x; c.yss = cfg.scene_y; c.DX_VAL = DX_VAL; c.DY_VAL = DY_VAL; c.msc = mesh_scale; c.mszi = mesh_scale_z_inv; c.bxo = ls.biome_x_offset;
+		tree_scene_consts(xoff2, yoff2, brush, c);
+		int const S = c.S;
 		float const tscale = (cfg.scene_z*tp.tree_scale)/16.0f; // calc_tree_scale (:325)
 		c.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale;             // calc_tree_size (:326)
 		c.ntrees_mult = brush ? tp.sm_tree_density*tscale*tscale/8.0f : ls.vegetation*tp.sm_tree_density*tscale*tscale/8.0f; // (:481, :442)
@@ -2321,15 +2341,10 @@ template<class BE> struct terra_engine {
 		if (!(sv < 2147483648.0)) throw std::invalid_argument("tiles_place_trees: 1/sqrt(sm_tree_density*tree_scale) does not fit an int (skip_val)");
 		c.skip_val = imax(1, (int)sv); // may exceed S: the loop then visits cell (0, 0) alone, and maybe_add_tree's offsets still scale with skip_val (:383-384)
 		c.ncell = (c.skip_val >= S) ? 1 : (S + c.skip_val - 1)/c.skip_val;
-		c.thresh = tp.tree_density_thresh; c.rand_zone = tp.tree_type_rand_zone; c.water_plane_z = water_plane_z; c.relh_adj_tex = relh_adj_tex;
-		c.glaciate_exp_inv = (float)(1.0/(double)glaciate_exp); // src/mesh_gen.cpp:393
 		float const tds = (float)((double)TREE_DIST_SCALE*((double)c.xy_mult/16384.0)); // (:447)
 		c.xscale = tds*DX_VAL*DX_VAL; c.yscale = tds*DY_VAL*DY_VAL;
-		c.tree_mode = tp.tree_mode; c.force_class = tp.force_tree_class; c.only_pine_palm = tp.only_pine_palm_trees; c.rand_gen_index = tp.rand_gen_index;
 		c.instanced = tp.instanced ? 1 : 0; c.num_pine = (int)tp.num_pine_insts; c.num_palm = (int)tp.num_palm_insts;
 		c.approx_zval = (!brush && (mode == MGEN_SINE || (double)c.ntrees_mult > 0.025)) ? 1 : 0; // (:446; world_mode == WMODE_INF_TERRAIN, no heightmap texture)
-		c.terrain_env = ls.enable_terrain_env;
-		c.brush = brush ? 1 : 0; c.bx = brush ? brush[0] : 0.0f; c.by = brush ? brush[1] : 0.0f; c.brad = brush ? brush[2] : 0.0f; c.is_square = (brush && brush[3] != 0.0f) ? 1 : 0;
 		// the running sums: xv += dxv from 0 on, once per visited column, and the same per row (dxv == dyv: x2 - x1 == y2 - y1 == S)
 		float const dxv = (float)c.skip_val/((float)S - 1.0f);
 		sums.resize(c.ncell);
@@ -2388,6 +2403,98 @@ template<class BE> struct terra_engine {
 						if (!tree_cell_selected(cc, dens, r.tx, r.ty, ix, iy, rg)) continue;
 						tree_place_pod_t o;
 						if (!tree_cell_finish(cc, r.tx, r.ty, ix, iy, rg, o)) continue;
+						if (count < capacity) {d_trees[(size_t)t*capacity + count] = o;}
+						++count;
+					}
+				}
+			}
+			d_counts[t] = count;
+		});
+	}
+
+	// ---- deciduous tree placement (terra_decidplace.hpp): tree_cont_t::gen_trees_tt_within_radius (src/Tree.cpp:2209-2305) from :2240 on for every tile of the batch,
+	// as gen_deterministic calls it (no brush: vegetation*get_avg_veg(), the coverage field) or as tile_t::add_new_trees does (`brush` = {pos.x, pos.y, radius, is_square}).
+	// false: no generated trees (:2240).
+	bool decid_place_consts(int xoff2, int yoff2, float const *brush, bool slope, decid_place_consts_t &c) {
+		if (using_hmap()) throw std::logic_error("tiles_place_decid_trees: a heightmap texture is set (the texture heights of get_exact_zval are not part of this call)");
+		double const sv = 1.0/(double)tp.tree_scale; // max(1, int(1.0/tree_scale)) (:2243)
+		if (!(sv < 2147483648.0)) throw std::invalid_argument("tiles_place_decid_trees: 1/tree_scale does not fit an int (skip_val)");
+		// unsigned(num_trees/(NONUNIFORM_TREE_DEN ? sqrt(tree_density_thresh) : 1.0)): sqrt(float) in a double ternary, an int divided by a double (:2214)
+		double const mq = (double)dp.num_trees/(double)sqrtf(tp.tree_density_thresh);
+		if (dp.num_trees > 0 && !(mq >= 0.0 && mq < 4294967296.0)) throw std::invalid_argument("tiles_place_decid_trees: num_trees/sqrt(tree_density_thresh) does not fit an unsigned (mod_num_trees)");
+		uint32_t const mod_num_trees = (dp.num_trees > 0) ? (uint32_t)mq : 0u;
+		if (mod_num_trees == 0 || !(tp.tree_mode & 1)) return false;
+		tree_scene_consts(xoff2, yoff2, brush, c.b);
+		tree_place_consts_t &b = c.b;
+		int const S = b.S;
+		b.skip_val = imax(1, (int)sv);
+		b.ncell = (b.skip_val >= S) ? 1 : (S + b.skip_val - 1)/b.skip_val;
+		c.smod = (uint32_t)(3.321*(double)b.xy_mult + 1.0);
+		c.tree_prob = std::max(1u, (uint32_t)b.xy_mult/mod_num_trees); // XY_MULT_SIZE/mod_num_trees: int by unsigned
+		c.num_shared = dp.num_shared_trees;
+		c.use_density = brush ? 0 : 1; c.slope = slope ? 1 : 0;
+		c.vegetation = ls.vegetation;
+		c.min_tree_h = (float)((double)water_plane_z + 0.01*(double)zmax_est); c.max_tree_h = (float)(1.8*(double)zmax_est); // (:2215)
+		c.height_thresh = height_histogram.empty() ? tp.tree_density_thresh : // get_median_height(tree_density_thresh) (:2241)
+			height_histogram[(size_t)imax(0, imin((int)height_histogram.size() - 1, f2i_x86((float)height_histogram.size()*tp.tree_density_thresh)))];
+		c.slope_thresh = dp.tree_slope_thresh;
+		for (int i = 0; i < 2; ++i) { // (:2250)
+			float const tds = (float)((double)TREE_DIST_SCALE*((double)b.xy_mult/16384.0)*(i == 0 ? 1.0 : 0.1));
+			c.xscale[i] = tds*DX_VAL*DX_VAL; c.yscale[i] = tds*DY_VAL*DY_VAL;
+		}
+		for (int tt = 0; tt < NUM_TREE_TYPES; ++tt) { // adjust_tree_zval with size 0, no bush (src/Tree.cpp:1465-1474)
+			float const size_scale = (float)((double)(TREE_SIZE*dp.branch_size[tt]/tp.tree_scale)*1.0);
+			float const base_radius = (float)(60.0*(0.1*(double)size_scale));
+			c.radius[tt] = (float)(2.0*(double)base_radius);
+		}
+		return true;
+	}
+	void tiles_place_decid_trees_dev(int32_t const *tile_xy, uint32_t n, int xoff2, int yoff2, uint8_t const *d_skip, terra_tile_stats const *d_stats, float const *d_zvals,
+		float const *brush, uint32_t capacity, decid_place_pod_t *d_trees, uint32_t *d_counts)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		if (d_stats && !d_zvals) throw std::invalid_argument("tiles_place_decid_trees: stats without zvals (the slope test reads the tile's heights)");
+		decid_place_consts_t c;
+		bool const any = decid_place_consts(xoff2, yoff2, brush, d_stats != nullptr, c);
+		if (capacity && !d_trees) throw std::invalid_argument("tiles_place_decid_trees: null d_trees");
+		if (((uintptr_t)d_trees & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0 || ((uintptr_t)d_zvals & 3u) != 0 || ((uintptr_t)d_stats & 3u) != 0) {
+			throw std::invalid_argument("tiles_place_decid_trees: d_trees, d_counts, d_stats and d_zvals must be 4-byte aligned");
+		}
+		if (!any) {be.fill32(d_counts, 0u, n); return;}
+		std::vector<tile_ref_pod_t> refs(n);
+		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
+		size_t const kb = (sizeof(decid_place_consts_t) + 255) & ~(size_t)255, rb = ((size_t)n*sizeof(tile_ref_pod_t) + 255) & ~(size_t)255;
+		uint8_t *base = scratch<uint8_t>(s_ao, kb + rb + (size_t)n*4*sizeof(float));
+		decid_place_consts_t *d_consts = (decid_place_consts_t *)base; // the kernel reads its constants from memory, as k_tree_place does
+		tile_ref_pod_t *d_refs_w = (tile_ref_pod_t *)(base + kb);
+		float *d_dens = (float *)(base + kb + rb);
+		be.h2d_async(d_refs_w, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
+		tile_ref_pod_t const *d_refs = d_refs_w;
+		c.b.st = sinTable_dev(); c.b.hist = height_histogram_dev();
+		decid_place_consts_t const cc = c;
+		be.h2d_async(d_consts, &cc, sizeof(cc));
+		if (!brush) {tree_place_consts_t const cb = c.b; be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cb, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});}
+		if (be.tile_place_decid_trees(d_consts, d_refs, n, d_dens, d_skip, d_stats, d_zvals, capacity, d_trees, d_counts)) return;
+		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
+		size_t const zsz = (size_t)(cc.b.S + 2)*(size_t)(cc.b.S + 2);
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			tile_ref_pod_t const r = d_refs[t];
+			float dens[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+			if (!cc.b.brush) {for (int k = 0; k < 4; ++k) {dens[k] = d_dens[4*t + k];}}
+			uint32_t count = 0;
+			if (!(d_skip && d_skip[t]) && !(d_stats && !decid_zrange_ok(cc.b, d_stats[t].mzmin, d_stats[t].mzmax))) {
+				float const veg = decid_tile_veg(cc, dens);
+				bool const slope_test = d_stats && decid_mesh_dz(d_stats[t]) > 1.0f; // (:2297; a tile's mesh_dz is never negative)
+				for (unsigned iy = 0; iy < (unsigned)cc.b.ncell; ++iy) {
+					for (unsigned ix = 0; ix < (unsigned)cc.b.ncell; ++ix) {
+						tree_rgen_t rg;
+						if (!decid_cell_selected(cc, veg, r.tx, r.ty, ix, iy, rg)) continue;
+						float pos[3];
+						if (!decid_cell_site(cc, r.tx, r.ty, ix, iy, rg, pos)) continue;
+						decid_place_pod_t o;
+						if (!decid_cell_finish(cc, r.tx, r.ty, ix, iy, rg, pos, slope_test, d_zvals ? d_zvals + t*zsz : nullptr, o)) continue;
 						if (count < capacity) {d_trees[(size_t)t*capacity + count] = o;}
 						++count;
 					}

@@ -584,6 +584,16 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// deciduous tree placement: one workgroup per tile (k_decid_place)
+	bool tile_place_decid_trees(terra::decid_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
+		float const *zvals, uint32_t capacity, terra::decid_place_pod_t *trees, uint32_t *counts)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_decid_place, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, dens, skip, stats, zvals, capacity, trees, counts);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

@@ -1559,6 +1559,99 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_tree_place(tree_place_consts_
 	if (tid == 0) {counts[t] = count;}
 }
 
+// ------------------------------------------------------------------ deciduous tree placement (tree_cont_t::gen_trees_tt_within_radius, src/Tree.cpp:2240-2303; terra_decidplace.hpp)
+// One workgroup per tile and the loop's cells 256 at a time, row-major, as in k_tree_place: every thread runs the selection of :2269-2275 for its cell and the
+// survivors' cell numbers go, in order, into a first ring in LDS.  Whenever that ring holds 256 of them (and at the end) every thread takes one and finds its
+// site -- the position, get_exact_zval, the range, the class, the 80-term coverage field -- and what is left goes, in order, with its height and its generator,
+// into a second ring.  Whenever that one holds 256 (and at the end) every thread takes one and runs the five type fields, the slope test over the tile's zvals
+// and add_new_tree's index; the trees of a batch are written behind those of the batches before.  Three ballot-and-prefix compactions, no atomics.
+// Why two rings: at num_trees 400 about one cell in thirty is selected and a third to a half of those fail the range, the class or the coverage field, so without
+// the second compaction the five type fields (5 x 80 terms of two SINF gathers, the bulk of a tree's work) would run with that share of the lanes idle.  The type
+// fields take one pass over k (decid_type_fields).  87 VGPRs, 106 SGPRs with 20 spilled to vector lanes, 14352 B LDS, no scratch: five waves per SIMD.
+// The variants without the second ring and with five separate field passes, and the timings (tools/bench_decid_place.py): DESIGN.md, section 4.
+constexpr uint32_t DECIDP_RING = 512;
+__global__ __launch_bounds__(TREEP_THREADS) void k_decid_place(decid_place_consts_t const *__restrict__ consts, tile_ref_pod_t const *__restrict__ tiles, float const *__restrict__ d_dens,
+	uint8_t const *__restrict__ skip, terra_tile_stats const *__restrict__ stats, float const *__restrict__ zvals, uint32_t capacity, decid_place_pod_t *__restrict__ trees,
+	uint32_t *__restrict__ counts)
+{
+	__shared__ uint32_t s_ring[DECIDP_RING], s_wave[TREEP_THREADS/64];
+	__shared__ uint32_t s_cell[DECIDP_RING]; __shared__ float s_pos[DECIDP_RING][3]; __shared__ int32_t s_seed[DECIDP_RING][2]; // the second ring
+	decid_place_consts_t const &c = *consts;
+	uint32_t const t = blockIdx.x, tid = threadIdx.x;
+	tile_ref_pod_t const r = tiles[t];
+	float dens[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+	if (!c.b.brush) {for (int k = 0; k < 4; ++k) {dens[k] = d_dens[4*(size_t)t + k];}}
+	// (uniform over the block)
+	if ((skip && skip[t]) || (stats && !decid_zrange_ok(c.b, stats[t].mzmin, stats[t].mzmax))) {
+		if (tid == 0) {counts[t] = 0;}
+		return;
+	}
+	float const veg = decid_tile_veg(c, dens);
+	bool const slope_test = stats && decid_mesh_dz(stats[t]) > 1.0f;
+	float const *const tz = zvals ? zvals + (size_t)t*(size_t)(c.b.S + 2)*(size_t)(c.b.S + 2) : nullptr;
+	uint32_t const ncell = (uint32_t)c.b.ncell, ncells = ncell*ncell;
+	decid_place_pod_t *const out = trees + (size_t)t*capacity;
+	uint32_t h1 = 0, t1 = 0, h2 = 0, t2 = 0, count = 0; // the rings [h1, t1) and [h2, t2) and the tile's trees so far: the same in every thread
+	for (uint32_t base = 0; ; base += TREEP_THREADS) {
+		if (base < ncells) {
+			uint32_t const cell = base + tid;
+			bool sel = false;
+			if (cell < ncells) {
+				uint32_t const iy = cell/ncell, ix = cell - iy*ncell;
+				tree_rgen_t rg;
+				sel = decid_cell_selected(c, veg, r.tx, r.ty, ix, iy, rg);
+			}
+			uint32_t nsel;
+			uint32_t const rank = tp_block_rank(sel, s_wave, nsel);
+			if (sel) {s_ring[(t1 + rank) & (DECIDP_RING - 1)] = cell;}
+			t1 += nsel;
+			__syncthreads();
+		}
+		bool const last = base + TREEP_THREADS >= ncells; // no cell comes after this round
+		if (t1 - h1 >= TREEP_THREADS || (last && h1 < t1)) { // the sites of up to 256 selected cells
+			uint32_t const nb = (t1 - h1 < TREEP_THREADS) ? t1 - h1 : TREEP_THREADS;
+			bool ok = false;
+			uint32_t cell = 0;
+			float pos[3] = {0.0f, 0.0f, 0.0f};
+			tree_rgen_t rg; rg.set_state(0, 0);
+			if (tid < nb) {
+				cell = s_ring[(h1 + tid) & (DECIDP_RING - 1)];
+				uint32_t const iy = cell/ncell, ix = cell - iy*ncell;
+				decid_cell_selected(c, veg, r.tx, r.ty, ix, iy, rg); // (the generator as the selection left it: cheaper to redo than to keep)
+				ok = decid_cell_site(c, r.tx, r.ty, ix, iy, rg, pos);
+			}
+			h1 += nb;
+			uint32_t nok;
+			uint32_t const rank = tp_block_rank(ok, s_wave, nok);
+			if (ok) {
+				uint32_t const k = (t2 + rank) & (DECIDP_RING - 1);
+				s_cell[k] = cell; s_pos[k][0] = pos[0]; s_pos[k][1] = pos[1]; s_pos[k][2] = pos[2]; s_seed[k][0] = rg.rseed1; s_seed[k][1] = rg.rseed2;
+			}
+			t2 += nok;
+			__syncthreads();
+		}
+		bool const drained = last && h1 == t1; // nothing comes after what the second ring holds
+		if (t2 - h2 >= TREEP_THREADS || (drained && h2 < t2)) { // the types, the slope test and the records of up to 256 sites
+			uint32_t const nb = (t2 - h2 < TREEP_THREADS) ? t2 - h2 : TREEP_THREADS;
+			bool ok = false;
+			decid_place_pod_t o;
+			if (tid < nb) {
+				uint32_t const k = (h2 + tid) & (DECIDP_RING - 1), cell = s_cell[k], iy = cell/ncell, ix = cell - iy*ncell;
+				float const pos[3] = {s_pos[k][0], s_pos[k][1], s_pos[k][2]};
+				tree_rgen_t rg; rg.set_state(s_seed[k][0], s_seed[k][1]);
+				ok = decid_cell_finish(c, r.tx, r.ty, ix, iy, rg, pos, slope_test, tz, o);
+			}
+			h2 += nb;
+			uint32_t ntree;
+			uint32_t const rank = tp_block_rank(ok, s_wave, ntree); // (its barriers also keep the next round's writes to the second ring behind these reads)
+			if (ok && count + rank < capacity) {out[count + rank] = o;}
+			count += ntree;
+		}
+		if (drained && h2 == t2) break;
+	}
+	if (tid == 0) {counts[t] = count;}
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

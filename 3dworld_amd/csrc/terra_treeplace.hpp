@@ -184,8 +184,7 @@ TERRA_HD float tree_bias_zone(float v, float ref_pt, float zone_width) { // val_
 	return v + range*(float)(2.0*(double)fract - 1.0);
 }
 TERRA_HD bool tree_rel_height_check(tree_place_consts_t const &c, float v, float thresh, float zw_scale) {return tree_bias_zone(v, thresh, zw_scale*c.rand_zone) > thresh;}
-TERRA_HD int tree_class_from_height(tree_place_consts_t const &c, float zpos) {
-	bool const pine_trees_only = (c.tree_mode == 2 || c.tree_mode == 3); // world_mode == WMODE_INF_TERRAIN, for_scenery = 0 (:556)
+TERRA_HD int tree_class_from_height(tree_place_consts_t const &c, float zpos, bool pine_trees_only) {
 	if (zpos < c.water_plane_z) return TREE_CLASS_NONE;
 	if (c.force_class >= 0) return c.force_class;
 	float const relh = tree_rel_height(c, zpos);
@@ -197,7 +196,8 @@ TERRA_HD int tree_class_from_height(tree_place_consts_t const &c, float zpos) {
 	return c.only_pine_palm ? TREE_CLASS_PINE : TREE_CLASS_DECID;
 }
 TERRA_HD int tree_type_from_height(tree_place_consts_t const &c, float zpos, tree_rgen_t &r) {
-	switch (tree_class_from_height(c, zpos)) {
+	bool const pine_trees_only = (c.tree_mode == 2 || c.tree_mode == 3); // world_mode == WMODE_INF_TERRAIN, for_scenery = 0 (:556)
+	switch (tree_class_from_height(c, zpos, pine_trees_only)) {
 	case TREE_CLASS_PINE:  return (r.rand()%10 == 0) ? T_SH_PINE : T_PINE;
 	case TREE_CLASS_PALM:  return T_PALM;
 	case TREE_CLASS_DECID: return T_DECID + r.rand()%3;

@@ -75,6 +75,20 @@ def make_tree_params(sm_tree_density=1.0, tree_scale=1.0, tree_density_thresh=0.
                       int(bool(instanced)), num_pine_insts, num_palm_insts)
 
 
+DECID_PLACE_DTYPE = np.dtype([("pos", np.float32, (3,)), ("zval", np.float32), ("type", np.int32), ("tree_id", np.int32), ("rseed1", np.int32), ("rseed2", np.int32),
+                              ("cx", np.uint16), ("cy", np.uint16)])  # terra_decid_place
+assert DECID_PLACE_DTYPE.itemsize == 36
+
+
+class DecidParams(C.Structure):  # terra_decid_params
+    _fields_ = [("num_trees", C.c_int32), ("num_shared_trees", C.c_uint32), ("tree_slope_thresh", C.c_float), ("branch_size", C.c_float * 5)]
+
+
+def make_decid_params(num_trees=0, num_shared_trees=0, tree_slope_thresh=5.0, branch_size=(1.0, 1.0, 1.0, 1.0, 1.0)):
+    """terra_decid_params with the reference's defaults (num_trees 0: no generated trees)."""
+    return DecidParams(num_trees, num_shared_trees, tree_slope_thresh, (C.c_float * 5)(*branch_size))
+
+
 class GRASS_BRUSH(C.Structure):
     """terra_grass_brush: one stroke of the fire modes "Add Grass" / "Remove Grass" (tile_t::add_or_remove_grass_at's arguments)"""
     _fields_ = [("pos", C.c_float * 3), ("radius", C.c_float), ("add_grass", C.c_int32), ("shape", C.c_int32), ("brush_weight", C.c_float)]
@@ -227,6 +241,12 @@ _PROTOS = {
     "terra_tiles_place_trees": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_place_trees_brush_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
     "terra_tiles_place_trees_brush": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
+    "terra_set_decid_params": (_i32, [_vp, _vp]),
+    "terra_get_decid_params": (_i32, [_vp, _vp]),
+    "terra_tiles_place_decid_trees_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "terra_tiles_place_decid_trees": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "terra_tiles_place_decid_trees_brush_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
+    "terra_tiles_place_decid_trees_brush": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -738,6 +758,33 @@ class Terra:
             self._ck(self.lib.terra_tiles_place_trees_brush(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), *tail))
         return trees, counts
 
+    def set_decid_params(self, dp):
+        self._ck(self.lib.terra_set_decid_params(self.ctx, C.byref(dp)))
+
+    def get_decid_params(self):
+        dp = DecidParams()
+        self._ck(self.lib.terra_get_decid_params(self.ctx, C.byref(dp)))
+        return dp
+
+    def tiles_place_decid_trees(self, tile_xy, capacity, xoff2=0, yoff2=0, skip=None, stats=None, zvals=None, brush=None):
+        """tree_cont_t::gen_trees_tt_within_radius for every tile, as gen_deterministic calls it or, with brush = (pos[3], radius, is_square), as add_new_trees does.
+        skip: [n] bytes (can_have_trees() false), stats: the TileStats array of tiles_create_zvals, zvals: [n, S+2, S+2] (required with stats).
+        -> (trees DECID_PLACE_DTYPE [n, capacity], counts uint32 [n]); records past counts[t] are zero"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        z = None if zvals is None else np.ascontiguousarray(zvals, np.float32)
+        trees, counts = np.zeros((n, capacity), DECID_PLACE_DTYPE), np.zeros(n, np.uint32)
+        args = (self.ctx, txy.ctypes.data, n, xoff2, yoff2, None if sk is None else sk.ctypes.data, None if stats is None else C.addressof(stats),
+                None if z is None else z.ctypes.data)
+        tail = (capacity, trees.ctypes.data if capacity else None, counts.ctypes.data)
+        if brush is None:
+            self._ck(self.lib.terra_tiles_place_decid_trees(*args, *tail))
+        else:
+            pos, radius, is_square = brush
+            self._ck(self.lib.terra_tiles_place_decid_trees_brush(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), *tail))
+        return trees, counts
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -898,6 +945,18 @@ class Terra:
         else:
             pos, radius, is_square = brush
             self._ck(self.lib.terra_tiles_place_trees_brush_dev(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), capacity, trees_ptr, counts_ptr))
+
+    def tiles_place_decid_trees_dev(self, tile_xy, capacity, trees_ptr, counts_ptr, xoff2=0, yoff2=0, skip_ptr=None, stats_ptr=None, z_ptr=None, brush=None):
+        """deciduous tree placement of a device-resident batch: trees_ptr [n][capacity] DECID_PLACE_DTYPE records, counts_ptr [n] uint32, skip_ptr [n] bytes /
+        stats_ptr [n] terra_tile_stats / z_ptr [n][S+2][S+2] floats (or None; z_ptr is required with stats_ptr).  brush = (pos[3], radius, is_square) for the brush
+        form.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        args = (self.ctx, txy.ctypes.data, len(txy), xoff2, yoff2, skip_ptr, stats_ptr, z_ptr)
+        if brush is None:
+            self._ck(self.lib.terra_tiles_place_decid_trees_dev(*args, capacity, trees_ptr, counts_ptr))
+        else:
+            pos, radius, is_square = brush
+            self._ck(self.lib.terra_tiles_place_decid_trees_brush_dev(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), capacity, trees_ptr, counts_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

@@ -559,7 +559,7 @@ int  terra_get_height_histogram(terra_ctx *ctx, float *h_vals, uint32_t capacity
  * with more than `capacity` trees gets the first `capacity` and counts[t] still reports all of them.  Records past counts[t] are not written.
  * With the engine stay check_valid_scenery_pos and point_inside_voxel_terrain (:399, :402; they draw no random numbers, so filtering the records afterwards is
  * identical), the tree placer block (:412-438), the small_tree constructor (for a tree that is not instanced, from the generator state in the record),
- * postproc_trees and deciduous trees.
+ * and postproc_trees.  Deciduous trees have a call of their own: terra_tiles_place_decid_trees, below.
  * Zero trees everywhere (:439-440): vegetation == 0, sm_tree_density == 0, bit 2 of tree_mode clear; per tile: all four density corners 0.
  * TERRA_ERR_ARG when some cell could have XY_MULT_SIZE < 2*ntrees: the reference then does not re-seed its generator per cell (:370), the sequence runs serially
  * through the tile and trees_this_xy can exceed 1.  The test, on the host: ntrees = int(min(1, cur_density*ntrees_mult)*40000) with cur_density = 1.001, which
@@ -591,6 +591,69 @@ int  terra_tiles_place_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, u
                                        const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *d_trees, uint32_t *d_counts);
 int  terra_tiles_place_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
                                    const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *h_trees, uint32_t *h_counts);
+
+/* ---- deciduous tree placement of a tile batch (every supported tile size S): tree_cont_t::gen_trees_tt_within_radius (src/Tree.cpp:2209-2305) from :2240 on, the
+ * generating half of tile_t::gen_decid_trees_if_needed (src/tiled_mesh.cpp:1536-1547) and of the decid_trees half of "Add Trees" (tile_t::add_new_trees, :3805-3811,
+ * :3837).  With terra_tiles_place_trees both tree containers of a tile now come from the device.
+ * terra_decid_params: what this path reads beyond terra_tree_params (tree_scale, tree_density_thresh, tree_type_rand_zone, tree_mode, force_tree_class,
+ * only_pine_palm_trees, rand_gen_index), terra_landscape and the scene.  TERRA_ERR_ARG (and nothing changes): num_trees < 0, a tree_slope_thresh or a branch_size
+ * that is not finite and > 0. */
+typedef struct terra_decid_params {
+	int32_t  num_trees;          /* config "num_trees", 0: no generated trees */
+	uint32_t num_shared_trees;   /* shared_tree_data.size() (max_unique_trees); 0: tree_id = -1 */
+	float    tree_slope_thresh;  /* config "tree_slope_thresh", 5 */
+	float    branch_size[5];     /* tree_types[].branch_size (src/Tree.cpp:38), 1 */
+} terra_decid_params;
+int  terra_set_decid_params(terra_ctx *ctx, const terra_decid_params *params);
+int  terra_get_decid_params(terra_ctx *ctx, terra_decid_params *out);
+/* terra_tiles_place_decid_trees: gen_deterministic (src/Tree.cpp:2153-2155) for every tile, bit for bit, trees in the reference's loop order (rows, then columns): the
+ * loop visits every skip_val = max(1, int(1.0/tree_scale))-th cell; the seeds of :2269-2270 from i + yoff2, j + xoff2 and rand_gen_index (int products that wrap),
+ * rand_mix, val = unsigned(rand_seed_mix()) % smod; the cell is dropped when val <= 100, when val % tree_prob != 0 or when (rseed1 & 127)/128.0 >= vegetation_
+ * (smod = unsigned(3.321*XY_MULT_SIZE + 1), tree_prob = max(1U, XY_MULT_SIZE/mod_num_trees), mod_num_trees = unsigned(num_trees/sqrt(tree_density_thresh)), an int
+ * divided by the double of a float sqrt); pos.xy = get_xval(j) / get_yval(i) + 0.5*DX_VAL*randd(); pos.z = get_exact_zval; the range [water_plane_z + 0.01*zmax_est,
+ * 1.8*zmax_est]; at tree_mode 3 get_tree_class_from_height(pos.z, 0) must be TREE_CLASS_DECID; the coverage test density_gen[0].eval_index(j - x1, i - y1) >
+ * get_median_height(tree_density_thresh); the type as the arg-max over the five jittered type fields density_gen[1 .. 5] (:2286-2293); the slope test (below);
+ * add_new_tree's tree_id (:2163-2166) from the generator as it stands.  vegetation_ = vegetation*get_avg_veg(), the four veg corners generated internally as for
+ * terra_tiles_place_trees and averaged as src/tiled_mesh.h:221 does.  xoff2 / yoff2: as for terra_tiles_place_trees (dtree_off.set_from_xyoff2()).
+ * skip (optional): [n] bytes, non-zero = can_have_trees() is false.  stats (optional): a tile failing can_have_decid_trees_in_zrange(mzmin, mzmax)
+ * (src/sm_tree.cpp:580-587, no tree placer) gets no trees, and a tile whose mesh_dz = max(sub_zmax[k] - sub_zmin[k]), taken from 0 (src/tiled_mesh.cpp:535), is above
+ * 1.0 runs the slope test adjust_tree_zval(pos, 0, ttype, 0, cur_tile) (src/Tree.cpp:1471-1480): radius = 2*(60*(0.1*(TREE_SIZE*branch_size[ttype]/tree_scale))), the
+ * tile's zvals scanned over get_z_minmax_for_area(pos + (xoff2*DX_VAL, yoff2*DY_VAL), 0.5*radius) (src/tiled_mesh.cpp:548-564: round-down indices against the tile's
+ * x1 = tx*S, unsigned max(0, ..) / min(stride, ..), rows and columns inclusive), pos.z lowered to the area's minimum, and the tree dropped unless
+ * mzmax - pos.z < tree_slope_thresh*radius.  zvals: [n][S+2][S+2], required with stats; without stats no tile is culled and no slope test runs.
+ * get_z_minmax_for_area asserts that its index range is not empty.  It never is: pos lies within half a cell of a cell of its own tile, so the column of
+ * pos.x + radius is at least the tile's first (ix2 >= 0 after the + 1) and that of pos.x - radius at most its last (ix1 <= S < stride), and ix1 <= ix2 because
+ * rx1 <= rx2 and both indices round the same way; the same holds in y.  (The kernel's loops do not rely on it: an empty range reads nothing.)
+ * trees: [n][capacity] records; counts: [n].  A tile with more than `capacity` trees gets the first `capacity` and counts[t] still reports all of them.  Records
+ * past counts[t] are not written.
+ * With the engine stay check_valid_scenery_pos (:2295; it sees the height before adjust_tree_zval, which is why the record carries both), point_inside_voxel_terrain
+ * (:2281), the pre-placed city trees of tree_placer (:2219-2239), the is_created() type override of add_new_tree (:2171), tree::gen_tree (fed from the generator
+ * state in the record) and postproc_trees.  None of them draws a random number and cells are independent, so filtering the records afterwards is identical.
+ * Zero trees everywhere (:2240): mod_num_trees == 0 (num_trees 0, or fewer than sqrt(tree_density_thresh)), bit 1 of tree_mode clear.
+ * TERRA_ERR_ARG: a 1.0/tree_scale that does not fit an int, a num_trees/sqrt(tree_density_thresh) that does not fit an unsigned (undefined in the reference), an
+ * unsupported S, a NULL required pointer (tile_xy, counts when n > 0; trees when capacity > 0), a misaligned pointer, stats without zvals.
+ * TERRA_ERR_STATE before terra_init_scene, and while a heightmap texture is set (the texture heights of get_exact_zval are not part of this call).  n == 0 does
+ * nothing once the scene and the tile size have passed.  The device form only enqueues. */
+typedef struct terra_decid_place {
+	float pos[3];            /* pos.z after adjust_tree_zval */
+	float zval;              /* get_exact_zval(pos.x, pos.y): what check_valid_scenery_pos sees */
+	int32_t type;            /* 0 .. 4 (src/tree_leaf.h:8) */
+	int32_t tree_id;         /* add_new_tree's, -1 without shared trees */
+	int32_t rseed1, rseed2;  /* the generator where the reference calls gen_tree */
+	uint16_t cx, cy;         /* the cell inside the tile */
+} terra_decid_place;         /* 36 bytes */
+int  terra_tiles_place_decid_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                       const float *d_zvals, uint32_t capacity, terra_decid_place *d_trees, uint32_t *d_counts);
+int  terra_tiles_place_decid_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                                   const float *h_zvals, uint32_t capacity, terra_decid_place *h_trees, uint32_t *h_counts);
+/* terra_tiles_place_decid_trees_brush: the same function as tile_t::add_new_trees calls it (xoff2 / yoff2 = -toff.dxoff / -toff.dyoff): vegetation_ = 1, no coverage
+ * field, and the fabs / dist_xy_less_than test of the cell's get_xval / get_yval against pos (x and y are read) and radius (:2256-2264).  A radius of 0 or less means
+ * the whole tile.  is_square is accepted as the reference accepts it: this function never reads it (a square brush places deciduous trees within the circle).
+ * The caller keeps the mesh_sphere_intersect culls and the removal loop (:3822-3838). */
+int  terra_tiles_place_decid_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
+                                             const float *d_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *d_trees, uint32_t *d_counts);
+int  terra_tiles_place_decid_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
+                                         const float *h_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *h_trees, uint32_t *h_counts);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

@@ -260,6 +260,25 @@ inline void tiles_gen_trees_tt_within_radius(tile_batch_dev_t const &b, int toff
 	check(terra_tiles_place_trees_brush_dev(default_ctx(), b.tile_xy, b.n, -toff_dxoff, -toff_dyoff, d_can_have_trees_false, b.d_stats, pos, radius, is_square ? 1 : 0, capacity, d_trees, d_counts),
 		"gen_trees_tt_within_radius");
 }
+// ---- deciduous tree placement of a batch on device arrays.  The globals beyond set_tree_globals go in once (set_decid_globals: num_trees, shared_tree_data.size(),
+// tree_slope_thresh and tree_types[].branch_size).
+inline void set_decid_globals(terra_decid_params const &p) {check(terra_set_decid_params(default_ctx(), &p), "set_decid_params");}
+// tree_cont_t::gen_deterministic (src/Tree.cpp:2153-2155) for every tile as tile_t::gen_decid_trees_if_needed (src/tiled_mesh.cpp:1536-1547) calls it: xoff2 / yoff2 are
+// the globals at that time (dtree_off.set_from_xyoff2()); vegetation*get_avg_veg() and mesh_dz are taken from the landscape, the biome field and b.d_stats.
+// d_can_have_trees_false[t] != 0: can_have_trees() is false; b.d_stats (may be null, then without cull and slope test): can_have_decid_trees_in_zrange(mzmin, mzmax) and
+// mesh_dz; b.d_zvals: the tile heights adjust_tree_zval scans.  d_trees [n][capacity], d_counts [n]: the engine filters each record with check_valid_scenery_pos (on
+// zval, the height before adjust_tree_zval) / point_inside_voxel_terrain, calls add_new_tree with tree_id and type, then rgen.set_state(rseed1, rseed2) and gen_tree
+inline void tiles_gen_decid_trees(tile_batch_dev_t const &b, int xoff2, int yoff2, unsigned char const *d_can_have_trees_false, unsigned capacity, terra_decid_place *d_trees, unsigned *d_counts) {
+	check(terra_tiles_place_decid_trees_dev(default_ctx(), b.tile_xy, b.n, xoff2, yoff2, d_can_have_trees_false, b.d_stats, b.d_stats ? b.d_zvals : nullptr, capacity, d_trees, d_counts), "gen_decid_trees");
+}
+// tree_cont_t::gen_trees_tt_within_radius (src/Tree.cpp:2209-2305) as tile_t::add_new_trees (src/tiled_mesh.cpp:3805-3811) calls it for decid_trees: toff_dxoff /
+// toff_dyoff = dtree_off's members, pos = dt_pos, is_square = (brush_shape == BSHAPE_CONST_SQ) (passed on; the reference's function never reads it)
+inline void tiles_gen_decid_trees_tt_within_radius(tile_batch_dev_t const &b, int toff_dxoff, int toff_dyoff, unsigned char const *d_can_have_trees_false, float const pos[3], float radius,
+	bool is_square, unsigned capacity, terra_decid_place *d_trees, unsigned *d_counts)
+{
+	check(terra_tiles_place_decid_trees_brush_dev(default_ctx(), b.tile_xy, b.n, -toff_dxoff, -toff_dyoff, d_can_have_trees_false, b.d_stats, b.d_stats ? b.d_zvals : nullptr, pos, radius,
+		is_square ? 1 : 0, capacity, d_trees, d_counts), "gen_decid_trees_tt_within_radius");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
