@@ -837,6 +837,44 @@ int terra_tiles_place_decid_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, 
 	float const brush[4] = {pos[0], pos[1], radius, is_square ? 1.0f : 0.0f};
 	return tiles_place_decid_trees_impl(ctx, tile_xy, n, xoff2, yoff2, h_skip, h_stats, h_zvals, brush, capacity, h_trees, h_counts, true);
 }
+int terra_set_scenery_params(terra_ctx *ctx, const terra_scenery_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_scenery_params(*params); TERRA_CATCH
+}
+int terra_get_scenery_params(terra_ctx *ctx, terra_scenery_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	*out = ctx->eng.sp; return TERRA_OK;
+}
+static_assert(sizeof(terra_scenery_place) == 72 && sizeof(terra::scenery_place_pod_t) == 72 && (int)TERRA_SCENERY_KINDS == (int)terra::SCENERY_KINDS, "terra_scenery_place layout");
+int terra_tiles_place_scenery_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, uint32_t capacity,
+                                  terra_scenery_place *d_objs, uint32_t *d_counts, uint32_t *d_kind_counts) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !d_counts || (capacity && !d_objs))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_place_scenery_dev(tile_xy, n, xoff2, yoff2, d_skip, capacity, (terra::scenery_place_pod_t *)d_objs, d_counts, d_kind_counts); TERRA_CATCH
+}
+int terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, uint32_t capacity,
+                              terra_scenery_place *h_objs, uint32_t *h_counts, uint32_t *h_kind_counts) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !h_counts || (capacity && !h_objs))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size();
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const ob = (size_t)n*capacity*sizeof(terra_scenery_place), cb = (size_t)n*4, kb = n, qb = (size_t)n*TERRA_SCENERY_KINDS*4;
+		size_t const oo = 0, oc = oo + up(ob), ok = oc + up(cb), oq = ok + up(kb);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oq + up(qb));
+		if (n && h_skip) {be.h2d(d + ok, h_skip, kb);}
+		ctx->eng.tiles_place_scenery_dev(tile_xy, n, xoff2, yoff2, h_skip ? d + ok : nullptr, capacity, (terra::scenery_place_pod_t *)(d + oo), (uint32_t *)(d + oc),
+			h_kind_counts ? (uint32_t *)(d + oq) : nullptr);
+		if (n == 0) return TERRA_OK;
+		be.d2h(h_counts, d + oc, cb);
+		if (h_kind_counts) {be.d2h(h_kind_counts, d + oq, qb);}
+		// only the records the counts name were written: the rest of the caller's array stays as it was
+		for (uint32_t t = 0; t < n; ++t) {
+			uint32_t const m = std::min(h_counts[t], capacity);
+			if (m) {be.d2h(h_objs + (size_t)t*capacity, d + oo + (size_t)t*capacity*sizeof(terra_scenery_place), (size_t)m*sizeof(terra_scenery_place));}
+		}
+	TERRA_CATCH
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

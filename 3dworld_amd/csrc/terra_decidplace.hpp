@@ -41,8 +41,9 @@ TERRA_HD float decid_mesh_dz(terra_tile_stats const &s) {
 	return dz;
 }
 // vegetation*get_avg_veg() (src/tiled_mesh.cpp:1545, src/tiled_mesh.h:221); dens = {params[0][0].veg, [0][1], [1][0], [1][1]}.  The brush passes the default 1.0
+TERRA_HD float decid_avg_veg(float const dens[4]) {return 0.25f*(dens[0] + dens[1] + dens[2] + dens[3]);}
 TERRA_HD float decid_tile_veg(decid_place_consts_t const &c, float const dens[4]) {
-	return c.b.brush ? 1.0f : c.vegetation*(0.25f*(dens[0] + dens[1] + dens[2] + dens[3]));
+	return c.b.brush ? 1.0f : c.vegetation*decid_avg_veg(dens);
 }
 
 // density_gen[f].eval_index(x, y): build_arrays((x1 + xoff2 + 1000*f), (y1 + yoff2 - 1500*f), xscale, yscale, S, S, 0, force_sine_mode = 1), no glaciate

@@ -15,6 +15,7 @@
 #include "terra_treemap.hpp"
 #include "terra_treeplace.hpp"
 #include "terra_decidplace.hpp"
+#include "terra_sceneryplace.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
@@ -706,6 +707,12 @@ template<class BE> struct terra_engine {
 		if (!(p.tree_slope_thresh > 0.0f) || !std::isfinite(p.tree_slope_thresh)) throw std::invalid_argument("terra_set_decid_params: tree_slope_thresh must be finite and > 0");
 		for (float bs : p.branch_size) {if (!(bs > 0.0f) || !std::isfinite(bs)) throw std::invalid_argument("terra_set_decid_params: branch_size must be finite and > 0");}
 		dp = p;
+	}
+	// what scenery_group::gen reads beyond terra_tree_params: use_voxel_rocks
+	terra_scenery_params sp = {2};
+	void set_scenery_params(terra_scenery_params const &p) {
+		if (p.use_voxel_rocks < 0) throw std::invalid_argument("terra_set_scenery_params: use_voxel_rocks must be >= 0");
+		sp = p;
 	}
 	// height_histogram of estimate_zminmax (src/mesh_gen.cpp:467-480), what get_median_height reads; the device copy follows on the next placement call
 	std::vector<float> height_histogram;
@@ -2501,6 +2508,71 @@ template<class BE> struct terra_engine {
 				}
 			}
 			d_counts[t] = count;
+		});
+	}
+
+	// ---- scenery placement (terra_sceneryplace.hpp): the cell loop of scenery_group::gen (src/scenery.cpp:1263-1353) for every tile of the batch, as
+	// tile_t::update_scenery calls it (vegetation*get_avg_veg()).  There is no setting under which no tile can have scenery: a tile without it is skipped by the caller.
+	void scenery_place_consts(int xoff2, int yoff2, scenery_place_consts_t &c) {
+		if (using_hmap()) throw std::logic_error("tiles_place_scenery: a heightmap texture is set (the texture heights of get_exact_zval are not part of this call)");
+		tree_scene_consts(xoff2, yoff2, nullptr, c.b);
+		c.b.skip_val = 1; c.b.ncell = c.b.S;
+		float const q = 3.321f*(float)c.b.xy_mult/(tp.tree_scale + 1.0f); // unsigned(3.321f*XY_MULT_SIZE/(tree_scale+1)) (:1266)
+		if (!(q >= 0.0f && q < 4294967296.0f)) throw std::invalid_argument("tiles_place_scenery: 3.321*XY_MULT_SIZE/(tree_scale + 1) does not fit an unsigned (smod)");
+		c.smod = std::max(200u, (uint32_t)q);
+		c.voxel_rocks = (sp.use_voxel_rocks == 1 || (sp.use_voxel_rocks >= 2 && ls.vegetation == 0.0f)) ? 1 : 0; // the global, not vegetation_ (:1311)
+		c.vegetation = ls.vegetation; c.tree_scale = tp.tree_scale;
+		c.min_stump_z = (float)((double)water_plane_z + 0.010*(double)zmax_est); c.min_plant_z = (float)((double)water_plane_z + 0.016*(double)zmax_est);
+		c.min_log_z = (float)((double)water_plane_z - 0.040*(double)zmax_est); c.min_mushroom_z = water_plane_z;
+		c.min_water_plane_z = get_water_z_height() - ocean_wave_height;
+		c.zmin = zmin;
+	}
+	void tiles_place_scenery_dev(int32_t const *tile_xy, uint32_t n, int xoff2, int yoff2, uint8_t const *d_skip, uint32_t capacity, scenery_place_pod_t *d_objs,
+		uint32_t *d_counts, uint32_t *d_kind_counts)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		scenery_place_consts_t c;
+		scenery_place_consts(xoff2, yoff2, c);
+		if (capacity && !d_objs) throw std::invalid_argument("tiles_place_scenery: null d_objs");
+		if (((uintptr_t)d_objs & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0 || ((uintptr_t)d_kind_counts & 3u) != 0) {
+			throw std::invalid_argument("tiles_place_scenery: d_objs, d_counts and d_kind_counts must be 4-byte aligned");
+		}
+		std::vector<tile_ref_pod_t> refs(n);
+		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
+		size_t const kb = (sizeof(scenery_place_consts_t) + 255) & ~(size_t)255, rb = ((size_t)n*sizeof(tile_ref_pod_t) + 255) & ~(size_t)255;
+		uint8_t *base = scratch<uint8_t>(s_ao, kb + rb + (size_t)n*4*sizeof(float));
+		scenery_place_consts_t *d_consts = (scenery_place_consts_t *)base; // the kernel reads its constants from memory, as k_tree_place does
+		tile_ref_pod_t *d_refs_w = (tile_ref_pod_t *)(base + kb);
+		float *d_dens = (float *)(base + kb + rb);
+		be.h2d_async(d_refs_w, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
+		tile_ref_pod_t const *d_refs = d_refs_w;
+		c.b.st = sinTable_dev(); c.b.hist = height_histogram_dev();
+		scenery_place_consts_t const cc = c;
+		be.h2d_async(d_consts, &cc, sizeof(cc));
+		{tree_place_consts_t const cb = c.b; be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cb, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});}
+		if (be.tile_place_scenery(d_consts, d_refs, n, d_dens, d_skip, capacity, d_objs, d_counts, d_kind_counts)) return;
+		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			tile_ref_pod_t const r = d_refs[t];
+			uint32_t count = 0, kinds[SCENERY_KINDS];
+			for (int k = 0; k < SCENERY_KINDS; ++k) {kinds[k] = 0;}
+			if (!(d_skip && d_skip[t])) {
+				float const veg_ = scenery_tile_veg(cc, d_dens + 4*t);
+				for (unsigned iy = 0; iy < (unsigned)cc.b.S; ++iy) {
+					for (unsigned ix = 0; ix < (unsigned)cc.b.S; ++ix) {
+						tree_rgen_t rg; int val; bool veg;
+						if (!scenery_cell_selected(cc, veg_, r.tx, r.ty, ix, iy, rg, val, veg)) continue;
+						scenery_place_pod_t o;
+						if (!scenery_cell_finish(cc, r.tx, r.ty, ix, iy, val, veg, rg, o)) continue;
+						if (count < capacity) {d_objs[(size_t)t*capacity + count] = o;}
+						++count; ++kinds[o.kind];
+					}
+				}
+			}
+			d_counts[t] = count;
+			if (d_kind_counts) {for (int k = 0; k < SCENERY_KINDS; ++k) {d_kind_counts[t*SCENERY_KINDS + k] = kinds[k];}}
 		});
 	}
 

@@ -594,6 +594,16 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// scenery placement: one workgroup per tile (k_scenery_place)
+	bool tile_place_scenery(terra::scenery_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, uint32_t capacity,
+		terra::scenery_place_pod_t *objs, uint32_t *counts, uint32_t *kind_counts)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_scenery_place, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, dens, skip, capacity, objs, counts, kind_counts);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

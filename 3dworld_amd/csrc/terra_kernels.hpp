@@ -1652,6 +1652,98 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_decid_place(decid_place_const
 	if (tid == 0) {counts[t] = count;}
 }
 
+// ------------------------------------------------------------------ scenery placement (scenery_group::gen, src/scenery.cpp:1274-1353; terra_sceneryplace.hpp)
+// One workgroup per tile and the tile's S*S cells 256 at a time, row-major, as in k_tree_place: every thread runs the selection of :1276-1281 for its cell (three
+// generator steps and a modulo, then one more step for veg) and the survivors' cell numbers go, in order, into a ring in LDS.  When the ring is flushed every
+// thread takes one survivor and creates its object; the objects of a batch are written behind those of the batches before.  Two ballot-and-prefix compactions, no
+// atomics.  The per-kind counts are ballots too: lane k of every wave adds up the wave's objects of kind k, and the four waves' sums meet in LDS at the end.
+// The finish stage diverges by kind, so it is cut in three: the kind and what it draws before its position (a few generator steps), then gen_spos with its
+// get_exact_zval -- 80 terms of two SINF gathers, the bulk of a survivor's time -- for all lanes together, then the kind's create().  A log's second get_exact_zval
+// (pt2) runs after that in a region of its own in which only the log lanes are live, so no other kind's code waits inside it.
+// When to flush: at 256 pending (and at the end), not at one wave's 64.  The barriers make a flush a block-wide event whatever its size, and its time is the latency
+// of one survivor's gather loop, which is the same for 64 survivors in one wave as for 256 in four waves on four SIMDs.  At the defaults a tile has about 90
+// survivors among 16384 cells: at 256 they are finished in one flush at the end, at 64 in two, the first of them with three waves idle at the barrier.  A higher
+// threshold never adds a flush; only above 256 survivors per tile (tree_scale 8) do both forms flush equally full waves.  The other workgroups of the CU hide a
+// flush's latency in either form.  Measured, 4096 tiles at S = 128: 0.59 ms with 256 against 0.86 ms with 64 in sine mode, 1.22 against 2.43 ms at tree_scale 8.
+// 86 VGPRs, 106 SGPRs with 111 spilled to vector lanes, 2208 B LDS, no scratch: five waves per SIMD.  The timings (tools/bench_scenery_place.py): DESIGN.md, section 4.
+constexpr uint32_t SCENP_FLUSH = TREEP_THREADS;
+__global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_consts_t const *__restrict__ consts, tile_ref_pod_t const *__restrict__ tiles, float const *__restrict__ d_dens,
+	uint8_t const *__restrict__ skip, uint32_t capacity, scenery_place_pod_t *__restrict__ objs, uint32_t *__restrict__ counts, uint32_t *__restrict__ kind_counts)
+{
+	__shared__ uint32_t s_ring[TREEP_RING], s_wave[TREEP_THREADS/64], s_kind[TREEP_THREADS/64][SCENERY_KINDS];
+	scenery_place_consts_t const &c = *consts;
+	uint32_t const t = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+	tile_ref_pod_t const r = tiles[t];
+	// (uniform over the block)
+	if (skip && skip[t]) {
+		if (tid == 0) {counts[t] = 0;}
+		if (kind_counts && tid < (uint32_t)SCENERY_KINDS) {kind_counts[(size_t)t*SCENERY_KINDS + tid] = 0;}
+		return;
+	}
+	float dens[4];
+	for (int k = 0; k < 4; ++k) {dens[k] = d_dens[4*(size_t)t + k];}
+	float const veg_ = scenery_tile_veg(c, dens);
+	uint32_t const S = (uint32_t)c.b.S, ncells = S*S;
+	scenery_place_pod_t *const out = objs + (size_t)t*capacity;
+	uint32_t head = 0, tail = 0, count = 0; // ring [head, tail) and the tile's objects so far: the same in every thread
+	uint32_t kc = 0;                        // lane k < SCENERY_KINDS: this wave's objects of kind k so far
+	for (uint32_t base = 0; base < ncells || head < tail; base += TREEP_THREADS) {
+		if (base < ncells) {
+			uint32_t const cell = base + tid;
+			bool sel = false;
+			if (cell < ncells) {
+				uint32_t const iy = cell/S, ix = cell - iy*S;
+				tree_rgen_t rg; int val; bool veg;
+				sel = scenery_cell_selected(c, veg_, r.tx, r.ty, ix, iy, rg, val, veg);
+			}
+			uint32_t nsel;
+			uint32_t const rank = tp_block_rank(sel, s_wave, nsel);
+			if (sel) {s_ring[(tail + rank) & (TREEP_RING - 1)] = cell;}
+			tail += nsel;
+			__syncthreads();
+		}
+		bool const last = base + TREEP_THREADS >= ncells;
+		if (tail - head < SCENP_FLUSH && !(last && head < tail)) continue; // (too few pending and more cells to come)
+		uint32_t const nb = (tail - head < TREEP_THREADS) ? tail - head : TREEP_THREADS;
+		bool ok = false;
+		int kind = SCENERY_NONE, val = 0; bool veg = false;
+		int32_t pre_i = 0; float pre_f[3] = {0.0f, 0.0f, 0.0f}, pos[3] = {0.0f, 0.0f, 0.0f};
+		uint32_t ix = 0, iy = 0;
+		tree_rgen_t rg; rg.set_state(1, 1);
+		scenery_place_pod_t o;
+		if (tid < nb) {
+			uint32_t const cell = s_ring[(head + tid) & (TREEP_RING - 1)];
+			iy = cell/S; ix = cell - iy*S;
+			scenery_cell_selected(c, veg_, r.tx, r.ty, ix, iy, rg, val, veg); // (the generator as the selection left it: cheaper to redo than to keep)
+			kind = scenery_cell_kind(c, val, veg, rg, pre_i, pre_f);
+		}
+		if (kind != SCENERY_NONE) {scenery_gen_spos(c, r.tx, r.ty, ix, iy, rg, pos);} // all kinds together
+		if (kind != SCENERY_NONE) {ok = scenery_cell_create(c, kind, pre_i, pre_f, rg, pos, o);}
+		if (ok && kind == SCENERY_LOG) {ok = scenery_log_finish(c, tree_exact_zval(c.b, o.p[5], o.p[6]), rg, o);} // the log lanes alone
+		if (ok) {scenery_set_tail(rg, ix, iy, o);}
+		head += nb;
+		uint32_t nobj;
+		uint32_t const rank = tp_block_rank(ok, s_wave, nobj); // (its barriers also keep the next round's writes to the ring behind these reads)
+		if (ok && count + rank < capacity) {out[count + rank] = o;}
+		count += nobj;
+#pragma unroll
+		for (int k = 0; k < SCENERY_KINDS; ++k) {
+			uint32_t const nk = (uint32_t)__popcll(__ballot(ok && kind == k));
+			if (lane == (uint32_t)k) {kc += nk;}
+		}
+	}
+	if (tid == 0) {counts[t] = count;}
+	if (kind_counts) { // (uniform)
+		if (lane < (uint32_t)SCENERY_KINDS) {s_kind[tid >> 6][lane] = kc;}
+		__syncthreads();
+		if (tid < (uint32_t)SCENERY_KINDS) {
+			uint32_t sum = 0;
+			for (uint32_t w = 0; w < TREEP_THREADS/64; ++w) {sum += s_kind[w][tid];}
+			kind_counts[(size_t)t*SCENERY_KINDS + tid] = sum;
+		}
+	}
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

@@ -195,8 +195,8 @@ TERRA_HD int tree_class_from_height(tree_place_consts_t const &c, float zpos, bo
 	if (pine_trees_only) return (c.tree_mode == 3) ? TREE_CLASS_NONE : TREE_CLASS_PINE;
 	return c.only_pine_palm ? TREE_CLASS_PINE : TREE_CLASS_DECID;
 }
-TERRA_HD int tree_type_from_height(tree_place_consts_t const &c, float zpos, tree_rgen_t &r) {
-	bool const pine_trees_only = (c.tree_mode == 2 || c.tree_mode == 3); // world_mode == WMODE_INF_TERRAIN, for_scenery = 0 (:556)
+TERRA_HD int tree_type_from_height(tree_place_consts_t const &c, float zpos, tree_rgen_t &r, bool for_scenery = false) {
+	bool const pine_trees_only = (c.tree_mode == 2 || (!for_scenery && c.tree_mode == 3)); // world_mode == WMODE_INF_TERRAIN (:556)
 	switch (tree_class_from_height(c, zpos, pine_trees_only)) {
 	case TREE_CLASS_PINE:  return (r.rand()%10 == 0) ? T_SH_PINE : T_PINE;
 	case TREE_CLASS_PALM:  return T_PALM;

@@ -89,6 +89,21 @@ def make_decid_params(num_trees=0, num_shared_trees=0, tree_slope_thresh=5.0, br
     return DecidParams(num_trees, num_shared_trees, tree_slope_thresh, (C.c_float * 5)(*branch_size))
 
 
+SCENERY_PLACE_DTYPE = np.dtype([("pos", np.float32, (3,)), ("radius", np.float32), ("kind", np.int32), ("iv", np.int32, (2,)), ("p", np.float32, (8,)),
+                                ("rseed1", np.int32), ("rseed2", np.int32), ("cx", np.uint16), ("cy", np.uint16)])  # terra_scenery_place
+assert SCENERY_PLACE_DTYPE.itemsize == 72
+SCENERY_KINDS = ("leafy_plant", "plant", "rock_shape", "surface_rock", "voxel_rock", "rock", "log", "stump", "mushroom")  # TERRA_SCENERY_*
+
+
+class SceneryParams(C.Structure):  # terra_scenery_params
+    _fields_ = [("use_voxel_rocks", C.c_int32)]
+
+
+def make_scenery_params(use_voxel_rocks=2):
+    """terra_scenery_params with the reference's default (voxel rocks only when the landscape has no vegetation)."""
+    return SceneryParams(use_voxel_rocks)
+
+
 class GRASS_BRUSH(C.Structure):
     """terra_grass_brush: one stroke of the fire modes "Add Grass" / "Remove Grass" (tile_t::add_or_remove_grass_at's arguments)"""
     _fields_ = [("pos", C.c_float * 3), ("radius", C.c_float), ("add_grass", C.c_int32), ("shape", C.c_int32), ("brush_weight", C.c_float)]
@@ -247,6 +262,10 @@ _PROTOS = {
     "terra_tiles_place_decid_trees": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_place_decid_trees_brush_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
     "terra_tiles_place_decid_trees_brush": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
+    "terra_set_scenery_params": (_i32, [_vp, _vp]),
+    "terra_get_scenery_params": (_i32, [_vp, _vp]),
+    "terra_tiles_place_scenery_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
+    "terra_tiles_place_scenery": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -785,6 +804,26 @@ class Terra:
             self._ck(self.lib.terra_tiles_place_decid_trees_brush(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), *tail))
         return trees, counts
 
+    def set_scenery_params(self, sp):
+        self._ck(self.lib.terra_set_scenery_params(self.ctx, C.byref(sp)))
+
+    def get_scenery_params(self):
+        sp = SceneryParams()
+        self._ck(self.lib.terra_get_scenery_params(self.ctx, C.byref(sp)))
+        return sp
+
+    def tiles_place_scenery(self, tile_xy, capacity, xoff2=0, yoff2=0, skip=None, kind_counts=True):
+        """the cell loop of scenery_group::gen for every tile, as tile_t::update_scenery calls it.  skip: [n] bytes (update_scenery does not generate).
+        -> (objs SCENERY_PLACE_DTYPE [n, capacity], counts uint32 [n], kind_counts uint32 [n, 9] or None); records past counts[t] are zero"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        objs, counts = np.zeros((n, capacity), SCENERY_PLACE_DTYPE), np.zeros(n, np.uint32)
+        kinds = np.zeros((n, len(SCENERY_KINDS)), np.uint32) if kind_counts else None
+        self._ck(self.lib.terra_tiles_place_scenery(self.ctx, txy.ctypes.data, n, xoff2, yoff2, None if sk is None else sk.ctypes.data, capacity,
+                                                    objs.ctypes.data if capacity else None, counts.ctypes.data, None if kinds is None else kinds.ctypes.data))
+        return objs, counts, kinds
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -957,6 +996,12 @@ class Terra:
         else:
             pos, radius, is_square = brush
             self._ck(self.lib.terra_tiles_place_decid_trees_brush_dev(*args, (C.c_float * 3)(*pos), radius, int(bool(is_square)), capacity, trees_ptr, counts_ptr))
+
+    def tiles_place_scenery_dev(self, tile_xy, capacity, objs_ptr, counts_ptr, xoff2=0, yoff2=0, skip_ptr=None, kind_counts_ptr=None):
+        """scenery placement of a device-resident batch: objs_ptr [n][capacity] SCENERY_PLACE_DTYPE records, counts_ptr [n] uint32, skip_ptr [n] bytes or None,
+        kind_counts_ptr [n][9] uint32 or None.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_place_scenery_dev(self.ctx, txy.ctypes.data, len(txy), xoff2, yoff2, skip_ptr, capacity, objs_ptr, counts_ptr, kind_counts_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

@@ -594,7 +594,7 @@ int  terra_tiles_place_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint3
 
 /* ---- deciduous tree placement of a tile batch (every supported tile size S): tree_cont_t::gen_trees_tt_within_radius (src/Tree.cpp:2209-2305) from :2240 on, the
  * generating half of tile_t::gen_decid_trees_if_needed (src/tiled_mesh.cpp:1536-1547) and of the decid_trees half of "Add Trees" (tile_t::add_new_trees, :3805-3811,
- * :3837).  With terra_tiles_place_trees both tree containers of a tile now come from the device.
+ * :3837).  With terra_tiles_place_trees both tree containers of a tile now come from the device; the scenery container: terra_tiles_place_scenery, below.
  * terra_decid_params: what this path reads beyond terra_tree_params (tree_scale, tree_density_thresh, tree_type_rand_zone, tree_mode, force_tree_class,
  * only_pine_palm_trees, rand_gen_index), terra_landscape and the scene.  TERRA_ERR_ARG (and nothing changes): num_trees < 0, a tree_slope_thresh or a branch_size
  * that is not finite and > 0. */
@@ -654,6 +654,58 @@ int  terra_tiles_place_decid_trees_brush_dev(terra_ctx *ctx, const int32_t *tile
                                              const float *d_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *d_trees, uint32_t *d_counts);
 int  terra_tiles_place_decid_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
                                          const float *h_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *h_trees, uint32_t *h_counts);
+
+/* ---- scenery placement of a tile batch (every supported tile size S): the cell loop of scenery_group::gen (src/scenery.cpp:1263-1353), the generating half of
+ * tile_t::update_scenery (src/tiled_mesh.cpp:1568-1578), which fills the third container of a tile -- rocks, plants, logs, stumps and mushrooms.  The reference
+ * "assumes trees are generated before scenery"; nothing here reads the trees.
+ * terra_scenery_params: what this path reads beyond terra_tree_params (tree_scale, tree_type_rand_zone, tree_mode, force_tree_class, only_pine_palm_trees,
+ * rand_gen_index), terra_landscape (vegetation, the biome field) and the scene.  TERRA_ERR_ARG (and nothing changes): use_voxel_rocks < 0. */
+typedef struct terra_scenery_params {
+	int32_t use_voxel_rocks;     /* config "use_voxel_rocks", 2 (src/3DWorld.cpp:93): 0 never, 1 always, 2 only when the landscape's vegetation is 0 */
+} terra_scenery_params;
+int  terra_set_scenery_params(terra_ctx *ctx, const terra_scenery_params *params);
+int  terra_get_scenery_params(terra_ctx *ctx, terra_scenery_params *out);
+/* terra_tiles_place_scenery: scenery_group::gen(x1 - xoff2, y1 - yoff2, .., vegetation*get_avg_veg(), ..) for every tile, bit for bit.  All objects of a tile go into
+ * one list in the reference's loop order (rows, then columns); the reference pushes into nine vectors, and a stable split of the list by `kind` reproduces each.
+ * Per cell: the seeds of :1276-1277 from i + yoff2, j + xoff2 and rand_gen_index (int products that wrap); val = int(unsigned(rand2_seed_mix()) % smod) with
+ * smod = max(200U, unsigned(3.321f*XY_MULT_SIZE/(tree_scale+1))) in float arithmetic; the cell is dropped when val >= 150; rand2_mix(); veg = (rseed1&127)/128.0 <
+ * vegetation_, with vegetation_ = vegetation*get_avg_veg() from the four veg corners generated internally as for terra_tiles_place_decid_trees; then the chain of
+ * :1284-1351 in the reference's order (rand2()%100 < 35 draws only when veg holds, and the later branches see the advanced generator); voxel rocks when
+ * use_voxel_rocks == 1 or (use_voxel_rocks >= 2 and the landscape's vegetation == 0.0: the global, not vegetation_).  The minimum heights of :1267-1270 are formed in
+ * double.  Every create() runs with use_xy = 1: gen_spos (:94-99: get_xval / get_yval of the local index + 0.5*DX_VAL*rand2d(), then get_exact_zval) and the class's
+ * own statements with the operand types the source gives them (the double literals, pointT's operator/= and mag(), signed_rand_vector_norm whose first draw is z and
+ * third x, the left operand of rand_uniform2(..)*rand_float2() drawing first).  get_min_water_plane_z() is get_water_z_height() - ocean_wave_height of the scene; a
+ * log's `zmin` is the scene's.  Logs and stumps take calc_type() = get_tree_type_from_height(pos.z, rgen, 1) and are dropped when it is negative.
+ * The record stops where the object's random draws for its placement end: leafy_plant before gen_leaves(), rock_shape3d before gen_rock (the record carries rs_rock and
+ * the type bit; gen_rock re-seeds itself from rs_rock), surface_rock before the surface cache, voxel_rock without gen_model_ix.  rseed1 / rseed2 are global_rand_gen
+ * at that point, which is what gen_leaves() and the surface cache continue from.
+ * xoff2 / yoff2: as for terra_tiles_place_trees (scenery_off.set_from_xyoff2()): the loop runs over the local indices, the seeds use i + yoff2 and j + xoff2,
+ * get_xval takes the local index.  skip (optional): [n] bytes, non-zero = update_scenery does not generate (scenery_enabled, is_distant, dist_scale, is_visible).
+ * objs: [n][capacity] records; counts: [n].  A tile with more than `capacity` objects gets the first `capacity` and counts[t] still reports all of them.  Records
+ * past counts[t] are not written.  kind_counts (optional): [n][TERRA_SCENERY_KINDS], every object of the tile per kind, those beyond `capacity` included (what the
+ * engine reserve()s).
+ * With the engine stay check_valid_scenery_pos (on pos and radius of the record; for a rock_shape after its gen_rock), the city ponds (:1354-1375), post_gen_setup
+ * (geometry, VBOs, cache_closest_tree_type) and leafy_plants.size() as plant_ix.  None of them draws from a cell's generator before the next cell re-seeds it, so
+ * filtering the records afterwards is identical.
+ * TERRA_ERR_ARG: a 3.321*XY_MULT_SIZE/(tree_scale+1) that does not fit an unsigned, an unsupported S, a NULL required pointer (tile_xy, counts when n > 0; objs when
+ * capacity > 0), a misaligned pointer.  TERRA_ERR_STATE before terra_init_scene, and while a heightmap texture is set (the texture heights of get_exact_zval are not
+ * part of this call).  n == 0 does nothing once the scene and the tile size have passed.  The device form only enqueues. */
+enum {TERRA_SCENERY_LEAFY_PLANT, TERRA_SCENERY_PLANT, TERRA_SCENERY_ROCK_SHAPE, TERRA_SCENERY_SURFACE_ROCK, TERRA_SCENERY_VOXEL_ROCK,
+      TERRA_SCENERY_ROCK, TERRA_SCENERY_LOG, TERRA_SCENERY_STUMP, TERRA_SCENERY_MUSHROOM, TERRA_SCENERY_KINDS};
+typedef struct terra_scenery_place {
+	float pos[3];            /* the object's pos as its create() leaves it (rock_shape: before the += 0.1*radius of :156, radius comes from gen_rock) */
+	float radius;            /* 0 for rock_shape */
+	int32_t kind;            /* TERRA_SCENERY_* */
+	int32_t iv[2];           /* plant / leafy plant: {type, 0}; log / stump: {calc_type()'s type, 0}; rock_shape: {rs_rock, gen_rock's type bit}; voxel_rock: {rseed, 0}; else 0 */
+	float p[8];              /* plant {height}; mushroom {height}; stump {radius2, height}; surface_rock {dir xyz}; rock {scale xyz, size, dir xyz, angle};
+	                            log {radius2, length, dir xyz, pt2 xyz}; unused entries 0 */
+	int32_t rseed1, rseed2;  /* global_rand_gen where the device stops */
+	uint16_t cx, cy;         /* the cell inside the tile */
+} terra_scenery_place;       /* 72 bytes */
+int  terra_tiles_place_scenery_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, uint32_t capacity,
+                                   terra_scenery_place *d_objs, uint32_t *d_counts, uint32_t *d_kind_counts);
+int  terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, uint32_t capacity,
+                               terra_scenery_place *h_objs, uint32_t *h_counts, uint32_t *h_kind_counts);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

@@ -279,6 +279,19 @@ inline void tiles_gen_decid_trees_tt_within_radius(tile_batch_dev_t const &b, in
 	check(terra_tiles_place_decid_trees_brush_dev(default_ctx(), b.tile_xy, b.n, -toff_dxoff, -toff_dyoff, d_can_have_trees_false, b.d_stats, b.d_stats ? b.d_zvals : nullptr, pos, radius,
 		is_square ? 1 : 0, capacity, d_trees, d_counts), "gen_decid_trees_tt_within_radius");
 }
+// ---- scenery placement of a batch on device arrays.  use_voxel_rocks goes in once (set_scenery_globals); tree_scale, tree_mode .. come from set_tree_globals.
+inline void set_scenery_globals(terra_scenery_params const &p) {check(terra_set_scenery_params(default_ctx(), &p), "set_scenery_params");}
+// scenery_group::gen (src/scenery.cpp:1263-1353, the cell loop) for every tile as tile_t::update_scenery (src/tiled_mesh.cpp:1568-1578) calls it: xoff2 / yoff2 are the
+// globals at that time (scenery_off.set_from_xyoff2()); vegetation*get_avg_veg() is taken from the landscape and the biome field.  d_no_scenery[t] != 0: update_scenery
+// returns before gen() (scenery_enabled, is_distant, dist_scale, is_visible).  d_objs [n][capacity], d_counts [n], d_kind_counts [n][TERRA_SCENERY_KINDS] (or null):
+// the engine reserve()s from the kind counts, then for each record in order: builds the object of `kind` from the fields (for a rock_shape: set_state is not needed,
+// gen_rock(48, 0.05/tree_scale, iv[0], iv[1]) re-seeds; for a leafy plant and a surface rock: global_rand_gen.set_state(rseed1, rseed2) before gen_leaves() / the
+// surface cache), filters it with check_valid_scenery_pos and pushes it; then the city ponds and post_gen_setup as before
+inline void tiles_gen_scenery(tile_batch_dev_t const &b, int xoff2, int yoff2, unsigned char const *d_no_scenery, unsigned capacity, terra_scenery_place *d_objs, unsigned *d_counts,
+	unsigned *d_kind_counts)
+{
+	check(terra_tiles_place_scenery_dev(default_ctx(), b.tile_xy, b.n, xoff2, yoff2, d_no_scenery, capacity, d_objs, d_counts, d_kind_counts), "scenery_group::gen");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
