@@ -875,6 +875,71 @@ int terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
 		}
 	TERRA_CATCH
 }
+int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_tree_size_params(*params); TERRA_CATCH
+}
+int terra_get_tree_size_params(terra_ctx *ctx, terra_tree_size_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	*out = ctx->eng.tsp; return TERRA_OK;
+}
+static_assert(sizeof(terra_tree_inst) == 12 && sizeof(terra::tree_inst_pod_t) == 12, "terra_tree_inst layout");
+int terra_set_tree_instances(terra_ctx *ctx, const terra_tree_inst *h_insts, uint32_t count) {
+	TERRA_CHECK_CTX if (count && !h_insts) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_tree_instances((terra::tree_inst_pod_t const *)h_insts, count); TERRA_CATCH
+}
+int terra_get_tree_instances(terra_ctx *ctx, terra_tree_inst *h_insts, uint32_t capacity, uint32_t *count) {
+	TERRA_CHECK_CTX if (!count) return terra::fail(TERRA_ERR_ARG, "null argument");
+	std::vector<terra::tree_inst_pod_t> const &v = ctx->eng.tree_insts;
+	*count = (uint32_t)v.size();
+	if (h_insts) {memcpy(h_insts, v.data(), std::min<size_t>(capacity, v.size())*sizeof(terra_tree_inst));}
+	return TERRA_OK;
+}
+int terra_tiles_tree_ao_shadows_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                                    const terra_tree_place *d_pine, const uint32_t *d_pine_counts, uint32_t pine_capacity,
+                                    const terra_decid_place *d_decid, const uint32_t *d_decid_counts, uint32_t decid_capacity,
+                                    const float *d_decid_radius, const float *d_decid_radius_by_id, uint32_t num_radius_by_id, const uint8_t *d_flags,
+                                    uint32_t list_capacity, uint8_t *d_tree_map, uint8_t *d_updated, float *d_trmax, uint32_t *d_list_counts) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !d_tree_map)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_tree_ao_shadows_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, (terra::tree_place_pod_t const *)d_pine, d_pine_counts, pine_capacity,
+		(terra::decid_place_pod_t const *)d_decid, d_decid_counts, decid_capacity, d_decid_radius, d_decid_radius_by_id, num_radius_by_id, d_flags, list_capacity,
+		d_tree_map, d_updated, d_trmax, d_list_counts); TERRA_CATCH
+}
+int terra_tiles_tree_ao_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                                const terra_tree_place *h_pine, const uint32_t *h_pine_counts, uint32_t pine_capacity,
+                                const terra_decid_place *h_decid, const uint32_t *h_decid_counts, uint32_t decid_capacity,
+                                const float *h_decid_radius, const float *h_decid_radius_by_id, uint32_t num_radius_by_id, const uint8_t *h_flags,
+                                uint32_t list_capacity, uint8_t *h_tree_map, uint8_t *h_updated, float *h_trmax, uint32_t *h_list_counts) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !h_tree_map)) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size(); // (before the arrays are read: they are sized by S)
+		if (n == 0) return TERRA_OK;
+		bool const has_pine = h_pine_counts && pine_capacity, has_decid = h_decid_counts && decid_capacity;
+		if ((has_pine && !h_pine) || (has_decid && !h_decid)) return terra::fail(TERRA_ERR_ARG, "tiles_tree_ao_shadows: counts without records");
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const S = ctx->eng.tile_size();
+		size_t const mb = (size_t)n*(S + 1)*(S + 1)*2, pb = has_pine ? (size_t)n*pine_capacity*sizeof(terra_tree_place) : 0, db = has_decid ? (size_t)n*decid_capacity*sizeof(terra_decid_place) : 0,
+			rb = (has_decid && h_decid_radius) ? (size_t)n*decid_capacity*4 : 0, ib = (has_decid && h_decid_radius_by_id) ? (size_t)num_radius_by_id*4 : 0, cb = (size_t)n*4;
+		size_t const om = 0, op = om + up(mb), od = op + up(pb), orr = od + up(db), oi = orr + up(rb), opc = oi + up(ib), odc = opc + up(cb), of = odc + up(cb), ou = of + up(n),
+			ot = ou + up(n), ol = ot + up(cb);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(ol + up(cb));
+		if (has_pine) {be.h2d(d + op, h_pine, pb); be.h2d(d + opc, h_pine_counts, cb);}
+		if (has_decid) {be.h2d(d + od, h_decid, db); be.h2d(d + odc, h_decid_counts, cb);}
+		if (rb) {be.h2d(d + orr, h_decid_radius, rb);}
+		if (ib) {be.h2d(d + oi, h_decid_radius_by_id, ib);}
+		if (h_flags) {be.h2d(d + of, h_flags, n);}
+		ctx->eng.tiles_tree_ao_shadows_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, has_pine ? (terra::tree_place_pod_t const *)(d + op) : nullptr, has_pine ? (uint32_t const *)(d + opc) : nullptr,
+			pine_capacity, has_decid ? (terra::decid_place_pod_t const *)(d + od) : nullptr, has_decid ? (uint32_t const *)(d + odc) : nullptr, decid_capacity,
+			(has_decid && h_decid_radius) ? (float const *)(d + orr) : nullptr, (has_decid && h_decid_radius_by_id) ? (float const *)(d + oi) : nullptr, num_radius_by_id,
+			h_flags ? d + of : nullptr, list_capacity, d + om, d + ou, (float *)(d + ot), (uint32_t *)(d + ol));
+		be.d2h(h_tree_map, d + om, mb);
+		if (h_updated) {be.d2h(h_updated, d + ou, n);}
+		if (h_trmax) {be.d2h(h_trmax, d + ot, cb);}
+		if (h_list_counts) {be.d2h(h_list_counts, d + ol, cb);}
+	TERRA_CATCH
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

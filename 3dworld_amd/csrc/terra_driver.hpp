@@ -16,6 +16,7 @@
 #include "terra_treeplace.hpp"
 #include "terra_decidplace.hpp"
 #include "terra_sceneryplace.hpp"
+#include "terra_treeao.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
@@ -571,6 +572,7 @@ template<class BE> struct terra_engine {
 		if (d_noise3_lut) be.free(d_noise3_lut);
 		if (d_sinTable) be.free(d_sinTable);
 		if (d_hist) be.free(d_hist);
+		if (d_tree_insts) be.free(d_tree_insts);
 	}
 
 	sin_lut_t lut() const {return sin_lut_t{d_sin_table, sscale};}
@@ -713,6 +715,28 @@ template<class BE> struct terra_engine {
 	void set_scenery_params(terra_scenery_params const &p) {
 		if (p.use_voxel_rocks < 0) throw std::invalid_argument("terra_set_scenery_params: use_voxel_rocks must be >= 0");
 		sp = p;
+	}
+	// what the trees' radii read beyond terra_tree_params (small_tree's constructor and get_pine_tree_radius): tree_height_scale, sm_tree_scale, pine_tree_radius_scale
+	terra_tree_size_params tsp = {1.0f, 1.0f, 1.0f};
+	void set_tree_size_params(terra_tree_size_params const &p) {
+		for (float v : {p.tree_height_scale, p.sm_tree_scale, p.pine_tree_radius_scale}) {
+			if (!(v > 0.0f) || !std::isfinite(v)) throw std::invalid_argument("terra_set_tree_size_params: every scale must be finite and > 0");
+		}
+		tsp = p;
+	}
+	// tree_instances (src/sm_tree.cpp:342-364) as far as the radii read it: type, height and width of every instance; the device copy follows on the next call that reads it
+	std::vector<tree_inst_pod_t> tree_insts;
+	tree_inst_pod_t *d_tree_insts = nullptr; size_t d_tree_insts_cap = 0; bool tree_insts_dev_valid = false;
+	void set_tree_instances(tree_inst_pod_t const *v, uint32_t count) {tree_insts.assign(v, v + count); tree_insts_dev_valid = false;}
+	tree_inst_pod_t const *tree_insts_dev() {
+		size_t const ni = tree_insts.size();
+		if (ni > d_tree_insts_cap) {
+			if (d_tree_insts) {be.sync(); be.free(d_tree_insts); d_tree_insts = nullptr; d_tree_insts_cap = 0;}
+			d_tree_insts = (tree_inst_pod_t *)be.alloc(ni*sizeof(tree_inst_pod_t)); d_tree_insts_cap = ni; tree_insts_dev_valid = false;
+		}
+		if (!tree_insts_dev_valid && ni) {be.h2d(d_tree_insts, tree_insts.data(), ni*sizeof(tree_inst_pod_t));}
+		tree_insts_dev_valid = true;
+		return d_tree_insts;
 	}
 	// height_histogram of estimate_zminmax (src/mesh_gen.cpp:467-480), what get_median_height reads; the device copy follows on the next placement call
 	std::vector<float> height_histogram;
@@ -2258,6 +2282,13 @@ template<class BE> struct terra_engine {
 			tree_tile_pod_t const &tt = d_tiles[tree_tile_of(d_tiles, n, (uint32_t)i)];
 			d_par[i] = tree_splat_params(sp[i], tt.xstart, tt.ystart, dxv, dyv);
 		});
+		tree_map_rows_simple(d_tiles, n, S, d_distant, d_par, reset, d_map, d_rowf, d_updated);
+	}
+	// the tree map's simple form on parameterised lists: one logical thread per (tile, texel row) walks the tile's list, then one per tile folds the rows' flags
+	void tree_map_rows_simple(tree_tile_pod_t const *d_tiles, uint32_t n, uint32_t S, uint8_t const *d_distant, tree_splat_pod_t const *d_par, bool reset, uint16_t *d_map,
+		uint8_t *d_rowf, uint8_t *d_updated)
+	{
+		uint32_t const W = S + 1;
 		be.launch((size_t)n*W, [=] TERRA_LAMBDA (size_t i) {
 			uint32_t const t = (uint32_t)(i / W); int const y = (int)(i % W);
 			tree_tile_pod_t const tt = d_tiles[t];
@@ -2282,6 +2313,142 @@ template<class BE> struct terra_engine {
 			for (uint32_t y = 0; y < W; ++y) {u |= d_rowf[t*W + y];}
 			d_updated[t] = u;
 		});
+	}
+	// ---- tree AO shadows of a batch from the placement records (terra_treeao.hpp): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828) run on the tiles in batch
+	// order, every tree_map empty at the start.  Tile t's ordered list is its own trees (culled by its box when no_adj_test(t)), then -- unless no_adj_test(t) -- the trees
+	// of the neighbours that come earlier, in dy, dx order, culled by t's box and gated by t's flags, then what the neighbours that come later push: their own trees that
+	// pass x_test / y_test in their frame.  Three passes: the records' (x, y, ao radius) and trmax, the gather into parameterised lists, the tree map's texel loop.
+	void tiles_tree_ao_shadows_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, tree_place_pod_t const *d_pine, uint32_t const *d_pine_counts,
+		uint32_t pine_cap, decid_place_pod_t const *d_decid, uint32_t const *d_decid_counts, uint32_t decid_cap, float const *d_decid_radius, float const *d_decid_radius_by_id,
+		uint32_t num_radius_by_id, uint8_t const *d_flags, uint32_t list_cap, uint8_t *d_tree_map, uint8_t *d_updated, float *d_trmax, uint32_t *d_list_counts)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		bool const has_pine = d_pine_counts != nullptr && pine_cap != 0, has_decid = d_decid_counts != nullptr && decid_cap != 0;
+		if (!has_pine) {d_pine_counts = nullptr; pine_cap = 0;}
+		if (!has_decid) {d_decid_counts = nullptr; decid_cap = 0; d_decid_radius = nullptr;}
+		if (has_pine && !d_pine) throw std::invalid_argument("tiles_tree_ao_shadows: pine counts without records");
+		if (has_decid && !d_decid) throw std::invalid_argument("tiles_tree_ao_shadows: deciduous counts without records");
+		if (has_decid && !d_decid_radius) {
+			if (!d_decid_radius_by_id) throw std::invalid_argument("tiles_tree_ao_shadows: deciduous records need decid_radius or decid_radius_by_id (sphere_radius stays with the engine)");
+			if (dp.num_shared_trees == 0) throw std::invalid_argument("tiles_tree_ao_shadows: decid_radius_by_id with num_shared_trees == 0 (tree_id is -1)");
+			if (num_radius_by_id != dp.num_shared_trees) throw std::invalid_argument("tiles_tree_ao_shadows: decid_radius_by_id must hold num_shared_trees values");
+		}
+		if (d_decid_radius) {d_decid_radius_by_id = nullptr;} // (the per-record form wins)
+		if (has_pine && tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
+			throw std::invalid_argument("tiles_tree_ao_shadows: instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
+		}
+		if (((uintptr_t)d_tree_map & 1u) != 0) throw std::invalid_argument("tiles_tree_ao_shadows: d_tree_map must be 2-byte aligned");
+		if ((((uintptr_t)d_pine | (uintptr_t)d_pine_counts | (uintptr_t)d_decid | (uintptr_t)d_decid_counts | (uintptr_t)d_decid_radius | (uintptr_t)d_decid_radius_by_id |
+		      (uintptr_t)d_trmax | (uintptr_t)d_list_counts) & 3u) != 0) throw std::invalid_argument("tiles_tree_ao_shadows: records, counts, radii, trmax and list_counts must be 4-byte aligned");
+		uint32_t const S = tile_size(), W = S + 1;
+		uint64_t const src_cap = (uint64_t)pine_cap + decid_cap;
+		if ((uint64_t)n*list_cap > 0xFFFFFFFFull || (uint64_t)n*src_cap > 0xFFFFFFFFull) throw std::invalid_argument("tiles_tree_ao_shadows: n*list_capacity and n*(capacities) must fit 32 bits");
+		// the [n][9] neighbour table, (dy+1)*3 + dx+1 -> batch index or -1; a tile may appear once
+		if (n > (1u << 30)) throw std::invalid_argument("tiles_tree_ao_shadows: more than 2^30 tiles");
+		// (an open-addressed table keyed by the tile's coordinates: the call only enqueues, and at 4096 tiles a tree of pairs would cost more than the kernels)
+		uint32_t hbits = 4;
+		while ((1ull << hbits) < 2ull*n) {++hbits;}
+		uint32_t const hmask = (uint32_t)((1ull << hbits) - 1);
+		std::vector<int32_t> slots((size_t)hmask + 1, -1);
+		auto key_of = [](int32_t tx, int32_t ty) {return ((uint64_t)(uint32_t)tx << 32) | (uint32_t)ty;};
+		auto hash_of = [hbits](uint64_t k) {return (uint32_t)((k*0x9E3779B97F4A7C15ull) >> (64 - hbits));};
+		auto find = [&](int64_t tx, int64_t ty) -> int32_t { // the batch index of tile (tx, ty), -1: not in the batch
+			if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX) return -1;
+			uint64_t const k = key_of((int32_t)tx, (int32_t)ty);
+			for (uint32_t h = hash_of(k);; h = (h + 1) & hmask) {
+				int32_t const v = slots[h];
+				if (v < 0 || key_of(tile_xy[2*v], tile_xy[2*v+1]) == k) return v;
+			}
+		};
+		for (uint32_t t = 0; t < n; ++t) {
+			uint64_t const k = key_of(tile_xy[2*t], tile_xy[2*t+1]);
+			uint32_t h = hash_of(k);
+			for (; slots[h] >= 0; h = (h + 1) & hmask) {
+				if (key_of(tile_xy[2*slots[h]], tile_xy[2*slots[h]+1]) == k) throw std::invalid_argument("tiles_tree_ao_shadows: a tile appears twice in tile_xy");
+			}
+			slots[h] = (int32_t)t;
+		}
+		std::vector<int32_t> nbr((size_t)n*9);
+		std::vector<tree_frame_t> fr(n);
+		for (uint32_t t = 0; t < n; ++t) {
+			for (int k = 0; k < 9; ++k) {nbr[(size_t)t*9 + k] = find((int64_t)tile_xy[2*t] + (k%3 - 1), (int64_t)tile_xy[2*t+1] + (k/3 - 1));}
+			int const x1 = (int)((uint32_t)tile_xy[2*t]*S), y1 = (int)((uint32_t)tile_xy[2*t+1]*S); // (as tiles_tree_map_dev)
+			fr[t].x = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); fr[t].y = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
+		}
+		tree_ao_consts_t c;
+		c.hs = tsp.tree_height_scale*tsp.sm_tree_scale; c.pine_radius_scale = tsp.pine_tree_radius_scale; c.tree_scale = tp.tree_scale;
+		c.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
+		c.dxv = DX_VAL; c.dyv = DY_VAL; c.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; c.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL;
+		c.S = (int)S; c.instanced = tp.instanced ? 1 : 0; c.num_insts = (uint32_t)tree_insts.size(); c.num_shared = dp.num_shared_trees;
+		c.pine_cap = pine_cap; c.decid_cap = decid_cap; c.list_cap = list_cap; c.src_cap = (uint32_t)src_cap;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const fb = up((size_t)n*sizeof(tree_frame_t)), nb = up((size_t)n*9*sizeof(int32_t)), sb = up((size_t)n*src_cap*sizeof(tree_splat_in_t)), rb = up((size_t)n*sizeof(float)),
+			tb = up((size_t)n*sizeof(tree_tile_pod_t)), pb = up((size_t)n*list_cap*sizeof(tree_splat_pod_t));
+		uint8_t *base = scratch<uint8_t>(s_ao, fb + nb + sb + rb + tb + pb + (size_t)n*W + n + 256);
+		tree_frame_t *d_fr_w = (tree_frame_t *)base;
+		int32_t *d_nbr_w = (int32_t *)(base + fb);
+		tree_splat_in_t *d_src = (tree_splat_in_t *)(base + fb + nb);
+		if (!d_trmax) {d_trmax = (float *)(base + fb + nb + sb);} // (written and not returned)
+		tree_tile_pod_t *d_tiles = (tree_tile_pod_t *)(base + fb + nb + sb + rb);
+		tree_splat_pod_t *d_par = (tree_splat_pod_t *)(base + fb + nb + sb + rb + tb);
+		uint8_t *d_rowf = base + fb + nb + sb + rb + tb + pb; // the simple form's per-row `updated`
+		if (!d_updated) {d_updated = d_rowf + (size_t)n*W;}
+		be.h2d_async(d_fr_w, fr.data(), (size_t)n*sizeof(tree_frame_t));
+		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		tree_frame_t const *d_fr = d_fr_w; int32_t const *d_nbr = d_nbr_w;
+		tree_inst_pod_t const *d_insts = (has_pine && tp.instanced) ? tree_insts_dev() : nullptr;
+		be.fill32(d_trmax, 0u, n);
+		uint16_t *d_map = (uint16_t *)d_tree_map;
+		if (be.tile_tree_ao(c, n, d_insts, d_pine, d_pine_counts, d_decid, d_decid_counts, d_decid_radius, d_decid_radius_by_id, d_flags, d_fr, d_nbr, d_src, d_trmax, d_tiles,
+			d_par, d_list_counts, d_map, d_updated)) return;
+		// the simple form: one logical thread per tile for its sources and trmax, one per tile for its list, then the tree map's per-row form
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			float trmax = 0.0f, radius;
+			uint32_t const np = d_pine_counts ? min_u32(d_pine_counts[t], c.pine_cap) : 0u, nd = d_decid_counts ? min_u32(d_decid_counts[t], c.decid_cap) : 0u;
+			for (uint32_t j = 0; j < np; ++j) {d_src[t*c.src_cap + j] = tree_ao_source_pine(c, d_insts, d_pine[t*c.pine_cap + j], radius); trmax = max_std(trmax, radius);}
+			for (uint32_t k = 0; k < nd; ++k) {
+				size_t const i = t*c.decid_cap + k;
+				d_src[t*c.src_cap + c.pine_cap + k] = tree_ao_source_decid(c, d_decid[i], d_decid_radius ? d_decid_radius + i : nullptr, d_decid_radius_by_id, radius);
+				trmax = max_std(trmax, radius);
+			}
+			d_trmax[t] = trmax;
+		});
+		be.launch(n, [=] TERRA_LAMBDA (size_t ti) {
+			uint32_t const t = (uint32_t)ti;
+			tree_frame_t const ft = d_fr[t];
+			int32_t const *nb9 = d_nbr + (size_t)t*9;
+			tree_splat_pod_t *const out = d_par + (size_t)t*c.list_cap;
+			uint32_t count = 0, last = t;
+			for (int k = 0; k < 17; ++k) {
+				int mode = TREE_AO_OWN, slot = 4;
+				uint32_t u = t;
+				if (k >= 1 && k <= 8) {
+					slot = (k <= 4) ? k - 1 : k;
+					if (nb9[slot] < 0 || (uint32_t)nb9[slot] >= t) continue;
+					mode = TREE_AO_PULL; u = (uint32_t)nb9[slot];
+				}
+				else if (k >= 9) {
+					if (!tree_ao_next_push(nb9, last, slot)) break;
+					mode = TREE_AO_PUSH; u = last;
+				}
+				tree_ao_seg_t sg;
+				if (!tree_ao_segment(c, t, mode, u, slot, d_flags, d_trmax, d_pine_counts, d_decid_counts, sg)) continue;
+				tree_frame_t const fu = d_fr[u];
+				for (uint32_t j = 0; j < sg.np + sg.nd; ++j) {
+					tree_splat_in_t const s = d_src[tree_ao_entry(c, sg, j)];
+					if (!tree_ao_keep(c, sg, s, ft.x, ft.y, fu.x, fu.y)) continue;
+					if (count < c.list_cap) {out[count] = tree_splat_params(s, ft.x, ft.y, c.dxv, c.dyv);}
+					++count;
+				}
+			}
+			tree_tile_pod_t tt;
+			tt.xstart = ft.x; tt.ystart = ft.y; tt.first = t*c.list_cap; tt.count = min_u32(count, c.list_cap);
+			d_tiles[t] = tt;
+			if (d_list_counts) {d_list_counts[t] = count;}
+		});
+		tree_map_rows_simple(d_tiles, n, S, nullptr, d_par, true, d_map, d_rowf, d_updated);
 	}
 	// tile_t::upload_shadow_map_texture (:885-911) for n tiles: smask [n][S+2][S+2] per light (read only where the lights that are up need it), ao [n][S+1][S+1] or
 	// null (170), tree map or null (empty) -> [n][S+1][S+1] RGBA8 {mesh shadow, tree shadow, ambient occlusion, 0}

@@ -574,6 +574,24 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// tree AO shadows from the placement records: k_tree_ao_sources once per record slot, k_tree_ao_gather once per tile, then k_tree_map on the device-built lists
+	// (trmax is zero on entry)
+	bool tile_tree_ao(terra::tree_ao_consts_t const &c, uint32_t n, terra::tree_inst_pod_t const *insts, terra::tree_place_pod_t const *pine, uint32_t const *pine_counts,
+		terra::decid_place_pod_t const *decid, uint32_t const *decid_counts, float const *decid_radius, float const *decid_radius_by_id, uint8_t const *flags,
+		terra::tree_frame_t const *frames, int32_t const *nbr, terra::tree_splat_in_t *src, float *trmax, terra::tree_tile_pod_t *tiles, terra::tree_splat_pod_t *par,
+		uint32_t *list_counts, uint16_t *map, uint8_t *updated)
+	{
+		uint32_t const chunks = (c.src_cap + 255)/256;
+		if (simple_kernels || n > 0x7FFFFFFFu || chunks > 65535u) return false;
+		use();
+		uint32_t const S = (uint32_t)c.S, W = S + 1, rmax = terra::TM_CELLS/W, bands = (W + rmax - 1)/rmax, R = (W + bands - 1)/bands;
+		hipLaunchKernelGGL(terra::k_tree_ao_sources, dim3(n, chunks ? chunks : 1), dim3(256), 0, stream, c, insts, pine, pine_counts, decid, decid_counts, decid_radius,
+			decid_radius_by_id, src, trmax, updated);
+		hipLaunchKernelGGL(terra::k_tree_ao_gather, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, frames, nbr, flags, trmax, pine_counts, decid_counts, src, tiles, par, list_counts);
+		hipLaunchKernelGGL(terra::k_tree_map, dim3(n, (W + R - 1)/R), dim3(64), 0, stream, tiles, (uint8_t const *)nullptr, par, (int)S, (int)R, 1, map, updated);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	// tree placement: one workgroup per tile (k_tree_place)
 	bool tile_place_trees(terra::tree_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
 		uint32_t capacity, terra::tree_place_pod_t *trees, uint32_t *counts)

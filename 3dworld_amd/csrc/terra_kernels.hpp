@@ -1744,6 +1744,84 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_c
 	}
 }
 
+// ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
+// terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
+// k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes
+// into the tile's part of the source array, pine first; get_radius() is reduced over the wave and one lane raises trmax[t] with an atomic max on the float's bits
+// (the values are non-negative, so unsigned order is float order; the driver zeroes trmax first).  It also clears `updated`.
+__global__ __launch_bounds__(256) void k_tree_ao_sources(tree_ao_consts_t c, tree_inst_pod_t const *__restrict__ insts, tree_place_pod_t const *__restrict__ pine,
+	uint32_t const *__restrict__ pine_counts, decid_place_pod_t const *__restrict__ decid, uint32_t const *__restrict__ decid_counts, float const *__restrict__ decid_radius,
+	float const *__restrict__ decid_radius_by_id, tree_splat_in_t *__restrict__ src, float *__restrict__ trmax, uint8_t *__restrict__ updated)
+{
+	uint32_t const t = blockIdx.x, j = blockIdx.y*256u + threadIdx.x;
+	if (j == 0) {updated[t] = 0;}
+	float radius = 0.0f;
+	if (j < c.pine_cap) {
+		if (pine_counts && j < min_u32(pine_counts[t], c.pine_cap)) {src[(size_t)t*c.src_cap + j] = tree_ao_source_pine(c, insts, pine[(size_t)t*c.pine_cap + j], radius);}
+	}
+	else if (j < c.src_cap) {
+		uint32_t const k = j - c.pine_cap;
+		if (decid_counts && k < min_u32(decid_counts[t], c.decid_cap)) {
+			size_t const i = (size_t)t*c.decid_cap + k;
+			src[(size_t)t*c.src_cap + j] = tree_ao_source_decid(c, decid[i], decid_radius ? decid_radius + i : nullptr, decid_radius_by_id, radius);
+		}
+	}
+	for (int m = 32; m > 0; m >>= 1) {radius = fmaxf(radius, __shfl_xor(radius, m));}
+	if ((threadIdx.x & 63u) == 0 && radius > 0.0f) {atomicMax((unsigned int *)(trmax + t), __float_as_uint(radius));}
+}
+// k_tree_ao_gather: a workgroup per destination tile t.  It walks t's segments in list order -- own, the pulls in dy, dx order, the pushes in batch order -- 256
+// source entries at a time; every thread runs the filter of its entry (the box cull of :793, or the integer test of :769-775 in the source tile's frame) and the
+// survivors are appended in order through a ballot per wave and a prefix over the four waves, already parameterised against t's frame for k_tree_map.  The tile's
+// pod (first = t*list_cap, count) is written here: nothing of the lists ever exists on the host.
+__global__ __launch_bounds__(TREEP_THREADS) void k_tree_ao_gather(tree_ao_consts_t c, tree_frame_t const *__restrict__ frames, int32_t const *__restrict__ nbr,
+	uint8_t const *__restrict__ flags, float const *__restrict__ trmax, uint32_t const *__restrict__ pine_counts, uint32_t const *__restrict__ decid_counts,
+	tree_splat_in_t const *__restrict__ src, tree_tile_pod_t *__restrict__ tiles, tree_splat_pod_t *__restrict__ par, uint32_t *__restrict__ list_counts)
+{
+	__shared__ uint32_t s_wave[TREEP_THREADS/64];
+	uint32_t const t = blockIdx.x, tid = threadIdx.x;
+	tree_frame_t const ft = frames[t];
+	int32_t nb[9];
+	for (int k = 0; k < 9; ++k) {nb[k] = nbr[(size_t)t*9 + k];}
+	tree_splat_pod_t *const out = par + (size_t)t*c.list_cap;
+	uint32_t count = 0, last = t; // (the same in every thread)
+	for (int k = 0; k < 17; ++k) {
+		int mode = TREE_AO_OWN, slot = 4;
+		uint32_t u = t;
+		if (k >= 1 && k <= 8) { // pull: the neighbours in dy, dx order that come earlier in the batch
+			slot = (k <= 4) ? k - 1 : k;
+			if (nb[slot] < 0 || (uint32_t)nb[slot] >= t) continue;
+			mode = TREE_AO_PULL; u = (uint32_t)nb[slot];
+		}
+		else if (k >= 9) { // push: the neighbours that come later, in batch order
+			if (!tree_ao_next_push(nb, last, slot)) break;
+			mode = TREE_AO_PUSH; u = last;
+		}
+		tree_ao_seg_t sg;
+		if (!tree_ao_segment(c, t, mode, u, slot, flags, trmax, pine_counts, decid_counts, sg)) continue;
+		tree_frame_t const fu = frames[u];
+		uint32_t const total = sg.np + sg.nd;
+		for (uint32_t base = 0; base < total; base += TREEP_THREADS) {
+			uint32_t const j = base + tid;
+			bool keep = false;
+			tree_splat_in_t s = {0.0f, 0.0f, -1.0f};
+			if (j < total) {
+				s = src[tree_ao_entry(c, sg, j)];
+				keep = tree_ao_keep(c, sg, s, ft.x, ft.y, fu.x, fu.y);
+			}
+			uint32_t nk;
+			uint32_t const rank = tp_block_rank(keep, s_wave, nk);
+			if (keep && count + rank < c.list_cap) {out[count + rank] = tree_splat_params(s, ft.x, ft.y, c.dxv, c.dyv);}
+			count += nk;
+		}
+	}
+	if (tid == 0) {
+		tree_tile_pod_t tt;
+		tt.xstart = ft.x; tt.ystart = ft.y; tt.first = t*c.list_cap; tt.count = min_u32(count, c.list_cap);
+		tiles[t] = tt;
+		if (list_counts) {list_counts[t] = count;}
+	}
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

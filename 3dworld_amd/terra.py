@@ -104,6 +104,20 @@ def make_scenery_params(use_voxel_rocks=2):
     return SceneryParams(use_voxel_rocks)
 
 
+TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
+assert TREE_INST_DTYPE.itemsize == 12
+TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
+
+
+class TreeSizeParams(C.Structure):  # terra_tree_size_params
+    _fields_ = [("tree_height_scale", C.c_float), ("sm_tree_scale", C.c_float), ("pine_tree_radius_scale", C.c_float)]
+
+
+def make_tree_size_params(tree_height_scale=1.0, sm_tree_scale=1.0, pine_tree_radius_scale=1.0):
+    """terra_tree_size_params with the reference's defaults."""
+    return TreeSizeParams(tree_height_scale, sm_tree_scale, pine_tree_radius_scale)
+
+
 class GRASS_BRUSH(C.Structure):
     """terra_grass_brush: one stroke of the fire modes "Add Grass" / "Remove Grass" (tile_t::add_or_remove_grass_at's arguments)"""
     _fields_ = [("pos", C.c_float * 3), ("radius", C.c_float), ("add_grass", C.c_int32), ("shape", C.c_int32), ("brush_weight", C.c_float)]
@@ -262,6 +276,12 @@ _PROTOS = {
     "terra_tiles_place_decid_trees": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_place_decid_trees_brush_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
     "terra_tiles_place_decid_trees_brush": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _f3, _f, _i32, _u32, _vp, _vp]),
+    "terra_set_tree_size_params": (_i32, [_vp, _vp]),
+    "terra_get_tree_size_params": (_i32, [_vp, _vp]),
+    "terra_set_tree_instances": (_i32, [_vp, _vp, _u32]),
+    "terra_get_tree_instances": (_i32, [_vp, _vp, _u32, _vp]),
+    "terra_tiles_tree_ao_shadows_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "terra_tiles_tree_ao_shadows": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_set_scenery_params": (_i32, [_vp, _vp]),
     "terra_get_scenery_params": (_i32, [_vp, _vp]),
     "terra_tiles_place_scenery_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
@@ -824,6 +844,50 @@ class Terra:
                                                     objs.ctypes.data if capacity else None, counts.ctypes.data, None if kinds is None else kinds.ctypes.data))
         return objs, counts, kinds
 
+    def set_tree_size_params(self, tsp):
+        self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
+
+    def get_tree_size_params(self):
+        tsp = TreeSizeParams()
+        self._ck(self.lib.terra_get_tree_size_params(self.ctx, C.byref(tsp)))
+        return tsp
+
+    def set_tree_instances(self, insts):
+        """tree_instances as the radii read it: TREE_INST_DTYPE records (type, height, width after the constructor), pines first"""
+        v = np.ascontiguousarray(insts, TREE_INST_DTYPE).reshape(-1)
+        self._ck(self.lib.terra_set_tree_instances(self.ctx, v.ctypes.data if len(v) else None, len(v)))
+
+    def get_tree_instances(self):
+        n = _u32()
+        self._ck(self.lib.terra_get_tree_instances(self.ctx, None, 0, C.byref(n)))
+        out = np.empty(n.value, TREE_INST_DTYPE)
+        self._ck(self.lib.terra_get_tree_instances(self.ctx, out.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def tiles_tree_ao_shadows(self, tile_xy, list_capacity, pine=None, pine_counts=None, decid=None, decid_counts=None, decid_radius=None, decid_radius_by_id=None,
+                              flags=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):
+        """tile_t::apply_tree_ao_shadows on the tiles of the batch in batch order, from the placement records: pine TREE_PLACE_DTYPE [n, cap] with pine_counts [n],
+        decid DECID_PLACE_DTYPE [n, cap] with decid_counts [n] and decid_radius [n, cap] or decid_radius_by_id [num_shared_trees]; flags: [n] bytes (TREE_AO_*).
+        -> (tree_map u8 [n,S+1,S+1,2], updated bool [n], trmax float32 [n], list_counts uint32 [n])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        S = self.tile_size
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        pr = None if pine is None else np.ascontiguousarray(pine, TREE_PLACE_DTYPE).reshape(n, -1)
+        pc = None if pine_counts is None else np.ascontiguousarray(pine_counts, np.uint32).reshape(n)
+        dr = None if decid is None else np.ascontiguousarray(decid, DECID_PLACE_DTYPE).reshape(n, -1)
+        dc = None if decid_counts is None else np.ascontiguousarray(decid_counts, np.uint32).reshape(n)
+        rr = None if decid_radius is None else np.ascontiguousarray(decid_radius, np.float32).reshape(n, -1)
+        assert rr is None or (dr is not None and rr.shape == dr.shape)
+        ri = None if decid_radius_by_id is None else np.ascontiguousarray(decid_radius_by_id, np.float32).reshape(-1)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint8).reshape(n)
+        tree_map, upd = np.empty((n, S + 1, S + 1, 2), np.uint8), np.empty(n, np.uint8)
+        trmax, lc = np.empty(n, np.float32), np.empty(n, np.uint32)
+        self._ck(self.lib.terra_tiles_tree_ao_shadows(self.ctx, txy.ctypes.data, n, dxoff, dyoff, xoff2, yoff2, ptr(pr), ptr(pc), 0 if pr is None else pr.shape[1],
+                                                      ptr(dr), ptr(dc), 0 if dr is None else dr.shape[1], ptr(rr), ptr(ri), 0 if ri is None else len(ri), ptr(fl),
+                                                      list_capacity, tree_map.ctypes.data, upd.ctypes.data, trmax.ctypes.data, lc.ctypes.data))
+        return tree_map, upd.astype(bool), trmax, lc
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -1002,6 +1066,16 @@ class Terra:
         kind_counts_ptr [n][9] uint32 or None.  Only enqueues."""
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_place_scenery_dev(self.ctx, txy.ctypes.data, len(txy), xoff2, yoff2, skip_ptr, capacity, objs_ptr, counts_ptr, kind_counts_ptr))
+
+    def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
+                                  decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,
+                                  list_counts_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):
+        """the tree AO shadows of a device-resident batch, from the records the placement calls left on the device: tree_map_ptr [n][S+1][S+1][2] bytes, updated_ptr
+        n bytes, trmax_ptr n floats, list_counts_ptr n uint32 (each or None).  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_tree_ao_shadows_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, pine_ptr, pine_counts_ptr, pine_capacity,
+                                                          decid_ptr, decid_counts_ptr, decid_capacity, decid_radius_ptr, decid_radius_by_id_ptr, num_radius_by_id,
+                                                          flags_ptr, list_capacity, tree_map_ptr, updated_ptr, trmax_ptr, list_counts_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

@@ -487,8 +487,9 @@ int  terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t
  * the map with 255 (tree_map.clear() + resize, :824-825), reset == 0 continues on the map as it is (a neighbour's push_tree_ao_shadow, :740-746); then every splat of
  * its list is the texel loop of tile_t::add_tree_ao_shadow (:751-767), in list order, bit for bit: the order matters, (uchar)((uchar)(255*a)*b) is not
  * (uchar)((uchar)(255*b)*a).  x, y: pos in the tile's camera-space frame (get_center() + pt_off, :791, or pos2 of :744); radius: get_ao_radius().
- * The caller builds the lists: the own-tree loop, the eight neighbours in dy, dx order with the bounding-box cull of :793, the x_test / y_test border push of
- * :768-778 and the trmax < min(DX_VAL, DY_VAL) shortcut stay in the engine; add_tree_ao_shadow's body becomes "append to the tile's list".
+ * Here the caller builds the lists -- the own-tree loop, the eight neighbours in dy, dx order with the bounding-box cull of :793, the x_test / y_test border push of
+ * :768-778 and the trmax < min(DX_VAL, DY_VAL) shortcut -- and add_tree_ao_shadow's body becomes "append to the tile's list": the call for engines that keep their
+ * own trees.  terra_tiles_tree_ao_shadows, below, builds the lists on the device from the placement records.
  * tree_map: [n][S+1][S+1][2] bytes {ao, sh}, 2-byte aligned.  updated: [n] bytes or NULL; updated[t] = 1 when any texel of tile t was multiplied in this call
  * (:765, :779).  is_distant: [n] bytes or NULL; a distant tile is filled with 255 under reset and left alone otherwise, updated = 0 (:743, :822): an all-255 map reads
  * as the reference's empty tree_map in both consumers.  dxoff / dyoff = xoff - xoff2 / yoff - yoff2.
@@ -519,7 +520,8 @@ int  terra_tiles_tree_weights_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_m
 int  terra_tiles_tree_weights(terra_ctx *ctx, uint32_t n, const uint8_t *h_mesh_weights, const uint8_t *h_tree_map, uint8_t *h_weights);
 
 /* ---- pine / palm tree placement of a tile batch (every supported tile size S): the generating half of "Add Trees" and of tile_t::init_pine_tree_draw
- * (src/tiled_mesh.cpp:1430-1437).  The chain zvals -> tree placement -> splat lists -> tree map -> shadow texture and weights then runs without the host in between.
+ * (src/tiled_mesh.cpp:1430-1437).  The chain zvals -> tree placement -> terra_tiles_tree_ao_shadows (radii, splat lists and tree map) -> shadow texture and weights
+ * runs without the host in between.
  * terra_tree_params: the globals this path reads beyond the scene (water_plane_z, zmax_est, glaciate_exp, relh_adj_tex: terra_state) and the landscape (vegetation,
  * biome_x_offset, enable_terrain_env: terra_landscape).  The defaults are the reference's; with tree_mode 1 no call places a tree.
  * TERRA_ERR_ARG: sm_tree_density < 0, tree_scale <= 0, tree_mode outside 0 .. 3, force_tree_class outside -1 .. 3 (TREE_CLASS_DETAILED has no small tree type:
@@ -706,6 +708,72 @@ int  terra_tiles_place_scenery_dev(terra_ctx *ctx, const int32_t *tile_xy, uint3
                                    terra_scenery_place *d_objs, uint32_t *d_counts, uint32_t *d_kind_counts);
 int  terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, uint32_t capacity,
                                terra_scenery_place *h_objs, uint32_t *h_counts, uint32_t *h_kind_counts);
+
+/* ---- tree AO shadows of a tile batch from the placement records (every supported tile size S): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828), the step
+ * between the two placements above and terra_tiles_shadow_texture / terra_tiles_tree_weights.  One call goes from the records as they lie in device memory to the
+ * tree maps of the batch, bit for bit; with it zvals -> stats -> both placements -> tree map -> shadow texture / tree weights is one stream of launches.
+ * terra_tree_size_params: the globals the radii read beyond terra_tree_params.tree_scale (config keys, src/3DWorld.cpp:1968-1999).  A value that is not finite and
+ * > 0 is TERRA_ERR_ARG and changes nothing.
+ * terra_set_tree_instances: tree_instances (create_pine_tree_instances, src/sm_tree.cpp:342-364) as far as the radii read it: type, height and width of every
+ * instance after its constructor.  The library keeps a copy on the host and one on the device.  get: *count = the length; up to `capacity` values are written when
+ * h_insts is not NULL.
+ * Radii.  A pine / palm record that is not instanced (inst < 0) is the constructor of src/sm_tree.cpp:717-753 as far as it touches the size -- height *=
+ * tree_height_scale*sm_tree_scale, width *= stt[type].width_scale, height *= stt[type].height_scale (stt[], :46-53), none of its random draws -- then
+ * get_pine_tree_radius (:911-914), get_radius and get_ao_radius (src/small_tree.h:74-75, branch_xy_scale 1) with the source's operand types.  An instanced record
+ * (inst >= 0) is small_tree(p, instance_id) (:705-715): the instance's type (not the record's: T_SH_PINE shares the pine range), its width and height times
+ * calc_tree_size() (:326).  Instanced records are applied only while terra_tree_params.instanced is set.  A deciduous record's get_radius() is
+ * tdata().sphere_radius, which comes from gen_tree's geometry and stays with the engine: decid_radius [n][decid_capacity] holds one value per record, or
+ * decid_radius_by_id [num_radius_by_id] one per shared tree, indexed by the record's tree_id; the per-record form wins when both are given.  get_ao_radius() is
+ * 0.5*radius (src/tree_3dw.h:313).  A record the reference could not have made is dropped (no splat, nothing added to trmax): a type outside 0 .. 5, an inst outside
+ * the table or while `instanced` is off, a tree_id outside the table, a radius that is negative or not finite.
+ * Inputs.  dxoff / dyoff: the map's mesh_off, as for terra_tiles_tree_map.  xoff2 / yoff2: what the placement ran with (ptree_off / dtree_off.set_from_xyoff2()):
+ * pt = get_center() + pt_off with pt_off = ((dxoff + xoff2)*DX_VAL, (dyoff + yoff2)*DY_VAL), an int sum times a float (src/animals.h:26).  pine / pine_counts /
+ * pine_capacity and decid / decid_counts / decid_capacity: as the placement calls wrote them; a count above its capacity means the first `capacity` records.  A
+ * group is absent when its counts are NULL or its capacity 0.  flags (optional): [n] bytes, bit 0 = can_have_pine_palm_trees() is false, bit 1 =
+ * can_have_decid_trees() is false, bit 2 = is_distant.
+ * Semantics.  The result is what the reference leaves after apply_tree_ao_shadows() has run on the tiles of the batch in batch order, every tree_map empty at the
+ * start; tiles outside the batch do not exist.  get_adj_tile_smap (src/tiled_mesh.h:295-298) returns a neighbour only when its tree_map is not empty, that is when
+ * it was processed earlier and is not distant.  trmax(t) = the maximum of 0 and get_radius() over both groups of tile t as passed, whatever the flags say
+ * (postproc_trees, small_tree_group::add_tree, tree_cont_t::get_rmax); no_adj_test(t) = trmax(t) < min(DX_VAL, DY_VAL) (:826).  Tile t's ordered list:
+ *  1. its own pine trees, then its own deciduous trees, each group gated by t's flag (:800-807); under no_adj_test(t) the bounding-box cull of :793 against
+ *     get_mesh_bcube() (src/tiled_mesh.h:238-241) applies;
+ *  2. unless no_adj_test(t): for dy = -1 .. 1, dx = -1 .. 1 (:809-815) the trees of the neighbour u that is in the batch, earlier than t and not distant, pine then
+ *     deciduous, gated by t's flags (the reference tests `this`, not `tile`), the cull of :793 always on;
+ *  3. for every neighbour u later than t, in batch order, not distant and with no_adj_test(u) false: those of u's own trees, gated by u's flags, for which
+ *     x_test[dx+1] && y_test[dy+1] of :769-775 holds with xc, yc, rval taken in u's frame and (dx, dy) pointing from u to t (push_tree_ao_shadow, :740-746;
+ *     pos2 = pos: all tiles of a batch share mesh_off).
+ * The list then runs through the texel loop of terra_tiles_tree_map in list order, with its tie-breaking and its skipped splats.  A distant tile's map is filled
+ * with 255, its updated is 0, and it is neither a pull source nor a push target.
+ * The same tile set in another batch order gives other maps: step 2 culls by the float box, step 3 by the integer test on rounded texel coordinates, so a tree near
+ * a border can reach the neighbour in one order and not in the other, and the order of the list decides the roundings of the texels' products.
+ * Outputs.  tree_map: [n][S+1][S+1][2], 2-byte aligned.  updated (optional): [n] bytes.  trmax (optional): [n] floats, what get_bcube needs.  list_counts
+ * (optional): [n], the full length of each tile's list; a tile whose list exceeds list_capacity gets its first list_capacity splats applied.
+ * TERRA_ERR_ARG: a NULL required pointer (tile_xy, tree_map when n > 0; the records of a group that is present; a radius array for a deciduous group), a misaligned
+ * pointer, an unsupported S, a tile that appears twice in tile_xy, `instanced` with an instance table whose length is not num_pine_insts + num_palm_insts,
+ * decid_radius_by_id alone with num_radius_by_id != terra_decid_params.num_shared_trees or with 0 shared trees, n*list_capacity or n*(pine_capacity +
+ * decid_capacity) beyond 32 bits.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing.  The device form only enqueues; tile_xy is a host array in both
+ * forms (the [n][9] neighbour table is built from it and uploaded).  Scratch comes from the context's arena (terra_release_scratch frees it). */
+typedef struct terra_tree_size_params {
+	float tree_height_scale;       /* config "tree_height_scale", 1 */
+	float sm_tree_scale;           /* config "sm_tree_scale", 1 */
+	float pine_tree_radius_scale;  /* config "pine_tree_radius_scale", 1 */
+} terra_tree_size_params;
+int  terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params);
+int  terra_get_tree_size_params(terra_ctx *ctx, terra_tree_size_params *out);
+typedef struct terra_tree_inst {int32_t type; float height, width;} terra_tree_inst;
+int  terra_set_tree_instances(terra_ctx *ctx, const terra_tree_inst *h_insts, uint32_t count);
+int  terra_get_tree_instances(terra_ctx *ctx, terra_tree_inst *h_insts, uint32_t capacity, uint32_t *count);
+enum {TERRA_TREE_AO_NO_PINE_PALM = 1, TERRA_TREE_AO_NO_DECID = 2, TERRA_TREE_AO_DISTANT = 4};
+int  terra_tiles_tree_ao_shadows_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                                     const terra_tree_place *d_pine, const uint32_t *d_pine_counts, uint32_t pine_capacity,
+                                     const terra_decid_place *d_decid, const uint32_t *d_decid_counts, uint32_t decid_capacity,
+                                     const float *d_decid_radius, const float *d_decid_radius_by_id, uint32_t num_radius_by_id, const uint8_t *d_flags,
+                                     uint32_t list_capacity, uint8_t *d_tree_map, uint8_t *d_updated, float *d_trmax, uint32_t *d_list_counts);
+int  terra_tiles_tree_ao_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                                 const terra_tree_place *h_pine, const uint32_t *h_pine_counts, uint32_t pine_capacity,
+                                 const terra_decid_place *h_decid, const uint32_t *h_decid_counts, uint32_t decid_capacity,
+                                 const float *h_decid_radius, const float *h_decid_radius_by_id, uint32_t num_radius_by_id, const uint8_t *h_flags,
+                                 uint32_t list_capacity, uint8_t *h_tree_map, uint8_t *h_updated, float *h_trmax, uint32_t *h_list_counts);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

@@ -292,6 +292,29 @@ inline void tiles_gen_scenery(tile_batch_dev_t const &b, int xoff2, int yoff2, u
 {
 	check(terra_tiles_place_scenery_dev(default_ctx(), b.tile_xy, b.n, xoff2, yoff2, d_no_scenery, capacity, d_objs, d_counts, d_kind_counts), "scenery_group::gen");
 }
+// tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:820-828) for every tile of the batch in batch order, from the records tiles_gen_trees / tiles_gen_decid_trees left
+// on the device: small_tree::get_radius / get_ao_radius and tree::get_ao_radius per record, apply_ao_shadows_for_trees' own loop, pulls and pushes, add_tree_ao_shadow's
+// texel loop.  xoff2 / yoff2: what the placements ran with (ptree_off / dtree_off).  d_sphere_radius [n][decid_capacity] (tdata().sphere_radius per record) or
+// d_sphere_radius_by_id [num_shared_trees]; d_flags[t]: TERRA_TREE_AO_* (or null).  d_trmax feeds get_bcube; d_updated sets sun / moon_shadows_invalid and
+// recalc_tree_grass_weights.  Globals: set_tree_size_params once, set_tree_instances after create_pine_tree_instances
+struct tile_trees_dev_t {
+	terra_tree_place const *d_pine_trees; unsigned const *d_pine_counts; unsigned pine_capacity;
+	terra_decid_place const *d_decid_trees; unsigned const *d_decid_counts; unsigned decid_capacity;
+	float const *d_sphere_radius, *d_sphere_radius_by_id; unsigned num_shared_trees;
+};
+inline void tiles_apply_tree_ao_shadows(tile_batch_dev_t const &b, int xoff2, int yoff2, tile_trees_dev_t const &tr, unsigned char const *d_flags, unsigned list_capacity,
+	unsigned char *d_tree_map, unsigned char *d_updated = nullptr, float *d_trmax = nullptr, unsigned *d_list_counts = nullptr)
+{
+	check(terra_tiles_tree_ao_shadows_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, tr.d_pine_trees, tr.d_pine_counts, tr.pine_capacity, tr.d_decid_trees,
+		tr.d_decid_counts, tr.decid_capacity, tr.d_sphere_radius, tr.d_sphere_radius_by_id, tr.num_shared_trees, d_flags, list_capacity, d_tree_map, d_updated, d_trmax,
+		d_list_counts), "apply_tree_ao_shadows");
+}
+inline void set_tree_size_params(float tree_height_scale, float sm_tree_scale, float pine_tree_radius_scale) {
+	terra_tree_size_params const p = {tree_height_scale, sm_tree_scale, pine_tree_radius_scale};
+	check(terra_set_tree_size_params(default_ctx(), &p), "set_tree_size_params");
+}
+// tree_instances after create_pine_tree_instances (src/sm_tree.cpp:342-364): {get_type(), get_height(), get_width()} of every instance, in order
+inline void set_tree_instances(terra_tree_inst const *insts, unsigned count) {check(terra_set_tree_instances(default_ctx(), insts, count), "create_pine_tree_instances");}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
