@@ -940,6 +940,63 @@ int terra_tiles_tree_ao_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_t
 		if (h_list_counts) {be.d2h(h_list_counts, d + ol, cb);}
 	TERRA_CATCH
 }
+int terra_tiles_edit_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                               const float pos[3], float radius, int32_t add_trees, int32_t is_square,
+                               const uint8_t *d_skip, const terra_tile_stats *d_stats, const float *d_zvals, const uint8_t *d_gen_flags,
+                               terra_tree_place *d_pine, uint32_t *d_pine_counts, uint32_t pine_capacity,
+                               terra_decid_place *d_decid, uint32_t *d_decid_counts, uint32_t decid_capacity,
+                               float *d_decid_radius, const float *d_decid_radius_by_id, uint32_t num_radius_by_id,
+                               float *d_trmax, uint8_t *d_status, uint8_t *d_changed, float *d_update_bcube) {
+	TERRA_CHECK_CTX if (!pos || (n && (!tile_xy || !d_stats || !d_trmax || !d_status || !d_changed))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_edit_trees_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, pos, radius, add_trees != 0, is_square != 0, d_skip, d_stats, d_zvals, d_gen_flags,
+		(terra::tree_place_pod_t *)d_pine, d_pine_counts, pine_capacity, (terra::decid_place_pod_t *)d_decid, d_decid_counts, decid_capacity, d_decid_radius,
+		d_decid_radius_by_id, num_radius_by_id, d_trmax, d_status, d_changed, d_update_bcube); TERRA_CATCH
+}
+int terra_tiles_edit_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                           const float pos[3], float radius, int32_t add_trees, int32_t is_square,
+                           const uint8_t *h_skip, const terra_tile_stats *h_stats, const float *h_zvals, const uint8_t *h_gen_flags,
+                           terra_tree_place *h_pine, uint32_t *h_pine_counts, uint32_t pine_capacity,
+                           terra_decid_place *h_decid, uint32_t *h_decid_counts, uint32_t decid_capacity,
+                           float *h_decid_radius, const float *h_decid_radius_by_id, uint32_t num_radius_by_id,
+                           float *h_trmax, uint8_t *h_status, uint8_t *h_changed, float *h_update_bcube) {
+	TERRA_CHECK_CTX if (!pos || (n && (!tile_xy || !h_stats || !h_trmax || !h_status || !h_changed))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size(); // (before the arrays are read: they are sized by S)
+		if (n == 0) return TERRA_OK;
+		bool const has_pine = h_pine_counts && pine_capacity, has_decid = h_decid_counts && decid_capacity;
+		if ((has_pine && !h_pine) || (has_decid && !h_decid)) return terra::fail(TERRA_ERR_ARG, "tiles_edit_trees: counts without records");
+		// the cheap refusals before anything is staged (the driver repeats them)
+		if (!std::isfinite(radius) || radius < 0.0f) return terra::fail(TERRA_ERR_ARG, "tiles_edit_trees: the radius must be finite and not negative");
+		if ((has_pine && (uint64_t)n*pine_capacity > 0xFFFFFFFFull) || (has_decid && (uint64_t)n*decid_capacity > 0xFFFFFFFFull)) return terra::fail(TERRA_ERR_ARG, "tiles_edit_trees: n*capacity must fit 32 bits");
+		auto &be = ctx->eng.be;
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		size_t const Z = (size_t)ctx->eng.tile_size() + 2;
+		size_t const pb = has_pine ? (size_t)n*pine_capacity*sizeof(terra_tree_place) : 0, db = has_decid ? (size_t)n*decid_capacity*sizeof(terra_decid_place) : 0,
+			rb = (has_decid && h_decid_radius) ? (size_t)n*decid_capacity*4 : 0, ib = (has_decid && h_decid_radius_by_id) ? (size_t)num_radius_by_id*4 : 0, cb = (size_t)n*4,
+			sb = (size_t)n*sizeof(terra_tile_stats), zb = h_zvals ? (size_t)n*Z*Z*sizeof(float) : 0;
+		size_t const op = 0, od = op + up(pb), orr = od + up(db), oi = orr + up(rb), opc = oi + up(ib), odc = opc + up(cb), os = odc + up(cb), oz = os + up(sb), ok = oz + up(zb),
+			og = ok + up(n), ot = og + up(n), ou = ot + up(cb), oc = ou + up(n), ob = oc + up(n);
+		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(ob + 256);
+		if (has_pine) {be.h2d(d + op, h_pine, pb); be.h2d(d + opc, h_pine_counts, cb);}
+		if (has_decid) {be.h2d(d + od, h_decid, db); be.h2d(d + odc, h_decid_counts, cb);}
+		if (rb) {be.h2d(d + orr, h_decid_radius, rb);}
+		if (ib) {be.h2d(d + oi, h_decid_radius_by_id, ib);}
+		be.h2d(d + os, h_stats, sb); be.h2d(d + ot, h_trmax, cb);
+		if (zb) {be.h2d(d + oz, h_zvals, zb);}
+		if (h_skip) {be.h2d(d + ok, h_skip, n);}
+		if (h_gen_flags) {be.h2d(d + og, h_gen_flags, n);}
+		ctx->eng.tiles_edit_trees_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, pos, radius, add_trees != 0, is_square != 0, h_skip ? d + ok : nullptr, (terra_tile_stats const *)(d + os),
+			zb ? (float const *)(d + oz) : nullptr, h_gen_flags ? d + og : nullptr, has_pine ? (terra::tree_place_pod_t *)(d + op) : nullptr, has_pine ? (uint32_t *)(d + opc) : nullptr,
+			pine_capacity, has_decid ? (terra::decid_place_pod_t *)(d + od) : nullptr, has_decid ? (uint32_t *)(d + odc) : nullptr, decid_capacity, rb ? (float *)(d + orr) : nullptr,
+			ib ? (float const *)(d + oi) : nullptr, num_radius_by_id, (float *)(d + ot), d + ou, d + oc, (float *)(d + ob));
+		if (has_pine) {be.d2h(h_pine, d + op, pb); be.d2h(h_pine_counts, d + opc, cb);}
+		if (has_decid) {be.d2h(h_decid, d + od, db); be.d2h(h_decid_counts, d + odc, cb);}
+		if (rb) {be.d2h(h_decid_radius, d + orr, rb);}
+		be.d2h(h_trmax, d + ot, cb); be.d2h(h_status, d + ou, n); be.d2h(h_changed, d + oc, n);
+		if (h_update_bcube) {be.d2h(h_update_bcube, d + ob, 24);}
+	TERRA_CATCH
+}
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !d_zvals || !d_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.tiles_ao_lighting_dev(tile_xy, n, d_zvals, d_ao); TERRA_CATCH

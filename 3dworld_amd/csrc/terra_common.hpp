@@ -43,6 +43,9 @@ enum {MGEN_SINE = 0, MGEN_SIMPLEX, MGEN_PERLIN, MGEN_SIMPLEX_GPU, MGEN_DWARP_GPU
 // std::min / std::max semantics (NaN-propagation exactly as "(b<a)?b:a" / "(a<b)?b:a"), NOT fminf/fmaxf
 TERRA_HD float min_std(float a, float b) {return (b < a) ? b : a;}
 TERRA_HD float max_std(float a, float b) {return (a < b) ? b : a;}
+// float <-> order-preserving uint (for atomic min/max of floats)
+TERRA_HD uint32_t f2ord(float f) {uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u);}
+TERRA_HD float ord2f(uint32_t o) {uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; float f; memcpy(&f, &u, 4); return f;}
 TERRA_HD int   imin(int a, int b) {return (b < a) ? b : a;}
 TERRA_HD int   imax(int a, int b) {return (a < b) ? b : a;}
 TERRA_HD float clip01(float x)  {return max_std(0.0f, min_std(1.0f, x));}    // CLIP_TO_01  src/3DWorld.h:148

@@ -17,6 +17,7 @@
 #include "terra_decidplace.hpp"
 #include "terra_sceneryplace.hpp"
 #include "terra_treeao.hpp"
+#include "terra_treeedit.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
@@ -48,10 +49,6 @@ struct grid_job_t { // one build_arrays() + eval loop
 constexpr unsigned VOX_SINES = 60, VOX_PARAMS = 7;
 
 inline uint32_t round_up(uint32_t v, uint32_t m) {return (v + m - 1)/m*m;}
-
-// float <-> order-preserving uint (for atomic min/max of floats)
-TERRA_HD uint32_t f2ord(float f) {uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u);}
-TERRA_HD float ord2f(uint32_t o) {uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; float f; memcpy(&f, &u, 4); return f;}
 
 // ---- "simple" (one logical thread per cell) bodies shared by the CPU emulator and the GPU cross-check kernels
 struct tile_ref_pod_t {int32_t tx, ty; uint32_t xi, yi;};
@@ -547,7 +544,7 @@ template<class BE> struct terra_engine {
 
 	// grow-only device scratch
 	struct scratch_t {void *p = nullptr; size_t bytes = 0;};
-	scratch_t s_xt, s_yt, s_smx, s_smy, s_misc, s_border, s_spec, s_spec_blocks, s_tiles, s_ao, s_shadow, s_shadow_map, s_shadow_gather, s_vox, s_sk, s_mm, s_hostgrid;
+	scratch_t s_xt, s_yt, s_smx, s_smy, s_misc, s_border, s_spec, s_spec_blocks, s_tiles, s_ao, s_edit, s_shadow, s_shadow_map, s_shadow_gather, s_vox, s_sk, s_mm, s_hostgrid;
 	bool tiled_mesh_ao = false; // enable_tiled_mesh_ao (src/3DWorld.cpp:73,1778)
 	uint8_t const *hmap_pix = nullptr; int hmap_w = 0, hmap_h = 0, hmap_nc = 0; // terrain_hmap_manager's image (device memory, owned by the caller)
 	float mesh_file_scale = 1.0f, mesh_file_tz = 0.0f;                          // src/mesh_gen.cpp:41, set by set_mesh_height_scales_for_zval_range
@@ -561,12 +558,12 @@ template<class BE> struct terra_engine {
 	// every grow-only device buffer of the context back to the allocator (they grow again on demand): the erosion ring of a 16384^2 map alone is ~8.5 GiB
 	void release_scratch() {
 		be.sync();
-		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {if (s->p) {be.free(s->p); s->p = nullptr; s->bytes = 0;}}
+		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {if (s->p) {be.free(s->p); s->p = nullptr; s->bytes = 0;}}
 		spec_blocks_clean = nullptr; spec_blocks_n = 0;
 		be.release_scratch();
 	}
 	~terra_engine() {
-		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {if (s->p) be.free(s->p);}
+		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {if (s->p) be.free(s->p);}
 		if (d_sin_table) be.free(d_sin_table);
 		if (d_noise_lut) be.free(d_noise_lut);
 		if (d_noise3_lut) be.free(d_noise3_lut);
@@ -2449,6 +2446,166 @@ template<class BE> struct terra_engine {
 			if (d_list_counts) {d_list_counts[t] = count;}
 		});
 		tree_map_rows_simple(d_tiles, n, S, nullptr, d_par, true, d_map, d_rowf, d_updated);
+	}
+	// ---- one stroke of the tree brush on the two record arrays of a batch, in place (terra_treeedit.hpp): tile_draw_t::add_or_remove_trees_at (src/tiled_mesh.cpp:
+	// 3746-3769) from :3756 on.  Three passes: per tile the culls and the removal loops of both groups (k_tree_edit); when adding, the two brush placements into the
+	// arena and the append behind the survivors (k_tree_edit_append); then status and changed of every tile against the batch's box (k_tree_edit_finish).  The box is
+	// reduced on the device with order-preserving uint atomics; nothing is read back.  Every refusal comes before the first launch.
+	void tiles_edit_trees_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, float const pos[3], float radius, bool add, bool is_square,
+		uint8_t const *d_skip, terra_tile_stats const *d_stats, float const *d_zvals, uint8_t const *d_gen_flags, tree_place_pod_t *d_pine, uint32_t *d_pine_counts,
+		uint32_t pine_cap, decid_place_pod_t *d_decid, uint32_t *d_decid_counts, uint32_t decid_cap, float *d_decid_radius, float const *d_decid_radius_by_id,
+		uint32_t num_radius_by_id, float *d_trmax, uint8_t *d_status, uint8_t *d_changed, float *d_update_bcube)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		if (!tile_xy || !d_stats || !d_trmax || !d_status || !d_changed) throw std::invalid_argument("tiles_edit_trees: null argument (tile_xy, stats, trmax, status, changed)");
+		if (!std::isfinite(radius) || radius < 0.0f) throw std::invalid_argument("tiles_edit_trees: the radius must be finite and not negative");
+		bool const has_pine = d_pine_counts != nullptr && pine_cap != 0, has_decid = d_decid_counts != nullptr && decid_cap != 0;
+		if (!has_pine) {d_pine_counts = nullptr; pine_cap = 0;}
+		if (!has_decid) {d_decid_counts = nullptr; decid_cap = 0; d_decid_radius = nullptr;}
+		if (has_pine && !d_pine) throw std::invalid_argument("tiles_edit_trees: pine counts without records");
+		if (has_decid && !d_decid) throw std::invalid_argument("tiles_edit_trees: deciduous counts without records");
+		if (has_decid && (!d_decid_radius || add)) { // (a new record's radius is known only through the table)
+			if (!d_decid_radius_by_id) {
+				throw std::invalid_argument(add ? "tiles_edit_trees: adding deciduous records needs decid_radius_by_id (sphere_radius stays with the engine)" :
+					"tiles_edit_trees: deciduous records need decid_radius or decid_radius_by_id (sphere_radius stays with the engine)");
+			}
+			if (dp.num_shared_trees == 0) throw std::invalid_argument("tiles_edit_trees: decid_radius_by_id with num_shared_trees == 0 (tree_id is -1)");
+			if (num_radius_by_id != dp.num_shared_trees) throw std::invalid_argument("tiles_edit_trees: decid_radius_by_id must hold num_shared_trees values");
+		}
+		else {d_decid_radius_by_id = nullptr;} // (no deciduous group, or the per-record form alone)
+		if (has_pine && tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
+			throw std::invalid_argument("tiles_edit_trees: instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
+		}
+		if ((((uintptr_t)d_pine | (uintptr_t)d_pine_counts | (uintptr_t)d_decid | (uintptr_t)d_decid_counts | (uintptr_t)d_decid_radius | (uintptr_t)d_decid_radius_by_id |
+		      (uintptr_t)d_trmax | (uintptr_t)d_stats | (uintptr_t)d_zvals | (uintptr_t)d_update_bcube) & 3u) != 0) {
+			throw std::invalid_argument("tiles_edit_trees: records, counts, radii, trmax, stats, zvals and update_bcube must be 4-byte aligned");
+		}
+		if ((uint64_t)n*pine_cap > 0xFFFFFFFFull || (uint64_t)n*decid_cap > 0xFFFFFFFFull) throw std::invalid_argument("tiles_edit_trees: n*capacity must fit 32 bits");
+		uint32_t const S = tile_size();
+		tree_edit_consts_t c;
+		c.a.hs = tsp.tree_height_scale*tsp.sm_tree_scale; c.a.pine_radius_scale = tsp.pine_tree_radius_scale; c.a.tree_scale = tp.tree_scale;
+		c.a.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale;
+		c.a.dxv = DX_VAL; c.a.dyv = DY_VAL; c.a.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; c.a.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // get_xlate() (src/animals.h:25)
+		c.a.S = (int)S; c.a.instanced = tp.instanced ? 1 : 0; c.a.num_insts = (uint32_t)tree_insts.size(); c.a.num_shared = dp.num_shared_trees;
+		c.a.pine_cap = pine_cap; c.a.decid_cap = decid_cap; c.a.list_cap = 0; c.a.src_cap = pine_cap + decid_cap;
+		c.px = pos[0]; c.py = pos[1]; c.pz = pos[2]; c.ptx = pos[0] - c.a.offx; c.pty = pos[1] - c.a.offy; c.rr = radius;
+		c.calc_radius = (float)(0.5*(double)sqrtf(DX_VAL*DX_VAL + DY_VAL*DY_VAL)*(double)S); // 0.5*sqrt(DX_VAL*DX_VAL + DY_VAL*DY_VAL)*size: float sqrt, double products
+		c.is_square = is_square ? 1 : 0; c.add = add ? 1 : 0;
+		// the placements' own refusals, before anything is launched
+		float const brush[4] = {c.ptx, c.pty, radius, is_square ? 1.0f : 0.0f};
+		bool const add_pine = add && has_pine, add_decid = add && has_decid;
+		if (add_pine) {tree_place_consts_t pc; std::vector<float> sums; tree_place_consts(xoff2, yoff2, brush, sums, pc);}
+		if (add_decid) {
+			if (!d_zvals) throw std::invalid_argument("tiles_edit_trees: adding deciduous records needs zvals (the slope test reads the tile's heights)");
+			decid_place_consts_t dc; decid_place_consts(xoff2, yoff2, brush, true, dc);
+		}
+		std::vector<tree_edit_frame_t> fr(n);
+		for (uint32_t t = 0; t < n; ++t) {
+			int const x1 = (int)((uint32_t)tile_xy[2*t]*S), y1 = (int)((uint32_t)tile_xy[2*t+1]*S), h = (int)(S >> 1); // ((x1 + x2) >> 1) = x1 + (S >> 1): x1 is a multiple of S
+			fr[t].x = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); fr[t].y = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
+			fr[t].cx = -cfg.scene_x + DX_VAL*(float)add_wrap(add_wrap(x1, h), dxoff); fr[t].cy = -cfg.scene_y + DY_VAL*(float)add_wrap(add_wrap(y1, h), dyoff);
+		}
+		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
+		uint32_t const idx_cap = std::max(pine_cap, decid_cap);
+		size_t const fb = up((size_t)n*sizeof(tree_edit_frame_t)), xb = up((size_t)n*idx_cap*4), cb = up((size_t)n*4),
+			npb = add_pine ? up((size_t)n*pine_cap*sizeof(tree_place_pod_t)) : 0, ndb = add_decid ? up((size_t)n*decid_cap*sizeof(decid_place_pod_t)) : 0;
+		uint8_t *base = scratch<uint8_t>(s_edit, fb + 256 + xb + 2*cb + npb + ndb + up(2*(size_t)n));
+		tree_edit_frame_t *d_fr_w = (tree_edit_frame_t *)base;
+		uint32_t *d_box = (uint32_t *)(base + fb);          // six words of the box, then two spare
+		uint32_t *d_idx = (uint32_t *)(base + fb + 256);    // [n][idx_cap]: the tail survivors of the group in hand
+		uint32_t *d_new_pc = (uint32_t *)(base + fb + 256 + xb), *d_new_dc = (uint32_t *)(base + fb + 256 + xb + cb);
+		tree_place_pod_t *d_new_pine = (tree_place_pod_t *)(base + fb + 256 + xb + 2*cb);
+		decid_place_pod_t *d_new_decid = (decid_place_pod_t *)(base + fb + 256 + xb + 2*cb + npb);
+		uint8_t *d_place_skip = (add_pine || add_decid) ? base + fb + 256 + xb + 2*cb + npb + ndb : nullptr; // [2][n], pine / palm first: skip, gated by gen_flags, or not hit -- what the brush placements run with
+		be.h2d_async(d_fr_w, fr.data(), (size_t)n*sizeof(tree_edit_frame_t));
+		tree_edit_frame_t const *d_fr = d_fr_w;
+		tree_inst_pod_t const *d_insts = (has_pine && tp.instanced) ? tree_insts_dev() : nullptr;
+		be.fill32(d_box, 0xFFFFFFFFu, 8);
+		float const *d_by_rec = d_decid_radius;                                   // a present record's radius: the per-record form wins
+		float const *d_by_id = d_decid_radius ? nullptr : d_decid_radius_by_id;
+		bool const kernels = be.tile_edit_trees(c, n, d_fr, d_stats, d_insts, d_pine, d_pine_counts, d_decid, d_decid_counts, d_decid_radius, d_by_id, d_trmax, d_idx, d_box, d_status,
+			d_skip, d_gen_flags, d_place_skip);
+		if (!kernels) { // the simple form: one logical thread per tile runs the reference's loops, remove_element and all
+			be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+				terra_tile_stats const &st = d_stats[t];
+				uint32_t state = tree_edit_cull(c, d_fr[t], st.mzmin, st.mzmax, st.radius, d_trmax[t]);
+				if (d_place_skip) {
+					uint32_t const sk = d_skip ? d_skip[t] : 0u, gf = d_gen_flags ? d_gen_flags[t] : 0u;
+					d_place_skip[t] = tree_edit_place_skip(state, sk, gf & TREE_EDIT_NO_PINE_GEN); d_place_skip[n + t] = tree_edit_place_skip(state, sk, gf & TREE_EDIT_NO_DECID_GEN);
+				}
+				if (state & TREE_EDIT_HIT) {
+					tree_box_t box;
+					tree_box_clear(box);
+					if (d_pine_counts) {
+						uint32_t const cnt = min_u32(d_pine_counts[t], c.a.pine_cap);
+						uint32_t const m = tree_edit_remove_serial(c, d_pine + t*c.a.pine_cap, (float *)nullptr, cnt, [&](tree_place_pod_t const &r, float const *) {tree_edit_box_pine(c, d_insts, r, box);});
+						if (m != cnt) {state |= TREE_EDIT_CHANGED;}
+						d_pine_counts[t] = m;
+					}
+					if (d_decid_counts) {
+						uint32_t const cnt = min_u32(d_decid_counts[t], c.a.decid_cap);
+						uint32_t const m = tree_edit_remove_serial(c, d_decid + t*c.a.decid_cap, d_by_rec ? d_decid_radius + t*c.a.decid_cap : nullptr, cnt,
+							[&](decid_place_pod_t const &r, float const *rad) {tree_edit_box_decid(c, r, rad, d_by_id, box);});
+						if (m != cnt) {state |= TREE_EDIT_CHANGED;}
+						d_decid_counts[t] = m;
+					}
+					tree_box_commit(box, d_box);
+				}
+				d_status[t] = (uint8_t)state;
+			});
+		}
+		if (add_pine) {tiles_place_trees_dev(tile_xy, n, xoff2, yoff2, d_place_skip, d_stats, brush, pine_cap, d_new_pine, d_new_pc);}
+		if (add_decid) {tiles_place_decid_trees_dev(tile_xy, n, xoff2, yoff2, d_place_skip + n, d_stats, d_zvals, brush, decid_cap, d_new_decid, d_new_dc);}
+		if (add_pine || add_decid) {
+			tree_place_pod_t const *np_ = add_pine ? d_new_pine : nullptr; decid_place_pod_t const *nd_ = add_decid ? d_new_decid : nullptr;
+			if (!(kernels && be.tile_edit_trees_append(c, n, d_gen_flags, d_insts, np_, d_new_pc, d_pine, d_pine_counts, nd_, d_new_dc, d_decid, d_decid_counts, d_decid_radius,
+				d_decid_radius_by_id, d_trmax, d_box, d_status)))
+			{
+				be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+					uint32_t state = d_status[t];
+					if (!(state & TREE_EDIT_HIT)) return;
+					uint32_t const gf = d_gen_flags ? d_gen_flags[t] : 0u;
+					tree_box_t box;
+					tree_box_clear(box);
+					float trmax = d_trmax[t];
+					if (np_ && !(gf & TREE_EDIT_NO_PINE_GEN)) {
+						uint32_t const m = d_pine_counts[t], nn = d_new_pc[t];
+						for (uint32_t j = 0; j < min_u32(nn, c.a.pine_cap) && m + j < c.a.pine_cap; ++j) {
+							tree_place_pod_t const r = np_[t*c.a.pine_cap + j];
+							d_pine[t*c.a.pine_cap + m + j] = r;
+							trmax = max_std(trmax, tree_edit_box_pine(c, d_insts, r, box));
+						}
+						d_pine_counts[t] = m + nn;
+						if (nn) {state |= TREE_EDIT_CHANGED;}
+					}
+					if (nd_ && !(gf & TREE_EDIT_NO_DECID_GEN)) {
+						uint32_t const m = d_decid_counts[t], nn = d_new_dc[t];
+						for (uint32_t j = 0; j < min_u32(nn, c.a.decid_cap) && m + j < c.a.decid_cap; ++j) {
+							decid_place_pod_t const r = nd_[t*c.a.decid_cap + j];
+							float const rad = tree_edit_new_decid_radius(c, r, d_decid_radius_by_id);
+							d_decid[t*c.a.decid_cap + m + j] = r;
+							if (d_decid_radius) {d_decid_radius[t*c.a.decid_cap + m + j] = rad;}
+							trmax = max_std(trmax, tree_edit_box_decid(c, r, &rad, nullptr, box));
+						}
+						d_decid_counts[t] = m + nn;
+						if (nn) {state |= TREE_EDIT_CHANGED;}
+					}
+					d_trmax[t] = trmax;
+					tree_box_commit(box, d_box);
+					d_status[t] = (uint8_t)state;
+				});
+			}
+		}
+		if (kernels && be.tile_edit_trees_finish(c, n, d_fr, d_stats, d_box, d_status, d_changed, d_update_bcube)) return;
+		uint32_t const *d_box_r = d_box;
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			terra_tile_stats const &st = d_stats[t];
+			uint8_t status, changed;
+			tree_edit_finish(c, d_fr[t], st.mzmin, st.mzmax, d_status[t], d_box_r, status, changed, (t == 0) ? d_update_bcube : nullptr);
+			d_status[t] = status; d_changed[t] = changed;
+		});
 	}
 	// tile_t::upload_shadow_map_texture (:885-911) for n tiles: smask [n][S+2][S+2] per light (read only where the lights that are up need it), ao [n][S+1][S+1] or
 	// null (170), tree map or null (empty) -> [n][S+1][S+1] RGBA8 {mesh shadow, tree shadow, ambient occlusion, 0}

@@ -592,6 +592,39 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// the tree brush on the record arrays: k_tree_edit once per tile (culls and removal), k_tree_edit_append once per tile after the brush placements, k_tree_edit_finish
+	// once per tile for status and changed
+	bool tile_edit_trees(terra::tree_edit_consts_t const &c, uint32_t n, terra::tree_edit_frame_t const *frames, terra_tile_stats const *stats, terra::tree_inst_pod_t const *insts,
+		terra::tree_place_pod_t *pine, uint32_t *pine_counts, terra::decid_place_pod_t *decid, uint32_t *decid_counts, float *decid_radius, float const *by_id, float const *trmax,
+		uint32_t *idx, uint32_t *box, uint8_t *status, uint8_t const *skip, uint8_t const *gen_flags, uint8_t *place_skip)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_tree_edit, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, frames, stats, insts, pine, pine_counts, decid, decid_counts, decid_radius, by_id,
+			trmax, idx, box, status, skip, gen_flags, place_skip);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
+	bool tile_edit_trees_append(terra::tree_edit_consts_t const &c, uint32_t n, uint8_t const *gen_flags, terra::tree_inst_pod_t const *insts, terra::tree_place_pod_t const *new_pine,
+		uint32_t const *new_pine_counts, terra::tree_place_pod_t *pine, uint32_t *pine_counts, terra::decid_place_pod_t const *new_decid, uint32_t const *new_decid_counts,
+		terra::decid_place_pod_t *decid, uint32_t *decid_counts, float *decid_radius, float const *by_id, float *trmax, uint32_t *box, uint8_t *status)
+	{
+		if (simple_kernels) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_tree_edit_append, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, gen_flags, insts, new_pine, new_pine_counts, pine, pine_counts, new_decid,
+			new_decid_counts, decid, decid_counts, decid_radius, by_id, trmax, box, status);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
+	bool tile_edit_trees_finish(terra::tree_edit_consts_t const &c, uint32_t n, terra::tree_edit_frame_t const *frames, terra_tile_stats const *stats, uint32_t const *box,
+		uint8_t *status, uint8_t *changed, float *update_bcube)
+	{
+		if (simple_kernels) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_tree_edit_finish, dim3((n + 255)/256), dim3(256), 0, stream, c, n, frames, stats, box, status, changed, update_bcube);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	// tree placement: one workgroup per tile (k_tree_place)
 	bool tile_place_trees(terra::tree_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
 		uint32_t capacity, terra::tree_place_pod_t *trees, uint32_t *counts)

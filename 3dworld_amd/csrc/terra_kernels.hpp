@@ -1822,6 +1822,143 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_tree_ao_gather(tree_ao_consts
 	}
 }
 
+// ------------------------------------------------------------------ the tree brush on the record arrays of a batch (tile_draw_t::add_or_remove_trees_at,
+// src/tiled_mesh.cpp:3746-3843; terra_treeedit.hpp), three launches: k_tree_edit, k_tree_edit_append (only when adding, after the two brush placements), k_tree_edit_finish.
+// The removal loop of one group by the workgroup.  remove_element swaps the back into the hole and tests the same index again, so the result is not in input order; its
+// closed form: with M survivors among the cnt records, a survivor below M stays, and the holes below M, ascending, receive the survivors at M and above, descending
+// (tests/test_tree_edit_emul.py checks this against the literal loop).  Three sweeps of 256 records: (1) M and the removed records' box, (2) the survivors at M and
+// above into idx[] in ascending order, (3) the k-th hole below M takes record idx[H - 1 - k].  Sources lie at M and above, destinations below: in place after a barrier.
+template<class REC, class BOX> __device__ __forceinline__ uint32_t te_remove_group(tree_edit_consts_t const &c, REC *v, float *radius, uint32_t cnt, uint32_t *idx, uint32_t *s_wave, BOX box_of) {
+	uint32_t const tid = threadIdx.x;
+	uint32_t m = 0, nk;
+	for (uint32_t base = 0; base < cnt; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		bool keep = false;
+		if (i < cnt) {
+			keep = !tree_edit_removed(c, v[i].pos[0], v[i].pos[1]);
+			if (!keep) {box_of(v[i], radius ? radius + i : nullptr);}
+		}
+		tp_block_rank(keep, s_wave, nk);
+		m += nk;
+	}
+	if (m == cnt) return m;
+	uint32_t h = 0;
+	for (uint32_t base = m; base < cnt; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		bool const keep = i < cnt && !tree_edit_removed(c, v[i].pos[0], v[i].pos[1]);
+		uint32_t const rank = tp_block_rank(keep, s_wave, nk);
+		if (keep) {idx[h + rank] = i;}
+		h += nk;
+	}
+	__syncthreads(); // idx[] is complete
+	uint32_t k0 = 0;
+	for (uint32_t base = 0; base < m; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		bool const hole = i < m && tree_edit_removed(c, v[i].pos[0], v[i].pos[1]);
+		uint32_t const rank = tp_block_rank(hole, s_wave, nk);
+		if (hole) {
+			uint32_t const src = idx[h - 1u - (k0 + rank)];
+			v[i] = v[src];
+			if (radius) {radius[i] = radius[src];}
+		}
+		k0 += nk;
+	}
+	return m;
+}
+// the threads' boxes -> one per wave (xor butterfly), then the six atomics of tree_box_commit from lane 0
+__device__ __forceinline__ void te_box_commit_wave(tree_box_t b, uint32_t *box) {
+	for (int m = 32; m > 0; m >>= 1) {
+		for (int i = 0; i < 3; ++i) {b.lo[i] = min_std(b.lo[i], __shfl_xor(b.lo[i], m)); b.hi[i] = max_std(b.hi[i], __shfl_xor(b.hi[i], m));}
+	}
+	if ((threadIdx.x & 63u) == 0) {tree_box_commit(b, box);}
+}
+// k_tree_edit: a workgroup per tile.  The two culls are one wave-uniform test on the tile's frame, stats and trmax: a brush touches a handful of the tiles of a batch and
+// every other workgroup ends there.  A tile that is hit runs the removal of both groups and leaves M in its counts and its state in `status`.
+__global__ __launch_bounds__(TREEP_THREADS) void k_tree_edit(tree_edit_consts_t c, tree_edit_frame_t const *__restrict__ frames, terra_tile_stats const *__restrict__ stats,
+	tree_inst_pod_t const *__restrict__ insts, tree_place_pod_t *pine, uint32_t *pine_counts, decid_place_pod_t *decid, uint32_t *decid_counts, float *decid_radius,
+	float const *__restrict__ by_id, float const *__restrict__ trmax, uint32_t *idx, uint32_t *box, uint8_t *status, uint8_t const *__restrict__ skip, uint8_t const *__restrict__ gen_flags, uint8_t *__restrict__ place_skip)
+{
+	__shared__ uint32_t s_wave[TREEP_THREADS/64];
+	uint32_t const t = blockIdx.x, tid = threadIdx.x;
+	uint32_t state = tree_edit_cull(c, frames[t], stats[t].mzmin, stats[t].mzmax, stats[t].radius, trmax[t]);
+	if (tid == 0 && place_skip) { // (adding: the brush placements leave at once every tile that is not hit and every group that is gated)
+		uint32_t const sk = skip ? skip[t] : 0u, gf = gen_flags ? gen_flags[t] : 0u;
+		place_skip[t] = tree_edit_place_skip(state, sk, gf & TREE_EDIT_NO_PINE_GEN); place_skip[gridDim.x + t] = tree_edit_place_skip(state, sk, gf & TREE_EDIT_NO_DECID_GEN);
+	}
+	if (!(state & TREE_EDIT_HIT)) {if (tid == 0) {status[t] = (uint8_t)state;} return;}
+	tree_box_t b;
+	tree_box_clear(b);
+	uint32_t const idx_cap = (c.a.pine_cap < c.a.decid_cap) ? c.a.decid_cap : c.a.pine_cap;
+	uint32_t *const my_idx = idx + (size_t)t*idx_cap;
+	if (pine_counts) {
+		uint32_t const cnt = min_u32(pine_counts[t], c.a.pine_cap);
+		uint32_t const m = te_remove_group(c, pine + (size_t)t*c.a.pine_cap, (float *)nullptr, cnt, my_idx, s_wave,
+			[&](tree_place_pod_t const &r, float const *) {tree_edit_box_pine(c, insts, r, b);});
+		if (m != cnt) {state |= TREE_EDIT_CHANGED;}
+		__syncthreads(); // every thread has read the count
+		if (tid == 0) {pine_counts[t] = m;}
+	}
+	if (decid_counts) {
+		uint32_t const cnt = min_u32(decid_counts[t], c.a.decid_cap);
+		uint32_t const m = te_remove_group(c, decid + (size_t)t*c.a.decid_cap, decid_radius ? decid_radius + (size_t)t*c.a.decid_cap : nullptr, cnt, my_idx, s_wave,
+			[&](decid_place_pod_t const &r, float const *rad) {tree_edit_box_decid(c, r, rad, by_id, b);});
+		if (m != cnt) {state |= TREE_EDIT_CHANGED;}
+		__syncthreads();
+		if (tid == 0) {decid_counts[t] = m;}
+	}
+	te_box_commit_wave(b, box);
+	if (tid == 0) {status[t] = (uint8_t)state;}
+}
+// k_tree_edit_append: a workgroup per tile; only the tiles k_tree_edit found hit do anything.  The records the brush placements left in the arena go behind the M
+// survivors as far as the array has room, counts[t] = M + all of them; the stored records raise trmax[t] (an atomic max on the bits of a positive float) and widen the box.
+__global__ __launch_bounds__(TREEP_THREADS) void k_tree_edit_append(tree_edit_consts_t c, uint8_t const *__restrict__ gen_flags, tree_inst_pod_t const *__restrict__ insts,
+	tree_place_pod_t const *__restrict__ new_pine, uint32_t const *__restrict__ new_pine_counts, tree_place_pod_t *pine, uint32_t *pine_counts,
+	decid_place_pod_t const *__restrict__ new_decid, uint32_t const *__restrict__ new_decid_counts, decid_place_pod_t *decid, uint32_t *decid_counts, float *decid_radius,
+	float const *__restrict__ by_id, float *trmax, uint32_t *box, uint8_t *status)
+{
+	uint32_t const t = blockIdx.x, tid = threadIdx.x;
+	uint32_t state = status[t];
+	if (!(state & TREE_EDIT_HIT)) return;
+	uint32_t const gf = gen_flags ? gen_flags[t] : 0u;
+	bool const do_pine = new_pine && !(gf & TREE_EDIT_NO_PINE_GEN), do_decid = new_decid && !(gf & TREE_EDIT_NO_DECID_GEN);
+	uint32_t const mp = do_pine ? pine_counts[t] : 0u, np = do_pine ? new_pine_counts[t] : 0u, md = do_decid ? decid_counts[t] : 0u, nd = do_decid ? new_decid_counts[t] : 0u;
+	__syncthreads(); // every thread has read the state and the counts
+	tree_box_t b;
+	tree_box_clear(b);
+	float rmax = 0.0f;
+	uint32_t const sp = min_u32(np, c.a.pine_cap - min_u32(mp, c.a.pine_cap)), sd = min_u32(nd, c.a.decid_cap - min_u32(md, c.a.decid_cap)); // how many are stored
+	for (uint32_t j = tid; j < sp; j += TREEP_THREADS) {
+		tree_place_pod_t const r = new_pine[(size_t)t*c.a.pine_cap + j];
+		pine[(size_t)t*c.a.pine_cap + mp + j] = r;
+		rmax = max_std(rmax, tree_edit_box_pine(c, insts, r, b));
+	}
+	for (uint32_t j = tid; j < sd; j += TREEP_THREADS) {
+		decid_place_pod_t const r = new_decid[(size_t)t*c.a.decid_cap + j];
+		float const rad = tree_edit_new_decid_radius(c, r, by_id);
+		decid[(size_t)t*c.a.decid_cap + md + j] = r;
+		if (decid_radius) {decid_radius[(size_t)t*c.a.decid_cap + md + j] = rad;}
+		rmax = max_std(rmax, tree_edit_box_decid(c, r, &rad, nullptr, b));
+	}
+	te_box_commit_wave(b, box);
+	for (int m = 32; m > 0; m >>= 1) {rmax = max_std(rmax, __shfl_xor(rmax, m));}
+	if ((tid & 63u) == 0 && rmax > 0.0f) {atomicMax((unsigned int *)(trmax + t), __float_as_uint(rmax));}
+	if (tid == 0) {
+		if (do_pine) {pine_counts[t] = mp + np;}
+		if (do_decid) {decid_counts[t] = md + nd;}
+		if (np | nd) {status[t] = (uint8_t)(state | TREE_EDIT_CHANGED);}
+	}
+}
+// k_tree_edit_finish: a thread per tile, after the box is complete: the state byte becomes the status, changed follows from it and from the box
+__global__ __launch_bounds__(256) void k_tree_edit_finish(tree_edit_consts_t c, uint32_t n, tree_edit_frame_t const *__restrict__ frames, terra_tile_stats const *__restrict__ stats,
+	uint32_t const *__restrict__ box, uint8_t *status, uint8_t *__restrict__ changed, float *__restrict__ update_bcube)
+{
+	uint32_t const t = blockIdx.x*256u + threadIdx.x;
+	if (t >= n) return;
+	uint8_t st, ch;
+	tree_edit_finish(c, frames[t], stats[t].mzmin, stats[t].mzmax, status[t], box, st, ch, (t == 0) ? update_bcube : nullptr);
+	status[t] = st; changed[t] = ch;
+}
+
 // ------------------------------------------------------------------ K10: 16-bit quantise (heightmap_t::from_floats + write_pixel_16_bits, src/heightmap.cpp:205-215, src/Textures.cpp:1889-1893)
 // HBM-bound, 4 B read + 2 B written per cell: eight cells per thread = two 16-byte loads and one 16-byte store of {fraction, integer} byte pairs
 __device__ __forceinline__ uint32_t q16_pair(float z, float val_add, float val_div) {

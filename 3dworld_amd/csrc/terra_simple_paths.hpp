@@ -168,6 +168,12 @@ template<class DERIVED> struct simple_paths {
 	bool tile_tree_ao(tree_ao_consts_t const &, uint32_t, tree_inst_pod_t const *, tree_place_pod_t const *, uint32_t const *, decid_place_pod_t const *, uint32_t const *,
 		float const *, float const *, uint8_t const *, tree_frame_t const *, int32_t const *, tree_splat_in_t *, float *, tree_tile_pod_t *, tree_splat_pod_t *, uint32_t *,
 		uint16_t *, uint8_t *) {return false;}
+	// the tree brush's kernels: none here -- the driver (tiles_edit_trees_dev) then runs its one-thread-per-tile forms, the removal as the literal remove_element loop
+	bool tile_edit_trees(tree_edit_consts_t const &, uint32_t, tree_edit_frame_t const *, terra_tile_stats const *, tree_inst_pod_t const *, tree_place_pod_t *, uint32_t *,
+		decid_place_pod_t *, uint32_t *, float *, float const *, float const *, uint32_t *, uint32_t *, uint8_t *, uint8_t const *, uint8_t const *, uint8_t *) {return false;}
+	bool tile_edit_trees_append(tree_edit_consts_t const &, uint32_t, uint8_t const *, tree_inst_pod_t const *, tree_place_pod_t const *, uint32_t const *, tree_place_pod_t *,
+		uint32_t *, decid_place_pod_t const *, uint32_t const *, decid_place_pod_t *, uint32_t *, float *, float const *, float *, uint32_t *, uint8_t *) {return false;}
+	bool tile_edit_trees_finish(tree_edit_consts_t const &, uint32_t, tree_edit_frame_t const *, terra_tile_stats const *, uint32_t const *, uint8_t *, uint8_t *, float *) {return false;}
 	// tree placement's kernel: none here -- the driver (tiles_place_trees_dev) then runs its one-thread-per-tile form
 	bool tile_place_trees(tree_place_consts_t const *, tile_ref_pod_t const *, uint32_t, float const *, uint8_t const *, terra_tile_stats const *, uint32_t, tree_place_pod_t *, uint32_t *) {return false;}
 	// deciduous placement's kernel: none here -- the driver (tiles_place_decid_trees_dev) then runs its one-thread-per-tile form

@@ -107,6 +107,7 @@ def make_scenery_params(use_voxel_rocks=2):
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
+TREE_EDIT_PINE_NOT_GENERATED, TREE_EDIT_DECID_NOT_GENERATED = 1, 2  # the per-tile gen_flags byte of tiles_edit_trees
 
 
 class TreeSizeParams(C.Structure):  # terra_tree_size_params
@@ -282,6 +283,8 @@ _PROTOS = {
     "terra_get_tree_instances": (_i32, [_vp, _vp, _u32, _vp]),
     "terra_tiles_tree_ao_shadows_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_tree_ao_shadows": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "terra_tiles_edit_trees_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _f3, _f, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "terra_tiles_edit_trees": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _f3, _f, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_set_scenery_params": (_i32, [_vp, _vp]),
     "terra_get_scenery_params": (_i32, [_vp, _vp]),
     "terra_tiles_place_scenery_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
@@ -888,6 +891,28 @@ class Terra:
                                                       list_capacity, tree_map.ctypes.data, upd.ctypes.data, trmax.ctypes.data, lc.ctypes.data))
         return tree_map, upd.astype(bool), trmax, lc
 
+    def tiles_edit_trees(self, tile_xy, stats, pos, radius, add_trees, is_square, trmax, pine=None, pine_counts=None, decid=None, decid_counts=None, decid_radius=None,
+                         decid_radius_by_id=None, skip=None, zvals=None, gen_flags=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):
+        """tile_draw_t::add_or_remove_trees_at on host arrays: pine (TREE_PLACE_DTYPE [n, cap]), pine_counts, decid (DECID_PLACE_DTYPE [n, cap]), decid_counts,
+        decid_radius [n, cap] and trmax [n] are edited IN PLACE (they must be C-contiguous arrays of their dtype); stats: the TileStats array of tiles_create_zvals.
+        -> (status u8 [n], changed bool [n], update_bcube float32 [6] = x1 x2 y1 y2 z1 z2)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        for a, dt in ((pine, TREE_PLACE_DTYPE), (pine_counts, np.uint32), (decid, DECID_PLACE_DTYPE), (decid_counts, np.uint32), (decid_radius, np.float32), (trmax, np.float32)):
+            assert a is None or (a.flags["C_CONTIGUOUS"] and a.dtype == dt)
+        assert decid_radius is None or (decid is not None and decid_radius.shape == decid.shape)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        gf = None if gen_flags is None else np.ascontiguousarray(gen_flags, np.uint8).reshape(n)
+        z = None if zvals is None else np.ascontiguousarray(zvals, np.float32)
+        ri = None if decid_radius_by_id is None else np.ascontiguousarray(decid_radius_by_id, np.float32).reshape(-1)
+        status, changed, box = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(6, np.float32)
+        self._ck(self.lib.terra_tiles_edit_trees(self.ctx, txy.ctypes.data, n, dxoff, dyoff, xoff2, yoff2, (C.c_float * 3)(*pos), radius, int(bool(add_trees)), int(bool(is_square)),
+                                                 ptr(sk), C.addressof(stats), ptr(z), ptr(gf), ptr(pine), ptr(pine_counts), 0 if pine is None else pine.shape[1],
+                                                 ptr(decid), ptr(decid_counts), 0 if decid is None else decid.shape[1], ptr(decid_radius), ptr(ri), 0 if ri is None else len(ri),
+                                                 trmax.ctypes.data, status.ctypes.data, changed.ctypes.data, box.ctypes.data))
+        return status, changed.astype(bool), box
+
     def tiles_ao_lighting(self, tile_xy, zvals):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         n = len(txy)
@@ -1076,6 +1101,17 @@ class Terra:
         self._ck(self.lib.terra_tiles_tree_ao_shadows_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, pine_ptr, pine_counts_ptr, pine_capacity,
                                                           decid_ptr, decid_counts_ptr, decid_capacity, decid_radius_ptr, decid_radius_by_id_ptr, num_radius_by_id,
                                                           flags_ptr, list_capacity, tree_map_ptr, updated_ptr, trmax_ptr, list_counts_ptr))
+
+    def tiles_edit_trees_dev(self, tile_xy, stats_ptr, pos, radius, add_trees, is_square, trmax_ptr, status_ptr, changed_ptr, pine_ptr=None, pine_counts_ptr=None,
+                             pine_capacity=0, decid_ptr=None, decid_counts_ptr=None, decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0,
+                             skip_ptr=None, z_ptr=None, gen_flags_ptr=None, update_bcube_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):
+        """the tree brush on the device-resident records of a batch, in place: trmax_ptr n floats (in / out), status_ptr / changed_ptr n bytes, update_bcube_ptr 6 floats
+        (or None).  Only enqueues; nothing is read back."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_edit_trees_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, (C.c_float * 3)(*pos), radius, int(bool(add_trees)),
+                                                     int(bool(is_square)), skip_ptr, stats_ptr, z_ptr, gen_flags_ptr, pine_ptr, pine_counts_ptr, pine_capacity, decid_ptr,
+                                                     decid_counts_ptr, decid_capacity, decid_radius_ptr, decid_radius_by_id_ptr, num_radius_by_id, trmax_ptr, status_ptr,
+                                                     changed_ptr, update_bcube_ptr))
 
     def tiles_ao_lighting_dev(self, tile_xy, z_ptr, ao_ptr):
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)

@@ -587,7 +587,7 @@ int  terra_tiles_place_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 /* terra_tiles_place_trees_brush: gen_trees_tt_within_radius (:477-502) as tile_t::add_new_trees (src/tiled_mesh.cpp:3805-3811) calls it, xoff2 / yoff2 = -toff.dxoff /
  * -toff.dyoff: the same cell with ntrees_mult without vegetation, no density field, one discarded rand_float, zpos always from get_exact_zval, and the fabs /
  * dist_xy_less_than test of the cell's centre against pos (x and y are read) and radius; is_square = (brush_shape == BSHAPE_CONST_SQ).  The caller keeps the
- * mesh_sphere_intersect culls and the removal loop (:3822-3838).  skip / stats: can_have_pine_palm_trees() as above.  Zero trees: sm_tree_density == 0 or bit 2
+ * mesh_sphere_intersect culls and the removal loop (:3822-3838); terra_tiles_edit_trees, below, runs both and this call on resident records.  skip / stats: can_have_pine_palm_trees() as above.  Zero trees: sm_tree_density == 0 or bit 2
  * of tree_mode clear.  Refusals as above, the bound on ntrees taken at ntrees_mult itself. */
 int  terra_tiles_place_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
                                        const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_tree_place *d_trees, uint32_t *d_counts);
@@ -651,7 +651,7 @@ int  terra_tiles_place_decid_trees(terra_ctx *ctx, const int32_t *tile_xy, uint3
 /* terra_tiles_place_decid_trees_brush: the same function as tile_t::add_new_trees calls it (xoff2 / yoff2 = -toff.dxoff / -toff.dyoff): vegetation_ = 1, no coverage
  * field, and the fabs / dist_xy_less_than test of the cell's get_xval / get_yval against pos (x and y are read) and radius (:2256-2264).  A radius of 0 or less means
  * the whole tile.  is_square is accepted as the reference accepts it: this function never reads it (a square brush places deciduous trees within the circle).
- * The caller keeps the mesh_sphere_intersect culls and the removal loop (:3822-3838). */
+ * The caller keeps the mesh_sphere_intersect culls and the removal loop (:3822-3838); terra_tiles_edit_trees, below, runs both and this call on resident records. */
 int  terra_tiles_place_decid_trees_brush_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
                                              const float *d_zvals, const float pos[3], float radius, int32_t is_square, uint32_t capacity, terra_decid_place *d_trees, uint32_t *d_counts);
 int  terra_tiles_place_decid_trees_brush(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, const terra_tile_stats *h_stats,
@@ -774,6 +774,73 @@ int  terra_tiles_tree_ao_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_
                                  const terra_decid_place *h_decid, const uint32_t *h_decid_counts, uint32_t decid_capacity,
                                  const float *h_decid_radius, const float *h_decid_radius_by_id, uint32_t num_radius_by_id, const uint8_t *h_flags,
                                  uint32_t list_capacity, uint8_t *h_tree_map, uint8_t *h_updated, float *h_trmax, uint32_t *h_list_counts);
+
+/* ---- tree brush on the resident records of a tile batch (every supported tile size S): the fire modes "Add Trees" / "Remove Trees" -> tile_draw_t::add_or_remove_trees_at
+ * (src/tiled_mesh.cpp:3746-3769) from :3756 on -> tile_t::add_or_remove_trees_at (:3822-3843) on every tile of the batch, with remove_tree (:3779-3787), remove_element
+ * (src/inlines.h:743-747), update_trees_bcube (:3776-3778), tile_t::add_new_trees (:3805-3819), tile_t::mesh_sphere_intersect (:3796-3799) and the register_tree_change
+ * decision of :3766-3768.  One call edits the pine / palm and the deciduous record arrays of the batch in place, bit for bit as the reference leaves its two vectors; with
+ * terra_tiles_tree_ao_shadows before and after it a stroke is one stream of launches on resident data.
+ * Inputs.  dxoff / dyoff: the tiles' mesh_off (xoff - xoff2), as for terra_tiles_tree_map.  xoff2 / yoff2: what the placements ran with; pine_xlate = decid_xlate =
+ * ((dxoff + xoff2)*DX_VAL, (dyoff + yoff2)*DY_VAL, 0), an int sum times a float (tile_offset_t::get_xlate, src/animals.h:25), the same value as the tree AO call's
+ * pt_off.  pos: camera space, as the reference receives it; pt_pos = dt_pos = pos - xlate.  radius: rradius.  is_square = (brush_shape == BSHAPE_CONST_SQ).
+ * stats (required): mzmin, mzmax and radius are read.  skip, zvals: what they mean for the two brush placement calls; read only when add_trees is set (zvals is then
+ * required for a deciduous group).  gen_flags (optional): [n] bytes, bit 0 = pine_trees_generated() is false, bit 1 = decid_trees.was_generated() is false.
+ * pine / pine_counts / pine_capacity, decid / decid_counts / decid_capacity, decid_radius, decid_radius_by_id: as for terra_tiles_tree_ao_shadows, but written: a group
+ * is absent when its counts are NULL or its capacity 0; a count above its capacity means the first `capacity` records.  trmax: [n], in and out.
+ * Per tile, in the reference's order:
+ *  1. The culls (:3824-3825).  mesh_sphere_intersect(pos, r) = dist_less_than(pos, get_center(), radius_t + r) && sphere_cube_intersect(pos, r, get_mesh_bcube())
+ *     (src/tiled_mesh.h:229-241, BCUBE_ZTOLER 1e-6; DMIN_CHECK of src/Math3d.cpp:920-935 with its early return per axis) with radius_t = max(stats.radius,
+ *     calc_radius() + trmax[t]): what postproc_trees (src/tiled_mesh.h:342-347) leaves, because trmax only grows; calc_radius() = 0.5*sqrt(DX_VAL*DX_VAL +
+ *     DY_VAL*DY_VAL)*size, a float sqrt and double products (:204).  r = 1.1*rradius + 2.0*trmax[t] (a double expression narrowed at the call) fails: status 0.
+ *     r = rradius fails: status 1.
+ *  2. The removal loops (:3832-3833), pine / palm first.  A record stays when fabs(tpos.x - pos.x) > rradius || fabs(tpos.y - pos.y) > rradius, or when the brush is
+ *     not square and dist_xy_less_than(tpos, pos, rradius) fails.  Removal is remove_element: the back is swapped in and the same index is tested again, so the
+ *     survivors do NOT keep their order.  The resulting order: with M survivors among the first min(count, capacity) records, a survivor at an index below M stays
+ *     where it is, and the holes below M, in ascending order, receive the survivors at indices >= M in descending order.  decid_radius, when given, moves with its
+ *     records.  Every removed record adds the sphere (tpos + xlate, 2.0*get_radius()) to the update box, get_radius() as terra_tiles_tree_ao_shadows forms it (the
+ *     per-record radius wins over decid_radius_by_id[tree_id]); a record that call would drop (bad type, instance, tree_id or radius) is removed by its position
+ *     like any other and adds nothing to the box.  Records past the new count keep whatever the moves left there.
+ *  3. The addition (:3835-3838), only when add_trees.  A group is extended when it is present, its gen_flags bit is clear and can_have_pine_palm_trees() /
+ *     can_have_decid_trees() holds (skip and the zrange test of the brush placement calls).  The records terra_tiles_place_trees_brush makes for (pt_pos, rradius,
+ *     is_square), in that call's order, are appended behind the M survivors; the same for terra_tiles_place_decid_trees_brush (which, like the reference, places over
+ *     the whole tile at rradius == 0 and never reads is_square).  counts[t] = M + all new records; the array receives those that fit, and a count above the capacity
+ *     keeps its meaning.  The appended records that are stored add their spheres to the update box (:3815-3817) and raise trmax[t] = max(trmax[t], get_radius())
+ *     (postproc_trees).  This is exact as long as trmax[t] on input is at least the radius of every record present: PRECONDITION, met by the trmax output of
+ *     terra_tiles_tree_ao_shadows on the same records.  A new deciduous record's radius is decid_radius_by_id[tree_id]; decid_radius, when given, receives it.
+ *  4. status[t] = 2 when either group changed (a record removed, or new records made: trees.size() > start_sz), else 1.  On a tile that passed both
+ *     culls counts[t] is rewritten (M + new) even when nothing changed; on every other tile nothing is written but status and changed.
+ * After all tiles (:3764-3768): update_bcube = {x1, x2, y1, y2, z1, z2}, the union of all spheres over the batch, or six zeros when no sphere was added.  changed[t] = 1
+ * when status[t] == 2 (register_tree_change, :3841), and when status[t] >= 1 and get_mesh_bcube().intersects(update_bcube) (src/3DWorld.h:536-539, adjacency
+ * included); for each such tile the caller runs register_tree_change.  The box is specified BY VALUE (== on floats): it is a min / max union reduced on the device with
+ * atomics, so it does not depend on the order of tiles and records, but a bound that is zero may come out as -0 where the reference has +0 (std::min keeps its first
+ * argument on a tie).  Not reproduced: the is_all_zeros() restart of update_trees_bcube (:3777), which fires only while the box is exactly zero in all six values --
+ * a tree of radius 0 at the origin; a box that is all zeros by value ends the call like the reference's :3764 (no changed beyond status 2).
+ * With the caller stay: the static same-position early-out of :3748-3754, clear_pine_tree_vbos and the shadow-map clears of register_tree_change, the small_tree /
+ * tree constructors of the new records, and the re-shadowing.  The reference re-shadows incrementally (only the changed tiles, against neighbours whose maps
+ * exist); terra_tiles_tree_ao_shadows recomputes a batch from empty maps, and that is what a caller runs after this call.
+ * radius == 0 is not special-cased: a round brush then removes nothing, a square one removes a record exactly at pt_pos, and the additions follow the two placement
+ * calls.  TERRA_ERR_ARG (and nothing is changed): a NULL required pointer (pos; tile_xy, stats, trmax, status, changed when n > 0; the records of a group that is
+ * present), a misaligned pointer, an unsupported S, a radius that is negative or not finite, a deciduous group without decid_radius and without
+ * decid_radius_by_id, add_trees with a deciduous group and no decid_radius_by_id or no zvals, decid_radius_by_id (where it is needed) with num_radius_by_id !=
+ * terra_decid_params.num_shared_trees or with 0 shared trees, `instanced` with an instance table of the wrong length, everything the two brush placement calls refuse
+ * when add_trees, n*pine_capacity or n*decid_capacity beyond 32 bits.  TERRA_ERR_STATE before terra_init_scene (and, when add_trees, while a heightmap texture is
+ * set).  n == 0 does nothing.  The device form only enqueues and reads nothing back; tile_xy and pos are host arrays in both forms.  update_bcube may be NULL.  Scratch
+ * comes from the context's arena. */
+enum {TERRA_TREE_EDIT_PINE_NOT_GENERATED = 1, TERRA_TREE_EDIT_DECID_NOT_GENERATED = 2}; /* gen_flags */
+int  terra_tiles_edit_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                                const float pos[3], float radius, int32_t add_trees, int32_t is_square,
+                                const uint8_t *d_skip, const terra_tile_stats *d_stats, const float *d_zvals, const uint8_t *d_gen_flags,
+                                terra_tree_place *d_pine, uint32_t *d_pine_counts, uint32_t pine_capacity,
+                                terra_decid_place *d_decid, uint32_t *d_decid_counts, uint32_t decid_capacity,
+                                float *d_decid_radius, const float *d_decid_radius_by_id, uint32_t num_radius_by_id,
+                                float *d_trmax, uint8_t *d_status, uint8_t *d_changed, float *d_update_bcube);
+int  terra_tiles_edit_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
+                            const float pos[3], float radius, int32_t add_trees, int32_t is_square,
+                            const uint8_t *h_skip, const terra_tile_stats *h_stats, const float *h_zvals, const uint8_t *h_gen_flags,
+                            terra_tree_place *h_pine, uint32_t *h_pine_counts, uint32_t pine_capacity,
+                            terra_decid_place *h_decid, uint32_t *h_decid_counts, uint32_t decid_capacity,
+                            float *h_decid_radius, const float *h_decid_radius_by_id, uint32_t num_radius_by_id,
+                            float *h_trmax, uint8_t *h_status, uint8_t *h_changed, float *h_update_bcube);
 
 /* ---- tile mesh shadows of one directional light: tile_t::calc_shadows_for_light + calc_mesh_shadows / mesh_shadow_gen (src/tiled_mesh.cpp:664-692,
  * src/visibility.cpp:411-520).  zvals: [n][S+2][S+2]; light_pos: the light's position vector (get_light_pos(l)); smask: [n][S+2][S+2] bytes, 0 or

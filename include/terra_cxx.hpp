@@ -309,6 +309,19 @@ inline void tiles_apply_tree_ao_shadows(tile_batch_dev_t const &b, int xoff2, in
 		tr.d_decid_counts, tr.decid_capacity, tr.d_sphere_radius, tr.d_sphere_radius_by_id, tr.num_shared_trees, d_flags, list_capacity, d_tree_map, d_updated, d_trmax,
 		d_list_counts), "apply_tree_ao_shadows");
 }
+// tile_draw_t::add_or_remove_trees_at (src/tiled_mesh.cpp:3746-3769) from :3756 on, for the tiles of the batch, on the records tiles_gen_trees / tiles_gen_decid_trees
+// left on the device, in place: the culls, the removal loops, add_new_trees and the near_tiles decision.  xoff2 / yoff2: what the placements ran with.  The caller keeps
+// the same-position early-out (:3748-3754), then calls register_tree_change on every tile with d_changed[t] != 0 and tiles_apply_tree_ao_shadows on the batch.
+// d_trmax: tiles_apply_tree_ao_shadows' output, in and out
+inline void tiles_add_or_remove_trees_at(tile_batch_dev_t const &b, int xoff2, int yoff2, float const pos[3], float radius, bool add_trees, bool is_square,
+	unsigned char const *d_no_trees, unsigned char const *d_gen_flags, terra_tree_place *d_pine_trees,
+	unsigned *d_pine_counts, unsigned pine_capacity, terra_decid_place *d_decid_trees, unsigned *d_decid_counts, unsigned decid_capacity, float *d_sphere_radius,
+	float const *d_sphere_radius_by_id, unsigned num_shared_trees, float *d_trmax, unsigned char *d_status, unsigned char *d_changed, float *d_update_bcube = nullptr)
+{
+	check(terra_tiles_edit_trees_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, pos, radius, add_trees, is_square, d_no_trees, b.d_stats, b.d_zvals, d_gen_flags,
+		d_pine_trees, d_pine_counts, pine_capacity, d_decid_trees, d_decid_counts, decid_capacity, d_sphere_radius, d_sphere_radius_by_id, num_shared_trees, d_trmax, d_status,
+		d_changed, d_update_bcube), "add_or_remove_trees_at");
+}
 inline void set_tree_size_params(float tree_height_scale, float sm_tree_scale, float pine_tree_radius_scale) {
 	terra_tree_size_params const p = {tree_height_scale, sm_tree_scale, pine_tree_radius_scale};
 	check(terra_set_tree_size_params(default_ctx(), &p), "set_tree_size_params");
