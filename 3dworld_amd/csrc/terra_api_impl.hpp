@@ -45,6 +45,7 @@ struct terra_gen { // mesh_xy_grid_cache_t (src/mesh.h:22-45)
                       catch (std::exception const &e) {return terra::fail(TERRA_ERR_HIP, e.what());} \
                       return TERRA_OK;
 #define TERRA_CHECK_CTX if (!ctx) return terra::fail(TERRA_ERR_ARG, "null terra_ctx");
+typedef terra::host_stage_t<terra::terra_engine<terra_backend_t>> terra_stage; // the device copies of a host-pointer entry point's arrays (terra_stage.hpp)
 
 extern "C" {
 
@@ -256,8 +257,11 @@ int terra_gen_grid(terra_ctx *ctx, float x0, float y0, float dx, float dy, uint3
 	TERRA_TRY
 		size_t const bytes = (size_t)nx*ny*sizeof(float);
 		if (bytes == 0) throw std::invalid_argument("build_arrays: nx, ny must be > 0");
-		float *d = ctx->eng.host_grid_scratch(bytes);
-		ctx->eng.gen_grid_dev(x0, y0, dx, dy, nx, ny, flags, min_start_sin, d); ctx->eng.be.d2h(h_out, d, bytes);
+		terra_stage st(ctx->eng);
+		int const o = st.out(h_out, bytes);
+		st.begin();
+		ctx->eng.gen_grid_dev(x0, y0, dx, dy, nx, ny, flags, min_start_sin, st.dev<float>(o));
+		st.end();
 	TERRA_CATCH
 }
 
@@ -320,8 +324,11 @@ int terra_apply_erosion(terra_ctx *ctx, float *h, int xs, int ys, float min_zval
 		if (iters == 0 || ctx->eng.erode_amount <= 0.0f) return TERRA_OK;
 		if (xs <= 0 || ys <= 0) throw std::invalid_argument("apply_erosion: bad grid size");
 		size_t const bytes = (size_t)xs*ys*sizeof(float);
-		float *d = ctx->eng.host_grid_scratch(bytes); // grow-only (a 1 GiB hipMalloc + hipFree per call cost more than the erosion)
-		ctx->eng.be.h2d(d, h, bytes); ctx->eng.apply_erosion_dev(d, xs, ys, min_zval, iters, 0); ctx->eng.be.d2h(h, d, bytes);
+		terra_stage st(ctx->eng); // grow-only (a 1 GiB hipMalloc + hipFree per call cost more than the erosion)
+		int const g = st.inout(h, bytes);
+		st.begin();
+		ctx->eng.apply_erosion_dev(st.dev<float>(g), xs, ys, min_zval, iters, 0);
+		st.end();
 	TERRA_CATCH
 }
 int terra_set_erosion_tuning(terra_ctx *ctx, uint32_t window, uint32_t cap_log2, uint32_t maxb) {
@@ -374,11 +381,12 @@ int terra_heightmap_proc_gen(terra_ctx *ctx, uint32_t width, uint32_t height, ui
 	if (width == 0 || height == 0) return terra::fail(TERRA_ERR_ARG, "terra_heightmap_proc_gen: empty map");
 	TERRA_TRY
 		size_t const n = (size_t)width*height;
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(n*6 + 512); // floats, then the 16-bit pixels (16-byte aligned)
-		uint8_t *d_pix = d + ((n*4 + 255) & ~(size_t)255);
-		int const rc = terra_heightmap_proc_gen_dev(ctx, width, height, erosion_iters, (float *)d, d_pix, h_range);
+		terra_stage st(ctx->eng);
+		int const v = st.temp(n*4), p = st.out(h_pix, n*2); // floats, then the 16-bit pixels
+		st.begin();
+		int const rc = terra_heightmap_proc_gen_dev(ctx, width, height, erosion_iters, st.dev<float>(v), st.dev<uint8_t>(p), h_range);
 		if (rc != TERRA_OK) return rc;
-		ctx->eng.be.d2h(h_pix, d_pix, n*2);
+		st.end();
 	TERRA_CATCH
 }
 
@@ -530,17 +538,15 @@ int terra_export_heightmap_dev(terra_ctx *ctx, float xstart, float ystart, uint3
 int terra_write_map_mode_heightmap_image(terra_ctx *ctx, const char *path, float xstart, float ystart, uint32_t width, uint32_t height) {
 	TERRA_CHECK_CTX if (!path) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY
-		auto &be = ctx->eng.be;
 		size_t const n = (size_t)width*height;
 		if (n == 0) return terra::fail(TERRA_ERR_ARG, "empty image");
-		uint8_t *d = (uint8_t *)be.alloc(n*6);
-		try {
-			ctx->eng.export_heightmap_dev(xstart, ystart, width, height, (float *)d, d + n*4, nullptr);
-			std::vector<uint8_t> px(n*2);
-			be.d2h(px.data(), d + n*4, n*2);
-			terra::png_write_gray(path, px.data(), width, height, 2);
-		} catch (...) {be.free(d); throw;}
-		be.free(d);
+		std::vector<uint8_t> px(n*2);
+		terra_stage st(ctx->eng, terra_stage::OWN_ALLOC);
+		int const v = st.temp(n*4), p = st.out(px.data(), n*2);
+		st.begin();
+		ctx->eng.export_heightmap_dev(xstart, ystart, width, height, st.dev<float>(v), st.dev<uint8_t>(p), nullptr);
+		st.end();
+		terra::png_write_gray(path, px.data(), width, height, 2);
 	TERRA_CATCH
 }
 int terra_set_landscape(terra_ctx *ctx, const terra_landscape *params) {
@@ -565,17 +571,12 @@ int terra_tiles_create_weights(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
 		ctx->eng.require_tile_128("tiles_create_weights"); // (before the zvals are read: they are 130^2 floats a tile)
-		auto &be = ctx->eng.be;
-		size_t const zb = (size_t)n*130*130*4, wb = (size_t)n*129*129*4, gb = (size_t)n*32*32*sizeof(terra_grass_block), hb = ((size_t)n + 3) & ~(size_t)3;
-		uint8_t *d = (uint8_t *)be.alloc(zb + wb + gb + hb);
-		try {
-			be.h2d(d, h_zvals, zb);
-			ctx->eng.tiles_create_weights_dev(tile_xy, n, (float const *)d, d + zb, h_grass_blocks ? (terra::grass_block_pod_t *)(d + zb + wb) : nullptr, h_has_any_grass ? d + zb + wb + gb : nullptr);
-			be.d2h(h_weights, d + zb, wb);
-			if (h_grass_blocks) {be.d2h(h_grass_blocks, d + zb + wb, gb);}
-			if (h_has_any_grass) {be.d2h(h_has_any_grass, d + zb + wb + gb, n);}
-		} catch (...) {be.free(d); throw;}
-		be.free(d);
+		terra_stage st(ctx->eng, terra_stage::OWN_ALLOC);
+		int const z = st.in(h_zvals, (size_t)n*130*130*4), w = st.out(h_weights, (size_t)n*129*129*4), g = st.opt_out(h_grass_blocks, (size_t)n*32*32*sizeof(terra_grass_block)),
+			a = st.opt_out(h_has_any_grass, n);
+		st.begin();
+		ctx->eng.tiles_create_weights_dev(tile_xy, n, st.dev<float>(z), st.dev<uint8_t>(w), st.dev<terra::grass_block_pod_t>(g), st.dev<uint8_t>(a));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_edit_grass_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *d_zvals, const terra_tile_stats *d_stats,
@@ -591,17 +592,13 @@ int terra_tiles_edit_grass(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 		ctx->eng.require_scene();
 		ctx->eng.require_tile_128("tiles_edit_grass"); // (before the arrays are read: they are sized for 128)
 		if (n == 0) return TERRA_OK;
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const zb = (size_t)n*130*130*4, sb = (size_t)n*sizeof(terra_tile_stats), db = n, wb = (size_t)n*129*129*4, gb = (size_t)n*32*32*sizeof(terra_grass_block), ub = n, rb = (size_t)n*16;
-		size_t const oz = 0, os = oz + up(zb), od = os + up(sb), ow = od + up(db), og = ow + up(wb), ou = og + up(gb), orr = ou + up(ub);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(orr + up(rb));
-		be.h2d(d + oz, h_zvals, zb); be.h2d(d + os, h_stats, sb); be.h2d(d + ow, h_weights, wb); be.h2d(d + og, h_grass_blocks, gb);
-		if (h_is_distant) {be.h2d(d + od, h_is_distant, db);}
-		ctx->eng.tiles_edit_grass_dev(tile_xy, n, dxoff, dyoff, (float const *)(d + oz), (terra_tile_stats const *)(d + os), h_is_distant ? d + od : nullptr, brush->pos, brush->radius,
-			brush->add_grass != 0, brush->shape, brush->brush_weight, d + ow, (terra::grass_block_pod_t *)(d + og), d + ou, (uint32_t *)(d + orr));
-		be.d2h(h_weights, d + ow, wb); be.d2h(h_grass_blocks, d + og, gb); be.d2h(h_updated, d + ou, ub);
-		if (h_ranges) {be.d2h(h_ranges, d + orr, rb);}
+		terra_stage st(ctx->eng);
+		int const z = st.in(h_zvals, (size_t)n*130*130*4), s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), w = st.inout(h_weights, (size_t)n*129*129*4),
+			g = st.inout(h_grass_blocks, (size_t)n*32*32*sizeof(terra_grass_block)), k = st.opt_in(h_is_distant, n), u = st.out(h_updated, n), r = st.out(h_ranges, (size_t)n*16);
+		st.begin();
+		ctx->eng.tiles_edit_grass_dev(tile_xy, n, dxoff, dyoff, st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<uint8_t>(k), brush->pos, brush->radius,
+			brush->add_grass != 0, brush->shape, brush->brush_weight, st.dev<uint8_t>(w), st.dev<terra::grass_block_pod_t>(g), st.dev<uint8_t>(u), st.dev<uint32_t>(r));
+		st.end();
 	TERRA_CATCH
 }
 static_assert(sizeof(terra_line_hit) == 32 && sizeof(terra::line_hit_pod_t) == 32, "terra_line_hit layout");
@@ -620,19 +617,14 @@ int terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 			for (uint32_t r = 0; r < nlines; ++r) {if (h_line_tile[r] >= 0 && (uint32_t)h_line_tile[r] >= n) {return terra::fail(TERRA_ERR_ARG, "tiles_line_intersect: line_tile entry out of range");}}
 		}
 		if (nlines == 0) return TERRA_OK;
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
 		size_t const S = ctx->eng.tile_size();
-		size_t const zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*sizeof(terra_tile_stats), db = n, lb = (size_t)nlines*24, tb = (size_t)nlines*4, hb = (size_t)nlines*32;
-		size_t const oz = 0, os = oz + up(zb), od = os + up(sb), ol = od + up(db), ot = ol + up(lb), oh = ot + up(tb);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oh + up(hb));
-		if (n) {be.h2d(d + oz, h_zvals, zb); be.h2d(d + os, h_stats, sb);}
-		if (n && h_is_distant) {be.h2d(d + od, h_is_distant, db);}
-		be.h2d(d + ol, h_lines, lb);
-		if (h_line_tile) {be.h2d(d + ot, h_line_tile, tb);}
-		ctx->eng.tiles_line_intersect_dev(tile_xy, n, dxoff, dyoff, (float const *)(d + oz), (terra_tile_stats const *)(d + os), h_is_distant ? d + od : nullptr,
-			(float const *)(d + ol), h_line_tile ? (int32_t const *)(d + ot) : nullptr, nlines, (terra::line_hit_pod_t *)(d + oh));
-		be.d2h(h_hits, d + oh, hb);
+		terra_stage st(ctx->eng); // (with n == 0 the tile arrays are empty: nothing of them is uploaded)
+		int const z = st.in(h_zvals, (size_t)n*(S + 2)*(S + 2)*4), s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), k = st.opt_in(h_is_distant, n),
+			l = st.in(h_lines, (size_t)nlines*24), lt = st.opt_in(h_line_tile, (size_t)nlines*4), h = st.out(h_hits, (size_t)nlines*32);
+		st.begin();
+		ctx->eng.tiles_line_intersect_dev(tile_xy, n, dxoff, dyoff, st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<uint8_t>(k), st.dev<float>(l), st.dev<int32_t>(lt), nlines,
+			st.dev<terra::line_hit_pod_t>(h));
+		st.end();
 	TERRA_CATCH
 }
 static_assert(sizeof(terra_tree_splat) == 12 && sizeof(terra::tree_splat_in_t) == 12, "terra_tree_splat layout");
@@ -651,20 +643,15 @@ int terra_tiles_tree_map(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int
 		for (uint32_t t = 0; t < n; ++t) {if (h_first[t+1] < h_first[t]) {return terra::fail(TERRA_ERR_ARG, "tiles_tree_map: h_first must not decrease");}}
 		uint32_t const s0 = h_first[0], ns = h_first[n] - s0;
 		if (ns && !h_splats) return terra::fail(TERRA_ERR_ARG, "tiles_tree_map: null splat list");
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
 		size_t const S = ctx->eng.tile_size();
-		size_t const mb = (size_t)n*(S + 1)*(S + 1)*2, sb = (size_t)ns*sizeof(terra_tree_splat), db = n, ub = n;
-		size_t const om = 0, os = om + up(mb), od = os + up(sb), ou = od + up(db);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(ou + up(ub));
-		if (!reset) {be.h2d(d + om, h_tree_map, mb);}
-		if (ns) {be.h2d(d + os, h_splats + s0, sb);}
-		if (h_is_distant) {be.h2d(d + od, h_is_distant, db);}
+		terra_stage st(ctx->eng);
+		int const m = st.add(reset ? nullptr : h_tree_map, h_tree_map, (size_t)n*(S + 1)*(S + 1)*2), s = st.in(ns ? h_splats + s0 : nullptr, (size_t)ns*sizeof(terra_tree_splat)),
+			k = st.opt_in(h_is_distant, n), u = st.out(h_updated, n);
+		st.begin();
 		std::vector<uint32_t> first(h_first, h_first + n + 1);
 		for (uint32_t &f : first) {f -= s0;} // (the device copy holds only the splats the lists name)
-		ctx->eng.tiles_tree_map_dev(tile_xy, n, dxoff, dyoff, h_is_distant ? d + od : nullptr, (terra::tree_splat_in_t const *)(d + os), first.data(), reset != 0, d + om, d + ou);
-		be.d2h(h_tree_map, d + om, mb);
-		if (h_updated) {be.d2h(h_updated, d + ou, ub);}
+		ctx->eng.tiles_tree_map_dev(tile_xy, n, dxoff, dyoff, st.dev<uint8_t>(k), st.dev<terra::tree_splat_in_t>(s), first.data(), reset != 0, st.dev<uint8_t>(m), st.dev<uint8_t>(u));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_shadow_texture_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_smask_sun, const uint8_t *d_smask_moon, const uint8_t *d_ao, const uint8_t *d_tree_map,
@@ -678,19 +665,13 @@ int terra_tiles_shadow_texture(terra_ctx *ctx, uint32_t n, const uint8_t *h_smas
 	TERRA_TRY
 		ctx->eng.require_scene();
 		ctx->eng.require_tile_size();
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
 		size_t const S = ctx->eng.tile_size();
-		size_t const zb = (size_t)n*(S + 2)*(S + 2), ab = (size_t)n*(S + 1)*(S + 1), tb = 2*ab, ob = 4*ab;
-		size_t const o1 = 0, o2 = o1 + up(zb), oa = o2 + up(zb), ot = oa + up(ab), oo = ot + up(tb);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oo + up(ob));
-		if (n && h_smask_sun) {be.h2d(d + o1, h_smask_sun, zb);}
-		if (n && h_smask_moon) {be.h2d(d + o2, h_smask_moon, zb);}
-		if (n && h_ao) {be.h2d(d + oa, h_ao, ab);}
-		if (n && h_tree_map) {be.h2d(d + ot, h_tree_map, tb);}
-		ctx->eng.tiles_shadow_texture_dev(n, h_smask_sun ? d + o1 : nullptr, h_smask_moon ? d + o2 : nullptr, h_ao ? d + oa : nullptr, h_tree_map ? d + ot : nullptr,
-			light_factor, mesh_shadows, d + oo);
-		if (n) {be.d2h(h_shadow, d + oo, ob);}
+		size_t const zb = (size_t)n*(S + 2)*(S + 2), ab = (size_t)n*(S + 1)*(S + 1);
+		terra_stage st(ctx->eng); // (with n == 0 every array is empty: nothing is copied)
+		int const s1 = st.opt_in(h_smask_sun, zb), s2 = st.opt_in(h_smask_moon, zb), a = st.opt_in(h_ao, ab), t = st.opt_in(h_tree_map, 2*ab), o = st.out(h_shadow, 4*ab);
+		st.begin();
+		ctx->eng.tiles_shadow_texture_dev(n, st.dev<uint8_t>(s1), st.dev<uint8_t>(s2), st.dev<uint8_t>(a), st.dev<uint8_t>(t), light_factor, mesh_shadows, st.dev<uint8_t>(o));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_tree_weights_dev(terra_ctx *ctx, uint32_t n, const uint8_t *d_mesh_weights, const uint8_t *d_tree_map, uint8_t *d_weights) {
@@ -703,14 +684,11 @@ int terra_tiles_tree_weights(terra_ctx *ctx, uint32_t n, const uint8_t *h_mesh_w
 		ctx->eng.require_scene();
 		ctx->eng.require_tile_128("tiles_tree_weights"); // (before the arrays are read: they are sized for 128)
 		if (n == 0) return TERRA_OK;
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const wb = (size_t)n*129*129*4, tb = (size_t)n*129*129*2;
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(up(wb) + up(tb));
-		be.h2d(d, h_mesh_weights, wb);
-		if (h_tree_map) {be.h2d(d + up(wb), h_tree_map, tb);}
-		ctx->eng.tiles_tree_weights_dev(n, d, h_tree_map ? d + up(wb) : nullptr, d);
-		be.d2h(h_weights, d, wb);
+		terra_stage st(ctx->eng);
+		int const w = st.add(h_mesh_weights, h_weights, (size_t)n*129*129*4), t = st.opt_in(h_tree_map, (size_t)n*129*129*2); // (the output is written over the input)
+		st.begin();
+		ctx->eng.tiles_tree_weights_dev(n, st.dev<uint8_t>(w), st.dev<uint8_t>(t), st.dev<uint8_t>(w));
+		st.end();
 	TERRA_CATCH
 }
 int terra_set_tree_params(terra_ctx *ctx, const terra_tree_params *params) {
@@ -741,22 +719,12 @@ static int tiles_place_trees_impl(terra_ctx *ctx, const int32_t *tile_xy, uint32
 		if (!host) {ctx->eng.tiles_place_trees_dev(tile_xy, n, xoff2, yoff2, skip, stats, brush, capacity, (terra::tree_place_pod_t *)trees, counts); return TERRA_OK;}
 		ctx->eng.require_scene();
 		ctx->eng.require_tile_size();
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const tb = (size_t)n*capacity*sizeof(terra_tree_place), cb = (size_t)n*4, kb = n, sb = (size_t)n*sizeof(terra_tile_stats);
-		size_t const ot = 0, oc = ot + up(tb), ok = oc + up(cb), os = ok + up(kb);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(os + up(sb));
-		if (n && skip) {be.h2d(d + ok, skip, kb);}
-		if (n && stats) {be.h2d(d + os, stats, sb);}
-		ctx->eng.tiles_place_trees_dev(tile_xy, n, xoff2, yoff2, skip ? d + ok : nullptr, stats ? (terra_tile_stats const *)(d + os) : nullptr, brush, capacity,
-			(terra::tree_place_pod_t *)(d + ot), (uint32_t *)(d + oc));
 		if (n == 0) return TERRA_OK;
-		be.d2h(counts, d + oc, cb);
-		// only the records the counts name were written: the rest of the caller's array stays as it was
-		for (uint32_t t = 0; t < n; ++t) {
-			uint32_t const m = std::min(counts[t], capacity);
-			if (m) {be.d2h(trees + (size_t)t*capacity, d + ot + (size_t)t*capacity*sizeof(terra_tree_place), (size_t)m*sizeof(terra_tree_place));}
-		}
+		terra_stage st(ctx->eng);
+		int const r = st.temp((size_t)n*capacity*sizeof(terra_tree_place)), c = st.temp((size_t)n*4), k = st.opt_in(skip, n), s = st.opt_in(stats, (size_t)n*sizeof(terra_tile_stats));
+		st.begin();
+		ctx->eng.tiles_place_trees_dev(tile_xy, n, xoff2, yoff2, st.dev<uint8_t>(k), st.dev<terra_tile_stats>(s), brush, capacity, st.dev<terra::tree_place_pod_t>(r), st.dev<uint32_t>(c));
+		st.end_counted(r, c, trees, counts, n, capacity);
 	TERRA_CATCH
 }
 int terra_tiles_place_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
@@ -797,24 +765,15 @@ static int tiles_place_decid_trees_impl(terra_ctx *ctx, const int32_t *tile_xy, 
 		ctx->eng.require_scene();
 		ctx->eng.require_tile_size();
 		if (n && stats && !zvals) throw std::invalid_argument("tiles_place_decid_trees: stats without zvals (the slope test reads the tile's heights)");
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const Z = (size_t)ctx->eng.tile_size() + 2;
-		size_t const tb = (size_t)n*capacity*sizeof(terra_decid_place), cb = (size_t)n*4, kb = n, sb = (size_t)n*sizeof(terra_tile_stats), zb = zvals ? (size_t)n*Z*Z*sizeof(float) : 0;
-		size_t const ot = 0, oc = ot + up(tb), ok = oc + up(cb), os = ok + up(kb), oz = os + up(sb);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oz + up(zb));
-		if (n && skip) {be.h2d(d + ok, skip, kb);}
-		if (n && stats) {be.h2d(d + os, stats, sb);}
-		if (n && zvals) {be.h2d(d + oz, zvals, zb);}
-		ctx->eng.tiles_place_decid_trees_dev(tile_xy, n, xoff2, yoff2, skip ? d + ok : nullptr, stats ? (terra_tile_stats const *)(d + os) : nullptr,
-			zvals ? (float const *)(d + oz) : nullptr, brush, capacity, (terra::decid_place_pod_t *)(d + ot), (uint32_t *)(d + oc));
 		if (n == 0) return TERRA_OK;
-		be.d2h(counts, d + oc, cb);
-		// only the records the counts name were written: the rest of the caller's array stays as it was
-		for (uint32_t t = 0; t < n; ++t) {
-			uint32_t const m = std::min(counts[t], capacity);
-			if (m) {be.d2h(trees + (size_t)t*capacity, d + ot + (size_t)t*capacity*sizeof(terra_decid_place), (size_t)m*sizeof(terra_decid_place));}
-		}
+		size_t const Z = (size_t)ctx->eng.tile_size() + 2;
+		terra_stage st(ctx->eng);
+		int const r = st.temp((size_t)n*capacity*sizeof(terra_decid_place)), c = st.temp((size_t)n*4), k = st.opt_in(skip, n), s = st.opt_in(stats, (size_t)n*sizeof(terra_tile_stats)),
+			z = st.opt_in(zvals, (size_t)n*Z*Z*sizeof(float));
+		st.begin();
+		ctx->eng.tiles_place_decid_trees_dev(tile_xy, n, xoff2, yoff2, st.dev<uint8_t>(k), st.dev<terra_tile_stats>(s), st.dev<float>(z), brush, capacity,
+			st.dev<terra::decid_place_pod_t>(r), st.dev<uint32_t>(c));
+		st.end_counted(r, c, trees, counts, n, capacity);
 	TERRA_CATCH
 }
 int terra_tiles_place_decid_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *d_skip, const terra_tile_stats *d_stats,
@@ -857,22 +816,13 @@ int terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
 	TERRA_TRY
 		ctx->eng.require_scene();
 		ctx->eng.require_tile_size();
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const ob = (size_t)n*capacity*sizeof(terra_scenery_place), cb = (size_t)n*4, kb = n, qb = (size_t)n*TERRA_SCENERY_KINDS*4;
-		size_t const oo = 0, oc = oo + up(ob), ok = oc + up(cb), oq = ok + up(kb);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(oq + up(qb));
-		if (n && h_skip) {be.h2d(d + ok, h_skip, kb);}
-		ctx->eng.tiles_place_scenery_dev(tile_xy, n, xoff2, yoff2, h_skip ? d + ok : nullptr, capacity, (terra::scenery_place_pod_t *)(d + oo), (uint32_t *)(d + oc),
-			h_kind_counts ? (uint32_t *)(d + oq) : nullptr);
 		if (n == 0) return TERRA_OK;
-		be.d2h(h_counts, d + oc, cb);
-		if (h_kind_counts) {be.d2h(h_kind_counts, d + oq, qb);}
-		// only the records the counts name were written: the rest of the caller's array stays as it was
-		for (uint32_t t = 0; t < n; ++t) {
-			uint32_t const m = std::min(h_counts[t], capacity);
-			if (m) {be.d2h(h_objs + (size_t)t*capacity, d + oo + (size_t)t*capacity*sizeof(terra_scenery_place), (size_t)m*sizeof(terra_scenery_place));}
-		}
+		terra_stage st(ctx->eng);
+		int const r = st.temp((size_t)n*capacity*sizeof(terra_scenery_place)), c = st.temp((size_t)n*4), k = st.opt_in(h_skip, n), q = st.opt_out(h_kind_counts, (size_t)n*TERRA_SCENERY_KINDS*4);
+		st.begin();
+		ctx->eng.tiles_place_scenery_dev(tile_xy, n, xoff2, yoff2, st.dev<uint8_t>(k), capacity, st.dev<terra::scenery_place_pod_t>(r), st.dev<uint32_t>(c), st.dev<uint32_t>(q));
+		st.end_counted(r, c, h_objs, h_counts, n, capacity);
+		st.end();
 	TERRA_CATCH
 }
 int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
@@ -917,27 +867,19 @@ int terra_tiles_tree_ao_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_t
 		if (n == 0) return TERRA_OK;
 		bool const has_pine = h_pine_counts && pine_capacity, has_decid = h_decid_counts && decid_capacity;
 		if ((has_pine && !h_pine) || (has_decid && !h_decid)) return terra::fail(TERRA_ERR_ARG, "tiles_tree_ao_shadows: counts without records");
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const S = ctx->eng.tile_size();
-		size_t const mb = (size_t)n*(S + 1)*(S + 1)*2, pb = has_pine ? (size_t)n*pine_capacity*sizeof(terra_tree_place) : 0, db = has_decid ? (size_t)n*decid_capacity*sizeof(terra_decid_place) : 0,
-			rb = (has_decid && h_decid_radius) ? (size_t)n*decid_capacity*4 : 0, ib = (has_decid && h_decid_radius_by_id) ? (size_t)num_radius_by_id*4 : 0, cb = (size_t)n*4;
-		size_t const om = 0, op = om + up(mb), od = op + up(pb), orr = od + up(db), oi = orr + up(rb), opc = oi + up(ib), odc = opc + up(cb), of = odc + up(cb), ou = of + up(n),
-			ot = ou + up(n), ol = ot + up(cb);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(ol + up(cb));
-		if (has_pine) {be.h2d(d + op, h_pine, pb); be.h2d(d + opc, h_pine_counts, cb);}
-		if (has_decid) {be.h2d(d + od, h_decid, db); be.h2d(d + odc, h_decid_counts, cb);}
-		if (rb) {be.h2d(d + orr, h_decid_radius, rb);}
-		if (ib) {be.h2d(d + oi, h_decid_radius_by_id, ib);}
-		if (h_flags) {be.h2d(d + of, h_flags, n);}
-		ctx->eng.tiles_tree_ao_shadows_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, has_pine ? (terra::tree_place_pod_t const *)(d + op) : nullptr, has_pine ? (uint32_t const *)(d + opc) : nullptr,
-			pine_capacity, has_decid ? (terra::decid_place_pod_t const *)(d + od) : nullptr, has_decid ? (uint32_t const *)(d + odc) : nullptr, decid_capacity,
-			(has_decid && h_decid_radius) ? (float const *)(d + orr) : nullptr, (has_decid && h_decid_radius_by_id) ? (float const *)(d + oi) : nullptr, num_radius_by_id,
-			h_flags ? d + of : nullptr, list_capacity, d + om, d + ou, (float *)(d + ot), (uint32_t *)(d + ol));
-		be.d2h(h_tree_map, d + om, mb);
-		if (h_updated) {be.d2h(h_updated, d + ou, n);}
-		if (h_trmax) {be.d2h(h_trmax, d + ot, cb);}
-		if (h_list_counts) {be.d2h(h_list_counts, d + ol, cb);}
+		size_t const S = ctx->eng.tile_size(), cb = (size_t)n*4;
+		terra_stage st(ctx->eng);
+		int const m = st.out(h_tree_map, (size_t)n*(S + 1)*(S + 1)*2),
+			p = st.add(h_pine, nullptr, (size_t)n*pine_capacity*sizeof(terra_tree_place), has_pine), pc = st.add(h_pine_counts, nullptr, cb, has_pine),
+			e = st.add(h_decid, nullptr, (size_t)n*decid_capacity*sizeof(terra_decid_place), has_decid), ec = st.add(h_decid_counts, nullptr, cb, has_decid),
+			r = st.add(h_decid_radius, nullptr, (size_t)n*decid_capacity*4, has_decid && h_decid_radius),
+			ri = st.add(h_decid_radius_by_id, nullptr, (size_t)num_radius_by_id*4, has_decid && h_decid_radius_by_id),
+			f = st.opt_in(h_flags, n), u = st.out(h_updated, n), t = st.out(h_trmax, cb), l = st.out(h_list_counts, cb);
+		st.begin();
+		ctx->eng.tiles_tree_ao_shadows_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, st.dev<terra::tree_place_pod_t>(p), st.dev<uint32_t>(pc), pine_capacity,
+			st.dev<terra::decid_place_pod_t>(e), st.dev<uint32_t>(ec), decid_capacity, st.dev<float>(r), st.dev<float>(ri), num_radius_by_id,
+			st.dev<uint8_t>(f), list_capacity, st.dev<uint8_t>(m), st.dev<uint8_t>(u), st.dev<float>(t), st.dev<uint32_t>(l));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_edit_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2,
@@ -969,32 +911,19 @@ int terra_tiles_edit_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 		// the cheap refusals before anything is staged (the driver repeats them)
 		if (!std::isfinite(radius) || radius < 0.0f) return terra::fail(TERRA_ERR_ARG, "tiles_edit_trees: the radius must be finite and not negative");
 		if ((has_pine && (uint64_t)n*pine_capacity > 0xFFFFFFFFull) || (has_decid && (uint64_t)n*decid_capacity > 0xFFFFFFFFull)) return terra::fail(TERRA_ERR_ARG, "tiles_edit_trees: n*capacity must fit 32 bits");
-		auto &be = ctx->eng.be;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const Z = (size_t)ctx->eng.tile_size() + 2;
-		size_t const pb = has_pine ? (size_t)n*pine_capacity*sizeof(terra_tree_place) : 0, db = has_decid ? (size_t)n*decid_capacity*sizeof(terra_decid_place) : 0,
-			rb = (has_decid && h_decid_radius) ? (size_t)n*decid_capacity*4 : 0, ib = (has_decid && h_decid_radius_by_id) ? (size_t)num_radius_by_id*4 : 0, cb = (size_t)n*4,
-			sb = (size_t)n*sizeof(terra_tile_stats), zb = h_zvals ? (size_t)n*Z*Z*sizeof(float) : 0;
-		size_t const op = 0, od = op + up(pb), orr = od + up(db), oi = orr + up(rb), opc = oi + up(ib), odc = opc + up(cb), os = odc + up(cb), oz = os + up(sb), ok = oz + up(zb),
-			og = ok + up(n), ot = og + up(n), ou = ot + up(cb), oc = ou + up(n), ob = oc + up(n);
-		uint8_t *d = (uint8_t *)ctx->eng.host_grid_scratch(ob + 256);
-		if (has_pine) {be.h2d(d + op, h_pine, pb); be.h2d(d + opc, h_pine_counts, cb);}
-		if (has_decid) {be.h2d(d + od, h_decid, db); be.h2d(d + odc, h_decid_counts, cb);}
-		if (rb) {be.h2d(d + orr, h_decid_radius, rb);}
-		if (ib) {be.h2d(d + oi, h_decid_radius_by_id, ib);}
-		be.h2d(d + os, h_stats, sb); be.h2d(d + ot, h_trmax, cb);
-		if (zb) {be.h2d(d + oz, h_zvals, zb);}
-		if (h_skip) {be.h2d(d + ok, h_skip, n);}
-		if (h_gen_flags) {be.h2d(d + og, h_gen_flags, n);}
-		ctx->eng.tiles_edit_trees_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, pos, radius, add_trees != 0, is_square != 0, h_skip ? d + ok : nullptr, (terra_tile_stats const *)(d + os),
-			zb ? (float const *)(d + oz) : nullptr, h_gen_flags ? d + og : nullptr, has_pine ? (terra::tree_place_pod_t *)(d + op) : nullptr, has_pine ? (uint32_t *)(d + opc) : nullptr,
-			pine_capacity, has_decid ? (terra::decid_place_pod_t *)(d + od) : nullptr, has_decid ? (uint32_t *)(d + odc) : nullptr, decid_capacity, rb ? (float *)(d + orr) : nullptr,
-			ib ? (float const *)(d + oi) : nullptr, num_radius_by_id, (float *)(d + ot), d + ou, d + oc, (float *)(d + ob));
-		if (has_pine) {be.d2h(h_pine, d + op, pb); be.d2h(h_pine_counts, d + opc, cb);}
-		if (has_decid) {be.d2h(h_decid, d + od, db); be.d2h(h_decid_counts, d + odc, cb);}
-		if (rb) {be.d2h(h_decid_radius, d + orr, rb);}
-		be.d2h(h_trmax, d + ot, cb); be.d2h(h_status, d + ou, n); be.d2h(h_changed, d + oc, n);
-		if (h_update_bcube) {be.d2h(h_update_bcube, d + ob, 24);}
+		size_t const Z = (size_t)ctx->eng.tile_size() + 2, cb = (size_t)n*4;
+		terra_stage st(ctx->eng);
+		int const p = st.inout(h_pine, (size_t)n*pine_capacity*sizeof(terra_tree_place), has_pine), pc = st.inout(h_pine_counts, cb, has_pine),
+			e = st.inout(h_decid, (size_t)n*decid_capacity*sizeof(terra_decid_place), has_decid), ec = st.inout(h_decid_counts, cb, has_decid),
+			r = st.inout(h_decid_radius, (size_t)n*decid_capacity*4, has_decid && h_decid_radius),
+			ri = st.add(h_decid_radius_by_id, nullptr, (size_t)num_radius_by_id*4, has_decid && h_decid_radius_by_id && num_radius_by_id),
+			s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), t = st.inout(h_trmax, cb), z = st.opt_in(h_zvals, (size_t)n*Z*Z*sizeof(float)), k = st.opt_in(h_skip, n),
+			g = st.opt_in(h_gen_flags, n), u = st.out(h_status, n), c = st.out(h_changed, n), b = st.out(h_update_bcube, 24);
+		st.begin();
+		ctx->eng.tiles_edit_trees_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, pos, radius, add_trees != 0, is_square != 0, st.dev<uint8_t>(k), st.dev<terra_tile_stats>(s),
+			st.dev<float>(z), st.dev<uint8_t>(g), st.dev<terra::tree_place_pod_t>(p), st.dev<uint32_t>(pc), pine_capacity, st.dev<terra::decid_place_pod_t>(e), st.dev<uint32_t>(ec),
+			decid_capacity, st.dev<float>(r), st.dev<float>(ri), num_radius_by_id, st.dev<float>(t), st.dev<uint8_t>(u), st.dev<uint8_t>(c), st.dev<float>(b));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_ao_lighting_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, uint8_t *d_ao) {
@@ -1005,16 +934,13 @@ int terra_tiles_ao_lighting(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
 	TERRA_CHECK_CTX if (n && (!tile_xy || !h_zvals || !h_ao)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
-		auto &be = ctx->eng.be;
 		ctx->eng.require_scene(); ctx->eng.require_tile_size();
-		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, ab = (size_t)n*(S + 1)*(S + 1);
-		uint8_t *d = (uint8_t *)be.alloc(zb + ab);
-		try {
-			be.h2d(d, h_zvals, zb);
-			ctx->eng.tiles_ao_lighting_dev(tile_xy, n, (float const *)d, d + zb);
-			be.d2h(h_ao, d + zb, ab);
-		} catch (...) {be.free(d); throw;}
-		be.free(d);
+		size_t const S = ctx->eng.tile_size();
+		terra_stage st(ctx->eng, terra_stage::OWN_ALLOC);
+		int const z = st.in(h_zvals, (size_t)n*(S + 2)*(S + 2)*4), a = st.out(h_ao, (size_t)n*(S + 1)*(S + 1));
+		st.begin();
+		ctx->eng.tiles_ao_lighting_dev(tile_xy, n, st.dev<float>(z), st.dev<uint8_t>(a));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_mesh_shadows_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const float *d_zvals, const float light_pos[3], uint8_t *d_smask) {
@@ -1039,16 +965,13 @@ int terra_tiles_mesh_shadows(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 	TERRA_CHECK_CTX if (n && (!tile_xy || !h_zvals || !h_smask || !light_pos)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
-		auto &be = ctx->eng.be;
 		ctx->eng.require_scene(); ctx->eng.require_tile_size();
-		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*(S + 2)*(S + 2);
-		uint8_t *d = (uint8_t *)be.alloc(zb + sb);
-		try {
-			be.h2d(d, h_zvals, zb);
-			ctx->eng.tiles_mesh_shadows_dev(tile_xy, n, (float const *)d, light_pos, d + zb);
-			be.d2h(h_smask, d + zb, sb);
-		} catch (...) {be.free(d); throw;}
-		be.free(d);
+		size_t const S = ctx->eng.tile_size();
+		terra_stage st(ctx->eng, terra_stage::OWN_ALLOC);
+		int const z = st.in(h_zvals, (size_t)n*(S + 2)*(S + 2)*4), m = st.out(h_smask, (size_t)n*(S + 2)*(S + 2));
+		st.begin();
+		ctx->eng.tiles_mesh_shadows_dev(tile_xy, n, st.dev<float>(z), light_pos, st.dev<uint8_t>(m));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_create_zvals_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, uint32_t iters_tt, float *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz) {
@@ -1063,38 +986,28 @@ int terra_tiles_post(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const f
 	TERRA_CHECK_CTX if (n && (!tile_xy || !h_zvals)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
-		auto &be = ctx->eng.be;
 		ctx->eng.require_scene(); ctx->eng.require_tile_size();
-		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*sizeof(terra_tile_stats), nb = (size_t)n*(S + 1)*(S + 1)*4, mb = (size_t)n*4;
-		uint8_t *d = (uint8_t *)be.alloc(zb + sb + nb + mb + 1024);
-		float *dz = (float *)d; terra_tile_stats *ds = (terra_tile_stats *)(d + zb); uint8_t *dn = d + zb + sb; float *dm = (float *)(d + zb + sb + nb);
-		try {
-			be.h2d(dz, h_zvals, zb);
-			ctx->eng.tiles_post_dev(tile_xy, n, dz, h_stats ? ds : nullptr, h_normals ? dn : nullptr, (h_normals && h_min_nz) ? dm : nullptr);
-			if (h_stats) be.d2h(h_stats, ds, sb);
-			if (h_normals) be.d2h(h_normals, dn, nb);
-			if (h_normals && h_min_nz) be.d2h(h_min_nz, dm, mb);
-		} catch (...) {be.free(d); throw;}
-		be.free(d);
+		size_t const S = ctx->eng.tile_size();
+		terra_stage st(ctx->eng, terra_stage::OWN_ALLOC);
+		int const z = st.in(h_zvals, (size_t)n*(S + 2)*(S + 2)*4), s = st.opt_out(h_stats, (size_t)n*sizeof(terra_tile_stats)), m = st.opt_out(h_normals, (size_t)n*(S + 1)*(S + 1)*4),
+			mn = st.add(nullptr, h_min_nz, (size_t)n*4, h_normals && h_min_nz);
+		st.begin();
+		ctx->eng.tiles_post_dev(tile_xy, n, st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<uint8_t>(m), st.dev<float>(mn));
+		st.end();
 	TERRA_CATCH
 }
 int terra_tiles_create_zvals(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, uint32_t iters_tt, float *h_zvals, terra_tile_stats *h_stats, uint8_t *h_normals, float *h_min_nz) {
 	TERRA_CHECK_CTX if (n && (!tile_xy || !h_zvals)) return terra::fail(TERRA_ERR_ARG, "null argument");
 	if (n == 0) return TERRA_OK;
 	TERRA_TRY
-		auto &be = ctx->eng.be;
 		ctx->eng.require_scene(); ctx->eng.require_tile_size();
-		size_t const S = ctx->eng.tile_size(), zb = (size_t)n*(S + 2)*(S + 2)*4, sb = (size_t)n*sizeof(terra_tile_stats), nb = (size_t)n*(S + 1)*(S + 1)*4, mb = (size_t)n*4;
-		uint8_t *d = (uint8_t *)be.alloc(zb + sb + nb + mb + 1024);
-		float *dz = (float *)d; terra_tile_stats *ds = (terra_tile_stats *)(d + zb); uint8_t *dn = d + zb + sb; float *dm = (float *)(d + zb + sb + nb);
-		try {
-			ctx->eng.tiles_create_zvals_dev(tile_xy, n, iters_tt, dz, h_stats ? ds : nullptr, h_normals ? dn : nullptr, (h_normals && h_min_nz) ? dm : nullptr);
-			be.d2h(h_zvals, dz, zb);
-			if (h_stats) be.d2h(h_stats, ds, sb);
-			if (h_normals) be.d2h(h_normals, dn, nb);
-			if (h_normals && h_min_nz) be.d2h(h_min_nz, dm, mb);
-		} catch (...) {be.free(d); throw;}
-		be.free(d);
+		size_t const S = ctx->eng.tile_size();
+		terra_stage st(ctx->eng, terra_stage::OWN_ALLOC);
+		int const z = st.out(h_zvals, (size_t)n*(S + 2)*(S + 2)*4), s = st.opt_out(h_stats, (size_t)n*sizeof(terra_tile_stats)), m = st.opt_out(h_normals, (size_t)n*(S + 1)*(S + 1)*4),
+			mn = st.add(nullptr, h_min_nz, (size_t)n*4, h_normals && h_min_nz);
+		st.begin();
+		ctx->eng.tiles_create_zvals_dev(tile_xy, n, iters_tt, st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<uint8_t>(m), st.dev<float>(mn));
+		st.end();
 	TERRA_CATCH
 }
 

@@ -18,6 +18,7 @@
 #include "terra_sceneryplace.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
+#include "terra_stage.hpp"
 #include "../../include/terra.h"
 #include <vector>
 #include <map>
@@ -512,6 +513,18 @@ template<bool PERLIN> TERRA_HD nv2 voxel_noise_pair(unsigned x, unsigned y, unsi
 	return val;
 }
 
+// the device mirror of a host vector the engine owns: grown on demand, uploaded when the vector changed since (its setter clears `valid`), not per call
+template<class T> struct dev_mirror_t {
+	T *d = nullptr; size_t cap = 0; bool valid = false;
+	template<class BE> T const *get(BE &be, std::vector<T> const &h) {
+		size_t const n = h.size();
+		if (n > cap) {if (d) {be.sync(); be.free(d); d = nullptr; cap = 0;} d = (T *)be.alloc(n*sizeof(T)); cap = n; valid = false;}
+		if (!valid && n) {be.h2d(d, h.data(), n*sizeof(T));}
+		valid = true;
+		return d;
+	}
+};
+
 template<class BE> struct terra_engine {
 	BE be;
 	options_t opt;
@@ -545,6 +558,9 @@ template<class BE> struct terra_engine {
 	// grow-only device scratch
 	struct scratch_t {void *p = nullptr; size_t bytes = 0;};
 	scratch_t s_xt, s_yt, s_smx, s_smy, s_misc, s_border, s_spec, s_spec_blocks, s_tiles, s_ao, s_edit, s_shadow, s_shadow_map, s_shadow_gather, s_vox, s_sk, s_mm, s_hostgrid;
+	template<class F> void for_each_scratch(F f) { // the one list of them: what release_scratch() and the destructor walk
+		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {f(*s);}
+	}
 	bool tiled_mesh_ao = false; // enable_tiled_mesh_ao (src/3DWorld.cpp:73,1778)
 	uint8_t const *hmap_pix = nullptr; int hmap_w = 0, hmap_h = 0, hmap_nc = 0; // terrain_hmap_manager's image (device memory, owned by the caller)
 	float mesh_file_scale = 1.0f, mesh_file_tz = 0.0f;                          // src/mesh_gen.cpp:41, set by set_mesh_height_scales_for_zval_range
@@ -558,18 +574,18 @@ template<class BE> struct terra_engine {
 	// every grow-only device buffer of the context back to the allocator (they grow again on demand): the erosion ring of a 16384^2 map alone is ~8.5 GiB
 	void release_scratch() {
 		be.sync();
-		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {if (s->p) {be.free(s->p); s->p = nullptr; s->bytes = 0;}}
+		for_each_scratch([&](scratch_t &s) {if (s.p) {be.free(s.p); s.p = nullptr; s.bytes = 0;}});
 		spec_blocks_clean = nullptr; spec_blocks_n = 0;
 		be.release_scratch();
 	}
 	~terra_engine() {
-		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {if (s->p) be.free(s->p);}
+		for_each_scratch([&](scratch_t &s) {if (s.p) be.free(s.p);});
 		if (d_sin_table) be.free(d_sin_table);
 		if (d_noise_lut) be.free(d_noise_lut);
 		if (d_noise3_lut) be.free(d_noise3_lut);
 		if (d_sinTable) be.free(d_sinTable);
-		if (d_hist) be.free(d_hist);
-		if (d_tree_insts) be.free(d_tree_insts);
+		if (hist_mirror.d) be.free(hist_mirror.d);
+		if (tree_insts_mirror.d) be.free(tree_insts_mirror.d);
 	}
 
 	sin_lut_t lut() const {return sin_lut_t{d_sin_table, sscale};}
@@ -723,29 +739,14 @@ template<class BE> struct terra_engine {
 	}
 	// tree_instances (src/sm_tree.cpp:342-364) as far as the radii read it: type, height and width of every instance; the device copy follows on the next call that reads it
 	std::vector<tree_inst_pod_t> tree_insts;
-	tree_inst_pod_t *d_tree_insts = nullptr; size_t d_tree_insts_cap = 0; bool tree_insts_dev_valid = false;
-	void set_tree_instances(tree_inst_pod_t const *v, uint32_t count) {tree_insts.assign(v, v + count); tree_insts_dev_valid = false;}
-	tree_inst_pod_t const *tree_insts_dev() {
-		size_t const ni = tree_insts.size();
-		if (ni > d_tree_insts_cap) {
-			if (d_tree_insts) {be.sync(); be.free(d_tree_insts); d_tree_insts = nullptr; d_tree_insts_cap = 0;}
-			d_tree_insts = (tree_inst_pod_t *)be.alloc(ni*sizeof(tree_inst_pod_t)); d_tree_insts_cap = ni; tree_insts_dev_valid = false;
-		}
-		if (!tree_insts_dev_valid && ni) {be.h2d(d_tree_insts, tree_insts.data(), ni*sizeof(tree_inst_pod_t));}
-		tree_insts_dev_valid = true;
-		return d_tree_insts;
-	}
+	dev_mirror_t<tree_inst_pod_t> tree_insts_mirror;
+	void set_tree_instances(tree_inst_pod_t const *v, uint32_t count) {tree_insts.assign(v, v + count); tree_insts_mirror.valid = false;}
+	tree_inst_pod_t const *tree_insts_dev() {return tree_insts_mirror.get(be, tree_insts);}
 	// height_histogram of estimate_zminmax (src/mesh_gen.cpp:467-480), what get_median_height reads; the device copy follows on the next placement call
 	std::vector<float> height_histogram;
-	float *d_hist = nullptr; size_t d_hist_cap = 0; bool hist_dev_valid = false;
-	void set_height_histogram(float const *v, uint32_t count) {height_histogram.assign(v, v + count); hist_dev_valid = false;}
-	float const *height_histogram_dev() {
-		size_t const nh = height_histogram.size();
-		if (nh > d_hist_cap) {if (d_hist) {be.sync(); be.free(d_hist); d_hist = nullptr; d_hist_cap = 0;} d_hist = (float *)be.alloc(nh*sizeof(float)); d_hist_cap = nh; hist_dev_valid = false;}
-		if (!hist_dev_valid && nh) {be.h2d(d_hist, height_histogram.data(), nh*sizeof(float));}
-		hist_dev_valid = true;
-		return d_hist;
-	}
+	dev_mirror_t<float> hist_mirror;
+	void set_height_histogram(float const *v, uint32_t count) {height_histogram.assign(v, v + count); hist_mirror.valid = false;}
+	float const *height_histogram_dev() {return hist_mirror.get(be, height_histogram);}
 
 	// the config-file values only (no derivation): what an engine that already owns the derived globals passes before terra_set_state
 	void set_config(terra_config const &c) {
@@ -1253,8 +1254,7 @@ template<class BE> struct terra_engine {
 	static uint32_t sparse_touched_cap(uint32_t N) {return (uint32_t)std::min<uint64_t>((uint64_t)N*1024u + 65536u, 64u << 20);}
 	size_t sparse_arena_bytes(uint32_t N) const { // the layout below with the record of written cells included: what a rank's arena must hold
 		uint32_t const maxb = std::min<uint32_t>(std::max<uint32_t>(spec_cfg.maxb, 16), SPEC_MAXB);
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		return 2*(up((size_t)N*maxb*SPEC_PAGE*4) + up((size_t)N*maxb*8) + up((size_t)N*maxb*4) + up((size_t)N*4)) + up((size_t)N*4*6) + up(sizeof(sparse_ctl_t)) + up((size_t)sparse_touched_cap(N)*4 + 4);
+		return 2*(stage_up((size_t)N*maxb*SPEC_PAGE*4) + stage_up((size_t)N*maxb*8) + stage_up((size_t)N*maxb*4) + stage_up((size_t)N*4)) + stage_up((size_t)N*4*6) + stage_up(sizeof(sparse_ctl_t)) + stage_up((size_t)sparse_touched_cap(N)*4 + 4);
 	}
 	bool sparse_erosion(grid_view_t const &g, erosion_consts_t const &ec, uint32_t N, bool record_touched, float const *d_min, uint32_t &first, sparse_shard_t const *sh = nullptr) {
 		sparse_buffers_t sb{};
@@ -1266,21 +1266,21 @@ template<class BE> struct terra_engine {
 		if (opt.ero_sparse_retraces >= 0) {sb.max_retraces = (uint32_t)opt.ero_sparse_retraces;}
 		size_t const nblocks = (size_t)sb.nbx*sb.nby;
 		uint32_t const touched_cap = record_touched ? sparse_touched_cap(N) : 0u;
-		size_t off = 0;
-		auto carve = [&](size_t bytes) {size_t const o = off; off += (bytes + 255) & ~(size_t)255; return o;};
+		stage_layout_t lay;
+		auto carve = [&](size_t bytes) {return lay.add_bytes(bytes);};
 		size_t o_vals[2], o_mask[2], o_bl[2], o_bc[2];
 		for (int b = 0; b < 2; ++b) {o_vals[b] = carve((size_t)N*sb.maxb*SPEC_PAGE*4); o_mask[b] = carve((size_t)N*sb.maxb*8); o_bl[b] = carve((size_t)N*sb.maxb*4); o_bc[b] = carve((size_t)N*4);}
 		size_t const o_slot = carve((size_t)N*4*6), o_ctl = carve(sizeof(sparse_ctl_t)), o_touched = carve((size_t)touched_cap*4 + 4); // (the record comes last: the arenas of a sharded run agree on everything in front of it)
 		// ~137 KB per droplet.  When the buffer has to grow, the request must fit what the device has free (the same budget rule as the general scheduler's ring, incl. the
 		// "ero.mem_budget" test knob); if it does not -- or the allocation fails anyway -- nothing has been touched yet: the general scheduler takes the whole run
-		if (!sh && off > s_spec.bytes) {
+		if (!sh && lay.total > s_spec.bytes) {
 			size_t avail = be.mem_free() + s_spec.bytes, reserve = (size_t)1 << 30;
 			if (opt.ero_mem_budget >= 0) {avail = (size_t)opt.ero_mem_budget; reserve = 0;}
-			if (off + reserve > avail) {first = 0; return false;}
+			if (lay.total + reserve > avail) {first = 0; return false;}
 		}
 		uint8_t *base = sh ? sh->arena : nullptr; // (a sharded run works in the caller's arena: sparse_arena_bytes())
 		if (!sh) {
-			try {base = scratch<uint8_t>(s_spec, off);} // (the general scheduler's ring lives in the same grow-only buffer: the two never run at the same time)
+			try {base = scratch<uint8_t>(s_spec, lay.total);} // (the general scheduler's ring lives in the same grow-only buffer: the two never run at the same time)
 			catch (std::exception const &) {first = 0; return false;}
 		}
 		for (int b = 0; b < 2; ++b) {
@@ -1410,13 +1410,13 @@ template<class BE> struct terra_engine {
 		size_t const nblocks = (size_t)sb.nbx*sb.nby;
 		// carve one allocation.  The ring is the one big buffer of the library (~266 KiB per slot): it must fit what the device has free right now -- several contexts share
 		// a GPU (bench.py keeps 4 heightmaps in flight), and a result never depends on W -- so a ring that would not fit is made smaller until it does
-		size_t off = 0;
-		auto carve = [&](size_t bytes) {size_t const o = off; off += (bytes + 255) & ~(size_t)255; return o;};
+		stage_layout_t lay;
+		auto carve = [&](size_t bytes) {return lay.add_bytes(bytes);};
 		size_t o_vals[2], o_mask[2], o_bl[2], o_bc[2], o_cks[2], o_ckn[2], o_cku[2], o_ckm[2], o_ckc[2], o_ui[2], o_uv[2], o_un[2];
 		size_t o_slot = 0, o_state = 0, o_resume = 0, o_next = 0, o_nodeblk = 0, o_dlist = 0, o_ctl = 0, o_touched = 0, o_done = 0;
 		uint32_t const touched_cap = record_touched ? (uint32_t)std::min<uint64_t>((uint64_t)num_iters*1024u + 65536u, 64u << 20) : 0u;
 		auto layout = [&](uint32_t W) {
-			off = 0;
+			lay.total = 0;
 			for (int b = 0; b < 2; ++b) {o_vals[b] = carve((size_t)W*sb.maxb*SPEC_PAGE*4); o_mask[b] = carve((size_t)W*sb.maxb*8); o_bl[b] = carve((size_t)W*sb.maxb*4); o_bc[b] = carve(W*4);}
 			for (int b = 0; b < 2; ++b) {
 				// (indexed with the stride SPEC_CK_MAX / SPEC_UNDO_MAX per slot; without checkpoints nothing is ever read or written there, so nothing is allocated)
@@ -1429,7 +1429,7 @@ template<class BE> struct terra_engine {
 			o_next = carve((size_t)W*sb.maxb*sizeof(spec_u32x4)); o_nodeblk = carve((size_t)W*sb.maxb*4); o_dlist = carve((size_t)W*sb.maxb*16); o_ctl = carve(sizeof(spec_ctl_t));
 			o_touched = carve((size_t)touched_cap*4 + 4);
 			o_done = carve(((size_t)W + 63)/64*4);
-			return off;
+			return lay.total;
 		};
 		{
 			size_t need = layout(W);
@@ -1440,7 +1440,7 @@ template<class BE> struct terra_engine {
 				sb.W = W;
 			}
 		}
-		uint8_t *base = scratch<uint8_t>(s_spec, off);
+		uint8_t *base = scratch<uint8_t>(s_spec, lay.total);
 		for (int b = 0; b < 2; ++b) {
 			sb.page_vals[b] = (float *)(base + o_vals[b]); sb.page_mask[b] = (unsigned long long *)(base + o_mask[b]); // nothing to initialise: only entries below a version's count are ever read
 			sb.ck_state[b] = (droplet_state_t *)(base + o_cks[b]); sb.ck_nblk[b] = (uint32_t *)(base + o_ckn[b]); sb.ck_undo[b] = (uint32_t *)(base + o_cku[b]);
@@ -1618,8 +1618,9 @@ template<class BE> struct terra_engine {
 		uint32_t const nxpv = round_up(nux*zvx, 128), nypv = round_up(nuy*zvy, 128);
 		size_t const tab_floats = (size_t)F_TABLE_SIZE*(nxpv + nypv), sm_floats = (size_t)nux*zvx + (size_t)nuy*zvy;
 		// one parameter block: tile references | origins of the distinct columns / rows | their per-k constants -- assembled on the host, ONE asynchronous upload
-		size_t const o_refs = 0, o_m0 = (refs.size()*sizeof(tile_ref_t) + 255) & ~(size_t)255, o_sk = o_m0 + (((size_t)(nux + nuy)*4 + 255) & ~(size_t)255);
-		size_t const par_bytes = o_sk + (((nux + nuy)*sizeof(sine_k_t) + 255) & ~(size_t)255);
+		stage_layout_t par_lay;
+		size_t const o_refs = par_lay.add_bytes(refs.size()*sizeof(tile_ref_t)), o_m0 = par_lay.add_bytes((size_t)(nux + nuy)*4), o_sk = par_lay.add_bytes((nux + nuy)*sizeof(sine_k_t));
+		size_t const par_bytes = par_lay.total;
 		size_t const bytes = par_bytes + (tab_floats + sm_floats)*4 + 1024;
 		uint8_t *base = scratch<uint8_t>(s_tiles, bytes);
 		tile_ref_t *d_refs = (tile_ref_t *)(base + o_refs);
@@ -1833,11 +1834,10 @@ template<class BE> struct terra_engine {
 			}
 			std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {return level[a] < level[b];});
 		}
-		size_t const bytes = (size_t)n*4 + adj.size()*4 + (size_t)2*nslots*zv*8 + ((size_t)n + 1)*4 + 256*4 + ((size_t)nslots + 2)*4 + 256;
-		uint8_t *base = scratch<uint8_t>(s_shadow, bytes);
-		uint32_t *d_order = (uint32_t *)base;
-		int32_t *d_adj = (int32_t *)(base + (((size_t)n*4 + 255) & ~(size_t)255));
-		unsigned long long *d_out = (unsigned long long *)((uint8_t *)d_adj + ((adj.size()*4 + 255) & ~(size_t)255)); // [2][n][zv]: (order << 32) | float bits, 0 = never written
+		uint32_t *d_order, *d_sync; int32_t *d_adj; unsigned long long *d_out; // d_out [2][n][zv]: (order << 32) | float bits, 0 = never written; d_sync: the ticket counter of the dataflow launch
+		stage_layout_t lay;
+		lay.add(d_order, n); lay.add(d_adj, adj.size()); lay.add(d_out, (size_t)2*nslots*zv); lay.add(d_sync, 1);
+		lay.bind(scratch<uint8_t>(s_shadow, lay.total));
 		be.h2d_async(d_order, order.data(), (size_t)n*4);
 		be.h2d_async(d_adj, adj.data(), adj.size()*4);
 		be.fill32(d_out, 0, (size_t)2*nslots*zv*2);
@@ -1860,7 +1860,6 @@ template<class BE> struct terra_engine {
 			}
 		}
 		uint32_t const npaths = 4*zv;
-		uint32_t *d_sync = (uint32_t *)((uint8_t *)d_out + (((size_t)2*nslots*zv*8 + 255) & ~(size_t)255)); // the ticket counter of the dataflow launch
 		if (be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync)) {} // one launch; tiles start as their two upstream tiles publish
 		else for (uint32_t first = 0; first < n;) { // "shadows.levels" / cross-check kernels / the emulator / other tile sizes: one launch per dependency level
 			uint32_t last = first;
@@ -2263,12 +2262,11 @@ template<class BE> struct terra_engine {
 			tl[t].xstart = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); tl[t].ystart = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
 			tl[t].first = h_first[t] - h_first[0]; tl[t].count = h_first[t+1] - h_first[t];
 		}
-		size_t const tb = ((size_t)n*sizeof(tree_tile_pod_t) + 255) & ~(size_t)255, pb = ((size_t)ns*sizeof(tree_splat_pod_t) + 255) & ~(size_t)255;
-		uint8_t *base = scratch<uint8_t>(s_ao, tb + pb + (size_t)n*W + n + 256);
-		tree_tile_pod_t *d_tiles = (tree_tile_pod_t *)base;
-		tree_splat_pod_t *d_par = (tree_splat_pod_t *)(base + tb);
-		uint8_t *d_rowf = base + tb + pb; // the simple form's per-row `updated`
-		if (!d_updated) {d_updated = d_rowf + (size_t)n*W;} // (written and not returned)
+		tree_tile_pod_t *d_tiles; tree_splat_pod_t *d_par; uint8_t *d_rowf, *d_upd; // d_rowf: the simple form's per-row `updated`
+		stage_layout_t lay;
+		lay.add(d_tiles, n); lay.add(d_par, ns); lay.add(d_rowf, (size_t)n*W); lay.add(d_upd, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		if (!d_updated) {d_updated = d_upd;} // (written and not returned)
 		be.h2d_async(d_tiles, tl.data(), (size_t)n*sizeof(tree_tile_pod_t));
 		tree_splat_in_t const *sp = d_splats ? d_splats + h_first[0] : nullptr;
 		float const dxv = DX_VAL, dyv = DY_VAL;
@@ -2380,18 +2378,13 @@ template<class BE> struct terra_engine {
 		c.dxv = DX_VAL; c.dyv = DY_VAL; c.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; c.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL;
 		c.S = (int)S; c.instanced = tp.instanced ? 1 : 0; c.num_insts = (uint32_t)tree_insts.size(); c.num_shared = dp.num_shared_trees;
 		c.pine_cap = pine_cap; c.decid_cap = decid_cap; c.list_cap = list_cap; c.src_cap = (uint32_t)src_cap;
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
-		size_t const fb = up((size_t)n*sizeof(tree_frame_t)), nb = up((size_t)n*9*sizeof(int32_t)), sb = up((size_t)n*src_cap*sizeof(tree_splat_in_t)), rb = up((size_t)n*sizeof(float)),
-			tb = up((size_t)n*sizeof(tree_tile_pod_t)), pb = up((size_t)n*list_cap*sizeof(tree_splat_pod_t));
-		uint8_t *base = scratch<uint8_t>(s_ao, fb + nb + sb + rb + tb + pb + (size_t)n*W + n + 256);
-		tree_frame_t *d_fr_w = (tree_frame_t *)base;
-		int32_t *d_nbr_w = (int32_t *)(base + fb);
-		tree_splat_in_t *d_src = (tree_splat_in_t *)(base + fb + nb);
-		if (!d_trmax) {d_trmax = (float *)(base + fb + nb + sb);} // (written and not returned)
-		tree_tile_pod_t *d_tiles = (tree_tile_pod_t *)(base + fb + nb + sb + rb);
-		tree_splat_pod_t *d_par = (tree_splat_pod_t *)(base + fb + nb + sb + rb + tb);
-		uint8_t *d_rowf = base + fb + nb + sb + rb + tb + pb; // the simple form's per-row `updated`
-		if (!d_updated) {d_updated = d_rowf + (size_t)n*W;}
+		tree_frame_t *d_fr_w; int32_t *d_nbr_w; tree_splat_in_t *d_src; float *d_trm; tree_tile_pod_t *d_tiles; tree_splat_pod_t *d_par; uint8_t *d_rowf, *d_upd; // d_rowf: the simple form's per-row `updated`
+		stage_layout_t lay;
+		lay.add(d_fr_w, n); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_src, (size_t)n*src_cap); lay.add(d_trm, n); lay.add(d_tiles, n); lay.add(d_par, (size_t)n*list_cap);
+		lay.add(d_rowf, (size_t)n*W); lay.add(d_upd, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		if (!d_trmax) {d_trmax = d_trm;} // (written and not returned)
+		if (!d_updated) {d_updated = d_upd;}
 		be.h2d_async(d_fr_w, fr.data(), (size_t)n*sizeof(tree_frame_t));
 		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
 		tree_frame_t const *d_fr = d_fr_w; int32_t const *d_nbr = d_nbr_w;
@@ -2507,18 +2500,15 @@ template<class BE> struct terra_engine {
 			fr[t].x = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); fr[t].y = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
 			fr[t].cx = -cfg.scene_x + DX_VAL*(float)add_wrap(add_wrap(x1, h), dxoff); fr[t].cy = -cfg.scene_y + DY_VAL*(float)add_wrap(add_wrap(y1, h), dyoff);
 		}
-		auto up = [](size_t b) {return (b + 255) & ~(size_t)255;};
 		uint32_t const idx_cap = std::max(pine_cap, decid_cap);
-		size_t const fb = up((size_t)n*sizeof(tree_edit_frame_t)), xb = up((size_t)n*idx_cap*4), cb = up((size_t)n*4),
-			npb = add_pine ? up((size_t)n*pine_cap*sizeof(tree_place_pod_t)) : 0, ndb = add_decid ? up((size_t)n*decid_cap*sizeof(decid_place_pod_t)) : 0;
-		uint8_t *base = scratch<uint8_t>(s_edit, fb + 256 + xb + 2*cb + npb + ndb + up(2*(size_t)n));
-		tree_edit_frame_t *d_fr_w = (tree_edit_frame_t *)base;
-		uint32_t *d_box = (uint32_t *)(base + fb);          // six words of the box, then two spare
-		uint32_t *d_idx = (uint32_t *)(base + fb + 256);    // [n][idx_cap]: the tail survivors of the group in hand
-		uint32_t *d_new_pc = (uint32_t *)(base + fb + 256 + xb), *d_new_dc = (uint32_t *)(base + fb + 256 + xb + cb);
-		tree_place_pod_t *d_new_pine = (tree_place_pod_t *)(base + fb + 256 + xb + 2*cb);
-		decid_place_pod_t *d_new_decid = (decid_place_pod_t *)(base + fb + 256 + xb + 2*cb + npb);
-		uint8_t *d_place_skip = (add_pine || add_decid) ? base + fb + 256 + xb + 2*cb + npb + ndb : nullptr; // [2][n], pine / palm first: skip, gated by gen_flags, or not hit -- what the brush placements run with
+		tree_edit_frame_t *d_fr_w; tree_place_pod_t *d_new_pine; decid_place_pod_t *d_new_decid;
+		uint32_t *d_box, *d_idx, *d_new_pc, *d_new_dc; // d_box: six words of the box, then two spare; d_idx [n][idx_cap]: the tail survivors of the group in hand
+		uint8_t *d_place_skip;                         // [2][n], pine / palm first: skip, gated by gen_flags, or not hit -- what the brush placements run with
+		stage_layout_t lay;
+		lay.add(d_fr_w, n); lay.add(d_box, 8); lay.add(d_idx, (size_t)n*idx_cap); lay.add(d_new_pc, n); lay.add(d_new_dc, n);
+		lay.add(d_new_pine, add_pine ? (size_t)n*pine_cap : 0); lay.add(d_new_decid, add_decid ? (size_t)n*decid_cap : 0); lay.add(d_place_skip, 2*(size_t)n);
+		lay.bind(scratch<uint8_t>(s_edit, lay.total));
+		if (!add_pine && !add_decid) {d_place_skip = nullptr;}
 		be.h2d_async(d_fr_w, fr.data(), (size_t)n*sizeof(tree_edit_frame_t));
 		tree_edit_frame_t const *d_fr = d_fr_w;
 		tree_inst_pod_t const *d_insts = (has_pine && tp.instanced) ? tree_insts_dev() : nullptr;
@@ -2693,6 +2683,28 @@ template<class BE> struct terra_engine {
 		}
 		return true;
 	}
+	// what every placement pass stages in s_ao before its kernel: the tile references, the running sums where the pass has some, its constants `c` (completed here with
+	// the device tables of `b`, its tree_place_consts_t part, and uploaded: the kernels read their constants from memory, by value they fill the scalar registers) and,
+	// where the pass reads densities, the four corner densities of every tile
+	template<class C> struct place_stage_t {C const *d_consts; tile_ref_pod_t const *d_refs; float *d_dens;};
+	template<class C> place_stage_t<C> stage_placement(int32_t const *tile_xy, uint32_t n, C &c, tree_place_consts_t &b, std::vector<float> const &sums, bool corner_dens) {
+		// only (tx, ty) of a tile reference is read here: no tables, no sort of the distinct columns and rows
+		std::vector<tile_ref_pod_t> refs(n);
+		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
+		float *d_sums, *d_dens; C *d_consts; tile_ref_pod_t *d_refs;
+		stage_layout_t lay;
+		lay.add(d_sums, sums.size()); lay.add(d_consts, 1); lay.add(d_refs, n); lay.add(d_dens, (size_t)n*4);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_refs, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
+		if (!sums.empty()) {be.h2d_async(d_sums, sums.data(), sums.size()*sizeof(float));}
+		b.st = sinTable_dev(); b.hist = height_histogram_dev(); b.sums = sums.empty() ? nullptr : d_sums;
+		be.h2d_async(d_consts, &c, sizeof(c));
+		if (corner_dens) {launch_corner_dens(b, d_refs, n, d_dens);}
+		return place_stage_t<C>{d_consts, d_refs, d_dens};
+	}
+	void launch_corner_dens(tree_place_consts_t const &cb, tile_ref_pod_t const *d_refs, uint32_t n, float *d_dens) { // (not in the template above: one kernel for the three passes)
+		be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cb, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});
+	}
 	void tiles_place_trees_dev(int32_t const *tile_xy, uint32_t n, int xoff2, int yoff2, uint8_t const *d_skip, terra_tile_stats const *d_stats, float const *brush,
 		uint32_t capacity, tree_place_pod_t *d_trees, uint32_t *d_counts)
 	{
@@ -2705,22 +2717,10 @@ template<class BE> struct terra_engine {
 		if (capacity && !d_trees) throw std::invalid_argument("tiles_place_trees: null d_trees");
 		if (((uintptr_t)d_trees & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0) throw std::invalid_argument("tiles_place_trees: d_trees and d_counts must be 4-byte aligned");
 		if (!any) {be.fill32(d_counts, 0u, n); return;}
-		// only (tx, ty) of a tile reference is read here: no tables, no sort of the distinct columns and rows
-		std::vector<tile_ref_pod_t> refs(n);
-		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
-		size_t const sb = (sums.size()*sizeof(float) + 255) & ~(size_t)255, kb = (sizeof(tree_place_consts_t) + 255) & ~(size_t)255, rb = ((size_t)n*sizeof(tile_ref_pod_t) + 255) & ~(size_t)255;
-		uint8_t *base = scratch<uint8_t>(s_ao, sb + kb + rb + (size_t)n*4*sizeof(float));
-		float *d_sums = (float *)base, *d_dens = (float *)(base + sb + kb + rb);
-		tree_place_consts_t *d_consts = (tree_place_consts_t *)(base + sb); // the kernel reads its constants from memory: by value they fill the scalar registers
-		tile_ref_pod_t *d_refs_w = (tile_ref_pod_t *)(base + sb + kb);
-		be.h2d_async(d_refs_w, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
-		tile_ref_pod_t const *d_refs = d_refs_w;
-		be.h2d_async(d_sums, sums.data(), sums.size()*sizeof(float));
-		c.st = sinTable_dev(); c.hist = height_histogram_dev(); c.sums = d_sums;
+		auto const sg = stage_placement(tile_xy, n, c, c, sums, !brush);
 		tree_place_consts_t const cc = c;
-		be.h2d_async(d_consts, &cc, sizeof(cc));
-		if (!brush) {be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cc, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});}
-		if (be.tile_place_trees(d_consts, d_refs, n, d_dens, d_skip, d_stats, capacity, d_trees, d_counts)) return;
+		tile_ref_pod_t const *d_refs = sg.d_refs; float *d_dens = sg.d_dens;
+		if (be.tile_place_trees(sg.d_consts, d_refs, n, sg.d_dens, d_skip, d_stats, capacity, d_trees, d_counts)) return;
 		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			tile_ref_pod_t const r = d_refs[t];
@@ -2794,20 +2794,10 @@ template<class BE> struct terra_engine {
 			throw std::invalid_argument("tiles_place_decid_trees: d_trees, d_counts, d_stats and d_zvals must be 4-byte aligned");
 		}
 		if (!any) {be.fill32(d_counts, 0u, n); return;}
-		std::vector<tile_ref_pod_t> refs(n);
-		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
-		size_t const kb = (sizeof(decid_place_consts_t) + 255) & ~(size_t)255, rb = ((size_t)n*sizeof(tile_ref_pod_t) + 255) & ~(size_t)255;
-		uint8_t *base = scratch<uint8_t>(s_ao, kb + rb + (size_t)n*4*sizeof(float));
-		decid_place_consts_t *d_consts = (decid_place_consts_t *)base; // the kernel reads its constants from memory, as k_tree_place does
-		tile_ref_pod_t *d_refs_w = (tile_ref_pod_t *)(base + kb);
-		float *d_dens = (float *)(base + kb + rb);
-		be.h2d_async(d_refs_w, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
-		tile_ref_pod_t const *d_refs = d_refs_w;
-		c.b.st = sinTable_dev(); c.b.hist = height_histogram_dev();
+		auto const sg = stage_placement(tile_xy, n, c, c.b, std::vector<float>(), !brush);
 		decid_place_consts_t const cc = c;
-		be.h2d_async(d_consts, &cc, sizeof(cc));
-		if (!brush) {tree_place_consts_t const cb = c.b; be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cb, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});}
-		if (be.tile_place_decid_trees(d_consts, d_refs, n, d_dens, d_skip, d_stats, d_zvals, capacity, d_trees, d_counts)) return;
+		tile_ref_pod_t const *d_refs = sg.d_refs; float *d_dens = sg.d_dens;
+		if (be.tile_place_decid_trees(sg.d_consts, d_refs, n, sg.d_dens, d_skip, d_stats, d_zvals, capacity, d_trees, d_counts)) return;
 		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
 		size_t const zsz = (size_t)(cc.b.S + 2)*(size_t)(cc.b.S + 2);
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
@@ -2863,20 +2853,10 @@ template<class BE> struct terra_engine {
 		if (((uintptr_t)d_objs & 3u) != 0 || ((uintptr_t)d_counts & 3u) != 0 || ((uintptr_t)d_kind_counts & 3u) != 0) {
 			throw std::invalid_argument("tiles_place_scenery: d_objs, d_counts and d_kind_counts must be 4-byte aligned");
 		}
-		std::vector<tile_ref_pod_t> refs(n);
-		for (uint32_t t = 0; t < n; ++t) {refs[t] = tile_ref_pod_t{tile_xy[2*t], tile_xy[2*t+1], 0u, 0u};}
-		size_t const kb = (sizeof(scenery_place_consts_t) + 255) & ~(size_t)255, rb = ((size_t)n*sizeof(tile_ref_pod_t) + 255) & ~(size_t)255;
-		uint8_t *base = scratch<uint8_t>(s_ao, kb + rb + (size_t)n*4*sizeof(float));
-		scenery_place_consts_t *d_consts = (scenery_place_consts_t *)base; // the kernel reads its constants from memory, as k_tree_place does
-		tile_ref_pod_t *d_refs_w = (tile_ref_pod_t *)(base + kb);
-		float *d_dens = (float *)(base + kb + rb);
-		be.h2d_async(d_refs_w, refs.data(), (size_t)n*sizeof(tile_ref_pod_t));
-		tile_ref_pod_t const *d_refs = d_refs_w;
-		c.b.st = sinTable_dev(); c.b.hist = height_histogram_dev();
+		auto const sg = stage_placement(tile_xy, n, c, c.b, std::vector<float>(), true);
 		scenery_place_consts_t const cc = c;
-		be.h2d_async(d_consts, &cc, sizeof(cc));
-		{tree_place_consts_t const cb = c.b; be.launch((size_t)n*4, [=] TERRA_LAMBDA (size_t i) {tile_ref_pod_t const r = d_refs[i >> 2]; d_dens[i] = tree_veg_corner(cb, r.tx, r.ty, (unsigned)i & 1u, ((unsigned)i >> 1) & 1u);});}
-		if (be.tile_place_scenery(d_consts, d_refs, n, d_dens, d_skip, capacity, d_objs, d_counts, d_kind_counts)) return;
+		tile_ref_pod_t const *d_refs = sg.d_refs; float *d_dens = sg.d_dens;
+		if (be.tile_place_scenery(sg.d_consts, d_refs, n, sg.d_dens, d_skip, capacity, d_objs, d_counts, d_kind_counts)) return;
 		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			tile_ref_pod_t const r = d_refs[t];

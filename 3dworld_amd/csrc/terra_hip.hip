@@ -90,7 +90,7 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		if (bytes == 0) return;
 		use();
 		if (!pin && !pin_failed) {pin_bytes = (size_t)8 << 20; if (hipHostMalloc((void **)&pin, pin_bytes, hipHostMallocDefault) != hipSuccess) {pin = nullptr; pin_bytes = 0; pin_failed = true; (void)hipGetLastError();}}
-		size_t const need = (bytes + 255) & ~(size_t)255;
+		size_t const need = terra::stage_up(bytes);
 		if (!pin || need > pin_bytes/2) {h2d(d, h, bytes); return;}
 		if (pin_off + need > pin_bytes) {TERRA_HIP_CHECK(hipStreamSynchronize(stream)); pin_off = 0;}
 		memcpy(pin + pin_off, h, bytes);

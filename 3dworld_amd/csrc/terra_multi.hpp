@@ -146,9 +146,9 @@ inline int multi_tiles_mesh_shadows_dev(terra_multi *m, int32_t const *tile_xy, 
 					txy[2*k] = tile_xy[2*ti]; txy[2*k+1] = tile_xy[2*ti+1];
 					// sh_in_x: from the tile one row toward the light in the same column -- always in this strip; when it lies in an EARLIER chunk its outgoing edge is
 					// gathered in (inside the chunk the engine hands the edges on itself)
-					auto up = L.index.find(std::make_pair(tile_xy[2*ti], tile_xy[2*ti+1] + L.sy));
-					if (up != L.index.end() && L.pos[up->second] < first) {
-						gl.push_back(shadow_gather_t{(unsigned long long)(uintptr_t)(d_eout + ((size_t)L.pos[up->second]*2 + 0)*zv), (first + k)*2 + 0, 0});
+					auto const above = L.index.find(std::make_pair(tile_xy[2*ti], tile_xy[2*ti+1] + L.sy));
+					if (above != L.index.end() && L.pos[above->second] < first) {
+						gl.push_back(shadow_gather_t{(unsigned long long)(uintptr_t)(d_eout + ((size_t)L.pos[above->second]*2 + 0)*zv), (first + k)*2 + 0, 0});
 						present[(size_t)(first + k)*2 + 0] = 1;
 					}
 					// sh_in_y: from the tile one column toward the light; when that tile belongs to the previous strip its edge lives on that strip's device
