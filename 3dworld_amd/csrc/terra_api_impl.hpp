@@ -825,6 +825,64 @@ int terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
 		st.end();
 	TERRA_CATCH
 }
+int terra_set_flower_params(terra_ctx *ctx, const terra_flower_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_flower_params(*params); TERRA_CATCH
+}
+int terra_get_flower_params(terra_ctx *ctx, terra_flower_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	*out = ctx->eng.fp; return TERRA_OK;
+}
+static_assert(sizeof(terra_flower) == 48 && sizeof(terra::flower_pod_t) == 48, "terra_flower layout: flower_t (src/grass.h:80-88)");
+int terra_tiles_place_flowers_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const uint8_t *d_skip, const uint8_t *d_weights, uint32_t capacity,
+                                  terra_flower *d_flowers, uint32_t *d_aux, uint32_t *d_counts) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !d_counts || (capacity && !d_flowers))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_place_flowers_dev(tile_xy, n, d_skip, d_weights, capacity, (terra::flower_pod_t *)d_flowers, d_aux, d_counts); TERRA_CATCH
+}
+int terra_tiles_place_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const uint8_t *h_skip, const uint8_t *h_weights, uint32_t capacity,
+                              terra_flower *h_flowers, uint32_t *h_aux, uint32_t *h_counts) {
+	TERRA_CHECK_CTX if (n && (!tile_xy || !h_counts || (capacity && !h_flowers))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size(); // (before the arrays are read: they are sized by S)
+		if (n == 0) return TERRA_OK;
+		size_t const S = ctx->eng.tile_size();
+		terra_stage st(ctx->eng);
+		int const r = st.temp((size_t)n*capacity*sizeof(terra_flower)), a = st.add(nullptr, nullptr, (size_t)n*capacity*4, h_aux != nullptr), c = st.temp((size_t)n*4),
+			k = st.opt_in(h_skip, n), w = st.opt_in(ctx->eng.flowers_skip_generate() ? nullptr : h_weights, (size_t)n*(S + 1)*(S + 1)*4); // (skip_generate: the weights are not read)
+		st.begin();
+		ctx->eng.tiles_place_flowers_dev(tile_xy, n, st.dev<uint8_t>(k), st.dev<uint8_t>(w), capacity, st.dev<terra::flower_pod_t>(r), st.dev<uint32_t>(a), st.dev<uint32_t>(c));
+		st.end_counted(r, c, h_flowers, h_counts, n, capacity);
+		if (h_aux) {st.end_counted(a, c, h_aux, h_counts, n, capacity);}
+	TERRA_CATCH
+}
+int terra_tiles_edit_flowers_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *d_generated,
+                                 const terra_grass_brush *brush, const uint8_t *d_updated, const uint32_t *d_ranges, const uint8_t *d_weights, uint32_t capacity,
+                                 terra_flower *d_flowers, uint32_t *d_aux, uint32_t *d_counts, uint8_t *d_status) {
+	TERRA_CHECK_CTX if (!brush || (n && (!tile_xy || !d_updated || !d_counts || !d_status || (capacity && !d_flowers)))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.tiles_edit_flowers_dev(tile_xy, n, dxoff, dyoff, d_generated, brush->pos, brush->radius, brush->add_grass != 0, brush->shape, d_updated, d_ranges,
+		d_weights, capacity, (terra::flower_pod_t *)d_flowers, d_aux, d_counts, d_status); TERRA_CATCH
+}
+int terra_tiles_edit_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *h_generated,
+                             const terra_grass_brush *brush, const uint8_t *h_updated, const uint32_t *h_ranges, const uint8_t *h_weights, uint32_t capacity,
+                             terra_flower *h_flowers, uint32_t *h_aux, uint32_t *h_counts, uint8_t *h_status) {
+	TERRA_CHECK_CTX if (!brush || (n && (!tile_xy || !h_updated || !h_counts || !h_status || (capacity && !h_flowers)))) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY
+		ctx->eng.require_scene();
+		ctx->eng.require_tile_size(); // (before the arrays are read: they are sized by S)
+		if (n == 0) return TERRA_OK;
+		size_t const S = ctx->eng.tile_size();
+		bool const add = brush->add_grass != 0;
+		terra_stage st(ctx->eng);
+		int const r = st.inout(h_flowers, (size_t)n*capacity*sizeof(terra_flower)), a = st.inout(h_aux, (size_t)n*capacity*4, h_aux != nullptr), c = st.inout(h_counts, (size_t)n*4),
+			g = st.opt_in(h_generated, n), u = st.in(h_updated, n), q = st.opt_in(h_ranges, (size_t)n*16), w = st.opt_in(add ? h_weights : nullptr, (size_t)n*(S + 1)*(S + 1)*4),
+			s = st.out(h_status, n);
+		st.begin();
+		ctx->eng.tiles_edit_flowers_dev(tile_xy, n, dxoff, dyoff, st.dev<uint8_t>(g), brush->pos, brush->radius, add, brush->shape, st.dev<uint8_t>(u), st.dev<uint32_t>(q),
+			st.dev<uint8_t>(w), capacity, st.dev<terra::flower_pod_t>(r), st.dev<uint32_t>(a), st.dev<uint32_t>(c), st.dev<uint8_t>(s));
+		st.end();
+	TERRA_CATCH
+}
 int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
 	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.set_tree_size_params(*params); TERRA_CATCH

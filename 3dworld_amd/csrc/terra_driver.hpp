@@ -16,6 +16,7 @@
 #include "terra_treeplace.hpp"
 #include "terra_decidplace.hpp"
 #include "terra_sceneryplace.hpp"
+#include "terra_flowers.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_stage.hpp"
@@ -728,6 +729,15 @@ template<class BE> struct terra_engine {
 	void set_scenery_params(terra_scenery_params const &p) {
 		if (p.use_voxel_rocks < 0) throw std::invalid_argument("terra_set_scenery_params: use_voxel_rocks must be >= 0");
 		sp = p;
+	}
+	// what flower_manager_t reads: flower_density, grass_length, grass_width (src/grass.cpp:15), flower_color (src/3DWorld.cpp:124), no_grass()
+	terra_flower_params fp = {0.0f, 0.02f, 0.002f, {0.0f, 0.0f, 0.0f, 0.0f}, 0};
+	void set_flower_params(terra_flower_params const &p) {
+		for (float v : {p.flower_density, p.grass_length, p.grass_width}) {
+			if (!(v >= 0.0f) || !std::isfinite(v)) throw std::invalid_argument("terra_set_flower_params: flower_density, grass_length and grass_width must be finite and >= 0");
+		}
+		if (p.flower_density > FLOWER_DENSITY_MAX) throw std::invalid_argument("terra_set_flower_params: flower_density must be <= 1024 (a tile's count is 32 bits)");
+		fp = p;
 	}
 	// what the trees' radii read beyond terra_tree_params (small_tree's constructor and get_pine_tree_radius): tree_height_scale, sm_tree_scale, pine_tree_radius_scale
 	terra_tree_size_params tsp = {1.0f, 1.0f, 1.0f};
@@ -1588,11 +1598,12 @@ template<class BE> struct terra_engine {
 	// Returns the device copy of the tile references (valid until the next tile call of this context).
 	tile_ref_pod_t const *tile_fields_dev(int32_t const *tile_xy, uint32_t n, uint32_t tw, int shift, float *d_out, float xy_scale = 1.0f, // xy_scale 0: only the tile references
 		bool glac = true, bool force_sine = false, int min_start_sin = 0, // enable_glaciate() after build_arrays; build_arrays' force_sine_mode; eval_index's min_start_sin
-		tile_band_t const *band = nullptr, bool *band_used = nullptr)         // band: only these cells of every tile's field, if the backend can (*band_used); else the whole fields
+		tile_band_t const *band = nullptr, bool *band_used = nullptr,         // band: only these cells of every tile's field, if the backend can (*band_used); else the whole fields
+		float y_scale = 0.0f)                                                 // a scale of its own for the y axis (the flowers' fields); 0: xy_scale
 	{
 		uint32_t const size = tile_size(), zv = tw;
 		if (band_used) {*band_used = false;}
-		float const fdx = xy_scale*DX_VAL, fdy = xy_scale*DY_VAL; // setup_height_gen_async: build_arrays(..., xy_scale*DX_VAL, xy_scale*DY_VAL, ...)
+		float const fdx = xy_scale*DX_VAL, fdy = ((y_scale != 0.0f) ? y_scale : xy_scale)*DY_VAL; // setup_height_gen_async: build_arrays(..., xy_scale*DX_VAL, xy_scale*DY_VAL, ...)
 		// a tile's X table depends only on its tile x, its Y table only on its tile y: build each distinct one once
 		std::vector<int32_t> ux, uy;
 		for (uint32_t i = 0; i < n; ++i) {ux.push_back(tile_xy[2*i]); uy.push_back(tile_xy[2*i+1]);}
@@ -2877,6 +2888,110 @@ template<class BE> struct terra_engine {
 			}
 			d_counts[t] = count;
 			if (d_kind_counts) {for (int k = 0; k < SCENERY_KINDS; ++k) {d_kind_counts[t*SCENERY_KINDS + k] = kinds[k];}}
+		});
+	}
+
+	// ---- flowers (terra_flowers.hpp): flower_tile_manager_t::gen_flowers for every tile of the batch, as tile_t::draw_flowers calls it (tsize_bitshift 0), and its
+	// upkeep after a grass stroke -- update_subrange or clear_within on the resident records, as tile_t::add_or_remove_grass_at calls them.  Both read the weights
+	// of terra_tiles_tree_weights and generate the two density fields internally.
+	bool flowers_skip_generate() const {return fp.no_grass != 0 || fp.flower_density == 0.0f;} // skip_generate() (src/grass.cpp:752-754) without `generated`, the caller's
+	flower_consts_t flower_consts() const {
+		flower_consts_t c;
+		c.S = (int)tile_size(); c.DX_VAL = DX_VAL; c.DY_VAL = DY_VAL; c.DX_VAL_INV = DX_VAL_INV; c.DY_VAL_INV = DY_VAL_INV;
+		c.flower_density = fp.flower_density; c.grass_length = fp.grass_length; c.grass_width = fp.grass_width;
+		for (int k = 0; k < 4; ++k) {c.color[k] = fp.flower_color[k];}
+		c.fixed_color = (fp.flower_color[3] > 0.0f) ? 1 : 0;
+		float const FLOWER_DIST_THRESH = 0.5f; // get_median_height(FLOWER_DIST_THRESH) (src/mesh_gen.cpp:487-491)
+		c.hthresh = height_histogram.empty() ? FLOWER_DIST_THRESH :
+			height_histogram[(size_t)imax(0, imin((int)height_histogram.size() - 1, f2i_x86((float)height_histogram.size()*FLOWER_DIST_THRESH)))];
+		c.zs = 0.2*(double)zmax_est;
+		return c;
+	}
+	// gen_density_cache (src/grass.cpp:840-845): build_arrays(x1, y1, fds*DX_VAL*DX_VAL, fds*DY_VAL*DY_VAL, S, S, 0, force_sine_mode=1) for fds = 500 and 650, read
+	// with eval_index(x, y, 50).  x1 is the tile's own: tile_fields_dev subtracts MESH_X_SIZE/2, the shift adds it back.  -> d_den, d_col: [n][S][S]
+	tile_ref_pod_t const *flower_density_fields(int32_t const *tile_xy, uint32_t n, float *d_den, float *d_col) {
+		uint32_t const S = tile_size();
+		tile_ref_pod_t const *d_refs = nullptr;
+		for (unsigned i = 0; i < 2; ++i) {
+			float const fds = (float)(500.0*(1.0 + 0.3*(double)i)); // fds*DX_VAL*DX_VAL groups as (fds*DX_VAL)*DX_VAL: one scale per axis
+			d_refs = tile_fields_dev(tile_xy, n, S, -(cfg.mesh_x/2), i ? d_col : d_den, fds*DX_VAL, false, true, FLOWER_START_EVAL_SIN, nullptr, nullptr, fds*DY_VAL);
+		}
+		return d_refs;
+	}
+	void tiles_place_flowers_dev(int32_t const *tile_xy, uint32_t n, uint8_t const *d_skip, uint8_t const *d_weights, uint32_t capacity, flower_pod_t *d_flowers,
+		uint32_t *d_aux, uint32_t *d_counts)
+	{
+		require_scene();
+		require_tile_size();
+		if (n == 0) return;
+		if (capacity && !d_flowers) throw std::invalid_argument("tiles_place_flowers: null d_flowers");
+		if ((((uintptr_t)d_flowers | (uintptr_t)d_aux | (uintptr_t)d_counts) & 3u) != 0) throw std::invalid_argument("tiles_place_flowers: d_flowers, d_aux and d_counts must be 4-byte aligned");
+		if (flowers_skip_generate()) {be.fill32(d_counts, 0u, n); return;} // (the weights are not read: they may be null)
+		if (!d_weights) throw std::invalid_argument("tiles_place_flowers: null d_weights");
+		uint32_t const S = tile_size();
+		size_t const ncell = (size_t)S*S, nw = (size_t)(S + 1)*(S + 1)*4;
+		float *d_den = scratch<float>(s_ao, 2*(size_t)n*ncell), *d_col = d_den + (size_t)n*ncell;
+		tile_ref_pod_t const *d_refs = flower_density_fields(tile_xy, n, d_den, d_col);
+		flower_consts_t const c = flower_consts();
+		if (be.tile_place_flowers(c, d_refs, n, d_skip, d_weights, d_den, d_col, capacity, d_flowers, d_aux, d_counts)) return;
+		// the simple form: one logical thread per tile runs the reference's loop
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			tile_ref_pod_t const r = d_refs[t];
+			uint32_t count = 0;
+			if (!(d_skip && d_skip[t])) {
+				count = flower_gen_serial(c, r.tx, r.ty, 0u, 0u, S, S, d_weights + t*nw, d_den + t*ncell, d_col + t*ncell, capacity, d_flowers + t*capacity,
+					d_aux ? d_aux + t*capacity : nullptr, 0u);
+			}
+			d_counts[t] = count;
+		});
+	}
+	void tiles_edit_flowers_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, uint8_t const *d_generated, float const pos[3], float radius, bool add, int shape,
+		uint8_t const *d_updated, uint32_t const *d_ranges, uint8_t const *d_weights, uint32_t capacity, flower_pod_t *d_flowers, uint32_t *d_aux, uint32_t *d_counts,
+		uint8_t *d_status)
+	{
+		require_scene();
+		require_tile_size();
+		if (shape < 0 || shape >= NUM_BSHAPES) throw std::invalid_argument("tiles_edit_flowers: bad brush shape");
+		if (n == 0) return;
+		if (capacity && !d_flowers) throw std::invalid_argument("tiles_edit_flowers: null d_flowers");
+		if (add && (!d_ranges || !d_weights)) throw std::invalid_argument("tiles_edit_flowers: an adding stroke needs d_ranges and d_weights");
+		if ((((uintptr_t)d_flowers | (uintptr_t)d_aux | (uintptr_t)d_counts | (uintptr_t)d_ranges) & 3u) != 0) {
+			throw std::invalid_argument("tiles_edit_flowers: d_flowers, d_aux, d_counts and d_ranges must be 4-byte aligned");
+		}
+		uint32_t const S = tile_size();
+		size_t const ncell = (size_t)S*S, nw = (size_t)(S + 1)*(S + 1)*4;
+		flower_edit_consts_t c;
+		c.f = flower_consts();
+		c.add = add ? 1 : 0; c.is_square = (shape == BSHAPE_CONST_SQ) ? 1 : 0; c.dxoff = dxoff; c.dyoff = dyoff;
+		c.px = pos[0]; c.py = pos[1]; c.radius = radius; c.xss = cfg.scene_x; c.yss = cfg.scene_y;
+		// the two density fields (adding only), one index per record slot for the removal's parallel form, one byte per tile for what the edit does to it
+		float *d_den, *d_col; uint32_t *d_idx; uint8_t *d_kind;
+		stage_layout_t lay;
+		lay.add(d_den, add ? (size_t)n*ncell : 0); lay.add(d_col, add ? (size_t)n*ncell : 0); lay.add(d_idx, (size_t)n*capacity); lay.add(d_kind, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		tile_ref_pod_t const *d_refs = add ? flower_density_fields(tile_xy, n, d_den, d_col) : tile_fields_dev(tile_xy, n, S, 0, nullptr, 0.0f);
+		if (be.tile_edit_flowers(c, d_refs, n, d_generated, d_updated, d_ranges, d_weights, d_den, d_col, capacity, d_flowers, d_aux, d_counts, d_status, d_idx, d_kind)) return;
+		// the simple form: one logical thread per tile, the removal as the literal remove_element loop, then the reference's cell loop behind the survivors
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			tile_ref_pod_t const r = d_refs[t];
+			uint32_t rg[4] = {0u, 0u, 0u, 0u};
+			if (d_ranges) {for (int k = 0; k < 4; ++k) {rg[k] = d_ranges[4*t + k];}}
+			int const kind = flower_edit_kind(c, d_updated[t], d_generated ? d_generated[t] : (uint8_t)1, rg);
+			d_status[t] = (kind == FLOWER_EDIT_NONE) ? 0 : ((kind == FLOWER_EDIT_REFUSED) ? 2 : 1);
+			if (kind != FLOWER_EDIT_ADD && kind != FLOWER_EDIT_REMOVE) return;
+			flower_pod_t *const v = d_flowers + t*capacity;
+			uint32_t *const aux = d_aux ? d_aux + t*capacity : nullptr;
+			uint32_t count = min_u32(d_counts[t], capacity);
+			if (kind == FLOWER_EDIT_ADD) {
+				count = flower_remove_serial(v, aux, count, [&](flower_pod_t const &f) {return flower_in_range(c.f, f, (int)rg[0], (int)rg[1], (int)rg[2], (int)rg[3]);});
+				count = flower_gen_serial(c.f, r.tx, r.ty, rg[0], rg[1], rg[2], rg[3], d_weights + t*nw, d_den + t*ncell, d_col + t*ncell, capacity, v, aux, count);
+			}
+			else {
+				float px, py;
+				flower_brush_local(c, r.tx, r.ty, px, py);
+				count = flower_remove_serial(v, aux, count, [&](flower_pod_t const &f) {return flower_in_brush(f, px, py, c.radius, c.is_square != 0);});
+			}
+			d_counts[t] = count;
 		});
 	}
 

@@ -655,6 +655,32 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// flowers: one wave per tile (k_flowers_place)
+	bool tile_place_flowers(terra::flower_consts_t const &c, terra::tile_ref_pod_t const *tiles, uint32_t n, uint8_t const *skip, uint8_t const *weights, float const *den,
+		float const *col, uint32_t capacity, terra::flower_pod_t *flowers, uint32_t *aux, uint32_t *counts)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_flowers_place<false>, dim3(n), dim3(64), 0, stream, c, tiles, skip, (uint8_t const *)nullptr, (uint32_t const *)nullptr, weights, den, col,
+			capacity, flowers, aux, counts);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
+	// the flowers' upkeep after a grass stroke: k_flowers_remove once per tile, then, when adding, k_flowers_place over the strokes' rectangles
+	bool tile_edit_flowers(terra::flower_edit_consts_t const &c, terra::tile_ref_pod_t const *tiles, uint32_t n, uint8_t const *generated, uint8_t const *updated,
+		uint32_t const *ranges, uint8_t const *weights, float const *den, float const *col, uint32_t capacity, terra::flower_pod_t *flowers, uint32_t *aux, uint32_t *counts,
+		uint8_t *status, uint32_t *idx, uint8_t *kind)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_flowers_remove, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, generated, updated, ranges, capacity, flowers, aux, counts, status, idx, kind);
+		if (c.add) {
+			hipLaunchKernelGGL(terra::k_flowers_place<true>, dim3(n), dim3(64), 0, stream, c.f, tiles, (uint8_t const *)nullptr, (uint8_t const *)kind, ranges, weights, den, col,
+				capacity, flowers, aux, counts);
+		}
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

@@ -1744,6 +1744,201 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_c
 	}
 }
 
+// ------------------------------------------------------------------ flowers (flower_tile_manager_t::gen_flowers / update_subrange / clear_within, src/grass.cpp:859-926; terra_flowers.hpp)
+// k_flowers_place: ONE WAVE per tile.  The reference seeds its generator once per tile and draws once for a rejected candidate and nine times (eight with a fixed
+// colour) for an accepted one, so where candidate i's test draw lies in the stream depends on every acceptance before it: a literal walk is a chain of generator
+// steps as long as the tile's stream.  Both recurrences are multiplications modulo a prime, so the state k draws on is one modular multiplication away (lcg_jump),
+// and the wave speculates:
+//   - the cells of the rectangle 64 at a time, row-major; a prefix sum over the lanes numbers their candidates in loop order, and the chunk's candidates are laid out
+//     in LDS in that order with their cell and its dval;
+//   - the candidates FLW_B = 10 at a time.  Candidate l of a block can have 0 .. l acceptances before it, so its test draw lies at one of l + 1 stream offsets
+//     l + E*a (E = the further draws of an acceptance): 55 (l, a) pairs, one per lane.  Every lane jumps to its pair's state, runs the density test there and the
+//     ballot is the block's whole outcome table in two scalar registers;
+//   - the true path is then ten scalar steps over that mask (bit l(l+1)/2 + a, a += bit), not ten dependent generator steps and double compares;
+//   - the accepted candidates' test states go into a queue in LDS; whenever it cannot take another block (and at the end) every lane takes one entry, draws the
+//     rest of its record and writes it at queue order behind the records so far.
+// No window of states in LDS: a lane reaches its state with one multiplication each of the two seeds by a power from a 91-entry table that the wave computes once.
+// The update_subrange generation is the same kernel over the stroke's rectangle with that call's seed, behind the survivors k_flowers_remove left.
+constexpr uint32_t FLW_B = 10, FLW_PAIRS = FLW_B*(FLW_B + 1)/2, FLW_POW = FLW_B*9 + 1, FLW_Q = 64, FLW_MAP = 256;
+template<bool EDIT> __global__ __launch_bounds__(64) void k_flowers_place(flower_consts_t c, tile_ref_pod_t const *__restrict__ tiles, uint8_t const *__restrict__ skip,
+	uint8_t const *__restrict__ kind, uint32_t const *__restrict__ ranges, uint8_t const *__restrict__ weights, float const *__restrict__ den, float const *__restrict__ col,
+	uint32_t capacity, flower_pod_t *flowers, uint32_t *aux, uint32_t *counts)
+{
+	__shared__ uint32_t s_p1[FLW_POW], s_p2[FLW_POW]; // A1^k mod M1, A2^k mod M2
+	__shared__ uint32_t s_pre[65];                    // candidates before cell `lane` of the chunk; [64]: all of them (read only by a chunk with more than FLW_MAP)
+	__shared__ float s_cd[FLW_MAP];                   // the chunk's candidates in loop order: dval of the cell ..
+	__shared__ uint32_t s_cc[FLW_MAP];                // .. and the cell
+	__shared__ uint32_t s_q[3*FLW_Q];                 // accepted candidates: the two seeds at the test draw, the cell
+	uint32_t const t = blockIdx.x, lane = threadIdx.x;
+	uint32_t const S = (uint32_t)c.S;
+	uint32_t xl = 0, yl = 0, xh = S, yh = S, count = 0;
+	if (EDIT) {
+		if (kind[t] != FLOWER_EDIT_ADD) return; // (uniform)
+		xl = ranges[4*t]; yl = ranges[4*t + 1]; xh = ranges[4*t + 2]; yh = ranges[4*t + 3]; // inside the tile: flower_edit_kind
+		count = counts[t];                                                                 // the survivors
+	}
+	else if (skip && skip[t]) {
+		if (lane == 0) {counts[t] = 0;}
+		return;
+	}
+	for (uint32_t k = lane; k < FLW_POW; k += 64) {s_p1[k] = lcg_powmod<LCG_M1>(LCG_A1, k); s_p2[k] = lcg_powmod<LCG_M2>(LCG_A2, k);}
+	tile_ref_pod_t const r = tiles[t];
+	uint32_t const nx = xh - xl, ncells = nx*(yh - yl);
+	uint8_t const *const w = weights + (size_t)t*(S + 1)*(S + 1)*4;
+	float const *const dn = den + (size_t)t*S*S, *const cl = col + (size_t)t*S*S;
+	flower_pod_t *const out = flowers + (size_t)t*capacity;
+	uint32_t *const out_aux = aux ? aux + (size_t)t*capacity : nullptr;
+	uint32_t const E = c.fixed_color ? 7u : 8u; // the draws of an accepted candidate after its test
+	// lane p < 55 owns the pair (l, a): candidate l of a block with a acceptances before it
+	uint32_t pl = 0;
+	while ((pl + 1)*(pl + 2)/2 <= lane) {++pl;}
+	uint32_t const pa = lane - pl*(pl + 1)/2;
+	bool const is_pair = lane < FLW_PAIRS;
+	tree_rgen_t cur; // the state that stands for the next draw of the stream
+	flower_seed(c.S, r.tx, r.ty, (int)xl, (int)yl, cur);
+	cur.advance(); // the first step literally: the seeds may lie outside [0, m)
+	uint32_t qn = 0; // (uniform)
+	auto flush = [&]() {
+		__syncthreads();
+		if (lane < qn) {
+			tree_rgen_t rg; rg.rseed1 = (int32_t)s_q[lane]; rg.rseed2 = (int32_t)s_q[FLW_Q + lane];
+			uint32_t const cell = s_q[2*FLW_Q + lane], x = cell & 1023u, y = cell >> 10;
+			flower_pod_t o;
+			uint32_t const cf = flower_record(c, (int)x, (int)y, cl[(size_t)y*S + x], rg, o);
+			if (count + lane < capacity) {out[count + lane] = o; if (out_aux) {out_aux[count + lane] = flower_aux(x, y, cf);}}
+		}
+		count += qn; qn = 0;
+		__syncthreads();
+	};
+	__syncthreads(); // the power tables
+	for (uint32_t base = 0; base < ncells; base += 64) {
+		uint32_t const k = base + lane;
+		uint32_t npb = 0, cell = 0; float dval = 0.0f;
+		if (k < ncells) {
+			uint32_t const y = yl + k/nx, x = xl + k%nx;
+			npb = flower_num_per_bin(c, w[4*((size_t)y*(S + 1) + x) + 2]);
+			if (npb) {dval = dn[(size_t)y*S + x];}
+			cell = x | (y << 10);
+		}
+		uint32_t incl = npb; // inclusive prefix over the lanes
+		for (uint32_t d = 1; d < 64; d <<= 1) {uint32_t const v = __shfl_up(incl, d); if (lane >= d) {incl += v;}}
+		uint32_t const total = __builtin_amdgcn_readfirstlane(__shfl(incl, 63));
+		if (total == 0) continue;
+		// a chunk's candidates are laid out in LDS, so that a lane finds its candidate's cell with one read; a chunk with more of them than the table holds (five and
+		// more candidates a cell) searches the prefix sums instead
+		bool const mapped = total <= FLW_MAP; // (uniform)
+		if (mapped) {for (uint32_t i = 0; i < npb; ++i) {s_cd[incl - npb + i] = dval; s_cc[incl - npb + i] = cell;}}
+		else {
+			s_pre[lane] = incl - npb;
+			if (lane == 63) {s_pre[64] = incl;}
+		}
+		__syncthreads();
+		for (uint32_t kb = 0; kb < total; kb += FLW_B) {
+			uint32_t const nb = (total - kb < FLW_B) ? total - kb : FLW_B;
+			bool const live = is_pair && pl < nb;
+			uint32_t owner = 0; // (searching form) the lane that holds the cell of candidate kb + l: the last one whose prefix is <= kb + l
+			float dv = 0.0f;
+			if (mapped) {if (live) {dv = s_cd[kb + pl];}}
+			else {
+				if (live) {
+					uint32_t const ci = kb + pl;
+					uint32_t lo = 0, hi = 64; // s_pre[lo] <= ci < s_pre[hi]
+					while (hi - lo > 1) {uint32_t const mid = (lo + hi) >> 1; if (s_pre[mid] <= ci) {lo = mid;} else {hi = mid;}}
+					owner = lo;
+				}
+				dv = __shfl(dval, owner);
+			}
+			bool acc = false;
+			if (live) {
+				uint32_t const off = pl + E*pa;
+				acc = !((double)dv + c.zs*(double)lcg_state_signed_rand_float(lcg_jump(cur, s_p1[off], s_p2[off])) > (double)c.hthresh); // flower_candidate_accepted on that state
+			}
+			unsigned long long const mask = __ballot(acc);
+			uint32_t a = 0, my_a = 0; bool my_acc = false;
+#pragma unroll
+			for (uint32_t l = 0; l < FLW_B; ++l) {
+				uint32_t const bit = (l < nb) ? (uint32_t)((mask >> (l*(l + 1)/2 + a)) & 1ull) : 0u;
+				if (lane == l) {my_a = a; my_acc = bit != 0;}
+				a += bit;
+			}
+			a = __builtin_amdgcn_readfirstlane(a);
+			// lane l < nb holds candidate l's outcome; (searching form) its cell is the one pair (l, 0) found, lane l(l+1)/2
+			uint32_t my_cell;
+			if (mapped) {my_cell = (lane < nb) ? s_cc[kb + lane] : 0u;}
+			else {
+				uint32_t const lc = (lane < FLW_B) ? lane : 0u;
+				my_cell = __shfl(cell, __shfl(owner, lc*(lc + 1)/2));
+			}
+			if (my_acc) {
+				uint32_t const off = lane + E*my_a;
+				tree_rgen_t const st = lcg_jump(cur, s_p1[off], s_p2[off]);
+				s_q[qn + my_a] = (uint32_t)st.rseed1; s_q[FLW_Q + qn + my_a] = (uint32_t)st.rseed2; s_q[2*FLW_Q + qn + my_a] = my_cell;
+			}
+			qn += a;
+			cur = lcg_jump(cur, s_p1[nb + E*a], s_p2[nb + E*a]);
+			if (qn + FLW_B > FLW_Q) {flush();}
+		}
+		__syncthreads(); // the next chunk rewrites the candidate table
+	}
+	if (qn) {flush();}
+	if (lane == 0) {counts[t] = count;}
+}
+// k_flowers_remove: a workgroup per tile decides what the stroke does to the tile (flower_edit_kind), writes its status and runs the removal loop of update_subrange
+// or clear_within in te_remove_group's closed form of remove_element: with M survivors among the cnt records a survivor below M stays, and the holes below M,
+// ascending, receive the survivors at M and above, descending.  aux moves with its records.  counts[t] = M; an adding stroke's k_flowers_place continues from there.
+__global__ __launch_bounds__(TREEP_THREADS) void k_flowers_remove(flower_edit_consts_t c, tile_ref_pod_t const *__restrict__ tiles, uint8_t const *__restrict__ generated,
+	uint8_t const *__restrict__ updated, uint32_t const *__restrict__ ranges, uint32_t capacity, flower_pod_t *flowers, uint32_t *aux, uint32_t *counts, uint8_t *status,
+	uint32_t *idx, uint8_t *kind_out)
+{
+	__shared__ uint32_t s_wave[TREEP_THREADS/64];
+	uint32_t const t = blockIdx.x, tid = threadIdx.x;
+	uint32_t rg[4] = {0u, 0u, 0u, 0u};
+	if (ranges) {for (int k = 0; k < 4; ++k) {rg[k] = ranges[4*t + k];}}
+	int const kind = flower_edit_kind(c, updated[t], generated ? generated[t] : (uint8_t)1, rg); // (uniform)
+	if (tid == 0) {kind_out[t] = (uint8_t)kind; status[t] = (kind == FLOWER_EDIT_NONE) ? 0 : ((kind == FLOWER_EDIT_REFUSED) ? 2 : 1);}
+	if (kind != FLOWER_EDIT_ADD && kind != FLOWER_EDIT_REMOVE) return;
+	tile_ref_pod_t const r = tiles[t];
+	float px, py;
+	flower_brush_local(c, r.tx, r.ty, px, py);
+	auto removed = [&](flower_pod_t const &f) {
+		return (kind == FLOWER_EDIT_ADD) ? flower_in_range(c.f, f, (int)rg[0], (int)rg[1], (int)rg[2], (int)rg[3]) : flower_in_brush(f, px, py, c.radius, c.is_square != 0);
+	};
+	flower_pod_t *const v = flowers + (size_t)t*capacity;
+	uint32_t *const ax = aux ? aux + (size_t)t*capacity : nullptr, *const my_idx = idx + (size_t)t*capacity;
+	uint32_t const cnt = min_u32(counts[t], capacity);
+	uint32_t m = 0, nk;
+	for (uint32_t base = 0; base < cnt; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		tp_block_rank(i < cnt && !removed(v[i]), s_wave, nk);
+		m += nk;
+	}
+	if (m != cnt) {
+		uint32_t h = 0;
+		for (uint32_t base = m; base < cnt; base += TREEP_THREADS) { // the survivors at M and above, ascending
+			uint32_t const i = base + tid;
+			bool const keep = i < cnt && !removed(v[i]);
+			uint32_t const rank = tp_block_rank(keep, s_wave, nk);
+			if (keep) {my_idx[h + rank] = i;}
+			h += nk;
+		}
+		__syncthreads(); // idx[] is complete
+		uint32_t k0 = 0;
+		for (uint32_t base = 0; base < m; base += TREEP_THREADS) { // the k-th hole below M takes survivor idx[h - 1 - k]: sources at M and above, destinations below
+			uint32_t const i = base + tid;
+			bool const hole = i < m && removed(v[i]);
+			uint32_t const rank = tp_block_rank(hole, s_wave, nk);
+			if (hole) {
+				uint32_t const src = my_idx[h - 1u - (k0 + rank)];
+				v[i] = v[src];
+				if (ax) {ax[i] = ax[src];}
+			}
+			k0 += nk;
+		}
+	}
+	__syncthreads(); // every thread has read the count
+	if (tid == 0) {counts[t] = m;}
+}
+
 // ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
 // terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
 // k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes

@@ -181,6 +181,12 @@ template<class DERIVED> struct simple_paths {
 		decid_place_pod_t *, uint32_t *) {return false;}
 	// scenery placement's kernel: none here -- the driver (tiles_place_scenery_dev) then runs its one-thread-per-tile form
 	bool tile_place_scenery(scenery_place_consts_t const *, tile_ref_pod_t const *, uint32_t, float const *, uint8_t const *, uint32_t, scenery_place_pod_t *, uint32_t *, uint32_t *) {return false;}
+	// the flowers' kernels: none here -- the driver (tiles_place_flowers_dev, tiles_edit_flowers_dev) then runs its one-thread-per-tile forms: the reference's cell loop
+	// with one generator through the tile, the removal as the literal remove_element loop
+	bool tile_place_flowers(flower_consts_t const &, tile_ref_pod_t const *, uint32_t, uint8_t const *, uint8_t const *, float const *, float const *, uint32_t, flower_pod_t *,
+		uint32_t *, uint32_t *) {return false;}
+	bool tile_edit_flowers(flower_edit_consts_t const &, tile_ref_pod_t const *, uint32_t, uint8_t const *, uint8_t const *, uint32_t const *, uint8_t const *, float const *,
+		float const *, uint32_t, flower_pod_t *, uint32_t *, uint32_t *, uint8_t *, uint32_t *, uint8_t *) {return false;}
 	// tile erosion, wave form: the clamp-padded copies live in HBM/L2, ONE WAVE per tile walks the droplets in order through a 32x32 LDS window
 	// (10 KB of LDS per tile instead of 76 KB: ~15 tiles per CU in flight instead of 2)
 	void tile_erosion_windowed(uint32_t n, float *zvals, erosion_consts_t const &ec, uint32_t iters, float *padded /* n*NX*NY */) {

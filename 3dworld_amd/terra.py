@@ -104,6 +104,26 @@ def make_scenery_params(use_voxel_rocks=2):
     return SceneryParams(use_voxel_rocks)
 
 
+FLOWER_DTYPE = np.dtype([("pos", np.float32, (3,)), ("normal", np.float32, (3,)), ("radius", np.float32), ("height", np.float32), ("color", np.float32, (4,))])  # terra_flower
+assert FLOWER_DTYPE.itemsize == 48
+FLOWER_AUX_FIXED = 7  # the aux word's colour field under a fixed flower_color
+
+
+def flower_aux_fields(aux):
+    """the aux words of tiles_place_flowers -> (cx, cy, colour field: 2 + the signed remainder int(1.5*color_val) % 3, or FLOWER_AUX_FIXED)"""
+    aux = np.asarray(aux, np.uint32)
+    return aux & 1023, (aux >> 10) & 1023, (aux >> 20) & 7
+
+
+class FlowerParams(C.Structure):  # terra_flower_params
+    _fields_ = [("flower_density", C.c_float), ("grass_length", C.c_float), ("grass_width", C.c_float), ("flower_color", C.c_float * 4), ("no_grass", C.c_int32)]
+
+
+def make_flower_params(flower_density=0.0, grass_length=0.02, grass_width=0.002, flower_color=(0.0, 0.0, 0.0, 0.0), no_grass=0):
+    """terra_flower_params with the reference's defaults (flower_density 0: no flowers)."""
+    return FlowerParams(flower_density, grass_length, grass_width, (C.c_float * 4)(*flower_color), int(bool(no_grass)))
+
+
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
@@ -289,6 +309,12 @@ _PROTOS = {
     "terra_get_scenery_params": (_i32, [_vp, _vp]),
     "terra_tiles_place_scenery_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_place_scenery": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
+    "terra_set_flower_params": (_i32, [_vp, _vp]),
+    "terra_get_flower_params": (_i32, [_vp, _vp]),
+    "terra_tiles_place_flowers_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "terra_tiles_place_flowers": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "terra_tiles_edit_flowers_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "terra_tiles_edit_flowers": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -847,6 +873,45 @@ class Terra:
                                                     objs.ctypes.data if capacity else None, counts.ctypes.data, None if kinds is None else kinds.ctypes.data))
         return objs, counts, kinds
 
+    def set_flower_params(self, fp):
+        self._ck(self.lib.terra_set_flower_params(self.ctx, C.byref(fp)))
+
+    def get_flower_params(self):
+        fp = FlowerParams()
+        self._ck(self.lib.terra_get_flower_params(self.ctx, C.byref(fp)))
+        return fp
+
+    def tiles_place_flowers(self, tile_xy, weights, capacity, skip=None, aux=True):
+        """flower_tile_manager_t::gen_flowers for every tile.  weights: [n, S+1, S+1, 4] bytes as tiles_tree_weights leaves them (None under skip_generate()),
+        skip: [n] bytes.  -> (flowers FLOWER_DTYPE [n, capacity], aux uint32 [n, capacity] or None, counts uint32 [n]); records past counts[t] are zero"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint8)
+        flowers, counts = np.zeros((n, capacity), FLOWER_DTYPE), np.zeros(n, np.uint32)
+        ax = np.zeros((n, capacity), np.uint32) if aux else None
+        self._ck(self.lib.terra_tiles_place_flowers(self.ctx, txy.ctypes.data, n, None if sk is None else sk.ctypes.data, None if w is None else w.ctypes.data, capacity,
+                                                    flowers.ctypes.data if capacity else None, None if ax is None else ax.ctypes.data, counts.ctypes.data))
+        return flowers, ax, counts
+
+    def tiles_edit_flowers(self, tile_xy, brush, updated, ranges, weights, flowers, aux, counts, generated=None, dxoff=0, dyoff=0):
+        """the flowers' half of a grass stroke, in place on flowers [n, capacity] FLOWER_DTYPE, aux [n, capacity] uint32 (or None) and counts [n] uint32; brush,
+        updated [n] bytes and ranges [n, 4] uint32 as tiles_edit_grass took and returned them.  -> status uint8 [n]"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        assert flowers.dtype == FLOWER_DTYPE and flowers.flags.c_contiguous and counts.dtype == np.uint32 and counts.flags.c_contiguous
+        assert aux is None or (aux.dtype == np.uint32 and aux.flags.c_contiguous and aux.shape == flowers.shape)
+        capacity = flowers.shape[1]
+        up = np.ascontiguousarray(updated, np.uint8).reshape(n)
+        rg = None if ranges is None else np.ascontiguousarray(ranges, np.uint32).reshape(n, 4)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint8)
+        ge = None if generated is None else np.ascontiguousarray(generated, np.uint8).reshape(n)
+        status = np.zeros(n, np.uint8)
+        self._ck(self.lib.terra_tiles_edit_flowers(self.ctx, txy.ctypes.data, n, dxoff, dyoff, None if ge is None else ge.ctypes.data, C.byref(brush), up.ctypes.data,
+                                                   None if rg is None else rg.ctypes.data, None if w is None else w.ctypes.data, capacity,
+                                                   flowers.ctypes.data if capacity else None, None if aux is None else aux.ctypes.data, counts.ctypes.data, status.ctypes.data))
+        return status
+
     def set_tree_size_params(self, tsp):
         self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
 
@@ -1091,6 +1156,20 @@ class Terra:
         kind_counts_ptr [n][9] uint32 or None.  Only enqueues."""
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_place_scenery_dev(self.ctx, txy.ctypes.data, len(txy), xoff2, yoff2, skip_ptr, capacity, objs_ptr, counts_ptr, kind_counts_ptr))
+
+    def tiles_place_flowers_dev(self, tile_xy, weights_ptr, capacity, flowers_ptr, counts_ptr, aux_ptr=None, skip_ptr=None):
+        """the flowers of a device-resident batch: weights_ptr [n][S+1][S+1][4] bytes, flowers_ptr [n][capacity] FLOWER_DTYPE records, aux_ptr [n][capacity] uint32 or
+        None, counts_ptr [n] uint32, skip_ptr [n] bytes or None.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_place_flowers_dev(self.ctx, txy.ctypes.data, len(txy), skip_ptr, weights_ptr, capacity, flowers_ptr, aux_ptr, counts_ptr))
+
+    def tiles_edit_flowers_dev(self, tile_xy, brush, updated_ptr, ranges_ptr, weights_ptr, capacity, flowers_ptr, counts_ptr, status_ptr, aux_ptr=None, generated_ptr=None,
+                               dxoff=0, dyoff=0):
+        """the flowers' half of a grass stroke on device-resident records, in place: updated_ptr / ranges_ptr as tiles_edit_grass_dev left them, status_ptr n bytes.
+        Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_edit_flowers_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, generated_ptr, C.byref(brush), updated_ptr, ranges_ptr, weights_ptr,
+                                                       capacity, flowers_ptr, aux_ptr, counts_ptr, status_ptr))
 
     def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
                                   decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,

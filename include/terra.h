@@ -709,6 +709,74 @@ int  terra_tiles_place_scenery_dev(terra_ctx *ctx, const int32_t *tile_xy, uint3
 int  terra_tiles_place_scenery(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t xoff2, int32_t yoff2, const uint8_t *h_skip, uint32_t capacity,
                                terra_scenery_place *h_objs, uint32_t *h_counts, uint32_t *h_kind_counts);
 
+/* ---- flowers of a tile batch (every supported tile size S): flower_tile_manager_t::gen_flowers (src/grass.cpp:859-888) with flower_manager_t::add_flowers
+ * (:813-838), as tile_t::draw_flowers (src/tiled_mesh.cpp:1666-1677) calls it -- the fourth generated container of a tile -- and its upkeep after a grass
+ * stroke, update_subrange / clear_within (src/grass.cpp:890-926) as tile_t::add_or_remove_grass_at (src/tiled_mesh.cpp:3930-3937) calls them.  The input is
+ * "mesh weight + tree dirt": the weights terra_tiles_create_weights followed by terra_tiles_tree_weights leaves.  Only tsize_bitshift == 0: a city tile with a
+ * finer weight texture stays with the caller, as for the grass brush.
+ * terra_flower_params: flower_density (config "flower_density", 0: no flowers), grass_length / grass_width (config "grass_size", 0.02 / 0.002), flower_color
+ * (config "flower_color" sets alpha 1; alpha > 0 = every flower has this colour), no_grass (no_grass()).  TERRA_ERR_ARG (and nothing changes): a density,
+ * length or width that is negative or not finite; a flower_density above 1024 (a tile's count is 32 bits).
+ * Generation, bit for bit.  The generator is seeded ONCE per tile with (tile x1 + 123, tile y1 + 456) -- set_state(x1 + xoff2 + 123, ..) with the caller's
+ * x1 - xoff2: the offsets cancel -- and runs through all cells, rows then columns.  The two density fields are generated internally: build_arrays(tile x1, tile y1,
+ * fds*DX_VAL*DX_VAL, fds*DY_VAL*DY_VAL, S, S, 0, force_sine_mode=1) for fds = 500 and 650, read with eval_index(x, y, 50).  Per cell: the weight is byte 2 (grass)
+ * of texel (x, y); grass_den = weight/255.0 as a float; below 0.5 (weight 0 .. 127) no flowers; num_per_bin = unsigned(flower_density*grass_den + 0.5).  Per
+ * candidate: dval + 0.2*zmax_est*signed_rand_float() > get_median_height(0.5) in double rejects it after that one draw (the histogram is
+ * terra_set_height_histogram's; empty: 0.5); an accepted one draws rand_uniform(0.85, 1.0) for the height, the position's two rand_float() -- y's first: g++
+ * evaluates the constructor's arguments right to left --, signed_rand_vector(0.2)'s three (z's first), rand_uniform(1.5, 2.5) for the radius and, unless
+ * flower_color.alpha > 0, signed_rand_float() for the colour.  pos is tile-local (dx = dy = 0, gen_zval = 0: pos.z = height).
+ * The colour index.  The source reads colors[int(0.5*NUM_COLORS*color_val)%NUM_COLORS] with `unsigned const NUM_COLORS(3)`: the usual arithmetic conversions turn
+ * the int into an unsigned BEFORE the remainder, so the index is unsigned(int(1.5*color_val)) % 3u -- 0 .. 2 for every color_val, defined behaviour -- and that
+ * is the colour of the record.  For a negative int this is NOT the signed remainder plus 3 (-1 -> 4294967295 % 3 = 0, -2 -> 2, -3 -> 1, -4 -> 0).  About four
+ * flowers in ten have a negative int (the colour field is a zero-mean sine sum); aux reports the signed remainder so that a caller or a test can tell them apart.
+ * weights: [n][S+1][S+1][4] bytes.  flowers: [n][capacity] records of terra_flower, whose layout is flower_t's (src/grass.h:80-88): an engine copies a tile's
+ * records straight into its vector.  aux (optional): [n][capacity] words, bits 0-9 the cell's x, 10-19 its y, 20-22 the colour field: 2 + (int(1.5*color_val) % 3
+ * as a signed remainder, -2 .. 2), or 7 under a fixed flower_color.  counts: [n].  The reference's order is kept; only the first `capacity` records of a tile are
+ * written and counts[t] still reports all; records past counts[t] are not written.  skip (optional): [n] bytes, non-zero = the tile is not generated (counts[t] = 0).
+ * skip_generate(): with flower_density == 0 or no_grass every count is 0 and the weights are not touched (they may be NULL).
+ * With the engine stay `generated`, check_vbo, create_verts_range, the drawing and scale_flowers.
+ * TERRA_ERR_ARG: an unsupported S, a NULL required pointer (tile_xy, counts, weights when n > 0; flowers when capacity > 0), a misaligned pointer.
+ * TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the scene and the tile size have passed.  The device form only enqueues. */
+typedef struct terra_flower_params {
+	float flower_density;    /* 0 */
+	float grass_length;      /* 0.02 */
+	float grass_width;       /* 0.002 */
+	float flower_color[4];   /* RGBA, alpha 0: the three colours of add_flowers */
+	int32_t no_grass;        /* 0 */
+} terra_flower_params;
+typedef struct terra_flower {
+	float pos[3];
+	float normal[3];
+	float radius, height;
+	float color[4];
+} terra_flower;              /* 48 bytes, flower_t */
+int  terra_set_flower_params(terra_ctx *ctx, const terra_flower_params *params);
+int  terra_get_flower_params(terra_ctx *ctx, terra_flower_params *out);
+int  terra_tiles_place_flowers_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const uint8_t *d_skip, const uint8_t *d_weights, uint32_t capacity,
+                                   terra_flower *d_flowers, uint32_t *d_aux, uint32_t *d_counts);
+int  terra_tiles_place_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const uint8_t *h_skip, const uint8_t *h_weights, uint32_t capacity,
+                               terra_flower *h_flowers, uint32_t *h_aux, uint32_t *h_counts);
+/* terra_tiles_edit_flowers: the flowers' half of a grass stroke, in place on the records (and aux, where given) of a batch.  brush, updated and ranges are what
+ * terra_tiles_edit_grass[_dev] took and left; generated (optional, [n] bytes; NULL = all) is the engine's flag.  Only tiles with updated[t] && generated[t] are
+ * touched.  A tile's container is its first min(counts[t], capacity) records.
+ * Adding: update_subrange(.., xl, yl, xh, yh); nothing when xh <= xl or yh <= yl.  The remove_element loop (swap with the back, pop, test the index again) runs
+ * over the cell test int(pos.x*DX_VAL_INV), int(pos.y*DY_VAL_INV) inside the range, which truncates; the generator is re-seeded with (tile x1 + xl + 123,
+ * tile y1 + yl + 456); add_flowers runs over the rectangle's cells (no minimum over texels); the new records go behind the survivors while they fit, counts[t]
+ * reports all.  Removing: clear_within(pos - flower_xlate, radius, shape == TERRA_BSHAPE_CONST_SQ) with the same loop; flower_xlate = (get_xval(x1 + dxoff),
+ * get_yval(y1 + dyoff)), dxoff / dyoff = xoff - xoff2 / yoff - yoff2 as for the grass brush.  ranges and weights are read only when adding.
+ * status: [n] bytes.  0: untouched.  1: edited (the loops ran, whether or not a record changed).  2: left unchanged because the range reaches texel row or column
+ * S (xh > S or yh > S): update_subrange would call eval_index(S, ..) there, which the reference asserts against (the density fields have S x S cells).
+ * terra_tiles_edit_grass never leaves such a range -- it clamps xh and yh to S as src/tiled_mesh.cpp:3900-3901 does, so a stroke at a tile's far edge updates
+ * columns up to S - 1 -- the value guards ranges that come from elsewhere.
+ * TERRA_ERR_ARG: a bad brush shape, an unsupported S, a NULL required pointer (brush; tile_xy, updated, counts, status when n > 0; ranges and weights when adding;
+ * flowers when capacity > 0), a misaligned pointer.  TERRA_ERR_STATE before terra_init_scene.  The device form only enqueues. */
+int  terra_tiles_edit_flowers_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *d_generated,
+                                  const terra_grass_brush *brush, const uint8_t *d_updated, const uint32_t *d_ranges, const uint8_t *d_weights, uint32_t capacity,
+                                  terra_flower *d_flowers, uint32_t *d_aux, uint32_t *d_counts, uint8_t *d_status);
+int  terra_tiles_edit_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *h_generated,
+                              const terra_grass_brush *brush, const uint8_t *h_updated, const uint32_t *h_ranges, const uint8_t *h_weights, uint32_t capacity,
+                              terra_flower *h_flowers, uint32_t *h_aux, uint32_t *h_counts, uint8_t *h_status);
+
 /* ---- tree AO shadows of a tile batch from the placement records (every supported tile size S): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828), the step
  * between the two placements above and terra_tiles_shadow_texture / terra_tiles_tree_weights.  One call goes from the records as they lie in device memory to the
  * tree maps of the batch, bit for bit; with it zvals -> stats -> both placements -> tree map -> shadow texture / tree weights is one stream of launches.

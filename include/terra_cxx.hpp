@@ -292,6 +292,28 @@ inline void tiles_gen_scenery(tile_batch_dev_t const &b, int xoff2, int yoff2, u
 {
 	check(terra_tiles_place_scenery_dev(default_ctx(), b.tile_xy, b.n, xoff2, yoff2, d_no_scenery, capacity, d_objs, d_counts, d_kind_counts), "scenery_group::gen");
 }
+// ---- the flowers of a batch on device arrays.  flower_density, grass_length, grass_width, flower_color and no_grass() go in once (set_flower_globals).
+inline void set_flower_globals(terra_flower_params const &p) {check(terra_set_flower_params(default_ctx(), &p), "set_flower_params");}
+// flower_tile_manager_t::gen_flowers(weight_data, weights_tsize, x1 - xoff2, y1 - yoff2, 0) (src/grass.cpp:859-888) for every tile as tile_t::draw_flowers
+// (src/tiled_mesh.cpp:1666-1677) calls it: d_weight_data is what tiles_create_texture_tree_weights left.  d_no_flowers[t] != 0 (or null): the tile is not generated
+// (already generated, too far, a city tile with tsize_bitshift > 0).  d_flowers [n][capacity] records with flower_t's layout, d_aux (or null), d_counts [n]: the
+// engine copies flowers[t][0 .. counts[t]) into the tile's vector and sets generated; check_vbo, create_verts_range and the drawing stay where they are
+inline void tiles_gen_flowers(tile_batch_dev_t const &b, unsigned char const *d_no_flowers, unsigned char const *d_weight_data, unsigned capacity, terra_flower *d_flowers,
+	unsigned *d_aux, unsigned *d_counts)
+{
+	check(terra_tiles_place_flowers_dev(default_ctx(), b.tile_xy, b.n, d_no_flowers, d_weight_data, capacity, d_flowers, d_aux, d_counts), "gen_flowers");
+}
+// the flowers' half of tile_t::add_or_remove_grass_at (src/tiled_mesh.cpp:3930-3937) on the resident records, after tiles_add_or_remove_grass_at's device form left
+// d_updated / d_ranges: flowers.update_subrange when adding, flowers.clear_within(pos - flower_xlate, rradius, is_square) when removing.  d_generated[t] (or null: all):
+// the tile's `generated`.  d_status[t]: 0 untouched, 1 edited (the engine clears the tile's VBO), 2 refused (a range that reaches texel row or column S)
+inline void tiles_update_flowers_at(tile_batch_dev_t const &b, unsigned char const *d_generated, float const pos[3], float rradius, bool add_grass, int brush_shape,
+	unsigned char const *d_updated, unsigned const *d_ranges, unsigned char const *d_weight_data, unsigned capacity, terra_flower *d_flowers, unsigned *d_aux, unsigned *d_counts,
+	unsigned char *d_status)
+{
+	terra_grass_brush const br = {{pos[0], pos[1], pos[2]}, rradius, add_grass ? 1 : 0, brush_shape, 0.0f};
+	check(terra_tiles_edit_flowers_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, d_generated, &br, d_updated, d_ranges, d_weight_data, capacity, d_flowers, d_aux, d_counts,
+		d_status), "flowers.update_subrange / clear_within");
+}
 // tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:820-828) for every tile of the batch in batch order, from the records tiles_gen_trees / tiles_gen_decid_trees left
 // on the device: small_tree::get_radius / get_ao_radius and tree::get_ao_radius per record, apply_ao_shadows_for_trees' own loop, pulls and pushes, add_tree_ao_shadow's
 // texel loop.  xoff2 / yoff2: what the placements ran with (ptree_off / dtree_off).  d_sphere_radius [n][decid_capacity] (tdata().sphere_radius per record) or
