@@ -883,6 +883,55 @@ int terra_tiles_edit_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 		st.end();
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_view) == sizeof(terra::view_pod_t) && sizeof(terra_view) == 68, "terra_view layout");
+int terra_make_view(const float pos[3], const float dir[3], const float up[3], float angle, float aspect, float near_clip, float far_clip, terra_view *out) {
+	if (!pos || !dir || !up || !out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v;
+	if (!terra::view_make(pos, dir, up, angle, aspect, near_clip, far_clip, v)) {
+		return terra::fail(TERRA_ERR_ARG, "terra_make_view: needs near >= 0, far > near, a non-zero dir, and tanf(angle) > 0 unless aspect == 1");
+	}
+	memcpy(out, &v, sizeof(v));
+	return TERRA_OK;
+}
+int terra_set_grass_view_params(terra_ctx *ctx, const terra_grass_view_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	TERRA_TRY ctx->eng.set_grass_view_params(*params); TERRA_CATCH
+}
+int terra_get_grass_view_params(terra_ctx *ctx, terra_grass_view_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	*out = ctx->eng.gvp; return TERRA_OK;
+}
+int terra_tiles_grass_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *d_zvals, const terra_tile_stats *d_stats,
+                               const terra_grass_block *d_grass_blocks, const uint8_t *d_skip, const terra_view *view, uint32_t capacity, float *d_insts, uint32_t *d_aux,
+                               uint32_t *d_group_counts, uint32_t *d_counts, uint8_t *d_pass) {
+	TERRA_CHECK_CTX if (!view) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	TERRA_TRY ctx->eng.tiles_grass_view_dev(tile_xy, n, dxoff, dyoff, d_zvals, d_stats, (terra::grass_block_pod_t const *)d_grass_blocks, d_skip, v, capacity, d_insts, d_aux,
+		d_group_counts, d_counts, d_pass); TERRA_CATCH
+}
+int terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *h_zvals, const terra_tile_stats *h_stats,
+                           const terra_grass_block *h_grass_blocks, const uint8_t *h_skip, const terra_view *view, uint32_t capacity, float *h_insts, uint32_t *h_aux,
+                           uint32_t *h_group_counts, uint32_t *h_counts, uint8_t *h_pass) {
+	TERRA_CHECK_CTX if (!view) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	TERRA_TRY
+		ctx->eng.grass_view_check(v); // the scene, the tile size (the arrays are sized by S), the view, num_rnd_grass_blocks: before anything is staged
+		if (n == 0) return TERRA_OK;
+		if (!tile_xy || !h_zvals || !h_stats || !h_grass_blocks || !h_group_counts || !h_counts || (capacity && !h_insts)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		size_t const S = ctx->eng.tile_size(), dim = 1 + (S - 1)/4, nbins = (size_t)terra::GRASS_VIEW_LODS*ctx->eng.ls.num_rnd_grass_blocks;
+		struct inst_t {float v[2];};
+		terra_stage st(ctx->eng);
+		int const z = st.in(h_zvals, (size_t)n*(S + 2)*(S + 2)*4), s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), g = st.in(h_grass_blocks, (size_t)n*dim*dim*sizeof(terra_grass_block)),
+			k = st.opt_in(h_skip, n), r = st.temp((size_t)n*capacity*sizeof(inst_t)), a = st.add(nullptr, nullptr, (size_t)n*capacity*4, h_aux != nullptr),
+			gc = st.out(h_group_counts, (size_t)n*nbins*4), c = st.temp((size_t)n*4), p = st.opt_out(h_pass, n);
+		st.begin();
+		ctx->eng.tiles_grass_view_dev(tile_xy, n, dxoff, dyoff, st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<terra::grass_block_pod_t>(g), st.dev<uint8_t>(k), v, capacity,
+			st.dev<float>(r), st.dev<uint32_t>(a), st.dev<uint32_t>(gc), st.dev<uint32_t>(c), st.dev<uint8_t>(p));
+		st.end();
+		st.end_counted(r, c, (inst_t *)h_insts, h_counts, n, capacity);
+		if (h_aux) {st.end_counted(a, c, h_aux, h_counts, n, capacity);}
+	TERRA_CATCH
+}
 int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
 	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.set_tree_size_params(*params); TERRA_CATCH

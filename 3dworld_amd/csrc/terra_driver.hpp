@@ -17,6 +17,7 @@
 #include "terra_decidplace.hpp"
 #include "terra_sceneryplace.hpp"
 #include "terra_flowers.hpp"
+#include "terra_grassview.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_stage.hpp"
@@ -281,6 +282,12 @@ TERRA_HD line_box_t line_tile_box(line_query_consts_t const &c, int tx, int ty, 
 	return b;
 }
 TERRA_HD bool line_box_clip(line_box_t const &b, shadow_pt_t v1, shadow_pt_t v2) {return shadow_line_clip(v1, v2, b.d);}
+// the same box from the grass view's constants (terra_grassview.hpp): tile_t::draw_grass reads get_mesh_bcube() for all_visible and the minimum distance
+TERRA_HD line_box_t grass_view_box(grass_view_consts_t const &c, int tx, int ty, float mzmin, float mzmax) {
+	line_query_consts_t q;
+	q.xss = c.xss; q.yss = c.yss; q.DX_VAL = c.DX_VAL; q.DY_VAL = c.DY_VAL; q.DX_VAL_INV = 0.0f; q.DY_VAL_INV = 0.0f; q.S = c.S; q.dxoff = c.dxoff; q.dyoff = c.dyoff;
+	return line_tile_box(q, tx, ty, mzmin, mzmax);
+}
 // the walk of one (line, tile): false = no hit; else t = cur_t and (ix, iy) = the cell in the tile.  zt: the tile's (S+2)^2 zvals.  Non-finite lines and distant tiles
 // are the caller's (they never hit).  Steps are taken LINE_CHUNK at a time: the x / y / z sums advance serially as in the reference, the chunk's zvals are loaded
 // before any of its height tests, then the tests run in step order.  Every step loads, a step off the tile from cell 0 (it always exists; its value is not
@@ -738,6 +745,13 @@ template<class BE> struct terra_engine {
 		}
 		if (p.flower_density > FLOWER_DENSITY_MAX) throw std::invalid_argument("terra_set_flower_params: flower_density must be <= 1024 (a tile's count is 32 bits)");
 		fp = p;
+	}
+	// what the grass view reads beyond the flowers' grass_length and the landscape's num_rnd_grass_blocks: tt_grass_scale_factor (src/grass.cpp:1126 resets a value
+	// that is not > 0 to 1; here such a value is refused)
+	terra_grass_view_params gvp = {1.0f};
+	void set_grass_view_params(terra_grass_view_params const &p) {
+		if (!(p.tt_grass_scale_factor > 0.0f) || !std::isfinite(p.tt_grass_scale_factor)) throw std::invalid_argument("terra_set_grass_view_params: tt_grass_scale_factor must be finite and > 0");
+		gvp = p;
 	}
 	// what the trees' radii read beyond terra_tree_params (small_tree's constructor and get_pine_tree_radius): tree_height_scale, sm_tree_scale, pine_tree_radius_scale
 	terra_tree_size_params tsp = {1.0f, 1.0f, 1.0f};
@@ -2992,6 +3006,81 @@ template<class BE> struct terra_engine {
 				count = flower_remove_serial(v, aux, count, [&](flower_pod_t const &f) {return flower_in_brush(f, px, py, c.radius, c.is_square != 0);});
 			}
 			d_counts[t] = count;
+		});
+	}
+
+	// ---- the grass draw lists of a batch for a camera (terra_grassview.hpp): tile_t::draw_grass (src/tiled_mesh.cpp:1607-1664) without its GL calls, behind the
+	// per-tile filters of tile_draw_t::draw_grass (:3420-3425), over zvals, stats and grass blocks as the tile passes left them.  The checks that need no array
+	// (the host form runs them before it stages anything):
+	void grass_view_check(view_pod_t const &view) const {
+		require_scene();
+		require_tile_size();
+		if ((tile_size() & 3u) != 0) throw std::invalid_argument("tiles_grass_view: the tile size must be a multiple of 4 (the back-face loop of src/tiled_mesh.cpp:1638-1641 would read past the zvals)");
+		if (!view_finite(view)) throw std::invalid_argument("tiles_grass_view: a member of the view is not finite");
+		if (ls.num_rnd_grass_blocks == 0 || ls.num_rnd_grass_blocks > GRASS_VIEW_MAX_RND) throw std::invalid_argument("tiles_grass_view: num_rnd_grass_blocks must be 1 .. 4096");
+	}
+	void tiles_grass_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, float const *d_zvals, terra_tile_stats const *d_stats, grass_block_pod_t const *d_blocks,
+		uint8_t const *d_skip, view_pod_t const &view, uint32_t capacity, float *d_insts, uint32_t *d_aux, uint32_t *d_group_counts, uint32_t *d_counts, uint8_t *d_pass)
+	{
+		grass_view_check(view);
+		if (n == 0) return;
+		if (!tile_xy || !d_zvals || !d_stats || !d_blocks || !d_group_counts || !d_counts || (capacity && !d_insts)) throw std::invalid_argument("tiles_grass_view: null argument");
+		if ((((uintptr_t)d_zvals | (uintptr_t)d_stats | (uintptr_t)d_blocks | (uintptr_t)d_insts | (uintptr_t)d_aux | (uintptr_t)d_group_counts | (uintptr_t)d_counts) & 3u) != 0) {
+			throw std::invalid_argument("tiles_grass_view: d_zvals, d_stats, d_grass_blocks, d_insts, d_aux, d_group_counts and d_counts must be 4-byte aligned");
+		}
+		uint32_t const S = tile_size();
+		grass_view_consts_t const c = grass_view_consts(view, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, dxdy, (int)S, dxoff, dyoff, ls.num_rnd_grass_blocks,
+			gvp.tt_grass_scale_factor, fp.grass_length);
+		size_t const nb = (size_t)c.dim*c.dim, nbins = (size_t)GRASS_VIEW_LODS*c.nrnd, zn = (size_t)(S + 2)*(S + 2);
+		// a key per block (16 bits: dropped, or lod*nrnd + bix) and, for the simple form, a running offset per group
+		// and the tile coordinates: this pass reads nothing else of a tile reference, so it uploads them as they are (through tile_fields_dev a call on 4096 tiles
+		// took 311.8 us instead of 94.0 us with the same kernel: DESIGN.md, the grass draw lists)
+		uint16_t *d_keys; uint32_t *d_offs; int32_t *d_txy;
+		stage_layout_t lay;
+		lay.add(d_keys, (size_t)n*nb); lay.add(d_offs, (size_t)n*nbins); lay.add(d_txy, (size_t)n*2);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		if (be.tile_grass_view(c, d_txy, n, d_zvals, d_stats, d_blocks, d_skip, capacity, d_insts, d_aux, d_group_counts, d_counts, d_pass, d_keys)) return;
+		// the simple form: one logical thread per tile runs the reference's loops; its per-LOD, per-bix lists are the groups' counts, then their offsets, then a second
+		// walk in the same scan order that appends every kept block to its group
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			terra_tile_stats const &st = d_stats[t];
+			line_box_t const box = grass_view_box(c, d_txy[2*t], d_txy[2*t + 1], st.mzmin, st.mzmax);
+			grass_view_tile_t const tl = grass_view_tile(c, box.d, box.x1, box.y1, st.mzmin, st.mzmax, st.radius);
+			uint32_t *const gc = d_group_counts + t*nbins, *const of = d_offs + t*nbins;
+			uint16_t *const ky = d_keys + t*nb;
+			for (size_t b = 0; b < nbins; ++b) {gc[b] = 0u;}
+			bool has_grass = false;
+			if (!(d_skip && d_skip[t]) && tl.in_range) {
+				grass_block_pod_t const *const bl = d_blocks + t*nb;
+				for (uint32_t y = 0; y < c.dim; ++y) {
+					for (uint32_t x = 0; x < c.dim; ++x) {
+						grass_block_pod_t const gb = bl[y*c.dim + x];
+						has_grass = has_grass || gb.ix != 0u;
+						uint32_t const key = grass_view_block(c, tl, x, y, gb.ix, gb.zmin, gb.zmax, d_zvals + t*zn);
+						ky[y*c.dim + x] = (uint16_t)key;
+						if (key != GRASS_VIEW_DROPPED) {++gc[key];}
+					}
+				}
+			}
+			if (!has_grass) { // skipped, too far away (:1612) or !has_grass() (:1609, :3422)
+				d_counts[t] = 0u;
+				if (d_pass) {d_pass[t] = GRASS_VIEW_NO_PASS;}
+				return;
+			}
+			uint32_t total = 0;
+			for (size_t b = 0; b < nbins; ++b) {of[b] = total; total += gc[b];}
+			for (uint32_t i = 0; i < (uint32_t)nb; ++i) {
+				uint32_t const key = ky[i];
+				if (key == GRASS_VIEW_DROPPED) continue;
+				uint32_t const rank = of[key]++;
+				if (rank >= capacity) continue;
+				float *const o = d_insts + (t*capacity + rank)*2;
+				o[0] = (float)(i % c.dim)*c.dx_step; o[1] = (float)(i / c.dim)*c.dy_step; // emplace_back(x*dx_step, y*dy_step) (:1651)
+				if (d_aux) {d_aux[t*capacity + rank] = grass_view_aux(c, i, key);}
+			}
+			d_counts[t] = total;
+			if (d_pass) {d_pass[t] = (uint8_t)tl.wpass;}
 		});
 	}
 

@@ -1,0 +1,202 @@
+// terra_grassview.hpp -- the grass draw lists of a tile for a camera: tile_t::draw_grass (src/tiled_mesh.cpp:1607-1664) without its GL calls, the per-tile filters of
+// its caller tile_draw_t::draw_grass (:3420-3425), tile_t::get_min_dist_to_pt (:354-364, mesh_only), get_rel_dist_to_camera / get_dist_to_camera_in_tiles
+// (src/tiled_mesh.h:320-332), get_norm_not_normalized (:281-283), the thresholds (src/tiled_mesh.cpp:27-29,118-120; src/tiled_mesh.h:24,93-94), and the view
+// frustum pos_dir_up (src/visibility.cpp:67-103,141-174,186-196) with cube_t::closest_pt / closest_pt_dist_sq (src/3DWorld.h:591,636-641; src/csg.cpp:244-246),
+// dist_less_than (src/inlines.h:176-192) and orthogonalize_dir (src/inlines.h:265-268).
+//
+// The bodies are shared by the driver's simple form (one logical thread per tile, the reference's loops) and by k_grass_view (terra_kernels.hpp).  Every operand
+// carries the type the reference statement gives it; where the C++ source promotes to double the promotion is written out; dot products are summed in the
+// reference's order (the library is built without contraction).
+//
+// The tests of a block are pure: where the reference leaves a loop early (check_clip_plane's first passing point, the near / far loop of pt_set_visible, the
+// `&& back_facing` of the back-face loops) the bodies here evaluate every term and combine them -- the same booleans, no branch per term.
+#pragma once
+#include "terra_common.hpp"
+
+namespace terra {
+
+constexpr uint32_t GRASS_VIEW_LODS    = 6;       // NUM_GRASS_LODS (src/grass.h:9)
+constexpr uint32_t GRASS_VIEW_BLOCK   = 4;       // GRASS_BLOCK_SZ (src/grass.h:10)
+constexpr uint32_t GRASS_VIEW_DROPPED = 0xFFFFu; // the key of a block that is not drawn; a kept block's key is lod*num_rnd_grass_blocks + bix
+constexpr uint32_t GRASS_VIEW_MAX_RND = 4096;    // 6*4096 keys fit 16 bits beside GRASS_VIEW_DROPPED; bix fits the aux word's 13 bits
+constexpr uint8_t  GRASS_VIEW_NO_PASS = 255;     // the pass byte of a tile that draws nothing
+
+struct view_pod_t {float pos[3], dir[3], upv[3], cp[3]; float sterm, x_sterm, near_, far_; int32_t valid;}; // terra_view: pos_dir_up's pos, dir, upv_, cp, ...
+
+// ---- the constants block: what draw_grass computes before its loops from globals alone
+struct grass_view_consts_t {
+	view_pod_t v;
+	float xss, yss, DX_VAL, DY_VAL, dxdy;
+	int S, dxoff, dyoff;
+	uint32_t dim, nrnd;                 // get_grass_block_dim() (src/tiled_mesh.h:315), num_rnd_grass_blocks
+	float tt;                           // tt_grass_scale_factor
+	float grass_thresh;                 // get_grass_thresh_pad() (src/tiled_mesh.cpp:118-120)
+	float scaled_tile_radius;           // get_scaled_tile_radius() (src/tiled_mesh.h:94)
+	float dx_step, dy_step, lod_scale;  // :1619-1620
+	float grass_length, adj_z;          // adj_camera.z (:1622)
+};
+inline grass_view_consts_t grass_view_consts(view_pod_t const &v, float xss, float yss, float DX_VAL, float DY_VAL, float dxdy, int S, int dxoff, int dyoff, uint32_t nrnd,
+	float tt, float grass_length)
+{
+	grass_view_consts_t c;
+	c.v = v; c.xss = xss; c.yss = yss; c.DX_VAL = DX_VAL; c.DY_VAL = DY_VAL; c.dxdy = dxdy; c.S = S; c.dxoff = dxoff; c.dyoff = dyoff;
+	c.dim = 1u + ((uint32_t)S - 1u)/GRASS_VIEW_BLOCK; c.nrnd = nrnd; c.tt = tt; c.grass_length = grass_length;
+	float const GRASS_LOD_SCALE = 15.0f, GRASS_DIST_SLOPE = 0.25f, GRASS_THRESH = 1.6f; // src/tiled_mesh.cpp:27-29
+	int const TILE_RADIUS = 6;                                                             // src/tiled_mesh.h:24
+	float const tile_width = xss + yss;                                                    // get_tile_width() (src/tiled_mesh.h:93)
+	c.scaled_tile_radius = (float)TILE_RADIUS*tile_width;
+	c.grass_thresh = GRASS_THRESH*tt*tile_width + tt/GRASS_DIST_SLOPE;                     // get_grass_thresh() + get_grass_blend_dist()
+	c.dx_step = (float)GRASS_VIEW_BLOCK*DX_VAL; c.dy_step = (float)GRASS_VIEW_BLOCK*DY_VAL; // unsigned*float
+	c.lod_scale = GRASS_LOD_SCALE/(tt*c.scaled_tile_radius);
+	c.adj_z = v.pos[2] + (float)(2.0*(double)grass_length);                                // camera + point(0.0, 0.0, 2.0*grass_length): the double narrows in point()
+	return c;
+}
+
+// float -> unsigned as the reference binary converts it (cvttss2si to 64 bits, the low word): NaN and values beyond the 64-bit range give 0
+TERRA_HD uint32_t f2u_x86(float f) {return (f > -9223372036854775808.0f && f < 9223372036854775808.0f) ? (uint32_t)(uint64_t)(int64_t)f : 0u;}
+
+TERRA_HD float view_dot(float const a[3], float x, float y, float z) {return a[0]*x + a[1]*y + a[2]*z;} // dot_product (src/inlines.h:220-222)
+
+// pos_dir_up::point_visible_test (src/visibility.cpp:94-103)
+TERRA_HD bool view_point_visible(view_pod_t const &v, float px, float py, float pz) {
+	if (!v.valid) return true;
+	float const x = px - v.pos[0], y = py - v.pos[1], z = pz - v.pos[2]; // vector3d const pv(pos_, pos)
+	if (view_dot(v.dir, x, y, z) < 0.0f) return false;
+	float const dist = sqrtf(x*x + y*y + z*z);
+	if (fabsf(view_dot(v.upv, x, y, z)) > dist*v.sterm) return false;
+	if (fabsf(view_dot(v.cp, x, y, z)) > dist*v.x_sterm) return false;
+	return dist > v.near_ && dist < v.far_;
+}
+// pos_dir_up::cube_completely_visible (:186-196)
+TERRA_HD bool view_cube_completely_visible(view_pod_t const &v, float const d[3][2]) {
+	if (!v.valid) return true;
+	bool all = true;
+	for (int k = 0; k < 8; ++k) {all = all && view_point_visible(v, d[0][k >> 2], d[1][(k >> 1) & 1], d[2][k & 1]);}
+	return all;
+}
+// cube_t::closest_pt_dist_sq(pos) = p2p_dist_sq(closest_pt(pos), pos), clamp_pt's min(d[1], max(d[0], p))
+TERRA_HD float view_closest_dist_sq(float const d[3][2], float px, float py, float pz) {
+	float const cx = min_std(d[0][1], max_std(d[0][0], px)), cy = min_std(d[1][1], max_std(d[1][0], py)), cz = min_std(d[2][1], max_std(d[2][0], pz));
+	return (cx - px)*(cx - px) + (cy - py)*(cy - py) + (cz - pz)*(cz - pz);
+}
+// pos_dir_up::cube_visible (:165-174) with pt_set_visible<8> and check_clip_plane<8> (:141-163)
+TERRA_HD bool view_cube_visible(view_pod_t const &v, float const d[3][2]) {
+	if (!v.valid) return true;
+	float const aau = v.sterm*v.sterm, aac = v.x_sterm*v.x_sterm;
+	bool u0 = false, u1 = false, c0 = false, c1 = false, npass = false, fpass = false;
+	for (int k = 0; k < 8; ++k) {
+		float const x = d[0][k >> 2] - v.pos[0], y = d[1][(k >> 1) & 1] - v.pos[1], z = d[2][k & 1] - v.pos[2];
+		float const msq = x*x + y*y + z*z, du = view_dot(v.upv, x, y, z), dc = view_dot(v.cp, x, y, z), dd = view_dot(v.dir, x, y, z);
+		bool const iu = du*du <= aau*msq, ic = dc*dc <= aac*msq;
+		u0 = u0 || du <= 0.0f || iu; u1 = u1 || -du <= 0.0f || iu; // (d ? -dp : dp) <= 0.0 || dp*dp <= aa*pv.mag_sq()
+		c0 = c0 || dc <= 0.0f || ic; c1 = c1 || -dc <= 0.0f || ic;
+		npass = npass || dd > v.near_; fpass = fpass || dd < v.far_;
+	}
+	if (!(u0 && u1 && c0 && c1 && npass && fpass)) return false;
+	return view_closest_dist_sq(d, v.pos[0], v.pos[1], v.pos[2]) < v.far_*v.far_; // dist_less_than(pos, c.closest_pt(pos), far_)
+}
+
+// ---- the tile test: what decides for a whole tile (has_grass() is the caller's: it reads the blocks)
+struct grass_view_tile_t {
+	float llcx, llcy;      // get_xval(x1 + xoff - xoff2), get_yval(y1 + yoff - yoff2) (:1618)
+	float bg_thresh_sq;    // :1621
+	int in_range;          // !(get_min_dist_to_pt(camera) > grass_thresh) (:1612)
+	int all_visible;       // :1623
+	int wpass;             // get_dist_to_camera_in_tiles(0) > 0.5*tt_grass_scale_factor (:3424)
+};
+// d: get_mesh_bcube() of the tile (line_tile_box), x1 / y1: its first mesh cell
+TERRA_HD grass_view_tile_t grass_view_tile(grass_view_consts_t const &c, float const d[3][2], int x1, int y1, float mzmin, float mzmax, float radius) {
+	grass_view_tile_t o;
+	float const *cam = c.v.pos;
+	o.llcx = d[0][0]; o.llcy = d[1][0];
+	float dsq = 0.0f; // get_min_dist_to_pt(camera, xy_only=0, mesh_only=1)
+	for (int i = 0; i < 3; ++i) {
+		float const dist = max_std(0.0f, max_std(d[i][0] - cam[i], cam[i] - d[i][1]));
+		dsq += dist*dist;
+	}
+	o.in_range = !(sqrtf(dsq) > c.grass_thresh);
+	o.bg_thresh_sq = 0.0f; o.all_visible = 0; o.wpass = 0;
+	if (!o.in_range) return o; // too far away to draw (:1612): nothing below is read, and most tiles of a large batch end here
+	float const SQRT2 = 1.41421356237309515f; // float const SQRT2 = sqrt(2.0) (src/3DWorld.h:132)
+	float const block_grass_thresh = c.grass_thresh + (SQRT2*radius)/(float)c.dim;
+	o.bg_thresh_sq = block_grass_thresh*block_grass_thresh;
+	o.all_visible = view_cube_completely_visible(c.v, d);
+	// get_center() (src/tiled_mesh.h:229-231): get_xval(((x1 + x2) >> 1) + (xoff - xoff2)), x2 = x1 + S; integer steps wrap as in the reference binary
+	int const mx = (int)((uint32_t)x1 + (uint32_t)x1 + (uint32_t)c.S) >> 1, my = (int)((uint32_t)y1 + (uint32_t)y1 + (uint32_t)c.S) >> 1;
+	float const ccx = -c.xss + c.DX_VAL*(float)(int)((uint32_t)mx + (uint32_t)c.dxoff), ccy = -c.yss + c.DY_VAL*(float)(int)((uint32_t)my + (uint32_t)c.dyoff);
+	float const ccz = 0.5f*(mzmin + mzmax);
+	float const dist = sqrtf((cam[0] - ccx)*(cam[0] - ccx) + (cam[1] - ccy)*(cam[1] - ccy) + (cam[2] - ccz)*(cam[2] - ccz)); // p2p_dist(get_camera_pos(), get_center())
+	float const in_tiles = (max_std(0.0f, dist - radius)/c.scaled_tile_radius)*(float)6; // get_rel_dist_to_camera(0)*TILE_RADIUS
+	o.wpass = ((double)in_tiles > 0.5*(double)c.tt) ? 1 : 0;
+	return o;
+}
+
+// ---- the back-face test of a near block (:1636-1643): true = every one of its 25 texels faces away from adj_camera.  zt: the tile's (S + 2)^2 zvals.
+// The block's 6 x 6 zvals are loaded before the first product is formed: a texel reads its own, its +x and its +y neighbour, neighbours share them.
+// S is a multiple of 4 here (the caller refuses others): rows and columns up to (dim*4 + 1) = S + 1 exist.
+TERRA_HD bool grass_view_back_facing(grass_view_consts_t const &c, grass_view_tile_t const &t, uint32_t x, uint32_t y, float const *zt) {
+	uint32_t const zvsize = (uint32_t)c.S + 2u, x0 = x*GRASS_VIEW_BLOCK, y0 = y*GRASS_VIEW_BLOCK;
+	float z[6][6];
+	for (uint32_t r = 0; r < 6; ++r) {for (uint32_t q = 0; q < 6; ++q) {z[r][q] = zt[(y0 + r)*zvsize + x0 + q];}}
+	bool back_facing = true;
+	for (uint32_t r = 0; r < 5; ++r) {
+		for (uint32_t q = 0; q < 5; ++q) {
+			uint32_t const xx = x0 + q, yy = y0 + r;
+			float const nx = c.DY_VAL*(z[r][q] - z[r][q + 1]), ny = c.DX_VAL*(z[r][q] - z[r + 1][q]), nz = c.dxdy; // get_norm_not_normalized(ix)
+			float const vx = c.v.pos[0] - (t.llcx + (float)xx*c.DX_VAL), vy = c.v.pos[1] - (t.llcy + (float)yy*c.DY_VAL), vz = c.adj_z - z[r][q];
+			back_facing = back_facing && (nx*vx + ny*vy + nz*vz < 0.0f);
+		}
+	}
+	return back_facing;
+}
+
+// ---- the block test (:1628-1650): GRASS_VIEW_DROPPED or lod*nrnd + bix
+TERRA_HD uint32_t grass_view_block(grass_view_consts_t const &c, grass_view_tile_t const &t, uint32_t x, uint32_t y, uint32_t ix, float zmin, float zmax, float const *zt) {
+	if (ix == 0) return GRASS_VIEW_DROPPED; // empty block
+	float const bcx1 = t.llcx + (float)x*c.dx_step, bcy1 = t.llcy + (float)y*c.dy_step;
+	float const d[3][2] = {{bcx1, bcx1 + c.dx_step}, {bcy1, bcy1 + c.dy_step}, {zmin, zmax + c.grass_length}};
+	float const dist_sq = view_closest_dist_sq(d, c.v.pos[0], c.v.pos[1], c.v.pos[2]);
+	if (dist_sq > t.bg_thresh_sq || (!t.all_visible && !view_cube_visible(c.v, d))) return GRASS_VIEW_DROPPED;
+	if ((double)dist_sq < 0.56*(double)t.bg_thresh_sq) { // only do back face culling on nearby blocks
+		if (grass_view_back_facing(c, t, x, y, zt)) return GRASS_VIEW_DROPPED;
+	}
+	uint32_t const lod = f2u_x86(c.lod_scale*sqrtf(dist_sq)), lod_level = (lod < GRASS_VIEW_LODS - 1u) ? lod : GRASS_VIEW_LODS - 1u;
+	uint32_t const bix = ix - 1u;
+	if (bix >= c.nrnd) return GRASS_VIEW_DROPPED; // assert(bix < num_rnd_grass_blocks): skipped
+	return lod_level*c.nrnd + bix;
+}
+// the aux word of a kept block: bits 0-15 y*dim + x, 16-18 the LOD, 19-31 bix
+TERRA_HD uint32_t grass_view_aux(grass_view_consts_t const &c, uint32_t block, uint32_t key) {return block | ((key / c.nrnd) << 16) | ((key % c.nrnd) << 19);}
+
+// ---- pos_dir_up's constructor (:67-85) and orthogonalize_up_dir (:87-92) with the C library's tanf / sinf / atanf.  false where the constructor asserts.
+inline bool view_make(float const pos[3], float const dir[3], float const up[3], float angle, float aspect, float near_, float far_, view_pod_t &o) {
+	if (!(near_ >= 0.0f && far_ > 0.0f && far_ > near_)) return false;
+	if (dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f) return false; // assert(dir != zero_vector)
+	double const A = (double)aspect;
+	float const tterm = tanf(angle), sterm = sinf(angle);
+	float x_sterm;
+	if (A == 1.0) {x_sterm = sterm;}
+	else {
+		if (!(tterm > 0.0f)) return false; // angle < 90
+		float atan_val = atanf((float)(A*(double)tterm));
+		if (atan_val < 0.0f) {atan_val += PI_F;}
+		x_sterm = (atan_val/angle)*sterm;
+	}
+	for (int k = 0; k < 3; ++k) {o.pos[k] = pos[k]; o.dir[k] = dir[k];}
+	// orthogonalize_dir(upv, dir, upv_, 1): cross_product(dir, cross_product(upv, dir)), normalized (pointT::normalize, src/3DWorld.h:273-279)
+	float const tx = up[1]*dir[2] - up[2]*dir[1], ty = up[2]*dir[0] - up[0]*dir[2], tz = up[0]*dir[1] - up[1]*dir[0];
+	float ux = dir[1]*tz - dir[2]*ty, uy = dir[2]*tx - dir[0]*tz, uz = dir[0]*ty - dir[1]*tx;
+	float const mag = sqrtf(ux*ux + uy*uy + uz*uz);
+	if (mag >= 1.0E-12f) {float const m = (float)(1.0/(double)mag); ux *= m; uy *= m; uz *= m;}
+	o.upv[0] = ux; o.upv[1] = uy; o.upv[2] = uz;
+	o.cp[0] = dir[1]*uz - dir[2]*uy; o.cp[1] = dir[2]*ux - dir[0]*uz; o.cp[2] = dir[0]*uy - dir[1]*ux; // cross_product(dir, upv_, cp)
+	o.sterm = sterm; o.x_sterm = x_sterm; o.near_ = near_; o.far_ = far_; o.valid = 1;
+	return true;
+}
+TERRA_HD bool view_finite(view_pod_t const &v) {
+	bool ok = isfinite(v.sterm) && isfinite(v.x_sterm) && isfinite(v.near_) && isfinite(v.far_);
+	for (int k = 0; k < 3; ++k) {ok = ok && isfinite(v.pos[k]) && isfinite(v.dir[k]) && isfinite(v.upv[k]) && isfinite(v.cp[k]);}
+	return ok;
+}
+
+} // namespace terra

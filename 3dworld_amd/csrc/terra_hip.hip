@@ -681,6 +681,17 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// the grass draw lists for a camera: one workgroup per tile (k_grass_view)
+	bool tile_grass_view(terra::grass_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, float const *zvals, terra_tile_stats const *stats,
+		terra::grass_block_pod_t const *blocks, uint8_t const *skip, uint32_t capacity, float *insts, uint32_t *aux, uint32_t *group_counts, uint32_t *counts, uint8_t *pass,
+		uint16_t *keys)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(terra::k_grass_view, dim3(n), dim3(terra::GV_THREADS), 0, stream, c, tile_xy, zvals, stats, blocks, skip, capacity, insts, aux, group_counts, counts, pass, keys);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

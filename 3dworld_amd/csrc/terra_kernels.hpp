@@ -1939,6 +1939,109 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_flowers_remove(flower_edit_co
 	if (tid == 0) {counts[t] = m;}
 }
 
+// ------------------------------------------------------------------ the grass draw lists of a tile batch for a camera (tile_t::draw_grass, src/tiled_mesh.cpp:1607-1664;
+// terra_grassview.hpp).  k_grass_view: a workgroup of 16 waves per tile.
+//  1. Every thread runs the tile test (uniform: a few dozen flops on scalars); a skipped tile and one beyond grass_thresh -- most tiles of a large batch -- read no
+//     block and leave after zeroing their group counts.
+//  2. Sweeps of 1024 blocks in scan order (one sweep at S = 128, whose latency 16 waves share): a thread runs the block test of its block (grass_view_block; the
+//     back-face test loads the block's 6 x 6 zvals before it forms the first product) and leaves the block's key -- dropped, or lod*nrnd + bix -- as 16 bits.  The
+//     first GV_LDS_KEYS keys of a tile lie in LDS (8 KB: every key up to S = 256), the rest in the tile's row of `keys` in global scratch (65 536 blocks at
+//     S = 1024 would be 128 KB, more than a workgroup should ask for): one kernel and one walk for every tile size, a chunk of 64 keys comes from one or the other.
+//     has_grass() is the OR of `ix != 0` over the sweeps, taken at the barrier that ends them.
+//  3. The stable grouping, 1024 bins at a time (one pass at the reference's 6 x 16 bins): lane l of wave w owns bin 16*l + w and keeps its running sum in a register.
+//     A wave walks the keys 64 at a time, one load a chunk, and for each of its bins takes the ballot of `key == bin`: the population count goes to the owner lane.
+//     The counts go through LDS into bin order, are scanned there (wave scans and the waves' totals), and come back to the owners as the bins' offsets;
+//     group_counts is written on the way.  A second walk of the same shape writes the instances: a matching lane's rank is its bin's running sum (read from the
+//     owner lane) plus the matches below it in the ballot.  No atomics anywhere, so the order inside a group is the scan order by construction.
+constexpr uint32_t GV_THREADS = 1024, GV_WAVES = GV_THREADS/64, GV_LDS_KEYS = 4096;
+__global__ __launch_bounds__(GV_THREADS) void k_grass_view(grass_view_consts_t c, int32_t const *__restrict__ tile_xy, float const *__restrict__ zvals,
+	terra_tile_stats const *__restrict__ stats, grass_block_pod_t const *__restrict__ blocks, uint8_t const *__restrict__ skip, uint32_t capacity, float *__restrict__ insts,
+	uint32_t *__restrict__ aux, uint32_t *__restrict__ group_counts, uint32_t *__restrict__ counts, uint8_t *__restrict__ pass, uint16_t *keys)
+{
+	__shared__ uint32_t s_cnt[GV_THREADS], s_wave[GV_WAVES];
+	__shared__ uint16_t s_keys[GV_LDS_KEYS];
+	uint32_t const t = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	uint32_t const dim = c.dim, nb = dim*dim, nbins = GRASS_VIEW_LODS*c.nrnd;
+	uint32_t *const gc = group_counts + (size_t)t*nbins;
+	uint16_t *const ky = keys + (size_t)t*nb;
+	float const mzmin = stats[t].mzmin, mzmax = stats[t].mzmax, radius = stats[t].radius;
+	line_box_t const box = grass_view_box(c, tile_xy[2u*t], tile_xy[2u*t + 1u], mzmin, mzmax);
+	grass_view_tile_t const tl = grass_view_tile(c, box.d, box.x1, box.y1, mzmin, mzmax, radius);
+	int has = 0;
+	if (!(skip && skip[t]) && tl.in_range) { // (uniform)
+		size_t const zn = (size_t)(c.S + 2)*(size_t)(c.S + 2);
+		float const *const zt = zvals + (size_t)t*zn;
+		grass_block_pod_t const *const bl = blocks + (size_t)t*nb;
+		for (uint32_t base = 0; base < nb; base += GV_THREADS) {
+			uint32_t const i = base + tid;
+			if (i < nb) {
+				grass_block_pod_t const gb = bl[i];
+				has |= (gb.ix != 0u);
+				uint16_t const key = (uint16_t)grass_view_block(c, tl, i % dim, i / dim, gb.ix, gb.zmin, gb.zmax, zt);
+				if (i < GV_LDS_KEYS) {s_keys[i] = key;} else {ky[i] = key;}
+			}
+		}
+	}
+	if (!__syncthreads_or(has)) { // skipped, too far away or no grass: nothing is drawn (the keys were not all written: they are not read)
+		for (uint32_t b = tid; b < nbins; b += GV_THREADS) {gc[b] = 0u;}
+		if (tid == 0) {counts[t] = 0u; if (pass) {pass[t] = GRASS_VIEW_NO_PASS;}}
+		return;
+	}
+	if (tid == 0 && pass) {pass[t] = (uint8_t)tl.wpass;}
+	auto key_at = [&](uint32_t j) -> uint32_t {return (j < nb) ? (uint32_t)((j < GV_LDS_KEYS) ? s_keys[j] : ky[j]) : GRASS_VIEW_DROPPED;}; // (one source per chunk of 64)
+	float *const my_insts = insts + (size_t)t*capacity*2u;
+	uint32_t *const my_aux = aux ? aux + (size_t)t*capacity : nullptr;
+	uint64_t const below = (1ull << lane) - 1ull;
+	uint32_t carry = 0; // the instances of the bins before b0
+	for (uint32_t b0 = 0; b0 < nbins; b0 += GV_THREADS) {
+		uint32_t const rem = nbins - b0, nl = (rem > wave) ? min_u32(64u, (rem - wave + GV_WAVES - 1u)/GV_WAVES) : 0u; // this wave's bins: b0 + 16*l + wave for l < nl
+		uint32_t cnt = 0;
+		for (uint32_t j0 = 0; j0 < nb && nl; j0 += 64u) {
+			uint32_t const k = key_at(j0 + lane);
+			if (__ballot(k != GRASS_VIEW_DROPPED) == 0ull) continue;
+			for (uint32_t l = 0; l < nl; ++l) {
+				uint64_t const m = __ballot(k == b0 + GV_WAVES*l + wave);
+				if (lane == l) {cnt += (uint32_t)__popcll(m);}
+			}
+		}
+		s_cnt[GV_WAVES*lane + wave] = cnt; // into bin order
+		__syncthreads();
+		uint32_t const v = s_cnt[tid];
+		uint32_t incl = v;
+		for (uint32_t d = 1; d < 64u; d <<= 1) {uint32_t const u = __shfl_up(incl, d); if (lane >= d) {incl += u;}}
+		if (lane == 63u) {s_wave[wave] = incl;}
+		if (b0 + tid < nbins) {gc[b0 + tid] = v;}
+		__syncthreads();
+		uint32_t before = 0, total = 0;
+		for (uint32_t w = 0; w < GV_WAVES; ++w) {uint32_t const sw = s_wave[w]; if (w < wave) {before += sw;} total += sw;}
+		s_cnt[tid] = carry + before + incl - v; // the bin's offset (each thread overwrites the count it alone has read)
+		carry += total;
+		__syncthreads();
+		uint32_t pos = s_cnt[GV_WAVES*lane + wave];
+		for (uint32_t j0 = 0; j0 < nb && nl; j0 += 64u) {
+			uint32_t const j = j0 + lane, k = key_at(j);
+			if (__ballot(k != GRASS_VIEW_DROPPED) == 0ull) continue;
+			uint32_t const x = j % dim, y = j / dim;
+			for (uint32_t l = 0; l < nl; ++l) {
+				uint32_t const bin = b0 + GV_WAVES*l + wave;
+				uint64_t const m = __ballot(k == bin);
+				if (m == 0ull) continue;
+				uint32_t const at = (uint32_t)__builtin_amdgcn_readlane((int)pos, (int)l);
+				if (k == bin) {
+					uint32_t const rank = at + (uint32_t)__popcll(m & below);
+					if (rank < capacity) {
+						my_insts[2u*rank] = (float)x*c.dx_step; my_insts[2u*rank + 1u] = (float)y*c.dy_step; // emplace_back(x*dx_step, y*dy_step) (:1651)
+						if (my_aux) {my_aux[rank] = grass_view_aux(c, j, bin);}
+					}
+				}
+				if (lane == l) {pos += (uint32_t)__popcll(m);}
+			}
+		}
+		__syncthreads(); // the next pass rewrites s_cnt and s_wave
+	}
+	if (tid == 0) {counts[t] = carry;}
+}
+
 // ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
 // terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
 // k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes

@@ -124,6 +124,30 @@ def make_flower_params(flower_density=0.0, grass_length=0.02, grass_width=0.002,
     return FlowerParams(flower_density, grass_length, grass_width, (C.c_float * 4)(*flower_color), int(bool(no_grass)))
 
 
+class View(C.Structure):  # terra_view: pos_dir_up's pos, dir, upv_, cp, sterm, x_sterm, near_, far_, valid
+    _fields_ = [("pos", C.c_float * 3), ("dir", C.c_float * 3), ("upv", C.c_float * 3), ("cp", C.c_float * 3), ("sterm", C.c_float), ("x_sterm", C.c_float),
+                ("near_", C.c_float), ("far_", C.c_float), ("valid", C.c_int32)]
+
+
+class GrassViewParams(C.Structure):  # terra_grass_view_params
+    _fields_ = [("tt_grass_scale_factor", C.c_float)]
+
+
+def make_grass_view_params(tt_grass_scale_factor=1.0):
+    """terra_grass_view_params with the reference's default."""
+    return GrassViewParams(tt_grass_scale_factor)
+
+
+GRASS_VIEW_LODS = 6      # NUM_GRASS_LODS
+GRASS_VIEW_NO_PASS = 255  # the pass byte of a tile that draws nothing
+
+
+def grass_view_aux_fields(aux):
+    """the aux words of tiles_grass_view -> (block index y*dim + x, LOD, bix)"""
+    aux = np.asarray(aux, np.uint32)
+    return aux & 0xFFFF, (aux >> 16) & 7, aux >> 19
+
+
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
@@ -315,6 +339,11 @@ _PROTOS = {
     "terra_tiles_place_flowers": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_edit_flowers_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "terra_tiles_edit_flowers": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "terra_make_view": (_i32, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "terra_set_grass_view_params": (_i32, [_vp, _vp]),
+    "terra_get_grass_view_params": (_i32, [_vp, _vp]),
+    "terra_tiles_grass_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_grass_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -912,6 +941,39 @@ class Terra:
                                                    flowers.ctypes.data if capacity else None, None if aux is None else aux.ctypes.data, counts.ctypes.data, status.ctypes.data))
         return status
 
+    def make_view(self, pos, dir, up, angle, aspect, near, far):
+        """pos_dir_up's constructor (terra_make_view; no context is involved) -> View"""
+        v = View()
+        f3 = lambda a: (C.c_float * 3)(*a)  # noqa: E731
+        self._ck(self.lib.terra_make_view(f3(pos), f3(dir), f3(up), angle, aspect, near, far, C.byref(v)))
+        return v
+
+    def set_grass_view_params(self, gvp):
+        self._ck(self.lib.terra_set_grass_view_params(self.ctx, C.byref(gvp)))
+
+    def get_grass_view_params(self):
+        gvp = GrassViewParams()
+        self._ck(self.lib.terra_get_grass_view_params(self.ctx, C.byref(gvp)))
+        return gvp
+
+    def tiles_grass_view(self, tile_xy, zvals, stats, grass_blocks, view, capacity, skip=None, aux=True, want_pass=True, dxoff=0, dyoff=0):
+        """tile_t::draw_grass' lists for every tile.  zvals [n, S+2, S+2] float32, stats TileStats * n, grass_blocks [n, dim, dim] GRASS_BLOCK_DTYPE, skip [n] bytes.
+        -> (insts float32 [n, capacity, 2], aux uint32 [n, capacity] or None, group_counts uint32 [n, 6, num_rnd_grass_blocks], counts uint32 [n], pass uint8 [n] or
+        None); instances past counts[t] are zero.  num_rnd_grass_blocks is read from the context's landscape"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        z = np.ascontiguousarray(zvals, np.float32)
+        gb = np.ascontiguousarray(grass_blocks, GRASS_BLOCK_DTYPE)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        insts, counts = np.zeros((n, capacity, 2), np.float32), np.zeros(n, np.uint32)
+        gc = np.zeros((n, GRASS_VIEW_LODS, max(1, int(self.get_landscape().num_rnd_grass_blocks))), np.uint32)
+        ax = np.zeros((n, capacity), np.uint32) if aux else None
+        ps = np.zeros(n, np.uint8) if want_pass else None
+        self._ck(self.lib.terra_tiles_grass_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, z.ctypes.data, C.addressof(stats) if n else None, gb.ctypes.data,
+                                                 None if sk is None else sk.ctypes.data, C.byref(view), capacity, insts.ctypes.data if capacity else None,
+                                                 None if ax is None else ax.ctypes.data, gc.ctypes.data, counts.ctypes.data, None if ps is None else ps.ctypes.data))
+        return insts, ax, gc, counts, ps
+
     def set_tree_size_params(self, tsp):
         self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
 
@@ -1170,6 +1232,14 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_edit_flowers_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, generated_ptr, C.byref(brush), updated_ptr, ranges_ptr, weights_ptr,
                                                        capacity, flowers_ptr, aux_ptr, counts_ptr, status_ptr))
+
+    def tiles_grass_view_dev(self, tile_xy, zvals_ptr, stats_ptr, grass_blocks_ptr, view, capacity, insts_ptr, group_counts_ptr, counts_ptr, aux_ptr=None, pass_ptr=None,
+                             skip_ptr=None, dxoff=0, dyoff=0):
+        """the grass draw lists of a device-resident batch: insts_ptr [n][capacity][2] floats, group_counts_ptr [n][6][num_rnd_grass_blocks] uint32, counts_ptr [n]
+        uint32, aux_ptr [n][capacity] uint32 or None, pass_ptr / skip_ptr [n] bytes or None.  view is a host View.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_grass_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, zvals_ptr, stats_ptr, grass_blocks_ptr, skip_ptr, C.byref(view), capacity,
+                                                     insts_ptr, aux_ptr, group_counts_ptr, counts_ptr, pass_ptr))
 
     def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
                                   decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,

@@ -777,6 +777,54 @@ int  terra_tiles_edit_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
                               const terra_grass_brush *brush, const uint8_t *h_updated, const uint32_t *h_ranges, const uint8_t *h_weights, uint32_t capacity,
                               terra_flower *h_flowers, uint32_t *h_aux, uint32_t *h_counts, uint8_t *h_status);
 
+/* ---- the grass draw lists of a tile batch for a camera (every supported tile size S that is a multiple of 4): tile_t::draw_grass (src/tiled_mesh.cpp:1607-1664)
+ * without its GL calls, behind the per-tile filters of its caller tile_draw_t::draw_grass (:3420-3425) -- the library's first view-dependent call.  It answers for
+ * every tile of a batch which of its grass blocks are drawn from this camera, at what LOD, and in what order the instanced draws take them, bit for bit.
+ * terra_view: the members of pos_dir_up (src/3DWorld.h:705-711) that the view tests read.  An engine copies camera_pdu's pos, dir, upv_ (the orthogonalized up
+ * vector, NOT upv), cp, sterm, x_sterm, near_, far_ and valid into it; valid == 0 makes every frustum test pass, as in the reference.
+ * terra_make_view: pos_dir_up's constructor (src/visibility.cpp:67-92) with the C library's tanf / sinf / atanf, for callers without a camera_pdu.  angle (radians,
+ * half the vertical field of view) and aspect are the caller's: the window_width / PERSP_ANGLE defaults that the constructor takes for 0 stay with the engine.
+ * TERRA_ERR_ARG where the constructor asserts (near < 0, far <= near, a zero dir, tanf(angle) <= 0 with aspect != 1) and for a NULL pointer; *out is untouched then.
+ * terra_grass_view_params: tt_grass_scale_factor (1).  TERRA_ERR_ARG for a value that is not finite and > 0 (src/grass.cpp:1126 resets such a value to 1; here it is
+ * refused and nothing changes).  grass_length is terra_flower_params.grass_length, num_rnd_grass_blocks the landscape's.
+ * Per tile: skipped (skip[t] != 0: the tile is not in the engine's to_draw), or get_min_dist_to_pt(camera) > get_grass_thresh_pad() (:1612), or every block's
+ * ix == 0 (the reference's empty grass_blocks: !has_grass(), :1609 and :3422) -> nothing is drawn: counts[t] = 0, its group counts are 0, pass[t] = 255.  Otherwise
+ * pass[t] is the wpass of :3424 in which the tile is drawn -- 1 where get_dist_to_camera_in_tiles(0) > 0.5*tt_grass_scale_factor (no wind), else 0 (wind) -- and every
+ * block runs :1628-1651: empty; closest_pt_dist_sq(camera) against bg_thresh_sq; cube_visible unless the tile's mesh box is completely visible; for blocks nearer
+ * than 0.56*bg_thresh_sq the back-face test over its 25 texels' zvals and slopes against the camera raised by 2*grass_length; the LOD
+ * min(5, unsigned(lod_scale*sqrt(dist_sq))); bix = ix - 1.  Where the reference asserts (bix >= num_rnd_grass_blocks, :1650) the block is skipped.
+ * Inputs.  tile_xy is on the host.  dxoff / dyoff = xoff - xoff2 / yoff - yoff2 as for the line queries.  zvals: [n][S+2][S+2].  stats: [n], of which mzmin, mzmax
+ * and radius are read (the engine may have enlarged radius).  grass_blocks: [n][dim][dim] with dim = 1 + (S-1)/4, the layout terra_tiles_create_weights writes at
+ * S = 128 and terra_tiles_edit_grass keeps.  skip (optional): [n] bytes.  view is a host struct read at the call, like the brushes.
+ * Outputs.  insts: [n][capacity] pairs of floats {x*dx_step, y*dy_step}, the layout of the reference's vector2d, in the reference's DRAW ORDER: LOD 0 .. 5, within a
+ * LOD block index 0 .. num_rnd_grass_blocks - 1, within such a group the (y, x) scan order of :1626-1627.  An engine uploads a tile's row as its instance buffer
+ * and walks group_counts: [n][6][num_rnd_grass_blocks], the v.size() of :1659.  counts: [n] totals.  Only the first `capacity` instances of a tile are written;
+ * counts and group_counts still report all; records past the count are not written.  aux (optional): [n][capacity] words, bits 0-15 the block's y*dim + x, bits
+ * 16-18 the LOD, bits 19-31 bix.  pass (optional): [n] bytes, see above.
+ * With the engine stay the shaders, the texture binds, render_block and the using_shadow_maps() split of :3423.
+ * TERRA_ERR_ARG: an unsupported S; an S that is not a multiple of 4 (dim = 1 + (S-1)/4 rounds up, and the back-face loop of :1638-1641 runs to texel (y+1)*4 of
+ * the last block row, whose slopes would read past the (S+2)^2 zvals: the reference reads out of bounds there); a view with a non-finite member;
+ * num_rnd_grass_blocks equal to 0 or above 4096; a NULL required pointer (view; tile_xy, zvals, stats, grass_blocks, counts, group_counts when n > 0; insts when capacity > 0); a
+ * misaligned pointer (4 bytes).  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the scene, the tile size and the view have passed.  The device
+ * form only enqueues; the host form refuses bad arguments before it stages anything. */
+typedef struct terra_view {
+	float pos[3], dir[3], upv[3] /* upv_ */, cp[3];
+	float sterm, x_sterm, near_, far_;
+	int32_t valid;
+} terra_view;
+typedef struct terra_grass_view_params {
+	float tt_grass_scale_factor; /* 1 */
+} terra_grass_view_params;
+int  terra_make_view(const float pos[3], const float dir[3], const float up[3], float angle, float aspect, float near_clip, float far_clip, terra_view *out);
+int  terra_set_grass_view_params(terra_ctx *ctx, const terra_grass_view_params *params);
+int  terra_get_grass_view_params(terra_ctx *ctx, terra_grass_view_params *out);
+int  terra_tiles_grass_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *d_zvals, const terra_tile_stats *d_stats,
+                                const terra_grass_block *d_grass_blocks, const uint8_t *d_skip, const terra_view *view, uint32_t capacity, float *d_insts, uint32_t *d_aux,
+                                uint32_t *d_group_counts, uint32_t *d_counts, uint8_t *d_pass);
+int  terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *h_zvals, const terra_tile_stats *h_stats,
+                            const terra_grass_block *h_grass_blocks, const uint8_t *h_skip, const terra_view *view, uint32_t capacity, float *h_insts, uint32_t *h_aux,
+                            uint32_t *h_group_counts, uint32_t *h_counts, uint8_t *h_pass);
+
 /* ---- tree AO shadows of a tile batch from the placement records (every supported tile size S): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828), the step
  * between the two placements above and terra_tiles_shadow_texture / terra_tiles_tree_weights.  One call goes from the records as they lie in device memory to the
  * tree maps of the batch, bit for bit; with it zvals -> stats -> both placements -> tree map -> shadow texture / tree weights is one stream of launches.

@@ -314,6 +314,27 @@ inline void tiles_update_flowers_at(tile_batch_dev_t const &b, unsigned char con
 	check(terra_tiles_edit_flowers_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, d_generated, &br, d_updated, d_ranges, d_weight_data, capacity, d_flowers, d_aux, d_counts,
 		d_status), "flowers.update_subrange / clear_within");
 }
+// ---- the grass draw lists of a batch for the camera.  tt_grass_scale_factor goes in once (set_grass_view_globals); grass_length is set_flower_globals'.
+inline void set_grass_view_globals(float tt_grass_scale_factor) {
+	terra_grass_view_params const p = {tt_grass_scale_factor};
+	check(terra_set_grass_view_params(default_ctx(), &p), "set_grass_view_params");
+}
+// camera_pdu as the library reads it: pos, dir, upv_, cp, sterm, x_sterm, near_, far_, valid
+inline terra_view view_of(float const pos[3], float const dir[3], float const upv_[3], float const cp[3], float sterm, float x_sterm, float near_, float far_, bool valid) {
+	terra_view v;
+	for (int k = 0; k < 3; ++k) {v.pos[k] = pos[k]; v.dir[k] = dir[k]; v.upv[k] = upv_[k]; v.cp[k] = cp[k];}
+	v.sterm = sterm; v.x_sterm = x_sterm; v.near_ = near_; v.far_ = far_; v.valid = valid ? 1 : 0;
+	return v;
+}
+// tile_t::draw_grass (src/tiled_mesh.cpp:1607-1664) for every tile of the batch as tile_draw_t::draw_grass (:3420-3425) calls it, up to the GL calls: d_insts[t] is
+// the tile's instance buffer in draw order, d_group_counts[t][lod][bix] the v.size() of each render_block call, d_pass[t] the wpass the tile is drawn in (255: not at
+// all).  d_not_drawn[t] != 0 (or null): the tile is not in to_draw.  The using_shadow_maps() split, the shaders, the texture binds and render_block stay with the engine
+inline void tile_draw_grass_lists(tile_batch_dev_t const &b, terra_grass_block const *d_grass_blocks, unsigned char const *d_not_drawn, terra_view const &camera_pdu, unsigned capacity, float *d_insts, unsigned *d_aux, unsigned *d_group_counts, unsigned *d_counts,
+	unsigned char *d_pass)
+{
+	check(terra_tiles_grass_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, b.d_zvals, b.d_stats, d_grass_blocks, d_not_drawn, &camera_pdu, capacity, d_insts, d_aux,
+		d_group_counts, d_counts, d_pass), "tile_t::draw_grass");
+}
 // tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:820-828) for every tile of the batch in batch order, from the records tiles_gen_trees / tiles_gen_decid_trees left
 // on the device: small_tree::get_radius / get_ao_radius and tree::get_ao_radius per record, apply_ao_shadows_for_trees' own loop, pulls and pushes, add_tree_ao_shadow's
 // texel loop.  xoff2 / yoff2: what the placements ran with (ptree_off / dtree_off).  d_sphere_radius [n][decid_capacity] (tdata().sphere_radius per record) or
