@@ -239,6 +239,14 @@ int terra_gen_grid_minmax_async_dev(terra_ctx *ctx, float x0, float y0, float dx
 	TERRA_CHECK_CTX if (!d_out || !d_minmax) return terra::fail(TERRA_ERR_ARG, "null output");
 	TERRA_TRY ctx->eng.gen_grid_dev(x0, y0, dx, dy, nx, ny, flags, min_start_sin, d_out, nullptr, 0, 0xFFFFFFFFu, d_minmax); TERRA_CATCH
 }
+int terra_gen_grid_minmax_turn_dev(terra_ctx *ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *d_out, float *d_minmax, terra_event *wait_for, terra_event *turn) {
+	TERRA_CHECK_CTX if (!d_out || !d_minmax) return terra::fail(TERRA_ERR_ARG, "null output");
+	TERRA_TRY
+		terra::noise_turn_t nt;
+		nt.wait_for = wait_for ? wait_for->ev : nullptr; nt.record = turn ? turn->ev : nullptr; nt.rows = ctx->eng.turn_rows(ny);
+		ctx->eng.gen_grid_dev(x0, y0, dx, dy, nx, ny, flags, min_start_sin, d_out, nullptr, 0, 0xFFFFFFFFu, d_minmax, &nt);
+	TERRA_CATCH
+}
 int terra_gen_grid_rows_minmax_dev(terra_ctx *ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, uint32_t row0, uint32_t nrows, float *d_out, float *h_min, float *h_max) {
 	TERRA_CHECK_CTX if (!d_out) return terra::fail(TERRA_ERR_ARG, "null output");
 	TERRA_TRY

@@ -46,7 +46,16 @@ struct grid_job_t { // one build_arrays() + eval loop
 	int fused = 0; // TERRA_GEN_FUSED (tolerance mode; sine mode with plain_only): every multiply-add of the sum and of the tail rounds once (sine_cell_fused / finish_cell_fused); 2 = TERRA_GEN_FAST
 	float fast_amax = 0.0f; // TERRA_GEN_FAST: the largest |value| the y table can hold (its power-of-two scale on the half-precision matrix pipe, terra_fused.hpp)
 	uint32_t row0 = 0; // the job covers rows [row0, row0 + ny) of a taller grid (row strips of one heightmap on several GPUs): cell row y is eval_index's y + row0
+	uint32_t ty0 = 0, tyn = 0; // sine mode, heightmaps: this launch evaluates tile rows [ty0, ty0 + tyn) of the job's grid only (a tile row = 128 rows); tyn = 0: the whole grid.  Everything else stays in whole-grid terms
 };
+// the tile rows of a job's window as rows [first, end) of its grid
+TERRA_HD uint32_t job_window_first(grid_job_t const &job) {return job.tyn ? job.ty0*128u : 0u;}
+TERRA_HD uint32_t job_window_end(grid_job_t const &job) {uint64_t const e = ((uint64_t)job.ty0 + job.tyn)*128u; return (job.tyn && e < job.ny) ? (uint32_t)e : job.ny;}
+// the noise turn of a heightmap among several in flight (terra_gen_grid_minmax_turn_dev): the host waits for `wait_for` (the turn event of the map before) in front of
+// the map's first launch, and `record` is recorded while the last `rows` rows of the grid are still to be evaluated -- so the next map's thread wakes, and its tables and
+// first grid blocks arrive, while this map's tail drains.  Events are the backend's (event_create).
+constexpr uint32_t SG_TURN_ROWS = 2048; // "sg.turn_rows" default: two chip generations of k_sine_grid blocks on a 16384-wide map (2 x 1024 blocks = 16 tile rows, ~98 us): the shortest tail that outlasts the next map's wake-up + table launch + dispatch (~60 us); measured best of 0 / 512 / 1024 / 1536 / 2048 (profiles/r07_turn_rows_sweep.txt)
+struct noise_turn_t {void *wait_for = nullptr, *record = nullptr; uint32_t rows = 0;};
 
 // noise_gen_3d constants (src/upsurface.h:10-16)
 constexpr unsigned VOX_SINES = 60, VOX_PARAMS = 7;
@@ -447,6 +456,7 @@ struct options_t {
 	int graphs = 1;               // "graphs" 0 / 1: replay the erosion rounds as hipGraphs
 	int sg_kc = 27, sg_kc_tiles = 27; // "sg.kc" 20 / 27 / 45, "sg.kc_tiles" 27 / 45: terms per LDS chunk of k_sine_grid (heightmap / tile batch)
 	int sg_rowgroup = 4;          // "sg.rowgroup" 1..1024: tile rows walked together by k_sine_grid
+	int sg_turn_rows = -1;        // "sg.turn_rows" n | "default": rows of a heightmap still to evaluate when its noise turn is handed on (terra_gen_grid_minmax_turn_dev), rounded up to whole tile rows; 0: no split; -1 = "default": SG_TURN_ROWS on grids of at least 8 x that many rows
 	int tile_erosion_window = 0;  // "tile_erosion" "lds" / "window": tile erosion through the 32 x 32 window over an HBM copy instead of the whole tile in LDS
 	int weights_simple = 0;       // "weights.simple" 0 / 1: the per-texel form of the weights-texture pass (cross-check of k_tile_weights)
 	int shadows_levels = 0;       // "shadows.levels" 0 / 1: one launch per dependency level instead of the one dataflow launch (cross-check)
@@ -477,6 +487,7 @@ struct options_t {
 		if (k == "sg.kc") {if (!is_int || (n != 20 && n != 27 && n != 45)) return false; sg_kc = (int)n; return true;}
 		if (k == "sg.kc_tiles") {if (!is_int || (n != 27 && n != 45)) return false; sg_kc_tiles = (int)n; return true;}
 		if (k == "sg.rowgroup") {if (!is_int || n < 1 || n > 1024) return false; sg_rowgroup = (int)n; return true;}
+		if (k == "sg.turn_rows") {if (v == "default") {sg_turn_rows = -1; return true;} if (!is_int || n < 0 || n > (1 << 30)) return false; sg_turn_rows = (int)n; return true;}
 		if (k == "tile_erosion") {if (v == "lds") {tile_erosion_window = 0; return true;} if (v == "window") {tile_erosion_window = 1; return true;} return false;}
 		if (k == "weights.simple") return flag(weights_simple);
 		if (k == "shadows.levels") return flag(shadows_levels);
@@ -537,6 +548,8 @@ template<class BE> struct terra_engine {
 	BE be;
 	options_t opt;
 	terra_engine() {be.opt = &opt;}
+	// rows handed over early by a map of ny rows ("sg.turn_rows"): a value that was set applies as it is (tests force a split on small grids), the default only to grids of at least 8 x as many rows
+	uint32_t turn_rows(uint32_t ny) const {return (opt.sg_turn_rows >= 0) ? (uint32_t)opt.sg_turn_rows : ((uint64_t)ny >= 8ull*SG_TURN_ROWS ? SG_TURN_ROWS : 0u);}
 	void set_option(char const *key, char const *value) {
 		options_t o = opt;
 		if (!o.set(key, value)) throw std::invalid_argument(std::string("terra_set_option: unknown key or bad value: ") + (key ? key : "(null)") + " = " + (value ? value : "(null)"));
@@ -867,7 +880,10 @@ template<class BE> struct terra_engine {
 	// full-grid call produces (the tables and cell coordinates use the row's index in the whole grid), so row strips evaluated on different GPUs tile the
 	// heightmap exactly (heightmap_t::proc_gen's loop is row-independent, src/heightmap.cpp:139-143)
 	// d_minmax (optional): DEVICE float[2] that receives {min, max} without the host ever seeing them (an enqueue-only proc_gen step: terra_apply_erosion_devmin_dev reads it)
-	void gen_grid_dev(float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *d_out, float *h_minmax = nullptr, uint32_t row0 = 0, uint32_t nrows = 0xFFFFFFFFu, float *d_minmax = nullptr) {
+	// turn (optional): the map's noise turn (noise_turn_t).  Sine mode on the exact kernel: tables -> grid kernel over all but the last turn->rows rows -> record -> grid kernel
+	// over the last rows; the same cells and the same atomics into s_mm (reset by the table launch, once per map), so the same bits.  No split -- the event is recorded right
+	// behind the grid kernel, in front of the min / max conversion -- when rows is 0 or covers the grid, in the fBm modes, and for the fused kernels (persistent blocks)
+	void gen_grid_dev(float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *d_out, float *h_minmax = nullptr, uint32_t row0 = 0, uint32_t nrows = 0xFFFFFFFFu, float *d_minmax = nullptr, noise_turn_t const *turn = nullptr) {
 		require_scene();
 		if (nx == 0 || ny == 0) throw std::invalid_argument("build_arrays: nx, ny must be > 0"); // assert(nx > 0 && ny > 0), src/mesh_gen.cpp:589
 		if (nrows == 0xFFFFFFFFu) {if (row0 != 0) throw std::invalid_argument("gen_grid rows: row0 without a row count"); nrows = ny;}
@@ -889,6 +905,7 @@ template<class BE> struct terra_engine {
 		float *smx = scratch<float>(s_smx, job.nxp), *smy = scratch<float>(s_smy, job.nyp);
 		uint32_t *d_mm = nullptr;
 		bool const sine = (job.mode == MGEN_SINE);
+		if (turn && turn->wait_for) {BE::event_synchronize(turn->wait_for);} // the noise of the map before has (all but) left the chip: nothing of this map is enqueued earlier
 		if (h_minmax || d_minmax || sine) {d_mm = scratch<uint32_t>(s_mm, 2); if (!sine) {be.fill32(d_mm, 0xFFFFFFFFu, 2);}} // (sine mode: reset by the table launch)
 		bool fused;
 		bool const sm_on = job.use_sine_mag != 0;
@@ -933,9 +950,25 @@ template<class BE> struct terra_engine {
 					else {unsigned const y = (unsigned)(q - nxp); smy[y] = (y < ny) ? L.COSF(((float)(y + row0)*mdy + jmy0)*dyi*sm_freq) : 0.0f;}
 				}
 			});
-			fused = be.sine_grid(job, nc, L, xt, yt, smx, smy, d_out, (h_minmax || d_minmax) ? d_mm : nullptr);
+			uint32_t *const mm_arg = (h_minmax || d_minmax) ? d_mm : nullptr;
+			uint32_t const nty = (ny + 127u)/128u, tail = (turn && turn->record && !job.fused) ? std::min((turn->rows + 127u)/128u, nty) : 0u;
+			if (tail > 0 && tail < nty) {
+				grid_job_t part = job;
+				part.ty0 = 0; part.tyn = nty - tail;
+				fused = be.sine_grid(part, nc, L, xt, yt, smx, smy, d_out, mm_arg);
+				be.event_record(turn->record);
+				part.ty0 = nty - tail; part.tyn = tail;
+				be.sine_grid(part, nc, L, xt, yt, smx, smy, d_out, mm_arg);
+			}
+			else {
+				fused = be.sine_grid(job, nc, L, xt, yt, smx, smy, d_out, mm_arg);
+				if (turn && turn->record) {be.event_record(turn->record);}
+			}
 		}
-		else {fused = be.noise_grid(job, nc, L, smx, smy, d_out, (h_minmax || d_minmax) ? d_mm : nullptr, d_noise_lut);}
+		else {
+			fused = be.noise_grid(job, nc, L, smx, smy, d_out, (h_minmax || d_minmax) ? d_mm : nullptr, d_noise_lut);
+			if (turn && turn->record) {be.event_record(turn->record);}
+		}
 		if ((h_minmax || d_minmax) && !fused) {be.minmax(d_out, (size_t)nx*ny, d_mm);}
 		if (d_minmax) {uint32_t const *mm = d_mm; be.launch(1, [=] TERRA_LAMBDA (size_t) {d_minmax[0] = ord2f(mm[0]); d_minmax[1] = ord2f(~mm[1]);}, 64);}
 		if (h_minmax) {

@@ -287,7 +287,9 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	bool sine_grid(terra::grid_job_t const &job, terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float const *xt, float const *yt, float const *smx, float const *smy, float *out, uint32_t *mm) {
 		if (simple_kernels) {sine_grid_simple(job, nc, L, xt, yt, smx, smy, out); return false;}
 		use();
-		unsigned const ntx = job.nxp/terra::SG_BX, nty = (job.ny + terra::SG_BY - 1)/terra::SG_BY;
+		unsigned const ntx = job.nxp/terra::SG_BX, nty_all = (job.ny + terra::SG_BY - 1)/terra::SG_BY;
+		if ((job.tyn || job.ty0) && (job.fused || job.tyn == 0 || job.ty0 >= nty_all || job.tyn > nty_all - job.ty0)) throw std::invalid_argument("sine_grid: a tile-row window must lie inside the grid (the fused kernels take whole grids only)");
+		unsigned const nty = job.tyn ? job.tyn : nty_all; // the launch's tile rows: the kernel adds job.ty0 (grid_job_t: a window of the grid, the whole of it by default)
 		unsigned const nb = ntx*nty, grid = ((nb + 7)/8)*8;
 		if (job.fused) { // TERRA_GEN_FUSED: the sum on the f32 matrix pipe, persistent blocks (two per CU: 225 registers per lane)
 			terra::sgf_job_t J; memset(&J, 0, sizeof(J));

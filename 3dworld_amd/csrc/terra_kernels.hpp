@@ -109,7 +109,8 @@ template<bool TILES, bool GENERAL, int KC = SG_KC> __global__ __launch_bounds__(
 	__shared__ __attribute__((aligned(16))) float sX[(KC + 2)*SG_BX];
 	__shared__ __attribute__((aligned(16))) float sY[(KC + 2)*SG_BY];
 	unsigned bxi, byi;
-	if (!sg_tile_of_block(blockIdx.x, ntx, nty, tiles.rowgroup, bxi, byi)) return;
+	if (!sg_tile_of_block(blockIdx.x, ntx, nty, tiles.rowgroup, bxi, byi)) return; // (nty: the tile rows of this launch, walked in XCD band order)
+	if (!TILES) {byi += job.ty0;} // a heightmap launch may cover a window of the grid's tile rows (grid_job_t::ty0, tyn): everything below is in whole-grid terms
 	uint32_t mm_lo = 0xFFFFFFFFu, mm_hi = 0xFFFFFFFFu; // fused min(vals)/max(vals) (heightmap_t::run_erosion, get_heightmap_z_range): saves a 4 B/cell read pass
 	unsigned const tid = threadIdx.x, bx0 = bxi*SG_BX, by0 = byi*SG_BY;
 	unsigned const tx = tid & 15, ty = tid >> 4;

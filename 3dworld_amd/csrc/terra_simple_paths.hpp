@@ -10,7 +10,11 @@ template<class DERIVED> struct simple_paths {
 	DERIVED &self() {return *static_cast<DERIVED *>(this);}
 
 	void sine_grid_simple(grid_job_t const &job, noise_consts_t const &nc, sin_lut_t const &L, float const *xt, float const *yt, float const *smx, float const *smy, float *out) {
-		self().launch((size_t)job.nx*job.ny, [=] TERRA_LAMBDA (size_t i) {
+		uint32_t const y0 = job_window_first(job), y1 = job_window_end(job); // (grid_job_t::ty0, tyn: the rows of the job's window, all of them by default)
+		if (y0 >= y1) throw std::invalid_argument("sine_grid: the job's tile-row window lies outside its grid");
+		size_t const first = (size_t)y0*job.nx;
+		self().launch((size_t)job.nx*(y1 - y0), [=] TERRA_LAMBDA (size_t j) {
+			size_t const i = first + j;
 			unsigned const x = (unsigned)(i % job.nx), y = (unsigned)(i / job.nx);
 			out[i] = job.fused ? finish_cell_fused(sine_cell_fused(job, xt, yt, x, y), job, nc, smx, smy, x, y) : finish_cell(sine_cell(job, xt, yt, x, y), job, nc, L, smx, smy, x, y);
 		});

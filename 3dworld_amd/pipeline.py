@@ -3,9 +3,10 @@ context (stream, scratch) and host thread and runs heightmap_t::proc_gen's devic
 
 A map's erosion is a chain of dependent droplet steps on a few hundred waves; the NEXT map's noise kernel (vector-ALU bound, fills the chip) runs beside it.  Two noise kernels
 at once only share the chip and finish together, so the maps take turns in their noise phase -- and the turn is handed over by the GPU itself: the thread of the next map waits
-(terra_event_synchronize, on the host) for the event recorded right behind the previous map's noise kernel, not for the thread that launched that kernel to wake up, read
-min(vals) back and release a semaphore (~65 us of the ~90 us between two noise kernels, profiles/r05_timeline_sparse_v2.txt).  min(vals) stays in device memory
-(terra_gen_grid_minmax_async_dev -> terra_apply_erosion_devmin_dev): a map's erosion is enqueued directly behind its noise, no host round trip in between."""
+on the host for the previous map's turn event, not for the thread that launched that kernel to wake up, read min(vals) back and release a semaphore (~65 us of the ~90 us
+between two noise kernels, profiles/r05_timeline_sparse_v2.txt).  The event is recorded in FRONT of the map's last rows (terra_gen_grid_minmax_turn_dev: the grid kernel runs
+as two launches, option "sg.turn_rows"), so the next map's thread wakes, builds its tables and dispatches its grid kernel while those rows drain from the chip.  min(vals)
+stays in device memory (-> terra_apply_erosion_devmin_dev): a map's erosion is enqueued directly behind its noise, no host round trip in between."""
 import threading
 
 
@@ -31,10 +32,8 @@ def proc_gen_step(pkg, ctx, turns, ev, z_ptr, mm_ptr, x0, y0, dx, dy, nx, ny, dr
     try:
         if prev_flag is not None:
             prev_flag.wait()             # the previous map's noise has been enqueued and its event recorded (long ago, in the steady state)
-            ctx.event_synchronize(prev_ev)   # ... and has left the chip
-        ctx.gen_grid_minmax_async_dev(z_ptr, x0, y0, dx, dy, nx, ny, mm_ptr, pkg.GEN_GLACIATE if flags is None else flags)
-        if ev is not None:
-            ctx.event_record(ev)
+        # the host waits for prev_ev (all but the last rows of the previous map's noise have left the chip), enqueues this map's noise and records ev in front of its own last rows
+        ctx.gen_grid_minmax_turn_dev(z_ptr, x0, y0, dx, dy, nx, ny, mm_ptr, prev_ev if prev_flag is not None else None, ev, pkg.GEN_GLACIATE if flags is None else flags)
     finally:
         if my_flag is not None:
             my_flag.set()                # (also after a failure: the next map must not wait for a record that will never come)

@@ -266,6 +266,7 @@ _PROTOS = {
     "terra_erosion_shard_trace_dev": (_i32, [_vp, _vp, _i32, _i32, _u32, _u32, _u32, _vp]),
     "terra_erosion_shard_finish_dev": (_i32, [_vp, _vp, _i32, _i32, _vp, _u32, _u32, _u32, _u32, C.POINTER(_u32), _vp, C.c_size_t]),
     "terra_gen_grid_minmax_async_dev": (_i32, [_vp, _f, _f, _f, _f, _u32, _u32, _u32, _i32, _vp, _vp]),
+    "terra_gen_grid_minmax_turn_dev": (_i32, [_vp, _f, _f, _f, _f, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp]),
     "terra_gen_grid_rows_minmax_async_dev": (_i32, [_vp, _f, _f, _f, _f, _u32, _u32, _u32, _i32, _u32, _u32, _vp, _vp]),
     "terra_get_erosion_report": (_i32, [_vp, C.POINTER(ErosionReport)]),
     "terra_set_erosion_tuning": (_i32, [_vp, _u32, _u32, _u32]),
@@ -470,7 +471,7 @@ class PinnedArray:
 # (variable -> (option key, value when the variable is unset)); Terra.apply_env_options() is called at construction and by whoever changes a variable afterwards.
 ENV_OPTIONS = {
     "TERRA_GEN_FUSED": ("gen.fused", "0"), "TERRA_SIMPLE_KERNELS": ("kernels.simple", "0"), "TERRA_GRAPHS": ("graphs", "1"),
-    "TERRA_SG_KC": ("sg.kc", "27"), "TERRA_SG_KC_TILES": ("sg.kc_tiles", "27"), "TERRA_SG_ROWGROUP": ("sg.rowgroup", "4"), "TERRA_TILE_EROSION": ("tile_erosion", "lds"),
+    "TERRA_SG_KC": ("sg.kc", "27"), "TERRA_SG_KC_TILES": ("sg.kc_tiles", "27"), "TERRA_SG_ROWGROUP": ("sg.rowgroup", "4"), "TERRA_SG_TURN_ROWS": ("sg.turn_rows", "default"), "TERRA_TILE_EROSION": ("tile_erosion", "lds"),
     "TERRA_WEIGHTS_SIMPLE": ("weights.simple", "0"), "TERRA_VOXELS_COLS": ("voxels.cols", "1"), "TERRA_AO_BANDS": ("ao.bands", "1"), "TERRA_AO_WHOLE": ("ao.whole", "1"), "TERRA_SHADOWS_LEVELS": ("shadows.levels", "0"),
     "TERRA_ERO_SPARSE": ("ero.sparse", "auto"), "TERRA_ERO_SPARSE_RETRACES": ("ero.sparse_retraces", "-1"), "TERRA_ERO_LEAD": ("ero.lead", "2"), "TERRA_ERO_BATCH": ("ero.batch", "0"), "TERRA_ERO_FUSE": ("ero.fuse", "3"),
     "TERRA_ERO_LIVE": ("ero.live", "1"), "TERRA_ERO_DIAG": ("ero.diag", "0"), "TERRA_ERO_CK": ("ero.ck", "default"), "TERRA_ERO_NEAR": ("ero.near", "default"),
@@ -1093,6 +1094,11 @@ class Terra:
     def gen_grid_minmax_async_dev(self, ptr, x0, y0, dx, dy, nx, ny, minmax_ptr, flags=GEN_GLACIATE, min_start_sin=0):
         """noise (+ glaciate) with {min, max} left in device memory at minmax_ptr (2 floats); nothing is read back, the call only enqueues"""
         self._ck(self.lib.terra_gen_grid_minmax_async_dev(self.ctx, x0, y0, dx, dy, nx, ny, flags, min_start_sin, ptr, minmax_ptr))
+
+    def gen_grid_minmax_turn_dev(self, ptr, x0, y0, dx, dy, nx, ny, minmax_ptr, wait_for=None, turn=None, flags=GEN_GLACIATE, min_start_sin=0):
+        """gen_grid_minmax_async_dev with the noise turn in the call: the host waits for event wait_for, `turn` is recorded while the map's last rows (option sg.turn_rows) are
+        still to be evaluated.  When `turn` fires the map is NOT complete: only this context's stream order (or synchronize) says that it is"""
+        self._ck(self.lib.terra_gen_grid_minmax_turn_dev(self.ctx, x0, y0, dx, dy, nx, ny, flags, min_start_sin, ptr, minmax_ptr, wait_for, turn))
 
     def gen_grid_rows_minmax_async_dev(self, ptr, x0, y0, dx, dy, nx, ny, row0, nrows, minmax_ptr, flags=GEN_GLACIATE, min_start_sin=0):
         """rows [row0, row0 + nrows) with the strip's {min, max} left in device memory at minmax_ptr; the call only enqueues"""

@@ -159,6 +159,8 @@ int  terra_synchronize(terra_ctx *ctx);
  *   "kernels.simple"       "0" | "1"      one-thread-per-cell cross-check kernels instead of the tiled ones (tests)
  *   "graphs"               "0" | "1"      replay the erosion rounds as hipGraphs (default 1)
  *   "sg.kc" "20"|"27"|"45", "sg.kc_tiles" "27"|"45", "sg.rowgroup" "1".."1024"      LDS chunking / tile walk of the exact sine kernel
+ *   "sg.turn_rows"         n | "default"  rows of a heightmap still to be evaluated when terra_gen_grid_minmax_turn_dev hands the noise turn on, rounded up to whole 128-row tile rows; "0": no split.
+ *                                          "default": 2048 on grids of at least 8 x as many rows, 0 on smaller ones; a value that was set applies to every grid (results never depend on it)
  *   "tile_erosion"         "lds" | "window"   the whole padded tile in LDS (default) or a 32 x 32 window over a copy in HBM
  *   "weights.simple"       "0" | "1"      per-texel form of the weights-texture pass;   "shadows.levels" "0" | "1"   one launch per dependency level of the mesh shadows
  *   "ao.bands"             "1" | "0"      the AO context of a tile batch evaluated as four bands around each tile (its centre is the tile's own heights) / as whole squares
@@ -230,6 +232,16 @@ int  terra_gen_grid_minmax_dev(terra_ctx *ctx, float x0, float y0, float dx, flo
 /* the same with min / max left in DEVICE memory (d_minmax: 2 floats) and nothing read back: asynchronous.  With terra_apply_erosion_devmin_dev the whole
  * heightmap_t::proc_gen step (src/heightmap.cpp:135-169: eval loop, min(vals), apply_erosion) is enqueued without a host round trip in between */
 int  terra_gen_grid_minmax_async_dev(terra_ctx *ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *d_out, float *d_minmax);
+/* terra_gen_grid_minmax_async_dev for one of several heightmaps in flight that take turns in their noise phase (3dworld_amd/pipeline.py), the turn in one call:
+ *   the HOST waits for the last record of wait_for (may be NULL: no wait) -> tables -> the grid kernel over all but the last T rows -> turn is recorded (may be NULL)
+ *   -> the grid kernel over the last T rows -> {min, max} into d_minmax.
+ * T is option "sg.turn_rows".  The thread of the next map, waiting for `turn` with terra_event_synchronize (or through its own call's wait_for), wakes and enqueues its
+ * tables and first grid launch while this map's last rows drain from the chip, instead of after them.  Values are those of terra_gen_grid_minmax_async_dev, bit for bit.
+ * CONTRACT: when `turn` fires this map is NOT complete -- neither d_out nor d_minmax.  `turn` says only that the next noise phase may be enqueued; that the map is complete
+ * is said by this context's stream order (terra_apply_erosion_devmin_dev on the same context, a terra_event_record after this call) or by terra_synchronize, by nothing else.
+ * No split (turn recorded right behind the grid kernel, in front of the min / max conversion): T = 0, T covers the grid, the fBm modes, TERRA_GEN_FUSED / TERRA_GEN_FAST. */
+int  terra_gen_grid_minmax_turn_dev(terra_ctx *ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *d_out, float *d_minmax,
+                                    terra_event *wait_for, terra_event *turn);
 int  terra_gen_grid(terra_ctx *ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *h_out);
 /* rows [row0, row0 + nrows) of the nx x ny grid only, d_out = nrows*nx floats; bit-identical to the same rows of the full-grid call (heightmap_t::proc_gen's
  * row loop is independent per row, src/heightmap.cpp:139-143): one heightmap as row strips on several GPUs.  h_min / h_max (optional, synchronous when given):

@@ -32,6 +32,28 @@ def klass(name):
     return "other"
 
 
+def noise_maps(rows):
+    """the grid launches of the trace grouped into maps: a map's noise phase is one launch, or two (all but the last rows, then the last rows: the noise turn is handed on
+    between them) that follow each other on their queue with no other kernel of that queue between them.  -> [(first start, last end, queue, [(start, end), ...])] by start"""
+    maps, open_map = [], {}
+    for a, b, n, q in sorted(rows):
+        if klass(n) == "noise":
+            if q in open_map:
+                open_map[q][1] = b
+                open_map[q][3].append((a, b))
+            else:
+                open_map[q] = [a, b, q, [(a, b)]]
+                maps.append(open_map[q])
+        else:
+            open_map.pop(q, None)
+    return sorted((m[0], m[1], m[2], m[3]) for m in maps)
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2] if v else 0
+
+
 def union(iv):
     iv = sorted(iv)
     out = []
@@ -74,9 +96,10 @@ def main():
     t0 = t_end - int(last_ms * 1e6)
     if "--timed-steps" in sys.argv:  # a --headline-only run: the timed region starts with the K-th last noise kernel (one per step)
         k = int(sys.argv[sys.argv.index("--timed-steps") + 1])
-        ns = sorted(r[0] for r in rows if klass(r[2]) == "noise" and r[1] - r[0] > 100_000)
+        ns = [m[0] for m in noise_maps(rows) if sum(e - s for s, e in m[3]) > 100_000]
         if len(ns) >= k:
             t0 = ns[-k] - 20_000
+    all_rows = rows
     rows = [r for r in rows if r[1] > t0]
     t0 = max(t0, min(r[0] for r in rows))
     span = t_end - t0
@@ -98,6 +121,20 @@ def main():
         ds = sorted(b - a for a, b in by["noise"])
         print(f"  noise kernel durations: min {ds[0] / 1e3:.1f} median {ds[len(ds) // 2] / 1e3:.1f} max {ds[-1] / 1e3:.1f} us; concurrent noise kernels (time with >= 2): "
               f"{sum(max(0, min(b1, b2) - max(a1, a2)) for i, (a1, b1) in enumerate(by['noise']) for (a2, b2) in by['noise'][i + 1:]) / 1e6:.3f} ms")
+        # map by map: a map's launches together, the hand-over to the next map, and how long launches of different maps share the chip
+        maps = [m for m in noise_maps(all_rows) if m[1] > t0]
+        both = [sum(e - s for s, e in m[3]) for m in maps]
+        gaps = [maps[i + 1][0] - maps[i][1] for i in range(len(maps) - 1)]
+        early = sum(1 for g in gaps if g < 0)
+        conc = sum(max(0, min(e1, e2) - max(s1, s2)) for i, m1 in enumerate(maps) for m2 in maps[i + 1:] for (s1, e1) in m1[3] for (s2, e2) in m2[3])
+        bs = sorted(both)
+        print(f"  maps: {len(maps)}, launches per map {sorted(set(len(m[3]) for m in maps))}; a map's grid launches together: min {bs[0] / 1e3:.1f} q1 {bs[len(bs) // 4] / 1e3:.1f} "
+              f"median {median(bs) / 1e3:.1f} q3 {bs[(3 * len(bs)) // 4] / 1e3:.1f} max {bs[-1] / 1e3:.1f} us")
+        if gaps:
+            gs = sorted(gaps)
+            print(f"  gap, end of map i's last grid launch -> start of map i+1's first (negative: overlap): min {gs[0] / 1e3:.1f} q1 {gs[len(gs) // 4] / 1e3:.1f} median {median(gs) / 1e3:.1f} "
+                  f"q3 {gs[(3 * len(gs)) // 4] / 1e3:.1f} max {gs[-1] / 1e3:.1f} us, sum {sum(gaps) / 1e6:.3f} ms; the next map starts before the last launch ends in {early} of {len(gaps)} hand-overs")
+        print(f"  grid launches of different maps on the chip together: {conc / 1e6:.3f} ms")
     cell = 50_000
     chart = []
     for c in range(int(span // cell) + 1):
