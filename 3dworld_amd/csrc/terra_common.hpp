@@ -53,6 +53,19 @@ TERRA_HD float clip_pm1(float x) {return max_std(-1.0f, min_std(1.0f, x));}  // 
 // float -> int with x86 cvttss2si semantics (NaN / out of range -> INT_MIN): what the reference binary does
 TERRA_HD int f2i_x86(float f) {return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;}
 
+// the reference's removal loops, literally: `for (i = 0; i < size; ++i) if (removed(i)) remove_element(v, i)` with remove_element (src/inlines.h:743-747) = swap with
+// the back, pop, --i.  removed(i) tests record i and returning true is its removal, once; move(dst, src) copies the back and whatever travels with it into the hole
+// (what the back receives is gone).  Returns the new size
+template<class REMOVED, class MOVE> TERRA_HD uint32_t remove_elements_serial(uint32_t size, REMOVED removed, MOVE move) {
+	for (uint32_t i = 0; i < size; ++i) {
+		if (!removed(i)) continue;
+		move(i, size - 1);
+		--size;
+		--i; // (wraps at 0 and comes back with the ++i, as the reference's unsigned does)
+	}
+	return size;
+}
+
 // ------------------------------------------------------------------ RNG (src/rand_gen.h:20-35,63-79; src/gen_object.cpp:377-381)
 // L'Ecuyer combined LCG; the reference holds the state in `long`, values always fit in int32 after the first step.
 struct rand_gen_t {

@@ -2588,14 +2588,24 @@ template<class BE> struct terra_engine {
 					tree_box_clear(box);
 					if (d_pine_counts) {
 						uint32_t const cnt = min_u32(d_pine_counts[t], c.a.pine_cap);
-						uint32_t const m = tree_edit_remove_serial(c, d_pine + t*c.a.pine_cap, (float *)nullptr, cnt, [&](tree_place_pod_t const &r, float const *) {tree_edit_box_pine(c, d_insts, r, box);});
+						tree_place_pod_t *const v = d_pine + t*c.a.pine_cap; // the removal loops of :3832-3833, literally
+						uint32_t const m = remove_elements_serial(cnt, [&](uint32_t i) {
+							if (!tree_edit_removed(c, v[i].pos[0], v[i].pos[1])) return false;
+							tree_edit_box_pine(c, d_insts, v[i], box);
+							return true;
+						}, [&](uint32_t dst, uint32_t src) {v[dst] = v[src];});
 						if (m != cnt) {state |= TREE_EDIT_CHANGED;}
 						d_pine_counts[t] = m;
 					}
 					if (d_decid_counts) {
 						uint32_t const cnt = min_u32(d_decid_counts[t], c.a.decid_cap);
-						uint32_t const m = tree_edit_remove_serial(c, d_decid + t*c.a.decid_cap, d_by_rec ? d_decid_radius + t*c.a.decid_cap : nullptr, cnt,
-							[&](decid_place_pod_t const &r, float const *rad) {tree_edit_box_decid(c, r, rad, d_by_id, box);});
+						decid_place_pod_t *const v = d_decid + t*c.a.decid_cap;
+						float *const radius = d_by_rec ? d_decid_radius + t*c.a.decid_cap : nullptr; // (moves with its records)
+						uint32_t const m = remove_elements_serial(cnt, [&](uint32_t i) {
+							if (!tree_edit_removed(c, v[i].pos[0], v[i].pos[1])) return false;
+							tree_edit_box_decid(c, v[i], radius ? radius + i : nullptr, d_by_id, box);
+							return true;
+						}, [&](uint32_t dst, uint32_t src) {v[dst] = v[src]; if (radius) {radius[dst] = radius[src];}});
 						if (m != cnt) {state |= TREE_EDIT_CHANGED;}
 						d_decid_counts[t] = m;
 					}
@@ -3029,14 +3039,15 @@ template<class BE> struct terra_engine {
 			flower_pod_t *const v = d_flowers + t*capacity;
 			uint32_t *const aux = d_aux ? d_aux + t*capacity : nullptr;
 			uint32_t count = min_u32(d_counts[t], capacity);
+			auto move = [&](uint32_t dst, uint32_t src) {v[dst] = v[src]; if (aux) {aux[dst] = aux[src];}}; // the literal loops of :894-897 and :918-924
 			if (kind == FLOWER_EDIT_ADD) {
-				count = flower_remove_serial(v, aux, count, [&](flower_pod_t const &f) {return flower_in_range(c.f, f, (int)rg[0], (int)rg[1], (int)rg[2], (int)rg[3]);});
+				count = remove_elements_serial(count, [&](uint32_t i) {return flower_in_range(c.f, v[i], (int)rg[0], (int)rg[1], (int)rg[2], (int)rg[3]);}, move);
 				count = flower_gen_serial(c.f, r.tx, r.ty, rg[0], rg[1], rg[2], rg[3], d_weights + t*nw, d_den + t*ncell, d_col + t*ncell, capacity, v, aux, count);
 			}
 			else {
 				float px, py;
 				flower_brush_local(c, r.tx, r.ty, px, py);
-				count = flower_remove_serial(v, aux, count, [&](flower_pod_t const &f) {return flower_in_brush(f, px, py, c.radius, c.is_square != 0);});
+				count = remove_elements_serial(count, [&](uint32_t i) {return flower_in_brush(v[i], px, py, c.radius, c.is_square != 0);}, move);
 			}
 			d_counts[t] = count;
 		});

@@ -105,18 +105,6 @@ TERRA_HD int flower_edit_kind(flower_edit_consts_t const &c, uint8_t updated, ui
 	if (rg[2] > (uint32_t)c.f.S || rg[3] > (uint32_t)c.f.S) return FLOWER_EDIT_REFUSED;
 	return FLOWER_EDIT_ADD;
 }
-// the literal loops of :894-897 and :918-924: `for (i = 0; i < size; ++i) if (..) remove_element(flowers, i)` with remove_element = swap with the back, pop, --i.
-// Returns the new size.  aux (optional) moves with its records
-template<class TEST> TERRA_HD uint32_t flower_remove_serial(flower_pod_t *v, uint32_t *aux, uint32_t size, TEST removed) {
-	for (uint32_t i = 0; i < size; ++i) {
-		if (!removed(v[i])) continue;
-		v[i] = v[size - 1];
-		if (aux) {aux[i] = aux[size - 1];}
-		--size;
-		--i; // (wraps at 0 and comes back with the ++i, as the reference's unsigned does)
-	}
-	return size;
-}
 
 // the tile's corner in camera space for clear_within: flower_xlate = (get_xval(x1 + xoff - xoff2), get_yval(y1 + yoff - yoff2)) (src/tiled_mesh.cpp:3935)
 TERRA_HD void flower_brush_local(flower_edit_consts_t const &c, int tx, int ty, float &px, float &py) {

@@ -594,18 +594,22 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
+	// one workgroup of T threads per tile of a batch of n; false (and no launch) where the driver's simple form is to run
+	template<unsigned T, class K, class... A> bool launch_per_tile(K kernel, uint32_t n, A... args) {
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		hipLaunchKernelGGL(kernel, dim3(n), dim3(T), 0, stream, args...);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	// the tree brush on the record arrays: k_tree_edit once per tile (culls and removal), k_tree_edit_append once per tile after the brush placements, k_tree_edit_finish
 	// once per tile for status and changed
 	bool tile_edit_trees(terra::tree_edit_consts_t const &c, uint32_t n, terra::tree_edit_frame_t const *frames, terra_tile_stats const *stats, terra::tree_inst_pod_t const *insts,
 		terra::tree_place_pod_t *pine, uint32_t *pine_counts, terra::decid_place_pod_t *decid, uint32_t *decid_counts, float *decid_radius, float const *by_id, float const *trmax,
 		uint32_t *idx, uint32_t *box, uint8_t *status, uint8_t const *skip, uint8_t const *gen_flags, uint8_t *place_skip)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_tree_edit, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, frames, stats, insts, pine, pine_counts, decid, decid_counts, decid_radius, by_id,
-			trmax, idx, box, status, skip, gen_flags, place_skip);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_per_tile<terra::TREEP_THREADS>(terra::k_tree_edit, n, c, frames, stats, insts, pine, pine_counts, decid, decid_counts, decid_radius, by_id, trmax, idx, box, status,
+			skip, gen_flags, place_skip);
 	}
 	bool tile_edit_trees_append(terra::tree_edit_consts_t const &c, uint32_t n, uint8_t const *gen_flags, terra::tree_inst_pod_t const *insts, terra::tree_place_pod_t const *new_pine,
 		uint32_t const *new_pine_counts, terra::tree_place_pod_t *pine, uint32_t *pine_counts, terra::decid_place_pod_t const *new_decid, uint32_t const *new_decid_counts,
@@ -631,56 +635,33 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	bool tile_place_trees(terra::tree_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
 		uint32_t capacity, terra::tree_place_pod_t *trees, uint32_t *counts)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_tree_place, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, dens, skip, stats, capacity, trees, counts);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_per_tile<terra::TREEP_THREADS>(terra::k_tree_place, n, c, tiles, dens, skip, stats, capacity, trees, counts);
 	}
 	// deciduous tree placement: one workgroup per tile (k_decid_place)
 	bool tile_place_decid_trees(terra::decid_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
 		float const *zvals, uint32_t capacity, terra::decid_place_pod_t *trees, uint32_t *counts)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_decid_place, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, dens, skip, stats, zvals, capacity, trees, counts);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_per_tile<terra::TREEP_THREADS>(terra::k_decid_place, n, c, tiles, dens, skip, stats, zvals, capacity, trees, counts);
 	}
 	// scenery placement: one workgroup per tile (k_scenery_place)
 	bool tile_place_scenery(terra::scenery_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, uint32_t capacity,
 		terra::scenery_place_pod_t *objs, uint32_t *counts, uint32_t *kind_counts)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_scenery_place, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, dens, skip, capacity, objs, counts, kind_counts);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_per_tile<terra::TREEP_THREADS>(terra::k_scenery_place, n, c, tiles, dens, skip, capacity, objs, counts, kind_counts);
 	}
 	// flowers: one wave per tile (k_flowers_place)
 	bool tile_place_flowers(terra::flower_consts_t const &c, terra::tile_ref_pod_t const *tiles, uint32_t n, uint8_t const *skip, uint8_t const *weights, float const *den,
 		float const *col, uint32_t capacity, terra::flower_pod_t *flowers, uint32_t *aux, uint32_t *counts)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_flowers_place<false>, dim3(n), dim3(64), 0, stream, c, tiles, skip, (uint8_t const *)nullptr, (uint32_t const *)nullptr, weights, den, col,
-			capacity, flowers, aux, counts);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_per_tile<64>(terra::k_flowers_place<false>, n, c, tiles, skip, (uint8_t const *)nullptr, (uint32_t const *)nullptr, weights, den, col, capacity, flowers, aux, counts);
 	}
 	// the flowers' upkeep after a grass stroke: k_flowers_remove once per tile, then, when adding, k_flowers_place over the strokes' rectangles
 	bool tile_edit_flowers(terra::flower_edit_consts_t const &c, terra::tile_ref_pod_t const *tiles, uint32_t n, uint8_t const *generated, uint8_t const *updated,
 		uint32_t const *ranges, uint8_t const *weights, float const *den, float const *col, uint32_t capacity, terra::flower_pod_t *flowers, uint32_t *aux, uint32_t *counts,
 		uint8_t *status, uint32_t *idx, uint8_t *kind)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_flowers_remove, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, tiles, generated, updated, ranges, capacity, flowers, aux, counts, status, idx, kind);
-		if (c.add) {
-			hipLaunchKernelGGL(terra::k_flowers_place<true>, dim3(n), dim3(64), 0, stream, c.f, tiles, (uint8_t const *)nullptr, (uint8_t const *)kind, ranges, weights, den, col,
-				capacity, flowers, aux, counts);
-		}
-		TERRA_HIP_CHECK(hipGetLastError());
+		if (!launch_per_tile<terra::TREEP_THREADS>(terra::k_flowers_remove, n, c, tiles, generated, updated, ranges, capacity, flowers, aux, counts, status, idx, kind)) return false;
+		if (c.add) {launch_per_tile<64>(terra::k_flowers_place<true>, n, c.f, tiles, (uint8_t const *)nullptr, (uint8_t const *)kind, ranges, weights, den, col, capacity, flowers, aux, counts);}
 		return true;
 	}
 	// the grass draw lists for a camera: one workgroup per tile (k_grass_view)
@@ -688,11 +669,7 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		terra::grass_block_pod_t const *blocks, uint8_t const *skip, uint32_t capacity, float *insts, uint32_t *aux, uint32_t *group_counts, uint32_t *counts, uint8_t *pass,
 		uint16_t *keys)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_grass_view, dim3(n), dim3(terra::GV_THREADS), 0, stream, c, tile_xy, zvals, stats, blocks, skip, capacity, insts, aux, group_counts, counts, pass, keys);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_per_tile<terra::GV_THREADS>(terra::k_grass_view, n, c, tile_xy, zvals, stats, blocks, skip, capacity, insts, aux, group_counts, counts, pass, keys);
 	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}

@@ -1496,6 +1496,7 @@ __global__ __launch_bounds__(256) void k_tree_weights(size_t ntex, uint32_t cons
 // look-ups each, and a look-up is a gather from the 128 KB table that no two lanes share; four cells per thread in the selection made the kernel slower (443 us
 // against 353: one wave less per SIMD to hide those gathers behind).
 constexpr uint32_t TREEP_THREADS = 256, TREEP_RING = 512;
+// ---- the block-stream helpers of the per-tile record kernels: a workgroup of TREEP_THREADS threads, everything "uniform" the same in every thread of it
 // rank of the calling thread among the block's threads with `flag`, in thread order, and their number; two barriers
 __device__ __forceinline__ uint32_t tp_block_rank(bool flag, uint32_t *s_wave, uint32_t &total) {
 	uint32_t const lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -1507,6 +1508,75 @@ __device__ __forceinline__ uint32_t tp_block_rank(bool flag, uint32_t *s_wave, u
 	__syncthreads();
 	total = all;
 	return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+// A ring of RING slots in LDS that holds entries [head, tail) in the order they were pushed (head, tail: uniform); the slots themselves belong to the kernel.
+// A round of the kernel is: push what the round's threads selected; if due(), take() up to TREEP_THREADS entries, one per thread, and hand what becomes of them
+// to tp_emit or to the push of a next ring.  Why RING >= 2*TREEP_THREADS is enough: due() leaves at most `at` - 1 <= TREEP_THREADS - 1 entries behind, a push adds
+// at most TREEP_THREADS, and a take that is due follows before the next push, so no more than RING - 1 entries are ever pending.
+// The barriers: push ends with one, after its stores, so a take that follows reads complete slots.  Every take is followed by a tp_emit or a push before the next
+// push to its ring, and the next push ranks before it stores: the barriers of those tp_block_ranks lie between a take's reads and the stores that reuse its slots.
+template<uint32_t RING> struct tp_ring_t {
+	static_assert((RING & (RING - 1)) == 0 && RING >= 2*TREEP_THREADS, "a power of two that holds a not-yet-due remainder and one push");
+	uint32_t head = 0, tail = 0;
+	// the threads with `flag` append, in thread order: store(slot) writes one's entry
+	template<class STORE> __device__ __forceinline__ void push(bool flag, uint32_t *s_wave, STORE store) {
+		uint32_t n;
+		uint32_t const rank = tp_block_rank(flag, s_wave, n);
+		if (flag) {store((tail + rank) & (RING - 1));}
+		tail += n;
+		__syncthreads();
+	}
+	// the flush rule: `at` (<= TREEP_THREADS) entries pending, or anything pending when no push will follow
+	__device__ __forceinline__ bool due(bool nothing_more_comes, uint32_t at = TREEP_THREADS) const {return tail - head >= at || (nothing_more_comes && head < tail);}
+	// the oldest min(pending, TREEP_THREADS) entries leave, thread i with the i-th: whether this thread has one, and its slot
+	__device__ __forceinline__ bool take(uint32_t &slot) {
+		uint32_t const nb = (tail - head < TREEP_THREADS) ? tail - head : TREEP_THREADS;
+		slot = (head + threadIdx.x) & (RING - 1);
+		head += nb;
+		return threadIdx.x < nb;
+	}
+};
+// the records of the threads with `ok` go behind the `count` records so far, in thread order, as far as the array has room; count (uniform) counts them all.
+// record() gives a thread's record and is called only where it is stored
+template<class REC, class RECORD> __device__ __forceinline__ void tp_emit(bool ok, RECORD record, REC *out, uint32_t capacity, uint32_t &count, uint32_t *s_wave) {
+	uint32_t n;
+	uint32_t const rank = tp_block_rank(ok, s_wave, n);
+	if (ok && count + rank < capacity) {out[count + rank] = record();}
+	count += n;
+}
+// remove_elements_serial's result (terra_common.hpp) on records [0, cnt) by the workgroup, in place; returns the new size M (uniform).  remove_element swaps the
+// back into the hole and tests the same index again, so the result is not in input order; its closed form: with M survivors among the cnt records, a survivor below M
+// stays, and the holes below M, ascending, receive the survivors at M and above, descending (tests/test_tree_edit_emul.py checks this against the literal loop).
+// Three sweeps of TREEP_THREADS records: (1) M, (2) the survivors at M and above into idx[] (cnt words of global scratch) in ascending order, (3) the k-th hole below M
+// takes record idx[H - 1 - k].  Sources lie at M and above, destinations below: in place after a barrier.  removed(i) is a pure test of record i that the sweeps
+// repeat.  move(dst, src) copies a record and whatever travels with it.
+template<class REMOVED, class MOVE> __device__ __forceinline__ uint32_t tp_block_remove(uint32_t cnt, uint32_t *idx, uint32_t *s_wave, REMOVED removed, MOVE move) {
+	uint32_t const tid = threadIdx.x;
+	uint32_t m = 0, nk;
+	for (uint32_t base = 0; base < cnt; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		tp_block_rank(i < cnt && !removed(i), s_wave, nk);
+		m += nk;
+	}
+	if (m == cnt) return m;
+	uint32_t h = 0;
+	for (uint32_t base = m; base < cnt; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		bool const keep = i < cnt && !removed(i);
+		uint32_t const rank = tp_block_rank(keep, s_wave, nk);
+		if (keep) {idx[h + rank] = i;}
+		h += nk;
+	}
+	__syncthreads(); // idx[] is complete
+	uint32_t k0 = 0;
+	for (uint32_t base = 0; base < m; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		bool const hole = i < m && removed(i);
+		uint32_t const rank = tp_block_rank(hole, s_wave, nk);
+		if (hole) {move(i, idx[h - 1u - (k0 + rank)]);}
+		k0 += nk;
+	}
+	return m;
 }
 __global__ __launch_bounds__(TREEP_THREADS) void k_tree_place(tree_place_consts_t const *__restrict__ consts, tile_ref_pod_t const *__restrict__ tiles, float const *__restrict__ d_dens,
 	uint8_t const *__restrict__ skip, terra_tile_stats const *__restrict__ stats, uint32_t capacity, tree_place_pod_t *__restrict__ trees, uint32_t *__restrict__ counts)
@@ -1524,8 +1594,9 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_tree_place(tree_place_consts_
 	}
 	uint32_t const ncell = (uint32_t)c.ncell, ncells = ncell*ncell;
 	tree_place_pod_t *const out = trees + (size_t)t*capacity;
-	uint32_t head = 0, tail = 0, count = 0; // ring [head, tail) and the tile's trees so far: the same in every thread
-	for (uint32_t base = 0; base < ncells || head < tail; base += TREEP_THREADS) {
+	tp_ring_t<TREEP_RING> q;
+	uint32_t count = 0; // the tile's trees so far (uniform)
+	for (uint32_t base = 0; base < ncells || q.head < q.tail; base += TREEP_THREADS) {
 		if (base < ncells) {
 			uint32_t const cell = base + tid;
 			bool sel = false;
@@ -1534,28 +1605,19 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_tree_place(tree_place_consts_
 				tree_rgen_t rg;
 				sel = tree_cell_selected(c, dens, r.tx, r.ty, ix, iy, rg);
 			}
-			uint32_t nsel;
-			uint32_t const rank = tp_block_rank(sel, s_wave, nsel);
-			if (sel) {s_ring[(tail + rank) & (TREEP_RING - 1)] = cell;}
-			tail += nsel;
-			__syncthreads();
+			q.push(sel, s_wave, [&](uint32_t k) {s_ring[k] = cell;});
 		}
-		bool const last = base + TREEP_THREADS >= ncells;
-		if (tail - head < TREEP_THREADS && !(last && head < tail)) continue; // (fewer than 256 pending and more cells to come)
-		uint32_t const nb = (tail - head < TREEP_THREADS) ? tail - head : TREEP_THREADS;
+		if (!q.due(base + TREEP_THREADS >= ncells)) continue; // (fewer than 256 pending and more cells to come)
 		bool ok = false;
 		tree_place_pod_t o;
-		if (tid < nb) {
-			uint32_t const cell = s_ring[(head + tid) & (TREEP_RING - 1)], iy = cell/ncell, ix = cell - iy*ncell;
+		uint32_t k;
+		if (q.take(k)) {
+			uint32_t const cell = s_ring[k], iy = cell/ncell, ix = cell - iy*ncell;
 			tree_rgen_t rg;
 			tree_cell_selected(c, dens, r.tx, r.ty, ix, iy, rg); // (the generator as the selection left it: cheaper to redo than to keep)
 			ok = tree_cell_finish(c, r.tx, r.ty, ix, iy, rg, o);
 		}
-		head += nb;
-		uint32_t ntree;
-		uint32_t const rank = tp_block_rank(ok, s_wave, ntree);
-		if (ok && count + rank < capacity) {out[count + rank] = o;}
-		count += ntree;
+		tp_emit(ok, [&] {return o;}, out, capacity, count, s_wave);
 	}
 	if (tid == 0) {counts[t] = count;}
 }
@@ -1592,7 +1654,8 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_decid_place(decid_place_const
 	float const *const tz = zvals ? zvals + (size_t)t*(size_t)(c.b.S + 2)*(size_t)(c.b.S + 2) : nullptr;
 	uint32_t const ncell = (uint32_t)c.b.ncell, ncells = ncell*ncell;
 	decid_place_pod_t *const out = trees + (size_t)t*capacity;
-	uint32_t h1 = 0, t1 = 0, h2 = 0, t2 = 0, count = 0; // the rings [h1, t1) and [h2, t2) and the tile's trees so far: the same in every thread
+	tp_ring_t<DECIDP_RING> q1, q2;
+	uint32_t count = 0; // the tile's trees so far (uniform)
 	for (uint32_t base = 0; ; base += TREEP_THREADS) {
 		if (base < ncells) {
 			uint32_t const cell = base + tid;
@@ -1602,53 +1665,38 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_decid_place(decid_place_const
 				tree_rgen_t rg;
 				sel = decid_cell_selected(c, veg, r.tx, r.ty, ix, iy, rg);
 			}
-			uint32_t nsel;
-			uint32_t const rank = tp_block_rank(sel, s_wave, nsel);
-			if (sel) {s_ring[(t1 + rank) & (DECIDP_RING - 1)] = cell;}
-			t1 += nsel;
-			__syncthreads();
+			q1.push(sel, s_wave, [&](uint32_t k) {s_ring[k] = cell;});
 		}
 		bool const last = base + TREEP_THREADS >= ncells; // no cell comes after this round
-		if (t1 - h1 >= TREEP_THREADS || (last && h1 < t1)) { // the sites of up to 256 selected cells
-			uint32_t const nb = (t1 - h1 < TREEP_THREADS) ? t1 - h1 : TREEP_THREADS;
+		if (q1.due(last)) { // the sites of up to 256 selected cells
 			bool ok = false;
-			uint32_t cell = 0;
+			uint32_t cell = 0, k1;
 			float pos[3] = {0.0f, 0.0f, 0.0f};
 			tree_rgen_t rg; rg.set_state(0, 0);
-			if (tid < nb) {
-				cell = s_ring[(h1 + tid) & (DECIDP_RING - 1)];
+			if (q1.take(k1)) {
+				cell = s_ring[k1];
 				uint32_t const iy = cell/ncell, ix = cell - iy*ncell;
 				decid_cell_selected(c, veg, r.tx, r.ty, ix, iy, rg); // (the generator as the selection left it: cheaper to redo than to keep)
 				ok = decid_cell_site(c, r.tx, r.ty, ix, iy, rg, pos);
 			}
-			h1 += nb;
-			uint32_t nok;
-			uint32_t const rank = tp_block_rank(ok, s_wave, nok);
-			if (ok) {
-				uint32_t const k = (t2 + rank) & (DECIDP_RING - 1);
+			q2.push(ok, s_wave, [&](uint32_t k) {
 				s_cell[k] = cell; s_pos[k][0] = pos[0]; s_pos[k][1] = pos[1]; s_pos[k][2] = pos[2]; s_seed[k][0] = rg.rseed1; s_seed[k][1] = rg.rseed2;
-			}
-			t2 += nok;
-			__syncthreads();
+			});
 		}
-		bool const drained = last && h1 == t1; // nothing comes after what the second ring holds
-		if (t2 - h2 >= TREEP_THREADS || (drained && h2 < t2)) { // the types, the slope test and the records of up to 256 sites
-			uint32_t const nb = (t2 - h2 < TREEP_THREADS) ? t2 - h2 : TREEP_THREADS;
+		bool const drained = last && q1.head == q1.tail; // nothing comes after what the second ring holds
+		if (q2.due(drained)) { // the types, the slope test and the records of up to 256 sites
 			bool ok = false;
 			decid_place_pod_t o;
-			if (tid < nb) {
-				uint32_t const k = (h2 + tid) & (DECIDP_RING - 1), cell = s_cell[k], iy = cell/ncell, ix = cell - iy*ncell;
+			uint32_t k;
+			if (q2.take(k)) {
+				uint32_t const cell = s_cell[k], iy = cell/ncell, ix = cell - iy*ncell;
 				float const pos[3] = {s_pos[k][0], s_pos[k][1], s_pos[k][2]};
 				tree_rgen_t rg; rg.set_state(s_seed[k][0], s_seed[k][1]);
 				ok = decid_cell_finish(c, r.tx, r.ty, ix, iy, rg, pos, slope_test, tz, o);
 			}
-			h2 += nb;
-			uint32_t ntree;
-			uint32_t const rank = tp_block_rank(ok, s_wave, ntree); // (its barriers also keep the next round's writes to the second ring behind these reads)
-			if (ok && count + rank < capacity) {out[count + rank] = o;}
-			count += ntree;
+			tp_emit(ok, [&] {return o;}, out, capacity, count, s_wave);
 		}
-		if (drained && h2 == t2) break;
+		if (drained && q2.head == q2.tail) break;
 	}
 	if (tid == 0) {counts[t] = count;}
 }
@@ -1668,6 +1716,7 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_decid_place(decid_place_const
 // flush's latency in either form.  Measured, 4096 tiles at S = 128: 0.59 ms with 256 against 0.86 ms with 64 in sine mode, 1.22 against 2.43 ms at tree_scale 8.
 // 86 VGPRs, 106 SGPRs with 111 spilled to vector lanes, 2208 B LDS, no scratch: five waves per SIMD.  The timings (tools/bench_scenery_place.py): DESIGN.md, section 4.
 constexpr uint32_t SCENP_FLUSH = TREEP_THREADS;
+static_assert(SCENP_FLUSH <= TREEP_THREADS, "tp_ring_t's bound on what is pending");
 __global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_consts_t const *__restrict__ consts, tile_ref_pod_t const *__restrict__ tiles, float const *__restrict__ d_dens,
 	uint8_t const *__restrict__ skip, uint32_t capacity, scenery_place_pod_t *__restrict__ objs, uint32_t *__restrict__ counts, uint32_t *__restrict__ kind_counts)
 {
@@ -1686,9 +1735,10 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_c
 	float const veg_ = scenery_tile_veg(c, dens);
 	uint32_t const S = (uint32_t)c.b.S, ncells = S*S;
 	scenery_place_pod_t *const out = objs + (size_t)t*capacity;
-	uint32_t head = 0, tail = 0, count = 0; // ring [head, tail) and the tile's objects so far: the same in every thread
-	uint32_t kc = 0;                        // lane k < SCENERY_KINDS: this wave's objects of kind k so far
-	for (uint32_t base = 0; base < ncells || head < tail; base += TREEP_THREADS) {
+	tp_ring_t<TREEP_RING> q;
+	uint32_t count = 0; // the tile's objects so far (uniform)
+	uint32_t kc = 0;    // lane k < SCENERY_KINDS: this wave's objects of kind k so far
+	for (uint32_t base = 0; base < ncells || q.head < q.tail; base += TREEP_THREADS) {
 		if (base < ncells) {
 			uint32_t const cell = base + tid;
 			bool sel = false;
@@ -1697,23 +1747,17 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_c
 				tree_rgen_t rg; int val; bool veg;
 				sel = scenery_cell_selected(c, veg_, r.tx, r.ty, ix, iy, rg, val, veg);
 			}
-			uint32_t nsel;
-			uint32_t const rank = tp_block_rank(sel, s_wave, nsel);
-			if (sel) {s_ring[(tail + rank) & (TREEP_RING - 1)] = cell;}
-			tail += nsel;
-			__syncthreads();
+			q.push(sel, s_wave, [&](uint32_t k) {s_ring[k] = cell;});
 		}
-		bool const last = base + TREEP_THREADS >= ncells;
-		if (tail - head < SCENP_FLUSH && !(last && head < tail)) continue; // (too few pending and more cells to come)
-		uint32_t const nb = (tail - head < TREEP_THREADS) ? tail - head : TREEP_THREADS;
+		if (!q.due(base + TREEP_THREADS >= ncells, SCENP_FLUSH)) continue; // (too few pending and more cells to come)
 		bool ok = false;
 		int kind = SCENERY_NONE, val = 0; bool veg = false;
 		int32_t pre_i = 0; float pre_f[3] = {0.0f, 0.0f, 0.0f}, pos[3] = {0.0f, 0.0f, 0.0f};
-		uint32_t ix = 0, iy = 0;
+		uint32_t ix = 0, iy = 0, k;
 		tree_rgen_t rg; rg.set_state(1, 1);
 		scenery_place_pod_t o;
-		if (tid < nb) {
-			uint32_t const cell = s_ring[(head + tid) & (TREEP_RING - 1)];
+		if (q.take(k)) {
+			uint32_t const cell = s_ring[k];
 			iy = cell/S; ix = cell - iy*S;
 			scenery_cell_selected(c, veg_, r.tx, r.ty, ix, iy, rg, val, veg); // (the generator as the selection left it: cheaper to redo than to keep)
 			kind = scenery_cell_kind(c, val, veg, rg, pre_i, pre_f);
@@ -1722,11 +1766,7 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_scenery_place(scenery_place_c
 		if (kind != SCENERY_NONE) {ok = scenery_cell_create(c, kind, pre_i, pre_f, rg, pos, o);}
 		if (ok && kind == SCENERY_LOG) {ok = scenery_log_finish(c, tree_exact_zval(c.b, o.p[5], o.p[6]), rg, o);} // the log lanes alone
 		if (ok) {scenery_set_tail(rg, ix, iy, o);}
-		head += nb;
-		uint32_t nobj;
-		uint32_t const rank = tp_block_rank(ok, s_wave, nobj); // (its barriers also keep the next round's writes to the ring behind these reads)
-		if (ok && count + rank < capacity) {out[count + rank] = o;}
-		count += nobj;
+		tp_emit(ok, [&] {return o;}, out, capacity, count, s_wave);
 #pragma unroll
 		for (int k = 0; k < SCENERY_KINDS; ++k) {
 			uint32_t const nk = (uint32_t)__popcll(__ballot(ok && kind == k));
@@ -1885,8 +1925,7 @@ template<bool EDIT> __global__ __launch_bounds__(64) void k_flowers_place(flower
 	if (lane == 0) {counts[t] = count;}
 }
 // k_flowers_remove: a workgroup per tile decides what the stroke does to the tile (flower_edit_kind), writes its status and runs the removal loop of update_subrange
-// or clear_within in te_remove_group's closed form of remove_element: with M survivors among the cnt records a survivor below M stays, and the holes below M,
-// ascending, receive the survivors at M and above, descending.  aux moves with its records.  counts[t] = M; an adding stroke's k_flowers_place continues from there.
+// or clear_within with tp_block_remove.  aux moves with its records.  counts[t] = M; an adding stroke's k_flowers_place continues from there.
 __global__ __launch_bounds__(TREEP_THREADS) void k_flowers_remove(flower_edit_consts_t c, tile_ref_pod_t const *__restrict__ tiles, uint8_t const *__restrict__ generated,
 	uint8_t const *__restrict__ updated, uint32_t const *__restrict__ ranges, uint32_t capacity, flower_pod_t *flowers, uint32_t *aux, uint32_t *counts, uint8_t *status,
 	uint32_t *idx, uint8_t *kind_out)
@@ -1907,35 +1946,7 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_flowers_remove(flower_edit_co
 	flower_pod_t *const v = flowers + (size_t)t*capacity;
 	uint32_t *const ax = aux ? aux + (size_t)t*capacity : nullptr, *const my_idx = idx + (size_t)t*capacity;
 	uint32_t const cnt = min_u32(counts[t], capacity);
-	uint32_t m = 0, nk;
-	for (uint32_t base = 0; base < cnt; base += TREEP_THREADS) {
-		uint32_t const i = base + tid;
-		tp_block_rank(i < cnt && !removed(v[i]), s_wave, nk);
-		m += nk;
-	}
-	if (m != cnt) {
-		uint32_t h = 0;
-		for (uint32_t base = m; base < cnt; base += TREEP_THREADS) { // the survivors at M and above, ascending
-			uint32_t const i = base + tid;
-			bool const keep = i < cnt && !removed(v[i]);
-			uint32_t const rank = tp_block_rank(keep, s_wave, nk);
-			if (keep) {my_idx[h + rank] = i;}
-			h += nk;
-		}
-		__syncthreads(); // idx[] is complete
-		uint32_t k0 = 0;
-		for (uint32_t base = 0; base < m; base += TREEP_THREADS) { // the k-th hole below M takes survivor idx[h - 1 - k]: sources at M and above, destinations below
-			uint32_t const i = base + tid;
-			bool const hole = i < m && removed(v[i]);
-			uint32_t const rank = tp_block_rank(hole, s_wave, nk);
-			if (hole) {
-				uint32_t const src = my_idx[h - 1u - (k0 + rank)];
-				v[i] = v[src];
-				if (ax) {ax[i] = ax[src];}
-			}
-			k0 += nk;
-		}
-	}
+	uint32_t const m = tp_block_remove(cnt, my_idx, s_wave, [&](uint32_t i) {return removed(v[i]);}, [&](uint32_t dst, uint32_t src) {v[dst] = v[src]; if (ax) {ax[dst] = ax[src];}});
 	__syncthreads(); // every thread has read the count
 	if (tid == 0) {counts[t] = m;}
 }
@@ -2107,10 +2118,7 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_tree_ao_gather(tree_ao_consts
 				s = src[tree_ao_entry(c, sg, j)];
 				keep = tree_ao_keep(c, sg, s, ft.x, ft.y, fu.x, fu.y);
 			}
-			uint32_t nk;
-			uint32_t const rank = tp_block_rank(keep, s_wave, nk);
-			if (keep && count + rank < c.list_cap) {out[count + rank] = tree_splat_params(s, ft.x, ft.y, c.dxv, c.dyv);}
-			count += nk;
+			tp_emit(keep, [&] {return tree_splat_params(s, ft.x, ft.y, c.dxv, c.dyv);}, out, c.list_cap, count, s_wave);
 		}
 	}
 	if (tid == 0) {
@@ -2123,10 +2131,9 @@ __global__ __launch_bounds__(TREEP_THREADS) void k_tree_ao_gather(tree_ao_consts
 
 // ------------------------------------------------------------------ the tree brush on the record arrays of a batch (tile_draw_t::add_or_remove_trees_at,
 // src/tiled_mesh.cpp:3746-3843; terra_treeedit.hpp), three launches: k_tree_edit, k_tree_edit_append (only when adding, after the two brush placements), k_tree_edit_finish.
-// The removal loop of one group by the workgroup.  remove_element swaps the back into the hole and tests the same index again, so the result is not in input order; its
-// closed form: with M survivors among the cnt records, a survivor below M stays, and the holes below M, ascending, receive the survivors at M and above, descending
-// (tests/test_tree_edit_emul.py checks this against the literal loop).  Three sweeps of 256 records: (1) M and the removed records' box, (2) the survivors at M and
-// above into idx[] in ascending order, (3) the k-th hole below M takes record idx[H - 1 - k].  Sources lie at M and above, destinations below: in place after a barrier.
+// The removal of one group of k_tree_edit: tp_block_remove's three sweeps written out, the first one also taking the removed records' box.  Kept apart because
+// k_tree_edit on tp_block_remove measured slower on a whole-batch stroke (106.4 and 108.5 us against the parent's 102.7-105.5 and 96.6-103.0 in two alternating runs;
+// same instructions in another schedule): this is the form those figures of the parent belong to.
 template<class REC, class BOX> __device__ __forceinline__ uint32_t te_remove_group(tree_edit_consts_t const &c, REC *v, float *radius, uint32_t cnt, uint32_t *idx, uint32_t *s_wave, BOX box_of) {
 	uint32_t const tid = threadIdx.x;
 	uint32_t m = 0, nk;

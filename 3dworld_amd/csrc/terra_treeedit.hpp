@@ -5,7 +5,7 @@
 //   the two culls of add_or_remove_trees_at    (src/tiled_mesh.cpp:3824-3825)   -> tree_edit_cull
 //   remove_tree's two tests                    (src/tiled_mesh.cpp:3782-3783)   -> tree_edit_removed
 //   update_trees_bcube of a record             (src/tiled_mesh.cpp:3776-3778, :3784, :3816) -> tree_edit_box_pine / tree_edit_box_decid
-//   remove_element                             (src/inlines.h:743-747)          -> tree_edit_remove_serial (the literal loop, the simple form's)
+//   remove_element                             (src/inlines.h:743-747)          -> remove_elements_serial (terra_common.hpp: the literal loop, the simple form's)
 //   the near_tiles loop                        (src/tiled_mesh.cpp:3764-3768)   -> tree_edit_finish
 // Every operand has the type the reference statement gives it; where the statement promotes to double the doubles are written out.
 #pragma once
@@ -116,19 +116,6 @@ TERRA_HD void tree_edit_finish(tree_edit_consts_t const &c, tree_edit_frame_t co
 		for (int i = 0; i < 3; ++i) {if (hi[i] < mlo[i] || lo[i] > mhi[i]) {ch = false;}}
 	}
 	changed = ch ? 1u : 0u;
-}
-// the removal loops of :3832-3833 on one group, literally: `for (i = 0; i < size; ++i) remove_tree(v, i, ..)` with remove_element = swap with the back, pop, --i.
-// Returns the new size.  radius (optional) moves with its records.  REC: tree_place_pod_t or decid_place_pod_t
-template<class REC, class BOX> TERRA_HD uint32_t tree_edit_remove_serial(tree_edit_consts_t const &c, REC *v, float *radius, uint32_t size, BOX box_of) {
-	for (uint32_t i = 0; i < size; ++i) {
-		if (!tree_edit_removed(c, v[i].pos[0], v[i].pos[1])) continue;
-		box_of(v[i], radius ? radius + i : nullptr);
-		v[i] = v[size - 1]; // swap(v[i], v.back()); v.pop_back(): what the back receives is gone
-		if (radius) {radius[i] = radius[size - 1];}
-		--size;
-		--i; // (wraps at 0 and comes back with the ++i, as the reference's unsigned does)
-	}
-	return size;
 }
 
 } // namespace terra

@@ -167,11 +167,15 @@ def run_case(pkg, t, orc, case, dev=False, aux=True):
 # A stroke is (brush, updated [n], ranges [n, 4] or None, weights after the grass brush); the grass brush itself is not part of these cases: an adding stroke sets the
 # grass byte of its range to 255 as a full addition does, a removing one leaves the weights alone (clear_within does not read them).
 BASE = Case("edit_base_s20", weights="pattern", capacity=800)
+# (BASE's tiles hold 152 to 186 records.)  The same tiles with every weight 255 and five candidates a cell: more than 512 records a tile, so that a removal takes
+# k_flowers_remove's sweeps of 256 records more than once
+DENSE = Case("edit_dense_s20", params=dict(flower_density=5.3), capacity=1100)
 
 
 class EditCase:
-    def __init__(self, name, strokes, generated=None, dxoff=0, dyoff=0, capacity=800, want_status=None, check=None):
+    def __init__(self, name, strokes, generated=None, dxoff=0, dyoff=0, capacity=800, want_status=None, check=None, base=BASE):
         self.name, self.strokes, self.generated, self.dxoff, self.dyoff, self.capacity, self.want_status, self.check = name, strokes, generated, dxoff, dyoff, capacity, want_status, check
+        self.base = base  # the case whose records the strokes start from
 
 
 def _brush(sc, tile, cx, cy, cells, add, shape, dxoff=0, dyoff=0):
@@ -183,7 +187,7 @@ def _brush(sc, tile, cx, cy, cells, add, shape, dxoff=0, dyoff=0):
     return pkg.make_grass_brush((x, y, 0.0), cells * float(sc.DX_VAL), add, shape, 0.5)
 
 
-EDIT_NAMES = ("add_inside", "add_reaches_column_S", "add_empty_ranges", "remove_round", "remove_square", "remove_offsets", "not_generated", "two_strokes", "add_small_capacity")
+EDIT_NAMES = ("add_inside", "add_reaches_column_S", "add_empty_ranges", "remove_round", "remove_square", "remove_offsets", "not_generated", "two_strokes", "add_small_capacity", "remove_dense")
 
 
 def edit_case(orc, name):
@@ -210,6 +214,8 @@ def edit_cases(sc):
         EditCase("two_strokes", [add([[3, 4, 12, 13], D, D]), rem(tiles[0], 9, 9, 4.5, 1, [1, 0, 0]), add([[6, 6, 15, 10], D, D])], want_status=[1, 0, 0],
                  check=lambda t, st: t["removed"] >= 10 and t["refilled"] >= 10),
         EditCase("add_small_capacity", [add([[0, 0, S, S], D, D])], capacity=260, want_status=[1, 0, 0], check=some("refilled", 261)),  # the refill does not fit: counts say so
+        # a disc in the middle of a tile of DENSE: removed records on either side of M, the survivors' count (test_flowers_emul.py::test_cases_are_not_vacuous)
+        EditCase("remove_dense", [rem(tiles[0], 10, 9, 6.5, 1, [1, 1, 1])], base=DENSE, capacity=DENSE.capacity, want_status=[1, 1, 1], check=some("removed", 100)),
     ]
 
 
@@ -224,7 +230,8 @@ def edit_weights(w, ranges):
 
 
 def run_edit_case(pkg, t, orc, ec, dev=False, aux=True):
-    """the strokes of ec through the library and through the model, from the model's records of BASE; compared after every stroke"""
+    """the strokes of ec through the library and through the model, from the model's records of ec.base; compared after every stroke"""
+    BASE = ec.base
     w, base, _ = model(orc, BASE)
     sc = scene_of(orc, BASE)
     configure(pkg, t, BASE)

@@ -42,6 +42,7 @@ def cases():
         Case("capacity_small", capacity=25),
         Case("tree_scale_8_s64", S=64, tp=dict(tree_scale=8.0), capacity=450),  # smod 1511: a tenth of the cells, the ring fills more than once in a tile
         Case("tree_scale_8_s20", S=20, tp=dict(tree_scale=8.0), tiles=TILES9, capacity=320),  # smod clamped to 200: three quarters of the cells
+        Case("tree_scale_16_s64", S=64, tp=dict(tree_scale=16.0), tiles=TILES[:3], capacity=800),  # smod 800: a fifth of the cells, the kernel's ring of 512 wraps
     ]
 
 

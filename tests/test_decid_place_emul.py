@@ -85,6 +85,12 @@ def test_cases_are_not_vacuous(pkg, orc):
     assert max(len(w) for w in M["capacity_small"][0]) > BY_NAME["capacity_small"].capacity
     assert [len(w) > 0 for w in M["brush_square_four_tiles"][0]] == [True, True, True, True, False]
     assert M["brush_radius_0"][1]["coverage"] == 0 and all(len(w) > 300 for w in M["brush_radius_0"][0])
+    # both of the kernel's rings of 512 wrap: a record has been through both, and four tiles there hold more than 512; at the defaults the first ring does on the mean tile
+    # (the selected cells that pass the vegetation test: every outcome but "unselected" and "veg"; slope_kept counts records a second time)
+    assert all(len(w) > 512 for w in M["brush_radius_0"][0][:4])
+    ta = M["defaults_s128"][1]
+    first = sum(v for k, v in ta.items() if k not in ("unselected", "veg", "slope_kept"))
+    assert first > 512 * len(BY_NAME["defaults_s128"].tiles), (first, ta)
     # mode 3: two empty tiles, rejections by class
     assert sum(len(w) == 0 for w in M["mode3_shore"][0]) == 2 and M["mode3_shore"][1]["class"] >= 10
     # skip and the two stats culls

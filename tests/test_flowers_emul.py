@@ -139,6 +139,18 @@ def test_cases_are_not_vacuous(pkg, orc):
     sc = fc.scene_of(orc, BY_NAME["negative_tiles_s20"])
     seeds = [(fm.seed(sc, tx, ty).rseed1, fm.seed(sc, tx, ty).rseed2) for tx, ty in fc.NEG_TILES]
     assert seeds[1][0] <= 0 and seeds[1][1] <= 0 and seeds[2][0] <= 0 < seeds[2][1] and seeds[3][1] <= 0 < seeds[3][0], seeds
+    # remove_dense: a tile with more than 512 records before the stroke and M survivors, records removed below M and at M and above: every sweep of the kernel's
+    # removal runs more than once and the moves happen; the tiles the brush misses have more than 256 records and lose none
+    ec = fc.edit_case(orc, "remove_dense")
+    w, base, _ = fc.model(orc, ec.base)
+    lists = [list(x) for x in base]
+    brush, upd, rg = ec.strokes[0]
+    fm.edit(fc.scene_of(orc, ec.base), ec.base.tiles, w, lists, (tuple(brush.pos), brush.radius, False, brush.shape == 0), upd, rg)
+    m, kept = len(lists[0]), {id(x) for x in lists[0]}
+    gone = [i for i, x in enumerate(base[0]) if id(x) not in kept]
+    assert len(base[0]) > 512 and m > 256 and len(base[0]) - m > 256, (len(base[0]), m)
+    assert sum(i < m for i in gone) >= 10 and sum(i >= m for i in gone) >= 10, (m, gone)
+    assert all(len(a) == len(b) > 256 for a, b in zip(lists[1:], base[1:]))
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])

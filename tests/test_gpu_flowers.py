@@ -55,7 +55,7 @@ def test_edit_cases_host_form(pkg, gpu, orc, name):
     fc.run_edit_case(pkg, gpu, orc, fc.edit_case(orc, name))
 
 
-@pytest.mark.parametrize("name", ["two_strokes", "remove_square"])
+@pytest.mark.parametrize("name", ["two_strokes", "remove_square", "remove_dense"])
 def test_edit_cases_simple_form(pkg, gpu, orc, name):
     with simple_form(gpu):
         fc.run_edit_case(pkg, gpu, orc, fc.edit_case(orc, name), dev=True)

@@ -62,7 +62,7 @@ def test_model_on_oracle_primitives(orc):
 
 
 def test_cases_are_not_vacuous(pkg, orc):
-    """on the model alone: every kind occurs, every drop reason occurs, some tile has more than 256 selected cells"""
+    """on the model alone: every kind occurs, every drop reason occurs, some tile has more than 256 selected cells and one more than the 512 the kernel's ring holds"""
     assert pkg.SCENERY_PLACE_DTYPE == spm.PLACE_DTYPE and tuple(pkg.SCENERY_KINDS) == spm.KINDS
     total = spm.new_tally()
     for case in CASES:
@@ -90,6 +90,7 @@ def test_cases_are_not_vacuous(pkg, orc):
     assert [len(w) > 0 for w in M["skipped_tile"][0]] == [True, False, True, True]
     assert max(len(w) for w in M["capacity_small"][0]) > BY_NAME["capacity_small"].capacity
     assert M["tree_scale_8_s64"][1]["max_selected"] > 256 and M["tree_scale_8_s20"][1]["max_selected"] > 256
+    assert M["tree_scale_16_s64"][1]["max_selected"] > 512  # the ring index wraps
     for case in CASES:
         if case.name != "capacity_small":
             assert max(len(w) for w in M[case.name][0]) <= case.capacity, case.name

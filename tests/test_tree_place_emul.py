@@ -58,6 +58,10 @@ def test_cases_are_not_vacuous(pkg, orc):
     by_name = {c.name: c for c in CASES}
     assert max(len(w) for w in tpc.MODEL["capacity_small"][0]) > by_name["capacity_small"].capacity
     assert sum(len(w) > 0 for w in tpc.MODEL["brush_four_tiles"][0]) == 4
+    # the kernel's ring of 512 cell numbers wraps: the selected cells of a case are what its tally counts besides "unselected", and some tile has their mean at least
+    for name in ("dwarp_exact_s64", "dwarp_approx_s64", "palms_mode3"):
+        selected = sum(v for k, v in tpc.MODEL[name][1].items() if k != "unselected")
+        assert selected > 512 * len(by_name[name].tiles), (name, selected)
     # the tile with four zero corners is one (on the oracle's own biome field) and gets no tree, its neighbours in the batch do
     cfg = orclib.make_config(mesh_gen_mode=0)
     orc.init(cfg)
