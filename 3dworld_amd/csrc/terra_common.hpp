@@ -53,6 +53,35 @@ TERRA_HD float clip_pm1(float x) {return max_std(-1.0f, min_std(1.0f, x));}  // 
 // float -> int with x86 cvttss2si semantics (NaN / out of range -> INT_MIN): what the reference binary does
 TERRA_HD int f2i_x86(float f) {return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;}
 
+// do_line_clip (src/Math3d.cpp:1029-1086) with get_region (src/inlines.h:522-528): shared by the mesh shadows, the line queries and the terrain view, whose
+// check_line_clip (get_line_clip, src/Math3d.cpp:1037-1052) is the same function without the two updates of the end points
+struct shadow_pt_t {float x, y, z;};
+TERRA_HD int shadow_region(shadow_pt_t v, float const d[3][2]) {
+	int region = 0;
+	if (v.x < d[0][0]) {region |= 0x01;} else if (v.x >= d[0][1]) {region |= 0x02;}
+	if (v.y < d[1][0]) {region |= 0x04;} else if (v.y >= d[1][1]) {region |= 0x08;}
+	if (v.z < d[2][0]) {region |= 0x10;} else if (v.z >= d[2][1]) {region |= 0x20;}
+	return region;
+}
+TERRA_HD bool shadow_line_clip(shadow_pt_t &v1, shadow_pt_t &v2, float const d[3][2]) {
+	int const region1 = shadow_region(v1, d), region2 = shadow_region(v2, d);
+	if (region1 & region2) return false;
+	int const region3 = region1 | region2;
+	if (region3 == 0) return true;
+	float tmin = 0.0f, tmax = 1.0f;
+	shadow_pt_t const dv = {v2.x - v1.x, v2.y - v1.y, v2.z - v1.z};
+#define TERRA_SH_CLIP(reg, va, vb, vd, vc) if (region3 & (reg)) {float const t = ((va) - (vb))/(vd); if ((vc) > 0.0f) {if (t > tmin) tmin = t;} else {if (t < tmax) tmax = t;} if (tmin >= tmax) return false;}
+	TERRA_SH_CLIP(0x01, d[0][0], v1.x, dv.x,  dv.x)
+	TERRA_SH_CLIP(0x02, d[0][1], v1.x, dv.x, -dv.x)
+	TERRA_SH_CLIP(0x04, d[1][0], v1.y, dv.y,  dv.y)
+	TERRA_SH_CLIP(0x08, d[1][1], v1.y, dv.y, -dv.y)
+	TERRA_SH_CLIP(0x10, d[2][0], v1.z, dv.z,  dv.z)
+	TERRA_SH_CLIP(0x20, d[2][1], v1.z, dv.z, -dv.z)
+#undef TERRA_SH_CLIP
+	if ((double)tmax > 1.0E-12) {v2.x = v1.x + dv.x*tmax; v2.y = v1.y + dv.y*tmax; v2.z = v1.z + dv.z*tmax;}
+	if ((double)tmin < (1.0 - 1.0E-12)) {v1.x += dv.x*tmin; v1.y += dv.y*tmin; v1.z += dv.z*tmin;}
+	return true;
+}
 // the reference's removal loops, literally: `for (i = 0; i < size; ++i) if (removed(i)) remove_element(v, i)` with remove_element (src/inlines.h:743-747) = swap with
 // the back, pop, --i.  removed(i) tests record i and returning true is its removal, once; move(dst, src) copies the back and whatever travels with it into the hole
 // (what the back receives is gone).  Returns the new size

@@ -18,6 +18,7 @@
 #include "terra_sceneryplace.hpp"
 #include "terra_flowers.hpp"
 #include "terra_grassview.hpp"
+#include "terra_terrainview.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_stage.hpp"
@@ -118,33 +119,6 @@ struct shadow_consts_t {
 	TERRA_HD float xval(int xp) const {return -X_SCENE_SIZE + DX_VAL*(float)xp;}                           // get_xval (src/mesh.h:122)
 	TERRA_HD float yval(int yp) const {return -Y_SCENE_SIZE + DY_VAL*(float)yp;}
 };
-struct shadow_pt_t {float x, y, z;};
-TERRA_HD int shadow_region(shadow_pt_t v, float const d[3][2]) {
-	int region = 0;
-	if (v.x < d[0][0]) {region |= 0x01;} else if (v.x >= d[0][1]) {region |= 0x02;}
-	if (v.y < d[1][0]) {region |= 0x04;} else if (v.y >= d[1][1]) {region |= 0x08;}
-	if (v.z < d[2][0]) {region |= 0x10;} else if (v.z >= d[2][1]) {region |= 0x20;}
-	return region;
-}
-TERRA_HD bool shadow_line_clip(shadow_pt_t &v1, shadow_pt_t &v2, float const d[3][2]) {
-	int const region1 = shadow_region(v1, d), region2 = shadow_region(v2, d);
-	if (region1 & region2) return false;
-	int const region3 = region1 | region2;
-	if (region3 == 0) return true;
-	float tmin = 0.0f, tmax = 1.0f;
-	shadow_pt_t const dv = {v2.x - v1.x, v2.y - v1.y, v2.z - v1.z};
-#define TERRA_SH_CLIP(reg, va, vb, vd, vc) if (region3 & (reg)) {float const t = ((va) - (vb))/(vd); if ((vc) > 0.0f) {if (t > tmin) tmin = t;} else {if (t < tmax) tmax = t;} if (tmin >= tmax) return false;}
-	TERRA_SH_CLIP(0x01, d[0][0], v1.x, dv.x,  dv.x)
-	TERRA_SH_CLIP(0x02, d[0][1], v1.x, dv.x, -dv.x)
-	TERRA_SH_CLIP(0x04, d[1][0], v1.y, dv.y,  dv.y)
-	TERRA_SH_CLIP(0x08, d[1][1], v1.y, dv.y, -dv.y)
-	TERRA_SH_CLIP(0x10, d[2][0], v1.z, dv.z,  dv.z)
-	TERRA_SH_CLIP(0x20, d[2][1], v1.z, dv.z, -dv.z)
-#undef TERRA_SH_CLIP
-	if ((double)tmax > 1.0E-12) {v2.x = v1.x + dv.x*tmax; v2.y = v1.y + dv.y*tmax; v2.z = v1.z + dv.z*tmax;}
-	if ((double)tmin < (1.0 - 1.0E-12)) {v1.x += dv.x*tmin; v1.y += dv.y*tmin; v1.z += dv.z*tmin;}
-	return true;
-}
 // Sweep number p in the reference's single-threaded order: p < 2*ysize are run_x's sweeps (y = p), the rest run_y's (x = p - 2*ysize).
 // OUT::shadow(x, y) sets the MESH_SHADOW bit; OUT::out_x / out_y(index, order, value) record an outgoing edge height -- `order` grows with the
 // sequential execution order (sweep, then step), the writer with the highest order must win.
@@ -2367,6 +2341,38 @@ template<class BE> struct terra_engine {
 			d_updated[t] = u;
 		});
 	}
+	// the [n][9] neighbour table of a batch, (dy+1)*3 + dx+1 -> batch index or -1; a tile may appear once (the tree AO shadows and the terrain view read it)
+	static std::vector<int32_t> batch_neighbours(int32_t const *tile_xy, uint32_t n, char const *what) {
+		if (n > (1u << 30)) throw std::invalid_argument(std::string(what) + ": more than 2^30 tiles");
+		// (an open-addressed table keyed by the tile's coordinates: the call only enqueues, and at 4096 tiles a tree of pairs would cost more than the kernels)
+		uint32_t hbits = 4;
+		while ((1ull << hbits) < 2ull*n) {++hbits;}
+		uint32_t const hmask = (uint32_t)((1ull << hbits) - 1);
+		std::vector<int32_t> slots((size_t)hmask + 1, -1);
+		auto key_of = [](int32_t tx, int32_t ty) {return ((uint64_t)(uint32_t)tx << 32) | (uint32_t)ty;};
+		auto hash_of = [hbits](uint64_t k) {return (uint32_t)((k*0x9E3779B97F4A7C15ull) >> (64 - hbits));};
+		auto find = [&](int64_t tx, int64_t ty) -> int32_t { // the batch index of tile (tx, ty), -1: not in the batch
+			if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX) return -1;
+			uint64_t const k = key_of((int32_t)tx, (int32_t)ty);
+			for (uint32_t h = hash_of(k);; h = (h + 1) & hmask) {
+				int32_t const v = slots[h];
+				if (v < 0 || key_of(tile_xy[2*v], tile_xy[2*v+1]) == k) return v;
+			}
+		};
+		for (uint32_t t = 0; t < n; ++t) {
+			uint64_t const k = key_of(tile_xy[2*t], tile_xy[2*t+1]);
+			uint32_t h = hash_of(k);
+			for (; slots[h] >= 0; h = (h + 1) & hmask) {
+				if (key_of(tile_xy[2*slots[h]], tile_xy[2*slots[h]+1]) == k) throw std::invalid_argument(std::string(what) + ": a tile appears twice in tile_xy");
+			}
+			slots[h] = (int32_t)t;
+		}
+		std::vector<int32_t> nbr((size_t)n*9);
+		for (uint32_t t = 0; t < n; ++t) {
+			for (int k = 0; k < 9; ++k) {nbr[(size_t)t*9 + k] = find((int64_t)tile_xy[2*t] + (k%3 - 1), (int64_t)tile_xy[2*t+1] + (k/3 - 1));}
+		}
+		return nbr;
+	}
 	// ---- tree AO shadows of a batch from the placement records (terra_treeao.hpp): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828) run on the tiles in batch
 	// order, every tree_map empty at the start.  Tile t's ordered list is its own trees (culled by its box when no_adj_test(t)), then -- unless no_adj_test(t) -- the trees
 	// of the neighbours that come earlier, in dy, dx order, culled by t's box and gated by t's flags, then what the neighbours that come later push: their own trees that
@@ -2398,35 +2404,9 @@ template<class BE> struct terra_engine {
 		uint32_t const S = tile_size(), W = S + 1;
 		uint64_t const src_cap = (uint64_t)pine_cap + decid_cap;
 		if ((uint64_t)n*list_cap > 0xFFFFFFFFull || (uint64_t)n*src_cap > 0xFFFFFFFFull) throw std::invalid_argument("tiles_tree_ao_shadows: n*list_capacity and n*(capacities) must fit 32 bits");
-		// the [n][9] neighbour table, (dy+1)*3 + dx+1 -> batch index or -1; a tile may appear once
-		if (n > (1u << 30)) throw std::invalid_argument("tiles_tree_ao_shadows: more than 2^30 tiles");
-		// (an open-addressed table keyed by the tile's coordinates: the call only enqueues, and at 4096 tiles a tree of pairs would cost more than the kernels)
-		uint32_t hbits = 4;
-		while ((1ull << hbits) < 2ull*n) {++hbits;}
-		uint32_t const hmask = (uint32_t)((1ull << hbits) - 1);
-		std::vector<int32_t> slots((size_t)hmask + 1, -1);
-		auto key_of = [](int32_t tx, int32_t ty) {return ((uint64_t)(uint32_t)tx << 32) | (uint32_t)ty;};
-		auto hash_of = [hbits](uint64_t k) {return (uint32_t)((k*0x9E3779B97F4A7C15ull) >> (64 - hbits));};
-		auto find = [&](int64_t tx, int64_t ty) -> int32_t { // the batch index of tile (tx, ty), -1: not in the batch
-			if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX) return -1;
-			uint64_t const k = key_of((int32_t)tx, (int32_t)ty);
-			for (uint32_t h = hash_of(k);; h = (h + 1) & hmask) {
-				int32_t const v = slots[h];
-				if (v < 0 || key_of(tile_xy[2*v], tile_xy[2*v+1]) == k) return v;
-			}
-		};
-		for (uint32_t t = 0; t < n; ++t) {
-			uint64_t const k = key_of(tile_xy[2*t], tile_xy[2*t+1]);
-			uint32_t h = hash_of(k);
-			for (; slots[h] >= 0; h = (h + 1) & hmask) {
-				if (key_of(tile_xy[2*slots[h]], tile_xy[2*slots[h]+1]) == k) throw std::invalid_argument("tiles_tree_ao_shadows: a tile appears twice in tile_xy");
-			}
-			slots[h] = (int32_t)t;
-		}
-		std::vector<int32_t> nbr((size_t)n*9);
+		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_tree_ao_shadows");
 		std::vector<tree_frame_t> fr(n);
 		for (uint32_t t = 0; t < n; ++t) {
-			for (int k = 0; k < 9; ++k) {nbr[(size_t)t*9 + k] = find((int64_t)tile_xy[2*t] + (k%3 - 1), (int64_t)tile_xy[2*t+1] + (k/3 - 1));}
 			int const x1 = (int)((uint32_t)tile_xy[2*t]*S), y1 = (int)((uint32_t)tile_xy[2*t+1]*S); // (as tiles_tree_map_dev)
 			fr[t].x = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); fr[t].y = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
 		}
@@ -3125,6 +3105,90 @@ template<class BE> struct terra_engine {
 			}
 			d_counts[t] = total;
 			if (d_pass) {d_pass[t] = (uint8_t)tl.wpass;}
+		});
+	}
+
+	// ---- the terrain draw list of a batch for a camera (terra_terrainview.hpp): the head of tile_draw_t::draw (src/tiled_mesh.cpp:2844-2915), get_lod_level
+	// (:1910-1932) and the crack look-ups of tile_t::draw (:2059-2074), over stats, min_normal_z and trmax as the tile passes left them.  The checks that need no array
+	// (the host form runs them before it stages anything):
+	void terrain_view_check(view_pod_t const &view, terrain_view_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_terrain_view: a member of the view is not finite");
+		if (!terrain_view_args_finite(a)) throw std::invalid_argument("tiles_terrain_view: a member of the args is not finite");
+		if (a.reflection_pass == 1) throw std::invalid_argument("tiles_terrain_view: reflection_pass 1 needs can_have_reflection, which stays with the engine");
+		if (a.reflection_pass < 0 || a.reflection_pass > 3) throw std::invalid_argument("tiles_terrain_view: reflection_pass must be 0, 2 or 3");
+	}
+	void tiles_terrain_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, terrain_view_args_pod_t const &a, terrain_view_in_t const &in,
+		uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn)
+	{
+		terrain_view_check(view, a);
+		if (n == 0) return;
+		if (!tile_xy || !in.stats || !d_status || !d_dist || !d_lod || !d_crack || !d_draw_order || !d_occluded || !d_counts) throw std::invalid_argument("tiles_terrain_view: null argument");
+		if ((((uintptr_t)in.stats | (uintptr_t)in.min_normal_z | (uintptr_t)in.trmax | (uintptr_t)in.tile_zmax | (uintptr_t)d_dist | (uintptr_t)d_draw_order | (uintptr_t)d_occluded |
+		      (uintptr_t)d_counts) & 3u) != 0) throw std::invalid_argument("tiles_terrain_view: d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_dist, d_draw_order, d_occluded and d_counts must be 4-byte aligned");
+		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_terrain_view");
+		terrain_view_consts_t const c = terrain_view_consts(view, a, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
+		// scratch: the coordinates and the neighbour table, the occluders of the batch in batch order with their count, the candidates that run the occlusion test, and
+		// the (dist, batch index) keys of the drawn tiles in batch order for the order's second path
+		int32_t *d_txy, *d_nbr_w; terrain_view_occluder_t *d_occ; uint32_t *d_nocc, *d_key_tile; uint8_t *d_test; float *d_keys;
+		stage_layout_t lay;
+		lay.add(d_occ, n); lay.add(d_txy, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_nocc, 4); lay.add(d_keys, n); lay.add(d_key_tile, n); lay.add(d_test, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		int32_t const *d_nbr = d_nbr_w;
+		if (be.tile_terrain_view(c, in, d_txy, d_nbr, n, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_occ, d_nocc, d_test, d_keys, d_key_tile)) return;
+		// the simple form.  (1) a logical thread per tile: everything but the occlusion test, the cracks and the lists
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			terrain_view_tile_t const o = terrain_view_tile(c, in, d_txy, t);
+			d_status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); d_dist[t] = o.dist; d_lod[t] = o.lod; d_test[t] = o.test;
+		});
+		// (2) one thread: the occluders in batch order, as the loop of :2858-2861 leaves them
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {
+			uint32_t m = 0;
+			for (uint32_t t = 0; t < n; ++t) {
+				if (!(d_status[t] & TV_WAS_OCCLUDER)) continue;
+				terrain_view_geom_t const g = terrain_view_geom_of(c, in, d_txy, t);
+				terrain_view_occluder_t &o = d_occ[m++];
+				terrain_view_mesh_box(g, in.stats[t].mzmin, in.stats[t].mzmax, o.bc);
+				for (uint32_t s = 0; s < 16; ++s) {terrain_view_occluder_column(c, g, in.stats[t], s, o.sub[s]);}
+				o.tile = (int32_t)t; o.pad = 0;
+			}
+			*d_nocc = m;
+		});
+		// (3) a thread per tile: the loop of :2872-2908
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint32_t const nocc = *d_nocc;
+			if ((d_status[t] & TV_STATUS_MASK) != TV_DRAWN || !d_test[t] || nocc == 0) return;
+			bool const occluded = terrain_view_occluded(c, terrain_view_geom_of(c, in, d_txy, t), in.stats[t], d_occ, nocc, (int32_t)t);
+			if (occluded) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
+			if (in.occl_state) {in.occl_state[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED;} // set_last_occluded (:2906)
+		});
+		// (4) a thread per tile: its cracks, and its place in its list -- the rank of (dist, batch index) among the drawn tiles is where the sort of :2915 puts it
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint32_t const me = d_status[t] & TV_STATUS_MASK;
+			for (uint32_t k = 0; k < 4; ++k) {
+				int32_t const u = d_nbr[t*9 + terrain_view_nbr_slot(k >> 1, k & 1u)];
+				bool const adj = me == TV_DRAWN && u >= 0 && (d_status[u] & TV_STATUS_MASK) != TV_ABSENT;
+				d_crack[t*4 + k] = adj ? (uint8_t)terrain_view_crack_index(k >> 1, k & 1u, d_lod[t], d_lod[u]) : TERRAIN_VIEW_NO_CRACK;
+			}
+			if (d_not_drawn) {d_not_drawn[t] = (me != TV_DRAWN) ? 1 : 0;}
+			if (me == TV_DRAWN) {
+				uint32_t rank = 0;
+				for (uint32_t u = 0; u < n; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_DRAWN && terrain_view_before(d_dist[u], u, d_dist[t], (uint32_t)t)) ? 1u : 0u;}
+				d_draw_order[rank] = (uint32_t)t;
+			}
+			else if (me == TV_OCCLUDED) {
+				uint32_t rank = 0;
+				for (uint32_t u = 0; u < t; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_OCCLUDED) ? 1u : 0u;}
+				d_occluded[rank] = (uint32_t)t;
+			}
+			if (t == 0) {
+				uint32_t nd = 0, no = 0;
+				for (uint32_t u = 0; u < n; ++u) {uint32_t const su = d_status[u] & TV_STATUS_MASK; nd += (su == TV_DRAWN) ? 1u : 0u; no += (su == TV_OCCLUDED) ? 1u : 0u;}
+				d_counts[0] = nd; d_counts[1] = no;
+			}
 		});
 	}
 

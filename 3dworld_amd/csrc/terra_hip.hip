@@ -671,6 +671,22 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	{
 		return launch_per_tile<terra::GV_THREADS>(terra::k_grass_view, n, c, tile_xy, zvals, stats, blocks, skip, capacity, insts, aux, group_counts, counts, pass, keys);
 	}
+	// the terrain draw list for a camera: the five launches of k_terrain_view_* (terra_kernels.hpp)
+	bool tile_terrain_view(terra::terrain_view_consts_t const &c, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, uint8_t *status,
+		float *dist, uint8_t *lod, uint8_t *crack, uint32_t *draw_order, uint32_t *occluded, uint32_t *counts, uint8_t *not_drawn, terra::terrain_view_occluder_t *occ, uint32_t *nocc, uint8_t *test,
+		float *keys, uint32_t *key_tile)
+	{
+		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
+		hipLaunchKernelGGL(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, stream, c, in, tile_xy, n, status, dist, lod, test);
+		hipLaunchKernelGGL(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, stream, c, in, tile_xy, n, status, occ, nocc);
+		hipLaunchKernelGGL(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, stream, c, in, tile_xy, occ, nocc, test, status);
+		hipLaunchKernelGGL(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, stream, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
+		hipLaunchKernelGGL(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, stream, keys, key_tile, counts, draw_order);
+		TERRA_HIP_CHECK(hipGetLastError());
+		return true;
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

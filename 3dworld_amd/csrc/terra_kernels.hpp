@@ -2054,6 +2054,139 @@ __global__ __launch_bounds__(GV_THREADS) void k_grass_view(grass_view_consts_t c
 	if (tid == 0) {counts[t] = carry;}
 }
 
+// ------------------------------------------------------------------ the terrain draw list of a tile batch for a camera (the head of tile_draw_t::draw,
+// src/tiled_mesh.cpp:2844-2915; terra_terrainview.hpp), five launches on one stream:
+//  1. k_terrain_view_tiles: a lane per tile runs terrain_view_tile -- centre, boxes, is_visible, use_as_occluder, the filters of :2867-2868, get_lod_level -- and
+//     leaves status (a candidate as TV_DRAWN), dist, lod and whether the tile runs the occlusion test.
+//  2. k_terrain_view_occluders: one workgroup compacts the occluders in batch order (tp_block_rank, the record kernels' ranking) and builds their 17 boxes, a lane a box.
+//  3. k_terrain_view_occlusion: a workgroup of 256 lanes per tile; every tile but a candidate that is to be tested leaves at once.  Lane (q, s) = (sub-box of the
+//     tile, column of the occluder).  The occluders are walked in order; an occluder's record is read at a uniform address (scalar loads), and the `intersected`
+//     test of :2881 -- the tile's four top points against the occluder's mesh box -- is a uniform branch around everything else.  A lane then clips its sub-box's
+//     centre against the mesh box and its four top points against its column.  "Any over s" is a 16-bit segment of the wave's ballot, "all over q" the four
+//     segments of a wave and the four waves through LDS.  No atomics; the result does not depend on the order of the occluders.
+//  4. k_terrain_view_lists: one workgroup walks the batch 256 tiles at a time: a lane writes its tile's four crack bytes (the neighbours' lod and presence through
+//     the [n][9] table), the optional skip byte, the occluded tiles are appended in batch order (tp_emit), and the drawn tiles' (dist, batch index) keys are compacted in batch order, into
+//     global scratch and, the first TV_ORDER_LDS of them, into LDS.  With at most TV_ORDER_LDS drawn tiles the order is made here: an entry's place after the sort
+//     of :2915 is its rank by (dist, batch index) -- std::pair's operator< with the index in the pointer's place --, counted against the keys in LDS, which every
+//     lane reads at the same address.
+//  5. k_terrain_view_rank: the second path, for more drawn tiles than that: the same rank, a lane an entry over as many workgroups as it takes, against the keys in
+//     global scratch (uniform addresses again).  It leaves at once when step 4 has made the order.
+constexpr uint32_t TV_THREADS = 256, TV_ORDER_LDS = 1024;
+static_assert(TV_THREADS == TREEP_THREADS, "tp_block_rank and tp_emit rank TREEP_THREADS threads");
+__global__ __launch_bounds__(TV_THREADS) void k_terrain_view_tiles(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy, uint32_t n,
+	uint8_t *__restrict__ status, float *__restrict__ dist, uint8_t *__restrict__ lod, uint8_t *__restrict__ test)
+{
+	uint32_t const t = blockIdx.x*TV_THREADS + threadIdx.x;
+	if (t >= n) return;
+	terrain_view_tile_t const o = terrain_view_tile(c, in, tile_xy, t);
+	status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); dist[t] = o.dist; lod[t] = o.lod; test[t] = o.test;
+}
+__global__ __launch_bounds__(TV_THREADS) void k_terrain_view_occluders(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy, uint32_t n,
+	uint8_t const *__restrict__ status, terrain_view_occluder_t *occ, uint32_t *__restrict__ nocc)
+{
+	__shared__ uint32_t s_wave[TV_THREADS/64];
+	uint32_t const tid = threadIdx.x;
+	uint32_t count = 0;
+	for (uint32_t base = 0; base < n; base += TV_THREADS) {
+		uint32_t const t = base + tid;
+		bool const ok = t < n && (status[t] & TV_WAS_OCCLUDER) != 0;
+		uint32_t total;
+		uint32_t const rank = tp_block_rank(ok, s_wave, total);
+		if (ok) {occ[count + rank].tile = (int32_t)t; occ[count + rank].pad = 0;}
+		count += total;
+	}
+	if (tid == 0) {*nocc = count;}
+	__syncthreads(); // the tiles of the records, written by other lanes
+	for (uint32_t i = tid; i < count*17u; i += TV_THREADS) {
+		uint32_t const j = i/17u, s = i - j*17u;
+		uint32_t const t = (uint32_t)occ[j].tile;
+		terrain_view_geom_t const g = terrain_view_geom_of(c, in, tile_xy, t);
+		float d[3][2];
+		if (s == 16u) {terrain_view_mesh_box(g, in.stats[t].mzmin, in.stats[t].mzmax, d);}
+		else {terrain_view_occluder_column(c, g, in.stats[t], s, d);}
+		float *const o = (s == 16u) ? &occ[j].bc[0][0] : &occ[j].sub[s][0][0];
+		for (int k = 0; k < 6; ++k) {o[k] = d[k >> 1][k & 1];}
+	}
+}
+__global__ __launch_bounds__(TV_THREADS) void k_terrain_view_occlusion(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy,
+	terrain_view_occluder_t const *__restrict__ occ, uint32_t const *__restrict__ nocc_p, uint8_t const *__restrict__ test, uint8_t *status)
+{
+	__shared__ uint32_t s_all[TV_THREADS/64];
+	uint32_t const t = blockIdx.x, tid = threadIdx.x, nocc = *nocc_p;
+	if ((status[t] & TV_STATUS_MASK) != TV_DRAWN || !test[t] || nocc == 0u) return; // (uniform)
+	terrain_view_geom_t const g = terrain_view_geom_of(c, in, tile_xy, t);
+	uint32_t const q = tid >> 4, s = tid & 15u;
+	float b[3][2];
+	terrain_view_sub_box(g, in.stats[t], q, b);
+	float const cx = 0.5f*(b[0][0] + b[0][1]), cy = 0.5f*(b[1][0] + b[1][1]), cz = 0.5f*(b[2][0] + b[2][1]); // get_cube_center()
+	bool hidden = false;
+	for (uint32_t j = 0; j < nocc; ++j) {
+		terrain_view_occluder_t const &o = occ[j];
+		if (o.tile == (int32_t)t) continue;                 // no self-occlusion (uniform)
+		if (!terrain_view_top_any(c, g.bc, o.bc)) continue; // not in occluder_ixs (uniform)
+		hidden = hidden || terrain_view_column_hides(c, o, s, b, cx, cy, cz);
+	}
+	unsigned long long const m = __ballot(hidden);
+	bool all4 = true; // this wave's four sub-boxes: each hidden by some column
+	for (uint32_t k = 0; k < 4u; ++k) {all4 = all4 && ((m >> (16u*k)) & 0xFFFFull) != 0ull;}
+	if ((tid & 63u) == 0u) {s_all[tid >> 6] = all4 ? 1u : 0u;}
+	__syncthreads();
+	if (tid == 0) {
+		bool const occluded = s_all[0] && s_all[1] && s_all[2] && s_all[3];
+		if (occluded) {status[t] = (uint8_t)((status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
+		if (in.occl_state) {in.occl_state[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED;} // set_last_occluded (:2906)
+	}
+}
+// rank of entry i (key di) among the m keys k[0 .. m): the entries before it by (dist, position); positions are in batch order
+__device__ __forceinline__ uint32_t tv_rank(float const *k, uint32_t m, float di, uint32_t i) {
+	uint32_t rank = 0;
+	for (uint32_t j = 0; j < m; ++j) {rank += terrain_view_before(k[j], j, di, i) ? 1u : 0u;}
+	return rank;
+}
+__global__ __launch_bounds__(TV_THREADS) void k_terrain_view_lists(int32_t const *__restrict__ nbr, uint32_t n, uint8_t const *__restrict__ status, float const *__restrict__ dist,
+	uint8_t const *__restrict__ lod, uint8_t *__restrict__ crack, uint32_t *__restrict__ draw_order, uint32_t *__restrict__ occluded, uint32_t *__restrict__ counts,
+	uint8_t *__restrict__ not_drawn, float *__restrict__ keys, uint32_t *__restrict__ key_tile)
+{
+	__shared__ uint32_t s_wave[TV_THREADS/64], s_tile[TV_ORDER_LDS];
+	__shared__ float s_key[TV_ORDER_LDS];
+	uint32_t const tid = threadIdx.x;
+	uint32_t nd = 0, no = 0;
+	for (uint32_t base = 0; base < n; base += TV_THREADS) {
+		uint32_t const t = base + tid;
+		uint32_t const me = (t < n) ? (uint32_t)(status[t] & TV_STATUS_MASK) : (uint32_t)TV_ABSENT;
+		if (t < n) {
+			uint32_t cr = 0;
+			for (uint32_t k = 0; k < 4u; ++k) {
+				int32_t const u = nbr[(size_t)t*9u + terrain_view_nbr_slot(k >> 1, k & 1u)];
+				bool const adj = me == TV_DRAWN && u >= 0 && (status[u] & TV_STATUS_MASK) != TV_ABSENT;
+				cr |= (adj ? terrain_view_crack_index(k >> 1, k & 1u, lod[t], lod[u]) : (uint32_t)TERRAIN_VIEW_NO_CRACK) << (8u*k);
+			}
+			for (uint32_t k = 0; k < 4u; ++k) {crack[(size_t)t*4u + k] = (uint8_t)(cr >> (8u*k));}
+			if (not_drawn) {not_drawn[t] = (me != TV_DRAWN) ? 1 : 0;}
+		}
+		tp_emit(me == TV_OCCLUDED, [&] {return t;}, occluded, n, no, s_wave);
+		uint32_t total;
+		uint32_t const rank = tp_block_rank(me == TV_DRAWN, s_wave, total);
+		if (me == TV_DRAWN) {
+			float const d = dist[t];
+			keys[nd + rank] = d; key_tile[nd + rank] = t;
+			if (nd + rank < TV_ORDER_LDS) {s_key[nd + rank] = d; s_tile[nd + rank] = t;}
+		}
+		nd += total;
+	}
+	if (tid == 0) {counts[0] = nd; counts[1] = no;}
+	if (nd > TV_ORDER_LDS) return; // k_terrain_view_rank makes the order
+	__syncthreads();
+	for (uint32_t i = tid; i < nd; i += TV_THREADS) {draw_order[tv_rank(s_key, nd, s_key[i], i)] = s_tile[i];}
+}
+__global__ __launch_bounds__(TV_THREADS) void k_terrain_view_rank(float const *__restrict__ keys, uint32_t const *__restrict__ key_tile, uint32_t const *__restrict__ counts,
+	uint32_t *__restrict__ draw_order)
+{
+	uint32_t const nd = counts[0], i = blockIdx.x*TV_THREADS + threadIdx.x;
+	if (nd <= TV_ORDER_LDS || i >= nd) return;
+	draw_order[tv_rank(keys, nd, keys[i], i)] = key_tile[i];
+}
+
 // ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
 // terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
 // k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes

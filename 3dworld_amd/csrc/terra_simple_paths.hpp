@@ -194,6 +194,9 @@ template<class DERIVED> struct simple_paths {
 	// the grass view's kernel: none here -- the driver (tiles_grass_view_dev) then runs its one-thread-per-tile form, the reference's loops
 	bool tile_grass_view(grass_view_consts_t const &, int32_t const *, uint32_t, float const *, terra_tile_stats const *, grass_block_pod_t const *, uint8_t const *, uint32_t,
 		float *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint16_t *) {return false;}
+	// the terrain view's kernels: none here -- the driver (tiles_terrain_view_dev) then runs its one-thread-per-tile form, the reference's loops
+	bool tile_terrain_view(terrain_view_consts_t const &, terrain_view_in_t const &, int32_t const *, int32_t const *, uint32_t, uint8_t *, float *, uint8_t *, uint8_t *, uint32_t *,
+		uint32_t *, uint32_t *, uint8_t *, terrain_view_occluder_t *, uint32_t *, uint8_t *, float *, uint32_t *) {return false;}
 	// tile erosion, wave form: the clamp-padded copies live in HBM/L2, ONE WAVE per tile walks the droplets in order through a 32x32 LDS window
 	// (10 KB of LDS per tile instead of 76 KB: ~15 tiles per CU in flight instead of 2)
 	void tile_erosion_windowed(uint32_t n, float *zvals, erosion_consts_t const &ec, uint32_t iters, float *padded /* n*NX*NY */) {

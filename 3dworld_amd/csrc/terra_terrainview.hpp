@@ -1,0 +1,270 @@
+// terra_terrainview.hpp -- the terrain draw list of a tile batch for a camera: the head of tile_draw_t::draw (src/tiled_mesh.cpp:2844-2915) with
+// occluder_cubes_t's constructor (:2834-2842) and calc_cube_top_points (:2823-2832), tile_t::get_lod_level (:1910-1932), the crack look-ups of tile_t::draw
+// (:2059-2074) with crack_ibuf_t::get_index (:2020-2023), tile_t::use_as_occluder (:3801-3803), get_bsphere_radius_inc_water (:366-368), get_center / get_bcube /
+// get_mesh_sub_bcube / get_sub_bcube / get_rel_dist_to_camera / rel_dist_to_camera_xy_lt / is_visible (src/tiled_mesh.h:229-252,320-332), the constants
+// (src/tiled_mesh.cpp:23,33; src/tiled_mesh.h:24-25,32,93-94), pos_dir_up::sphere_visible_test and sphere_and_cube_visible_test (src/visibility.cpp:119-128,
+// 215-219), behind_sphere_mult (:83), cube_t::get_cube_center (src/3DWorld.h:602-604), dist_xy_less_than / p2p_dist_xy (src/inlines.h:183-195) and
+// check_line_clip (src/inlines.h:509-512) = get_line_clip (src/Math3d.cpp:1037-1052).
+//
+// The bodies are shared by the driver's simple form (one logical thread per tile, the reference's loops) and by the k_terrain_view_* kernels
+// (terra_kernels.hpp).  cube_visible is terra_grassview.hpp's view_cube_visible, the line clip terra_common.hpp's shadow_line_clip.  Every operand carries the type
+// the reference statement gives it; where the C++ source promotes to double the promotion is written out; sums run in the reference's order (the library is built
+// without contraction).
+//
+// The occlusion loops' early exits (`&& !intersected`, `&& !sub_tile_occluded`, `&& sub_tile_occluded`, the `break` of :2904) only shortcut booleans: the result of
+// a tile is "for every sub-box t there is an occluder o, not the tile itself, with any of the tile's four top points clipped by o's mesh box, the sub-box's centre
+// clipped by it, and a column s of o that is not zeroed and clips all four top points of the sub-box".  It does not depend on the order of the occluders.
+#pragma once
+#include "terra_common.hpp"
+#include "terra_grassview.hpp"
+#include "../../include/terra.h"
+
+namespace terra {
+
+constexpr uint32_t TERRAIN_VIEW_LODS = 5;          // NUM_LODS (src/tiled_mesh.h:25)
+constexpr uint8_t  TERRAIN_VIEW_NO_CRACK = 255;    // no present neighbour, or the tile is not drawn
+enum {TV_ABSENT = 0, TV_TOO_FAR = 1, TV_NOT_VISIBLE = 2, TV_OCCLUDED_BEFORE = 3, TV_OCCLUDED = 4, TV_DRAWN = 5, TV_STATUS_MASK = 7, TV_WAS_OCCLUDER = 0x80}; // status
+enum {TV_FLAG_ABSENT = 1, TV_FLAG_NO_OCCLUDER = 2, TV_FLAG_SHADOW_MAPS = 4};                                                                                 // flags
+enum {TV_STATE_NONE = 0, TV_STATE_OCCLUDED = 1, TV_STATE_UNOCCLUDED = 2};                                                                                    // occl_state
+
+struct terrain_view_args_pod_t {float behind_sphere_mult, occluder_zmin; int32_t water_enabled, check_occlusion, reflection_pass;}; // terra_terrain_view_args
+
+struct terrain_view_consts_t {
+	view_pod_t v;
+	float behind_sphere_mult;
+	float xss, yss, DX_VAL, DY_VAL;
+	int S, dxoff, dyoff;
+	float scaled_tile_radius;            // get_scaled_tile_radius() (src/tiled_mesh.h:94)
+	float water_plane_z, occluder_zmin;
+	int water_enabled, check_occlusion, reflection_pass;
+};
+inline terrain_view_consts_t terrain_view_consts(view_pod_t const &v, terrain_view_args_pod_t const &a, float xss, float yss, float DX_VAL, float DY_VAL, int S, int dxoff,
+	int dyoff, float water_plane_z)
+{
+	terrain_view_consts_t c;
+	c.v = v; c.behind_sphere_mult = a.behind_sphere_mult; c.xss = xss; c.yss = yss; c.DX_VAL = DX_VAL; c.DY_VAL = DY_VAL; c.S = S; c.dxoff = dxoff; c.dyoff = dyoff;
+	int const TILE_RADIUS = 6;                           // src/tiled_mesh.h:24
+	c.scaled_tile_radius = (float)TILE_RADIUS*(xss + yss); // TILE_RADIUS*get_tile_width()
+	c.water_plane_z = water_plane_z; c.occluder_zmin = a.occluder_zmin;
+	c.water_enabled = a.water_enabled ? 1 : 0; c.check_occlusion = a.check_occlusion ? 1 : 0; c.reflection_pass = a.reflection_pass;
+	return c;
+}
+// behind_sphere_mult = max(1.0, A*A)*max(1.0, 2.0f/((double)tterm*tterm*(1.0 + A*A))) (src/visibility.cpp:83): A is a double member, tterm the float tanf(angle)
+inline float view_behind_sphere_mult(float angle, float aspect) {
+	double const A = (double)aspect;
+	float const tterm = tanf(angle);
+	double const a = (1.0 < A*A) ? A*A : 1.0, q = (double)2.0f/(((double)tterm*(double)tterm)*(1.0 + A*A)), b = (1.0 < q) ? q : 1.0; // std::max(a, b) = (a < b) ? b : a
+	return (float)(a*b);
+}
+
+// ---- log2 of a positive normal double in plain double arithmetic, the same on the host and on the device (get_lod_level divides by -log2(2.0*min_normal_z),
+// :1924, and the device library's log2 is not the C library's).  x = 2^e*m with m in (sqrt(1/2), sqrt(2)]; f = m - 1, s = f/(2 + f), z = s*s;
+// log(m) = 2*atanh(s) = f - hfsq + s*(hfsq + R), hfsq = f*f/2, R = z*(2/3 + z*(2/5 + ...)) (z <= 0.0295: twelve terms reach below 2^-60); the head f - hfsq is
+// split so that its product with the head of 1/ln 2 is exact, and e is added last with its rounding error carried.
+TERRA_HD double terrain_view_log2(double x) {
+	uint64_t u; memcpy(&u, &x, 8);
+	int e = (int)(u >> 52) - 1023;
+	u = (u & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;
+	double m; memcpy(&m, &u, 8);
+	if (m > 1.4142135623730951) {m *= 0.5; ++e;}
+	double const f = m - 1.0, s = f/(2.0 + f), z = s*s, hfsq = 0.5*f*f;
+	double r = 2.0/25.0;
+	r = 2.0/23.0 + z*r; r = 2.0/21.0 + z*r; r = 2.0/19.0 + z*r; r = 2.0/17.0 + z*r; r = 2.0/15.0 + z*r; r = 2.0/13.0 + z*r; r = 2.0/11.0 + z*r;
+	r = 2.0/9.0 + z*r; r = 2.0/7.0 + z*r; r = 2.0/5.0 + z*r; r = 2.0/3.0 + z*r;
+	double const R = z*r;
+	double hi = f - hfsq;
+	uint64_t h; memcpy(&h, &hi, 8); h &= 0xFFFFFFFFF8000000ull; memcpy(&hi, &h, 8);
+	double const lo = ((f - hi) - hfsq) + s*(hfsq + R);
+	double const ivln2hi = 0x1.715476p+0, ivln2lo = 0x1.4ae0bf85ddf44p-26; // 1/ln 2 = ivln2hi + ivln2lo, ivln2hi of 26 bits
+	double const val_hi = hi*ivln2hi;
+	double val_lo = (lo + hi)*ivln2lo + lo*ivln2hi;
+	double const y = (double)e, w = y + val_hi;
+	val_lo += (y - w) + val_hi;
+	return val_lo + w;
+}
+
+// ---- a tile's boxes and centre
+struct terrain_view_geom_t {
+	float cx, cy, cz;          // get_center()
+	float xv1, yv1, xv2, yv2;  // the mesh box's corners: get_xval(x1 + xoff - xoff2), xv1 + (x2 - x1)*DX_VAL
+	float bc[3][2];            // get_bcube()
+	float zadd;                // get_tile_zmax() - mzmax (get_sub_bcube)
+};
+TERRA_HD terrain_view_geom_t terrain_view_geom(terrain_view_consts_t const &c, int tx, int ty, float mzmin, float mzmax, float trmax, float tile_zmax) {
+	terrain_view_geom_t g;
+	float const BCUBE_ZTOLER = 1.0E-6f;
+	int const x1 = (int)((uint32_t)tx*(uint32_t)c.S), y1 = (int)((uint32_t)ty*(uint32_t)c.S); // integer steps wrap as in the reference binary
+	int const mx = (int)((uint32_t)x1 + (uint32_t)x1 + (uint32_t)c.S) >> 1, my = (int)((uint32_t)y1 + (uint32_t)y1 + (uint32_t)c.S) >> 1;
+	g.cx = -c.xss + c.DX_VAL*(float)(int)((uint32_t)mx + (uint32_t)c.dxoff); g.cy = -c.yss + c.DY_VAL*(float)(int)((uint32_t)my + (uint32_t)c.dyoff);
+	g.cz = 0.5f*(mzmin + mzmax);
+	g.xv1 = -c.xss + c.DX_VAL*(float)(int)((uint32_t)x1 + (uint32_t)c.dxoff); g.yv1 = -c.yss + c.DY_VAL*(float)(int)((uint32_t)y1 + (uint32_t)c.dyoff);
+	g.xv2 = g.xv1 + (float)c.S*c.DX_VAL; g.yv2 = g.yv1 + (float)c.S*c.DY_VAL;
+	g.bc[0][0] = g.xv1 - trmax; g.bc[0][1] = g.xv2 + trmax; g.bc[1][0] = g.yv1 - trmax; g.bc[1][1] = g.yv2 + trmax;
+	g.bc[2][0] = mzmin - BCUBE_ZTOLER; g.bc[2][1] = max_std(tile_zmax + BCUBE_ZTOLER, c.water_plane_z);
+	g.zadd = tile_zmax - mzmax;
+	return g;
+}
+// get_mesh_bcube()
+TERRA_HD void terrain_view_mesh_box(terrain_view_geom_t const &g, float mzmin, float mzmax, float d[3][2]) {
+	d[0][0] = g.xv1; d[0][1] = g.xv2; d[1][0] = g.yv1; d[1][1] = g.yv2; d[2][0] = mzmin - 1.0E-6f; d[2][1] = mzmax + 1.0E-6f;
+}
+// get_mesh_sub_bcube(x, y): sub_zmin[y][x]
+TERRA_HD void terrain_view_mesh_sub_box(terrain_view_geom_t const &g, terra_tile_stats const &st, uint32_t x, uint32_t y, float d[3][2]) {
+	float const dx = (g.xv2 - g.xv1)/(float)4, dy = (g.yv2 - g.yv1)/(float)4;
+	d[0][0] = g.xv1 + (float)x*dx; d[0][1] = g.xv1 + (float)(x + 1u)*dx; d[1][0] = g.yv1 + (float)y*dy; d[1][1] = g.yv1 + (float)(y + 1u)*dy;
+	d[2][0] = st.sub_zmin[4u*y + x]; d[2][1] = st.sub_zmax[4u*y + x];
+}
+// get_rel_dist_to_camera(xy_dist = 1)
+TERRA_HD float terrain_view_rel_dist_xy(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float radius) {
+	float const *cam = c.v.pos;
+	float const d = sqrtf((cam[0] - g.cx)*(cam[0] - g.cx) + (cam[1] - g.cy)*(cam[1] - g.cy));
+	return max_std(0.0f, d - radius)/c.scaled_tile_radius;
+}
+// get_dist_to_camera_in_tiles(xy_dist = 0)
+TERRA_HD float terrain_view_dist_in_tiles(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float radius) {
+	float const *cam = c.v.pos;
+	float const d = sqrtf((cam[0] - g.cx)*(cam[0] - g.cx) + (cam[1] - g.cy)*(cam[1] - g.cy) + (cam[2] - g.cz)*(cam[2] - g.cz));
+	return (max_std(0.0f, d - radius)/c.scaled_tile_radius)*(float)6;
+}
+// pos_dir_up::sphere_visible_test
+TERRA_HD bool view_sphere_visible(view_pod_t const &v, float behind_sphere_mult, float px, float py, float pz, float radius) {
+	if (!v.valid) return radius >= 0.0f;
+	float const x = px - v.pos[0], y = py - v.pos[1], z = pz - v.pos[2]; // vector3d const pv(pos_, pos)
+	float const msq = x*x + y*y + z*z;
+	if (view_dot(v.dir, x, y, z) < 0.0f) return radius > 0.0f && msq < radius*radius*behind_sphere_mult; // sphere behind
+	float const dist = sqrtf(msq);
+	if (fabsf(view_dot(v.upv, x, y, z)) > dist*v.sterm + radius) return false;
+	if (fabsf(view_dot(v.cp, x, y, z)) > dist*v.x_sterm + radius) return false;
+	return (dist + radius) > v.near_ && (dist - radius) < v.far_;
+}
+// tile_t::is_visible(): sphere_and_cube_visible_test(get_center(), get_bsphere_radius_inc_water(), get_bcube())
+TERRA_HD bool terrain_view_visible(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float mzmin, float mzmax, float radius) {
+	float const r = (c.water_enabled && mzmax < c.water_plane_z) ? max_std(radius, c.water_plane_z - 0.5f*(mzmin + mzmax)) : radius;
+	if (!view_sphere_visible(c.v, c.behind_sphere_mult, g.cx, g.cy, g.cz, r)) return false; // none of the sphere is visible
+	if (view_sphere_visible(c.v, c.behind_sphere_mult, g.cx, g.cy, g.cz, -r)) return true;  // all of the sphere is visible
+	return view_cube_visible(c.v, g.bc);
+}
+// rel_dist_to_camera_xy_lt(OCCLUDER_DIST): the distance half of use_as_occluder()
+TERRA_HD bool terrain_view_occluder_dist(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float radius) {
+	float const *cam = c.v.pos;
+	float const OCCLUDER_DIST = 0.2f, dval = OCCLUDER_DIST*c.scaled_tile_radius + radius;
+	return (cam[0] - g.cx)*(cam[0] - g.cx) + (cam[1] - g.cy)*(cam[1] - g.cy) < dval*dval;
+}
+// tile_t::get_lod_level(reflection_pass) for reflection_pass != 1 (low_detail is false): in_tiles = get_dist_to_camera_in_tiles(0)
+TERRA_HD uint32_t terrain_view_lod(terrain_view_consts_t const &c, float mzmin, float mzmax, float min_normal_z, float in_tiles, bool shadow_maps) {
+	if (mzmax == mzmin) return TERRAIN_VIEW_LODS - 1u; // flat, use lowest LOD
+	uint32_t lod_level = 0;
+	float dist = in_tiles;
+	if (shadow_maps) {dist /= (float)2;}
+	if (min_normal_z > 0.0f) {
+		if ((double)min_normal_z > 0.9) {
+			if (!c.water_enabled || mzmax < c.water_plane_z || mzmin > c.water_plane_z) {dist = (float)((double)dist*(((double)min_normal_z > 0.95) ? 4.0 : 2.0));}
+		}
+		else if ((double)min_normal_z < 0.25) {dist = (float)((double)dist/-terrain_view_log2(2.0*(double)min_normal_z));}
+	}
+	double const thresh = c.reflection_pass ? 1.8 : 2.0;
+	while ((double)dist > thresh && lod_level + 1u < TERRAIN_VIEW_LODS && ((uint32_t)c.S >> (lod_level + 1u)) >= 4u) {
+		dist /= (float)2;
+		++lod_level;
+	}
+	return lod_level;
+}
+// crack_ibuf_t::get_index
+TERRA_HD uint32_t terrain_view_crack_index(uint32_t dim, uint32_t dir, uint32_t cur_lod, uint32_t adj_lod) {
+	return TERRAIN_VIEW_LODS*(TERRAIN_VIEW_LODS*(2u*dim + dir) + cur_lod) + adj_lod;
+}
+// the slot of get_adj_tile(dx, dy) in the [n][9] neighbour table ((dy + 1)*3 + dx + 1) for the crack loop's (dim, dir) (:2063-2067)
+TERRA_HD uint32_t terrain_view_nbr_slot(uint32_t dim, uint32_t dir) {return dim ? (dir ? 7u : 1u) : (dir ? 5u : 3u);}
+
+// ---- what the first pass leaves of a tile: everything but the occlusion test, the cracks and the lists
+struct terrain_view_tile_t {float dist; uint8_t status, lod, occluder, test;}; // status: TV_ABSENT .. TV_OCCLUDED_BEFORE, or TV_DRAWN for a candidate; test: the loop of :2872 runs (if there are occluders)
+struct terrain_view_in_t { // the per-tile arrays
+	terra_tile_stats const *stats; float const *min_normal_z, *trmax, *tile_zmax; uint8_t const *flags; uint8_t *occl_state;
+};
+TERRA_HD terrain_view_geom_t terrain_view_geom_of(terrain_view_consts_t const &c, terrain_view_in_t const &in, int32_t const *tile_xy, size_t t) {
+	terra_tile_stats const &st = in.stats[t];
+	return terrain_view_geom(c, tile_xy[2*t], tile_xy[2*t + 1], st.mzmin, st.mzmax, in.trmax ? in.trmax[t] : 0.0f, in.tile_zmax ? in.tile_zmax[t] : st.mzmax);
+}
+TERRA_HD terrain_view_tile_t terrain_view_tile(terrain_view_consts_t const &c, terrain_view_in_t const &in, int32_t const *tile_xy, size_t t) {
+	terrain_view_tile_t o;
+	o.dist = 0.0f; o.status = TV_ABSENT; o.lod = 0; o.occluder = 0; o.test = 0;
+	uint32_t const fl = in.flags ? in.flags[t] : 0u;
+	if (fl & TV_FLAG_ABSENT) return o;
+	terra_tile_stats const &st = in.stats[t];
+	terrain_view_geom_t const g = terrain_view_geom_of(c, in, tile_xy, t);
+	float const DRAW_DIST_TILES = 1.5f;
+	o.dist = terrain_view_rel_dist_xy(c, g, st.radius);
+	o.lod = (uint8_t)terrain_view_lod(c, st.mzmin, st.mzmax, in.min_normal_z ? in.min_normal_z[t] : 0.0f, terrain_view_dist_in_tiles(c, g, st.radius), (fl & TV_FLAG_SHADOW_MAPS) != 0);
+	bool const visible = terrain_view_visible(c, g, st.mzmin, st.mzmax, st.radius);
+	o.occluder = (c.check_occlusion && !(fl & TV_FLAG_NO_OCCLUDER) && terrain_view_occluder_dist(c, g, st.radius) && visible) ? 1 : 0; // use_as_occluder() (:2857-2860)
+	uint32_t const state = in.occl_state ? in.occl_state[t] : (uint32_t)TV_STATE_NONE;
+	if (o.dist > DRAW_DIST_TILES) {o.status = TV_TOO_FAR;}
+	else if (!visible) {o.status = TV_NOT_VISIBLE;}
+	else if (state == TV_STATE_OCCLUDED) {o.status = TV_OCCLUDED_BEFORE;} // was_last_occluded() (:2868)
+	else {o.status = TV_DRAWN; o.test = (state != TV_STATE_UNOCCLUDED) ? 1 : 0;} // !was_last_unoccluded() (:2872)
+	return o;
+}
+
+// ---- an occluder: occluder_cubes_t
+struct alignas(16) terrain_view_occluder_t {float bc[3][2]; float sub[16][3][2]; int32_t tile, pad;};
+static_assert(sizeof(terrain_view_occluder_t) == 416, "terrain_view_occluder_t: 26 16-byte loads");
+// column s of the occluder: get_mesh_sub_bcube(s >> 2, s & 3), zeroed where cube_visible fails, else the column from occluder_zmin up to sub_zmin (:2837-2840)
+TERRA_HD void terrain_view_occluder_column(terrain_view_consts_t const &c, terrain_view_geom_t const &g, terra_tile_stats const &st, uint32_t s, float d[3][2]) {
+	terrain_view_mesh_sub_box(g, st, s >> 2, s & 3u, d);
+	if (!view_cube_visible(c.v, d)) {for (int i = 0; i < 3; ++i) {d[i][0] = 0.0f; d[i][1] = 0.0f;} return;}
+	d[2][1] = d[2][0]; // cube below the bcube
+	d[2][0] = c.occluder_zmin;
+}
+TERRA_HD bool terrain_view_all_zeros(float const d[3][2]) {return d[0][0] == 0.0f && d[0][1] == 0.0f && d[1][0] == 0.0f && d[1][1] == 0.0f && d[2][0] == 0.0f && d[2][1] == 0.0f;}
+// check_line_clip(p, camera, d)
+TERRA_HD bool terrain_view_clip(terrain_view_consts_t const &c, float px, float py, float pz, float const d[3][2]) {
+	shadow_pt_t v1 = {px, py, pz}, v2 = {c.v.pos[0], c.v.pos[1], c.v.pos[2]};
+	return shadow_line_clip(v1, v2, d);
+}
+// calc_cube_top_points: cube_pts[(i0 << 1) + i1] = (d[0][i0], d[1][i1], d[2][1]); any / all of the four against a box
+TERRA_HD bool terrain_view_top_any(terrain_view_consts_t const &c, float const b[3][2], float const d[3][2]) {
+	bool r = false;
+	for (int k = 0; k < 4; ++k) {r = r || terrain_view_clip(c, b[0][k >> 1], b[1][k & 1], b[2][1], d);}
+	return r;
+}
+TERRA_HD bool terrain_view_top_all(terrain_view_consts_t const &c, float const b[3][2], float const d[3][2]) {
+	bool r = true;
+	for (int k = 0; k < 4; ++k) {r = r && terrain_view_clip(c, b[0][k >> 1], b[1][k & 1], b[2][1], d);}
+	return r;
+}
+// get_sub_bcube(t >> 2, t & 3)
+TERRA_HD void terrain_view_sub_box(terrain_view_geom_t const &g, terra_tile_stats const &st, uint32_t t, float d[3][2]) {
+	terrain_view_mesh_sub_box(g, st, t >> 2, t & 3u, d);
+	d[2][1] += g.zadd;
+}
+// does occluder o's column s hide sub-box b (centre cx, cy, cz) of a tile that o's mesh box intersects?  (:2892-2901 for one s)
+TERRA_HD bool terrain_view_column_hides(terrain_view_consts_t const &c, terrain_view_occluder_t const &o, uint32_t s, float const b[3][2], float cx, float cy, float cz) {
+	if (!terrain_view_clip(c, cx, cy, cz, o.bc)) return false; // if not occluded by the full tile, then won't be occluded by a sub-cube of it
+	if (terrain_view_all_zeros(o.sub[s])) return false;          // invalid cube, skip
+	return terrain_view_top_all(c, b, o.sub[s]);
+}
+// the loop of :2873-2905 for tile t: true = occluded
+TERRA_HD bool terrain_view_occluded(terrain_view_consts_t const &c, terrain_view_geom_t const &g, terra_tile_stats const &st, terrain_view_occluder_t const *occ, uint32_t nocc,
+	int32_t t)
+{
+	for (uint32_t q = 0; q < 16; ++q) {
+		float b[3][2];
+		terrain_view_sub_box(g, st, q, b);
+		float const cx = 0.5f*(b[0][0] + b[0][1]), cy = 0.5f*(b[1][0] + b[1][1]), cz = 0.5f*(b[2][0] + b[2][1]); // get_cube_center()
+		bool hidden = false;
+		for (uint32_t j = 0; j < nocc && !hidden; ++j) {
+			terrain_view_occluder_t const &o = occ[j];
+			if (o.tile == t) continue;                      // no self-occlusion
+			if (!terrain_view_top_any(c, g.bc, o.bc)) continue; // not in occluder_ixs
+			for (uint32_t s = 0; s < 16 && !hidden; ++s) {hidden = terrain_view_column_hides(c, o, s, b, cx, cy, cz);}
+		}
+		if (!hidden) return false;
+	}
+	return true;
+}
+// std::pair<float, tile_t *>'s operator< with the batch index in the pointer's place
+TERRA_HD bool terrain_view_before(float da, uint32_t ia, float db, uint32_t ib) {return da < db || (!(db < da) && ia < ib);}
+
+TERRA_HD bool terrain_view_args_finite(terrain_view_args_pod_t const &a) {return isfinite(a.behind_sphere_mult) && isfinite(a.occluder_zmin);}
+
+} // namespace terra

@@ -148,6 +148,22 @@ def grass_view_aux_fields(aux):
     return aux & 0xFFFF, (aux >> 16) & 7, aux >> 19
 
 
+class TerrainViewArgs(C.Structure):  # terra_terrain_view_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("occluder_zmin", C.c_float), ("water_enabled", C.c_int32), ("check_occlusion", C.c_int32), ("reflection_pass", C.c_int32)]
+
+
+def make_terrain_view_args(behind_sphere_mult=1.0, occluder_zmin=0.0, water_enabled=1, check_occlusion=1, reflection_pass=0):
+    """terra_terrain_view_args: behind_sphere_mult from Terra.view_behind_sphere_mult or camera_pdu, occluder_zmin the engine's zmin"""
+    return TerrainViewArgs(behind_sphere_mult, occluder_zmin, int(water_enabled), int(check_occlusion), int(reflection_pass))
+
+
+TERRAIN_VIEW_LODS = 5        # NUM_LODS
+TERRAIN_VIEW_NO_CRACK = 255  # the crack byte where there is no present neighbour or the tile is not drawn
+TVIEW_ABSENT, TVIEW_TOO_FAR, TVIEW_NOT_VISIBLE, TVIEW_OCCLUDED_BEFORE, TVIEW_OCCLUDED, TVIEW_DRAWN = range(6)  # the low bits of the status byte
+TVIEW_STATUS_MASK, TVIEW_WAS_OCCLUDER = 7, 0x80
+TVIEW_FLAG_ABSENT, TVIEW_FLAG_NO_OCCLUDER, TVIEW_FLAG_SHADOW_MAPS = 1, 2, 4  # the per-tile flag byte of tiles_terrain_view
+
+
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
@@ -345,6 +361,9 @@ _PROTOS = {
     "terra_get_grass_view_params": (_i32, [_vp, _vp]),
     "terra_tiles_grass_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_grass_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "terra_view_behind_sphere_mult": (_i32, [C.c_float, C.c_float, _vp]),
+    "terra_tiles_terrain_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_terrain_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -975,6 +994,28 @@ class Terra:
                                                  None if ax is None else ax.ctypes.data, gc.ctypes.data, counts.ctypes.data, None if ps is None else ps.ctypes.data))
         return insts, ax, gc, counts, ps
 
+    def view_behind_sphere_mult(self, angle, aspect):
+        """pos_dir_up::behind_sphere_mult (terra_view_behind_sphere_mult; no context is involved) -> float"""
+        out = C.c_float()
+        self._ck(self.lib.terra_view_behind_sphere_mult(angle, aspect, C.byref(out)))
+        return out.value
+
+    def tiles_terrain_view(self, tile_xy, stats, view, args, min_normal_z=None, trmax=None, tile_zmax=None, flags=None, occl_state=None, dxoff=0, dyoff=0):
+        """the head of tile_draw_t::draw for every tile.  stats TileStats * n; min_normal_z / trmax / tile_zmax [n] float32, flags / occl_state [n] bytes, all optional.
+        -> (status uint8 [n], dist float32 [n], lod uint8 [n], crack uint8 [n, 4], draw_order uint32 [counts[0]], occluded uint32 [counts[1]], counts uint32 [2],
+        occl_state uint8 [n] after the call or None)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        opt = lambda a, dt: None if a is None else np.array(a, dt).reshape(n)  # noqa: E731  (copies: occl_state is written)
+        mn, tr, tz, fl, os_ = opt(min_normal_z, np.float32), opt(trmax, np.float32), opt(tile_zmax, np.float32), opt(flags, np.uint8), opt(occl_state, np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        status, dist, lod, crack = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros((n, 4), np.uint8)
+        order, occluded, counts = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(2, np.uint32)
+        self._ck(self.lib.terra_tiles_terrain_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, C.byref(view), C.byref(args), C.addressof(stats) if n else None, ptr(mn), ptr(tr),
+                                                   ptr(tz), ptr(fl), ptr(os_), status.ctypes.data, dist.ctypes.data, lod.ctypes.data, crack.ctypes.data, order.ctypes.data,
+                                                   occluded.ctypes.data, counts.ctypes.data, None))
+        return status, dist, lod, crack, order[:counts[0]], occluded[:counts[1]], counts, os_
+
     def set_tree_size_params(self, tsp):
         self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
 
@@ -1246,6 +1287,14 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_grass_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, zvals_ptr, stats_ptr, grass_blocks_ptr, skip_ptr, C.byref(view), capacity,
                                                      insts_ptr, aux_ptr, group_counts_ptr, counts_ptr, pass_ptr))
+
+    def tiles_terrain_view_dev(self, tile_xy, view, args, stats_ptr, status_ptr, dist_ptr, lod_ptr, crack_ptr, draw_order_ptr, occluded_ptr, counts_ptr, min_normal_z_ptr=None,
+                               trmax_ptr=None, tile_zmax_ptr=None, flags_ptr=None, occl_state_ptr=None, not_drawn_ptr=None, dxoff=0, dyoff=0):
+        """the terrain draw list of a device-resident batch: status_ptr / lod_ptr [n] bytes, dist_ptr [n] floats, crack_ptr [n][4] bytes, draw_order_ptr / occluded_ptr [n]
+        uint32, counts_ptr [2] uint32; not_drawn_ptr [n] bytes or None (the grass view's skip bytes); the optional per-tile arrays as in tiles_terrain_view.  view and args are host structs.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_terrain_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, min_normal_z_ptr, trmax_ptr,
+                                                       tile_zmax_ptr, flags_ptr, occl_state_ptr, status_ptr, dist_ptr, lod_ptr, crack_ptr, draw_order_ptr, occluded_ptr, counts_ptr, not_drawn_ptr))
 
     def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
                                   decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,

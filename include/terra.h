@@ -837,6 +837,63 @@ int  terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
                             const terra_grass_block *h_grass_blocks, const uint8_t *h_skip, const terra_view *view, uint32_t capacity, float *h_insts, uint32_t *h_aux,
                             uint32_t *h_group_counts, uint32_t *h_counts, uint8_t *h_pass);
 
+/* ---- the terrain draw list of a tile batch for a camera (every supported tile size S): the head of tile_draw_t::draw (src/tiled_mesh.cpp:2844-2915) up to and
+ * including its sort, tile_t::get_lod_level (:1910-1932) and the crack look-ups of tile_t::draw (:2059-2074) -- the per-frame decision about the tiles themselves:
+ * which are drawn, in what order, at which mesh LOD, with which crack strips towards each neighbour, bit for bit.  Its status is also what an engine turns into the
+ * skip bytes of terra_tiles_grass_view.  The tile size enters only through `size` (:1926), the boxes and radius.
+ * terra_terrain_view_args: a host struct read at the call, like the brushes.  behind_sphere_mult: pos_dir_up's member that terra_view lacks;
+ * terra_view_behind_sphere_mult restates src/visibility.cpp:83 with the C library's tanf and the statement's own float / double mix (angle and aspect as for
+ * terra_make_view; TERRA_ERR_ARG for a NULL out).  water_enabled: is_water_enabled(); water_plane_z is the scene's.  occluder_zmin: the global zmin that
+ * occluder_cubes_t reads (:2840) -- an engine passes its zmin (terra_get_state's zmin for a generated scene).  check_occlusion: the condition of :2857,
+ * (display_mode & 0x08) && (display_mode & 0x01) && check_tt_mesh_occlusion.  reflection_pass: 0, 2 or 3; pass 1 needs can_have_reflection (:2869), which stays
+ * with the engine, and is refused.
+ * Inputs.  tile_xy is on the host; a tile may appear once (the neighbour look-up is the [n][9] table of terra_tiles_tree_ao_shadows).  dxoff / dyoff = xoff - xoff2 /
+ * yoff - yoff2 as for the grass view.  Per-tile arrays: stats [n] (sub_zmin, sub_zmax, mzmin, mzmax and radius are read); min_normal_z [n] (optional; NULL = 0,
+ * "normals not yet calculated"); trmax [n] (optional; NULL = 0; terra_tiles_tree_ao_shadows writes it); tile_zmax [n] (optional; the engine's get_tile_zmax(),
+ * src/tiled_mesh.h:207; NULL = mzmax); flags [n] bytes (optional): bit 0 = the tile is absent for this frame -- not drawn, no occluder, no neighbour: where an
+ * engine puts its building-occluder and city filters --, bit 1 = has_tunnel || has_city (never an occluder), bit 2 = shadow_maps_allocated() (the dist /= 2 of
+ * :1916); occl_state [n] bytes (optional, in and out): last_occluded as of this frame, 0 = nothing recorded this frame, 1 = was_last_occluded(), 2 =
+ * was_last_unoccluded(); the call writes 1 or 2 wherever the reference calls set_last_occluded (:2906).
+ * Per tile that is present: get_center(), get_rel_dist_to_camera() (xy), get_bcube() (trmax, tile_zmax + BCUBE_ZTOLER, the water plane), is_visible()
+ * (sphere_and_cube_visible_test with get_bsphere_radius_inc_water()), use_as_occluder() (:3801) under check_occlusion, the filters of :2867-2868, and
+ * get_lod_level(reflection_pass) -- for every present tile, since neighbours' LODs feed the crack index.  A candidate whose occl_state is not 2 runs, when the batch
+ * has any occluder, the test of :2872-2908: the occluders' boxes are get_mesh_bcube() and the 16 get_mesh_sub_bcube columns, each zeroed where cube_visible fails and
+ * else turned into the column from occluder_zmin up to sub_zmin; check_line_clip is get_line_clip (src/Math3d.cpp:1037-1052).  The loop's early exits only shortcut
+ * booleans, so the result does not depend on the order of the occluders.
+ * Outputs.  status [n] bytes, low bits: 0 absent, 1 beyond DRAW_DIST_TILES, 2 not visible, 3 occluded earlier this frame (occl_state was 1), 4 occluded now, 5 drawn;
+ * bit 7 is set where the tile served as an occluder.  dist [n] floats, get_rel_dist_to_camera() (0 for an absent tile).  lod [n] bytes (0 for an absent tile).
+ * crack [n][4] bytes indexed 2*dim + dir: crack_ibuf_t::get_index(dim, dir, lod, adj_lod) (:2020-2023), or 255 where there is no present neighbour in the batch or
+ * the tile is not drawn.  draw_order [n] words: its first counts[0] entries are the batch indices of to_draw after the sort of :2915, front to back.  occluded [n]
+ * words: its first counts[1] entries are occluded_tiles, in batch order.  counts [2].  Entries past the counts are not written.  not_drawn [n] bytes (optional): 1
+ * where the status is not 5, else 0 -- the skip bytes of terra_tiles_grass_view, so that a frame's two view calls chain on the device.
+ * One deviation: the reference sorts pair<float, tile_t *>, so equal distances fall back on pointer values; here equal distances order by batch index (a camera
+ * over a tile centre makes such ties common).
+ * With the engine stay the shaders, the binds, inside_city == 2, the texture-ready test, the building occluders (:2855, :2870), can_have_reflection and the water
+ * caps.
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or of the args; reflection_pass 1, negative or above 3; an unsupported S; a NULL required
+ * pointer (view, args; tile_xy, stats and every output when n > 0); a misaligned pointer (4 bytes: stats, min_normal_z, trmax, tile_zmax, dist, draw_order,
+ * occluded, counts); a tile that appears twice.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.  The device form only
+ * enqueues; tile_xy is a host array in both forms.  Scratch comes from the context's arena. */
+typedef struct terra_terrain_view_args {
+	float behind_sphere_mult;  /* pos_dir_up::behind_sphere_mult */
+	float occluder_zmin;       /* the global zmin */
+	int32_t water_enabled;     /* is_water_enabled() */
+	int32_t check_occlusion;   /* (display_mode & 0x08) && (display_mode & 0x01) && check_tt_mesh_occlusion */
+	int32_t reflection_pass;   /* 0, 2 or 3 */
+} terra_terrain_view_args;
+enum {TERRA_TVIEW_ABSENT = 0, TERRA_TVIEW_TOO_FAR = 1, TERRA_TVIEW_NOT_VISIBLE = 2, TERRA_TVIEW_OCCLUDED_BEFORE = 3, TERRA_TVIEW_OCCLUDED = 4, TERRA_TVIEW_DRAWN = 5,
+      TERRA_TVIEW_STATUS_MASK = 7, TERRA_TVIEW_WAS_OCCLUDER = 0x80};
+enum {TERRA_TVIEW_FLAG_ABSENT = 1, TERRA_TVIEW_FLAG_NO_OCCLUDER = 2, TERRA_TVIEW_FLAG_SHADOW_MAPS = 4};
+int  terra_view_behind_sphere_mult(float angle, float aspect, float *out);
+int  terra_tiles_terrain_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_terrain_view_args *args,
+                                  const terra_tile_stats *d_stats, const float *d_min_normal_z, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags,
+                                  uint8_t *d_occl_state, uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded,
+                                  uint32_t *d_counts, uint8_t *d_not_drawn);
+int  terra_tiles_terrain_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_terrain_view_args *args,
+                              const terra_tile_stats *h_stats, const float *h_min_normal_z, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags,
+                              uint8_t *h_occl_state, uint8_t *h_status, float *h_dist, uint8_t *h_lod, uint8_t *h_crack, uint32_t *h_draw_order, uint32_t *h_occluded,
+                              uint32_t *h_counts, uint8_t *h_not_drawn);
+
 /* ---- tree AO shadows of a tile batch from the placement records (every supported tile size S): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828), the step
  * between the two placements above and terra_tiles_shadow_texture / terra_tiles_tree_weights.  One call goes from the records as they lie in device memory to the
  * tree maps of the batch, bit for bit; with it zvals -> stats -> both placements -> tree map -> shadow texture / tree weights is one stream of launches.

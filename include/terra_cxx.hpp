@@ -335,6 +335,25 @@ inline void tile_draw_grass_lists(tile_batch_dev_t const &b, terra_grass_block c
 	check(terra_tiles_grass_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, b.d_zvals, b.d_stats, d_grass_blocks, d_not_drawn, &camera_pdu, capacity, d_insts, d_aux,
 		d_group_counts, d_counts, d_pass), "tile_t::draw_grass");
 }
+// ---- the terrain draw list of a batch for the camera: the head of tile_draw_t::draw (src/tiled_mesh.cpp:2844-2915) up to its sort, get_lod_level for every present
+// tile and the crack indices of tile_t::draw (:2059-2074).  The per-tile state that the library does not hold comes in as arrays (any of them may be null):
+// d_min_normal_z (tiles_create_zvals' output), d_trmax (tiles_apply_tree_ao_shadows' output), d_tile_zmax (get_tile_zmax()), d_flags (TERRA_TVIEW_FLAG_*),
+// d_last_occluded (in and out: 0 nothing recorded this frame, 1 was_last_occluded(), 2 was_last_unoccluded()).  d_status[t]: TERRA_TVIEW_* with bit 7 on the
+// occluders; d_draw_order's first d_counts[0] entries are to_draw after its sort, d_occluded's first d_counts[1] entries occluded_tiles; d_crack[t][2*dim + dir] is
+// crack_ibuf.get_index(dim, dir, lod, adj_lod) or 255; d_not_drawn (or null) is what tile_draw_grass_lists takes.  Equal distances order by batch index
+struct tile_draw_state_dev_t {
+	float const *d_min_normal_z, *d_trmax, *d_tile_zmax; unsigned char const *d_flags; unsigned char *d_last_occluded;
+};
+inline terra_terrain_view_args terrain_view_args_of(float behind_sphere_mult, float zmin, bool water_enabled, bool check_occlusion, int reflection_pass) {
+	terra_terrain_view_args const a = {behind_sphere_mult, zmin, water_enabled ? 1 : 0, check_occlusion ? 1 : 0, reflection_pass};
+	return a;
+}
+inline void tile_draw_lists(tile_batch_dev_t const &b, terra_view const &camera_pdu, terra_terrain_view_args const &args, tile_draw_state_dev_t const &st, unsigned char *d_status,
+	float *d_dist, unsigned char *d_lod, unsigned char *d_crack, unsigned *d_draw_order, unsigned *d_occluded, unsigned *d_counts, unsigned char *d_not_drawn = nullptr)
+{
+	check(terra_tiles_terrain_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &args, b.d_stats, st.d_min_normal_z, st.d_trmax, st.d_tile_zmax, st.d_flags,
+		st.d_last_occluded, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn), "tile_draw_t::draw");
+}
 // tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:820-828) for every tile of the batch in batch order, from the records tiles_gen_trees / tiles_gen_decid_trees left
 // on the device: small_tree::get_radius / get_ao_radius and tree::get_ao_radius per record, apply_ao_shadows_for_trees' own loop, pulls and pushes, add_tree_ao_shadow's
 // texel loop.  xoff2 / yoff2: what the placements ran with (ptree_off / dtree_off).  d_sphere_radius [n][decid_capacity] (tdata().sphere_radius per record) or

@@ -8,7 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
 MUST_NOT_SPILL = [("speculative_erosion", "wave_scratch_t"),  # k_waves<trace lambda>: the only speculative_erosion kernel that takes the LDS scratch
                   ("k_sine_grid", "Lb0ELb0E"), ("k_noise_grid", ""), ("k_tile_erosion", ""),
-                  ("k_tree_place", ""), ("k_decid_place", ""), ("k_scenery_place", "")]  # their comments promise "no scratch"
+                  ("k_tree_place", ""), ("k_decid_place", ""), ("k_scenery_place", ""),  # their comments promise "no scratch"
+                  ("k_terrain_view_tiles", ""), ("k_terrain_view_occluders", ""), ("k_terrain_view_occlusion", ""), ("k_terrain_view_lists", ""), ("k_terrain_view_rank", "")]
 
 
 def kernels():
@@ -21,16 +22,16 @@ def kernels():
     res = []
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S):
         g = lambda k: int(re.search(k + r" (\S+)", m.group(2)).group(1))
-        res.append((m.group(1), g(".amdhsa_next_free_vgpr"), g(".amdhsa_group_segment_fixed_size"), g(".amdhsa_private_segment_fixed_size")))
+        res.append((m.group(1), g(".amdhsa_next_free_vgpr"), g(".amdhsa_next_free_sgpr"), g(".amdhsa_group_segment_fixed_size"), g(".amdhsa_private_segment_fixed_size")))
     return res
 
 
 def main():
     bad = []
-    for name, vgpr, lds, scratch in kernels():
+    for name, vgpr, sgpr, lds, scratch in kernels():
         hot = any(a in name and b in name for a, b in MUST_NOT_SPILL)
         if hot or "--all" in sys.argv:
-            print(f"{name[:40]}..{name[-48:]}  vgpr {vgpr}  lds {lds}  scratch {scratch}{'  <-- hot' if hot else ''}")
+            print(f"{name[:40]}..{name[-48:]}  vgpr {vgpr}  sgpr {sgpr}  lds {lds}  scratch {scratch}{'  <-- hot' if hot else ''}")
         if hot and scratch:
             bad.append(name)
     if "--check" in sys.argv and bad:
