@@ -508,10 +508,11 @@ template<bool PERLIN> TERRA_HD nv2 voxel_noise_pair(unsigned x, unsigned y, unsi
 
 // the device mirror of a host vector the engine owns: grown on demand, uploaded when the vector changed since (its setter clears `valid`), not per call
 template<class T> struct dev_mirror_t {
-	T *d = nullptr; size_t cap = 0; bool valid = false;
+	dev_buf_t buf; bool valid = false;
 	template<class BE> T const *get(BE &be, std::vector<T> const &h) {
 		size_t const n = h.size();
-		if (n > cap) {if (d) {be.sync(); be.free(d); d = nullptr; cap = 0;} d = (T *)be.alloc(n*sizeof(T)); cap = n; valid = false;}
+		if (n*sizeof(T) > buf.bytes) {valid = false;}
+		T *const d = (T *)buf.grow(be, n*sizeof(T));
 		if (!valid && n) {be.h2d(d, h.data(), n*sizeof(T));}
 		valid = true;
 		return d;
@@ -551,36 +552,30 @@ template<class BE> struct terra_engine {
 	terra_erosion_report report{};
 
 	// grow-only device scratch
-	struct scratch_t {void *p = nullptr; size_t bytes = 0;};
-	scratch_t s_xt, s_yt, s_smx, s_smy, s_misc, s_border, s_spec, s_spec_blocks, s_tiles, s_ao, s_edit, s_shadow, s_shadow_map, s_shadow_gather, s_vox, s_sk, s_mm, s_hostgrid;
+	dev_buf_t s_xt, s_yt, s_smx, s_smy, s_misc, s_border, s_spec, s_spec_blocks, s_tiles, s_ao, s_edit, s_shadow, s_shadow_map, s_shadow_gather, s_vox, s_sk, s_mm, s_hostgrid;
 	template<class F> void for_each_scratch(F f) { // the one list of them: what release_scratch() and the destructor walk
-		for (scratch_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {f(*s);}
+		for (dev_buf_t *s : {&s_xt, &s_yt, &s_smx, &s_smy, &s_misc, &s_border, &s_spec, &s_spec_blocks, &s_tiles, &s_ao, &s_edit, &s_shadow, &s_shadow_map, &s_shadow_gather, &s_vox, &s_sk, &s_mm, &s_hostgrid}) {f(*s);}
 	}
 	bool tiled_mesh_ao = false; // enable_tiled_mesh_ao (src/3DWorld.cpp:73,1778)
 	uint8_t const *hmap_pix = nullptr; int hmap_w = 0, hmap_h = 0, hmap_nc = 0; // terrain_hmap_manager's image (device memory, owned by the caller)
 	float mesh_file_scale = 1.0f, mesh_file_tz = 0.0f;                          // src/mesh_gen.cpp:41, set by set_mesh_height_scales_for_zval_range
 	uint32_t *spec_blocks_clean = nullptr; size_t spec_blocks_n = 0; // s_spec_blocks is known to be all-NIL for this pointer / block count
-	template<class T> T *scratch(scratch_t &s, size_t count) {
-		size_t const bytes = std::max<size_t>(count*sizeof(T), 256);
-		if (bytes > s.bytes) {if (s.p) {be.sync(); be.free(s.p); s.p = nullptr; s.bytes = 0;} s.p = be.alloc(bytes); s.bytes = bytes;} // (a failed allocation leaves an empty buffer, not a stale pointer)
-		return (T *)s.p;
-	}
+	template<class T> T *scratch(dev_buf_t &s, size_t count) {return (T *)s.grow(be, std::max<size_t>(count*sizeof(T), 256));}
 	float *host_grid_scratch(size_t bytes) {return (float *)scratch<uint8_t>(s_hostgrid, bytes);} // device copy of a caller's host array (the host-pointer entry points)
 	// every grow-only device buffer of the context back to the allocator (they grow again on demand): the erosion ring of a 16384^2 map alone is ~8.5 GiB
 	void release_scratch() {
 		be.sync();
-		for_each_scratch([&](scratch_t &s) {if (s.p) {be.free(s.p); s.p = nullptr; s.bytes = 0;}});
+		for_each_scratch([&](dev_buf_t &s) {s.drop(be);});
 		spec_blocks_clean = nullptr; spec_blocks_n = 0;
 		be.release_scratch();
 	}
 	~terra_engine() {
-		for_each_scratch([&](scratch_t &s) {if (s.p) be.free(s.p);});
+		for_each_scratch([&](dev_buf_t &s) {s.drop(be);});
 		if (d_sin_table) be.free(d_sin_table);
 		if (d_noise_lut) be.free(d_noise_lut);
 		if (d_noise3_lut) be.free(d_noise3_lut);
 		if (d_sinTable) be.free(d_sinTable);
-		if (hist_mirror.d) be.free(hist_mirror.d);
-		if (tree_insts_mirror.d) be.free(tree_insts_mirror.d);
+		hist_mirror.buf.drop(be); tree_insts_mirror.buf.drop(be);
 	}
 
 	sin_lut_t lut() const {return sin_lut_t{d_sin_table, sscale};}
@@ -1643,7 +1638,8 @@ template<class BE> struct terra_engine {
 		// tables of all distinct tile columns / rows side by side, k-major like the big-grid tables: xt[k][u*tw + c], yt[k][u*tw + c].
 		// The batch is then ONE "virtual" (nux*tw) x (nuy*tw) sine grid whose cells are exactly the requested tiles' cells.
 		int const md_ = force_sine ? (int)MGEN_SINE : mode;
-		bool const banded = band && xy_scale != 0.0f && d_out && be.tile_band_ok(n, nux, nuy, band->twx, unique_tiles, md_ == MGEN_SINE && sine_plain_only(force_sine ? 0 : shape, imax(start_eval_sin, min_start_sin)), md_);
+		bool banded = false; // (a backend without kernels evaluates whole squares)
+		if constexpr (BE::has_kernels) {banded = band && xy_scale != 0.0f && d_out && be.tile_band_ok(n, nux, nuy, band->twx, unique_tiles, md_ == MGEN_SINE && sine_plain_only(force_sine ? 0 : shape, imax(start_eval_sin, min_start_sin)), md_);}
 		if (band_used) {*band_used = banded;}
 		tile_band_t const bd = banded ? *band : tile_band_t{zv, zv, zv, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
 		uint32_t const zvx = bd.twx, zvy = bd.twy; // cells per tile in the virtual grid
@@ -1892,8 +1888,9 @@ template<class BE> struct terra_engine {
 			}
 		}
 		uint32_t const npaths = 4*zv;
-		if (be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync)) {} // one launch; tiles start as their two upstream tiles publish
-		else for (uint32_t first = 0; first < n;) { // "shadows.levels" / cross-check kernels / the emulator / other tile sizes: one launch per dependency level
+		bool flow = false; // one launch; tiles start as their two upstream tiles publish
+		if constexpr (BE::has_kernels) {flow = be.tile_shadows_flow(c, n, nslots, d_order, d_adj, d_zvals, d_out, d_smask, npaths, d_sync);}
+		for (uint32_t first = 0; !flow && first < n;) { // "shadows.levels" / cross-check kernels / the emulator / other tile sizes: one launch per dependency level
 			uint32_t last = first;
 			while (last < n && level[order[last]] == level[order[first]]) ++last;
 			be.tile_shadows(c, last - first, d_order + first, d_adj, nslots, d_zvals, d_out, d_smask, npaths);
@@ -2118,9 +2115,11 @@ template<class BE> struct terra_engine {
 		be.fill8(d_any, 0, n);
 		uint32_t *d_w32 = (uint32_t *)d_weights; // n*129*129*4 bytes from a device allocation: 4-byte aligned
 		if (((uintptr_t)d_weights & 3u) != 0) throw std::invalid_argument("tiles_create_weights: d_weights must be 4-byte aligned");
-		if (!opt.weights_simple && be.tile_weights(c, d_refs, n, d_zvals, d_rand, d_params, d_w32, d_blocks, d_any)) { // k_tile_weights: texels + grass blocks in one launch
-			if (d_has_grass) {be.launch(n, [=] TERRA_LAMBDA (size_t i) {d_has_grass[i] = d_any[i];});}
-			return;
+		if constexpr (BE::has_kernels) {
+			if (!opt.weights_simple && be.tile_weights(c, d_refs, n, d_zvals, d_rand, d_params, d_w32, d_blocks, d_any)) { // k_tile_weights: texels + grass blocks in one launch
+				if (d_has_grass) {be.launch(n, [=] TERRA_LAMBDA (size_t i) {d_has_grass[i] = d_any[i];});}
+				return;
+			}
 		}
 		be.launch(ntex, [=] TERRA_LAMBDA (size_t i) { // the per-texel form ("weights.simple": cross-check; the emulator)
 			unsigned const t = (unsigned)(i / (ts*ts)), p = (unsigned)(i % (ts*ts)), y = p / ts, x = p % ts;
@@ -2169,7 +2168,7 @@ template<class BE> struct terra_engine {
 		tile_ref_pod_t const *d_refs = tile_fields_dev(tile_xy, n, WT_TEX, 0, nullptr, 0.0f);
 		if (live && !add) {tiles_terrain_params_dev(d_refs, n, d_params);} // the dirt scale of the remove path (:3917)
 		uint32_t *d_w32 = (uint32_t *)d_weights;
-		if (be.tile_edit_grass(g, c, d_refs, n, d_zvals, d_stats, d_distant, d_params, d_w32, d_blocks, d_flags, d_updated, d_ranges)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_edit_grass(g, c, d_refs, n, d_zvals, d_stats, d_distant, d_params, d_w32, d_blocks, d_flags, d_updated, d_ranges)) return;}
 		// the simple form: position tables, one logical thread per window texel, per grass block, per tile
 		uint32_t const wx = g.wx, wy = g.wy;
 		if (live) {
@@ -2254,7 +2253,7 @@ template<class BE> struct terra_engine {
 		c.S = (int)tile_size(); c.dxoff = dxoff; c.dyoff = dyoff;
 		tile_ref_pod_t const *d_refs = n ? tile_fields_dev(tile_xy, n, tile_size() + 2, 0, nullptr, 0.0f) : nullptr; // (only the tile references)
 		line_box_t *d_boxes = scratch<line_box_t>(s_ao, n);
-		if (be.tile_line_intersect(c, d_refs, n, d_zvals, d_stats, d_distant, d_boxes, d_lines, d_line_tile, nlines, d_hits)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_line_intersect(c, d_refs, n, d_zvals, d_stats, d_distant, d_boxes, d_lines, d_line_tile, nlines, d_hits)) return;}
 		// the simple form: one logical thread per line, the reference's loop over the tiles in batch order
 		size_t const zn = (size_t)(c.S + 2)*(c.S + 2);
 		be.launch(nlines, [=] TERRA_LAMBDA (size_t r) {
@@ -2303,7 +2302,7 @@ template<class BE> struct terra_engine {
 		tree_splat_in_t const *sp = d_splats ? d_splats + h_first[0] : nullptr;
 		float const dxv = DX_VAL, dyv = DY_VAL;
 		uint16_t *d_map = (uint16_t *)d_tree_map;
-		if (be.tile_tree_map(d_tiles, n, S, d_distant, sp, ns, d_par, dxv, dyv, reset, d_map, d_updated)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_tree_map(d_tiles, n, S, d_distant, sp, ns, d_par, dxv, dyv, reset, d_map, d_updated)) return;}
 		// the simple form: one logical thread per splat for its parameters, then one per (tile, texel row) that walks the tile's list, then one per tile
 		be.launch(ns, [=] TERRA_LAMBDA (size_t i) {
 			tree_tile_pod_t const &tt = d_tiles[tree_tile_of(d_tiles, n, (uint32_t)i)];
@@ -2429,8 +2428,10 @@ template<class BE> struct terra_engine {
 		tree_inst_pod_t const *d_insts = (has_pine && tp.instanced) ? tree_insts_dev() : nullptr;
 		be.fill32(d_trmax, 0u, n);
 		uint16_t *d_map = (uint16_t *)d_tree_map;
-		if (be.tile_tree_ao(c, n, d_insts, d_pine, d_pine_counts, d_decid, d_decid_counts, d_decid_radius, d_decid_radius_by_id, d_flags, d_fr, d_nbr, d_src, d_trmax, d_tiles,
-			d_par, d_list_counts, d_map, d_updated)) return;
+		if constexpr (BE::has_kernels) {
+			if (be.tile_tree_ao(c, n, d_insts, d_pine, d_pine_counts, d_decid, d_decid_counts, d_decid_radius, d_decid_radius_by_id, d_flags, d_fr, d_nbr, d_src, d_trmax, d_tiles,
+				d_par, d_list_counts, d_map, d_updated)) return;
+		}
 		// the simple form: one logical thread per tile for its sources and trmax, one per tile for its list, then the tree map's per-row form
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			float trmax = 0.0f, radius;
@@ -2553,8 +2554,11 @@ template<class BE> struct terra_engine {
 		be.fill32(d_box, 0xFFFFFFFFu, 8);
 		float const *d_by_rec = d_decid_radius;                                   // a present record's radius: the per-record form wins
 		float const *d_by_id = d_decid_radius ? nullptr : d_decid_radius_by_id;
-		bool const kernels = be.tile_edit_trees(c, n, d_fr, d_stats, d_insts, d_pine, d_pine_counts, d_decid, d_decid_counts, d_decid_radius, d_by_id, d_trmax, d_idx, d_box, d_status,
-			d_skip, d_gen_flags, d_place_skip);
+		bool kernels = false;
+		if constexpr (BE::has_kernels) {
+			kernels = be.tile_edit_trees(c, n, d_fr, d_stats, d_insts, d_pine, d_pine_counts, d_decid, d_decid_counts, d_decid_radius, d_by_id, d_trmax, d_idx, d_box, d_status,
+				d_skip, d_gen_flags, d_place_skip);
+		}
 		if (!kernels) { // the simple form: one logical thread per tile runs the reference's loops, remove_element and all
 			be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 				terra_tile_stats const &st = d_stats[t];
@@ -2598,9 +2602,12 @@ template<class BE> struct terra_engine {
 		if (add_decid) {tiles_place_decid_trees_dev(tile_xy, n, xoff2, yoff2, d_place_skip + n, d_stats, d_zvals, brush, decid_cap, d_new_decid, d_new_dc);}
 		if (add_pine || add_decid) {
 			tree_place_pod_t const *np_ = add_pine ? d_new_pine : nullptr; decid_place_pod_t const *nd_ = add_decid ? d_new_decid : nullptr;
-			if (!(kernels && be.tile_edit_trees_append(c, n, d_gen_flags, d_insts, np_, d_new_pc, d_pine, d_pine_counts, nd_, d_new_dc, d_decid, d_decid_counts, d_decid_radius,
-				d_decid_radius_by_id, d_trmax, d_box, d_status)))
-			{
+			bool appended = false;
+			if constexpr (BE::has_kernels) {
+				appended = kernels && be.tile_edit_trees_append(c, n, d_gen_flags, d_insts, np_, d_new_pc, d_pine, d_pine_counts, nd_, d_new_dc, d_decid, d_decid_counts, d_decid_radius,
+					d_decid_radius_by_id, d_trmax, d_box, d_status);
+			}
+			if (!appended) {
 				be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 					uint32_t state = d_status[t];
 					if (!(state & TREE_EDIT_HIT)) return;
@@ -2636,7 +2643,7 @@ template<class BE> struct terra_engine {
 				});
 			}
 		}
-		if (kernels && be.tile_edit_trees_finish(c, n, d_fr, d_stats, d_box, d_status, d_changed, d_update_bcube)) return;
+		if constexpr (BE::has_kernels) {if (kernels && be.tile_edit_trees_finish(c, n, d_fr, d_stats, d_box, d_status, d_changed, d_update_bcube)) return;}
 		uint32_t const *d_box_r = d_box;
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			terra_tile_stats const &st = d_stats[t];
@@ -2660,7 +2667,7 @@ template<class BE> struct terra_engine {
 		uint8_t const *sun = (c.mesh_shadows && c.has_sun) ? d_sun : nullptr, *moon = (c.mesh_shadows && c.has_moon) ? d_moon : nullptr;
 		uint16_t const *tree = (uint16_t const *)d_tree_map;
 		uint32_t *out = (uint32_t *)d_shadow;
-		if (be.tile_shadow_texture(c, n, S, sun, moon, d_ao, tree, out)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_shadow_texture(c, n, S, sun, moon, d_ao, tree, out)) return;}
 		be.launch((size_t)n*W*W, [=] TERRA_LAMBDA (size_t i) {
 			size_t const t = i / ((size_t)W*W); uint32_t const p = (uint32_t)(i % ((size_t)W*W)), y = p / W, x = p % W;
 			size_t const iz = t*Z*Z + (size_t)y*Z + x;
@@ -2678,7 +2685,7 @@ template<class BE> struct terra_engine {
 		size_t const ntex = (size_t)n*WT_TEX*WT_TEX;
 		if (!d_tree_map) {if (d_weights != d_mesh_weights) {be.d2d(d_weights, d_mesh_weights, ntex*4);} return;}
 		uint32_t const *in = (uint32_t const *)d_mesh_weights; uint32_t *out = (uint32_t *)d_weights;
-		if (be.tile_tree_weights(ntex, in, d_tree_map, out)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_tree_weights(ntex, in, d_tree_map, out)) return;}
 		be.launch(ntex, [=] TERRA_LAMBDA (size_t i) {out[i] = tree_weights_texel(in[i], d_tree_map[2*i]);});
 	}
 
@@ -2768,7 +2775,7 @@ template<class BE> struct terra_engine {
 		auto const sg = stage_placement(tile_xy, n, c, c, sums, !brush);
 		tree_place_consts_t const cc = c;
 		tile_ref_pod_t const *d_refs = sg.d_refs; float *d_dens = sg.d_dens;
-		if (be.tile_place_trees(sg.d_consts, d_refs, n, sg.d_dens, d_skip, d_stats, capacity, d_trees, d_counts)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_place_trees(sg.d_consts, d_refs, n, sg.d_dens, d_skip, d_stats, capacity, d_trees, d_counts)) return;}
 		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			tile_ref_pod_t const r = d_refs[t];
@@ -2845,7 +2852,7 @@ template<class BE> struct terra_engine {
 		auto const sg = stage_placement(tile_xy, n, c, c.b, std::vector<float>(), !brush);
 		decid_place_consts_t const cc = c;
 		tile_ref_pod_t const *d_refs = sg.d_refs; float *d_dens = sg.d_dens;
-		if (be.tile_place_decid_trees(sg.d_consts, d_refs, n, sg.d_dens, d_skip, d_stats, d_zvals, capacity, d_trees, d_counts)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_place_decid_trees(sg.d_consts, d_refs, n, sg.d_dens, d_skip, d_stats, d_zvals, capacity, d_trees, d_counts)) return;}
 		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
 		size_t const zsz = (size_t)(cc.b.S + 2)*(size_t)(cc.b.S + 2);
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
@@ -2904,7 +2911,7 @@ template<class BE> struct terra_engine {
 		auto const sg = stage_placement(tile_xy, n, c, c.b, std::vector<float>(), true);
 		scenery_place_consts_t const cc = c;
 		tile_ref_pod_t const *d_refs = sg.d_refs; float *d_dens = sg.d_dens;
-		if (be.tile_place_scenery(sg.d_consts, d_refs, n, sg.d_dens, d_skip, capacity, d_objs, d_counts, d_kind_counts)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_place_scenery(sg.d_consts, d_refs, n, sg.d_dens, d_skip, capacity, d_objs, d_counts, d_kind_counts)) return;}
 		// the simple form: one logical thread per tile runs the reference's loop, rows then columns
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			tile_ref_pod_t const r = d_refs[t];
@@ -2970,7 +2977,7 @@ template<class BE> struct terra_engine {
 		float *d_den = scratch<float>(s_ao, 2*(size_t)n*ncell), *d_col = d_den + (size_t)n*ncell;
 		tile_ref_pod_t const *d_refs = flower_density_fields(tile_xy, n, d_den, d_col);
 		flower_consts_t const c = flower_consts();
-		if (be.tile_place_flowers(c, d_refs, n, d_skip, d_weights, d_den, d_col, capacity, d_flowers, d_aux, d_counts)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_place_flowers(c, d_refs, n, d_skip, d_weights, d_den, d_col, capacity, d_flowers, d_aux, d_counts)) return;}
 		// the simple form: one logical thread per tile runs the reference's loop
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			tile_ref_pod_t const r = d_refs[t];
@@ -3007,7 +3014,7 @@ template<class BE> struct terra_engine {
 		lay.add(d_den, add ? (size_t)n*ncell : 0); lay.add(d_col, add ? (size_t)n*ncell : 0); lay.add(d_idx, (size_t)n*capacity); lay.add(d_kind, n);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
 		tile_ref_pod_t const *d_refs = add ? flower_density_fields(tile_xy, n, d_den, d_col) : tile_fields_dev(tile_xy, n, S, 0, nullptr, 0.0f);
-		if (be.tile_edit_flowers(c, d_refs, n, d_generated, d_updated, d_ranges, d_weights, d_den, d_col, capacity, d_flowers, d_aux, d_counts, d_status, d_idx, d_kind)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_edit_flowers(c, d_refs, n, d_generated, d_updated, d_ranges, d_weights, d_den, d_col, capacity, d_flowers, d_aux, d_counts, d_status, d_idx, d_kind)) return;}
 		// the simple form: one logical thread per tile, the removal as the literal remove_element loop, then the reference's cell loop behind the survivors
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			tile_ref_pod_t const r = d_refs[t];
@@ -3064,7 +3071,7 @@ template<class BE> struct terra_engine {
 		lay.add(d_keys, (size_t)n*nb); lay.add(d_offs, (size_t)n*nbins); lay.add(d_txy, (size_t)n*2);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
 		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
-		if (be.tile_grass_view(c, d_txy, n, d_zvals, d_stats, d_blocks, d_skip, capacity, d_insts, d_aux, d_group_counts, d_counts, d_pass, d_keys)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_grass_view(c, d_txy, n, d_zvals, d_stats, d_blocks, d_skip, capacity, d_insts, d_aux, d_group_counts, d_counts, d_pass, d_keys)) return;}
 		// the simple form: one logical thread per tile runs the reference's loops; its per-LOD, per-bix lists are the groups' counts, then their offsets, then a second
 		// walk in the same scan order that appends every kept block to its group
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
@@ -3138,7 +3145,7 @@ template<class BE> struct terra_engine {
 		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
 		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
 		int32_t const *d_nbr = d_nbr_w;
-		if (be.tile_terrain_view(c, in, d_txy, d_nbr, n, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_occ, d_nocc, d_test, d_keys, d_key_tile)) return;
+		if constexpr (BE::has_kernels) {if (be.tile_terrain_view(c, in, d_txy, d_nbr, n, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_occ, d_nocc, d_test, d_keys, d_key_tile)) return;}
 		// the simple form.  (1) a logical thread per tile: everything but the occlusion test, the cracks and the lists
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
 			terrain_view_tile_t const o = terrain_view_tile(c, in, d_txy, t);

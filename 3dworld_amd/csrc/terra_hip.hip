@@ -15,15 +15,13 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	int device = -1;
 	hipStream_t stream = nullptr, own_stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	terra::options_t const *opt = nullptr; // the engine's options (terra_set_option); the members below are copies taken by options_changed()
-	bool simple_kernels = false; // "kernels.simple": run the one-thread-per-cell cross-check kernels instead of the LDS-tiled ones
+	static constexpr bool has_kernels = true; // the driver tries the bool tile_*() hooks below before its own one-thread-per-tile forms
+	terra::options_t const *opt = nullptr; // the engine's options (terra_set_option), set by terra_engine() before init(): read where they are used, never copied
 	int num_cus = 256;
-	float *tile_pad = nullptr; size_t tile_pad_bytes = 0;
-	uint32_t *tile_order = nullptr; size_t tile_order_bytes = 0; // k_tile_erosion's land counts + launch order
-	float *vox_p = nullptr; size_t vox_p_bytes = 0;
-	bool vox_cols = true; // "voxels.cols": the lane-per-column voxel sine kernel (k_voxel_sines_cols) where it applies (nz a multiple of 4)
-	int sg_kc = 27; // "sg.kc": terms per LDS chunk of the heightmap's sine kernel (27: 3 chunks of <= 27 for 8 octaves, 29.7 KB per block; 45: 2 chunks, 48 KB)
-	unsigned sg_rowgroup = 4; // "sg.rowgroup": tile rows walked together by k_sine_grid (L2 reuse of table slices)
+	// the grow-only device buffers (terra_stage.hpp: dev_buf_t): tile erosion's padded copies, its land counts + launch order, k_tile_post's per-tile accumulators,
+	// tile_grid's (column, row) -> tile map, the voxel sine field's P array, the split tables of TERRA_GEN_FAST
+	terra::dev_buf_t tile_pad, tile_order, tile_acc, tile_map, vox_p, h3_tab;
+	template<class F> void for_each_buf(F f) {for (terra::dev_buf_t *b : {&tile_pad, &tile_order, &tile_acc, &tile_map, &vox_p, &h3_tab}) {f(*b);}} // the one list of them: what release_scratch() and the destructor walk
 
 	static int device_count() {int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n;}
 	void init(int dev) {
@@ -46,18 +44,11 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		if (!ao_tile_ok) {(void)hipGetLastError();}
 	}
 	void options_changed() { // (the engine has drained the stream)
-		if (!opt) return;
-		simple_kernels = opt->simple_kernels != 0; sg_kc = opt->sg_kc; sg_rowgroup = (unsigned)opt->sg_rowgroup; vox_cols = opt->voxels_cols != 0;
 		if (graphs_enabled != (opt->graphs != 0)) {for (graph_slot_t &g : graphs) {graph_drop(g);} graphs_enabled = opt->graphs != 0;}
 	}
 	~hip_backend_t() {
 		if (pin) (void)hipHostFree(pin);
-		if (h3_tab) (void)hipFree(h3_tab);
-		if (tile_pad) (void)hipFree(tile_pad);
-		if (tile_order) (void)hipFree(tile_order);
-		if (tile_acc) (void)hipFree(tile_acc);
-		if (tile_map) (void)hipFree(tile_map);
-		if (vox_p) (void)hipFree(vox_p);
+		for_each_buf([&](terra::dev_buf_t &b) {b.drop(*this);});
 		if (ev0) (void)hipEventDestroy(ev0);
 		if (ev1) (void)hipEventDestroy(ev1);
 		for (graph_slot_t &g : graphs) {graph_drop(g);}
@@ -66,10 +57,7 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		if (own_stream) (void)hipStreamDestroy(own_stream);
 	}
 	size_t mem_free() {use(); size_t f = 0, t = 0; if (hipMemGetInfo(&f, &t) != hipSuccess) {(void)hipGetLastError(); return ~(size_t)0 >> 1;} return f;}
-	void release_scratch() { // the backend's own grow-only buffers (the caller has drained the stream)
-		for (void **p : {(void **)&tile_pad, (void **)&tile_order, (void **)&tile_acc, (void **)&tile_map, (void **)&vox_p}) {if (*p) {(void)hipFree(*p); *p = nullptr;}}
-		tile_pad_bytes = tile_order_bytes = tile_acc_bytes = vox_p_bytes = 0; tile_map_count = 0;
-	}
+	void release_scratch() {for_each_buf([&](terra::dev_buf_t &b) {b.drop(*this);});} // the backend's own grow-only buffers (the caller has drained the stream)
 	void use() {TERRA_HIP_CHECK(hipSetDevice(device));}
 	void set_stream(void *s) {sync(); pin_off = 0; stream = s ? (hipStream_t)s : own_stream;} // cached graphs are stream-agnostic (the stream is given at launch)
 	void sync() {use(); TERRA_HIP_CHECK(hipStreamSynchronize(stream));}
@@ -223,42 +211,52 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		TERRA_HIP_CHECK(hipGraphLaunch(ex, stream));
 	}
 
+	// every kernel launch of this file: on the context's stream and checked at once, so a refused launch stops a pass before the launches that depend on it.
+	// No use(): a method calls it once at entry
+	template<class K, class... A> void run(K kernel, dim3 grid, dim3 block, size_t lds, A... args) {
+		hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+		TERRA_HIP_CHECK(hipGetLastError());
+	}
+	template<class F> static void with_noise_mode(int md, F f) { // f(the fBm mode as a compile-time constant): the kernels are templates over it
+		switch (md) {
+		case terra::MGEN_PERLIN:      f(std::integral_constant<int, terra::MGEN_PERLIN>()); break;
+		case terra::MGEN_DWARP_GPU:   f(std::integral_constant<int, terra::MGEN_DWARP_GPU>()); break;
+		case terra::MGEN_SIMPLEX_GPU: f(std::integral_constant<int, terra::MGEN_SIMPLEX_GPU>()); break;
+		default:                      f(std::integral_constant<int, terra::MGEN_SIMPLEX>()); break;
+		}
+	}
+
 	template<class F> void launch(size_t n, F f, int block = 256) {
 		if (n == 0) return;
 		use();
 		size_t const nblocks = (n + block - 1)/block;
 		if (nblocks > 0x7FFFFFFFull) throw std::invalid_argument("launch: grid too large");
-		hipLaunchKernelGGL(terra::k_generic<F>, dim3((unsigned)nblocks), dim3(block), 0, stream, n, f);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_generic<F>, dim3((unsigned)nblocks), dim3(block), 0, n, f);
 	}
 
 	template<class F> void launch_waves(size_t n, F f) {
 		if (n == 0) return;
 		use();
 		if (n > 0x7FFFFFFFull) throw std::invalid_argument("launch_waves: grid too large");
-		hipLaunchKernelGGL(terra::k_waves<F>, dim3((unsigned)n), dim3(64), 0, stream, f, 0u);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_waves<F>, dim3((unsigned)n), dim3(64), 0, f, 0u);
 	}
 
 	template<class F> void launch_waves_lean(size_t n, F f) { // one 64-lane workgroup per item with the lean droplet scratch (terra_kernels.hpp: k_waves_lean)
 		if (n == 0) return;
 		use();
 		if (n > 0x7FFFFFFFull) throw std::invalid_argument("launch_waves: grid too large");
-		hipLaunchKernelGGL(terra::k_waves_lean<F>, dim3((unsigned)n), dim3(64), 0, stream, f);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_waves_lean<F>, dim3((unsigned)n), dim3(64), 0, f);
 	}
 
 	template<class F> void launch_waves_nolds(size_t n, F f) { // one 64-lane workgroup per item, no LDS scratch (does not compete with LDS-heavy kernels for a CU)
 		if (n == 0) return;
 		use();
 		if (n > 0x7FFFFFFFull) throw std::invalid_argument("launch_waves: grid too large");
-		hipLaunchKernelGGL(terra::k_waves_nolds<F>, dim3((unsigned)n), dim3(64), 0, stream, f);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_waves_nolds<F>, dim3((unsigned)n), dim3(64), 0, f);
 	}
 
 	// TERRA_GEN_FAST (terra_fused.hpp: k_sine_grid_h3): split the f32 tables of J (k-major, rows padded to nxp / nyp) into scaled half-precision pairs and run the contraction on
 	// the half-precision matrix pipe.  amax_y / amax_x: the largest magnitude the row / column table can hold.  Returns false when the tables are too large for its 32-bit offsets.
-	void *h3_tab = nullptr; size_t h3_tab_bytes = 0;
 	static float h3_scale(float amax) {int e = 0; if (amax > 0.0f && amax < 3.0e38f) {(void)frexpf(amax, &e);} return ldexpf(1.0f, 14 - e);} // amax < 2^e: scaled magnitudes stay below 2^14
 	// vox_tab: (voxels) noise_gen_3d's [entry][nsines] sine table with the field's nx, ny -- the split tables are then made straight from it (J.xt / J.yt unused)
 	template<int KIND> bool sine_grid_h3(terra::sgf_job_t J, float amax_x, float amax_y, float const *vox_tab = nullptr, uint32_t vnx = 0, uint32_t vny = 0) {
@@ -266,69 +264,63 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		uint32_t const nchunks = (uint32_t)((3*nk + 15)/16);
 		if ((uint64_t)std::max(J.nxp, J.nyp)*32u*(nchunks + 1) >= 0xFFFFFFFFull) return false;
 		size_t const bx = (size_t)nchunks*J.nxp*32u, by = (size_t)nchunks*J.nyp*32u;
-		if (bx + by + 64 > h3_tab_bytes) {if (h3_tab) {sync(); (void)hipFree(h3_tab);} TERRA_HIP_CHECK(hipMalloc(&h3_tab, bx + by + 64)); h3_tab_bytes = bx + by + 64;}
 		float const sx = h3_scale(amax_x), sy = h3_scale(amax_y);
-		J.xh = h3_tab; J.yh = (char *)h3_tab + bx; J.nchunks = nchunks; J.unscale = 1.0f/(sx*sy);
+		J.xh = h3_tab.grow(*this, bx + by + 64); J.yh = (char const *)J.xh + bx; J.nchunks = nchunks; J.unscale = 1.0f/(sx*sy);
 		if (nchunks && vox_tab) {
-			hipLaunchKernelGGL((terra::k_split_voxel_table<false, terra::VOX_SINES>), dim3((J.nxp + 255)/256), dim3(256), 0, stream, vox_tab, vnx, vny, J.nx, J.nxp, sx, (terra::sgh_u4 *)J.xh);
-			hipLaunchKernelGGL((terra::k_split_voxel_table<true, terra::VOX_SINES>),  dim3((J.nyp + 255)/256), dim3(256), 0, stream, vox_tab, vnx, vny, J.nx, J.nyp, sy, (terra::sgh_u4 *)J.yh);
+			run(terra::k_split_voxel_table<false, terra::VOX_SINES>, dim3((J.nxp + 255)/256), dim3(256), 0, vox_tab, vnx, vny, J.nx, J.nxp, sx, (terra::sgh_u4 *)J.xh);
+			run(terra::k_split_voxel_table<true, terra::VOX_SINES>, dim3((J.nyp + 255)/256), dim3(256), 0, vox_tab, vnx, vny, J.nx, J.nyp, sy, (terra::sgh_u4 *)J.yh);
 		}
 		else if (nchunks) {
-			hipLaunchKernelGGL(terra::k_split_table<false>, dim3((unsigned)(((size_t)nchunks*J.nxp + 255)/256)), dim3(256), 0, stream, J.xt, J.nxp, J.kstart, J.kend, nchunks, sx, (terra::sgh_u4 *)J.xh);
-			hipLaunchKernelGGL(terra::k_split_table<true>,  dim3((unsigned)(((size_t)nchunks*J.nyp + 255)/256)), dim3(256), 0, stream, J.yt, J.nyp, J.kstart, J.kend, nchunks, sy, (terra::sgh_u4 *)J.yh);
+			run(terra::k_split_table<false>, dim3((unsigned)(((size_t)nchunks*J.nxp + 255)/256)), dim3(256), 0, J.xt, J.nxp, J.kstart, J.kend, nchunks, sx, (terra::sgh_u4 *)J.xh);
+			run(terra::k_split_table<true>, dim3((unsigned)(((size_t)nchunks*J.nyp + 255)/256)), dim3(256), 0, J.yt, J.nyp, J.kstart, J.kend, nchunks, sy, (terra::sgh_u4 *)J.yh);
 		}
 		if (KIND == terra::SGF_VOXELS && J.nx <= 64 && (J.nyp % 256u) == 0) {J.narrow = 1; J.ntx = 1; J.nty = J.nyp/256u;} // (rows beyond ny: zero table rows, nothing stored)
 		unsigned const nb = J.ntx*J.nty, grid = ((nb + 7)/8)*8;
-		hipLaunchKernelGGL(terra::k_sine_grid_h3<KIND>, dim3(grid), dim3(256), 0, stream, J);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_sine_grid_h3<KIND>, dim3(grid), dim3(256), 0, J);
 		return true;
+	}
+	// the job of the matrix-pipe sum (k_sine_grid_mx / k_sine_grid_h3) over a grid job's tables; a tile batch adds its map
+	terra::sgf_job_t make_sgf_job(terra::grid_job_t const &job, terra::noise_consts_t const &nc, float const *xt, float const *yt, float const *smx, float const *smy, float *out, uint32_t *mm, unsigned ntx, unsigned nty) const {
+		terra::sgf_job_t J; memset(&J, 0, sizeof(J));
+		J.xt = xt; J.yt = yt; J.smx = smx; J.smy = smy; J.out = out; J.mm = mm; J.nx = job.nx; J.ny = job.ny; J.nxp = job.nxp; J.nyp = job.nyp; J.ntx = ntx; J.nty = nty; J.rowgroup = (unsigned)opt->sg_rowgroup;
+		J.kstart = job.kstart; J.kend = terra::F_TABLE_SIZE; J.glaciate = (job.glaciate && nc.glaciate) ? 1 : 0; J.sine_mag = (job.glaciate && job.use_sine_mag) ? 1 : 0;
+		J.zmax_est = nc.zmax_est; J.zmax_est2 = nc.zmax_est2; J.zmax_est2_inv = nc.zmax_est2_inv; J.sine_offset = job.sine_offset;
+		return J;
 	}
 	// mm (optional): device uint32[2] pre-set to 0xFFFFFFFF receiving min f2ord(z) / min ~f2ord(z); returns false when the caller must run minmax() itself
 	bool sine_grid(terra::grid_job_t const &job, terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float const *xt, float const *yt, float const *smx, float const *smy, float *out, uint32_t *mm) {
-		if (simple_kernels) {sine_grid_simple(job, nc, L, xt, yt, smx, smy, out); return false;}
+		if (opt->simple_kernels) {sine_grid_simple(job, nc, L, xt, yt, smx, smy, out); return false;}
 		use();
 		unsigned const ntx = job.nxp/terra::SG_BX, nty_all = (job.ny + terra::SG_BY - 1)/terra::SG_BY;
 		if ((job.tyn || job.ty0) && (job.fused || job.tyn == 0 || job.ty0 >= nty_all || job.tyn > nty_all - job.ty0)) throw std::invalid_argument("sine_grid: a tile-row window must lie inside the grid (the fused kernels take whole grids only)");
 		unsigned const nty = job.tyn ? job.tyn : nty_all; // the launch's tile rows: the kernel adds job.ty0 (grid_job_t: a window of the grid, the whole of it by default)
 		unsigned const nb = ntx*nty, grid = ((nb + 7)/8)*8;
 		if (job.fused) { // TERRA_GEN_FUSED: the sum on the f32 matrix pipe, persistent blocks (two per CU: 225 registers per lane)
-			terra::sgf_job_t J; memset(&J, 0, sizeof(J));
-			J.xt = xt; J.yt = yt; J.smx = smx; J.smy = smy; J.out = out; J.mm = mm; J.nx = job.nx; J.ny = job.ny; J.nxp = job.nxp; J.nyp = job.nyp; J.ntx = ntx; J.nty = nty; J.rowgroup = sg_rowgroup;
-			J.kstart = job.kstart; J.kend = terra::F_TABLE_SIZE; J.glaciate = (job.glaciate && nc.glaciate) ? 1 : 0; J.sine_mag = (job.glaciate && job.use_sine_mag) ? 1 : 0;
-			J.zmax_est = nc.zmax_est; J.zmax_est2 = nc.zmax_est2; J.zmax_est2_inv = nc.zmax_est2_inv; J.sine_offset = job.sine_offset;
+			terra::sgf_job_t const J = make_sgf_job(job, nc, xt, yt, smx, smy, out, mm, ntx, nty);
 			if (job.fused == 2 && sine_grid_h3<terra::SGF_GRID>(J, 1.0f, job.fast_amax)) return true; // TERRA_GEN_FAST (|SINF| <= 1 bounds the x table)
-			hipLaunchKernelGGL(terra::k_sine_grid_mx<terra::SGF_GRID>, dim3(std::min(grid, (unsigned)(2*num_cus + 7)/8*8)), dim3(256), 0, stream, J);
-			TERRA_HIP_CHECK(hipGetLastError());
+			run(terra::k_sine_grid_mx<terra::SGF_GRID>, dim3(std::min(grid, (unsigned)(2*num_cus + 7)/8*8)), dim3(256), 0, J);
 			return true;
 		}
-		terra::sg_tiles_t const tl{nullptr, nullptr, 0, sg_rowgroup, 0, 0, 0, 0xFFFFFFFFu, 0, 0xFFFFFFFFu, 0};
+		terra::sg_tiles_t const tl{nullptr, nullptr, 0, (unsigned)opt->sg_rowgroup, 0, 0, 0, 0xFFFFFFFFu, 0, 0xFFFFFFFFu, 0};
 		if (job.plain_only) {
-			auto const go = [&](auto kern) {hipLaunchKernelGGL(kern, dim3(grid), dim3(terra::SG_THREADS), 0, stream, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);};
-			if (sg_kc == 27) go(terra::k_sine_grid<false, false, 27>); else if (sg_kc == 20) go(terra::k_sine_grid<false, false, 20>); else go(terra::k_sine_grid<false, false, 45>);
+			auto const go = [&](auto kern) {run(kern, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);};
+			if (opt->sg_kc == 27) go(terra::k_sine_grid<false, false, 27>); else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20>); else go(terra::k_sine_grid<false, false, 45>);
 		}
-		else                {hipLaunchKernelGGL((terra::k_sine_grid<false, true>),  dim3(grid), dim3(terra::SG_THREADS), 0, stream, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);}
-		TERRA_HIP_CHECK(hipGetLastError());
+		else                {run(terra::k_sine_grid<false, true>, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);}
 		return true;
 	}
 	bool noise_grid(terra::grid_job_t const &job, terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float const *smx, float const *smy, float *out, uint32_t *mm, uint32_t const *nlut) {
-		if (simple_kernels) {noise_grid_simple(job, nc, L, smx, smy, out); return false;}
+		if (opt->simple_kernels) {noise_grid_simple(job, nc, L, smx, smy, out); return false;}
 		use();
 		if (job.fused) {TERRA_HIP_CHECK((hipError_t)terra_fz_noise_grid(job.mode, &job, &nc, &L, smx, smy, out, mm, nlut, (void *)stream)); return true;} // TERRA_GEN_FUSED: the contraction-allowed build (terra_fz.hip)
 		dim3 const grid((job.nx + 127)/128, (job.ny + terra::NG_ROWS - 1)/terra::NG_ROWS), block(256); // 64 lanes x 2 cells per row segment, 4 rows at a time, NG_ROWS rows per block
 		terra::noise_oct_t const oc = terra::make_noise_oct(nc);
-		switch (job.mode) {
-		case terra::MGEN_PERLIN:      hipLaunchKernelGGL(terra::k_noise_grid<terra::MGEN_PERLIN>,      grid, block, 0, stream, job, nc, L, smx, smy, out, mm, nlut, oc); break;
-		case terra::MGEN_DWARP_GPU:   hipLaunchKernelGGL(terra::k_noise_grid<terra::MGEN_DWARP_GPU>,   grid, block, 0, stream, job, nc, L, smx, smy, out, mm, nlut, oc); break;
-		case terra::MGEN_SIMPLEX_GPU: hipLaunchKernelGGL(terra::k_noise_grid<terra::MGEN_SIMPLEX_GPU>, grid, block, 0, stream, job, nc, L, smx, smy, out, mm, nlut, oc); break;
-		default:                      hipLaunchKernelGGL(terra::k_noise_grid<terra::MGEN_SIMPLEX>,     grid, block, 0, stream, job, nc, L, smx, smy, out, mm, nlut, oc); break;
-		}
-		TERRA_HIP_CHECK(hipGetLastError());
+		with_noise_mode(job.mode, [&](auto m) {run(terra::k_noise_grid<decltype(m)::value>, grid, block, 0, job, nc, L, smx, smy, out, mm, nlut, oc);});
 		return true;
 	}
-	int32_t *tile_map = nullptr; size_t tile_map_count = 0;
 	// may a band of the tiles' fields be evaluated instead of whole squares?  Only where tile_grid takes the packed epilogue of the plain sine kernel (the one that knows bands)
 	bool tile_band_ok(uint32_t n, uint32_t nux, uint32_t nuy, uint32_t twx, bool unique_tiles, bool plain_only, int md) const {
-		return !simple_kernels && md == terra::MGEN_SINE && unique_tiles && plain_only && (uint64_t)n*2 >= (uint64_t)nux*nuy && ((nux*twx) & 3u) == 0 && (!opt || opt->sg_kc_tiles == 27) && (!opt || opt->ao_bands != 0);
+		return !opt->simple_kernels && md == terra::MGEN_SINE && unique_tiles && plain_only && (uint64_t)n*2 >= (uint64_t)nux*nuy && ((nux*twx) & 3u) == 0 && opt->sg_kc_tiles == 27 && opt->ao_bands != 0;
 	}
 	void tile_grid(uint32_t n, terra::tile_ref_pod_t const *refs, uint32_t nux, uint32_t nuy, float const *xt, float const *yt, uint32_t nxpv, uint32_t nypv, float const *d_sm, float const *d_m0,
 		int md, int shp, int kstart, bool use_sm, float so, terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float dxv, float dyv, float *zvals, bool plain_only, uint32_t tw, bool unique_tiles, bool glaciate = true, uint32_t const *nlut = nullptr, int fused = 0, float fast_amax = 0.0f,
@@ -336,7 +328,7 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	{
 		// sine mode and a batch that fills at least half of (distinct tile columns) x (distinct tile rows): ONE LDS-tiled k_sine_grid launch over the
 		// virtual grid, scattered into the per-tile layout.  Sparse batches and the fBm modes are per-cell anyway.
-		if (!simple_kernels && md != terra::MGEN_SINE) { // fBm modes: per-cell work, two cells per lane
+		if (!opt->simple_kernels && md != terra::MGEN_SINE) { // fBm modes: per-cell work, two cells per lane
 			use();
 			terra::grid_job_t job;
 			job.mx0 = 0; job.my0 = 0; job.mdx = dxv; job.mdy = dyv; job.nx = job.ny = tw; job.nxp = nxpv; job.nyp = nypv;
@@ -345,45 +337,33 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 			terra::noise_oct_t const oc = terra::make_noise_oct(nc);
 			size_t const threads = (size_t)n*tw*((tw + 1)/2);
 			dim3 const grid((unsigned)((threads + 255)/256)), block(256);
-			switch (md) {
-			case terra::MGEN_PERLIN:      hipLaunchKernelGGL(terra::k_noise_tiles<terra::MGEN_PERLIN>,      grid, block, 0, stream, refs, n, nux, d_sm, d_m0, job, nc, L, zvals, tw, nlut, oc); break;
-			case terra::MGEN_DWARP_GPU:   hipLaunchKernelGGL(terra::k_noise_tiles<terra::MGEN_DWARP_GPU>,   grid, block, 0, stream, refs, n, nux, d_sm, d_m0, job, nc, L, zvals, tw, nlut, oc); break;
-			case terra::MGEN_SIMPLEX_GPU: hipLaunchKernelGGL(terra::k_noise_tiles<terra::MGEN_SIMPLEX_GPU>, grid, block, 0, stream, refs, n, nux, d_sm, d_m0, job, nc, L, zvals, tw, nlut, oc); break;
-			default:                      hipLaunchKernelGGL(terra::k_noise_tiles<terra::MGEN_SIMPLEX>,     grid, block, 0, stream, refs, n, nux, d_sm, d_m0, job, nc, L, zvals, tw, nlut, oc); break;
-			}
-			TERRA_HIP_CHECK(hipGetLastError());
+			with_noise_mode(md, [&](auto m) {run(terra::k_noise_tiles<decltype(m)::value>, grid, block, 0, refs, n, nux, d_sm, d_m0, job, nc, L, zvals, tw, nlut, oc);});
 			return;
 		}
-		if (simple_kernels || md != terra::MGEN_SINE || !unique_tiles || (uint64_t)n*2 < (uint64_t)nux*nuy || ((uintptr_t)zvals & 7)) {tile_grid_simple(n, refs, nux, nuy, xt, yt, nxpv, nypv, d_sm, d_m0, md, shp, kstart, use_sm, so, nc, L, dxv, dyv, zvals, tw, glaciate, fused); return;}
+		if (opt->simple_kernels || md != terra::MGEN_SINE || !unique_tiles || (uint64_t)n*2 < (uint64_t)nux*nuy || ((uintptr_t)zvals & 7)) {tile_grid_simple(n, refs, nux, nuy, xt, yt, nxpv, nypv, d_sm, d_m0, md, shp, kstart, use_sm, so, nc, L, dxv, dyv, zvals, tw, glaciate, fused); return;}
 		use();
 		size_t const cnt = (size_t)nux*nuy;
-		if (cnt > tile_map_count) {if (tile_map) {sync(); (void)hipFree(tile_map);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_map, cnt*sizeof(int32_t))); tile_map_count = cnt;}
-		fill32(tile_map, 0xFFFFFFFFu, cnt);
-		int32_t *tm = tile_map;
+		int32_t *tm = (int32_t *)tile_map.grow(*this, cnt*sizeof(int32_t));
+		fill32(tm, 0xFFFFFFFFu, cnt);
 		launch(n, [=] TERRA_LAMBDA (size_t i) {terra::tile_ref_pod_t const r = refs[i]; tm[(size_t)r.yi*nux + r.xi] = (int32_t)i;});
 		terra::grid_job_t job;
 		job.mx0 = 0; job.my0 = 0; job.mdx = dxv; job.mdy = dyv; job.nx = nux*tw; job.ny = nuy*(band ? band->twy : tw); job.nxp = nxpv; job.nyp = nypv;
 		job.mode = terra::MGEN_SINE; job.shape = shp; job.kstart = kstart; job.glaciate = glaciate ? 1 : 0; job.use_sine_mag = use_sm ? 1 : 0; job.sine_offset = so;
 		unsigned const ntx = job.nxp/terra::SG_BX, nty = (job.ny + terra::SG_BY - 1)/terra::SG_BY, nb = ntx*nty, grid = ((nb + 7)/8)*8;
-		terra::sg_tiles_t tl{tm, d_m0, nux, sg_rowgroup, tw, tw, tw, 0xFFFFFFFFu, 0, 0xFFFFFFFFu, 0};
+		terra::sg_tiles_t tl{tm, d_m0, nux, (unsigned)opt->sg_rowgroup, tw, tw, tw, 0xFFFFFFFFu, 0, 0xFFFFFFFFu, 0};
 		if (band) {tl.twy = band->twy; tl.ostride = band->ostride; tl.xsplit = band->xsplit; tl.xgap = band->xgap; tl.ysplit = band->ysplit; tl.ygap = band->ygap; fused = 0;}
 		job.plain_only = plain_only ? 1 : 0;
 		if (fused && plain_only) { // "gen.fused": the batch's virtual grid on the matrix pipe, scattered into the per-tile layout
-			terra::sgf_job_t J; memset(&J, 0, sizeof(J));
-			J.xt = xt; J.yt = yt; J.smx = d_sm; J.smy = d_sm + (size_t)nux*tw; J.out = zvals; J.mm = nullptr; J.nx = job.nx; J.ny = job.ny; J.nxp = job.nxp; J.nyp = job.nyp; J.ntx = ntx; J.nty = nty; J.rowgroup = sg_rowgroup;
-			J.kstart = kstart; J.kend = terra::F_TABLE_SIZE; J.glaciate = (glaciate && nc.glaciate) ? 1 : 0; J.sine_mag = (glaciate && use_sm) ? 1 : 0;
-			J.zmax_est = nc.zmax_est; J.zmax_est2 = nc.zmax_est2; J.zmax_est2_inv = nc.zmax_est2_inv; J.sine_offset = so;
+			terra::sgf_job_t J = make_sgf_job(job, nc, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, nullptr, ntx, nty);
 			J.tile_map = tm; J.nux = nux; J.tw = tw;
 			if (fused == 2 && sine_grid_h3<terra::SGF_TILES>(J, 1.0f, fast_amax)) return;
-			hipLaunchKernelGGL(terra::k_sine_grid_mx<terra::SGF_TILES>, dim3(std::min(grid, (unsigned)(2*num_cus + 7)/8*8)), dim3(256), 0, stream, J);
-			TERRA_HIP_CHECK(hipGetLastError());
+			run(terra::k_sine_grid_mx<terra::SGF_TILES>, dim3(std::min(grid, (unsigned)(2*num_cus + 7)/8*8)), dim3(256), 0, J);
 			return;
 		}
-		int const kc_tiles = opt ? opt->sg_kc_tiles : 27; // 27: three chunks, 29.7 KB per block (measured on the 64 x 64 batch: 291.8 -> 283.9 us, the 201-wide AO context 735 -> 706 us); "sg.kc_tiles" 45: two chunks, 48 KB.  The same sum either way
-		if (plain_only && kc_tiles == 27) {hipLaunchKernelGGL((terra::k_sine_grid<true, false, 27>), dim3(grid), dim3(terra::SG_THREADS), 0, stream, job, nc, L, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, ntx, nty, (uint32_t *)nullptr, tl);}
-		else if (plain_only) {hipLaunchKernelGGL((terra::k_sine_grid<true, false>), dim3(grid), dim3(terra::SG_THREADS), 0, stream, job, nc, L, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, ntx, nty, (uint32_t *)nullptr, tl);}
-		else            {hipLaunchKernelGGL((terra::k_sine_grid<true, true>),  dim3(grid), dim3(terra::SG_THREADS), 0, stream, job, nc, L, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, ntx, nty, (uint32_t *)nullptr, tl);}
-		TERRA_HIP_CHECK(hipGetLastError());
+		int const kc_tiles = opt->sg_kc_tiles; // 27: three chunks, 29.7 KB per block (measured on the 64 x 64 batch: 291.8 -> 283.9 us, the 201-wide AO context 735 -> 706 us); "sg.kc_tiles" 45: two chunks, 48 KB.  The same sum either way
+		if (plain_only && kc_tiles == 27) {run(terra::k_sine_grid<true, false, 27>, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, ntx, nty, (uint32_t *)nullptr, tl);}
+		else if (plain_only) {run(terra::k_sine_grid<true, false>, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, ntx, nty, (uint32_t *)nullptr, tl);}
+		else            {run(terra::k_sine_grid<true, true>, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, d_sm, d_sm + (size_t)nux*tw, zvals, ntx, nty, (uint32_t *)nullptr, tl);}
 	}
 	// the whole batch in one dataflow launch (k_tile_shadows_flow); sync_words: the ticket counter, zeroed here.  false: use the per-level launches.  Leaves SHADOW_EDGE_PUB set in `out`
 	// the lane order of the shadow kernels (terra::shadow_lane_order) for the last light / tile geometry seen: the per-level launches of a batch ask for it once per level
@@ -399,49 +379,44 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	// The LDS kernels: their layout is for tiles of 130 cells a side (S = 128), the block ORs its mask out a word at a time.  Every level of a batch must take the same
 	// path (the LDS kernels order a sweep's edge writes with stride 1024, tile_shadows_simple with 4096): the choice depends only on the batch's constants
 	bool shadow_kernels_ok(terra::shadow_consts_t const &c, uint8_t const *sm, uint32_t np, terra::shadow_lanes_t &lanes) {
-		return !simple_kernels && c.xsize == 130 && !((uintptr_t)sm & 3) && shadow_lanes(c, np, lanes);
+		return !opt->simple_kernels && c.xsize == 130 && !((uintptr_t)sm & 3) && shadow_lanes(c, np, lanes);
 	}
 	bool tile_shadows_flow(terra::shadow_consts_t const &c, uint32_t ntiles, uint32_t nslots, uint32_t const *ord, int32_t const *adj, float const *z, unsigned long long *out, uint8_t *sm, uint32_t np, uint32_t *sync_words) {
 		terra::shadow_lanes_t lanes;
-		if ((opt && opt->shadows_levels) || !shadow_kernels_ok(c, sm, np, lanes)) return false;
+		if (opt->shadows_levels || !shadow_kernels_ok(c, sm, np, lanes)) return false;
 		use();
 		fill32(sync_words, 0u, 1); // the ticket (the edge arrays were zeroed by the caller: no stale `published` bit)
 		unsigned const grid = std::min<unsigned>(ntiles, (unsigned)(2*num_cus));
-		hipLaunchKernelGGL(terra::k_tile_shadows_flow, dim3(grid), dim3(terra::SH_LEVEL_THREADS), terra::SH_LEVEL_LDS, stream, c, nslots, ntiles, ord, adj, z, out, sm, np, sync_words, lanes);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_tile_shadows_flow, dim3(grid), dim3(terra::SH_LEVEL_THREADS), terra::SH_LEVEL_LDS, c, nslots, ntiles, ord, adj, z, out, sm, np, sync_words, lanes);
 		return true;
 	}
 	void tile_shadows(terra::shadow_consts_t const &c, uint32_t cnt, uint32_t const *ord, int32_t const *adj, uint32_t n, float const *z, unsigned long long *out, uint8_t *sm, uint32_t np) {
 		terra::shadow_lanes_t lanes;
 		if (!shadow_kernels_ok(c, sm, np, lanes)) {tile_shadows_simple(c, cnt, ord, adj, n, z, out, sm, np); return;}
 		use();
-		hipLaunchKernelGGL(terra::k_tile_shadows_level, dim3(cnt), dim3(terra::SH_LEVEL_THREADS), terra::SH_LEVEL_LDS, stream, c, n, ord, adj, z, out, sm, np, lanes);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_tile_shadows_level, dim3(cnt), dim3(terra::SH_LEVEL_THREADS), terra::SH_LEVEL_LDS, c, n, ord, adj, z, out, sm, np, lanes);
 	}
 	bool ao_tile_ok = false;
 	void tile_ao_pass(uint32_t n, float const *z, float const *ctx, uint8_t *ao, float dz, bool own, uint32_t S) {
-		if (simple_kernels || S != 128) {tile_ao_simple(n, z, ctx, ao, dz, own, S); return;} // (the kernels' LDS layout is for 130-cell tiles)
+		if (opt->simple_kernels || S != 128) {tile_ao_simple(n, z, ctx, ao, dz, own, S); return;} // (the kernels' LDS layout is for 130-cell tiles)
 		use();
-		if (ao_tile_ok && (!opt || opt->ao_whole)) { // one workgroup per tile, the context staged once
+		if (ao_tile_ok && opt->ao_whole) { // one workgroup per tile, the context staged once
 			unsigned const grid = std::min<unsigned>(n, (unsigned)num_cus); // persistent: a CU holds one of these workgroups
-			if (own) {hipLaunchKernelGGL(terra::k_tile_ao_tile<true>, dim3(grid), dim3(terra::AOT_THREADS), terra::AOT_LDS, stream, z, ctx, ao, dz, n);}
-			else {hipLaunchKernelGGL(terra::k_tile_ao_tile<false>, dim3(grid), dim3(terra::AOT_THREADS), terra::AOT_LDS, stream, z, ctx, ao, dz, n);}
-			TERRA_HIP_CHECK(hipGetLastError());
+			if (own) {run(terra::k_tile_ao_tile<true>, dim3(grid), dim3(terra::AOT_THREADS), terra::AOT_LDS, z, ctx, ao, dz, n);}
+			else {run(terra::k_tile_ao_tile<false>, dim3(grid), dim3(terra::AOT_THREADS), terra::AOT_LDS, z, ctx, ao, dz, n);}
 			return;
 		}
 		unsigned const nbands = (terra::AO_TEX + terra::AO_BAND - 1)/terra::AO_BAND;
 		size_t const lds = (size_t)(terra::AO_BAND + terra::AO_RL)*terra::AO_CS*sizeof(float);
-		if (own) {hipLaunchKernelGGL(terra::k_tile_ao<true>, dim3(n*nbands), dim3(terra::AO_THREADS), lds, stream, z, ctx, ao, dz);}
-		else {hipLaunchKernelGGL(terra::k_tile_ao<false>, dim3(n*nbands), dim3(terra::AO_THREADS), lds, stream, z, ctx, ao, dz);}
-		TERRA_HIP_CHECK(hipGetLastError());
+		if (own) {run(terra::k_tile_ao<true>, dim3(n*nbands), dim3(terra::AO_THREADS), lds, z, ctx, ao, dz);}
+		else {run(terra::k_tile_ao<false>, dim3(n*nbands), dim3(terra::AO_THREADS), lds, z, ctx, ao, dz);}
 	}
-	uint32_t *tile_acc = nullptr; size_t tile_acc_bytes = 0; // k_tile_post's per-tile accumulators
 	// k_tile_post (S = 128, LDS-staged: the zvals 16-byte aligned), else k_tile_post_sized, else tile_post_simple; both kernels store texels as words
 	void tile_post_pass(uint32_t n, terra::tile_ref_pod_t const *refs, float const *z, terra_tile_stats *st, uint8_t *nm, float *mnz, float wpz, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {
 		float const c2 = dxy*dxy;
 		// the kernels take min_normal_z from the largest |n|^2 and never look at get_norm's "mag < TOLERANCE" branch: a texel's mag is >= sqrtf(dxdy*dxdy) (a sum that only grows, monotone roundings)
 		bool const normalized = !(sqrtf(c2) < 1.0E-12f) && dxy > 0.0f;
-		bool const kernels = !simple_kernels && !((uintptr_t)nm & 3) && normalized;
+		bool const kernels = !opt->simple_kernels && !((uintptr_t)nm & 3) && normalized;
 		bool const tuned = kernels && S == 128 && !((uintptr_t)z & 15), sized = kernels && (uint64_t)n*4 <= 0x7FFFFFFFull;
 		if (!tuned && !sized) {tile_post_simple(n, refs, z, st, nm, mnz, wpz, rad_c, dxv, dyv, dxy, S); return;}
 		use();
@@ -450,13 +425,11 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 			float nv[3]; terra::tile_normal_v(0.0f, 0.0f, 0.0f, dxv, dyv, dxy, nv);
 			flat_word = (uint32_t)(uint8_t)(127.0*((double)nv[0] + 1.0)) | ((uint32_t)(uint8_t)(127.0*((double)nv[1] + 1.0)) << 8) | ((uint32_t)(uint8_t)(127.0*((double)nv[2] + 1.0)) << 16);
 		}
-		size_t const bytes = (size_t)n*terra::TP_ACC*sizeof(uint32_t);
-		if (bytes > tile_acc_bytes) {if (tile_acc) {sync(); (void)hipFree(tile_acc);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_acc, bytes)); tile_acc_bytes = bytes;}
-		hipLaunchKernelGGL(terra::k_tile_post_init, dim3((n*terra::TP_ACC + 255)/256), dim3(256), 0, stream, tile_acc, n);
-		if (tuned) {hipLaunchKernelGGL(terra::k_tile_post, dim3(n*4), dim3(terra::TP_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word);}
-		else {hipLaunchKernelGGL(terra::k_tile_post_sized, dim3(n*4), dim3(terra::TPS_THREADS), 0, stream, refs, z, st, nm, tile_acc, wpz, dxv, dyv, dxy, c2, flat_word, S);}
-		hipLaunchKernelGGL(terra::k_tile_post_final, dim3((n + 255)/256), dim3(256), 0, stream, refs, n, st, mnz, tile_acc, rad_c, dxy, nm ? 1 : 0, S);
-		TERRA_HIP_CHECK(hipGetLastError());
+		uint32_t *const acc = (uint32_t *)tile_acc.grow(*this, (size_t)n*terra::TP_ACC*sizeof(uint32_t));
+		run(terra::k_tile_post_init, dim3((n*terra::TP_ACC + 255)/256), dim3(256), 0, acc, n);
+		if (tuned) {run(terra::k_tile_post, dim3(n*4), dim3(terra::TP_THREADS), 0, refs, z, st, nm, acc, wpz, dxv, dyv, dxy, c2, flat_word);}
+		else {run(terra::k_tile_post_sized, dim3(n*4), dim3(terra::TPS_THREADS), 0, refs, z, st, nm, acc, wpz, dxv, dyv, dxy, c2, flat_word, S);}
+		run(terra::k_tile_post_final, dim3((n + 255)/256), dim3(256), 0, refs, n, st, mnz, acc, rad_c, dxy, nm ? 1 : 0, S);
 	}
 	void tile_erosion(uint32_t n, float *zvals, terra::erosion_consts_t const &ec, uint32_t iters) {
 		use();
@@ -464,25 +437,20 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		// default: the whole clamp-padded tile resident in LDS (76 KB, 2 tiles per CU; measured 126 ms for 4096 tiles x 1000 droplets);
 		// option "tile_erosion" = "window": a 32x32 LDS window over an HBM/L2-resident copy (10 KB, ~15 tiles per CU; 141 ms: the batch is bound by its
 		// heaviest land tiles, ~50k dependent droplet steps each, not by occupancy).  Grids too large for LDS always use the window.
-		bool const use_lds = !(opt && opt->tile_erosion_window) && lds <= 96*1024;
+		bool const use_lds = !opt->tile_erosion_window && lds <= 96*1024;
 		if (!use_lds) {
-			size_t const bytes = (size_t)n*lds;
-			if (bytes > tile_pad_bytes) {if (tile_pad) {sync(); (void)hipFree(tile_pad);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_pad, bytes)); tile_pad_bytes = bytes;}
-			if (simple_kernels) {tile_erosion_simple(n, zvals, ec, iters, tile_pad);} // cross-check path: one scalar lane per tile
-			else {tile_erosion_windowed(n, zvals, ec, iters, tile_pad);}
+			float *const pad = (float *)tile_pad.grow(*this, (size_t)n*lds);
+			if (opt->simple_kernels) {tile_erosion_simple(n, zvals, ec, iters, pad);} // cross-check path: one scalar lane per tile
+			else {tile_erosion_windowed(n, zvals, ec, iters, pad);}
 			return;
 		}
 		uint32_t const *d_order = nullptr, *d_landc = nullptr;
 		if (n > 512 && (uint64_t)n*iters >= (1u << 16)) { // more tiles than the chip holds at once (2 per CU): longest predicted chains first
-			size_t const bytes = (size_t)n*2*sizeof(uint32_t);
-			if (bytes > tile_order_bytes) {if (tile_order) {sync(); (void)hipFree(tile_order);} TERRA_HIP_CHECK(hipMalloc((void **)&tile_order, bytes)); tile_order_bytes = bytes;}
-			uint32_t *d_land = tile_order, *d_ord = tile_order + n;
+			uint32_t *d_land = (uint32_t *)tile_order.grow(*this, (size_t)n*2*sizeof(uint32_t)), *d_ord = d_land + n;
 			fill32(d_land, 0, n);
-			hipLaunchKernelGGL(terra::k_tile_land_cells, dim3(n), dim3(256), 0, stream, zvals, (uint32_t)(ec.xsize*ec.ysize), ec.water_thresh, d_land);
-			TERRA_HIP_CHECK(hipGetLastError());
+			run(terra::k_tile_land_cells, dim3(n), dim3(256), 0, zvals, (uint32_t)(ec.xsize*ec.ysize), ec.water_thresh, d_land);
 			if (n <= 65536) { // the order is made on the device (rank by counting: n^2 / 2^12 block-steps, 16 M comparisons for the 64 x 64 batch): the call never waits for the stream
-				hipLaunchKernelGGL(terra::k_tile_order_by_land, dim3((n + 255)/256), dim3(256), 0, stream, d_land, n, d_ord);
-				TERRA_HIP_CHECK(hipGetLastError());
+				run(terra::k_tile_order_by_land, dim3((n + 255)/256), dim3(256), 0, d_land, n, d_ord);
 			}
 			else {
 				std::vector<uint32_t> land(n), ord(n);
@@ -493,43 +461,44 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 			}
 			d_order = d_ord; d_landc = d_land;
 		}
-		hipLaunchKernelGGL(terra::k_tile_erosion, dim3(n), dim3(64), lds, stream, zvals, ec, iters, d_order, d_landc);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_tile_erosion, dim3(n), dim3(64), lds, zvals, ec, iters, d_order, d_landc);
 	}
 	void minmax(float const *vals, size_t n, uint32_t *d) {
-		if (simple_kernels || ((uintptr_t)vals & 15)) {minmax_simple(vals, n, d); return;}
+		if (opt->simple_kernels || ((uintptr_t)vals & 15)) {minmax_simple(vals, n, d); return;}
 		use();
 		unsigned const blocks = (unsigned)std::min<size_t>((n/4 + 255)/256 + 1, 256*8);
-		hipLaunchKernelGGL(terra::k_minmax, dim3(blocks), dim3(256), 0, stream, vals, n, d);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_minmax, dim3(blocks), dim3(256), 0, vals, n, d);
 	}
 	void quantize16(float const *vals, size_t n, float val_add, float val_div, uint8_t *pix) {
-		size_t const n8 = ((simple_kernels || ((uintptr_t)vals & 15) || ((uintptr_t)pix & 15)) ? 0 : n/8);
+		size_t const n8 = ((opt->simple_kernels || ((uintptr_t)vals & 15) || ((uintptr_t)pix & 15)) ? 0 : n/8);
 		if (n8) {
 			use();
 			if ((n8 + 255)/256 > 0x7FFFFFFFull) throw std::invalid_argument("quantize16: grid too large");
-			hipLaunchKernelGGL(terra::k_quantize16, dim3((unsigned)((n8 + 255)/256)), dim3(256), 0, stream, vals, n8, val_add, val_div, (terra::st_u4 *)pix);
-			TERRA_HIP_CHECK(hipGetLastError());
+			run(terra::k_quantize16, dim3((unsigned)((n8 + 255)/256)), dim3(256), 0, vals, n8, val_add, val_div, (terra::st_u4 *)pix);
 		}
 		quantize16_simple(vals + n8*8, n - n8*8, val_add, val_div, pix + n8*16); // the tail (or everything, unaligned / cross-check)
 	}
-	bool tile_weights(terra::landscape_consts_t const &c, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals, float const *noise, float const *params, uint32_t *w32, terra::grass_block_pod_t *blocks, uint8_t *any_grass) {
-		if (simple_kernels || (uint64_t)n*terra::WK_BANDS > 0x7FFFFFFFull) return false;
+	// a hook that is one launch: false (and no launch) where the driver's simple form is to run -- "kernels.simple", or a grid that does not fit (`fits`)
+	template<class K, class... A> bool launch_if(bool fits, K kernel, dim3 grid, dim3 block, A... args) {
+		if (opt->simple_kernels || !fits) return false;
 		use();
-		hipLaunchKernelGGL(terra::k_tile_weights, dim3(n*terra::WK_BANDS), dim3(256), 0, stream, c, refs, zvals, noise, params, w32, blocks, any_grass);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(kernel, grid, block, 0, args...);
 		return true;
+	}
+	// one workgroup of T threads per tile of a batch of n
+	template<unsigned T, class K, class... A> bool launch_per_tile(K kernel, uint32_t n, A... args) {return launch_if(n <= 0x7FFFFFFFu, kernel, dim3(n), dim3(T), args...);}
+	bool tile_weights(terra::landscape_consts_t const &c, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals, float const *noise, float const *params, uint32_t *w32, terra::grass_block_pod_t *blocks, uint8_t *any_grass) {
+		return launch_if((uint64_t)n*terra::WK_BANDS <= 0x7FFFFFFFull, terra::k_tile_weights, dim3(n*terra::WK_BANDS), dim3(256), c, refs, zvals, noise, params, w32, blocks, any_grass);
 	}
 	// the grass brush: k_grass_brush_texels over (tile, window chunk) -- only when the brush has a radius -- then k_grass_brush_tiles once per tile
 	bool tile_edit_grass(terra::grass_brush_consts_t const &g, terra::landscape_consts_t const &c, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals, terra_tile_stats const *stats,
 		uint8_t const *distant, float const *params, uint32_t *w32, terra::grass_block_pod_t *blocks, uint8_t *flags, uint8_t *updated, uint32_t *ranges)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
 		uint32_t const chunks = (g.wx*g.wy + terra::GB_CHUNK - 1)/terra::GB_CHUNK;
-		if (g.rr > 0.0f && chunks) {hipLaunchKernelGGL(terra::k_grass_brush_texels, dim3(n, chunks), dim3(terra::GB_THREADS), 0, stream, g, c, refs, zvals, stats, params, w32, flags);}
-		hipLaunchKernelGGL(terra::k_grass_brush_tiles, dim3(n), dim3(terra::GB_THREADS), 0, stream, g, c, refs, zvals, stats, distant, w32, blocks, flags, updated, ranges);
-		TERRA_HIP_CHECK(hipGetLastError());
+		if (g.rr > 0.0f && chunks) {run(terra::k_grass_brush_texels, dim3(n, chunks), dim3(terra::GB_THREADS), 0, g, c, refs, zvals, stats, params, w32, flags);}
+		run(terra::k_grass_brush_tiles, dim3(n), dim3(terra::GB_THREADS), 0, g, c, refs, zvals, stats, distant, w32, blocks, flags, updated, ranges);
 		return true;
 	}
 	// the line queries: k_line_boxes once per tile, then k_line_intersect once per line, in launches of fewer than 2^32 / LI_THREADS lines (HIP's limit on the
@@ -537,44 +506,34 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	bool tile_line_intersect(terra::line_query_consts_t const &c, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals, terra_tile_stats const *stats,
 		uint8_t const *distant, terra::line_box_t *boxes, float const *lines, int32_t const *line_tile, uint32_t nlines, terra::line_hit_pod_t *hits)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
-		if (n) {hipLaunchKernelGGL(terra::k_line_boxes, dim3((n + 255)/256), dim3(256), 0, stream, c, refs, stats, distant, n, boxes);}
+		if (n) {run(terra::k_line_boxes, dim3((n + 255)/256), dim3(256), 0, c, refs, stats, distant, n, boxes);}
 		uint32_t const per = (0xFFFFFFFFu/terra::LI_THREADS) & ~255u;
 		for (uint32_t r0 = 0; r0 < nlines;) {
 			uint32_t const m = terra::min_u32(per, nlines - r0);
-			hipLaunchKernelGGL(terra::k_line_intersect, dim3(m), dim3(terra::LI_THREADS), 0, stream, c, zvals, boxes, n, lines + (size_t)6*r0, line_tile ? line_tile + r0 : nullptr, hits + r0);
+			run(terra::k_line_intersect, dim3(m), dim3(terra::LI_THREADS), 0, c, zvals, boxes, n, lines + (size_t)6*r0, line_tile ? line_tile + r0 : nullptr, hits + r0);
 			r0 += m;
 		}
-		TERRA_HIP_CHECK(hipGetLastError());
 		return true;
 	}
 	// the tree map: k_tree_splats once per splat, then k_tree_map once per (tile, band of rows): bands of equal height that fit the kernel's LDS
 	bool tile_tree_map(terra::tree_tile_pod_t const *tiles, uint32_t n, uint32_t S, uint8_t const *distant, terra::tree_splat_in_t const *splats, uint32_t ns,
 		terra::tree_splat_pod_t *par, float dxv, float dyv, bool reset, uint16_t *map, uint8_t *updated)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
 		uint32_t const W = S + 1, rmax = terra::TM_CELLS/W, bands = (W + rmax - 1)/rmax, R = (W + bands - 1)/bands;
 		uint32_t const m = (ns > n) ? ns : n;
-		hipLaunchKernelGGL(terra::k_tree_splats, dim3((m + 255)/256), dim3(256), 0, stream, tiles, n, splats, ns, dxv, dyv, par, updated);
-		hipLaunchKernelGGL(terra::k_tree_map, dim3(n, (W + R - 1)/R), dim3(64), 0, stream, tiles, distant, par, (int)S, (int)R, reset ? 1 : 0, map, updated);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_tree_splats, dim3((m + 255)/256), dim3(256), 0, tiles, n, splats, ns, dxv, dyv, par, updated);
+		run(terra::k_tree_map, dim3(n, (W + R - 1)/R), dim3(64), 0, tiles, distant, par, (int)S, (int)R, reset ? 1 : 0, map, updated);
 		return true;
 	}
 	bool tile_shadow_texture(terra::shadow_tex_consts_t const &c, uint32_t n, uint32_t S, uint8_t const *sun, uint8_t const *moon, uint8_t const *ao, uint16_t const *tree, uint32_t *out) {
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_shadow_texture, dim3(n, ((S + 1)*(S + 1) + 255)/256), dim3(256), 0, stream, c, S, sun, moon, ao, tree, out);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_if(n <= 0x7FFFFFFFu, terra::k_shadow_texture, dim3(n, ((S + 1)*(S + 1) + 255)/256), dim3(256), c, S, sun, moon, ao, tree, out);
 	}
 	bool tile_tree_weights(size_t ntex, uint32_t const *in, uint8_t const *tree, uint32_t *out) {
-		if (simple_kernels || (ntex + 255)/256 > 0x7FFFFFFFull) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_tree_weights, dim3((unsigned)((ntex + 255)/256)), dim3(256), 0, stream, ntex, in, tree, out);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_if((ntex + 255)/256 <= 0x7FFFFFFFull, terra::k_tree_weights, dim3((unsigned)((ntex + 255)/256)), dim3(256), ntex, in, tree, out);
 	}
 	// tree AO shadows from the placement records: k_tree_ao_sources once per record slot, k_tree_ao_gather once per tile, then k_tree_map on the device-built lists
 	// (trmax is zero on entry)
@@ -584,22 +543,13 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		uint32_t *list_counts, uint16_t *map, uint8_t *updated)
 	{
 		uint32_t const chunks = (c.src_cap + 255)/256;
-		if (simple_kernels || n > 0x7FFFFFFFu || chunks > 65535u) return false;
+		if (opt->simple_kernels || n > 0x7FFFFFFFu || chunks > 65535u) return false;
 		use();
 		uint32_t const S = (uint32_t)c.S, W = S + 1, rmax = terra::TM_CELLS/W, bands = (W + rmax - 1)/rmax, R = (W + bands - 1)/bands;
-		hipLaunchKernelGGL(terra::k_tree_ao_sources, dim3(n, chunks ? chunks : 1), dim3(256), 0, stream, c, insts, pine, pine_counts, decid, decid_counts, decid_radius,
+		run(terra::k_tree_ao_sources, dim3(n, chunks ? chunks : 1), dim3(256), 0, c, insts, pine, pine_counts, decid, decid_counts, decid_radius,
 			decid_radius_by_id, src, trmax, updated);
-		hipLaunchKernelGGL(terra::k_tree_ao_gather, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, frames, nbr, flags, trmax, pine_counts, decid_counts, src, tiles, par, list_counts);
-		hipLaunchKernelGGL(terra::k_tree_map, dim3(n, (W + R - 1)/R), dim3(64), 0, stream, tiles, (uint8_t const *)nullptr, par, (int)S, (int)R, 1, map, updated);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
-	}
-	// one workgroup of T threads per tile of a batch of n; false (and no launch) where the driver's simple form is to run
-	template<unsigned T, class K, class... A> bool launch_per_tile(K kernel, uint32_t n, A... args) {
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		hipLaunchKernelGGL(kernel, dim3(n), dim3(T), 0, stream, args...);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_tree_ao_gather, dim3(n), dim3(terra::TREEP_THREADS), 0, c, frames, nbr, flags, trmax, pine_counts, decid_counts, src, tiles, par, list_counts);
+		run(terra::k_tree_map, dim3(n, (W + R - 1)/R), dim3(64), 0, tiles, (uint8_t const *)nullptr, par, (int)S, (int)R, 1, map, updated);
 		return true;
 	}
 	// the tree brush on the record arrays: k_tree_edit once per tile (culls and removal), k_tree_edit_append once per tile after the brush placements, k_tree_edit_finish
@@ -615,21 +565,13 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		uint32_t const *new_pine_counts, terra::tree_place_pod_t *pine, uint32_t *pine_counts, terra::decid_place_pod_t const *new_decid, uint32_t const *new_decid_counts,
 		terra::decid_place_pod_t *decid, uint32_t *decid_counts, float *decid_radius, float const *by_id, float *trmax, uint32_t *box, uint8_t *status)
 	{
-		if (simple_kernels) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_tree_edit_append, dim3(n), dim3(terra::TREEP_THREADS), 0, stream, c, gen_flags, insts, new_pine, new_pine_counts, pine, pine_counts, new_decid,
+		return launch_if(true, terra::k_tree_edit_append, dim3(n), dim3(terra::TREEP_THREADS), c, gen_flags, insts, new_pine, new_pine_counts, pine, pine_counts, new_decid,
 			new_decid_counts, decid, decid_counts, decid_radius, by_id, trmax, box, status);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
 	}
 	bool tile_edit_trees_finish(terra::tree_edit_consts_t const &c, uint32_t n, terra::tree_edit_frame_t const *frames, terra_tile_stats const *stats, uint32_t const *box,
 		uint8_t *status, uint8_t *changed, float *update_bcube)
 	{
-		if (simple_kernels) return false;
-		use();
-		hipLaunchKernelGGL(terra::k_tree_edit_finish, dim3((n + 255)/256), dim3(256), 0, stream, c, n, frames, stats, box, status, changed, update_bcube);
-		TERRA_HIP_CHECK(hipGetLastError());
-		return true;
+		return launch_if(true, terra::k_tree_edit_finish, dim3((n + 255)/256), dim3(256), c, n, frames, stats, box, status, changed, update_bcube);
 	}
 	// tree placement: one workgroup per tile (k_tree_place)
 	bool tile_place_trees(terra::tree_place_consts_t const *c, terra::tile_ref_pod_t const *tiles, uint32_t n, float const *dens, uint8_t const *skip, terra_tile_stats const *stats,
@@ -676,19 +618,18 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		float *dist, uint8_t *lod, uint8_t *crack, uint32_t *draw_order, uint32_t *occluded, uint32_t *counts, uint8_t *not_drawn, terra::terrain_view_occluder_t *occ, uint32_t *nocc, uint8_t *test,
 		float *keys, uint32_t *key_tile)
 	{
-		if (simple_kernels || n > 0x7FFFFFFFu) return false;
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
 		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
-		hipLaunchKernelGGL(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, stream, c, in, tile_xy, n, status, dist, lod, test);
-		hipLaunchKernelGGL(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, stream, c, in, tile_xy, n, status, occ, nocc);
-		hipLaunchKernelGGL(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, stream, c, in, tile_xy, occ, nocc, test, status);
-		hipLaunchKernelGGL(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, stream, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
-		hipLaunchKernelGGL(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, stream, keys, key_tile, counts, draw_order);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c, in, tile_xy, n, status, dist, lod, test);
+		run(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, c, in, tile_xy, n, status, occ, nocc);
+		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c, in, tile_xy, occ, nocc, test, status);
+		run(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
+		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, keys, key_tile, counts, draw_order);
 		return true;
 	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
-		if (simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
+		if (opt->simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;
 		use();
 		// "gen.fused" has no kernel here: glm's 3-D lattice noise picks its gradients by the SIGN of expressions that are exactly zero at some of the hash's 49 / 289 values
@@ -699,23 +640,21 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		size_t const npairs = (nvox / J.nz)*nzp, per_block = (size_t)256*terra::VN_CHUNKS;
 		if ((npairs + per_block - 1)/per_block > 0x7FFFFFFFull) throw std::invalid_argument("voxel_fill: grid too large");
 		dim3 const grid((unsigned)((npairs + per_block - 1)/per_block)), block(256);
-		if (perlin) {hipLaunchKernelGGL(terra::k_voxel_noise<true>, grid, block, 0, stream, out, npairs, nzp, J, lut3);}
-		else        {hipLaunchKernelGGL(terra::k_voxel_noise<false>, grid, block, 0, stream, out, npairs, nzp, J, lut3);}
-		TERRA_HIP_CHECK(hipGetLastError());
+		if (perlin) {run(terra::k_voxel_noise<true>, grid, block, 0, out, npairs, nzp, J, lut3);}
+		else        {run(terra::k_voxel_noise<false>, grid, block, 0, out, npairs, nzp, J, lut3);}
 	}
 	void voxel_sines(float *out, uint32_t nx, uint32_t ny, uint32_t nz, float const *d_tab, float zscale, int normalize, int fused = 0, float fast_amax = 0.0f, float const *d_zt = nullptr, uint32_t nzp = 0) {
-		if (simple_kernels) {voxel_sines_simple(out, nx, ny, nz, d_tab, zscale, normalize, fused); return;}
+		if (opt->simple_kernels) {voxel_sines_simple(out, nx, ny, nz, d_tab, zscale, normalize, fused); return;}
 		use();
 		if (fused && (uint64_t)nx*ny <= 0x7FFFFF00ull) { // "gen.fused": the field as a (columns x 60) x (60 x nz) product on the f32 matrix pipe (terra_fused.hpp)
 			size_t const ncol = (size_t)nx*ny;
 			uint32_t const nyp = (uint32_t)((ncol + 255)/256*256), nxp = (nz + 127)/128*128; // (256: the narrow form of k_sine_grid_h3 walks 256-row tiles)
 			terra::sgf_job_t J; memset(&J, 0, sizeof(J));
-			J.out = out; J.nx = nz; J.ny = (uint32_t)ncol; J.nxp = nxp; J.nyp = nyp; J.ntx = nxp/128; J.nty = nyp/128; J.rowgroup = sg_rowgroup;
+			J.out = out; J.nx = nz; J.ny = (uint32_t)ncol; J.nxp = nxp; J.nyp = nyp; J.ntx = nxp/128; J.nty = nyp/128; J.rowgroup = (unsigned)opt->sg_rowgroup;
 			J.kstart = 0; J.kend = terra::VOX_SINES; J.zscale = zscale; J.normalize = normalize;
 			if (fused == 2 && sine_grid_h3<terra::SGF_VOXELS>(J, 1.0f, fast_amax, d_tab, nx, ny)) return; // TERRA_GEN_FAST (|zv| <= 1; |xv*yv| <= the largest magnitude)
 			size_t const np = (size_t)terra::VOX_SINES*((size_t)nyp + nxp);
-			if (np*4 > vox_p_bytes) {if (vox_p) {sync(); (void)hipFree(vox_p);} TERRA_HIP_CHECK(hipMalloc((void **)&vox_p, np*4)); vox_p_bytes = np*4;}
-			float *const pt = vox_p, *const zt = vox_p + (size_t)terra::VOX_SINES*nyp;
+			float *const pt = (float *)vox_p.grow(*this, np*4), *const zt = pt + (size_t)terra::VOX_SINES*nyp;
 			// PT[k][column] = xv[x][k]*yv[y][k] (the product rounds as in the reference, src/upsurface.cpp:66; only the multiply-add with zv is fused), ZT[k][z]: both k-major, zero padded
 			launch(np, [=] TERRA_LAMBDA (size_t i) {
 				if (i < (size_t)terra::VOX_SINES*nyp) {
@@ -732,23 +671,20 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 			});
 			J.xt = zt; J.yt = pt;
 			unsigned const nb = J.ntx*J.nty, grid = ((nb + 7)/8)*8;
-			hipLaunchKernelGGL(terra::k_sine_grid_mx<terra::SGF_VOXELS>, dim3(std::min(grid, (unsigned)(2*num_cus + 7)/8*8)), dim3(256), 0, stream, J);
-			TERRA_HIP_CHECK(hipGetLastError());
+			run(terra::k_sine_grid_mx<terra::SGF_VOXELS>, dim3(std::min(grid, (unsigned)(2*num_cus + 7)/8*8)), dim3(256), 0, J);
 			return;
 		}
-		if ((nz & 3u) == 0 && vox_cols && d_zt) { // a lane per column, the products in registers, the z table as scalar operands (k_voxel_sines_cols): no P array
+		if ((nz & 3u) == 0 && opt->voxels_cols && d_zt) { // a lane per column, the products in registers, the z table as scalar operands (k_voxel_sines_cols): no P array
 			size_t const ncolc = (size_t)nx*ny;
-			hipLaunchKernelGGL(terra::k_voxel_sines_cols, dim3((unsigned)((ncolc + terra::VC_COLS - 1)/terra::VC_COLS), (nz + terra::VC_Z - 1)/terra::VC_Z), dim3(256), 0, stream, out, nx, ny, nz, nzp, d_tab, d_zt, zscale, normalize);
-			TERRA_HIP_CHECK(hipGetLastError());
+			run(terra::k_voxel_sines_cols, dim3((unsigned)((ncolc + terra::VC_COLS - 1)/terra::VC_COLS), (nz + terra::VC_Z - 1)/terra::VC_Z), dim3(256), 0, out, nx, ny, nz, nzp, d_tab, d_zt, zscale, normalize);
 			return;
 		}
 		size_t const ncol2 = ((size_t)nx*ny + 1) & ~(size_t)1, np = (ncol2/2)*terra::VX_PSTRIDE + (size_t)nz*terra::VOX_SINES, nprod = (ncol2 + nz)*terra::VOX_SINES; // column pairs + transposed z table
-		if (np*4 > vox_p_bytes) {if (vox_p) {sync(); (void)hipFree(vox_p);} TERRA_HIP_CHECK(hipMalloc((void **)&vox_p, np*4)); vox_p_bytes = np*4;}
-		hipLaunchKernelGGL(terra::k_voxel_P, dim3((unsigned)((nprod + 255)/256)), dim3(256), 0, stream, vox_p, vox_p + (ncol2/2)*terra::VX_PSTRIDE, nx, ny, nz, d_tab);
+		float *const vp = (float *)vox_p.grow(*this, np*4), *const vz = vp + (ncol2/2)*terra::VX_PSTRIDE; // the products, the transposed z table behind them
+		run(terra::k_voxel_P, dim3((unsigned)((nprod + 255)/256)), dim3(256), 0, vp, vz, nx, ny, nz, d_tab);
 		unsigned const block = (nz >= 256) ? 256 : ((nz + 63)/64)*64;
 		size_t const ncol = (size_t)nx*ny;
-		hipLaunchKernelGGL(terra::k_voxel_sines, dim3((unsigned)((ncol + terra::VX_PER_BLOCK - 1)/terra::VX_PER_BLOCK), (nz + block - 1)/block), dim3(block), 0, stream, out, nx, ny, nz, vox_p + (ncol2/2)*terra::VX_PSTRIDE, vox_p, zscale, normalize);
-		TERRA_HIP_CHECK(hipGetLastError());
+		run(terra::k_voxel_sines, dim3((unsigned)((ncol + terra::VX_PER_BLOCK - 1)/terra::VX_PER_BLOCK), (nz + block - 1)/block), dim3(block), 0, out, nx, ny, nz, vz, vp, zscale, normalize);
 	}
 };
 typedef hip_backend_t terra_backend_t;

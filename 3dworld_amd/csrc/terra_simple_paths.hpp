@@ -8,6 +8,9 @@ namespace terra {
 
 template<class DERIVED> struct simple_paths {
 	DERIVED &self() {return *static_cast<DERIVED *>(this);}
+	// has the backend kernels of its own for the tile passes (bool tile_*() hooks that the driver tries before its one-thread-per-tile forms)?  Not unless it says so:
+	// the HIP backend does; for a backend that is only these paths (the emulator) the driver does not instantiate the calls
+	static constexpr bool has_kernels = false;
 
 	void sine_grid_simple(grid_job_t const &job, noise_consts_t const &nc, sin_lut_t const &L, float const *xt, float const *yt, float const *smx, float const *smy, float *out) {
 		uint32_t const y0 = job_window_first(job), y1 = job_window_end(job); // (grid_job_t::ty0, tyn: the rows of the job's window, all of them by default)
@@ -157,46 +160,6 @@ template<class DERIVED> struct simple_paths {
 	void tile_post_pass(uint32_t n, tile_ref_pod_t const *d_refs, float const *d_zvals, terra_tile_stats *d_stats, uint8_t *d_normals, float *d_min_nz,
 		float wpz_max, float rad_c, float dxv, float dyv, float dxy, uint32_t S) {tile_post_simple(n, d_refs, d_zvals, d_stats, d_normals, d_min_nz, wpz_max, rad_c, dxv, dyv, dxy, S);}
 	void tile_ao_pass(uint32_t n, float const *d_zvals, float const *d_ctx, uint8_t *d_ao, float dz, bool own, uint32_t S) {tile_ao_simple(n, d_zvals, d_ctx, d_ao, dz, own, S);}
-	// the grass brush's kernels: none here -- the driver (tiles_edit_grass_dev) then runs its per-texel / per-block / per-tile form
-	bool tile_edit_grass(grass_brush_consts_t const &, landscape_consts_t const &, tile_ref_pod_t const *, uint32_t, float const *, terra_tile_stats const *, uint8_t const *,
-		float const *, uint32_t *, grass_block_pod_t *, uint8_t *, uint8_t *, uint32_t *) {return false;}
-	// the line queries' kernels: none here -- the driver (tiles_line_intersect_dev) then runs its one-thread-per-line form
-	bool tile_line_intersect(line_query_consts_t const &, tile_ref_pod_t const *, uint32_t, float const *, terra_tile_stats const *, uint8_t const *, line_box_t *,
-		float const *, int32_t const *, uint32_t, line_hit_pod_t *) {return false;}
-	// the tree map's, the shadow texture's and the tree weights' kernels: none here -- the driver (tiles_tree_map_dev, tiles_shadow_texture_dev, tiles_tree_weights_dev)
-	// then runs its per-row / per-texel forms
-	bool tile_tree_map(tree_tile_pod_t const *, uint32_t, uint32_t, uint8_t const *, tree_splat_in_t const *, uint32_t, tree_splat_pod_t *, float, float, bool, uint16_t *, uint8_t *) {return false;}
-	bool tile_shadow_texture(shadow_tex_consts_t const &, uint32_t, uint32_t, uint8_t const *, uint8_t const *, uint8_t const *, uint16_t const *, uint32_t *) {return false;}
-	bool tile_tree_weights(size_t, uint32_t const *, uint8_t const *, uint32_t *) {return false;}
-	// the tree AO shadows' kernels: none here -- the driver (tiles_tree_ao_shadows_dev) then runs its one-thread-per-tile forms and the tree map's per-row form
-	bool tile_tree_ao(tree_ao_consts_t const &, uint32_t, tree_inst_pod_t const *, tree_place_pod_t const *, uint32_t const *, decid_place_pod_t const *, uint32_t const *,
-		float const *, float const *, uint8_t const *, tree_frame_t const *, int32_t const *, tree_splat_in_t *, float *, tree_tile_pod_t *, tree_splat_pod_t *, uint32_t *,
-		uint16_t *, uint8_t *) {return false;}
-	// the tree brush's kernels: none here -- the driver (tiles_edit_trees_dev) then runs its one-thread-per-tile forms, the removal as the literal remove_element loop
-	bool tile_edit_trees(tree_edit_consts_t const &, uint32_t, tree_edit_frame_t const *, terra_tile_stats const *, tree_inst_pod_t const *, tree_place_pod_t *, uint32_t *,
-		decid_place_pod_t *, uint32_t *, float *, float const *, float const *, uint32_t *, uint32_t *, uint8_t *, uint8_t const *, uint8_t const *, uint8_t *) {return false;}
-	bool tile_edit_trees_append(tree_edit_consts_t const &, uint32_t, uint8_t const *, tree_inst_pod_t const *, tree_place_pod_t const *, uint32_t const *, tree_place_pod_t *,
-		uint32_t *, decid_place_pod_t const *, uint32_t const *, decid_place_pod_t *, uint32_t *, float *, float const *, float *, uint32_t *, uint8_t *) {return false;}
-	bool tile_edit_trees_finish(tree_edit_consts_t const &, uint32_t, tree_edit_frame_t const *, terra_tile_stats const *, uint32_t const *, uint8_t *, uint8_t *, float *) {return false;}
-	// tree placement's kernel: none here -- the driver (tiles_place_trees_dev) then runs its one-thread-per-tile form
-	bool tile_place_trees(tree_place_consts_t const *, tile_ref_pod_t const *, uint32_t, float const *, uint8_t const *, terra_tile_stats const *, uint32_t, tree_place_pod_t *, uint32_t *) {return false;}
-	// deciduous placement's kernel: none here -- the driver (tiles_place_decid_trees_dev) then runs its one-thread-per-tile form
-	bool tile_place_decid_trees(decid_place_consts_t const *, tile_ref_pod_t const *, uint32_t, float const *, uint8_t const *, terra_tile_stats const *, float const *, uint32_t,
-		decid_place_pod_t *, uint32_t *) {return false;}
-	// scenery placement's kernel: none here -- the driver (tiles_place_scenery_dev) then runs its one-thread-per-tile form
-	bool tile_place_scenery(scenery_place_consts_t const *, tile_ref_pod_t const *, uint32_t, float const *, uint8_t const *, uint32_t, scenery_place_pod_t *, uint32_t *, uint32_t *) {return false;}
-	// the flowers' kernels: none here -- the driver (tiles_place_flowers_dev, tiles_edit_flowers_dev) then runs its one-thread-per-tile forms: the reference's cell loop
-	// with one generator through the tile, the removal as the literal remove_element loop
-	bool tile_place_flowers(flower_consts_t const &, tile_ref_pod_t const *, uint32_t, uint8_t const *, uint8_t const *, float const *, float const *, uint32_t, flower_pod_t *,
-		uint32_t *, uint32_t *) {return false;}
-	bool tile_edit_flowers(flower_edit_consts_t const &, tile_ref_pod_t const *, uint32_t, uint8_t const *, uint8_t const *, uint32_t const *, uint8_t const *, float const *,
-		float const *, uint32_t, flower_pod_t *, uint32_t *, uint32_t *, uint8_t *, uint32_t *, uint8_t *) {return false;}
-	// the grass view's kernel: none here -- the driver (tiles_grass_view_dev) then runs its one-thread-per-tile form, the reference's loops
-	bool tile_grass_view(grass_view_consts_t const &, int32_t const *, uint32_t, float const *, terra_tile_stats const *, grass_block_pod_t const *, uint8_t const *, uint32_t,
-		float *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint16_t *) {return false;}
-	// the terrain view's kernels: none here -- the driver (tiles_terrain_view_dev) then runs its one-thread-per-tile form, the reference's loops
-	bool tile_terrain_view(terrain_view_consts_t const &, terrain_view_in_t const &, int32_t const *, int32_t const *, uint32_t, uint8_t *, float *, uint8_t *, uint8_t *, uint32_t *,
-		uint32_t *, uint32_t *, uint8_t *, terrain_view_occluder_t *, uint32_t *, uint8_t *, float *, uint32_t *) {return false;}
 	// tile erosion, wave form: the clamp-padded copies live in HBM/L2, ONE WAVE per tile walks the droplets in order through a 32x32 LDS window
 	// (10 KB of LDS per tile instead of 76 KB: ~15 tiles per CU in flight instead of 2)
 	void tile_erosion_windowed(uint32_t n, float *zvals, erosion_consts_t const &ec, uint32_t iters, float *padded /* n*NX*NY */) {

@@ -1,4 +1,5 @@
 // terra_stage.hpp -- host-only plumbing of the driver and of the host-pointer entry points: how several arrays share one grow-only device scratch buffer.
+//   dev_buf_t       the one grow-only device buffer: grow(backend, bytes), drop(backend)
 //   stage_up        the one rounding: every carved array starts on a 256-byte boundary
 //   stage_layout_t  a running offset: add(pointer, count) hands out the next array, `total` is what the buffer must hold, bind(base) sets the pointers
 //   host_stage_t    the device copies of a host-pointer entry point's arrays: declare, begin() (upload), dev<T>(), end() (download)
@@ -10,6 +11,20 @@
 #include <string.h>
 
 namespace terra {
+
+// A device buffer that only grows.  grow() of no more than it holds hands back what it holds; otherwise the old allocation goes first (after a sync: kernels in flight may
+// still use it) and the buffer is empty while the new one is made, so an allocation that throws leaves an empty buffer, not a stale pointer or size.
+// BE: anything with sync(), alloc(bytes) and free(pointer).
+struct dev_buf_t {
+	void *p = nullptr; size_t bytes = 0;
+	template<class BE> void *grow(BE &be, size_t want) {
+		if (want <= bytes) return p;
+		if (p) {be.sync(); drop(be);}
+		p = be.alloc(want); bytes = want;
+		return p;
+	}
+	template<class BE> void drop(BE &be) {if (p) {void *const q = p; p = nullptr; bytes = 0; be.free(q);}}
+};
 
 inline size_t stage_up(size_t bytes) {return (bytes + 255) & ~(size_t)255;}
 

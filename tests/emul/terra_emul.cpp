@@ -89,7 +89,6 @@ struct cpu_backend_t : terra::simple_paths<cpu_backend_t> {
 
 	bool sine_grid(terra::grid_job_t const &job, terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float const *xt, float const *yt, float const *smx, float const *smy, float *out, uint32_t *) {sine_grid_simple(job, nc, L, xt, yt, smx, smy, out); return false;}
 	bool noise_grid(terra::grid_job_t const &job, terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float const *smx, float const *smy, float *out, uint32_t *, uint32_t const *) {noise_grid_simple(job, nc, L, smx, smy, out); return false;}
-	bool tile_band_ok(uint32_t, uint32_t, uint32_t, uint32_t, bool, bool, int) const {return false;} // (the per-cell path evaluates whole squares)
 	void tile_grid(uint32_t n, terra::tile_ref_pod_t const *refs, uint32_t nux, uint32_t nuy, float const *xt, float const *yt, uint32_t nxpv, uint32_t nypv, float const *d_sm, float const *d_m0, int md, int shp, int kstart, bool use_sm, float so,
 		terra::noise_consts_t const &nc, terra::sin_lut_t const &L, float dxv, float dyv, float *zvals, bool /*plain_only*/, uint32_t tw, bool /*unique_tiles*/, bool glaciate = true, uint32_t const * = nullptr, int fused = 0, float = 0.0f, terra::tile_band_t const * = nullptr) {tile_grid_simple(n, refs, nux, nuy, xt, yt, nxpv, nypv, d_sm, d_m0, md, shp, kstart, use_sm, so, nc, L, dxv, dyv, zvals, tw, glaciate, fused);}
 	void tile_erosion(uint32_t n, float *zvals, terra::erosion_consts_t const &ec, uint32_t iters) {
@@ -111,8 +110,6 @@ struct cpu_backend_t : terra::simple_paths<cpu_backend_t> {
 	}
 	void minmax(float const *vals, size_t n, uint32_t *d) {minmax_simple(vals, n, d);}
 	void quantize16(float const *vals, size_t n, float val_add, float val_div, uint8_t *pix) {quantize16_simple(vals, n, val_add, val_div, pix);}
-	bool tile_shadows_flow(terra::shadow_consts_t const &, uint32_t, uint32_t, uint32_t const *, int32_t const *, float const *, unsigned long long *, uint8_t *, uint32_t, uint32_t *) {return false;} // (level by level)
-	bool tile_weights(terra::landscape_consts_t const &, terra::tile_ref_pod_t const *, uint32_t, float const *, float const *, float const *, uint32_t *, terra::grass_block_pod_t *, uint8_t *) {return false;} // (the per-texel form)
 	// the pair evaluation of the HIP kernel (k_voxel_noise) over the same table, serially: columns x (z, z + 1) pairs
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool /*fused: the exact values are within every tolerance*/, uint32_t const *lut3) {
 		size_t const ncol = nvox / J.nz;

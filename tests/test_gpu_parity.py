@@ -451,6 +451,78 @@ def test_experiment_knobs_never_change_a_result(pkg, orc, monkeypatch, env):
         t.close()
 
 
+def _release_then_reuse(t, what, call, small, large, check):
+    """call(small), release_scratch(), call(small) again: the same bits, and the oracle's (check); then, after another release, call(large): a size that survived its
+    pointer would hand out a null or too small buffer"""
+    first = call(small)
+    t.release_scratch()
+    again = call(small)
+    for a, b in zip(first, again):
+        assert bytes(a) == bytes(b), f"{what}: the call after release_scratch differs from the one before"  # (the arrays' raw bytes)
+    check(small, again)
+    t.release_scratch()
+    check(large, call(large))
+
+
+def test_release_scratch_then_reuse(pkg, gpu, orc):
+    """terra_release_scratch hands back every grow-only buffer of the context, the backend's six included, and each grows again on demand: per backend buffer the
+    smallest call that allocates it, before and after a release, and a larger one after a release.
+    h3_tab: a TERRA_GEN_FAST sine grid.  tile_map + tile_acc: a dense batch at S = 16 with stats and normals (the one-launch tile grid, k_tile_post_sized).  tile_order:
+    more than 512 tiles with n*iters >= 65536 (the erosion launch order).  tile_pad: option "tile_erosion" = "window".  vox_p: a voxel sine field whose depth is no
+    multiple of 4 (the P-array kernel)."""
+    import tile_size_model as tsm
+    t, S = gpu, 16
+    # ---- h3_tab: within the tolerance of the mode (parity_cases.case_fast_mode)
+    pc_, oc = pc.cfg_pair(pkg, mesh_gen_mode=0)
+    st = t.init_scene(pc_); orc.init(oc)
+    tol = pc.FUSED_REL_TOL*float(st.zmax_est)
+
+    def fast_grid(dims):
+        return (t.gen_grid(-0.37*dims[0], 11.0 - dims[1], st.DX_VAL, st.DY_VAL, dims[0], dims[1], pkg.GEN_GLACIATE | pkg.GEN_FAST),)
+
+    def check_grid(dims, out):
+        exact = orc.gen_grid(-0.37*dims[0], 11.0 - dims[1], st.DX_VAL, st.DY_VAL, dims[0], dims[1], 1)
+        d = float(np.abs(out[0].astype(np.float64) - exact).max())
+        assert d <= tol, (dims, d, tol)
+    _release_then_reuse(t, "h3_tab", fast_grid, (300, 300), (520, 300), check_grid)
+    # ---- vox_p: bit for bit (parity_cases.case_voxels_vs_oracle)
+    vox_args = lambda dims: (*dims, pc.VOX["lo"], pc.VOX["vsz"], pc.VOX["off"], 0.8, 1.3, 7, 9, 0, -0.02, 0)  # noqa: E731
+    _release_then_reuse(t, "vox_p", lambda dims: (t.voxel_fill(*vox_args(dims)),), (8, 8, 6), (16, 8, 6),
+                        lambda dims, out: assert_bit_equal(orc.voxel_fill(*vox_args(dims)), out[0], f"voxels {dims}"))
+    # ---- the tile passes at S = 16, against the size-general model of the reference's tile (tests/tile_size_model.py)
+    t.init_scene(pkg.make_config(mesh_gen_mode=0, mesh_xy=S)); orc.init(orclib.make_config(mesh_gen_mode=0, mesh_xy=S))
+    assert t.tile_size == S
+    block = lambda w, h: [(x, y) for y in range(-(h // 2), h - h // 2) for x in range(-(w // 2), w - w // 2)]  # noqa: E731
+
+    def tiles_call(iters):
+        def call(tiles):
+            z, stt, nm, mnz = t.tiles_create_zvals(tiles, iters)
+            return z, bytes(stt), nm, mnz
+        return call
+
+    def tiles_check(iters, sample):
+        def check(tiles, out):
+            z, stt, nm, mnz = out
+            for i in sample(len(tiles)):
+                tx, ty = tiles[i]
+                zm = tsm.tile_zvals(orc, S, tx, ty, iters)
+                assert_bit_equal(zm, z[i], f"zvals tile {tx},{ty} of {len(tiles)}, {iters} droplets")
+                nb = len(stt)//len(tiles)
+                assert stt[i*nb:(i + 1)*nb] == tsm.stats_bytes(tsm.tile_stats(orc, S, tx, ty, zm)), f"stats tile {tx},{ty}"
+                nmm, mm = tsm.tile_normals(orc, S, zm)
+                assert (nm[i] == nmm).all() and np.float32(mnz[i]).view(np.uint32) == np.float32(mm).view(np.uint32), f"normals tile {tx},{ty}"
+        return check
+    every = lambda n: range(n)  # noqa: E731
+    some = lambda n: (0, 1, n//3, n//2 + 7, n - 2, n - 1)  # noqa: E731
+    _release_then_reuse(t, "tile_map + tile_acc", tiles_call(0), block(3, 3), block(5, 5), tiles_check(0, every))
+    _release_then_reuse(t, "tile_order", tiles_call(128), block(26, 20), block(30, 20), tiles_check(128, some))  # 520 and 600 tiles: n > 512, n*iters >= 65536
+    t.set_option("tile_erosion", "window")
+    try:
+        _release_then_reuse(t, "tile_pad", tiles_call(50), block(2, 1), block(3, 2), tiles_check(50, every))
+    finally:
+        t.set_option("tile_erosion", "lds")
+
+
 def test_overlapped_download_equals_synchronous(pkg, gpu, orc):
     pc.case_big_transfers(pkg, gpu, orc)
 
