@@ -981,6 +981,58 @@ int terra_tiles_terrain_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 		if (h_counts[1]) {ctx->eng.be.d2h(h_occluded, st.dev<uint32_t>(oc), (size_t)std::min(h_counts[1], n)*4);}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_tree_view_args) == sizeof(terra::tree_view_args_pod_t) && sizeof(terra_tree_view_args) == 32, "terra_tree_view_args layout");
+static_assert(sizeof(terra_tree_view_tile) == sizeof(terra::tree_view_tile_pod_t) && sizeof(terra_tree_view_tile) == 32, "terra_tree_view_tile layout");
+static_assert(sizeof(terra_tree_view_inst) == sizeof(terra::tree_view_inst_pod_t) && sizeof(terra_tree_view_inst) == 16, "terra_tree_view_inst layout");
+static_assert(sizeof(terra_trunk_override) == sizeof(terra::trunk_override_pod_t) && sizeof(terra_trunk_override) == 36, "terra_trunk_override layout");
+int terra_tiles_tree_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                              const terra_tree_view_args *args, const terra_tile_stats *d_stats, const uint8_t *d_skip, const float *d_trmax, const terra_tree_place *d_pine,
+                              const uint32_t *d_pine_counts, uint32_t capacity, const terra_trunk_override *d_trunk_override, terra_tree_view_tile *d_tile_out,
+                              float *d_all_bcube, terra_tree_view_inst *d_pine_insts, terra_tree_view_inst *d_palm_insts, uint32_t *d_inst_counts, uint32_t *d_leaf_list,
+                              uint32_t *d_leaf_counts, uint8_t *d_trunk) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::tree_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY ctx->eng.tiles_tree_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, d_stats, d_skip, d_trmax, (terra::tree_place_pod_t const *)d_pine, d_pine_counts, capacity,
+		(terra::trunk_override_pod_t const *)d_trunk_override, (terra::tree_view_tile_pod_t *)d_tile_out, d_all_bcube, (terra::tree_view_inst_pod_t *)d_pine_insts,
+		(terra::tree_view_inst_pod_t *)d_palm_insts, d_inst_counts, d_leaf_list, d_leaf_counts, d_trunk); TERRA_CATCH
+}
+int terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                          const terra_tree_view_args *args, const terra_tile_stats *h_stats, const uint8_t *h_skip, const float *h_trmax, const terra_tree_place *h_pine,
+                          const uint32_t *h_pine_counts, uint32_t capacity, const terra_trunk_override *h_trunk_override, terra_tree_view_tile *h_tile_out,
+                          float *h_all_bcube, terra_tree_view_inst *h_pine_insts, terra_tree_view_inst *h_palm_insts, uint32_t *h_inst_counts, uint32_t *h_leaf_list,
+                          uint32_t *h_leaf_counts, uint8_t *h_trunk) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::tree_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.tree_view_check(v, a); // the scene, the tile size, the view, the args and the instance table: before anything is staged
+		if ((uint64_t)n*capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_tree_view: n*capacity must fit 32 bits");
+		if (n == 0) return TERRA_OK;
+		if (!tile_xy || !h_stats || !h_pine_counts || !h_tile_out || !h_all_bcube || !h_inst_counts || !h_leaf_counts ||
+		    (capacity && (!h_pine || !h_pine_insts || !h_palm_insts || !h_leaf_list || !h_trunk))) return terra::fail(TERRA_ERR_ARG, "null argument");
+		typedef terra::tree_view_inst_pod_t inst_t;
+		size_t const nc = (size_t)n*capacity;
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), sk = st.opt_in(h_skip, n), tr = st.opt_in(h_trmax, (size_t)n*4), p = st.in(h_pine, nc*sizeof(terra_tree_place)),
+			pc = st.in(h_pine_counts, (size_t)n*4), ov = st.opt_in(h_trunk_override, nc*sizeof(terra_trunk_override)), to = st.out(h_tile_out, (size_t)n*sizeof(terra_tree_view_tile)),
+			bc = st.out(h_all_bcube, (size_t)n*24), pi = st.temp(nc*sizeof(inst_t)), mi = st.temp(nc*sizeof(inst_t)), ic = st.out(h_inst_counts, (size_t)n*8), ll = st.temp(nc*4),
+			lc = st.out(h_leaf_counts, (size_t)n*8), tk = st.temp(nc);
+		st.begin();
+		ctx->eng.tiles_tree_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, st.dev<terra_tile_stats>(s), st.dev<uint8_t>(sk), st.dev<float>(tr), st.dev<terra::tree_place_pod_t>(p),
+			st.dev<uint32_t>(pc), capacity, st.dev<terra::trunk_override_pod_t>(ov), st.dev<terra::tree_view_tile_pod_t>(to), st.dev<float>(bc), st.dev<inst_t>(pi), st.dev<inst_t>(mi),
+			st.dev<uint32_t>(ic), st.dev<uint32_t>(ll), st.dev<uint32_t>(lc), st.dev<uint8_t>(tk));
+		st.end();
+		for (uint32_t t = 0; t < n; ++t) { // of every tile only what the counts name: the rest of the caller's arrays stays as it was
+			size_t const o = (size_t)t*capacity;
+			uint32_t const np = std::min(h_inst_counts[2*t], capacity), nm = std::min(h_inst_counts[2*t + 1], capacity), nl = std::min(h_tile_out[t].leaf_written, capacity);
+			if (np) {ctx->eng.be.d2h(h_pine_insts + o, st.dev<inst_t>(pi) + o, (size_t)np*sizeof(inst_t));}
+			if (nm) {ctx->eng.be.d2h(h_palm_insts + o, st.dev<inst_t>(mi) + o, (size_t)nm*sizeof(inst_t));}
+			if (nl) {ctx->eng.be.d2h(h_leaf_list + o, st.dev<uint32_t>(ll) + o, (size_t)nl*4);}
+			if (h_tile_out[t].num_trees) {ctx->eng.be.d2h(h_trunk + o, st.dev<uint8_t>(tk) + o, std::min(h_pine_counts[t], capacity));}
+		}
+	TERRA_CATCH
+}
 int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
 	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.set_tree_size_params(*params); TERRA_CATCH

@@ -21,6 +21,7 @@
 #include "terra_terrainview.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
+#include "terra_treeview.hpp"
 #include "terra_stage.hpp"
 #include "../../include/terra.h"
 #include <vector>
@@ -3196,6 +3197,121 @@ template<class BE> struct terra_engine {
 				for (uint32_t u = 0; u < n; ++u) {uint32_t const su = d_status[u] & TV_STATUS_MASK; nd += (su == TV_DRAWN) ? 1u : 0u; no += (su == TV_OCCLUDED) ? 1u : 0u;}
 				d_counts[0] = nd; d_counts[1] = no;
 			}
+		});
+	}
+
+	// ---- the pine and palm tree draw lists of a batch for a camera (terra_treeview.hpp): tile_t::draw_pine_trees (src/tiled_mesh.cpp:1465-1526) with
+	// small_tree_group's draw_tree_insts, draw_pine_leaves, draw_non_pine_leaves and draw_trunks under it, over the records as the placement and the brush keep them.
+	// The checks that need no array (the host form runs them before it stages anything):
+	void tree_view_check(view_pod_t const &view, tree_view_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_tree_view: a member of the view is not finite");
+		if (!isfinite(a.behind_sphere_mult) || !isfinite(a.zoom_f) || !isfinite(a.tree_depth_scale)) throw std::invalid_argument("tiles_tree_view: a member of the args is not finite");
+		if (!tree_view_args_ok(a)) throw std::invalid_argument("tiles_tree_view: window_width, zoom_f and tree_depth_scale must be finite and > 0");
+		if (tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
+			throw std::invalid_argument("tiles_tree_view: instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
+		}
+	}
+	void tiles_tree_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, tree_view_args_pod_t const &a,
+		terra_tile_stats const *d_stats, uint8_t const *d_skip, float const *d_trmax, tree_place_pod_t const *d_pine, uint32_t const *d_counts, uint32_t capacity,
+		trunk_override_pod_t const *d_ov, tree_view_tile_pod_t *d_tile_out, float *d_bcube, tree_view_inst_pod_t *d_pine_insts, tree_view_inst_pod_t *d_palm_insts,
+		uint32_t *d_inst_counts, uint32_t *d_leaf_list, uint32_t *d_leaf_counts, uint8_t *d_trunk)
+	{
+		tree_view_check(view, a);
+		if ((uint64_t)n*capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_tree_view: n*capacity must fit 32 bits");
+		if (n == 0) return;
+		if (!tile_xy || !d_stats || !d_counts || !d_tile_out || !d_bcube || !d_inst_counts || !d_leaf_counts || (capacity && (!d_pine || !d_pine_insts || !d_palm_insts || !d_leaf_list || !d_trunk))) {
+			throw std::invalid_argument("tiles_tree_view: null argument");
+		}
+		if ((((uintptr_t)d_stats | (uintptr_t)d_trmax | (uintptr_t)d_pine | (uintptr_t)d_counts | (uintptr_t)d_ov | (uintptr_t)d_tile_out | (uintptr_t)d_bcube | (uintptr_t)d_pine_insts |
+		      (uintptr_t)d_palm_insts | (uintptr_t)d_inst_counts | (uintptr_t)d_leaf_list | (uintptr_t)d_leaf_counts) & 3u) != 0) {
+			throw std::invalid_argument("tiles_tree_view: every array but skip and trunk must be 4-byte aligned");
+		}
+		tree_ao_consts_t ac;
+		ac.hs = tsp.tree_height_scale*tsp.sm_tree_scale; ac.pine_radius_scale = tsp.pine_tree_radius_scale; ac.tree_scale = tp.tree_scale;
+		ac.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
+		ac.dxv = DX_VAL; ac.dyv = DY_VAL; ac.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; ac.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // ptree_off.get_xlate()
+		ac.S = (int)tile_size(); ac.instanced = tp.instanced ? 1 : 0; ac.num_insts = (uint32_t)tree_insts.size(); ac.num_shared = 0;
+		ac.pine_cap = capacity; ac.decid_cap = 0; ac.list_cap = 0; ac.src_cap = capacity;
+		tree_view_consts_t const c = tree_view_consts(view, a, ac, cfg.scene_x, cfg.scene_y, dxoff, dyoff, capacity);
+		// scratch: the coordinates; for a capacity beyond what k_tree_view ranks in LDS, a tile's (key, record) pairs
+		int32_t *d_txy_w; uint32_t *d_keys;
+		stage_layout_t lay;
+		lay.add(d_txy_w, (size_t)n*2); lay.add(d_keys, (capacity > TREE_VIEW_LDS_KEYS) ? (size_t)n*capacity*2 : 0);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy_w, tile_xy, (size_t)n*8);
+		int32_t const *d_txy = d_txy_w;
+		tree_inst_pod_t const *d_insts = tp.instanced ? tree_insts_dev() : nullptr;
+		if constexpr (BE::has_kernels) {
+			if (be.tile_tree_view(c, d_txy, n, d_insts, d_stats, d_skip, d_trmax, d_pine, d_counts, d_ov, d_tile_out, d_bcube, d_pine_insts, d_palm_insts, d_inst_counts, d_leaf_list,
+				d_leaf_counts, d_trunk, d_keys)) return;
+		}
+		// the simple form: a logical thread per tile walks its records in the reference's order
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint32_t const cnt = (d_skip && d_skip[t]) ? 0u : min_u32(d_counts[t], c.cap);
+			tree_place_pod_t const *const recs = d_pine + t*c.cap;
+			trunk_override_pod_t const *const ovs = d_ov ? d_ov + t*c.cap : nullptr;
+			// calc_bcube, num_pine_trees, num_palm_trees
+			float bc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+			bool any = false;
+			uint32_t nvalid = 0, np = 0, npalm = 0;
+			tree_view_rec_t rec;
+			for (uint32_t j = 0; j < cnt; ++j) {
+				if (!tree_view_record(c, d_insts, recs[j], ovs ? ovs + j : nullptr, rec)) continue;
+				++nvalid; np += is_pine_tree_type(rec.type) ? 1u : 0u; npalm += (rec.type == T_PALM) ? 1u : 0u;
+				float d[6];
+				if (!tree_view_bounds(rec, d)) continue;
+				if (!any) {for (int k = 0; k < 6; ++k) {bc[k] = d[k];} any = true;}
+				else {for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], d[k]); bc[k + 1] = max_std(bc[k + 1], d[k + 1]);}}
+			}
+			for (int k = 0; k < 6; ++k) {d_bcube[t*6 + k] = bc[k];}
+			if (nvalid == 0) { // skipped, or pine_trees.empty() (:1468)
+				tree_view_tile_pod_t z; z.dscale = 0.0f; z.weight = 0.0f; z.flags = 0u; z.num_pine = z.num_palm = z.num_trees = z.leaf_written = z.pad = 0u;
+				d_tile_out[t] = z; d_inst_counts[2*t] = d_inst_counts[2*t + 1] = 0u; d_leaf_counts[2*t] = d_leaf_counts[2*t + 1] = 0u;
+				return;
+			}
+			tree_view_tile_t tl = tree_view_tile(c, d_txy[2*t], d_txy[2*t + 1], d_stats[t], d_trmax ? d_trmax[t] : 0.0f, nvalid, np, npalm, bc);
+			tree_view_inst_pod_t *const pi = d_pine_insts + t*c.cap, *const mi = d_palm_insts + t*c.cap;
+			uint32_t *const ll = d_leaf_list + t*c.cap;
+			uint32_t npi = 0, nmi = 0, nl = 0, nm = 0;
+			bool skipped = false;
+			bool const need_vis = (tl.pine_insts && !tl.draw_all_near) || (tl.palm_insts && !tl.all_visible) || tl.pine_list;
+			for (uint32_t j = 0; j < cnt; ++j) {
+				bool const valid = tree_view_record(c, d_insts, recs[j], ovs ? ovs + j : nullptr, rec);
+				uint8_t const b = (valid && tl.trunks) ? tree_view_trunk(c, rec, tl.all_visible != 0) : (uint8_t)0;
+				d_trunk[t*c.cap + j] = b; skipped = skipped || b == 1;
+				if (!valid) continue;
+				bool const pine = is_pine_tree_type(rec.type), palm = rec.type == T_PALM;
+				bool const vis = need_vis && tree_view_leaves_visible(c, rec);
+				int32_t const id = recs[j].inst;
+				auto insert = [&](tree_view_inst_pod_t *out, uint32_t &m) { // where sort(insts) puts it: behind every entry with an id that is not larger
+					uint32_t k = m++;
+					for (; k > 0 && out[k - 1].id > (uint32_t)id; --k) {out[k] = out[k - 1];}
+					out[k].id = (uint32_t)id; for (int q = 0; q < 3; ++q) {out[k].pt[q] = rec.pos[q];}
+				};
+				if (tl.pine_insts && pine && id >= 0 && (tl.draw_all_near || vis)) {insert(pi, npi);}
+				if (tl.palm_insts && palm && id >= 0 && (tl.all_visible || vis)) {insert(mi, nmi);}
+				if (tl.pine_list && pine && vis) {
+					uint32_t k = nl++;
+					if (tl.pine_sorted) { // get_back_to_front_ordering: ascending (p2p_dist_sq, index)
+						float const key = tree_view_sort_key(c, rec.pos);
+						for (; k > 0 && tree_view_before_f(key, j, tree_view_sort_key(c, recs[ll[k - 1]].pos), ll[k - 1]); --k) {ll[k] = ll[k - 1];}
+					}
+					ll[k] = j;
+				}
+			}
+			if (tl.palm_list) { // draw_non_pine_leaves(0, 1, 0, ..): behind the pine entries
+				for (uint32_t j = 0; j < cnt; ++j) {
+					if (!tree_view_record(c, d_insts, recs[j], ovs ? ovs + j : nullptr, rec) || rec.type != T_PALM || !tree_view_leaves_visible(c, rec)) continue;
+					ll[nl + nm++] = j;
+				}
+			}
+			if (skipped) {tl.out.flags = (tl.out.flags & ~(uint32_t)TRV_TRUNK_MASK) | TRV_TRUNK_POLY_SKIPPED;}
+			tl.out.leaf_written = nl + nm;
+			d_tile_out[t] = tl.out;
+			d_inst_counts[2*t] = npi; d_inst_counts[2*t + 1] = nmi;
+			d_leaf_counts[2*t] = tl.pine_list ? nl : tree_view_render_all(c, tl); d_leaf_counts[2*t + 1] = nm;
 		});
 	}
 

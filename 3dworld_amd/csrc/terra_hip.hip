@@ -628,6 +628,14 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, keys, key_tile, counts, draw_order);
 		return true;
 	}
+	// the pine and palm tree draw lists for a camera: one workgroup per tile (k_tree_view)
+	bool tile_tree_view(terra::tree_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra::tree_inst_pod_t const *insts, terra_tile_stats const *stats, uint8_t const *skip,
+		float const *trmax, terra::tree_place_pod_t const *pine, uint32_t const *counts, terra::trunk_override_pod_t const *ov, terra::tree_view_tile_pod_t *tile_out, float *bcube,
+		terra::tree_view_inst_pod_t *pine_insts, terra::tree_view_inst_pod_t *palm_insts, uint32_t *inst_counts, uint32_t *leaf_list, uint32_t *leaf_counts, uint8_t *trunk, uint32_t *keys)
+	{
+		return launch_per_tile<terra::TRV_THREADS>(terra::k_tree_view, n, c, tile_xy, insts, stats, skip, trmax, pine, counts, ov, tile_out, bcube, pine_insts, palm_insts, inst_counts,
+			leaf_list, leaf_counts, trunk, keys);
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (opt->simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

@@ -2187,6 +2187,223 @@ __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_rank(float const *_
 	draw_order[tv_rank(keys, nd, keys[i], i)] = key_tile[i];
 }
 
+// ------------------------------------------------------------------ the pine and palm tree draw lists of a tile batch for a camera (tile_t::draw_pine_trees,
+// src/tiled_mesh.cpp:1465-1526; terra_treeview.hpp).  k_tree_view: a workgroup of 256 lanes per tile; a skipped tile and one without records leave at once.
+//  1. A sweep over the tile's records, a lane a record: the record's size and trunk cylinder (tree_view_record), the counts of the valid, pine and palm records and
+//     the min / max union of the boxes (calc_bcube), reduced over the wave with shuffles and over the four waves through LDS.
+//  2. One lane takes the tile-level decisions (tree_view_tile) and broadcasts them through LDS.
+//  3. A second sweep in record order: the trunk byte of every record, and the pine entries of leaf_list -- appended in record order (tp_emit), or, in the tile that
+//     holds the camera, compacted as (p2p_dist_sq, index) pairs and placed by their rank among the pairs (as k_terrain_view_rank places a tile).  A third sweep
+//     appends the palm entries where draw_non_pine_leaves draws them.
+//  4. The instance lists, pine then palm: a stable counting sort by id.  A histogram of the ids in LDS (atomic adds: only counts), an exclusive scan of it, then
+//     emission in record order: the waves of a sweep take turns, and in a wave the lanes that share an id are ranked by a ballot, so the order inside an id is the
+//     record index and no atomic decides an order.  The histogram holds instance tables of up to TREE_VIEW_LDS_IDS entries; a larger table takes the second path:
+//     the (id, index) pairs are compacted and ranked like the camera tile's list.
+// The pairs lie in LDS for capacities up to TREE_VIEW_LDS_KEYS, else in the tile's part of the driver's scratch.  The sweeps recompute a record's geometry instead
+// of keeping it: a few dozen flops against a round trip through memory, and the records come from L2 after the first sweep.
+constexpr uint32_t TRV_THREADS = 256;
+static_assert(TRV_THREADS == TREEP_THREADS, "tp_block_rank and tp_emit rank TREEP_THREADS threads");
+static_assert(TREE_VIEW_LDS_IDS % TRV_THREADS == 0, "the scan gives every lane the same number of bins");
+template<bool FLOATKEY> __device__ __forceinline__ uint32_t trv_rank(uint32_t const *key, uint32_t const *idx, uint32_t m, uint32_t ki, uint32_t ii) {
+	uint32_t rank = 0;
+	for (uint32_t j = 0; j < m; ++j) {
+		bool const b = FLOATKEY ? tree_view_before_f(__uint_as_float(key[j]), idx[j], __uint_as_float(ki), ii) : tree_view_before_u(key[j], idx[j], ki, ii);
+		rank += b ? 1u : 0u;
+	}
+	return rank;
+}
+// one instance list of the tile (PINE: draw_pine_insts, else draw_palm_insts) -> its count (uniform)
+template<bool PINE> __device__ __forceinline__ uint32_t trv_insts(tree_view_consts_t const &c, tree_view_tile_t const &tl, tree_inst_pod_t const *__restrict__ insts,
+	tree_place_pod_t const *__restrict__ recs, trunk_override_pod_t const *__restrict__ ovs, uint32_t cnt, tree_view_inst_pod_t *__restrict__ out, uint32_t *s_hist, uint32_t *s_wave,
+	uint32_t *kbuf, uint32_t *ibuf)
+{
+	uint32_t const tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	bool const all = PINE ? tl.draw_all_near != 0 : tl.all_visible != 0;
+	auto entry = [&](uint32_t i, uint32_t &id) -> bool { // does record i enter the list, and with which id
+		if (i >= cnt) return false;
+		tree_view_rec_t rec;
+		if (recs[i].inst < 0 || !tree_view_record(c, insts, recs[i], ovs ? ovs + i : nullptr, rec)) return false;
+		if (PINE ? !is_pine_tree_type(rec.type) : rec.type != T_PALM) return false;
+		id = (uint32_t)recs[i].inst;
+		return all || tree_view_leaves_visible(c, rec);
+	};
+	auto store = [&](uint32_t at, uint32_t id, uint32_t i) {out[at].id = id; for (int q = 0; q < 3; ++q) {out[at].pt[q] = recs[i].pos[q];}};
+	uint32_t const nid = c.a.num_insts;
+	if (nid <= TREE_VIEW_LDS_IDS) {
+		for (uint32_t b = tid; b < nid; b += TRV_THREADS) {s_hist[b] = 0u;}
+		__syncthreads();
+		for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
+			uint32_t id = 0;
+			if (entry(base + tid, id)) {atomicAdd(&s_hist[id], 1u);}
+		}
+		__syncthreads();
+		// exclusive scan of the nid counts: lane q owns bins PER*q .. PER*q + PER - 1
+		constexpr uint32_t PER = TREE_VIEW_LDS_IDS/TRV_THREADS;
+		uint32_t v[PER], sum = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < PER; ++k) {uint32_t const b = PER*tid + k; v[k] = (b < nid) ? s_hist[b] : 0u; sum += v[k];}
+		uint32_t incl = sum;
+		for (uint32_t d = 1; d < 64u; d <<= 1) {uint32_t const u = __shfl_up(incl, d); if (lane >= d) {incl += u;}}
+		if (lane == 63u) {s_wave[wave] = incl;}
+		__syncthreads();
+		uint32_t before = 0, total = 0;
+		for (uint32_t w = 0; w < TRV_THREADS/64; ++w) {uint32_t const sw = s_wave[w]; if (w < wave) {before += sw;} total += sw;}
+		uint32_t at = before + incl - sum;
+#pragma unroll
+		for (uint32_t k = 0; k < PER; ++k) {uint32_t const b = PER*tid + k; if (b < nid) {s_hist[b] = at;} at += v[k];}
+		__syncthreads();
+		uint64_t const below = (1ull << lane) - 1ull;
+		for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
+			uint32_t id = 0;
+			bool const e = entry(base + tid, id);
+			for (uint32_t w = 0; w < TRV_THREADS/64; ++w) { // the waves in record order
+				if (wave == w) {
+					uint64_t rem = __ballot(e);
+					while (rem) {
+						int const leader = __ffsll((unsigned long long)rem) - 1;
+						uint32_t const lid = (uint32_t)__shfl((int)id, leader);
+						uint64_t const m = __ballot(e && id == lid);
+						uint32_t const start = s_hist[lid]; // (every lane reads before the leader writes)
+						if (e && id == lid) {store(start + (uint32_t)__popcll(m & below), id, base + tid);}
+						if ((int)lane == leader) {s_hist[lid] = start + (uint32_t)__popcll(m);}
+						rem &= ~m;
+					}
+				}
+				__syncthreads();
+			}
+		}
+		return total;
+	}
+	// the second path: compact the (id, index) pairs in record order, then place every pair by its rank
+	uint32_t m = 0;
+	for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
+		uint32_t id = 0, tot;
+		bool const e = entry(base + tid, id);
+		uint32_t const rank = tp_block_rank(e, s_wave, tot);
+		if (e) {kbuf[m + rank] = id; ibuf[m + rank] = base + tid;}
+		m += tot;
+	}
+	__syncthreads();
+	for (uint32_t i = tid; i < m; i += TRV_THREADS) {store(trv_rank<false>(kbuf, ibuf, m, kbuf[i], ibuf[i]), kbuf[i], ibuf[i]);}
+	__syncthreads(); // the pairs are reused
+	return m;
+}
+__global__ __launch_bounds__(TRV_THREADS) void k_tree_view(tree_view_consts_t c, int32_t const *__restrict__ tile_xy, tree_inst_pod_t const *__restrict__ insts,
+	terra_tile_stats const *__restrict__ stats, uint8_t const *__restrict__ skip, float const *__restrict__ trmax, tree_place_pod_t const *__restrict__ pine,
+	uint32_t const *__restrict__ counts, trunk_override_pod_t const *__restrict__ ov, tree_view_tile_pod_t *__restrict__ tile_out, float *__restrict__ bcube,
+	tree_view_inst_pod_t *__restrict__ pine_insts, tree_view_inst_pod_t *__restrict__ palm_insts, uint32_t *__restrict__ inst_counts, uint32_t *__restrict__ leaf_list,
+	uint32_t *__restrict__ leaf_counts, uint8_t *__restrict__ trunk, uint32_t *keys)
+{
+	__shared__ uint32_t s_wave[TRV_THREADS/64], s_cnt[TRV_THREADS/64][4], s_key[TREE_VIEW_LDS_KEYS], s_idx[TREE_VIEW_LDS_KEYS], s_hist[TREE_VIEW_LDS_IDS];
+	__shared__ float s_box[TRV_THREADS/64][6];
+	__shared__ tree_view_tile_t s_tile;
+	uint32_t const t = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	uint32_t const cnt = (skip && skip[t]) ? 0u : min_u32(counts[t], c.cap); // (uniform)
+	auto leave_empty = [&] {
+		if (tid < 6u) {bcube[(size_t)t*6u + tid] = 0.0f;}
+		if (tid == 0) {
+			tree_view_tile_pod_t z; z.dscale = 0.0f; z.weight = 0.0f; z.flags = 0u; z.num_pine = z.num_palm = z.num_trees = z.leaf_written = z.pad = 0u;
+			tile_out[t] = z; inst_counts[2u*t] = inst_counts[2u*t + 1u] = 0u; leaf_counts[2u*t] = leaf_counts[2u*t + 1u] = 0u;
+		}
+	};
+	if (cnt == 0u) {leave_empty(); return;}
+	tree_place_pod_t const *const recs = pine + (size_t)t*c.cap;
+	trunk_override_pod_t const *const ovs = ov ? ov + (size_t)t*c.cap : nullptr;
+	// 1. calc_bcube and the counts
+	float const INF = __builtin_inff();
+	float box[6] = {INF, -INF, INF, -INF, INF, -INF};
+	uint32_t nv = 0, np = 0, nm = 0, nb = 0;
+	for (uint32_t i = tid; i < cnt; i += TRV_THREADS) {
+		tree_view_rec_t rec;
+		if (!tree_view_record(c, insts, recs[i], ovs ? ovs + i : nullptr, rec)) continue;
+		++nv; np += is_pine_tree_type(rec.type) ? 1u : 0u; nm += (rec.type == T_PALM) ? 1u : 0u;
+		float d[6];
+		if (!tree_view_bounds(rec, d)) continue;
+		++nb;
+#pragma unroll
+		for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], d[k]); box[k + 1] = max_std(box[k + 1], d[k + 1]);}
+	}
+	for (int off = 32; off; off >>= 1) {
+		nv += __shfl_xor(nv, off); np += __shfl_xor(np, off); nm += __shfl_xor(nm, off); nb += __shfl_xor(nb, off);
+#pragma unroll
+		for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], __shfl_xor(box[k], off)); box[k + 1] = max_std(box[k + 1], __shfl_xor(box[k + 1], off));}
+	}
+	if (lane == 0) {
+		s_cnt[wave][0] = nv; s_cnt[wave][1] = np; s_cnt[wave][2] = nm; s_cnt[wave][3] = nb;
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {s_box[wave][k] = box[k];}
+	}
+	__syncthreads();
+	nv = np = nm = nb = 0;
+	for (uint32_t w = 0; w < TRV_THREADS/64; ++w) {nv += s_cnt[w][0]; np += s_cnt[w][1]; nm += s_cnt[w][2]; nb += s_cnt[w][3];}
+	if (nv == 0u) {leave_empty(); return;} // pine_trees.empty() (:1468) (uniform)
+	// 2. the tile's decisions
+	if (tid == 0) {
+		float bc[6];
+#pragma unroll
+		for (int k = 0; k < 6; k += 2) {
+			float lo = s_box[0][k], hi = s_box[0][k + 1];
+			for (uint32_t w = 1; w < TRV_THREADS/64; ++w) {lo = min_std(lo, s_box[w][k]); hi = max_std(hi, s_box[w][k + 1]);}
+			bc[k] = nb ? lo : 0.0f; bc[k + 1] = nb ? hi : 0.0f;
+		}
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {bcube[(size_t)t*6u + k] = bc[k];}
+		s_tile = tree_view_tile(c, tile_xy[2u*t], tile_xy[2u*t + 1u], stats[t], trmax ? trmax[t] : 0.0f, nv, np, nm, bc);
+	}
+	__syncthreads();
+	tree_view_tile_t const tl = s_tile;
+	uint32_t *const kbuf = (c.cap > TREE_VIEW_LDS_KEYS) ? keys + (size_t)t*c.cap*2u : s_key, *const ibuf = (c.cap > TREE_VIEW_LDS_KEYS) ? kbuf + c.cap : s_idx;
+	uint32_t *const ll = leaf_list + (size_t)t*c.cap;
+	// 3. the trunk bytes and the pine entries of leaf_list
+	uint32_t nl = 0;
+	int skipped = 0;
+	for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
+		uint32_t const i = base + tid;
+		tree_view_rec_t rec;
+		bool const valid = i < cnt && tree_view_record(c, insts, recs[i], ovs ? ovs + i : nullptr, rec);
+		if (i < cnt) {
+			uint8_t const b = (valid && tl.trunks) ? tree_view_trunk(c, rec, tl.all_visible != 0) : (uint8_t)0;
+			trunk[(size_t)t*c.cap + i] = b; skipped |= (b == 1) ? 1 : 0;
+		}
+		if (tl.pine_list) { // (uniform)
+			bool const e = valid && is_pine_tree_type(rec.type) && tree_view_leaves_visible(c, rec);
+			if (!tl.pine_sorted) {tp_emit(e, [&] {return i;}, ll, c.cap, nl, s_wave);}
+			else {
+				uint32_t tot;
+				uint32_t const rank = tp_block_rank(e, s_wave, tot);
+				if (e) {kbuf[nl + rank] = __float_as_uint(tree_view_sort_key(c, rec.pos)); ibuf[nl + rank] = i;}
+				nl += tot;
+			}
+		}
+	}
+	skipped = __syncthreads_or(skipped); // (also: the pairs are complete)
+	if (tl.pine_sorted) {
+		for (uint32_t i = tid; i < nl; i += TRV_THREADS) {ll[trv_rank<true>(kbuf, ibuf, nl, kbuf[i], ibuf[i])] = ibuf[i];}
+		__syncthreads(); // the pairs are reused
+	}
+	uint32_t npl = 0;
+	if (tl.palm_list) { // draw_non_pine_leaves(0, 1, 0, ..): behind the pine entries
+		for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
+			uint32_t const i = base + tid;
+			tree_view_rec_t rec;
+			bool const e = i < cnt && tree_view_record(c, insts, recs[i], ovs ? ovs + i : nullptr, rec) && rec.type == T_PALM && tree_view_leaves_visible(c, rec);
+			tp_emit(e, [&] {return i;}, ll + nl, c.cap - nl, npl, s_wave);
+		}
+	}
+	// 4. the instance lists
+	uint32_t npi = 0, nmi = 0;
+	if (tl.pine_insts) {npi = trv_insts<true>(c, tl, insts, recs, ovs, cnt, pine_insts + (size_t)t*c.cap, s_hist, s_wave, kbuf, ibuf);}
+	if (tl.palm_insts) {nmi = trv_insts<false>(c, tl, insts, recs, ovs, cnt, palm_insts + (size_t)t*c.cap, s_hist, s_wave, kbuf, ibuf);}
+	if (tid == 0) {
+		tree_view_tile_pod_t o = tl.out;
+		if (skipped) {o.flags = (o.flags & ~(uint32_t)TRV_TRUNK_MASK) | TRV_TRUNK_POLY_SKIPPED;}
+		o.leaf_written = nl + npl;
+		tile_out[t] = o;
+		inst_counts[2u*t] = npi; inst_counts[2u*t + 1u] = nmi;
+		leaf_counts[2u*t] = tl.pine_list ? nl : tree_view_render_all(c, tl); leaf_counts[2u*t + 1u] = npl;
+	}
+}
+
 // ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
 // terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
 // k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes

@@ -164,6 +164,27 @@ TVIEW_STATUS_MASK, TVIEW_WAS_OCCLUDER = 7, 0x80
 TVIEW_FLAG_ABSENT, TVIEW_FLAG_NO_OCCLUDER, TVIEW_FLAG_SHADOW_MAPS = 1, 2, 4  # the per-tile flag byte of tiles_terrain_view
 
 
+class TreeViewArgs(C.Structure):  # terra_tree_view_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("zoom_f", C.c_float), ("tree_depth_scale", C.c_float), ("window_width", C.c_int32), ("shadow_pass", C.c_int32),
+                ("draw_trunks", C.c_int32), ("draw_near_leaves", C.c_int32), ("draw_far_leaves", C.c_int32)]
+
+
+def make_tree_view_args(behind_sphere_mult=1.0, zoom_f=1.0, tree_depth_scale=1.0, window_width=1920, shadow_pass=0, draw_trunks=1, draw_near_leaves=1, draw_far_leaves=1):
+    """terra_tree_view_args: behind_sphere_mult as for the terrain view; the three draw booleans of one draw_pine_tree_bl sweep, in any combination"""
+    return TreeViewArgs(behind_sphere_mult, zoom_f, tree_depth_scale, window_width, int(bool(shadow_pass)), int(bool(draw_trunks)), int(bool(draw_near_leaves)),
+                        int(bool(draw_far_leaves)))
+
+
+TREE_VIEW_TILE_DTYPE = np.dtype([("dscale", np.float32), ("weight", np.float32), ("flags", np.uint32), ("num_pine", np.uint32), ("num_palm", np.uint32),
+                                 ("num_trees", np.uint32), ("leaf_written", np.uint32), ("pad", np.uint32)])  # terra_tree_view_tile
+TREE_VIEW_INST_DTYPE = np.dtype([("id", np.uint32), ("pt", np.float32, (3,))])  # terra_tree_view_inst
+TRUNK_OVERRIDE_DTYPE = np.dtype([("p1", np.float32, (3,)), ("p2", np.float32, (3,)), ("r1", np.float32), ("r2", np.float32), ("rotated", np.int32)])  # terra_trunk_override
+assert TREE_VIEW_TILE_DTYPE.itemsize == 32 and TREE_VIEW_INST_DTYPE.itemsize == 16 and TRUNK_OVERRIDE_DTYPE.itemsize == 36
+TRV_TRUNK_NONE, TRV_TRUNK_POLY_ALL, TRV_TRUNK_POLY_SKIPPED, TRV_TRUNK_POINTS, TRV_TRUNK_MASK = 0, 1, 2, 3, 3  # the flags word of terra_tree_view_tile
+TRV_NEAR_LEAVES, TRV_FAR_LEAVES, TRV_DITHERED, TRV_PALMS, TRV_DRAW_ALL_NEAR, TRV_DRAW_ALL_FAR = 0x4, 0x8, 0x10, 0x20, 0x40, 0x80
+TRV_ALL_VISIBLE, TRV_NEEDS_HIGH, TRV_NEEDS_LOW, TRV_CONTAINS_CAMERA = 0x100, 0x200, 0x400, 0x800
+
+
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
@@ -364,6 +385,8 @@ _PROTOS = {
     "terra_view_behind_sphere_mult": (_i32, [C.c_float, C.c_float, _vp]),
     "terra_tiles_terrain_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_terrain_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_tree_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_tree_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -1016,6 +1039,33 @@ class Terra:
                                                    occluded.ctypes.data, counts.ctypes.data, None))
         return status, dist, lod, crack, order[:counts[0]], occluded[:counts[1]], counts, os_
 
+    def tiles_tree_view(self, tile_xy, stats, view, args, pine, pine_counts, skip=None, trmax=None, trunk_override=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0, fill=0):
+        """tile_t::draw_pine_trees for every tile: pine TREE_PLACE_DTYPE [n, cap] with pine_counts [n]; stats TileStats * n; skip [n] bytes, trmax [n] float32,
+        trunk_override TRUNK_OVERRIDE_DTYPE [n, cap], all optional.  The [n, cap] outputs start filled with the byte `fill`; entries past the counts keep it.
+        -> dict(tile TREE_VIEW_TILE_DTYPE [n], all_bcube float32 [n, 6], pine_insts / palm_insts TREE_VIEW_INST_DTYPE [n, cap], inst_counts uint32 [n, 2],
+        leaf_list uint32 [n, cap], leaf_counts uint32 [n, 2], trunk uint8 [n, cap])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        pr = np.ascontiguousarray(pine, TREE_PLACE_DTYPE).reshape(n, -1)
+        cap = pr.shape[1]
+        pc = np.ascontiguousarray(pine_counts, np.uint32).reshape(n)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        tr = None if trmax is None else np.ascontiguousarray(trmax, np.float32).reshape(n)
+        ov = None if trunk_override is None else np.ascontiguousarray(trunk_override, TRUNK_OVERRIDE_DTYPE).reshape(n, cap)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        out = self._tree_view_outputs(n, cap, fill)
+        self._ck(self.lib.terra_tiles_tree_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), C.addressof(stats) if n else None, ptr(sk),
+                                                ptr(tr), pr.ctypes.data, pc.ctypes.data, cap, ptr(ov), *[out[k].ctypes.data for k in self.TREE_VIEW_OUTPUTS]))
+        return out
+
+    TREE_VIEW_OUTPUTS = ("tile", "all_bcube", "pine_insts", "palm_insts", "inst_counts", "leaf_list", "leaf_counts", "trunk")
+
+    @staticmethod
+    def _tree_view_outputs(n, cap, fill=0):
+        mk = lambda shape, dt: np.frombuffer(bytearray([fill]) * (int(np.prod(shape)) * np.dtype(dt).itemsize), dt).reshape(shape)  # noqa: E731
+        return dict(tile=mk((n,), TREE_VIEW_TILE_DTYPE), all_bcube=mk((n, 6), np.float32), pine_insts=mk((n, cap), TREE_VIEW_INST_DTYPE), palm_insts=mk((n, cap), TREE_VIEW_INST_DTYPE),
+                    inst_counts=mk((n, 2), np.uint32), leaf_list=mk((n, cap), np.uint32), leaf_counts=mk((n, 2), np.uint32), trunk=mk((n, cap), np.uint8))
+
     def set_tree_size_params(self, tsp):
         self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
 
@@ -1295,6 +1345,17 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_terrain_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, min_normal_z_ptr, trmax_ptr,
                                                        tile_zmax_ptr, flags_ptr, occl_state_ptr, status_ptr, dist_ptr, lod_ptr, crack_ptr, draw_order_ptr, occluded_ptr, counts_ptr, not_drawn_ptr))
+
+    def tiles_tree_view_dev(self, tile_xy, view, args, stats_ptr, pine_ptr, pine_counts_ptr, capacity, tile_out_ptr, all_bcube_ptr, pine_insts_ptr, palm_insts_ptr, inst_counts_ptr,
+                            leaf_list_ptr, leaf_counts_ptr, trunk_ptr, skip_ptr=None, trmax_ptr=None, trunk_override_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):
+        """the tree draw lists of a device-resident batch, from the records the placement calls left on the device: tile_out_ptr [n] terra_tree_view_tile, all_bcube_ptr
+        [n][6] floats, pine_insts_ptr / palm_insts_ptr [n][capacity] terra_tree_view_inst, inst_counts_ptr / leaf_counts_ptr [n][2] uint32, leaf_list_ptr [n][capacity]
+        uint32, trunk_ptr [n][capacity] bytes; skip_ptr [n] bytes (the terrain view's not_drawn), trmax_ptr [n] floats, trunk_override_ptr [n][capacity] or None.
+        view and args are host structs.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_tree_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), stats_ptr, skip_ptr, trmax_ptr,
+                                                    pine_ptr, pine_counts_ptr, capacity, trunk_override_ptr, tile_out_ptr, all_bcube_ptr, pine_insts_ptr, palm_insts_ptr,
+                                                    inst_counts_ptr, leaf_list_ptr, leaf_counts_ptr, trunk_ptr))
 
     def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
                                   decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,

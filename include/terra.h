@@ -1107,6 +1107,83 @@ int  terra_dgrid_map(terra_dgrid *g, void **d_base);
 void terra_dgrid_destroy(terra_dgrid *g);
 int  terra_multi_dgrid_create(terra_multi *m, const size_t *strip_bytes, terra_dgrid **out, void **d_base);
 
+/* ---- the pine and palm tree draw lists of a tile batch for a camera (every supported tile size S): tile_t::draw_pine_trees (src/tiled_mesh.cpp:1465-1526) without
+ * its GL and shader calls, with small_tree_group::draw_tree_insts, draw_pine_leaves, draw_non_pine_leaves and draw_trunks under it (src/sm_tree.cpp:206-323) -- the
+ * per-frame decision about the trees of every drawn tile: which are drawn, in which form, in what order, bit for bit, from the records that
+ * terra_tiles_place_trees_dev and terra_tiles_edit_trees_dev keep on the device.  A frame is then one stream of launches: zvals -> placements -> tree AO -> terrain
+ * draw list -> grass draw lists -> tree draw lists, and only the lists are read back.
+ * Restated with the source's operand types: draw_tree_leaves_lod (:1459-1462), the weights of update_pine_tree_state (:1440-1448), get_tree_dist_scale,
+ * get_tree_far_weight, get_tree_scale_denom, get_dist_to_camera_in_tiles (src/tiled_mesh.h:95,332-338), contains_camera, get_back_to_front_ordering, calc_bcube /
+ * add_bounds_to_bcube, small_tree::are_leaves_visible (:1007-1017), the decisions of small_tree::draw_trunk (:1081-1102, down to nsides), get_trunk_cylin (:767-777)
+ * with get_tree_z_bottom / get_default_tree_depth (src/Tree.cpp:209-214, the tiled-terrain branch), get_xy_radius, get_trunk_bsphere_radius (src/small_tree.h:
+ * 77-78), the two small_tree constructors as terra_tiles_tree_ao_shadows forms them, and pos_dir_up::sphere_visible_test (src/visibility.cpp:119-128).
+ * sphere_in_camera_view(.., 2) is sphere_visible_test alone in tiled-terrain mode (src/visibility.cpp:338-339).
+ * Inputs.  tile_xy on the host; dxoff / dyoff = xoff - xoff2 / yoff - yoff2 and xoff2 / yoff2 as for terra_tiles_tree_ao_shadows: xlate = ptree_off.get_xlate() =
+ * ((dxoff + xoff2)*DX_VAL, (dyoff + yoff2)*DY_VAL, 0).  stats [n] (mzmin, mzmax, radius).  skip [n] bytes (optional): !can_have_trees(), or the tile is not in
+ * to_draw -- the not_drawn bytes of terra_tiles_terrain_view plug in here.  trmax [n] (optional; NULL = 0; terra_tiles_tree_ao_shadows writes it): contains_camera()
+ * tests get_bcube(), which is wider than the mesh by trmax.  pine [n][capacity] with counts [n] as the placement wrote them; a count above the capacity means the
+ * first `capacity` records.  view; terra_tree_view_args, a host struct read at the call: behind_sphere_mult as for terra_tiles_terrain_view; shadow_pass;
+ * window_width; zoom_f = (do_zoom ? ZOOM_FACTOR : 1); tree_depth_scale; draw_trunks / draw_near_leaves / draw_far_leaves: the three booleans of one
+ * draw_pine_tree_bl sweep, in any combination, so that one call can answer a whole frame.  Everything else comes from terra_tree_params (tree_scale, instanced),
+ * terra_tree_size_params and the instance table.
+ * trunk_override [n][capacity] (optional).  A record's geometry is derived with a vertical trunk (r_angle == 0): exact for every pine, for every instanced record
+ * (instances are never rotated, src/sm_tree.cpp:351,358) and for three in four generated palms.  setup_rotation's random draws belong to the small_tree
+ * constructor, which stays with the engine: for a record whose entry has rotated != 0 the call uses the entry's cylinder as trunk_cylin and get_rot_dir() =
+ * (p2 - p1).get_norm().  Entries with rotated == 0 are ignored.  This is the one thing an engine with rotated palms that are not instanced passes in.
+ * Records that terra_tiles_tree_ao_shadows would drop -- a type outside stt[], an instance index outside the table, an instanced record while `instanced` is off --
+ * are skipped everywhere and do not enter all_bcube.  `instanced` is the group's flag (enable_instanced()); a record with inst < 0 in an instanced group enters no
+ * instance list (get_inst_id() asserts).  A skipped tile, or one without a valid record (pine_trees.empty()), gets a zero tile_out, zero all_bcube and zero counts,
+ * and nothing else of it is written.
+ * Outputs.  tile_out [n]: dscale = get_tree_dist_scale(); weight = the weight of :1492; num_pine / num_palm = num_pine_trees / num_palm_trees over the valid
+ * records, num_trees = all valid records (bushes too), leaf_written = the entries of leaf_list that were written; flags: bits 0-1 the trunk mode (the branches of :1477-1489: 0 none, 1 polygons and all drawn, 2 polygons and draw_trunks() returned 0, so the tile also
+ * joins to_draw_trunk_pts, 3 trunk points only), TERRA_TRV_NEAR_LEAVES / TERRA_TRV_FAR_LEAVES: draw_tree_leaves_lod ran with low_detail 0 / 1, TERRA_TRV_DITHERED: 0 <
+ * weight < 1, TERRA_TRV_PALMS: the condition of :1517, TERRA_TRV_DRAW_ALL_NEAR / _FAR: draw_all of :1460 in the sweep that ran, TERRA_TRV_ALL_VISIBLE: the
+ * sphere test of :1483 and :1520, TERRA_TRV_NEEDS_HIGH / _LOW: weights[0] > 0 / weights[1] > 0 in update_pine_tree_state (with force_high_detail = shadow_pass),
+ * TERRA_TRV_CONTAINS_CAMERA.  all_bcube [n][6] = x1 x2 y1 y2 z1 z2 after calc_bcube(), by value: it is a min / max union, so a zero bound may come out with the
+ * other sign.
+ * pine_insts / palm_insts [n][capacity] with inst_counts [n][2]: the reference's tree_inst_t {id, pt} of draw_pine_insts / draw_palm_insts, written when the group is
+ * instanced and the sweep draws it, after the cull of :250, in ascending id and within an id in ascending record index.  That order is the one deviation: the
+ * reference calls std::sort on a comparison that looks at the id alone, so its order inside an id is whatever the library's introsort leaves; the instanced draw
+ * per id does not depend on it.
+ * leaf_list [n][capacity] with leaf_counts [n][2] (pine, palm): record indices of the forms that are not instanced.  The pine entries are what the high-detail
+ * sweep draws when the group is not instanced and draw_all does not hold: in record order, but in the tile that contains the camera in the order of
+ * get_back_to_front_ordering, ascending (p2p_dist_sq, index) -- a total order.  Under draw_all the list is not written and leaf_counts[0] is num_pine
+ * (render_all); so it is when only the low-detail sweep draws pines.  The palm entries (draw_non_pine_leaves(0, 1, 0, ..), the group not instanced) follow the
+ * written pine entries, in record order.
+ * trunk [n][capacity] bytes, one per record in record order, written for every tile that is not skipped or empty, nonzero only in the polygon trunk modes: 0 not
+ * drawn (a bush, culled, size_scale < dist, a dropped record), 1 a line that skip_lines skipped, otherwise nsides (4 .. N_CYL_SIDES = 32).  Vertex generation stays
+ * with the engine.  Entries past the counts are never written.
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or the args; window_width, zoom_f or tree_depth_scale not > 0; a NULL required pointer
+ * (view, args; tile_xy, stats, counts, tile_out, all_bcube, inst_counts, leaf_counts when n > 0; the records and the four [n][capacity] outputs when capacity > 0
+ * as well); a pointer other than skip and trunk that is not 4-byte aligned; an unsupported S; `instanced` with an instance table whose length is not
+ * num_pine_insts + num_palm_insts; n*capacity beyond 32 bits.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.  The
+ * device form only enqueues and reads nothing back; tile_xy is a host array in both forms.  Scratch comes from the context's arena. */
+typedef struct terra_tree_view_args {
+	float behind_sphere_mult;  /* pos_dir_up::behind_sphere_mult */
+	float zoom_f;              /* do_zoom ? ZOOM_FACTOR : 1 */
+	float tree_depth_scale;
+	int32_t window_width;
+	int32_t shadow_pass;
+	int32_t draw_trunks, draw_near_leaves, draw_far_leaves;
+} terra_tree_view_args;      /* 32 bytes */
+typedef struct terra_tree_view_tile {float dscale, weight; uint32_t flags, num_pine, num_palm, num_trees, leaf_written, pad;} terra_tree_view_tile; /* 32 bytes */
+typedef struct terra_tree_view_inst {uint32_t id; float pt[3];} terra_tree_view_inst;                                        /* tree_inst_t, 16 bytes */
+typedef struct terra_trunk_override {float p1[3], p2[3], r1, r2; int32_t rotated;} terra_trunk_override;                     /* 36 bytes */
+enum {TERRA_TRV_TRUNK_NONE = 0, TERRA_TRV_TRUNK_POLY_ALL = 1, TERRA_TRV_TRUNK_POLY_SKIPPED = 2, TERRA_TRV_TRUNK_POINTS = 3, TERRA_TRV_TRUNK_MASK = 3,
+      TERRA_TRV_NEAR_LEAVES = 0x4, TERRA_TRV_FAR_LEAVES = 0x8, TERRA_TRV_DITHERED = 0x10, TERRA_TRV_PALMS = 0x20, TERRA_TRV_DRAW_ALL_NEAR = 0x40,
+      TERRA_TRV_DRAW_ALL_FAR = 0x80, TERRA_TRV_ALL_VISIBLE = 0x100, TERRA_TRV_NEEDS_HIGH = 0x200, TERRA_TRV_NEEDS_LOW = 0x400, TERRA_TRV_CONTAINS_CAMERA = 0x800};
+int  terra_tiles_tree_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                               const terra_tree_view_args *args, const terra_tile_stats *d_stats, const uint8_t *d_skip, const float *d_trmax, const terra_tree_place *d_pine,
+                               const uint32_t *d_pine_counts, uint32_t capacity, const terra_trunk_override *d_trunk_override, terra_tree_view_tile *d_tile_out,
+                               float *d_all_bcube, terra_tree_view_inst *d_pine_insts, terra_tree_view_inst *d_palm_insts, uint32_t *d_inst_counts, uint32_t *d_leaf_list,
+                               uint32_t *d_leaf_counts, uint8_t *d_trunk);
+int  terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                           const terra_tree_view_args *args, const terra_tile_stats *h_stats, const uint8_t *h_skip, const float *h_trmax, const terra_tree_place *h_pine,
+                           const uint32_t *h_pine_counts, uint32_t capacity, const terra_trunk_override *h_trunk_override, terra_tree_view_tile *h_tile_out,
+                           float *h_all_bcube, terra_tree_view_inst *h_pine_insts, terra_tree_view_inst *h_palm_insts, uint32_t *h_inst_counts, uint32_t *h_leaf_list,
+                           uint32_t *h_leaf_counts, uint8_t *h_trunk);
+
+
 /* ---- plumbing for callers without a HIP runtime of their own (tests, ctypes) */
 int  terra_malloc(terra_ctx *ctx, void **d_ptr, size_t bytes);
 int  terra_free(terra_ctx *ctx, void *d_ptr);

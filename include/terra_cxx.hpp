@@ -390,6 +390,25 @@ inline void set_tree_size_params(float tree_height_scale, float sm_tree_scale, f
 }
 // tree_instances after create_pine_tree_instances (src/sm_tree.cpp:342-364): {get_type(), get_height(), get_width()} of every instance, in order
 inline void set_tree_instances(terra_tree_inst const *insts, unsigned count) {check(terra_set_tree_instances(default_ctx(), insts, count), "create_pine_tree_instances");}
+// ---- the pine and palm tree draw lists of a batch for the camera: tile_t::draw_pine_trees (src/tiled_mesh.cpp:1465-1526) for every tile, without its GL and shader
+// calls, from the records tiles_gen_trees left on the device.  One call answers the three draw_pine_tree_bl sweeps of a frame (args.draw_trunks / draw_near_leaves /
+// draw_far_leaves).  d_not_drawn: tile_draw_lists' output (or null); d_trmax: tiles_apply_tree_ao_shadows' output (or null); d_trunk_override: the cylinders of the
+// rotated palms that are not instanced (or null).  d_tile_out[t].flags: TERRA_TRV_*; the instance lists are tree_inst_t records in ascending (id, record index);
+// d_leaf_list holds record indices, the pine entries first; d_trunk one byte per record (0, 1 = a skipped line, else nsides)
+inline terra_tree_view_args tree_view_args_of(float behind_sphere_mult, bool shadow_pass, int window_width, float zoom_f, float tree_depth_scale, bool draw_trunks,
+	bool draw_near_leaves, bool draw_far_leaves)
+{
+	terra_tree_view_args const a = {behind_sphere_mult, zoom_f, tree_depth_scale, window_width, shadow_pass ? 1 : 0, draw_trunks ? 1 : 0, draw_near_leaves ? 1 : 0, draw_far_leaves ? 1 : 0};
+	return a;
+}
+inline void tile_draw_pine_tree_lists(tile_batch_dev_t const &b, int xoff2, int yoff2, terra_view const &camera_pdu, terra_tree_view_args const &args, unsigned char const *d_not_drawn,
+	float const *d_trmax, terra_tree_place const *d_pine_trees, unsigned const *d_pine_counts, unsigned capacity, terra_trunk_override const *d_trunk_override,
+	terra_tree_view_tile *d_tile_out, float *d_all_bcube, terra_tree_view_inst *d_pine_insts, terra_tree_view_inst *d_palm_insts, unsigned *d_inst_counts, unsigned *d_leaf_list,
+	unsigned *d_leaf_counts, unsigned char *d_trunk)
+{
+	check(terra_tiles_tree_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, &camera_pdu, &args, b.d_stats, d_not_drawn, d_trmax, d_pine_trees, d_pine_counts,
+		capacity, d_trunk_override, d_tile_out, d_all_bcube, d_pine_insts, d_palm_insts, d_inst_counts, d_leaf_list, d_leaf_counts, d_trunk), "tile_t::draw_pine_trees");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest

@@ -9,7 +9,8 @@ HIPCC = os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
 MUST_NOT_SPILL = [("speculative_erosion", "wave_scratch_t"),  # k_waves<trace lambda>: the only speculative_erosion kernel that takes the LDS scratch
                   ("k_sine_grid", "Lb0ELb0E"), ("k_noise_grid", ""), ("k_tile_erosion", ""),
                   ("k_tree_place", ""), ("k_decid_place", ""), ("k_scenery_place", ""),  # their comments promise "no scratch"
-                  ("k_terrain_view_tiles", ""), ("k_terrain_view_occluders", ""), ("k_terrain_view_occlusion", ""), ("k_terrain_view_lists", ""), ("k_terrain_view_rank", "")]
+                  ("k_terrain_view_tiles", ""), ("k_terrain_view_occluders", ""), ("k_terrain_view_occlusion", ""), ("k_terrain_view_lists", ""), ("k_terrain_view_rank", ""),
+                  ("k_tree_view", "")]
 
 
 def kernels():
