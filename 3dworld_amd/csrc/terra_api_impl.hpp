@@ -1033,6 +1033,56 @@ int terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, in
 		}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_scenery_view_args) == sizeof(terra::scenery_view_args_pod_t) && sizeof(terra_scenery_view_args) == 40, "terra_scenery_view_args layout");
+static_assert(sizeof(terra_scenery_view_tile) == sizeof(terra::scenery_view_tile_pod_t) && sizeof(terra_scenery_view_tile) == 32, "terra_scenery_view_tile layout");
+static_assert((uint32_t)TERRA_SCV_GROUPS == terra::SCV_GROUPS && (int)TERRA_SCV_ENGINE == (int)terra::SCV_ENGINE && (int)TERRA_SCV_BERRIES == (int)terra::SCV_BERRIES &&
+              (int)TERRA_SCV_G_PLD_LINES == (int)terra::SCV_G_PLD_LINES, "TERRA_SCV_* mirror terra_sceneryview.hpp");
+int terra_tiles_scenery_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                                 const terra_scenery_view_args *args, const terra_tile_stats *d_stats, const uint8_t *d_skip, const terra_scenery_place *d_objs,
+                                 const uint32_t *d_counts, uint32_t capacity, const float *d_radius_override, terra_scenery_view_tile *d_tile_out, uint32_t *d_draw,
+                                 float *d_size_scale, float *d_dist, uint32_t *d_list, uint32_t list_capacity, uint32_t *d_group_counts) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::scenery_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY ctx->eng.tiles_scenery_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, d_stats, d_skip, (terra::scenery_place_pod_t const *)d_objs, d_counts, capacity,
+		d_radius_override, (terra::scenery_view_tile_pod_t *)d_tile_out, d_draw, d_size_scale, d_dist, d_list, list_capacity, d_group_counts); TERRA_CATCH
+}
+int terra_tiles_scenery_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                             const terra_scenery_view_args *args, const terra_tile_stats *h_stats, const uint8_t *h_skip, const terra_scenery_place *h_objs,
+                             const uint32_t *h_counts, uint32_t capacity, const float *h_radius_override, terra_scenery_view_tile *h_tile_out, uint32_t *h_draw,
+                             float *h_size_scale, float *h_dist, uint32_t *h_list, uint32_t list_capacity, uint32_t *h_group_counts) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::scenery_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.scenery_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
+		if ((uint64_t)n*capacity > 0xFFFFFFFFull || (uint64_t)n*list_capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_scenery_view: n*capacity and n*list_capacity must fit 32 bits");
+		if (n == 0) return TERRA_OK;
+		if (!tile_xy || !h_stats || !h_counts || !h_tile_out || !h_group_counts || (capacity && (!h_objs || !h_draw || !h_size_scale || !h_dist)) || (list_capacity && !h_list)) {
+			return terra::fail(TERRA_ERR_ARG, "null argument");
+		}
+		size_t const nc = (size_t)n*capacity, nl = (size_t)n*list_capacity;
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), sk = st.opt_in(h_skip, n), ob = st.in(h_objs, nc*sizeof(terra_scenery_place)), pc = st.in(h_counts, (size_t)n*4),
+			ov = st.opt_in(h_radius_override, nc*4), to = st.out(h_tile_out, (size_t)n*sizeof(terra_scenery_view_tile)), dr = st.temp(nc*4), sz = st.temp(nc*4), di = st.temp(nc*4),
+			ll = st.temp(nl*4), gc = st.out(h_group_counts, (size_t)n*TERRA_SCV_GROUPS*4);
+		st.begin();
+		ctx->eng.tiles_scenery_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, st.dev<terra_tile_stats>(s), st.dev<uint8_t>(sk), st.dev<terra::scenery_place_pod_t>(ob),
+			st.dev<uint32_t>(pc), capacity, st.dev<float>(ov), st.dev<terra::scenery_view_tile_pod_t>(to), st.dev<uint32_t>(dr), st.dev<float>(sz), st.dev<float>(di), st.dev<uint32_t>(ll),
+			list_capacity, st.dev<uint32_t>(gc));
+		st.end();
+		for (uint32_t t = 0; t < n; ++t) { // of every tile only what its record names: the rest of the caller's arrays stays as it was
+			size_t const o = (size_t)t*capacity, lo = (size_t)t*list_capacity;
+			uint32_t const nr = std::min(h_tile_out[t].num_records, capacity), nw = std::min(h_tile_out[t].list_written, list_capacity);
+			if (nr) {
+				ctx->eng.be.d2h(h_draw + o, st.dev<uint32_t>(dr) + o, (size_t)nr*4);
+				ctx->eng.be.d2h(h_size_scale + o, st.dev<float>(sz) + o, (size_t)nr*4);
+				ctx->eng.be.d2h(h_dist + o, st.dev<float>(di) + o, (size_t)nr*4);
+			}
+			if (nw) {ctx->eng.be.d2h(h_list + lo, st.dev<uint32_t>(ll) + lo, (size_t)nw*4);}
+		}
+	TERRA_CATCH
+}
 int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
 	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.set_tree_size_params(*params); TERRA_CATCH

@@ -22,6 +22,7 @@
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_treeview.hpp"
+#include "terra_sceneryview.hpp"
 #include "terra_stage.hpp"
 #include "../../include/terra.h"
 #include <vector>
@@ -3312,6 +3313,71 @@ template<class BE> struct terra_engine {
 			d_tile_out[t] = tl.out;
 			d_inst_counts[2*t] = npi; d_inst_counts[2*t + 1] = nmi;
 			d_leaf_counts[2*t] = tl.pine_list ? nl : tree_view_render_all(c, tl); d_leaf_counts[2*t + 1] = nm;
+		});
+	}
+
+	// ---- the scenery draw lists of a batch for a camera (terra_sceneryview.hpp): tile_t::draw_scenery (src/tiled_mesh.cpp:1580-1592) with scenery_group's
+	// draw_opaque_objects and draw_plant_leaves and the per-object draw methods under them, over the records as the placement keeps them.
+	// The checks that need no array (the host form runs them before it stages anything):
+	void scenery_view_check(view_pod_t const &view, scenery_view_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_scenery_view: a member of the view is not finite");
+		if (!scenery_view_args_finite(a)) throw std::invalid_argument("tiles_scenery_view: a member of the args is not finite");
+		if (!scenery_view_args_ok(a)) throw std::invalid_argument("tiles_scenery_view: window_width and zoom_f, and smap_pixel_width under shadow_pass, must be > 0");
+		if (a.reflection_pass != 0 && a.reflection_pass != 1) throw std::invalid_argument("tiles_scenery_view: reflection_pass must be 0 or 1");
+	}
+	void tiles_scenery_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, scenery_view_args_pod_t const &a,
+		terra_tile_stats const *d_stats, uint8_t const *d_skip, scenery_place_pod_t const *d_objs, uint32_t const *d_counts, uint32_t capacity, float const *d_rov,
+		scenery_view_tile_pod_t *d_tile_out, uint32_t *d_draw, float *d_size_scale, float *d_dist, uint32_t *d_list, uint32_t list_capacity, uint32_t *d_group_counts)
+	{
+		scenery_view_check(view, a);
+		if ((uint64_t)n*capacity > 0xFFFFFFFFull || (uint64_t)n*list_capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_scenery_view: n*capacity and n*list_capacity must fit 32 bits");
+		if (n == 0) return;
+		if (!tile_xy || !d_stats || !d_counts || !d_tile_out || !d_group_counts || (capacity && (!d_objs || !d_draw || !d_size_scale || !d_dist)) || (list_capacity && !d_list)) {
+			throw std::invalid_argument("tiles_scenery_view: null argument");
+		}
+		if ((((uintptr_t)d_stats | (uintptr_t)d_objs | (uintptr_t)d_counts | (uintptr_t)d_rov | (uintptr_t)d_tile_out | (uintptr_t)d_draw | (uintptr_t)d_size_scale | (uintptr_t)d_dist |
+		      (uintptr_t)d_list | (uintptr_t)d_group_counts) & 3u) != 0) {
+			throw std::invalid_argument("tiles_scenery_view: every array but skip must be 4-byte aligned");
+		}
+		float const offx = (float)add_wrap(dxoff, xoff2)*DX_VAL, offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // scenery_off.get_xlate()
+		scenery_view_consts_t const c = scenery_view_consts(view, a, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, offx, offy, water_plane_z,
+			get_water_z_height() - ocean_wave_height, tp.tree_scale, capacity, list_capacity);
+		int32_t *d_txy_w;
+		stage_layout_t lay;
+		lay.add(d_txy_w, (size_t)n*2);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy_w, tile_xy, (size_t)n*8);
+		int32_t const *d_txy = d_txy_w;
+		if constexpr (BE::has_kernels) {
+			if (be.tile_scenery_view(c, d_txy, n, d_stats, d_skip, d_objs, d_counts, d_rov, d_tile_out, d_draw, d_size_scale, d_dist, d_list, d_group_counts)) return;
+		}
+		// the simple form: a logical thread per tile walks its records, then once per stream for the lists
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint32_t const cnt = (d_skip && d_skip[t]) ? 0u : min_u32(d_counts[t], c.cap);
+			scenery_view_tile_pod_t o; o.dist_scale = 0.0f; o.scale_val = 0.0f; o.flags = o.num_records = o.list_written = 0u; o.pad[0] = o.pad[1] = o.pad[2] = 0u;
+			uint32_t groups[SCV_GROUPS];
+			for (uint32_t g = 0; g < SCV_GROUPS; ++g) {groups[g] = 0u;}
+			float ds = 0.0f;
+			if (cnt != 0u && scenery_view_tile(c, d_txy[2*t], d_txy[2*t + 1], d_stats[t].mzmin, d_stats[t].mzmax, d_stats[t].radius, ds)) {
+				scenery_place_pod_t const *const recs = d_objs + t*c.cap;
+				for (uint32_t j = 0; j < cnt; ++j) {
+					scenery_view_rec_t const r = scenery_view_record(c, recs[j], d_rov ? d_rov[t*c.cap + j] : 0.0f);
+					d_draw[t*c.cap + j] = r.word; d_size_scale[t*c.cap + j] = r.size_scale; d_dist[t*c.cap + j] = r.dist;
+				}
+				uint32_t at = 0;
+				for (uint32_t s = 0; s < SCV_STREAMS; ++s) { // a stable split of the record list
+					for (uint32_t j = 0; j < cnt; ++j) {
+						if (!((scenery_view_streams(recs[j].kind, d_draw[t*c.cap + j]) >> s) & 1u)) continue;
+						if (at < c.list_cap) {d_list[t*c.list_cap + at] = j;}
+						++at; ++groups[scenery_view_group(s)];
+					}
+				}
+				o.dist_scale = ds; o.scale_val = c.scale_val; o.flags = scenery_view_tile_flags(c); o.num_records = cnt; o.list_written = min_u32(at, c.list_cap);
+			}
+			d_tile_out[t] = o;
+			for (uint32_t g = 0; g < SCV_GROUPS; ++g) {d_group_counts[t*SCV_GROUPS + g] = groups[g];}
 		});
 	}
 

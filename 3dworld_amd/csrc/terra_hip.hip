@@ -636,6 +636,13 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		return launch_per_tile<terra::TRV_THREADS>(terra::k_tree_view, n, c, tile_xy, insts, stats, skip, trmax, pine, counts, ov, tile_out, bcube, pine_insts, palm_insts, inst_counts,
 			leaf_list, leaf_counts, trunk, keys);
 	}
+	// the scenery draw lists for a camera: one workgroup per tile (k_scenery_view)
+	bool tile_scenery_view(terra::scenery_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra_tile_stats const *stats, uint8_t const *skip,
+		terra::scenery_place_pod_t const *objs, uint32_t const *counts, float const *rov, terra::scenery_view_tile_pod_t *tile_out, uint32_t *draw, float *size_scale, float *dist,
+		uint32_t *list, uint32_t *group_counts)
+	{
+		return launch_per_tile<terra::SCVW_THREADS>(terra::k_scenery_view, n, c, tile_xy, stats, skip, objs, counts, rov, tile_out, draw, size_scale, dist, list, group_counts);
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (opt->simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

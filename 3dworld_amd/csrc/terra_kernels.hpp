@@ -2404,6 +2404,114 @@ __global__ __launch_bounds__(TRV_THREADS) void k_tree_view(tree_view_consts_t c,
 	}
 }
 
+// ------------------------------------------------------------------ the scenery draw lists of a tile batch for a camera (tile_t::draw_scenery, src/tiled_mesh.cpp:1580-1592;
+// terra_sceneryview.hpp).  k_scenery_view: a workgroup of 256 lanes per tile.
+//  1. One lane reads the tile's centre and radius, forms get_scenery_dist_scale() and broadcasts the decision through LDS: a dropped tile -- most tiles of a large
+//     batch -- leaves here, like a skipped or an empty one, with a zero record and zero counts.
+//  2. A sweep over the tile's records, a lane a record: the draw word, size_scale and dist of every record (scenery_view_record), and the number of records in each of
+//     the 16 streams (the 13 groups with the pld groups split by kind) -- a ballot per stream, lane s of a wave keeps the wave's count of stream s.  The counts of
+//     the waves meet in LDS; one lane turns them into the streams' starts and writes group_counts and the tile record.
+//  3. A second sweep in chunks of 256 records: a record's streams follow from its kind and its own draw word; per chunk and stream a ballot ranks the lanes of a wave,
+//     the waves' counts of the chunk give the start of a wave, and the running starts advance by the chunk's totals.  So every list comes out in record order for any
+//     number of records, and no atomic decides a position.  tp_block_rank would rank one stream with two barriers; the 16 streams share three barriers per chunk here.
+constexpr uint32_t SCVW_THREADS = 256, SCVW_WAVES = SCVW_THREADS/64;
+static_assert(SCV_STREAMS <= 64, "lane s of a wave counts stream s");
+__global__ __launch_bounds__(SCVW_THREADS) void k_scenery_view(scenery_view_consts_t c, int32_t const *__restrict__ tile_xy, terra_tile_stats const *__restrict__ stats,
+	uint8_t const *__restrict__ skip, scenery_place_pod_t const *__restrict__ objs, uint32_t const *__restrict__ counts, float const *__restrict__ rov,
+	scenery_view_tile_pod_t *__restrict__ tile_out, uint32_t *draw, float *__restrict__ size_scale, float *__restrict__ dist, uint32_t *__restrict__ list,
+	uint32_t *__restrict__ group_counts)
+{
+	__shared__ uint32_t s_w[SCVW_WAVES][SCV_STREAMS], s_base[SCV_STREAMS], s_total;
+	__shared__ float s_dist_scale;
+	__shared__ int s_go;
+	uint32_t const t = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	uint32_t const cnt = (skip && skip[t]) ? 0u : min_u32(counts[t], c.cap); // (uniform)
+	auto leave_empty = [&] {
+		if (tid < SCV_GROUPS) {group_counts[(size_t)t*SCV_GROUPS + tid] = 0u;}
+		if (tid == 0) {scenery_view_tile_pod_t z; z.dist_scale = 0.0f; z.scale_val = 0.0f; z.flags = z.num_records = z.list_written = 0u; z.pad[0] = z.pad[1] = z.pad[2] = 0u; tile_out[t] = z;}
+	};
+	if (cnt == 0u) {leave_empty(); return;}
+	// 1. the tile
+	if (tid == 0) {
+		terra_tile_stats const &st = stats[t];
+		float ds;
+		s_go = scenery_view_tile(c, tile_xy[2u*t], tile_xy[2u*t + 1u], st.mzmin, st.mzmax, st.radius, ds) ? 1 : 0;
+		s_dist_scale = ds;
+	}
+	__syncthreads();
+	if (!s_go) {leave_empty(); return;} // (uniform)
+	scenery_place_pod_t const *const recs = objs + (size_t)t*c.cap;
+	size_t const o0 = (size_t)t*c.cap;
+	// 2. the records
+	uint32_t mine = 0;
+	for (uint32_t base = 0; base < cnt; base += SCVW_THREADS) {
+		uint32_t const i = base + tid;
+		uint32_t streams = 0;
+		if (i < cnt) {
+			scenery_view_rec_t const r = scenery_view_record(c, recs[i], rov ? rov[o0 + i] : 0.0f);
+			draw[o0 + i] = r.word; size_scale[o0 + i] = r.size_scale; dist[o0 + i] = r.dist;
+			streams = r.streams;
+		}
+#pragma unroll
+		for (uint32_t s = 0; s < SCV_STREAMS; ++s) {
+			uint32_t const m = (uint32_t)__popcll(__ballot((streams >> s) & 1u));
+			if (lane == s) {mine += m;}
+		}
+	}
+	if (lane < SCV_STREAMS) {s_w[wave][lane] = mine;}
+	__syncthreads();
+	if (tid == 0) {
+		uint32_t at = 0, groups[SCV_GROUPS];
+#pragma unroll
+		for (uint32_t g = 0; g < SCV_GROUPS; ++g) {groups[g] = 0u;}
+#pragma unroll
+		for (uint32_t s = 0; s < SCV_STREAMS; ++s) {
+			uint32_t m = 0;
+			for (uint32_t w = 0; w < SCVW_WAVES; ++w) {m += s_w[w][s];}
+			s_base[s] = at; at += m;
+			groups[scenery_view_group(s)] += m;
+		}
+#pragma unroll
+		for (uint32_t g = 0; g < SCV_GROUPS; ++g) {group_counts[(size_t)t*SCV_GROUPS + g] = groups[g];}
+		s_total = at;
+		scenery_view_tile_pod_t o;
+		o.dist_scale = s_dist_scale; o.scale_val = c.scale_val; o.flags = scenery_view_tile_flags(c); o.num_records = cnt; o.list_written = min_u32(at, c.list_cap);
+		o.pad[0] = o.pad[1] = o.pad[2] = 0u;
+		tile_out[t] = o;
+	}
+	__syncthreads();
+	if (s_total == 0u || c.list_cap == 0u) return; // (uniform)
+	// 3. the lists
+	uint32_t *const ll = list + (size_t)t*c.list_cap;
+	uint64_t const below = (1ull << lane) - 1ull;
+	for (uint32_t base = 0; base < cnt; base += SCVW_THREADS) {
+		uint32_t const i = base + tid;
+		uint32_t const streams = (i < cnt) ? scenery_view_streams(recs[i].kind, draw[o0 + i]) : 0u; // (the lane reads the word it wrote)
+#pragma unroll
+		for (uint32_t s = 0; s < SCV_STREAMS; ++s) {
+			uint32_t const m = (uint32_t)__popcll(__ballot((streams >> s) & 1u));
+			if (lane == s) {s_w[wave][s] = m;}
+		}
+		__syncthreads();
+#pragma unroll
+		for (uint32_t s = 0; s < SCV_STREAMS; ++s) {
+			uint64_t const m = __ballot((streams >> s) & 1u);
+			if ((streams >> s) & 1u) {
+				uint32_t at = s_base[s] + (uint32_t)__popcll(m & below);
+				for (uint32_t w = 0; w < wave; ++w) {at += s_w[w][s];}
+				if (at < c.list_cap) {ll[at] = i;}
+			}
+		}
+		__syncthreads(); // every start is read
+		if (tid < SCV_STREAMS) {
+			uint32_t m = 0;
+			for (uint32_t w = 0; w < SCVW_WAVES; ++w) {m += s_w[w][tid];}
+			s_base[tid] += m;
+		}
+		__syncthreads(); // before the next chunk's counts
+	}
+}
+
 // ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
 // terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
 // k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes

@@ -185,6 +185,29 @@ TRV_NEAR_LEAVES, TRV_FAR_LEAVES, TRV_DITHERED, TRV_PALMS, TRV_DRAW_ALL_NEAR, TRV
 TRV_ALL_VISIBLE, TRV_NEEDS_HIGH, TRV_NEEDS_LOW, TRV_CONTAINS_CAMERA = 0x100, 0x200, 0x400, 0x800
 
 
+class SceneryViewArgs(C.Structure):  # terra_scenery_view_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("zoom_f", C.c_float), ("smap_pixel_width", C.c_float), ("window_width", C.c_int32), ("shadow_pass", C.c_int32),
+                ("reflection_pass", C.c_int32), ("uw_skip", C.c_int32), ("skip_small_shadow_objs", C.c_int32), ("draw_opaque", C.c_int32), ("draw_leaves", C.c_int32)]
+
+
+def make_scenery_view_args(behind_sphere_mult=1.0, zoom_f=1.0, smap_pixel_width=0.0, window_width=1920, shadow_pass=0, reflection_pass=0, uw_skip=1, skip_small_shadow_objs=0,
+                           draw_opaque=1, draw_leaves=1):
+    """terra_scenery_view_args: behind_sphere_mult as for the terrain view; draw_opaque / draw_leaves: the two sweeps of tile_draw_t::draw_scenery, in any combination"""
+    return SceneryViewArgs(behind_sphere_mult, zoom_f, smap_pixel_width, window_width, int(bool(shadow_pass)), int(reflection_pass), int(bool(uw_skip)),
+                           int(bool(skip_small_shadow_objs)), int(bool(draw_opaque)), int(bool(draw_leaves)))
+
+
+SCENERY_VIEW_TILE_DTYPE = np.dtype([("dist_scale", np.float32), ("scale_val", np.float32), ("flags", np.uint32), ("num_records", np.uint32), ("list_written", np.uint32),
+                                    ("pad", np.uint32, (3,))])  # terra_scenery_view_tile
+assert SCENERY_VIEW_TILE_DTYPE.itemsize == 32 and C.sizeof(SceneryViewArgs) == 40
+SCV_NONE, SCV_POINT, SCV_LINE, SCV_POLY, SCV_ENGINE, SCV_FORM_MASK = 0, 1, 2, 3, 7, 7  # bits 0-2 of a draw word of tiles_scenery_view
+SCV_LOG_END, SCV_LOG_END2, SCV_STUMP_TOP, SCV_CAP_UNDERSIDE, SCV_LEAVES, SCV_UNDERWATER, SCV_BERRIES = 0x8, 0x10, 0x20, 0x40, 0x80, 0x4000, 0x8000
+SCV_NDIV_SHIFT, SCV_NDIV_MASK, SCV_BERRY_NDIV_SHIFT = 8, 0x3F, 16
+SCV_TILE_DRAWN, SCV_TILE_OPAQUE, SCV_TILE_LEAVES = 1, 2, 4  # the flags word of terra_scenery_view_tile
+SCV_GROUPS = ("rock_shape", "surface_rock", "rock", "log", "stump", "mushroom", "stem", "berries", "voxel_rock", "plant_leaves", "leafy_leaves", "pld_points",
+              "pld_lines")  # TERRA_SCV_G_*
+
+
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
@@ -387,6 +410,8 @@ _PROTOS = {
     "terra_tiles_terrain_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_tree_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_tree_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_scenery_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_scenery_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -1066,6 +1091,34 @@ class Terra:
         return dict(tile=mk((n,), TREE_VIEW_TILE_DTYPE), all_bcube=mk((n, 6), np.float32), pine_insts=mk((n, cap), TREE_VIEW_INST_DTYPE), palm_insts=mk((n, cap), TREE_VIEW_INST_DTYPE),
                     inst_counts=mk((n, 2), np.uint32), leaf_list=mk((n, cap), np.uint32), leaf_counts=mk((n, 2), np.uint32), trunk=mk((n, cap), np.uint8))
 
+    def tiles_scenery_view(self, tile_xy, stats, view, args, objs, counts, list_capacity=None, skip=None, radius_override=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0, fill=0):
+        """tile_t::draw_scenery for every tile: objs SCENERY_PLACE_DTYPE [n, cap] with counts [n]; stats TileStats * n; skip [n] bytes and radius_override [n, cap]
+        float32 optional; list_capacity defaults to 3*cap.  The [n, cap] and [n, list_capacity] outputs start filled with the byte `fill`; entries past the counts keep it.
+        -> dict(tile SCENERY_VIEW_TILE_DTYPE [n], draw uint32 [n, cap], size_scale / dist float32 [n, cap], list uint32 [n, list_capacity], group_counts uint32
+        [n, len(SCV_GROUPS)])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        ob = np.ascontiguousarray(objs, SCENERY_PLACE_DTYPE).reshape(n, -1)
+        cap = ob.shape[1]
+        lcap = 3 * cap if list_capacity is None else int(list_capacity)
+        pc = np.ascontiguousarray(counts, np.uint32).reshape(n)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        ov = None if radius_override is None else np.ascontiguousarray(radius_override, np.float32).reshape(n, cap)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        out = self._scenery_view_outputs(n, cap, lcap, fill)
+        o = [out[k].ctypes.data for k in self.SCENERY_VIEW_OUTPUTS]
+        self._ck(self.lib.terra_tiles_scenery_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), C.addressof(stats) if n else None, ptr(sk),
+                                                   ob.ctypes.data, pc.ctypes.data, cap, ptr(ov), *o[:5], lcap, o[5]))
+        return out
+
+    SCENERY_VIEW_OUTPUTS = ("tile", "draw", "size_scale", "dist", "list", "group_counts")  # (list_capacity stands between the last two in the C signature)
+
+    @staticmethod
+    def _scenery_view_outputs(n, cap, list_cap, fill=0):
+        mk = lambda shape, dt: np.frombuffer(bytearray([fill]) * (int(np.prod(shape)) * np.dtype(dt).itemsize), dt).reshape(shape)  # noqa: E731
+        return dict(tile=mk((n,), SCENERY_VIEW_TILE_DTYPE), draw=mk((n, cap), np.uint32), size_scale=mk((n, cap), np.float32), dist=mk((n, cap), np.float32),
+                    list=mk((n, list_cap), np.uint32), group_counts=mk((n, len(SCV_GROUPS)), np.uint32))
+
     def set_tree_size_params(self, tsp):
         self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
 
@@ -1356,6 +1409,16 @@ class Terra:
         self._ck(self.lib.terra_tiles_tree_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), stats_ptr, skip_ptr, trmax_ptr,
                                                     pine_ptr, pine_counts_ptr, capacity, trunk_override_ptr, tile_out_ptr, all_bcube_ptr, pine_insts_ptr, palm_insts_ptr,
                                                     inst_counts_ptr, leaf_list_ptr, leaf_counts_ptr, trunk_ptr))
+
+    def tiles_scenery_view_dev(self, tile_xy, view, args, stats_ptr, objs_ptr, counts_ptr, capacity, tile_out_ptr, draw_ptr, size_scale_ptr, dist_ptr, list_ptr, list_capacity,
+                               group_counts_ptr, skip_ptr=None, radius_override_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):
+        """the scenery draw lists of a device-resident batch, from the records tiles_place_scenery_dev left on the device: tile_out_ptr [n] terra_scenery_view_tile,
+        draw_ptr [n][capacity] uint32, size_scale_ptr / dist_ptr [n][capacity] floats, list_ptr [n][list_capacity] uint32, group_counts_ptr [n][len(SCV_GROUPS)] uint32;
+        skip_ptr [n] bytes (the terrain view's not_drawn), radius_override_ptr [n][capacity] floats or None.  view and args are host structs.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_scenery_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), stats_ptr, skip_ptr, objs_ptr,
+                                                       counts_ptr, capacity, radius_override_ptr, tile_out_ptr, draw_ptr, size_scale_ptr, dist_ptr, list_ptr, list_capacity,
+                                                       group_counts_ptr))
 
     def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
                                   decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,

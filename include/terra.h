@@ -1183,6 +1183,76 @@ int  terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
                            float *h_all_bcube, terra_tree_view_inst *h_pine_insts, terra_tree_view_inst *h_palm_insts, uint32_t *h_inst_counts, uint32_t *h_leaf_list,
                            uint32_t *h_leaf_counts, uint8_t *h_trunk);
 
+/* ---- the scenery draw lists of a tile batch for a camera (every supported tile size S): tile_t::draw_scenery (src/tiled_mesh.cpp:1580-1592) for every tile, without
+ * its GL, shader and colour calls, over the records terra_tiles_place_scenery[_dev] leaves -- so that a frame's stream is zvals -> placements -> ... -> tree draw
+ * lists -> scenery draw lists, with nothing read back but the lists.  One call answers both sweeps of tile_draw_t::draw_scenery (args.draw_opaque / draw_leaves).
+ * Restated with the source's operand types: scenery_group::draw_opaque_objects and draw_plant_leaves (src/scenery.cpp:1413-1500), rock_shape3d::draw (:300-305),
+ * surface_rock::draw (:394-417), s_rock::draw (:442-461), voxel_rock::draw (:517-530), s_log::draw (:606-632), s_stump::draw (:670-693), s_plant::draw_stem,
+ * draw_leaves and draw_berries (:853-871, 898-934), leafy_plant::draw_leaves (:1030-1045), mushroom::draw (:1062-1081), scenery_obj::check_visible / is_visible /
+ * get_size_scale (:122-135; the float pow with scale_exp 8.0), skip_uw_draw and get_pt_line_thresh (:61-74), the get_bsphere_radius() overrides, get_scenery_thresh /
+ * get_scenery_dist_scale (src/tiled_mesh.h:333-334) over get_dist_to_camera_in_tiles(0), get_tile_width, get_def_smap_ndiv (src/shadow_map.cpp:57-64) and
+ * distance_to_camera.  sscale is the int of :1456 taken as the float parameter of every draw(); 2.0*sscale*radius/dist, 0.5*radius/approx_pixel_width,
+ * 0.75*get_pt_line_thresh()*radius, 1000.0*radius and the 0.5*height / 0.1*(..) terms are formed in double, 2*get_pt_line_thresh()*radius in float.  In tiled-terrain
+ * mode check_visible is camera_pdu.sphere_visible_test alone, in the shadow pass too, and sphere_in_camera_view(.., 2) is the same test.  next_frame, burn_amt,
+ * is_shadowed and the colours stay with the engine.
+ * Inputs.  tile_xy on the host; dxoff / dyoff and xoff2 / yoff2 as for terra_tiles_tree_view: xlate = scenery_off.get_xlate() = ((dxoff + xoff2)*DX_VAL,
+ * (dyoff + yoff2)*DY_VAL, 0).  stats [n] (mzmin, mzmax, radius).  skip [n] bytes (optional): !scenery.generated, or the tile is not in to_draw -- the not_drawn
+ * bytes of terra_tiles_terrain_view plug in.  objs [n][capacity] with counts [n] as the placement wrote them; a count above the capacity means the first `capacity`
+ * records.  radius_override [n][capacity] floats (optional): an entry > 0 replaces the record's radius -- voxel_rock::build_model divides the radius by the model's
+ * bounding radius, and a rock_shape3d record carries radius 0 because gen_rock runs in the engine; a rock_shape with an override also gets pos.z += 0.1*radius (:156).
+ * A rock_shape without an override is not decided: its draw word is TERRA_SCV_ENGINE and it enters no list.  water_plane_z and get_min_water_plane_z() are the
+ * scene's, tree_scale comes from terra_tree_params.
+ * Per tile: get_scenery_dist_scale(reflection_pass) > 1.0 drops the tile; scale_val = get_scenery_thresh(reflection_pass)*get_tile_width().  tile_out [n]:
+ * dist_scale, scale_val, flags (TERRA_SCV_TILE_DRAWN, _OPAQUE / _LEAVES: which sweeps ran), num_records = min(counts, capacity), list_written = the entries of `list`
+ * that were written.  A skipped, dropped or empty tile gets a zero record and zero group_counts, and nothing else of it is written.
+ * Per record of every other tile, in record order: draw [n][capacity] words.  Bits 0-2 the opaque form: 0 not drawn, TERRA_SCV_POINT a point in tree_scenery_pld
+ * (surface rocks and rocks beyond 2*get_pt_line_thresh()*radius), TERRA_SCV_LINE a line in it (logs, stumps, plant stems), TERRA_SCV_POLY polygons, TERRA_SCV_ENGINE.
+ * Bits 8-13 ndiv of the polygon form (0 for rock_shape, surface_rock and voxel_rock, which have none).  TERRA_SCV_LOG_END: the log's end cap is drawn (:623), with
+ * TERRA_SCV_LOG_END2 the end at pt2 (radius2), else the end at pos; TERRA_SCV_STUMP_TOP (:687); TERRA_SCV_CAP_UNDERSIDE (:1077); TERRA_SCV_LEAVES: the leaves of a
+ * plant or a leafy plant are drawn; TERRA_SCV_UNDERWATER: the leafy plant's is_underwater (:1035); TERRA_SCV_BERRIES: the plant passes draw_berries up to
+ * berries.empty(), which the engine knows, with the berries' ndiv in bits 16-21.  A record whose kind is none of TERRA_SCENERY_* gets 0.
+ * size_scale [n][capacity] floats: get_size_scale(dist, scale_val) of a surface rock, rock or voxel rock drawn as polygons (the engine multiplies by scale,
+ * size*scale or radius), 0 elsewhere.  dist [n][capacity] floats: the distance_to_camera the kind computes (a plant: of the stem or the berries, the same point), 0
+ * where the record was culled before it or the kind computes none (rock_shape, leafy plants, a plant in a leaves-only call).
+ * Logs and stumps are not drawn when shadow_pass && skip_small_shadow_objs (:1471); mushrooms and berries are not drawn in the shadow pass; the water-plant
+ * conditions of :855 and :901 read the record's iv[0] against NUM_LAND_PLANT_TYPES.
+ * Lists.  list [n][list_capacity] record indices with group_counts [n][TERRA_SCV_GROUPS], the groups in the order in which the reference issues them: rock_shape,
+ * surface_rock, rock, log, stump, mushroom, plant stem (polygon forms only), berries, voxel_rock, plant leaves, leafy-plant leaves, pld points (surface rocks, then
+ * rocks), pld lines (logs, stumps, stems).  Within a group, and within each kind inside the two pld groups, the order is record order: the order of the reference's
+ * per-kind vectors.  A group's entries start at the sum of the counts before it; only the first list_capacity entries of a tile are written, group_counts still
+ * reports all, entries past the counts are never written.  A plant can appear in three groups: 3*capacity always suffices.
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or the args; window_width or zoom_f not > 0; smap_pixel_width not > 0 under shadow_pass;
+ * reflection_pass other than 0 or 1; a NULL required pointer (view, args; tile_xy, stats, counts, tile_out, group_counts when n > 0; objs, draw, size_scale, dist
+ * when capacity > 0 as well; list when list_capacity > 0); a pointer other than skip that is not 4-byte aligned; an unsupported S; n*capacity or n*list_capacity
+ * beyond 32 bits.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.  The device form only enqueues and reads nothing
+ * back; tile_xy is a host array in both forms.  Scratch comes from the context's arena. */
+typedef struct terra_scenery_view_args {
+	float behind_sphere_mult;   /* as for terra_tiles_terrain_view */
+	float zoom_f;               /* do_zoom ? ZOOM_FACTOR : 1 */
+	float smap_pixel_width;     /* approx_pixel_width(shadow_map_sz); read only when shadow_pass */
+	int32_t window_width;
+	int32_t shadow_pass;        /* shadow_only */
+	int32_t reflection_pass;    /* 0 or 1: the bool of tile_t::draw_scenery */
+	int32_t uw_skip;            /* !DISABLE_WATER && (display_mode & 0x04): skip_uw_draw's gate */
+	int32_t skip_small_shadow_objs; /* can_skip_small_shadow_objs() */
+	int32_t draw_opaque, draw_leaves; /* the two sweeps of tile_draw_t::draw_scenery, in any combination */
+} terra_scenery_view_args;      /* 40 bytes */
+typedef struct terra_scenery_view_tile {float dist_scale, scale_val; uint32_t flags, num_records, list_written, pad[3];} terra_scenery_view_tile; /* 32 bytes */
+enum {TERRA_SCV_NONE = 0, TERRA_SCV_POINT = 1, TERRA_SCV_LINE = 2, TERRA_SCV_POLY = 3, TERRA_SCV_ENGINE = 7, TERRA_SCV_FORM_MASK = 7,
+      TERRA_SCV_LOG_END = 0x8, TERRA_SCV_LOG_END2 = 0x10, TERRA_SCV_STUMP_TOP = 0x20, TERRA_SCV_CAP_UNDERSIDE = 0x40, TERRA_SCV_LEAVES = 0x80,
+      TERRA_SCV_NDIV_SHIFT = 8, TERRA_SCV_NDIV_MASK = 0x3F, TERRA_SCV_UNDERWATER = 0x4000, TERRA_SCV_BERRIES = 0x8000, TERRA_SCV_BERRY_NDIV_SHIFT = 16};
+enum {TERRA_SCV_TILE_DRAWN = 1, TERRA_SCV_TILE_OPAQUE = 2, TERRA_SCV_TILE_LEAVES = 4};
+enum {TERRA_SCV_G_ROCK_SHAPE, TERRA_SCV_G_SURFACE_ROCK, TERRA_SCV_G_ROCK, TERRA_SCV_G_LOG, TERRA_SCV_G_STUMP, TERRA_SCV_G_MUSHROOM, TERRA_SCV_G_STEM, TERRA_SCV_G_BERRIES,
+      TERRA_SCV_G_VOXEL_ROCK, TERRA_SCV_G_PLANT_LEAVES, TERRA_SCV_G_LEAFY_LEAVES, TERRA_SCV_G_PLD_POINTS, TERRA_SCV_G_PLD_LINES, TERRA_SCV_GROUPS};
+int  terra_tiles_scenery_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                                  const terra_scenery_view_args *args, const terra_tile_stats *d_stats, const uint8_t *d_skip, const terra_scenery_place *d_objs,
+                                  const uint32_t *d_counts, uint32_t capacity, const float *d_radius_override, terra_scenery_view_tile *d_tile_out, uint32_t *d_draw,
+                                  float *d_size_scale, float *d_dist, uint32_t *d_list, uint32_t list_capacity, uint32_t *d_group_counts);
+int  terra_tiles_scenery_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                              const terra_scenery_view_args *args, const terra_tile_stats *h_stats, const uint8_t *h_skip, const terra_scenery_place *h_objs,
+                              const uint32_t *h_counts, uint32_t capacity, const float *h_radius_override, terra_scenery_view_tile *h_tile_out, uint32_t *h_draw,
+                              float *h_size_scale, float *h_dist, uint32_t *h_list, uint32_t list_capacity, uint32_t *h_group_counts);
+
 
 /* ---- plumbing for callers without a HIP runtime of their own (tests, ctypes) */
 int  terra_malloc(terra_ctx *ctx, void **d_ptr, size_t bytes);

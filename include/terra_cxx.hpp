@@ -409,6 +409,24 @@ inline void tile_draw_pine_tree_lists(tile_batch_dev_t const &b, int xoff2, int 
 	check(terra_tiles_tree_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, &camera_pdu, &args, b.d_stats, d_not_drawn, d_trmax, d_pine_trees, d_pine_counts,
 		capacity, d_trunk_override, d_tile_out, d_all_bcube, d_pine_insts, d_palm_insts, d_inst_counts, d_leaf_list, d_leaf_counts, d_trunk), "tile_t::draw_pine_trees");
 }
+// ---- the scenery draw lists of a batch for the camera: tile_t::draw_scenery (src/tiled_mesh.cpp:1580-1592) for every tile, without its GL, shader and colour calls,
+// from the records tiles_gen_scenery left on the device.  One call answers both sweeps of tile_draw_t::draw_scenery (args.draw_opaque / draw_leaves).  d_not_drawn:
+// tile_draw_lists' output (or null); d_radius_override: voxel_rock::build_model's and gen_rock's radii (or null).  d_draw holds one TERRA_SCV_* word per record,
+// d_list record indices in TERRA_SCV_GROUPS groups per tile in the order draw_opaque_objects and draw_plant_leaves issue them
+inline terra_scenery_view_args scenery_view_args_of(float behind_sphere_mult, bool shadow_only, bool reflection_pass, int window_width, float zoom_f, float smap_pixel_width,
+	bool uw_skip, bool can_skip_small_shadow_objs, bool draw_opaque, bool draw_leaves)
+{
+	terra_scenery_view_args const a = {behind_sphere_mult, zoom_f, smap_pixel_width, window_width, shadow_only ? 1 : 0, reflection_pass ? 1 : 0, uw_skip ? 1 : 0,
+		can_skip_small_shadow_objs ? 1 : 0, draw_opaque ? 1 : 0, draw_leaves ? 1 : 0};
+	return a;
+}
+inline void tile_draw_scenery_lists(tile_batch_dev_t const &b, int xoff2, int yoff2, terra_view const &camera_pdu, terra_scenery_view_args const &args, unsigned char const *d_not_drawn,
+	terra_scenery_place const *d_scenery, unsigned const *d_counts, unsigned capacity, float const *d_radius_override, terra_scenery_view_tile *d_tile_out, unsigned *d_draw,
+	float *d_size_scale, float *d_dist, unsigned *d_list, unsigned list_capacity, unsigned *d_group_counts)
+{
+	check(terra_tiles_scenery_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, &camera_pdu, &args, b.d_stats, d_not_drawn, d_scenery, d_counts, capacity,
+		d_radius_override, d_tile_out, d_draw, d_size_scale, d_dist, d_list, list_capacity, d_group_counts), "tile_t::draw_scenery");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest
