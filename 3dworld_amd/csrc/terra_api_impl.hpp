@@ -1083,6 +1083,62 @@ int terra_tiles_scenery_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 		}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_decid_view_args) == sizeof(terra::decid_view_args_pod_t) && sizeof(terra_decid_view_args) == 48, "terra_decid_view_args layout");
+static_assert(sizeof(terra_decid_tree_data) == sizeof(terra::decid_tree_data_pod_t) && sizeof(terra_decid_tree_data) == 80, "terra_decid_tree_data layout");
+static_assert(sizeof(terra_decid_view_tile) == sizeof(terra::decid_view_tile_pod_t) && sizeof(terra_decid_view_tile) == 32, "terra_decid_view_tile layout");
+static_assert(sizeof(terra_decid_view_bb) == sizeof(terra::decid_view_bb_pod_t) && sizeof(terra_decid_view_bb) == 24, "terra_decid_view_bb layout");
+static_assert((int)TERRA_DCV_BRANCH_TEX == (int)terra::DCV_BRANCH_TEX && (int)TERRA_DCV_TILE_BCUBE_ZERO_AREA == (int)terra::DCV_TILE_BCUBE_ZERO_AREA &&
+              (int)TERRA_DCV_LOW_DETAIL == (int)terra::DCV_LOW_DETAIL && (int)TERRA_DCV_STAGE_SHADOW_SPHERE == (int)terra::DCV_STAGE_SHADOW_SPHERE &&
+              (int)TERRA_DCV_STAGE_SHIFT == (int)terra::DCV_STAGE_SHIFT, "TERRA_DCV_* mirror terra_decidview.hpp");
+int terra_tiles_decid_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                               const terra_decid_view_args *args, const terra_decid_tree_data *d_tree_data, uint32_t num_tree_data, const uint8_t *d_skip,
+                               const terra_decid_place *d_decid, const uint32_t *d_counts, uint32_t capacity, uint8_t *d_not_visible, terra_decid_view_tile *d_tile_out,
+                               float *d_all_bcube, uint32_t *d_leaf_word, float *d_leaf_scale, float *d_leaf_opacity, uint32_t *d_leaf_num, uint32_t *d_branch_word,
+                               float *d_branch_scale, float *d_branch_opacity, uint32_t *d_branch_num, uint32_t *d_leaf_list, uint32_t *d_branch_list,
+                               terra_decid_view_bb *d_leaf_bb, terra_decid_view_bb *d_branch_bb, uint32_t *d_list_counts) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::decid_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY ctx->eng.tiles_decid_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, (terra::decid_tree_data_pod_t const *)d_tree_data, num_tree_data, d_skip,
+		(terra::decid_place_pod_t const *)d_decid, d_counts, capacity, d_not_visible, (terra::decid_view_tile_pod_t *)d_tile_out, d_all_bcube, d_leaf_word, d_leaf_scale, d_leaf_opacity,
+		d_leaf_num, d_branch_word, d_branch_scale, d_branch_opacity, d_branch_num, d_leaf_list, d_branch_list, (terra::decid_view_bb_pod_t *)d_leaf_bb,
+		(terra::decid_view_bb_pod_t *)d_branch_bb, d_list_counts); TERRA_CATCH
+}
+int terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                           const terra_decid_view_args *args, const terra_decid_tree_data *h_tree_data, uint32_t num_tree_data, const uint8_t *h_skip,
+                           const terra_decid_place *h_decid, const uint32_t *h_counts, uint32_t capacity, uint8_t *h_not_visible, terra_decid_view_tile *h_tile_out,
+                           float *h_all_bcube, uint32_t *h_leaf_word, float *h_leaf_scale, float *h_leaf_opacity, uint32_t *h_leaf_num, uint32_t *h_branch_word,
+                           float *h_branch_scale, float *h_branch_opacity, uint32_t *h_branch_num, uint32_t *h_leaf_list, uint32_t *h_branch_list,
+                           terra_decid_view_bb *h_leaf_bb, terra_decid_view_bb *h_branch_bb, uint32_t *h_list_counts) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::decid_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.decid_view_check(v, a, num_tree_data); // the scene, the tile size, the view, the args and the table's length: before anything is staged
+		if (!h_tree_data) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if ((uint64_t)n*capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_decid_view: n*capacity must fit 32 bits");
+		if (n == 0) return TERRA_OK;
+		if (!tile_xy || !h_counts || !h_tile_out || !h_all_bcube || !h_list_counts ||
+		    (capacity && (!h_decid || !h_leaf_word || !h_leaf_scale || !h_leaf_opacity || !h_leaf_num || !h_branch_word || !h_branch_scale || !h_branch_opacity || !h_branch_num ||
+		                  !h_leaf_list || !h_branch_list || !h_leaf_bb || !h_branch_bb))) return terra::fail(TERRA_ERR_ARG, "null argument");
+		typedef terra::decid_view_bb_pod_t bb_t;
+		size_t const nc = (size_t)n*capacity;
+		terra_stage st(ctx->eng);
+		// the per-record arrays and the lists go up as the caller has them and come back: the call writes only some of their entries
+		int const td = st.in(h_tree_data, (size_t)num_tree_data*sizeof(terra_decid_tree_data)), sk = st.opt_in(h_skip, n), de = st.in(h_decid, nc*sizeof(terra_decid_place)),
+			pc = st.in(h_counts, (size_t)n*4), nv = st.inout(h_not_visible, nc, h_not_visible != nullptr), to = st.out(h_tile_out, (size_t)n*sizeof(terra_decid_view_tile)),
+			bc = st.out(h_all_bcube, (size_t)n*24), lw = st.inout(h_leaf_word, nc*4), ls = st.inout(h_leaf_scale, nc*4), lo = st.inout(h_leaf_opacity, nc*4),
+			ln = st.inout(h_leaf_num, nc*4), bw = st.inout(h_branch_word, nc*4), bs = st.inout(h_branch_scale, nc*4), bo = st.inout(h_branch_opacity, nc*4),
+			bn = st.inout(h_branch_num, nc*4), ll = st.inout(h_leaf_list, nc*4), bl = st.inout(h_branch_list, nc*4), lb = st.inout(h_leaf_bb, nc*sizeof(bb_t)),
+			bb = st.inout(h_branch_bb, nc*sizeof(bb_t)), lc = st.out(h_list_counts, (size_t)n*16);
+		st.begin();
+		ctx->eng.tiles_decid_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, st.dev<terra::decid_tree_data_pod_t>(td), num_tree_data, st.dev<uint8_t>(sk),
+			st.dev<terra::decid_place_pod_t>(de), st.dev<uint32_t>(pc), capacity, st.dev<uint8_t>(nv), st.dev<terra::decid_view_tile_pod_t>(to), st.dev<float>(bc), st.dev<uint32_t>(lw),
+			st.dev<float>(ls), st.dev<float>(lo), st.dev<uint32_t>(ln), st.dev<uint32_t>(bw), st.dev<float>(bs), st.dev<float>(bo), st.dev<uint32_t>(bn), st.dev<uint32_t>(ll),
+			st.dev<uint32_t>(bl), st.dev<bb_t>(lb), st.dev<bb_t>(bb), st.dev<uint32_t>(lc));
+		st.end();
+	TERRA_CATCH
+}
 int terra_set_tree_size_params(terra_ctx *ctx, const terra_tree_size_params *params) {
 	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
 	TERRA_TRY ctx->eng.set_tree_size_params(*params); TERRA_CATCH

@@ -22,6 +22,7 @@
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_treeview.hpp"
+#include "terra_decidview.hpp"
 #include "terra_sceneryview.hpp"
 #include "terra_stage.hpp"
 #include "../../include/terra.h"
@@ -3378,6 +3379,131 @@ template<class BE> struct terra_engine {
 			}
 			d_tile_out[t] = o;
 			for (uint32_t g = 0; g < SCV_GROUPS; ++g) {d_group_counts[t*SCV_GROUPS + g] = groups[g];}
+		});
+	}
+
+	// ---- the deciduous tree draw lists of a batch for a camera (terra_decidview.hpp): tile_t::draw_decid_trees (src/tiled_mesh.cpp:1555-1563) with
+	// tree_cont_t::draw_branches_and_leaves, tree::draw_leaves_top and tree::draw_branches_top under it, over the records as the placement and the brush keep them.
+	// The checks that need no array (the host form runs them before it stages anything):
+	void decid_view_check(view_pod_t const &view, decid_view_args_pod_t const &a, uint32_t num_tree_data) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_decid_view: a member of the view is not finite");
+		if (!decid_view_args_finite(a)) throw std::invalid_argument("tiles_decid_view: a member of the args is not finite");
+		if (!(a.zoom_f > 0.0f)) throw std::invalid_argument("tiles_decid_view: zoom_f must be > 0");
+		if (a.reflection_pass != 0 && a.reflection_pass != 1) throw std::invalid_argument("tiles_decid_view: reflection_pass must be 0 or 1");
+		if (num_tree_data == 0 || num_tree_data != dp.num_shared_trees) throw std::invalid_argument("tiles_decid_view: num_tree_data must be terra_decid_params.num_shared_trees and > 0");
+	}
+	void tiles_decid_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, decid_view_args_pod_t const &a,
+		decid_tree_data_pod_t const *d_data, uint32_t num_tree_data, uint8_t const *d_skip, decid_place_pod_t const *d_decid, uint32_t const *d_counts, uint32_t capacity,
+		uint8_t *d_not_visible, decid_view_tile_pod_t *d_tile_out, float *d_bcube, uint32_t *d_leaf_word, float *d_leaf_scale, float *d_leaf_opacity, uint32_t *d_leaf_num,
+		uint32_t *d_branch_word, float *d_branch_scale, float *d_branch_opacity, uint32_t *d_branch_num, uint32_t *d_leaf_list, uint32_t *d_branch_list,
+		decid_view_bb_pod_t *d_leaf_bb, decid_view_bb_pod_t *d_branch_bb, uint32_t *d_list_counts)
+	{
+		decid_view_check(view, a, num_tree_data);
+		if (!d_data) throw std::invalid_argument("tiles_decid_view: null argument");
+		if ((uint64_t)n*capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_decid_view: n*capacity must fit 32 bits");
+		if (n && (!tile_xy || !d_counts || !d_tile_out || !d_bcube || !d_list_counts)) throw std::invalid_argument("tiles_decid_view: null argument");
+		if (n && capacity && (!d_decid || !d_leaf_word || !d_leaf_scale || !d_leaf_opacity || !d_leaf_num || !d_branch_word || !d_branch_scale || !d_branch_opacity || !d_branch_num ||
+		                      !d_leaf_list || !d_branch_list || !d_leaf_bb || !d_branch_bb)) throw std::invalid_argument("tiles_decid_view: null argument");
+		if ((((uintptr_t)d_data | (uintptr_t)d_decid | (uintptr_t)d_counts | (uintptr_t)d_tile_out | (uintptr_t)d_bcube | (uintptr_t)d_leaf_word | (uintptr_t)d_leaf_scale |
+		      (uintptr_t)d_leaf_opacity | (uintptr_t)d_leaf_num | (uintptr_t)d_branch_word | (uintptr_t)d_branch_scale | (uintptr_t)d_branch_opacity | (uintptr_t)d_branch_num |
+		      (uintptr_t)d_leaf_list | (uintptr_t)d_branch_list | (uintptr_t)d_leaf_bb | (uintptr_t)d_branch_bb | (uintptr_t)d_list_counts) & 3u) != 0) {
+			throw std::invalid_argument("tiles_decid_view: every array but skip and not_visible must be 4-byte aligned");
+		}
+		if (n == 0) return;
+		float const offx = (float)add_wrap(dxoff, xoff2)*DX_VAL, offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // dtree_off.get_xlate()
+		decid_view_consts_t const c = decid_view_consts(view, a, cfg.scene_x, cfg.scene_y, offx, offy, num_tree_data, capacity);
+		// scratch: for a capacity beyond what k_decid_view ranks in LDS, a tile's pairs and its sorted sequence
+		uint32_t *d_keys;
+		stage_layout_t lay;
+		lay.add(d_keys, (capacity > DECID_VIEW_LDS_KEYS) ? (size_t)n*capacity*3 : 0);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		if constexpr (BE::has_kernels) {
+			if (be.tile_decid_view(c, n, d_data, d_skip, d_decid, d_counts, d_not_visible, d_tile_out, d_bcube, d_leaf_word, d_leaf_scale, d_leaf_opacity, d_leaf_num, d_branch_word,
+				d_branch_scale, d_branch_opacity, d_branch_num, d_leaf_list, d_branch_list, d_leaf_bb, d_branch_bb, d_list_counts, d_keys)) return;
+		}
+		// the simple form: a logical thread per tile walks its records in the reference's order, the leaves sweep before the branches sweep
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint32_t const cnt = (d_skip && d_skip[t]) ? 0u : min_u32(d_counts[t], c.cap);
+			size_t const o = t*c.cap;
+			decid_place_pod_t const *const recs = d_decid + o;
+			// calc_bcube, literally
+			float bc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+			uint32_t nvalid = 0;
+			for (uint32_t j = 0; j < cnt; ++j) {
+				if (!decid_view_valid(c, d_data, recs[j])) continue;
+				++nvalid;
+				float b[6], l[6];
+				decid_view_bounds(d_data[recs[j].tree_id], recs[j].pos, b, l);
+				if (!decid_view_all_zeros(b)) { // assign_or_union_with_cube
+					if (decid_view_all_zeros(bc)) {for (int k = 0; k < 6; ++k) {bc[k] = b[k];}}
+					else {for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], b[k]); bc[k + 1] = max_std(bc[k + 1], b[k + 1]);}}
+				}
+				for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], l[k]); bc[k + 1] = max_std(bc[k + 1], l[k + 1]);} // union_with_cube
+			}
+			for (int k = 0; k < 6; ++k) {d_bcube[t*6 + k] = bc[k];}
+			decid_view_tile_pod_t out; out.flags = 0u; out.num_trees = nvalid; out.leaf_written = out.branch_written = out.leaf_bb_written = out.branch_bb_written = out.pad[0] = out.pad[1] = 0u;
+			uint32_t nl = 0, nb = 0, nlb = 0, nbb = 0;
+			decid_view_tile_t tl; tl.flags = 0u; tl.drawn = 0; tl.sorted = 0;
+			if (nvalid != 0u) {tl = decid_view_tile(c, bc);} // else: skipped, or decid_trees.empty() (:1557)
+			out.flags = tl.flags;
+			if (tl.drawn) {
+				uint32_t *const ll = d_leaf_list + o, *const bl = d_branch_list + o;
+				decid_view_bb_pod_t *const lb = d_leaf_bb + o, *const bb = d_branch_bb + o;
+				auto insert = [&](decid_view_bb_pod_t *list, uint32_t &m, decid_view_bb_pod_t const &e) { // behind every entry with an id that is not larger
+					uint32_t k = m++;
+					for (; k > 0 && list[k - 1].tree_id > e.tree_id; --k) {list[k] = list[k - 1];}
+					list[k] = e;
+				};
+				if (c.leaves) {
+					// the sequence of the sweep: the valid records in record order, or ascending (p2p_dist_sq, index) (:355-357).  No array holds it (the outputs keep
+					// their bytes where the call writes no entry): the sorted walk selects, step after step, the smallest pair behind the one before
+					auto key_of = [&](uint32_t q) {return decid_view_sort_key(c, decid_view_tree(c, d_data[recs[q].tree_id], recs[q].pos));};
+					float prev_key = 0.0f; uint32_t prev = 0; bool first = true;
+					for (uint32_t p = 0, rj = 0; p < nvalid; ++p) {
+						uint32_t j = 0;
+						if (!tl.sorted) {
+							while (!decid_view_valid(c, d_data, recs[rj])) {++rj;}
+							j = rj++;
+						}
+						else {
+							bool have = false; float best = 0.0f;
+							for (uint32_t q = 0; q < cnt; ++q) {
+								if (!decid_view_valid(c, d_data, recs[q])) continue;
+								float const k = key_of(q);
+								if (!first && !tree_view_before_f(prev_key, prev, k, q)) continue;
+								if (!have || tree_view_before_f(k, q, best, j)) {have = true; best = k; j = q;}
+							}
+							prev_key = best; prev = j; first = false;
+						}
+						decid_tree_data_pod_t const td = d_data[recs[j].tree_id];
+						decid_view_tree_t const g = decid_view_tree(c, td, recs[j].pos);
+						bool nvis = false, wrote = false;
+						decid_view_rec_t const r = decid_view_leaves(c, td, g, nvis, wrote);
+						d_leaf_word[o + j] = r.word; d_leaf_scale[o + j] = r.scale; d_leaf_opacity[o + j] = r.opacity; d_leaf_num[o + j] = r.num;
+						if (wrote && d_not_visible) {d_not_visible[o + j] = nvis ? 1 : 0;}
+						if (r.added) {insert(lb, nlb, decid_view_bb<true>(td, g, (uint32_t)recs[j].tree_id, j, r.opacity));}
+						if (r.listed) {ll[nl++] = j;}
+					}
+				}
+				if (c.branches) {
+					for (uint32_t j = 0; j < cnt; ++j) {
+						if (!decid_view_valid(c, d_data, recs[j])) continue;
+						decid_tree_data_pod_t const td = d_data[recs[j].tree_id];
+						decid_view_tree_t const g = decid_view_tree(c, td, recs[j].pos);
+						bool nvis = false;
+						if (!c.shadow) {nvis = c.leaves ? (d_leaf_word[o + j] & DCV_NOT_VISIBLE) != 0 : (d_not_visible && d_not_visible[o + j] != 0);}
+						decid_view_rec_t const r = decid_view_branches(c, td, g, nvis);
+						d_branch_word[o + j] = r.word; d_branch_scale[o + j] = r.scale; d_branch_opacity[o + j] = r.opacity; d_branch_num[o + j] = r.num;
+						if (r.added) {insert(bb, nbb, decid_view_bb<false>(td, g, (uint32_t)recs[j].tree_id, j, r.opacity));}
+						if (r.listed) {bl[nb++] = j;}
+					}
+				}
+				out.leaf_written = nl; out.branch_written = nb; out.leaf_bb_written = nlb; out.branch_bb_written = nbb; // (a list holds a record once: never more than the capacity)
+			}
+			d_tile_out[t] = out;
+			d_list_counts[4*t] = nl; d_list_counts[4*t + 1] = nb; d_list_counts[4*t + 2] = nlb; d_list_counts[4*t + 3] = nbb;
 		});
 	}
 

@@ -643,6 +643,15 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	{
 		return launch_per_tile<terra::SCVW_THREADS>(terra::k_scenery_view, n, c, tile_xy, stats, skip, objs, counts, rov, tile_out, draw, size_scale, dist, list, group_counts);
 	}
+	// the deciduous tree draw lists for a camera: one workgroup per tile (k_decid_view)
+	bool tile_decid_view(terra::decid_view_consts_t const &c, uint32_t n, terra::decid_tree_data_pod_t const *data, uint8_t const *skip, terra::decid_place_pod_t const *decid,
+		uint32_t const *counts, uint8_t *not_visible, terra::decid_view_tile_pod_t *tile_out, float *bcube, uint32_t *leaf_word, float *leaf_scale, float *leaf_opacity,
+		uint32_t *leaf_num, uint32_t *branch_word, float *branch_scale, float *branch_opacity, uint32_t *branch_num, uint32_t *leaf_list, uint32_t *branch_list,
+		terra::decid_view_bb_pod_t *leaf_bb, terra::decid_view_bb_pod_t *branch_bb, uint32_t *list_counts, uint32_t *keys)
+	{
+		return launch_per_tile<terra::DCV_THREADS>(terra::k_decid_view, n, c, data, skip, decid, counts, not_visible, tile_out, bcube, leaf_word, leaf_scale, leaf_opacity, leaf_num,
+			branch_word, branch_scale, branch_opacity, branch_num, leaf_list, branch_list, leaf_bb, branch_bb, list_counts, keys);
+	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (opt->simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}
 		if (nvox == 0) return;

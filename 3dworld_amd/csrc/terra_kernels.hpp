@@ -2195,15 +2195,14 @@ __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_rank(float const *_
 //  3. A second sweep in record order: the trunk byte of every record, and the pine entries of leaf_list -- appended in record order (tp_emit), or, in the tile that
 //     holds the camera, compacted as (p2p_dist_sq, index) pairs and placed by their rank among the pairs (as k_terrain_view_rank places a tile).  A third sweep
 //     appends the palm entries where draw_non_pine_leaves draws them.
-//  4. The instance lists, pine then palm: a stable counting sort by id.  A histogram of the ids in LDS (atomic adds: only counts), an exclusive scan of it, then
-//     emission in record order: the waves of a sweep take turns, and in a wave the lanes that share an id are ranked by a ballot, so the order inside an id is the
-//     record index and no atomic decides an order.  The histogram holds instance tables of up to TREE_VIEW_LDS_IDS entries; a larger table takes the second path:
-//     the (id, index) pairs are compacted and ranked like the camera tile's list.
+//  4. The instance lists, pine then palm: a stable counting sort by id (tp_sort_by_id).  The entries are compacted as (id, index) pairs in record order; up to
+//     TREE_VIEW_RANK_MAX of them, or with an instance table beyond TREE_VIEW_LDS_IDS entries, every pair is placed by its rank like the camera tile's list.  More
+//     take a histogram of the ids in LDS (atomic adds: only counts), an exclusive scan of it, then emission in record order: the waves take turns, and in a wave
+//     the lanes that share an id are ranked by a ballot, so the order inside an id is the record index and no atomic decides an order.
 // The pairs lie in LDS for capacities up to TREE_VIEW_LDS_KEYS, else in the tile's part of the driver's scratch.  The sweeps recompute a record's geometry instead
 // of keeping it: a few dozen flops against a round trip through memory, and the records come from L2 after the first sweep.
 constexpr uint32_t TRV_THREADS = 256;
 static_assert(TRV_THREADS == TREEP_THREADS, "tp_block_rank and tp_emit rank TREEP_THREADS threads");
-static_assert(TREE_VIEW_LDS_IDS % TRV_THREADS == 0, "the scan gives every lane the same number of bins");
 template<bool FLOATKEY> __device__ __forceinline__ uint32_t trv_rank(uint32_t const *key, uint32_t const *idx, uint32_t m, uint32_t ki, uint32_t ii) {
 	uint32_t rank = 0;
 	for (uint32_t j = 0; j < m; ++j) {
@@ -2212,15 +2211,80 @@ template<bool FLOATKEY> __device__ __forceinline__ uint32_t trv_rank(uint32_t co
 	}
 	return rank;
 }
+// ---- a stable counting sort by id of the entries of a sequence, for the workgroup (the instance lists of k_tree_view, the billboard lists of k_decid_view):
+// positions [0, m) of a sequence; entry(p, id): does position p enter the list, and with which id (< nid); store(at, id, p) -> the number of entries (uniform).
+// The entries are compacted first, as (id, position) pairs in sequence order.  Up to RANK_MAX of them, or with a table beyond the LDS bins, every pair is
+// placed by its rank among the pairs: n/256 rounds of n comparisons, which for the few hundred entries of a real tile is far less than the turns below.  More
+// entries take the histogram: its emission costs a turn per wave and chunk and in it a step per distinct id, whatever the number of entries.
+template<uint32_t BINS, uint32_t RANK_MAX, class ENTRY, class STORE> __device__ __forceinline__ uint32_t tp_sort_by_id(uint32_t nid, uint32_t m, ENTRY entry, STORE store, uint32_t *s_hist, uint32_t *s_wave,
+	uint32_t *kbuf, uint32_t *ibuf)
+{
+	uint32_t const tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	uint32_t n = 0;
+	for (uint32_t base = 0; base < m; base += TREEP_THREADS) {
+		uint32_t id = 0, tot;
+		bool const e = base + tid < m && entry(base + tid, id);
+		uint32_t const rank = tp_block_rank(e, s_wave, tot);
+		if (e) {kbuf[n + rank] = id; ibuf[n + rank] = base + tid;}
+		n += tot;
+	}
+	__syncthreads();
+	if (n == 0u) return 0u; // (uniform)
+	if (nid > BINS || n <= RANK_MAX) {
+		for (uint32_t i = tid; i < n; i += TREEP_THREADS) {store(trv_rank<false>(kbuf, ibuf, n, kbuf[i], ibuf[i]), kbuf[i], ibuf[i]);}
+		__syncthreads(); // the pairs are reused
+		return n;
+	}
+	for (uint32_t b = tid; b < nid; b += TREEP_THREADS) {s_hist[b] = 0u;}
+	__syncthreads();
+	for (uint32_t i = tid; i < n; i += TREEP_THREADS) {atomicAdd(&s_hist[kbuf[i]], 1u);}
+	__syncthreads();
+	// exclusive scan of the nid counts: lane q owns bins PER*q .. PER*q + PER - 1
+	static_assert(BINS % TREEP_THREADS == 0, "the scan gives every lane the same number of bins");
+	constexpr uint32_t PER = BINS/TREEP_THREADS;
+	uint32_t v[PER], sum = 0;
+#pragma unroll
+	for (uint32_t k = 0; k < PER; ++k) {uint32_t const b = PER*tid + k; v[k] = (b < nid) ? s_hist[b] : 0u; sum += v[k];}
+	uint32_t incl = sum;
+	for (uint32_t d = 1; d < 64u; d <<= 1) {uint32_t const u = __shfl_up(incl, d); if (lane >= d) {incl += u;}}
+	if (lane == 63u) {s_wave[wave] = incl;}
+	__syncthreads();
+	uint32_t before = 0;
+	for (uint32_t w = 0; w < wave; ++w) {before += s_wave[w];}
+	uint32_t at = before + incl - sum;
+#pragma unroll
+	for (uint32_t k = 0; k < PER; ++k) {uint32_t const b = PER*tid + k; if (b < nid) {s_hist[b] = at;} at += v[k];}
+	__syncthreads();
+	uint64_t const below = (1ull << lane) - 1ull;
+	for (uint32_t base = 0; base < n; base += TREEP_THREADS) {
+		uint32_t const i = base + tid;
+		bool const e = i < n;
+		uint32_t const id = e ? kbuf[i] : 0u;
+		for (uint32_t w = 0; w < TREEP_THREADS/64; ++w) { // the waves in sequence order
+			if (wave == w) {
+				uint64_t rem = __ballot(e);
+				while (rem) {
+					int const leader = __ffsll((unsigned long long)rem) - 1;
+					uint32_t const lid = (uint32_t)__shfl((int)id, leader);
+					uint64_t const mm = __ballot(e && id == lid);
+					uint32_t const start = s_hist[lid]; // (every lane reads before the leader writes)
+					if (e && id == lid) {store(start + (uint32_t)__popcll(mm & below), id, ibuf[i]);}
+					if ((int)lane == leader) {s_hist[lid] = start + (uint32_t)__popcll(mm);}
+					rem &= ~mm;
+				}
+			}
+			__syncthreads();
+		}
+	}
+	return n;
+}
 // one instance list of the tile (PINE: draw_pine_insts, else draw_palm_insts) -> its count (uniform)
 template<bool PINE> __device__ __forceinline__ uint32_t trv_insts(tree_view_consts_t const &c, tree_view_tile_t const &tl, tree_inst_pod_t const *__restrict__ insts,
 	tree_place_pod_t const *__restrict__ recs, trunk_override_pod_t const *__restrict__ ovs, uint32_t cnt, tree_view_inst_pod_t *__restrict__ out, uint32_t *s_hist, uint32_t *s_wave,
 	uint32_t *kbuf, uint32_t *ibuf)
 {
-	uint32_t const tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
 	bool const all = PINE ? tl.draw_all_near != 0 : tl.all_visible != 0;
 	auto entry = [&](uint32_t i, uint32_t &id) -> bool { // does record i enter the list, and with which id
-		if (i >= cnt) return false;
 		tree_view_rec_t rec;
 		if (recs[i].inst < 0 || !tree_view_record(c, insts, recs[i], ovs ? ovs + i : nullptr, rec)) return false;
 		if (PINE ? !is_pine_tree_type(rec.type) : rec.type != T_PALM) return false;
@@ -2228,65 +2292,7 @@ template<bool PINE> __device__ __forceinline__ uint32_t trv_insts(tree_view_cons
 		return all || tree_view_leaves_visible(c, rec);
 	};
 	auto store = [&](uint32_t at, uint32_t id, uint32_t i) {out[at].id = id; for (int q = 0; q < 3; ++q) {out[at].pt[q] = recs[i].pos[q];}};
-	uint32_t const nid = c.a.num_insts;
-	if (nid <= TREE_VIEW_LDS_IDS) {
-		for (uint32_t b = tid; b < nid; b += TRV_THREADS) {s_hist[b] = 0u;}
-		__syncthreads();
-		for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
-			uint32_t id = 0;
-			if (entry(base + tid, id)) {atomicAdd(&s_hist[id], 1u);}
-		}
-		__syncthreads();
-		// exclusive scan of the nid counts: lane q owns bins PER*q .. PER*q + PER - 1
-		constexpr uint32_t PER = TREE_VIEW_LDS_IDS/TRV_THREADS;
-		uint32_t v[PER], sum = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < PER; ++k) {uint32_t const b = PER*tid + k; v[k] = (b < nid) ? s_hist[b] : 0u; sum += v[k];}
-		uint32_t incl = sum;
-		for (uint32_t d = 1; d < 64u; d <<= 1) {uint32_t const u = __shfl_up(incl, d); if (lane >= d) {incl += u;}}
-		if (lane == 63u) {s_wave[wave] = incl;}
-		__syncthreads();
-		uint32_t before = 0, total = 0;
-		for (uint32_t w = 0; w < TRV_THREADS/64; ++w) {uint32_t const sw = s_wave[w]; if (w < wave) {before += sw;} total += sw;}
-		uint32_t at = before + incl - sum;
-#pragma unroll
-		for (uint32_t k = 0; k < PER; ++k) {uint32_t const b = PER*tid + k; if (b < nid) {s_hist[b] = at;} at += v[k];}
-		__syncthreads();
-		uint64_t const below = (1ull << lane) - 1ull;
-		for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
-			uint32_t id = 0;
-			bool const e = entry(base + tid, id);
-			for (uint32_t w = 0; w < TRV_THREADS/64; ++w) { // the waves in record order
-				if (wave == w) {
-					uint64_t rem = __ballot(e);
-					while (rem) {
-						int const leader = __ffsll((unsigned long long)rem) - 1;
-						uint32_t const lid = (uint32_t)__shfl((int)id, leader);
-						uint64_t const m = __ballot(e && id == lid);
-						uint32_t const start = s_hist[lid]; // (every lane reads before the leader writes)
-						if (e && id == lid) {store(start + (uint32_t)__popcll(m & below), id, base + tid);}
-						if ((int)lane == leader) {s_hist[lid] = start + (uint32_t)__popcll(m);}
-						rem &= ~m;
-					}
-				}
-				__syncthreads();
-			}
-		}
-		return total;
-	}
-	// the second path: compact the (id, index) pairs in record order, then place every pair by its rank
-	uint32_t m = 0;
-	for (uint32_t base = 0; base < cnt; base += TRV_THREADS) {
-		uint32_t id = 0, tot;
-		bool const e = entry(base + tid, id);
-		uint32_t const rank = tp_block_rank(e, s_wave, tot);
-		if (e) {kbuf[m + rank] = id; ibuf[m + rank] = base + tid;}
-		m += tot;
-	}
-	__syncthreads();
-	for (uint32_t i = tid; i < m; i += TRV_THREADS) {store(trv_rank<false>(kbuf, ibuf, m, kbuf[i], ibuf[i]), kbuf[i], ibuf[i]);}
-	__syncthreads(); // the pairs are reused
-	return m;
+	return tp_sort_by_id<TREE_VIEW_LDS_IDS, TREE_VIEW_RANK_MAX>(c.a.num_insts, cnt, entry, store, s_hist, s_wave, kbuf, ibuf);
 }
 __global__ __launch_bounds__(TRV_THREADS) void k_tree_view(tree_view_consts_t c, int32_t const *__restrict__ tile_xy, tree_inst_pod_t const *__restrict__ insts,
 	terra_tile_stats const *__restrict__ stats, uint8_t const *__restrict__ skip, float const *__restrict__ trmax, tree_place_pod_t const *__restrict__ pine,
@@ -2509,6 +2515,173 @@ __global__ __launch_bounds__(SCVW_THREADS) void k_scenery_view(scenery_view_cons
 			s_base[tid] += m;
 		}
 		__syncthreads(); // before the next chunk's counts
+	}
+}
+
+// ------------------------------------------------------------------ the deciduous tree draw lists of a tile batch for a camera (tile_t::draw_decid_trees,
+// src/tiled_mesh.cpp:1555-1563, tree_cont_t::draw_branches_and_leaves, src/Tree.cpp:312-368; terra_decidview.hpp).  k_decid_view: a workgroup of 256 lanes per
+// tile; a skipped tile and one without records leave at once.
+//  1. A sweep over the tile's records, a lane a record: the table entry (80 bytes, from L2), the number of valid records and the unions of calc_bcube
+//     (decid_view_union_t), reduced over the wave with shuffles and over the four waves through LDS.
+//  2. One lane takes the tile-level decisions (decid_view_tile: the cull of :316, the choice of :347-348) and broadcasts them through LDS.
+//  3. One sweep in chunks of 256 answers both of the reference's sweeps for a record: the leaves' word, scale, opacity and count, not_visible, then the branches'.
+//     tree::not_visible goes from the one to the other in a register, and into the caller's array when there is one: no second array.  leaf_list and branch_list
+//     are appended in record order (tp_emit); in a sorted tile the records that reach draw_leaves or add a billboard are compacted as (key, index) pairs instead
+//     and placed by their rank (trv_rank, as k_tree_view places the camera tile), which gives the sequence the reference walks; leaf_list is its filtered copy.
+//  4. The two billboard lists: a stable counting sort by tree_id over a sequence (record order, or the sorted sequence for the leaves of a sorted tile), so the order
+//     inside an id is the sequence's.  tp_sort_by_id (above, shared with k_tree_view) compacts the entries as (id, position) pairs in sequence order (tp_block_rank).  A few hundred pairs, or a table
+//     of more than DECID_VIEW_LDS_IDS entries, are placed by rank (trv_rank); more take a histogram in LDS (atomic adds: only counts), an
+//     exclusive scan, then emission in sequence order, the waves taking turns and a ballot ranking the lanes that share an id, so no atomic decides an order.
+// The pairs lie in LDS for capacities up to DECID_VIEW_LDS_KEYS, else in the tile's part of the driver's scratch.  Steps 3 and 4 read words and opacities that other
+// lanes of the workgroup stored: the barriers of tp_block_rank lie between.
+constexpr uint32_t DCV_THREADS = 256;
+static_assert(DCV_THREADS == TREEP_THREADS, "tp_block_rank and tp_emit rank TREEP_THREADS threads");
+__global__ __launch_bounds__(DCV_THREADS) void k_decid_view(decid_view_consts_t c, decid_tree_data_pod_t const *__restrict__ data, uint8_t const *__restrict__ skip,
+	decid_place_pod_t const *__restrict__ decid, uint32_t const *__restrict__ counts, uint8_t *not_visible, decid_view_tile_pod_t *__restrict__ tile_out, float *__restrict__ bcube,
+	uint32_t *leaf_word, float *__restrict__ leaf_scale, float *leaf_opacity, uint32_t *__restrict__ leaf_num, uint32_t *branch_word, float *__restrict__ branch_scale,
+	float *branch_opacity, uint32_t *__restrict__ branch_num, uint32_t *__restrict__ leaf_list, uint32_t *__restrict__ branch_list, decid_view_bb_pod_t *__restrict__ leaf_bb,
+	decid_view_bb_pod_t *__restrict__ branch_bb, uint32_t *__restrict__ list_counts, uint32_t *keys)
+{
+	__shared__ uint32_t s_wave[DCV_THREADS/64], s_nv[DCV_THREADS/64], s_key[DECID_VIEW_LDS_KEYS], s_idx[DECID_VIEW_LDS_KEYS], s_seq[DECID_VIEW_LDS_KEYS], s_hist[DECID_VIEW_LDS_IDS];
+	__shared__ decid_view_union_t s_un[DCV_THREADS/64];
+	__shared__ decid_view_tile_t s_tile;
+	uint32_t const t = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	uint32_t const cnt = (skip && skip[t]) ? 0u : min_u32(counts[t], c.cap); // (uniform)
+	auto leave = [&](uint32_t flags, uint32_t num_trees) {
+		if (tid == 0) {
+			decid_view_tile_pod_t z; z.flags = flags; z.num_trees = num_trees; z.leaf_written = z.branch_written = z.leaf_bb_written = z.branch_bb_written = z.pad[0] = z.pad[1] = 0u;
+			tile_out[t] = z;
+		}
+		if (tid < 4u) {list_counts[4u*t + tid] = 0u;}
+	};
+	if (cnt == 0u) {if (tid < 6u) {bcube[(size_t)t*6u + tid] = 0.0f;} leave(0u, 0u); return;}
+	size_t const o = (size_t)t*c.cap;
+	decid_place_pod_t const *const recs = decid + o;
+	// 1. the valid records and calc_bcube
+	decid_view_union_t un;
+	decid_view_union_init(un);
+	uint32_t nv = 0;
+	for (uint32_t i = tid; i < cnt; i += DCV_THREADS) {
+		decid_place_pod_t const r = recs[i];
+		if (!decid_view_valid(c, data, r)) continue;
+		++nv;
+		float b[6], l[6];
+		decid_view_bounds(data[r.tree_id], r.pos, b, l);
+		decid_view_union_add(un, i, b, l);
+	}
+	for (int off = 32; off; off >>= 1) {
+		decid_view_union_t ot;
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {ot.b[k] = __shfl_xor(un.b[k], off); ot.l[k] = __shfl_xor(un.l[k], off);}
+		ot.first = __shfl_xor(un.first, off); ot.last_zero = __shfl_xor(un.last_zero, off);
+		decid_view_union_merge(un, ot);
+		nv += __shfl_xor(nv, off);
+	}
+	if (lane == 0) {s_un[wave] = un; s_nv[wave] = nv;}
+	__syncthreads();
+	nv = 0;
+	for (uint32_t w = 0; w < DCV_THREADS/64; ++w) {nv += s_nv[w];}
+	if (nv == 0u) {if (tid < 6u) {bcube[(size_t)t*6u + tid] = 0.0f;} leave(0u, 0u); return;} // decid_trees.empty() (:1557) (uniform)
+	// 2. the tile's decisions
+	if (tid == 0) {
+		decid_view_union_t all = s_un[0];
+		for (uint32_t w = 1; w < DCV_THREADS/64; ++w) {decid_view_union_merge(all, s_un[w]);}
+		float bc[6];
+		decid_view_union_result(all, bc);
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {bcube[(size_t)t*6u + k] = bc[k];}
+		s_tile = decid_view_tile(c, bc);
+	}
+	__syncthreads();
+	decid_view_tile_t const tl = s_tile;
+	if (!tl.drawn) {leave(tl.flags, nv); return;} // (uniform)
+	bool const big = c.cap > DECID_VIEW_LDS_KEYS;
+	uint32_t *const kbuf = big ? keys + o*3u : s_key, *const ibuf = big ? kbuf + c.cap : s_idx, *const sbuf = big ? ibuf + c.cap : s_seq;
+	uint32_t *const ll = leaf_list + o, *const bl = branch_list + o;
+	// 3. both sweeps of a record
+	uint32_t nll = 0, nbl = 0, ms = 0;
+	for (uint32_t base = 0; base < cnt; base += DCV_THREADS) {
+		uint32_t const i = base + tid;
+		bool const valid = i < cnt && decid_view_valid(c, data, recs[i]);
+		bool l_listed = false, l_seq = false, b_listed = false;
+		float key = 0.0f;
+		if (valid) {
+			decid_tree_data_pod_t const td = data[recs[i].tree_id];
+			decid_view_tree_t const g = decid_view_tree(c, td, recs[i].pos);
+			bool nvis = false, wrote = false;
+			if (c.leaves) {
+				decid_view_rec_t const r = decid_view_leaves(c, td, g, nvis, wrote);
+				leaf_word[o + i] = r.word; leaf_scale[o + i] = r.scale; leaf_opacity[o + i] = r.opacity; leaf_num[o + i] = r.num;
+				if (wrote && not_visible) {not_visible[o + i] = nvis ? 1 : 0;}
+				l_listed = r.listed != 0; l_seq = r.listed != 0 || r.added != 0;
+				if (tl.sorted) {key = decid_view_sort_key(c, g);}
+			}
+			else if (!c.shadow && not_visible) {nvis = not_visible[o + i] != 0;}
+			if (c.branches) {
+				decid_view_rec_t const r = decid_view_branches(c, td, g, nvis);
+				branch_word[o + i] = r.word; branch_scale[o + i] = r.scale; branch_opacity[o + i] = r.opacity; branch_num[o + i] = r.num;
+				b_listed = r.listed != 0;
+			}
+		}
+		if (c.leaves) { // (uniform)
+			if (!tl.sorted) {tp_emit(l_listed, [&] {return i;}, ll, c.cap, nll, s_wave);}
+			else {
+				uint32_t tot;
+				uint32_t const rank = tp_block_rank(l_seq, s_wave, tot);
+				if (l_seq) {kbuf[ms + rank] = __float_as_uint(key); ibuf[ms + rank] = i;}
+				ms += tot;
+			}
+		}
+		if (c.branches) {tp_emit(b_listed, [&] {return i;}, bl, c.cap, nbl, s_wave);}
+	}
+	__syncthreads(); // the words, the opacities and the pairs are complete
+	if (tl.sorted) { // the sequence the reference walks, then leaf_list out of it
+		for (uint32_t i = tid; i < ms; i += DCV_THREADS) {sbuf[trv_rank<true>(kbuf, ibuf, ms, kbuf[i], ibuf[i])] = ibuf[i];}
+		__syncthreads(); // the pairs are reused
+		for (uint32_t base = 0; base < ms; base += DCV_THREADS) {
+			uint32_t const p = base + tid, idx = (p < ms) ? sbuf[p] : 0u;
+			uint32_t const form = (p < ms) ? (leaf_word[o + idx] & (uint32_t)DCV_FORM_MASK) : 0u;
+			tp_emit(form == DCV_FORM_GEOM || form == DCV_FORM_BOTH, [&] {return idx;}, ll, c.cap, nll, s_wave);
+		}
+	}
+	// 4. the billboard lists
+	uint32_t nlb = 0, nbb = 0;
+	if (c.billboards) { // (uniform)
+		if (c.leaves) {
+			decid_view_bb_pod_t *const out = leaf_bb + o;
+			auto rec_of = [&](uint32_t p) {return tl.sorted ? sbuf[p] : p;};
+			nlb = tp_sort_by_id<DECID_VIEW_LDS_IDS, DECID_VIEW_RANK_MAX>(c.num_data, tl.sorted ? ms : cnt,
+				[&](uint32_t p, uint32_t &id) {
+					uint32_t const idx = rec_of(p);
+					if (!decid_view_valid(c, data, recs[idx]) || (leaf_word[o + idx] & (uint32_t)DCV_FORM_MASK) < (uint32_t)DCV_FORM_BOTH) return false;
+					id = (uint32_t)recs[idx].tree_id;
+					return true;
+				},
+				[&](uint32_t at, uint32_t id, uint32_t p) {
+					uint32_t const idx = rec_of(p);
+					decid_tree_data_pod_t const td = data[id];
+					if (at < c.cap) {out[at] = decid_view_bb<true>(td, decid_view_tree(c, td, recs[idx].pos), id, idx, leaf_opacity[o + idx]);}
+				}, s_hist, s_wave, kbuf, ibuf);
+		}
+		if (c.branches) {
+			decid_view_bb_pod_t *const out = branch_bb + o;
+			nbb = tp_sort_by_id<DECID_VIEW_LDS_IDS, DECID_VIEW_RANK_MAX>(c.num_data, cnt,
+				[&](uint32_t idx, uint32_t &id) {
+					if (!decid_view_valid(c, data, recs[idx]) || (branch_word[o + idx] & (uint32_t)DCV_FORM_MASK) < (uint32_t)DCV_FORM_BOTH) return false;
+					id = (uint32_t)recs[idx].tree_id;
+					return true;
+				},
+				[&](uint32_t at, uint32_t id, uint32_t idx) {
+					decid_tree_data_pod_t const td = data[id];
+					if (at < c.cap) {out[at] = decid_view_bb<false>(td, decid_view_tree(c, td, recs[idx].pos), id, idx, branch_opacity[o + idx]);}
+				}, s_hist, s_wave, kbuf, ibuf);
+		}
+	}
+	if (tid == 0) {
+		decid_view_tile_pod_t z; z.flags = tl.flags; z.num_trees = nv; z.pad[0] = z.pad[1] = 0u;
+		z.leaf_written = min_u32(nll, c.cap); z.branch_written = min_u32(nbl, c.cap); z.leaf_bb_written = min_u32(nlb, c.cap); z.branch_bb_written = min_u32(nbb, c.cap);
+		tile_out[t] = z;
+		list_counts[4u*t] = nll; list_counts[4u*t + 1u] = nbl; list_counts[4u*t + 2u] = nlb; list_counts[4u*t + 3u] = nbb;
 	}
 }
 

@@ -46,7 +46,7 @@ private:
 // grow-only host-grid scratch or, with `own`, an allocation of the call's own that goes with the object.
 // A slot that is not `present` takes no part: no upload, no download, dev() is null -- so a caller states the condition of an optional array once.
 template<class ENGINE> struct host_stage_t {
-	enum {MAX_SLOTS = 16};
+	enum {MAX_SLOTS = 24};
 	struct slot_t {void const *src; void *dst; size_t bytes, off; bool present;};
 	ENGINE &eng;
 	static constexpr bool OWN_ALLOC = true;

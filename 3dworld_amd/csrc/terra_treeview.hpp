@@ -26,6 +26,7 @@ constexpr int T_BUSH = 3;                  // src/small_tree.h:9
 constexpr int TREE_VIEW_CYL_SIDES = 32;    // N_CYL_SIDES (src/3DWorld.h:104)
 constexpr uint32_t TREE_VIEW_LDS_KEYS = 2048; // the (key, record) pairs of a tile that k_tree_view ranks in LDS; a larger capacity ranks in global scratch
 constexpr uint32_t TREE_VIEW_LDS_IDS = 1024;  // the instance table that k_tree_view's histogram holds in LDS; a larger table takes the ranking path
+constexpr uint32_t TREE_VIEW_RANK_MAX = 512;  // the entries of an instance list that k_tree_view places by rank; more take the histogram
 enum {TRV_TRUNK_NONE = 0, TRV_TRUNK_POLY_ALL = 1, TRV_TRUNK_POLY_SKIPPED = 2, TRV_TRUNK_POINTS = 3, TRV_TRUNK_MASK = 3, // :1477-1489
       TRV_NEAR_LEAVES = 0x4, TRV_FAR_LEAVES = 0x8, TRV_DITHERED = 0x10, TRV_PALMS = 0x20, TRV_DRAW_ALL_NEAR = 0x40, TRV_DRAW_ALL_FAR = 0x80, TRV_ALL_VISIBLE = 0x100,
       TRV_NEEDS_HIGH = 0x200, TRV_NEEDS_LOW = 0x400, TRV_CONTAINS_CAMERA = 0x800};

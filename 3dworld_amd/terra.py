@@ -208,6 +208,32 @@ SCV_GROUPS = ("rock_shape", "surface_rock", "rock", "log", "stump", "mushroom", 
               "pld_lines")  # TERRA_SCV_G_*
 
 
+class DecidViewArgs(C.Structure):  # terra_decid_view_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("zoom_f", C.c_float), ("lod_scales", C.c_float * 4), ("shadow_pass", C.c_int32), ("reflection_pass", C.c_int32),
+                ("billboards", C.c_int32), ("leaf_color_changed", C.c_int32), ("draw_leaves", C.c_int32), ("draw_branches", C.c_int32)]
+
+
+def make_decid_view_args(behind_sphere_mult=1.0, zoom_f=1.0, lod_scales=(0.0, 0.0, 0.0, 0.0), shadow_pass=0, reflection_pass=0, billboards=1, leaf_color_changed=0,
+                         draw_leaves=1, draw_branches=1):
+    """terra_decid_view_args: behind_sphere_mult as for the terrain view; lod_scales = tree_lod_scales (branch start, branch end, leaf start, leaf end); draw_leaves /
+    draw_branches: the two sweeps of tile_draw_t::draw_decid_trees, in any combination"""
+    return DecidViewArgs(behind_sphere_mult, zoom_f, (C.c_float * 4)(*[float(x) for x in lod_scales]), int(bool(shadow_pass)), int(reflection_pass), int(bool(billboards)),
+                         int(bool(leaf_color_changed)), int(bool(draw_leaves)), int(bool(draw_branches)))
+
+
+DECID_TREE_DATA_DTYPE = np.dtype([("base_radius", np.float32), ("sphere_radius", np.float32), ("sphere_center_zoff", np.float32), ("lr_z_cent", np.float32),
+                                  ("leaves_bcube", np.float32, (6,)), ("branches_bcube", np.float32, (6,)), ("num_leaves", np.uint32), ("num_branch_quads", np.uint32),
+                                  ("flags", np.uint32), ("pad", np.uint32)])  # terra_decid_tree_data
+DECID_VIEW_TILE_DTYPE = np.dtype([("flags", np.uint32), ("num_trees", np.uint32), ("leaf_written", np.uint32), ("branch_written", np.uint32), ("leaf_bb_written", np.uint32),
+                                  ("branch_bb_written", np.uint32), ("pad", np.uint32, (2,))])  # terra_decid_view_tile
+DECID_VIEW_BB_DTYPE = np.dtype([("tree_id", np.uint32), ("rec", np.uint32), ("pos", np.float32, (3,)), ("opacity", np.float32)])  # terra_decid_view_bb
+assert DECID_TREE_DATA_DTYPE.itemsize == 80 and DECID_VIEW_TILE_DTYPE.itemsize == 32 and DECID_VIEW_BB_DTYPE.itemsize == 24 and C.sizeof(DecidViewArgs) == 48
+DCV_GENERATED, DCV_HAS_4TH, DCV_LEAF_TEX, DCV_BRANCH_TEX = 1, 2, 4, 8  # the flags of terra_decid_tree_data
+DCV_TILE_DRAWN, DCV_TILE_LEAVES, DCV_TILE_BRANCHES, DCV_TILE_SORTED, DCV_TILE_BCUBE_ZERO_AREA = 1, 2, 4, 8, 16  # the flags word of terra_decid_view_tile
+DCV_FORM_NONE, DCV_FORM_GEOM, DCV_FORM_BOTH, DCV_FORM_BILLBOARD, DCV_FORM_MASK, DCV_NOT_VISIBLE, DCV_LOW_DETAIL, DCV_STAGE_SHIFT = 0, 1, 2, 3, 3, 4, 8, 4  # a leaf / branch word
+DCV_STAGE_NONE, DCV_STAGE_NOT_VISIBLE, DCV_STAGE_NO_LEAVES, DCV_STAGE_BOX, DCV_STAGE_SIZE, DCV_STAGE_SHADOW_DIST, DCV_STAGE_SHADOW_SPHERE = range(7)
+
+
 TREE_INST_DTYPE = np.dtype([("type", np.int32), ("height", np.float32), ("width", np.float32)])  # terra_tree_inst
 assert TREE_INST_DTYPE.itemsize == 12
 TREE_AO_NO_PINE_PALM, TREE_AO_NO_DECID, TREE_AO_DISTANT = 1, 2, 4  # the per-tile flag byte of tiles_tree_ao_shadows
@@ -412,6 +438,8 @@ _PROTOS = {
     "terra_tiles_tree_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_scenery_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_scenery_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_decid_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32] + [_vp] * 16),
+    "terra_tiles_decid_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32] + [_vp] * 16),
     "terra_tiles_ao_lighting_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_ao_lighting": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "terra_heightmap_proc_gen": (_i32, [_vp, _u32, _u32, _u32, _vp, _f3]),
@@ -1119,6 +1147,39 @@ class Terra:
         return dict(tile=mk((n,), SCENERY_VIEW_TILE_DTYPE), draw=mk((n, cap), np.uint32), size_scale=mk((n, cap), np.float32), dist=mk((n, cap), np.float32),
                     list=mk((n, list_cap), np.uint32), group_counts=mk((n, len(SCV_GROUPS)), np.uint32))
 
+    def tiles_decid_view(self, tile_xy, view, args, tree_data, decid, counts, skip=None, not_visible=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0, fill=0, out=None):
+        """tile_t::draw_decid_trees for every tile: decid DECID_PLACE_DTYPE [n, cap] with counts [n]; tree_data DECID_TREE_DATA_DTYPE [num_shared_trees]; skip [n] bytes
+        optional; not_visible uint8 [n, cap] optional, read and written in place.  The [n, cap] outputs start filled with the byte `fill` (or are the arrays of `out`);
+        entries the call does not write keep it.
+        -> dict(tile DECID_VIEW_TILE_DTYPE [n], all_bcube float32 [n, 6], leaf_word / leaf_num / branch_word / branch_num uint32 [n, cap], leaf_scale / leaf_opacity /
+        branch_scale / branch_opacity float32 [n, cap], leaf_list / branch_list uint32 [n, cap], leaf_bb / branch_bb DECID_VIEW_BB_DTYPE [n, cap], list_counts uint32 [n, 4])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        dr = np.ascontiguousarray(decid, DECID_PLACE_DTYPE).reshape(n, -1)
+        cap = dr.shape[1]
+        pc = np.ascontiguousarray(counts, np.uint32).reshape(n)
+        td = np.ascontiguousarray(tree_data, DECID_TREE_DATA_DTYPE).reshape(-1)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(n)
+        if not_visible is not None:
+            assert not_visible.dtype == np.uint8 and not_visible.shape == (n, cap) and not_visible.flags.c_contiguous and not_visible.flags.writeable
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
+        out = self._decid_view_outputs(n, cap, fill) if out is None else out
+        self._ck(self.lib.terra_tiles_decid_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), td.ctypes.data, len(td), ptr(sk), ptr(dr),
+                                                 pc.ctypes.data, cap, ptr(not_visible), *[ptr(out[k]) for k in self.DECID_VIEW_OUTPUTS]))
+        return out
+
+    DECID_VIEW_OUTPUTS = ("tile", "all_bcube", "leaf_word", "leaf_scale", "leaf_opacity", "leaf_num", "branch_word", "branch_scale", "branch_opacity", "branch_num", "leaf_list",
+                          "branch_list", "leaf_bb", "branch_bb", "list_counts")
+
+    @staticmethod
+    def _decid_view_outputs(n, cap, fill=0):
+        mk = lambda shape, dt: np.frombuffer(bytearray([fill]) * (int(np.prod(shape)) * np.dtype(dt).itemsize), dt).reshape(shape)  # noqa: E731
+        u, f = np.uint32, np.float32
+        return dict(tile=mk((n,), DECID_VIEW_TILE_DTYPE), all_bcube=mk((n, 6), f), leaf_word=mk((n, cap), u), leaf_scale=mk((n, cap), f), leaf_opacity=mk((n, cap), f),
+                    leaf_num=mk((n, cap), u), branch_word=mk((n, cap), u), branch_scale=mk((n, cap), f), branch_opacity=mk((n, cap), f), branch_num=mk((n, cap), u),
+                    leaf_list=mk((n, cap), u), branch_list=mk((n, cap), u), leaf_bb=mk((n, cap), DECID_VIEW_BB_DTYPE), branch_bb=mk((n, cap), DECID_VIEW_BB_DTYPE),
+                    list_counts=mk((n, 4), u))
+
     def set_tree_size_params(self, tsp):
         self._ck(self.lib.terra_set_tree_size_params(self.ctx, C.byref(tsp)))
 
@@ -1419,6 +1480,16 @@ class Terra:
         self._ck(self.lib.terra_tiles_scenery_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), stats_ptr, skip_ptr, objs_ptr,
                                                        counts_ptr, capacity, radius_override_ptr, tile_out_ptr, draw_ptr, size_scale_ptr, dist_ptr, list_ptr, list_capacity,
                                                        group_counts_ptr))
+
+    def tiles_decid_view_dev(self, tile_xy, view, args, tree_data_ptr, num_tree_data, decid_ptr, counts_ptr, capacity, out_ptrs, skip_ptr=None, not_visible_ptr=None, dxoff=0,
+                             dyoff=0, xoff2=0, yoff2=0):
+        """the deciduous tree draw lists of a device-resident batch, from the records tiles_place_decid_trees_dev and tiles_edit_trees_dev keep on the device:
+        tree_data_ptr [num_tree_data] terra_decid_tree_data on the device; out_ptrs: the device pointers of DECID_VIEW_OUTPUTS in that order (shapes as
+        _decid_view_outputs); skip_ptr [n] bytes (the terrain view's not_drawn), not_visible_ptr [n][capacity] bytes or None.  view and args are host structs.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        assert len(out_ptrs) == len(self.DECID_VIEW_OUTPUTS)
+        self._ck(self.lib.terra_tiles_decid_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, xoff2, yoff2, C.byref(view), C.byref(args), tree_data_ptr, num_tree_data,
+                                                     skip_ptr, decid_ptr, counts_ptr, capacity, not_visible_ptr, *out_ptrs))
 
     def tiles_tree_ao_shadows_dev(self, tile_xy, list_capacity, tree_map_ptr, pine_ptr=None, pine_counts_ptr=None, pine_capacity=0, decid_ptr=None, decid_counts_ptr=None,
                                   decid_capacity=0, decid_radius_ptr=None, decid_radius_by_id_ptr=None, num_radius_by_id=0, flags_ptr=None, updated_ptr=None, trmax_ptr=None,

@@ -1253,6 +1253,108 @@ int  terra_tiles_scenery_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
                               const uint32_t *h_counts, uint32_t capacity, const float *h_radius_override, terra_scenery_view_tile *h_tile_out, uint32_t *h_draw,
                               float *h_size_scale, float *h_dist, uint32_t *h_list, uint32_t list_capacity, uint32_t *h_group_counts);
 
+/* ---- the deciduous tree draw lists of a tile batch for a camera (every supported tile size S): tile_t::draw_decid_trees (src/tiled_mesh.cpp:1555-1563) without its
+ * GL, shader and colour calls, with tree_cont_t::draw_branches_and_leaves (src/Tree.cpp:312-368), tree::draw_leaves_top (:993-1052) and tree::draw_branches_top
+ * (:948-990) under it -- the per-frame decision about the deciduous trees of every drawn tile: which are drawn, in which form, with how many leaves and branch
+ * quads, in what order, bit for bit in fp32 and integers, from the records that terra_tiles_place_decid_trees_dev and terra_tiles_edit_trees_dev keep on the device.
+ * A frame is then one stream of launches: zvals -> placements -> tree AO -> terrain draw list -> grass -> tree -> scenery -> deciduous draw lists, and only the lists
+ * are read back.  One call answers both sweeps of tile_draw_t::draw_decid_trees (args.draw_leaves / args.draw_branches); when both run the leaves come first, as at
+ * src/tiled_mesh.cpp:3268-3292.
+ * Restated with the source's operand types: tree::is_visible_to_camera (:858-861), tree::calc_size_scale (:919-928), tree_data_t::get_size_scale_mult (:930), the
+ * counts of tree_data_t::draw_leaves (:1182-1188) and draw_branches (:1128-1140), tree_cont_t::calc_bcube (:2458-2461) with tree::add_bounds_to_bcube (:862-865),
+ * get_draw_tile_dist (src/tiled_mesh.cpp:117), InvSqrt (src/inlines.h:39-50: the bit trick with one iteration, not 1/sqrtf), pos_dir_up::cube_visible_likely
+ * (src/3DWorld.h:724: !valid || point_visible_test(c.get_cube_center()) || cube_visible(c)), cube_t::get_cube_center (0.5f*(d0 + d1)), is_zero_area (some d0 == d1),
+ * is_all_zeros, closest_dist_less_than (dist_less_than(pos, closest_pt(pos), dist), src/csg.cpp:247) and sphere_visible_test.
+ * Tiled-terrain mode throughout: sphere_in_camera_view(.., 0 or 2) is sphere_visible_test alone (src/visibility.cpp:338-339), so ztop / czmax are not read;
+ * wind_enabled and leaf_dynamic_en are 0; rot_angle, the world_space_offset uniform, bcolor, gen_leaf_color and update_leaf_cobj_color stay with the engine.
+ * Mixed arithmetic: 1.1*sphere_radius is a double product narrowed to the float parameter; 1.0*(X_SCENE_SIZE + Y_SCENE_SIZE), 1.5*num_branch_quads*size_scale*mult
+ * and 4.0*nl*size_scale*mult are formed in double; (1.0 - geom_opacity) is a double narrowed to the float parameter of add_leaves / add_branches; size_scale < 0.05
+ * and the tests against 0.0 and 2.0 compare in double.  unsigned(double) converts as the reference binary does (cvttsd2si to 64 bits, the low word; a value beyond
+ * the 64-bit range gives 0): with the camera on a tree's sphere centre InvSqrt(0) is about 2e19 and the product overflows, so the count falls to nl/8 or num/40.
+ * Billboard opacity: CLIP_TO_01((size_scale - lod_end)/lod_denom), 0 when lod_denom == 0; lod_start / lod_end are args.lod_scales (tree_lod_scales[4]: branch start,
+ * branch end, leaf start, leaf end).
+ * Inputs.  tile_xy on the host (checked, not read: no decision depends on a tile's place).  dxoff / dyoff and xoff2 / yoff2 as for terra_tiles_tree_view: xlate =
+ * dtree_off.get_xlate() = ((dxoff + xoff2)*DX_VAL, (dyoff + yoff2)*DY_VAL, 0).  skip [n] bytes (optional): !can_have_trees(), or the tile is not in to_draw -- the
+ * not_drawn bytes of terra_tiles_terrain_view plug in here.  decid [n][capacity] with counts [n] as the placement and the brush leave them; a count above the
+ * capacity means the first `capacity` records.  view; terra_decid_view_args, a host struct read at the call: behind_sphere_mult as for terra_tiles_terrain_view;
+ * zoom_f = (do_zoom ? ZOOM_FACTOR : 1); lod_scales; shadow_pass; reflection_pass (0 or 1); billboards = USE_TREE_BILLBOARDS (the call itself applies && !shadow_pass,
+ * src/tiled_mesh.cpp:3262); leaf_color_changed; draw_leaves, draw_branches.
+ * tree_data [num_tree_data] of terra_decid_tree_data: what the decisions read of a shared tree_data_t, which gen_tree makes and the engine owns -- base_radius,
+ * sphere_radius, sphere_center_zoff, lr_z_cent; leaves_bcube / branches_bcube (x1 x2 y1 y2 z1 z2, relative to tree_center); num_leaves = leaves.size(),
+ * num_branch_quads; flags: TERRA_DCV_GENERATED (is_created(): the trees that use it are `created`), TERRA_DCV_HAS_4TH (has_4th_branches), TERRA_DCV_LEAF_TEX /
+ * TERRA_DCV_BRANCH_TEX (get_render_leaf_texture().is_valid() / get_render_branch_texture().is_valid()).  A device array in the device form.  num_tree_data must equal
+ * terra_decid_params.num_shared_trees and be > 0: tiled terrain always runs with shared trees (max_unique_trees, src/tiled_mesh.cpp:1540).
+ * A record is dropped if its tree_id is outside the table or its entry is not GENERATED: it is not drawn and not in all_bcube, as in terra_tiles_tree_ao_shadows.
+ * Every order below is taken over the remaining (valid) records.
+ * not_visible [n][capacity] bytes (optional, read and written): tree::not_visible, the one piece of state the leaves sweep hands to the branches sweep.  The leaves
+ * sweep outside the shadow pass writes it exactly where :1017 assigns it -- every valid record of a tile that passes the all_bcube test -- and no other byte.  A
+ * branches sweep in the same call reads what that sweep computed, whether the array is given or not; a branches-only call reads the array (NULL = all zero).  The
+ * shadow pass neither reads nor writes it.
+ * Outputs.  tile_out [n]: flags -- TERRA_DCV_TILE_DRAWN (passed :1557 and the cull of :316: !all_bcube.is_zero_area() && !cube_visible(all_bcube + xlate) culls),
+ * TERRA_DCV_TILE_LEAVES / _BRANCHES (which sweeps ran), TERRA_DCV_TILE_SORTED (the sorted branch of :352: not the shadow pass, and all_bcube is all zeros or
+ * closer to camera - xlate than X_SCENE_SIZE + Y_SCENE_SIZE), TERRA_DCV_TILE_BCUBE_ZERO_AREA; num_trees = the valid records; leaf_written, branch_written,
+ * leaf_bb_written, branch_bb_written = the entries written to the four lists.  all_bcube [n][6] = x1 x2 y1 y2 z1 z2 after calc_bcube(), by value: it is a min / max
+ * union, so a zero bound may come out with either sign.  (assign_or_union_with_cube ignores a branches box of all zeros and replaces an all_bcube of all zeros;
+ * union_with_cube takes every leaves box, so the zero cube stays in the union when the first tree's branches box is all zeros or a leaves box is.)  A tile that is
+ * skipped, or empty after the drops, gets a zero record, a zero all_bcube and zero counts, and nothing else of it is written; a tile culled by all_bcube gets its
+ * flags, num_trees, all_bcube and zero counts.
+ * Per record, in record order, for every valid record of a drawn tile, the four arrays of a sweep only when that sweep ran; entries of dropped records and past the
+ * counts are never written.  leaf_word [n][capacity]: bits 0-1 the leaves' form -- 0 not drawn, 1 geometry, 2 geometry and a billboard entry (0 < geom_opacity < 1
+ * in every usual setting of lod_scales), 3 billboard only (geom_opacity == 0); TERRA_DCV_NOT_VISIBLE: not_visible as computed; bits 4-7 the stage at which a record
+ * that is not drawn left: TERRA_DCV_STAGE_NOT_VISIBLE, _NO_LEAVES, _BOX (the leaves' box), _SIZE (size_scale == 0), and in the shadow pass _SHADOW_DIST /
+ * _SHADOW_SPHERE (the culls of :338-339), 0 otherwise.  leaf_scale, leaf_opacity [n][capacity] floats: size_scale as last_size_scale would hold it (0 where the
+ * record left before it was formed) and geom_opacity (0 where not formed); in the shadow pass 0.5 (the value passed to draw_leaves_shadow_only) and 1.  leaf_num
+ * [n][capacity]: nl of draw_leaves (0 where not drawn as geometry).  branch_word, branch_scale, branch_opacity, branch_num: the same for draw_branches_top, the
+ * stages TERRA_DCV_STAGE_NOT_VISIBLE, _BOX (the branches' box), _SIZE (size_scale < 0.05) and _SHADOW_DIST (:325); TERRA_DCV_NOT_VISIBLE as read; branch_num = num
+ * of draw_branches, TERRA_DCV_LOW_DETAIL its low_detail (:1131-1133; force_low_detail = reflection_pass); the shadow pass is draw_branches(1.0, 1, 1).
+ * Lists per tile, with list_counts [n][4] (leaf_list, branch_list, leaf_bb, branch_bb).  A list holds a record at most once, so it never outgrows the capacity.
+ * leaf_list [n][capacity]: record indices of the trees that reach td.draw_leaves, in the reference's order: under TERRA_DCV_TILE_SORTED ascending
+ * (p2p_dist_sq(sphere_center(), camera - xlate), index) -- std::sort of a pair<float, unsigned> is a total order, so no deviation; the key takes sphere_center()
+ * without xlate --, otherwise record order.  branch_list [n][capacity]: the trees that reach td.draw_branches, in record order.  leaf_bb / branch_bb [n][capacity]
+ * of terra_decid_view_bb: the entries add_leaves / add_branches receive from this tile; pos for leaves is draw_pos + (0, 0, lr_z_cent - sphere_center_zoff), for
+ * branches draw_pos = sphere_center() + xlate; opacity = 1 - geom_opacity; rec the record's index.  Order: ascending tree_id, and within an id the order in which
+ * the reference adds them (leaf_list's order for leaves -- the sorted sequence under TERRA_DCV_TILE_SORTED --, record order for branches).  This is the one stated
+ * deviation, the one the tree view's instance lists carry: tree_lod_render_t::finalize sorts all tiles' entries with a comparison that looks at the tree_data_t
+ * pointer alone, so the order inside one tree's run is whatever introsort leaves; render_billboards only needs the runs.  Merging the tiles' runs stays with the
+ * engine.
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or the args (lod_scales included); zoom_f not > 0; reflection_pass other than 0 or 1; a NULL
+ * required pointer (view, args, tree_data; tile_xy, counts, tile_out, all_bcube, list_counts when n > 0; the records, the eight per-record arrays and the four lists
+ * when capacity > 0 as well); a pointer other than skip and not_visible that is not 4-byte aligned; an unsupported S; num_tree_data that is 0 or differs from
+ * num_shared_trees; n*capacity beyond 32 bits.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.  The device form only
+ * enqueues and reads nothing back; tile_xy is a host array in both forms.  Scratch comes from the context's arena.  The host form uploads the per-record arrays and
+ * the lists as the caller has them and copies them back, so the entries the call does not write keep the caller's bytes. */
+typedef struct terra_decid_view_args {
+	float behind_sphere_mult;  /* pos_dir_up::behind_sphere_mult */
+	float zoom_f;              /* do_zoom ? ZOOM_FACTOR : 1 */
+	float lod_scales[4];       /* tree_lod_scales: branch start, branch end, leaf start, leaf end */
+	int32_t shadow_pass, reflection_pass, billboards, leaf_color_changed;
+	int32_t draw_leaves, draw_branches;
+} terra_decid_view_args;     /* 48 bytes */
+typedef struct terra_decid_tree_data {
+	float base_radius, sphere_radius, sphere_center_zoff, lr_z_cent;
+	float leaves_bcube[6], branches_bcube[6];
+	uint32_t num_leaves, num_branch_quads, flags, pad;
+} terra_decid_tree_data;     /* 80 bytes */
+typedef struct terra_decid_view_tile {uint32_t flags, num_trees, leaf_written, branch_written, leaf_bb_written, branch_bb_written, pad[2];} terra_decid_view_tile; /* 32 bytes */
+typedef struct terra_decid_view_bb {uint32_t tree_id, rec; float pos[3], opacity;} terra_decid_view_bb;                                                        /* 24 bytes */
+enum {TERRA_DCV_GENERATED = 1, TERRA_DCV_HAS_4TH = 2, TERRA_DCV_LEAF_TEX = 4, TERRA_DCV_BRANCH_TEX = 8};
+enum {TERRA_DCV_TILE_DRAWN = 1, TERRA_DCV_TILE_LEAVES = 2, TERRA_DCV_TILE_BRANCHES = 4, TERRA_DCV_TILE_SORTED = 8, TERRA_DCV_TILE_BCUBE_ZERO_AREA = 16};
+enum {TERRA_DCV_FORM_NONE = 0, TERRA_DCV_FORM_GEOM = 1, TERRA_DCV_FORM_BOTH = 2, TERRA_DCV_FORM_BILLBOARD = 3, TERRA_DCV_FORM_MASK = 3, TERRA_DCV_NOT_VISIBLE = 4,
+      TERRA_DCV_LOW_DETAIL = 8, TERRA_DCV_STAGE_SHIFT = 4, TERRA_DCV_STAGE_NONE = 0, TERRA_DCV_STAGE_NOT_VISIBLE = 1, TERRA_DCV_STAGE_NO_LEAVES = 2, TERRA_DCV_STAGE_BOX = 3,
+      TERRA_DCV_STAGE_SIZE = 4, TERRA_DCV_STAGE_SHADOW_DIST = 5, TERRA_DCV_STAGE_SHADOW_SPHERE = 6};
+int  terra_tiles_decid_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                                const terra_decid_view_args *args, const terra_decid_tree_data *d_tree_data, uint32_t num_tree_data, const uint8_t *d_skip,
+                                const terra_decid_place *d_decid, const uint32_t *d_counts, uint32_t capacity, uint8_t *d_not_visible, terra_decid_view_tile *d_tile_out,
+                                float *d_all_bcube, uint32_t *d_leaf_word, float *d_leaf_scale, float *d_leaf_opacity, uint32_t *d_leaf_num, uint32_t *d_branch_word,
+                                float *d_branch_scale, float *d_branch_opacity, uint32_t *d_branch_num, uint32_t *d_leaf_list, uint32_t *d_branch_list,
+                                terra_decid_view_bb *d_leaf_bb, terra_decid_view_bb *d_branch_bb, uint32_t *d_list_counts);
+int  terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
+                            const terra_decid_view_args *args, const terra_decid_tree_data *h_tree_data, uint32_t num_tree_data, const uint8_t *h_skip,
+                            const terra_decid_place *h_decid, const uint32_t *h_counts, uint32_t capacity, uint8_t *h_not_visible, terra_decid_view_tile *h_tile_out,
+                            float *h_all_bcube, uint32_t *h_leaf_word, float *h_leaf_scale, float *h_leaf_opacity, uint32_t *h_leaf_num, uint32_t *h_branch_word,
+                            float *h_branch_scale, float *h_branch_opacity, uint32_t *h_branch_num, uint32_t *h_leaf_list, uint32_t *h_branch_list,
+                            terra_decid_view_bb *h_leaf_bb, terra_decid_view_bb *h_branch_bb, uint32_t *h_list_counts);
+
 
 /* ---- plumbing for callers without a HIP runtime of their own (tests, ctypes) */
 int  terra_malloc(terra_ctx *ctx, void **d_ptr, size_t bytes);

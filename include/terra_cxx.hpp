@@ -427,6 +427,32 @@ inline void tile_draw_scenery_lists(tile_batch_dev_t const &b, int xoff2, int yo
 	check(terra_tiles_scenery_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, &camera_pdu, &args, b.d_stats, d_not_drawn, d_scenery, d_counts, capacity,
 		d_radius_override, d_tile_out, d_draw, d_size_scale, d_dist, d_list, list_capacity, d_group_counts), "tile_t::draw_scenery");
 }
+// ---- the deciduous tree draw lists of a batch for the camera: tile_t::draw_decid_trees (src/tiled_mesh.cpp:1555-1563) for every tile, without its GL, shader and
+// colour calls, from the records tiles_gen_decid_trees left on the device.  One call answers both sweeps of tile_draw_t::draw_decid_trees (args.draw_leaves /
+// draw_branches), the leaves first.  d_not_drawn: tile_draw_lists' output (or null); d_tree_data: what the decisions read of the shared tree_data_t's, on the device;
+// d_not_visible: tree::not_visible per record (or null).  out.leaf_word / branch_word hold one TERRA_DCV_* word per record, leaf_list / branch_list record indices in
+// the reference's order, leaf_bb / branch_bb the entries of add_leaves / add_branches in runs of one tree_id
+struct decid_view_out_t {
+	terra_decid_view_tile *d_tile_out; float *d_all_bcube;
+	unsigned *d_leaf_word; float *d_leaf_scale, *d_leaf_opacity; unsigned *d_leaf_num, *d_branch_word; float *d_branch_scale, *d_branch_opacity; unsigned *d_branch_num;
+	unsigned *d_leaf_list, *d_branch_list; terra_decid_view_bb *d_leaf_bb, *d_branch_bb; unsigned *d_list_counts;
+};
+inline terra_decid_view_args decid_view_args_of(float behind_sphere_mult, float zoom_f, float const tree_lod_scales[4], bool shadow_pass, bool reflection_pass, bool use_tree_billboards,
+	bool leaf_color_changed, bool draw_leaves, bool draw_branches)
+{
+	terra_decid_view_args const a = {behind_sphere_mult, zoom_f, {tree_lod_scales[0], tree_lod_scales[1], tree_lod_scales[2], tree_lod_scales[3]}, shadow_pass ? 1 : 0,
+		reflection_pass ? 1 : 0, use_tree_billboards ? 1 : 0, leaf_color_changed ? 1 : 0, draw_leaves ? 1 : 0, draw_branches ? 1 : 0};
+	return a;
+}
+inline void tile_draw_decid_tree_lists(tile_batch_dev_t const &b, int xoff2, int yoff2, terra_view const &camera_pdu, terra_decid_view_args const &args,
+	terra_decid_tree_data const *d_tree_data, unsigned num_tree_data, unsigned char const *d_not_drawn, terra_decid_place const *d_decid_trees, unsigned const *d_counts,
+	unsigned capacity, unsigned char *d_not_visible, decid_view_out_t const &out)
+{
+	check(terra_tiles_decid_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, xoff2, yoff2, &camera_pdu, &args, d_tree_data, num_tree_data, d_not_drawn, d_decid_trees,
+		d_counts, capacity, d_not_visible, out.d_tile_out, out.d_all_bcube, out.d_leaf_word, out.d_leaf_scale, out.d_leaf_opacity, out.d_leaf_num, out.d_branch_word,
+		out.d_branch_scale, out.d_branch_opacity, out.d_branch_num, out.d_leaf_list, out.d_branch_list, out.d_leaf_bb, out.d_branch_bb, out.d_list_counts),
+		"tile_t::draw_decid_trees");
+}
 // tile_t::update_terrain_params (src/tiled_mesh.cpp:321-343): params [n][2][2]{veg, grass, dirt}
 inline void tiles_terrain_params(int const *tile_xy, unsigned n, float *params) {check(terra_tiles_terrain_params(default_ctx(), tile_xy, n, params), "update_terrain_params");}
 // voxel_manager::create_procedural fill (src/voxels.cpp:278-346): `vals` is the voxel_grid<float> storage, z fastest

@@ -10,7 +10,7 @@ MUST_NOT_SPILL = [("speculative_erosion", "wave_scratch_t"),  # k_waves<trace la
                   ("k_sine_grid", "Lb0ELb0E"), ("k_noise_grid", ""), ("k_tile_erosion", ""),
                   ("k_tree_place", ""), ("k_decid_place", ""), ("k_scenery_place", ""),  # their comments promise "no scratch"
                   ("k_terrain_view_tiles", ""), ("k_terrain_view_occluders", ""), ("k_terrain_view_occlusion", ""), ("k_terrain_view_lists", ""), ("k_terrain_view_rank", ""),
-                  ("k_tree_view", ""), ("k_scenery_view", "")]
+                  ("k_tree_view", ""), ("k_scenery_view", ""), ("k_decid_view", "")]
 
 
 def kernels():
