@@ -38,6 +38,30 @@ constexpr int   TSIZE          = 1 << 15; // src/sinf.h:8
 constexpr float PI_F           = 3.141592654f; // src/3DWorld.h:43
 constexpr int   EROSION_PAD    = 4;      // src/erosion.cpp:25
 
+// The sine tables of k_sine_grid (terra_kernels.hpp) and what its staging reads of them.  The kernel sums the terms kstart..89 in ceil(nk / KC) chunks of equal length (the
+// last may be shorter) and copies a chunk into LDS in whole row PAIRS without a test per row: a chunk of kn rows from row k0 reads the rows k0 .. k0 + kn - 1 and, when kn is
+// odd, row k0 + kn as well -- the next chunk's first row or, behind the last term, row 90.  So every table has SG_TABLE_ROWS rows, and the launch that builds the tables
+// writes zeros into the rows behind row 89 (they never reach a sum).  Nothing depends on how large the scratch buffer under a table is: row k begins at k*(padded row length)
+// of the CURRENT grid, so a buffer that grew for a larger grid holds the smaller grid's table in its first SG_TABLE_ROWS*(row length) floats, all written by that grid's launch.
+TERRA_HD constexpr int sg_chunk_len(int kstart, int KC) {int const nk = F_TABLE_SIZE - kstart, n = (nk + KC - 1)/KC; return (nk > 0 && n > 0) ? (nk + n - 1)/n : 0;}
+TERRA_HD constexpr int sg_chunk_last_row(int k0, int kn) {return k0 + kn - 1 + (kn & 1);}
+TERRA_HD constexpr int sg_last_row_read(int kstart, int KC) { // the last table row the staging of any chunk reads (-1: no term, nothing is read)
+	int const per = sg_chunk_len(kstart, KC);
+	int last = -1;
+	for (int k0 = kstart; per > 0 && k0 < F_TABLE_SIZE; k0 += per) {
+		int const kn = (k0 + per > F_TABLE_SIZE) ? F_TABLE_SIZE - k0 : per, l = sg_chunk_last_row(k0, kn);
+		if (l > last) {last = l;}
+	}
+	return last;
+}
+constexpr int SG_TABLE_ROWS = F_TABLE_SIZE + 1;
+constexpr bool sg_table_rows_suffice() {
+	constexpr int kcs[3] = {20, 27, 45}; // "sg.kc" / "sg.kc_tiles"
+	for (int i = 0; i < 3; ++i) {for (int kstart = 0; kstart <= F_TABLE_SIZE; ++kstart) {if (sg_last_row_read(kstart, kcs[i]) >= SG_TABLE_ROWS) return false;}}
+	return true;
+}
+static_assert(sg_table_rows_suffice(), "k_sine_grid's staging would read behind the sine tables");
+
 enum {MGEN_SINE = 0, MGEN_SIMPLEX, MGEN_PERLIN, MGEN_SIMPLEX_GPU, MGEN_DWARP_GPU}; // src/3DWorld.h:1399
 
 // std::min / std::max semantics (NaN-propagation exactly as "(b<a)?b:a" / "(a<b)?b:a"), NOT fminf/fmaxf

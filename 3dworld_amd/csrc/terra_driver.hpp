@@ -897,24 +897,27 @@ template<class BE> struct terra_engine {
 			// front of this one (three dependent launches per grid were ~25 us of a 0.88 ms step).
 			float const *st = sinTable_dev();
 			float const msx = mesh_scale*DX_VAL_INV, msy = mesh_scale*DY_VAL_INV, ms2 = (float)(0.5*(double)mesh_scale), mszi = mesh_scale_z_inv, jmx0 = job.mx0, jmy0 = job.my0, mdx = dx, mdy = dy;
-			float *xt = scratch<float>(s_xt, (size_t)F_TABLE_SIZE*job.nxp), *yt = scratch<float>(s_yt, (size_t)F_TABLE_SIZE*job.nyp);
+			// SG_TABLE_ROWS rows each (terra_common.hpp: what the grid kernel's staging may read); only the rows kstart .. SG_TABLE_ROWS - 1 are read by anyone, so only they are
+			// built -- row k at k*nxp / k*nyp whatever the scratch buffers were grown to by earlier grids -- and the rows behind the last term are zeros
+			float *xt = scratch<float>(s_xt, (size_t)SG_TABLE_ROWS*job.nxp), *yt = scratch<float>(s_yt, (size_t)SG_TABLE_ROWS*job.nyp);
 			uint32_t const nxp = job.nxp, nyp = job.nyp;
-			size_t const ntab = (size_t)F_TABLE_SIZE*(nxp + nyp);
+			unsigned const kfirst = (unsigned)imin(imax(job.kstart, 0), F_TABLE_SIZE);
+			size_t const nxtab = (size_t)(SG_TABLE_ROWS - kfirst)*nxp, ntab = nxtab + (size_t)(SG_TABLE_ROWS - kfirst)*nyp;
 			uint32_t *const mmz = d_mm;
 			be.launch(ntab + (sm_on ? (size_t)nxp + nyp : 0), [=] TERRA_LAMBDA (size_t i) {
 				if (i == 0) {mmz[0] = 0xFFFFFFFFu; mmz[1] = 0xFFFFFFFFu;} // the fused min / max of the grid kernel start here (one launch less than a fill of its own)
-				if (i < (size_t)F_TABLE_SIZE*nxp) {
-					unsigned const k = (unsigned)(i / nxp), x = (unsigned)(i % nxp);
-					float const *stk = st + 5*k;
+				if (i < nxtab) {
+					unsigned const k = kfirst + (unsigned)(i / nxp), x = (unsigned)(i % nxp);
+					float const *stk = st + 5*imin((int)k, F_TABLE_SIZE - 1);
 					float const x_mult = msx*stk[4], xconst = ms2*stk[4] + stk[2] + x_mult*jmx0, xmdx = x_mult*mdx;
-					xt[i] = (x < nx) ? L.SINF(xmdx*(float)x + xconst) : 0.0f;
+					xt[(size_t)k*nxp + x] = (x < nx && k < (unsigned)F_TABLE_SIZE) ? L.SINF(xmdx*(float)x + xconst) : 0.0f;
 				}
 				else if (i < ntab) {
-					size_t const j = i - (size_t)F_TABLE_SIZE*nxp;
-					unsigned const k = (unsigned)(j / nyp), y = (unsigned)(j % nyp);
-					float const *stk = st + 5*k;
+					size_t const j = i - nxtab;
+					unsigned const k = kfirst + (unsigned)(j / nyp), y = (unsigned)(j % nyp);
+					float const *stk = st + 5*imin((int)k, F_TABLE_SIZE - 1);
 					float const y_mult = msy*stk[3], yscale = mszi*stk[0], yconst = ms2*stk[3] + stk[1] + y_mult*jmy0, ymdy = y_mult*mdy;
-					yt[j] = (y < ny) ? yscale*L.SINF(ymdy*(float)(y + row0) + yconst) : 0.0f;
+					yt[(size_t)k*nyp + y] = (y < ny && k < (unsigned)F_TABLE_SIZE) ? yscale*L.SINF(ymdy*(float)(y + row0) + yconst) : 0.0f;
 				}
 				else {
 					size_t const q = i - ntab;
@@ -1647,7 +1650,7 @@ template<class BE> struct terra_engine {
 		tile_band_t const bd = banded ? *band : tile_band_t{zv, zv, zv, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
 		uint32_t const zvx = bd.twx, zvy = bd.twy; // cells per tile in the virtual grid
 		uint32_t const nxpv = round_up(nux*zvx, 128), nypv = round_up(nuy*zvy, 128);
-		size_t const tab_floats = (size_t)F_TABLE_SIZE*(nxpv + nypv), sm_floats = (size_t)nux*zvx + (size_t)nuy*zvy;
+		size_t const tab_floats = (size_t)SG_TABLE_ROWS*(nxpv + nypv), sm_floats = (size_t)nux*zvx + (size_t)nuy*zvy;
 		// one parameter block: tile references | origins of the distinct columns / rows | their per-k constants -- assembled on the host, ONE asynchronous upload
 		stage_layout_t par_lay;
 		size_t const o_refs = par_lay.add_bytes(refs.size()*sizeof(tile_ref_t)), o_m0 = par_lay.add_bytes((size_t)(nux + nuy)*4), o_sk = par_lay.add_bytes((nux + nuy)*sizeof(sine_k_t));
@@ -1682,19 +1685,21 @@ template<class BE> struct terra_engine {
 				else {size_t const j = i - nsx; unsigned const u = (unsigned)(j / zvy), c = tile_band_coord((unsigned)(j % zvy), bd.ysplit, bd.ygap); d_sm[i] = L.COSF(((float)c*dyv + d_m0[nux + u])*dyi*freq);}
 			});
 		}
-		float *d_taby = d_tab + (size_t)F_TABLE_SIZE*nxpv;
-		if (md == MGEN_SINE) {
-			be.launch(tab_floats, [=] TERRA_LAMBDA (size_t i) {
-				bool const isx = i < (size_t)F_TABLE_SIZE*nxpv;
-				size_t const j = isx ? i : i - (size_t)F_TABLE_SIZE*nxpv;
-				unsigned const rowlen = isx ? nxpv : nypv, per = isx ? zvx : zvy, k = (unsigned)(j / rowlen), v = (unsigned)(j % rowlen), u = v / per;
+		float *d_taby = d_tab + (size_t)SG_TABLE_ROWS*nxpv;
+		if (md == MGEN_SINE) { // (SG_TABLE_ROWS rows per table, the rows kstart .. SG_TABLE_ROWS - 1 built, zeros behind the last term: as in gen_grid_dev)
+			unsigned const kfirst = (unsigned)imin(imax(kstart, 0), F_TABLE_SIZE);
+			size_t const nxtab = (size_t)(SG_TABLE_ROWS - kfirst)*nxpv, ntab = nxtab + (size_t)(SG_TABLE_ROWS - kfirst)*nypv;
+			be.launch(ntab, [=] TERRA_LAMBDA (size_t i) {
+				bool const isx = i < nxtab;
+				size_t const j = isx ? i : i - nxtab;
+				unsigned const rowlen = isx ? nxpv : nypv, per = isx ? zvx : zvy, k = kfirst + (unsigned)(j / rowlen), v = (unsigned)(j % rowlen), u = v / per;
 				unsigned const c = isx ? tile_band_coord(v % per, bd.xsplit, bd.xgap) : tile_band_coord(v % per, bd.ysplit, bd.ygap); // the cell's coordinate in the tile's field
-				float val = 0.0f; // zero padding up to a multiple of 128
-				if (u < (isx ? nux : nuy)) {
+				float val = 0.0f; // zero padding up to a multiple of 128, and behind the last term
+				if (u < (isx ? nux : nuy) && k < (unsigned)F_TABLE_SIZE) {
 					sine_k_t const &sk = d_sk[isx ? u : nux + u];
 					val = isx ? L.SINF(sk.xmdx[k]*(float)c + sk.xconst[k]) : sk.yscale[k]*L.SINF(sk.ymdy[k]*(float)c + sk.yconst[k]);
 				}
-				d_tab[i] = val;
+				(isx ? d_tab : d_taby)[(size_t)k*rowlen + v] = val;
 			});
 		}
 		float const sine_offset = hp.sine_bias*mesh_scale_z_inv;

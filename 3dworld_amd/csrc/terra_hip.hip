@@ -304,7 +304,12 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		terra::sg_tiles_t const tl{nullptr, nullptr, 0, (unsigned)opt->sg_rowgroup, 0, 0, 0, 0xFFFFFFFFu, 0, 0xFFFFFFFFu, 0};
 		if (job.plain_only) {
 			auto const go = [&](auto kern) {run(kern, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);};
-			if (opt->sg_kc == 27) go(terra::k_sine_grid<false, false, 27>); else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20>); else go(terra::k_sine_grid<false, false, 45>);
+			if ((job.nx & 3u) == 0) { // rows of whole 16-byte groups: the packed epilogue, and nothing else in the kernel
+				if (opt->sg_kc == 27) go(terra::k_sine_grid<false, false, 27>); else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20>); else go(terra::k_sine_grid<false, false, 45>);
+			}
+			else { // any other row length: the same sum with the per-cell epilogue, instantiations of their own
+				if (opt->sg_kc == 27) go(terra::k_sine_grid<false, false, 27, false>); else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20, false>); else go(terra::k_sine_grid<false, false, 45, false>);
+			}
 		}
 		else                {run(terra::k_sine_grid<false, true>, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);}
 		return true;

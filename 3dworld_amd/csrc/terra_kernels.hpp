@@ -35,7 +35,7 @@ template<class F> __global__ __launch_bounds__(64) void k_waves(F f, unsigned fi
 template<class F> __global__ __launch_bounds__(64) void k_waves_nolds(F f) {f((size_t)blockIdx.x);}
 
 // the same for the lean traces of the sparse erosion scheduler (terra_erosion.hpp: lean_back_t): window + dirty bytes + 4.6 KB of footprint bookkeeping = 9.8 KB of LDS, and
-// at most 128 registers (four waves per SIMD requested) -- beside a k_sine_grid block of another heightmap (29.7 KB, 120 registers per wave) a SIMD then holds three of that
+// at most 128 registers (four waves per SIMD requested) -- beside a k_sine_grid block of another heightmap (29.7 KB, 106 registers per wave, allocated as 112) a SIMD then holds three of that
 // kernel's waves and one of these, and a CU four of its blocks and four of these; the general trace wave (22.7 KB, 260 registers) leaves room for two and two
 template<class F> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_waves_lean(F f) {
 	__builtin_amdgcn_s_setprio(3); // a droplet is a chain of dependent instructions: beside three waves of another kernel on its SIMD it should never wait for an issue slot (it asks for one every ~5 cycles)
@@ -52,8 +52,12 @@ template<class F> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_p
 // v_mul and one v_add (no FMA: the CPU reference rounds the product before adding), i.e. 2*terms VALU ops for 4 B written.
 // Tiling: 128 x 128 cells per 256-thread block, 8 x 8 cells per thread (64 independent accumulator chains), the K range staged
 // through LDS in chunks of <= KC terms (template parameter; the heightmap kernel uses 27: three chunks for 8 octaves, 29.7 KB per block,
-// 118 VGPRs -> 4 blocks = 16 waves per CU alone, and two waves per SIMD beside a 264-register droplet wave of another map's erosion;
-// the plain tile variant uses 27 as well, the general one keeps SG_KC = 45: two chunks, 48 KB), operands of the next step prefetched from LDS while this one is multiplied.
+// 106 VGPRs -> 4 blocks = 16 waves per CU alone, and two waves per SIMD beside a 264-register droplet wave of another map's erosion;
+// the plain tile variant -- 118 VGPRs -- uses 27 as well, the general one keeps SG_KC = 45: two chunks, 48 KB), operands of the next step prefetched from LDS while this one is multiplied.
+// What is not the sum is kept short (profiles/r09_sine_overhead_ab.txt: 5976 -> 5718 vector instructions per wave, 5120 of them the sum; 4 % fewer cycles, which the
+// power-limited clock turns into time on some machines only): a chunk goes from the tables to LDS by direct-to-LDS loads of whole row pairs (no register, no test per row: the tables have a zero row behind the last
+// term, terra_common.hpp), a block inside the grid runs its 16 groups of four cells in a straight line with the island terms waiting in LDS, and row lengths that are no
+// multiple of 4 have an instantiation of their own.
 // Per k a thread issues four ds_read_b128 (conflict-free / broadcast) for 64 mul + 64 add.  The f32 matrix instructions cannot take the
 // products: exact with K = 1, C = 0, but they share the packed-f32 datapath (profiles/r04_sine_matrix_pipe.txt).
 constexpr int SG_BX = 128, SG_BY = 128, SG_TX = 8, SG_TY = 8, SG_THREADS = 256, SG_KC = 45; // 16 x 16 threads
@@ -92,6 +96,13 @@ __device__ __forceinline__ void sg_mul_add_2x8(sg_v2f (&r0)[SG_TX/2], sg_v2f (&r
 	    : "v"(xp[0]), "v"(xp[1]), "v"(xp[2]), "v"(yp), "v"(xp[3]));
 #undef TERRA_SG_2X2
 }
+// {a.x*y, a.y*y} with y the low (SEL = 0) or high (SEL = 1) half of the register pair yp, broadcast by op_sel: the products of a*{y, y} without the copy that builds {y, y}
+template<int SEL> __device__ __forceinline__ sg_v2f sg_pk_mul_bcast(sg_v2f a, sg_v2f yp) {
+	sg_v2f r;
+	if (SEL) {asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(yp));}
+	else     {asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(yp));}
+	return r;
+}
 // acc[i][jp] holds cells (row i, columns 2*jp, 2*jp+1) of the thread's 8 x 8 patch; one call = the four rows that one 16-byte Y read feeds (rows 4 h .. 4 h + 3)
 struct sg_xop_t {float4 a, b;};
 __device__ __forceinline__ sg_xop_t sg_load_x(float const *px, int k) {return sg_xop_t{*(float4 const *)(px + k*SG_BX), *(float4 const *)(px + k*SG_BX + 64)};}
@@ -101,9 +112,22 @@ __device__ __forceinline__ void sg_accumulate_half(sg_v2f (&acc)[SG_TY][SG_TX/2]
 	sg_mul_add_2x8(acc[4*h + 2], acc[4*h + 3], xp, sg_v2f{y.z, y.w});
 }
 
+// a value the compiler cannot see to be the same in all lanes of a wave (the wave's number in its block), as the scalar it is
+__device__ __forceinline__ unsigned sg_wave_uniform(unsigned v) {return (unsigned)__builtin_amdgcn_readfirstlane((int)v);}
+__device__ __forceinline__ char const *sg_wave_uniform_ptr(void const *p) {uint64_t const v = (uint64_t)(uintptr_t)p; return (char const *)(uintptr_t)(((uint64_t)sg_wave_uniform((unsigned)(v >> 32)) << 32) | sg_wave_uniform((unsigned)v));}
+// one direct-to-LDS load: every lane's BYTES (4 or 16) from its own global address to lds + BYTES*lane, lds being the same in all lanes.  Counted by vmcnt like any load; the
+// data is in LDS for the other waves after the next __syncthreads()
+template<int BYTES> __device__ __forceinline__ void sg_load_to_lds(void const *g, float *lds) {
+	static_assert(BYTES == 4 || BYTES == 16, "sg_load_to_lds: 4 or 16 bytes per lane");
+	auto const src = (__attribute__((address_space(1))) void *)(uintptr_t)g; auto const dst = (__attribute__((address_space(3))) void *)lds;
+	if (BYTES == 16) {__builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);} else {__builtin_amdgcn_global_load_lds(src, dst, 4, 0, 0);} // (the size is an immediate of the instruction)
+}
+
 // GENERAL = false: the host proved that every cell takes the short epilogue (terra_engine::sine_plain_only), so finish_cell() -- 64 inlined
 // copies of the plateau / crater / crack / volcano / powf code, ~340 KB of instructions the hot path would otherwise be threaded through -- is left out
-template<bool TILES, bool GENERAL, int KC = SG_KC> __global__ __launch_bounds__(SG_THREADS) void k_sine_grid(grid_job_t job, noise_consts_t nc, sin_lut_t L,
+// PACKED (heightmap, GENERAL = false): the row length is a multiple of 4 (the host's promise, terra_hip.hip), the kernel is the packed epilogue and nothing else; PACKED = false
+// is the same sum with the per-cell epilogue for the other row lengths, an instantiation of its own so that the hot one does not carry it
+template<bool TILES, bool GENERAL, int KC = SG_KC, bool PACKED = true> __global__ __launch_bounds__(SG_THREADS) void k_sine_grid(grid_job_t job, noise_consts_t nc, sin_lut_t L,
 	float const *__restrict__ xt, float const *__restrict__ yt, float const *__restrict__ smx, float const *__restrict__ smy, float *__restrict__ out, unsigned ntx, unsigned nty, uint32_t *__restrict__ mm, sg_tiles_t tiles)
 {
 	__shared__ __attribute__((aligned(16))) float sX[(KC + 2)*SG_BX];
@@ -123,26 +147,34 @@ template<bool TILES, bool GENERAL, int KC = SG_KC> __global__ __launch_bounds__(
 #pragma unroll
 		for (int jp = 0; jp < SG_TX/2; ++jp) {acc[i][jp] = sg_v2f{0.0f, 0.0f};}
 	}
-	int const nk = F_TABLE_SIZE - job.kstart, nchunks = (nk + KC - 1)/KC, per_chunk = (nk + nchunks - 1)/nchunks;
+	int const nk = F_TABLE_SIZE - job.kstart, nchunks = (nk + KC - 1)/KC, per_chunk = sg_chunk_len(job.kstart, KC);
+	// the packed heightmap epilogue takes its island terms from LDS: the block's 128 of each axis go into the spare row KC + 1 (no chunk is staged there and no product reads it)
+	// by direct-to-LDS loads, 4 bytes per lane -- waves 0, 1 the columns', waves 2, 3 the rows' -- which the first chunk's barrier waits for, so the epilogue never
+	// waits for memory (the island tables are zero-padded to the tile grid like the sine tables)
+	constexpr bool ISLANDS_IN_LDS = !TILES && !GENERAL && PACKED;
+	if (ISLANDS_IN_LDS && job.glaciate && job.use_sine_mag) {
+		unsigned const w = sg_wave_uniform(tid >> 6), h = w & 1u, lane = tid & 63u;
+		if (w < 2u) {sg_load_to_lds<4>(smx + bx0 + h*64u + lane, sX + (KC + 1)*SG_BX + h*64u);}
+		else        {sg_load_to_lds<4>(smy + by0 + h*64u + lane, sY + (KC + 1)*SG_BY + h*64u);}
+		if (nchunks <= 0) {__syncthreads();} // (no term to sum: no chunk barrier either)
+	}
 	for (int c = 0; c < nchunks; ++c) { // terms are summed in k order across chunks, exactly like the CPU loop
 		int const k0 = job.kstart + c*per_chunk, kn = ((k0 + per_chunk > F_TABLE_SIZE) ? F_TABLE_SIZE - k0 : per_chunk);
 		if (c > 0) {__syncthreads();} // everyone is done reading the previous chunk
-		{	// stage the chunk: thread (kr, q) copies 16-byte group q of rows kr, kr + 8, ... of both tables.  All loads of a table's chunk are issued before its first LDS write (two
-			// HBM / L2 latencies per chunk instead of one per row group), addresses advance by a uniform stride (tables are zero-padded to a multiple of 128 columns / rows)
-			constexpr int ITERS = (KC*(SG_BX/4) + SG_THREADS - 1)/SG_THREADS;
-			unsigned const kr = tid >> 5, q4 = (tid & 31u)*4u;
-			float const *const gx = xt + (size_t)(k0 + (int)kr)*job.nxp + bx0 + q4, *const gy = yt + (size_t)(k0 + (int)kr)*job.nyp + by0 + q4;
-#pragma unroll
-			for (int tab = 0; tab < 2; ++tab) { // X, then Y: ITERS 16-byte loads in flight per thread (both tables at once would not fit the register budget of four waves per SIMD)
-				float const *const g = tab ? gy : gx; size_t const stride = tab ? job.nyp : job.nxp; float *const sT = tab ? sY : sX;
-				float4 v[ITERS];
-#pragma unroll
-				for (int it = 0; it < ITERS; ++it) {v[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); if ((int)kr + 8*it < kn) {v[it] = *(float4 const *)(g + (size_t)(8*it)*stride);}}
-#pragma unroll
-				for (int it = 0; it < ITERS; ++it) {if ((int)kr + 8*it < kn) {*(float4 *)&sT[(kr + 8u*it)*SG_BX + q4] = v[it];}}
+		{	// stage the chunk straight into LDS, no register in between: one 16-byte direct-to-LDS load per wave moves 64 x 16 B = two whole 128-float rows (lanes 0..31 row r, lanes
+			// 32..63 row r + 1; the LDS side of such a load is wave-uniform base + 16*lane, which is exactly the rows' layout).  Wave w takes the row pairs r = 2 w, 2 w + 8, ...
+			// below kn: the only test is the scalar loop condition, and the addresses are a scalar base that advances by eight table rows plus one per-lane offset.  An odd kn
+			// copies table row k0 + kn as well: the next chunk's first row or, behind row 89, the zero row the tables are padded with (sg_last_row_read(), terra_common.hpp)
+			// into LDS row kn <= KC, which exists and is never used.
+			unsigned const w2 = sg_wave_uniform(tid >> 6)*2u, lane = tid & 63u;
+			unsigned const vx = ((lane >> 5)*job.nxp + (lane & 31u)*4u)*4u, vy = ((lane >> 5)*job.nyp + (lane & 31u)*4u)*4u; // bytes from the row pair's first cell (nxp, nyp < 2^29)
+			char const *gx = sg_wave_uniform_ptr(xt + (size_t)(k0 + (int)w2)*job.nxp + bx0), *gy = sg_wave_uniform_ptr(yt + (size_t)(k0 + (int)w2)*job.nyp + by0);
+			for (int r = (int)w2; r < kn; r += 8) {
+				sg_load_to_lds<16>(gx + vx, sX + r*SG_BX); sg_load_to_lds<16>(gy + vy, sY + r*SG_BY);
+				gx += (size_t)job.nxp*32u; gy += (size_t)job.nyp*32u;
 			}
 		}
-		__syncthreads();
+		__syncthreads(); // (waits for the wave's direct-to-LDS loads -- vmcnt(0) -- before the barrier)
 		// Operand registers: X (the eight columns, used by all eight rows of a step) in two sets that alternate between steps; Y (four rows per 16-byte read) in ONE set --
 		// a Y read is reloaded with the next step's values right after the four rows that use it, half a step (64 packed instructions, ~256 cycles) before it is needed
 		// again, an X set right after its step, a whole step ahead.  24 operand registers instead of 32: the kernel stays under 120 VGPRs, so that two of its waves fit on a
@@ -245,19 +277,55 @@ template<bool TILES, bool GENERAL, int KC = SG_KC> __global__ __launch_bounds__(
 		}
 		return; // (a tile batch has no fused min / max)
 	}
-	if (!GENERAL && !TILES && vec_ok) {
+	if constexpr (!GENERAL && !TILES && PACKED) {
 		// the common case, two cells per instruction (v_pk_mul_f32 / v_pk_add_f32): the island tables are zero-padded to the tile grid, rows of 4 cells
 		// are either wholly inside the grid or wholly outside
 		typedef sg_v2f v2f;
 		bool const gl = job.glaciate && nc.glaciate, sm = job.glaciate && job.use_sine_mag;
 		float4 sx[2], sy[2];
-		sx[0] = sx[1] = sy[0] = sy[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-		if (sm) {
-			sx[0] = *(float4 const *)(smx + bx0 + tx*4); sx[1] = *(float4 const *)(smx + bx0 + 64 + tx*4);
-			sy[0] = *(float4 const *)(smy + by0 + ty*4); sy[1] = *(float4 const *)(smy + by0 + 64 + ty*4);
-		}
+		auto const islands = [&]() { // (staged in front of the first chunk, see above)
+			sx[0] = *(float4 const *)(px + (KC + 1)*SG_BX); sx[1] = *(float4 const *)(px + (KC + 1)*SG_BX + 64);
+			sy[0] = *(float4 const *)(py + (KC + 1)*SG_BY); sy[1] = *(float4 const *)(py + (KC + 1)*SG_BY + 64);
+		};
 		v2f const zme = {nc.zmax_est, nc.zmax_est}, inv = {nc.zmax_est2_inv, nc.zmax_est2_inv}, z2 = {nc.zmax_est2, nc.zmax_est2}, off = {job.sine_offset, job.sine_offset};
 		float fmn = INFINITY, fmx = -INFINITY;
+		if (bx0 + SG_BX <= job.nx && by0 + SG_BY <= job.ny && job.nx < (1u << 24)) {
+			// a block wholly inside the grid (all but the last tile column / row of a map): the 16 groups of 4 cells in a straight line -- no lane is masked, gl / sm are
+			// tested once per block, a row's island term is broadcast from its register pair by op_sel, and the stores share one per-lane offset (< 2^32 bytes: nx < 2^24) on a
+			// scalar row address.  The same operations on the same values in the same order as the guarded loop below.
+			unsigned const voff = (ty*4u*job.nx + tx*4u)*4u;
+			char *const ob = (char *)(out + (size_t)by0*job.nx + bx0);
+			size_t const rowb = (size_t)job.nx*4u;
+			auto const groups = [&](auto GL, auto SM) {
+				if (decltype(SM)::value) {islands();}
+#pragma unroll
+				for (int i = 0; i < SG_TY; ++i) {
+					char *const orow = ob + (size_t)((i >> 2)*64 + (i & 3))*rowb;
+					v2f const syp = (i & 2) ? v2f{sy[i >> 2].z, sy[i >> 2].w} : v2f{sy[i >> 2].x, sy[i >> 2].y};
+#pragma unroll
+					for (int half = 0; half < 2; ++half) {
+						v2f z01 = acc[i][half*2], z23 = acc[i][half*2 + 1];
+						if (decltype(GL)::value) {
+							v2f const r01 = (z01 + zme)*inv, r23 = (z23 + zme)*inv;
+							z01 = ((r01*r01)*r01)*z2 - zme; z23 = ((r23*r23)*r23)*z2 - zme;
+						}
+						if (decltype(SM)::value) {
+							v2f const s01 = {sx[half].x, sx[half].y}, s23 = {sx[half].z, sx[half].w};
+							z01 = z01 + (((i & 1) ? sg_pk_mul_bcast<1>(s01, syp) : sg_pk_mul_bcast<0>(s01, syp)) + off); z23 = z23 + (((i & 1) ? sg_pk_mul_bcast<1>(s23, syp) : sg_pk_mul_bcast<0>(s23, syp)) + off);
+						}
+						fmn = sg_min3(sg_min3(fmn, z01.x, z01.y), z23.x, z23.y);
+						fmx = sg_max3(sg_max3(fmx, z01.x, z01.y), z23.x, z23.y);
+						*(float4 *)(orow + half*256 + voff) = make_float4(z01.x, z01.y, z23.x, z23.y);
+					}
+				}
+			};
+			typedef std::true_type yes; typedef std::false_type no;
+			if (gl) {if (sm) {groups(yes(), yes());} else {groups(yes(), no());}}
+			else    {if (sm) {groups(no(), yes());} else {groups(no(), no());}}
+		}
+		else { // a block on the grid's right or lower edge
+		sx[0] = sx[1] = sy[0] = sy[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		if (sm) {islands();}
 #pragma unroll
 		for (int i = 0; i < SG_TY; ++i) {
 			unsigned const y = by0 + (i >> 2)*64 + ty*4 + (i & 3);
@@ -282,9 +350,10 @@ template<bool TILES, bool GENERAL, int KC = SG_KC> __global__ __launch_bounds__(
 				*(float4 *)(out + (size_t)y*job.nx + x) = make_float4(z01.x, z01.y, z23.x, z23.y);
 			}
 		}
+		}
 		if (mm) {
 			if (fmn <= fmx) {mm_lo = f2ord(fmn); mm_hi = ~f2ord(fmx);}
-			wave_minmax_publish(mm_lo, mm_hi, mm);
+			wave_minmax_publish_full(mm_lo, mm_hi, mm); // (all 64 lanes are here: a block leaves the kernel as a whole or not at all)
 		}
 		return;
 	}

@@ -21,6 +21,27 @@ __device__ __forceinline__ void wave_minmax_publish(uint32_t lo, uint32_t hi, ui
 		if (hi < __hip_atomic_load(&mm[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {atomicMin(&mm[1], hi);}
 	}
 }
+// the same for a wave whose 64 lanes are ALL active, without a trip through the LDS crossbar per step: the minimum of each row of 16 lanes by data-parallel-primitive
+// moves (lanes i ^ 1, i ^ 2, then the mirror images inside 8 and inside 16 lanes -- afterwards every lane holds its row's minimum), the four rows as scalars.
+// A minimum of unsigned integers does not depend on the order it is taken in.
+__device__ __forceinline__ uint32_t wave_min_u32_full(uint32_t v) {
+#define TERRA_DPP_MIN(CTRL) {uint32_t const o = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false); v = (o < v) ? o : v;}
+	TERRA_DPP_MIN(0xB1)  // quad_perm:[1,0,3,2]
+	TERRA_DPP_MIN(0x4E)  // quad_perm:[2,3,0,1]
+	TERRA_DPP_MIN(0x141) // row_half_mirror
+	TERRA_DPP_MIN(0x140) // row_mirror
+#undef TERRA_DPP_MIN
+	uint32_t const a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16), c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+	uint32_t const ab = (a < b) ? a : b, cd = (c < d) ? c : d;
+	return (ab < cd) ? ab : cd;
+}
+__device__ __forceinline__ void wave_minmax_publish_full(uint32_t lo, uint32_t hi, uint32_t *mm) {
+	lo = wave_min_u32_full(lo); hi = wave_min_u32_full(hi);
+	if ((threadIdx.x & 63) == 0 && lo != 0xFFFFFFFFu) { // (as above)
+		if (lo < __hip_atomic_load(&mm[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {atomicMin(&mm[0], lo);}
+		if (hi < __hip_atomic_load(&mm[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {atomicMin(&mm[1], hi);}
+	}
+}
 __device__ __forceinline__ float sg_min3(float a, float b, float c) {float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;}
 __device__ __forceinline__ float sg_max3(float a, float b, float c) {float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;}
 __device__ __forceinline__ void minmax_acc(float v, uint32_t &lo, uint32_t &hi) {if (v == v) {uint32_t const o = f2ord(v); lo = (o < lo) ? o : lo; hi = (~o < hi) ? ~o : hi;}}
