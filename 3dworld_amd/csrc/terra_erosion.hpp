@@ -168,7 +168,7 @@ template<class MEM> TERRA_HD bool droplet_run(droplet_state_t &d, MEM &mem, eros
 		float const dl = sqrtf(dx*dx+dz*dz);
 		if (TERRA_UNLIKELY(dl <= FLT_EPSILON)) { // pick random dir: libm cosf/sinf in the reference, reproduced bit-for-bit (terra_sincosf.hpp)
 			float const a = rgen.rand_float()*ec.two_pi;
-			dx = glibc_cosf(a); dz = glibc_sinf(a);
+			dx = glibc_cosf_below_120(a); dz = glibc_sinf_below_120(a); // 0 <= a < 2*pi
 		}
 		else {dx /= dl; dz /= dl;}
 		float const nxp = xp+dx, nzp = zp+dz;

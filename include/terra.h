@@ -796,6 +796,8 @@ int  terra_tiles_edit_flowers(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
  * vector, NOT upv), cp, sterm, x_sterm, near_, far_ and valid into it; valid == 0 makes every frustum test pass, as in the reference.
  * terra_make_view: pos_dir_up's constructor (src/visibility.cpp:67-92) with the C library's tanf / sinf / atanf, for callers without a camera_pdu.  angle (radians,
  * half the vertical field of view) and aspect are the caller's: the window_width / PERSP_ANGLE defaults that the constructor takes for 0 stay with the engine.
+ * (They are not the same numbers: for its default angle the reference's build folds tanf at compile time, correctly rounded, and camera_pdu's x_sterm and
+ * behind_sphere_mult differ in the last place from what the C library's tanf gives for the same angle passed explicitly.  Copy camera_pdu's members.)
  * TERRA_ERR_ARG where the constructor asserts (near < 0, far <= near, a zero dir, tanf(angle) <= 0 with aspect != 1) and for a NULL pointer; *out is untouched then.
  * terra_grass_view_params: tt_grass_scale_factor (1).  TERRA_ERR_ARG for a value that is not finite and > 0 (src/grass.cpp:1126 resets such a value to 1; here it is
  * refused and nothing changes).  grass_length is terra_flower_params.grass_length, num_rnd_grass_blocks the landscape's.

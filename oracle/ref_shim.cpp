@@ -824,3 +824,71 @@ REF_API void ref_voxel_rdata(int rseed1, int rseed2, float mag, float freq, floa
 	ngen.gen_sines(mag, freq);
 	memcpy(rdata, ngen.rdata, sizeof(ngen.rdata));
 }
+
+// ---------------------------------------------------------------------------------------------
+// (5) the primitives every pass shares (tests/golden/make_primitive_golden.py records them, tests/primitive_cases.py compares): pos_dir_up and its tests
+//     (src/visibility.cpp:67-219, compiled in place), cube_t::closest_dist_less_than, InvSqrt (src/inlines.h:39-50), do_line_clip (src/Math3d.cpp:1070-1086,
+//     compiled in place), the steep-slope statement of tile_t::get_lod_level and the four float -> integer conversions as this build performs them.
+// ---------------------------------------------------------------------------------------------
+int window_width(1920), window_height(1080), do_zoom(0); // src/3DWorld.cpp: the constructor reads them only for an aspect or an angle of 0.0
+static pos_dir_up shim_pdu;
+// out[19]: pos, dir, upv_, cp, sterm, x_sterm, near_, far_, behind_sphere_mult, angle, tterm.  0 where the constructor would assert (:70,78,89): it is not called then
+REF_API int ref_pdu_make(float const pos[3], float const dir[3], float const up[3], float angle, float aspect, float near_clip, float far_clip, float *out) {
+	if (!(near_clip >= 0.0 && far_clip > 0.0 && far_clip > near_clip)) return 0;
+	if (vector3d(dir[0], dir[1], dir[2]) == zero_vector) return 0;
+	if (aspect == 0.0f) return 0; // would read the window's size
+	float const angle_used((angle == 0.0) ? float(0.5*TO_RADIANS*PERSP_ANGLE) : angle);
+	if (double(aspect) != 1.0 && !(tanf(angle_used) > 0.0)) return 0;
+	shim_pdu = pos_dir_up(point(pos[0], pos[1], pos[2]), vector3d(dir[0], dir[1], dir[2]), vector3d(up[0], up[1], up[2]), angle, near_clip, far_clip, aspect, 1);
+	pos_dir_up const &p(shim_pdu);
+	for (unsigned i = 0; i < 3; ++i) {out[i] = p.pos[i]; out[3+i] = p.dir[i]; out[6+i] = p.upv_[i]; out[9+i] = p.cp[i];}
+	out[12] = p.sterm; out[13] = p.x_sterm; out[14] = p.near_; out[15] = p.far_; out[16] = p.behind_sphere_mult; out[17] = p.angle; out[18] = p.tterm;
+	return 1;
+}
+REF_API void ref_pdu_set_valid(int v) {shim_pdu.valid = (v != 0);}
+REF_API void ref_pdu_points(float const *p, unsigned n, unsigned char *out) { // p: x y z
+	for (unsigned i = 0; i < n; ++i) {out[i] = shim_pdu.point_visible_test(point(p[3*i], p[3*i+1], p[3*i+2]));}
+}
+REF_API void ref_pdu_spheres(float const *s, unsigned n, unsigned char *out) { // s: x y z radius
+	for (unsigned i = 0; i < n; ++i) {out[i] = shim_pdu.sphere_visible_test(point(s[4*i], s[4*i+1], s[4*i+2]), s[4*i+3]);}
+}
+// c: x1 x2 y1 y2 z1 z2; s: the sphere of sphere_and_cube_visible_test; q: the point and the distance of closest_dist_less_than.
+// out[5]: cube_visible, cube_completely_visible, cube_visible_likely, sphere_and_cube_visible_test, closest_dist_less_than
+REF_API void ref_pdu_cubes(float const *c, float const *s, float const *q, unsigned n, unsigned char *out) {
+	for (unsigned i = 0; i < n; ++i) {
+		cube_t const cube(c[6*i], c[6*i+1], c[6*i+2], c[6*i+3], c[6*i+4], c[6*i+5]);
+		point const qp(q[4*i], q[4*i+1], q[4*i+2]);
+		out[5*i]   = shim_pdu.cube_visible(cube);
+		out[5*i+1] = shim_pdu.cube_completely_visible(cube);
+		out[5*i+2] = shim_pdu.cube_visible_likely(cube);
+		out[5*i+3] = shim_pdu.sphere_and_cube_visible_test(point(s[4*i], s[4*i+1], s[4*i+2]), s[4*i+3], cube);
+		out[5*i+4] = dist_less_than(qp, cube.closest_pt(qp), q[4*i+3]); // cube_t::closest_dist_less_than (src/csg.cpp:247-249, a file that is not built): its one statement over the reference's own inlines
+	}
+}
+REF_API void ref_inv_sqrt(float const *x, unsigned n, float *out) {for (unsigned i = 0; i < n; ++i) {out[i] = InvSqrt(x[i]);}}
+bool do_line_clip(point &v1, point &v2, float const d[3][2]); // src/Math3d.cpp:1070
+REF_API void ref_do_line_clip(float const *v, float const *d, unsigned n, unsigned char *ok, float *out) { // v: v1 v2; d: x1 x2 y1 y2 z1 z2; out: the clipped v1 v2
+	for (unsigned i = 0; i < n; ++i) {
+		point v1(v[6*i], v[6*i+1], v[6*i+2]), v2(v[6*i+3], v[6*i+4], v[6*i+5]);
+		float const dd[3][2] = {{d[6*i], d[6*i+1]}, {d[6*i+2], d[6*i+3]}, {d[6*i+4], d[6*i+5]}};
+		ok[i] = do_line_clip(v1, v2, dd);
+		for (unsigned k = 0; k < 3; ++k) {out[6*i+k] = v1[k]; out[6*i+3+k] = v2[k];}
+	}
+}
+// tile_t::get_lod_level's statement for a steep tile (src/tiled_mesh.cpp:1924), alone, with the operand types and the log2 this translation unit's headers give it
+REF_API void ref_lod_steep_dist(float const *dist_in, float const *mnz, unsigned n, float *out) {
+	for (unsigned i = 0; i < n; ++i) {
+		float dist(dist_in[i]);
+		float const min_normal_z(mnz[i]);
+		dist /= -log2(2.0*min_normal_z);
+		out[i] = dist;
+	}
+}
+// the conversions as the binary performs them: the argument arrives at run time in a function of its own, nothing is folded
+#define SHIM_NOINLINE __attribute__((noinline, noclone))
+SHIM_NOINLINE static unsigned shim_f2u(float  v) {return unsigned(v);}
+SHIM_NOINLINE static int      shim_f2i(float  v) {return int(v);}
+SHIM_NOINLINE static unsigned shim_d2u(double v) {return unsigned(v);}
+SHIM_NOINLINE static int      shim_d2i(double v) {return int(v);}
+REF_API void ref_convert_floats (float  const *x, unsigned n, unsigned *u, int *s) {for (unsigned i = 0; i < n; ++i) {u[i] = shim_f2u(x[i]); s[i] = shim_f2i(x[i]);}}
+REF_API void ref_convert_doubles(double const *x, unsigned n, unsigned *u, int *s) {for (unsigned i = 0; i < n; ++i) {u[i] = shim_d2u(x[i]); s[i] = shim_d2i(x[i]);}}

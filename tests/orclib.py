@@ -207,6 +207,19 @@ class Checker:
             f("get_use_hip_terrain", C.c_int, [])
             f("hip_terrain_calls", C.c_uint, [])
             f("set_use_hip_proc_gen", None, [C.c_int])
+        # the shared primitives, from the reference's own code only (oracle/ref_shim.cpp section 5); the C restatement has no such rows.  A library built from an
+        # older harness (a prebuilt oracle/_ref/libengine_*.so) still loads for the rows it has: the primitive tests then fail on the missing method, no other test does
+        if kind == "ref" and hasattr(self.lib, "ref_pdu_make"):
+            f("pdu_make", C.c_int, [C.c_void_p] * 3 + [C.c_float] * 4 + [C.c_void_p])
+            f("pdu_set_valid", None, [C.c_int])
+            f("pdu_points", None, [C.c_void_p, C.c_uint, C.c_void_p])
+            f("pdu_spheres", None, [C.c_void_p, C.c_uint, C.c_void_p])
+            f("pdu_cubes", None, [C.c_void_p] * 3 + [C.c_uint, C.c_void_p])
+            f("inv_sqrt", None, [C.c_void_p, C.c_uint, C.c_void_p])
+            f("do_line_clip", None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p])
+            f("lod_steep_dist", None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p])
+            f("convert_floats", None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p])
+            f("convert_doubles", None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p])
         if kind == "orc":
             f("apply_erosion_stats", None, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(ErosionStats), C.c_void_p])
 
@@ -458,6 +471,56 @@ class Checker:
         out = np.zeros(420, np.float32)
         self._voxel_rdata(rseed1, rseed2, mag, freq, out.ctypes.data)
         return out
+
+    # ---- the shared primitives ("ref" only)
+    def pdu_make(self, pos, dir, up, angle, aspect, near, far):
+        """pos_dir_up's constructor; the object stays current for the pdu_* tests.  -> float32[19] (pos, dir, upv_, cp, sterm, x_sterm, near_, far_,
+        behind_sphere_mult, angle, tterm), or None where the constructor would assert"""
+        a = [np.ascontiguousarray(v, np.float32) for v in (pos, dir, up)]
+        out = np.zeros(19, np.float32)
+        ok = self._pdu_make(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, angle, aspect, near, far, out.ctypes.data)
+        return out if ok else None
+
+    def pdu_set_valid(self, v): self._pdu_set_valid(int(v))
+
+    def pdu_points(self, p):
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        out = np.zeros(len(p), np.uint8); self._pdu_points(p.ctypes.data, len(p), out.ctypes.data); return out
+
+    def pdu_spheres(self, s):
+        s = np.ascontiguousarray(s, np.float32).reshape(-1, 4)
+        out = np.zeros(len(s), np.uint8); self._pdu_spheres(s.ctypes.data, len(s), out.ctypes.data); return out
+
+    def pdu_cubes(self, c, s, q):
+        """-> uint8[n][5]: cube_visible, cube_completely_visible, cube_visible_likely, sphere_and_cube_visible_test(s), closest_dist_less_than(q)"""
+        c = np.ascontiguousarray(c, np.float32).reshape(-1, 6)
+        s = np.ascontiguousarray(s, np.float32).reshape(len(c), 4); q = np.ascontiguousarray(q, np.float32).reshape(len(c), 4)
+        out = np.zeros((len(c), 5), np.uint8); self._pdu_cubes(c.ctypes.data, s.ctypes.data, q.ctypes.data, len(c), out.ctypes.data); return out
+
+    def inv_sqrt(self, x):
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros(x.size, np.float32); self._inv_sqrt(x.ctypes.data, x.size, out.ctypes.data); return out
+
+    def do_line_clip(self, v, d):
+        """v [n][6] = v1 v2, d [n][6] = x1 x2 y1 y2 z1 z2 -> (ok uint8[n], clipped v1 v2 float32[n][6])"""
+        v = np.ascontiguousarray(v, np.float32).reshape(-1, 6); d = np.ascontiguousarray(d, np.float32).reshape(len(v), 6)
+        ok = np.zeros(len(v), np.uint8); out = np.zeros((len(v), 6), np.float32)
+        self._do_line_clip(v.ctypes.data, d.ctypes.data, len(v), ok.ctypes.data, out.ctypes.data)
+        return ok, out
+
+    def lod_steep_dist(self, dist, mnz):
+        dist = np.ascontiguousarray(dist, np.float32); mnz = np.ascontiguousarray(mnz, np.float32)
+        assert dist.size == mnz.size
+        out = np.zeros(dist.size, np.float32); self._lod_steep_dist(dist.ctypes.data, mnz.ctypes.data, dist.size, out.ctypes.data); return out
+
+    def convert_floats(self, x):
+        """-> (unsigned(float) uint32[n], int(float) int32[n]) as the reference's build converts"""
+        x = np.ascontiguousarray(x, np.float32)
+        u = np.zeros(x.size, np.uint32); s = np.zeros(x.size, np.int32); self._convert_floats(x.ctypes.data, x.size, u.ctypes.data, s.ctypes.data); return u, s
+
+    def convert_doubles(self, x):
+        x = np.ascontiguousarray(x, np.float64)
+        u = np.zeros(x.size, np.uint32); s = np.zeros(x.size, np.int32); self._convert_doubles(x.ctypes.data, x.size, u.ctypes.data, s.ctypes.data); return u, s
 
 
 def bits(a):

@@ -253,6 +253,11 @@ class Occluder:
             self.sub_cubes.append(c)
 
 
+def lod_steep_dist(dist, mnz):
+    """get_lod_level's statement for a steep tile: dist /= -log2(2.0*min_normal_z) (:1924), the quotient in double, narrowed into the float"""
+    return f32(float(f32(dist)) / -_libm.log2(2.0 * float(f32(mnz))))
+
+
 def get_lod_level(sc, v, a, t, tally=None):
     def count(k):
         if tally is not None:
@@ -275,7 +280,7 @@ def get_lod_level(sc, v, a, t, tally=None):
             else:
                 count("lod_water_blocked")
         elif float(mnz) < 0.25:
-            dist = f32(float(dist) / -_libm.log2(2.0 * float(mnz)))
+            dist = lod_steep_dist(dist, mnz)
             count("lod_steep")
         else:
             count("lod_mid")
