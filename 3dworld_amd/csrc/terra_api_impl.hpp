@@ -981,6 +981,75 @@ int terra_tiles_terrain_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 		if (h_counts[1]) {ctx->eng.be.d2h(h_occluded, st.dev<uint32_t>(oc), (size_t)std::min(h_counts[1], n)*4);}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_reflection_view_args) == sizeof(terra::reflection_view_args_pod_t) && sizeof(terra_reflection_view_args) == 24, "terra_reflection_view_args layout");
+static_assert(sizeof(terra_water_view_args) == sizeof(terra::water_view_args_pod_t) && sizeof(terra_water_view_args) == 8, "terra_water_view_args layout");
+int terra_tiles_reflection_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view,
+                                    const terra_reflection_view_args *args, const terra_tile_stats *d_stats, const float *d_min_normal_z, const float *d_trmax,
+                                    const float *d_tile_zmax, const uint8_t *d_flags, uint8_t *d_occl_state, uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack,
+                                    uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn, uint8_t *d_reflect) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::reflection_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY ctx->eng.tiles_reflection_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_flags, d_occl_state},
+		d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_reflect); TERRA_CATCH
+}
+int terra_tiles_reflection_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view,
+                                const terra_reflection_view_args *args, const terra_tile_stats *h_stats, const float *h_min_normal_z, const float *h_trmax,
+                                const float *h_tile_zmax, const uint8_t *h_flags, uint8_t *h_occl_state, uint8_t *h_status, float *h_dist, uint8_t *h_lod, uint8_t *h_crack,
+                                uint32_t *h_draw_order, uint32_t *h_occluded, uint32_t *h_counts, uint8_t *h_not_drawn, uint8_t *h_reflect) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::reflection_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.reflection_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
+		if (n == 0) return TERRA_OK;
+		if (!tile_xy || !h_stats || !h_status || !h_dist || !h_lod || !h_crack || !h_draw_order || !h_occluded || !h_counts) return terra::fail(TERRA_ERR_ARG, "null argument");
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), mn = st.opt_in(h_min_normal_z, (size_t)n*4), tr = st.opt_in(h_trmax, (size_t)n*4),
+			tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n), os = st.inout(h_occl_state, n, h_occl_state != nullptr), su = st.out(h_status, n),
+			di = st.out(h_dist, (size_t)n*4), lo = st.out(h_lod, n), cr = st.out(h_crack, (size_t)n*4), dr = st.temp((size_t)n*4), oc = st.temp((size_t)n*4), cn = st.temp(8),
+			nd = st.opt_out(h_not_drawn, n), rf = st.opt_out(h_reflect, n);
+		st.begin();
+		ctx->eng.tiles_reflection_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{st.dev<terra_tile_stats>(s), st.dev<float>(mn), st.dev<float>(tr), st.dev<float>(tz),
+			st.dev<uint8_t>(fl), st.dev<uint8_t>(os)}, st.dev<uint8_t>(su), st.dev<float>(di), st.dev<uint8_t>(lo), st.dev<uint8_t>(cr), st.dev<uint32_t>(dr), st.dev<uint32_t>(oc),
+			st.dev<uint32_t>(cn), st.dev<uint8_t>(nd), st.dev<uint8_t>(rf));
+		st.end();
+		st.end_counted(dr, cn, h_draw_order, h_counts, 1, n); // the lists' entries past their counts stay as the caller had them
+		ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);
+		if (h_counts[1]) {ctx->eng.be.d2h(h_occluded, st.dev<uint32_t>(oc), (size_t)std::min(h_counts[1], n)*4);}
+	TERRA_CATCH
+}
+int terra_tiles_water_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_water_view_args *args,
+                               const terra_tile_stats *d_stats, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags, const uint8_t *d_status,
+                               uint32_t *d_water_list, uint8_t *d_cap_mask, uint32_t *d_counts) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::water_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY ctx->eng.tiles_water_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{d_stats, nullptr, d_trmax, d_tile_zmax, d_flags, nullptr}, d_status, d_water_list,
+		d_cap_mask, d_counts); TERRA_CATCH
+}
+int terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_water_view_args *args,
+                           const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, const uint8_t *h_status,
+                           uint32_t *h_water_list, uint8_t *h_cap_mask, uint32_t *h_counts) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::water_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.water_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
+		if ((h_status != nullptr) != (h_cap_mask != nullptr)) return terra::fail(TERRA_ERR_ARG, "tiles_water_view: status and cap_mask are both null or both given");
+		if (n == 0) return TERRA_OK;
+		if (!tile_xy || !h_stats || !h_water_list || !h_counts) return terra::fail(TERRA_ERR_ARG, "null argument");
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), tr = st.opt_in(h_trmax, (size_t)n*4), tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n),
+			su = st.opt_in(h_status, n), wl = st.temp((size_t)n*4), cm = st.opt_out(h_cap_mask, n), cn = st.temp(8);
+		st.begin();
+		ctx->eng.tiles_water_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{st.dev<terra_tile_stats>(s), nullptr, st.dev<float>(tr), st.dev<float>(tz), st.dev<uint8_t>(fl),
+			nullptr}, st.dev<uint8_t>(su), st.dev<uint32_t>(wl), st.dev<uint8_t>(cm), st.dev<uint32_t>(cn));
+		st.end();
+		st.end_counted(wl, cn, h_water_list, h_counts, 1, n); // the list's entries past its count stay as the caller had them
+		if (h_status) {ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);}
+	TERRA_CATCH
+}
 static_assert(sizeof(terra_tree_view_args) == sizeof(terra::tree_view_args_pod_t) && sizeof(terra_tree_view_args) == 32, "terra_tree_view_args layout");
 static_assert(sizeof(terra_tree_view_tile) == sizeof(terra::tree_view_tile_pod_t) && sizeof(terra_tree_view_tile) == 32, "terra_tree_view_tile layout");
 static_assert(sizeof(terra_tree_view_inst) == sizeof(terra::tree_view_inst_pod_t) && sizeof(terra_tree_view_inst) == 16, "terra_tree_view_inst layout");

@@ -19,6 +19,7 @@
 #include "terra_flowers.hpp"
 #include "terra_grassview.hpp"
 #include "terra_terrainview.hpp"
+#include "terra_waterview.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_treeview.hpp"
@@ -3131,8 +3132,38 @@ template<class BE> struct terra_engine {
 		require_tile_size();
 		if (!view_finite(view)) throw std::invalid_argument("tiles_terrain_view: a member of the view is not finite");
 		if (!terrain_view_args_finite(a)) throw std::invalid_argument("tiles_terrain_view: a member of the args is not finite");
-		if (a.reflection_pass == 1) throw std::invalid_argument("tiles_terrain_view: reflection_pass 1 needs can_have_reflection, which stays with the engine");
+		if (a.reflection_pass == 1) throw std::invalid_argument("tiles_terrain_view: reflection_pass 1 needs can_have_reflection: it is terra_tiles_reflection_view's");
 		if (a.reflection_pass < 0 || a.reflection_pass > 3) throw std::invalid_argument("tiles_terrain_view: reflection_pass must be 0, 2 or 3");
+	}
+	// the last step of the simple forms of the terrain view and the reflection view, a thread per tile: its cracks, and its place in its list -- the rank of
+	// (dist, batch index) among the drawn tiles is where the sort of :2915 puts it
+	void terrain_view_lists_simple(uint32_t n, int32_t const *d_nbr, uint8_t const *d_status, float const *d_dist, uint8_t const *d_lod, uint8_t *d_crack, uint32_t *d_draw_order,
+		uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn)
+	{
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
+			uint32_t const me = d_status[t] & TV_STATUS_MASK;
+			for (uint32_t k = 0; k < 4; ++k) {
+				int32_t const u = d_nbr[t*9 + terrain_view_nbr_slot(k >> 1, k & 1u)];
+				bool const adj = me == TV_DRAWN && u >= 0 && (d_status[u] & TV_STATUS_MASK) != TV_ABSENT;
+				d_crack[t*4 + k] = adj ? (uint8_t)terrain_view_crack_index(k >> 1, k & 1u, d_lod[t], d_lod[u]) : TERRAIN_VIEW_NO_CRACK;
+			}
+			if (d_not_drawn) {d_not_drawn[t] = (me != TV_DRAWN) ? 1 : 0;}
+			if (me == TV_DRAWN) {
+				uint32_t rank = 0;
+				for (uint32_t u = 0; u < n; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_DRAWN && terrain_view_before(d_dist[u], u, d_dist[t], (uint32_t)t)) ? 1u : 0u;}
+				d_draw_order[rank] = (uint32_t)t;
+			}
+			else if (me == TV_OCCLUDED) {
+				uint32_t rank = 0;
+				for (uint32_t u = 0; u < t; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_OCCLUDED) ? 1u : 0u;}
+				d_occluded[rank] = (uint32_t)t;
+			}
+			if (t == 0) {
+				uint32_t nd = 0, no = 0;
+				for (uint32_t u = 0; u < n; ++u) {uint32_t const su = d_status[u] & TV_STATUS_MASK; nd += (su == TV_DRAWN) ? 1u : 0u; no += (su == TV_OCCLUDED) ? 1u : 0u;}
+				d_counts[0] = nd; d_counts[1] = no;
+			}
+		});
 	}
 	void tiles_terrain_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, terrain_view_args_pod_t const &a, terrain_view_in_t const &in,
 		uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn)
@@ -3180,30 +3211,144 @@ template<class BE> struct terra_engine {
 			if (occluded) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
 			if (in.occl_state) {in.occl_state[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED;} // set_last_occluded (:2906)
 		});
-		// (4) a thread per tile: its cracks, and its place in its list -- the rank of (dist, batch index) among the drawn tiles is where the sort of :2915 puts it
+		terrain_view_lists_simple(n, d_nbr, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn); // (4) the cracks and the lists
+	}
+
+	// ---- the terrain draw list of reflection pass 1 (terra_waterview.hpp): tile_draw_t::draw(1) -- the loop above with the filter of :2869, can_have_reflection
+	// (:2630-2683), and get_lod_level(1).  The checks that need no array (the host form runs them before it stages anything):
+	void reflection_view_check(view_pod_t const &view, reflection_view_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_reflection_view: a member of the view is not finite");
+		if (!reflection_view_args_finite(a)) throw std::invalid_argument("tiles_reflection_view: a member of the args is not finite");
+		if (a.tv.reflection_pass != 1) throw std::invalid_argument("tiles_reflection_view: reflection_pass must be 1 (terra_tiles_terrain_view takes 0, 2 and 3)");
+	}
+	// the bounding box of the batch's tile positions: the walk's visited bits
+	static reflect_box_t reflection_view_box(int32_t const *tile_xy, uint32_t n) {
+		int64_t x0 = tile_xy[0], x1 = x0, y0 = tile_xy[1], y1 = y0;
+		for (uint32_t t = 1; t < n; ++t) {
+			x0 = std::min<int64_t>(x0, tile_xy[2*t]); x1 = std::max<int64_t>(x1, tile_xy[2*t]); y0 = std::min<int64_t>(y0, tile_xy[2*t+1]); y1 = std::max<int64_t>(y1, tile_xy[2*t+1]);
+		}
+		int64_t const w = x1 - x0 + 1, h = y1 - y0 + 1;
+		if (w > 2048 || h > 2048 || w*h > (1 << 18)) throw std::invalid_argument("tiles_reflection_view: the bounding box of the batch's tile positions is more than 2048 wide or holds more than 2^18 positions");
+		reflect_box_t b;
+		b.x0 = (int32_t)x0; b.y0 = (int32_t)y0; b.w = (uint32_t)w; b.nwords = (uint32_t)((w*h + 31)/32); b.cap = (uint32_t)(w + h + 2);
+		return b;
+	}
+	void tiles_reflection_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, reflection_view_args_pod_t const &a, terrain_view_in_t const &in,
+		uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn, uint8_t *d_reflect)
+	{
+		reflection_view_check(view, a);
+		if (n == 0) return;
+		if (!tile_xy || !in.stats || !d_status || !d_dist || !d_lod || !d_crack || !d_draw_order || !d_occluded || !d_counts) throw std::invalid_argument("tiles_reflection_view: null argument");
+		if ((((uintptr_t)in.stats | (uintptr_t)in.min_normal_z | (uintptr_t)in.trmax | (uintptr_t)in.tile_zmax | (uintptr_t)d_dist | (uintptr_t)d_draw_order | (uintptr_t)d_occluded |
+		      (uintptr_t)d_counts) & 3u) != 0) throw std::invalid_argument("tiles_reflection_view: d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_dist, d_draw_order, d_occluded and d_counts must be 4-byte aligned");
+		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_reflection_view");
+		reflect_box_t const box = reflection_view_box(tile_xy, n);
+		reflect_consts_t rc;
+		rc.tv = terrain_view_consts(view, a.tv, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
+		rc.zmin = a.tv.occluder_zmin; rc.zmax = a.zmax;
+		terrain_view_consts_t const c = rc.tv;
+		// scratch: that of the terrain view, and per tile what the walk reads of it (reflect_tile_t), the provisional result of the occlusion test, the answer of :2869; for the simple form the
+		// state of last_occluded as the loop goes, the marks of the walk (the start tile's index + 1) and its work list; the constants for k_reflect_walk
+		int32_t *d_txy, *d_nbr_w, *d_work; terrain_view_occluder_t *d_occ; uint32_t *d_nocc, *d_key_tile, *d_mark; uint8_t *d_test, *d_prov, *d_refl, *d_state; float *d_keys; reflect_consts_t *d_rc; reflect_tile_t *d_rt;
+		stage_layout_t lay;
+		lay.add(d_rc, 1); lay.add(d_rt, n); lay.add(d_occ, n); lay.add(d_txy, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_nocc, 4); lay.add(d_keys, n); lay.add(d_key_tile, n); lay.add(d_mark, n); lay.add(d_work, n);
+		lay.add(d_test, n); lay.add(d_prov, n); lay.add(d_refl, n); lay.add(d_state, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		be.h2d_async(d_rc, &rc, sizeof(rc)); // (k_reflect_walk reads the constants from memory)
+		int32_t const *d_nbr = d_nbr_w;
+		if constexpr (BE::has_kernels) {
+			if (be.tile_reflection_view(rc, d_rc, in, d_txy, d_nbr, n, box, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_reflect, d_occ, d_nocc, d_test,
+				d_keys, d_key_tile, d_rt, d_prov, d_refl)) return;
+		}
+		// the simple form.  (1) a logical thread per tile: everything but :2869, the occlusion test, the cracks and the lists
 		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			uint32_t const me = d_status[t] & TV_STATUS_MASK;
-			for (uint32_t k = 0; k < 4; ++k) {
-				int32_t const u = d_nbr[t*9 + terrain_view_nbr_slot(k >> 1, k & 1u)];
-				bool const adj = me == TV_DRAWN && u >= 0 && (d_status[u] & TV_STATUS_MASK) != TV_ABSENT;
-				d_crack[t*4 + k] = adj ? (uint8_t)terrain_view_crack_index(k >> 1, k & 1u, d_lod[t], d_lod[u]) : TERRAIN_VIEW_NO_CRACK;
+			terrain_view_tile_t const o = terrain_view_tile(c, in, d_txy, t);
+			d_status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); d_dist[t] = o.dist; d_lod[t] = o.lod; d_test[t] = o.test; d_rt[t] = reflect_tile(c, in, d_txy, t, o.visible != 0);
+			d_state[t] = in.occl_state ? in.occl_state[t] : (uint8_t)TV_STATE_NONE; d_mark[t] = 0u;
+			if (d_reflect) {d_reflect[t] = RF_NOT_ASKED;}
+		});
+		// (2) one thread: the occluders in batch order, then the loop of :2863 as written, in batch order: a tile's walk sees what the turns before it left of last_occluded
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {
+			uint32_t nocc = 0;
+			for (uint32_t t = 0; t < n; ++t) {
+				if (!(d_status[t] & TV_WAS_OCCLUDER)) continue;
+				terrain_view_geom_t const g = terrain_view_geom_of(c, in, d_txy, t);
+				terrain_view_occluder_t &o = d_occ[nocc++];
+				terrain_view_mesh_box(g, in.stats[t].mzmin, in.stats[t].mzmax, o.bc);
+				for (uint32_t s = 0; s < 16; ++s) {terrain_view_occluder_column(c, g, in.stats[t], s, o.sub[s]);}
+				o.tile = (int32_t)t; o.pad = 0;
 			}
-			if (d_not_drawn) {d_not_drawn[t] = (me != TV_DRAWN) ? 1 : 0;}
-			if (me == TV_DRAWN) {
-				uint32_t rank = 0;
-				for (uint32_t u = 0; u < n; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_DRAWN && terrain_view_before(d_dist[u], u, d_dist[t], (uint32_t)t)) ? 1u : 0u;}
-				d_draw_order[rank] = (uint32_t)t;
+			*d_nocc = nocc;
+			for (uint32_t t = 0; t < n; ++t) {
+				if ((d_status[t] & TV_STATUS_MASK) != TV_DRAWN) continue;
+				terrain_view_geom_t const g = terrain_view_geom_of(c, in, d_txy, t);
+				uint32_t r = reflect_without_walk(c, d_rt[t].flags);
+				if (r == RF_NOT_ASKED) {
+					reflect_corners_t const k = reflect_corners(c, g.bc, in.stats[t].mzmax);
+					auto seen = [&](uint32_t u) {bool const was = d_mark[u] == t + 1u; d_mark[u] = t + 1u; return was;};
+					auto occluded = [&](uint32_t u) {return d_state[u] == TV_STATE_OCCLUDED;};
+					r = reflect_walk(rc, in.stats, d_nbr, d_rt, t, k, d_work, n, seen, occluded, [](reflect_corners_t &) {}) ? RF_WALK_FOUND : RF_WALK_NOTHING;
+				}
+				if (d_reflect) {d_reflect[t] = (uint8_t)r;}
+				if (r < RF_HAS_WATER) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_NO_REFLECTION); continue;} // :2869
+				if (!d_test[t] || nocc == 0) continue;
+				bool const occluded_now = terrain_view_occluded(c, g, in.stats[t], d_occ, nocc, (int32_t)t);
+				if (occluded_now) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
+				d_state[t] = occluded_now ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED; // set_last_occluded (:2906)
+				if (in.occl_state) {in.occl_state[t] = d_state[t];}
 			}
-			else if (me == TV_OCCLUDED) {
-				uint32_t rank = 0;
-				for (uint32_t u = 0; u < t; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_OCCLUDED) ? 1u : 0u;}
-				d_occluded[rank] = (uint32_t)t;
+		});
+		terrain_view_lists_simple(n, d_nbr, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn); // (3) the cracks and the lists
+	}
+
+	// ---- water quads and water caps of a batch (terra_waterview.hpp): tile_t::is_water_visible (src/tiled_mesh.cpp:2131-2133) for every tile as tile_draw_t::draw_water
+	// (:3075) asks it, and the edge tests of tile_t::draw_water_cap (:2102-2119) for the tiles that tile_t::draw (:2046, :2078) and tile_draw_t::draw (:2957-2959)
+	// call it for.  The checks that need no array:
+	void water_view_check(view_pod_t const &view, water_view_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_water_view: a member of the view is not finite");
+		if (!isfinite(a.behind_sphere_mult)) throw std::invalid_argument("tiles_water_view: a member of the args is not finite");
+	}
+	void tiles_water_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, water_view_args_pod_t const &a, terrain_view_in_t const &in,
+		uint8_t const *d_status, uint32_t *d_water_list, uint8_t *d_cap_mask, uint32_t *d_counts)
+	{
+		water_view_check(view, a);
+		if ((d_status != nullptr) != (d_cap_mask != nullptr)) throw std::invalid_argument("tiles_water_view: status and cap_mask are both null or both given");
+		if (n == 0) return;
+		if (!tile_xy || !in.stats || !d_water_list || !d_counts) throw std::invalid_argument("tiles_water_view: null argument");
+		if ((((uintptr_t)in.stats | (uintptr_t)in.trmax | (uintptr_t)in.tile_zmax | (uintptr_t)d_water_list | (uintptr_t)d_counts) & 3u) != 0) {
+			throw std::invalid_argument("tiles_water_view: d_stats, d_trmax, d_tile_zmax, d_water_list and d_counts must be 4-byte aligned");
+		}
+		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_water_view");
+		terrain_view_args_pod_t const ta = {a.behind_sphere_mult, 0.0f, a.water_enabled, 0, 0};
+		terrain_view_consts_t const c = terrain_view_consts(view, ta, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
+		int32_t *d_txy, *d_nbr_w; uint8_t *d_wv; // scratch: the coordinates, the neighbour table, and what the pass keeps of a tile (WV_*)
+		stage_layout_t lay;
+		lay.add(d_txy, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_wv, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		int32_t const *d_nbr = d_nbr_w;
+		if constexpr (BE::has_kernels) {if (be.tile_water_view(c, in, d_txy, d_nbr, n, d_status, d_wv, d_water_list, d_cap_mask, d_counts)) return;}
+		// the simple form.  (1) a logical thread per tile: what is_water_visible() and a neighbour's draw_water_cap read of it
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {d_wv[t] = (uint8_t)water_view_tile(c, in, d_txy, t);});
+		// (2) one thread: tile_draw_t::draw_water's loop in batch order, then the caps
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {
+			uint32_t nw = 0, nc = 0;
+			for (uint32_t t = 0; t < n; ++t) {if (water_view_listed(d_wv[t])) {d_water_list[nw++] = t;}}
+			d_counts[0] = nw;
+			if (!d_status) return;
+			for (uint32_t t = 0; t < n; ++t) {
+				uint32_t const m = water_view_caps(c, d_wv[t], d_status[t], d_nbr, d_wv, t);
+				d_cap_mask[t] = (uint8_t)m;
+				nc += m ? 1u : 0u;
 			}
-			if (t == 0) {
-				uint32_t nd = 0, no = 0;
-				for (uint32_t u = 0; u < n; ++u) {uint32_t const su = d_status[u] & TV_STATUS_MASK; nd += (su == TV_DRAWN) ? 1u : 0u; no += (su == TV_OCCLUDED) ? 1u : 0u;}
-				d_counts[0] = nd; d_counts[1] = no;
-			}
+			d_counts[1] = nc;
 		});
 	}
 

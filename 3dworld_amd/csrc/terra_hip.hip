@@ -626,12 +626,35 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
 		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
-		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c, in, tile_xy, n, status, dist, lod, test);
+		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c, in, tile_xy, n, status, dist, lod, test, (terra::reflect_tile_t *)nullptr);
 		run(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, c, in, tile_xy, n, status, occ, nocc);
-		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c, in, tile_xy, occ, nocc, test, status);
+		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c, in, tile_xy, occ, nocc, test, status, (uint8_t *)nullptr);
 		run(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
 		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, keys, key_tile, counts, draw_order);
 		return true;
+	}
+	// the terrain draw list of reflection pass 1: the launches of the terrain view with k_reflect_walk and k_reflect_finish between the occlusion test and the lists
+	bool tile_reflection_view(terra::reflect_consts_t const &c, terra::reflect_consts_t const *d_consts, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, terra::reflect_box_t const &box,
+		uint8_t *status, float *dist, uint8_t *lod, uint8_t *crack, uint32_t *draw_order, uint32_t *occluded, uint32_t *counts, uint8_t *not_drawn, uint8_t *reflect,
+		terra::terrain_view_occluder_t *occ, uint32_t *nocc, uint8_t *test, float *keys, uint32_t *key_tile, terra::reflect_tile_t *rt, uint8_t *prov, uint8_t *refl)
+	{
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
+		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c.tv, in, tile_xy, n, status, dist, lod, test, rt);
+		run(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, c.tv, in, tile_xy, n, status, occ, nocc);
+		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c.tv, in, tile_xy, occ, nocc, test, status, prov);
+		run(terra::k_reflect_walk, dim3(n), dim3(terra::RF_THREADS), ((size_t)box.nwords + box.cap)*4, d_consts, in.stats, tile_xy, nbr, rt, status, prov, box, refl, reflect ? reflect : refl);
+		run(terra::k_reflect_finish, dim3(nb), dim3(T), 0, n, prov, refl, status, in.occl_state);
+		run(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
+		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, keys, key_tile, counts, draw_order);
+		return true;
+	}
+	// water quads and water caps: one workgroup (k_water_view)
+	bool tile_water_view(terra::terrain_view_consts_t const &c, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, uint8_t const *status, uint8_t *wv,
+		uint32_t *water_list, uint8_t *cap_mask, uint32_t *counts)
+	{
+		return launch_if(true, terra::k_water_view, dim3(1), dim3(terra::TV_THREADS), c, in, tile_xy, nbr, n, status, wv, water_list, cap_mask, counts);
 	}
 	// the pine and palm tree draw lists for a camera: one workgroup per tile (k_tree_view)
 	bool tile_tree_view(terra::tree_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra::tree_inst_pod_t const *insts, terra_tile_stats const *stats, uint8_t const *skip,

@@ -2143,12 +2143,13 @@ __global__ __launch_bounds__(GV_THREADS) void k_grass_view(grass_view_consts_t c
 constexpr uint32_t TV_THREADS = 256, TV_ORDER_LDS = 1024;
 static_assert(TV_THREADS == TREEP_THREADS, "tp_block_rank and tp_emit rank TREEP_THREADS threads");
 __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_tiles(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy, uint32_t n,
-	uint8_t *__restrict__ status, float *__restrict__ dist, uint8_t *__restrict__ lod, uint8_t *__restrict__ test)
+	uint8_t *__restrict__ status, float *__restrict__ dist, uint8_t *__restrict__ lod, uint8_t *__restrict__ test, reflect_tile_t *__restrict__ rt)
 {
 	uint32_t const t = blockIdx.x*TV_THREADS + threadIdx.x;
 	if (t >= n) return;
 	terrain_view_tile_t const o = terrain_view_tile(c, in, tile_xy, t);
 	status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); dist[t] = o.dist; lod[t] = o.lod; test[t] = o.test;
+	if (rt) {rt[t] = reflect_tile(c, in, tile_xy, t, o.visible != 0);} // (the reflection pass: what the walk of :2630-2662 reads of a tile)
 }
 __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_occluders(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy, uint32_t n,
 	uint8_t const *__restrict__ status, terrain_view_occluder_t *occ, uint32_t *__restrict__ nocc)
@@ -2178,11 +2179,14 @@ __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_occluders(terrain_v
 	}
 }
 __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_occlusion(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy,
-	terrain_view_occluder_t const *__restrict__ occ, uint32_t const *__restrict__ nocc_p, uint8_t const *__restrict__ test, uint8_t *status)
+	terrain_view_occluder_t const *__restrict__ occ, uint32_t const *__restrict__ nocc_p, uint8_t const *__restrict__ test, uint8_t *status, uint8_t *__restrict__ prov)
 {
 	__shared__ uint32_t s_all[TV_THREADS/64];
 	uint32_t const t = blockIdx.x, tid = threadIdx.x, nocc = *nocc_p;
-	if ((status[t] & TV_STATUS_MASK) != TV_DRAWN || !test[t] || nocc == 0u) return; // (uniform)
+	if ((status[t] & TV_STATUS_MASK) != TV_DRAWN || !test[t] || nocc == 0u) { // (uniform)
+		if (prov && tid == 0) {prov[t] = TV_STATE_NONE;}
+		return;
+	}
 	terrain_view_geom_t const g = terrain_view_geom_of(c, in, tile_xy, t);
 	uint32_t const q = tid >> 4, s = tid & 15u;
 	float b[3][2];
@@ -2202,6 +2206,7 @@ __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_occlusion(terrain_v
 	__syncthreads();
 	if (tid == 0) {
 		bool const occluded = s_all[0] && s_all[1] && s_all[2] && s_all[3];
+		if (prov) {prov[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED; return;} // (the reflection pass: k_reflect_finish decides whether the test took place)
 		if (occluded) {status[t] = (uint8_t)((status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
 		if (in.occl_state) {in.occl_state[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED;} // set_last_occluded (:2906)
 	}
@@ -2254,6 +2259,99 @@ __global__ __launch_bounds__(TV_THREADS) void k_terrain_view_rank(float const *_
 	uint32_t const nd = counts[0], i = blockIdx.x*TV_THREADS + threadIdx.x;
 	if (nd <= TV_ORDER_LDS || i >= nd) return;
 	draw_order[tv_rank(keys, nd, keys[i], i)] = key_tile[i];
+}
+
+// ------------------------------------------------------------------ the terrain draw list of reflection pass 1 (tile_draw_t::draw(1) with can_have_reflection, :2869 and
+// :2630-2683; terra_waterview.hpp): the launches above with pass 1's LOD, and between the occlusion test and the lists the two kernels of :2869.
+//  - k_terrain_view_tiles also leaves what the walk reads of a tile (reflect_tile_t: get_bcube(), is_visible() for :2657, has_water, all_water, the incoming state); k_terrain_view_occlusion leaves its result as a provisional byte (0 not
+//    tested, 1 occluded, 2 not) instead of writing status and occl_state: a candidate's test does not depend on :2869, only whether it takes place.
+//  - k_reflect_walk: one wave per tile; the lanes clear the visited bits in LDS -- one for every tile position of the batch's bounding box -- and lane 0 goes on: every
+//    tile but a candidate is done at once, and so is a candidate that :2667-2669 decide; for the others it runs reflect_walk with the work list in LDS too.  was_last_occluded()
+//    of a tile A met on the walk of tile T matters only where A has water, and there A's own answer at :2869 needs no walk (yes unless all_water): A was occluded
+//    by this loop exactly when it precedes T in the batch, its provisional byte is 1 and it is not all_water -- else its incoming state counts.  So no walk waits for
+//    another, and all of them are one launch.
+//  - k_reflect_finish: a lane per tile turns the provisional bytes into status and occl_state: a candidate that :2869 drops gets status 6 and keeps its state.
+constexpr uint32_t RF_THREADS = 64;
+__global__ __launch_bounds__(RF_THREADS) void k_reflect_walk(reflect_consts_t const *cp, terra_tile_stats const *__restrict__ stats, int32_t const *__restrict__ tile_xy,
+	int32_t const *__restrict__ nbr, reflect_tile_t const *__restrict__ rt, uint8_t const *__restrict__ status, uint8_t const *__restrict__ prov, reflect_box_t B,
+	uint8_t *refl, uint8_t *reflect)
+{
+	extern __shared__ uint32_t s_rf[]; // [B.nwords] visited bits, [B.cap] work list
+	for (uint32_t i = threadIdx.x; i < B.nwords; i += RF_THREADS) {s_rf[i] = 0u;}
+	__syncthreads();
+	if (threadIdx.x != 0) return;
+	// Everything a walk reads sits at addresses that are uniform over the wave, so the compiler would keep all of it in scalar registers, run out of them and park
+	// them in vector lanes.  One lane works: its values belong in vector registers.  Hiding the tile's index and the address of the constants (in device memory
+	// for this) in vector registers puts them there.
+	uint32_t t = blockIdx.x;
+	asm volatile("" : "+v"(t), "+v"(cp));
+	reflect_consts_t const c = *cp;
+	uint32_t r = RF_NOT_ASKED;
+	if ((status[t] & TV_STATUS_MASK) == TV_DRAWN) {
+		reflect_tile_t const me = rt[t];
+		r = reflect_without_walk(c.tv, me.flags);
+		if (r == RF_NOT_ASKED) {
+			reflect_corners_t const k = reflect_corners(c.tv, me.bc, stats[t].mzmax);
+			uint32_t *const bits = s_rf;
+			auto seen = [=](uint32_t u) {
+				uint32_t const bit = ((uint32_t)tile_xy[2u*u] - (uint32_t)B.x0) + ((uint32_t)tile_xy[2u*u + 1u] - (uint32_t)B.y0)*B.w;
+				if ((bit >> 5) >= B.nwords) return true; // (no tile of the batch lies outside its bounding box)
+				uint32_t const w = bits[bit >> 5], m = 1u << (bit & 31u);
+				bits[bit >> 5] = w | m;
+				return (w & m) != 0u;
+			};
+			auto occluded = [=](uint32_t u) {
+				uint32_t const f = rt[u].flags;
+				return (u < t && prov[u] == TV_STATE_OCCLUDED && !(f & RT_ALL_WATER)) || (f & RT_OCCLUDED_IN) != 0u;
+			};
+			// (opaque per visit: the corners do not change along a walk, so the tests of the line clip that depend on them alone -- a dozen lane masks, two scalar
+			// registers each -- would be hoisted out of the walk's loop, kept through it and spilled)
+			auto pin = [](reflect_corners_t &q) {asm volatile("" : "+v"(q.p[0][0]), "+v"(q.p[0][1]), "+v"(q.p[0][2]), "+v"(q.p[1][0]), "+v"(q.p[1][1]), "+v"(q.p[1][2]));};
+			r = reflect_walk(c, stats, nbr, rt, t, k, (int32_t *)(s_rf + B.nwords), B.cap, seen, occluded, pin) ? RF_WALK_FOUND : RF_WALK_NOTHING;
+		}
+	}
+	refl[t] = (uint8_t)r;
+	reflect[t] = (uint8_t)r; // (the caller's array, or `refl` again)
+}
+__global__ __launch_bounds__(TV_THREADS) void k_reflect_finish(uint32_t n, uint8_t const *__restrict__ prov, uint8_t const *__restrict__ refl, uint8_t *__restrict__ status,
+	uint8_t *__restrict__ occl_state)
+{
+	uint32_t const t = blockIdx.x*TV_THREADS + threadIdx.x;
+	if (t >= n || (status[t] & TV_STATUS_MASK) != TV_DRAWN) return;
+	if (refl[t] < RF_HAS_WATER) {status[t] = (uint8_t)((status[t] & ~TV_STATUS_MASK) | TV_NO_REFLECTION); return;} // :2869: no set_last_occluded
+	if (prov[t] == TV_STATE_NONE) return;
+	if (prov[t] == TV_STATE_OCCLUDED) {status[t] = (uint8_t)((status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
+	if (occl_state) {occl_state[t] = prov[t];} // set_last_occluded (:2906)
+}
+
+// ------------------------------------------------------------------ water quads and water caps of a tile batch (tile_t::is_water_visible, :2131-2133; the edge tests of
+// tile_t::draw_water_cap, :2102-2119; terra_waterview.hpp).  k_water_view: one workgroup walks the batch 256 tiles at a time, twice.  First a lane takes a tile's
+// four facts (present, has_water, within DRAW_DIST_TILES, is_visible) into a byte of global scratch, and the tiles with is_water_visible() are appended in batch
+// order (tp_emit).  Then, with a status array, a lane reads its four neighbours' bytes through the [n][9] table and writes its cap mask.
+__global__ __launch_bounds__(TV_THREADS) void k_water_view(terrain_view_consts_t c, terrain_view_in_t in, int32_t const *__restrict__ tile_xy, int32_t const *__restrict__ nbr, uint32_t n,
+	uint8_t const *__restrict__ status, uint8_t *wv, uint32_t *__restrict__ water_list, uint8_t *__restrict__ cap_mask, uint32_t *__restrict__ counts)
+{
+	__shared__ uint32_t s_wave[TV_THREADS/64];
+	uint32_t const tid = threadIdx.x;
+	uint32_t nw = 0, nc = 0;
+	for (uint32_t base = 0; base < n; base += TV_THREADS) {
+		uint32_t const t = base + tid;
+		uint32_t const w = (t < n) ? water_view_tile(c, in, tile_xy, t) : 0u;
+		if (t < n) {wv[t] = (uint8_t)w;}
+		tp_emit(t < n && water_view_listed(w), [&] {return t;}, water_list, n, nw, s_wave);
+	}
+	if (tid == 0) {counts[0] = nw;}
+	if (!status) return;
+	__syncthreads(); // the bytes of the neighbours, written by other lanes
+	for (uint32_t base = 0; base < n; base += TV_THREADS) {
+		uint32_t const t = base + tid;
+		uint32_t const m = (t < n) ? water_view_caps(c, wv[t], status[t], nbr, wv, t) : 0u;
+		if (t < n) {cap_mask[t] = (uint8_t)m;}
+		uint32_t total;
+		tp_block_rank(m != 0u, s_wave, total);
+		nc += total;
+	}
+	if (tid == 0) {counts[1] = nc;}
 }
 
 // ------------------------------------------------------------------ the pine and palm tree draw lists of a tile batch for a camera (tile_t::draw_pine_trees,

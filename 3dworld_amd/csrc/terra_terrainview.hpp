@@ -150,10 +150,11 @@ TERRA_HD bool terrain_view_occluder_dist(terrain_view_consts_t const &c, terrain
 	float const OCCLUDER_DIST = 0.2f, dval = OCCLUDER_DIST*c.scaled_tile_radius + radius;
 	return (cam[0] - g.cx)*(cam[0] - g.cx) + (cam[1] - g.cy)*(cam[1] - g.cy) < dval*dval;
 }
-// tile_t::get_lod_level(reflection_pass) for reflection_pass != 1 (low_detail is false): in_tiles = get_dist_to_camera_in_tiles(0)
+// tile_t::get_lod_level(reflection_pass): in_tiles = get_dist_to_camera_in_tiles(0); low_detail (:1913) holds in pass 1 only
 TERRA_HD uint32_t terrain_view_lod(terrain_view_consts_t const &c, float mzmin, float mzmax, float min_normal_z, float in_tiles, bool shadow_maps) {
 	if (mzmax == mzmin) return TERRAIN_VIEW_LODS - 1u; // flat, use lowest LOD
-	uint32_t lod_level = 0;
+	bool const low_detail = c.reflection_pass == 1 && (double)min_normal_z > 0.1;
+	uint32_t lod_level = low_detail ? 1u : 0u; // min(NUM_LODS-1, 1U)
 	float dist = in_tiles;
 	if (shadow_maps) {dist /= (float)2;}
 	if (min_normal_z > 0.0f) {
@@ -177,7 +178,7 @@ TERRA_HD uint32_t terrain_view_crack_index(uint32_t dim, uint32_t dir, uint32_t 
 TERRA_HD uint32_t terrain_view_nbr_slot(uint32_t dim, uint32_t dir) {return dim ? (dir ? 7u : 1u) : (dir ? 5u : 3u);}
 
 // ---- what the first pass leaves of a tile: everything but the occlusion test, the cracks and the lists
-struct terrain_view_tile_t {float dist; uint8_t status, lod, occluder, test;}; // status: TV_ABSENT .. TV_OCCLUDED_BEFORE, or TV_DRAWN for a candidate; test: the loop of :2872 runs (if there are occluders)
+struct terrain_view_tile_t {float dist; uint8_t status, lod, occluder, test, visible;}; // status: TV_ABSENT .. TV_OCCLUDED_BEFORE, or TV_DRAWN for a candidate; test: the loop of :2872 runs (if there are occluders)
 struct terrain_view_in_t { // the per-tile arrays
 	terra_tile_stats const *stats; float const *min_normal_z, *trmax, *tile_zmax; uint8_t const *flags; uint8_t *occl_state;
 };
@@ -187,7 +188,7 @@ TERRA_HD terrain_view_geom_t terrain_view_geom_of(terrain_view_consts_t const &c
 }
 TERRA_HD terrain_view_tile_t terrain_view_tile(terrain_view_consts_t const &c, terrain_view_in_t const &in, int32_t const *tile_xy, size_t t) {
 	terrain_view_tile_t o;
-	o.dist = 0.0f; o.status = TV_ABSENT; o.lod = 0; o.occluder = 0; o.test = 0;
+	o.dist = 0.0f; o.status = TV_ABSENT; o.lod = 0; o.occluder = 0; o.test = 0; o.visible = 0;
 	uint32_t const fl = in.flags ? in.flags[t] : 0u;
 	if (fl & TV_FLAG_ABSENT) return o;
 	terra_tile_stats const &st = in.stats[t];
@@ -196,6 +197,7 @@ TERRA_HD terrain_view_tile_t terrain_view_tile(terrain_view_consts_t const &c, t
 	o.dist = terrain_view_rel_dist_xy(c, g, st.radius);
 	o.lod = (uint8_t)terrain_view_lod(c, st.mzmin, st.mzmax, in.min_normal_z ? in.min_normal_z[t] : 0.0f, terrain_view_dist_in_tiles(c, g, st.radius), (fl & TV_FLAG_SHADOW_MAPS) != 0);
 	bool const visible = terrain_view_visible(c, g, st.mzmin, st.mzmax, st.radius);
+	o.visible = visible ? 1 : 0;
 	o.occluder = (c.check_occlusion && !(fl & TV_FLAG_NO_OCCLUDER) && terrain_view_occluder_dist(c, g, st.radius) && visible) ? 1 : 0; // use_as_occluder() (:2857-2860)
 	uint32_t const state = in.occl_state ? in.occl_state[t] : (uint32_t)TV_STATE_NONE;
 	if (o.dist > DRAW_DIST_TILES) {o.status = TV_TOO_FAR;}

@@ -163,6 +163,26 @@ TVIEW_ABSENT, TVIEW_TOO_FAR, TVIEW_NOT_VISIBLE, TVIEW_OCCLUDED_BEFORE, TVIEW_OCC
 TVIEW_STATUS_MASK, TVIEW_WAS_OCCLUDER = 7, 0x80
 TVIEW_FLAG_ABSENT, TVIEW_FLAG_NO_OCCLUDER, TVIEW_FLAG_SHADOW_MAPS = 1, 2, 4  # the per-tile flag byte of tiles_terrain_view
 
+TVIEW_NO_REFLECTION = 6      # tiles_reflection_view: the tile was dropped at can_have_reflection
+REFLECT_NOT_ASKED, REFLECT_NO_WATER, REFLECT_WALK_NOTHING, REFLECT_HAS_WATER, REFLECT_WALK_FOUND = range(5)  # the reflect byte of tiles_reflection_view
+
+
+class ReflectionViewArgs(C.Structure):  # terra_reflection_view_args
+    _fields_ = [("tv", TerrainViewArgs), ("zmax", C.c_float)]
+
+
+def make_reflection_view_args(behind_sphere_mult=1.0, zmin=0.0, zmax=0.0, water_enabled=1, check_occlusion=1, reflection_pass=1):
+    """terra_reflection_view_args: a terra_terrain_view_args of reflection pass 1 whose occluder_zmin is the engine's zmin, and the engine's zmax"""
+    return ReflectionViewArgs(make_terrain_view_args(behind_sphere_mult, zmin, water_enabled, check_occlusion, reflection_pass), zmax)
+
+
+class WaterViewArgs(C.Structure):  # terra_water_view_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("water_enabled", C.c_int32)]
+
+
+def make_water_view_args(behind_sphere_mult=1.0, water_enabled=1):
+    return WaterViewArgs(behind_sphere_mult, int(water_enabled))
+
 
 class TreeViewArgs(C.Structure):  # terra_tree_view_args
     _fields_ = [("behind_sphere_mult", C.c_float), ("zoom_f", C.c_float), ("tree_depth_scale", C.c_float), ("window_width", C.c_int32), ("shadow_pass", C.c_int32),
@@ -434,6 +454,10 @@ _PROTOS = {
     "terra_view_behind_sphere_mult": (_i32, [C.c_float, C.c_float, _vp]),
     "terra_tiles_terrain_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_terrain_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "terra_tiles_reflection_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 17),
+    "terra_tiles_reflection_view": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 17),
+    "terra_tiles_water_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 10),
+    "terra_tiles_water_view": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 10),
     "terra_tiles_tree_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_tree_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_scenery_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
@@ -1092,6 +1116,35 @@ class Terra:
                                                    occluded.ctypes.data, counts.ctypes.data, None))
         return status, dist, lod, crack, order[:counts[0]], occluded[:counts[1]], counts, os_
 
+    def tiles_reflection_view(self, tile_xy, stats, view, args, min_normal_z=None, trmax=None, tile_zmax=None, flags=None, occl_state=None, dxoff=0, dyoff=0):
+        """tile_draw_t::draw(1) for every tile: tiles_terrain_view's inputs with a ReflectionViewArgs.
+        -> (status, dist, lod, crack, draw_order, occluded, counts, occl_state after the call or None, reflect uint8 [n])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        opt = lambda a, dt: None if a is None else np.array(a, dt).reshape(n)  # noqa: E731  (copies: occl_state is written)
+        mn, tr, tz, fl, os_ = opt(min_normal_z, np.float32), opt(trmax, np.float32), opt(tile_zmax, np.float32), opt(flags, np.uint8), opt(occl_state, np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        status, dist, lod, crack, reflect = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros((n, 4), np.uint8), np.zeros(n, np.uint8)
+        order, occluded, counts = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(2, np.uint32)
+        self._ck(self.lib.terra_tiles_reflection_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, C.byref(view), C.byref(args), C.addressof(stats) if n else None, ptr(mn), ptr(tr),
+                                                      ptr(tz), ptr(fl), ptr(os_), status.ctypes.data, dist.ctypes.data, lod.ctypes.data, crack.ctypes.data, order.ctypes.data,
+                                                      occluded.ctypes.data, counts.ctypes.data, None, reflect.ctypes.data))
+        return status, dist, lod, crack, order[:counts[0]], occluded[:counts[1]], counts, os_, reflect
+
+    def tiles_water_view(self, tile_xy, stats, view, args, trmax=None, tile_zmax=None, flags=None, status=None, dxoff=0, dyoff=0):
+        """is_water_visible() and draw_water_cap's edge tests for every tile: status [n] bytes (optional) is a pass-0 tiles_terrain_view's.
+        -> (water_list uint32 [counts[0]], cap_mask uint8 [n] or None, counts uint32 [2]; counts[1] is 0 without status)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt).reshape(n)  # noqa: E731
+        tr, tz, fl, su = opt(trmax, np.float32), opt(tile_zmax, np.float32), opt(flags, np.uint8), opt(status, np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        wl, counts = np.zeros(n, np.uint32), np.zeros(2, np.uint32)
+        cm = None if su is None else np.zeros(n, np.uint8)
+        self._ck(self.lib.terra_tiles_water_view(self.ctx, txy.ctypes.data, n, dxoff, dyoff, C.byref(view), C.byref(args), C.addressof(stats) if n else None, ptr(tr), ptr(tz), ptr(fl),
+                                                 ptr(su), wl.ctypes.data, ptr(cm), counts.ctypes.data))
+        return wl[:counts[0]], cm, counts
+
     def tiles_tree_view(self, tile_xy, stats, view, args, pine, pine_counts, skip=None, trmax=None, trunk_override=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0, fill=0):
         """tile_t::draw_pine_trees for every tile: pine TREE_PLACE_DTYPE [n, cap] with pine_counts [n]; stats TileStats * n; skip [n] bytes, trmax [n] float32,
         trunk_override TRUNK_OVERRIDE_DTYPE [n, cap], all optional.  The [n, cap] outputs start filled with the byte `fill`; entries past the counts keep it.
@@ -1459,6 +1512,22 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_terrain_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, min_normal_z_ptr, trmax_ptr,
                                                        tile_zmax_ptr, flags_ptr, occl_state_ptr, status_ptr, dist_ptr, lod_ptr, crack_ptr, draw_order_ptr, occluded_ptr, counts_ptr, not_drawn_ptr))
+
+    def tiles_reflection_view_dev(self, tile_xy, view, args, stats_ptr, status_ptr, dist_ptr, lod_ptr, crack_ptr, draw_order_ptr, occluded_ptr, counts_ptr, min_normal_z_ptr=None,
+                                  trmax_ptr=None, tile_zmax_ptr=None, flags_ptr=None, occl_state_ptr=None, not_drawn_ptr=None, reflect_ptr=None, dxoff=0, dyoff=0):
+        """the terrain draw list of reflection pass 1 of a device-resident batch: tiles_terrain_view_dev's arrays, args a ReflectionViewArgs, reflect_ptr [n] bytes or None.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_reflection_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, min_normal_z_ptr, trmax_ptr,
+                                                          tile_zmax_ptr, flags_ptr, occl_state_ptr, status_ptr, dist_ptr, lod_ptr, crack_ptr, draw_order_ptr, occluded_ptr, counts_ptr,
+                                                          not_drawn_ptr, reflect_ptr))
+
+    def tiles_water_view_dev(self, tile_xy, view, args, stats_ptr, water_list_ptr, counts_ptr, status_ptr=None, cap_mask_ptr=None, trmax_ptr=None, tile_zmax_ptr=None, flags_ptr=None,
+                             dxoff=0, dyoff=0):
+        """water quads and water caps of a device-resident batch: water_list_ptr [n] uint32, counts_ptr [2] uint32; status_ptr (a pass-0 terrain view's) and cap_mask_ptr [n] bytes,
+        both or neither.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_water_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, trmax_ptr, tile_zmax_ptr, flags_ptr,
+                                                     status_ptr, water_list_ptr, cap_mask_ptr, counts_ptr))
 
     def tiles_tree_view_dev(self, tile_xy, view, args, stats_ptr, pine_ptr, pine_counts_ptr, capacity, tile_out_ptr, all_bcube_ptr, pine_insts_ptr, palm_insts_ptr, inst_counts_ptr,
                             leaf_list_ptr, leaf_counts_ptr, trunk_ptr, skip_ptr=None, trmax_ptr=None, trunk_override_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):

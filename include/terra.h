@@ -847,8 +847,8 @@ int  terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
  * terra_view_behind_sphere_mult restates src/visibility.cpp:83 with the C library's tanf and the statement's own float / double mix (angle and aspect as for
  * terra_make_view; TERRA_ERR_ARG for a NULL out).  water_enabled: is_water_enabled(); water_plane_z is the scene's.  occluder_zmin: the global zmin that
  * occluder_cubes_t reads (:2840) -- an engine passes its zmin (terra_get_state's zmin for a generated scene).  check_occlusion: the condition of :2857,
- * (display_mode & 0x08) && (display_mode & 0x01) && check_tt_mesh_occlusion.  reflection_pass: 0, 2 or 3; pass 1 needs can_have_reflection (:2869), which stays
- * with the engine, and is refused.
+ * (display_mode & 0x08) && (display_mode & 0x01) && check_tt_mesh_occlusion.  reflection_pass: 0, 2 or 3; pass 1 needs can_have_reflection (:2869): it is
+ * terra_tiles_reflection_view's, and is refused here.
  * Inputs.  tile_xy is on the host; a tile may appear once (the neighbour look-up is the [n][9] table of terra_tiles_tree_ao_shadows).  dxoff / dyoff = xoff - xoff2 /
  * yoff - yoff2 as for the grass view.  Per-tile arrays: stats [n] (sub_zmin, sub_zmax, mzmin, mzmax and radius are read); min_normal_z [n] (optional; NULL = 0,
  * "normals not yet calculated"); trmax [n] (optional; NULL = 0; terra_tiles_tree_ao_shadows writes it); tile_zmax [n] (optional; the engine's get_tile_zmax(),
@@ -870,8 +870,8 @@ int  terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
  * where the status is not 5, else 0 -- the skip bytes of terra_tiles_grass_view, so that a frame's two view calls chain on the device.
  * One deviation: the reference sorts pair<float, tile_t *>, so equal distances fall back on pointer values; here equal distances order by batch index (a camera
  * over a tile centre makes such ties common).
- * With the engine stay the shaders, the binds, inside_city == 2, the texture-ready test, the building occluders (:2855, :2870), can_have_reflection and the water
- * caps.
+ * With the engine stay the shaders, the binds, inside_city == 2, the texture-ready test and the building occluders (:2855, :2870).  Reflection pass 1 with
+ * can_have_reflection is terra_tiles_reflection_view, the water quads and the water caps are terra_tiles_water_view (below).
  * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or of the args; reflection_pass 1, negative or above 3; an unsupported S; a NULL required
  * pointer (view, args; tile_xy, stats and every output when n > 0); a misaligned pointer (4 bytes: stats, min_normal_z, trmax, tile_zmax, dist, draw_order,
  * occluded, counts); a tile that appears twice.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.  The device form only
@@ -895,6 +895,67 @@ int  terra_tiles_terrain_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
                               const terra_tile_stats *h_stats, const float *h_min_normal_z, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags,
                               uint8_t *h_occl_state, uint8_t *h_status, float *h_dist, uint8_t *h_lod, uint8_t *h_crack, uint32_t *h_draw_order, uint32_t *h_occluded,
                               uint32_t *h_counts, uint8_t *h_not_drawn);
+
+/* ---- the terrain draw list of reflection pass 1 (every supported tile size S): tile_draw_t::draw(1) (src/tiled_mesh.cpp:2844-2915) -- the loop of
+ * terra_tiles_terrain_view with the filter of :2869, tile_draw_t::can_have_reflection and can_have_reflection_recur (:2630-2683), and get_lod_level(1) (:1910-1932:
+ * min_normal_z > 0.1 starts at LOD 1, the threshold is 1.8), bit for bit.  It is the pass that every frame with water draws first; the tree, scenery and deciduous
+ * views take its not_drawn bytes as they take the main pass's.
+ * Inputs: those of terra_tiles_terrain_view with the same meaning; of stats, wx1 .. wy2 (get_water_bcube(), src/tiled_mesh.h:253-256) are read as well.  trmax must
+ * not be negative.  terra_reflection_view_args: a terra_terrain_view_args whose reflection_pass is 1 and whose occluder_zmin doubles as the global zmin of :2634, and
+ * zmax, the global zmax of :2635.
+ * A candidate -- within DRAW_DIST_TILES, visible, not occluded earlier this frame -- is dropped at :2869 unless can_have_reflection holds: 0 with water disabled and
+ * for an all_water() tile, 1 for a has_water() tile, else the walk of can_have_reflection_recur from the tile towards the camera through its neighbours in the batch:
+ * a neighbour must be present (not absent by flag) and is_visible(), is entered through check_line_clip(camera, corners[dim], its box widened to zmin .. zmax), and
+ * ends the walk with 1 where it has water, was not last occluded, its water box is cube_visible and the slope comparison of :2643-2644 holds (the float division may
+ * give inf or NaN; the comparison does what IEEE says).  The walk is pure reachability, and vis_ref_call never fires.  last_occluded of a tile met on the walk is
+ * what this same loop wrote where the tile came earlier in the batch and was tested, else the incoming occl_state: batch order stands for the loop's map order.
+ * Outputs: those of terra_tiles_terrain_view, and: status gains TERRA_TVIEW_NO_REFLECTION = 6 for a tile dropped at :2869 -- it is in neither list, its crack bytes
+ * are 255, its not_drawn byte is 1 and its occl_state is left alone (no set_last_occluded).  lod and crack follow get_lod_level(1).  reflect [n] bytes (optional): how
+ * :2869 was decided, 0 not asked (the tile left earlier or is absent), 1 all_water or water disabled, 2 the walk found nothing, 3 has_water, 4 the walk found water.
+ * Deviations: equal distances order by batch index, as documented above; an absent tile is no neighbour for the walk, as it is none for the cracks.
+ * TERRA_ERR_ARG, with nothing written: as for terra_tiles_terrain_view, and a reflection_pass other than 1, a non-finite zmax, a batch whose tile positions span a
+ * bounding box more than 2048 wide or of more than 2^18 positions (the walk's visited bits and work list are in LDS).  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.
+ * The device form only enqueues; tile_xy is a host array in both forms.  Scratch comes from the context's arena. */
+typedef struct terra_reflection_view_args {
+	terra_terrain_view_args tv; /* reflection_pass must be 1; occluder_zmin is also the global zmin of :2634 */
+	float zmax;                 /* the global zmax of :2635 */
+} terra_reflection_view_args;
+enum {TERRA_TVIEW_NO_REFLECTION = 6};
+enum {TERRA_REFLECT_NOT_ASKED = 0, TERRA_REFLECT_NO_WATER = 1, TERRA_REFLECT_WALK_NOTHING = 2, TERRA_REFLECT_HAS_WATER = 3, TERRA_REFLECT_WALK_FOUND = 4};
+int  terra_tiles_reflection_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view,
+                                     const terra_reflection_view_args *args, const terra_tile_stats *d_stats, const float *d_min_normal_z, const float *d_trmax,
+                                     const float *d_tile_zmax, const uint8_t *d_flags, uint8_t *d_occl_state, uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack,
+                                     uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn, uint8_t *d_reflect);
+int  terra_tiles_reflection_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view,
+                                 const terra_reflection_view_args *args, const terra_tile_stats *h_stats, const float *h_min_normal_z, const float *h_trmax,
+                                 const float *h_tile_zmax, const uint8_t *h_flags, uint8_t *h_occl_state, uint8_t *h_status, float *h_dist, uint8_t *h_lod, uint8_t *h_crack,
+                                 uint32_t *h_draw_order, uint32_t *h_occluded, uint32_t *h_counts, uint8_t *h_not_drawn, uint8_t *h_reflect);
+
+/* ---- water quads and water caps of a tile batch (every supported tile size S): which tiles tile_draw_t::draw_water (src/tiled_mesh.cpp:3075) draws a quad of the
+ * water plane for -- tile_t::is_water_visible (:2131-2133): has_water() && rel_dist_to_camera_xy_lt(DRAW_DIST_TILES) && is_visible(); is_distant is never set --
+ * and which of a tile's four edges tile_t::draw_water_cap (:2093-2128) closes the water volume at.
+ * Inputs: tile_xy, dxoff / dyoff, view, stats, trmax, tile_zmax and flags (bit 0, absent) as for terra_tiles_terrain_view; terra_water_view_args with
+ * behind_sphere_mult and water_enabled (is_water_enabled(): it widens is_visible()'s sphere and gates the caps).  status [n] bytes (optional, on the device in the
+ * device form): the status output of a pass-0 terra_tiles_terrain_view on the same batch and camera.
+ * Outputs: water_list [n] words, its first counts[0] entries the batch indices of the present tiles with is_water_visible(), in batch order; entries past the count
+ * are not written.  cap_mask [n] bytes and counts[1], produced only with status: bit 2*dim + dir of a tile's byte is set where draw_water_cap emits that edge's quad
+ * -- unless the neighbour exists (in the batch, not absent) and rel_dist_to_camera_xy_lt(DRAW_DIST_TILES), !has_water() or !is_visible() holds for it (:2108-2112).
+ * The byte is 0 unless water is enabled and the status is DRAWN and the tile has_water() (draw_near_water, :2046, :2078), or the status is OCCLUDED (occluded_tiles,
+ * :2957-2959; not OCCLUDED_BEFORE).  counts[1] is the number of non-zero bytes.  status and cap_mask are both NULL or both given.
+ * With the engine stay ztop (water_plane_z - (draw_distant_water() ? 0.1 : 0.0), one value per call), the quads' vertices and the GL calls.
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or of the args; an unsupported S; a NULL required pointer (view, args; tile_xy, stats,
+ * water_list, counts when n > 0); status without cap_mask or the reverse; a misaligned pointer (4 bytes: stats, trmax, tile_zmax, water_list, counts); a tile that
+ * appears twice.  TERRA_ERR_STATE before terra_init_scene.  n == 0 does nothing once the checks have passed.  The device form only enqueues. */
+typedef struct terra_water_view_args {
+	float behind_sphere_mult;  /* pos_dir_up::behind_sphere_mult */
+	int32_t water_enabled;     /* is_water_enabled() */
+} terra_water_view_args;
+int  terra_tiles_water_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_water_view_args *args,
+                                const terra_tile_stats *d_stats, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags, const uint8_t *d_status,
+                                uint32_t *d_water_list, uint8_t *d_cap_mask, uint32_t *d_counts);
+int  terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_water_view_args *args,
+                            const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, const uint8_t *h_status,
+                            uint32_t *h_water_list, uint8_t *h_cap_mask, uint32_t *h_counts);
 
 /* ---- tree AO shadows of a tile batch from the placement records (every supported tile size S): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828), the step
  * between the two placements above and terra_tiles_shadow_texture / terra_tiles_tree_weights.  One call goes from the records as they lie in device memory to the

@@ -354,6 +354,29 @@ inline void tile_draw_lists(tile_batch_dev_t const &b, terra_view const &camera_
 	check(terra_tiles_terrain_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &args, b.d_stats, st.d_min_normal_z, st.d_trmax, st.d_tile_zmax, st.d_flags,
 		st.d_last_occluded, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn), "tile_draw_t::draw");
 }
+// tile_draw_t::draw(1): the same lists for the water plane's reflection pass, with can_have_reflection (src/tiled_mesh.cpp:2630-2683, :2869) and get_lod_level(1).
+// A tile dropped at :2869 has status TERRA_TVIEW_NO_REFLECTION; d_reflect (or null) says how :2869 was decided.  zmin / zmax: the globals of :2634-2635
+inline terra_reflection_view_args reflection_view_args_of(float behind_sphere_mult, float zmin, float zmax, bool water_enabled, bool check_occlusion) {
+	terra_reflection_view_args const a = {terrain_view_args_of(behind_sphere_mult, zmin, water_enabled, check_occlusion, 1), zmax};
+	return a;
+}
+inline void tile_draw_lists_reflection(tile_batch_dev_t const &b, terra_view const &camera_pdu, terra_reflection_view_args const &args, tile_draw_state_dev_t const &st,
+	unsigned char *d_status, float *d_dist, unsigned char *d_lod, unsigned char *d_crack, unsigned *d_draw_order, unsigned *d_occluded, unsigned *d_counts,
+	unsigned char *d_not_drawn = nullptr, unsigned char *d_reflect = nullptr)
+{
+	check(terra_tiles_reflection_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &args, b.d_stats, st.d_min_normal_z, st.d_trmax, st.d_tile_zmax, st.d_flags,
+		st.d_last_occluded, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_reflect), "tile_draw_t::draw(1)");
+}
+// tile_draw_t::draw_water's per-tile test (tile_t::is_water_visible, :2131-2133) and tile_t::draw_water_cap's edge tests (:2102-2119): d_water_list's first
+// d_counts[0] entries are the tiles whose quad is drawn, in batch order; with d_status (a pass-0 tile_draw_lists' on the same batch and camera) d_cap_mask[t] has bit
+// 2*dim + dir set where the cap's quad of that edge is emitted, and d_counts[1] counts the tiles with any.  ztop, the vertices and the GL calls stay with the engine
+inline void tile_water_lists(tile_batch_dev_t const &b, terra_view const &camera_pdu, float behind_sphere_mult, bool water_enabled, tile_draw_state_dev_t const &st,
+	unsigned char const *d_status, unsigned *d_water_list, unsigned char *d_cap_mask, unsigned *d_counts)
+{
+	terra_water_view_args const a = {behind_sphere_mult, water_enabled ? 1 : 0};
+	check(terra_tiles_water_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &a, b.d_stats, st.d_trmax, st.d_tile_zmax, st.d_flags, d_status, d_water_list,
+		d_cap_mask, d_counts), "tile_t::draw_water / draw_water_cap");
+}
 // tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:820-828) for every tile of the batch in batch order, from the records tiles_gen_trees / tiles_gen_decid_trees left
 // on the device: small_tree::get_radius / get_ao_radius and tree::get_ao_radius per record, apply_ao_shadows_for_trees' own loop, pulls and pushes, add_tree_ao_shadow's
 // texel loop.  xoff2 / yoff2: what the placements ran with (ptree_off / dtree_off).  d_sphere_radius [n][decid_capacity] (tdata().sphere_radius per record) or
