@@ -1050,6 +1050,70 @@ int terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 		if (h_status) {ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_cloud_params) == sizeof(terra::cloud_params_pod_t) && sizeof(terra_cloud_params) == 12, "terra_cloud_params layout");
+static_assert(sizeof(terra_cloud_step) == sizeof(terra::cloud_step_pod_t) && sizeof(terra_cloud_step) == 20, "terra_cloud_step layout");
+static_assert(sizeof(terra_cloud) == sizeof(terra::cloud_pod_t) && sizeof(terra_cloud) == 32, "terra_cloud layout");
+static_assert(sizeof(terra_cloud_tile) == sizeof(terra::cloud_tile_pod_t) && sizeof(terra_cloud_tile) == 88, "terra_cloud_tile layout");
+static_assert(sizeof(terra_cloud_view_args) == sizeof(terra::cloud_view_args_pod_t) && sizeof(terra_cloud_view_args) == 20, "terra_cloud_view_args layout");
+static_assert(sizeof(terra_cloud_inst) == sizeof(terra::cloud_inst_pod_t) && sizeof(terra_cloud_inst) == 24, "terra_cloud_inst layout");
+int terra_set_cloud_params(terra_ctx *ctx, const terra_cloud_params *params) {
+	TERRA_CHECK_CTX if (!params) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::cloud_params_pod_t p; memcpy(&p, params, sizeof(p));
+	TERRA_TRY ctx->eng.set_cloud_params(p); TERRA_CATCH
+}
+int terra_get_cloud_params(terra_ctx *ctx, terra_cloud_params *out) {
+	TERRA_CHECK_CTX if (!out) return terra::fail(TERRA_ERR_ARG, "null argument");
+	memcpy(out, &ctx->eng.cp, sizeof(*out)); return TERRA_OK;
+}
+int terra_tiles_update_clouds_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_cloud_step *step, terra_cloud_tile *d_state, terra_cloud *d_clouds,
+                                  uint32_t capacity, uint32_t *d_total) {
+	TERRA_CHECK_CTX if (!step) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::cloud_step_pod_t s; memcpy(&s, step, sizeof(s));
+	TERRA_TRY ctx->eng.tiles_update_clouds_dev(tile_xy, n, s, (terra::cloud_tile_pod_t *)d_state, (terra::cloud_pod_t *)d_clouds, capacity, d_total); TERRA_CATCH
+}
+int terra_tiles_update_clouds(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_cloud_step *step, terra_cloud_tile *h_state, terra_cloud *h_clouds,
+                              uint32_t capacity, uint32_t *h_total) {
+	TERRA_CHECK_CTX if (!step) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::cloud_step_pod_t s; memcpy(&s, step, sizeof(s));
+	TERRA_TRY
+		ctx->eng.cloud_update_check(s, capacity); // the scene, the tile size, the step and the capacity: before anything is staged
+		if (n == 0) {if (h_total) {*h_total = 0u;} return TERRA_OK;}
+		if (!tile_xy || !h_state || (capacity && !h_clouds)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		terra_stage st(ctx->eng);
+		int const ss = st.inout(h_state, (size_t)n*sizeof(terra_cloud_tile)), cl = st.inout(h_clouds, (size_t)n*capacity*sizeof(terra_cloud), capacity != 0), to = st.opt_out(h_total, 4);
+		st.begin();
+		ctx->eng.tiles_update_clouds_dev(tile_xy, n, s, st.dev<terra::cloud_tile_pod_t>(ss), st.dev<terra::cloud_pod_t>(cl), capacity, st.dev<uint32_t>(to));
+		st.end();
+	TERRA_CATCH
+}
+int terra_tiles_cloud_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_view *view, const terra_cloud_view_args *args, const terra_tile_stats *d_stats,
+                               const terra_cloud_tile *d_state, const terra_cloud *d_clouds, uint32_t capacity, uint8_t *d_stage, terra_cloud_inst *d_list, uint32_t *d_list_count) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::cloud_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY ctx->eng.tiles_cloud_view_dev(tile_xy, n, v, a, d_stats, (terra::cloud_tile_pod_t const *)d_state, (terra::cloud_pod_t const *)d_clouds, capacity, d_stage,
+		(terra::cloud_inst_pod_t *)d_list, d_list_count); TERRA_CATCH
+}
+int terra_tiles_cloud_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_view *view, const terra_cloud_view_args *args, const terra_tile_stats *h_stats,
+                           const terra_cloud_tile *h_state, const terra_cloud *h_clouds, uint32_t capacity, uint8_t *h_stage, terra_cloud_inst *h_list, uint32_t *h_list_count) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::cloud_view_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.cloud_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
+		if (n == 0) {if (h_list_count) {*h_list_count = 0u;} return TERRA_OK;}
+		size_t const nrec = (size_t)n*capacity;
+		if (!tile_xy || !h_stats || !h_state || !h_list_count || (nrec && (!h_clouds || !h_stage || !h_list))) return terra::fail(TERRA_ERR_ARG, "null argument");
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), ss = st.in(h_state, (size_t)n*sizeof(terra_cloud_tile)), cl = st.add(h_clouds, nullptr, nrec*sizeof(terra_cloud), nrec != 0),
+			sg = st.add(nullptr, h_stage, nrec, nrec != 0), li = st.add(nullptr, nullptr, nrec*sizeof(terra_cloud_inst), nrec != 0), lc = st.out(h_list_count, 4);
+		st.begin();
+		ctx->eng.tiles_cloud_view_dev(tile_xy, n, v, a, st.dev<terra_tile_stats>(s), st.dev<terra::cloud_tile_pod_t>(ss), st.dev<terra::cloud_pod_t>(cl), capacity, st.dev<uint8_t>(sg),
+			st.dev<terra::cloud_inst_pod_t>(li), st.dev<uint32_t>(lc));
+		st.end();
+		if (*h_list_count) {ctx->eng.be.d2h(h_list, st.dev<terra_cloud_inst>(li), (size_t)*h_list_count*sizeof(terra_cloud_inst));} // the entries past the count stay as the caller had them
+	TERRA_CATCH
+}
 static_assert(sizeof(terra_tree_view_args) == sizeof(terra::tree_view_args_pod_t) && sizeof(terra_tree_view_args) == 32, "terra_tree_view_args layout");
 static_assert(sizeof(terra_tree_view_tile) == sizeof(terra::tree_view_tile_pod_t) && sizeof(terra_tree_view_tile) == 32, "terra_tree_view_tile layout");
 static_assert(sizeof(terra_tree_view_inst) == sizeof(terra::tree_view_inst_pod_t) && sizeof(terra_tree_view_inst) == 16, "terra_tree_view_inst layout");

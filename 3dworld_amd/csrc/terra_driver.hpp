@@ -20,6 +20,7 @@
 #include "terra_grassview.hpp"
 #include "terra_terrainview.hpp"
 #include "terra_waterview.hpp"
+#include "terra_clouds.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
 #include "terra_treeview.hpp"
@@ -579,6 +580,7 @@ template<class BE> struct terra_engine {
 		if (d_noise_lut) be.free(d_noise_lut);
 		if (d_noise3_lut) be.free(d_noise3_lut);
 		if (d_sinTable) be.free(d_sinTable);
+		if (d_gauss) be.free(d_gauss);
 		hist_mirror.buf.drop(be); tree_insts_mirror.buf.drop(be);
 	}
 
@@ -731,6 +733,22 @@ template<class BE> struct terra_engine {
 		}
 		if (p.flower_density > FLOWER_DENSITY_MAX) throw std::invalid_argument("terra_set_flower_params: flower_density must be <= 1024 (a tile's count is 32 bits)");
 		fp = p;
+	}
+	// what tile_cloud_manager_t reads: clouds_per_tile, cloud_height_offset (src/3DWorld.cpp:111,116) and rgen_seed, the seed of gauss_rand_arr (gen_gauss_rand_arr); the
+	// table is rebuilt on the host when the seed changes and uploaded when a cloud pass next needs it
+	cloud_params_pod_t cp = {0.5f, 0.0f, 1};
+	std::vector<float> h_gauss; float *d_gauss = nullptr; bool gauss_dev_valid = false;
+	void set_cloud_params(cloud_params_pod_t const &p) {
+		if (!(p.clouds_per_tile >= 0.0f) || !std::isfinite(p.clouds_per_tile) || p.clouds_per_tile > 1000.0f) throw std::invalid_argument("terra_set_cloud_params: clouds_per_tile must be finite and 0 .. 1000");
+		if (!std::isfinite(p.cloud_height_offset)) throw std::invalid_argument("terra_set_cloud_params: cloud_height_offset must be finite");
+		if (p.rgen_seed != cp.rgen_seed) {h_gauss.clear(); gauss_dev_valid = false;}
+		cp = p;
+	}
+	float const *gauss_dev() {
+		if (h_gauss.empty()) {h_gauss.resize(CLOUD_GAUSS_SIZE); cloud_gauss_table(cp.rgen_seed, h_gauss.data()); gauss_dev_valid = false;}
+		if (!d_gauss) {d_gauss = (float *)be.alloc(CLOUD_GAUSS_SIZE*sizeof(float));}
+		if (!gauss_dev_valid) {be.h2d(d_gauss, h_gauss.data(), CLOUD_GAUSS_SIZE*sizeof(float)); gauss_dev_valid = true;}
+		return d_gauss;
 	}
 	// what the grass view reads beyond the flowers' grass_length and the landscape's num_rnd_grass_blocks: tt_grass_scale_factor (src/grass.cpp:1126 resets a value
 	// that is not > 0 to 1; here such a value is refused)
@@ -3349,6 +3367,108 @@ template<class BE> struct terra_engine {
 				nc += m ? 1u : 0u;
 			}
 			d_counts[1] = nc;
+		});
+	}
+
+	// ---- the clouds of a batch (terra_clouds.hpp): tile_t::update_tile_clouds (src/tiled_mesh.cpp:1822-1827) for every tile in batch order -- the first loop of
+	// tile_draw_t::draw_tile_clouds (:3490).  The checks that need no array (the host form runs them before it stages anything):
+	void cloud_update_check(cloud_step_pod_t const &s, uint32_t capacity) const {
+		require_scene();
+		require_tile_size();
+		if (!isfinite(s.wind[0]) || !isfinite(s.wind[1]) || !isfinite(s.wind[2]) || !isfinite(s.fticks)) throw std::invalid_argument("tiles_update_clouds: a member of the step is not finite");
+		if (capacity == 0 && cp.clouds_per_tile > 0.0f) throw std::invalid_argument("tiles_update_clouds: capacity is 0 and clouds_per_tile is not");
+	}
+	void tiles_update_clouds_dev(int32_t const *tile_xy, uint32_t n, cloud_step_pod_t const &s, cloud_tile_pod_t *d_state, cloud_pod_t *d_clouds, uint32_t capacity, uint32_t *d_total) {
+		cloud_update_check(s, capacity);
+		if (((uintptr_t)d_state & 7u) != 0 || ((((uintptr_t)d_clouds | (uintptr_t)d_total)) & 3u) != 0) {
+			throw std::invalid_argument("tiles_update_clouds: d_state must be 8-byte aligned, d_clouds and d_total 4-byte aligned");
+		}
+		if (n == 0) {if (d_total) {be.fill32(d_total, 0u, 1);} return;}
+		if (!tile_xy || !d_state || (capacity && !d_clouds)) throw std::invalid_argument("tiles_update_clouds: null argument");
+		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_update_clouds");
+		cloud_consts_t const c = cloud_consts(cp, s, gauss_dev(), cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), zmin, zmax, capacity);
+		// scratch: the coordinates, the neighbour table; for the kernels the marks of cloud_path and the marked tiles in batch order
+		int32_t *d_txy_w, *d_nbr_w; uint32_t *d_marks, *d_order;
+		stage_layout_t lay;
+		lay.add(d_txy_w, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_marks, ((size_t)n + 3)/4); lay.add(d_order, n);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy_w, tile_xy, (size_t)n*8);
+		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		int32_t const *d_txy = d_txy_w, *d_nbr = d_nbr_w;
+		if constexpr (BE::has_kernels) {
+			be.fill32(d_marks, 0u, ((size_t)n + 3)/4);
+			if (be.tile_update_clouds(c, d_txy, d_nbr, n, d_state, d_clouds, (uint8_t *)d_marks, d_order, d_total)) return;
+		}
+		// the simple form: one thread, the reference's loop over the batch in order
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {
+			uint32_t num = 0;
+			for (uint32_t t = 0; t < n; ++t) {cloud_update_tile(c, d_txy, d_nbr, d_state, d_clouds, t); num += d_state[t].count;}
+			if (d_total) {*d_total = num;}
+		});
+	}
+	// ---- the cloud draw list of a batch: tile_cloud_manager_t::get_draw_list for every tile (:1799-1820), the sort of :3493, tile_cloud_t::draw's decision (:1691-1697)
+	void cloud_view_check(view_pod_t const &view, cloud_view_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (using_hmap()) throw std::logic_error("tiles_cloud_view: a heightmap texture is set (the texture heights of get_exact_zval are not part of this call)");
+		if (!view_finite(view)) throw std::invalid_argument("tiles_cloud_view: a member of the view is not finite");
+		if (!isfinite(a.behind_sphere_mult) || !isfinite(a.xlate[0]) || !isfinite(a.xlate[1]) || !isfinite(a.xlate[2]) || !isfinite(a.max_dist)) {
+			throw std::invalid_argument("tiles_cloud_view: a member of the args is not finite");
+		}
+		if (!(a.max_dist > 0.0f)) throw std::invalid_argument("tiles_cloud_view: max_dist must be > 0");
+	}
+	void tiles_cloud_view_dev(int32_t const *tile_xy, uint32_t n, view_pod_t const &view, cloud_view_args_pod_t const &a, terra_tile_stats const *d_stats, cloud_tile_pod_t const *d_state,
+		cloud_pod_t const *d_clouds, uint32_t capacity, uint8_t *d_stage, cloud_inst_pod_t *d_list, uint32_t *d_list_count)
+	{
+		cloud_view_check(view, a);
+		if (((uintptr_t)d_state & 7u) != 0 || ((((uintptr_t)d_stats | (uintptr_t)d_clouds | (uintptr_t)d_list | (uintptr_t)d_list_count)) & 3u) != 0) {
+			throw std::invalid_argument("tiles_cloud_view: d_state must be 8-byte aligned, d_stats, d_clouds, d_list and d_list_count 4-byte aligned");
+		}
+		if (n == 0) {if (d_list_count) {be.fill32(d_list_count, 0u, 1);} return;}
+		size_t const nrec = (size_t)n*capacity;
+		if (!tile_xy || !d_stats || !d_state || !d_list_count || (nrec && (!d_clouds || !d_stage || !d_list))) throw std::invalid_argument("tiles_cloud_view: null argument");
+		if (nrec > 0x7FFFFFFFu) throw std::invalid_argument("tiles_cloud_view: n*capacity must be below 2^31");
+		tree_place_consts_t tc;
+		tree_scene_consts(0, 0, nullptr, tc); // no_xyoff = 1
+		tc.st = sinTable_dev();
+		cloud_view_consts_t c;
+		c.v = view; c.behind_sphere_mult = a.behind_sphere_mult; c.xlate[0] = a.xlate[0]; c.xlate[1] = a.xlate[1]; c.xlate[2] = a.xlate[2]; c.max_dist = a.max_dist;
+		c.water_plane_z = water_plane_z; c.capacity = capacity;
+		// scratch: get_exact_zval's constants (read from memory), the instances by slot and then in the order they were listed, their number
+		tree_place_consts_t *d_tc; cloud_inst_pod_t *d_by_slot, *d_found; uint32_t *d_cnt;
+		stage_layout_t lay;
+		lay.add(d_tc, 1); lay.add(d_by_slot, nrec); lay.add(d_found, nrec); lay.add(d_cnt, 4);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_tc, &tc, sizeof(tc));
+		be.fill32(d_cnt, 0u, 1);
+		tree_place_consts_t const *d_tcc = d_tc;
+		if (nrec == 0) {be.fill32(d_list_count, 0u, 1); return;}
+		if constexpr (BE::has_kernels) {if (be.tile_cloud_view(c, d_tcc, n, d_stats, d_state, d_clouds, d_stage, d_found, d_cnt, d_list, d_list_count)) return;}
+		// the simple form.  (1) a logical thread per record slot: get_draw_list's decision
+		be.launch(nrec, [=] TERRA_LAMBDA (size_t i) {
+			uint32_t const t = (uint32_t)(i/capacity), k = (uint32_t)(i%capacity);
+			uint32_t stg = CLV_NONE;
+			if (k < d_state[t].count) {
+				cloud_inst_pod_t o; o.tile = t; o.slot = k;
+				stg = cloud_view_record(c, d_clouds[i], d_stats[t].mzmin, d_stats[t].mzmax, [&](float x, float y) {return tree_exact_zval(*d_tcc, x, y);}, o);
+				if (stg == CLV_LISTED) {d_by_slot[i] = o;}
+			}
+			d_stage[i] = (uint8_t)stg;
+		});
+		// (2) one thread: to_draw_clouds as the loop of :3491 fills it, in batch order
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {
+			uint32_t cnt = 0;
+			for (size_t i = 0; i < nrec; ++i) {if (d_stage[i] == CLV_LISTED) {d_found[cnt++] = d_by_slot[i];}}
+			*d_cnt = cnt; *d_list_count = cnt;
+		});
+		// (3) the sort of :3493: an entry's place is its rank
+		be.launch(nrec, [=] TERRA_LAMBDA (size_t i) {
+			uint32_t const cnt = *d_cnt;
+			if (i >= cnt) return;
+			cloud_inst_pod_t const me = d_found[i];
+			uint32_t rank = 0;
+			for (uint32_t j = 0; j < cnt; ++j) {rank += cloud_inst_before(d_found[j], me) ? 1u : 0u;}
+			d_list[rank] = me;
 		});
 	}
 

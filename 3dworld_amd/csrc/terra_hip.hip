@@ -656,6 +656,29 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	{
 		return launch_if(true, terra::k_water_view, dim3(1), dim3(terra::TV_THREADS), c, in, tile_xy, nbr, n, status, wv, water_list, cap_mask, counts);
 	}
+	// the clouds' update: the marks of every record's path, the unmarked tiles in parallel, the marked tiles replayed in batch order by one workgroup
+	bool tile_update_clouds(terra::cloud_consts_t const &c, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, terra::cloud_tile_pod_t *state, terra::cloud_pod_t *clouds,
+		uint8_t *touched, uint32_t *order, uint32_t *total)
+	{
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const T = terra::CLD_THREADS, nb = (n + T - 1)/T;
+		run(terra::k_cloud_mark, dim3(nb), dim3(T), 0, c, nbr, n, (terra::cloud_tile_pod_t const *)state, (terra::cloud_pod_t const *)clouds, touched);
+		run(terra::k_cloud_tiles, dim3(nb), dim3(T), 0, c, tile_xy, nbr, n, (uint8_t const *)touched, state, clouds);
+		run(terra::k_cloud_tail, dim3(1), dim3(T), 0, c, tile_xy, nbr, n, (uint8_t const *)touched, order, state, clouds, total);
+		return true;
+	}
+	// the clouds' draw list: a lane per record slot, then every listed instance to its rank
+	bool tile_cloud_view(terra::cloud_view_consts_t const &c, terra::tree_place_consts_t const *consts, uint32_t n, terra_tile_stats const *stats, terra::cloud_tile_pod_t const *state,
+		terra::cloud_pod_t const *clouds, uint8_t *stage, terra::cloud_inst_pod_t *found, uint32_t *cnt, terra::cloud_inst_pod_t *list, uint32_t *list_count)
+	{
+		if (opt->simple_kernels) return false;
+		use();
+		uint32_t const T = terra::CLD_THREADS, nrec = n*c.capacity, nb = (nrec + T - 1)/T;
+		run(terra::k_cloud_view, dim3(nb), dim3(T), 0, c, consts, nrec, stats, state, clouds, stage, found, cnt);
+		run(terra::k_cloud_rank, dim3(nb), dim3(T), 0, (terra::cloud_inst_pod_t const *)found, (uint32_t const *)cnt, list, list_count);
+		return true;
+	}
 	// the pine and palm tree draw lists for a camera: one workgroup per tile (k_tree_view)
 	bool tile_tree_view(terra::tree_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra::tree_inst_pod_t const *insts, terra_tile_stats const *stats, uint8_t const *skip,
 		float const *trmax, terra::tree_place_pod_t const *pine, uint32_t const *counts, terra::trunk_override_pod_t const *ov, terra::tree_view_tile_pod_t *tile_out, float *bcube,

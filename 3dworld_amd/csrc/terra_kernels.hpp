@@ -2354,6 +2354,85 @@ __global__ __launch_bounds__(TV_THREADS) void k_water_view(terrain_view_consts_t
 	if (tid == 0) {counts[1] = nc;}
 }
 
+// ------------------------------------------------------------------ the clouds of a tile batch (tile_cloud_manager_t, src/tiled_mesh.cpp:1710-1827; terra_clouds.hpp).
+// The wind step is order dependent only where a cloud crosses from one tile to another, and a cloud's way through a call depends on nothing but the cloud:
+//  - k_cloud_mark: a lane per tile follows each of its records through the call (cloud_path) and marks every tile that sends or receives (a byte store of 1).
+//  - k_cloud_tiles: a lane per unmarked tile runs that tile's update_tile_clouds; it reads and writes the tile alone.
+//  - k_cloud_tail: one workgroup.  Its lanes list the marked tiles in batch order; after the barrier lane 0 replays them with the literal loop, which hands clouds
+//    only to marked tiles; after a second barrier the lanes add the other tiles' counts to the replayed tiles' counts at their turns.  Nothing waits for another workgroup: the three steps are three launches.
+// The draw list: k_cloud_view, a lane per record slot, leaves the stage byte and appends a listed instance to scratch in any order; k_cloud_rank puts an instance at
+// its rank by (dist_sq, tile, slot), a total order, so the list does not depend on the order of the appends.
+constexpr uint32_t CLD_THREADS = 256;
+static_assert(CLD_THREADS == TREEP_THREADS, "tp_emit and tp_block_rank rank TREEP_THREADS threads");
+__global__ __launch_bounds__(CLD_THREADS) void k_cloud_mark(cloud_consts_t c, int32_t const *__restrict__ nbr, uint32_t n, cloud_tile_pod_t const *__restrict__ state,
+	cloud_pod_t const *__restrict__ clouds, uint8_t *touched)
+{
+	uint32_t const t = blockIdx.x*CLD_THREADS + threadIdx.x;
+	if (t < n) {cloud_mark_tile(c, nbr, state, clouds, t, n, touched);}
+}
+__global__ __launch_bounds__(CLD_THREADS) void k_cloud_tiles(cloud_consts_t c, int32_t const *__restrict__ tile_xy, int32_t const *__restrict__ nbr, uint32_t n,
+	uint8_t const *__restrict__ touched, cloud_tile_pod_t *state, cloud_pod_t *clouds)
+{
+	uint32_t const t = blockIdx.x*CLD_THREADS + threadIdx.x;
+	if (t < n && !touched[t]) {cloud_update_tile_alone(c, tile_xy, nbr, state, clouds, t);}
+}
+__global__ __launch_bounds__(CLD_THREADS) void k_cloud_tail(cloud_consts_t c, int32_t const *__restrict__ tile_xy, int32_t const *__restrict__ nbr, uint32_t n,
+	uint8_t const *__restrict__ touched, uint32_t *order, cloud_tile_pod_t *state, cloud_pod_t *clouds, uint32_t *__restrict__ total)
+{
+	__shared__ uint32_t s_wave[CLD_THREADS/64], s_sum;
+	uint32_t const tid = threadIdx.x;
+	uint32_t nm = 0;
+	for (uint32_t base = 0; base < n; base += CLD_THREADS) {
+		uint32_t const t = base + tid;
+		tp_emit(t < n && touched[t] != 0, [&] {return t;}, order, n, nm, s_wave);
+	}
+	__syncthreads(); // order[] is complete
+	if (tid == 0) { // (a replayed tile's part of `num` is its count right after its turn: an earlier tile's list may still grow)
+		uint32_t num = 0;
+		for (uint32_t k = 0; k < nm; ++k) {uint32_t const t = order[k]; cloud_update_tile(c, tile_xy, nbr, state, clouds, t); num += state[t].count;}
+		s_sum = num;
+	}
+	__syncthreads();
+	if (!total) return;
+	uint32_t sum = 0;
+	for (uint32_t t = tid; t < n; t += CLD_THREADS) {sum += touched[t] ? 0u : state[t].count;}
+	atomicAdd(&s_sum, sum);
+	__syncthreads();
+	if (tid == 0) {*total = s_sum;}
+}
+__global__ __launch_bounds__(CLD_THREADS) void k_cloud_view(cloud_view_consts_t c, tree_place_consts_t const *__restrict__ consts, uint32_t nrec, terra_tile_stats const *__restrict__ stats,
+	cloud_tile_pod_t const *__restrict__ state, cloud_pod_t const *__restrict__ clouds, uint8_t *__restrict__ stage, cloud_inst_pod_t *__restrict__ found, uint32_t *cnt)
+{
+	uint32_t const i = blockIdx.x*CLD_THREADS + threadIdx.x;
+	if (i >= nrec) return;
+	uint32_t const t = i/c.capacity, k = i%c.capacity;
+	uint32_t stg = CLV_NONE;
+	if (k < state[t].count) {
+		cloud_inst_pod_t o; o.tile = t; o.slot = k;
+		stg = cloud_view_record(c, clouds[i], stats[t].mzmin, stats[t].mzmax, [&](float x, float y) {return tree_exact_zval(*consts, x, y);}, o);
+		if (stg == CLV_LISTED) {found[atomicAdd(cnt, 1u)] = o;} // (at most one per slot: below nrec)
+	}
+	stage[i] = (uint8_t)stg;
+}
+__global__ __launch_bounds__(CLD_THREADS) void k_cloud_rank(cloud_inst_pod_t const *__restrict__ found, uint32_t const *__restrict__ cnt_p, cloud_inst_pod_t *__restrict__ list,
+	uint32_t *__restrict__ list_count)
+{
+	__shared__ cloud_inst_pod_t s_in[CLD_THREADS];
+	uint32_t const cnt = *cnt_p, i = blockIdx.x*CLD_THREADS + threadIdx.x;
+	if (i == 0) {*list_count = cnt;}
+	if (blockIdx.x*CLD_THREADS >= cnt) return; // (uniform)
+	cloud_inst_pod_t me = found[(i < cnt) ? i : 0u];
+	uint32_t rank = 0;
+	for (uint32_t base = 0; base < cnt; base += CLD_THREADS) {
+		uint32_t const m = (cnt - base < CLD_THREADS) ? cnt - base : CLD_THREADS;
+		__syncthreads(); // the reads of the last round
+		if (threadIdx.x < m) {s_in[threadIdx.x] = found[base + threadIdx.x];}
+		__syncthreads();
+		for (uint32_t j = 0; j < m; ++j) {rank += cloud_inst_before(s_in[j], me) ? 1u : 0u;}
+	}
+	if (i < cnt) {list[rank] = me;}
+}
+
 // ------------------------------------------------------------------ the pine and palm tree draw lists of a tile batch for a camera (tile_t::draw_pine_trees,
 // src/tiled_mesh.cpp:1465-1526; terra_treeview.hpp).  k_tree_view: a workgroup of 256 lanes per tile; a skipped tile and one without records leave at once.
 //  1. A sweep over the tile's records, a lane a record: the record's size and trunk cylinder (tree_view_record), the counts of the valid, pine and palm records and

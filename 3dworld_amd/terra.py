@@ -184,6 +184,39 @@ def make_water_view_args(behind_sphere_mult=1.0, water_enabled=1):
     return WaterViewArgs(behind_sphere_mult, int(water_enabled))
 
 
+class CloudParams(C.Structure):  # terra_cloud_params
+    _fields_ = [("clouds_per_tile", C.c_float), ("cloud_height_offset", C.c_float), ("rgen_seed", C.c_int32)]
+
+
+def make_cloud_params(clouds_per_tile=0.5, cloud_height_offset=0.0, rgen_seed=1):
+    """terra_cloud_params with the reference's defaults"""
+    return CloudParams(clouds_per_tile, cloud_height_offset, int(rgen_seed))
+
+
+class CloudStep(C.Structure):  # terra_cloud_step
+    _fields_ = [("wind", C.c_float * 3), ("fticks", C.c_float), ("animate", C.c_int32)]
+
+
+def make_cloud_step(wind=(0.4, 0.2, 0.0), fticks=1.0, animate=1):
+    return CloudStep((C.c_float * 3)(*wind), fticks, int(animate))
+
+
+class CloudViewArgs(C.Structure):  # terra_cloud_view_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("xlate", C.c_float * 3), ("max_dist", C.c_float)]
+
+
+def make_cloud_view_args(behind_sphere_mult=1.0, xlate=(0.0, 0.0, 0.0), max_dist=1.0):
+    return CloudViewArgs(behind_sphere_mult, (C.c_float * 3)(*xlate), max_dist)
+
+
+CLOUD_DTYPE = np.dtype([("pos_hash", np.float32), ("pos", np.float32, 3), ("size", np.float32, 3), ("pad", np.uint32)])  # terra_cloud
+CLOUD_TILE_DTYPE = np.dtype([("generated", np.uint32), ("flags", np.uint32), ("count", np.uint32), ("num_clouds", np.uint32), ("cur_move_dist", np.float32), ("pad", np.uint32),
+                             ("rseed1", np.int64), ("rseed2", np.int64), ("bcube", np.float32, 6), ("range", np.float32, 6)])  # terra_cloud_tile
+CLOUD_INST_DTYPE = np.dtype([("tile", np.uint32), ("slot", np.uint32), ("dist_sq", np.float32), ("alpha", np.float32), ("draw_alpha", np.float32), ("drawn", np.uint32)])  # terra_cloud_inst
+CLD_OVERFLOW = 1
+CLV_NONE, CLV_VFC, CLV_BELOW_ZMIN, CLV_BELOW_WATER, CLV_BELOW_MESH, CLV_LISTED = range(6)  # the stage byte of tiles_cloud_view
+
+
 class TreeViewArgs(C.Structure):  # terra_tree_view_args
     _fields_ = [("behind_sphere_mult", C.c_float), ("zoom_f", C.c_float), ("tree_depth_scale", C.c_float), ("window_width", C.c_int32), ("shadow_pass", C.c_int32),
                 ("draw_trunks", C.c_int32), ("draw_near_leaves", C.c_int32), ("draw_far_leaves", C.c_int32)]
@@ -458,6 +491,12 @@ _PROTOS = {
     "terra_tiles_reflection_view": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 17),
     "terra_tiles_water_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 10),
     "terra_tiles_water_view": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 10),
+    "terra_set_cloud_params": (_i32, [_vp, _vp]),
+    "terra_get_cloud_params": (_i32, [_vp, _vp]),
+    "terra_tiles_update_clouds_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_update_clouds": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_cloud_view_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "terra_tiles_cloud_view": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_tree_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_tree_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_scenery_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
@@ -1145,6 +1184,39 @@ class Terra:
                                                  ptr(su), wl.ctypes.data, ptr(cm), counts.ctypes.data))
         return wl[:counts[0]], cm, counts
 
+    def set_cloud_params(self, cp):
+        self._ck(self.lib.terra_set_cloud_params(self.ctx, C.byref(cp)))
+
+    def get_cloud_params(self):
+        cp = CloudParams()
+        self._ck(self.lib.terra_get_cloud_params(self.ctx, C.byref(cp)))
+        return cp
+
+    def tiles_update_clouds(self, tile_xy, step, state, clouds):
+        """tile_t::update_tile_clouds for every tile in batch order: state CLOUD_TILE_DTYPE [n] and clouds CLOUD_DTYPE [n, capacity], both updated in place (zeroed
+        state: a tile that has just entered the batch).  -> total, the sum of the tiles' counts at their turns (the reference's num)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        assert state.dtype == CLOUD_TILE_DTYPE and state.shape == (n,) and state.flags["C_CONTIGUOUS"]
+        assert clouds.dtype == CLOUD_DTYPE and clouds.ndim == 2 and clouds.shape[0] == n and clouds.flags["C_CONTIGUOUS"]
+        total = np.zeros(1, np.uint32)
+        self._ck(self.lib.terra_tiles_update_clouds(self.ctx, txy.ctypes.data, n, C.byref(step), state.ctypes.data if n else None, clouds.ctypes.data if clouds.size else None,
+                                                    clouds.shape[1], total.ctypes.data))
+        return int(total[0])
+
+    def tiles_cloud_view(self, tile_xy, stats, view, args, state, clouds):
+        """get_draw_list for every tile, the sort and tile_cloud_t::draw's decision.  -> (stage uint8 [n, capacity], list CLOUD_INST_DTYPE [list_count], back to front)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        assert state.dtype == CLOUD_TILE_DTYPE and state.shape == (n,) and clouds.dtype == CLOUD_DTYPE and clouds.ndim == 2 and clouds.shape[0] == n
+        state, clouds = np.ascontiguousarray(state), np.ascontiguousarray(clouds)
+        cap = clouds.shape[1]
+        stage, lst, cnt = np.zeros((n, cap), np.uint8), np.zeros(n * cap, CLOUD_INST_DTYPE), np.zeros(1, np.uint32)
+        self._ck(self.lib.terra_tiles_cloud_view(self.ctx, txy.ctypes.data, n, C.byref(view), C.byref(args), C.addressof(stats) if n else None, state.ctypes.data if n else None,
+                                                 clouds.ctypes.data if clouds.size else None, cap, stage.ctypes.data if stage.size else None, lst.ctypes.data if lst.size else None,
+                                                 cnt.ctypes.data))
+        return stage, lst[:cnt[0]]
+
     def tiles_tree_view(self, tile_xy, stats, view, args, pine, pine_counts, skip=None, trmax=None, trunk_override=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0, fill=0):
         """tile_t::draw_pine_trees for every tile: pine TREE_PLACE_DTYPE [n, cap] with pine_counts [n]; stats TileStats * n; skip [n] bytes, trmax [n] float32,
         trunk_override TRUNK_OVERRIDE_DTYPE [n, cap], all optional.  The [n, cap] outputs start filled with the byte `fill`; entries past the counts keep it.
@@ -1528,6 +1600,17 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_water_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, trmax_ptr, tile_zmax_ptr, flags_ptr,
                                                      status_ptr, water_list_ptr, cap_mask_ptr, counts_ptr))
+
+    def tiles_update_clouds_dev(self, tile_xy, step, state_ptr, clouds_ptr, capacity, total_ptr=None):
+        """update_tile_clouds of a device-resident batch: state_ptr [n] terra_cloud_tile, clouds_ptr [n][capacity] terra_cloud, total_ptr one uint32 or None.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_update_clouds_dev(self.ctx, txy.ctypes.data, len(txy), C.byref(step), state_ptr, clouds_ptr, capacity, total_ptr))
+
+    def tiles_cloud_view_dev(self, tile_xy, view, args, stats_ptr, state_ptr, clouds_ptr, capacity, stage_ptr, list_ptr, list_count_ptr):
+        """the cloud draw list of a device-resident batch: stage_ptr [n][capacity] bytes, list_ptr [n*capacity] terra_cloud_inst, list_count_ptr one uint32.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_cloud_view_dev(self.ctx, txy.ctypes.data, len(txy), C.byref(view), C.byref(args), stats_ptr, state_ptr, clouds_ptr, capacity, stage_ptr, list_ptr,
+                                                     list_count_ptr))
 
     def tiles_tree_view_dev(self, tile_xy, view, args, stats_ptr, pine_ptr, pine_counts_ptr, capacity, tile_out_ptr, all_bcube_ptr, pine_insts_ptr, palm_insts_ptr, inst_counts_ptr,
                             leaf_list_ptr, leaf_counts_ptr, trunk_ptr, skip_ptr=None, trmax_ptr=None, trunk_override_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):

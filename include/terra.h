@@ -957,6 +957,100 @@ int  terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
                             const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, const uint8_t *h_status,
                             uint32_t *h_water_list, uint8_t *h_cap_mask, uint32_t *h_counts);
 
+/* ---- the clouds of a tile batch (every supported tile size S): tile_cloud_manager_t (src/tiled_mesh.cpp:1689-1827) as tile_draw_t::draw_tile_clouds (:3484-3508)
+ * drives it.  No call reads a zval: a tile is its tile_xy, S (x1 = x*S, x2 = x1 + S) and, for the view, its stats.
+ *
+ * terra_cloud_params: clouds_per_tile (config "clouds_per_tile", 0.5), cloud_height_offset (config "cloud_height_offset", 0) and rgen_seed (1), the seed of
+ * gen_gauss_rand_arr's table of 10002 floats (src/gen_object.cpp:363-374) that rand_gaussian reads; the table is built on the host when the seed changes and kept on
+ * the device.  zmin, zmax and water_plane_z are the context's own (terra_set_zmax_est, terra_set_water_plane_z).  TERRA_ERR_ARG: clouds_per_tile negative, not finite
+ * or above 1000; a cloud_height_offset that is not finite.
+ *
+ * terra_tiles_update_clouds: the first loop of draw_tile_clouds (:3490) -- for every tile in batch order update_tile_clouds() (:1822-1827): move_by_wind when
+ * step->animate, then gen.  (The reference walks an unordered_map; here its order is the caller's batch order.)
+ *   state [n] terra_cloud_tile, in/out: everything a tile_cloud_manager_t holds.  An all-zero struct is a freshly constructed manager: the caller zeroes the state
+ *     of a tile that enters the batch.  State and records hold no batch index: a tile's state and records may move to another batch slot between calls.
+ *   clouds [n][capacity] terra_cloud, in/out: a tile's records are its first state.count entries; what lies behind them means nothing.  The points of volume_part_cloud are
+ *     gen_pts(size), a function of size alone: they stay with the engine.
+ *   total: optional, one word: the `num` of :3489, the sum of every tile's count right after its own turn (a cloud handed to an earlier tile is not in it).
+ * Bit for bit the reference's: gen (once; seed (x1 + 123, y1 + 321); range; choose_num_clouds, which draws nothing when clouds_per_tile == 0; populate_clouds with
+ * the draws of gen_new_cloud in g++'s order: pos x, y, z, size z, y, x, the common factor), and move_by_wind in full: the early return, cur_move_dist and the re-draw
+ * of num_clouds past 2*get_tile_width(), repopulation of an empty tile on a windward edge of the batch (its clouds are not moved in that call), the per-cloud step,
+ * the removal loop (swap with the back, pop, look at the same index again) and the rebuild of bcube.  A cloud that leaves its tile's range is appended to the
+ * neighbour (dx, dy) of the batch; it is dropped when the batch has no such tile or that tile is not generated at that moment.  The batch is walked in order: a
+ * cloud handed to a later tile is moved again at that tile's turn, one handed to an earlier tile is not; an empty tile repopulates only if no earlier tile has
+ * handed it a cloud; a later tile that is not yet generated drops what it is handed and then generates.
+ * capacity: a push_back onto a list that holds `capacity` records makes all its draws and stores nothing (generation and immigration alike), sets the sticky bit
+ * TERRA_CLD_OVERFLOW in the tile's flags and still unites bcube with the cloud; count never exceeds capacity.  32 holds what generation alone makes at the default
+ * density (num_clouds <= clouds_per_tile + 4*max|table|, about clouds_per_tile + 16 at seed 1).
+ * TERRA_ERR_STATE before terra_init_scene.  TERRA_ERR_ARG, with nothing written: an unsupported S; a NULL step; NULL tile_xy or state when n > 0; NULL clouds when
+ * capacity > 0; capacity == 0 with clouds_per_tile > 0; a non-finite member of the step; a misaligned pointer (8 bytes: state; 4 bytes: clouds, total); a tile that
+ * appears twice.  n == 0 writes total = 0 and nothing else.  The device form only enqueues.
+ *
+ * terra_tiles_cloud_view: the rest of draw_tile_clouds -- get_draw_list for every tile (:1799-1820), the sort of :3493 and the per-instance decision and alpha of
+ * tile_cloud_t::draw (:1691-1697).  terra_cloud_view_args: behind_sphere_mult as for the terrain view, xlate = get_tiled_terrain_model_xlate(), max_dist =
+ * max(get_draw_tile_dist(), get_inf_terrain_fog_dist()).  stats: mzmin / mzmax are read.
+ *   stage [n][capacity] bytes: where a record left get_draw_list: TERRA_CLV_NONE (slot >= count), _VFC, _BELOW_ZMIN, _BELOW_WATER, _BELOW_MESH, _LISTED.
+ *   list: up to n*capacity terra_cloud_inst, list_count of them written: tile, slot, dist_sq = -p2p_dist_sq(camera, pos + xlate), alpha (1, or dist/start_dist under
+ *     zbot < mzmax + start_dist with dist = zbot - get_exact_zval(pos.x, pos.y, 1)), draw_alpha = alpha*(1 - val*val) with the val of :1696, and drawn = view_dist <
+ *     max_dist: an entry that is too distant stays in the list, as it stays in to_draw_clouds, with drawn = 0 and draw_alpha = 0.
+ * The exact height is get_exact_zval with no_xyoff = 1 (the scroll offsets taken as 0), evaluated only for the records that reach :1813; as for the placements the
+ * call returns TERRA_ERR_STATE while a heightmap texture is set.
+ * Order: ascending in dist_sq, that is back to front.  std::sort leaves equal keys in unspecified order; here equal keys go by (tile, slot) ascending.
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of the view or of the args; max_dist not > 0; an unsupported S; a NULL required pointer (view, args;
+ * tile_xy, stats, state, stage, list_count when n > 0; clouds, list when n*capacity > 0); a misaligned pointer (8 bytes: state; 4 bytes: stats, clouds, list,
+ * list_count).  n == 0 writes list_count = 0 and nothing else.
+ * With the engine stay the gates clouds_enabled() && atmosphere >= 0.5 and animate2, the points, get_cloud_color(), tfticks (pos_hash + 0.002*tfticks), the shader and
+ * the GL state. */
+typedef struct terra_cloud_params {
+	float clouds_per_tile;      /* 0.5 */
+	float cloud_height_offset;  /* 0 */
+	int32_t rgen_seed;          /* 1 */
+} terra_cloud_params;
+typedef struct terra_cloud_step {
+	float wind[3];              /* wind == zero_vector tests all three; z does not move a cloud */
+	float fticks;
+	int32_t animate;            /* animate2 */
+} terra_cloud_step;
+typedef struct terra_cloud {
+	float pos_hash;
+	float pos[3];
+	float size[3];
+	uint32_t pad;               /* written as 0 */
+} terra_cloud;
+enum {TERRA_CLD_OVERFLOW = 1};
+typedef struct terra_cloud_tile {
+	uint32_t generated;
+	uint32_t flags;             /* TERRA_CLD_* */
+	uint32_t count;             /* size() */
+	uint32_t num_clouds;
+	float cur_move_dist;
+	uint32_t pad;
+	int64_t rseed1, rseed2;     /* rgen */
+	float bcube[6];             /* x1, x2, y1, y2, z1, z2 */
+	float range[6];
+} terra_cloud_tile;
+typedef struct terra_cloud_view_args {
+	float behind_sphere_mult;
+	float xlate[3];
+	float max_dist;
+} terra_cloud_view_args;
+enum {TERRA_CLV_NONE = 0, TERRA_CLV_VFC = 1, TERRA_CLV_BELOW_ZMIN = 2, TERRA_CLV_BELOW_WATER = 3, TERRA_CLV_BELOW_MESH = 4, TERRA_CLV_LISTED = 5};
+typedef struct terra_cloud_inst {
+	uint32_t tile, slot;
+	float dist_sq, alpha, draw_alpha;
+	uint32_t drawn;
+} terra_cloud_inst;
+int  terra_set_cloud_params(terra_ctx *ctx, const terra_cloud_params *params);
+int  terra_get_cloud_params(terra_ctx *ctx, terra_cloud_params *out);
+int  terra_tiles_update_clouds_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_cloud_step *step, terra_cloud_tile *d_state, terra_cloud *d_clouds,
+                                   uint32_t capacity, uint32_t *d_total);
+int  terra_tiles_update_clouds(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_cloud_step *step, terra_cloud_tile *h_state, terra_cloud *h_clouds,
+                               uint32_t capacity, uint32_t *h_total);
+int  terra_tiles_cloud_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_view *view, const terra_cloud_view_args *args, const terra_tile_stats *d_stats,
+                                const terra_cloud_tile *d_state, const terra_cloud *d_clouds, uint32_t capacity, uint8_t *d_stage, terra_cloud_inst *d_list, uint32_t *d_list_count);
+int  terra_tiles_cloud_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_view *view, const terra_cloud_view_args *args, const terra_tile_stats *h_stats,
+                            const terra_cloud_tile *h_state, const terra_cloud *h_clouds, uint32_t capacity, uint8_t *h_stage, terra_cloud_inst *h_list, uint32_t *h_list_count);
+
 /* ---- tree AO shadows of a tile batch from the placement records (every supported tile size S): tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:740-828), the step
  * between the two placements above and terra_tiles_shadow_texture / terra_tiles_tree_weights.  One call goes from the records as they lie in device memory to the
  * tree maps of the batch, bit for bit; with it zvals -> stats -> both placements -> tree map -> shadow texture / tree weights is one stream of launches.

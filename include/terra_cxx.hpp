@@ -377,6 +377,28 @@ inline void tile_water_lists(tile_batch_dev_t const &b, terra_view const &camera
 	check(terra_tiles_water_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &a, b.d_stats, st.d_trmax, st.d_tile_zmax, st.d_flags, d_status, d_water_list,
 		d_cap_mask, d_counts), "tile_t::draw_water / draw_water_cap");
 }
+// tile_draw_t::draw_tile_clouds (src/tiled_mesh.cpp:3484-3508), first loop: tile_t::update_tile_clouds for every tile in batch order (b.tile_xy, b.n alone are read).
+// d_state [n] terra_cloud_tile -- zeroed for a tile that enters the batch -- and d_clouds [n][capacity] terra_cloud travel with their tile between batches.
+// clouds_per_tile, cloud_height_offset and rgen_seed: set_cloud_params.  d_total (or null): the `num` of :3489
+inline void set_cloud_params(float clouds_per_tile, float cloud_height_offset, int rgen_seed = 1) {
+	terra_cloud_params const p = {clouds_per_tile, cloud_height_offset, rgen_seed};
+	check(terra_set_cloud_params(default_ctx(), &p), "clouds_per_tile / cloud_height_offset");
+}
+inline void tile_clouds_update(tile_batch_dev_t const &b, float const wind[3], float fticks, bool animate2, terra_cloud_tile *d_state, terra_cloud *d_clouds, unsigned capacity,
+	unsigned *d_total = nullptr)
+{
+	terra_cloud_step const s = {{wind[0], wind[1], wind[2]}, fticks, animate2 ? 1 : 0};
+	check(terra_tiles_update_clouds_dev(default_ctx(), b.tile_xy, b.n, &s, d_state, d_clouds, capacity, d_total), "tile_t::update_tile_clouds");
+}
+// the rest of draw_tile_clouds: get_draw_list, the sort (back to front; equal keys by (tile, slot)) and tile_cloud_t::draw's decision and alpha per instance.
+// xlate: get_tiled_terrain_model_xlate(); max_dist: max(get_draw_tile_dist(), get_inf_terrain_fog_dist()).  The gates clouds_enabled() && atmosphere >= 0.5, the
+// points (gen_pts(size)), get_cloud_color(), tfticks, the shader and the GL state stay with the engine
+inline void tile_clouds_draw_list(tile_batch_dev_t const &b, terra_view const &camera_pdu, float behind_sphere_mult, float const xlate[3], float max_dist,
+	terra_cloud_tile const *d_state, terra_cloud const *d_clouds, unsigned capacity, unsigned char *d_stage, terra_cloud_inst *d_list, unsigned *d_list_count)
+{
+	terra_cloud_view_args const a = {behind_sphere_mult, {xlate[0], xlate[1], xlate[2]}, max_dist};
+	check(terra_tiles_cloud_view_dev(default_ctx(), b.tile_xy, b.n, &camera_pdu, &a, b.d_stats, d_state, d_clouds, capacity, d_stage, d_list, d_list_count), "tile_draw_t::draw_tile_clouds");
+}
 // tile_t::apply_tree_ao_shadows (src/tiled_mesh.cpp:820-828) for every tile of the batch in batch order, from the records tiles_gen_trees / tiles_gen_decid_trees left
 // on the device: small_tree::get_radius / get_ao_radius and tree::get_ao_radius per record, apply_ao_shadows_for_trees' own loop, pulls and pushes, add_tree_ao_shadow's
 // texel loop.  xoff2 / yoff2: what the placements ran with (ptree_off / dtree_off).  d_sphere_radius [n][decid_capacity] (tdata().sphere_radius per record) or
