@@ -1114,6 +1114,83 @@ int terra_tiles_cloud_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, c
 		if (*h_list_count) {ctx->eng.be.d2h(h_list, st.dev<terra_cloud_inst>(li), (size_t)*h_list_count*sizeof(terra_cloud_inst));} // the entries past the count stay as the caller had them
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_sphere_query) == sizeof(terra::sphere_query_pod_t) && sizeof(terra_sphere_query) == 24, "terra_sphere_query layout");
+static_assert(sizeof(terra_sphere_hit) == sizeof(terra::sphere_hit_pod_t) && sizeof(terra_sphere_hit) == 24, "terra_sphere_hit layout");
+static_assert(sizeof(terra_collide_in) == 168, "terra_collide_in layout");
+int terra_tiles_sphere_collide_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const terra_sphere_query *d_queries, uint32_t nq,
+                                   terra_sphere_hit *d_hits) {
+	TERRA_CHECK_CTX
+	TERRA_TRY ctx->eng.tiles_sphere_collide_dev(tile_xy, n, in, (terra::sphere_query_pod_t const *)d_queries, nq, (terra::sphere_hit_pod_t *)d_hits); TERRA_CATCH
+}
+// the device copies of a terra_collide_in of host pointers: declared on `st`, bound into `dev` after st.begin()
+struct terra_collide_stage {
+	int s[14];
+	terra_collide_stage(terra_stage &st, terra_collide_in const &a, uint32_t n, bool cube) {
+		size_t const np = (size_t)n*a.pine_capacity, nd = (size_t)n*a.decid_capacity, ns = (size_t)n*a.scenery_capacity;
+		bool const hp = !cube && a.pine && a.pine_counts && np, hd = a.decid && a.decid_counts && nd, hs = !cube && a.scenery && a.scenery_counts && ns;
+		s[0] = st.add(a.stats, nullptr, (size_t)n*sizeof(terra_tile_stats), !cube && a.stats && n);
+		s[1] = st.add(a.trmax, nullptr, (size_t)n*4, !cube && a.trmax && n); s[2] = st.add(a.tile_zmax, nullptr, (size_t)n*4, !cube && a.tile_zmax && n);
+		s[3] = st.add(a.flags, nullptr, n, !cube && a.flags && n);
+		s[4] = st.add(a.pine, nullptr, np*sizeof(terra_tree_place), hp); s[5] = st.add(a.pine_counts, nullptr, (size_t)n*4, hp);
+		s[6] = st.add(a.trunk_override, nullptr, np*sizeof(terra_trunk_override), hp && a.trunk_override);
+		s[7] = st.add(a.decid, nullptr, nd*sizeof(terra_decid_place), hd); s[8] = st.add(a.decid_counts, nullptr, (size_t)n*4, hd);
+		s[9] = st.add(a.scenery, nullptr, ns*sizeof(terra_scenery_place), hs); s[10] = st.add(a.scenery_counts, nullptr, (size_t)n*4, hs);
+		s[11] = st.add(a.radius_override, nullptr, ns*4, hs && a.radius_override);
+		s[12] = st.add(a.tree_data, nullptr, (size_t)a.num_tree_data*sizeof(terra_decid_tree_data), hd && a.tree_data);
+		s[13] = st.add(a.br_scale, nullptr, (size_t)a.num_tree_data*4, hd && a.br_scale);
+	}
+	terra_collide_in bind(terra_stage const &st, terra_collide_in const &a) const {
+		terra_collide_in d = a;
+		d.stats = st.dev<terra_tile_stats>(s[0]); d.trmax = st.dev<float>(s[1]); d.tile_zmax = st.dev<float>(s[2]); d.flags = st.dev<uint8_t>(s[3]);
+		d.pine = st.dev<terra_tree_place>(s[4]); d.pine_counts = st.dev<uint32_t>(s[5]); d.trunk_override = st.dev<terra_trunk_override>(s[6]);
+		d.decid = st.dev<terra_decid_place>(s[7]); d.decid_counts = st.dev<uint32_t>(s[8]);
+		d.scenery = st.dev<terra_scenery_place>(s[9]); d.scenery_counts = st.dev<uint32_t>(s[10]); d.radius_override = st.dev<float>(s[11]);
+		d.tree_data = st.dev<terra_decid_tree_data>(s[12]); d.br_scale = st.dev<float>(s[13]);
+		return d;
+	}
+};
+int terra_tiles_sphere_collide(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const terra_sphere_query *h_queries, uint32_t nq,
+                               terra_sphere_hit *h_hits) {
+	TERRA_CHECK_CTX
+	TERRA_TRY
+		ctx->eng.collide_check(in, false, "tiles_sphere_collide"); // the scene, the tile size and the members that are no arrays: before anything is staged
+		if (n && (!tile_xy || !in->stats)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if (nq && (!h_queries || !h_hits)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if ((uint64_t)n*in->pine_capacity > 0xFFFFFFFFull || (uint64_t)n*in->decid_capacity > 0xFFFFFFFFull || (uint64_t)n*in->scenery_capacity > 0xFFFFFFFFull) {
+			return terra::fail(TERRA_ERR_ARG, "tiles_sphere_collide: n*capacity must fit 32 bits");
+		}
+		terra_stage st(ctx->eng);
+		terra_collide_stage const cs(st, *in, n, false);
+		int const q = st.add(h_queries, nullptr, (size_t)nq*sizeof(terra_sphere_query), nq != 0), h = st.add(nullptr, h_hits, (size_t)nq*sizeof(terra_sphere_hit), nq != 0);
+		st.begin();
+		terra_collide_in const d = cs.bind(st, *in);
+		ctx->eng.tiles_sphere_collide_dev(tile_xy, n, &d, st.dev<terra::sphere_query_pod_t>(q), nq, st.dev<terra::sphere_hit_pod_t>(h));
+		st.end();
+	TERRA_CATCH
+}
+int terra_tiles_cube_int_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const float *d_cubes, const int32_t *d_cube_tile,
+                                   uint32_t nq, uint8_t *d_result, int32_t *d_tile_out) {
+	TERRA_CHECK_CTX
+	TERRA_TRY ctx->eng.tiles_cube_int_trees_dev(tile_xy, n, in, d_cubes, d_cube_tile, nq, d_result, d_tile_out); TERRA_CATCH
+}
+int terra_tiles_cube_int_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const float *h_cubes, const int32_t *h_cube_tile,
+                               uint32_t nq, uint8_t *h_result, int32_t *h_tile_out) {
+	TERRA_CHECK_CTX
+	TERRA_TRY
+		ctx->eng.collide_check(in, true, "tiles_cube_int_trees");
+		if (n && !tile_xy) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if (nq && (!h_cubes || !h_result)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if ((uint64_t)n*in->decid_capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_cube_int_trees: n*capacity must fit 32 bits");
+		terra_stage st(ctx->eng);
+		terra_collide_stage const cs(st, *in, n, true);
+		int const q = st.add(h_cubes, nullptr, (size_t)nq*24, nq != 0), qt = st.add(h_cube_tile, nullptr, (size_t)nq*4, nq != 0 && h_cube_tile),
+			r = st.add(nullptr, h_result, nq, nq != 0), to = st.add(nullptr, h_tile_out, (size_t)nq*4, nq != 0 && h_tile_out);
+		st.begin();
+		terra_collide_in const d = cs.bind(st, *in);
+		ctx->eng.tiles_cube_int_trees_dev(tile_xy, n, &d, st.dev<float>(q), st.dev<int32_t>(qt), nq, st.dev<uint8_t>(r), st.dev<int32_t>(to));
+		st.end();
+	TERRA_CATCH
+}
 static_assert(sizeof(terra_tree_view_args) == sizeof(terra::tree_view_args_pod_t) && sizeof(terra_tree_view_args) == 32, "terra_tree_view_args layout");
 static_assert(sizeof(terra_tree_view_tile) == sizeof(terra::tree_view_tile_pod_t) && sizeof(terra_tree_view_tile) == 32, "terra_tree_view_tile layout");
 static_assert(sizeof(terra_tree_view_inst) == sizeof(terra::tree_view_inst_pod_t) && sizeof(terra_tree_view_inst) == 16, "terra_tree_view_inst layout");

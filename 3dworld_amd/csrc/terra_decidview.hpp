@@ -73,9 +73,10 @@ TERRA_HD float inv_sqrt_ref(float x) {
 }
 
 // ---- a record with its table entry.  false: dropped (tree_id outside the table, or the entry is not GENERATED): not drawn, not in all_bcube
-TERRA_HD bool decid_view_valid(decid_view_consts_t const &c, decid_tree_data_pod_t const *data, decid_place_pod_t const &r) {
-	return r.tree_id >= 0 && (uint32_t)r.tree_id < c.num_data && (data[r.tree_id].flags & DCV_GENERATED) != 0;
+TERRA_HD bool decid_view_valid(uint32_t num_data, decid_tree_data_pod_t const *data, decid_place_pod_t const &r) {
+	return r.tree_id >= 0 && (uint32_t)r.tree_id < num_data && (data[r.tree_id].flags & DCV_GENERATED) != 0;
 }
+TERRA_HD bool decid_view_valid(decid_view_consts_t const &c, decid_tree_data_pod_t const *data, decid_place_pod_t const &r) {return decid_view_valid(c.num_data, data, r);}
 TERRA_HD bool decid_view_all_zeros(float const d[6]) {return d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f && d[3] == 0.0f && d[4] == 0.0f && d[5] == 0.0f;}
 // add_bounds_to_bcube's two boxes: branches_bcube + tree_center and leaves_bcube + tree_center (cube_t::operator+ adds the point to both bounds)
 TERRA_HD void decid_view_bounds(decid_tree_data_pod_t const &td, float const pos[3], float b[6], float l[6]) {

@@ -26,6 +26,7 @@
 #include "terra_treeview.hpp"
 #include "terra_decidview.hpp"
 #include "terra_sceneryview.hpp"
+#include "terra_collide.hpp"
 #include "terra_stage.hpp"
 #include "../../include/terra.h"
 #include <vector>
@@ -2367,32 +2368,32 @@ template<class BE> struct terra_engine {
 			d_updated[t] = u;
 		});
 	}
-	// the [n][9] neighbour table of a batch, (dy+1)*3 + dx+1 -> batch index or -1; a tile may appear once (the tree AO shadows and the terrain view read it)
-	static std::vector<int32_t> batch_neighbours(int32_t const *tile_xy, uint32_t n, char const *what) {
+	// the key table of a batch (terra_collide.hpp: batch_key_find searches it, on the host and on the device): an open-addressed table keyed by the tile's coordinates,
+	// at most half full -- the call only enqueues, and at 4096 tiles a tree of pairs would cost more than the kernels.  A tile may appear once
+	static std::vector<int32_t> batch_key_table(int32_t const *tile_xy, uint32_t n, char const *what, uint32_t &hbits) {
 		if (n > (1u << 30)) throw std::invalid_argument(std::string(what) + ": more than 2^30 tiles");
-		// (an open-addressed table keyed by the tile's coordinates: the call only enqueues, and at 4096 tiles a tree of pairs would cost more than the kernels)
-		uint32_t hbits = 4;
+		hbits = 4;
 		while ((1ull << hbits) < 2ull*n) {++hbits;}
 		uint32_t const hmask = (uint32_t)((1ull << hbits) - 1);
 		std::vector<int32_t> slots((size_t)hmask + 1, -1);
-		auto key_of = [](int32_t tx, int32_t ty) {return ((uint64_t)(uint32_t)tx << 32) | (uint32_t)ty;};
-		auto hash_of = [hbits](uint64_t k) {return (uint32_t)((k*0x9E3779B97F4A7C15ull) >> (64 - hbits));};
-		auto find = [&](int64_t tx, int64_t ty) -> int32_t { // the batch index of tile (tx, ty), -1: not in the batch
-			if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX) return -1;
-			uint64_t const k = key_of((int32_t)tx, (int32_t)ty);
-			for (uint32_t h = hash_of(k);; h = (h + 1) & hmask) {
-				int32_t const v = slots[h];
-				if (v < 0 || key_of(tile_xy[2*v], tile_xy[2*v+1]) == k) return v;
-			}
-		};
 		for (uint32_t t = 0; t < n; ++t) {
-			uint64_t const k = key_of(tile_xy[2*t], tile_xy[2*t+1]);
-			uint32_t h = hash_of(k);
+			uint64_t const k = batch_key(tile_xy[2*t], tile_xy[2*t+1]);
+			uint32_t h = batch_key_hash(k, hbits);
 			for (; slots[h] >= 0; h = (h + 1) & hmask) {
-				if (key_of(tile_xy[2*slots[h]], tile_xy[2*slots[h]+1]) == k) throw std::invalid_argument(std::string(what) + ": a tile appears twice in tile_xy");
+				if (batch_key(tile_xy[2*slots[h]], tile_xy[2*slots[h]+1]) == k) throw std::invalid_argument(std::string(what) + ": a tile appears twice in tile_xy");
 			}
 			slots[h] = (int32_t)t;
 		}
+		return slots;
+	}
+	// the [n][9] neighbour table of a batch, (dy+1)*3 + dx+1 -> batch index or -1; a tile may appear once (the tree AO shadows and the terrain view read it)
+	static std::vector<int32_t> batch_neighbours(int32_t const *tile_xy, uint32_t n, char const *what) {
+		uint32_t hbits;
+		std::vector<int32_t> const slots = batch_key_table(tile_xy, n, what, hbits);
+		auto find = [&](int64_t tx, int64_t ty) -> int32_t { // the batch index of tile (tx, ty), -1: not in the batch
+			if (tx < INT32_MIN || tx > INT32_MAX || ty < INT32_MIN || ty > INT32_MAX) return -1;
+			return batch_key_find(tile_xy, slots.data(), hbits, n, (int32_t)tx, (int32_t)ty);
+		};
 		std::vector<int32_t> nbr((size_t)n*9);
 		for (uint32_t t = 0; t < n; ++t) {
 			for (int k = 0; k < 9; ++k) {nbr[(size_t)t*9 + k] = find((int64_t)tile_xy[2*t] + (k%3 - 1), (int64_t)tile_xy[2*t+1] + (k/3 - 1));}
@@ -3469,6 +3470,111 @@ template<class BE> struct terra_engine {
 			uint32_t rank = 0;
 			for (uint32_t j = 0; j < cnt; ++j) {rank += cloud_inst_before(d_found[j], me) ? 1u : 0u;}
 			d_list[rank] = me;
+		});
+	}
+
+	// ---- sphere collisions and tree box tests against the containers of a batch (terra_collide.hpp): tile_draw_t::check_sphere_collision / tile_t::check_sphere_collision
+	// (src/tiled_mesh.cpp:3566-3569, 2146-2168) and tile_draw_t::check_cube_int_trees (:3576-3579), nq of them at once.
+	// The checks that need no array (the host forms run them before they stage anything); cube: only the deciduous members are looked at
+	void collide_check(terra_collide_in const *in, bool cube, char const *what) const {
+		require_scene();
+		require_tile_size();
+		if (!in) throw std::invalid_argument(std::string(what) + ": null argument");
+		bool const has_pine = !cube && in->pine && in->pine_counts && in->pine_capacity, has_decid = in->decid && in->decid_counts && in->decid_capacity;
+		if (!cube && !(isfinite(in->tree_depth_scale) && in->tree_depth_scale > 0.0f)) throw std::invalid_argument(std::string(what) + ": tree_depth_scale must be finite and > 0");
+		if (has_pine && tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
+			throw std::invalid_argument(std::string(what) + ": instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
+		}
+		if (has_decid && (!in->tree_data || !in->br_scale)) throw std::invalid_argument(std::string(what) + ": null argument (tree_data and br_scale go with the deciduous records)");
+		if (has_decid && (in->num_tree_data == 0 || in->num_tree_data != dp.num_shared_trees)) {
+			throw std::invalid_argument(std::string(what) + ": num_tree_data must be terra_decid_params.num_shared_trees and > 0");
+		}
+	}
+	// the constants and the device arrays of a call; uploads the coordinates and the key table of the batch into scratch
+	void collide_setup(int32_t const *tile_xy, uint32_t n, terra_collide_in const &a, bool cube, char const *what, collide_consts_t &c, collide_in_t &in) {
+		bool const has_pine = !cube && a.pine && a.pine_counts && a.pine_capacity, has_decid = a.decid && a.decid_counts && a.decid_capacity,
+			has_scen = !cube && a.scenery && a.scenery_counts && a.scenery_capacity;
+		if ((uint64_t)n*a.pine_capacity > 0xFFFFFFFFull || (uint64_t)n*a.decid_capacity > 0xFFFFFFFFull || (uint64_t)n*a.scenery_capacity > 0xFFFFFFFFull) {
+			throw std::invalid_argument(std::string(what) + ": n*capacity must fit 32 bits");
+		}
+		if (!tile_xy || (!cube && !a.stats)) throw std::invalid_argument(std::string(what) + ": null argument");
+		if ((((uintptr_t)a.stats | (uintptr_t)a.trmax | (uintptr_t)a.tile_zmax | (uintptr_t)a.pine | (uintptr_t)a.pine_counts | (uintptr_t)a.trunk_override | (uintptr_t)a.decid |
+		      (uintptr_t)a.decid_counts | (uintptr_t)a.scenery | (uintptr_t)a.scenery_counts | (uintptr_t)a.radius_override | (uintptr_t)a.tree_data | (uintptr_t)a.br_scale) & 3u) != 0) {
+			throw std::invalid_argument(std::string(what) + ": every array but flags must be 4-byte aligned");
+		}
+		uint32_t hbits;
+		std::vector<int32_t> const slots = batch_key_table(tile_xy, n, what, hbits);
+		tree_ao_consts_t ac;
+		ac.hs = tsp.tree_height_scale*tsp.sm_tree_scale; ac.pine_radius_scale = tsp.pine_tree_radius_scale; ac.tree_scale = tp.tree_scale;
+		ac.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
+		ac.dxv = DX_VAL; ac.dyv = DY_VAL; ac.offx = (float)add_wrap(a.dxoff, a.ptree_xoff2)*DX_VAL; ac.offy = (float)add_wrap(a.dyoff, a.ptree_yoff2)*DY_VAL; // ptree_off.get_xlate()
+		ac.S = (int)tile_size(); ac.instanced = tp.instanced ? 1 : 0; ac.num_insts = (uint32_t)tree_insts.size(); ac.num_shared = 0;
+		ac.pine_cap = a.pine_capacity; ac.decid_cap = 0; ac.list_cap = 0; ac.src_cap = a.pine_capacity;
+		view_pod_t v; memset(&v, 0, sizeof(v)); // (no camera: of the view constants only the scene, the offsets and the tree depth are read)
+		tree_view_args_pod_t const ta = {0.0f, 1.0f, cube ? 1.0f : a.tree_depth_scale, 1, 0, 0, 0, 0};
+		c.pv = tree_view_consts(v, ta, ac, cfg.scene_x, cfg.scene_y, a.dxoff, a.dyoff, a.pine_capacity);
+		c.doffx = (float)add_wrap(a.dxoff, a.dtree_xoff2)*DX_VAL; c.doffy = (float)add_wrap(a.dyoff, a.dtree_yoff2)*DY_VAL;       // dtree_off.get_xlate()
+		c.soffx = (float)add_wrap(a.dxoff, a.scenery_xoff2)*DX_VAL; c.soffy = (float)add_wrap(a.dyoff, a.scenery_yoff2)*DY_VAL;   // scenery_off.get_xlate()
+		c.lookup_ox = (float)a.dxoff*DX_VAL; c.lookup_oy = (float)a.dyoff*DY_VAL;
+		c.n = n; c.hbits = hbits; c.num_data = has_decid ? a.num_tree_data : 0u;
+		c.pine_cap = has_pine ? a.pine_capacity : 0u; c.decid_cap = has_decid ? a.decid_capacity : 0u; c.scen_cap = has_scen ? a.scenery_capacity : 0u;
+		int32_t *d_txy, *d_slots;
+		stage_layout_t lay;
+		lay.add(d_txy, (size_t)n*2); lay.add(d_slots, slots.size());
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		be.h2d_async(d_slots, slots.data(), slots.size()*sizeof(int32_t));
+		in.stats = a.stats; in.trmax = cube ? nullptr : a.trmax; in.tile_zmax = cube ? nullptr : a.tile_zmax; in.flags = cube ? nullptr : a.flags;
+		in.pine = has_pine ? (tree_place_pod_t const *)a.pine : nullptr; in.pine_counts = has_pine ? a.pine_counts : nullptr;
+		in.ov = has_pine ? (trunk_override_pod_t const *)a.trunk_override : nullptr;
+		in.decid = has_decid ? (decid_place_pod_t const *)a.decid : nullptr; in.decid_counts = has_decid ? a.decid_counts : nullptr;
+		in.scen = has_scen ? (scenery_place_pod_t const *)a.scenery : nullptr; in.scen_counts = has_scen ? a.scenery_counts : nullptr; in.rov = has_scen ? a.radius_override : nullptr;
+		in.insts = (has_pine && tp.instanced) ? tree_insts_dev() : nullptr;
+		in.data = has_decid ? (decid_tree_data_pod_t const *)a.tree_data : nullptr; in.br_scale = has_decid ? a.br_scale : nullptr;
+		in.tile_xy = d_txy; in.slots = d_slots;
+	}
+	void tiles_sphere_collide_dev(int32_t const *tile_xy, uint32_t n, terra_collide_in const *a, sphere_query_pod_t const *d_queries, uint32_t nq, sphere_hit_pod_t *d_hits) {
+		char const *const what = "tiles_sphere_collide";
+		collide_check(a, false, what);
+		if ((((uintptr_t)d_queries | (uintptr_t)d_hits) & 3u) != 0) throw std::invalid_argument(std::string(what) + ": d_queries and d_hits must be 4-byte aligned");
+		collide_consts_t c; collide_in_t in;
+		if (n != 0) {collide_setup(tile_xy, n, *a, false, what, c, in);} // (the checks on the batch; with nq == 0 nothing more happens)
+		if (nq == 0) return;
+		if (!d_queries || !d_hits) throw std::invalid_argument(std::string(what) + ": null argument");
+		if (n == 0) { // no tile: every query is answered as such, nothing is read of the batch
+			memset(&c, 0, sizeof(c)); memset(&in, 0, sizeof(in));
+		}
+		if constexpr (BE::has_kernels) {if (be.tile_sphere_collide(c, in, d_queries, nq, d_hits)) return;}
+		// the simple form: a logical thread per query, the reference's loops
+		be.launch(nq, [=] TERRA_LAMBDA (size_t i) {
+			sphere_query_pod_t const q = d_queries[i];
+			d_hits[i] = coll_query(c, in, q, [&](uint32_t t) {return coll_query_literal(c, in, t, q.pos, q.radius, q.flags);});
+		});
+	}
+	void tiles_cube_int_trees_dev(int32_t const *tile_xy, uint32_t n, terra_collide_in const *a, float const *d_cubes, int32_t const *d_cube_tile, uint32_t nq, uint8_t *d_result,
+		int32_t *d_tile_out)
+	{
+		char const *const what = "tiles_cube_int_trees";
+		collide_check(a, true, what);
+		if ((((uintptr_t)d_cubes | (uintptr_t)d_cube_tile | (uintptr_t)d_tile_out) & 3u) != 0) throw std::invalid_argument(std::string(what) + ": d_cubes, d_cube_tile and d_tile_out must be 4-byte aligned");
+		collide_consts_t c; collide_in_t in;
+		if (n != 0) {collide_setup(tile_xy, n, *a, true, what, c, in);}
+		if (nq == 0) return;
+		if (!d_cubes || !d_result) throw std::invalid_argument(std::string(what) + ": null argument");
+		if (n == 0) {memset(&c, 0, sizeof(c)); memset(&in, 0, sizeof(in));}
+		if constexpr (BE::has_kernels) {if (be.tile_cube_int_trees(c, in, d_cubes, d_cube_tile, nq, d_result, d_tile_out)) return;}
+		be.launch(nq, [=] TERRA_LAMBDA (size_t i) {
+			float d[6];
+			for (int k = 0; k < 6; ++k) {d[k] = d_cubes[6*i + k];}
+			uint32_t res = 0;
+			int32_t t = -1;
+			if (!coll_cube_ok(d)) {res = CUBE_INT_BAD_QUERY;}
+			else {
+				t = coll_cube_tile(c, in, d_cube_tile ? d_cube_tile[i] : -1, d);
+				res = (t < 0) ? (uint32_t)CUBE_INT_NO_TILE : (uint32_t)coll_cube_literal(c, in, (uint32_t)t, d);
+			}
+			d_result[i] = (uint8_t)res;
+			if (d_tile_out) {d_tile_out[i] = t;}
 		});
 	}
 

@@ -679,6 +679,15 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		run(terra::k_cloud_rank, dim3(nb), dim3(T), 0, (terra::cloud_inst_pod_t const *)found, (uint32_t const *)cnt, list, list_count);
 		return true;
 	}
+	// sphere collisions and tree box tests: one wave per query, four to a workgroup (k_sphere_collide, k_cube_int_trees)
+	bool tile_sphere_collide(terra::collide_consts_t const &c, terra::collide_in_t const &in, terra::sphere_query_pod_t const *queries, uint32_t nq, terra::sphere_hit_pod_t *hits) {
+		uint32_t const per = terra::COLL_THREADS/64u;
+		return launch_if(true, terra::k_sphere_collide, dim3(nq/per + ((nq%per) ? 1u : 0u)), dim3(terra::COLL_THREADS), c, in, queries, nq, hits);
+	}
+	bool tile_cube_int_trees(terra::collide_consts_t const &c, terra::collide_in_t const &in, float const *cubes, int32_t const *cube_tile, uint32_t nq, uint8_t *result, int32_t *tile_out) {
+		uint32_t const per = terra::COLL_THREADS/64u;
+		return launch_if(true, terra::k_cube_int_trees, dim3(nq/per + ((nq%per) ? 1u : 0u)), dim3(terra::COLL_THREADS), c, in, cubes, cube_tile, nq, result, tile_out);
+	}
 	// the pine and palm tree draw lists for a camera: one workgroup per tile (k_tree_view)
 	bool tile_tree_view(terra::tree_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra::tree_inst_pod_t const *insts, terra_tile_stats const *stats, uint8_t const *skip,
 		float const *trmax, terra::tree_place_pod_t const *pine, uint32_t const *counts, terra::trunk_override_pod_t const *ov, terra::tree_view_tile_pod_t *tile_out, float *bcube,

@@ -2931,6 +2931,181 @@ __global__ __launch_bounds__(DCV_THREADS) void k_decid_view(decid_view_consts_t 
 	}
 }
 
+// ------------------------------------------------------------------ sphere collisions and tree box tests against the containers of a tile batch
+// (tile_t::check_sphere_collision, src/tiled_mesh.cpp:2146-2168; tile_t::check_cube_int_trees, :2170-2173; terra_collide.hpp).
+// k_sphere_collide: one 64-lane wave per query, four queries per workgroup; no LDS, no barrier, nothing waits for another wave.  Every lane holds the query and the
+// centre; what decides where the wave goes (the stage, the counts, the gates, the ballots) is the same in all 64 lanes.  Per container, in the reference's order:
+//  - the prologue: a sweep over the tile's records, a lane a record, for the number of valid records (the container's empty()) and calc_bcube, reduced with shuffles;
+//    for the scenery, which kinds the tile holds and whether a rock_shape has no override.
+//  - the chain: the wave tests the next 64 records against the current centre, a lane a record, with the exact test.  The lowest lane of the ballot is the first hit
+//    in the reference's order -- every record before it has seen the centre it would have seen sequentially -- so its pushed centre is broadcast and the wave resumes
+//    at the record behind it.  Without a hit the wave steps 64 records on.  The resume position advances strictly: a container of c records ends after at most c rounds.
+//    The scenery is walked once per kind that the tile holds, in scenery_group::check_sphere_coll's order; a lane whose record is of another kind does not hit.
+// k_cube_int_trees: the same wave per query; the test is an order-free "any" over the valid deciduous records, so one ballot per 64 records answers it.
+constexpr uint32_t COLL_THREADS = 256;
+__device__ __forceinline__ void coll_wave_take(coll_pt_t &c, coll_pt_t const &m, int l) {c.x = __shfl(m.x, l); c.y = __shfl(m.y, l); c.z = __shfl(m.z, l);}
+// the chain over records [0, cnt): test(j, m) -> whether record j moves the centre m
+template<class TEST> __device__ __forceinline__ uint32_t coll_wave_chain(uint32_t cnt, uint32_t lane, coll_pt_t &c, TEST test) {
+	uint32_t nhits = 0;
+	for (uint32_t start = 0; start < cnt;) {
+		uint32_t const j = start + lane;
+		coll_pt_t m = c;
+		bool const hit = j < cnt && test(j, m);
+		unsigned long long const mask = __ballot(hit);
+		if (mask == 0ull) {start += 64u; continue;}
+		int const l = __ffsll((long long)mask) - 1;
+		coll_wave_take(c, m, l);
+		++nhits; start += (uint32_t)l + 1u;
+	}
+	return nhits;
+}
+// calc_bcube of the deciduous container by the wave; -> the number of valid records
+__device__ __forceinline__ uint32_t coll_wave_decid_bcube(collide_consts_t const &c, collide_in_t const &in, uint32_t t, uint32_t nd, uint32_t lane, float bc[6]) {
+	decid_view_union_t un;
+	decid_view_union_init(un);
+	uint32_t nv = 0;
+	for (uint32_t j = lane; j < nd; j += 64u) {
+		decid_place_pod_t r;
+		if (!coll_decid_rec(c, in, t, j, r)) continue;
+		++nv;
+		float b[6], l[6];
+		decid_view_bounds(in.data[r.tree_id], r.pos, b, l);
+		decid_view_union_add(un, j, b, l);
+	}
+	for (int off = 32; off; off >>= 1) {
+		decid_view_union_t ot;
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {ot.b[k] = __shfl_xor(un.b[k], off); ot.l[k] = __shfl_xor(un.l[k], off);}
+		ot.first = __shfl_xor(un.first, off); ot.last_zero = __shfl_xor(un.last_zero, off);
+		decid_view_union_merge(un, ot);
+		nv += __shfl_xor(nv, off);
+	}
+	decid_view_union_result(un, bc);
+	return nv;
+}
+__device__ __forceinline__ coll_result_t coll_query_wave(collide_consts_t const &c, collide_in_t const &in, uint32_t t, float const pos[3], float radius, uint32_t flags, uint32_t lane) {
+	coll_result_t o; o.c.x = pos[0]; o.c.y = pos[1]; o.c.z = pos[2]; o.word = 0u; o.nhits = 0u;
+	float const INF = __builtin_inff();
+	uint32_t const np = (flags & COLL_INC_PTREES) ? coll_pine_count(c, in, t) : 0u;
+	if (np != 0u) {
+		float box[6] = {INF, -INF, INF, -INF, INF, -INF}; // (coll_pine_bcube assigns the first box and then unions: the same bounds but for the sign of a zero, which no comparison of the gate sees)
+		uint32_t nv = 0, nb = 0;
+		for (uint32_t j = lane; j < np; j += 64u) {
+			tree_view_rec_t rec;
+			if (!coll_pine_rec(c, in, t, j, rec)) continue;
+			++nv;
+			float d[6];
+			if (!tree_view_bounds(rec, d)) continue;
+			++nb;
+#pragma unroll
+			for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], d[k]); box[k + 1] = max_std(box[k + 1], d[k + 1]);}
+		}
+		for (int off = 32; off; off >>= 1) {
+			nv += __shfl_xor(nv, off); nb += __shfl_xor(nb, off);
+#pragma unroll
+			for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], __shfl_xor(box[k], off)); box[k + 1] = max_std(box[k + 1], __shfl_xor(box[k + 1], off));}
+		}
+		if (nv != 0u) { // inc_ptrees && !pine_trees.empty()
+			if (nb == 0u) {
+#pragma unroll
+				for (int k = 0; k < 6; ++k) {box[k] = 0.0f;}
+			}
+			o.c.x -= c.pv.a.offx; o.c.y -= c.pv.a.offy; o.c.z -= 0.0f;
+			if (!coll_gate_exits(o.c, radius, box)) {
+				uint32_t const nh = coll_wave_chain(np, lane, o.c, [&](uint32_t j, coll_pt_t &m) {
+					tree_view_rec_t rec;
+					return coll_pine_rec(c, in, t, j, rec) && coll_small_tree(rec, m, radius);
+				});
+				if (nh) {o.word |= COLL_HIT_PINE; o.nhits += nh;}
+			}
+			o.c.x += c.pv.a.offx; o.c.y += c.pv.a.offy; o.c.z += 0.0f;
+		}
+	}
+	uint32_t const nd = (flags & COLL_INC_DTREES) ? coll_decid_count(c, in, t) : 0u;
+	if (nd != 0u) {
+		float bc[6];
+		if (coll_wave_decid_bcube(c, in, t, nd, lane, bc) != 0u) {
+			o.c.x -= c.doffx; o.c.y -= c.doffy; o.c.z -= 0.0f;
+			if (!coll_gate_exits(o.c, radius, bc)) {
+				uint32_t const nh = coll_wave_chain(nd, lane, o.c, [&](uint32_t j, coll_pt_t &m) {
+					decid_place_pod_t r;
+					return coll_decid_rec(c, in, t, j, r) && coll_decid_tree(in.data[r.tree_id], in.br_scale ? in.br_scale[r.tree_id] : 1.0f, r.pos, m, radius);
+				});
+				if (nh) {o.word |= COLL_HIT_DECID; o.nhits += nh;}
+			}
+			o.c.x += c.doffx; o.c.y += c.doffy; o.c.z += 0.0f;
+		}
+	}
+	if ((flags & COLL_INC_SCENERY) && coll_scenery_generated(in, t)) {
+		uint32_t const ns = coll_scen_count(c, in, t);
+		size_t const base = (size_t)t*c.scen_cap;
+		uint32_t present = 0; // bit k: the tile holds a record of kind k; bit 31: a rock_shape without an override
+		for (uint32_t j = lane; j < ns; j += 64u) {
+			int const kind = in.scen[base + j].kind;
+			if (kind >= 0 && kind < SCENERY_KINDS) {present |= 1u << kind;}
+			if (kind == SCENERY_ROCK_SHAPE && !((in.rov ? in.rov[base + j] : 0.0f) > 0.0f)) {present |= 0x80000000u;}
+		}
+		for (int off = 32; off; off >>= 1) {present |= __shfl_xor(present, off);}
+		if (present & 0x80000000u) {o.word |= COLL_ROCK_SHAPE_UNDECIDED;}
+		o.c.x -= c.soffx; o.c.y -= c.soffy; o.c.z -= 0.0f;
+		for (int k = 0; k < COLL_SCENERY_PASSES; ++k) {
+			int const kind = coll_scenery_pass_kind(k);
+			if (!((present >> kind) & 1u)) continue;
+			uint32_t const nh = coll_wave_chain(ns, lane, o.c, [&](uint32_t j, coll_pt_t &m) {
+				if (in.scen[base + j].kind != kind) return false;
+				bool und = false;
+				return coll_scenery(in.scen[base + j], in.rov ? in.rov[base + j] : 0.0f, m, radius, und);
+			});
+			if (nh) {o.word |= COLL_HIT_SCENERY; o.nhits += nh;}
+		}
+		o.c.x += c.soffx; o.c.y += c.soffy; o.c.z += 0.0f;
+	}
+	return o;
+}
+__global__ __launch_bounds__(COLL_THREADS) void k_sphere_collide(collide_consts_t c, collide_in_t in, sphere_query_pod_t const *__restrict__ queries, uint32_t nq,
+	sphere_hit_pod_t *__restrict__ hits)
+{
+	uint32_t const lane = threadIdx.x & 63u;
+	uint32_t const qi = blockIdx.x*(COLL_THREADS/64u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	if (qi >= nq) return; // (the whole wave)
+	sphere_query_pod_t const q = queries[qi];
+	sphere_hit_pod_t const h = coll_query(c, in, q, [&](uint32_t t) {return coll_query_wave(c, in, t, q.pos, q.radius, q.flags, lane);});
+	if (lane == 0u) {hits[qi] = h;}
+}
+__global__ __launch_bounds__(COLL_THREADS) void k_cube_int_trees(collide_consts_t c, collide_in_t in, float const *__restrict__ cubes, int32_t const *__restrict__ cube_tile, uint32_t nq,
+	uint8_t *__restrict__ result, int32_t *__restrict__ tile_out)
+{
+	uint32_t const lane = threadIdx.x & 63u;
+	uint32_t const qi = blockIdx.x*(COLL_THREADS/64u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	if (qi >= nq) return; // (the whole wave)
+	float d[6];
+#pragma unroll
+	for (int k = 0; k < 6; ++k) {d[k] = cubes[(size_t)qi*6u + k];}
+	uint32_t res = 0;
+	int32_t t = -1;
+	if (!coll_cube_ok(d)) {res = CUBE_INT_BAD_QUERY;}
+	else {
+		t = coll_cube_tile(c, in, cube_tile ? cube_tile[qi] : -1, d);
+		if (t < 0) {res = CUBE_INT_NO_TILE;}
+		else {
+			uint32_t const nd = coll_decid_count(c, in, (uint32_t)t);
+			float bc[6], loc[6];
+			if (nd != 0u && coll_wave_decid_bcube(c, in, (uint32_t)t, nd, lane, bc) != 0u) {
+				coll_cube_local(c, d, loc);
+				if (coll_zero_area(bc) || coll_cubes_intersect(bc, loc)) {
+					for (uint32_t start = 0; start < nd && !res; start += 64u) {
+						uint32_t const j = start + lane;
+						decid_place_pod_t r;
+						bool const hit = j < nd && coll_decid_rec(c, in, (uint32_t)t, j, r) && coll_decid_cube(in.data[r.tree_id], r.pos, loc);
+						if (__ballot(hit) != 0ull) {res = CUBE_INT_HIT;}
+					}
+				}
+			}
+		}
+	}
+	if (lane == 0u) {result[qi] = (uint8_t)res; if (tile_out) {tile_out[qi] = t;}}
+}
+
 // ------------------------------------------------------------------ tree AO shadows from the placement records (tile_t::apply_tree_ao_shadows, src/tiled_mesh.cpp:740-828;
 // terra_treeao.hpp), three launches: k_tree_ao_sources, k_tree_ao_gather, then k_tree_map (above, unchanged) on the lists the gather wrote.
 // k_tree_ao_sources: a thread per record slot, a block = 256 slots of one tile (so a wave never spans two tiles).  {pt.x, pt.y, get_ao_radius()} of every record goes

@@ -217,6 +217,48 @@ CLD_OVERFLOW = 1
 CLV_NONE, CLV_VFC, CLV_BELOW_ZMIN, CLV_BELOW_WATER, CLV_BELOW_MESH, CLV_LISTED = range(6)  # the stage byte of tiles_cloud_view
 
 
+class CollideIn(C.Structure):  # terra_collide_in
+    _fields_ = [(k, C.c_void_p) for k in ("stats", "trmax", "tile_zmax", "flags", "pine", "pine_counts", "trunk_override", "decid", "decid_counts", "scenery", "scenery_counts",
+                                          "radius_override", "tree_data", "br_scale")] + \
+               [(k, C.c_uint32) for k in ("pine_capacity", "decid_capacity", "scenery_capacity", "num_tree_data")] + \
+               [(k, C.c_int32) for k in ("dxoff", "dyoff", "ptree_xoff2", "ptree_yoff2", "dtree_xoff2", "dtree_yoff2", "scenery_xoff2", "scenery_yoff2")] + \
+               [("tree_depth_scale", C.c_float), ("pad", C.c_uint32)]
+
+
+def _address(x):
+    """the address of a numpy array, a ctypes object or a DeviceBuffer; an int is taken as an address; None stays None"""
+    if x is None or isinstance(x, int):
+        return x
+    if isinstance(x, np.ndarray):
+        assert x.flags["C_CONTIGUOUS"]
+        return x.ctypes.data
+    return x.ptr if hasattr(x, "ptr") else C.addressof(x)
+
+
+def make_collide_in(stats=None, trmax=None, tile_zmax=None, flags=None, pine=None, pine_counts=None, trunk_override=None, decid=None, decid_counts=None, scenery=None,
+                    scenery_counts=None, radius_override=None, tree_data=None, br_scale=None, pine_capacity=None, decid_capacity=None, scenery_capacity=None,
+                    num_tree_data=None, dxoff=0, dyoff=0, ptree_xoff2=0, ptree_yoff2=0, dtree_xoff2=0, dtree_yoff2=0, scenery_xoff2=0, scenery_yoff2=0, tree_depth_scale=1.0):
+    """terra_collide_in.  An array is a C-contiguous numpy array, a ctypes object, a DeviceBuffer or an address; host arrays go with the host forms, device memory with
+    the _dev forms.  A capacity that is not given is a [n, capacity] numpy array's; num_tree_data the length of tree_data.  The struct keeps its arrays alive."""
+    cap = lambda given, arr: int(given) if given is not None else (arr.shape[1] if isinstance(arr, np.ndarray) and arr.ndim == 2 else 0)  # noqa: E731
+    ntd = int(num_tree_data) if num_tree_data is not None else (len(tree_data) if isinstance(tree_data, np.ndarray) else 0)
+    arrays = (stats, trmax, tile_zmax, flags, pine, pine_counts, trunk_override, decid, decid_counts, scenery, scenery_counts, radius_override, tree_data, br_scale)
+    cin = CollideIn(*[_address(x) for x in arrays], cap(pine_capacity, pine), cap(decid_capacity, decid), cap(scenery_capacity, scenery), ntd, dxoff, dyoff, ptree_xoff2,
+                    ptree_yoff2, dtree_xoff2, dtree_yoff2, scenery_xoff2, scenery_yoff2, tree_depth_scale, 0)
+    cin._keep = arrays
+    return cin
+
+
+SPHERE_QUERY_DTYPE = np.dtype([("pos", np.float32, (3,)), ("radius", np.float32), ("tile", np.int32), ("flags", np.uint32)])  # terra_sphere_query
+SPHERE_HIT_DTYPE = np.dtype([("pos", np.float32, (3,)), ("tile", np.int32), ("word", np.uint32), ("nhits", np.uint32)])      # terra_sphere_hit
+assert SPHERE_QUERY_DTYPE.itemsize == 24 and SPHERE_HIT_DTYPE.itemsize == 24 and C.sizeof(CollideIn) == 168
+COLL_INC_DTREES, COLL_INC_PTREES, COLL_INC_SCENERY, COLL_INC_ALL = 1, 2, 4, 7  # terra_sphere_query.flags
+COLL_TILE_DISTANT, COLL_TILE_NO_SCENERY = 1, 2                                 # the per-tile flag byte of terra_collide_in
+COLL_HIT_PINE, COLL_HIT_DECID, COLL_HIT_SCENERY, COLL_ROCK_SHAPE_UNDECIDED, COLL_STAGE_SHIFT, COLL_STAGE_MASK = 1, 2, 4, 8, 8, 0xF00  # terra_sphere_hit.word
+COLL_STAGE_TESTED, COLL_STAGE_NO_TILE, COLL_STAGE_DISTANT, COLL_STAGE_OUTSIDE, COLL_STAGE_ABOVE, COLL_STAGE_BAD_QUERY = range(6)
+CUBE_INT_HIT, CUBE_INT_NO_TILE, CUBE_INT_BAD_QUERY = 1, 2, 4                   # the result byte of tiles_cube_int_trees
+
+
 class TreeViewArgs(C.Structure):  # terra_tree_view_args
     _fields_ = [("behind_sphere_mult", C.c_float), ("zoom_f", C.c_float), ("tree_depth_scale", C.c_float), ("window_width", C.c_int32), ("shadow_pass", C.c_int32),
                 ("draw_trunks", C.c_int32), ("draw_near_leaves", C.c_int32), ("draw_far_leaves", C.c_int32)]
@@ -497,6 +539,10 @@ _PROTOS = {
     "terra_tiles_update_clouds": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_cloud_view_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "terra_tiles_cloud_view": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "terra_tiles_sphere_collide_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "terra_tiles_sphere_collide": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "terra_tiles_cube_int_trees_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "terra_tiles_cube_int_trees": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
     "terra_tiles_tree_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_tree_view": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_scenery_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
@@ -1217,6 +1263,28 @@ class Terra:
                                                  cnt.ctypes.data))
         return stage, lst[:cnt[0]]
 
+    def tiles_sphere_collide(self, tile_xy, cin, queries):
+        """nq calls of tile_draw_t::check_sphere_collision (a query's tile = -1) or tile_t::check_sphere_collision (tile = a batch index) against host arrays:
+        cin a make_collide_in of host arrays, queries SPHERE_QUERY_DTYPE [nq].  -> SPHERE_HIT_DTYPE [nq]"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        q = np.ascontiguousarray(queries, SPHERE_QUERY_DTYPE).reshape(-1)
+        hits = np.zeros(len(q), SPHERE_HIT_DTYPE)
+        self._ck(self.lib.terra_tiles_sphere_collide(self.ctx, txy.ctypes.data if len(txy) else None, len(txy), C.byref(cin), q.ctypes.data if len(q) else None, len(q),
+                                                     hits.ctypes.data if len(q) else None))
+        return hits
+
+    def tiles_cube_int_trees(self, tile_xy, cin, cubes, cube_tile=None):
+        """nq calls of tile_draw_t::check_cube_int_trees against host arrays: cubes [nq, 6] = x1 x2 y1 y2 z1 z2, cube_tile [nq] or None.
+        -> (result uint8 [nq] of CUBE_INT_*, tile int32 [nq])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        cb = np.ascontiguousarray(cubes, np.float32).reshape(-1, 6)
+        ct = None if cube_tile is None else np.ascontiguousarray(cube_tile, np.int32).reshape(len(cb))
+        res, tile = np.zeros(len(cb), np.uint8), np.zeros(len(cb), np.int32)
+        self._ck(self.lib.terra_tiles_cube_int_trees(self.ctx, txy.ctypes.data if len(txy) else None, len(txy), C.byref(cin), cb.ctypes.data if len(cb) else None,
+                                                     None if ct is None or not len(cb) else ct.ctypes.data, len(cb), res.ctypes.data if len(cb) else None,
+                                                     tile.ctypes.data if len(cb) else None))
+        return res, tile
+
     def tiles_tree_view(self, tile_xy, stats, view, args, pine, pine_counts, skip=None, trmax=None, trunk_override=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0, fill=0):
         """tile_t::draw_pine_trees for every tile: pine TREE_PLACE_DTYPE [n, cap] with pine_counts [n]; stats TileStats * n; skip [n] bytes, trmax [n] float32,
         trunk_override TRUNK_OVERRIDE_DTYPE [n, cap], all optional.  The [n, cap] outputs start filled with the byte `fill`; entries past the counts keep it.
@@ -1611,6 +1679,18 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_cloud_view_dev(self.ctx, txy.ctypes.data, len(txy), C.byref(view), C.byref(args), stats_ptr, state_ptr, clouds_ptr, capacity, stage_ptr, list_ptr,
                                                      list_count_ptr))
+
+    def tiles_sphere_collide_dev(self, tile_xy, cin, queries_ptr, nq, hits_ptr):
+        """the sphere queries of a device-resident batch: cin a make_collide_in of device arrays, queries_ptr [nq] terra_sphere_query, hits_ptr [nq] terra_sphere_hit.
+        Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_sphere_collide_dev(self.ctx, txy.ctypes.data if len(txy) else None, len(txy), C.byref(cin), queries_ptr, nq, hits_ptr))
+
+    def tiles_cube_int_trees_dev(self, tile_xy, cin, cubes_ptr, nq, result_ptr, cube_tile_ptr=None, tile_out_ptr=None):
+        """the tree box tests of a device-resident batch: cubes_ptr [nq][6] floats, result_ptr [nq] bytes, cube_tile_ptr / tile_out_ptr [nq] int32 or None.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_cube_int_trees_dev(self.ctx, txy.ctypes.data if len(txy) else None, len(txy), C.byref(cin), cubes_ptr, cube_tile_ptr, nq, result_ptr,
+                                                         tile_out_ptr))
 
     def tiles_tree_view_dev(self, tile_xy, view, args, stats_ptr, pine_ptr, pine_counts_ptr, capacity, tile_out_ptr, all_bcube_ptr, pine_insts_ptr, palm_insts_ptr, inst_counts_ptr,
                             leaf_list_ptr, leaf_counts_ptr, trunk_ptr, skip_ptr=None, trmax_ptr=None, trunk_override_ptr=None, dxoff=0, dyoff=0, xoff2=0, yoff2=0):

@@ -1512,6 +1512,85 @@ int  terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
                             float *h_branch_scale, float *h_branch_opacity, uint32_t *h_branch_num, uint32_t *h_leaf_list, uint32_t *h_branch_list,
                             terra_decid_view_bb *h_leaf_bb, terra_decid_view_bb *h_branch_bb, uint32_t *h_list_counts);
 
+/* ---- sphere collisions and tree box tests against the resident containers of a tile batch (every supported tile size S): what lets an engine drop its host copy
+ * of the pine / palm, deciduous and scenery containers.  terra_tiles_sphere_collide answers nq independent calls of tile_draw_t::check_sphere_collision
+ * (src/tiled_mesh.cpp:3566-3569: the player, :3570-3575, and every large physics object, src/Physics.cpp:858) or of tile_t::check_sphere_collision (:2146-2168: every
+ * butterfly every frame, src/animals.cpp:422); terra_tiles_cube_int_trees answers nq calls of tile_draw_t::check_cube_int_trees (:3576-3579: balcony placement,
+ * src/building_rooms.cpp:1655).  Restated bit for bit with the source's operand types: get_tile_pair_at_point (:3532-3534; round_fp of a float expression, converted
+ * as x86 converts it), tile_t::get_bcube / contains_point / get_tile_zmax (src/tiled_mesh.h:207,232-236,264), small_tree_group::check_sphere_coll and
+ * small_tree::check_sphere_coll (src/sm_tree.cpp:181-186, 841-852), tree_cont_t::check_sphere_coll and tree::check_sphere_coll (src/Tree.cpp:280-294),
+ * scenery_group::check_sphere_coll (src/scenery.cpp:1187-1199) over scenery_obj::check_sphere_coll (:80-86), s_stump::check_sphere_coll (:665-668) and
+ * s_plant::check_sphere_coll (:772-775), sphere_vert_cylin_intersect (src/Math3d.cpp:427-437, without its asserts), sphere_cube_intersect (:930-935), dist_less_than,
+ * dist_xy_less_than, contains_pt_exp, is_zero_area, contains_pt_xy, get_norm(); tree_cont_t::check_cube_int and tree::check_cube_int (src/Tree.cpp:296-309).
+ * 1.001*rsum, 0.9*br_scale*base_radius, 0.2*height, 0.1*height and 0.1*radius are formed in double and narrowed where the source narrows them.
+ * Line queries with inc_trees = 1 (they need line_intersect_trunc_cone) are not part of this: they stay with the engine.
+ *
+ * What a query sees, as in the reference.  Every hit moves the centre and every later object sees the moved centre, within a container and across containers:
+ * pine / palm, then deciduous, then scenery; nothing ends early.  The scenery is walked by kind -- rock_shapes, surface_rocks, voxel_rocks, rocks, (logs: no
+ * collision), stumps, plants, leafy_plants (mushrooms: none) -- and within a kind in record order; the record list is the stable interleave of those vectors.
+ * `pos -= xlate; ..; pos += xlate` runs for a container whenever it is included and present (a tree container: it holds a valid record; the scenery: generated), hit
+ * or no hit, also when its all_bcube gate returns early: in floats that round trip is not the identity, and pos comes back as the reference leaves it.  The three
+ * translations are ((dxoff + xoff2)*DX_VAL, (dyoff + yoff2)*DY_VAL, 0) with the container's own xoff2 / yoff2.  Both tree containers gate on
+ * !all_bcube.is_zero_area() && !sphere_cube_intersect(center, radius, all_bcube) with the centre as it stands at the container's turn; all_bcube is calc_bcube()
+ * over the valid records exactly as terra_tiles_tree_view and terra_tiles_decid_view form it, computed by this call.  Records that those views drop are skipped
+ * and do not enter all_bcube: a bad type, an instance outside the table, an instanced record while `instanced` is off, a tree_id outside the table or not
+ * TERRA_DCV_GENERATED.  A rock_shape or voxel_rock takes radius_override as terra_tiles_scenery_view defines it (pos.z += 0.1*radius for a rock_shape with one); a
+ * rock_shape without an override is not tested, and TERRA_COLL_ROCK_SHAPE_UNDECIDED says that the tile held one.
+ *
+ * terra_collide_in is read at the call; its pointers are device pointers for the _dev forms and host pointers otherwise.  Per tile: stats [n] (mzmin, mzmax),
+ * trmax [n] and tile_zmax [n] (optional) as for terra_tiles_terrain_view (no tile_zmax: get_tile_zmax() is mzmax), flags [n] bytes (optional): TERRA_COLL_TILE_DISTANT
+ * (is_distant), TERRA_COLL_TILE_NO_SCENERY (!scenery.generated).  The three record arrays [n][capacity] with counts [n] as the placements and the brush keep them; a
+ * count above the capacity means the first `capacity` records; a container with NULL records or counts or capacity 0 is absent everywhere.  trunk_override
+ * [n][pine_capacity] and radius_override [n][scenery_capacity] (optional).  The instance table and terra_tree_size_params are the context's, as for
+ * terra_tiles_tree_view; tree_depth_scale as in terra_tree_view_args.  tree_data [num_tree_data] with br_scale [num_tree_data] (tree_data_t::br_scale; the struct
+ * keeps its layout), required with the deciduous records; num_tree_data must be terra_decid_params.num_shared_trees.
+ * A query: pos, radius, tile, flags (TERRA_COLL_INC_*).  tile = -1: the tile is looked up from pos (tile_draw_t's form); tile >= 0: that batch index
+ * (tile_t's form, the analogue of line_tile).  A tile outside [-1, n) is answered as no tile.  A query with a non-finite member or a negative radius is a bad
+ * query: its pos comes back unchanged and nothing is read for it.  The kernels index nothing with a query's tile, a looked-up tile or a record's tree_id / inst
+ * before its range is known.
+ * A hit record: pos as the reference leaves it; tile: the batch index used or -1; word: TERRA_COLL_HIT_PINE / _DECID / _SCENERY (the container reported a
+ * collision), TERRA_COLL_ROCK_SHAPE_UNDECIDED, and in TERRA_COLL_STAGE_MASK where the query left: _TESTED (it reached the containers), _NO_TILE, _DISTANT,
+ * _OUTSIDE (contains_point failed), _ABOVE (pos.z > get_tile_zmax() + radius), _BAD_QUERY; nhits: the number of objects that moved the centre.
+ * The cube call: cubes [nq][6] = x1 x2 y1 y2 z1 z2 in camera space, cube_tile [nq] or NULL (as a query's tile; NULL: every tile from the cube's centre),
+ * result [nq] bytes: TERRA_CUBE_INT_HIT, TERRA_CUBE_INT_NO_TILE, TERRA_CUBE_INT_BAD_QUERY (a non-finite bound); tile_out [nq] (optional): the batch index or -1.
+ * It reads the deciduous members of terra_collide_in alone (with dxoff / dyoff and dtree_xoff2 / dtree_yoff2).
+ *
+ * TERRA_ERR_ARG, with nothing written: a NULL required pointer (in; tile_xy and stats when n > 0; queries / cubes and hits / result when nq > 0; tree_data and
+ * br_scale with deciduous records); a pointer other than flags and result that is not 4-byte aligned; tree_depth_scale not finite and > 0; num_tree_data other than
+ * num_shared_trees when there are deciduous records; `instanced` with an instance table of another length; an unsupported S; n*capacity beyond 32 bits; a tile
+ * that appears twice.  TERRA_ERR_STATE before terra_init_scene.  n == 0 or nq == 0 does nothing once the checks have passed.  The device forms only enqueue and read
+ * nothing back; tile_xy is a host array in both forms (the key table of the batch is built from it and searched on the device).  Scratch comes from the context's arena. */
+typedef struct terra_collide_in {
+	const terra_tile_stats *stats;
+	const float *trmax, *tile_zmax;
+	const uint8_t *flags;
+	const terra_tree_place *pine;       const uint32_t *pine_counts;    const terra_trunk_override *trunk_override;
+	const terra_decid_place *decid;     const uint32_t *decid_counts;
+	const terra_scenery_place *scenery; const uint32_t *scenery_counts; const float *radius_override;
+	const terra_decid_tree_data *tree_data; const float *br_scale;
+	uint32_t pine_capacity, decid_capacity, scenery_capacity, num_tree_data;
+	int32_t dxoff, dyoff;               /* xoff - xoff2, yoff - yoff2 */
+	int32_t ptree_xoff2, ptree_yoff2, dtree_xoff2, dtree_yoff2, scenery_xoff2, scenery_yoff2; /* what the three placements ran with */
+	float tree_depth_scale;
+	uint32_t pad;
+} terra_collide_in;          /* 168 bytes */
+typedef struct terra_sphere_query {float pos[3], radius; int32_t tile; uint32_t flags;} terra_sphere_query;    /* 24 bytes */
+typedef struct terra_sphere_hit {float pos[3]; int32_t tile; uint32_t word, nhits;} terra_sphere_hit;          /* 24 bytes */
+enum {TERRA_COLL_INC_DTREES = 1, TERRA_COLL_INC_PTREES = 2, TERRA_COLL_INC_SCENERY = 4, TERRA_COLL_INC_ALL = 7};
+enum {TERRA_COLL_TILE_DISTANT = 1, TERRA_COLL_TILE_NO_SCENERY = 2};
+enum {TERRA_COLL_HIT_PINE = 1, TERRA_COLL_HIT_DECID = 2, TERRA_COLL_HIT_SCENERY = 4, TERRA_COLL_ROCK_SHAPE_UNDECIDED = 8, TERRA_COLL_STAGE_SHIFT = 8,
+      TERRA_COLL_STAGE_MASK = 0xF00, TERRA_COLL_STAGE_TESTED = 0, TERRA_COLL_STAGE_NO_TILE = 1, TERRA_COLL_STAGE_DISTANT = 2, TERRA_COLL_STAGE_OUTSIDE = 3,
+      TERRA_COLL_STAGE_ABOVE = 4, TERRA_COLL_STAGE_BAD_QUERY = 5};
+enum {TERRA_CUBE_INT_HIT = 1, TERRA_CUBE_INT_NO_TILE = 2, TERRA_CUBE_INT_BAD_QUERY = 4};
+int  terra_tiles_sphere_collide_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const terra_sphere_query *d_queries, uint32_t nq,
+                                    terra_sphere_hit *d_hits);
+int  terra_tiles_sphere_collide(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const terra_sphere_query *h_queries, uint32_t nq,
+                                terra_sphere_hit *h_hits);
+int  terra_tiles_cube_int_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const float *d_cubes, const int32_t *d_cube_tile,
+                                    uint32_t nq, uint8_t *d_result, int32_t *d_tile_out);
+int  terra_tiles_cube_int_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_collide_in *in, const float *h_cubes, const int32_t *h_cube_tile,
+                                uint32_t nq, uint8_t *h_result, int32_t *h_tile_out);
+
 
 /* ---- plumbing for callers without a HIP runtime of their own (tests, ctypes) */
 int  terra_malloc(terra_ctx *ctx, void **d_ptr, size_t bytes);

@@ -223,6 +223,38 @@ inline bool line_intersect_tiled_mesh(tile_batch_dev_t const &b, float const v1[
 	if (h.hit) {p_int[0] = h.p_int[0]; p_int[1] = h.p_int[1]; p_int[2] = h.p_int[2];}
 	return h.hit != 0;
 }
+// ---- sphere collisions and tree box tests against the resident containers (terra_tiles_sphere_collide_dev / terra_tiles_cube_int_trees_dev): `in` holds the device
+// arrays of the three containers as the placements left them.  The one-query forms below go through a staging buffer of the process, like tiles_line_intersect; a
+// frame's queries (the player, the physics objects, the animals) are better collected and asked in one terra_tiles_sphere_collide_dev call.
+// tile_draw_t::check_sphere_collision (src/tiled_mesh.cpp:3566-3569): pos is modified; only_tile >= 0: tile_t::check_sphere_collision of that batch tile
+inline bool tile_draw_check_sphere_collision(tile_batch_dev_t const &b, terra_collide_in const &in, float pos[3], float radius, int only_tile = -1,
+	bool inc_dtrees = 1, bool inc_ptrees = 1, bool inc_scenery = 1, terra_sphere_hit *hit_out = nullptr)
+{
+	struct io_t {terra_sphere_query q; terra_sphere_hit hit;};
+	static void *d_io = [] {void *p = nullptr; check(terra_malloc(default_ctx(), &p, sizeof(io_t)), "terra_malloc"); return p;}();
+	io_t io = {{{pos[0], pos[1], pos[2]}, radius, only_tile, (inc_dtrees ? (unsigned)TERRA_COLL_INC_DTREES : 0u) | (inc_ptrees ? (unsigned)TERRA_COLL_INC_PTREES : 0u) |
+		(inc_scenery ? (unsigned)TERRA_COLL_INC_SCENERY : 0u)}, {}};
+	io_t *d = (io_t *)d_io;
+	check(terra_memcpy_h2d(default_ctx(), &d->q, &io.q, sizeof(io.q)), "terra_memcpy_h2d");
+	check(terra_tiles_sphere_collide_dev(default_ctx(), b.tile_xy, b.n, &in, &d->q, 1, &d->hit), "tile_draw_t::check_sphere_collision");
+	check(terra_memcpy_d2h(default_ctx(), &io.hit, &d->hit, sizeof(io.hit)), "terra_memcpy_d2h");
+	pos[0] = io.hit.pos[0]; pos[1] = io.hit.pos[1]; pos[2] = io.hit.pos[2];
+	if (hit_out) {*hit_out = io.hit;}
+	return (io.hit.word & (TERRA_COLL_HIT_PINE | TERRA_COLL_HIT_DECID | TERRA_COLL_HIT_SCENERY)) != 0;
+}
+// sphere_int_tiled_terrain (src/tiled_mesh.cpp: the call Physics.cpp:858 makes): check_sphere_collision on a copy that is written back
+inline bool sphere_int_tiled_terrain(tile_batch_dev_t const &b, terra_collide_in const &in, float pos[3], float radius) {return tile_draw_check_sphere_collision(b, in, pos, radius);}
+// cube_int_tiled_terrain_trees = tile_draw_t::check_cube_int_trees (:3576-3579): cube = x1 x2 y1 y2 z1 z2 in camera space
+inline bool cube_int_tiled_terrain_trees(tile_batch_dev_t const &b, terra_collide_in const &in, float const cube[6]) {
+	struct io_t {float cube[6]; int32_t tile; uint8_t res; uint8_t pad[3];};
+	static void *d_io = [] {void *p = nullptr; check(terra_malloc(default_ctx(), &p, sizeof(io_t)), "terra_malloc"); return p;}();
+	io_t io = {{cube[0], cube[1], cube[2], cube[3], cube[4], cube[5]}, -1, 0, {0, 0, 0}};
+	io_t *d = (io_t *)d_io;
+	check(terra_memcpy_h2d(default_ctx(), d->cube, io.cube, sizeof(io.cube)), "terra_memcpy_h2d");
+	check(terra_tiles_cube_int_trees_dev(default_ctx(), b.tile_xy, b.n, &in, d->cube, nullptr, 1, &d->res, nullptr), "tile_draw_t::check_cube_int_trees");
+	check(terra_memcpy_d2h(default_ctx(), &io.res, &d->res, 1), "terra_memcpy_d2h");
+	return (io.res & TERRA_CUBE_INT_HIT) != 0;
+}
 // ---- the tree map of a batch and the two textures that read it (what tile_t::pre_draw runs after register_tree_change, src/tiled_mesh.cpp:1900-1907), on device
 // arrays.  tile_t::apply_tree_ao_shadows (:820-828) for every tile: the engine's add_tree_ao_shadow (:749) appends terra_tree_splat{pos.x, pos.y, tradius} to the
 // tile's list instead of looping over texels, and this runs the lists (tile t: d_splats[first[t] .. first[t+1]), first on the host).  reset = false is a later
