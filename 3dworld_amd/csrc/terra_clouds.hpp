@@ -19,9 +19,8 @@
 //   generate before the sender's turn).  An unmarked tile's step reads and writes nothing but the tile itself: those run in parallel.  The
 //   marked tiles are replayed in batch order by the literal loop, which hands records only to marked tiles.
 #pragma once
-#include "terra_common.hpp"
+#include "terra_view.hpp"
 #include "terra_treeplace.hpp"
-#include "terra_terrainview.hpp"
 
 namespace terra {
 
@@ -84,7 +83,7 @@ TERRA_HD void cloud_rgen_store(cloud_tile_pod_t &st, tree_rgen_t const &r) {st.r
 // update_bcube (:1753-1756) with tile_cloud_t::get_bcube
 TERRA_HD void cloud_update_bcube(cloud_tile_pod_t &st, cloud_pod_t const &c) {
 	float *b = st.bcube;
-	bool const zeros = b[0] == 0.0f && b[1] == 0.0f && b[2] == 0.0f && b[3] == 0.0f && b[4] == 0.0f && b[5] == 0.0f;
+	bool const zeros = box_all_zeros(b);
 	for (int i = 0; i < 3; ++i) {
 		float const lo = c.pos[i] - c.size[i], hi = c.pos[i] + c.size[i];
 		if (zeros) {b[2*i] = lo; b[2*i+1] = hi;} else {b[2*i] = min_std(b[2*i], lo); b[2*i+1] = max_std(b[2*i+1], hi);}

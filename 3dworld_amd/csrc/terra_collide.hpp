@@ -211,7 +211,7 @@ TERRA_HD uint32_t coll_pine_bcube(collide_consts_t const &c, collide_in_t const 
 		float d[6];
 		if (!tree_view_bounds(rec, d)) continue;
 		if (!any) {for (int k = 0; k < 6; ++k) {bc[k] = d[k];} any = true;}
-		else {for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], d[k]); bc[k + 1] = max_std(bc[k + 1], d[k + 1]);}}
+		else {box_union(bc, d);}
 	}
 	return nvalid;
 }

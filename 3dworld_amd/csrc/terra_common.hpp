@@ -76,6 +76,11 @@ TERRA_HD float clip01(float x)  {return max_std(0.0f, min_std(1.0f, x));}    // 
 TERRA_HD float clip_pm1(float x) {return max_std(-1.0f, min_std(1.0f, x));}  // CLIP_TO_pm1 src/3DWorld.h:149
 // float -> int with x86 cvttss2si semantics (NaN / out of range -> INT_MIN): what the reference binary does
 TERRA_HD int f2i_x86(float f) {return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;}
+// double -> int with x86 cvttsd2si semantics: every double that truncates into the int range converts, NaN and the others give INT_MIN
+TERRA_HD int d2i_x86(double v) {return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;}
+// float / double -> unsigned as the reference binary converts them (cvttss2si / cvttsd2si to 64 bits, the low word): NaN and values beyond the 64-bit range give 0
+TERRA_HD uint32_t f2u_x86(float f) {return (f > -9223372036854775808.0f && f < 9223372036854775808.0f) ? (uint32_t)(uint64_t)(int64_t)f : 0u;}
+TERRA_HD uint32_t d2u_x86(double d) {return (d > -9223372036854775808.0 && d < 9223372036854775808.0) ? (uint32_t)(uint64_t)(int64_t)d : 0u;}
 
 // do_line_clip (src/Math3d.cpp:1029-1086) with get_region (src/inlines.h:522-528): shared by the mesh shadows, the line queries and the terrain view, whose
 // check_line_clip (get_line_clip, src/Math3d.cpp:1037-1052) is the same function without the two updates of the end points

@@ -2,9 +2,8 @@
 // shader calls, tree_cont_t::draw_branches_and_leaves (src/Tree.cpp:312-368), tree::draw_leaves_top (:993-1052), tree::draw_branches_top (:948-990),
 // tree::is_visible_to_camera (:858-861), tree::calc_size_scale (:919-928), tree_data_t::get_size_scale_mult (:930), the counts of tree_data_t::draw_leaves
 // (:1182-1188) and draw_branches (:1128-1140), tree_cont_t::calc_bcube (:2458-2461) with tree::add_bounds_to_bcube (:862-865), get_draw_tile_dist
-// (src/tiled_mesh.cpp:117), InvSqrt (src/inlines.h:39-50), pos_dir_up::cube_visible_likely (src/3DWorld.h:724), cube_t::get_cube_center, is_zero_area, is_all_zeros,
-// assign_or_union_with_cube (src/3DWorld.h:491,506-527,602) and closest_dist_less_than (src/csg.cpp:247).  The sphere test is terra_terrainview.hpp's
-// view_sphere_visible, cube_visible and point_visible_test terra_grassview.hpp's.
+// (src/tiled_mesh.cpp:117) and cube_t::is_zero_area (src/3DWorld.h:491-527).  The sphere and cube tests (cube_visible_likely, closest_dist_less_than), InvSqrt
+// and the box unions are terra_view.hpp's, unsigned(double) terra_common.hpp's d2u_x86.
 //
 // Tiled-terrain mode throughout: sphere_in_camera_view(.., 0 or 2) is sphere_visible_test alone (src/visibility.cpp:338-339), so ztop / czmax are not read;
 // wind_enabled and leaf_dynamic_en are 0; rot_angle, the world_space_offset uniform, bcolor, gen_leaf_color and update_leaf_cobj_color stay with the engine.
@@ -15,7 +14,7 @@
 // One deviation: the billboard lists are ordered by tree_id and, within an id, by the order in which the reference adds the entries.  tree_lod_render_t::finalize
 // sorts all tiles' entries with a comparison that looks at the tree_data_t pointer alone, so its order inside one tree's run is whatever introsort leaves.
 #pragma once
-#include "terra_terrainview.hpp"
+#include "terra_view.hpp"
 #include "terra_decidplace.hpp"
 
 namespace terra {
@@ -62,22 +61,11 @@ TERRA_HD bool decid_view_args_finite(decid_view_args_pod_t const &a) {
 	return isfinite(a.behind_sphere_mult) && isfinite(a.zoom_f) && isfinite(a.lod_scales[0]) && isfinite(a.lod_scales[1]) && isfinite(a.lod_scales[2]) && isfinite(a.lod_scales[3]);
 }
 
-// double -> unsigned as the reference binary converts it (cvttsd2si to 64 bits, the low word): NaN and values beyond the 64-bit range give 0 (f2u_x86's double form)
-TERRA_HD uint32_t d2u_x86(double d) {return (d > -9223372036854775808.0 && d < 9223372036854775808.0) ? (uint32_t)(uint64_t)(int64_t)d : 0u;}
-// InvSqrt (src/inlines.h:39-50): the bit trick with one iteration
-TERRA_HD float inv_sqrt_ref(float x) {
-	int32_t i; memcpy(&i, &x, 4);
-	i = (int32_t)(0x5f3759dfu - (uint32_t)(i >> 1));
-	float y; memcpy(&y, &i, 4);
-	return y*(1.5f - 0.5f*x*y*y);
-}
-
 // ---- a record with its table entry.  false: dropped (tree_id outside the table, or the entry is not GENERATED): not drawn, not in all_bcube
 TERRA_HD bool decid_view_valid(uint32_t num_data, decid_tree_data_pod_t const *data, decid_place_pod_t const &r) {
 	return r.tree_id >= 0 && (uint32_t)r.tree_id < num_data && (data[r.tree_id].flags & DCV_GENERATED) != 0;
 }
 TERRA_HD bool decid_view_valid(decid_view_consts_t const &c, decid_tree_data_pod_t const *data, decid_place_pod_t const &r) {return decid_view_valid(c.num_data, data, r);}
-TERRA_HD bool decid_view_all_zeros(float const d[6]) {return d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f && d[3] == 0.0f && d[4] == 0.0f && d[5] == 0.0f;}
 // add_bounds_to_bcube's two boxes: branches_bcube + tree_center and leaves_bcube + tree_center (cube_t::operator+ adds the point to both bounds)
 TERRA_HD void decid_view_bounds(decid_tree_data_pod_t const &td, float const pos[3], float b[6], float l[6]) {
 	for (int k = 0; k < 6; ++k) {b[k] = td.branches_bcube[k] + pos[k >> 1]; l[k] = td.leaves_bcube[k] + pos[k >> 1];}
@@ -93,7 +81,7 @@ TERRA_HD void decid_view_union_init(decid_view_union_t &u) {
 	u.first = 0xFFFFFFFFu; u.last_zero = 0u;
 }
 TERRA_HD void decid_view_union_add(decid_view_union_t &u, uint32_t i, float const b[6], float const l[6]) {
-	bool const bz = decid_view_all_zeros(b), lz = decid_view_all_zeros(l);
+	bool const bz = box_all_zeros(b), lz = box_all_zeros(l);
 	if (!bz) {for (int k = 0; k < 6; k += 2) {u.b[k] = min_std(u.b[k], b[k]); u.b[k + 1] = max_std(u.b[k + 1], b[k + 1]);}}
 	if (!lz) {for (int k = 0; k < 6; k += 2) {u.l[k] = min_std(u.l[k], l[k]); u.l[k + 1] = max_std(u.l[k + 1], l[k + 1]);}}
 	else {u.last_zero = (u.last_zero < i + 1u) ? i + 1u : u.last_zero;}
@@ -129,7 +117,7 @@ TERRA_HD decid_view_tile_t decid_view_tile(decid_view_consts_t const &c, float c
 	o.flags |= DCV_TILE_DRAWN | (c.leaves ? (uint32_t)DCV_TILE_LEAVES : 0u) | (c.branches ? (uint32_t)DCV_TILE_BRANCHES : 0u);
 	if (c.leaves && !c.shadow) { // direct draw: !all_bcube.is_all_zeros() && !all_bcube.closest_dist_less_than(local_camera, 1.0*(X_SCENE_SIZE + Y_SCENE_SIZE))
 		float const d[3][2] = {{bc[0], bc[1]}, {bc[2], bc[3]}, {bc[4], bc[5]}};
-		bool const direct = !decid_view_all_zeros(bc) && !(view_closest_dist_sq(d, c.lcx, c.lcy, c.lcz) < c.scene_sum*c.scene_sum);
+		bool const direct = !box_all_zeros(bc) && !view_closest_dist_less_than(d, c.lcx, c.lcy, c.lcz, c.scene_sum);
 		o.sorted = direct ? 0 : 1;
 	}
 	if (o.sorted) {o.flags |= DCV_TILE_SORTED;}
@@ -151,10 +139,9 @@ TERRA_HD bool decid_view_not_visible(decid_view_consts_t const &c, decid_tree_da
 }
 // camera_pdu.cube_visible_likely(box + tree_xlate)
 TERRA_HD bool decid_view_cube_likely(decid_view_consts_t const &c, float const box[6], decid_view_tree_t const &g) {
-	if (!c.v.valid) return true;
+	if (!c.v.valid) return true; // an invalid view reads no box
 	float const d[3][2] = {{box[0] + g.tx, box[1] + g.tx}, {box[2] + g.ty, box[3] + g.ty}, {box[4] + g.tz, box[5] + g.tz}};
-	if (view_point_visible(c.v, 0.5f*(d[0][0] + d[0][1]), 0.5f*(d[1][0] + d[1][1]), 0.5f*(d[2][0] + d[2][1]))) return true; // get_cube_center()
-	return view_cube_visible(c.v, d);
+	return view_cube_visible_likely(c.v, d);
 }
 // calc_size_scale(draw_pos) (:919-928)
 TERRA_HD float decid_view_size_scale(decid_view_consts_t const &c, decid_tree_data_pod_t const &td, decid_view_tree_t const &g) {

@@ -8,6 +8,7 @@
 // Citations are relative to the 3DWorld reference tree.
 #pragma once
 #include "terra_common.hpp"
+#include "terra_view.hpp"
 #include "terra_noise.hpp"
 #include "terra_erosion.hpp"
 #include "terra_landscape.hpp"
@@ -255,7 +256,6 @@ struct line_hit_pod_t {float t; int32_t tile, xpos, ypos; float p[3]; uint32_t h
 struct line_query_consts_t {float xss, yss, DX_VAL, DY_VAL, DX_VAL_INV, DY_VAL_INV; int S, dxoff, dyoff;};
 struct alignas(16) line_box_t {float d[3][2]; int32_t x1, y1;}; // a tile's get_mesh_bcube() and its first mesh cell
 static_assert(sizeof(line_box_t) == 32, "line_box_t: two 16-byte loads");
-TERRA_HD int d2i_x86(double v) {return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;}
 TERRA_HD int add_wrap(int a, int b) {return (int)((uint32_t)a + (uint32_t)b);}
 TERRA_HD int sub_wrap(int a, int b) {return (int)((uint32_t)a - (uint32_t)b);}
 TERRA_HD int abs_x86(int v) {return (v < 0) ? (int)(0u - (uint32_t)v) : v;} // abs(INT_MIN) == INT_MIN
@@ -3641,7 +3641,7 @@ template<class BE> struct terra_engine {
 				float d[6];
 				if (!tree_view_bounds(rec, d)) continue;
 				if (!any) {for (int k = 0; k < 6; ++k) {bc[k] = d[k];} any = true;}
-				else {for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], d[k]); bc[k + 1] = max_std(bc[k + 1], d[k + 1]);}}
+				else {box_union(bc, d);}
 			}
 			for (int k = 0; k < 6; ++k) {d_bcube[t*6 + k] = bc[k];}
 			if (nvalid == 0) { // skipped, or pine_trees.empty() (:1468)
@@ -3812,11 +3812,8 @@ template<class BE> struct terra_engine {
 				++nvalid;
 				float b[6], l[6];
 				decid_view_bounds(d_data[recs[j].tree_id], recs[j].pos, b, l);
-				if (!decid_view_all_zeros(b)) { // assign_or_union_with_cube
-					if (decid_view_all_zeros(bc)) {for (int k = 0; k < 6; ++k) {bc[k] = b[k];}}
-					else {for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], b[k]); bc[k + 1] = max_std(bc[k + 1], b[k + 1]);}}
-				}
-				for (int k = 0; k < 6; k += 2) {bc[k] = min_std(bc[k], l[k]); bc[k + 1] = max_std(bc[k + 1], l[k + 1]);} // union_with_cube
+				box_assign_or_union(bc, b);
+				box_union(bc, l);
 			}
 			for (int k = 0; k < 6; ++k) {d_bcube[t*6 + k] = bc[k];}
 			decid_view_tile_pod_t out; out.flags = 0u; out.num_trees = nvalid; out.leaf_written = out.branch_written = out.leaf_bb_written = out.branch_bb_written = out.pad[0] = out.pad[1] = 0u;

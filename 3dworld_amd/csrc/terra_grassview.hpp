@@ -1,17 +1,16 @@
 // terra_grassview.hpp -- the grass draw lists of a tile for a camera: tile_t::draw_grass (src/tiled_mesh.cpp:1607-1664) without its GL calls, the per-tile filters of
 // its caller tile_draw_t::draw_grass (:3420-3425), tile_t::get_min_dist_to_pt (:354-364, mesh_only), get_rel_dist_to_camera / get_dist_to_camera_in_tiles
-// (src/tiled_mesh.h:320-332), get_norm_not_normalized (:281-283), the thresholds (src/tiled_mesh.cpp:27-29,118-120; src/tiled_mesh.h:24,93-94), and the view
-// frustum pos_dir_up (src/visibility.cpp:67-103,141-174,186-196) with cube_t::closest_pt / closest_pt_dist_sq (src/3DWorld.h:591,636-641; src/csg.cpp:244-246),
-// dist_less_than (src/inlines.h:176-192) and orthogonalize_dir (src/inlines.h:265-268).
+// (src/tiled_mesh.h:320-332), get_norm_not_normalized (:281-283) and the thresholds (src/tiled_mesh.cpp:27-29,118-120; src/tiled_mesh.h:24,93-94).  The view
+// frustum (view_pod_t, the point and cube tests, closest_pt_dist_sq) is terra_view.hpp's, unsigned(float) terra_common.hpp's f2u_x86.
 //
 // The bodies are shared by the driver's simple form (one logical thread per tile, the reference's loops) and by k_grass_view (terra_kernels.hpp).  Every operand
 // carries the type the reference statement gives it; where the C++ source promotes to double the promotion is written out; dot products are summed in the
 // reference's order (the library is built without contraction).
 //
-// The tests of a block are pure: where the reference leaves a loop early (check_clip_plane's first passing point, the near / far loop of pt_set_visible, the
-// `&& back_facing` of the back-face loops) the bodies here evaluate every term and combine them -- the same booleans, no branch per term.
+// The tests of a block are pure: where the reference leaves a loop early (the `&& back_facing` of the back-face loops) the bodies here evaluate every term and
+// combine them -- the same booleans, no branch per term.
 #pragma once
-#include "terra_common.hpp"
+#include "terra_view.hpp"
 
 namespace terra {
 
@@ -20,8 +19,6 @@ constexpr uint32_t GRASS_VIEW_BLOCK   = 4;       // GRASS_BLOCK_SZ (src/grass.h:
 constexpr uint32_t GRASS_VIEW_DROPPED = 0xFFFFu; // the key of a block that is not drawn; a kept block's key is lod*num_rnd_grass_blocks + bix
 constexpr uint32_t GRASS_VIEW_MAX_RND = 4096;    // 6*4096 keys fit 16 bits beside GRASS_VIEW_DROPPED; bix fits the aux word's 13 bits
 constexpr uint8_t  GRASS_VIEW_NO_PASS = 255;     // the pass byte of a tile that draws nothing
-
-struct view_pod_t {float pos[3], dir[3], upv[3], cp[3]; float sterm, x_sterm, near_, far_; int32_t valid;}; // terra_view: pos_dir_up's pos, dir, upv_, cp, ...
 
 // ---- the constants block: what draw_grass computes before its loops from globals alone
 struct grass_view_consts_t {
@@ -50,50 +47,6 @@ inline grass_view_consts_t grass_view_consts(view_pod_t const &v, float xss, flo
 	c.lod_scale = GRASS_LOD_SCALE/(tt*c.scaled_tile_radius);
 	c.adj_z = v.pos[2] + (float)(2.0*(double)grass_length);                                // camera + point(0.0, 0.0, 2.0*grass_length): the double narrows in point()
 	return c;
-}
-
-// float -> unsigned as the reference binary converts it (cvttss2si to 64 bits, the low word): NaN and values beyond the 64-bit range give 0
-TERRA_HD uint32_t f2u_x86(float f) {return (f > -9223372036854775808.0f && f < 9223372036854775808.0f) ? (uint32_t)(uint64_t)(int64_t)f : 0u;}
-
-TERRA_HD float view_dot(float const a[3], float x, float y, float z) {return a[0]*x + a[1]*y + a[2]*z;} // dot_product (src/inlines.h:220-222)
-
-// pos_dir_up::point_visible_test (src/visibility.cpp:94-103)
-TERRA_HD bool view_point_visible(view_pod_t const &v, float px, float py, float pz) {
-	if (!v.valid) return true;
-	float const x = px - v.pos[0], y = py - v.pos[1], z = pz - v.pos[2]; // vector3d const pv(pos_, pos)
-	if (view_dot(v.dir, x, y, z) < 0.0f) return false;
-	float const dist = sqrtf(x*x + y*y + z*z);
-	if (fabsf(view_dot(v.upv, x, y, z)) > dist*v.sterm) return false;
-	if (fabsf(view_dot(v.cp, x, y, z)) > dist*v.x_sterm) return false;
-	return dist > v.near_ && dist < v.far_;
-}
-// pos_dir_up::cube_completely_visible (:186-196)
-TERRA_HD bool view_cube_completely_visible(view_pod_t const &v, float const d[3][2]) {
-	if (!v.valid) return true;
-	bool all = true;
-	for (int k = 0; k < 8; ++k) {all = all && view_point_visible(v, d[0][k >> 2], d[1][(k >> 1) & 1], d[2][k & 1]);}
-	return all;
-}
-// cube_t::closest_pt_dist_sq(pos) = p2p_dist_sq(closest_pt(pos), pos), clamp_pt's min(d[1], max(d[0], p))
-TERRA_HD float view_closest_dist_sq(float const d[3][2], float px, float py, float pz) {
-	float const cx = min_std(d[0][1], max_std(d[0][0], px)), cy = min_std(d[1][1], max_std(d[1][0], py)), cz = min_std(d[2][1], max_std(d[2][0], pz));
-	return (cx - px)*(cx - px) + (cy - py)*(cy - py) + (cz - pz)*(cz - pz);
-}
-// pos_dir_up::cube_visible (:165-174) with pt_set_visible<8> and check_clip_plane<8> (:141-163)
-TERRA_HD bool view_cube_visible(view_pod_t const &v, float const d[3][2]) {
-	if (!v.valid) return true;
-	float const aau = v.sterm*v.sterm, aac = v.x_sterm*v.x_sterm;
-	bool u0 = false, u1 = false, c0 = false, c1 = false, npass = false, fpass = false;
-	for (int k = 0; k < 8; ++k) {
-		float const x = d[0][k >> 2] - v.pos[0], y = d[1][(k >> 1) & 1] - v.pos[1], z = d[2][k & 1] - v.pos[2];
-		float const msq = x*x + y*y + z*z, du = view_dot(v.upv, x, y, z), dc = view_dot(v.cp, x, y, z), dd = view_dot(v.dir, x, y, z);
-		bool const iu = du*du <= aau*msq, ic = dc*dc <= aac*msq;
-		u0 = u0 || du <= 0.0f || iu; u1 = u1 || -du <= 0.0f || iu; // (d ? -dp : dp) <= 0.0 || dp*dp <= aa*pv.mag_sq()
-		c0 = c0 || dc <= 0.0f || ic; c1 = c1 || -dc <= 0.0f || ic;
-		npass = npass || dd > v.near_; fpass = fpass || dd < v.far_;
-	}
-	if (!(u0 && u1 && c0 && c1 && npass && fpass)) return false;
-	return view_closest_dist_sq(d, v.pos[0], v.pos[1], v.pos[2]) < v.far_*v.far_; // dist_less_than(pos, c.closest_pt(pos), far_)
 }
 
 // ---- the tile test: what decides for a whole tile (has_grass() is the caller's: it reads the blocks)
@@ -167,36 +120,5 @@ TERRA_HD uint32_t grass_view_block(grass_view_consts_t const &c, grass_view_tile
 }
 // the aux word of a kept block: bits 0-15 y*dim + x, 16-18 the LOD, 19-31 bix
 TERRA_HD uint32_t grass_view_aux(grass_view_consts_t const &c, uint32_t block, uint32_t key) {return block | ((key / c.nrnd) << 16) | ((key % c.nrnd) << 19);}
-
-// ---- pos_dir_up's constructor (:67-85) and orthogonalize_up_dir (:87-92) with the C library's tanf / sinf / atanf.  false where the constructor asserts.
-inline bool view_make(float const pos[3], float const dir[3], float const up[3], float angle, float aspect, float near_, float far_, view_pod_t &o) {
-	if (!(near_ >= 0.0f && far_ > 0.0f && far_ > near_)) return false;
-	if (dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f) return false; // assert(dir != zero_vector)
-	double const A = (double)aspect;
-	float const tterm = tanf(angle), sterm = sinf(angle);
-	float x_sterm;
-	if (A == 1.0) {x_sterm = sterm;}
-	else {
-		if (!(tterm > 0.0f)) return false; // angle < 90
-		float atan_val = atanf((float)(A*(double)tterm));
-		if (atan_val < 0.0f) {atan_val += PI_F;}
-		x_sterm = (atan_val/angle)*sterm;
-	}
-	for (int k = 0; k < 3; ++k) {o.pos[k] = pos[k]; o.dir[k] = dir[k];}
-	// orthogonalize_dir(upv, dir, upv_, 1): cross_product(dir, cross_product(upv, dir)), normalized (pointT::normalize, src/3DWorld.h:273-279)
-	float const tx = up[1]*dir[2] - up[2]*dir[1], ty = up[2]*dir[0] - up[0]*dir[2], tz = up[0]*dir[1] - up[1]*dir[0];
-	float ux = dir[1]*tz - dir[2]*ty, uy = dir[2]*tx - dir[0]*tz, uz = dir[0]*ty - dir[1]*tx;
-	float const mag = sqrtf(ux*ux + uy*uy + uz*uz);
-	if (mag >= 1.0E-12f) {float const m = (float)(1.0/(double)mag); ux *= m; uy *= m; uz *= m;}
-	o.upv[0] = ux; o.upv[1] = uy; o.upv[2] = uz;
-	o.cp[0] = dir[1]*uz - dir[2]*uy; o.cp[1] = dir[2]*ux - dir[0]*uz; o.cp[2] = dir[0]*uy - dir[1]*ux; // cross_product(dir, upv_, cp)
-	o.sterm = sterm; o.x_sterm = x_sterm; o.near_ = near_; o.far_ = far_; o.valid = 1;
-	return true;
-}
-TERRA_HD bool view_finite(view_pod_t const &v) {
-	bool ok = isfinite(v.sterm) && isfinite(v.x_sterm) && isfinite(v.near_) && isfinite(v.far_);
-	for (int k = 0; k < 3; ++k) {ok = ok && isfinite(v.pos[k]) && isfinite(v.dir[k]) && isfinite(v.upv[k]) && isfinite(v.cp[k]);}
-	return ok;
-}
 
 } // namespace terra

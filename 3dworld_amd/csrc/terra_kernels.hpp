@@ -2572,8 +2572,7 @@ __global__ __launch_bounds__(TRV_THREADS) void k_tree_view(tree_view_consts_t c,
 		float d[6];
 		if (!tree_view_bounds(rec, d)) continue;
 		++nb;
-#pragma unroll
-		for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], d[k]); box[k + 1] = max_std(box[k + 1], d[k + 1]);}
+		box_union(box, d);
 	}
 	for (int off = 32; off; off >>= 1) {
 		nv += __shfl_xor(nv, off); np += __shfl_xor(np, off); nm += __shfl_xor(nm, off); nb += __shfl_xor(nb, off);
@@ -2997,8 +2996,7 @@ __device__ __forceinline__ coll_result_t coll_query_wave(collide_consts_t const 
 			float d[6];
 			if (!tree_view_bounds(rec, d)) continue;
 			++nb;
-#pragma unroll
-			for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], d[k]); box[k + 1] = max_std(box[k + 1], d[k + 1]);}
+			box_union(box, d);
 		}
 		for (int off = 32; off; off >>= 1) {
 			nv += __shfl_xor(nv, off); nb += __shfl_xor(nb, off);

@@ -5,7 +5,7 @@
 // scale_exp = 8.0, src/shape_line3d.h:22), skip_uw_draw and get_pt_line_thresh (:61-74), the get_bsphere_radius() overrides (src/scenery.h:120,132,166,199,221),
 // get_scenery_thresh / get_scenery_dist_scale (src/tiled_mesh.h:333-334), get_tile_width (:93), get_smap_ndiv (src/shadow_map.cpp:60-64), distance_to_camera
 // (src/inlines.h:431) and dot_product_ptv (:227).  The records are terra_sceneryplace.hpp's, the tile's centre and get_dist_to_camera_in_tiles(0)
-// terra_terrainview.hpp's (terrain_view_geom, terrain_view_dist_in_tiles), the sphere test its view_sphere_visible, int(double) terra_treeview.hpp's tree_view_d2i.
+// terra_terrainview.hpp's (terrain_view_geom, terrain_view_dist_in_tiles), the sphere test terra_view.hpp's, int(double) and int(float) terra_common.hpp's.
 //
 // In tiled-terrain mode check_visible is camera_pdu.sphere_visible_test alone, in the shadow pass too, and sphere_in_camera_view(.., 2) (draw_berries) is the same
 // test (src/visibility.cpp:338-339).  next_frame, burn_amt, is_shadowed and the colours stay with the engine.
@@ -13,8 +13,8 @@
 // The bodies are shared by the driver's simple form (one logical thread per tile) and by k_scenery_view (terra_kernels.hpp).  Every operand carries the type the
 // reference statement gives it; where the C++ source promotes to double the promotion is written out; sums run in the reference's order.
 #pragma once
+#include "terra_view.hpp"
 #include "terra_terrainview.hpp"
-#include "terra_treeview.hpp"
 #include "terra_sceneryplace.hpp"
 #include "terra_powf.hpp"
 
@@ -56,7 +56,7 @@ inline scenery_view_consts_t scenery_view_consts(view_pod_t const &v, scenery_vi
 	c.thresh = a.reflection_pass ? SCENERY_THRESH_REF : SCENERY_THRESH;
 	c.scale_val = c.thresh*(xss + yss);
 	c.pt_thresh = (float)((double)PT_LINE_THRESH*(double)a.zoom_f);                         // PT_LINE_THRESH*(do_zoom ? ZOOM_FACTOR : 1.0)
-	c.sscale = (float)tree_view_d2i((double)a.zoom_f*(double)a.window_width);
+	c.sscale = (float)d2i_x86((double)a.zoom_f*(double)a.window_width);
 	c.smap_pw = a.smap_pixel_width;
 	c.shadow = a.shadow_pass ? 1 : 0; c.reflection = a.reflection_pass; c.uw_skip = a.uw_skip ? 1 : 0;
 	c.wood = (!c.shadow || !a.skip_small_shadow_objs) ? 1 : 0;
@@ -101,11 +101,9 @@ TERRA_HD float scv_size_scale(scenery_view_consts_t const &c, float dist) {
 }
 // get_def_smap_ndiv(radius): min(N_SPHERE_DIV, max(4, int(0.5*radius/approx_pixel_width(smap_sz))))
 TERRA_HD int scv_smap_ndiv(scenery_view_consts_t const &c, float radius) {
-	int const q = tree_view_d2i(0.5*(double)radius/(double)c.smap_pw), m = (4 < q) ? q : 4;
+	int const q = d2i_x86(0.5*(double)radius/(double)c.smap_pw), m = (4 < q) ? q : 4;
 	return (m < 32) ? m : 32;
 }
-// int(float) as the reference binary converts it (cvttss2si): NaN and values outside the int range give INT_MIN
-TERRA_HD int scv_f2i(float v) {return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;}
 // the `2*get_pt_line_thresh()*radius < dist` of the rocks and the stems
 TERRA_HD bool scv_small(scenery_view_consts_t const &c, float radius, float dist) {return !c.shadow && (2.0f*c.pt_thresh)*radius < dist;}
 
@@ -145,7 +143,7 @@ TERRA_HD scenery_view_rec_t scenery_view_record(scenery_view_consts_t const &c, 
 			break;
 		}
 		uint32_t ndiv = 0;
-		if (r.kind == SCENERY_ROCK) {ndiv = (uint32_t)scv_clamp(4, 32, c.shadow ? scv_smap_ndiv(c, radius) : scv_f2i(c.sscale*radius/dist));}
+		if (r.kind == SCENERY_ROCK) {ndiv = (uint32_t)scv_clamp(4, 32, c.shadow ? scv_smap_ndiv(c, radius) : f2i_x86(c.sscale*radius/dist));}
 		o.word = SCV_POLY | (ndiv << SCV_NDIV_SHIFT); o.size_scale = scv_size_scale(c, dist);
 		o.streams = 1u << ((r.kind == SCENERY_ROCK) ? SCV_S_ROCK : ((r.kind == SCENERY_VOXEL_ROCK) ? SCV_S_VOXEL_ROCK : SCV_S_SURFACE_ROCK));
 		break;
@@ -169,7 +167,7 @@ TERRA_HD scenery_view_rec_t scenery_view_record(scenery_view_consts_t const &c, 
 		o.dist = dist;
 		if (!c.shadow && c.pt_thresh*(radius + radius2) < dist) {o.word = SCV_LINE; o.streams = 1u << (log ? SCV_S_LN_LOG : SCV_S_LN_STUMP); break;} // draw as line
 		double const k = log ? 2.0 : 2.2;
-		int const ndiv = scv_clamp(3, 32, c.shadow ? scv_smap_ndiv(c, (float)(k*(double)radius)) : tree_view_d2i(k*(double)c.sscale*(double)radius/(double)dist));
+		int const ndiv = scv_clamp(3, 32, c.shadow ? scv_smap_ndiv(c, (float)(k*(double)radius)) : d2i_x86(k*(double)c.sscale*(double)radius/(double)dist));
 		uint32_t w = SCV_POLY | ((uint32_t)ndiv << SCV_NDIV_SHIFT);
 		if (log) {
 			if (c.shadow || !((double)dist > 0.75*(double)c.pt_thresh*(double)radius)) { // the end visible to the camera
@@ -193,7 +191,7 @@ TERRA_HD scenery_view_rec_t scenery_view_record(scenery_view_consts_t const &c, 
 		o.dist = dist;
 		if ((double)dist > 1000.0*(double)radius) break; // too far away
 		if (!scv_check_visible(c, scv_max(height, radius), radius, cx, cy, cz)) break;
-		int const ndiv = scv_clamp(3, 32, tree_view_d2i(1.0*(double)c.sscale*(double)radius/(double)dist));
+		int const ndiv = scv_clamp(3, 32, d2i_x86(1.0*(double)c.sscale*(double)radius/(double)dist));
 		o.word = SCV_POLY | ((uint32_t)ndiv << SCV_NDIV_SHIFT) | ((cam[2] < capz) ? (uint32_t)SCV_CAP_UNDERSIDE : 0u);
 		o.streams = 1u << SCV_S_MUSHROOM;
 		break;
@@ -209,7 +207,7 @@ TERRA_HD scenery_view_rec_t scenery_view_record(scenery_view_consts_t const &c, 
 			o.dist = dist;
 			if (scv_small(c, radius, dist)) {w = SCV_LINE; o.streams |= 1u << SCV_S_LN_STEM;} // draw as line
 			else {
-				int const ndiv = scv_clamp(3, 32, c.shadow ? scv_smap_ndiv(c, (float)(2.0*(double)radius)) : tree_view_d2i(2.0*(double)c.sscale*(double)radius/(double)dist));
+				int const ndiv = scv_clamp(3, 32, c.shadow ? scv_smap_ndiv(c, (float)(2.0*(double)radius)) : d2i_x86(2.0*(double)c.sscale*(double)radius/(double)dist));
 				w = SCV_POLY | ((uint32_t)ndiv << SCV_NDIV_SHIFT); o.streams |= 1u << SCV_S_STEM;
 			}
 		}
@@ -219,7 +217,7 @@ TERRA_HD scenery_view_rec_t scenery_view_record(scenery_view_consts_t const &c, 
 			o.dist = dist;
 			float const size_scale = c.pt_thresh*radius/dist;
 			if (!((double)size_scale < 1.2)) {
-				int const ndiv = scv_clamp(4, 16, tree_view_d2i(2.0*(double)size_scale));
+				int const ndiv = scv_clamp(4, 16, d2i_x86(2.0*(double)size_scale));
 				w |= SCV_BERRIES | ((uint32_t)ndiv << SCV_BERRY_NDIV_SHIFT); o.streams |= 1u << SCV_S_BERRIES;
 			}
 		}

@@ -2,21 +2,19 @@
 // occluder_cubes_t's constructor (:2834-2842) and calc_cube_top_points (:2823-2832), tile_t::get_lod_level (:1910-1932), the crack look-ups of tile_t::draw
 // (:2059-2074) with crack_ibuf_t::get_index (:2020-2023), tile_t::use_as_occluder (:3801-3803), get_bsphere_radius_inc_water (:366-368), get_center / get_bcube /
 // get_mesh_sub_bcube / get_sub_bcube / get_rel_dist_to_camera / rel_dist_to_camera_xy_lt / is_visible (src/tiled_mesh.h:229-252,320-332), the constants
-// (src/tiled_mesh.cpp:23,33; src/tiled_mesh.h:24-25,32,93-94), pos_dir_up::sphere_visible_test and sphere_and_cube_visible_test (src/visibility.cpp:119-128,
-// 215-219), behind_sphere_mult (:83), cube_t::get_cube_center (src/3DWorld.h:602-604), dist_xy_less_than / p2p_dist_xy (src/inlines.h:183-195) and
-// check_line_clip (src/inlines.h:509-512) = get_line_clip (src/Math3d.cpp:1037-1052).
+// (src/tiled_mesh.cpp:23,33; src/tiled_mesh.h:24-25,32,93-94), cube_t::get_cube_center (src/3DWorld.h:602-604), dist_xy_less_than / p2p_dist_xy
+// (src/inlines.h:183-195) and check_line_clip (src/inlines.h:509-512) = get_line_clip (src/Math3d.cpp:1037-1052).
 //
 // The bodies are shared by the driver's simple form (one logical thread per tile, the reference's loops) and by the k_terrain_view_* kernels
-// (terra_kernels.hpp).  cube_visible is terra_grassview.hpp's view_cube_visible, the line clip terra_common.hpp's shadow_line_clip.  Every operand carries the type
-// the reference statement gives it; where the C++ source promotes to double the promotion is written out; sums run in the reference's order (the library is built
+// (terra_kernels.hpp).  The sphere and cube tests and behind_sphere_mult are terra_view.hpp's, the line clip terra_common.hpp's shadow_line_clip.  Every operand
+// carries the type the reference statement gives it; where the C++ source promotes to double the promotion is written out; sums run in the reference's order (the library is built
 // without contraction).
 //
 // The occlusion loops' early exits (`&& !intersected`, `&& !sub_tile_occluded`, `&& sub_tile_occluded`, the `break` of :2904) only shortcut booleans: the result of
 // a tile is "for every sub-box t there is an occluder o, not the tile itself, with any of the tile's four top points clipped by o's mesh box, the sub-box's centre
 // clipped by it, and a column s of o that is not zeroed and clips all four top points of the sub-box".  It does not depend on the order of the occluders.
 #pragma once
-#include "terra_common.hpp"
-#include "terra_grassview.hpp"
+#include "terra_view.hpp"
 #include "../../include/terra.h"
 
 namespace terra {
@@ -49,14 +47,6 @@ inline terrain_view_consts_t terrain_view_consts(view_pod_t const &v, terrain_vi
 	c.water_enabled = a.water_enabled ? 1 : 0; c.check_occlusion = a.check_occlusion ? 1 : 0; c.reflection_pass = a.reflection_pass;
 	return c;
 }
-// behind_sphere_mult = max(1.0, A*A)*max(1.0, 2.0f/((double)tterm*tterm*(1.0 + A*A))) (src/visibility.cpp:83): A is a double member, tterm the float tanf(angle)
-inline float view_behind_sphere_mult(float angle, float aspect) {
-	double const A = (double)aspect;
-	float const tterm = tanf(angle);
-	double const a = (1.0 < A*A) ? A*A : 1.0, q = (double)2.0f/(((double)tterm*(double)tterm)*(1.0 + A*A)), b = (1.0 < q) ? q : 1.0; // std::max(a, b) = (a < b) ? b : a
-	return (float)(a*b);
-}
-
 // ---- log2 of a positive normal double in plain double arithmetic, the same on the host and on the device (get_lod_level divides by -log2(2.0*min_normal_z),
 // :1924, and the device library's log2 is not the C library's).  x = 2^e*m with m in (sqrt(1/2), sqrt(2)]; f = m - 1, s = f/(2 + f), z = s*s;
 // log(m) = 2*atanh(s) = f - hfsq + s*(hfsq + R), hfsq = f*f/2, R = z*(2/3 + z*(2/5 + ...)) (z <= 0.0295: twelve terms reach below 2^-60); the head f - hfsq is
@@ -82,6 +72,8 @@ TERRA_HD double terrain_view_log2(double x) {
 	val_lo += (y - w) + val_hi;
 	return val_lo + w;
 }
+// the steep-slope statement of get_lod_level (:1924): dist /= -log2(2.0*min_normal_z)
+TERRA_HD float terrain_view_steep_dist(float dist, float min_normal_z) {return (float)((double)dist/-terrain_view_log2(2.0*(double)min_normal_z));}
 
 // ---- a tile's boxes and centre
 struct terrain_view_geom_t {
@@ -126,23 +118,10 @@ TERRA_HD float terrain_view_dist_in_tiles(terrain_view_consts_t const &c, terrai
 	float const d = sqrtf((cam[0] - g.cx)*(cam[0] - g.cx) + (cam[1] - g.cy)*(cam[1] - g.cy) + (cam[2] - g.cz)*(cam[2] - g.cz));
 	return (max_std(0.0f, d - radius)/c.scaled_tile_radius)*(float)6;
 }
-// pos_dir_up::sphere_visible_test
-TERRA_HD bool view_sphere_visible(view_pod_t const &v, float behind_sphere_mult, float px, float py, float pz, float radius) {
-	if (!v.valid) return radius >= 0.0f;
-	float const x = px - v.pos[0], y = py - v.pos[1], z = pz - v.pos[2]; // vector3d const pv(pos_, pos)
-	float const msq = x*x + y*y + z*z;
-	if (view_dot(v.dir, x, y, z) < 0.0f) return radius > 0.0f && msq < radius*radius*behind_sphere_mult; // sphere behind
-	float const dist = sqrtf(msq);
-	if (fabsf(view_dot(v.upv, x, y, z)) > dist*v.sterm + radius) return false;
-	if (fabsf(view_dot(v.cp, x, y, z)) > dist*v.x_sterm + radius) return false;
-	return (dist + radius) > v.near_ && (dist - radius) < v.far_;
-}
 // tile_t::is_visible(): sphere_and_cube_visible_test(get_center(), get_bsphere_radius_inc_water(), get_bcube())
 TERRA_HD bool terrain_view_visible(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float mzmin, float mzmax, float radius) {
 	float const r = (c.water_enabled && mzmax < c.water_plane_z) ? max_std(radius, c.water_plane_z - 0.5f*(mzmin + mzmax)) : radius;
-	if (!view_sphere_visible(c.v, c.behind_sphere_mult, g.cx, g.cy, g.cz, r)) return false; // none of the sphere is visible
-	if (view_sphere_visible(c.v, c.behind_sphere_mult, g.cx, g.cy, g.cz, -r)) return true;  // all of the sphere is visible
-	return view_cube_visible(c.v, g.bc);
+	return view_sphere_and_cube_visible(c.v, c.behind_sphere_mult, g.cx, g.cy, g.cz, r, g.bc);
 }
 // rel_dist_to_camera_xy_lt(OCCLUDER_DIST): the distance half of use_as_occluder()
 TERRA_HD bool terrain_view_occluder_dist(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float radius) {
@@ -161,7 +140,7 @@ TERRA_HD uint32_t terrain_view_lod(terrain_view_consts_t const &c, float mzmin, 
 		if ((double)min_normal_z > 0.9) {
 			if (!c.water_enabled || mzmax < c.water_plane_z || mzmin > c.water_plane_z) {dist = (float)((double)dist*(((double)min_normal_z > 0.95) ? 4.0 : 2.0));}
 		}
-		else if ((double)min_normal_z < 0.25) {dist = (float)((double)dist/-terrain_view_log2(2.0*(double)min_normal_z));}
+		else if ((double)min_normal_z < 0.25) {dist = terrain_view_steep_dist(dist, min_normal_z);}
 	}
 	double const thresh = c.reflection_pass ? 1.8 : 2.0;
 	while ((double)dist > thresh && lod_level + 1u < TERRAIN_VIEW_LODS && ((uint32_t)c.S >> (lod_level + 1u)) >= 4u) {

@@ -6,7 +6,7 @@
 // small_tree::draw_trunk (:1081-1102, down to nsides), get_trunk_cylin (:767-777) with get_tree_z_bottom / get_default_tree_depth (src/Tree.cpp:209-214, the
 // tiled-terrain branch), get_xy_radius / get_trunk_bsphere_radius (src/small_tree.h:77-78), stt[] (src/sm_tree.cpp:46-53) and the constants (src/tiled_mesh.h:
 // 27-29; src/sm_tree.cpp:14; src/3DWorld.h:104; src/tree_3dw.h:10).  The size of a record is terra_treeao.hpp's small_tree_size, the tile's centre and box
-// terra_terrainview.hpp's, the sphere test its view_sphere_visible, cube_visible and point_visible_test terra_grassview.hpp's.
+// terra_terrainview.hpp's, the sphere, cube and point tests terra_view.hpp's, int(double) terra_common.hpp's d2i_x86.
 //
 // sphere_in_camera_view(.., 2) (are_leaves_visible's palm branch) is sphere_visible_test alone in tiled-terrain mode (src/visibility.cpp:338-339).
 //
@@ -17,6 +17,7 @@
 // (tree_inst_t::operator<), so its order inside an id is whatever the library's introsort leaves; the instanced draw per id does not depend on it.  The
 // front-to-back list of the tile that holds the camera is ordered by std::pair's operator< on (p2p_dist_sq, index), a total order: no deviation there.
 #pragma once
+#include "terra_view.hpp"
 #include "terra_terrainview.hpp"
 #include "terra_treeao.hpp"
 
@@ -67,8 +68,6 @@ TERRA_HD bool tree_view_args_ok(tree_view_args_pod_t const &a) {
 TERRA_HD float stt_w2(int type) {return (type == 1 || type == 2) ? 0.13f : ((type == T_PALM) ? 0.03f : 0.0f);}
 TERRA_HD float stt_ws(int type) {return (type == T_PINE) ? 0.14f : ((type == T_PALM) ? 0.12f : ((type == T_SH_PINE) ? 0.08f : 0.15f));}
 TERRA_HD float stt_ss(int type) {return (type == T_PINE || type == T_SH_PINE) ? 0.4f : ((type == 2) ? 0.7f : ((type == T_PALM) ? 0.6f : 0.8f));}
-// int(double) as the reference binary converts it (cvttsd2si): NaN and values outside the int range give INT_MIN
-TERRA_HD int tree_view_d2i(double v) {return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : (int)0x80000000u;}
 
 // ---- a record as the small_tree constructors leave it: type, size, pos and trunk_cylin; rotated: r_angle != 0 (only through the caller's override)
 struct tree_view_rec_t {int type; float height, width; float pos[3], p1[3], p2[3], r1, r2, dir[3]; int rotated;};
@@ -106,7 +105,7 @@ TERRA_HD float tree_view_xy_radius(tree_view_rec_t const &r) {
 TERRA_HD bool tree_view_bounds(tree_view_rec_t const &r, float d[6]) {
 	float const cx = 0.5f*(r.p1[0] + r.p2[0]), cy = 0.5f*(r.p1[1] + r.p2[1]), xyr = tree_view_xy_radius(r);
 	d[0] = cx - xyr; d[1] = cx + xyr; d[2] = cy - xyr; d[3] = cy + xyr; d[4] = r.p1[2]; d[5] = r.p2[2];
-	return !(d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f && d[3] == 0.0f && d[4] == 0.0f && d[5] == 0.0f);
+	return !box_all_zeros(d);
 }
 // are_leaves_visible(xlate); xlate = (offx, offy, 0).  (Written out per component: indexed locals would live in scratch memory on the device.)
 TERRA_HD bool tree_view_leaves_visible(tree_view_consts_t const &c, tree_view_rec_t const &r) {
@@ -152,7 +151,7 @@ TERRA_HD uint8_t tree_view_trunk(tree_view_consts_t const &c, tree_view_rec_t co
 	float const LINE_THRESH = 700.0f;
 	if (!c.shadow_pass && LINE_THRESH*c.zoom_f*(r.r1 + r.r2) < dist) return 1;
 	if (c.shadow_pass) return 4;
-	int const q = tree_view_d2i(0.25*(double)size_scale/(double)dist), lo = (TREE_VIEW_CYL_SIDES < q) ? TREE_VIEW_CYL_SIDES : ((q < TREE_VIEW_CYL_SIDES) ? q : TREE_VIEW_CYL_SIDES);
+	int const q = d2i_x86(0.25*(double)size_scale/(double)dist), lo = (TREE_VIEW_CYL_SIDES < q) ? TREE_VIEW_CYL_SIDES : ((q < TREE_VIEW_CYL_SIDES) ? q : TREE_VIEW_CYL_SIDES);
 	return (uint8_t)((4 < lo) ? lo : 4); // max(4, min(N_CYL_SIDES, int(0.25*size_scale/dist)))
 }
 

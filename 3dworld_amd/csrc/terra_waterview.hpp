@@ -5,7 +5,7 @@
 // get_cube_center (:602-604) and p2p_dist_xy (src/inlines.h:183-188).
 //
 // The bodies are shared by the driver's simple form (the reference's loop, sequential over the batch) and by the k_reflect_* / k_water_view kernels
-// (terra_kernels.hpp).  The geometry, is_visible, the line clip and cube_visible are terra_terrainview.hpp's and terra_grassview.hpp's.  Every operand carries the
+// (terra_kernels.hpp).  The geometry, is_visible and the line clip are terra_terrainview.hpp's, cube_visible terra_view.hpp's.  Every operand carries the
 // type the reference statement gives it (all of them are float here); sums run in the reference's order.
 //
 // can_have_reflection_recur is pure reachability: its result for a start tile is 1 exactly when some tile that is reachable by its steps -- every tile but the
@@ -13,6 +13,7 @@
 // dimension it was entered through, so a tile that was entered once and found nothing need not be entered again: reflect_walk keeps a visited set (the caller's)
 // and a work list instead of the call stack.  vis_ref_call never fires: every step moves one tile nearer to the camera in x or in y.
 #pragma once
+#include "terra_view.hpp"
 #include "terra_terrainview.hpp"
 
 namespace terra {

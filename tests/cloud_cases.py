@@ -8,10 +8,9 @@ import ctypes as C
 import numpy as np
 
 import cloud_model as cm
-import grass_view_model as gm
 import orclib
 import terrain_view_cases as tc
-import terrain_view_model as tm
+import view_model as vw
 
 f32 = np.float32
 ERR_ARG, ERR_STATE = -1, -3
@@ -254,9 +253,9 @@ def view_model(orc, case):
             sc.water_plane_z = f32(np.percentile([float(c.pos[2] - c.size[2]) for m in mgrs for c in m.clouds], 4))
         zc = float(mgrs[0].range[2][0])
         cam_z = zc + 4.0 if case.cam_dz == "clouds" else float(sc.zmax) * 0.5 + case.cam_dz
-        v = gm.make_view((case.cam[0], case.cam[1], cam_z), case.look["dir"], case.look["up"], case.angle, case.aspect, 0.05, case.far)
+        v = vw.make_view((case.cam[0], case.cam[1], cam_z), case.look["dir"], case.look["up"], case.angle, case.aspect, 0.05, case.far)
         v.valid = case.valid
-        a = cm.ViewArgs(tm.behind_sphere_mult(case.angle, case.aspect), case.xlate, case.max_dist)
+        a = cm.ViewArgs(vw.behind_sphere_mult(case.angle, case.aspect), case.xlate, case.max_dist)
         n = len(case.tiles)
         stats = (orclib.TileStats * n)()
         for t in range(n):  # every fourth tile's mesh lies above its clouds; every other one's mzmax asks for the exact height
@@ -319,8 +318,8 @@ def run_resident_chain(pkg, gpu, orc):
     sc, step, frames, tally = model(orc, case)
     mgrs = MODEL[case.name][4]
     configure(pkg, gpu, case)
-    v = gm.make_view((-75.0, -5.0, float(sc.zmax)), tc._unit(1.0, 0.6, 0.0), (0.0, 0.0, 1.0), 1.3, 1.5, 0.05, 500.0)
-    a = cm.ViewArgs(tm.behind_sphere_mult(1.3, 1.5), (0.5, -0.25, 0.0), 35.0)
+    v = vw.make_view((-75.0, -5.0, float(sc.zmax)), tc._unit(1.0, 0.6, 0.0), (0.0, 0.0, 1.0), 1.3, 1.5, 0.05, 500.0)
+    a = cm.ViewArgs(vw.behind_sphere_mult(1.3, 1.5), (0.5, -0.25, 0.0), 35.0)
     b = dict(z=gpu.alloc(n * Z * Z * 4), ss=gpu.alloc(n * C.sizeof(pkg.TileStats)), st=gpu.alloc(n * 88).upload(np.zeros(n * 88, np.uint8)), cl=gpu.alloc(n * cap * 32), to=gpu.alloc(4),
              sg=gpu.alloc(n * cap), li=gpu.alloc(n * cap * 24), lc=gpu.alloc(4))
     try:

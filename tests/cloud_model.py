@@ -14,7 +14,7 @@
     get_tile_width, get_xval / get_yval, p2p_dist_sq                   src/tiled_mesh.h:93; src/mesh.h:122-123; src/inlines.h:176-178
 
 Leaves from the reference's compiled code (the oracle): the draws of the Gaussian table are ref_rand_ints(rgen_seed, 123); the exact height is ref_eval_points with
-no_xyoff = 1; the generator below is pinned to ref_rand_ints / ref_rand_uniforms by test_model_alone.  sphere_visible_test is tests/terrain_view_model.py's restatement (the
+no_xyoff = 1; the generator below is pinned to ref_rand_ints / ref_rand_uniforms by test_model_alone.  sphere_visible_test is tests/view_model.py's restatement (the
 reference's own, ref_pdu_spheres, is exported by the reference build alone; tests/primitive_cases.py pins the library's sphere test to it).  Types: np.float32 for float, Python float for double, Python int for int / unsigned / long.
 
 Which sub-expressions are double: `+ 2.0`, `0.0*z_range` and `0.9*z_range` of :1727-1728; `(0.01*fticks)*wind.x` (:1761); `2.0*get_tile_width()` (:1765);
@@ -25,13 +25,13 @@ The batch order stands for the reference's map order.  capacity: a push_back ont
 Equal dist_sq order by (tile, slot).  The tally counts what happened, so that a case can show that it exercises what it is named for."""
 import numpy as np
 
-import terrain_view_model as tm
+import view_model
 
 f32 = np.float32
 N_RAND_DIST, N_RAND_GAUSS = 10000, 10
 OVERFLOW = 1
 NONE, VFC, BELOW_ZMIN, BELOW_WATER, BELOW_MESH, LISTED = range(6)
-cmax, cmin = tm.cmax, tm.cmin
+cmax, cmin = view_model.cmax, view_model.cmin
 
 CLOUD_DTYPE = np.dtype([("pos_hash", f32), ("pos", f32, 3), ("size", f32, 3), ("pad", np.uint32)])
 TILE_DTYPE = np.dtype([("generated", np.uint32), ("flags", np.uint32), ("count", np.uint32), ("num_clouds", np.uint32), ("cur_move_dist", f32), ("pad", np.uint32),
@@ -370,7 +370,7 @@ def view(sc, v, a, tiles, stats, mgrs, tally):
         for k, c in enumerate(m.clouds):
             pt = [f32(c.pos[i] + a.xlate[i]) for i in range(3)]
             rmax = cmax(c.size[0], cmax(c.size[1], c.size[2]))
-            if not tm.sphere_visible_test(v, a.behind_sphere_mult, pt, rmax):
+            if not view_model.sphere_visible_test(v, a.behind_sphere_mult, pt, rmax):
                 stage[t, k] = VFC
                 tally["vfc"] += 1
                 continue

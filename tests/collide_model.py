@@ -19,21 +19,21 @@ statements (not from the library's bodies), as the literal sequential loops:
 The tile's box is tests/terrain_view_model.py's, a small tree with its trunk_cylin and the group's calc_bcube tests/tree_view_model.py's, a deciduous tree and its
 container's calc_bcube tests/decid_view_model.py's (restatements of their own).  Types: np.float32 for float, Python float for double, Python int for int.  Which
 sub-expressions are double: 1.001*rsum (narrowed into operator*'s float parameter), 0.9*td.br_scale*td.base_radius (narrowed into trunk_radius), 0.2*height and
-0.1*height (narrowed into point's float member), 0.1*radius of a rock_shape's pos.z.  int(float) is the x86 conversion: INT_MIN for what does not fit.
+0.1*height (narrowed into point's float member), 0.1*radius of a rock_shape's pos.z.  int(float) is tests/view_model.py's x86 conversion: INT_MIN for what does not fit.
 
 The tally counts what each query met, so that a case can show that it exercises what it is named for."""
 import numpy as np
 
 import decid_view_model as dm
-import grass_view_model as gm
 import terrain_view_model as tm
 import tree_ao_model as tam
 import tree_view_model as vm
+import view_model
 
 f32 = np.float32
 ZERO, HALF = f32(0.0), f32(0.5)
 TOLERANCE = f32(1.0E-12)
-cmax, cmin, sub = gm.cmax, gm.cmin, gm.sub
+cmax, cmin, sub, f2i, p2p_dist_sq = view_model.cmax, view_model.cmin, view_model.sub, view_model.f2i, view_model.p2p_dist_sq
 LEAFY, PLANT, ROCK_SHAPE, SURFACE_ROCK, VOXEL_ROCK, ROCK, LOG, STUMP, MUSHROOM = range(9)
 WALK = (ROCK_SHAPE, SURFACE_ROCK, VOXEL_ROCK, ROCK, LOG, STUMP, PLANT, LEAFY)  # scenery_group::check_sphere_coll's order; no mushrooms
 INC_DTREES, INC_PTREES, INC_SCENERY = 1, 2, 4
@@ -59,12 +59,6 @@ def new_tally():
     return t
 
 
-def f2i(v):
-    """int(float) as cvttss2si converts it"""
-    v = float(v)
-    return int(v) if np.isfinite(v) and -2147483648.0 <= v < 2147483648.0 else -2147483648
-
-
 def round_fp(v):  # ((val > 0.0f) ? int(val + 0.5f) : int(val - 0.5f))
     v = f32(v)
     return f2i(f32(v + HALF)) if v > ZERO else f2i(f32(v - HALF))
@@ -72,10 +66,6 @@ def round_fp(v):  # ((val > 0.0f) ? int(val + 0.5f) : int(val - 0.5f))
 
 def add(a, b):
     return [f32(a[0] + b[0]), f32(a[1] + b[1]), f32(a[2] + b[2])]
-
-
-def p2p_dist_sq(a, b):
-    return f32(f32(f32(f32(a[0] - b[0]) * f32(a[0] - b[0])) + f32(f32(a[1] - b[1]) * f32(a[1] - b[1]))) + f32(f32(a[2] - b[2]) * f32(a[2] - b[2])))
 
 
 def p2p_dist_xy_sq(a, b):

@@ -16,6 +16,7 @@ import decid_view_model as dm
 import orclib
 import terrain_view_cases as tvc
 import terrain_view_model as tm
+import view_model
 
 ERR_ARG, ERR_STATE = -1, -3
 f32 = np.float32
@@ -426,7 +427,7 @@ def cases():
 
 
 def args_of(case, rec):
-    kw = dict(behind_sphere_mult=tm.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zoom_f=1.0)
+    kw = dict(behind_sphere_mult=view_model.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zoom_f=1.0)
     kw.update(case.args)
     kw.update(rec.args)
     return dm.Args(**kw)
@@ -580,7 +581,6 @@ def run_resident_chain(pkg, t, orc):
     """tiles_create_zvals_dev (zvals, stats) -> tiles_place_decid_trees_dev -> tiles_tree_ao_shadows_dev (the records' other reader) -> tiles_terrain_view_dev
     (not_drawn) -> tiles_decid_view_dev with not_drawn as its skip bytes, on a 3 x 3 batch at S = 128 on one context with nothing read back in between; the model is
     fed from the read-back records"""
-    import grass_view_model as gm
     S, cap, cap_l, shared = 128, 384, 2048, 16
     tiles = [(x, y) for y in range(-1, 2) for x in range(1, 4)]  # from the island's top out over its shore
     n, W, Z = len(tiles), S + 1, S + 2
@@ -597,8 +597,8 @@ def run_resident_chain(pkg, t, orc):
     for k in ("base_radius", "sphere_radius", "sphere_center_zoff", "lr_z_cent", "leaves_bcube", "branches_bcube"):  # trees of TREE_SIZE's order: a fifth of the cases' size
         data[k] = (data[k] * f32(0.2)).astype(f32)
     by_id = data["sphere_radius"].copy()
-    v = gm.make_view((float(tsc.g.get_xval(S + S // 2)), 0.3, 1.5), tvc._unit(1.0, 0.3, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 60.0)
-    bsm = tm.behind_sphere_mult(0.7, 1.6)
+    v = view_model.make_view((float(tsc.g.get_xval(S + S // 2)), 0.3, 1.5), tvc._unit(1.0, 0.3, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 60.0)
+    bsm = view_model.behind_sphere_mult(0.7, 1.6)
     ta, a = tm.Args(bsm, float(orc.state().zmin), 1, 0, 0), dm.Args(bsm, 1.0, (0.06, 0.03, 0.05, 0.02))
     lv, lta, la = tvc.lib_view(pkg, v), tvc.lib_args(pkg, ta), lib_args(pkg, a)
     out = pkg.Terra._decid_view_outputs(n, cap, FILL)

@@ -9,11 +9,10 @@ bodies):
     tree_data_t::get_size_scale_mult, draw_branches, draw_leaves (the counts)  src/Tree.cpp:930, 1128-1140, 1182-1188
     tree_cont_t::calc_bcube                                                    src/Tree.cpp:2458-2461
     get_draw_tile_dist, get_scaled_tile_radius                                 src/tiled_mesh.cpp:117, src/tiled_mesh.h:93-94
-    InvSqrt                                                                    src/inlines.h:39-50
-    cube_visible_likely, cube_t's helpers                                      src/3DWorld.h:491-527, 602, 724; src/csg.cpp:247
+    cube_t's helpers                                                           src/3DWorld.h:491-527, 602; src/csg.cpp:247
 
-cube_visible, point_visible_test and closest_pt are tests/grass_view_model.py's, sphere_visible_test (with its tally of the planes) tests/tree_view_model.py's:
-restatements of their own.  Types: np.float32 for float, Python float for double, Python int for int / unsigned.  Which sub-expressions are double: 1.1*sphere_radius
+The view tests (cube_visible, cube_visible_likely, sphere_visible_test with its tally of the planes), closest_pt, InvSqrt and unsigned(double) are
+tests/view_model.py's.  Types: np.float32 for float, Python float for double, Python int for int / unsigned.  Which sub-expressions are double: 1.1*sphere_radius
 (narrowed to the float parameter), 1.0*(X_SCENE_SIZE + Y_SCENE_SIZE) (narrowed likewise), 1.5*num_branch_quads*size_scale*mult and 4.0*nl*size_scale*mult,
 (1.0 - geom_opacity) (narrowed), and the comparisons of size_scale and geom_opacity with 0.0, 0.05 and 2.0.  unsigned(double) converts like x86-64: cvttsd2si to 64
 bits and the low word, 0 beyond the 64-bit range.  Tiled-terrain mode: sphere_in_camera_view is sphere_visible_test alone (src/visibility.cpp:338-339).
@@ -23,9 +22,8 @@ The billboard lists are sorted by tree_id and keep, within an id, the order in w
 The tally counts what each test decided, so that a case can show that it exercises what it is named for."""
 import numpy as np
 
-import grass_view_model as gm
 import tree_ao_model as tam
-import tree_view_model as tvm
+import view_model
 
 f32 = np.float32
 ZERO, ONE, HALF = f32(0.0), f32(1.0), f32(0.5)
@@ -34,7 +32,7 @@ GENERATED, HAS_4TH, LEAF_TEX, BRANCH_TEX = 1, 2, 4, 8
 TILE_DRAWN, TILE_LEAVES, TILE_BRANCHES, TILE_SORTED, TILE_BCUBE_ZERO_AREA = 1, 2, 4, 8, 16
 FORM_NONE, FORM_GEOM, FORM_BOTH, FORM_BILLBOARD, NOT_VISIBLE, LOW_DETAIL, STAGE_SHIFT = 0, 1, 2, 3, 4, 8, 4
 ST_NONE, ST_NOT_VISIBLE, ST_NO_LEAVES, ST_BOX, ST_SIZE, ST_SHADOW_DIST, ST_SHADOW_SPHERE = range(7)
-cmax, cmin = gm.cmax, gm.cmin
+cmax, cmin, d2u, inv_sqrt, cube_visible_likely = view_model.cmax, view_model.cmin, view_model.d2u, view_model.inv_sqrt, view_model.cube_visible_likely
 
 TD_DTYPE = np.dtype([("base_radius", f32), ("sphere_radius", f32), ("sphere_center_zoff", f32), ("lr_z_cent", f32), ("leaves_bcube", f32, (6,)), ("branches_bcube", f32, (6,)),
                      ("num_leaves", np.uint32), ("num_branch_quads", np.uint32), ("flags", np.uint32), ("pad", np.uint32)])  # terra_decid_tree_data
@@ -62,23 +60,6 @@ class Args:
         self.leaf_color_changed, self.draw_leaves, self.draw_branches = int(bool(leaf_color_changed)), int(bool(draw_leaves)), int(bool(draw_branches))
 
 
-def d2u(d):
-    """unsigned(double) as x86-64 converts it: cvttsd2si to 64 bits, the low word"""
-    d = float(d)
-    if not (-9223372036854775808.0 < d < 9223372036854775808.0):
-        return 0
-    return int(d) & 0xFFFFFFFF
-
-
-def inv_sqrt(x):
-    """InvSqrt: tmp.i = 0x5f3759df - (tmp.i >> 1); y*(1.5f - 0.5f*x*y*y)"""
-    x = f32(x)
-    i = int(np.array([x], f32).view(np.int32)[0])
-    y = np.array([(0x5f3759df - (i >> 1)) & 0xFFFFFFFF], np.uint32).view(f32)[0]
-    with np.errstate(all="ignore"):
-        return f32(y * f32(f32(1.5) - f32(f32(f32(HALF * x) * y) * y)))
-
-
 def add3(a, b):
     return [f32(a[0] + b[0]), f32(a[1] + b[1]), f32(a[2] + b[2])]
 
@@ -93,17 +74,6 @@ def is_all_zeros(d):
 
 def is_zero_area(d):
     return any(d[i][0] == d[i][1] for i in range(3))
-
-
-def cube_visible_likely(v, d, tally):
-    if not v.valid:
-        return True
-    if gm.point_visible_test(v, [f32(HALF * f32(d[i][0] + d[i][1])) for i in range(3)]):  # get_cube_center()
-        tally["cube_centre_visible"] += 1
-        return True
-    r = gm.cube_visible(v, d)
-    tally["cube_by_corners"] += int(r)
-    return r
 
 
 class Scene:
@@ -132,7 +102,7 @@ def size_scale_mult(td):
 
 
 def calc_size_scale(sc, v, a, td, draw_pos, tally=None):
-    dist_sq = gm.p2p_dist_sq(v.pos, draw_pos)
+    dist_sq = view_model.p2p_dist_sq(v.pos, draw_pos)
     dd = f32(sc.dmax * sc.dmax)
     if tally is not None:
         tally["at_dmax"] += int(dist_sq == dd)
@@ -216,7 +186,7 @@ def form_of(geom_opacity, added):
 
 
 def shadow_near(v, center):  # dist_less_than(center, camera_pdu.pos, camera_pdu.far_)
-    return bool(gm.p2p_dist_sq(center, v.pos) < f32(v.far_ * v.far_))
+    return bool(view_model.p2p_dist_sq(center, v.pos) < f32(v.far_ * v.far_))
 
 
 def draw_leaves_top(sc, v, a, t, index, billboards, tally):
@@ -227,7 +197,7 @@ def draw_leaves_top(sc, v, a, t, index, billboards, tally):
     if a.shadow_pass:
         if not shadow_near(v, center):
             return o.leave(ST_SHADOW_DIST, tally, "l")
-        if not tvm.sphere_visible_test(v, a.behind_sphere_mult, center, r11, tally):
+        if not view_model.sphere_visible_test(v, a.behind_sphere_mult, center, r11, tally):
             return o.leave(ST_SHADOW_SPHERE, tally, "l")
         if int(td["num_leaves"]) == 0:  # draw_leaves_shadow_only: leaves.empty()
             return o.leave(ST_NO_LEAVES, tally, "l")
@@ -235,7 +205,7 @@ def draw_leaves_top(sc, v, a, t, index, billboards, tally):
         tally["l_form_1"] += 1
         tally["shadow_leaves_drawn"] += 1
         return o
-    t.not_visible = not tvm.sphere_visible_test(v, a.behind_sphere_mult, center, r11, tally)  # !is_visible_to_camera(xlate)
+    t.not_visible = not view_model.sphere_visible_test(v, a.behind_sphere_mult, center, r11, tally)  # !is_visible_to_camera(xlate)
     tally["nv_written"] += 1
     if t.not_visible:
         o.word |= NOT_VISIBLE
@@ -352,7 +322,7 @@ def draw_decid_trees(sc, v, a, recs, data, nv_in, tally):
     if zero_area:
         res.flags |= TILE_BCUBE_ZERO_AREA
         tally["tile_zero_area"] += 1
-    if not zero_area and not gm.cube_visible(v, [[f32(bc[i][0] + sc.xlate[i]), f32(bc[i][1] + sc.xlate[i])] for i in range(3)]):  # VFC (:316)
+    if not zero_area and not view_model.cube_visible(v, [[f32(bc[i][0] + sc.xlate[i]), f32(bc[i][1] + sc.xlate[i])] for i in range(3)]):  # VFC (:316)
         tally["tile_culled"] += 1
         return res
     tally["tile_drawn"] += 1
@@ -364,14 +334,14 @@ def draw_decid_trees(sc, v, a, recs, data, nv_in, tally):
     if a.draw_leaves:  # the leaves sweep comes first (src/tiled_mesh.cpp:3268-3292)
         order = trees
         if not a.shadow_pass:
-            local_camera = gm.sub(v.pos, sc.xlate)
-            direct = not is_all_zeros(bc) and not bool(gm.p2p_dist_sq(local_camera, gm.closest_pt(bc, local_camera)) < f32(sc.scene_sum * sc.scene_sum))
+            local_camera = view_model.sub(v.pos, sc.xlate)
+            direct = not is_all_zeros(bc) and not bool(view_model.p2p_dist_sq(local_camera, view_model.closest_pt(bc, local_camera)) < f32(sc.scene_sum * sc.scene_sum))
             if direct:
                 tally["direct"] += 1
             else:
                 res.flags |= TILE_SORTED
                 tally["sorted"] += 1
-                keys = [(gm.p2p_dist_sq(t.sphere_center(), local_camera), k) for k, (_, t) in enumerate(trees)]
+                keys = [(view_model.p2p_dist_sq(t.sphere_center(), local_camera), k) for k, (_, t) in enumerate(trees)]
                 keys.sort(key=lambda e: (float(e[0]), e[1]))  # std::sort of pair<float, unsigned>
                 tally["sorted_ties"] += sum(1 for x, y in zip(keys, keys[1:]) if x[0] == y[0])
                 order = [trees[k] for _, k in keys]

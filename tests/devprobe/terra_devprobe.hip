@@ -5,16 +5,13 @@
 //   libterra_devprobe_hip.so    hipcc with the product's flags for gfx950: every entry point copies its arrays to device 0, launches ONE kernel (256 threads per
 //                               block, `i < n` guard) whose thread i evaluates element i, and copies the results back
 //   libterra_devprobe_host.so   g++ -x c++ with the host emulation's flags: the same bodies in a loop
-// Each body calls the product's own function.  The two places where the product has no function of exactly the recorded shape say so (closest_dist_less_than,
-// the steep-slope statement of terrain_view_lod).  Every entry point returns 0, or the first HIP error's code (-1: no device); nothing aborts.
+// Each body calls the product's own function: the view and box primitives of terra_view.hpp, the line clip and the conversions of terra_common.hpp, the libm
+// restatements, and terra_terrainview.hpp's two LOD functions.  Every entry point returns 0, or the first HIP error's code (-1: no device); nothing aborts.
+#include "terra_view.hpp"
+#include "terra_common.hpp"
 #include "terra_sincosf.hpp"
 #include "terra_powf.hpp"
-#include "terra_grassview.hpp"
-#include "terra_terrainview.hpp"
-#include "terra_treeview.hpp"
-#include "terra_sceneryview.hpp"
-#include "terra_decidview.hpp"
-#include "terra_driver.hpp" // d2i_x86
+#include "terra_terrainview.hpp" // terrain_view_steep_dist, terrain_view_lod
 #include <vector>
 
 using namespace terra;
@@ -105,20 +102,9 @@ struct f_cubes {
 		float const d[3][2] = {{c[6*i], c[6*i + 1]}, {c[6*i + 2], c[6*i + 3]}, {c[6*i + 4], c[6*i + 5]}};
 		o[5*i]     = view_cube_visible(v, d) ? 1 : 0;
 		o[5*i + 1] = view_cube_completely_visible(v, d) ? 1 : 0;
-		{ // decid_view_cube_likely translates the box by the tree's position: the position is zero here (v + 0.0f == v)
-			decid_view_consts_t dc = {}; dc.v = v;
-			decid_view_tree_t g = {};
-			float const box[6] = {d[0][0], d[0][1], d[1][0], d[1][1], d[2][0], d[2][1]};
-			o[5*i + 2] = decid_view_cube_likely(dc, box, g) ? 1 : 0;
-		}
-		{ // terrain_view_visible = sphere_and_cube_visible_test(get_center(), radius, get_bcube()): water off, so that the radius is the sphere's own
-			terrain_view_consts_t tc = {}; tc.v = v; tc.behind_sphere_mult = bsm; tc.water_enabled = 0;
-			terrain_view_geom_t g = {}; g.cx = s[4*i]; g.cy = s[4*i + 1]; g.cz = s[4*i + 2];
-			for (int a = 0; a < 3; ++a) {g.bc[a][0] = d[a][0]; g.bc[a][1] = d[a][1];}
-			o[5*i + 3] = terrain_view_visible(tc, g, 0.0f, 1.0f, s[4*i + 3]) ? 1 : 0;
-		}
-		// closest_dist_less_than as decid_view_tile states it (the product has no function of its own for it): view_closest_dist_sq against the squared distance
-		o[5*i + 4] = (view_closest_dist_sq(d, q[4*i], q[4*i + 1], q[4*i + 2]) < q[4*i + 3]*q[4*i + 3]) ? 1 : 0;
+		o[5*i + 2] = view_cube_visible_likely(v, d) ? 1 : 0;
+		o[5*i + 3] = view_sphere_and_cube_visible(v, bsm, s[4*i], s[4*i + 1], s[4*i + 2], s[4*i + 3], d) ? 1 : 0;
+		o[5*i + 4] = view_closest_dist_less_than(d, q[4*i], q[4*i + 1], q[4*i + 2], q[4*i + 3]) ? 1 : 0;
 	}
 };
 struct f_inv_sqrt {
@@ -134,12 +120,12 @@ struct f_line_clip {
 		o[6*i] = v1.x; o[6*i + 1] = v1.y; o[6*i + 2] = v1.z; o[6*i + 3] = v2.x; o[6*i + 4] = v2.y; o[6*i + 5] = v2.z;
 	}
 };
-// od: the steep-slope statement of terrain_view_lod with terrain_view_log2 (the function returns only the level, so the statement is repeated here to see the float);
+// od: the steep-slope statement of terrain_view_lod (terrain_view_steep_dist);
 // ol: terrain_view_lod itself for a tile of S = 128 that is not flat, no shadow maps, no water, no reflection: the level that float gives
 struct f_lod {
 	float const *dist, *mnz; float *od; uint8_t *ol;
 	PROBE_FN void operator()(uint32_t i) const {
-		od[i] = (float)((double)dist[i]/-terrain_view_log2(2.0*(double)mnz[i]));
+		od[i] = terrain_view_steep_dist(dist[i], mnz[i]);
 		terrain_view_consts_t tc = {}; tc.S = 128; tc.water_enabled = 0; tc.reflection_pass = 0;
 		ol[i] = (uint8_t)terrain_view_lod(tc, 0.0f, 1.0f, mnz[i], dist[i], false);
 	}

@@ -13,6 +13,7 @@ import numpy as np
 import grass_brush_cases as gbc
 import grass_brush_model as gbm
 import grass_view_model as gm
+import view_model
 import orclib
 
 ERR_ARG, ERR_STATE = -1, -3
@@ -120,7 +121,7 @@ def scene_of(orc, case):
 
 
 def view_of(case):
-    v = gm.make_view(**case.view)
+    v = view_model.make_view(**case.view)
     v.valid = case.valid
     return v
 
@@ -219,7 +220,7 @@ def run_resident_chain(pkg, gpu, orc):
     gpu.set_grass_view_params(pkg.make_grass_view_params(0.25))
     sc = gm.Scene(orc, pkg.make_config(mesh_gen_mode=0, mesh_xy=S), gm.Params(0.25, 0.02, nrnd))
     zc = float(d["z"][tiles.index((0, 0))][64, 64])
-    v = gm.make_view((0.4, -0.3, zc + 0.5), (1.0, 0.4, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 40.0)
+    v = view_model.make_view((0.4, -0.3, zc + 0.5), (1.0, 0.4, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 40.0)
     lv = lib_view(pkg, v)
     x, y = gbc.texel_pos(bsc, (0, 0), 80, 70)
     b_rem = pkg.make_grass_brush((x, y, float(d["z"][tiles.index((0, 0))][70, 80])), 14.5 * float(bsc.DX_VAL), 0, gbm.BSHAPE_CONST_SQ, 1.0)

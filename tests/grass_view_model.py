@@ -7,38 +7,26 @@
     get_rel_dist_to_camera, get_dist_to_camera_in_tiles                      src/tiled_mesh.h:320-332
     the thresholds                                                           src/tiled_mesh.cpp:27-29, 118-120; src/tiled_mesh.h:24, 93-94
     NUM_GRASS_LODS, GRASS_BLOCK_SZ                                           src/grass.h:9-10
-    pos_dir_up: constructor, orthogonalize_up_dir, point_visible_test,
-      check_clip_plane, pt_set_visible<8>, cube_visible,
-      cube_completely_visible                                                src/visibility.cpp:67-103, 141-174, 186-196
-    cube_t::closest_pt, closest_pt_dist_sq, dist_less_than, p2p_dist_sq      src/3DWorld.h:591, 636-641; src/csg.cpp:244-246; src/inlines.h:176-192
-    orthogonalize_dir, cross_product, dot_product, pointT::normalize         src/inlines.h:153-157, 220-222, 265-268; src/3DWorld.h:273-279
 
-Types: np.float32 for float, Python float for double, Python int for int / unsigned.  Which sub-expressions are double: 0.56*bg_thresh_sq and the comparison
-with it; 2.0*grass_length (narrowed by point's constructor); 0.5*tt_grass_scale_factor and the comparison with it; A*tterm (A is a double member; narrowed by
-atanf's parameter); 1.0/d in normalize (narrowed to the float m).  Everything else is float: dot products are x*x + y*y + z*z left to right, SQRT2 is the float
-sqrt(2.0), `unsigned*float` products convert the unsigned to float first.  tanf / sinf / atanf are the C library's, called through ctypes.
+The view (pos_dir_up's constructor and its point and cube tests), closest_pt, unsigned(float) and the vector helpers are tests/view_model.py's.  Types: np.float32
+for float, Python float for double, Python int for int / unsigned.  Which sub-expressions are double: 0.56*bg_thresh_sq and the comparison with it;
+2.0*grass_length (narrowed by point's constructor); 0.5*tt_grass_scale_factor and the comparison with it.  Everything else is float: SQRT2 is the float
+sqrt(2.0), `unsigned*float` products convert the unsigned to float first.
 
 The tally counts what each test decided, so that a case can show that it exercises what it is named for."""
-import ctypes
-import ctypes.util
 import math
 
 import numpy as np
+
+from view_model import closest_pt, cmax, cube_completely_visible, cube_visible, f2u, p2p_dist_sq
 
 f32 = np.float32
 NUM_GRASS_LODS, GRASS_BLOCK_SZ, TILE_RADIUS = 6, 4, 6
 GRASS_LOD_SCALE, GRASS_DIST_SLOPE, GRASS_THRESH = f32(15.0), f32(0.25), f32(1.6)
 BCUBE_ZTOLER = f32(1.0E-6)
 SQRT2 = f32(math.sqrt(2.0))
-PI = f32(3.141592654)
-TOLERANCE = f32(1.0E-12)
 NO_PASS = 255
 ZERO = f32(0.0)
-
-_libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
-for _n in ("tanf", "sinf", "atanf"):
-    getattr(_libm, _n).restype = ctypes.c_float
-    getattr(_libm, _n).argtypes = [ctypes.c_float]
 
 TALLY = ("tiles_skipped", "tiles_too_far", "tiles_no_grass", "tiles_all_visible", "tiles_frustum_tested", "too_far_tile_blocks_in_range", "empty", "beyond", "frustum_dropped",
          "frustum_kept", "far_dropped", "all_visible_kept", "backface_dropped", "backface_kept", "not_tested", "bad_ix", "kept", "lod_clamped", "wpass0", "wpass1",
@@ -47,76 +35,6 @@ TALLY = ("tiles_skipped", "tiles_too_far", "tiles_no_grass", "tiles_all_visible"
 
 def new_tally():
     return {k: 0 for k in TALLY}
-
-
-def cmax(a, b):  # std::max
-    return b if a < b else a
-
-
-def cmin(a, b):  # std::min
-    return a if not (b < a) else b
-
-
-def dot(a, b):
-    return f32(f32(f32(a[0] * b[0]) + f32(a[1] * b[1])) + f32(a[2] * b[2]))
-
-
-def cross(a, b):
-    return [f32(f32(a[1] * b[2]) - f32(a[2] * b[1])), f32(f32(a[2] * b[0]) - f32(a[0] * b[2])), f32(f32(a[0] * b[1]) - f32(a[1] * b[0]))]
-
-
-def sub(a, b):
-    return [f32(a[0] - b[0]), f32(a[1] - b[1]), f32(a[2] - b[2])]
-
-
-def mag_sq(a):
-    return dot(a, a)
-
-
-def f2u(v):
-    """unsigned(float) as x86-64 converts it: cvttss2si to 64 bits, the low word"""
-    v = float(v)
-    if not (-9.2e18 < v < 9.2e18):
-        return 0
-    return int(v) & 0xFFFFFFFF
-
-
-class View:
-    """pos_dir_up: pos, dir, upv_, cp, sterm, x_sterm, near_, far_, valid"""
-
-    def __init__(self, pos, dir, upv_, cp, sterm, x_sterm, near_, far_, valid=1):
-        self.pos, self.dir, self.upv_, self.cp = [f32(v) for v in pos], [f32(v) for v in dir], [f32(v) for v in upv_], [f32(v) for v in cp]
-        self.sterm, self.x_sterm, self.near_, self.far_, self.valid = f32(sterm), f32(x_sterm), f32(near_), f32(far_), int(valid)
-
-    def words(self):
-        return np.array(self.pos + self.dir + self.upv_ + self.cp + [self.sterm, self.x_sterm, self.near_, self.far_], f32).tobytes() + np.int32(self.valid).tobytes()
-
-
-def make_view(pos, dir, up, angle, aspect, near, far):
-    """the constructor (:67-85) and orthogonalize_up_dir (:87-92); None where it asserts"""
-    pos, dir, up = [f32(v) for v in pos], [f32(v) for v in dir], [f32(v) for v in up]
-    angle, near, far = f32(angle), f32(near), f32(far)
-    if not (near >= 0.0 and far > 0.0 and far > near):
-        return None
-    if dir[0] == 0.0 and dir[1] == 0.0 and dir[2] == 0.0:
-        return None
-    A = float(f32(aspect))
-    tterm, sterm = f32(_libm.tanf(angle)), f32(_libm.sinf(angle))
-    if A == 1.0:
-        x_sterm = sterm
-    else:
-        if not (tterm > 0.0):
-            return None
-        atan_val = f32(_libm.atanf(f32(A * float(tterm))))
-        if atan_val < 0.0:
-            atan_val = f32(atan_val + PI)
-        x_sterm = f32(f32(atan_val / angle) * sterm)
-    upv_ = cross(dir, cross(up, dir))  # orthogonalize_dir(upv, dir, upv_, 1)
-    d = f32(np.sqrt(mag_sq(upv_)))
-    if d >= TOLERANCE:
-        m = f32(1.0 / float(d))
-        upv_ = [f32(v * m) for v in upv_]
-    return View(pos, dir, upv_, cross(dir, upv_), sterm, x_sterm, near, far, 1)
 
 
 class Params:
@@ -148,74 +66,6 @@ class Scene:
 
     def get_yval(self, y):
         return f32(-self.Y_SCENE_SIZE + f32(self.DY_VAL * f32(y)))
-
-
-def cube_pts(d):
-    return [[d[0][i], d[1][j], d[2][k]] for i in (0, 1) for j in (0, 1) for k in (0, 1)]
-
-
-def point_visible_test(v, p):
-    if not v.valid:
-        return True
-    pv = sub(p, v.pos)
-    if dot(v.dir, pv) < 0.0:
-        return False
-    dist = f32(np.sqrt(mag_sq(pv)))
-    if abs(dot(v.upv_, pv)) > f32(dist * v.sterm):
-        return False
-    if abs(dot(v.cp, pv)) > f32(dist * v.x_sterm):
-        return False
-    return bool(dist > v.near_ and dist < v.far_)
-
-
-def cube_completely_visible(v, d):
-    if not v.valid:
-        return True
-    return all(point_visible_test(v, p) for p in cube_pts(d))
-
-
-def check_clip_plane(pts, pos, n, aa, d):
-    for p in pts:
-        pv = sub(p, pos)
-        dp = dot(n, pv)
-        if (f32(-dp) if d else dp) <= 0.0 or f32(dp * dp) <= f32(aa * mag_sq(pv)):
-            return True
-    return False
-
-
-def pt_set_visible(v, pts):
-    su, sc = f32(v.sterm * v.sterm), f32(v.x_sterm * v.x_sterm)
-    if not check_clip_plane(pts, v.pos, v.upv_, su, 0) or not check_clip_plane(pts, v.pos, v.upv_, su, 1):
-        return False
-    if not check_clip_plane(pts, v.pos, v.cp, sc, 0) or not check_clip_plane(pts, v.pos, v.cp, sc, 1):
-        return False
-    npass = fpass = False
-    for p in pts:
-        if npass and fpass:
-            break
-        dp = dot(v.dir, sub(p, v.pos))
-        npass |= bool(dp > v.near_)
-        fpass |= bool(dp < v.far_)
-    return npass and fpass
-
-
-def closest_pt(d, p):
-    return [cmin(d[i][1], cmax(d[i][0], p[i])) for i in range(3)]
-
-
-def p2p_dist_sq(a, b):
-    return mag_sq(sub(a, b))
-
-
-def cube_visible(v, d, tally=None):
-    if not v.valid:
-        return True
-    if not pt_set_visible(v, cube_pts(d)):
-        return False
-    ok = bool(p2p_dist_sq(v.pos, closest_pt(d, v.pos)) < f32(v.far_ * v.far_))  # dist_less_than(pos, c.closest_pt(pos), far_)
-    if tally is not None and not ok:
-        tally["far_dropped"] += 1
-    return ok
 
 
 def mesh_bcube(sc, tx, ty, mzmin, mzmax):

@@ -3,8 +3,7 @@
     tile_draw_t::line_intersect_mesh    src/tiled_mesh.cpp:3582-3605 (inc_trees = 0)
     tile_t::line_intersect_mesh         src/tiled_mesh.cpp:2176-2213
     get_mesh_bcube                      src/tiled_mesh.h:238-241, BCUBE_ZTOLER src/tiled_mesh.h:32
-    do_line_clip / TEST_CLIP_T          src/Math3d.cpp:1029-1034, 1070-1086
-    get_region                          src/inlines.h:522-528
+    do_line_clip, get_region            tests/view_model.py's
     get_xval / get_xpos                 src/mesh.h:122-123, 129-130
     line_intersect_tiled_mesh_get_tile  src/tiled_mesh.cpp:3643-3648
 
@@ -14,8 +13,10 @@ works on arrays of (line, tile) pairs so that it can check tens of thousands of 
 """
 import numpy as np
 
+import view_model
+
 f32, f64 = np.float32, np.float64
-TOLERANCE = f32(1.0E-12)     # src/3DWorld.h:50
+get_region, do_line_clip = view_model.line_region, view_model.do_line_clip
 BCUBE_ZTOLER = f32(1.0E-6)   # src/tiled_mesh.h:32
 INT_MIN = -2 ** 31
 MAX_STEPS = 10000            # assert(steps < 10000) (src/tiled_mesh.cpp:2187)
@@ -56,39 +57,6 @@ def mesh_bcube(sc, tx, ty, mzmin, mzmax, dxoff, dyoff):
     d = [xv1, xv1 + f32(sc.S) * sc.DX_VAL, yv1, yv1 + f32(sc.S) * sc.DY_VAL,  # xv1 + (x2 - x1)*DX_VAL
          np.asarray(mzmin, f32) - BCUBE_ZTOLER, np.asarray(mzmax, f32) + BCUBE_ZTOLER]
     return [np.asarray(a, f32) for a in d], x1, y1
-
-
-def get_region(v, d):
-    """get_region (src/inlines.h:522-528): low bounds with <, high bounds with >="""
-    r = np.zeros(len(v[0]), np.int64)
-    for a in range(3):
-        lo, hi = d[2 * a], d[2 * a + 1]
-        r |= np.where(v[a] < lo, 1 << (2 * a), np.where(v[a] >= hi, 2 << (2 * a), 0))
-    return r
-
-
-def do_line_clip(v1, v2, d):
-    """do_line_clip (src/Math3d.cpp:1070-1086) -> (ok, v1c, v2c); v1, v2: 3 float32 arrays, d: 6 float32 arrays"""
-    r1, r2 = get_region(v1, d), get_region(v2, d)
-    ok = (r1 & r2) == 0
-    r3 = r1 | r2
-    tmin, tmax = np.zeros(len(r1), f32), np.ones(len(r1), f32)
-    dv = [v2[a] - v1[a] for a in range(3)]  # vector3d const dv(v2, v1)
-    for a in range(3):
-        for side in range(2):  # TEST_CLIP_T(reg, d[a][side], v1[a], dv[a], side ? -dv[a] : dv[a]) (:1029-1034)
-            reg = (1 << side) << (2 * a)
-            act = ok & ((r3 & reg) != 0)
-            t = (d[2 * a + side] - v1[a]) / dv[a]  # float quotient
-            vc = -dv[a] if side else dv[a]
-            tmin = np.where(act & (vc > 0.0) & (t > tmin), t, tmin)
-            tmax = np.where(act & ~(vc > 0.0) & (t < tmax), t, tmax)
-            ok &= ~(act & (tmin >= tmax))
-    clip = ok & (r3 != 0)
-    mv2 = clip & (tmax > TOLERANCE)                          # float compare
-    mv1 = clip & (tmin.astype(f64) < (1.0 - f64(TOLERANCE)))  # double compare
-    v2c = [np.where(mv2, v1[a] + dv[a] * tmax, v2[a]) for a in range(3)]  # v2 first, from the original v1
-    v1c = [np.where(mv1, v1[a] + dv[a] * tmin, v1[a]) for a in range(3)]
-    return ok, v1c, v2c
 
 
 def get_pos(v, ss, inv):

@@ -33,6 +33,8 @@ import os
 
 import numpy as np
 
+import view_model
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE = os.path.join(HERE, "golden", "primitive_vectors.npz")
 f32 = np.float32
@@ -250,10 +252,9 @@ def check_abi_cameras(t, fx):
         assert_same(f"terra_view_behind_sphere_mult, camera {c}", co[16:17], np.array([t.view_behind_sphere_mult(angle, float(ci[10]))], f32))
 
 
-# ---- the Python models' own primitives on the fixture's inputs
+# ---- the Python models' primitives (tests/view_model.py, and the LOD statement of tests/terrain_view_model.py) on the fixture's inputs
 def model_views(fx):
-    import grass_view_model as gm
-    return [gm.View(o[0:3], o[3:6], o[6:9], o[9:12], o[12], o[13], o[14], o[15], int(valid)) for o, valid in zip(fx["cam_out"], fx["cam_valid"])]
+    return [view_model.View(o[0:3], o[3:6], o[6:9], o[9:12], o[12], o[13], o[14], o[15], int(valid)) for o, valid in zip(fx["cam_out"], fx["cam_valid"])]
 
 
 def box3(b):
@@ -262,12 +263,7 @@ def box3(b):
 
 def eval_models(fx):
     """-> {label: (expected, got)} for every primitive of the models that the fixture has rows for"""
-    import decid_view_model as dm
-    import grass_view_model as gm
-    import line_intersect_model as lm
-    import scenery_view_model as sm
     import terrain_view_model as tm
-    import tree_view_model as trm
     res = {}
     views = model_views(fx)
     ncam = num_cameras(fx)
@@ -276,46 +272,44 @@ def eval_models(fx):
     made = constructed_cameras(fx)
     for c in made:
         ci, co = fx["cam_in"][c], fx["cam_out"][c]
-        v = gm.make_view(ci[0:3], ci[3:6], ci[6:9], ci[9], ci[10], ci[11], ci[12])
+        v = view_model.make_view(ci[0:3], ci[3:6], ci[6:9], ci[9], ci[10], ci[11], ci[12])
         assert v is not None, f"camera {c}: the model refuses what the reference constructs"
         cams.append(np.array(v.pos + v.dir + v.upv_ + v.cp + [v.sterm, v.x_sterm, v.near_, v.far_], f32))
-        bsm.append(tm.behind_sphere_mult(ci[9], ci[10]))
-    res["grass_view_model.make_view"] = (fx["cam_out"][made, :16], np.array(cams, f32))
-    res["terrain_view_model.behind_sphere_mult"] = (fx["cam_out"][made, 16], np.array(bsm, f32))
-    pt, sp_t, sp_tr = [], [], []
+        bsm.append(view_model.behind_sphere_mult(ci[9], ci[10]))
+    res["view_model.make_view"] = (fx["cam_out"][made, :16], np.array(cams, f32))
+    res["view_model.behind_sphere_mult"] = (fx["cam_out"][made, 16], np.array(bsm, f32))
+    pt, sp = [], []
     cv, ccv, cvl = [], [], []
     for c in range(ncam):
         v, b = views[c], f32(fx["cam_out"][c][16])
         with np.errstate(all="ignore"):
-            pt += [gm.point_visible_test(v, [f32(x) for x in p]) for p in fx["pt_xyz"][rows(fx, "pt", c)]]
+            pt += [view_model.point_visible_test(v, [f32(x) for x in p]) for p in fx["pt_xyz"][rows(fx, "pt", c)]]
         for s in fx["sp_xyzr"][rows(fx, "sp", c)]:
             pos = [f32(s[0]), f32(s[1]), f32(s[2])]
             with np.errstate(all="ignore"):
-                sp_t.append(tm.sphere_visible_test(v, b, pos, f32(s[3])))
-                sp_tr.append(trm.sphere_visible_test(v, b, pos, f32(s[3])))
+                sp.append(view_model.sphere_visible_test(v, b, pos, f32(s[3])))
         for bx in fx["cb_box"][rows(fx, "cb", c)]:
             d = box3(bx)
             with np.errstate(all="ignore"):
-                cv.append(gm.cube_visible(v, d))
-                ccv.append(gm.cube_completely_visible(v, d))
-                cvl.append(dm.cube_visible_likely(v, d, collections.defaultdict(int)))
+                cv.append(view_model.cube_visible(v, d))
+                ccv.append(view_model.cube_completely_visible(v, d))
+                cvl.append(view_model.cube_visible_likely(v, d, collections.defaultdict(int)))
     u8 = lambda a: np.array(a, bool).astype(np.uint8)  # noqa: E731
-    res["grass_view_model.point_visible_test"] = (fx["pt_out"], u8(pt))
-    res["terrain_view_model.sphere_visible_test"] = (fx["sp_out"], u8(sp_t))
-    res["tree_view_model.sphere_visible_test"] = (fx["sp_out"], u8(sp_tr))
-    res["grass_view_model.cube_visible"] = (fx["cb_out"][:, 0], u8(cv))
-    res["grass_view_model.cube_completely_visible"] = (fx["cb_out"][:, 1], u8(ccv))
-    res["decid_view_model.cube_visible_likely"] = (fx["cb_out"][:, 2], u8(cvl))
+    res["view_model.point_visible_test"] = (fx["pt_out"], u8(pt))
+    res["view_model.sphere_visible_test"] = (fx["sp_out"], u8(sp))
+    res["view_model.cube_visible"] = (fx["cb_out"][:, 0], u8(cv))
+    res["view_model.cube_completely_visible"] = (fx["cb_out"][:, 1], u8(ccv))
+    res["view_model.cube_visible_likely"] = (fx["cb_out"][:, 2], u8(cvl))
     with np.errstate(all="ignore"):
-        res["decid_view_model.inv_sqrt"] = (fx["isq_out"], np.array([dm.inv_sqrt(x) for x in fx["isq_x"]], f32))
+        res["view_model.inv_sqrt"] = (fx["isq_out"], np.array([view_model.inv_sqrt(x) for x in fx["isq_x"]], f32))
         res["terrain_view_model.lod_steep_dist"] = (fx["lod_out"], np.array([tm.lod_steep_dist(d, z) for d, z in zip(fx["lod_dist"], fx["lod_mnz"])], f32))
-    res["grass_view_model.f2u"] = (fx["cvf_u"], np.array([gm.f2u(x) for x in fx["cvf_x"]], np.uint32))
-    res["scenery_view_model.f2i"] = (fx["cvf_i"], np.array([sm.f2i(x) for x in fx["cvf_x"]], np.int32))
-    res["decid_view_model.d2u"] = (fx["cvd_u"], np.array([dm.d2u(x) for x in fx["cvd_x"]], np.uint32))
-    res["scenery_view_model.d2i"] = (fx["cvd_i"], np.array([sm.d2i(x) for x in fx["cvd_x"]], np.int32))
+    res["view_model.f2u"] = (fx["cvf_u"], np.array([view_model.f2u(x) for x in fx["cvf_x"]], np.uint32))
+    res["view_model.f2i"] = (fx["cvf_i"], np.array([view_model.f2i(x) for x in fx["cvf_x"]], np.int32))
+    res["view_model.d2u"] = (fx["cvd_u"], np.array([view_model.d2u(x) for x in fx["cvd_x"]], np.uint32))
+    res["view_model.d2i"] = (fx["cvd_i"], np.array([view_model.d2i(x) for x in fx["cvd_x"]], np.int32))
     with np.errstate(all="ignore"):
         v, d = fx["lc_v"], fx["lc_d"]
-        ok, v1c, v2c = lm.do_line_clip([v[:, 0], v[:, 1], v[:, 2]], [v[:, 3], v[:, 4], v[:, 5]], [d[:, k] for k in range(6)])
-    res["line_intersect_model.do_line_clip (ok)"] = (fx["lc_ok"], np.asarray(ok).astype(np.uint8))
-    res["line_intersect_model.do_line_clip (ends)"] = (fx["lc_out"], np.stack([np.asarray(a, f32) for a in list(v1c) + list(v2c)], axis=1))
+        ok, v1c, v2c = view_model.do_line_clip([v[:, 0], v[:, 1], v[:, 2]], [v[:, 3], v[:, 4], v[:, 5]], [d[:, k] for k in range(6)])
+    res["view_model.do_line_clip (ok)"] = (fx["lc_ok"], np.asarray(ok).astype(np.uint8))
+    res["view_model.do_line_clip (ends)"] = (fx["lc_out"], np.stack([np.asarray(a, f32) for a in list(v1c) + list(v2c)], axis=1))
     return res

@@ -16,6 +16,7 @@ import orclib
 import scenery_view_model as sm
 import terrain_view_cases as tvc
 import terrain_view_model as tm
+import view_model
 
 ERR_ARG, ERR_STATE = -1, -3
 f32 = np.float32
@@ -362,7 +363,7 @@ def view_of(case):
 
 
 def args_of(case):
-    kw = dict(behind_sphere_mult=tm.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zoom_f=1.0, smap_pixel_width=0.0, window_width=1920)
+    kw = dict(behind_sphere_mult=view_model.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zoom_f=1.0, smap_pixel_width=0.0, window_width=1920)
     kw.update(case.args)
     return sm.Args(**kw)
 
@@ -470,7 +471,6 @@ def run_case(pkg, t, orc, case, dev=False):
 def run_resident_chain(pkg, t, orc):
     """tiles_create_zvals_dev (zvals, stats) -> tiles_place_scenery_dev -> tiles_terrain_view_dev (not_drawn) -> tiles_scenery_view_dev with not_drawn as its skip bytes,
     on a 3 x 3 batch at S = 128 on one context with nothing read back in between; the model is fed from the read-back records"""
-    import grass_view_model as gm
     S, cap = 128, 160
     lcap = 3 * cap
     tiles = [(x, y) for y in range(-1, 2) for x in range(1, 4)]  # over the island's shore
@@ -483,8 +483,8 @@ def run_resident_chain(pkg, t, orc):
     ocfg = orclib.make_config(mesh_gen_mode=0, mesh_xy=S)
     orc.init(ocfg)
     sc = tm.Scene(orc, ocfg)
-    v = gm.make_view((float(sc.g.get_xval(S + S // 2)), 0.3, 1.5), tvc._unit(1.0, 0.3, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 60.0)
-    bsm = tm.behind_sphere_mult(0.7, 1.6)
+    v = view_model.make_view((float(sc.g.get_xval(S + S // 2)), 0.3, 1.5), tvc._unit(1.0, 0.3, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 60.0)
+    bsm = view_model.behind_sphere_mult(0.7, 1.6)
     ta, a = tm.Args(bsm, float(orc.state().zmin), 1, 0, 0), sm.Args(bsm, 1.0, 0.0, 1920)
     lv, lta, la = tvc.lib_view(pkg, v), tvc.lib_args(pkg, ta), lib_args(pkg, a)
     out = pkg.Terra._scenery_view_outputs(n, cap, lcap, FILL)

@@ -14,8 +14,8 @@
     approx_pixel_width's use, get_smap_ndiv, get_def_smap_ndiv                 src/shadow_map.cpp:57-64
     distance_to_camera, dot_product_ptv                                        src/inlines.h:227, 431
 
-The tile's centre and distance are tests/terrain_view_model.py's, the sphere test tests/tree_view_model.py's restatement of pos_dir_up::sphere_visible_test (with its
-tally of the planes).  Types: np.float32 for float, np.float64 for double, Python int for int.  Which sub-expressions are double: PT_LINE_THRESH*(do_zoom ?
+The tile's centre and distance are tests/terrain_view_model.py's, the sphere test (with its tally of the planes), int(double) and int(float)
+tests/view_model.py's.  Types: np.float32 for float, np.float64 for double, Python int for int.  Which sub-expressions are double: PT_LINE_THRESH*(do_zoom ?
 ZOOM_FACTOR : 1.0) (narrowed by the float return), (do_zoom ? ZOOM_FACTOR : 1.0)*window_width (then int, then the float parameter sscale), 1.3*radius (narrowed by
 the float parameter), 2.0*sscale*radius/dist, 2.2*sscale*radius/dist, 1.0*sscale*radius/dist, 2.0*radius and 2.2*radius (narrowed by get_def_smap_ndiv's float
 parameter), 0.5*radius/approx_pixel_width, 0.75*get_pt_line_thresh()*radius, 1000.0*radius, 0.5*height (narrowed by point's constructor), 0.1*(abs + abs),
@@ -32,9 +32,8 @@ import ctypes
 
 import numpy as np
 
-import grass_view_model as gm
 import terrain_view_model as tm
-import tree_view_model as vm
+import view_model
 
 f32, f64 = np.float32, np.float64
 LEAFY_PLANT, PLANT, ROCK_SHAPE, SURFACE_ROCK, VOXEL_ROCK, ROCK, LOG, STUMP, MUSHROOM = range(9)  # TERRA_SCENERY_*
@@ -49,9 +48,9 @@ TILE_DRAWN, TILE_OPAQUE, TILE_LEAVES = 1, 2, 4
 G_ROCK_SHAPE, G_SURFACE_ROCK, G_ROCK, G_LOG, G_STUMP, G_MUSHROOM, G_STEM, G_BERRIES, G_VOXEL_ROCK, G_PLANT_LEAVES, G_LEAFY_LEAVES, G_PLD_POINTS, G_PLD_LINES = range(13)
 GROUPS = 13
 ZERO, HALF = f32(0.0), f32(0.5)
-cmax, cmin = gm.cmax, gm.cmin
+cmax, cmin, d2i, f2i = view_model.cmax, view_model.cmin, view_model.d2i, view_model.f2i
 
-_libm = gm._libm
+_libm = view_model._libm
 _libm.powf.restype = ctypes.c_float
 _libm.powf.argtypes = [ctypes.c_float, ctypes.c_float]
 
@@ -62,17 +61,6 @@ def powf(a, b):
 
 def new_tally():
     return collections.defaultdict(int)
-
-
-def d2i(x):
-    """int(double) as the reference binary converts it (cvttsd2si): NaN and values outside the int range give INT_MIN"""
-    x = float(x)
-    return int(x) if -2147483649.0 < x < 2147483648.0 else -2 ** 31
-
-
-def f2i(x):
-    x = float(f32(x))
-    return int(x) if -2147483648.0 <= x < 2147483648.0 else -2 ** 31
 
 
 class Args:
@@ -120,13 +108,13 @@ def add_z(p, dz):  # p + point(0.0, 0.0, dz)
 
 
 def distance_to_camera(cx, p):
-    return f32(np.sqrt(gm.p2p_dist_sq(cx.camera(), p)))
+    return f32(np.sqrt(view_model.p2p_dist_sq(cx.camera(), p)))
 
 
 def check_visible(cx, radius, bradius, p):
     """scenery_obj::check_visible in tiled-terrain mode"""
     bradius = f32(bradius)
-    return vm.sphere_visible_test(cx.v, cx.a.behind_sphere_mult, p, radius if bradius == 0.0 else bradius, cx.tally)
+    return view_model.sphere_visible_test(cx.v, cx.a.behind_sphere_mult, p, radius if bradius == 0.0 else bradius, cx.tally)
 
 
 def skip_uw_draw(cx, pos, radius):
@@ -321,7 +309,7 @@ def draw_stump(cx, o):
     ndiv = max(3, min(N_CYL_SIDES, get_def_smap_ndiv(cx, f32(f64(2.2) * f64(o.radius))) if cx.shadow_only else d2i(f64(2.2) * f64(cx.sscale) * f64(o.radius) / f64(dist))))
     tally_ndiv(cx, o, ndiv, 3, N_CYL_SIDES)
     w = POLY | (ndiv << NDIV_SHIFT)
-    delta = gm.sub(cx.camera(), pos_cs)  # camera_delta
+    delta = view_model.sub(cx.camera(), pos_cs)  # camera_delta
     above, steep = bool(delta[2] > height), bool(f64(delta[2]) > f64(0.1) * f64(f32(abs(delta[0]) + abs(delta[1]))))
     if above and steep:
         w |= STUMP_TOP
@@ -397,7 +385,7 @@ def draw_berries(cx, o):
     """up to berries.empty() and burn_amt, which the engine knows"""
     height = o.p[0]
     pos2 = add_z(add_xlate(cx, o.pos), f64(0.5) * f64(height))
-    if not vm.sphere_visible_test(cx.v, cx.a.behind_sphere_mult, pos2, f32(HALF * f32(height + o.radius)), cx.tally):  # sphere_in_camera_view(.., 2)
+    if not view_model.sphere_visible_test(cx.v, cx.a.behind_sphere_mult, pos2, f32(HALF * f32(height + o.radius)), cx.tally):  # sphere_in_camera_view(.., 2)
         return
     dist = distance_to_camera(cx, pos2)
     cx.dist[o.i] = dist

@@ -11,6 +11,7 @@ import numpy as np
 
 import orclib
 import terrain_view_model as tm
+import view_model
 
 ERR_ARG, ERR_STATE = -1, -3
 f32 = np.float32
@@ -176,13 +177,13 @@ def stats_of(pkg_or_orclib, case, wpz):
 
 def view_of(case):
     import grass_view_model as gm
-    v = gm.make_view(**case.view)
+    v = view_model.make_view(**case.view)
     v.valid = case.valid
     return v
 
 
 def args_of(case):
-    kw = dict(behind_sphere_mult=tm.behind_sphere_mult(case.view["angle"], case.view["aspect"]), occluder_zmin=-8.0, water_enabled=1, check_occlusion=1, reflection_pass=0)
+    kw = dict(behind_sphere_mult=view_model.behind_sphere_mult(case.view["angle"], case.view["aspect"]), occluder_zmin=-8.0, water_enabled=1, check_occlusion=1, reflection_pass=0)
     kw.update(case.args)
     return tm.Args(**kw)
 
@@ -308,8 +309,8 @@ def run_resident_chain(pkg, gpu, orc):
     gsc, sc = gm.Scene(orc, cfg, gm.Params(0.25, 0.02, nrnd)), tm.Scene(orc, cfg)
     mnz = np.array([orc.tile_normals(d["z"][i])[1] for i in range(n)], f32)
     zc = float(d["z"][tiles.index((0, 0))][64, 64])
-    v = gm.make_view((3.0, -0.3, zc + 0.5), _unit(1.0, 0.4, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 40.0)
-    a = tm.Args(tm.behind_sphere_mult(0.7, 1.6), float(orc.state().zmin), 1, 1, 0)
+    v = view_model.make_view((3.0, -0.3, zc + 0.5), _unit(1.0, 0.4, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 40.0)
+    a = tm.Args(view_model.behind_sphere_mult(0.7, 1.6), float(orc.state().zmin), 1, 1, 0)
     lv, la = lib_view(pkg, v), lib_args(pkg, a)
     state = np.zeros(n, np.uint8)
     state[tiles.index((1, 0))] = 1  # the tile ahead of the camera, within the grass distance, was occluded in the shadow pass: only the skip byte keeps its grass out

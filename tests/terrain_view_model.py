@@ -9,15 +9,14 @@
     get_rel_dist_to_camera, rel_dist_to_camera_xy_lt, is_visible,
       get_dist_to_camera_in_tiles                                            src/tiled_mesh.h:320-332
     DRAW_DIST_TILES, OCCLUDER_DIST, TILE_RADIUS, NUM_LODS, BCUBE_ZTOLER      src/tiled_mesh.cpp:23, 33; src/tiled_mesh.h:24-25, 32
-    pos_dir_up: behind_sphere_mult, sphere_visible_test,
-      sphere_and_cube_visible_test                                           src/visibility.cpp:83, 119-128, 215-219
+    pos_dir_up::sphere_and_cube_visible_test                                 src/visibility.cpp:215-219
     get_line_clip / check_line_clip, get_region                              src/Math3d.cpp:1029-1052; src/inlines.h:509-512, 522-528
     cube_t::get_cube_center, is_all_zeros                                    src/3DWorld.h:491, 602-604
     p2p_dist_xy, dist_xy_less_than                                           src/inlines.h:183-195
 
-cube_visible and the vector helpers are tests/grass_view_model.py's (a restatement of their own).  Types: np.float32 for float, Python float for double, Python int
-for int / unsigned.  Which sub-expressions are double: the whole of behind_sphere_mult but tterm; in get_lod_level the comparisons of min_normal_z with 0.9, 0.95 and
-0.25, `dist *= 4.0 / 2.0`, `dist /= -log2(2.0*min_normal_z)` (each narrowed back into the float dist) and the loop's comparison with 1.8 / 2.0; log2 and tanf are the C
+behind_sphere_mult, sphere_visible_test, cube_visible and the vector helpers are tests/view_model.py's.  Types: np.float32 for float, Python float for double, Python int
+for int / unsigned.  Which sub-expressions are double: in get_lod_level the comparisons of min_normal_z with 0.9, 0.95 and
+0.25, `dist *= 4.0 / 2.0`, `dist /= -log2(2.0*min_normal_z)` (each narrowed back into the float dist) and the loop's comparison with 1.8 / 2.0; log2 is the C
 library's, called through ctypes.  Equal distances order by batch index (the reference's pointer order is not reproducible).
 
 The tally counts what each test decided, so that a case can show that it exercises what it is named for."""
@@ -26,6 +25,8 @@ import ctypes
 import numpy as np
 
 import grass_view_model as gm
+
+import view_model
 
 f32 = np.float32
 NUM_LODS, TILE_RADIUS = 5, 6
@@ -36,9 +37,9 @@ ABSENT, TOO_FAR, NOT_VISIBLE, OCCLUDED_BEFORE, OCCLUDED, DRAWN = range(6)
 WAS_OCCLUDER = 0x80
 FLAG_ABSENT, FLAG_NO_OCCLUDER, FLAG_SHADOW_MAPS = 1, 2, 4
 NO_CRACK = 255
-cmax, cmin, dot, sub, mag_sq = gm.cmax, gm.cmin, gm.dot, gm.sub, gm.mag_sq
+cmax, cmin, sub, sphere_visible_test = view_model.cmax, view_model.cmin, view_model.sub, view_model.sphere_visible_test
 
-_libm = gm._libm
+_libm = view_model._libm
 _libm.log2.restype = ctypes.c_double
 _libm.log2.argtypes = [ctypes.c_double]
 
@@ -56,17 +57,6 @@ class Args:
     def __init__(self, behind_sphere_mult=1.0, occluder_zmin=0.0, water_enabled=1, check_occlusion=1, reflection_pass=0):
         self.behind_sphere_mult, self.occluder_zmin = f32(behind_sphere_mult), f32(occluder_zmin)
         self.water_enabled, self.check_occlusion, self.reflection_pass = int(water_enabled), int(check_occlusion), int(reflection_pass)
-
-
-def behind_sphere_mult(angle, aspect):
-    """max(1.0, A*A)*max(1.0, 2.0f/((double)tterm*tterm*(1.0 + A*A))) narrowed into the float member (src/visibility.cpp:83)"""
-    A = np.float64(f32(aspect))
-    tterm = np.float64(f32(_libm.tanf(f32(angle))))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        q = np.float64(2.0) / (tterm * tterm * (1.0 + A * A))
-        a = A * A if 1.0 < A * A else np.float64(1.0)
-        b = q if 1.0 < q else np.float64(1.0)
-        return f32(a * b)
 
 
 class Scene:
@@ -132,30 +122,13 @@ def p2p_dist_xy_sq(a, b):
 
 def get_rel_dist_to_camera(sc, v, t, xy_dist=True):
     c = get_center(sc, t)
-    d = f32(np.sqrt(p2p_dist_xy_sq(v.pos, c))) if xy_dist else f32(np.sqrt(gm.p2p_dist_sq(v.pos, c)))
+    d = f32(np.sqrt(p2p_dist_xy_sq(v.pos, c))) if xy_dist else f32(np.sqrt(view_model.p2p_dist_sq(v.pos, c)))
     return f32(cmax(ZERO, f32(d - t.radius)) / sc.scaled_tile_radius)
 
 
 def rel_dist_to_camera_xy_lt(sc, v, t, rel_dist):
     dval = f32(f32(rel_dist * sc.scaled_tile_radius) + t.radius)
     return bool(p2p_dist_xy_sq(v.pos, get_center(sc, t)) < f32(dval * dval))
-
-
-def sphere_visible_test(v, bsm, pos, radius, tally=None):
-    if not v.valid:
-        return bool(radius >= 0.0)
-    pv = sub(pos, v.pos)
-    if dot(v.dir, pv) < 0.0:
-        r = bool(radius > 0.0 and mag_sq(pv) < f32(f32(radius * radius) * bsm))
-        if tally is not None and radius > 0.0:
-            tally["behind_true" if r else "behind_false"] += 1
-        return r
-    dist = f32(np.sqrt(mag_sq(pv)))
-    if abs(dot(v.upv_, pv)) > f32(f32(dist * v.sterm) + radius):
-        return False
-    if abs(dot(v.cp, pv)) > f32(f32(dist * v.x_sterm) + radius):
-        return False
-    return bool(f32(dist + radius) > v.near_ and f32(dist - radius) < v.far_)
 
 
 def get_bsphere_radius_inc_water(sc, a, t, tally=None):
@@ -176,7 +149,7 @@ def is_visible(sc, v, a, t, tally=None):
         if tally is not None:
             tally["sphere_all"] += 1
         return True
-    r = gm.cube_visible(v, cube)
+    r = view_model.cube_visible(v, cube)
     if tally is not None:
         tally["cube_accepted" if r else "cube_rejected"] += 1
     return r
@@ -243,7 +216,7 @@ class Occluder:
         self.index, self.bcube, self.sub_cubes = index, get_mesh_bcube(sc, t), []
         for s in range(16):
             c = get_mesh_sub_bcube(sc, t, s >> 2, s & 3)
-            if not gm.cube_visible(v, c):
+            if not view_model.cube_visible(v, c):
                 c = [[ZERO, ZERO], [ZERO, ZERO], [ZERO, ZERO]]
                 tally["columns_zeroed"] += 1
             else:

@@ -6,7 +6,7 @@ import contextlib
 import pytest
 
 import grass_view_cases as gc
-import grass_view_model as gm
+import view_model
 import test_grass_view_emul as tge
 
 pytestmark = pytest.mark.gpu
@@ -47,7 +47,7 @@ def test_cases_simple_form(pkg, gpu, orc, name):
 def test_make_view(pkg, gpu):
     for kw in tge.VIEWS:
         got = gpu.make_view(kw["pos"], kw["dir"], kw["up"], kw["angle"], kw["aspect"], kw["near"], kw["far"])
-        assert bytes(got) == gm.make_view(**kw).words(), kw
+        assert bytes(got) == view_model.make_view(**kw).words(), kw
 
 
 def test_resident_chain(pkg, gpu, orc):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import terrain_view_cases as tc
-import terrain_view_model as tm
+import view_model
 import test_grass_view_emul as tge
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +43,7 @@ def test_cases_simple_form(pkg, gpu, orc, name):
 def test_behind_sphere_mult(pkg, gpu):
     for kw in tge.VIEWS:
         got = np.float32(gpu.view_behind_sphere_mult(kw["angle"], kw["aspect"]))
-        assert got.tobytes() == tm.behind_sphere_mult(kw["angle"], kw["aspect"]).tobytes(), kw
+        assert got.tobytes() == view_model.behind_sphere_mult(kw["angle"], kw["aspect"]).tobytes(), kw
 
 
 def test_resident_chain(pkg, gpu, orc):

@@ -10,6 +10,7 @@ import pytest
 
 import grass_view_cases as gc
 import grass_view_model as gm
+import view_model
 import orclib
 
 CASES = gc.cases()
@@ -48,12 +49,12 @@ def test_model_alone(orc):
 def test_make_view(pkg, emul):
     """terra_make_view against the model's constructor (the C library's tanf / sinf / atanf through ctypes), bit for bit; refused where the constructor asserts"""
     for kw in VIEWS:
-        want = gm.make_view(**kw)
+        want = view_model.make_view(**kw)
         got = emul.make_view(kw["pos"], kw["dir"], kw["up"], kw["angle"], kw["aspect"], kw["near"], kw["far"])
         assert bytes(got) == want.words(), (kw, [float(x) for x in got.upv], [float(x) for x in want.upv_])
     for bad in BAD_VIEWS:
         kw = dict(VIEWS[0], **bad)
-        assert gm.make_view(**kw) is None, bad
+        assert view_model.make_view(**kw) is None, bad
         out = pkg.View()
         ctypes.memset(ctypes.addressof(out), 0x5A, ctypes.sizeof(out))
         f3 = lambda a: (ctypes.c_float * 3)(*a)  # noqa: E731

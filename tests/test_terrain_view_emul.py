@@ -10,6 +10,7 @@ import pytest
 
 import terrain_view_cases as tc
 import terrain_view_model as tm
+import view_model
 import test_grass_view_emul as tge
 
 CASES = tc.cases()
@@ -43,7 +44,7 @@ def test_model_alone(orc):
 def test_behind_sphere_mult(pkg, emul):
     """terra_view_behind_sphere_mult against the model (the C library's tanf through ctypes), bit for bit, for the views of test_grass_view_emul.VIEWS"""
     for kw in tge.VIEWS:
-        want = tm.behind_sphere_mult(kw["angle"], kw["aspect"])
+        want = view_model.behind_sphere_mult(kw["angle"], kw["aspect"])
         got = f32(emul.view_behind_sphere_mult(kw["angle"], kw["aspect"]))
         assert got.tobytes() == want.tobytes(), (kw, got, want)
     assert emul.lib.terra_view_behind_sphere_mult(0.5, 1.0, None) == tc.ERR_ARG

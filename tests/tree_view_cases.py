@@ -14,6 +14,7 @@ import terrain_view_cases as tvc
 import terrain_view_model as tm
 import tree_ao_model as tam
 import tree_view_model as vm
+import view_model
 
 ERR_ARG, ERR_STATE = -1, -3
 f32 = np.float32
@@ -245,7 +246,7 @@ def view_of(case):
 
 
 def args_of(case):
-    kw = dict(behind_sphere_mult=tm.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zoom_f=1.0, tree_depth_scale=1.0, window_width=1920)
+    kw = dict(behind_sphere_mult=view_model.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zoom_f=1.0, tree_depth_scale=1.0, window_width=1920)
     kw.update(case.args)
     return vm.Args(**kw)
 
@@ -358,9 +359,8 @@ def run_resident_chain(pkg, t, orc):
     ocfg = orclib.make_config(mesh_gen_mode=0, mesh_xy=S)
     orc.init(ocfg)
     sc = tm.Scene(orc, ocfg)
-    import grass_view_model as gm
-    v = gm.make_view((float(sc.g.get_xval(S + S // 2)), 0.3, 1.5), tvc._unit(1.0, 0.3, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 60.0)
-    bsm = tm.behind_sphere_mult(0.7, 1.6)
+    v = view_model.make_view((float(sc.g.get_xval(S + S // 2)), 0.3, 1.5), tvc._unit(1.0, 0.3, -0.1), (0.0, 0.0, 1.0), 0.7, 1.6, 0.05, 60.0)
+    bsm = view_model.behind_sphere_mult(0.7, 1.6)
     ta, a = tm.Args(bsm, float(orc.state().zmin), 1, 0, 0), vm.Args(bsm, 1.0, 1.0, 1920)
     lv, lta, la = tvc.lib_view(pkg, v), tvc.lib_args(pkg, ta), lib_args(pkg, a)
     out = pkg.Terra._tree_view_outputs(n, cap, FILL)

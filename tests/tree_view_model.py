@@ -13,11 +13,10 @@ library's bodies):
       are_leaves_visible, draw_trunk (down to nsides), stt[]                   src/sm_tree.cpp:46-53, 705-777, 832-838, 1007-1017, 1081-1102
     get_xy_radius, get_trunk_bsphere_radius                                    src/small_tree.h:77-78
     get_default_tree_depth, get_tree_z_bottom (the tiled-terrain branch)       src/Tree.cpp:209-214
-    pos_dir_up::sphere_visible_test                                            src/visibility.cpp:119-128
     cube_t::assign_or_union_with_cube, cylinder_3dw::get_center                src/3DWorld.h:512-515, 748
 
-The tile's centre, box and distance are tests/terrain_view_model.py's, cube_visible and point_visible_test tests/grass_view_model.py's, the sizes of a record
-tests/tree_ao_model.py's (restatements of their own).  Types: np.float32 for float, Python float for double, Python int for int / unsigned.  Which sub-expressions are
+The tile's centre, box and distance are tests/terrain_view_model.py's, the view tests (sphere_visible_test with its tally of the planes, cube_visible,
+point_visible_test) tests/view_model.py's, the sizes of a record tests/tree_ao_model.py's (restatements of their own).  Types: np.float32 for float, Python float for double, Python int for int / unsigned.  Which sub-expressions are
 double: `(is_pine ? 1.05 : 0.8)*height`, `pos.z - 0.2*width`, the factor (0.5 + 0.5/tree_scale) of the tree depth, both arms of get_xy_radius's max, `0.2*width` and
 `0.5*height` times a direction (operator*(S, pointT<T>) multiplies in S and narrows each component), `0.3*height + 0.2*width`, `r1 + 0.5*(..)` of the trunk's bounding
 sphere, `-0.5*radius`, `0.25*size_scale/dist`, `1.0 - far_weight`, and the comparisons of dscale and weight with double literals.  sphere_in_camera_view(.., 2) is
@@ -26,10 +25,9 @@ id alone.
 
 The tally counts what each test decided, so that a case can show that it exercises what it is named for."""
 import numpy as np
-
-import grass_view_model as gm
 import terrain_view_model as tm
 import tree_ao_model as tam
+import view_model
 
 f32 = np.float32
 T_PINE, T_DECID, T_TDECID, T_BUSH, T_PALM, T_SH_PINE = range(6)
@@ -43,7 +41,7 @@ SS = [f32(x) for x in (0.4, 0.8, 0.7, 0.8, 0.6, 0.4)]        # stt[].ss
 ZERO, ONE = f32(0.0), f32(1.0)
 TRUNK_NONE, TRUNK_POLY_ALL, TRUNK_POLY_SKIPPED, TRUNK_POINTS = range(4)
 NEAR_LEAVES, FAR_LEAVES, DITHERED, PALMS, DRAW_ALL_NEAR, DRAW_ALL_FAR, ALL_VISIBLE, NEEDS_HIGH, NEEDS_LOW, CONTAINS_CAMERA = 0x4, 0x8, 0x10, 0x20, 0x40, 0x80, 0x100, 0x200, 0x400, 0x800
-cmax, cmin, dot, sub = gm.cmax, gm.cmin, gm.dot, gm.sub
+cmax, cmin, sub, sphere_visible_test = view_model.cmax, view_model.cmin, view_model.sub, view_model.sphere_visible_test
 
 TALLY = ("tiles", "skipped", "empty", "dropped", "trunk_none", "trunk_poly_all", "trunk_poly_skipped", "trunk_points", "trunks_culled", "weight0", "weight_mid", "weight1",
          "palms_yes", "palms_no", "palms_inst_clause", "palms_inst_clause_fails", "contains_camera", "sorted_lists", "sorted_ties", "draw_all_near", "near_not_all",
@@ -74,46 +72,6 @@ def scale_d(d, vec):  # operator*(S const v, pointT<T> const &p) with S = double
 
 def scale_f(vec, s):  # pointT::operator*(T const val)
     return [f32(vec[0] * s), f32(vec[1] * s), f32(vec[2] * s)]
-
-
-def sphere_visible_test(v, bsm, pos, radius, tally=None):
-    """pos_dir_up::sphere_visible_test, with a tally of which plane decided for a sphere whose centre lies beyond it"""
-    radius = f32(radius)
-    if not v.valid:
-        if tally is not None:
-            tally["invalid_view_tests"] += 1
-        return bool(radius >= 0.0)
-    pv = sub(pos, v.pos)
-    if dot(v.dir, pv) < 0.0:
-        r = bool(radius > 0.0 and gm.mag_sq(pv) < f32(f32(radius * radius) * bsm))
-        if tally is not None and radius > 0.0:
-            tally["behind_true" if r else "behind_false"] += 1
-        return r
-    dist = f32(np.sqrt(gm.mag_sq(pv)))
-    du, dc = abs(dot(v.upv_, pv)), abs(dot(v.cp, pv))
-    if du > f32(f32(dist * v.sterm) + radius):
-        if tally is not None:
-            tally["up_reject"] += 1
-        return False
-    if tally is not None and radius > 0.0 and du > f32(dist * v.sterm):
-        tally["up_straddle"] += 1
-    if dc > f32(f32(dist * v.x_sterm) + radius):
-        if tally is not None:
-            tally["side_reject"] += 1
-        return False
-    if tally is not None and radius > 0.0 and dc > f32(dist * v.x_sterm):
-        tally["side_straddle"] += 1
-    near_ok, far_ok = bool(f32(dist + radius) > v.near_), bool(f32(dist - radius) < v.far_)
-    if tally is not None and radius > 0.0:
-        if not near_ok:
-            tally["near_reject"] += 1
-        elif dist <= v.near_:
-            tally["near_straddle"] += 1
-        if near_ok and not far_ok:
-            tally["far_reject"] += 1
-        elif near_ok and dist >= v.far_:
-            tally["far_straddle"] += 1
-    return near_ok and far_ok
 
 
 class Globals:
@@ -177,7 +135,7 @@ class SmallTree:
         if not self.rotated:
             return [ZERO, ZERO, ONE]
         d = sub(self.p2, self.p1)
-        vmag = f32(np.sqrt(gm.mag_sq(d)))
+        vmag = f32(np.sqrt(view_model.mag_sq(d)))
         return d if vmag < TOLERANCE else [f32(d[0] / vmag), f32(d[1] / vmag), f32(d[2] / vmag)]
 
     def get_xy_radius(self):  # max(1.5*branch_xy_scale*width, 0.5*height)
@@ -195,7 +153,7 @@ class SmallTree:
         if not self.rotated:
             ext = abs(f32(self.p1[2] - self.p2[2]))
         else:
-            ext = f32(np.sqrt(gm.mag_sq(sub(self.p1, self.p2))))
+            ext = f32(np.sqrt(view_model.mag_sq(sub(self.p1, self.p2))))
         return f32(float(self.r1) + 0.5 * float(ext))
 
     def are_leaves_visible(self, v, g, xlate, tally):
@@ -223,7 +181,7 @@ class SmallTree:
                 tally["byte_culled"] += 1
                 return 0
         size_scale = f32(f32(f32(a.zoom_f * SS[self.type]) * self.width) * f32(a.window_width))
-        dist = f32(np.sqrt(gm.p2p_dist_sq(v.pos, add(self.pos, xlate))))  # distance_to_camera(pos + xlate)
+        dist = f32(np.sqrt(view_model.p2p_dist_sq(v.pos, add(self.pos, xlate))))  # distance_to_camera(pos + xlate)
         if not a.shadow_pass and size_scale < dist:
             tally["byte_small"] += 1
             return 0
@@ -300,7 +258,7 @@ def draw_pine_trees(sc, v, g, txy, st, trmax, recs, ovs, xlate, tally):
         return cmax(ZERO, cmin(ONE, f32(GEOMORPH_THRESH * f32(dist_scale(has_palm) - ONE))))  # CLIP_TO_01
 
     def cube_vis():
-        return gm.cube_visible(v, [[f32(bc[i][0] + xlate[i]), f32(bc[i][1] + xlate[i])] for i in range(3)])  # all_bcube + xlate
+        return view_model.cube_visible(v, [[f32(bc[i][0] + xlate[i]), f32(bc[i][1] + xlate[i])] for i in range(3)])  # all_bcube + xlate
 
     force = bool(a.shadow_pass)
     has_palm = num_palm > 0
@@ -363,7 +321,7 @@ def draw_pine_trees(sc, v, g, txy, st, trmax, recs, ovs, xlate, tally):
             tally["palms_yes" if palms else "palms_no"] += 1
     near, far = None, False  # near: what the high-detail sweep did when the group is not instanced: "all", "culled" or the list; far: the low-detail sweep drew the pines
     for low_detail in sweeps:  # draw_tree_leaves_lod -> draw_pine_leaves(s, 0, low_detail, draw_all, contains_camera(), xlate)
-        draw_all = bool(low_detail or gm.point_visible_test(v, center))
+        draw_all = bool(low_detail or view_model.point_visible_test(v, center))
         flags |= (FAR_LEAVES if low_detail else NEAR_LEAVES) | ((DRAW_ALL_FAR if low_detail else DRAW_ALL_NEAR) if draw_all else 0)
         if not low_detail:
             tally["draw_all_near" if draw_all else "near_not_all"] += 1
@@ -385,7 +343,7 @@ def draw_pine_trees(sc, v, g, txy, st, trmax, recs, ovs, xlate, tally):
         tally["pine_list"] += 1
         if contains_camera:  # sort_front_to_back: get_back_to_front_ordering
             ref_pos = sub(v.pos, xlate)
-            to_draw = sorted((gm.p2p_dist_sq(s.pos, ref_pos), j) for j, s in enumerate(trees) if s is not None and s.are_leaves_visible(v, g, xlate, tally))
+            to_draw = sorted((view_model.p2p_dist_sq(s.pos, ref_pos), j) for j, s in enumerate(trees) if s is not None and s.are_leaves_visible(v, g, xlate, tally))
             tally["sorted_lists"] += 1
             order = [j for _, j in to_draw]
         else:

@@ -15,6 +15,7 @@ import numpy as np
 import orclib
 import terrain_view_cases as tc
 import terrain_view_model as tm
+import view_model
 import water_view_model as wm
 
 ERR_ARG, ERR_STATE = -1, -3
@@ -228,17 +229,16 @@ def water_cases():
 
 
 def view_of(case, wpz):
-    import grass_view_model as gm
     kw = dict(case.view)
     if case.cam_z_water:
         kw["pos"] = (kw["pos"][0], kw["pos"][1], float(wpz))
-    v = gm.make_view(**kw)
+    v = view_model.make_view(**kw)
     v.valid = case.valid
     return v
 
 
 def args_of(case):
-    kw = dict(behind_sphere_mult=tm.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zmin=-8.0, zmax=45.0, water_enabled=1, check_occlusion=1, reflection_pass=1)
+    kw = dict(behind_sphere_mult=view_model.behind_sphere_mult(case.view["angle"], case.view["aspect"]), zmin=-8.0, zmax=45.0, water_enabled=1, check_occlusion=1, reflection_pass=1)
     kw.update({k: v for k, v in case.args.items() if k != "no_status"})
     return wm.Args(**kw)
 
@@ -403,7 +403,6 @@ def run_resident_chain(pkg, gpu, orc):
     """tiles_create_zvals_dev (zvals, stats, normals, min_normal_z) -> tiles_reflection_view_dev -> tiles_terrain_view_dev (pass 0, on the occl_state the reflection
     pass left) -> tiles_water_view_dev (on the pass-0 status) on a 5 x 5 batch at S = 128 on one context with nothing read back in between, against the models fed
     with the downloaded stats.  The camera stands over the sea and looks back at the land: dry tiles see the water between them and the camera, or do not"""
-    import grass_view_model as gm
     S = 128
     tiles = CHAIN_TILES
     n, Z, T = len(tiles), S + 2, S + 1
@@ -412,8 +411,8 @@ def run_resident_chain(pkg, gpu, orc):
     ocfg = orclib.make_config(mesh_gen_mode=0, mesh_xy=S)
     orc.init(ocfg)
     sc, os_ = tm.Scene(orc, ocfg), orc.state()
-    v = gm.make_view((36.0, 20.0, 0.0), _unit(-1.0, -0.5, -0.1), (0.0, 0.0, 1.0), 0.9, 1.6, 0.05, 100.0)
-    a = wm.Args(tm.behind_sphere_mult(0.9, 1.6), float(os_.zmin), float(os_.zmax), 1, 1, 1)
+    v = view_model.make_view((36.0, 20.0, 0.0), _unit(-1.0, -0.5, -0.1), (0.0, 0.0, 1.0), 0.9, 1.6, 0.05, 100.0)
+    a = wm.Args(view_model.behind_sphere_mult(0.9, 1.6), float(os_.zmin), float(os_.zmax), 1, 1, 1)
     a0 = tm.Args(a.behind_sphere_mult, a.occluder_zmin, 1, 1, 0)
     lv = tc.lib_view(pkg, v)
     state = np.zeros(n, np.uint8)

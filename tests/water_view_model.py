@@ -15,11 +15,11 @@ pass 1 (low_detail, :1913-1914).  Types: every statement of can_have_reflection[
 the camera, the boxes and z_over_xy are floats and no literal promotes them; `min_normal_z > 0.1` compares in double.  The recursion is the reference's own, with
 vis_ref_call; the loop runs in batch order, sequentially, and was_last_occluded() reads what the loop has written so far."""
 import numpy as np
-
-import grass_view_model as gm
 import terrain_view_model as tm
+import view_model
 
 f32 = np.float32
+closest_pt = view_model.closest_pt
 NO_REFLECTION = 6
 NOT_ASKED, NO_WATER, WALK_NOTHING, HAS_WATER, WALK_FOUND = range(5)
 TALLY = tm.TALLY + ("no_reflection", "refl_disabled", "refl_all_water", "refl_has_water", "refl_walk_found", "refl_walk_nothing", "found_x_only", "found_y_only",
@@ -61,10 +61,6 @@ def all_water(sc, t):
 def get_water_bcube(sc, t):
     xv1, yv1 = sc.g.get_xval(t.wx1 + sc.dxoff), sc.g.get_yval(t.wy1 + sc.dyoff)
     return [[xv1, f32(xv1 + f32(f32(t.wx2 - t.wx1) * sc.DX_VAL))], [yv1, f32(yv1 + f32(f32(t.wy2 - t.wy1) * sc.DY_VAL))], [sc.water_plane_z, sc.water_plane_z]]
-
-
-def closest_pt(d, p):
-    return [tm.cmin(d[i][1], tm.cmax(d[i][0], p[i])) for i in range(3)]  # clamp_pt: min(d[i][1], max(d[i][0], pt[i]))
 
 
 def p2p_dist_xy(a, b):
@@ -116,7 +112,7 @@ class Walk:
         sc, tally, t, camera = self.sc, self.tally, self.tiles[i], self.v.pos
         tally["visits"] += 1
         b = self.bcube(i)
-        bcube = [list(b[0]), list(b[1]), [tm.cmin(b[2][0], self.a.zmin), tm.cmax(b[2][1], self.a.zmax)]]  # make sure the line isn't clipped in z
+        bcube = [list(b[0]), list(b[1]), [view_model.cmin(b[2][0], self.a.zmin), view_model.cmax(b[2][1], self.a.zmax)]]  # make sure the line isn't clipped in z
         if dim_ix < 2 and not tm.check_line_clip(camera, corners[dim_ix], bcube):
             tally["cut_clip%d" % dim_ix] += 1
             return False
@@ -129,7 +125,7 @@ class Walk:
             tally["cut_occluded"] += 1
         if not self.state[i] == 1 and has_water(sc, t):  # !was_last_occluded() && has_water()
             water_bcube = get_water_bcube(sc, t)
-            if gm.cube_visible(self.v, water_bcube):
+            if view_model.cube_visible(self.v, water_bcube):
                 cp = closest_pt(water_bcube, corners[2])
                 with np.errstate(divide="ignore", invalid="ignore"):
                     den = p2p_dist_xy(camera, cp)
