@@ -914,8 +914,8 @@ int terra_tiles_grass_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
                                uint32_t *d_group_counts, uint32_t *d_counts, uint8_t *d_pass) {
 	TERRA_CHECK_CTX if (!view) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
-	TERRA_TRY ctx->eng.tiles_grass_view_dev(tile_xy, n, dxoff, dyoff, d_zvals, d_stats, (terra::grass_block_pod_t const *)d_grass_blocks, d_skip, v, capacity, d_insts, d_aux,
-		d_group_counts, d_counts, d_pass); TERRA_CATCH
+	terra::grass_view_io_t const io = {d_zvals, d_stats, (terra::grass_block_pod_t const *)d_grass_blocks, d_skip, d_insts, d_aux, d_group_counts, d_counts, d_pass};
+	TERRA_TRY ctx->eng.tiles_grass_view_dev(tile_xy, n, dxoff, dyoff, v, capacity, io); TERRA_CATCH
 }
 int terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const float *h_zvals, const terra_tile_stats *h_stats,
                            const terra_grass_block *h_grass_blocks, const uint8_t *h_skip, const terra_view *view, uint32_t capacity, float *h_insts, uint32_t *h_aux,
@@ -924,8 +924,8 @@ int terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	TERRA_TRY
 		ctx->eng.grass_view_check(v); // the scene, the tile size (the arrays are sized by S), the view, num_rnd_grass_blocks: before anything is staged
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_zvals || !h_stats || !h_grass_blocks || !h_group_counts || !h_counts || (capacity && !h_insts)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		terra::grass_view_io_t const h = {h_zvals, h_stats, (terra::grass_block_pod_t const *)h_grass_blocks, h_skip, h_insts, h_aux, h_group_counts, h_counts, h_pass};
+		if (!terra::grass_view_io_check(tile_xy, n, capacity, h, false)) return TERRA_OK;
 		size_t const S = ctx->eng.tile_size(), dim = 1 + (S - 1)/4, nbins = (size_t)terra::GRASS_VIEW_LODS*ctx->eng.ls.num_rnd_grass_blocks;
 		struct inst_t {float v[2];};
 		terra_stage st(ctx->eng);
@@ -933,8 +933,8 @@ int terra_tiles_grass_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 			k = st.opt_in(h_skip, n), r = st.temp((size_t)n*capacity*sizeof(inst_t)), a = st.add(nullptr, nullptr, (size_t)n*capacity*4, h_aux != nullptr),
 			gc = st.out(h_group_counts, (size_t)n*nbins*4), c = st.temp((size_t)n*4), p = st.opt_out(h_pass, n);
 		st.begin();
-		ctx->eng.tiles_grass_view_dev(tile_xy, n, dxoff, dyoff, st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<terra::grass_block_pod_t>(g), st.dev<uint8_t>(k), v, capacity,
-			st.dev<float>(r), st.dev<uint32_t>(a), st.dev<uint32_t>(gc), st.dev<uint32_t>(c), st.dev<uint8_t>(p));
+		ctx->eng.tiles_grass_view_dev(tile_xy, n, dxoff, dyoff, v, capacity, terra::grass_view_io_t{st.dev<float>(z), st.dev<terra_tile_stats>(s), st.dev<terra::grass_block_pod_t>(g),
+			st.dev<uint8_t>(k), st.dev<float>(r), st.dev<uint32_t>(a), st.dev<uint32_t>(gc), st.dev<uint32_t>(c), st.dev<uint8_t>(p)});
 		st.end();
 		st.end_counted(r, c, (inst_t *)h_insts, h_counts, n, capacity);
 		if (h_aux) {st.end_counted(a, c, h_aux, h_counts, n, capacity);}
@@ -1203,9 +1203,10 @@ int terra_tiles_tree_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::tree_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_tree_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, d_stats, d_skip, d_trmax, (terra::tree_place_pod_t const *)d_pine, d_pine_counts, capacity,
-		(terra::trunk_override_pod_t const *)d_trunk_override, (terra::tree_view_tile_pod_t *)d_tile_out, d_all_bcube, (terra::tree_view_inst_pod_t *)d_pine_insts,
-		(terra::tree_view_inst_pod_t *)d_palm_insts, d_inst_counts, d_leaf_list, d_leaf_counts, d_trunk); TERRA_CATCH
+	terra::tree_view_io_t const io = {d_stats, d_skip, d_trmax, (terra::tree_place_pod_t const *)d_pine, d_pine_counts, (terra::trunk_override_pod_t const *)d_trunk_override,
+		(terra::tree_view_tile_pod_t *)d_tile_out, d_all_bcube, (terra::tree_view_inst_pod_t *)d_pine_insts, (terra::tree_view_inst_pod_t *)d_palm_insts, d_inst_counts, d_leaf_list,
+		d_leaf_counts, d_trunk};
+	TERRA_TRY ctx->eng.tiles_tree_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, capacity, io); TERRA_CATCH
 }
 int terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
                           const terra_tree_view_args *args, const terra_tile_stats *h_stats, const uint8_t *h_skip, const float *h_trmax, const terra_tree_place *h_pine,
@@ -1217,11 +1218,10 @@ int terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, in
 	terra::tree_view_args_pod_t a; memcpy(&a, args, sizeof(a));
 	TERRA_TRY
 		ctx->eng.tree_view_check(v, a); // the scene, the tile size, the view, the args and the instance table: before anything is staged
-		if ((uint64_t)n*capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_tree_view: n*capacity must fit 32 bits");
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_stats || !h_pine_counts || !h_tile_out || !h_all_bcube || !h_inst_counts || !h_leaf_counts ||
-		    (capacity && (!h_pine || !h_pine_insts || !h_palm_insts || !h_leaf_list || !h_trunk))) return terra::fail(TERRA_ERR_ARG, "null argument");
 		typedef terra::tree_view_inst_pod_t inst_t;
+		terra::tree_view_io_t const h = {h_stats, h_skip, h_trmax, (terra::tree_place_pod_t const *)h_pine, h_pine_counts, (terra::trunk_override_pod_t const *)h_trunk_override,
+			(terra::tree_view_tile_pod_t *)h_tile_out, h_all_bcube, (inst_t *)h_pine_insts, (inst_t *)h_palm_insts, h_inst_counts, h_leaf_list, h_leaf_counts, h_trunk};
+		if (!terra::tree_view_io_check(tile_xy, n, capacity, h, false)) return TERRA_OK;
 		size_t const nc = (size_t)n*capacity;
 		terra_stage st(ctx->eng);
 		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), sk = st.opt_in(h_skip, n), tr = st.opt_in(h_trmax, (size_t)n*4), p = st.in(h_pine, nc*sizeof(terra_tree_place)),
@@ -1229,9 +1229,9 @@ int terra_tiles_tree_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, in
 			bc = st.out(h_all_bcube, (size_t)n*24), pi = st.temp(nc*sizeof(inst_t)), mi = st.temp(nc*sizeof(inst_t)), ic = st.out(h_inst_counts, (size_t)n*8), ll = st.temp(nc*4),
 			lc = st.out(h_leaf_counts, (size_t)n*8), tk = st.temp(nc);
 		st.begin();
-		ctx->eng.tiles_tree_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, st.dev<terra_tile_stats>(s), st.dev<uint8_t>(sk), st.dev<float>(tr), st.dev<terra::tree_place_pod_t>(p),
-			st.dev<uint32_t>(pc), capacity, st.dev<terra::trunk_override_pod_t>(ov), st.dev<terra::tree_view_tile_pod_t>(to), st.dev<float>(bc), st.dev<inst_t>(pi), st.dev<inst_t>(mi),
-			st.dev<uint32_t>(ic), st.dev<uint32_t>(ll), st.dev<uint32_t>(lc), st.dev<uint8_t>(tk));
+		ctx->eng.tiles_tree_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, capacity, terra::tree_view_io_t{st.dev<terra_tile_stats>(s), st.dev<uint8_t>(sk), st.dev<float>(tr),
+			st.dev<terra::tree_place_pod_t>(p), st.dev<uint32_t>(pc), st.dev<terra::trunk_override_pod_t>(ov), st.dev<terra::tree_view_tile_pod_t>(to), st.dev<float>(bc), st.dev<inst_t>(pi),
+			st.dev<inst_t>(mi), st.dev<uint32_t>(ic), st.dev<uint32_t>(ll), st.dev<uint32_t>(lc), st.dev<uint8_t>(tk)});
 		st.end();
 		for (uint32_t t = 0; t < n; ++t) { // of every tile only what the counts name: the rest of the caller's arrays stays as it was
 			size_t const o = (size_t)t*capacity;
@@ -1254,8 +1254,9 @@ int terra_tiles_scenery_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::scenery_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_scenery_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, d_stats, d_skip, (terra::scenery_place_pod_t const *)d_objs, d_counts, capacity,
-		d_radius_override, (terra::scenery_view_tile_pod_t *)d_tile_out, d_draw, d_size_scale, d_dist, d_list, list_capacity, d_group_counts); TERRA_CATCH
+	terra::scenery_view_io_t const io = {d_stats, d_skip, (terra::scenery_place_pod_t const *)d_objs, d_counts, d_radius_override, (terra::scenery_view_tile_pod_t *)d_tile_out, d_draw,
+		d_size_scale, d_dist, d_list, d_group_counts};
+	TERRA_TRY ctx->eng.tiles_scenery_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, capacity, list_capacity, io); TERRA_CATCH
 }
 int terra_tiles_scenery_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
                              const terra_scenery_view_args *args, const terra_tile_stats *h_stats, const uint8_t *h_skip, const terra_scenery_place *h_objs,
@@ -1266,20 +1267,18 @@ int terra_tiles_scenery_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 	terra::scenery_view_args_pod_t a; memcpy(&a, args, sizeof(a));
 	TERRA_TRY
 		ctx->eng.scenery_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
-		if ((uint64_t)n*capacity > 0xFFFFFFFFull || (uint64_t)n*list_capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_scenery_view: n*capacity and n*list_capacity must fit 32 bits");
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_stats || !h_counts || !h_tile_out || !h_group_counts || (capacity && (!h_objs || !h_draw || !h_size_scale || !h_dist)) || (list_capacity && !h_list)) {
-			return terra::fail(TERRA_ERR_ARG, "null argument");
-		}
+		terra::scenery_view_io_t const h = {h_stats, h_skip, (terra::scenery_place_pod_t const *)h_objs, h_counts, h_radius_override, (terra::scenery_view_tile_pod_t *)h_tile_out, h_draw,
+			h_size_scale, h_dist, h_list, h_group_counts};
+		if (!terra::scenery_view_io_check(tile_xy, n, capacity, list_capacity, h, false)) return TERRA_OK;
 		size_t const nc = (size_t)n*capacity, nl = (size_t)n*list_capacity;
 		terra_stage st(ctx->eng);
 		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), sk = st.opt_in(h_skip, n), ob = st.in(h_objs, nc*sizeof(terra_scenery_place)), pc = st.in(h_counts, (size_t)n*4),
 			ov = st.opt_in(h_radius_override, nc*4), to = st.out(h_tile_out, (size_t)n*sizeof(terra_scenery_view_tile)), dr = st.temp(nc*4), sz = st.temp(nc*4), di = st.temp(nc*4),
 			ll = st.temp(nl*4), gc = st.out(h_group_counts, (size_t)n*TERRA_SCV_GROUPS*4);
 		st.begin();
-		ctx->eng.tiles_scenery_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, st.dev<terra_tile_stats>(s), st.dev<uint8_t>(sk), st.dev<terra::scenery_place_pod_t>(ob),
-			st.dev<uint32_t>(pc), capacity, st.dev<float>(ov), st.dev<terra::scenery_view_tile_pod_t>(to), st.dev<uint32_t>(dr), st.dev<float>(sz), st.dev<float>(di), st.dev<uint32_t>(ll),
-			list_capacity, st.dev<uint32_t>(gc));
+		ctx->eng.tiles_scenery_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, capacity, list_capacity, terra::scenery_view_io_t{st.dev<terra_tile_stats>(s), st.dev<uint8_t>(sk),
+			st.dev<terra::scenery_place_pod_t>(ob), st.dev<uint32_t>(pc), st.dev<float>(ov), st.dev<terra::scenery_view_tile_pod_t>(to), st.dev<uint32_t>(dr), st.dev<float>(sz),
+			st.dev<float>(di), st.dev<uint32_t>(ll), st.dev<uint32_t>(gc)});
 		st.end();
 		for (uint32_t t = 0; t < n; ++t) { // of every tile only what its record names: the rest of the caller's arrays stays as it was
 			size_t const o = (size_t)t*capacity, lo = (size_t)t*list_capacity;
@@ -1309,10 +1308,10 @@ int terra_tiles_decid_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::decid_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_decid_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, (terra::decid_tree_data_pod_t const *)d_tree_data, num_tree_data, d_skip,
-		(terra::decid_place_pod_t const *)d_decid, d_counts, capacity, d_not_visible, (terra::decid_view_tile_pod_t *)d_tile_out, d_all_bcube, d_leaf_word, d_leaf_scale, d_leaf_opacity,
-		d_leaf_num, d_branch_word, d_branch_scale, d_branch_opacity, d_branch_num, d_leaf_list, d_branch_list, (terra::decid_view_bb_pod_t *)d_leaf_bb,
-		(terra::decid_view_bb_pod_t *)d_branch_bb, d_list_counts); TERRA_CATCH
+	terra::decid_view_io_t const io = {(terra::decid_tree_data_pod_t const *)d_tree_data, d_skip, (terra::decid_place_pod_t const *)d_decid, d_counts, d_not_visible,
+		(terra::decid_view_tile_pod_t *)d_tile_out, d_all_bcube, d_leaf_word, d_leaf_scale, d_leaf_opacity, d_leaf_num, d_branch_word, d_branch_scale, d_branch_opacity, d_branch_num,
+		d_leaf_list, d_branch_list, (terra::decid_view_bb_pod_t *)d_leaf_bb, (terra::decid_view_bb_pod_t *)d_branch_bb, d_list_counts};
+	TERRA_TRY ctx->eng.tiles_decid_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, num_tree_data, capacity, io); TERRA_CATCH
 }
 int terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, int32_t xoff2, int32_t yoff2, const terra_view *view,
                            const terra_decid_view_args *args, const terra_decid_tree_data *h_tree_data, uint32_t num_tree_data, const uint8_t *h_skip,
@@ -1325,13 +1324,11 @@ int terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 	terra::decid_view_args_pod_t a; memcpy(&a, args, sizeof(a));
 	TERRA_TRY
 		ctx->eng.decid_view_check(v, a, num_tree_data); // the scene, the tile size, the view, the args and the table's length: before anything is staged
-		if (!h_tree_data) return terra::fail(TERRA_ERR_ARG, "null argument");
-		if ((uint64_t)n*capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_decid_view: n*capacity must fit 32 bits");
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_counts || !h_tile_out || !h_all_bcube || !h_list_counts ||
-		    (capacity && (!h_decid || !h_leaf_word || !h_leaf_scale || !h_leaf_opacity || !h_leaf_num || !h_branch_word || !h_branch_scale || !h_branch_opacity || !h_branch_num ||
-		                  !h_leaf_list || !h_branch_list || !h_leaf_bb || !h_branch_bb))) return terra::fail(TERRA_ERR_ARG, "null argument");
 		typedef terra::decid_view_bb_pod_t bb_t;
+		terra::decid_view_io_t const h = {(terra::decid_tree_data_pod_t const *)h_tree_data, h_skip, (terra::decid_place_pod_t const *)h_decid, h_counts, h_not_visible,
+			(terra::decid_view_tile_pod_t *)h_tile_out, h_all_bcube, h_leaf_word, h_leaf_scale, h_leaf_opacity, h_leaf_num, h_branch_word, h_branch_scale, h_branch_opacity, h_branch_num,
+			h_leaf_list, h_branch_list, (bb_t *)h_leaf_bb, (bb_t *)h_branch_bb, h_list_counts};
+		if (!terra::decid_view_io_check(tile_xy, n, capacity, h, false)) return TERRA_OK;
 		size_t const nc = (size_t)n*capacity;
 		terra_stage st(ctx->eng);
 		// the per-record arrays and the lists go up as the caller has them and come back: the call writes only some of their entries
@@ -1342,10 +1339,10 @@ int terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 			bn = st.inout(h_branch_num, nc*4), ll = st.inout(h_leaf_list, nc*4), bl = st.inout(h_branch_list, nc*4), lb = st.inout(h_leaf_bb, nc*sizeof(bb_t)),
 			bb = st.inout(h_branch_bb, nc*sizeof(bb_t)), lc = st.out(h_list_counts, (size_t)n*16);
 		st.begin();
-		ctx->eng.tiles_decid_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, st.dev<terra::decid_tree_data_pod_t>(td), num_tree_data, st.dev<uint8_t>(sk),
-			st.dev<terra::decid_place_pod_t>(de), st.dev<uint32_t>(pc), capacity, st.dev<uint8_t>(nv), st.dev<terra::decid_view_tile_pod_t>(to), st.dev<float>(bc), st.dev<uint32_t>(lw),
-			st.dev<float>(ls), st.dev<float>(lo), st.dev<uint32_t>(ln), st.dev<uint32_t>(bw), st.dev<float>(bs), st.dev<float>(bo), st.dev<uint32_t>(bn), st.dev<uint32_t>(ll),
-			st.dev<uint32_t>(bl), st.dev<bb_t>(lb), st.dev<bb_t>(bb), st.dev<uint32_t>(lc));
+		ctx->eng.tiles_decid_view_dev(tile_xy, n, dxoff, dyoff, xoff2, yoff2, v, a, num_tree_data, capacity, terra::decid_view_io_t{st.dev<terra::decid_tree_data_pod_t>(td),
+			st.dev<uint8_t>(sk), st.dev<terra::decid_place_pod_t>(de), st.dev<uint32_t>(pc), st.dev<uint8_t>(nv), st.dev<terra::decid_view_tile_pod_t>(to), st.dev<float>(bc),
+			st.dev<uint32_t>(lw), st.dev<float>(ls), st.dev<float>(lo), st.dev<uint32_t>(ln), st.dev<uint32_t>(bw), st.dev<float>(bs), st.dev<float>(bo), st.dev<uint32_t>(bn),
+			st.dev<uint32_t>(ll), st.dev<uint32_t>(bl), st.dev<bb_t>(lb), st.dev<bb_t>(bb), st.dev<uint32_t>(lc)});
 		st.end();
 	TERRA_CATCH
 }

@@ -81,6 +81,10 @@ TERRA_HD int d2i_x86(double v) {return (v > -2147483649.0 && v < 2147483648.0) ?
 // float / double -> unsigned as the reference binary converts them (cvttss2si / cvttsd2si to 64 bits, the low word): NaN and values beyond the 64-bit range give 0
 TERRA_HD uint32_t f2u_x86(float f) {return (f > -9223372036854775808.0f && f < 9223372036854775808.0f) ? (uint32_t)(uint64_t)(int64_t)f : 0u;}
 TERRA_HD uint32_t d2u_x86(double d) {return (d > -9223372036854775808.0 && d < 9223372036854775808.0) ? (uint32_t)(uint64_t)(int64_t)d : 0u;}
+// int steps as the reference binary takes them: sums and differences wrap, abs(INT_MIN) == INT_MIN
+TERRA_HD int add_wrap(int a, int b) {return (int)((uint32_t)a + (uint32_t)b);}
+TERRA_HD int sub_wrap(int a, int b) {return (int)((uint32_t)a - (uint32_t)b);}
+TERRA_HD int abs_x86(int v) {return (v < 0) ? (int)(0u - (uint32_t)v) : v;}
 
 // do_line_clip (src/Math3d.cpp:1029-1086) with get_region (src/inlines.h:522-528): shared by the mesh shadows, the line queries and the terrain view, whose
 // check_line_clip (get_line_clip, src/Math3d.cpp:1037-1052) is the same function without the two updates of the end points

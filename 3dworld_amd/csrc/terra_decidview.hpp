@@ -16,6 +16,8 @@
 #pragma once
 #include "terra_view.hpp"
 #include "terra_decidplace.hpp"
+#include "terra_landscape.hpp" // min_u32
+#include <stdexcept>
 
 namespace terra {
 
@@ -257,5 +259,109 @@ TERRA_HD float decid_view_sort_key(decid_view_consts_t const &c, decid_view_tree
 }
 // std::pair<float, unsigned>'s operator<
 TERRA_HD bool decid_view_before(float da, uint32_t ia, float db, uint32_t ib) {return da < db || (!(db < da) && ia < ib);}
+
+// ---- the arrays of a call, in the order of terra_tiles_decid_view[_dev]: host pointers in the host form's first record, device pointers everywhere else
+struct decid_view_io_t {
+	decid_tree_data_pod_t const *data; uint8_t const *skip; decid_place_pod_t const *decid; uint32_t const *counts;
+	uint8_t *not_visible; decid_view_tile_pod_t *tile_out; float *bcube;
+	uint32_t *leaf_word; float *leaf_scale, *leaf_opacity; uint32_t *leaf_num, *branch_word; float *branch_scale, *branch_opacity; uint32_t *branch_num;
+	uint32_t *leaf_list, *branch_list; decid_view_bb_pod_t *leaf_bb, *branch_bb; uint32_t *list_counts;
+};
+// the argument rules of a call, behind decid_view_check: throws what the call refuses; false: nothing to do (n == 0).  The table is required and the alignment
+// is looked at for an empty batch too.  dev: the arrays are the device's
+inline bool decid_view_io_check(int32_t const *tile_xy, uint32_t n, uint32_t capacity, decid_view_io_t const &io, bool dev) {
+	if (!io.data) throw std::invalid_argument("tiles_decid_view: null argument");
+	if ((uint64_t)n*capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_decid_view: n*capacity must fit 32 bits");
+	if (n && (!tile_xy || !io.counts || !io.tile_out || !io.bcube || !io.list_counts)) throw std::invalid_argument("tiles_decid_view: null argument");
+	if (n && capacity && (!io.decid || !io.leaf_word || !io.leaf_scale || !io.leaf_opacity || !io.leaf_num || !io.branch_word || !io.branch_scale || !io.branch_opacity ||
+	                      !io.branch_num || !io.leaf_list || !io.branch_list || !io.leaf_bb || !io.branch_bb)) throw std::invalid_argument("tiles_decid_view: null argument");
+	if (dev && (((uintptr_t)io.data | (uintptr_t)io.decid | (uintptr_t)io.counts | (uintptr_t)io.tile_out | (uintptr_t)io.bcube | (uintptr_t)io.leaf_word | (uintptr_t)io.leaf_scale |
+	             (uintptr_t)io.leaf_opacity | (uintptr_t)io.leaf_num | (uintptr_t)io.branch_word | (uintptr_t)io.branch_scale | (uintptr_t)io.branch_opacity | (uintptr_t)io.branch_num |
+	             (uintptr_t)io.leaf_list | (uintptr_t)io.branch_list | (uintptr_t)io.leaf_bb | (uintptr_t)io.branch_bb | (uintptr_t)io.list_counts) & 3u) != 0) {
+		throw std::invalid_argument("tiles_decid_view: every array but skip and not_visible must be 4-byte aligned");
+	}
+	return n != 0;
+}
+
+// ---- the literal body: tile t of the batch, its records walked in the reference's order, the leaves sweep before the branches sweep
+TERRA_HD void decid_view_tile_literal(decid_view_consts_t const &c, decid_view_io_t const &io, size_t t) {
+	decid_tree_data_pod_t const *const data = io.data;
+	uint32_t const cnt = (io.skip && io.skip[t]) ? 0u : min_u32(io.counts[t], c.cap);
+	size_t const o = t*c.cap;
+	decid_place_pod_t const *const recs = io.decid + o;
+	// calc_bcube, literally
+	float bc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+	uint32_t nvalid = 0;
+	for (uint32_t j = 0; j < cnt; ++j) {
+		if (!decid_view_valid(c, data, recs[j])) continue;
+		++nvalid;
+		float b[6], l[6];
+		decid_view_bounds(data[recs[j].tree_id], recs[j].pos, b, l);
+		box_assign_or_union(bc, b);
+		box_union(bc, l);
+	}
+	for (int k = 0; k < 6; ++k) {io.bcube[t*6 + k] = bc[k];}
+	decid_view_tile_pod_t out; out.flags = 0u; out.num_trees = nvalid; out.leaf_written = out.branch_written = out.leaf_bb_written = out.branch_bb_written = out.pad[0] = out.pad[1] = 0u;
+	uint32_t nl = 0, nb = 0, nlb = 0, nbb = 0;
+	decid_view_tile_t tl; tl.flags = 0u; tl.drawn = 0; tl.sorted = 0;
+	if (nvalid != 0u) {tl = decid_view_tile(c, bc);} // else: skipped, or decid_trees.empty() (:1557)
+	out.flags = tl.flags;
+	if (tl.drawn) {
+		uint32_t *const ll = io.leaf_list + o, *const bl = io.branch_list + o;
+		decid_view_bb_pod_t *const lb = io.leaf_bb + o, *const bb = io.branch_bb + o;
+		auto insert = [&](decid_view_bb_pod_t *list, uint32_t &m, decid_view_bb_pod_t const &e) { // behind every entry with an id that is not larger
+			uint32_t k = m++;
+			for (; k > 0 && list[k - 1].tree_id > e.tree_id; --k) {list[k] = list[k - 1];}
+			list[k] = e;
+		};
+		if (c.leaves) {
+			// the sequence of the sweep: the valid records in record order, or ascending (p2p_dist_sq, index) (:355-357).  No array holds it (the outputs keep
+			// their bytes where the call writes no entry): the sorted walk selects, step after step, the smallest pair behind the one before
+			auto key_of = [&](uint32_t q) {return decid_view_sort_key(c, decid_view_tree(c, data[recs[q].tree_id], recs[q].pos));};
+			float prev_key = 0.0f; uint32_t prev = 0; bool first = true;
+			for (uint32_t p = 0, rj = 0; p < nvalid; ++p) {
+				uint32_t j = 0;
+				if (!tl.sorted) {
+					while (!decid_view_valid(c, data, recs[rj])) {++rj;}
+					j = rj++;
+				}
+				else {
+					bool have = false; float best = 0.0f;
+					for (uint32_t q = 0; q < cnt; ++q) {
+						if (!decid_view_valid(c, data, recs[q])) continue;
+						float const k = key_of(q);
+						if (!first && !tree_view_before_f(prev_key, prev, k, q)) continue;
+						if (!have || tree_view_before_f(k, q, best, j)) {have = true; best = k; j = q;}
+					}
+					prev_key = best; prev = j; first = false;
+				}
+				decid_tree_data_pod_t const td = data[recs[j].tree_id];
+				decid_view_tree_t const g = decid_view_tree(c, td, recs[j].pos);
+				bool nvis = false, wrote = false;
+				decid_view_rec_t const r = decid_view_leaves(c, td, g, nvis, wrote);
+				io.leaf_word[o + j] = r.word; io.leaf_scale[o + j] = r.scale; io.leaf_opacity[o + j] = r.opacity; io.leaf_num[o + j] = r.num;
+				if (wrote && io.not_visible) {io.not_visible[o + j] = nvis ? 1 : 0;}
+				if (r.added) {insert(lb, nlb, decid_view_bb<true>(td, g, (uint32_t)recs[j].tree_id, j, r.opacity));}
+				if (r.listed) {ll[nl++] = j;}
+			}
+		}
+		if (c.branches) {
+			for (uint32_t j = 0; j < cnt; ++j) {
+				if (!decid_view_valid(c, data, recs[j])) continue;
+				decid_tree_data_pod_t const td = data[recs[j].tree_id];
+				decid_view_tree_t const g = decid_view_tree(c, td, recs[j].pos);
+				bool nvis = false;
+				if (!c.shadow) {nvis = c.leaves ? (io.leaf_word[o + j] & DCV_NOT_VISIBLE) != 0 : (io.not_visible && io.not_visible[o + j] != 0);}
+				decid_view_rec_t const r = decid_view_branches(c, td, g, nvis);
+				io.branch_word[o + j] = r.word; io.branch_scale[o + j] = r.scale; io.branch_opacity[o + j] = r.opacity; io.branch_num[o + j] = r.num;
+				if (r.added) {insert(bb, nbb, decid_view_bb<false>(td, g, (uint32_t)recs[j].tree_id, j, r.opacity));}
+				if (r.listed) {bl[nb++] = j;}
+			}
+		}
+		out.leaf_written = nl; out.branch_written = nb; out.leaf_bb_written = nlb; out.branch_bb_written = nbb; // (a list holds a record once: never more than the capacity)
+	}
+	io.tile_out[t] = out;
+	io.list_counts[4*t] = nl; io.list_counts[4*t + 1] = nb; io.list_counts[4*t + 2] = nlb; io.list_counts[4*t + 3] = nbb;
+}
 
 } // namespace terra

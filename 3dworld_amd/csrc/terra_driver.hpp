@@ -18,6 +18,7 @@
 #include "terra_decidplace.hpp"
 #include "terra_sceneryplace.hpp"
 #include "terra_flowers.hpp"
+#include "terra_lineintersect.hpp"
 #include "terra_grassview.hpp"
 #include "terra_terrainview.hpp"
 #include "terra_waterview.hpp"
@@ -246,89 +247,6 @@ inline bool shadow_lane_order(shadow_consts_t const &c, uint32_t npaths, uint32_
 		for (uint32_t l = 0; l < 64; ++l) {uint32_t const j = 64*k + l; lane_path[64*dst + l] = (j < npaths) ? (uint16_t)len[j].second : (uint16_t)0xFFFF;}
 	}
 	return true;
-}
-
-// ---- line-vs-terrain hits: tile_t::line_intersect_mesh (src/tiled_mesh.cpp:2176-2213) with inc_trees = 0, shared by the driver's simple form and the HIP kernels.
-// shadow_line_clip above is do_line_clip: its `(double)tmax > 1e-12` and `(double)tmin < 1 - 1e-12` decide every float as the reference's `tmax > TOLERANCE`
-// (the float 1e-12f) and `tmin < 1.0 - TOLERANCE` do.  Integer steps wrap and float -> int conversions follow x86 (cvttsd2si: INT_MIN when out of range), as the
-// reference binary does for lines whose ends are far outside the scene.
-struct line_hit_pod_t {float t; int32_t tile, xpos, ypos; float p[3]; uint32_t hit;}; // terra_line_hit
-struct line_query_consts_t {float xss, yss, DX_VAL, DY_VAL, DX_VAL_INV, DY_VAL_INV; int S, dxoff, dyoff;};
-struct alignas(16) line_box_t {float d[3][2]; int32_t x1, y1;}; // a tile's get_mesh_bcube() and its first mesh cell
-static_assert(sizeof(line_box_t) == 32, "line_box_t: two 16-byte loads");
-TERRA_HD int add_wrap(int a, int b) {return (int)((uint32_t)a + (uint32_t)b);}
-TERRA_HD int sub_wrap(int a, int b) {return (int)((uint32_t)a - (uint32_t)b);}
-TERRA_HD int abs_x86(int v) {return (v < 0) ? (int)(0u - (uint32_t)v) : v;} // abs(INT_MIN) == INT_MIN
-TERRA_HD bool line_finite(shadow_pt_t a, shadow_pt_t b) {return isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && isfinite(b.x) && isfinite(b.y) && isfinite(b.z);}
-// get_mesh_bcube (src/tiled_mesh.h:238-241) of tile (tx, ty): get_xval(x1 + xoff - xoff2) = -X_SCENE_SIZE + DX_VAL*i (src/mesh.h:122), x2 - x1 = S, BCUBE_ZTOLER = 1e-6
-TERRA_HD line_box_t line_tile_box(line_query_consts_t const &c, int tx, int ty, float mzmin, float mzmax) {
-	line_box_t b;
-	b.x1 = (int)((uint32_t)tx*(uint32_t)c.S); b.y1 = (int)((uint32_t)ty*(uint32_t)c.S);
-	float const xv1 = -c.xss + c.DX_VAL*(float)add_wrap(b.x1, c.dxoff), yv1 = -c.yss + c.DY_VAL*(float)add_wrap(b.y1, c.dyoff);
-	b.d[0][0] = xv1; b.d[0][1] = xv1 + (float)c.S*c.DX_VAL;
-	b.d[1][0] = yv1; b.d[1][1] = yv1 + (float)c.S*c.DY_VAL;
-	b.d[2][0] = mzmin - 1.0E-6f; b.d[2][1] = mzmax + 1.0E-6f;
-	return b;
-}
-TERRA_HD bool line_box_clip(line_box_t const &b, shadow_pt_t v1, shadow_pt_t v2) {return shadow_line_clip(v1, v2, b.d);}
-// the same box from the grass view's constants (terra_grassview.hpp): tile_t::draw_grass reads get_mesh_bcube() for all_visible and the minimum distance
-TERRA_HD line_box_t grass_view_box(grass_view_consts_t const &c, int tx, int ty, float mzmin, float mzmax) {
-	line_query_consts_t q;
-	q.xss = c.xss; q.yss = c.yss; q.DX_VAL = c.DX_VAL; q.DY_VAL = c.DY_VAL; q.DX_VAL_INV = 0.0f; q.DY_VAL_INV = 0.0f; q.S = c.S; q.dxoff = c.dxoff; q.dyoff = c.dyoff;
-	return line_tile_box(q, tx, ty, mzmin, mzmax);
-}
-// the walk of one (line, tile): false = no hit; else t = cur_t and (ix, iy) = the cell in the tile.  zt: the tile's (S+2)^2 zvals.  Non-finite lines and distant tiles
-// are the caller's (they never hit).  Steps are taken LINE_CHUNK at a time: the x / y / z sums advance serially as in the reference, the chunk's zvals are loaded
-// before any of its height tests, then the tests run in step order.  Every step loads, a step off the tile from cell 0 (it always exists; its value is not
-// tested): the loads carry no condition, so the chunk's LINE_CHUNK loads are all in flight before the first test waits.
-constexpr int LINE_CHUNK = 8;
-TERRA_HD bool line_tile_hit(line_query_consts_t const &c, line_box_t const &b, shadow_pt_t const v1, shadow_pt_t const v2, float const *zt, float &t, int &ix, int &iy) {
-	shadow_pt_t v1c = v1, v2c = v2; // clipped verts
-	if (!shadow_line_clip(v1c, v2c, b.d)) return false;
-	// get_xpos(x) = int((x + X_SCENE_SIZE)*DX_VAL_INV + 0.5) (src/mesh.h:129-130); xp = get_xpos(x) - x1 - xoff + xoff2
-	auto xpos = [&](float x) {return d2i_x86((double)((x + c.xss)*c.DX_VAL_INV) + 0.5);};
-	auto ypos = [&](float y) {return d2i_x86((double)((y + c.yss)*c.DY_VAL_INV) + 0.5);};
-	int const xp1 = sub_wrap(sub_wrap(xpos(v1c.x), b.x1), c.dxoff), yp1 = sub_wrap(sub_wrap(ypos(v1c.y), b.y1), c.dyoff);
-	int const xp2 = sub_wrap(sub_wrap(xpos(v2c.x), b.x1), c.dxoff), yp2 = sub_wrap(sub_wrap(ypos(v2c.y), b.y1), c.dyoff);
-	int const dx = sub_wrap(xp2, xp1), dy = sub_wrap(yp2, yp1), steps = imax(1, imax(abs_x86(dx), abs_x86(dy)));
-	if (steps >= 10000) return false; // the reference asserts (:2187)
-	double const dz = (double)v2c.z - (double)v1c.z, xinc = dx/(double)steps, yinc = dy/(double)steps, zinc = dz/(double)steps;
-	double x = xp1, y = yp1, z = (double)v1c.z - 0.1*fabs(zinc);
-	double const zden = (double)v2.z - (double)v1.z;
-	int const S = c.S, zs = S + 2;
-	for (int k0 = 0; k0 <= steps; k0 += LINE_CHUNK) {
-		float zv[LINE_CHUNK]; double zc[LINE_CHUNK]; int cell[LINE_CHUNK];
-		for (int j = 0; j < LINE_CHUNK; ++j) {
-			int const cx = d2i_x86(x), cy = d2i_x86(y); // (int)x: truncation toward zero
-			bool const in = k0 + j <= steps && cx >= 0 && cy >= 0 && cx <= S && cy <= S;
-			cell[j] = in ? ((cy << 16) | cx) : -1;
-			zv[j] = zt[in ? cy*zs + cx : 0];
-			zc[j] = z;
-			x += xinc; y += yinc; z += zinc;
-		}
-		for (int j = 0; j < LINE_CHUNK; ++j) {
-			bool const above = (double)zv[j] > zc[j]; // (evaluated for every step: no load waits behind a branch)
-			if (!(above && cell[j] >= 0)) continue;
-			float const cur_t = (float)(((zc[j] - 0.5*zinc) - (double)v1.z)/zden); // t relative to the unclipped v1, v2
-			if (cur_t >= 0.0f && cur_t <= 1.0f) {t = cur_t; ix = cell[j] & 0xFFFF; iy = cell[j] >> 16; return true;}
-		}
-	}
-	return false;
-}
-// the record of a hit on batch tile i: p_int = v1 + t*(v2 - v1) (line_intersect_tiled_mesh_get_tile, :3643-3648)
-TERRA_HD line_hit_pod_t line_hit_make(shadow_pt_t v1, shadow_pt_t v2, float t, uint32_t i, line_box_t const &b, int ix, int iy) {
-	line_hit_pod_t h;
-	h.t = t; h.tile = (int32_t)i; h.xpos = add_wrap(b.x1, ix); h.ypos = add_wrap(b.y1, iy);
-	h.p[0] = v1.x + t*(v2.x - v1.x); h.p[1] = v1.y + t*(v2.y - v1.y); h.p[2] = v1.z + t*(v2.z - v1.z);
-	h.hit = 1;
-	return h;
-}
-TERRA_HD line_hit_pod_t line_miss() {line_hit_pod_t h; h.t = 2.0f; h.tile = -1; h.xpos = h.ypos = 0; h.p[0] = h.p[1] = h.p[2] = 0.0f; h.hit = 0; return h;}
-// the tiles line r may hit: [i0, i1) -- all of them, the one tile line_tile names (none when it is out of range), none for a non-finite line
-TERRA_HD void line_tile_range(int32_t only, uint32_t n, bool finite, uint32_t &i0, uint32_t &i1) {
-	i0 = 0; i1 = n;
-	if (only >= 0) {i0 = (uint32_t)only; i1 = ((uint32_t)only < n) ? i0 + 1 : i0;}
-	if (!finite) {i1 = i0;}
 }
 
 // terrain_hmap_manager_t's sampling of a heightmap texture (src/heightmap.cpp:60-84,310-407; value scaling src/mesh_gen.cpp:120): the image stays where the
@@ -771,6 +689,22 @@ template<class BE> struct terra_engine {
 	dev_mirror_t<tree_inst_pod_t> tree_insts_mirror;
 	void set_tree_instances(tree_inst_pod_t const *v, uint32_t count) {tree_insts.assign(v, v + count); tree_insts_mirror.valid = false;}
 	tree_inst_pod_t const *tree_insts_dev() {return tree_insts_mirror.get(be, tree_insts);}
+	// a pass that reads instanced pine records needs the whole table
+	void require_tree_insts(char const *what) const {
+		if (tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
+			throw std::invalid_argument(std::string(what) + ": instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
+		}
+	}
+	// what small_tree_size reads (terra_treeao.hpp) for a call: the sizes, the xlate of the trees' offsets, the capacities and the deciduous table's length
+	tree_ao_consts_t tree_ao_consts(int dxoff, int dyoff, int xoff2, int yoff2, uint32_t pine_cap, uint32_t decid_cap, uint32_t list_cap, uint32_t num_shared) const {
+		tree_ao_consts_t c;
+		c.hs = tsp.tree_height_scale*tsp.sm_tree_scale; c.pine_radius_scale = tsp.pine_tree_radius_scale; c.tree_scale = tp.tree_scale;
+		c.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
+		c.dxv = DX_VAL; c.dyv = DY_VAL; c.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; c.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // get_xlate() (src/animals.h:25)
+		c.S = (int)tile_size(); c.instanced = tp.instanced ? 1 : 0; c.num_insts = (uint32_t)tree_insts.size(); c.num_shared = num_shared;
+		c.pine_cap = pine_cap; c.decid_cap = decid_cap; c.list_cap = list_cap; c.src_cap = pine_cap + decid_cap;
+		return c;
+	}
 	// height_histogram of estimate_zminmax (src/mesh_gen.cpp:467-480), what get_median_height reads; the device copy follows on the next placement call
 	std::vector<float> height_histogram;
 	dev_mirror_t<float> hist_mirror;
@@ -2422,9 +2356,7 @@ template<class BE> struct terra_engine {
 			if (num_radius_by_id != dp.num_shared_trees) throw std::invalid_argument("tiles_tree_ao_shadows: decid_radius_by_id must hold num_shared_trees values");
 		}
 		if (d_decid_radius) {d_decid_radius_by_id = nullptr;} // (the per-record form wins)
-		if (has_pine && tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
-			throw std::invalid_argument("tiles_tree_ao_shadows: instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
-		}
+		if (has_pine) {require_tree_insts("tiles_tree_ao_shadows");}
 		if (((uintptr_t)d_tree_map & 1u) != 0) throw std::invalid_argument("tiles_tree_ao_shadows: d_tree_map must be 2-byte aligned");
 		if ((((uintptr_t)d_pine | (uintptr_t)d_pine_counts | (uintptr_t)d_decid | (uintptr_t)d_decid_counts | (uintptr_t)d_decid_radius | (uintptr_t)d_decid_radius_by_id |
 		      (uintptr_t)d_trmax | (uintptr_t)d_list_counts) & 3u) != 0) throw std::invalid_argument("tiles_tree_ao_shadows: records, counts, radii, trmax and list_counts must be 4-byte aligned");
@@ -2437,12 +2369,7 @@ template<class BE> struct terra_engine {
 			int const x1 = (int)((uint32_t)tile_xy[2*t]*S), y1 = (int)((uint32_t)tile_xy[2*t+1]*S); // (as tiles_tree_map_dev)
 			fr[t].x = -cfg.scene_x + DX_VAL*(float)add_wrap(x1, dxoff); fr[t].y = -cfg.scene_y + DY_VAL*(float)add_wrap(y1, dyoff);
 		}
-		tree_ao_consts_t c;
-		c.hs = tsp.tree_height_scale*tsp.sm_tree_scale; c.pine_radius_scale = tsp.pine_tree_radius_scale; c.tree_scale = tp.tree_scale;
-		c.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
-		c.dxv = DX_VAL; c.dyv = DY_VAL; c.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; c.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL;
-		c.S = (int)S; c.instanced = tp.instanced ? 1 : 0; c.num_insts = (uint32_t)tree_insts.size(); c.num_shared = dp.num_shared_trees;
-		c.pine_cap = pine_cap; c.decid_cap = decid_cap; c.list_cap = list_cap; c.src_cap = (uint32_t)src_cap;
+		tree_ao_consts_t const c = tree_ao_consts(dxoff, dyoff, xoff2, yoff2, pine_cap, decid_cap, list_cap, dp.num_shared_trees);
 		tree_frame_t *d_fr_w; int32_t *d_nbr_w; tree_splat_in_t *d_src; float *d_trm; tree_tile_pod_t *d_tiles; tree_splat_pod_t *d_par; uint8_t *d_rowf, *d_upd; // d_rowf: the simple form's per-row `updated`
 		stage_layout_t lay;
 		lay.add(d_fr_w, n); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_src, (size_t)n*src_cap); lay.add(d_trm, n); lay.add(d_tiles, n); lay.add(d_par, (size_t)n*list_cap);
@@ -2535,9 +2462,7 @@ template<class BE> struct terra_engine {
 			if (num_radius_by_id != dp.num_shared_trees) throw std::invalid_argument("tiles_edit_trees: decid_radius_by_id must hold num_shared_trees values");
 		}
 		else {d_decid_radius_by_id = nullptr;} // (no deciduous group, or the per-record form alone)
-		if (has_pine && tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
-			throw std::invalid_argument("tiles_edit_trees: instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
-		}
+		if (has_pine) {require_tree_insts("tiles_edit_trees");}
 		if ((((uintptr_t)d_pine | (uintptr_t)d_pine_counts | (uintptr_t)d_decid | (uintptr_t)d_decid_counts | (uintptr_t)d_decid_radius | (uintptr_t)d_decid_radius_by_id |
 		      (uintptr_t)d_trmax | (uintptr_t)d_stats | (uintptr_t)d_zvals | (uintptr_t)d_update_bcube) & 3u) != 0) {
 			throw std::invalid_argument("tiles_edit_trees: records, counts, radii, trmax, stats, zvals and update_bcube must be 4-byte aligned");
@@ -2545,11 +2470,7 @@ template<class BE> struct terra_engine {
 		if ((uint64_t)n*pine_cap > 0xFFFFFFFFull || (uint64_t)n*decid_cap > 0xFFFFFFFFull) throw std::invalid_argument("tiles_edit_trees: n*capacity must fit 32 bits");
 		uint32_t const S = tile_size();
 		tree_edit_consts_t c;
-		c.a.hs = tsp.tree_height_scale*tsp.sm_tree_scale; c.a.pine_radius_scale = tsp.pine_tree_radius_scale; c.a.tree_scale = tp.tree_scale;
-		c.a.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale;
-		c.a.dxv = DX_VAL; c.a.dyv = DY_VAL; c.a.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; c.a.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // get_xlate() (src/animals.h:25)
-		c.a.S = (int)S; c.a.instanced = tp.instanced ? 1 : 0; c.a.num_insts = (uint32_t)tree_insts.size(); c.a.num_shared = dp.num_shared_trees;
-		c.a.pine_cap = pine_cap; c.a.decid_cap = decid_cap; c.a.list_cap = 0; c.a.src_cap = pine_cap + decid_cap;
+		c.a = tree_ao_consts(dxoff, dyoff, xoff2, yoff2, pine_cap, decid_cap, 0, dp.num_shared_trees);
 		c.px = pos[0]; c.py = pos[1]; c.pz = pos[2]; c.ptx = pos[0] - c.a.offx; c.pty = pos[1] - c.a.offy; c.rr = radius;
 		c.calc_radius = (float)(0.5*(double)sqrtf(DX_VAL*DX_VAL + DY_VAL*DY_VAL)*(double)S); // 0.5*sqrt(DX_VAL*DX_VAL + DY_VAL*DY_VAL)*size: float sqrt, double products
 		c.is_square = is_square ? 1 : 0; c.add = add ? 1 : 0;
@@ -3078,15 +2999,9 @@ template<class BE> struct terra_engine {
 		if (!view_finite(view)) throw std::invalid_argument("tiles_grass_view: a member of the view is not finite");
 		if (ls.num_rnd_grass_blocks == 0 || ls.num_rnd_grass_blocks > GRASS_VIEW_MAX_RND) throw std::invalid_argument("tiles_grass_view: num_rnd_grass_blocks must be 1 .. 4096");
 	}
-	void tiles_grass_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, float const *d_zvals, terra_tile_stats const *d_stats, grass_block_pod_t const *d_blocks,
-		uint8_t const *d_skip, view_pod_t const &view, uint32_t capacity, float *d_insts, uint32_t *d_aux, uint32_t *d_group_counts, uint32_t *d_counts, uint8_t *d_pass)
-	{
+	void tiles_grass_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, uint32_t capacity, grass_view_io_t const &io) {
 		grass_view_check(view);
-		if (n == 0) return;
-		if (!tile_xy || !d_zvals || !d_stats || !d_blocks || !d_group_counts || !d_counts || (capacity && !d_insts)) throw std::invalid_argument("tiles_grass_view: null argument");
-		if ((((uintptr_t)d_zvals | (uintptr_t)d_stats | (uintptr_t)d_blocks | (uintptr_t)d_insts | (uintptr_t)d_aux | (uintptr_t)d_group_counts | (uintptr_t)d_counts) & 3u) != 0) {
-			throw std::invalid_argument("tiles_grass_view: d_zvals, d_stats, d_grass_blocks, d_insts, d_aux, d_group_counts and d_counts must be 4-byte aligned");
-		}
+		if (!grass_view_io_check(tile_xy, n, capacity, io, true)) return;
 		uint32_t const S = tile_size();
 		grass_view_consts_t const c = grass_view_consts(view, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, dxdy, (int)S, dxoff, dyoff, ls.num_rnd_grass_blocks,
 			gvp.tt_grass_scale_factor, fp.grass_length);
@@ -3099,48 +3014,9 @@ template<class BE> struct terra_engine {
 		lay.add(d_keys, (size_t)n*nb); lay.add(d_offs, (size_t)n*nbins); lay.add(d_txy, (size_t)n*2);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
 		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
-		if constexpr (BE::has_kernels) {if (be.tile_grass_view(c, d_txy, n, d_zvals, d_stats, d_blocks, d_skip, capacity, d_insts, d_aux, d_group_counts, d_counts, d_pass, d_keys)) return;}
-		// the simple form: one logical thread per tile runs the reference's loops; its per-LOD, per-bix lists are the groups' counts, then their offsets, then a second
-		// walk in the same scan order that appends every kept block to its group
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			terra_tile_stats const &st = d_stats[t];
-			line_box_t const box = grass_view_box(c, d_txy[2*t], d_txy[2*t + 1], st.mzmin, st.mzmax);
-			grass_view_tile_t const tl = grass_view_tile(c, box.d, box.x1, box.y1, st.mzmin, st.mzmax, st.radius);
-			uint32_t *const gc = d_group_counts + t*nbins, *const of = d_offs + t*nbins;
-			uint16_t *const ky = d_keys + t*nb;
-			for (size_t b = 0; b < nbins; ++b) {gc[b] = 0u;}
-			bool has_grass = false;
-			if (!(d_skip && d_skip[t]) && tl.in_range) {
-				grass_block_pod_t const *const bl = d_blocks + t*nb;
-				for (uint32_t y = 0; y < c.dim; ++y) {
-					for (uint32_t x = 0; x < c.dim; ++x) {
-						grass_block_pod_t const gb = bl[y*c.dim + x];
-						has_grass = has_grass || gb.ix != 0u;
-						uint32_t const key = grass_view_block(c, tl, x, y, gb.ix, gb.zmin, gb.zmax, d_zvals + t*zn);
-						ky[y*c.dim + x] = (uint16_t)key;
-						if (key != GRASS_VIEW_DROPPED) {++gc[key];}
-					}
-				}
-			}
-			if (!has_grass) { // skipped, too far away (:1612) or !has_grass() (:1609, :3422)
-				d_counts[t] = 0u;
-				if (d_pass) {d_pass[t] = GRASS_VIEW_NO_PASS;}
-				return;
-			}
-			uint32_t total = 0;
-			for (size_t b = 0; b < nbins; ++b) {of[b] = total; total += gc[b];}
-			for (uint32_t i = 0; i < (uint32_t)nb; ++i) {
-				uint32_t const key = ky[i];
-				if (key == GRASS_VIEW_DROPPED) continue;
-				uint32_t const rank = of[key]++;
-				if (rank >= capacity) continue;
-				float *const o = d_insts + (t*capacity + rank)*2;
-				o[0] = (float)(i % c.dim)*c.dx_step; o[1] = (float)(i / c.dim)*c.dy_step; // emplace_back(x*dx_step, y*dy_step) (:1651)
-				if (d_aux) {d_aux[t*capacity + rank] = grass_view_aux(c, i, key);}
-			}
-			d_counts[t] = total;
-			if (d_pass) {d_pass[t] = (uint8_t)tl.wpass;}
-		});
+		if constexpr (BE::has_kernels) {if (be.tile_grass_view(c, io, d_txy, n, capacity, d_keys)) return;}
+		// the simple form: one logical thread per tile runs the reference's loops (grass_view_tile_literal)
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {grass_view_tile_literal(c, io, d_txy, capacity, d_keys, d_offs, nb, nbins, zn, t);});
 	}
 
 	// ---- the terrain draw list of a batch for a camera (terra_terrainview.hpp): the head of tile_draw_t::draw (src/tiled_mesh.cpp:2844-2915), get_lod_level
@@ -3482,9 +3358,7 @@ template<class BE> struct terra_engine {
 		if (!in) throw std::invalid_argument(std::string(what) + ": null argument");
 		bool const has_pine = !cube && in->pine && in->pine_counts && in->pine_capacity, has_decid = in->decid && in->decid_counts && in->decid_capacity;
 		if (!cube && !(isfinite(in->tree_depth_scale) && in->tree_depth_scale > 0.0f)) throw std::invalid_argument(std::string(what) + ": tree_depth_scale must be finite and > 0");
-		if (has_pine && tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
-			throw std::invalid_argument(std::string(what) + ": instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
-		}
+		if (has_pine) {require_tree_insts(what);}
 		if (has_decid && (!in->tree_data || !in->br_scale)) throw std::invalid_argument(std::string(what) + ": null argument (tree_data and br_scale go with the deciduous records)");
 		if (has_decid && (in->num_tree_data == 0 || in->num_tree_data != dp.num_shared_trees)) {
 			throw std::invalid_argument(std::string(what) + ": num_tree_data must be terra_decid_params.num_shared_trees and > 0");
@@ -3504,12 +3378,7 @@ template<class BE> struct terra_engine {
 		}
 		uint32_t hbits;
 		std::vector<int32_t> const slots = batch_key_table(tile_xy, n, what, hbits);
-		tree_ao_consts_t ac;
-		ac.hs = tsp.tree_height_scale*tsp.sm_tree_scale; ac.pine_radius_scale = tsp.pine_tree_radius_scale; ac.tree_scale = tp.tree_scale;
-		ac.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
-		ac.dxv = DX_VAL; ac.dyv = DY_VAL; ac.offx = (float)add_wrap(a.dxoff, a.ptree_xoff2)*DX_VAL; ac.offy = (float)add_wrap(a.dyoff, a.ptree_yoff2)*DY_VAL; // ptree_off.get_xlate()
-		ac.S = (int)tile_size(); ac.instanced = tp.instanced ? 1 : 0; ac.num_insts = (uint32_t)tree_insts.size(); ac.num_shared = 0;
-		ac.pine_cap = a.pine_capacity; ac.decid_cap = 0; ac.list_cap = 0; ac.src_cap = a.pine_capacity;
+		tree_ao_consts_t const ac = tree_ao_consts(a.dxoff, a.dyoff, a.ptree_xoff2, a.ptree_yoff2, a.pine_capacity, 0, 0, 0); // ptree_off.get_xlate()
 		view_pod_t v; memset(&v, 0, sizeof(v)); // (no camera: of the view constants only the scene, the offsets and the tree depth are read)
 		tree_view_args_pod_t const ta = {0.0f, 1.0f, cube ? 1.0f : a.tree_depth_scale, 1, 0, 0, 0, 0};
 		c.pv = tree_view_consts(v, ta, ac, cfg.scene_x, cfg.scene_y, a.dxoff, a.dyoff, a.pine_capacity);
@@ -3587,31 +3456,14 @@ template<class BE> struct terra_engine {
 		if (!view_finite(view)) throw std::invalid_argument("tiles_tree_view: a member of the view is not finite");
 		if (!isfinite(a.behind_sphere_mult) || !isfinite(a.zoom_f) || !isfinite(a.tree_depth_scale)) throw std::invalid_argument("tiles_tree_view: a member of the args is not finite");
 		if (!tree_view_args_ok(a)) throw std::invalid_argument("tiles_tree_view: window_width, zoom_f and tree_depth_scale must be finite and > 0");
-		if (tp.instanced && tree_insts.size() != (size_t)tp.num_pine_insts + tp.num_palm_insts) {
-			throw std::invalid_argument("tiles_tree_view: instanced needs num_pine_insts + num_palm_insts instances (terra_set_tree_instances)");
-		}
+		require_tree_insts("tiles_tree_view");
 	}
-	void tiles_tree_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, tree_view_args_pod_t const &a,
-		terra_tile_stats const *d_stats, uint8_t const *d_skip, float const *d_trmax, tree_place_pod_t const *d_pine, uint32_t const *d_counts, uint32_t capacity,
-		trunk_override_pod_t const *d_ov, tree_view_tile_pod_t *d_tile_out, float *d_bcube, tree_view_inst_pod_t *d_pine_insts, tree_view_inst_pod_t *d_palm_insts,
-		uint32_t *d_inst_counts, uint32_t *d_leaf_list, uint32_t *d_leaf_counts, uint8_t *d_trunk)
+	void tiles_tree_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, tree_view_args_pod_t const &a, uint32_t capacity,
+		tree_view_io_t const &io)
 	{
 		tree_view_check(view, a);
-		if ((uint64_t)n*capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_tree_view: n*capacity must fit 32 bits");
-		if (n == 0) return;
-		if (!tile_xy || !d_stats || !d_counts || !d_tile_out || !d_bcube || !d_inst_counts || !d_leaf_counts || (capacity && (!d_pine || !d_pine_insts || !d_palm_insts || !d_leaf_list || !d_trunk))) {
-			throw std::invalid_argument("tiles_tree_view: null argument");
-		}
-		if ((((uintptr_t)d_stats | (uintptr_t)d_trmax | (uintptr_t)d_pine | (uintptr_t)d_counts | (uintptr_t)d_ov | (uintptr_t)d_tile_out | (uintptr_t)d_bcube | (uintptr_t)d_pine_insts |
-		      (uintptr_t)d_palm_insts | (uintptr_t)d_inst_counts | (uintptr_t)d_leaf_list | (uintptr_t)d_leaf_counts) & 3u) != 0) {
-			throw std::invalid_argument("tiles_tree_view: every array but skip and trunk must be 4-byte aligned");
-		}
-		tree_ao_consts_t ac;
-		ac.hs = tsp.tree_height_scale*tsp.sm_tree_scale; ac.pine_radius_scale = tsp.pine_tree_radius_scale; ac.tree_scale = tp.tree_scale;
-		ac.tsize = 16.0f*SM_TREE_SIZE/tp.tree_scale; // calc_tree_size (src/sm_tree.cpp:326)
-		ac.dxv = DX_VAL; ac.dyv = DY_VAL; ac.offx = (float)add_wrap(dxoff, xoff2)*DX_VAL; ac.offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // ptree_off.get_xlate()
-		ac.S = (int)tile_size(); ac.instanced = tp.instanced ? 1 : 0; ac.num_insts = (uint32_t)tree_insts.size(); ac.num_shared = 0;
-		ac.pine_cap = capacity; ac.decid_cap = 0; ac.list_cap = 0; ac.src_cap = capacity;
+		if (!tree_view_io_check(tile_xy, n, capacity, io, true)) return;
+		tree_ao_consts_t const ac = tree_ao_consts(dxoff, dyoff, xoff2, yoff2, capacity, 0, 0, 0); // ptree_off.get_xlate()
 		tree_view_consts_t const c = tree_view_consts(view, a, ac, cfg.scene_x, cfg.scene_y, dxoff, dyoff, capacity);
 		// scratch: the coordinates; for a capacity beyond what k_tree_view ranks in LDS, a tile's (key, record) pairs
 		int32_t *d_txy_w; uint32_t *d_keys;
@@ -3621,76 +3473,9 @@ template<class BE> struct terra_engine {
 		be.h2d_async(d_txy_w, tile_xy, (size_t)n*8);
 		int32_t const *d_txy = d_txy_w;
 		tree_inst_pod_t const *d_insts = tp.instanced ? tree_insts_dev() : nullptr;
-		if constexpr (BE::has_kernels) {
-			if (be.tile_tree_view(c, d_txy, n, d_insts, d_stats, d_skip, d_trmax, d_pine, d_counts, d_ov, d_tile_out, d_bcube, d_pine_insts, d_palm_insts, d_inst_counts, d_leaf_list,
-				d_leaf_counts, d_trunk, d_keys)) return;
-		}
-		// the simple form: a logical thread per tile walks its records in the reference's order
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			uint32_t const cnt = (d_skip && d_skip[t]) ? 0u : min_u32(d_counts[t], c.cap);
-			tree_place_pod_t const *const recs = d_pine + t*c.cap;
-			trunk_override_pod_t const *const ovs = d_ov ? d_ov + t*c.cap : nullptr;
-			// calc_bcube, num_pine_trees, num_palm_trees
-			float bc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-			bool any = false;
-			uint32_t nvalid = 0, np = 0, npalm = 0;
-			tree_view_rec_t rec;
-			for (uint32_t j = 0; j < cnt; ++j) {
-				if (!tree_view_record(c, d_insts, recs[j], ovs ? ovs + j : nullptr, rec)) continue;
-				++nvalid; np += is_pine_tree_type(rec.type) ? 1u : 0u; npalm += (rec.type == T_PALM) ? 1u : 0u;
-				float d[6];
-				if (!tree_view_bounds(rec, d)) continue;
-				if (!any) {for (int k = 0; k < 6; ++k) {bc[k] = d[k];} any = true;}
-				else {box_union(bc, d);}
-			}
-			for (int k = 0; k < 6; ++k) {d_bcube[t*6 + k] = bc[k];}
-			if (nvalid == 0) { // skipped, or pine_trees.empty() (:1468)
-				tree_view_tile_pod_t z; z.dscale = 0.0f; z.weight = 0.0f; z.flags = 0u; z.num_pine = z.num_palm = z.num_trees = z.leaf_written = z.pad = 0u;
-				d_tile_out[t] = z; d_inst_counts[2*t] = d_inst_counts[2*t + 1] = 0u; d_leaf_counts[2*t] = d_leaf_counts[2*t + 1] = 0u;
-				return;
-			}
-			tree_view_tile_t tl = tree_view_tile(c, d_txy[2*t], d_txy[2*t + 1], d_stats[t], d_trmax ? d_trmax[t] : 0.0f, nvalid, np, npalm, bc);
-			tree_view_inst_pod_t *const pi = d_pine_insts + t*c.cap, *const mi = d_palm_insts + t*c.cap;
-			uint32_t *const ll = d_leaf_list + t*c.cap;
-			uint32_t npi = 0, nmi = 0, nl = 0, nm = 0;
-			bool skipped = false;
-			bool const need_vis = (tl.pine_insts && !tl.draw_all_near) || (tl.palm_insts && !tl.all_visible) || tl.pine_list;
-			for (uint32_t j = 0; j < cnt; ++j) {
-				bool const valid = tree_view_record(c, d_insts, recs[j], ovs ? ovs + j : nullptr, rec);
-				uint8_t const b = (valid && tl.trunks) ? tree_view_trunk(c, rec, tl.all_visible != 0) : (uint8_t)0;
-				d_trunk[t*c.cap + j] = b; skipped = skipped || b == 1;
-				if (!valid) continue;
-				bool const pine = is_pine_tree_type(rec.type), palm = rec.type == T_PALM;
-				bool const vis = need_vis && tree_view_leaves_visible(c, rec);
-				int32_t const id = recs[j].inst;
-				auto insert = [&](tree_view_inst_pod_t *out, uint32_t &m) { // where sort(insts) puts it: behind every entry with an id that is not larger
-					uint32_t k = m++;
-					for (; k > 0 && out[k - 1].id > (uint32_t)id; --k) {out[k] = out[k - 1];}
-					out[k].id = (uint32_t)id; for (int q = 0; q < 3; ++q) {out[k].pt[q] = rec.pos[q];}
-				};
-				if (tl.pine_insts && pine && id >= 0 && (tl.draw_all_near || vis)) {insert(pi, npi);}
-				if (tl.palm_insts && palm && id >= 0 && (tl.all_visible || vis)) {insert(mi, nmi);}
-				if (tl.pine_list && pine && vis) {
-					uint32_t k = nl++;
-					if (tl.pine_sorted) { // get_back_to_front_ordering: ascending (p2p_dist_sq, index)
-						float const key = tree_view_sort_key(c, rec.pos);
-						for (; k > 0 && tree_view_before_f(key, j, tree_view_sort_key(c, recs[ll[k - 1]].pos), ll[k - 1]); --k) {ll[k] = ll[k - 1];}
-					}
-					ll[k] = j;
-				}
-			}
-			if (tl.palm_list) { // draw_non_pine_leaves(0, 1, 0, ..): behind the pine entries
-				for (uint32_t j = 0; j < cnt; ++j) {
-					if (!tree_view_record(c, d_insts, recs[j], ovs ? ovs + j : nullptr, rec) || rec.type != T_PALM || !tree_view_leaves_visible(c, rec)) continue;
-					ll[nl + nm++] = j;
-				}
-			}
-			if (skipped) {tl.out.flags = (tl.out.flags & ~(uint32_t)TRV_TRUNK_MASK) | TRV_TRUNK_POLY_SKIPPED;}
-			tl.out.leaf_written = nl + nm;
-			d_tile_out[t] = tl.out;
-			d_inst_counts[2*t] = npi; d_inst_counts[2*t + 1] = nmi;
-			d_leaf_counts[2*t] = tl.pine_list ? nl : tree_view_render_all(c, tl); d_leaf_counts[2*t + 1] = nm;
-		});
+		if constexpr (BE::has_kernels) {if (be.tile_tree_view(c, io, d_txy, n, d_insts, d_keys)) return;}
+		// the simple form: a logical thread per tile walks its records in the reference's order (tree_view_tile_literal)
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {tree_view_tile_literal(c, io, d_txy, d_insts, t);});
 	}
 
 	// ---- the scenery draw lists of a batch for a camera (terra_sceneryview.hpp): tile_t::draw_scenery (src/tiled_mesh.cpp:1580-1592) with scenery_group's
@@ -3705,19 +3490,10 @@ template<class BE> struct terra_engine {
 		if (a.reflection_pass != 0 && a.reflection_pass != 1) throw std::invalid_argument("tiles_scenery_view: reflection_pass must be 0 or 1");
 	}
 	void tiles_scenery_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, scenery_view_args_pod_t const &a,
-		terra_tile_stats const *d_stats, uint8_t const *d_skip, scenery_place_pod_t const *d_objs, uint32_t const *d_counts, uint32_t capacity, float const *d_rov,
-		scenery_view_tile_pod_t *d_tile_out, uint32_t *d_draw, float *d_size_scale, float *d_dist, uint32_t *d_list, uint32_t list_capacity, uint32_t *d_group_counts)
+		uint32_t capacity, uint32_t list_capacity, scenery_view_io_t const &io)
 	{
 		scenery_view_check(view, a);
-		if ((uint64_t)n*capacity > 0xFFFFFFFFull || (uint64_t)n*list_capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_scenery_view: n*capacity and n*list_capacity must fit 32 bits");
-		if (n == 0) return;
-		if (!tile_xy || !d_stats || !d_counts || !d_tile_out || !d_group_counts || (capacity && (!d_objs || !d_draw || !d_size_scale || !d_dist)) || (list_capacity && !d_list)) {
-			throw std::invalid_argument("tiles_scenery_view: null argument");
-		}
-		if ((((uintptr_t)d_stats | (uintptr_t)d_objs | (uintptr_t)d_counts | (uintptr_t)d_rov | (uintptr_t)d_tile_out | (uintptr_t)d_draw | (uintptr_t)d_size_scale | (uintptr_t)d_dist |
-		      (uintptr_t)d_list | (uintptr_t)d_group_counts) & 3u) != 0) {
-			throw std::invalid_argument("tiles_scenery_view: every array but skip must be 4-byte aligned");
-		}
+		if (!scenery_view_io_check(tile_xy, n, capacity, list_capacity, io, true)) return;
 		float const offx = (float)add_wrap(dxoff, xoff2)*DX_VAL, offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // scenery_off.get_xlate()
 		scenery_view_consts_t const c = scenery_view_consts(view, a, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, offx, offy, water_plane_z,
 			get_water_z_height() - ocean_wave_height, tp.tree_scale, capacity, list_capacity);
@@ -3727,35 +3503,9 @@ template<class BE> struct terra_engine {
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
 		be.h2d_async(d_txy_w, tile_xy, (size_t)n*8);
 		int32_t const *d_txy = d_txy_w;
-		if constexpr (BE::has_kernels) {
-			if (be.tile_scenery_view(c, d_txy, n, d_stats, d_skip, d_objs, d_counts, d_rov, d_tile_out, d_draw, d_size_scale, d_dist, d_list, d_group_counts)) return;
-		}
-		// the simple form: a logical thread per tile walks its records, then once per stream for the lists
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			uint32_t const cnt = (d_skip && d_skip[t]) ? 0u : min_u32(d_counts[t], c.cap);
-			scenery_view_tile_pod_t o; o.dist_scale = 0.0f; o.scale_val = 0.0f; o.flags = o.num_records = o.list_written = 0u; o.pad[0] = o.pad[1] = o.pad[2] = 0u;
-			uint32_t groups[SCV_GROUPS];
-			for (uint32_t g = 0; g < SCV_GROUPS; ++g) {groups[g] = 0u;}
-			float ds = 0.0f;
-			if (cnt != 0u && scenery_view_tile(c, d_txy[2*t], d_txy[2*t + 1], d_stats[t].mzmin, d_stats[t].mzmax, d_stats[t].radius, ds)) {
-				scenery_place_pod_t const *const recs = d_objs + t*c.cap;
-				for (uint32_t j = 0; j < cnt; ++j) {
-					scenery_view_rec_t const r = scenery_view_record(c, recs[j], d_rov ? d_rov[t*c.cap + j] : 0.0f);
-					d_draw[t*c.cap + j] = r.word; d_size_scale[t*c.cap + j] = r.size_scale; d_dist[t*c.cap + j] = r.dist;
-				}
-				uint32_t at = 0;
-				for (uint32_t s = 0; s < SCV_STREAMS; ++s) { // a stable split of the record list
-					for (uint32_t j = 0; j < cnt; ++j) {
-						if (!((scenery_view_streams(recs[j].kind, d_draw[t*c.cap + j]) >> s) & 1u)) continue;
-						if (at < c.list_cap) {d_list[t*c.list_cap + at] = j;}
-						++at; ++groups[scenery_view_group(s)];
-					}
-				}
-				o.dist_scale = ds; o.scale_val = c.scale_val; o.flags = scenery_view_tile_flags(c); o.num_records = cnt; o.list_written = min_u32(at, c.list_cap);
-			}
-			d_tile_out[t] = o;
-			for (uint32_t g = 0; g < SCV_GROUPS; ++g) {d_group_counts[t*SCV_GROUPS + g] = groups[g];}
-		});
+		if constexpr (BE::has_kernels) {if (be.tile_scenery_view(c, io, d_txy, n)) return;}
+		// the simple form: a logical thread per tile walks its records, then once per stream for the lists (scenery_view_tile_literal)
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {scenery_view_tile_literal(c, io, d_txy, t);});
 	}
 
 	// ---- the deciduous tree draw lists of a batch for a camera (terra_decidview.hpp): tile_t::draw_decid_trees (src/tiled_mesh.cpp:1555-1563) with
@@ -3771,23 +3521,10 @@ template<class BE> struct terra_engine {
 		if (num_tree_data == 0 || num_tree_data != dp.num_shared_trees) throw std::invalid_argument("tiles_decid_view: num_tree_data must be terra_decid_params.num_shared_trees and > 0");
 	}
 	void tiles_decid_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, int xoff2, int yoff2, view_pod_t const &view, decid_view_args_pod_t const &a,
-		decid_tree_data_pod_t const *d_data, uint32_t num_tree_data, uint8_t const *d_skip, decid_place_pod_t const *d_decid, uint32_t const *d_counts, uint32_t capacity,
-		uint8_t *d_not_visible, decid_view_tile_pod_t *d_tile_out, float *d_bcube, uint32_t *d_leaf_word, float *d_leaf_scale, float *d_leaf_opacity, uint32_t *d_leaf_num,
-		uint32_t *d_branch_word, float *d_branch_scale, float *d_branch_opacity, uint32_t *d_branch_num, uint32_t *d_leaf_list, uint32_t *d_branch_list,
-		decid_view_bb_pod_t *d_leaf_bb, decid_view_bb_pod_t *d_branch_bb, uint32_t *d_list_counts)
+		uint32_t num_tree_data, uint32_t capacity, decid_view_io_t const &io)
 	{
 		decid_view_check(view, a, num_tree_data);
-		if (!d_data) throw std::invalid_argument("tiles_decid_view: null argument");
-		if ((uint64_t)n*capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_decid_view: n*capacity must fit 32 bits");
-		if (n && (!tile_xy || !d_counts || !d_tile_out || !d_bcube || !d_list_counts)) throw std::invalid_argument("tiles_decid_view: null argument");
-		if (n && capacity && (!d_decid || !d_leaf_word || !d_leaf_scale || !d_leaf_opacity || !d_leaf_num || !d_branch_word || !d_branch_scale || !d_branch_opacity || !d_branch_num ||
-		                      !d_leaf_list || !d_branch_list || !d_leaf_bb || !d_branch_bb)) throw std::invalid_argument("tiles_decid_view: null argument");
-		if ((((uintptr_t)d_data | (uintptr_t)d_decid | (uintptr_t)d_counts | (uintptr_t)d_tile_out | (uintptr_t)d_bcube | (uintptr_t)d_leaf_word | (uintptr_t)d_leaf_scale |
-		      (uintptr_t)d_leaf_opacity | (uintptr_t)d_leaf_num | (uintptr_t)d_branch_word | (uintptr_t)d_branch_scale | (uintptr_t)d_branch_opacity | (uintptr_t)d_branch_num |
-		      (uintptr_t)d_leaf_list | (uintptr_t)d_branch_list | (uintptr_t)d_leaf_bb | (uintptr_t)d_branch_bb | (uintptr_t)d_list_counts) & 3u) != 0) {
-			throw std::invalid_argument("tiles_decid_view: every array but skip and not_visible must be 4-byte aligned");
-		}
-		if (n == 0) return;
+		if (!decid_view_io_check(tile_xy, n, capacity, io, true)) return;
 		float const offx = (float)add_wrap(dxoff, xoff2)*DX_VAL, offy = (float)add_wrap(dyoff, yoff2)*DY_VAL; // dtree_off.get_xlate()
 		decid_view_consts_t const c = decid_view_consts(view, a, cfg.scene_x, cfg.scene_y, offx, offy, num_tree_data, capacity);
 		// scratch: for a capacity beyond what k_decid_view ranks in LDS, a tile's pairs and its sorted sequence
@@ -3795,89 +3532,9 @@ template<class BE> struct terra_engine {
 		stage_layout_t lay;
 		lay.add(d_keys, (capacity > DECID_VIEW_LDS_KEYS) ? (size_t)n*capacity*3 : 0);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
-		if constexpr (BE::has_kernels) {
-			if (be.tile_decid_view(c, n, d_data, d_skip, d_decid, d_counts, d_not_visible, d_tile_out, d_bcube, d_leaf_word, d_leaf_scale, d_leaf_opacity, d_leaf_num, d_branch_word,
-				d_branch_scale, d_branch_opacity, d_branch_num, d_leaf_list, d_branch_list, d_leaf_bb, d_branch_bb, d_list_counts, d_keys)) return;
-		}
-		// the simple form: a logical thread per tile walks its records in the reference's order, the leaves sweep before the branches sweep
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			uint32_t const cnt = (d_skip && d_skip[t]) ? 0u : min_u32(d_counts[t], c.cap);
-			size_t const o = t*c.cap;
-			decid_place_pod_t const *const recs = d_decid + o;
-			// calc_bcube, literally
-			float bc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-			uint32_t nvalid = 0;
-			for (uint32_t j = 0; j < cnt; ++j) {
-				if (!decid_view_valid(c, d_data, recs[j])) continue;
-				++nvalid;
-				float b[6], l[6];
-				decid_view_bounds(d_data[recs[j].tree_id], recs[j].pos, b, l);
-				box_assign_or_union(bc, b);
-				box_union(bc, l);
-			}
-			for (int k = 0; k < 6; ++k) {d_bcube[t*6 + k] = bc[k];}
-			decid_view_tile_pod_t out; out.flags = 0u; out.num_trees = nvalid; out.leaf_written = out.branch_written = out.leaf_bb_written = out.branch_bb_written = out.pad[0] = out.pad[1] = 0u;
-			uint32_t nl = 0, nb = 0, nlb = 0, nbb = 0;
-			decid_view_tile_t tl; tl.flags = 0u; tl.drawn = 0; tl.sorted = 0;
-			if (nvalid != 0u) {tl = decid_view_tile(c, bc);} // else: skipped, or decid_trees.empty() (:1557)
-			out.flags = tl.flags;
-			if (tl.drawn) {
-				uint32_t *const ll = d_leaf_list + o, *const bl = d_branch_list + o;
-				decid_view_bb_pod_t *const lb = d_leaf_bb + o, *const bb = d_branch_bb + o;
-				auto insert = [&](decid_view_bb_pod_t *list, uint32_t &m, decid_view_bb_pod_t const &e) { // behind every entry with an id that is not larger
-					uint32_t k = m++;
-					for (; k > 0 && list[k - 1].tree_id > e.tree_id; --k) {list[k] = list[k - 1];}
-					list[k] = e;
-				};
-				if (c.leaves) {
-					// the sequence of the sweep: the valid records in record order, or ascending (p2p_dist_sq, index) (:355-357).  No array holds it (the outputs keep
-					// their bytes where the call writes no entry): the sorted walk selects, step after step, the smallest pair behind the one before
-					auto key_of = [&](uint32_t q) {return decid_view_sort_key(c, decid_view_tree(c, d_data[recs[q].tree_id], recs[q].pos));};
-					float prev_key = 0.0f; uint32_t prev = 0; bool first = true;
-					for (uint32_t p = 0, rj = 0; p < nvalid; ++p) {
-						uint32_t j = 0;
-						if (!tl.sorted) {
-							while (!decid_view_valid(c, d_data, recs[rj])) {++rj;}
-							j = rj++;
-						}
-						else {
-							bool have = false; float best = 0.0f;
-							for (uint32_t q = 0; q < cnt; ++q) {
-								if (!decid_view_valid(c, d_data, recs[q])) continue;
-								float const k = key_of(q);
-								if (!first && !tree_view_before_f(prev_key, prev, k, q)) continue;
-								if (!have || tree_view_before_f(k, q, best, j)) {have = true; best = k; j = q;}
-							}
-							prev_key = best; prev = j; first = false;
-						}
-						decid_tree_data_pod_t const td = d_data[recs[j].tree_id];
-						decid_view_tree_t const g = decid_view_tree(c, td, recs[j].pos);
-						bool nvis = false, wrote = false;
-						decid_view_rec_t const r = decid_view_leaves(c, td, g, nvis, wrote);
-						d_leaf_word[o + j] = r.word; d_leaf_scale[o + j] = r.scale; d_leaf_opacity[o + j] = r.opacity; d_leaf_num[o + j] = r.num;
-						if (wrote && d_not_visible) {d_not_visible[o + j] = nvis ? 1 : 0;}
-						if (r.added) {insert(lb, nlb, decid_view_bb<true>(td, g, (uint32_t)recs[j].tree_id, j, r.opacity));}
-						if (r.listed) {ll[nl++] = j;}
-					}
-				}
-				if (c.branches) {
-					for (uint32_t j = 0; j < cnt; ++j) {
-						if (!decid_view_valid(c, d_data, recs[j])) continue;
-						decid_tree_data_pod_t const td = d_data[recs[j].tree_id];
-						decid_view_tree_t const g = decid_view_tree(c, td, recs[j].pos);
-						bool nvis = false;
-						if (!c.shadow) {nvis = c.leaves ? (d_leaf_word[o + j] & DCV_NOT_VISIBLE) != 0 : (d_not_visible && d_not_visible[o + j] != 0);}
-						decid_view_rec_t const r = decid_view_branches(c, td, g, nvis);
-						d_branch_word[o + j] = r.word; d_branch_scale[o + j] = r.scale; d_branch_opacity[o + j] = r.opacity; d_branch_num[o + j] = r.num;
-						if (r.added) {insert(bb, nbb, decid_view_bb<false>(td, g, (uint32_t)recs[j].tree_id, j, r.opacity));}
-						if (r.listed) {bl[nb++] = j;}
-					}
-				}
-				out.leaf_written = nl; out.branch_written = nb; out.leaf_bb_written = nlb; out.branch_bb_written = nbb; // (a list holds a record once: never more than the capacity)
-			}
-			d_tile_out[t] = out;
-			d_list_counts[4*t] = nl; d_list_counts[4*t + 1] = nb; d_list_counts[4*t + 2] = nlb; d_list_counts[4*t + 3] = nbb;
-		});
+		if constexpr (BE::has_kernels) {if (be.tile_decid_view(c, io, n, d_keys)) return;}
+		// the simple form: a logical thread per tile walks its records in the reference's order, the leaves sweep before the branches sweep (decid_view_tile_literal)
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {decid_view_tile_literal(c, io, t);});
 	}
 
 	// ================================================================ voxels (a14, a15, K8, K9)

@@ -11,6 +11,10 @@
 // combine them -- the same booleans, no branch per term.
 #pragma once
 #include "terra_view.hpp"
+#include "terra_lineintersect.hpp"
+#include "terra_landscape.hpp" // grass_block_pod_t
+#include "../../include/terra.h" // terra_tile_stats
+#include <stdexcept>
 
 namespace terra {
 
@@ -47,6 +51,27 @@ inline grass_view_consts_t grass_view_consts(view_pod_t const &v, float xss, flo
 	c.lod_scale = GRASS_LOD_SCALE/(tt*c.scaled_tile_radius);
 	c.adj_z = v.pos[2] + (float)(2.0*(double)grass_length);                                // camera + point(0.0, 0.0, 2.0*grass_length): the double narrows in point()
 	return c;
+}
+// terra_lineintersect.hpp's box of a tile from these constants: tile_t::draw_grass reads get_mesh_bcube() for all_visible and the minimum distance
+TERRA_HD line_box_t grass_view_box(grass_view_consts_t const &c, int tx, int ty, float mzmin, float mzmax) {
+	line_query_consts_t q;
+	q.xss = c.xss; q.yss = c.yss; q.DX_VAL = c.DX_VAL; q.DY_VAL = c.DY_VAL; q.DX_VAL_INV = 0.0f; q.DY_VAL_INV = 0.0f; q.S = c.S; q.dxoff = c.dxoff; q.dyoff = c.dyoff;
+	return line_tile_box(q, tx, ty, mzmin, mzmax);
+}
+
+// ---- the arrays of a call, in the order of terra_tiles_grass_view[_dev]: host pointers in the host form's first record, device pointers everywhere else
+struct grass_view_io_t {
+	float const *zvals; terra_tile_stats const *stats; grass_block_pod_t const *blocks; uint8_t const *skip;
+	float *insts; uint32_t *aux, *group_counts, *counts; uint8_t *pass;
+};
+// the argument rules of a call, behind grass_view_check: throws what the call refuses; false: nothing to do (n == 0).  dev: the arrays are the device's
+inline bool grass_view_io_check(int32_t const *tile_xy, uint32_t n, uint32_t capacity, grass_view_io_t const &io, bool dev) {
+	if (n == 0) return false;
+	if (!tile_xy || !io.zvals || !io.stats || !io.blocks || !io.group_counts || !io.counts || (capacity && !io.insts)) throw std::invalid_argument("tiles_grass_view: null argument");
+	if (dev && (((uintptr_t)io.zvals | (uintptr_t)io.stats | (uintptr_t)io.blocks | (uintptr_t)io.insts | (uintptr_t)io.aux | (uintptr_t)io.group_counts | (uintptr_t)io.counts) & 3u) != 0) {
+		throw std::invalid_argument("tiles_grass_view: d_zvals, d_stats, d_grass_blocks, d_insts, d_aux, d_group_counts and d_counts must be 4-byte aligned");
+	}
+	return true;
 }
 
 // ---- the tile test: what decides for a whole tile (has_grass() is the caller's: it reads the blocks)
@@ -120,5 +145,51 @@ TERRA_HD uint32_t grass_view_block(grass_view_consts_t const &c, grass_view_tile
 }
 // the aux word of a kept block: bits 0-15 y*dim + x, 16-18 the LOD, 19-31 bix
 TERRA_HD uint32_t grass_view_aux(grass_view_consts_t const &c, uint32_t block, uint32_t key) {return block | ((key / c.nrnd) << 16) | ((key % c.nrnd) << 19);}
+
+// ---- the literal body: tile t of the batch runs the reference's loops; its per-LOD, per-bix lists are the groups' counts, then their offsets, then a second walk
+// in the same scan order that appends every kept block to its group.  keys: a key per block (16 bits: dropped, or lod*nrnd + bix); offs: a running offset per group;
+// nb = dim^2 blocks, nbins = GRASS_VIEW_LODS*nrnd groups and zn = (S + 2)^2 zvals of a tile, as the caller sized the arrays (arguments: computed here they cost the
+// device build registers it spills)
+TERRA_HD void grass_view_tile_literal(grass_view_consts_t const &c, grass_view_io_t const &io, int32_t const *tile_xy, uint32_t capacity, uint16_t *keys, uint32_t *offs,
+	size_t nb, size_t nbins, size_t zn, size_t t)
+{
+	terra_tile_stats const &st = io.stats[t];
+	line_box_t const box = grass_view_box(c, tile_xy[2*t], tile_xy[2*t + 1], st.mzmin, st.mzmax);
+	grass_view_tile_t const tl = grass_view_tile(c, box.d, box.x1, box.y1, st.mzmin, st.mzmax, st.radius);
+	uint32_t *const gc = io.group_counts + t*nbins, *const of = offs + t*nbins;
+	uint16_t *const ky = keys + t*nb;
+	for (size_t b = 0; b < nbins; ++b) {gc[b] = 0u;}
+	bool has_grass = false;
+	if (!(io.skip && io.skip[t]) && tl.in_range) {
+		grass_block_pod_t const *const bl = io.blocks + t*nb;
+		for (uint32_t y = 0; y < c.dim; ++y) {
+			for (uint32_t x = 0; x < c.dim; ++x) {
+				grass_block_pod_t const gb = bl[y*c.dim + x];
+				has_grass = has_grass || gb.ix != 0u;
+				uint32_t const key = grass_view_block(c, tl, x, y, gb.ix, gb.zmin, gb.zmax, io.zvals + t*zn);
+				ky[y*c.dim + x] = (uint16_t)key;
+				if (key != GRASS_VIEW_DROPPED) {++gc[key];}
+			}
+		}
+	}
+	if (!has_grass) { // skipped, too far away (:1612) or !has_grass() (:1609, :3422)
+		io.counts[t] = 0u;
+		if (io.pass) {io.pass[t] = GRASS_VIEW_NO_PASS;}
+		return;
+	}
+	uint32_t total = 0;
+	for (size_t b = 0; b < nbins; ++b) {of[b] = total; total += gc[b];}
+	for (uint32_t i = 0; i < (uint32_t)nb; ++i) {
+		uint32_t const key = ky[i];
+		if (key == GRASS_VIEW_DROPPED) continue;
+		uint32_t const rank = of[key]++;
+		if (rank >= capacity) continue;
+		float *const o = io.insts + (t*capacity + rank)*2;
+		o[0] = (float)(i % c.dim)*c.dx_step; o[1] = (float)(i / c.dim)*c.dy_step; // emplace_back(x*dx_step, y*dy_step) (:1651)
+		if (io.aux) {io.aux[t*capacity + rank] = grass_view_aux(c, i, key);}
+	}
+	io.counts[t] = total;
+	if (io.pass) {io.pass[t] = (uint8_t)tl.wpass;}
+}
 
 } // namespace terra

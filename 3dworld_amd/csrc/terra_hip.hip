@@ -612,11 +612,9 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		return true;
 	}
 	// the grass draw lists for a camera: one workgroup per tile (k_grass_view)
-	bool tile_grass_view(terra::grass_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, float const *zvals, terra_tile_stats const *stats,
-		terra::grass_block_pod_t const *blocks, uint8_t const *skip, uint32_t capacity, float *insts, uint32_t *aux, uint32_t *group_counts, uint32_t *counts, uint8_t *pass,
-		uint16_t *keys)
-	{
-		return launch_per_tile<terra::GV_THREADS>(terra::k_grass_view, n, c, tile_xy, zvals, stats, blocks, skip, capacity, insts, aux, group_counts, counts, pass, keys);
+	bool tile_grass_view(terra::grass_view_consts_t const &c, terra::grass_view_io_t const &io, int32_t const *tile_xy, uint32_t n, uint32_t capacity, uint16_t *keys) {
+		return launch_per_tile<terra::GV_THREADS>(terra::k_grass_view, n, c, tile_xy, io.zvals, io.stats, io.blocks, io.skip, capacity, io.insts, io.aux, io.group_counts, io.counts,
+			io.pass, keys);
 	}
 	// the terrain draw list for a camera: the five launches of k_terrain_view_* (terra_kernels.hpp)
 	bool tile_terrain_view(terra::terrain_view_consts_t const &c, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, uint8_t *status,
@@ -689,28 +687,19 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		return launch_if(true, terra::k_cube_int_trees, dim3(nq/per + ((nq%per) ? 1u : 0u)), dim3(terra::COLL_THREADS), c, in, cubes, cube_tile, nq, result, tile_out);
 	}
 	// the pine and palm tree draw lists for a camera: one workgroup per tile (k_tree_view)
-	bool tile_tree_view(terra::tree_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra::tree_inst_pod_t const *insts, terra_tile_stats const *stats, uint8_t const *skip,
-		float const *trmax, terra::tree_place_pod_t const *pine, uint32_t const *counts, terra::trunk_override_pod_t const *ov, terra::tree_view_tile_pod_t *tile_out, float *bcube,
-		terra::tree_view_inst_pod_t *pine_insts, terra::tree_view_inst_pod_t *palm_insts, uint32_t *inst_counts, uint32_t *leaf_list, uint32_t *leaf_counts, uint8_t *trunk, uint32_t *keys)
-	{
-		return launch_per_tile<terra::TRV_THREADS>(terra::k_tree_view, n, c, tile_xy, insts, stats, skip, trmax, pine, counts, ov, tile_out, bcube, pine_insts, palm_insts, inst_counts,
-			leaf_list, leaf_counts, trunk, keys);
+	bool tile_tree_view(terra::tree_view_consts_t const &c, terra::tree_view_io_t const &io, int32_t const *tile_xy, uint32_t n, terra::tree_inst_pod_t const *insts, uint32_t *keys) {
+		return launch_per_tile<terra::TRV_THREADS>(terra::k_tree_view, n, c, tile_xy, insts, io.stats, io.skip, io.trmax, io.pine, io.counts, io.ov, io.tile_out, io.bcube, io.pine_insts,
+			io.palm_insts, io.inst_counts, io.leaf_list, io.leaf_counts, io.trunk, keys);
 	}
 	// the scenery draw lists for a camera: one workgroup per tile (k_scenery_view)
-	bool tile_scenery_view(terra::scenery_view_consts_t const &c, int32_t const *tile_xy, uint32_t n, terra_tile_stats const *stats, uint8_t const *skip,
-		terra::scenery_place_pod_t const *objs, uint32_t const *counts, float const *rov, terra::scenery_view_tile_pod_t *tile_out, uint32_t *draw, float *size_scale, float *dist,
-		uint32_t *list, uint32_t *group_counts)
-	{
-		return launch_per_tile<terra::SCVW_THREADS>(terra::k_scenery_view, n, c, tile_xy, stats, skip, objs, counts, rov, tile_out, draw, size_scale, dist, list, group_counts);
+	bool tile_scenery_view(terra::scenery_view_consts_t const &c, terra::scenery_view_io_t const &io, int32_t const *tile_xy, uint32_t n) {
+		return launch_per_tile<terra::SCVW_THREADS>(terra::k_scenery_view, n, c, tile_xy, io.stats, io.skip, io.objs, io.counts, io.rov, io.tile_out, io.draw, io.size_scale, io.dist, io.list,
+			io.group_counts);
 	}
 	// the deciduous tree draw lists for a camera: one workgroup per tile (k_decid_view)
-	bool tile_decid_view(terra::decid_view_consts_t const &c, uint32_t n, terra::decid_tree_data_pod_t const *data, uint8_t const *skip, terra::decid_place_pod_t const *decid,
-		uint32_t const *counts, uint8_t *not_visible, terra::decid_view_tile_pod_t *tile_out, float *bcube, uint32_t *leaf_word, float *leaf_scale, float *leaf_opacity,
-		uint32_t *leaf_num, uint32_t *branch_word, float *branch_scale, float *branch_opacity, uint32_t *branch_num, uint32_t *leaf_list, uint32_t *branch_list,
-		terra::decid_view_bb_pod_t *leaf_bb, terra::decid_view_bb_pod_t *branch_bb, uint32_t *list_counts, uint32_t *keys)
-	{
-		return launch_per_tile<terra::DCV_THREADS>(terra::k_decid_view, n, c, data, skip, decid, counts, not_visible, tile_out, bcube, leaf_word, leaf_scale, leaf_opacity, leaf_num,
-			branch_word, branch_scale, branch_opacity, branch_num, leaf_list, branch_list, leaf_bb, branch_bb, list_counts, keys);
+	bool tile_decid_view(terra::decid_view_consts_t const &c, terra::decid_view_io_t const &io, uint32_t n, uint32_t *keys) {
+		return launch_per_tile<terra::DCV_THREADS>(terra::k_decid_view, n, c, io.data, io.skip, io.decid, io.counts, io.not_visible, io.tile_out, io.bcube, io.leaf_word, io.leaf_scale,
+			io.leaf_opacity, io.leaf_num, io.branch_word, io.branch_scale, io.branch_opacity, io.branch_num, io.leaf_list, io.branch_list, io.leaf_bb, io.branch_bb, io.list_counts, keys);
 	}
 	void voxel_noise(float *out, size_t nvox, terra::vox_noise_job_t const &J, bool perlin, bool fused, uint32_t const *lut3) {
 		if (opt->simple_kernels) {voxel_noise_simple(out, nvox, J, perlin); return;}

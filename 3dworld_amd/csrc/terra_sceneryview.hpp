@@ -17,6 +17,8 @@
 #include "terra_terrainview.hpp"
 #include "terra_sceneryplace.hpp"
 #include "terra_powf.hpp"
+#include "terra_landscape.hpp" // min_u32
+#include <stdexcept>
 
 namespace terra {
 
@@ -257,6 +259,53 @@ TERRA_HD uint32_t scenery_view_streams(int kind, uint32_t w) {
 	default: break;
 	}
 	return s;
+}
+
+// ---- the arrays of a call, in the order of terra_tiles_scenery_view[_dev]: host pointers in the host form's first record, device pointers everywhere else
+struct scenery_view_io_t {
+	terra_tile_stats const *stats; uint8_t const *skip; scenery_place_pod_t const *objs; uint32_t const *counts; float const *rov;
+	scenery_view_tile_pod_t *tile_out; uint32_t *draw; float *size_scale, *dist; uint32_t *list, *group_counts;
+};
+// the argument rules of a call, behind scenery_view_check: throws what the call refuses; false: nothing to do (n == 0).  dev: the arrays are the device's
+inline bool scenery_view_io_check(int32_t const *tile_xy, uint32_t n, uint32_t capacity, uint32_t list_capacity, scenery_view_io_t const &io, bool dev) {
+	if ((uint64_t)n*capacity > 0xFFFFFFFFull || (uint64_t)n*list_capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_scenery_view: n*capacity and n*list_capacity must fit 32 bits");
+	if (n == 0) return false;
+	if (!tile_xy || !io.stats || !io.counts || !io.tile_out || !io.group_counts || (capacity && (!io.objs || !io.draw || !io.size_scale || !io.dist)) || (list_capacity && !io.list)) {
+		throw std::invalid_argument("tiles_scenery_view: null argument");
+	}
+	if (dev && (((uintptr_t)io.stats | (uintptr_t)io.objs | (uintptr_t)io.counts | (uintptr_t)io.rov | (uintptr_t)io.tile_out | (uintptr_t)io.draw | (uintptr_t)io.size_scale |
+	             (uintptr_t)io.dist | (uintptr_t)io.list | (uintptr_t)io.group_counts) & 3u) != 0) {
+		throw std::invalid_argument("tiles_scenery_view: every array but skip must be 4-byte aligned");
+	}
+	return true;
+}
+
+// ---- the literal body: tile t of the batch, its records walked once, then once per stream for the lists
+TERRA_HD void scenery_view_tile_literal(scenery_view_consts_t const &c, scenery_view_io_t const &io, int32_t const *tile_xy, size_t t) {
+	uint32_t const cnt = (io.skip && io.skip[t]) ? 0u : min_u32(io.counts[t], c.cap);
+	scenery_view_tile_pod_t o; o.dist_scale = 0.0f; o.scale_val = 0.0f; o.flags = o.num_records = o.list_written = 0u; o.pad[0] = o.pad[1] = o.pad[2] = 0u;
+	uint32_t groups[SCV_GROUPS];
+	for (uint32_t g = 0; g < SCV_GROUPS; ++g) {groups[g] = 0u;}
+	float ds = 0.0f;
+	if (cnt != 0u && scenery_view_tile(c, tile_xy[2*t], tile_xy[2*t + 1], io.stats[t].mzmin, io.stats[t].mzmax, io.stats[t].radius, ds)) {
+		scenery_place_pod_t const *const recs = io.objs + t*c.cap;
+		for (uint32_t j = 0; j < cnt; ++j) {
+			scenery_view_rec_t const r = scenery_view_record(c, recs[j], io.rov ? io.rov[t*c.cap + j] : 0.0f);
+			io.draw[t*c.cap + j] = r.word; io.size_scale[t*c.cap + j] = r.size_scale; io.dist[t*c.cap + j] = r.dist;
+		}
+		uint32_t at = 0;
+		#pragma unroll // (a walk per stream with its bit and its group as constants, the groups in registers: what the device build made of the loop in the driver)
+		for (uint32_t s = 0; s < SCV_STREAMS; ++s) { // a stable split of the record list
+			for (uint32_t j = 0; j < cnt; ++j) {
+				if (!((scenery_view_streams(recs[j].kind, io.draw[t*c.cap + j]) >> s) & 1u)) continue;
+				if (at < c.list_cap) {io.list[t*c.list_cap + at] = j;}
+				++at; ++groups[scenery_view_group(s)];
+			}
+		}
+		o.dist_scale = ds; o.scale_val = c.scale_val; o.flags = scenery_view_tile_flags(c); o.num_records = cnt; o.list_written = min_u32(at, c.list_cap);
+	}
+	io.tile_out[t] = o;
+	for (uint32_t g = 0; g < SCV_GROUPS; ++g) {io.group_counts[t*SCV_GROUPS + g] = groups[g];}
 }
 
 } // namespace terra

@@ -20,6 +20,7 @@
 #include "terra_view.hpp"
 #include "terra_terrainview.hpp"
 #include "terra_treeao.hpp"
+#include <stdexcept>
 
 namespace terra {
 
@@ -236,8 +237,90 @@ TERRA_HD uint32_t tree_view_render_all(tree_view_consts_t const &c, tree_view_ti
 	if (tl.near_sweep && !c.a.instanced) return tl.draw_all_near ? tl.out.num_pine : 0u; // (a culled sweep draws nothing)
 	return tl.far_sweep ? tl.out.num_pine : 0u;
 }
-// std::pair<float, unsigned>'s operator< and tree_inst_t's with the record index behind the id
-TERRA_HD bool tree_view_before_f(float da, uint32_t ia, float db, uint32_t ib) {return da < db || (!(db < da) && ia < ib);}
-TERRA_HD bool tree_view_before_u(uint32_t da, uint32_t ia, uint32_t db, uint32_t ib) {return da < db || (da == db && ia < ib);}
+
+// ---- the arrays of a call, in the order of terra_tiles_tree_view[_dev]: host pointers in the host form's first record, device pointers everywhere else
+struct tree_view_io_t {
+	terra_tile_stats const *stats; uint8_t const *skip; float const *trmax; tree_place_pod_t const *pine; uint32_t const *counts; trunk_override_pod_t const *ov;
+	tree_view_tile_pod_t *tile_out; float *bcube; tree_view_inst_pod_t *pine_insts, *palm_insts; uint32_t *inst_counts, *leaf_list, *leaf_counts; uint8_t *trunk;
+};
+// the argument rules of a call, behind tree_view_check: throws what the call refuses; false: nothing to do (n == 0).  dev: the arrays are the device's
+inline bool tree_view_io_check(int32_t const *tile_xy, uint32_t n, uint32_t capacity, tree_view_io_t const &io, bool dev) {
+	if ((uint64_t)n*capacity > 0xFFFFFFFFull) throw std::invalid_argument("tiles_tree_view: n*capacity must fit 32 bits");
+	if (n == 0) return false;
+	if (!tile_xy || !io.stats || !io.counts || !io.tile_out || !io.bcube || !io.inst_counts || !io.leaf_counts ||
+	    (capacity && (!io.pine || !io.pine_insts || !io.palm_insts || !io.leaf_list || !io.trunk))) throw std::invalid_argument("tiles_tree_view: null argument");
+	if (dev && (((uintptr_t)io.stats | (uintptr_t)io.trmax | (uintptr_t)io.pine | (uintptr_t)io.counts | (uintptr_t)io.ov | (uintptr_t)io.tile_out | (uintptr_t)io.bcube |
+	             (uintptr_t)io.pine_insts | (uintptr_t)io.palm_insts | (uintptr_t)io.inst_counts | (uintptr_t)io.leaf_list | (uintptr_t)io.leaf_counts) & 3u) != 0) {
+		throw std::invalid_argument("tiles_tree_view: every array but skip and trunk must be 4-byte aligned");
+	}
+	return true;
+}
+
+// ---- the literal body: tile t of the batch, its records walked in the reference's order.  insts: the instance table (null unless instanced)
+TERRA_HD void tree_view_tile_literal(tree_view_consts_t const &c, tree_view_io_t const &io, int32_t const *tile_xy, tree_inst_pod_t const *insts, size_t t) {
+	uint32_t const cnt = (io.skip && io.skip[t]) ? 0u : min_u32(io.counts[t], c.cap);
+	tree_place_pod_t const *const recs = io.pine + t*c.cap;
+	trunk_override_pod_t const *const ovs = io.ov ? io.ov + t*c.cap : nullptr;
+	// calc_bcube, num_pine_trees, num_palm_trees
+	float bc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+	bool any = false;
+	uint32_t nvalid = 0, np = 0, npalm = 0;
+	tree_view_rec_t rec;
+	for (uint32_t j = 0; j < cnt; ++j) {
+		if (!tree_view_record(c, insts, recs[j], ovs ? ovs + j : nullptr, rec)) continue;
+		++nvalid; np += is_pine_tree_type(rec.type) ? 1u : 0u; npalm += (rec.type == T_PALM) ? 1u : 0u;
+		float d[6];
+		if (!tree_view_bounds(rec, d)) continue;
+		if (!any) {for (int k = 0; k < 6; ++k) {bc[k] = d[k];} any = true;}
+		else {box_union(bc, d);}
+	}
+	for (int k = 0; k < 6; ++k) {io.bcube[t*6 + k] = bc[k];}
+	if (nvalid == 0) { // skipped, or pine_trees.empty() (:1468)
+		tree_view_tile_pod_t z; z.dscale = 0.0f; z.weight = 0.0f; z.flags = 0u; z.num_pine = z.num_palm = z.num_trees = z.leaf_written = z.pad = 0u;
+		io.tile_out[t] = z; io.inst_counts[2*t] = io.inst_counts[2*t + 1] = 0u; io.leaf_counts[2*t] = io.leaf_counts[2*t + 1] = 0u;
+		return;
+	}
+	tree_view_tile_t tl = tree_view_tile(c, tile_xy[2*t], tile_xy[2*t + 1], io.stats[t], io.trmax ? io.trmax[t] : 0.0f, nvalid, np, npalm, bc);
+	tree_view_inst_pod_t *const pi = io.pine_insts + t*c.cap, *const mi = io.palm_insts + t*c.cap;
+	uint32_t *const ll = io.leaf_list + t*c.cap;
+	uint32_t npi = 0, nmi = 0, nl = 0, nm = 0;
+	bool skipped = false;
+	bool const need_vis = (tl.pine_insts && !tl.draw_all_near) || (tl.palm_insts && !tl.all_visible) || tl.pine_list;
+	for (uint32_t j = 0; j < cnt; ++j) {
+		bool const valid = tree_view_record(c, insts, recs[j], ovs ? ovs + j : nullptr, rec);
+		uint8_t const b = (valid && tl.trunks) ? tree_view_trunk(c, rec, tl.all_visible != 0) : (uint8_t)0;
+		io.trunk[t*c.cap + j] = b; skipped = skipped || b == 1;
+		if (!valid) continue;
+		bool const pine = is_pine_tree_type(rec.type), palm = rec.type == T_PALM;
+		bool const vis = need_vis && tree_view_leaves_visible(c, rec);
+		int32_t const id = recs[j].inst;
+		auto insert = [&](tree_view_inst_pod_t *out, uint32_t &m) { // where sort(insts) puts it: behind every entry with an id that is not larger
+			uint32_t k = m++;
+			for (; k > 0 && out[k - 1].id > (uint32_t)id; --k) {out[k] = out[k - 1];}
+			out[k].id = (uint32_t)id; for (int q = 0; q < 3; ++q) {out[k].pt[q] = rec.pos[q];}
+		};
+		if (tl.pine_insts && pine && id >= 0 && (tl.draw_all_near || vis)) {insert(pi, npi);}
+		if (tl.palm_insts && palm && id >= 0 && (tl.all_visible || vis)) {insert(mi, nmi);}
+		if (tl.pine_list && pine && vis) {
+			uint32_t k = nl++;
+			if (tl.pine_sorted) { // get_back_to_front_ordering: ascending (p2p_dist_sq, index)
+				float const key = tree_view_sort_key(c, rec.pos);
+				for (; k > 0 && tree_view_before_f(key, j, tree_view_sort_key(c, recs[ll[k - 1]].pos), ll[k - 1]); --k) {ll[k] = ll[k - 1];}
+			}
+			ll[k] = j;
+		}
+	}
+	if (tl.palm_list) { // draw_non_pine_leaves(0, 1, 0, ..): behind the pine entries
+		for (uint32_t j = 0; j < cnt; ++j) {
+			if (!tree_view_record(c, insts, recs[j], ovs ? ovs + j : nullptr, rec) || rec.type != T_PALM || !tree_view_leaves_visible(c, rec)) continue;
+			ll[nl + nm++] = j;
+		}
+	}
+	if (skipped) {tl.out.flags = (tl.out.flags & ~(uint32_t)TRV_TRUNK_MASK) | TRV_TRUNK_POLY_SKIPPED;}
+	tl.out.leaf_written = nl + nm;
+	io.tile_out[t] = tl.out;
+	io.inst_counts[2*t] = npi; io.inst_counts[2*t + 1] = nmi;
+	io.leaf_counts[2*t] = tl.pine_list ? nl : tree_view_render_all(c, tl); io.leaf_counts[2*t + 1] = nm;
+}
 
 } // namespace terra

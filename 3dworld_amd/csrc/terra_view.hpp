@@ -141,4 +141,9 @@ TERRA_HD void box_assign_or_union(float bc[6], float const d[6]) {
 	}
 }
 
+// ---- the (key, index) order of the tree and deciduous draw lists and of the kernels' ranks: std::pair<float, unsigned>'s operator< and tree_inst_t's with the
+// record index behind the id
+TERRA_HD bool tree_view_before_f(float da, uint32_t ia, float db, uint32_t ib) {return da < db || (!(db < da) && ia < ib);}
+TERRA_HD bool tree_view_before_u(uint32_t da, uint32_t ia, uint32_t db, uint32_t ib) {return da < db || (da == db && ia < ib);}
+
 } // namespace terra

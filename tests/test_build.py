@@ -1,3 +1,19 @@
+import pytest
+
+
+@pytest.mark.parametrize("header", ["terra_grassview.hpp", "terra_treeview.hpp", "terra_sceneryview.hpp", "terra_decidview.hpp", "terra_lineintersect.hpp"])
+def test_pass_header_stands_alone(header, tmp_path):
+    """A draw-list pass header holds the pass's records, constants, leaf functions and literal body, and the line-query header the leaf code the grass pass
+    shares with the line queries: a translation unit that includes nothing else compiles as plain C++17 -- nothing in them needs the driver."""
+    import os, shutil, subprocess
+    cxx = shutil.which(os.environ.get("CXX") or "g++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tu = tmp_path / "alone.cpp"
+    tu.write_text('#include "%s"\n' % header)
+    r = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I" + os.path.join(root, "3dworld_amd", "csrc"), str(tu)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
 
 
 def test_hot_kernels_do_not_spill():
