@@ -1050,6 +1050,84 @@ int terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 		if (h_status) {ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);}
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_smap_plan_args) == sizeof(terra::smap_plan_args_pod_t) && sizeof(terra_smap_plan_args) == 68, "terra_smap_plan_args layout");
+static_assert(sizeof(terra_smap_cast_args) == sizeof(terra::smap_cast_args_pod_t) && sizeof(terra_smap_cast_args) == 32, "terra_smap_cast_args layout");
+static_assert(TERRA_SMAP_NONE == terra::SMAP_NONE && (int)TERRA_SMAP_USABLE == (int)terra::SMP_USABLE && (int)TERRA_SMAP_TILE_FULLY_IN_CITY == (int)terra::TV_FLAG_FULLY_IN_CITY, "smap enums");
+int terra_tiles_smap_plan_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_smap_plan_args *args,
+                              const terra_tile_stats *d_stats, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags, uint8_t *d_smap_state, uint32_t *d_plan,
+                              float *d_dist_scale, float *d_shadow_bcube, uint32_t *d_receivers, uint32_t *d_counts, uint8_t *d_terrain_flags, uint32_t *d_recomp_order) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::smap_plan_args_pod_t a; memcpy(&a, args, sizeof(a));
+	terra::smap_plan_io_t const io = {d_stats, d_trmax, d_tile_zmax, d_flags, d_smap_state, d_plan, d_dist_scale, d_shadow_bcube, d_receivers, d_counts, d_terrain_flags, d_recomp_order};
+	TERRA_TRY ctx->eng.tiles_smap_plan_dev(tile_xy, n, dxoff, dyoff, v, a, io); TERRA_CATCH
+}
+int terra_tiles_smap_plan(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_smap_plan_args *args,
+                          const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, uint8_t *h_smap_state, uint32_t *h_plan,
+                          float *h_dist_scale, float *h_shadow_bcube, uint32_t *h_receivers, uint32_t *h_counts, uint8_t *h_terrain_flags, uint32_t *h_recomp_order) {
+	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
+	terra::smap_plan_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.smap_plan_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
+		terra::smap_plan_io_t const h = {h_stats, h_trmax, h_tile_zmax, h_flags, h_smap_state, h_plan, h_dist_scale, h_shadow_bcube, h_receivers, h_counts, h_terrain_flags, h_recomp_order};
+		if (!terra::smap_plan_io_check(tile_xy, n, h, false)) return TERRA_OK;
+		// every output goes up and comes back: what the call does not write keeps the caller's bytes
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), tr = st.opt_in(h_trmax, (size_t)n*4), tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n),
+			ss = st.inout(h_smap_state, n), pl = st.inout(h_plan, (size_t)n*4), ds = st.inout(h_dist_scale, (size_t)n*4), sb = st.inout(h_shadow_bcube, (size_t)n*24),
+			rc = st.inout(h_receivers, (size_t)n*4), cn = st.inout(h_counts, 8), tf = st.inout(h_terrain_flags, n, h_terrain_flags != nullptr),
+			ro = st.inout(h_recomp_order, (size_t)n*4, h_recomp_order != nullptr);
+		st.begin();
+		ctx->eng.tiles_smap_plan_dev(tile_xy, n, dxoff, dyoff, v, a, terra::smap_plan_io_t{st.dev<terra_tile_stats>(s), st.dev<float>(tr), st.dev<float>(tz), st.dev<uint8_t>(fl),
+			st.dev<uint8_t>(ss), st.dev<uint32_t>(pl), st.dev<float>(ds), st.dev<float>(sb), st.dev<uint32_t>(rc), st.dev<uint32_t>(cn), st.dev<uint8_t>(tf), st.dev<uint32_t>(ro)});
+		st.end();
+	TERRA_CATCH
+}
+int terra_tiles_smap_casters_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, uint32_t R, const uint32_t *d_recv, const terra_view *views,
+                                 const float *bsm, const float *lpos, const terra_smap_cast_args *args, const terra_tile_stats *d_stats, const float *d_trmax,
+                                 const float *d_tile_zmax, const uint8_t *d_flags, const uint32_t *d_decid_counts, uint32_t *d_to_draw, uint32_t *d_terrain, uint32_t *d_counts,
+                                 uint8_t *d_not_drawn, uint8_t *d_status) {
+	TERRA_CHECK_CTX if (!args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::smap_cast_args_pod_t a; memcpy(&a, args, sizeof(a));
+	terra::smap_cast_io_t const io = {d_stats, d_trmax, d_tile_zmax, d_flags, d_decid_counts, d_recv, d_to_draw, d_terrain, d_counts, d_not_drawn, d_status};
+	TERRA_TRY ctx->eng.tiles_smap_casters_dev(tile_xy, n, dxoff, dyoff, R, (terra::view_pod_t const *)views, bsm, lpos, a, io); TERRA_CATCH
+}
+int terra_tiles_smap_casters(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, uint32_t R, const uint32_t *h_recv, const terra_view *views,
+                             const float *bsm, const float *lpos, const terra_smap_cast_args *args, const terra_tile_stats *h_stats, const float *h_trmax,
+                             const float *h_tile_zmax, const uint8_t *h_flags, const uint32_t *h_decid_counts, uint32_t *h_to_draw, uint32_t *h_terrain, uint32_t *h_counts,
+                             uint8_t *h_not_drawn, uint8_t *h_status) {
+	TERRA_CHECK_CTX if (!args) return terra::fail(TERRA_ERR_ARG, "null argument");
+	terra::smap_cast_args_pod_t a; memcpy(&a, args, sizeof(a));
+	TERRA_TRY
+		ctx->eng.smap_cast_check(a); // the scene, the tile size and the args: before anything is staged
+		terra::smap_cast_io_t const h = {h_stats, h_trmax, h_tile_zmax, h_flags, h_decid_counts, h_recv, h_to_draw, h_terrain, h_counts, h_not_drawn, h_status};
+		if (!terra::smap_cast_io_check(tile_xy, n, R, (terra::view_pod_t const *)views, bsm, lpos, a, h, false)) return TERRA_OK;
+		size_t const rn = (size_t)R*n;
+		terra_stage st(ctx->eng);
+		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), tr = st.opt_in(h_trmax, (size_t)n*4), tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n),
+			dc = st.opt_in(h_decid_counts, (size_t)n*4), rv = st.in(h_recv, (size_t)R*4), td = st.inout(h_to_draw, rn*4), te = st.inout(h_terrain, rn*4), cn = st.inout(h_counts, (size_t)R*8),
+			nd = st.inout(h_not_drawn, rn), su = st.inout(h_status, R);
+		st.begin();
+		ctx->eng.tiles_smap_casters_dev(tile_xy, n, dxoff, dyoff, R, (terra::view_pod_t const *)views, bsm, lpos, a, terra::smap_cast_io_t{st.dev<terra_tile_stats>(s), st.dev<float>(tr),
+			st.dev<float>(tz), st.dev<uint8_t>(fl), st.dev<uint32_t>(dc), st.dev<uint32_t>(rv), st.dev<uint32_t>(td), st.dev<uint32_t>(te), st.dev<uint32_t>(cn), st.dev<uint8_t>(nd),
+			st.dev<uint8_t>(su)});
+		st.end();
+	TERRA_CATCH
+}
+int terra_make_light_view(const float lpos[3], const float bounds[6], float near_clip, terra_view *out, float *behind_sphere_mult) {
+	if (!lpos || !bounds || !out || !behind_sphere_mult) return terra::fail(TERRA_ERR_ARG, "null argument");
+	bool fin = isfinite(near_clip);
+	for (int k = 0; k < 3; ++k) {fin = fin && isfinite(lpos[k]);}
+	for (int k = 0; k < 6; ++k) {fin = fin && isfinite(bounds[k]);}
+	terra::view_pod_t v; float m = 0.0f;
+	if (!fin || !terra::smap_light_view(lpos, bounds, near_clip, v, m)) {
+		return terra::fail(TERRA_ERR_ARG, "terra_make_light_view: needs finite arguments, strictly normalized bounds, a light outside the box's centre and a finite view");
+	}
+	memcpy(out, &v, sizeof(v));
+	*behind_sphere_mult = m;
+	return TERRA_OK;
+}
 static_assert(sizeof(terra_cloud_params) == sizeof(terra::cloud_params_pod_t) && sizeof(terra_cloud_params) == 12, "terra_cloud_params layout");
 static_assert(sizeof(terra_cloud_step) == sizeof(terra::cloud_step_pod_t) && sizeof(terra_cloud_step) == 20, "terra_cloud_step layout");
 static_assert(sizeof(terra_cloud) == sizeof(terra::cloud_pod_t) && sizeof(terra_cloud) == 32, "terra_cloud layout");

@@ -22,6 +22,7 @@
 #include "terra_grassview.hpp"
 #include "terra_terrainview.hpp"
 #include "terra_waterview.hpp"
+#include "terra_smapview.hpp"
 #include "terra_clouds.hpp"
 #include "terra_treeao.hpp"
 #include "terra_treeedit.hpp"
@@ -3245,6 +3246,68 @@ template<class BE> struct terra_engine {
 			}
 			d_counts[1] = nc;
 		});
+	}
+
+	// ---- the shadow-map plan of a batch (terra_smapview.hpp): tile_t::update_range's deletion (src/tiled_mesh.cpp:1416), the shadow part of tile_draw_t::pre_draw's loop
+	// (:2781-2799), tile_t::setup_shadow_maps (:981-1016), the gate of try_bind_shadow_map (:1958-1959) and the recompute queue of :2445-2448.  The checks that need no array
+	// (the host form runs them before it stages anything):
+	void smap_plan_check(view_pod_t const &view, smap_plan_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!view_finite(view)) throw std::invalid_argument("tiles_smap_plan: a member of the view is not finite");
+		char const *why = nullptr;
+		if (!smap_plan_args_ok(a, why)) throw std::invalid_argument(why);
+	}
+	void tiles_smap_plan_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, smap_plan_args_pod_t const &a, smap_plan_io_t const &io) {
+		smap_plan_check(view, a);
+		if (!smap_plan_io_check(tile_xy, n, io, true)) return;
+		smap_consts_t const c = smap_plan_consts(view, a, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
+		terrain_view_in_t const in = {io.stats, nullptr, io.trmax, io.tile_zmax, io.flags, nullptr};
+		int32_t *d_txy; smap_rank_key_t *d_keys; // scratch: the coordinates, and what the queue's rank reads of a tile
+		stage_layout_t lay;
+		lay.add(d_keys, n); lay.add(d_txy, (size_t)n*2);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		if constexpr (BE::has_kernels) {if (be.tile_smap_plan(c, in, io, d_txy, n, d_keys)) return;}
+		// the simple form.  (1) one thread: the reference's loops in batch order; (2) a thread per tile: its place in the queue
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {smap_plan_literal_tiles(c, in, io, d_txy, n, d_keys);});
+		if (c.want_recomp && io.recomp_order) {
+			uint32_t *const order = io.recomp_order;
+			be.launch(n, [=] TERRA_LAMBDA (size_t t) {if (d_keys[t].present) {order[smap_recomp_place(d_keys, n, (uint32_t)t)] = (uint32_t)t;}});
+		}
+	}
+	// ---- the casters of R shadow-map renders (terra_smapview.hpp): the head of tile_draw_t::draw_shadow_pass (:3025-3043) and the filter of draw_tiles_shadow_pass
+	// (:3004-3018) for R independent (receiver, light) pairs.  views, bsm and lpos are host arrays; the call uploads them
+	void smap_cast_check(smap_cast_args_pod_t const &a) const {
+		require_scene();
+		require_tile_size();
+		if (!smap_cast_args_finite(a)) throw std::invalid_argument("tiles_smap_casters: a member of the args is not finite");
+	}
+	void tiles_smap_casters_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, uint32_t R, view_pod_t const *views, float const *bsm, float const *lpos,
+		smap_cast_args_pod_t const &a, smap_cast_io_t const &io)
+	{
+		smap_cast_check(a);
+		if (!smap_cast_io_check(tile_xy, n, R, views, bsm, lpos, a, io, true)) return;
+		view_pod_t const none = {};
+		smap_consts_t const c = smap_consts(none, 1.0f, a.water_enabled, a.b_ext, a.road_len, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
+		terrain_view_in_t const in = {io.stats, nullptr, io.trmax, io.tile_zmax, io.flags, nullptr};
+		// scratch: the coordinates, the per-tile geometry that all R renders share, the views, their behind_sphere_mult and the light positions
+		int32_t *d_txy; smap_geom_t *d_geom; view_pod_t *d_views; float *d_bsm, *d_lpos;
+		stage_layout_t lay;
+		lay.add(d_geom, n); lay.add(d_txy, (size_t)n*2); lay.add(d_views, R); lay.add(d_bsm, R); lay.add(d_lpos, (size_t)R*3);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
+		std::vector<view_pod_t> cast_views(R);
+		for (uint32_t r = 0; r < R; ++r) {cast_views[r] = smap_cast_view(views[r]);} // near_ = 0 (:3032) on the call's copy
+		be.h2d_async(d_views, cast_views.data(), (size_t)R*sizeof(view_pod_t));
+		be.h2d_async(d_bsm, bsm, (size_t)R*4);
+		be.h2d_async(d_lpos, lpos, (size_t)R*12);
+		int const decid = a.decid_trees_only ? 1 : 0, adj = a.inc_adj_smap ? 1 : 0;
+		if constexpr (BE::has_kernels) {if (be.tile_smap_casters(c, in, io, d_txy, n, R, d_geom, d_views, d_bsm, d_lpos, decid, adj)) return;}
+		// the simple form.  (1) a logical thread per tile: its geometry; (2) a logical thread per render: the reference's loops over the batch
+		uint32_t const *const decid_counts = io.decid_counts;
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {d_geom[t] = smap_geom(c, in, decid_counts, decid, d_txy, t);});
+		be.launch(R, [=] TERRA_LAMBDA (size_t r) {smap_casters_literal(d_geom, io, d_views, d_bsm, d_lpos, n, decid, adj, r);});
 	}
 
 	// ---- the clouds of a batch (terra_clouds.hpp): tile_t::update_tile_clouds (src/tiled_mesh.cpp:1822-1827) for every tile in batch order -- the first loop of

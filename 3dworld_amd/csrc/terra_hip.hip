@@ -654,6 +654,29 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 	{
 		return launch_if(true, terra::k_water_view, dim3(1), dim3(terra::TV_THREADS), c, in, tile_xy, nbr, n, status, wv, water_list, cap_mask, counts);
 	}
+	// the shadow-map plan: a lane per tile, the receivers by one workgroup, the recompute queue by rank (k_smap_plan*)
+	bool tile_smap_plan(terra::smap_consts_t const &c, terra::terrain_view_in_t const &in, terra::smap_plan_io_t const &io, int32_t const *tile_xy, uint32_t n, terra::smap_rank_key_t *keys) {
+		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
+		bool const recomp = c.want_recomp && io.recomp_order;
+		run(terra::k_smap_plan, dim3(nb), dim3(T), 0, c, in, io, tile_xy, n, keys);
+		run(terra::k_smap_plan_lists, dim3(1), dim3(T), 0, n, (uint32_t const *)io.plan, (terra::smap_rank_key_t const *)keys, io.receivers, io.counts, recomp ? 1 : 0);
+		if (recomp) {run(terra::k_smap_plan_rank, dim3(nb), dim3(T), 0, (terra::smap_rank_key_t const *)keys, n, io.recomp_order);}
+		return true;
+	}
+	// the casters of R renders: the geometry of the batch once, then a workgroup per render (k_smap_geom, k_smap_casters)
+	bool tile_smap_casters(terra::smap_consts_t const &c, terra::terrain_view_in_t const &in, terra::smap_cast_io_t const &io, int32_t const *tile_xy, uint32_t n, uint32_t R,
+		terra::smap_geom_t *geom, terra::view_pod_t const *views, float const *bsm, float const *lpos, int decid_trees_only, int inc_adj_smap)
+	{
+		if (opt->simple_kernels || n > 0x7FFFFFFFu || R > 0x7FFFFFFFu) return false;
+		use();
+		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
+		run(terra::k_smap_geom, dim3(nb), dim3(T), 0, c, in, io.decid_counts, decid_trees_only, tile_xy, n, geom);
+		run(terra::k_smap_casters, dim3(R), dim3(terra::SMC_THREADS), 0, (terra::smap_geom_t const *)geom, n, io.recv, views, bsm, lpos, decid_trees_only, inc_adj_smap, io.to_draw,
+			io.terrain, io.counts, io.not_drawn, io.status);
+		return true;
+	}
 	// the clouds' update: the marks of every record's path, the unmarked tiles in parallel, the marked tiles replayed in batch order by one workgroup
 	bool tile_update_clouds(terra::cloud_consts_t const &c, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, terra::cloud_tile_pod_t *state, terra::cloud_pod_t *clouds,
 		uint8_t *touched, uint32_t *order, uint32_t *total)

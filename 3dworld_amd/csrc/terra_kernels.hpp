@@ -2354,6 +2354,111 @@ __global__ __launch_bounds__(TV_THREADS) void k_water_view(terrain_view_consts_t
 	if (tid == 0) {counts[1] = nc;}
 }
 
+// ------------------------------------------------------------------ the shadow-map plan of a tile batch (tile_t::setup_shadow_maps, src/tiled_mesh.cpp:981-1016, with
+// update_range's deletion, :1416, pre_draw's loop, :2781-2799, and the queue of :2445-2448; terra_smapview.hpp), three launches on one stream:
+//  1. k_smap_plan: a lane per tile runs smap_plan_tile and leaves the plan word, dist_scale, the box, the new state byte, the terrain flag and what the queue's rank
+//     reads of the tile (its key, its position, whether it is present) as one 16-byte record.
+//  2. k_smap_plan_lists: one workgroup walks the batch 256 tiles at a time and appends the receivers in batch order (tp_emit); the present tiles are counted on the way.
+//  3. k_smap_plan_rank: k_terrain_view_rank's scheme on the queue: a lane per tile counts the present tiles that come after it in the sorted queue -- its place in
+//     the order of pop_back.  The records pass through LDS 256 at a time, where every lane reads them at the same address (as k_terrain_view_lists' keys): read
+//     from global memory at uniform addresses, a record a turn, the loop waited out one scalar load's latency per record (625 us for 4096 tiles, most of the call).
+//     Launched only where a recomp_order is wanted.
+// The casters (the head of tile_draw_t::draw_shadow_pass, :3025-3043, the filter of draw_tiles_shadow_pass, :3004-3018), two launches:
+//  4. k_smap_geom: a lane per tile leaves the 64 bytes every render reads of it (centre, radius with water, get_bcube(), the xy of get_shadow_bcube(), three flags).
+//  5. k_smap_casters: one workgroup per render, a lane per tile, SMC_THREADS tiles a turn.  The view, the light and the receiver's record sit at addresses that are
+//     uniform over the workgroup.  Both lists are compacted in batch order by one ballot per list and wave and one prefix over the waves' counts (tp_block_rank2:
+//     the two counts travel as the halves of one word, so the pair costs the two barriers of one).
+// Why 1024 lanes a workgroup: a call has R workgroups, a few dozen against 256 compute units, so its time is one workgroup's walk through the batch, not the
+// device's throughput; a turn costs two barriers and the latency of four 16-byte loads whatever the width, and 1024 lanes take a quarter of the turns of 256.  The
+// test needs few registers (see tools/check_kernel_resources.py), so sixteen waves of it fit a compute unit.
+constexpr uint32_t SMC_THREADS = 1024;
+__global__ __launch_bounds__(TV_THREADS) void k_smap_plan(smap_consts_t c, terrain_view_in_t in, smap_plan_io_t io, int32_t const *__restrict__ tile_xy, uint32_t n,
+	smap_rank_key_t *__restrict__ keys)
+{
+	uint32_t const t = blockIdx.x*TV_THREADS + threadIdx.x;
+	if (t >= n) return;
+	smap_plan_tile_t const o = smap_plan_tile(c, in, tile_xy, io.smap_state[t], t);
+	smap_plan_store(io, o, t);
+	smap_rank_key_t k; k.key = o.key; k.y = tile_xy[2u*t + 1u]; k.x = tile_xy[2u*t]; k.present = o.present;
+	keys[t] = k;
+}
+__global__ __launch_bounds__(TV_THREADS) void k_smap_plan_lists(uint32_t n, uint32_t const *__restrict__ plan, smap_rank_key_t const *__restrict__ keys, uint32_t *__restrict__ receivers,
+	uint32_t *__restrict__ counts, int recomp)
+{
+	__shared__ uint32_t s_wave[TV_THREADS/64];
+	uint32_t const tid = threadIdx.x;
+	uint32_t nr = 0, np = 0;
+	for (uint32_t base = 0; base < n; base += TV_THREADS) {
+		uint32_t const t = base + tid;
+		tp_emit(t < n && (plan[t] & SMP_RECEIVER) != 0u, [&] {return t;}, receivers, n, nr, s_wave);
+		uint32_t total;
+		tp_block_rank(t < n && keys[t].present != 0u, s_wave, total);
+		np += total;
+	}
+	if (tid == 0) {counts[0] = nr; counts[1] = recomp ? np : 0u;}
+}
+__global__ __launch_bounds__(TV_THREADS) void k_smap_plan_rank(smap_rank_key_t const *__restrict__ keys, uint32_t n, uint32_t *__restrict__ recomp_order) {
+	__shared__ smap_rank_key_t s_keys[TV_THREADS];
+	uint32_t const tid = threadIdx.x, t = blockIdx.x*TV_THREADS + tid;
+	smap_rank_key_t me; me.key = 0.0f; me.y = 0; me.x = 0; me.present = 0u;
+	if (t < n) {me = keys[t];}
+	uint32_t place = 0;
+	for (uint32_t base = 0; base < n; base += TV_THREADS) { // (every thread of the workgroup takes every turn: the barriers)
+		uint32_t const u = base + tid, m = (n - base < TV_THREADS) ? n - base : TV_THREADS;
+		__syncthreads(); // the turn before has read its records
+		if (u < n) {s_keys[tid] = keys[u];}
+		__syncthreads();
+		place += smap_recomp_count(s_keys, m, base, me, t);
+	}
+	if (t < n && me.present) {recomp_order[place] = t;}
+}
+__global__ __launch_bounds__(TV_THREADS) void k_smap_geom(smap_consts_t c, terrain_view_in_t in, uint32_t const *__restrict__ decid_counts, int decid_trees_only,
+	int32_t const *__restrict__ tile_xy, uint32_t n, smap_geom_t *__restrict__ geom)
+{
+	uint32_t const t = blockIdx.x*TV_THREADS + threadIdx.x;
+	if (t >= n) return;
+	geom[t] = smap_geom(c, in, decid_counts, decid_trees_only, tile_xy, t);
+}
+// tp_block_rank for two flags at once in a workgroup of THREADS threads: the ranks of the calling thread among the threads with f0 and among those with f1, in thread
+// order, and their numbers (uniform); two barriers
+template<uint32_t THREADS> __device__ __forceinline__ void tp_block_rank2(bool f0, bool f1, uint32_t *s_wave, uint32_t &r0, uint32_t &r1, uint32_t &n0, uint32_t &n1) {
+	static_assert(THREADS % 64 == 0 && THREADS <= 1024, "whole waves; a count fits half a word");
+	uint32_t const lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	unsigned long long const m0 = __ballot(f0), m1 = __ballot(f1);
+	if (lane == 0) {s_wave[w] = smap_rank2_word(m0, m1);}
+	__syncthreads();
+	smap_rank2_t const q = smap_rank2(s_wave, THREADS/64, w, lane, m0, m1); // (terra_smapview.hpp: the arithmetic the host check runs too)
+	__syncthreads();
+	r0 = q.r0; r1 = q.r1; n0 = q.n0; n1 = q.n1;
+}
+__global__ __launch_bounds__(SMC_THREADS) void k_smap_casters(smap_geom_t const *__restrict__ geom, uint32_t n, uint32_t const *__restrict__ recv, view_pod_t const *__restrict__ views,
+	float const *__restrict__ bsm, float const *__restrict__ lpos, int decid_trees_only, int inc_adj_smap, uint32_t *__restrict__ to_draw, uint32_t *__restrict__ terrain,
+	uint32_t *__restrict__ counts, uint8_t *__restrict__ not_drawn, uint8_t *__restrict__ status)
+{
+	__shared__ uint32_t s_wave[SMC_THREADS/64];
+	uint32_t const r = blockIdx.x, tid = threadIdx.x;
+	size_t const row = (size_t)r*n;
+	view_pod_t const &v = views[r]; // (the driver's copy: near_ is 0 already, :3032)
+	float const mult = bsm[r];
+	smap_recv_t const rc = smap_recv(geom, n, recv[r], lpos + 3u*(size_t)r);
+	uint32_t nd = 0, nt = 0;
+	for (uint32_t base = 0; base < n; base += SMC_THREADS) {
+		uint32_t const t = base + tid;
+		uint32_t w = 0u;
+		if (t < n) { // (the lane's own copy of its record, four 16-byte loads: with the test reading the record through a reference the kernel kept an 8-byte frame that nothing used)
+			smap_geom_t const g = geom[t];
+			w = smap_cast_tile(v, mult, g, rc, decid_trees_only, inc_adj_smap);
+			not_drawn[row + t] = (w & 1u) ? 0 : 1;
+		}
+		uint32_t r0, r1, n0, n1;
+		tp_block_rank2<SMC_THREADS>((w & 1u) != 0u, (w & 2u) != 0u, s_wave, r0, r1, n0, n1);
+		if (w & 1u) {to_draw[row + nd + r0] = t;} // (nd + r0 < n: the ranks count tiles of the batch)
+		if (w & 2u) {terrain[row + nt + r1] = t;}
+		nd += n0; nt += n1;
+	}
+	if (tid == 0) {counts[2u*r] = nd; counts[2u*r + 1u] = nt; status[r] = rc.ok ? 0 : (uint8_t)SMC_NO_TILE;}
+}
+
 // ------------------------------------------------------------------ the clouds of a tile batch (tile_cloud_manager_t, src/tiled_mesh.cpp:1710-1827; terra_clouds.hpp).
 // The wind step is order dependent only where a cloud crosses from one tile to another, and a cloud's way through a call depends on nothing but the cloud:
 //  - k_cloud_mark: a lane per tile follows each of its records through the call (cloud_path) and marks every tile that sends or receives (a byte store of 1).

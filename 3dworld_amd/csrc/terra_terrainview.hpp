@@ -118,9 +118,13 @@ TERRA_HD float terrain_view_dist_in_tiles(terrain_view_consts_t const &c, terrai
 	float const d = sqrtf((cam[0] - g.cx)*(cam[0] - g.cx) + (cam[1] - g.cy)*(cam[1] - g.cy) + (cam[2] - g.cz)*(cam[2] - g.cz));
 	return (max_std(0.0f, d - radius)/c.scaled_tile_radius)*(float)6;
 }
+// get_bsphere_radius_inc_water() (src/tiled_mesh.cpp:366-368)
+TERRA_HD float terrain_view_radius_inc_water(terrain_view_consts_t const &c, float mzmin, float mzmax, float radius) {
+	return (c.water_enabled && mzmax < c.water_plane_z) ? max_std(radius, c.water_plane_z - 0.5f*(mzmin + mzmax)) : radius;
+}
 // tile_t::is_visible(): sphere_and_cube_visible_test(get_center(), get_bsphere_radius_inc_water(), get_bcube())
 TERRA_HD bool terrain_view_visible(terrain_view_consts_t const &c, terrain_view_geom_t const &g, float mzmin, float mzmax, float radius) {
-	float const r = (c.water_enabled && mzmax < c.water_plane_z) ? max_std(radius, c.water_plane_z - 0.5f*(mzmin + mzmax)) : radius;
+	float const r = terrain_view_radius_inc_water(c, mzmin, mzmax, radius);
 	return view_sphere_and_cube_visible(c.v, c.behind_sphere_mult, g.cx, g.cy, g.cz, r, g.bc);
 }
 // rel_dist_to_camera_xy_lt(OCCLUDER_DIST): the distance half of use_as_occluder()

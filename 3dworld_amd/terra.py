@@ -184,6 +184,34 @@ def make_water_view_args(behind_sphere_mult=1.0, water_enabled=1):
     return WaterViewArgs(behind_sphere_mult, int(water_enabled))
 
 
+class SmapPlanArgs(C.Structure):  # terra_smap_plan_args
+    _fields_ = [("behind_sphere_mult", C.c_float), ("water_enabled", C.c_int32), ("smap_thresh_scale", C.c_float), ("shadow_map_sz", C.c_uint32), ("have_buildings", C.c_int32),
+                ("draw_model", C.c_int32), ("b_ext", C.c_float * 3), ("road_len", C.c_float * 2), ("models_z2", C.c_float), ("models_valid", C.c_int32),
+                ("sun_pos", C.c_float * 3), ("want_recomp", C.c_int32)]
+
+
+def make_smap_plan_args(behind_sphere_mult=1.0, water_enabled=1, smap_thresh_scale=1.0, shadow_map_sz=4096, have_buildings=0, draw_model=0, b_ext=(0.0, 0.0, 0.0),
+                        road_len=(0.0, 0.0), models_z2=0.0, models_valid=0, sun_pos=(0.0, 0.0, 1.0), want_recomp=0):
+    """terra_smap_plan_args: shadow_map_sz 0 means shadow_map_enabled() is false; b_ext / road_len are get_buildings_max_extent() / get_road_max_len()"""
+    return SmapPlanArgs(behind_sphere_mult, int(water_enabled), smap_thresh_scale, int(shadow_map_sz), int(have_buildings), int(draw_model), (C.c_float * 3)(*b_ext),
+                        (C.c_float * 2)(*road_len), models_z2, int(models_valid), (C.c_float * 3)(*sun_pos), int(want_recomp))
+
+
+class SmapCastArgs(C.Structure):  # terra_smap_cast_args
+    _fields_ = [("water_enabled", C.c_int32), ("decid_trees_only", C.c_int32), ("inc_adj_smap", C.c_int32), ("b_ext", C.c_float * 3), ("road_len", C.c_float * 2)]
+
+
+def make_smap_cast_args(water_enabled=1, decid_trees_only=0, inc_adj_smap=0, b_ext=(0.0, 0.0, 0.0), road_len=(0.0, 0.0)):
+    return SmapCastArgs(int(water_enabled), int(decid_trees_only), int(inc_adj_smap), (C.c_float * 3)(*b_ext), (C.c_float * 2)(*road_len))
+
+
+SMAP_NONE = 0xFF  # the smap_state byte of a tile without shadow maps
+(SMAP_IN_DRAW_DIST, SMAP_VISIBLE, SMAP_BOUNDS_VISIBLE, SMAP_UPDATE, SMAP_CLEARED_FAR, SMAP_CLEARED_WIREFRAME, SMAP_CLEARED_LOD_REDUCE, SMAP_CLEARED_LOD_RAISE, SMAP_ALLOCATED,
+ SMAP_RECEIVER, SMAP_USABLE) = (1 << k for k in range(11))  # the plan word of tiles_smap_plan; bits 16-19 lod_level, 20-23 lod_level_reduce
+SMAP_TILE_FULLY_IN_CITY = 8  # a bit of the per-tile flags byte
+SMAP_CAST_NO_TILE = 1        # the status byte of a render without a receiver
+
+
 class CloudParams(C.Structure):  # terra_cloud_params
     _fields_ = [("clouds_per_tile", C.c_float), ("cloud_height_offset", C.c_float), ("rgen_seed", C.c_int32)]
 
@@ -533,6 +561,11 @@ _PROTOS = {
     "terra_tiles_reflection_view": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 17),
     "terra_tiles_water_view_dev": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 10),
     "terra_tiles_water_view": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 10),
+    "terra_tiles_smap_plan_dev": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 14),
+    "terra_tiles_smap_plan": (_i32, [_vp, _vp, _u32, _i32, _i32] + [_vp] * 14),
+    "terra_tiles_smap_casters_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _u32] + [_vp] * 15),
+    "terra_tiles_smap_casters": (_i32, [_vp, _vp, _u32, _i32, _i32, _u32] + [_vp] * 15),
+    "terra_make_light_view": (_i32, [_vp, _vp, C.c_float, _vp, _vp]),
     "terra_set_cloud_params": (_i32, [_vp, _vp]),
     "terra_get_cloud_params": (_i32, [_vp, _vp]),
     "terra_tiles_update_clouds_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
@@ -1230,6 +1263,57 @@ class Terra:
                                                  ptr(su), wl.ctypes.data, ptr(cm), counts.ctypes.data))
         return wl[:counts[0]], cm, counts
 
+    def make_light_view(self, lpos, bounds, near_clip=0.01):
+        """get_pt_cube_frustum_pdu in its infinite-terrain form (terra_make_light_view; no context is involved): bounds x1 x2 y1 y2 z1 z2 -> (View, behind_sphere_mult)"""
+        v, m = View(), C.c_float()
+        lp, bd = (C.c_float * 3)(*[float(x) for x in lpos]), (C.c_float * 6)(*[float(x) for x in bounds])
+        self._ck(self.lib.terra_make_light_view(lp, bd, near_clip, C.byref(v), C.byref(m)))
+        return v, m.value
+
+    def tiles_smap_plan(self, tile_xy, stats, view, args, smap_state, trmax=None, tile_zmax=None, flags=None, terrain_flags=None, want_recomp_order=False, dxoff=0, dyoff=0, fill=None):
+        """one frame's shadow-map decisions for every tile.  smap_state [n] bytes (SMAP_NONE or the LOD), terrain_flags [n] bytes or None.  fill: a dict of the outputs'
+        initial arrays (the defaults are zeros) -- what the call does not write stays.
+        -> dict(plan uint32 [n], dist_scale float32 [n], shadow_bcube float32 [n, 6], receivers uint32 [n], counts uint32 [2], smap_state, terrain_flags, recomp_order or None)"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        opt = lambda a, dt: None if a is None else np.array(a, dt).reshape(n)  # noqa: E731  (copies: the state and the flags are written)
+        tr, tz, fl, tf, ss = opt(trmax, np.float32), opt(tile_zmax, np.float32), opt(flags, np.uint8), opt(terrain_flags, np.uint8), opt(smap_state, np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        fill = fill or {}
+        o = dict(plan=np.array(fill.get("plan", np.zeros(n, np.uint32)), np.uint32), dist_scale=np.array(fill.get("dist_scale", np.zeros(n, np.float32)), np.float32),
+                 shadow_bcube=np.array(fill.get("shadow_bcube", np.zeros((n, 6), np.float32)), np.float32), receivers=np.array(fill.get("receivers", np.zeros(n, np.uint32)), np.uint32),
+                 counts=np.array(fill.get("counts", np.zeros(2, np.uint32)), np.uint32), smap_state=ss, terrain_flags=tf,
+                 recomp_order=np.array(fill.get("recomp_order", np.zeros(n, np.uint32)), np.uint32) if want_recomp_order else None)
+        self._ck(self.lib.terra_tiles_smap_plan(self.ctx, txy.ctypes.data, n, dxoff, dyoff, C.byref(view), C.byref(args), C.addressof(stats) if n else None, ptr(tr), ptr(tz), ptr(fl),
+                                                ptr(ss), o["plan"].ctypes.data, o["dist_scale"].ctypes.data, o["shadow_bcube"].ctypes.data, o["receivers"].ctypes.data,
+                                                o["counts"].ctypes.data, ptr(tf), ptr(o["recomp_order"])))
+        return o
+
+    @staticmethod
+    def _smap_render_arrays(views, bsm, lpos):
+        R = len(views)
+        va = (View * max(R, 1))(*views)
+        return R, va, np.ascontiguousarray(bsm, np.float32).reshape(R), np.ascontiguousarray(lpos, np.float32).reshape(R, 3)
+
+    def tiles_smap_casters(self, tile_xy, stats, recv, views, bsm, lpos, args, trmax=None, tile_zmax=None, flags=None, decid_counts=None, dxoff=0, dyoff=0, fill=None):
+        """what is drawn into each receiver's shadow map: recv [R] batch indices, views a list of R View, bsm [R], lpos [R, 3].
+        -> dict(to_draw uint32 [R, n], terrain uint32 [R, n], counts uint32 [R, 2], not_drawn uint8 [R, n], status uint8 [R])"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        n = len(txy)
+        R, va, bm, lp = self._smap_render_arrays(views, bsm, lpos)
+        rv = np.ascontiguousarray(recv, np.uint32).reshape(R)
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt).reshape(n)  # noqa: E731
+        tr, tz, fl, dc = opt(trmax, np.float32), opt(tile_zmax, np.float32), opt(flags, np.uint8), opt(decid_counts, np.uint32)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        fill = fill or {}
+        o = dict(to_draw=np.array(fill.get("to_draw", np.zeros((R, n), np.uint32)), np.uint32), terrain=np.array(fill.get("terrain", np.zeros((R, n), np.uint32)), np.uint32),
+                 counts=np.array(fill.get("counts", np.zeros((R, 2), np.uint32)), np.uint32), not_drawn=np.array(fill.get("not_drawn", np.zeros((R, n), np.uint8)), np.uint8),
+                 status=np.array(fill.get("status", np.zeros(R, np.uint8)), np.uint8))
+        self._ck(self.lib.terra_tiles_smap_casters(self.ctx, txy.ctypes.data, n, dxoff, dyoff, R, rv.ctypes.data, C.addressof(va), bm.ctypes.data, lp.ctypes.data, C.byref(args),
+                                                   C.addressof(stats) if n else None, ptr(tr), ptr(tz), ptr(fl), ptr(dc), o["to_draw"].ctypes.data, o["terrain"].ctypes.data,
+                                                   o["counts"].ctypes.data, o["not_drawn"].ctypes.data, o["status"].ctypes.data))
+        return o
+
     def set_cloud_params(self, cp):
         self._ck(self.lib.terra_set_cloud_params(self.ctx, C.byref(cp)))
 
@@ -1668,6 +1752,24 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_water_view_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, trmax_ptr, tile_zmax_ptr, flags_ptr,
                                                      status_ptr, water_list_ptr, cap_mask_ptr, counts_ptr))
+
+    def tiles_smap_plan_dev(self, tile_xy, view, args, stats_ptr, smap_state_ptr, plan_ptr, dist_scale_ptr, shadow_bcube_ptr, receivers_ptr, counts_ptr, trmax_ptr=None,
+                            tile_zmax_ptr=None, flags_ptr=None, terrain_flags_ptr=None, recomp_order_ptr=None, dxoff=0, dyoff=0):
+        """one frame's shadow-map decisions of a device-resident batch: smap_state_ptr [n] bytes (read and written), plan_ptr / receivers_ptr [n] uint32, dist_scale_ptr [n]
+        floats, shadow_bcube_ptr [n][6] floats, counts_ptr [2] uint32; terrain_flags_ptr [n] bytes and recomp_order_ptr [n] uint32 or None.  view and args are host structs.
+        Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_smap_plan_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, C.byref(view), C.byref(args), stats_ptr, trmax_ptr, tile_zmax_ptr, flags_ptr,
+                                                    smap_state_ptr, plan_ptr, dist_scale_ptr, shadow_bcube_ptr, receivers_ptr, counts_ptr, terrain_flags_ptr, recomp_order_ptr))
+
+    def tiles_smap_casters_dev(self, tile_xy, recv_ptr, views, bsm, lpos, args, stats_ptr, to_draw_ptr, terrain_ptr, counts_ptr, not_drawn_ptr, status_ptr, trmax_ptr=None,
+                               tile_zmax_ptr=None, flags_ptr=None, decid_counts_ptr=None, dxoff=0, dyoff=0):
+        """the casters of R renders on a device-resident batch: recv_ptr [R] uint32 on the device; views (a list of R View), bsm [R] and lpos [R, 3] on the host;
+        to_draw_ptr / terrain_ptr [R][n] uint32, counts_ptr [R][2] uint32, not_drawn_ptr [R][n] bytes, status_ptr [R] bytes.  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        R, va, bm, lp = self._smap_render_arrays(views, bsm, lpos)
+        self._ck(self.lib.terra_tiles_smap_casters_dev(self.ctx, txy.ctypes.data, len(txy), dxoff, dyoff, R, recv_ptr, C.addressof(va), bm.ctypes.data, lp.ctypes.data, C.byref(args),
+                                                       stats_ptr, trmax_ptr, tile_zmax_ptr, flags_ptr, decid_counts_ptr, to_draw_ptr, terrain_ptr, counts_ptr, not_drawn_ptr, status_ptr))
 
     def tiles_update_clouds_dev(self, tile_xy, step, state_ptr, clouds_ptr, capacity, total_ptr=None):
         """update_tile_clouds of a device-resident batch: state_ptr [n] terra_cloud_tile, clouds_ptr [n][capacity] terra_cloud, total_ptr one uint32 or None.  Only enqueues."""

@@ -957,6 +957,87 @@ int  terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
                             const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, const uint8_t *h_status,
                             uint32_t *h_water_list, uint8_t *h_cap_mask, uint32_t *h_counts);
 
+/* ---- the shadow-map plan of a tile batch (every supported tile size S; S enters only through the boxes and the radius): which tiles hold a shadow map, at which
+ * LOD, and which tiles are drawn into a receiver's shadow map.  All line numbers are src/tiled_mesh.cpp's.
+ *
+ * terra_tiles_smap_plan[_dev]: one call is one frame's decisions for the camera `view`: tile_t::update_range's shadow-map deletion (:1416 with :1409), the loop of
+ * tile_draw_t::pre_draw (:2781-2799, its shadow part: the draw-distance gate of :2784, is_visible, is_smap_bounds_visible, to_update_shadows against cleanup_only),
+ * tile_t::setup_shadow_maps (:981-1016) with calc_max_smap_lod (:975-980) and tile_t::get_shadow_bcube (:959-965), the large-map branch of :994-997, and the gate of
+ * tile_t::try_bind_shadow_map (:1958-1959).
+ * Inputs: tile_xy, dxoff / dyoff, view, stats, trmax, tile_zmax and flags (bit 0, absent) as for terra_tiles_terrain_view; terra_smap_plan_args, read at the call.
+ * State, read and written: smap_state [n] bytes, TERRA_SMAP_NONE for smap_data.empty(), else smap_lod_level (0..3).  It is the engine's to keep between frames; a
+ * tile's stale smap_lod_level while it holds no shadow maps is not observable in the reference (its uses at :998 and :1000 only guard a clear_shadow_map that is
+ * then a no-op, and :1006 overwrites it), so the byte is the whole state.  An absent tile's byte is not touched.
+ * Outputs: plan [n] words (TERRA_SMAP_* bits; bits 16-19 lod_level and bits 20-23 lod_level_reduce where :988 was entered; 0 for an absent tile).  A CLEARED bit is
+ * set only when the tile held shadow maps at that point, so the engine releases exactly what the reference releases.  RECEIVER: :1015 was reached and the tile holds
+ * shadow maps -- the engine calls create_if_needed for it; USABLE: try_bind_shadow_map's gate with the new state.  dist_scale [n]: smap_dist_scale (:986), 0 where it
+ * was not formed.  shadow_bcube [n][6] (x1 x2 y1 y2 z1 z2): what :1010-1014 hand to create_if_needed, written for every tile inside the draw distance and for no
+ * other.  receivers [n]: its first counts[0] entries are the batch indices with RECEIVER in batch order; entries past the count are not written.  terrain_flags [n]
+ * bytes (optional): TERRA_TVIEW_FLAG_SHADOW_MAPS is or'ed into the byte of every present tile whose new state is not NONE -- the flags of the next
+ * terra_tiles_terrain_view, taken from the device (it may be the flags array itself).  recomp_order [n] (optional, written when want_recomp): every present tile in
+ * the order in which pop_back at :2459 yields the queue of :2445-2448 -- ascending (-p2p_dist(sun_pos, get_center()), tile_xy_pair) consumed from the back;
+ * tile_xy_pair::operator< compares y, then x, so the order is total; counts[1] is their number (0 when nothing was asked).  The 12-per-frame budget and
+ * clear_shadows stay with the engine.
+ *
+ * terra_tiles_smap_casters[_dev]: for R independent (receiver tile, light) renders the head of tile_draw_t::draw_shadow_pass (:3025-3043) and the filter of
+ * draw_tiles_shadow_pass (:3004-3018) with the inside_city == 2 return of tile_t::draw_shadow_pass (:2083).
+ * Inputs: the batch as above (flags bit 3, TERRA_SMAP_TILE_FULLY_IN_CITY); recv [R] batch indices (on the device in the device form: the plan's receivers can feed
+ * it; an index that is out of range or names an absent tile gets empty lists, a row of ones in not_drawn and status TERRA_SMAP_CAST_NO_TILE); views [R], the light
+ * frustum each render uses (the call applies near_ = 0, :3032, to its copy), bsm [R] their behind_sphere_mult and lpos [R][3] -- host arrays in both forms, read at
+ * the call like `view`; decid_counts [n] (needed only with decid_trees_only, :3038); terra_smap_cast_args.
+ * Outputs per render r: to_draw [R][n] with counts [R][2]: row r's first counts[r][0] entries are the tiles of :3042 in batch order; terrain [R][n]: the
+ * counts[r][1] of them that reach draw_mesh_vbo (:3013 or :3014 holds and the tile is not fully in a city); entries past the counts are not written.  not_drawn
+ * [R][n] bytes: 1 for a tile that is not in to_draw.  Row r is the `skip` argument (d_skip / h_skip) of the shadow-pass calls of terra_tiles_tree_view,
+ * terra_tiles_scenery_view and terra_tiles_decid_view for that render, the same contract as terra_tiles_terrain_view's not_drawn.  status [R] bytes.  Under
+ * decid_trees_only the terrain lists are empty and to_draw follows :3038.
+ *
+ * terra_make_light_view (host only): get_pt_cube_frustum_pdu (src/shadow_map.cpp:423-457) in its infinite-terrain form (pos *= 10.0) into pos_dir_up's constructor,
+ * with the C library's atan2f: the view of a render from lpos and a receiver's shadow_bcube, and its behind_sphere_mult.  near_clip is the engine's NEAR_CLIP.
+ * TERRA_ERR_ARG where the reference asserts (bounds not strictly normalized, the light in the box's centre) or the result is not finite.
+ *
+ * TERRA_ERR_ARG, with nothing written: a non-finite member of a view, the args, lpos, bsm or sun_pos; smap_thresh_scale not > 0; an unsupported S; a NULL required
+ * pointer; a pointer other than the byte arrays that is not 4-byte aligned (device forms); R*n beyond 32 bits.  TERRA_ERR_STATE before terra_init_scene.  n == 0 or
+ * R == 0 does nothing once the checks have passed.  The device forms only enqueue and read nothing back; tile_xy is a host array in both forms.  The host forms
+ * upload the caller's arrays and copy them back, so entries a call does not write keep the caller's bytes. */
+#define TERRA_SMAP_NONE 0xFF
+enum {TERRA_SMAP_IN_DRAW_DIST = 0x1, TERRA_SMAP_VISIBLE = 0x2, TERRA_SMAP_BOUNDS_VISIBLE = 0x4, TERRA_SMAP_UPDATE = 0x8, TERRA_SMAP_CLEARED_FAR = 0x10,
+      TERRA_SMAP_CLEARED_WIREFRAME = 0x20, TERRA_SMAP_CLEARED_LOD_REDUCE = 0x40, TERRA_SMAP_CLEARED_LOD_RAISE = 0x80, TERRA_SMAP_ALLOCATED = 0x100,
+      TERRA_SMAP_RECEIVER = 0x200, TERRA_SMAP_USABLE = 0x400, TERRA_SMAP_LOD_SHIFT = 16, TERRA_SMAP_LOD_REDUCE_SHIFT = 20};
+enum {TERRA_SMAP_TILE_FULLY_IN_CITY = 8};  /* a bit of the per-tile flags byte, beside TERRA_TVIEW_FLAG_* */
+enum {TERRA_SMAP_CAST_NO_TILE = 1};        /* the status byte of a render without a receiver */
+typedef struct terra_smap_plan_args {      /* 68 bytes */
+	float behind_sphere_mult;              /* pos_dir_up::behind_sphere_mult of `view` */
+	int32_t water_enabled;                 /* is_water_enabled() */
+	float smap_thresh_scale;               /* > 0 */
+	uint32_t shadow_map_sz;                /* 0: shadow_map_enabled() is false */
+	int32_t have_buildings;                /* have_buildings(): 1024 instead of 512 in calc_max_smap_lod */
+	int32_t draw_model;                    /* non-zero: the wireframe branch of :984 */
+	float b_ext[3];                        /* get_buildings_max_extent() */
+	float road_len[2];                     /* get_road_max_len() */
+	float models_z2; int32_t models_valid; /* calc_and_return_all_models_bcube().z2() and !is_all_zeros() (:1013-1014) */
+	float sun_pos[3]; int32_t want_recomp; /* the queue of :2445-2448 */
+} terra_smap_plan_args;
+typedef struct terra_smap_cast_args {      /* 32 bytes */
+	int32_t water_enabled, decid_trees_only;
+	int32_t inc_adj_smap;                  /* :3006, the engine's: get_buildings_max_extent() != zero_vector || get_road_max_len().x > 0.0 */
+	float b_ext[3], road_len[2];           /* for the receiver's get_shadow_bcube() */
+} terra_smap_cast_args;
+int  terra_tiles_smap_plan_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_smap_plan_args *args,
+                               const terra_tile_stats *d_stats, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags, uint8_t *d_smap_state, uint32_t *d_plan,
+                               float *d_dist_scale, float *d_shadow_bcube, uint32_t *d_receivers, uint32_t *d_counts, uint8_t *d_terrain_flags, uint32_t *d_recomp_order);
+int  terra_tiles_smap_plan(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_smap_plan_args *args,
+                           const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, uint8_t *h_smap_state, uint32_t *h_plan,
+                           float *h_dist_scale, float *h_shadow_bcube, uint32_t *h_receivers, uint32_t *h_counts, uint8_t *h_terrain_flags, uint32_t *h_recomp_order);
+int  terra_tiles_smap_casters_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, uint32_t R, const uint32_t *d_recv, const terra_view *views,
+                                  const float *bsm, const float *lpos, const terra_smap_cast_args *args, const terra_tile_stats *d_stats, const float *d_trmax,
+                                  const float *d_tile_zmax, const uint8_t *d_flags, const uint32_t *d_decid_counts, uint32_t *d_to_draw, uint32_t *d_terrain, uint32_t *d_counts,
+                                  uint8_t *d_not_drawn, uint8_t *d_status);
+int  terra_tiles_smap_casters(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, uint32_t R, const uint32_t *h_recv, const terra_view *views,
+                              const float *bsm, const float *lpos, const terra_smap_cast_args *args, const terra_tile_stats *h_stats, const float *h_trmax,
+                              const float *h_tile_zmax, const uint8_t *h_flags, const uint32_t *h_decid_counts, uint32_t *h_to_draw, uint32_t *h_terrain, uint32_t *h_counts,
+                              uint8_t *h_not_drawn, uint8_t *h_status);
+int  terra_make_light_view(const float lpos[3], const float bounds[6], float near_clip, terra_view *out, float *behind_sphere_mult);
+
 /* ---- the clouds of a tile batch (every supported tile size S): tile_cloud_manager_t (src/tiled_mesh.cpp:1689-1827) as tile_draw_t::draw_tile_clouds (:3484-3508)
  * drives it.  No call reads a zval: a tile is its tile_xy, S (x1 = x*S, x2 = x1 + S) and, for the view, its stats.
  *

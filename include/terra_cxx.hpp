@@ -409,6 +409,31 @@ inline void tile_water_lists(tile_batch_dev_t const &b, terra_view const &camera
 	check(terra_tiles_water_view_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &a, b.d_stats, st.d_trmax, st.d_tile_zmax, st.d_flags, d_status, d_water_list,
 		d_cap_mask, d_counts), "tile_t::draw_water / draw_water_cap");
 }
+// tile_draw_t::pre_draw's shadow part with tile_t::update_range's deletion and tile_t::setup_shadow_maps (src/tiled_mesh.cpp:1416, :2781-2799, :981-1016): one frame's
+// decisions for camera_pdu.  d_smap_state [n] bytes (TERRA_SMAP_NONE or smap_lod_level) is the engine's between frames; d_plan [n] TERRA_SMAP_* words, d_dist_scale [n],
+// d_shadow_bcube [n][6], d_receivers' first d_counts[0] entries the tiles to call create_if_needed for; d_terrain_flags (or null) gains TERRA_TVIEW_FLAG_SHADOW_MAPS;
+// d_recomp_order (or null, with args.want_recomp) is shadow_recomp_queue in pop_back order, d_counts[1] entries
+inline void tile_smap_plan(tile_batch_dev_t const &b, terra_view const &camera_pdu, terra_smap_plan_args const &args, tile_draw_state_dev_t const &st, unsigned char *d_smap_state,
+	unsigned *d_plan, float *d_dist_scale, float *d_shadow_bcube, unsigned *d_receivers, unsigned *d_counts, unsigned char *d_terrain_flags = nullptr, unsigned *d_recomp_order = nullptr)
+{
+	check(terra_tiles_smap_plan_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, &camera_pdu, &args, b.d_stats, st.d_trmax, st.d_tile_zmax, st.d_flags, d_smap_state, d_plan,
+		d_dist_scale, d_shadow_bcube, d_receivers, d_counts, d_terrain_flags, d_recomp_order), "tile_t::setup_shadow_maps");
+}
+// get_pt_cube_frustum_pdu (src/shadow_map.cpp:423-457, the infinite-terrain form) for a receiver's shadow_bcube: the view of one render and its behind_sphere_mult
+inline terra_view light_view_of(float const lpos[3], float const shadow_bcube[6], float near_clip, float &behind_sphere_mult) {
+	terra_view v;
+	check(terra_make_light_view(lpos, shadow_bcube, near_clip, &v, &behind_sphere_mult), "get_pt_cube_frustum_pdu");
+	return v;
+}
+// the head of tile_draw_t::draw_shadow_pass and the filter of draw_tiles_shadow_pass (src/tiled_mesh.cpp:3025-3043, :3004-3018) for R renders: d_recv [R] receivers (on the
+// device), views / bsm / lpos [R] on the host.  Row r of d_to_draw / d_terrain [R][n] with d_counts [R][2]; row r of d_not_drawn [R][n] is the skip array of that render's
+// shadow-pass tile_draw_pine_trees / scenery / deciduous lists
+inline void tile_smap_casters(tile_batch_dev_t const &b, unsigned R, unsigned const *d_recv, terra_view const *views, float const *bsm, float const *lpos, terra_smap_cast_args const &args,
+	tile_draw_state_dev_t const &st, unsigned const *d_decid_counts, unsigned *d_to_draw, unsigned *d_terrain, unsigned *d_counts, unsigned char *d_not_drawn, unsigned char *d_status)
+{
+	check(terra_tiles_smap_casters_dev(default_ctx(), b.tile_xy, b.n, b.dxoff, b.dyoff, R, d_recv, views, bsm, lpos, &args, b.d_stats, st.d_trmax, st.d_tile_zmax, st.d_flags,
+		d_decid_counts, d_to_draw, d_terrain, d_counts, d_not_drawn, d_status), "tile_draw_t::draw_shadow_pass");
+}
 // tile_draw_t::draw_tile_clouds (src/tiled_mesh.cpp:3484-3508), first loop: tile_t::update_tile_clouds for every tile in batch order (b.tile_xy, b.n alone are read).
 // d_state [n] terra_cloud_tile -- zeroed for a tile that enters the batch -- and d_clouds [n][capacity] terra_cloud travel with their tile between batches.
 // clouds_per_tile, cloud_height_offset and rgen_seed: set_cloud_params.  d_total (or null): the `num` of :3489
