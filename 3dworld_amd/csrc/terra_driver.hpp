@@ -61,10 +61,10 @@ struct grid_job_t { // one build_arrays() + eval loop
 // the tile rows of a job's window as rows [first, end) of its grid
 TERRA_HD uint32_t job_window_first(grid_job_t const &job) {return job.tyn ? job.ty0*128u : 0u;}
 TERRA_HD uint32_t job_window_end(grid_job_t const &job) {uint64_t const e = ((uint64_t)job.ty0 + job.tyn)*128u; return (job.tyn && e < job.ny) ? (uint32_t)e : job.ny;}
-// the noise turn of a heightmap among several in flight (terra_gen_grid_minmax_turn_dev): the host waits for `wait_for` (the turn event of the map before) in front of
-// the map's first launch, and `record` is recorded while the last `rows` rows of the grid are still to be evaluated -- so the next map's thread wakes, and its tables and
-// first grid blocks arrive, while this map's tail drains.  Events are the backend's (event_create).
-constexpr uint32_t SG_TURN_ROWS = 2048; // "sg.turn_rows" default: two chip generations of k_sine_grid blocks on a 16384-wide map (2 x 1024 blocks = 16 tile rows, ~98 us): the shortest tail that outlasts the next map's wake-up + table launch + dispatch (~60 us); measured best of 0 / 512 / 1024 / 1536 / 2048 (profiles/r07_turn_rows_sweep.txt)
+// the noise turn of a heightmap among several in flight (terra_gen_grid_minmax_turn_dev): the map's tables are enqueued at once (they read nothing of the map before), the
+// host then waits for `wait_for` (the turn event of the map before) in front of the map's first GRID launch, and `record` is recorded while the last `rows` rows of the grid
+// are still to be evaluated -- so the next map's thread wakes, and its first grid blocks arrive, while this map's tail drains.  Events are the backend's (event_create).
+constexpr uint32_t SG_TURN_ROWS = 2048; // "sg.turn_rows" default: two chip generations of k_sine_grid blocks on a 16384-wide map (2 x 1024 blocks = 16 tile rows, ~115 us beside erosion).  With the tables in front of the wait the chain behind it is wake-up + dispatch only: the next map's first grid block starts ~73 us after the tail launch does (~127 us with the table launch in the chain), so every tail from 512 rows up covers it: 512 / 1024 / 1536 / 2048 are within each other's spread, none beats 2048 by more than the spread of the 2048 runs, only 0 (no split) is behind (profiles/r10_turn_rows_sweep.txt)
 struct noise_turn_t {void *wait_for = nullptr, *record = nullptr; uint32_t rows = 0;};
 
 // noise_gen_3d constants (src/upsurface.h:10-16)
@@ -807,7 +807,9 @@ template<class BE> struct terra_engine {
 	// full-grid call produces (the tables and cell coordinates use the row's index in the whole grid), so row strips evaluated on different GPUs tile the
 	// heightmap exactly (heightmap_t::proc_gen's loop is row-independent, src/heightmap.cpp:139-143)
 	// d_minmax (optional): DEVICE float[2] that receives {min, max} without the host ever seeing them (an enqueue-only proc_gen step: terra_apply_erosion_devmin_dev reads it)
-	// turn (optional): the map's noise turn (noise_turn_t).  Sine mode on the exact kernel: tables -> grid kernel over all but the last turn->rows rows -> record -> grid kernel
+	// turn (optional): the map's noise turn (noise_turn_t).  Order: argument checks (a call that fails them enqueues nothing and waits for nothing) -> everything that does
+	// not depend on the turn (sine mode: the one table launch with the min / max reset; fBm modes: the fill of the min / max words and the island tables) -> the host waits
+	// for turn->wait_for -> the grid launches.  Sine mode on the exact kernel: grid kernel over all but the last turn->rows rows -> record -> grid kernel
 	// over the last rows; the same cells and the same atomics into s_mm (reset by the table launch, once per map), so the same bits.  No split -- the event is recorded right
 	// behind the grid kernel, in front of the min / max conversion -- when rows is 0 or covers the grid, in the fBm modes, and for the fused kernels (persistent blocks)
 	void gen_grid_dev(float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, uint32_t flags, int min_start_sin, float *d_out, float *h_minmax = nullptr, uint32_t row0 = 0, uint32_t nrows = 0xFFFFFFFFu, float *d_minmax = nullptr, noise_turn_t const *turn = nullptr) {
@@ -832,7 +834,8 @@ template<class BE> struct terra_engine {
 		float *smx = scratch<float>(s_smx, job.nxp), *smy = scratch<float>(s_smy, job.nyp);
 		uint32_t *d_mm = nullptr;
 		bool const sine = (job.mode == MGEN_SINE);
-		if (turn && turn->wait_for) {BE::event_synchronize(turn->wait_for);} // the noise of the map before has (all but) left the chip: nothing of this map is enqueued earlier
+		// ---- in FRONT of the turn: everything the grid launches read that depends on this call's arguments, the scene and this context's scratch only -- the min / max reset,
+		// the island tables, the sine tables.  Stream order puts them in front of the first grid launch; the map before (another context's) neither reads nor writes any of it
 		if (h_minmax || d_minmax || sine) {d_mm = scratch<uint32_t>(s_mm, 2); if (!sine) {be.fill32(d_mm, 0xFFFFFFFFu, 2);}} // (sine mode: reset by the table launch)
 		bool fused;
 		bool const sm_on = job.use_sine_mag != 0;
@@ -845,7 +848,8 @@ template<class BE> struct terra_engine {
 				else {unsigned const y = (unsigned)(i - nxp); smy[y] = (y < ny) ? L.COSF(((float)(y + row0)*mdy + my0)*dyi*sm_freq) : 0.0f;}
 			});
 		}
-		if (job.mode == MGEN_SINE) {
+		float *xt = nullptr, *yt = nullptr;
+		if (sine) {
 			// ONE launch builds everything the grid kernel reads: the k-major tables xt[k*nxp + x] = SINF(xmdx*x + x_const), yt[k*nyp + y] = y_scale*SINF(ymdy*y + y_const) (zero
 			// padded) and the island tables smx / smy.  The per-k constants of build_arrays (src/mesh_gen.cpp:607-613) are derived by every thread from the device copy of sinTable
 			// -- the same fp32 expressions in the same order as make_sine_k, no contraction on either side, so the same bits -- instead of by a 90-thread launch of their own in
@@ -854,7 +858,7 @@ template<class BE> struct terra_engine {
 			float const msx = mesh_scale*DX_VAL_INV, msy = mesh_scale*DY_VAL_INV, ms2 = (float)(0.5*(double)mesh_scale), mszi = mesh_scale_z_inv, jmx0 = job.mx0, jmy0 = job.my0, mdx = dx, mdy = dy;
 			// SG_TABLE_ROWS rows each (terra_common.hpp: what the grid kernel's staging may read); only the rows kstart .. SG_TABLE_ROWS - 1 are read by anyone, so only they are
 			// built -- row k at k*nxp / k*nyp whatever the scratch buffers were grown to by earlier grids -- and the rows behind the last term are zeros
-			float *xt = scratch<float>(s_xt, (size_t)SG_TABLE_ROWS*job.nxp), *yt = scratch<float>(s_yt, (size_t)SG_TABLE_ROWS*job.nyp);
+			xt = scratch<float>(s_xt, (size_t)SG_TABLE_ROWS*job.nxp); yt = scratch<float>(s_yt, (size_t)SG_TABLE_ROWS*job.nyp);
 			uint32_t const nxp = job.nxp, nyp = job.nyp;
 			unsigned const kfirst = (unsigned)imin(imax(job.kstart, 0), F_TABLE_SIZE);
 			size_t const nxtab = (size_t)(SG_TABLE_ROWS - kfirst)*nxp, ntab = nxtab + (size_t)(SG_TABLE_ROWS - kfirst)*nyp;
@@ -880,6 +884,10 @@ template<class BE> struct terra_engine {
 					else {unsigned const y = (unsigned)(q - nxp); smy[y] = (y < ny) ? L.COSF(((float)(y + row0)*mdy + jmy0)*dyi*sm_freq) : 0.0f;}
 				}
 			});
+		}
+		// ---- the turn: the noise of the map before has (all but) left the chip.  Only the grid launches, the event record and what follows them stay behind the wait
+		if (turn && turn->wait_for) {BE::event_synchronize(turn->wait_for);}
+		if (sine) {
 			uint32_t *const mm_arg = (h_minmax || d_minmax) ? d_mm : nullptr;
 			uint32_t const nty = (ny + 127u)/128u, tail = (turn && turn->record && !job.fused) ? std::min((turn->rows + 127u)/128u, nty) : 0u;
 			if (tail > 0 && tail < nty) {

@@ -5,7 +5,8 @@ A map's erosion is a chain of dependent droplet steps on a few hundred waves; th
 at once only share the chip and finish together, so the maps take turns in their noise phase -- and the turn is handed over by the GPU itself: the thread of the next map waits
 on the host for the previous map's turn event, not for the thread that launched that kernel to wake up, read min(vals) back and release a semaphore (~65 us of the ~90 us
 between two noise kernels, profiles/r05_timeline_sparse_v2.txt).  The event is recorded in FRONT of the map's last rows (terra_gen_grid_minmax_turn_dev: the grid kernel runs
-as two launches, option "sg.turn_rows"), so the next map's thread wakes, builds its tables and dispatches its grid kernel while those rows drain from the chip.  min(vals)
+as two launches, option "sg.turn_rows"), so the next map's thread -- its tables enqueued before it began to wait -- wakes and dispatches its grid kernel while those rows
+drain from the chip.  min(vals)
 stays in device memory (-> terra_apply_erosion_devmin_dev): a map's erosion is enqueued directly behind its noise, no host round trip in between."""
 import threading
 

@@ -1578,8 +1578,9 @@ class Terra:
         self._ck(self.lib.terra_gen_grid_minmax_async_dev(self.ctx, x0, y0, dx, dy, nx, ny, flags, min_start_sin, ptr, minmax_ptr))
 
     def gen_grid_minmax_turn_dev(self, ptr, x0, y0, dx, dy, nx, ny, minmax_ptr, wait_for=None, turn=None, flags=GEN_GLACIATE, min_start_sin=0):
-        """gen_grid_minmax_async_dev with the noise turn in the call: the host waits for event wait_for, `turn` is recorded while the map's last rows (option sg.turn_rows) are
-        still to be evaluated.  When `turn` fires the map is NOT complete: only this context's stream order (or synchronize) says that it is"""
+        """gen_grid_minmax_async_dev with the noise turn in the call: the map's tables are enqueued at once, the host then waits for event wait_for in front of the grid
+        launches, `turn` is recorded while the map's last rows (option sg.turn_rows) are still to be evaluated.  When `turn` fires the map is NOT complete: only this
+        context's stream order (or synchronize) says that it is"""
         self._ck(self.lib.terra_gen_grid_minmax_turn_dev(self.ctx, x0, y0, dx, dy, nx, ny, flags, min_start_sin, ptr, minmax_ptr, wait_for, turn))
 
     def gen_grid_rows_minmax_async_dev(self, ptr, x0, y0, dx, dy, nx, ny, row0, nrows, minmax_ptr, flags=GEN_GLACIATE, min_start_sin=0):
