@@ -61,6 +61,16 @@ constexpr bool sg_table_rows_suffice() {
 	return true;
 }
 static_assert(sg_table_rows_suffice(), "k_sine_grid's staging would read behind the sine tables");
+// k_sine_grid_rs (the heightmap's row-scalar form, KC = 27) stages X one table row per load -- rows k0 .. k0 + kn - 1 -- and prefetches the row operands one term ahead: the
+// last stage of a chunk asks for table row k0 + kn, the next chunk's first row or row 90
+TERRA_HD constexpr int sg_rs_last_row_read(int kstart, int KC) { // the last table row the row-scalar kernel reads (X staging: k0 + kn - 1; Y prefetch: k0 + kn)
+	int const per = sg_chunk_len(kstart, KC);
+	int last = -1;
+	for (int k0 = kstart; per > 0 && k0 < F_TABLE_SIZE; k0 += per) {int const kn = (k0 + per > F_TABLE_SIZE) ? F_TABLE_SIZE - k0 : per; if (k0 + kn > last) {last = k0 + kn;}}
+	return last;
+}
+constexpr bool sg_rs_table_rows_suffice() {for (int kstart = 0; kstart <= F_TABLE_SIZE; ++kstart) {if (sg_rs_last_row_read(kstart, 27) >= SG_TABLE_ROWS) return false;} return true;}
+static_assert(sg_rs_table_rows_suffice(), "k_sine_grid_rs's row prefetch would read behind the sine tables");
 
 enum {MGEN_SINE = 0, MGEN_SIMPLEX, MGEN_PERLIN, MGEN_SIMPLEX_GPU, MGEN_DWARP_GPU}; // src/3DWorld.h:1399
 

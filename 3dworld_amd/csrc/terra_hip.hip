@@ -305,7 +305,14 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		if (job.plain_only) {
 			auto const go = [&](auto kern) {run(kern, dim3(grid), dim3(terra::SG_THREADS), 0, job, nc, L, xt, yt, smx, smy, out, ntx, nty, mm, tl);};
 			if ((job.nx & 3u) == 0) { // rows of whole 16-byte groups: the packed epilogue, and nothing else in the kernel
-				if (opt->sg_kc == 27) go(terra::k_sine_grid<false, false, 27>); else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20>); else go(terra::k_sine_grid<false, false, 45>);
+				if (opt->sg_kc == 27) {
+					// the row-scalar form (terra_kernels.hpp: k_sine_grid_rs): blocks of 256 columns x 64 rows, the window's 128-row tile rows as two block rows each, "sg.rowgroup"
+					// tile rows walked together as twice as many block rows.  The other chunk lengths ("sg.kc" 20 / 45) stay on k_sine_grid: the same bits either way
+					unsigned const first = terra::job_window_first(job), end = terra::job_window_end(job);
+					unsigned const ntx2 = (job.nxp + terra::SGR_BX - 1)/terra::SGR_BX, nty2 = (end - first + terra::SGR_BY - 1)/terra::SGR_BY, nb2 = ntx2*nty2;
+					run(terra::k_sine_grid_rs<27>, dim3(((nb2 + 7)/8)*8), dim3(terra::SG_THREADS), 0, job, nc, xt, yt, smx, smy, out, ntx2, nty2, 2u*(unsigned)opt->sg_rowgroup, mm);
+				}
+				else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20>); else go(terra::k_sine_grid<false, false, 45>);
 			}
 			else { // any other row length: the same sum with the per-cell epilogue, instantiations of their own
 				if (opt->sg_kc == 27) go(terra::k_sine_grid<false, false, 27, false>); else if (opt->sg_kc == 20) go(terra::k_sine_grid<false, false, 20, false>); else go(terra::k_sine_grid<false, false, 45, false>);

@@ -2,6 +2,7 @@
 //
 //   k_sine_grid     K1+K4: z = sum_k X[x][k]*Y[y][k] as an LDS-tiled rank-90 outer-product contraction + fused
 //                   shape/glaciate/island epilogue (mesh_xy_grid_cache_t::eval_index, src/mesh_gen.cpp:766-790)
+//   k_sine_grid_rs  the same for the heightmap's hot case (plain-only, rows of whole 16-byte groups): row operands from scalar loads, only the columns in LDS
 //   k_noise_grid    K2/K3: per-cell simplex/Perlin fBm and domain warp (get_noise_zval, src/mesh_gen.cpp:734-751)
 //   k_tile_erosion  K5 (tile mode): one wave per tile, the clamp-padded 138x138 grid resident in LDS, droplets in serial order
 //   k_voxel_sines   K8: rank-60 3-D sine field, z-fastest output (noise_gen_3d::get_val, src/upsurface.cpp:60-70)
@@ -35,8 +36,9 @@ template<class F> __global__ __launch_bounds__(64) void k_waves(F f, unsigned fi
 template<class F> __global__ __launch_bounds__(64) void k_waves_nolds(F f) {f((size_t)blockIdx.x);}
 
 // the same for the lean traces of the sparse erosion scheduler (terra_erosion.hpp: lean_back_t): window + dirty bytes + 4.6 KB of footprint bookkeeping = 9.8 KB of LDS, and
-// at most 128 registers (four waves per SIMD requested) -- beside a k_sine_grid block of another heightmap (29.7 KB, 106 registers per wave, allocated as 112) a SIMD then holds three of that
-// kernel's waves and one of these, and a CU four of its blocks and four of these; the general trace wave (22.7 KB, 260 registers) leaves room for two and two
+// at most 128 registers (four waves per SIMD requested) -- beside a k_sine_grid_rs block of another heightmap (29.7 KB, 84 registers per wave, allocated as 88) a SIMD has room for four of
+// that kernel's waves and one of these (beside the 8 x 8 form's 106 registers: three and one), and a CU for four of its blocks and four of these; the general trace wave (22.7 KB, 260
+// registers) leaves room for two and two
 template<class F> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_waves_lean(F f) {
 	__builtin_amdgcn_s_setprio(3); // a droplet is a chain of dependent instructions: beside three waves of another kernel on its SIMD it should never wait for an issue slot (it asks for one every ~5 cycles)
 	__shared__ __attribute__((aligned(16))) float win[EW*EW];
@@ -50,8 +52,10 @@ template<class F> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_p
 // ------------------------------------------------------------------ K1: sine-sum grid
 // z[y][x] = sum_k X[k][x]*Y[k][y] is a rank-(90-kstart) outer-product contraction.  It is fp32-VALU bound: every term costs one
 // v_mul and one v_add (no FMA: the CPU reference rounds the product before adding), i.e. 2*terms VALU ops for 4 B written.
+// (The heightmap's hot case -- plain-only, row length a multiple of 4, KC = 27 -- runs on k_sine_grid_rs below since profiles/r11_sine_rowscalar_ab.txt; this kernel keeps the
+// tile batches, the general epilogue, the other row lengths and the chunk lengths 20 / 45.)
 // Tiling: 128 x 128 cells per 256-thread block, 8 x 8 cells per thread (64 independent accumulator chains), the K range staged
-// through LDS in chunks of <= KC terms (template parameter; the heightmap kernel uses 27: three chunks for 8 octaves, 29.7 KB per block,
+// through LDS in chunks of <= KC terms (template parameter; at 27: three chunks for 8 octaves, 29.7 KB per block,
 // 106 VGPRs -> 4 blocks = 16 waves per CU alone, and two waves per SIMD beside a 264-register droplet wave of another map's erosion;
 // the plain tile variant -- 118 VGPRs -- uses 27 as well, the general one keeps SG_KC = 45: two chunks, 48 KB), operands of the next step prefetched from LDS while this one is multiplied.
 // What is not the sum is kept short (profiles/r09_sine_overhead_ab.txt: 5976 -> 5718 vector instructions per wave, 5120 of them the sum; 4 % fewer cycles, which the
@@ -439,6 +443,175 @@ template<bool TILES, bool GENERAL, int KC = SG_KC, bool PACKED = true> __global_
 	if (mm) {
 		if (fmn <= fmx) {mm_lo = f2ord(fmn); mm_hi = ~f2ord(fmx);}
 		wave_minmax_publish(mm_lo, mm_hi, mm);
+	}
+}
+
+// ---- K1, the heightmap's hot form (plain-only, row length a multiple of 4, KC = 27): the ROW operands are scalars.
+// A wave is 64 lanes along x and a lane owns 4 columns x 16 rows -- the same 32 packed accumulators as above -- so a row's value is the same in all 64 lanes: it belongs in
+// scalar registers, not in LDS plus VGPRs.  A block is four waves stacked in y: 256 columns x 64 rows, the same 16384 cells as a 128 x 128 block.  Only X is staged in LDS
+// (one direct-to-LDS load per wave = one whole 256-float row; KC + 2 rows = 29.7 KB as before); per term a lane reads its four columns with ONE ds_read_b128 and the wave
+// its 16 row values yt[k][y0 .. y0 + 15] with ONE 64-byte scalar load, and the 32 + 32 packed instructions take the row value from an SGPR pair through op_sel -- a quarter
+// of the LDS read bytes of the 8 x 8 form, no VGPR read for the row operand, 8 operand VGPRs instead of 24.  Same multiplies and adds on the same values in the same k
+// order: same bits.  What it buys is CLOCK, not cycles (profiles/r11_sine_rowscalar_probe.txt: the two loops take the same shader cycles per block, the chip holds
+// ~2.24 GHz under this one against ~2.12 GHz under the 8 x 8 loop).
+// LDS reads and scalar loads share one counter and scalar loads return out of order, so the only wait is lgkmcnt(0): a stage is one term -- wait, put the next term's
+// ds_read_b128 and scalar load in flight, run this term's 64 packed instructions.  A buffer whose load is in flight must never meet a register copy: the buffers are asm
+// operands from issue to use, vector and scalar outputs never share an asm statement (mixed, the compiler takes the scalar ones for divergent values and cannot carry them
+// around the loop), and no scalar buffer is live from one chunk to the next (the compiler puts copies where two paths join).
+// Columns behind the padded row length (the last block of a grid whose nxp is an odd multiple of 128) are staged from the row's last four columns instead: whatever they
+// sum to is never stored.  Rows: nyp = round_up(ny, 128) covers every 64-row block's scalar loads, and the last prefetch of a chunk reads table row k0 + kn <= 90
+// (sg_rs_last_row_read(), terra_common.hpp) and LDS row kn <= KC.
+constexpr int SGR_BX = 256, SGR_BY = 64, SGR_ROWS = 16;
+typedef unsigned sgr_u2 __attribute__((ext_vector_type(2)));   // scalar operands live in integer types: uniform integers stay in SGPRs
+typedef unsigned sgr_u16 __attribute__((ext_vector_type(16)));
+typedef float sgr_v4f __attribute__((ext_vector_type(4)));
+typedef sgr_u16 const __attribute__((address_space(4))) *sgr_row16_ptr;
+// Eight rows x four columns per asm statement.  Per row pair, r0 += {x0*y0, x1*y0}, {x2*y0, x3*y0} and r1 the same with y1: (y0, y1) is an SGPR pair, the row's value
+// broadcast from either half by op_sel.  mul / mul / add / add as in sg_mul_add_2x8; product rounded by v_pk_mul_f32, then added by v_pk_add_f32: never fused.
+__device__ __forceinline__ void sgr_mul_add_8x4(sg_v2f (&acc)[SGR_ROWS][2], int r, sg_v2f x01, sg_v2f x23, sgr_u2 y01, sgr_u2 y23, sgr_u2 y45, sgr_u2 y67) { // rows r .. r + 7
+	sg_v2f t0, t1;
+#define TERRA_SGR_2X4(R00, R01, R10, R11, Y) \
+	"v_pk_mul_f32 %16, %18, " Y " op_sel:[0,0] op_sel_hi:[1,0]\n\t" \
+	"v_pk_mul_f32 %17, %18, " Y " op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
+	"v_pk_add_f32 " R00 ", " R00 ", %16\n\t" \
+	"v_pk_add_f32 " R10 ", " R10 ", %17\n\t" \
+	"v_pk_mul_f32 %16, %19, " Y " op_sel:[0,0] op_sel_hi:[1,0]\n\t" \
+	"v_pk_mul_f32 %17, %19, " Y " op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
+	"v_pk_add_f32 " R01 ", " R01 ", %16\n\t" \
+	"v_pk_add_f32 " R11 ", " R11 ", %17\n\t"
+	asm(TERRA_SGR_2X4("%0", "%1", "%2", "%3", "%20") TERRA_SGR_2X4("%4", "%5", "%6", "%7", "%21") TERRA_SGR_2X4("%8", "%9", "%10", "%11", "%22") TERRA_SGR_2X4("%12", "%13", "%14", "%15", "%23")
+	    : "+v"(acc[r][0]), "+v"(acc[r][1]), "+v"(acc[r + 1][0]), "+v"(acc[r + 1][1]), "+v"(acc[r + 2][0]), "+v"(acc[r + 2][1]), "+v"(acc[r + 3][0]), "+v"(acc[r + 3][1]),
+	      "+v"(acc[r + 4][0]), "+v"(acc[r + 4][1]), "+v"(acc[r + 5][0]), "+v"(acc[r + 5][1]), "+v"(acc[r + 6][0]), "+v"(acc[r + 6][1]), "+v"(acc[r + 7][0]), "+v"(acc[r + 7][1]),
+	      "=&v"(t0), "=&v"(t1)
+	    : "v"(x01), "v"(x23), "s"(y01), "s"(y23), "s"(y45), "s"(y67));
+#undef TERRA_SGR_2X4
+}
+__device__ __forceinline__ void sgr_accumulate_term(sg_v2f (&acc)[SGR_ROWS][2], sgr_v4f const &x, sgr_u16 const &y) {
+	sg_v2f const x01 = {x.x, x.y}, x23 = {x.z, x.w};
+	sgr_mul_add_8x4(acc, 0, x01, x23, sgr_u2{y.s0, y.s1}, sgr_u2{y.s2, y.s3}, sgr_u2{y.s4, y.s5}, sgr_u2{y.s6, y.s7});
+	sgr_mul_add_8x4(acc, 8, x01, x23, sgr_u2{y.s8, y.s9}, sgr_u2{y.sa, y.sb}, sgr_u2{y.sc, y.sd}, sgr_u2{y.se, y.sf});
+}
+// {a.x*y, a.y*y} with y the low (SEL = 0) or high (SEL = 1) half of the SGPR pair yp
+template<int SEL> __device__ __forceinline__ sg_v2f sgr_pk_mul_bcast(sg_v2f a, sgr_u2 yp) {
+	sg_v2f r;
+	if (SEL) {asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "s"(yp));}
+	else     {asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "s"(yp));}
+	return r;
+}
+// ntx: 256-column blocks of the padded row; nty: 64-row blocks of this launch, the first of them block row 2 job.ty0 of the grid (grid_job_t::ty0 / tyn stay in 128-row units)
+template<int KC> __global__ __launch_bounds__(SG_THREADS) void k_sine_grid_rs(grid_job_t job, noise_consts_t nc, float const *__restrict__ xt, float const *__restrict__ yt,
+	float const *__restrict__ smx, float const *__restrict__ smy, float *__restrict__ out, unsigned ntx, unsigned nty, unsigned rowgroup, uint32_t *__restrict__ mm)
+{
+	__shared__ __attribute__((aligned(16))) float sX[(KC + 2)*SGR_BX];
+	unsigned bxi, byi;
+	if (!sg_tile_of_block(blockIdx.x, ntx, nty, rowgroup, bxi, byi)) return;
+	byi += job.ty0*2u;
+	uint32_t mm_lo = 0xFFFFFFFFu, mm_hi = 0xFFFFFFFFu;
+	unsigned const tid = threadIdx.x, bx0 = bxi*SGR_BX, by0 = byi*SGR_BY;
+	unsigned const w = sg_wave_uniform(tid >> 6), lane = tid & 63u;
+	sg_v2f acc[SGR_ROWS][2];
+#pragma unroll
+	for (int i = 0; i < SGR_ROWS; ++i) {acc[i][0] = sg_v2f{0.0f, 0.0f}; acc[i][1] = sg_v2f{0.0f, 0.0f};}
+	int const nk = F_TABLE_SIZE - job.kstart, nchunks = (nk + KC - 1)/KC, per_chunk = sg_chunk_len(job.kstart, KC);
+	// the island terms of the block's 256 columns go into the spare LDS row KC + 1, 64 per wave (the row terms are scalars: loaded in the epilogue)
+	if (job.glaciate && job.use_sine_mag) {
+		if (bx0 + w*64u < job.nxp) {sg_load_to_lds<4>(smx + bx0 + w*64u + lane, sX + (KC + 1)*SGR_BX + w*64u);}
+		if (nchunks <= 0) {__syncthreads();}
+	}
+	unsigned const xcol = bx0 + lane*4u, vx = (((xcol < job.nxp) ? xcol : job.nxp - 4u) - bx0)*4u; // bytes from the block's first column; behind the padded row: its last four columns
+	size_t const rowb = (size_t)job.nyp*4u;
+	char const *const ybase = sg_wave_uniform_ptr(yt + by0 + w*(unsigned)SGR_ROWS); // the wave's 16 rows of table row 0: 64 bytes, 64-byte aligned
+	unsigned const la = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)sX + lane*16u; // the lane's four columns of LDS row 0
+	sgr_v4f xa, xb; sgr_u16 ya, yb;
+#define TERRA_SGR_NEXT(CX, CY, NX, NY, LADDR, OFF, YP) \
+	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx16 %1, %2, 0x0" : "+s"(CY), "=&s"(NY) : "s"(YP)); \
+	asm volatile("ds_read_b128 %1, %2 offset:" #OFF : "+v"(CX), "=&v"(NX) : "v"(LADDR))
+	for (int c = 0; c < nchunks; ++c) { // terms are summed in k order across chunks, exactly like the CPU loop
+		int const k0 = job.kstart + c*per_chunk, kn = ((k0 + per_chunk > F_TABLE_SIZE) ? F_TABLE_SIZE - k0 : per_chunk);
+		if (c > 0) {__syncthreads();} // everyone is done reading the previous chunk
+		char const *yp = ybase + (size_t)k0*rowb;
+		asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=&s"(ya) : "s"(yp)); // the chunk's first row operands, asked for in front of the staging, land under it
+		{	// wave w takes the table rows w, w + 4, ... below kn: the only test is the scalar loop condition
+			char const *gx = sg_wave_uniform_ptr(xt + (size_t)(k0 + (int)w)*job.nxp + bx0);
+			for (int r = (int)w; r < kn; r += 4) {sg_load_to_lds<16>(gx + vx, sX + r*SGR_BX); gx += (size_t)job.nxp*16u;}
+		}
+		__syncthreads(); // (waits for the wave's direct-to-LDS loads -- vmcnt(0) -- before the barrier)
+		asm volatile("ds_read_b128 %0, %1" : "=&v"(xa) : "v"(la));
+		unsigned a = la;
+		int k = 0;
+		for (; k + 1 < kn; k += 2) { // (the last pair's second stage asks for LDS row kn and table row k0 + kn: both exist, neither is used)
+			TERRA_SGR_NEXT(xa, ya, xb, yb, a, 1024, yp + rowb);   sgr_accumulate_term(acc, xa, ya); __builtin_amdgcn_sched_barrier(0);
+			TERRA_SGR_NEXT(xb, yb, xa, ya, a, 2048, yp + 2*rowb); sgr_accumulate_term(acc, xb, yb); __builtin_amdgcn_sched_barrier(0);
+			a += 2048u; yp += 2*rowb;
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ya)); asm volatile("" : "+v"(xa)); // nothing is in flight when the block meets at the next barrier
+		if (k < kn) {sgr_accumulate_term(acc, xa, ya); __builtin_amdgcn_sched_barrier(0);}
+	}
+#undef TERRA_SGR_NEXT
+	// ---- the packed epilogue of k_sine_grid (glaciate, island term, off; fused min / max): a lane's island column terms are its 4 floats of LDS row KC + 1, the 16 row terms
+	// of the wave are scalars (one 64-byte scalar load; the island tables are zero-padded like the sine tables)
+	typedef sg_v2f v2f;
+	bool const gl = job.glaciate && nc.glaciate, sm = job.glaciate && job.use_sine_mag;
+	float4 sx = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	sgr_u16 sy = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+	auto const islands = [&]() {sx = *(float4 const *)(sX + (KC + 1)*SGR_BX + lane*4u); sy = *(sgr_row16_ptr)(uintptr_t)(smy + by0 + w*(unsigned)SGR_ROWS);};
+	v2f const zme = {nc.zmax_est, nc.zmax_est}, inv = {nc.zmax_est2_inv, nc.zmax_est2_inv}, z2 = {nc.zmax_est2, nc.zmax_est2}, off = {job.sine_offset, job.sine_offset};
+	float fmn = INFINITY, fmx = -INFINITY;
+	if (bx0 + SGR_BX <= job.nx && by0 + SGR_BY <= job.ny && job.nx < (1u << 24)) {
+		// a block wholly inside the grid: 16 rows in a straight line -- no lane is masked, gl / sm are tested once per block, and a wave's store is 64 lanes x 16 bytes = 1 KB
+		// of one row, one per-lane offset on a scalar row address.  The same operations on the same values in the same order as the guarded loop below.
+		unsigned const voff = lane*16u;
+		char *const ob = (char *)(out + (size_t)(by0 + w*(unsigned)SGR_ROWS)*job.nx + bx0);
+		size_t const rowbytes = (size_t)job.nx*4u;
+		auto const rows = [&](auto GL, auto SM) {
+			if (decltype(SM)::value) {islands();}
+#pragma unroll
+			for (int i = 0; i < SGR_ROWS; ++i) {
+				v2f z01 = acc[i][0], z23 = acc[i][1];
+				if (decltype(GL)::value) {
+					v2f const r01 = (z01 + zme)*inv, r23 = (z23 + zme)*inv;
+					z01 = ((r01*r01)*r01)*z2 - zme; z23 = ((r23*r23)*r23)*z2 - zme;
+				}
+				if (decltype(SM)::value) {
+					v2f const s01 = {sx.x, sx.y}, s23 = {sx.z, sx.w};
+					sgr_u2 const syp = {sy[i & ~1], sy[i | 1]};
+					z01 = z01 + (((i & 1) ? sgr_pk_mul_bcast<1>(s01, syp) : sgr_pk_mul_bcast<0>(s01, syp)) + off); z23 = z23 + (((i & 1) ? sgr_pk_mul_bcast<1>(s23, syp) : sgr_pk_mul_bcast<0>(s23, syp)) + off);
+				}
+				fmn = sg_min3(sg_min3(fmn, z01.x, z01.y), z23.x, z23.y);
+				fmx = sg_max3(sg_max3(fmx, z01.x, z01.y), z23.x, z23.y);
+				*(float4 *)(ob + (size_t)i*rowbytes + voff) = make_float4(z01.x, z01.y, z23.x, z23.y);
+			}
+		};
+		typedef std::true_type yes; typedef std::false_type no;
+		if (gl) {if (sm) {rows(yes(), yes());} else {rows(yes(), no());}}
+		else    {if (sm) {rows(no(), yes());} else {rows(no(), no());}}
+	}
+	else { // a block on the grid's right or lower edge: rows of 4 cells are either wholly inside the grid or wholly outside
+		if (sm) {islands();}
+		unsigned const x = bx0 + lane*4u;
+#pragma unroll
+		for (int i = 0; i < SGR_ROWS; ++i) {
+			unsigned const y = by0 + w*(unsigned)SGR_ROWS + (unsigned)i;
+			if (y >= job.ny || x >= job.nx) continue;
+			float const syf = __uint_as_float(sy[i]);
+			v2f const syi = {syf, syf};
+			v2f z01 = acc[i][0], z23 = acc[i][1];
+			if (gl) {
+				v2f const r01 = (z01 + zme)*inv, r23 = (z23 + zme)*inv;
+				z01 = ((r01*r01)*r01)*z2 - zme; z23 = ((r23*r23)*r23)*z2 - zme;
+			}
+			if (sm) {
+				v2f const s01 = {sx.x, sx.y}, s23 = {sx.z, sx.w};
+				z01 = z01 + (s01*syi + off); z23 = z23 + (s23*syi + off);
+			}
+			fmn = sg_min3(sg_min3(fmn, z01.x, z01.y), z23.x, z23.y);
+			fmx = sg_max3(sg_max3(fmx, z01.x, z01.y), z23.x, z23.y);
+			*(float4 *)(out + (size_t)y*job.nx + x) = make_float4(z01.x, z01.y, z23.x, z23.y);
+		}
+	}
+	if (mm) {
+		if (fmn <= fmx) {mm_lo = f2ord(fmn); mm_hi = ~f2ord(fmx);}
+		wave_minmax_publish_full(mm_lo, mm_hi, mm); // (all 64 lanes are here: a block leaves the kernel as a whole or not at all)
 	}
 }
 

@@ -7,7 +7,7 @@ import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
 MUST_NOT_SPILL = [("speculative_erosion", "wave_scratch_t"),  # k_waves<trace lambda>: the only speculative_erosion kernel that takes the LDS scratch
-                  ("k_sine_grid", "Lb0ELb0E"), ("k_noise_grid", ""), ("k_tile_erosion", ""),
+                  ("k_sine_grid", "Lb0ELb0E"), ("k_sine_grid_rs", ""), ("k_noise_grid", ""), ("k_tile_erosion", ""),
                   ("k_tree_place", ""), ("k_decid_place", ""), ("k_scenery_place", ""),  # their comments promise "no scratch"
                   ("k_terrain_view_tiles", ""), ("k_terrain_view_occluders", ""), ("k_terrain_view_occlusion", ""), ("k_terrain_view_lists", ""), ("k_terrain_view_rank", ""),
                   ("k_reflect_walk", ""), ("k_reflect_finish", ""), ("k_water_view", ""),
@@ -20,6 +20,8 @@ MUST_NOT_SPILL = [("speculative_erosion", "wave_scratch_t"),  # k_waves<trace la
 # Recorded at this commit (vgpr / sgpr / lds / scratch): k_smap_plan 70 / 94 / 0 / 0, k_smap_plan_lists 18 / 29 / 16 / 0, k_smap_plan_rank 34 / 84 / 4096 / 0,
 # k_smap_geom 24 / 20 / 0 / 0, k_smap_casters 70 / 100 / 64 / 0.
 UNUSED_FRAME = ["k_reflect_walk"]
+# registers a kernel must stay under: k_sine_grid_rs at 96 leaves room for four of its waves and a 128-register droplet wave of another heightmap on a SIMD
+MAX_VGPR = {"k_sine_grid_rs": 96}
 
 
 def kernels():
@@ -48,8 +50,10 @@ def main():
             print(f"{name[:40]}..{name[-48:]}  vgpr {vgpr}  sgpr {sgpr}  lds {lds}  scratch {scratch} ({ops} accesses){'  <-- hot' if hot else ''}")
         if hot and ((scratch and not unused) or ops or scratch > 8):
             bad.append(name)
+        if any(k in name and vgpr > v for k, v in MAX_VGPR.items()):
+            bad.append(name + f" ({vgpr} VGPRs)")
     if "--check" in sys.argv and bad:
-        raise SystemExit("scratch (register spills) in: " + ", ".join(b[-60:] for b in bad))
+        raise SystemExit("scratch (register spills) or too many registers in: " + ", ".join(b[-60:] for b in bad))
 
 
 if __name__ == "__main__":
