@@ -635,6 +635,40 @@ int terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 		st.end();
 	TERRA_CATCH
 }
+static_assert(sizeof(terra_line_tree_hit) == 40 && sizeof(terra::line_tree_hit_pod_t) == 40 && sizeof(terra_line_trees_in) == 72, "terra_line_tree_hit / terra_line_trees_in layout");
+int terra_tiles_line_intersect_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_line_trees_in *in, const float *d_lines, const int32_t *d_line_tile,
+                                         uint32_t nlines, terra_line_tree_hit *d_hits) {
+	TERRA_CHECK_CTX
+	TERRA_TRY ctx->eng.tiles_line_intersect_trees_dev(tile_xy, n, in, d_lines, d_line_tile, nlines, (terra::line_tree_hit_pod_t *)d_hits); TERRA_CATCH
+}
+int terra_tiles_line_intersect_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_line_trees_in *in, const float *h_lines, const int32_t *h_line_tile,
+                                     uint32_t nlines, terra_line_tree_hit *h_hits) {
+	TERRA_CHECK_CTX
+	TERRA_TRY
+		ctx->eng.line_trees_check(in, "tiles_line_intersect_trees"); // the scene, the tile size and the members that are no arrays: before anything is staged
+		if ((n && (!tile_xy || !in->zvals || !in->stats)) || (nlines && (!h_lines || !h_hits))) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if ((uint64_t)n*in->pine_capacity > 0xFFFFFFFFull) return terra::fail(TERRA_ERR_ARG, "tiles_line_intersect_trees: n*pine_capacity must fit 32 bits");
+		if ((((uintptr_t)in->zvals | (uintptr_t)in->stats | (uintptr_t)in->pine | (uintptr_t)in->pine_counts | (uintptr_t)in->trunk_override | (uintptr_t)h_lines | (uintptr_t)h_line_tile |
+		      (uintptr_t)h_hits) & 3u) != 0) return terra::fail(TERRA_ERR_ARG, "tiles_line_intersect_trees: every array but is_distant must be 4-byte aligned");
+		if (h_line_tile) {
+			for (uint32_t r = 0; r < nlines; ++r) {if (h_line_tile[r] >= 0 && (uint32_t)h_line_tile[r] >= n) {return terra::fail(TERRA_ERR_ARG, "tiles_line_intersect_trees: line_tile entry out of range");}}
+		}
+		if (nlines == 0) return TERRA_OK;
+		size_t const S = ctx->eng.tile_size(), np = (size_t)n*in->pine_capacity;
+		bool const hp = in->pine && in->pine_counts && np;
+		terra_stage st(ctx->eng); // (with n == 0 the tile arrays are empty: nothing of them is uploaded)
+		int const z = st.in(in->zvals, (size_t)n*(S + 2)*(S + 2)*4), s = st.in(in->stats, (size_t)n*sizeof(terra_tile_stats)), k = st.opt_in(in->is_distant, n),
+			p = st.add(in->pine, nullptr, np*sizeof(terra_tree_place), hp), pc = st.add(in->pine_counts, nullptr, (size_t)n*4, hp),
+			ov = st.add(in->trunk_override, nullptr, np*sizeof(terra_trunk_override), hp && in->trunk_override),
+			l = st.in(h_lines, (size_t)nlines*24), lt = st.opt_in(h_line_tile, (size_t)nlines*4), h = st.out(h_hits, (size_t)nlines*sizeof(terra_line_tree_hit));
+		st.begin();
+		terra_line_trees_in d = *in;
+		d.zvals = st.dev<float>(z); d.stats = st.dev<terra_tile_stats>(s); d.is_distant = st.dev<uint8_t>(k);
+		d.pine = st.dev<terra_tree_place>(p); d.pine_counts = st.dev<uint32_t>(pc); d.trunk_override = st.dev<terra_trunk_override>(ov);
+		ctx->eng.tiles_line_intersect_trees_dev(tile_xy, n, &d, st.dev<float>(l), st.dev<int32_t>(lt), nlines, st.dev<terra::line_tree_hit_pod_t>(h));
+		st.end();
+	TERRA_CATCH
+}
 static_assert(sizeof(terra_tree_splat) == 12 && sizeof(terra::tree_splat_in_t) == 12, "terra_tree_splat layout");
 int terra_tiles_tree_map_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const uint8_t *d_is_distant, const terra_tree_splat *d_splats,
                              const uint32_t *h_first, int32_t reset, uint8_t *d_tree_map, uint8_t *d_updated) {

@@ -30,6 +30,7 @@
 #include "terra_decidview.hpp"
 #include "terra_sceneryview.hpp"
 #include "terra_collide.hpp"
+#include "terra_linetrees.hpp"
 #include "terra_stage.hpp"
 #include "../../include/terra.h"
 #include <vector>
@@ -2241,6 +2242,60 @@ template<class BE> struct terra_engine {
 				if (line_tile_hit(c, b, v1, v2, d_zvals + i*zn, tn, ix, iy) && tn < h.t) {h = line_hit_make(v1, v2, tn, i, b, ix, iy);}
 			}
 			d_hits[r] = h;
+		});
+	}
+	// tile_draw_t::line_intersect_mesh (src/tiled_mesh.cpp:3582-3604) with inc_trees != 0 (terra_linetrees.hpp): the mesh walk of every tile as above and, where it
+	// misses, small_tree_group::line_intersect over the tile's pine records.  The checks that need no array (the host form runs them before it stages anything):
+	void line_trees_check(terra_line_trees_in const *in, char const *what) const {
+		require_scene();
+		require_tile_size();
+		if (!in) throw std::invalid_argument(std::string(what) + ": null argument");
+		if (!(isfinite(in->tree_depth_scale) && in->tree_depth_scale > 0.0f)) throw std::invalid_argument(std::string(what) + ": tree_depth_scale must be finite and > 0");
+		if (in->pine && in->pine_counts && in->pine_capacity) {require_tree_insts(what);}
+	}
+	void tiles_line_intersect_trees_dev(int32_t const *tile_xy, uint32_t n, terra_line_trees_in const *a, float const *d_lines, int32_t const *d_line_tile, uint32_t nlines,
+		line_tree_hit_pod_t *d_hits)
+	{
+		char const *const what = "tiles_line_intersect_trees";
+		line_trees_check(a, what);
+		bool const has_pine = a->pine && a->pine_counts && a->pine_capacity;
+		if ((uint64_t)n*a->pine_capacity > 0xFFFFFFFFull) throw std::invalid_argument(std::string(what) + ": n*pine_capacity must fit 32 bits");
+		if (n && (!tile_xy || !a->zvals || !a->stats)) throw std::invalid_argument(std::string(what) + ": null argument");
+		if (nlines && (!d_lines || !d_hits)) throw std::invalid_argument(std::string(what) + ": null argument");
+		if ((((uintptr_t)a->zvals | (uintptr_t)a->stats | (uintptr_t)a->pine | (uintptr_t)a->pine_counts | (uintptr_t)a->trunk_override | (uintptr_t)d_lines | (uintptr_t)d_line_tile |
+		      (uintptr_t)d_hits) & 3u) != 0) throw std::invalid_argument(std::string(what) + ": every array but is_distant must be 4-byte aligned");
+		if (nlines == 0) return;
+		line_trees_consts_t c;
+		c.q.xss = cfg.scene_x; c.q.yss = cfg.scene_y; c.q.DX_VAL = DX_VAL; c.q.DY_VAL = DY_VAL; c.q.DX_VAL_INV = DX_VAL_INV; c.q.DY_VAL_INV = DY_VAL_INV;
+		c.q.S = (int)tile_size(); c.q.dxoff = a->dxoff; c.q.dyoff = a->dyoff;
+		tree_ao_consts_t const ac = tree_ao_consts(a->dxoff, a->dyoff, a->ptree_xoff2, a->ptree_yoff2, a->pine_capacity, 0, 0, 0); // ptree_off.get_xlate()
+		view_pod_t v; memset(&v, 0, sizeof(v)); // (no camera: of the view constants only the scene, the offsets and the tree depth are read)
+		tree_view_args_pod_t const ta = {0.0f, 1.0f, a->tree_depth_scale, 1, 0, 0, 0, 0};
+		c.pv = tree_view_consts(v, ta, ac, cfg.scene_x, cfg.scene_y, a->dxoff, a->dyoff, a->pine_capacity);
+		c.cap = has_pine ? a->pine_capacity : 0u;
+		line_trees_in_t in;
+		in.pine = has_pine ? (tree_place_pod_t const *)a->pine : nullptr; in.counts = has_pine ? a->pine_counts : nullptr;
+		in.ov = has_pine ? (trunk_override_pod_t const *)a->trunk_override : nullptr;
+		in.insts = (has_pine && tp.instanced) ? tree_insts_dev() : nullptr;
+		tile_ref_pod_t const *d_refs = n ? tile_fields_dev(tile_xy, n, tile_size() + 2, 0, nullptr, 0.0f) : nullptr; // (only the tile references)
+		line_box_t *d_boxes; line_tree_box_t *d_tboxes;
+		stage_layout_t lay;
+		lay.add(d_boxes, n); lay.add(d_tboxes, has_pine ? n : 0);
+		lay.bind(scratch<uint8_t>(s_ao, lay.total));
+		if (!has_pine) {d_tboxes = nullptr;}
+		float const *d_zvals = a->zvals; terra_tile_stats const *d_stats = a->stats; uint8_t const *d_distant = a->is_distant;
+		if constexpr (BE::has_kernels) {if (be.tile_line_intersect_trees(c, in, d_refs, n, d_zvals, d_stats, d_distant, d_boxes, d_tboxes, d_lines, d_line_tile, nlines, d_hits)) return;}
+		// the simple form: one logical thread per tile for its two boxes, then one per line, the reference's loops over the tiles in batch order
+		be.launch(n, [=] TERRA_LAMBDA (size_t i) {
+			line_box_t b = line_tile_box(c.q, d_refs[i].tx, d_refs[i].ty, d_stats[i].mzmin, d_stats[i].mzmax);
+			if (d_distant && d_distant[i]) {b.d[2][0] = INFINITY; b.d[2][1] = -INFINITY;}
+			d_boxes[i] = b;
+			if (d_tboxes) {d_tboxes[i] = line_trees_box(c, in, (uint32_t)i);}
+		});
+		be.launch(nlines, [=] TERRA_LAMBDA (size_t r) {
+			float const *L = d_lines + 6*r;
+			shadow_pt_t const v1 = {L[0], L[1], L[2]}, v2 = {L[3], L[4], L[5]};
+			d_hits[r] = line_trees_query_literal(c, in, d_zvals, d_boxes, d_tboxes, n, v1, v2, d_line_tile ? d_line_tile[r] : -1);
 		});
 	}
 	// ---- the tree map and the two textures that read it (terra_treemap.hpp)

@@ -529,6 +529,23 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		}
 		return true;
 	}
+	// the line queries with inc_trees != 0: k_line_tree_boxes once per tile (a wave a tile), then k_line_intersect_trees once per line, in launches as above.
+	// record*2 + part must fit 32 bits: a capacity beyond 2^31 goes to the simple form
+	bool tile_line_intersect_trees(terra::line_trees_consts_t const &c, terra::line_trees_in_t const &in, terra::tile_ref_pod_t const *refs, uint32_t n, float const *zvals,
+		terra_tile_stats const *stats, uint8_t const *distant, terra::line_box_t *boxes, terra::line_tree_box_t *tboxes, float const *lines, int32_t const *line_tile, uint32_t nlines,
+		terra::line_tree_hit_pod_t *hits)
+	{
+		if (opt->simple_kernels || n > 0x7FFFFFFFu || c.cap > 0x7FFFFFFFu) return false;
+		use();
+		if (n) {run(terra::k_line_tree_boxes, dim3((n + 3)/4), dim3(256), 0, c, in, refs, stats, distant, n, boxes, tboxes);}
+		uint32_t const per = (0xFFFFFFFFu/terra::LT_THREADS) & ~255u;
+		for (uint32_t r0 = 0; r0 < nlines;) {
+			uint32_t const m = terra::min_u32(per, nlines - r0);
+			run(terra::k_line_intersect_trees, dim3(m), dim3(terra::LT_THREADS), 0, c, in, zvals, boxes, tboxes, n, lines + (size_t)6*r0, line_tile ? line_tile + r0 : nullptr, hits + r0);
+			r0 += m;
+		}
+		return true;
+	}
 	// the tree map: k_tree_splats once per splat, then k_tree_map once per (tile, band of rows): bands of equal height that fit the kernel's LDS
 	bool tile_tree_map(terra::tree_tile_pod_t const *tiles, uint32_t n, uint32_t S, uint8_t const *distant, terra::tree_splat_in_t const *splats, uint32_t ns,
 		terra::tree_splat_pod_t *par, float dxv, float dyv, bool reset, uint16_t *map, uint8_t *updated)

@@ -1635,6 +1635,145 @@ __global__ __launch_bounds__(LI_THREADS) void k_line_intersect(line_query_consts
 	}
 }
 
+// ------------------------------------------------------------------ line queries with inc_trees != 0 (tile_t::line_intersect_mesh, src/tiled_mesh.cpp:2176-2216;
+// terra_linetrees.hpp), two launches
+// k_line_tree_boxes: one 64-lane wave per tile, four tiles per workgroup.  Lane 0 writes the tile's mesh box as k_line_boxes does; the wave sweeps the tile's pine
+// records, a lane a record, for calc_bcube() and the number of valid records, reduced with shuffles (the union starts from an empty box instead of the first
+// record's: the same bounds but for the sign of a zero, which neither is_zero_area() nor the clip's comparisons see).
+__global__ __launch_bounds__(256) void k_line_tree_boxes(line_trees_consts_t c, line_trees_in_t in, tile_ref_pod_t const *__restrict__ refs, terra_tile_stats const *__restrict__ stats,
+	uint8_t const *__restrict__ distant, uint32_t n, line_box_t *__restrict__ boxes, line_tree_box_t *__restrict__ tboxes)
+{
+	uint32_t const lane = threadIdx.x & 63u;
+	uint32_t const i = blockIdx.x*4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	if (i >= n) return; // (the whole wave)
+	if (lane == 0u) {
+		line_box_t b = line_tile_box(c.q, refs[i].tx, refs[i].ty, stats[i].mzmin, stats[i].mzmax);
+		if (distant && distant[i]) {b.d[2][0] = INFINITY; b.d[2][1] = -INFINITY;}
+		boxes[i] = b;
+	}
+	if (!tboxes) return;
+	float const INF = __builtin_inff();
+	float box[6] = {INF, -INF, INF, -INF, INF, -INF};
+	uint32_t nv = 0, nb = 0;
+	uint32_t const cnt = line_trees_count(c, in, i);
+	for (uint32_t j = lane; j < cnt; j += 64u) {
+		tree_view_rec_t rec;
+		if (!line_trees_rec(c, in, i, j, rec)) continue;
+		++nv;
+		float d[6];
+		if (!tree_view_bounds(rec, d)) continue;
+		++nb;
+		box_union(box, d);
+	}
+	for (int off = 32; off; off >>= 1) {
+		nv += __shfl_xor(nv, off); nb += __shfl_xor(nb, off);
+#pragma unroll
+		for (int k = 0; k < 6; k += 2) {box[k] = min_std(box[k], __shfl_xor(box[k], off)); box[k + 1] = max_std(box[k + 1], __shfl_xor(box[k + 1], off));}
+	}
+	if (lane == 0u) {
+		line_tree_box_t b;
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {b.bc[k] = nb ? box[k] : 0.0f;}
+		b.nvalid = nv; b.pad = 0u;
+		tboxes[i] = b;
+	}
+}
+// k_line_intersect_trees: one workgroup per line, k_line_intersect's rounds.  A tile is kept when its mesh box or the gate of its pine container passes (a distant
+// tile never); the kept tiles' mesh walks run first, a tile per thread; a tile whose walk hit drops out (the reference returns cur_t and does not look at its
+// trees); then the waves take the remaining gated tiles, a tile per wave, its records 64 at a time, a record per lane, each lane the literal
+// small_tree::line_intersect with *t = 1.0.  Every thread keeps its best (t, batch index) as k_line_intersect's 64-bit key and beside it record*2 + part (0 for a
+// mesh hit; a tile gives mesh hits or tree hits, never both).  The workgroup takes the minimum key, then among its holders the minimum record*2 + part: over the tiles
+// the strictly smaller tn and then the lowest batch index, within a tile the first record and cylinder that reaches the minimum -- what the sequential `t_new < *t`
+// leaves.  No per-record pre-test stands in front of the cone test: a record's add_bounds_to_bcube box does not bound its leaf cone.
+// Nothing is indexed with a line_tile, a count or a record's inst before its range is known (line_tile_range, line_trees_count, small_tree_size).
+constexpr uint32_t LT_THREADS = 256, LT_PER = 4, LT_ROUND = LT_THREADS*LT_PER, LT_TREES = 0x80000000u;
+TERRA_D line_tree_box_t line_tree_box_load(line_tree_box_t const *p) {
+	uint4 const a = ((uint4 const *)p)[0], b = ((uint4 const *)p)[1];
+	uint32_t const w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+	line_tree_box_t r;
+	memcpy(&r, w, sizeof(r));
+	return r;
+}
+__global__ __launch_bounds__(LT_THREADS) void k_line_intersect_trees(line_trees_consts_t c, line_trees_in_t in, float const *__restrict__ zvals, line_box_t const *__restrict__ boxes,
+	line_tree_box_t const *__restrict__ tboxes, uint32_t n, float const *__restrict__ lines, int32_t const *__restrict__ line_tile, line_tree_hit_pod_t *__restrict__ hits)
+{
+	__shared__ uint32_t s_list[LT_ROUND]; // the round's kept tiles; LT_TREES: the container's gate passed and the mesh walk has not hit
+	__shared__ uint32_t s_cnt, s_sub;
+	__shared__ unsigned long long s_best;
+	uint32_t const r = blockIdx.x, lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	float const *L = lines + (size_t)6*r;
+	shadow_pt_t const v1 = {L[0], L[1], L[2]}, v2 = {L[3], L[4], L[5]};
+	uint32_t i0, i1;
+	line_tile_range(line_tile ? line_tile[r] : -1, n, line_finite(v1, v2), i0, i1);
+	float p1[3], p2[3];
+	line_trees_local(c, v1, p1); line_trees_local(c, v2, p2);
+	size_t const zn = (size_t)(c.q.S + 2)*(c.q.S + 2);
+	unsigned long long best = ~0ull;
+	uint32_t bsub = 0u;
+	bool bmesh = false;
+	float bt = 0.0f; int bx = 0, by = 0;
+	if (threadIdx.x == 0) {s_best = ~0ull; s_sub = 0xFFFFFFFFu;}
+	for (uint32_t base = i0; base < i1; base += LT_ROUND) {
+		if (threadIdx.x == 0) {s_cnt = 0;}
+		__syncthreads();
+		for (uint32_t k = 0; k < LT_PER; ++k) {
+			uint32_t const i = base + k*LT_THREADS + threadIdx.x;
+			if (i >= i1) continue;
+			line_box_t const b = line_box_load(boxes + i);
+			if (b.d[2][0] > b.d[2][1]) continue; // distant (:2178)
+			bool const mesh = line_box_clip(b, v1, v2);
+			bool trees = false;
+			if (tboxes) {
+				line_tree_box_t const tb = line_tree_box_load(tboxes + i);
+				trees = tb.nvalid != 0u && line_trees_gate(tb, p1, p2);
+			}
+			if (mesh || trees) {s_list[atomicAdd(&s_cnt, 1u)] = i | (trees ? LT_TREES : 0u);}
+		}
+		__syncthreads();
+		uint32_t const cnt = s_cnt;
+		for (uint32_t j = threadIdx.x; j < cnt; j += LT_THREADS) {
+			uint32_t const i = s_list[j] & ~LT_TREES;
+			float t = 1.0f; int ix = 0, iy = 0;
+			if (!line_tile_hit(c.q, line_box_load(boxes + i), v1, v2, zvals + i*zn, t, ix, iy)) continue;
+			s_list[j] = i; // the mesh hit: the tile's trees are not looked at
+			uint32_t tb = __float_as_uint(t);
+			if (tb == 0x80000000u) {tb = 0u;}
+			unsigned long long const key = ((unsigned long long)tb << 32) | i;
+			if (key < best) {best = key; bsub = 0u; bmesh = true; bt = t; bx = ix; by = iy;}
+		}
+		__syncthreads();
+		for (uint32_t j = wave; j < cnt; j += LT_THREADS/64u) {
+			uint32_t const e = s_list[j];
+			if (!(e & LT_TREES)) continue; // (the whole wave)
+			uint32_t const i = e & ~LT_TREES, nrec = line_trees_count(c, in, i);
+			for (uint32_t j0 = 0; j0 < nrec; j0 += 64u) {
+				uint32_t const jj = j0 + lane;
+				float t; uint32_t part;
+				if (!(jj < nrec && line_trees_test(c, in, i, jj, p1, p2, t, part))) continue;
+				uint32_t tb = __float_as_uint(t);
+				if (tb == 0x80000000u) {tb = 0u;}
+				unsigned long long const key = ((unsigned long long)tb << 32) | i;
+				uint32_t const sub = jj*2u + part;
+				if (key < best || (key == best && !bmesh && sub < bsub)) {best = key; bsub = sub; bmesh = false; bt = t;}
+			}
+		}
+		__syncthreads(); // (the next round rewrites s_cnt / s_list)
+	}
+	if (best != ~0ull) {atomicMin(&s_best, best);}
+	__syncthreads();
+	unsigned long long const win = s_best;
+	if (win == ~0ull) { // (the whole workgroup)
+		if (threadIdx.x == 0) {hits[r] = line_tree_miss();}
+		return;
+	}
+	if (best == win) {atomicMin(&s_sub, bsub);}
+	__syncthreads();
+	if (best == win && bsub == s_sub) {
+		uint32_t const i = (uint32_t)win;
+		hits[r] = bmesh ? line_tree_hit_mesh(v1, v2, bt, i, boxes[i], bx, by) : line_tree_hit_tree(v1, v2, bt, i, (int32_t)(bsub >> 1), bsub & 1u);
+	}
+}
+
 // ------------------------------------------------------------------ tree map (tile_t::add_tree_ao_shadow, src/tiled_mesh.cpp:749-767), two launches
 // k_tree_splats: xc, yc, rval and scale of every splat, once per call (a float division per axis and a double one per splat); it also clears `updated`.
 __global__ __launch_bounds__(256) void k_tree_splats(tree_tile_pod_t const *__restrict__ tiles, uint32_t n, tree_splat_in_t const *__restrict__ splats, uint32_t ns,

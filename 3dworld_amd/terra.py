@@ -55,6 +55,10 @@ MOD_DTYPE = np.dtype([("x", np.uint16), ("y", np.uint16), ("delta", np.int32)]) 
 GRASS_BLOCK_DTYPE = np.dtype([("ix", np.uint32), ("zmin", np.float32), ("zmax", np.float32)])  # terra_grass_block
 LINE_HIT_DTYPE = np.dtype([("t", np.float32), ("tile", np.int32), ("xpos", np.int32), ("ypos", np.int32), ("p_int", np.float32, (3,)), ("hit", np.uint32)])  # terra_line_hit
 assert LINE_HIT_DTYPE.itemsize == 32
+LINE_TREE_HIT_DTYPE = np.dtype([("t", np.float32), ("tile", np.int32), ("xpos", np.int32), ("ypos", np.int32), ("p_int", np.float32, (3,)), ("hit", np.uint32),
+                                ("tree", np.int32), ("part", np.uint32)])  # terra_line_tree_hit
+assert LINE_TREE_HIT_DTYPE.itemsize == 40
+LINE_HIT_NONE, LINE_HIT_MESH, LINE_HIT_TREE = 0, 1, 2  # terra_line_tree_hit.hit
 TREE_SPLAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("radius", np.float32)])  # terra_tree_splat
 assert TREE_SPLAT_DTYPE.itemsize == 12
 TREE_PLACE_DTYPE = np.dtype([("pos", np.float32, (3,)), ("type", np.int32), ("inst", np.int32), ("height", np.float32), ("width", np.float32),
@@ -253,6 +257,19 @@ class CollideIn(C.Structure):  # terra_collide_in
                [("tree_depth_scale", C.c_float), ("pad", C.c_uint32)]
 
 
+class LineTreesIn(C.Structure):  # terra_line_trees_in
+    _fields_ = [(k, C.c_void_p) for k in ("zvals", "stats", "is_distant", "pine", "pine_counts", "trunk_override")] + [("pine_capacity", C.c_uint32)] + \
+               [(k, C.c_int32) for k in ("dxoff", "dyoff", "ptree_xoff2", "ptree_yoff2")] + [("tree_depth_scale", C.c_float)]
+
+
+class LineTreeHit(C.Structure):  # terra_line_tree_hit
+    _fields_ = [("t", C.c_float), ("tile", C.c_int32), ("xpos", C.c_int32), ("ypos", C.c_int32), ("p_int", C.c_float * 3), ("hit", C.c_uint32), ("tree", C.c_int32),
+                ("part", C.c_uint32)]
+
+
+assert C.sizeof(LineTreesIn) == 72 and C.sizeof(LineTreeHit) == 40
+
+
 def _address(x):
     """the address of a numpy array, a ctypes object or a DeviceBuffer; an int is taken as an address; None stays None"""
     if x is None or isinstance(x, int):
@@ -275,6 +292,17 @@ def make_collide_in(stats=None, trmax=None, tile_zmax=None, flags=None, pine=Non
                     ptree_yoff2, dtree_xoff2, dtree_yoff2, scenery_xoff2, scenery_yoff2, tree_depth_scale, 0)
     cin._keep = arrays
     return cin
+
+
+def make_line_trees_in(zvals=None, stats=None, is_distant=None, pine=None, pine_counts=None, trunk_override=None, pine_capacity=None, dxoff=0, dyoff=0, ptree_xoff2=0,
+                       ptree_yoff2=0, tree_depth_scale=1.0):
+    """terra_line_trees_in.  An array is a C-contiguous numpy array, a ctypes object, a DeviceBuffer or an address; host arrays go with the host form, device memory with
+    the _dev form.  A capacity that is not given is a [n, capacity] numpy array's.  The struct keeps its arrays alive."""
+    cap = int(pine_capacity) if pine_capacity is not None else (pine.shape[1] if isinstance(pine, np.ndarray) and pine.ndim == 2 else 0)
+    arrays = (zvals, stats, is_distant, pine, pine_counts, trunk_override)
+    lin = LineTreesIn(*[_address(x) for x in arrays], cap, dxoff, dyoff, ptree_xoff2, ptree_yoff2, tree_depth_scale)
+    lin._keep = arrays
+    return lin
 
 
 SPHERE_QUERY_DTYPE = np.dtype([("pos", np.float32, (3,)), ("radius", np.float32), ("tile", np.int32), ("flags", np.uint32)])  # terra_sphere_query
@@ -511,6 +539,8 @@ _PROTOS = {
     "terra_tiles_edit_grass": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "terra_tiles_line_intersect_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_line_intersect": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_line_intersect_trees_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "terra_tiles_line_intersect_trees": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "terra_tiles_tree_map_dev": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "terra_tiles_tree_map": (_i32, [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "terra_tiles_shadow_texture_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _f, _i32, _vp]),
@@ -1011,6 +1041,17 @@ class Terra:
         hits = np.zeros(len(ln), LINE_HIT_DTYPE)
         self._ck(self.lib.terra_tiles_line_intersect(self.ctx, txy.ctypes.data, n, dxoff, dyoff, z.ctypes.data, C.addressof(st) if n else None,
                                                      None if dist is None else dist.ctypes.data, ln.ctypes.data, None if lt is None else lt.ctypes.data, len(ln), hits.ctypes.data))
+        return hits
+
+    def tiles_line_intersect_trees(self, tile_xy, lin, lines, line_tile=None):
+        """tile_draw_t::line_intersect_mesh with inc_trees = 1 of every line against host arrays: lin a make_line_trees_in of host arrays, lines ([nlines,2,3] = v1, v2);
+        line_tile ([nlines], or None): >= 0 restricts a line to that batch tile.  -> LINE_TREE_HIT_DTYPE [nlines]"""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        ln = np.ascontiguousarray(lines, np.float32).reshape(-1, 2, 3)
+        lt = None if line_tile is None else np.ascontiguousarray(line_tile, np.int32).reshape(len(ln))
+        hits = np.zeros(len(ln), LINE_TREE_HIT_DTYPE)
+        self._ck(self.lib.terra_tiles_line_intersect_trees(self.ctx, txy.ctypes.data if len(txy) else None, len(txy), C.byref(lin), ln.ctypes.data if len(ln) else None,
+                                                           None if lt is None else lt.ctypes.data, len(ln), hits.ctypes.data if len(ln) else None))
         return hits
 
     @staticmethod
@@ -1782,6 +1823,12 @@ class Terra:
         txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
         self._ck(self.lib.terra_tiles_cloud_view_dev(self.ctx, txy.ctypes.data, len(txy), C.byref(view), C.byref(args), stats_ptr, state_ptr, clouds_ptr, capacity, stage_ptr, list_ptr,
                                                      list_count_ptr))
+
+    def tiles_line_intersect_trees_dev(self, tile_xy, lin, lines_ptr, nlines, hits_ptr, line_tile_ptr=None):
+        """line hits with inc_trees = 1 against a device-resident batch: lin a make_line_trees_in of device arrays, lines_ptr [nlines][2][3] floats, hits_ptr nlines x
+        LINE_TREE_HIT_DTYPE, line_tile_ptr [nlines] int32 (or None).  Only enqueues."""
+        txy = np.ascontiguousarray(tile_xy, np.int32).reshape(-1, 2)
+        self._ck(self.lib.terra_tiles_line_intersect_trees_dev(self.ctx, txy.ctypes.data if len(txy) else None, len(txy), C.byref(lin), lines_ptr, line_tile_ptr, nlines, hits_ptr))
 
     def tiles_sphere_collide_dev(self, tile_xy, cin, queries_ptr, nq, hits_ptr):
         """the sphere queries of a device-resident batch: cin a make_collide_in of device arrays, queries_ptr [nq] terra_sphere_query, hits_ptr [nq] terra_sphere_hit.

@@ -492,6 +492,60 @@ int  terra_tiles_line_intersect(terra_ctx *ctx, const int32_t *tile_xy, uint32_t
                                 const float *h_zvals, const terra_tile_stats *h_stats, const uint8_t *h_is_distant,
                                 const float *h_lines, const int32_t *h_line_tile, uint32_t nlines, terra_line_hit *h_hits);
 
+/* ---- line queries with inc_trees = 1 on a tile batch (every supported tile size S): the hit-scan weapon path, line_intersect_tiled_mesh(pos, pos2, coll_pos, 1)
+ * (src/Gameplay.cpp:2143).  Per line: tile_draw_t::line_intersect_mesh (src/tiled_mesh.cpp:3582-3604) over tile_t::line_intersect_mesh (:2176-2216) with
+ * inc_trees != 0, bit for bit: small_tree_group::line_intersect with t != NULL (src/sm_tree.cpp:189-200), small_tree::line_intersect (:854-876) and
+ * line_intersect_trunc_cone with check_ends = 0 (src/Math3d.cpp:543-593) with the source's operand types -- the double matrix M, matrix_mult's float x double sums,
+ * m = 1.0/d of normalize(), 0.35*dirh narrowed per component, g = cosf(atan2f(r2, |A|)) with the C library's results (glibc 2.35), and `(1-2*i)*num` with its
+ * unsigned i.  Where line_intersect_trunc_cone asserts (!(r2 > 0 && r2 > r1)) that cylinder does not hit; nothing else is special-cased.
+ * Per (line, tile), in the reference's order: a distant tile returns 0 before the trees; a mesh hit returns cur_t and the tile's trees are not looked at, even when
+ * one stands nearer; otherwise, when the tile holds a valid record, the trees run on (v1 - xlate, v2 - xlate) with xlate = ((dxoff + ptree_xoff2)*DX_VAL,
+ * (dyoff + ptree_yoff2)*DY_VAL, 0), *t starting at 1.0: only a t_new < 1 hits, and within a tile the first record and cylinder that reaches the minimum wins.  The
+ * gate is !all_bcube.is_zero_area() && !check_line_clip(p1, p2, all_bcube.d); a tile whose mesh box the line misses still tests its trees.  Only T_PINE and
+ * T_SH_PINE records hit (two cylinders: trunk_cylin and the leaf cone from pos + 0.35*dirh, or pos for T_SH_PINE, to pos + dirh with get_radius()).
+ * Records, validity and geometry are terra_tiles_tree_view's: the context's instance table and terra_tree_size_params, tree_depth_scale, trunk_override with
+ * rotated != 0 as documented there.  Records that the tree view drops are skipped and do not enter all_bcube, which is calc_bcube() over the valid records,
+ * computed by this call.  A count above the capacity means the first `capacity` records.
+ * Over the tiles the strictly smaller tn wins, ties go to the lowest batch index (as terra_tiles_line_intersect).
+ * zvals, stats, is_distant, lines, line_tile, misses, non-finite lines and n == 0 / nlines == 0: as terra_tiles_line_intersect.  hits, one record per line:
+ * a mesh hit has hit = TERRA_LINE_HIT_MESH, tree = -1, part = 0 and the fields of terra_line_hit; a tree hit has hit = TERRA_LINE_HIT_TREE, xpos = ypos = 0 (the
+ * reference leaves new_xpos / new_ypos at 0), tree = the record index in its tile, part = 0 (trunk_cylin) or 1 (the leaf cone) and p_int = v1 + t*(v2 - v1) from
+ * the untranslated ends; a miss has hit = 0, tree = -1, part = 0.  With pine == NULL, pine_counts == NULL or pine_capacity == 0 the first 32 bytes of every
+ * record equal terra_tiles_line_intersect's, byte for byte.  terra_tiles_line_intersect[_dev] itself does not change.
+ * TERRA_ERR_ARG, with nothing written: a NULL required pointer (in; tile_xy, zvals, stats when n > 0; lines, hits when nlines > 0); a pointer other than
+ * is_distant that is not 4-byte aligned; tree_depth_scale not finite and > 0; `instanced` with an instance table of another length; an unsupported S;
+ * n*pine_capacity beyond 32 bits; in the host form a line_tile entry >= n.  TERRA_ERR_STATE before terra_init_scene.  The device form only enqueues and reads
+ * nothing back; tile_xy is a host array in both forms.  Scratch comes from the context's arena.  The kernels index nothing with a record's inst, a line_tile or a
+ * count before its range is known. */
+struct terra_tree_place;
+struct terra_trunk_override;
+typedef struct terra_line_trees_in {
+	const float *zvals;                  /* [n][S+2][S+2] */
+	const terra_tile_stats *stats;       /* [n] */
+	const uint8_t *is_distant;           /* [n] or NULL */
+	const struct terra_tree_place *pine; /* [n][pine_capacity] or NULL */
+	const uint32_t *pine_counts;         /* [n] or NULL */
+	const struct terra_trunk_override *trunk_override; /* [n][pine_capacity] or NULL */
+	uint32_t pine_capacity;
+	int32_t dxoff, dyoff;                /* xoff - xoff2, yoff - yoff2 */
+	int32_t ptree_xoff2, ptree_yoff2;    /* what the placement ran with */
+	float tree_depth_scale;
+} terra_line_trees_in;      /* 72 bytes */
+typedef struct terra_line_tree_hit {
+	float t;            /* the winning tn, 2 on a miss */
+	int32_t tile;       /* batch index, -1 on a miss */
+	int32_t xpos, ypos; /* mesh indices of the hit cell; 0 for a tree */
+	float p_int[3];     /* v1 + t*(v2 - v1) */
+	uint32_t hit;       /* TERRA_LINE_HIT_* */
+	int32_t tree;       /* record index in the tile, -1 unless a tree was hit */
+	uint32_t part;      /* 0 trunk_cylin, 1 the leaf cone */
+} terra_line_tree_hit;      /* 40 bytes */
+enum {TERRA_LINE_HIT_NONE = 0, TERRA_LINE_HIT_MESH = 1, TERRA_LINE_HIT_TREE = 2};
+int  terra_tiles_line_intersect_trees_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_line_trees_in *in,
+                                          const float *d_lines, const int32_t *d_line_tile, uint32_t nlines, terra_line_tree_hit *d_hits);
+int  terra_tiles_line_intersect_trees(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_line_trees_in *in,
+                                      const float *h_lines, const int32_t *h_line_tile, uint32_t nlines, terra_line_tree_hit *h_hits);
+
 /* ---- tree map of a tile batch (every supported tile size S): what the fire modes "Add Trees" / "Remove Trees" (src/tiled_mesh.cpp:3998-4002) leave for the terrain
  * to do.  tile_t::register_tree_change (:3789-3794) clears tree_map and forces the textures to be re-made; tile_t::pre_draw (:1900-1907) then runs apply_tree_ao_shadows,
  * create_texture and check_shadow_map_and_normal_texture.  The three calls below are the terrain side of those steps; trees themselves (generation, drawing,
@@ -1605,7 +1659,7 @@ int  terra_tiles_decid_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, 
  * s_plant::check_sphere_coll (:772-775), sphere_vert_cylin_intersect (src/Math3d.cpp:427-437, without its asserts), sphere_cube_intersect (:930-935), dist_less_than,
  * dist_xy_less_than, contains_pt_exp, is_zero_area, contains_pt_xy, get_norm(); tree_cont_t::check_cube_int and tree::check_cube_int (src/Tree.cpp:296-309).
  * 1.001*rsum, 0.9*br_scale*base_radius, 0.2*height, 0.1*height and 0.1*radius are formed in double and narrowed where the source narrows them.
- * Line queries with inc_trees = 1 (they need line_intersect_trunc_cone) are not part of this: they stay with the engine.
+ * Line queries with inc_trees = 1 (line_intersect_trunc_cone against the pine cylinders) are terra_tiles_line_intersect_trees[_dev], beside the line queries above.
  *
  * What a query sees, as in the reference.  Every hit moves the centre and every later object sees the moved centre, within a container and across containers:
  * pine / palm, then deciduous, then scenery; nothing ends early.  The scenery is walked by kind -- rock_shapes, surface_rocks, voxel_rocks, rocks, (logs: no

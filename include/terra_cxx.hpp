@@ -223,6 +223,40 @@ inline bool line_intersect_tiled_mesh(tile_batch_dev_t const &b, float const v1[
 	if (h.hit) {p_int[0] = h.p_int[0]; p_int[1] = h.p_int[1]; p_int[2] = h.p_int[2];}
 	return h.hit != 0;
 }
+// The same with the reference's inc_trees argument: inc_trees != 0 adds the pine records of `trees` (terra_tiles_line_intersect_trees_dev).  Of `trees` the device
+// arrays pine / pine_counts / trunk_override, pine_capacity, ptree_xoff2 / ptree_yoff2 and tree_depth_scale are the caller's; zvals, stats, is_distant, dxoff and
+// dyoff are taken from the batch.  With inc_trees == 0 the record's first 32 bytes are tiles_line_intersect's and no tree is looked at
+inline terra_line_tree_hit tiles_line_intersect(tile_batch_dev_t const &b, terra_line_trees_in const &trees, float const v1[3], float const v2[3], float inc_trees, int only_tile = -1) {
+	struct io_t {float line[6]; int32_t only; int32_t pad; terra_line_tree_hit hit;};
+	static void *d_io = [] {void *p = nullptr; check(terra_malloc(default_ctx(), &p, sizeof(io_t)), "terra_malloc"); return p;}();
+	io_t const in = {{v1[0], v1[1], v1[2], v2[0], v2[1], v2[2]}, only_tile, 0, {}};
+	io_t *d = (io_t *)d_io;
+	terra_line_trees_in a = trees;
+	a.zvals = b.d_zvals; a.stats = b.d_stats; a.is_distant = b.d_is_distant; a.dxoff = b.dxoff; a.dyoff = b.dyoff;
+	if (inc_trees == 0.0f) {a.pine = nullptr; a.pine_counts = nullptr; a.trunk_override = nullptr; a.pine_capacity = 0;}
+	check(terra_memcpy_h2d(default_ctx(), d, &in, offsetof(io_t, hit)), "line_intersect_mesh");
+	check(terra_tiles_line_intersect_trees_dev(default_ctx(), b.tile_xy, b.n, &a, d->line, &d->only, 1, &d->hit), "line_intersect_mesh");
+	terra_line_tree_hit h;
+	check(terra_memcpy_d2h(default_ctx(), &h, &d->hit, sizeof(h)), "line_intersect_mesh");
+	return h;
+}
+// tile_draw_t::line_intersect_mesh(v1, v2, t, intersected_tile, xpos, ypos, inc_trees): a tree hit leaves xpos / ypos at 0, as the reference's new_xpos / new_ypos
+inline bool tile_draw_line_intersect_mesh(tile_batch_dev_t const &b, terra_line_trees_in const &trees, float const v1[3], float const v2[3], float &t, int &tile, int &xpos, int &ypos,
+	float inc_trees, terra_line_tree_hit *hit_out = nullptr)
+{
+	terra_line_tree_hit const h = tiles_line_intersect(b, trees, v1, v2, inc_trees);
+	t = h.t;
+	tile = h.tile;
+	if (h.hit) {xpos = h.xpos; ypos = h.ypos;}
+	if (hit_out) {*hit_out = h;}
+	return h.hit != 0;
+}
+// line_intersect_tiled_mesh(v1, v2, p_int, inc_trees) (src/tiled_mesh.cpp:3954-3957): what the hit-scan weapon path calls with inc_trees = 1 (src/Gameplay.cpp:2143)
+inline bool line_intersect_tiled_mesh(tile_batch_dev_t const &b, terra_line_trees_in const &trees, float const v1[3], float const v2[3], float p_int[3], float inc_trees) {
+	terra_line_tree_hit const h = tiles_line_intersect(b, trees, v1, v2, inc_trees);
+	if (h.hit) {p_int[0] = h.p_int[0]; p_int[1] = h.p_int[1]; p_int[2] = h.p_int[2];}
+	return h.hit != 0;
+}
 // ---- sphere collisions and tree box tests against the resident containers (terra_tiles_sphere_collide_dev / terra_tiles_cube_int_trees_dev): `in` holds the device
 // arrays of the three containers as the placements left them.  The one-query forms below go through a staging buffer of the process, like tiles_line_intersect; a
 // frame's queries (the player, the physics objects, the animals) are better collected and asked in one terra_tiles_sphere_collide_dev call.

@@ -12,7 +12,7 @@ MUST_NOT_SPILL = [("speculative_erosion", "wave_scratch_t"),  # k_waves<trace la
                   ("k_terrain_view_tiles", ""), ("k_terrain_view_occluders", ""), ("k_terrain_view_occlusion", ""), ("k_terrain_view_lists", ""), ("k_terrain_view_rank", ""),
                   ("k_reflect_walk", ""), ("k_reflect_finish", ""), ("k_water_view", ""),
                   ("k_cloud_mark", ""), ("k_cloud_tiles", ""), ("k_cloud_tail", ""), ("k_cloud_view", ""), ("k_cloud_rank", ""),
-                  ("k_sphere_collide", ""), ("k_cube_int_trees", ""),
+                  ("k_sphere_collide", ""), ("k_cube_int_trees", ""), ("k_line_tree_boxes", ""), ("k_line_intersect_trees", ""),
                   ("k_tree_view", ""), ("k_scenery_view", ""), ("k_decid_view", ""),
                   ("k_smap_plan", ""), ("k_smap_geom", ""), ("k_smap_casters", "")]  # (k_smap_plan matches k_smap_plan_lists and k_smap_plan_rank too)
 # k_reflect_walk: instruction selection leaves two dead temporaries (1 and 4 bytes) in its frame, so its private segment is 8 bytes that no instruction reads or
