@@ -9,7 +9,8 @@
 // calls (tiled_mesh.cpp and Textures.cpp are mostly renderer: -ffunction-sections + --gc-sections drop everything the exported
 // harness does not reach, the link then needs a dozen libGL no-ops instead of hundreds of stubs), and (3) exports a plain C harness ("ref_*") that ctypes can drive.
 // The tile rows are the reference's own members: tile_t::create_zvals, calc_mesh_ao_lighting, create_texture (+ add_grass_block_at, update_terrain_params),
-// upload_normal_texture / get_norm, and get_tids / update_lttex_ix / gen_tex_height_tables / get_bare_ls_tid from Textures.cpp.
+// upload_normal_texture / get_norm, add_tree_ao_shadow, upload_shadow_map_texture, line_intersect_mesh, add_or_remove_grass_at, and get_tids / update_lttex_ix /
+// gen_tex_height_tables / get_bare_ls_tid from Textures.cpp.
 //
 // The handful of functions that live in TUs we cannot build are restated here, each with its citation:
 //   set_scene_constants   src/matrix_ops.cpp:59-84
@@ -668,6 +669,117 @@ REF_API float ref_tile_normals(float const *zvals, unsigned char *rgba /*129*129
 	// upload_normal_texture's vector is gone by now; glTexImage2D was called while it was alive -- copy there instead
 	memcpy(rgba, ref_upload_copy.data(), 4*129*129);
 	return b.t->min_normal_z;
+}
+
+// ---- five more members whose whole body lies in tiled_mesh.o: add_tree_ao_shadow (src/tiled_mesh.cpp:749-783), upload_shadow_map_texture (:882-913), the existing-weights
+// branch of create_texture (:1322-1350), line_intersect_mesh with inc_trees = 0 (:2176-2207) and add_or_remove_grass_at (:3845-3948).  Each export sets the members the
+// function reads, calls the member itself and copies the member data out; the vectors ~ref_tile_box_t does not know are destroyed by hand.
+int ground_effects_level(2); // src/3DWorld.cpp: mesh_shadows_enabled() reads it
+float light_factor(1.0);     // src/3DWorld.cpp: the engine's sun / moon balance
+typedef vector<tile_t::tree_map_val> shim_tree_map_t; typedef vector<unsigned char> shim_bytes_t;
+static void shim_set_tree_map(tile_t *t, unsigned char const *tm) {
+	static_assert(sizeof(tile_t::tree_map_val) == 2, "tree_map_val is {ao, sh}");
+	t->tree_map.resize(t->stride*t->stride);
+	memcpy((void *)t->tree_map.data(), tm, 2*t->stride*t->stride);
+}
+// splats: n x {x, y, radius}; tm: 129*129*2 bytes {ao, sh}, in and out; flags out: sun_shadows_invalid, moon_shadows_invalid, recalc_tree_grass_weights
+REF_API void ref_tile_tree_map(int tx, int ty, float const *splats, unsigned n, int has_any_grass, unsigned char *tm, int *flags) {
+	ref_tile_box_t b(tx, ty);
+	shim_set_tree_map(b.t, tm);
+	b.t->sun_shadows_invalid = b.t->moon_shadows_invalid = b.t->recalc_tree_grass_weights = 0;
+	b.t->has_any_grass = (has_any_grass != 0);
+	for (unsigned i = 0; i < n; ++i) {b.t->add_tree_ao_shadow(point(splats[3*i], splats[3*i+1], 0.0), splats[3*i+2], 1);} // no_adj_test: there is no adjacent tile
+	memcpy(tm, b.t->tree_map.data(), 2*b.t->stride*b.t->stride);
+	flags[0] = b.t->sun_shadows_invalid; flags[1] = b.t->moon_shadows_invalid; flags[2] = b.t->recalc_tree_grass_weights;
+	b.t->tree_map.~shim_tree_map_t();
+}
+// sun / moon: 130*130 mask bytes, ao: 129*129, tm: 129*129*2; a null input leaves that vector empty.  rgba: the 129*129*4 bytes handed to glTexImage2D
+REF_API void ref_tile_shadow_texture(float lf, int gel, unsigned char const *sun, unsigned char const *moon, unsigned char const *ao, unsigned char const *tm, unsigned char *rgba) {
+	ref_tile_box_t b(0, 0);
+	unsigned const W(b.t->stride), Z(b.t->zvsize);
+	float const lf0(light_factor); int const gel0(ground_effects_level);
+	light_factor = lf; ground_effects_level = gel;
+	if (sun)  {b.t->smask[LIGHT_SUN ].assign(sun,  sun  + Z*Z);}
+	if (moon) {b.t->smask[LIGHT_MOON].assign(moon, moon + Z*Z);}
+	if (ao)   {b.t->ao_lighting.assign(ao, ao + W*W);}
+	if (tm)   {shim_set_tree_map(b.t, tm);}
+	ref_upload_copy.clear();
+	b.t->upload_shadow_map_texture(0);
+	light_factor = lf0; ground_effects_level = gel0;
+	if (ref_upload_copy.size() != (size_t)4*W*W) {ref_unreachable("upload_shadow_map_texture without a stride x stride upload");}
+	memcpy(rgba, ref_upload_copy.data(), 4*W*W);
+	b.t->smask[0].~shim_bytes_t(); b.t->smask[1].~shim_bytes_t(); b.t->tree_map.~shim_tree_map_t();
+}
+// mw: mesh_weight_data, 129*129*4; tm: 129*129*2 or null (no tree map); out: weight_data
+REF_API void ref_tile_tree_weights(unsigned char const *mw, unsigned char const *tm, unsigned char *out) {
+	if (textures.size() < 256) {textures.resize(256);} // see ref_tile_create_weights
+	ref_tile_box_t b(0, 0);
+	unsigned const W(b.t->stride), Z(b.t->zvsize);
+	b.t->zvals.assign(Z*Z, 0.0f);
+	b.t->weight_tid = 1; b.t->weights_tsize = W; b.t->recalc_tree_grass_weights = 1; // weights exist: create_texture takes its "use existing weights" branch
+	b.t->mesh_weight_data.assign(mw, mw + 4*W*W);
+	if (tm) {shim_set_tree_map(b.t, tm);}
+	mesh_xy_grid_cache_t height_gen;
+	b.t->create_texture(height_gen);
+	memcpy(out, b.t->weight_data.data(), 4*W*W);
+	b.t->tree_map.~shim_tree_map_t();
+}
+// lines: n x {v1, v2}; t is preset to 1.0 per line as tile_draw_t::line_intersect_mesh's callers do; xpos / ypos are left 0 on a miss
+REF_API void ref_tile_line_intersect(int tx, int ty, float const *zvals, float mzmin, float mzmax, int is_distant, float const *lines, unsigned n,
+	unsigned char *hit, float *t, int *xpos, int *ypos)
+{
+	ref_tile_box_t b(tx, ty);
+	b.set_zvals(zvals);
+	b.t->mzmin = mzmin; b.t->mzmax = mzmax; b.t->is_distant = (is_distant != 0);
+	for (unsigned i = 0; i < n; ++i) {
+		float const *v(lines + 6*i);
+		float tt(1.0); int xp(0), yp(0);
+		hit[i] = b.t->line_intersect_mesh(point(v[0], v[1], v[2]), point(v[3], v[4], v[5]), tt, xp, yp, 0.0);
+		t[i] = tt; xpos[i] = xp; ypos[i] = yp;
+	}
+}
+bool small_tree_group::line_intersect(point const &, point const &, float *) const {ref_unreachable("small_tree_group::line_intersect"); return 0;} // inc_trees = 0 never gets there
+// the two flower calls add_or_remove_grass_at ends with (src/grass.cpp, a file that is not built) only record their arguments
+struct ref_flower_calls_t {int n_update, n_clear; unsigned wd_stride; int x1, y1, xl, yl, xh, yh; float pos[3], radius; int is_square;};
+static ref_flower_calls_t shim_flower_calls;
+void flower_tile_manager_t::update_subrange(vector<unsigned char> const &, unsigned wd_stride, int x1, int y1, int xl, int yl, int xh, int yh) {
+	ref_flower_calls_t &c(shim_flower_calls);
+	++c.n_update; c.wd_stride = wd_stride; c.x1 = x1; c.y1 = y1; c.xl = xl; c.yl = yl; c.xh = xh; c.yh = yh;
+}
+void flower_tile_manager_t::clear_within(point const &pos, float radius, bool is_square) {
+	ref_flower_calls_t &c(shim_flower_calls);
+	++c.n_clear; c.pos[0] = pos.x; c.pos[1] = pos.y; c.pos[2] = pos.z; c.radius = radius; c.is_square = is_square;
+}
+// mz: {mzmin, mzmax, radius} as create_zvals leaves them (src/tiled_mesh.cpp:537-541; mesh_sphere_intersect reads all three); weights: weight_data 129*129*4, in and out; blocks: 32*32, in and out (all ix == 0: the empty vector); has_flowers: the tile holds a flower
+// (a removal calls clear_within only then); pos: the brush centre.  Returns add_or_remove_grass_at's bool
+REF_API int ref_tile_grass_brush(int tx, int ty, float const *zvals, float const *mz, unsigned char *weights, ref_grass_block_t *blocks, int *has_any_grass, int has_flowers,
+	float const *pos, float radius, int add, int shape, float brush_weight, ref_flower_calls_t *calls)
+{
+	if (textures.size() < 256) {textures.resize(256);} // see ref_tile_create_weights
+	ref_tile_box_t b(tx, ty);
+	unsigned const W(b.t->stride), nblocks(32*32);
+	b.set_zvals(zvals);
+	b.t->mzmin = mz[0]; b.t->mzmax = mz[1]; b.t->radius = mz[2];
+	if (enable_terrain_env) {b.t->update_terrain_params();} // what create_zvals does before (src/tiled_mesh.cpp:471)
+	b.t->weight_tid = 1; b.t->weights_tsize = W; b.t->has_any_grass = (*has_any_grass != 0);
+	b.t->weight_data.assign(weights, weights + 4*W*W);
+	bool any_block(0);
+	for (unsigned i = 0; i < nblocks; ++i) {any_block |= (blocks[i].ix != 0);}
+	if (any_block) {
+		b.t->grass_blocks.resize(nblocks);
+		for (unsigned i = 0; i < nblocks; ++i) {b.t->grass_blocks[i].ix = blocks[i].ix; b.t->grass_blocks[i].zmin = blocks[i].zmin; b.t->grass_blocks[i].zmax = blocks[i].zmax;}
+	}
+	if (has_flowers) {b.t->flowers.flowers.resize(1);}
+	memset(&shim_flower_calls, 0, sizeof(shim_flower_calls));
+	int const ret(b.t->add_or_remove_grass_at(point(pos[0], pos[1], pos[2]), radius, (add != 0), shape, brush_weight));
+	memcpy(weights, b.t->weight_data.data(), 4*W*W);
+	memset(blocks, 0, nblocks*sizeof(ref_grass_block_t));
+	for (unsigned i = 0; i < b.t->grass_blocks.size() && i < nblocks; ++i) {blocks[i].ix = b.t->grass_blocks[i].ix; blocks[i].zmin = b.t->grass_blocks[i].zmin; blocks[i].zmax = b.t->grass_blocks[i].zmax;}
+	*has_any_grass = b.t->has_any_grass;
+	*calls = shim_flower_calls;
+	typedef vector<flower_manager_t::flower_t> shim_flowers_t;
+	b.t->flowers.flowers.~shim_flowers_t();
+	return ret;
 }
 
 // ---- row f2: mesh shadows.  calc_mesh_shadows / mesh_shadow_gen are the reference's own code (src/visibility.cpp:411-517, do_line_clip from src/Math3d.cpp:1070);

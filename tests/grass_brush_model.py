@@ -9,6 +9,8 @@
 Every float expression is evaluated in float32 in the reference's order (x86-64 SSE2, no fused multiply-add); where the C++ promotes to double the model uses a
 Python float.  The oracle supplies the primitives it exports: the SINF / COSF table (orc.sin_table), the biome parameters (orc.tile_terrain_params) and the scene
 state (orc.state).  powf is the C library's own, as in the reference.
+This reading is confirmed against the compiler's output: tests/test_tile_members_ref.py compares the model, weights, blocks, return value and the arguments of the
+two flower calls, with the compiled tile_t::add_or_remove_grass_at (oracle/ref_shim.cpp section 4).
 """
 import ctypes as C
 

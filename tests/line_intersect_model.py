@@ -10,6 +10,8 @@
 Every float statement is evaluated in float32 in the reference's order (x86-64 SSE2, no fused multiply-add); where the C++ promotes to double the model uses
 float64.  Conversions to int are x86's cvttsd2si (INT_MIN when out of range or NaN) and int arithmetic wraps at 32 bits, as in the reference binary.  The model
 works on arrays of (line, tile) pairs so that it can check tens of thousands of lines against a 64 x 64 batch; each array statement is the scalar statement it cites.
+This reading is confirmed against the compiler's output: tests/test_tile_members_ref.py compares the model with the compiled tile_t::line_intersect_mesh
+(oracle/ref_shim.cpp section 4) on lines built around the box's faces, get_xpos' ties and the zero denominator.
 """
 import numpy as np
 

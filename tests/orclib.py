@@ -81,6 +81,16 @@ def make_mods(rows):
 
 
 GRASS_BLOCK_DTYPE = np.dtype([("ix", np.uint32), ("zmin", np.float32), ("zmax", np.float32)])
+LINE_REF_DTYPE = np.dtype([("hit", np.uint8), ("t", np.float32), ("xpos", np.int32), ("ypos", np.int32)])  # what tile_t::line_intersect_mesh returns and writes
+
+
+class FlowerCalls(C.Structure):
+    """ref_flower_calls_t: what add_or_remove_grass_at handed to flower_tile_manager_t::update_subrange (n_update, wd_stride .. yh) and clear_within (n_clear, pos ..)"""
+    _fields_ = [("n_update", C.c_int), ("n_clear", C.c_int), ("wd_stride", C.c_uint), ("x1", C.c_int), ("y1", C.c_int), ("xl", C.c_int), ("yl", C.c_int),
+                ("xh", C.c_int), ("yh", C.c_int), ("pos", C.c_float * 3), ("radius", C.c_float), ("is_square", C.c_int)]
+
+    def as_tuple(self):
+        return (self.n_update, self.n_clear, self.wd_stride, self.x1, self.y1, self.xl, self.yl, self.xh, self.yh, tuple(self.pos), self.radius, self.is_square)
 
 
 def make_config(mesh_gen_mode=0, mesh_gen_shape=0, mesh_seed=1, mesh_freq_filter=0, hmap=None, glaciate=1, mesh_scale=1.0,
@@ -118,6 +128,12 @@ def engine_lib(which):
     emulation library or against libterra_hip.so (oracle/Makefile: engine); None when it was not built (no /root/reference here and nothing prebuilt)"""
     p = os.path.join(ORACLE_DIR, "_ref", f"libengine_{which}.so")
     return p if os.path.exists(p) else None
+
+
+def ref_source_available():
+    """the reference tree oracle/Makefile compiles from ($(REF), default /root/reference) is on this machine: `make -C oracle ref` then rebuilds oracle/_ref from
+    the harness in the tree, otherwise it leaves whatever prebuilt library is there"""
+    return os.path.isdir(os.path.join(os.environ.get("REF", "/root/reference"), "src"))
 
 
 def ref_available():
@@ -220,6 +236,14 @@ class Checker:
             f("lod_steep_dist", None, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p])
             f("convert_floats", None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p])
             f("convert_doubles", None, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p])
+        # five more tile_t members from the reference's own object file (oracle/ref_shim.cpp section 4): tree map, shadow texture, tree weights, line query, grass brush
+        if kind == "ref" and hasattr(self.lib, "ref_tile_tree_map"):
+            f("tile_tree_map", None, [C.c_int, C.c_int, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_void_p])
+            f("tile_shadow_texture", None, [C.c_float, C.c_int] + [C.c_void_p] * 5)
+            f("tile_tree_weights", None, [C.c_void_p] * 3)
+            f("tile_line_intersect", None, [C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_uint] + [C.c_void_p] * 4)
+            f("tile_grass_brush", C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_float,
+                                            C.c_int, C.c_int, C.c_float, C.POINTER(FlowerCalls)])
         if kind == "orc":
             f("apply_erosion_stats", None, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(ErosionStats), C.c_void_p])
 
@@ -471,6 +495,62 @@ class Checker:
         out = np.zeros(420, np.float32)
         self._voxel_rdata(rseed1, rseed2, mag, freq, out.ctypes.data)
         return out
+
+    # ---- tile_t members beyond the heightmap chain ("ref" only): one 128-cell tile per call
+    def has_tile_members(self):
+        """False for a library built from a harness without these exports"""
+        return hasattr(self, "_tile_tree_map")
+
+    def tile_tree_map(self, tx, ty, splats, tree_map, has_any_grass=False):
+        """tile_t::add_tree_ao_shadow(point(x, y, 0), radius, 1) for every row of splats [n, 3] in order, on a copy of tree_map u8 [129, 129, 2]
+        -> (tree_map, (sun_shadows_invalid, moon_shadows_invalid, recalc_tree_grass_weights))"""
+        sp = np.ascontiguousarray(splats, np.float32).reshape(-1, 3)
+        tm = np.ascontiguousarray(tree_map, np.uint8).reshape(129, 129, 2).copy()
+        flags = np.zeros(3, np.int32)
+        self._tile_tree_map(tx, ty, sp.ctypes.data, len(sp), int(bool(has_any_grass)), tm.ctypes.data, flags.ctypes.data)
+        return tm, tuple(bool(v) for v in flags)
+
+    def tile_shadow_texture(self, light_factor, ground_effects_level, sun=None, moon=None, ao=None, tree_map=None):
+        """tile_t::upload_shadow_map_texture(0): sun / moon u8 [130, 130], ao u8 [129, 129], tree_map u8 [129, 129, 2]; None leaves the vector empty -> u8 [129, 129, 4]"""
+        arrs = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in (sun, moon, ao, tree_map)]
+        for a, size in zip(arrs, (130 * 130, 130 * 130, 129 * 129, 129 * 129 * 2)):
+            assert a is None or a.size == size
+        out = np.zeros((129, 129, 4), np.uint8)
+        self._tile_shadow_texture(light_factor, ground_effects_level, *[None if a is None else a.ctypes.data for a in arrs], out.ctypes.data)
+        return out
+
+    def tile_tree_weights(self, mesh_weights, tree_map=None):
+        """tile_t::create_texture's existing-weights branch: mesh_weights u8 [129, 129, 4], tree_map u8 [129, 129, 2] or None -> weight_data"""
+        mw = np.ascontiguousarray(mesh_weights, np.uint8).reshape(129, 129, 4)
+        tm = None if tree_map is None else np.ascontiguousarray(tree_map, np.uint8).reshape(129, 129, 2)
+        out = np.zeros((129, 129, 4), np.uint8)
+        self._tile_tree_weights(mw.ctypes.data, None if tm is None else tm.ctypes.data, out.ctypes.data)
+        return out
+
+    def tile_line_intersect(self, tx, ty, zvals, mzmin, mzmax, lines, is_distant=False):
+        """tile_t::line_intersect_mesh(v1, v2, t = 1.0, xpos, ypos, 0.0) for every row of lines [n, 2, 3] -> LINE_REF_DTYPE [n]"""
+        z = np.ascontiguousarray(zvals, np.float32).reshape(130, 130)
+        ln = np.ascontiguousarray(lines, np.float32).reshape(-1, 6)
+        assert np.isfinite(ln).all()  # the member asserts
+        n = len(ln)
+        hit, t, xp, yp = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._tile_line_intersect(tx, ty, z.ctypes.data, mzmin, mzmax, int(bool(is_distant)), ln.ctypes.data, n, hit.ctypes.data, t.ctypes.data, xp.ctypes.data, yp.ctypes.data)
+        out = np.zeros(n, LINE_REF_DTYPE)
+        out["hit"], out["t"], out["xpos"], out["ypos"] = hit, t, xp, yp
+        return out
+
+    def tile_grass_brush(self, tx, ty, zvals, mzmin, mzmax, tile_radius, weights, blocks, pos, radius, add, shape, brush_weight, has_any_grass=False, has_flowers=False):
+        """tile_t::add_or_remove_grass_at on copies of weights u8 [129, 129, 4] and blocks [32, 32] GRASS_BLOCK_DTYPE (update_terrain_params first under enable_terrain_env);
+        mzmin, mzmax, tile_radius: the members create_zvals leaves and mesh_sphere_intersect reads
+        -> (returned bool, weights, blocks, has_any_grass, FlowerCalls)"""
+        z = np.ascontiguousarray(zvals, np.float32).reshape(130, 130)
+        w = np.ascontiguousarray(weights, np.uint8).reshape(129, 129, 4).copy()
+        gb = np.ascontiguousarray(blocks, GRASS_BLOCK_DTYPE).reshape(32, 32).copy()
+        mz, p = np.array([mzmin, mzmax, tile_radius], np.float32), np.ascontiguousarray(pos, np.float32).reshape(3)
+        hg, calls = C.c_int(int(bool(has_any_grass))), FlowerCalls()
+        ret = self._tile_grass_brush(tx, ty, z.ctypes.data, mz.ctypes.data, w.ctypes.data, gb.ctypes.data, C.byref(hg), int(bool(has_flowers)), p.ctypes.data, radius,
+                                     int(bool(add)), int(shape), brush_weight, C.byref(calls))
+        return bool(ret), w, gb, bool(hg.value), calls
 
     # ---- the shared primitives ("ref" only)
     def pdu_make(self, pos, dir, up, angle, aspect, near, far):

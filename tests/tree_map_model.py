@@ -18,6 +18,9 @@ sum are double and the result is rounded to float once, by the initialisation.  
 (src/3DWorld.h:13, src/inlines.h:8), and g++'s <math.h> declares std::sqrt's overloads in the global namespace, so sqrt(float) is the float overload: the root is
 rounded to float first and enters the double expression as that float.  scale (:754) is `float const scale(0.6/rval)`: a double division rounded to float.
 
+This reading -- the overloads and promotions above, and those of the two textures -- is confirmed against the compiler's output: tests/test_tile_members_ref.py
+compares this model, every byte, with tile_t's own compiled members (oracle/ref_shim.cpp section 4), on maps where a double sqrt or float products would change a byte.
+
 The scene constants (DX_VAL, DY_VAL, X_SCENE_SIZE, Y_SCENE_SIZE) come from the oracle's state (orclib.Checker.state()), not from the library under test.
 """
 import numpy as np
