@@ -980,6 +980,27 @@ int terra_view_behind_sphere_mult(float angle, float aspect, float *out) {
 	*out = terra::view_behind_sphere_mult(angle, aspect);
 	return TERRA_OK;
 }
+// the host form of the terrain view (ra null) and of the reflection view (ta null): `h` holds the caller's arrays
+static int terra_terrain_lists_host(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, terra::view_pod_t const &v, terra::terrain_view_args_pod_t const *ta,
+                                    terra::reflection_view_args_pod_t const *ra, terra::terrain_view_io_t const &h) {
+	TERRA_TRY
+		if (ra) {ctx->eng.reflection_view_check(v, *ra);} else {ctx->eng.terrain_view_check(v, *ta);} // the scene, the tile size, the view and the args: before anything is staged
+		if (!terra::terrain_view_io_check(ra ? "tiles_reflection_view" : "tiles_terrain_view", tile_xy, n, h, false)) return TERRA_OK;
+		terra_stage st(ctx->eng);
+		int const s = st.in(h.in.stats, (size_t)n*sizeof(terra_tile_stats)), mn = st.opt_in(h.in.min_normal_z, (size_t)n*4), tr = st.opt_in(h.in.trmax, (size_t)n*4),
+			tz = st.opt_in(h.in.tile_zmax, (size_t)n*4), fl = st.opt_in(h.in.flags, n), os = st.inout(h.in.occl_state, n, h.in.occl_state != nullptr), su = st.out(h.status, n),
+			di = st.out(h.dist, (size_t)n*4), lo = st.out(h.lod, n), cr = st.out(h.crack, (size_t)n*4), dr = st.temp((size_t)n*4), oc = st.temp((size_t)n*4), cn = st.temp(8),
+			nd = st.opt_out(h.not_drawn, n), rf = st.opt_out(h.reflect, n);
+		st.begin();
+		terra::terrain_view_io_t const io = {{st.dev<terra_tile_stats>(s), st.dev<float>(mn), st.dev<float>(tr), st.dev<float>(tz), st.dev<uint8_t>(fl), st.dev<uint8_t>(os)}, st.dev<uint8_t>(su),
+			st.dev<float>(di), st.dev<uint8_t>(lo), st.dev<uint8_t>(cr), st.dev<uint32_t>(dr), st.dev<uint32_t>(oc), st.dev<uint32_t>(cn), st.dev<uint8_t>(nd), st.dev<uint8_t>(rf)};
+		if (ra) {ctx->eng.tiles_reflection_view_dev(tile_xy, n, dxoff, dyoff, v, *ra, io);} else {ctx->eng.tiles_terrain_view_dev(tile_xy, n, dxoff, dyoff, v, *ta, io);}
+		st.end();
+		st.end_counted(dr, cn, h.draw_order, h.counts, 1, n); // the lists' entries past their counts stay as the caller had them
+		ctx->eng.be.d2h(h.counts + 1, st.dev<uint32_t>(cn) + 1, 4);
+		if (h.counts[1]) {ctx->eng.be.d2h(h.occluded, st.dev<uint32_t>(oc), (size_t)std::min(h.counts[1], n)*4);}
+	TERRA_CATCH
+}
 int terra_tiles_terrain_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_terrain_view_args *args,
                                  const terra_tile_stats *d_stats, const float *d_min_normal_z, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags,
                                  uint8_t *d_occl_state, uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded,
@@ -987,8 +1008,8 @@ int terra_tiles_terrain_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::terrain_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_terrain_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_flags, d_occl_state},
-		d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn); TERRA_CATCH
+	TERRA_TRY ctx->eng.tiles_terrain_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_io_t{{d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_flags, d_occl_state}, d_status, d_dist, d_lod,
+		d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, nullptr}); TERRA_CATCH
 }
 int terra_tiles_terrain_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_terrain_view_args *args,
                              const terra_tile_stats *h_stats, const float *h_min_normal_z, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags,
@@ -997,23 +1018,8 @@ int terra_tiles_terrain_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n,
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::terrain_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY
-		ctx->eng.terrain_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_stats || !h_status || !h_dist || !h_lod || !h_crack || !h_draw_order || !h_occluded || !h_counts) return terra::fail(TERRA_ERR_ARG, "null argument");
-		terra_stage st(ctx->eng);
-		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), mn = st.opt_in(h_min_normal_z, (size_t)n*4), tr = st.opt_in(h_trmax, (size_t)n*4),
-			tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n), os = st.inout(h_occl_state, n, h_occl_state != nullptr), su = st.out(h_status, n),
-			di = st.out(h_dist, (size_t)n*4), lo = st.out(h_lod, n), cr = st.out(h_crack, (size_t)n*4), dr = st.temp((size_t)n*4), oc = st.temp((size_t)n*4), cn = st.temp(8), nd = st.opt_out(h_not_drawn, n);
-		st.begin();
-		ctx->eng.tiles_terrain_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{st.dev<terra_tile_stats>(s), st.dev<float>(mn), st.dev<float>(tr), st.dev<float>(tz),
-			st.dev<uint8_t>(fl), st.dev<uint8_t>(os)}, st.dev<uint8_t>(su), st.dev<float>(di), st.dev<uint8_t>(lo), st.dev<uint8_t>(cr), st.dev<uint32_t>(dr), st.dev<uint32_t>(oc),
-			st.dev<uint32_t>(cn), st.dev<uint8_t>(nd));
-		st.end();
-		st.end_counted(dr, cn, h_draw_order, h_counts, 1, n); // the lists' entries past their counts stay as the caller had them
-		ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);
-		if (h_counts[1]) {ctx->eng.be.d2h(h_occluded, st.dev<uint32_t>(oc), (size_t)std::min(h_counts[1], n)*4);}
-	TERRA_CATCH
+	return terra_terrain_lists_host(ctx, tile_xy, n, dxoff, dyoff, v, &a, nullptr, {{h_stats, h_min_normal_z, h_trmax, h_tile_zmax, h_flags, h_occl_state}, h_status, h_dist, h_lod, h_crack,
+		h_draw_order, h_occluded, h_counts, h_not_drawn, nullptr});
 }
 static_assert(sizeof(terra_reflection_view_args) == sizeof(terra::reflection_view_args_pod_t) && sizeof(terra_reflection_view_args) == 24, "terra_reflection_view_args layout");
 static_assert(sizeof(terra_water_view_args) == sizeof(terra::water_view_args_pod_t) && sizeof(terra_water_view_args) == 8, "terra_water_view_args layout");
@@ -1024,8 +1030,8 @@ int terra_tiles_reflection_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::reflection_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_reflection_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_flags, d_occl_state},
-		d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_reflect); TERRA_CATCH
+	TERRA_TRY ctx->eng.tiles_reflection_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_io_t{{d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_flags, d_occl_state}, d_status, d_dist, d_lod,
+		d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_reflect}); TERRA_CATCH
 }
 int terra_tiles_reflection_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view,
                                 const terra_reflection_view_args *args, const terra_tile_stats *h_stats, const float *h_min_normal_z, const float *h_trmax,
@@ -1034,24 +1040,8 @@ int terra_tiles_reflection_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::reflection_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY
-		ctx->eng.reflection_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_stats || !h_status || !h_dist || !h_lod || !h_crack || !h_draw_order || !h_occluded || !h_counts) return terra::fail(TERRA_ERR_ARG, "null argument");
-		terra_stage st(ctx->eng);
-		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), mn = st.opt_in(h_min_normal_z, (size_t)n*4), tr = st.opt_in(h_trmax, (size_t)n*4),
-			tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n), os = st.inout(h_occl_state, n, h_occl_state != nullptr), su = st.out(h_status, n),
-			di = st.out(h_dist, (size_t)n*4), lo = st.out(h_lod, n), cr = st.out(h_crack, (size_t)n*4), dr = st.temp((size_t)n*4), oc = st.temp((size_t)n*4), cn = st.temp(8),
-			nd = st.opt_out(h_not_drawn, n), rf = st.opt_out(h_reflect, n);
-		st.begin();
-		ctx->eng.tiles_reflection_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{st.dev<terra_tile_stats>(s), st.dev<float>(mn), st.dev<float>(tr), st.dev<float>(tz),
-			st.dev<uint8_t>(fl), st.dev<uint8_t>(os)}, st.dev<uint8_t>(su), st.dev<float>(di), st.dev<uint8_t>(lo), st.dev<uint8_t>(cr), st.dev<uint32_t>(dr), st.dev<uint32_t>(oc),
-			st.dev<uint32_t>(cn), st.dev<uint8_t>(nd), st.dev<uint8_t>(rf));
-		st.end();
-		st.end_counted(dr, cn, h_draw_order, h_counts, 1, n); // the lists' entries past their counts stay as the caller had them
-		ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);
-		if (h_counts[1]) {ctx->eng.be.d2h(h_occluded, st.dev<uint32_t>(oc), (size_t)std::min(h_counts[1], n)*4);}
-	TERRA_CATCH
+	return terra_terrain_lists_host(ctx, tile_xy, n, dxoff, dyoff, v, nullptr, &a, {{h_stats, h_min_normal_z, h_trmax, h_tile_zmax, h_flags, h_occl_state}, h_status, h_dist, h_lod, h_crack,
+		h_draw_order, h_occluded, h_counts, h_not_drawn, h_reflect});
 }
 int terra_tiles_water_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_water_view_args *args,
                                const terra_tile_stats *d_stats, const float *d_trmax, const float *d_tile_zmax, const uint8_t *d_flags, const uint8_t *d_status,
@@ -1059,8 +1049,8 @@ int terra_tiles_water_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::water_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_water_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{d_stats, nullptr, d_trmax, d_tile_zmax, d_flags, nullptr}, d_status, d_water_list,
-		d_cap_mask, d_counts); TERRA_CATCH
+	terra::water_view_io_t const io = {{d_stats, nullptr, d_trmax, d_tile_zmax, d_flags, nullptr}, d_status, d_water_list, d_cap_mask, d_counts};
+	TERRA_TRY ctx->eng.tiles_water_view_dev(tile_xy, n, dxoff, dyoff, v, a, io); TERRA_CATCH
 }
 int terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, int32_t dxoff, int32_t dyoff, const terra_view *view, const terra_water_view_args *args,
                            const terra_tile_stats *h_stats, const float *h_trmax, const float *h_tile_zmax, const uint8_t *h_flags, const uint8_t *h_status,
@@ -1070,15 +1060,13 @@ int terra_tiles_water_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, i
 	terra::water_view_args_pod_t a; memcpy(&a, args, sizeof(a));
 	TERRA_TRY
 		ctx->eng.water_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
-		if ((h_status != nullptr) != (h_cap_mask != nullptr)) return terra::fail(TERRA_ERR_ARG, "tiles_water_view: status and cap_mask are both null or both given");
-		if (n == 0) return TERRA_OK;
-		if (!tile_xy || !h_stats || !h_water_list || !h_counts) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if (!terra::water_view_io_check(tile_xy, n, {{h_stats, nullptr, h_trmax, h_tile_zmax, h_flags, nullptr}, h_status, h_water_list, h_cap_mask, h_counts}, false)) return TERRA_OK;
 		terra_stage st(ctx->eng);
 		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), tr = st.opt_in(h_trmax, (size_t)n*4), tz = st.opt_in(h_tile_zmax, (size_t)n*4), fl = st.opt_in(h_flags, n),
 			su = st.opt_in(h_status, n), wl = st.temp((size_t)n*4), cm = st.opt_out(h_cap_mask, n), cn = st.temp(8);
 		st.begin();
-		ctx->eng.tiles_water_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::terrain_view_in_t{st.dev<terra_tile_stats>(s), nullptr, st.dev<float>(tr), st.dev<float>(tz), st.dev<uint8_t>(fl),
-			nullptr}, st.dev<uint8_t>(su), st.dev<uint32_t>(wl), st.dev<uint8_t>(cm), st.dev<uint32_t>(cn));
+		ctx->eng.tiles_water_view_dev(tile_xy, n, dxoff, dyoff, v, a, terra::water_view_io_t{{st.dev<terra_tile_stats>(s), nullptr, st.dev<float>(tr), st.dev<float>(tz), st.dev<uint8_t>(fl), nullptr},
+			st.dev<uint8_t>(su), st.dev<uint32_t>(wl), st.dev<uint8_t>(cm), st.dev<uint32_t>(cn)});
 		st.end();
 		st.end_counted(wl, cn, h_water_list, h_counts, 1, n); // the list's entries past its count stay as the caller had them
 		if (h_status) {ctx->eng.be.d2h(h_counts + 1, st.dev<uint32_t>(cn) + 1, 4);}
@@ -1181,7 +1169,7 @@ int terra_tiles_update_clouds_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32
                                   uint32_t capacity, uint32_t *d_total) {
 	TERRA_CHECK_CTX if (!step) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::cloud_step_pod_t s; memcpy(&s, step, sizeof(s));
-	TERRA_TRY ctx->eng.tiles_update_clouds_dev(tile_xy, n, s, (terra::cloud_tile_pod_t *)d_state, (terra::cloud_pod_t *)d_clouds, capacity, d_total); TERRA_CATCH
+	TERRA_TRY ctx->eng.tiles_update_clouds_dev(tile_xy, n, s, capacity, terra::cloud_update_io_t{(terra::cloud_tile_pod_t *)d_state, (terra::cloud_pod_t *)d_clouds, d_total}); TERRA_CATCH
 }
 int terra_tiles_update_clouds(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_cloud_step *step, terra_cloud_tile *h_state, terra_cloud *h_clouds,
                               uint32_t capacity, uint32_t *h_total) {
@@ -1189,12 +1177,11 @@ int terra_tiles_update_clouds(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n
 	terra::cloud_step_pod_t s; memcpy(&s, step, sizeof(s));
 	TERRA_TRY
 		ctx->eng.cloud_update_check(s, capacity); // the scene, the tile size, the step and the capacity: before anything is staged
-		if (n == 0) {if (h_total) {*h_total = 0u;} return TERRA_OK;}
-		if (!tile_xy || !h_state || (capacity && !h_clouds)) return terra::fail(TERRA_ERR_ARG, "null argument");
+		if (!terra::cloud_update_io_check(tile_xy, n, capacity, {(terra::cloud_tile_pod_t *)h_state, (terra::cloud_pod_t *)h_clouds, h_total}, false)) {if (h_total) {*h_total = 0u;} return TERRA_OK;}
 		terra_stage st(ctx->eng);
 		int const ss = st.inout(h_state, (size_t)n*sizeof(terra_cloud_tile)), cl = st.inout(h_clouds, (size_t)n*capacity*sizeof(terra_cloud), capacity != 0), to = st.opt_out(h_total, 4);
 		st.begin();
-		ctx->eng.tiles_update_clouds_dev(tile_xy, n, s, st.dev<terra::cloud_tile_pod_t>(ss), st.dev<terra::cloud_pod_t>(cl), capacity, st.dev<uint32_t>(to));
+		ctx->eng.tiles_update_clouds_dev(tile_xy, n, s, capacity, terra::cloud_update_io_t{st.dev<terra::cloud_tile_pod_t>(ss), st.dev<terra::cloud_pod_t>(cl), st.dev<uint32_t>(to)});
 		st.end();
 	TERRA_CATCH
 }
@@ -1203,8 +1190,8 @@ int terra_tiles_cloud_view_dev(terra_ctx *ctx, const int32_t *tile_xy, uint32_t 
 	TERRA_CHECK_CTX if (!view || !args) return terra::fail(TERRA_ERR_ARG, "null argument");
 	terra::view_pod_t v; memcpy(&v, view, sizeof(v));
 	terra::cloud_view_args_pod_t a; memcpy(&a, args, sizeof(a));
-	TERRA_TRY ctx->eng.tiles_cloud_view_dev(tile_xy, n, v, a, d_stats, (terra::cloud_tile_pod_t const *)d_state, (terra::cloud_pod_t const *)d_clouds, capacity, d_stage,
-		(terra::cloud_inst_pod_t *)d_list, d_list_count); TERRA_CATCH
+	terra::cloud_view_io_t const io = {d_stats, (terra::cloud_tile_pod_t const *)d_state, (terra::cloud_pod_t const *)d_clouds, d_stage, (terra::cloud_inst_pod_t *)d_list, d_list_count};
+	TERRA_TRY ctx->eng.tiles_cloud_view_dev(tile_xy, n, v, a, capacity, io); TERRA_CATCH
 }
 int terra_tiles_cloud_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, const terra_view *view, const terra_cloud_view_args *args, const terra_tile_stats *h_stats,
                            const terra_cloud_tile *h_state, const terra_cloud *h_clouds, uint32_t capacity, uint8_t *h_stage, terra_cloud_inst *h_list, uint32_t *h_list_count) {
@@ -1213,15 +1200,15 @@ int terra_tiles_cloud_view(terra_ctx *ctx, const int32_t *tile_xy, uint32_t n, c
 	terra::cloud_view_args_pod_t a; memcpy(&a, args, sizeof(a));
 	TERRA_TRY
 		ctx->eng.cloud_view_check(v, a); // the scene, the tile size, the view and the args: before anything is staged
-		if (n == 0) {if (h_list_count) {*h_list_count = 0u;} return TERRA_OK;}
+		terra::cloud_view_io_t const h = {h_stats, (terra::cloud_tile_pod_t const *)h_state, (terra::cloud_pod_t const *)h_clouds, h_stage, (terra::cloud_inst_pod_t *)h_list, h_list_count};
+		if (!terra::cloud_view_io_check(tile_xy, n, capacity, h, false)) {if (h_list_count) {*h_list_count = 0u;} return TERRA_OK;}
 		size_t const nrec = (size_t)n*capacity;
-		if (!tile_xy || !h_stats || !h_state || !h_list_count || (nrec && (!h_clouds || !h_stage || !h_list))) return terra::fail(TERRA_ERR_ARG, "null argument");
 		terra_stage st(ctx->eng);
 		int const s = st.in(h_stats, (size_t)n*sizeof(terra_tile_stats)), ss = st.in(h_state, (size_t)n*sizeof(terra_cloud_tile)), cl = st.add(h_clouds, nullptr, nrec*sizeof(terra_cloud), nrec != 0),
 			sg = st.add(nullptr, h_stage, nrec, nrec != 0), li = st.add(nullptr, nullptr, nrec*sizeof(terra_cloud_inst), nrec != 0), lc = st.out(h_list_count, 4);
 		st.begin();
-		ctx->eng.tiles_cloud_view_dev(tile_xy, n, v, a, st.dev<terra_tile_stats>(s), st.dev<terra::cloud_tile_pod_t>(ss), st.dev<terra::cloud_pod_t>(cl), capacity, st.dev<uint8_t>(sg),
-			st.dev<terra::cloud_inst_pod_t>(li), st.dev<uint32_t>(lc));
+		ctx->eng.tiles_cloud_view_dev(tile_xy, n, v, a, capacity, terra::cloud_view_io_t{st.dev<terra_tile_stats>(s), st.dev<terra::cloud_tile_pod_t>(ss), st.dev<terra::cloud_pod_t>(cl),
+			st.dev<uint8_t>(sg), st.dev<terra::cloud_inst_pod_t>(li), st.dev<uint32_t>(lc)});
 		st.end();
 		if (*h_list_count) {ctx->eng.be.d2h(h_list, st.dev<terra_cloud_inst>(li), (size_t)*h_list_count*sizeof(terra_cloud_inst));} // the entries past the count stay as the caller had them
 	TERRA_CATCH

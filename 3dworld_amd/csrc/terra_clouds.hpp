@@ -21,6 +21,9 @@
 #pragma once
 #include "terra_view.hpp"
 #include "terra_treeplace.hpp"
+#include "terra_stage.hpp"
+#include "../../include/terra.h" // terra_tile_stats
+#include <stdexcept>
 
 namespace terra {
 
@@ -182,6 +185,25 @@ TERRA_HD void cloud_update_tile(cloud_consts_t const &c, int32_t const *tile_xy,
 	}
 	cloud_gen(c, state[t], recs, tile_xy[2*t], tile_xy[2*t+1]);
 }
+// ---- the arrays of an update call, in the order of terra_tiles_update_clouds[_dev]: host pointers in the host form's first record, device pointers everywhere else
+struct cloud_update_io_t {cloud_tile_pod_t *state; cloud_pod_t *clouds; uint32_t *total;};
+// the argument rules of a call, behind cloud_update_check: throws what the call refuses; false: n == 0, nothing to do but total = 0 (the caller's).  dev: the arrays are the device's
+inline bool cloud_update_io_check(int32_t const *tile_xy, uint32_t n, uint32_t capacity, cloud_update_io_t const &io, bool dev) {
+	if (dev && (((uintptr_t)io.state & 7u) != 0 || ((((uintptr_t)io.clouds | (uintptr_t)io.total)) & 3u) != 0)) throw std::invalid_argument(
+		"tiles_update_clouds: d_state must be 8-byte aligned, d_clouds and d_total 4-byte aligned");
+	if (n == 0) return false;
+	if (!tile_xy || !io.state || (capacity && !io.clouds)) throw std::invalid_argument("tiles_update_clouds: null argument");
+	return true;
+}
+// scratch: the coordinates, the neighbour table; for the kernels the marks of cloud_path and the marked tiles in batch order
+struct cloud_update_scratch_t {int32_t *txy, *nbr; uint32_t *marks, *order;};
+inline void cloud_update_scratch_add(stage_layout_t &lay, cloud_update_scratch_t &s, uint32_t n) {lay.add(s.txy, (size_t)n*2); lay.add(s.nbr, (size_t)n*9); lay.add(s.marks, ((size_t)n + 3)/4); lay.add(s.order, n);}
+// the literal body of the simple form: one thread, the reference's loop over the batch in order
+TERRA_HD void cloud_update_literal(cloud_consts_t const &c, cloud_update_io_t const &io, cloud_update_scratch_t const &s, uint32_t n) {
+	uint32_t num = 0;
+	for (uint32_t t = 0; t < n; ++t) {cloud_update_tile(c, s.txy, s.nbr, io.state, io.clouds, t); num += io.state[t].count;}
+	if (io.total) {*io.total = num;}
+}
 // the path of record i of tile t through this call: mark(u) for the tile it leaves and the tile that takes it.  Every hop but the last goes to a later tile
 TERRA_HD void cloud_path(cloud_consts_t const &c, int32_t const *nbr, cloud_tile_pod_t const *state, cloud_pod_t r, uint32_t t, uint32_t n, uint8_t *touched) {
 	uint32_t cur = t;
@@ -251,6 +273,48 @@ TERRA_HD bool cloud_inst_before(cloud_inst_pod_t const &a, cloud_inst_pod_t cons
 	if (a.dist_sq < b.dist_sq) return true;
 	if (b.dist_sq < a.dist_sq) return false;
 	return a.tile < b.tile || (a.tile == b.tile && a.slot < b.slot);
+}
+
+// ---- the arrays of a view call, in the order of terra_tiles_cloud_view[_dev]
+struct cloud_view_io_t {terra_tile_stats const *stats; cloud_tile_pod_t const *state; cloud_pod_t const *clouds; uint8_t *stage; cloud_inst_pod_t *list; uint32_t *list_count;};
+// the argument rules of a call, behind cloud_view_check: throws what the call refuses; false: n == 0, nothing to do but list_count = 0 (the caller's).  dev: the arrays are the device's
+inline bool cloud_view_io_check(int32_t const *tile_xy, uint32_t n, uint32_t capacity, cloud_view_io_t const &io, bool dev) {
+	if (dev && (((uintptr_t)io.state & 7u) != 0 || ((((uintptr_t)io.stats | (uintptr_t)io.clouds | (uintptr_t)io.list | (uintptr_t)io.list_count)) & 3u) != 0)) throw std::invalid_argument(
+		"tiles_cloud_view: d_state must be 8-byte aligned, d_stats, d_clouds, d_list and d_list_count 4-byte aligned");
+	if (n == 0) return false;
+	size_t const nrec = (size_t)n*capacity;
+	if (!tile_xy || !io.stats || !io.state || !io.list_count || (nrec && (!io.clouds || !io.stage || !io.list))) throw std::invalid_argument("tiles_cloud_view: null argument");
+	if (nrec > 0x7FFFFFFFu) throw std::invalid_argument("tiles_cloud_view: n*capacity must be below 2^31");
+	return true;
+}
+// scratch: get_exact_zval's constants (read from memory), the instances by slot and then in the order they were listed, their number
+struct cloud_view_scratch_t {tree_place_consts_t *tc; cloud_inst_pod_t *by_slot, *found; uint32_t *cnt;};
+inline void cloud_view_scratch_add(stage_layout_t &lay, cloud_view_scratch_t &s, size_t nrec) {lay.add(s.tc, 1); lay.add(s.by_slot, nrec); lay.add(s.found, nrec); lay.add(s.cnt, 4);}
+// the literal bodies of the simple form.  (1) a logical thread per record slot: get_draw_list's decision
+TERRA_HD void cloud_view_slot_literal(cloud_view_consts_t const &c, cloud_view_io_t const &io, cloud_view_scratch_t const &s, size_t i) {
+	uint32_t const t = (uint32_t)(i/c.capacity), k = (uint32_t)(i%c.capacity);
+	uint32_t stg = CLV_NONE;
+	if (k < io.state[t].count) {
+		cloud_inst_pod_t o; o.tile = t; o.slot = k;
+		stg = cloud_view_record(c, io.clouds[i], io.stats[t].mzmin, io.stats[t].mzmax, [&](float x, float y) {return tree_exact_zval(*s.tc, x, y);}, o);
+		if (stg == CLV_LISTED) {s.by_slot[i] = o;}
+	}
+	io.stage[i] = (uint8_t)stg;
+}
+// (2) one thread: to_draw_clouds as the loop of :3491 fills it, in batch order
+TERRA_HD void cloud_view_found_literal(cloud_view_io_t const &io, cloud_view_scratch_t const &s, size_t nrec) {
+	uint32_t cnt = 0;
+	for (size_t i = 0; i < nrec; ++i) {if (io.stage[i] == CLV_LISTED) {s.found[cnt++] = s.by_slot[i];}}
+	*s.cnt = cnt; *io.list_count = cnt;
+}
+// (3) a logical thread per record slot: the sort of :3493 -- an entry's place is its rank
+TERRA_HD void cloud_view_rank_literal(cloud_view_io_t const &io, cloud_view_scratch_t const &s, size_t i) {
+	uint32_t const cnt = *s.cnt;
+	if (i >= cnt) return;
+	cloud_inst_pod_t const me = s.found[i];
+	uint32_t rank = 0;
+	for (uint32_t j = 0; j < cnt; ++j) {rank += cloud_inst_before(s.found[j], me) ? 1u : 0u;}
+	io.list[rank] = me;
 }
 
 } // namespace terra

@@ -3094,83 +3094,22 @@ template<class BE> struct terra_engine {
 		if (a.reflection_pass == 1) throw std::invalid_argument("tiles_terrain_view: reflection_pass 1 needs can_have_reflection: it is terra_tiles_reflection_view's");
 		if (a.reflection_pass < 0 || a.reflection_pass > 3) throw std::invalid_argument("tiles_terrain_view: reflection_pass must be 0, 2 or 3");
 	}
-	// the last step of the simple forms of the terrain view and the reflection view, a thread per tile: its cracks, and its place in its list -- the rank of
-	// (dist, batch index) among the drawn tiles is where the sort of :2915 puts it
-	void terrain_view_lists_simple(uint32_t n, int32_t const *d_nbr, uint8_t const *d_status, float const *d_dist, uint8_t const *d_lod, uint8_t *d_crack, uint32_t *d_draw_order,
-		uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn)
-	{
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			uint32_t const me = d_status[t] & TV_STATUS_MASK;
-			for (uint32_t k = 0; k < 4; ++k) {
-				int32_t const u = d_nbr[t*9 + terrain_view_nbr_slot(k >> 1, k & 1u)];
-				bool const adj = me == TV_DRAWN && u >= 0 && (d_status[u] & TV_STATUS_MASK) != TV_ABSENT;
-				d_crack[t*4 + k] = adj ? (uint8_t)terrain_view_crack_index(k >> 1, k & 1u, d_lod[t], d_lod[u]) : TERRAIN_VIEW_NO_CRACK;
-			}
-			if (d_not_drawn) {d_not_drawn[t] = (me != TV_DRAWN) ? 1 : 0;}
-			if (me == TV_DRAWN) {
-				uint32_t rank = 0;
-				for (uint32_t u = 0; u < n; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_DRAWN && terrain_view_before(d_dist[u], u, d_dist[t], (uint32_t)t)) ? 1u : 0u;}
-				d_draw_order[rank] = (uint32_t)t;
-			}
-			else if (me == TV_OCCLUDED) {
-				uint32_t rank = 0;
-				for (uint32_t u = 0; u < t; ++u) {rank += ((d_status[u] & TV_STATUS_MASK) == TV_OCCLUDED) ? 1u : 0u;}
-				d_occluded[rank] = (uint32_t)t;
-			}
-			if (t == 0) {
-				uint32_t nd = 0, no = 0;
-				for (uint32_t u = 0; u < n; ++u) {uint32_t const su = d_status[u] & TV_STATUS_MASK; nd += (su == TV_DRAWN) ? 1u : 0u; no += (su == TV_OCCLUDED) ? 1u : 0u;}
-				d_counts[0] = nd; d_counts[1] = no;
-			}
-		});
-	}
-	void tiles_terrain_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, terrain_view_args_pod_t const &a, terrain_view_in_t const &in,
-		uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn)
-	{
+	void tiles_terrain_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, terrain_view_args_pod_t const &a, terrain_view_io_t const &io) {
 		terrain_view_check(view, a);
-		if (n == 0) return;
-		if (!tile_xy || !in.stats || !d_status || !d_dist || !d_lod || !d_crack || !d_draw_order || !d_occluded || !d_counts) throw std::invalid_argument("tiles_terrain_view: null argument");
-		if ((((uintptr_t)in.stats | (uintptr_t)in.min_normal_z | (uintptr_t)in.trmax | (uintptr_t)in.tile_zmax | (uintptr_t)d_dist | (uintptr_t)d_draw_order | (uintptr_t)d_occluded |
-		      (uintptr_t)d_counts) & 3u) != 0) throw std::invalid_argument("tiles_terrain_view: d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_dist, d_draw_order, d_occluded and d_counts must be 4-byte aligned");
+		if (!terrain_view_io_check("tiles_terrain_view", tile_xy, n, io, true)) return;
 		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_terrain_view");
 		terrain_view_consts_t const c = terrain_view_consts(view, a, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
-		// scratch: the coordinates and the neighbour table, the occluders of the batch in batch order with their count, the candidates that run the occlusion test, and
-		// the (dist, batch index) keys of the drawn tiles in batch order for the order's second path
-		int32_t *d_txy, *d_nbr_w; terrain_view_occluder_t *d_occ; uint32_t *d_nocc, *d_key_tile; uint8_t *d_test; float *d_keys;
-		stage_layout_t lay;
-		lay.add(d_occ, n); lay.add(d_txy, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_nocc, 4); lay.add(d_keys, n); lay.add(d_key_tile, n); lay.add(d_test, n);
+		terrain_view_scratch_t s = {}; stage_layout_t lay;
+		terrain_view_scratch_add(lay, s, n);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
-		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
-		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
-		int32_t const *d_nbr = d_nbr_w;
-		if constexpr (BE::has_kernels) {if (be.tile_terrain_view(c, in, d_txy, d_nbr, n, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_occ, d_nocc, d_test, d_keys, d_key_tile)) return;}
-		// the simple form.  (1) a logical thread per tile: everything but the occlusion test, the cracks and the lists
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			terrain_view_tile_t const o = terrain_view_tile(c, in, d_txy, t);
-			d_status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); d_dist[t] = o.dist; d_lod[t] = o.lod; d_test[t] = o.test;
-		});
-		// (2) one thread: the occluders in batch order, as the loop of :2858-2861 leaves them
-		be.launch(1, [=] TERRA_LAMBDA (size_t) {
-			uint32_t m = 0;
-			for (uint32_t t = 0; t < n; ++t) {
-				if (!(d_status[t] & TV_WAS_OCCLUDER)) continue;
-				terrain_view_geom_t const g = terrain_view_geom_of(c, in, d_txy, t);
-				terrain_view_occluder_t &o = d_occ[m++];
-				terrain_view_mesh_box(g, in.stats[t].mzmin, in.stats[t].mzmax, o.bc);
-				for (uint32_t s = 0; s < 16; ++s) {terrain_view_occluder_column(c, g, in.stats[t], s, o.sub[s]);}
-				o.tile = (int32_t)t; o.pad = 0;
-			}
-			*d_nocc = m;
-		});
-		// (3) a thread per tile: the loop of :2872-2908
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			uint32_t const nocc = *d_nocc;
-			if ((d_status[t] & TV_STATUS_MASK) != TV_DRAWN || !d_test[t] || nocc == 0) return;
-			bool const occluded = terrain_view_occluded(c, terrain_view_geom_of(c, in, d_txy, t), in.stats[t], d_occ, nocc, (int32_t)t);
-			if (occluded) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
-			if (in.occl_state) {in.occl_state[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED;} // set_last_occluded (:2906)
-		});
-		terrain_view_lists_simple(n, d_nbr, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn); // (4) the cracks and the lists
+		be.h2d_async(s.txy, tile_xy, (size_t)n*8);
+		be.h2d_async(s.nbr, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		if constexpr (BE::has_kernels) {if (be.tile_terrain_view(c, io, s, n)) return;}
+		// the simple form (terra_terrainview.hpp): (1) a logical thread per tile, (2) one thread: the occluders, (3) a thread per tile: the occlusion test, (4) the cracks and the lists
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {terrain_view_tile_literal(c, io, s, t);});
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {terrain_view_occluders_literal(c, io, s, n);});
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {terrain_view_occlusion_literal(c, io, s, t);});
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {terrain_view_lists_literal(io, s, n, t);});
 	}
 
 	// ---- the terrain draw list of reflection pass 1 (terra_waterview.hpp): tile_draw_t::draw(1) -- the loop above with the filter of :2869, can_have_reflection
@@ -3194,74 +3133,26 @@ template<class BE> struct terra_engine {
 		b.x0 = (int32_t)x0; b.y0 = (int32_t)y0; b.w = (uint32_t)w; b.nwords = (uint32_t)((w*h + 31)/32); b.cap = (uint32_t)(w + h + 2);
 		return b;
 	}
-	void tiles_reflection_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, reflection_view_args_pod_t const &a, terrain_view_in_t const &in,
-		uint8_t *d_status, float *d_dist, uint8_t *d_lod, uint8_t *d_crack, uint32_t *d_draw_order, uint32_t *d_occluded, uint32_t *d_counts, uint8_t *d_not_drawn, uint8_t *d_reflect)
-	{
+	void tiles_reflection_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, reflection_view_args_pod_t const &a, terrain_view_io_t const &io) {
 		reflection_view_check(view, a);
-		if (n == 0) return;
-		if (!tile_xy || !in.stats || !d_status || !d_dist || !d_lod || !d_crack || !d_draw_order || !d_occluded || !d_counts) throw std::invalid_argument("tiles_reflection_view: null argument");
-		if ((((uintptr_t)in.stats | (uintptr_t)in.min_normal_z | (uintptr_t)in.trmax | (uintptr_t)in.tile_zmax | (uintptr_t)d_dist | (uintptr_t)d_draw_order | (uintptr_t)d_occluded |
-		      (uintptr_t)d_counts) & 3u) != 0) throw std::invalid_argument("tiles_reflection_view: d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_dist, d_draw_order, d_occluded and d_counts must be 4-byte aligned");
+		if (!terrain_view_io_check("tiles_reflection_view", tile_xy, n, io, true)) return;
 		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_reflection_view");
 		reflect_box_t const box = reflection_view_box(tile_xy, n);
 		reflect_consts_t rc;
 		rc.tv = terrain_view_consts(view, a.tv, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
 		rc.zmin = a.tv.occluder_zmin; rc.zmax = a.zmax;
-		terrain_view_consts_t const c = rc.tv;
-		// scratch: that of the terrain view, and per tile what the walk reads of it (reflect_tile_t), the provisional result of the occlusion test, the answer of :2869; for the simple form the
-		// state of last_occluded as the loop goes, the marks of the walk (the start tile's index + 1) and its work list; the constants for k_reflect_walk
-		int32_t *d_txy, *d_nbr_w, *d_work; terrain_view_occluder_t *d_occ; uint32_t *d_nocc, *d_key_tile, *d_mark; uint8_t *d_test, *d_prov, *d_refl, *d_state; float *d_keys; reflect_consts_t *d_rc; reflect_tile_t *d_rt;
-		stage_layout_t lay;
-		lay.add(d_rc, 1); lay.add(d_rt, n); lay.add(d_occ, n); lay.add(d_txy, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_nocc, 4); lay.add(d_keys, n); lay.add(d_key_tile, n); lay.add(d_mark, n); lay.add(d_work, n);
-		lay.add(d_test, n); lay.add(d_prov, n); lay.add(d_refl, n); lay.add(d_state, n);
+		terrain_view_scratch_t s = {}; stage_layout_t lay;
+		reflection_view_scratch_add(lay, s, n);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
-		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
-		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
-		be.h2d_async(d_rc, &rc, sizeof(rc)); // (k_reflect_walk reads the constants from memory)
-		int32_t const *d_nbr = d_nbr_w;
-		if constexpr (BE::has_kernels) {
-			if (be.tile_reflection_view(rc, d_rc, in, d_txy, d_nbr, n, box, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn, d_reflect, d_occ, d_nocc, d_test,
-				d_keys, d_key_tile, d_rt, d_prov, d_refl)) return;
-		}
-		// the simple form.  (1) a logical thread per tile: everything but :2869, the occlusion test, the cracks and the lists
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {
-			terrain_view_tile_t const o = terrain_view_tile(c, in, d_txy, t);
-			d_status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); d_dist[t] = o.dist; d_lod[t] = o.lod; d_test[t] = o.test; d_rt[t] = reflect_tile(c, in, d_txy, t, o.visible != 0);
-			d_state[t] = in.occl_state ? in.occl_state[t] : (uint8_t)TV_STATE_NONE; d_mark[t] = 0u;
-			if (d_reflect) {d_reflect[t] = RF_NOT_ASKED;}
-		});
-		// (2) one thread: the occluders in batch order, then the loop of :2863 as written, in batch order: a tile's walk sees what the turns before it left of last_occluded
-		be.launch(1, [=] TERRA_LAMBDA (size_t) {
-			uint32_t nocc = 0;
-			for (uint32_t t = 0; t < n; ++t) {
-				if (!(d_status[t] & TV_WAS_OCCLUDER)) continue;
-				terrain_view_geom_t const g = terrain_view_geom_of(c, in, d_txy, t);
-				terrain_view_occluder_t &o = d_occ[nocc++];
-				terrain_view_mesh_box(g, in.stats[t].mzmin, in.stats[t].mzmax, o.bc);
-				for (uint32_t s = 0; s < 16; ++s) {terrain_view_occluder_column(c, g, in.stats[t], s, o.sub[s]);}
-				o.tile = (int32_t)t; o.pad = 0;
-			}
-			*d_nocc = nocc;
-			for (uint32_t t = 0; t < n; ++t) {
-				if ((d_status[t] & TV_STATUS_MASK) != TV_DRAWN) continue;
-				terrain_view_geom_t const g = terrain_view_geom_of(c, in, d_txy, t);
-				uint32_t r = reflect_without_walk(c, d_rt[t].flags);
-				if (r == RF_NOT_ASKED) {
-					reflect_corners_t const k = reflect_corners(c, g.bc, in.stats[t].mzmax);
-					auto seen = [&](uint32_t u) {bool const was = d_mark[u] == t + 1u; d_mark[u] = t + 1u; return was;};
-					auto occluded = [&](uint32_t u) {return d_state[u] == TV_STATE_OCCLUDED;};
-					r = reflect_walk(rc, in.stats, d_nbr, d_rt, t, k, d_work, n, seen, occluded, [](reflect_corners_t &) {}) ? RF_WALK_FOUND : RF_WALK_NOTHING;
-				}
-				if (d_reflect) {d_reflect[t] = (uint8_t)r;}
-				if (r < RF_HAS_WATER) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_NO_REFLECTION); continue;} // :2869
-				if (!d_test[t] || nocc == 0) continue;
-				bool const occluded_now = terrain_view_occluded(c, g, in.stats[t], d_occ, nocc, (int32_t)t);
-				if (occluded_now) {d_status[t] = (uint8_t)((d_status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
-				d_state[t] = occluded_now ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED; // set_last_occluded (:2906)
-				if (in.occl_state) {in.occl_state[t] = d_state[t];}
-			}
-		});
-		terrain_view_lists_simple(n, d_nbr, d_status, d_dist, d_lod, d_crack, d_draw_order, d_occluded, d_counts, d_not_drawn); // (3) the cracks and the lists
+		be.h2d_async(s.txy, tile_xy, (size_t)n*8);
+		be.h2d_async(s.nbr, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		be.h2d_async(s.rc, &rc, sizeof(rc)); // (k_reflect_walk reads the constants from memory)
+		if constexpr (BE::has_kernels) {if (be.tile_reflection_view(rc, box, io, s, n)) return;}
+		// the simple form (terra_waterview.hpp): (1) a logical thread per tile, (2) one thread: the occluders and the loop of :2863 in batch order, (3) the cracks and the lists
+		terrain_view_consts_t const c = rc.tv;
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {reflection_view_tile_literal(c, io, s, t);});
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {reflection_view_loop_literal(c, rc, io, s, n);});
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {terrain_view_lists_literal(io, s, n, t);});
 	}
 
 	// ---- water quads and water caps of a batch (terra_waterview.hpp): tile_t::is_water_visible (src/tiled_mesh.cpp:2131-2133) for every tile as tile_draw_t::draw_water
@@ -3273,42 +3164,21 @@ template<class BE> struct terra_engine {
 		if (!view_finite(view)) throw std::invalid_argument("tiles_water_view: a member of the view is not finite");
 		if (!isfinite(a.behind_sphere_mult)) throw std::invalid_argument("tiles_water_view: a member of the args is not finite");
 	}
-	void tiles_water_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, water_view_args_pod_t const &a, terrain_view_in_t const &in,
-		uint8_t const *d_status, uint32_t *d_water_list, uint8_t *d_cap_mask, uint32_t *d_counts)
-	{
+	void tiles_water_view_dev(int32_t const *tile_xy, uint32_t n, int dxoff, int dyoff, view_pod_t const &view, water_view_args_pod_t const &a, water_view_io_t const &io) {
 		water_view_check(view, a);
-		if ((d_status != nullptr) != (d_cap_mask != nullptr)) throw std::invalid_argument("tiles_water_view: status and cap_mask are both null or both given");
-		if (n == 0) return;
-		if (!tile_xy || !in.stats || !d_water_list || !d_counts) throw std::invalid_argument("tiles_water_view: null argument");
-		if ((((uintptr_t)in.stats | (uintptr_t)in.trmax | (uintptr_t)in.tile_zmax | (uintptr_t)d_water_list | (uintptr_t)d_counts) & 3u) != 0) {
-			throw std::invalid_argument("tiles_water_view: d_stats, d_trmax, d_tile_zmax, d_water_list and d_counts must be 4-byte aligned");
-		}
+		if (!water_view_io_check(tile_xy, n, io, true)) return;
 		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_water_view");
 		terrain_view_args_pod_t const ta = {a.behind_sphere_mult, 0.0f, a.water_enabled, 0, 0};
 		terrain_view_consts_t const c = terrain_view_consts(view, ta, cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), dxoff, dyoff, water_plane_z);
-		int32_t *d_txy, *d_nbr_w; uint8_t *d_wv; // scratch: the coordinates, the neighbour table, and what the pass keeps of a tile (WV_*)
-		stage_layout_t lay;
-		lay.add(d_txy, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_wv, n);
+		water_view_scratch_t s; stage_layout_t lay;
+		water_view_scratch_add(lay, s, n);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
-		be.h2d_async(d_txy, tile_xy, (size_t)n*8);
-		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
-		int32_t const *d_nbr = d_nbr_w;
-		if constexpr (BE::has_kernels) {if (be.tile_water_view(c, in, d_txy, d_nbr, n, d_status, d_wv, d_water_list, d_cap_mask, d_counts)) return;}
-		// the simple form.  (1) a logical thread per tile: what is_water_visible() and a neighbour's draw_water_cap read of it
-		be.launch(n, [=] TERRA_LAMBDA (size_t t) {d_wv[t] = (uint8_t)water_view_tile(c, in, d_txy, t);});
-		// (2) one thread: tile_draw_t::draw_water's loop in batch order, then the caps
-		be.launch(1, [=] TERRA_LAMBDA (size_t) {
-			uint32_t nw = 0, nc = 0;
-			for (uint32_t t = 0; t < n; ++t) {if (water_view_listed(d_wv[t])) {d_water_list[nw++] = t;}}
-			d_counts[0] = nw;
-			if (!d_status) return;
-			for (uint32_t t = 0; t < n; ++t) {
-				uint32_t const m = water_view_caps(c, d_wv[t], d_status[t], d_nbr, d_wv, t);
-				d_cap_mask[t] = (uint8_t)m;
-				nc += m ? 1u : 0u;
-			}
-			d_counts[1] = nc;
-		});
+		be.h2d_async(s.txy, tile_xy, (size_t)n*8);
+		be.h2d_async(s.nbr, nbr.data(), (size_t)n*9*sizeof(int32_t));
+		if constexpr (BE::has_kernels) {if (be.tile_water_view(c, io, s, n)) return;}
+		// the simple form.  (1) a logical thread per tile: what is_water_visible() and a neighbour's draw_water_cap read of it; (2) one thread: the list and the caps
+		be.launch(n, [=] TERRA_LAMBDA (size_t t) {s.wv[t] = (uint8_t)water_view_tile(c, io.in, s.txy, t);});
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {water_view_lists_literal(c, io, s, n);});
 	}
 
 	// ---- the shadow-map plan of a batch (terra_smapview.hpp): tile_t::update_range's deletion (src/tiled_mesh.cpp:1416), the shadow part of tile_draw_t::pre_draw's loop
@@ -3381,33 +3251,22 @@ template<class BE> struct terra_engine {
 		if (!isfinite(s.wind[0]) || !isfinite(s.wind[1]) || !isfinite(s.wind[2]) || !isfinite(s.fticks)) throw std::invalid_argument("tiles_update_clouds: a member of the step is not finite");
 		if (capacity == 0 && cp.clouds_per_tile > 0.0f) throw std::invalid_argument("tiles_update_clouds: capacity is 0 and clouds_per_tile is not");
 	}
-	void tiles_update_clouds_dev(int32_t const *tile_xy, uint32_t n, cloud_step_pod_t const &s, cloud_tile_pod_t *d_state, cloud_pod_t *d_clouds, uint32_t capacity, uint32_t *d_total) {
-		cloud_update_check(s, capacity);
-		if (((uintptr_t)d_state & 7u) != 0 || ((((uintptr_t)d_clouds | (uintptr_t)d_total)) & 3u) != 0) {
-			throw std::invalid_argument("tiles_update_clouds: d_state must be 8-byte aligned, d_clouds and d_total 4-byte aligned");
-		}
-		if (n == 0) {if (d_total) {be.fill32(d_total, 0u, 1);} return;}
-		if (!tile_xy || !d_state || (capacity && !d_clouds)) throw std::invalid_argument("tiles_update_clouds: null argument");
+	void tiles_update_clouds_dev(int32_t const *tile_xy, uint32_t n, cloud_step_pod_t const &step, uint32_t capacity, cloud_update_io_t const &io) {
+		cloud_update_check(step, capacity);
+		if (!cloud_update_io_check(tile_xy, n, capacity, io, true)) {if (io.total) {be.fill32(io.total, 0u, 1);} return;}
 		std::vector<int32_t> const nbr = batch_neighbours(tile_xy, n, "tiles_update_clouds");
-		cloud_consts_t const c = cloud_consts(cp, s, gauss_dev(), cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), zmin, zmax, capacity);
-		// scratch: the coordinates, the neighbour table; for the kernels the marks of cloud_path and the marked tiles in batch order
-		int32_t *d_txy_w, *d_nbr_w; uint32_t *d_marks, *d_order;
-		stage_layout_t lay;
-		lay.add(d_txy_w, (size_t)n*2); lay.add(d_nbr_w, (size_t)n*9); lay.add(d_marks, ((size_t)n + 3)/4); lay.add(d_order, n);
+		cloud_consts_t const c = cloud_consts(cp, step, gauss_dev(), cfg.scene_x, cfg.scene_y, DX_VAL, DY_VAL, (int)tile_size(), zmin, zmax, capacity);
+		cloud_update_scratch_t s; stage_layout_t lay;
+		cloud_update_scratch_add(lay, s, n);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
-		be.h2d_async(d_txy_w, tile_xy, (size_t)n*8);
-		be.h2d_async(d_nbr_w, nbr.data(), (size_t)n*9*sizeof(int32_t));
-		int32_t const *d_txy = d_txy_w, *d_nbr = d_nbr_w;
+		be.h2d_async(s.txy, tile_xy, (size_t)n*8);
+		be.h2d_async(s.nbr, nbr.data(), (size_t)n*9*sizeof(int32_t));
 		if constexpr (BE::has_kernels) {
-			be.fill32(d_marks, 0u, ((size_t)n + 3)/4);
-			if (be.tile_update_clouds(c, d_txy, d_nbr, n, d_state, d_clouds, (uint8_t *)d_marks, d_order, d_total)) return;
+			be.fill32(s.marks, 0u, ((size_t)n + 3)/4);
+			if (be.tile_update_clouds(c, io, s, n)) return;
 		}
 		// the simple form: one thread, the reference's loop over the batch in order
-		be.launch(1, [=] TERRA_LAMBDA (size_t) {
-			uint32_t num = 0;
-			for (uint32_t t = 0; t < n; ++t) {cloud_update_tile(c, d_txy, d_nbr, d_state, d_clouds, t); num += d_state[t].count;}
-			if (d_total) {*d_total = num;}
-		});
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {cloud_update_literal(c, io, s, n);});
 	}
 	// ---- the cloud draw list of a batch: tile_cloud_manager_t::get_draw_list for every tile (:1799-1820), the sort of :3493, tile_cloud_t::draw's decision (:1691-1697)
 	void cloud_view_check(view_pod_t const &view, cloud_view_args_pod_t const &a) const {
@@ -3420,59 +3279,27 @@ template<class BE> struct terra_engine {
 		}
 		if (!(a.max_dist > 0.0f)) throw std::invalid_argument("tiles_cloud_view: max_dist must be > 0");
 	}
-	void tiles_cloud_view_dev(int32_t const *tile_xy, uint32_t n, view_pod_t const &view, cloud_view_args_pod_t const &a, terra_tile_stats const *d_stats, cloud_tile_pod_t const *d_state,
-		cloud_pod_t const *d_clouds, uint32_t capacity, uint8_t *d_stage, cloud_inst_pod_t *d_list, uint32_t *d_list_count)
-	{
+	void tiles_cloud_view_dev(int32_t const *tile_xy, uint32_t n, view_pod_t const &view, cloud_view_args_pod_t const &a, uint32_t capacity, cloud_view_io_t const &io) {
 		cloud_view_check(view, a);
-		if (((uintptr_t)d_state & 7u) != 0 || ((((uintptr_t)d_stats | (uintptr_t)d_clouds | (uintptr_t)d_list | (uintptr_t)d_list_count)) & 3u) != 0) {
-			throw std::invalid_argument("tiles_cloud_view: d_state must be 8-byte aligned, d_stats, d_clouds, d_list and d_list_count 4-byte aligned");
-		}
-		if (n == 0) {if (d_list_count) {be.fill32(d_list_count, 0u, 1);} return;}
+		if (!cloud_view_io_check(tile_xy, n, capacity, io, true)) {if (io.list_count) {be.fill32(io.list_count, 0u, 1);} return;}
 		size_t const nrec = (size_t)n*capacity;
-		if (!tile_xy || !d_stats || !d_state || !d_list_count || (nrec && (!d_clouds || !d_stage || !d_list))) throw std::invalid_argument("tiles_cloud_view: null argument");
-		if (nrec > 0x7FFFFFFFu) throw std::invalid_argument("tiles_cloud_view: n*capacity must be below 2^31");
 		tree_place_consts_t tc;
 		tree_scene_consts(0, 0, nullptr, tc); // no_xyoff = 1
 		tc.st = sinTable_dev();
 		cloud_view_consts_t c;
 		c.v = view; c.behind_sphere_mult = a.behind_sphere_mult; c.xlate[0] = a.xlate[0]; c.xlate[1] = a.xlate[1]; c.xlate[2] = a.xlate[2]; c.max_dist = a.max_dist;
 		c.water_plane_z = water_plane_z; c.capacity = capacity;
-		// scratch: get_exact_zval's constants (read from memory), the instances by slot and then in the order they were listed, their number
-		tree_place_consts_t *d_tc; cloud_inst_pod_t *d_by_slot, *d_found; uint32_t *d_cnt;
-		stage_layout_t lay;
-		lay.add(d_tc, 1); lay.add(d_by_slot, nrec); lay.add(d_found, nrec); lay.add(d_cnt, 4);
+		cloud_view_scratch_t s; stage_layout_t lay;
+		cloud_view_scratch_add(lay, s, nrec);
 		lay.bind(scratch<uint8_t>(s_ao, lay.total));
-		be.h2d_async(d_tc, &tc, sizeof(tc));
-		be.fill32(d_cnt, 0u, 1);
-		tree_place_consts_t const *d_tcc = d_tc;
-		if (nrec == 0) {be.fill32(d_list_count, 0u, 1); return;}
-		if constexpr (BE::has_kernels) {if (be.tile_cloud_view(c, d_tcc, n, d_stats, d_state, d_clouds, d_stage, d_found, d_cnt, d_list, d_list_count)) return;}
-		// the simple form.  (1) a logical thread per record slot: get_draw_list's decision
-		be.launch(nrec, [=] TERRA_LAMBDA (size_t i) {
-			uint32_t const t = (uint32_t)(i/capacity), k = (uint32_t)(i%capacity);
-			uint32_t stg = CLV_NONE;
-			if (k < d_state[t].count) {
-				cloud_inst_pod_t o; o.tile = t; o.slot = k;
-				stg = cloud_view_record(c, d_clouds[i], d_stats[t].mzmin, d_stats[t].mzmax, [&](float x, float y) {return tree_exact_zval(*d_tcc, x, y);}, o);
-				if (stg == CLV_LISTED) {d_by_slot[i] = o;}
-			}
-			d_stage[i] = (uint8_t)stg;
-		});
-		// (2) one thread: to_draw_clouds as the loop of :3491 fills it, in batch order
-		be.launch(1, [=] TERRA_LAMBDA (size_t) {
-			uint32_t cnt = 0;
-			for (size_t i = 0; i < nrec; ++i) {if (d_stage[i] == CLV_LISTED) {d_found[cnt++] = d_by_slot[i];}}
-			*d_cnt = cnt; *d_list_count = cnt;
-		});
-		// (3) the sort of :3493: an entry's place is its rank
-		be.launch(nrec, [=] TERRA_LAMBDA (size_t i) {
-			uint32_t const cnt = *d_cnt;
-			if (i >= cnt) return;
-			cloud_inst_pod_t const me = d_found[i];
-			uint32_t rank = 0;
-			for (uint32_t j = 0; j < cnt; ++j) {rank += cloud_inst_before(d_found[j], me) ? 1u : 0u;}
-			d_list[rank] = me;
-		});
+		be.h2d_async(s.tc, &tc, sizeof(tc));
+		be.fill32(s.cnt, 0u, 1);
+		if (nrec == 0) {be.fill32(io.list_count, 0u, 1); return;}
+		if constexpr (BE::has_kernels) {if (be.tile_cloud_view(c, io, s, n)) return;}
+		// the simple form.  (1) a logical thread per record slot: get_draw_list's decision; (2) one thread: the listed instances in batch order; (3) the sort: an entry's place is its rank
+		be.launch(nrec, [=] TERRA_LAMBDA (size_t i) {cloud_view_slot_literal(c, io, s, i);});
+		be.launch(1, [=] TERRA_LAMBDA (size_t) {cloud_view_found_literal(io, s, nrec);});
+		be.launch(nrec, [=] TERRA_LAMBDA (size_t i) {cloud_view_rank_literal(io, s, i);});
 	}
 
 	// ---- sphere collisions and tree box tests against the containers of a batch (terra_collide.hpp): tile_draw_t::check_sphere_collision / tile_t::check_sphere_collision

@@ -640,43 +640,28 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		return launch_per_tile<terra::GV_THREADS>(terra::k_grass_view, n, c, tile_xy, io.zvals, io.stats, io.blocks, io.skip, capacity, io.insts, io.aux, io.group_counts, io.counts,
 			io.pass, keys);
 	}
-	// the terrain draw list for a camera: the five launches of k_terrain_view_* (terra_kernels.hpp)
-	bool tile_terrain_view(terra::terrain_view_consts_t const &c, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, uint8_t *status,
-		float *dist, uint8_t *lod, uint8_t *crack, uint32_t *draw_order, uint32_t *occluded, uint32_t *counts, uint8_t *not_drawn, terra::terrain_view_occluder_t *occ, uint32_t *nocc, uint8_t *test,
-		float *keys, uint32_t *key_tile)
-	{
+	// the terrain draw list for a camera: the five launches of k_terrain_view_* (terra_kernels.hpp); with a box, reflection pass 1: k_reflect_walk and k_reflect_finish between
+	// the occlusion test and the lists (s.rt and s.prov are null in the terrain view)
+	bool terrain_view_launches(terra::terrain_view_consts_t const &c, terra::reflect_box_t const *box, terra::terrain_view_io_t const &io, terra::terrain_view_scratch_t const &s, uint32_t n) {
 		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
 		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
-		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c, in, tile_xy, n, status, dist, lod, test, (terra::reflect_tile_t *)nullptr);
-		run(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, c, in, tile_xy, n, status, occ, nocc);
-		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c, in, tile_xy, occ, nocc, test, status, (uint8_t *)nullptr);
-		run(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
-		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, keys, key_tile, counts, draw_order);
+		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c, io.in, s.txy, n, io.status, io.dist, io.lod, s.test, s.rt);
+		run(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, c, io.in, s.txy, n, io.status, s.occ, s.nocc);
+		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c, io.in, s.txy, s.occ, s.nocc, s.test, io.status, s.prov);
+		if (box) {
+			run(terra::k_reflect_walk, dim3(n), dim3(terra::RF_THREADS), ((size_t)box->nwords + box->cap)*4, s.rc, io.in.stats, s.txy, s.nbr, s.rt, io.status, s.prov, *box, s.refl, io.reflect ? io.reflect : s.refl);
+			run(terra::k_reflect_finish, dim3(nb), dim3(T), 0, n, s.prov, s.refl, io.status, io.in.occl_state);
+		}
+		run(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, s.nbr, n, io.status, io.dist, io.lod, io.crack, io.draw_order, io.occluded, io.counts, io.not_drawn, s.keys, s.key_tile);
+		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, s.keys, s.key_tile, io.counts, io.draw_order);
 		return true;
 	}
-	// the terrain draw list of reflection pass 1: the launches of the terrain view with k_reflect_walk and k_reflect_finish between the occlusion test and the lists
-	bool tile_reflection_view(terra::reflect_consts_t const &c, terra::reflect_consts_t const *d_consts, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, terra::reflect_box_t const &box,
-		uint8_t *status, float *dist, uint8_t *lod, uint8_t *crack, uint32_t *draw_order, uint32_t *occluded, uint32_t *counts, uint8_t *not_drawn, uint8_t *reflect,
-		terra::terrain_view_occluder_t *occ, uint32_t *nocc, uint8_t *test, float *keys, uint32_t *key_tile, terra::reflect_tile_t *rt, uint8_t *prov, uint8_t *refl)
-	{
-		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
-		use();
-		uint32_t const T = terra::TV_THREADS, nb = (n + T - 1)/T;
-		run(terra::k_terrain_view_tiles, dim3(nb), dim3(T), 0, c.tv, in, tile_xy, n, status, dist, lod, test, rt);
-		run(terra::k_terrain_view_occluders, dim3(1), dim3(T), 0, c.tv, in, tile_xy, n, status, occ, nocc);
-		run(terra::k_terrain_view_occlusion, dim3(n), dim3(T), 0, c.tv, in, tile_xy, occ, nocc, test, status, prov);
-		run(terra::k_reflect_walk, dim3(n), dim3(terra::RF_THREADS), ((size_t)box.nwords + box.cap)*4, d_consts, in.stats, tile_xy, nbr, rt, status, prov, box, refl, reflect ? reflect : refl);
-		run(terra::k_reflect_finish, dim3(nb), dim3(T), 0, n, prov, refl, status, in.occl_state);
-		run(terra::k_terrain_view_lists, dim3(1), dim3(T), 0, nbr, n, status, dist, lod, crack, draw_order, occluded, counts, not_drawn, keys, key_tile);
-		run(terra::k_terrain_view_rank, dim3(nb), dim3(T), 0, keys, key_tile, counts, draw_order);
-		return true;
-	}
+	bool tile_terrain_view(terra::terrain_view_consts_t const &c, terra::terrain_view_io_t const &io, terra::terrain_view_scratch_t const &s, uint32_t n) {return terrain_view_launches(c, nullptr, io, s, n);}
+	bool tile_reflection_view(terra::reflect_consts_t const &c, terra::reflect_box_t const &box, terra::terrain_view_io_t const &io, terra::terrain_view_scratch_t const &s, uint32_t n) {return terrain_view_launches(c.tv, &box, io, s, n);}
 	// water quads and water caps: one workgroup (k_water_view)
-	bool tile_water_view(terra::terrain_view_consts_t const &c, terra::terrain_view_in_t const &in, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, uint8_t const *status, uint8_t *wv,
-		uint32_t *water_list, uint8_t *cap_mask, uint32_t *counts)
-	{
-		return launch_if(true, terra::k_water_view, dim3(1), dim3(terra::TV_THREADS), c, in, tile_xy, nbr, n, status, wv, water_list, cap_mask, counts);
+	bool tile_water_view(terra::terrain_view_consts_t const &c, terra::water_view_io_t const &io, terra::water_view_scratch_t const &s, uint32_t n) {
+		return launch_if(true, terra::k_water_view, dim3(1), dim3(terra::TV_THREADS), c, io.in, s.txy, s.nbr, n, io.status, s.wv, io.water_list, io.cap_mask, io.counts);
 	}
 	// the shadow-map plan: a lane per tile, the receivers by one workgroup, the recompute queue by rank (k_smap_plan*)
 	bool tile_smap_plan(terra::smap_consts_t const &c, terra::terrain_view_in_t const &in, terra::smap_plan_io_t const &io, int32_t const *tile_xy, uint32_t n, terra::smap_rank_key_t *keys) {
@@ -702,26 +687,23 @@ struct hip_backend_t : terra::simple_paths<hip_backend_t> {
 		return true;
 	}
 	// the clouds' update: the marks of every record's path, the unmarked tiles in parallel, the marked tiles replayed in batch order by one workgroup
-	bool tile_update_clouds(terra::cloud_consts_t const &c, int32_t const *tile_xy, int32_t const *nbr, uint32_t n, terra::cloud_tile_pod_t *state, terra::cloud_pod_t *clouds,
-		uint8_t *touched, uint32_t *order, uint32_t *total)
-	{
+	bool tile_update_clouds(terra::cloud_consts_t const &c, terra::cloud_update_io_t const &io, terra::cloud_update_scratch_t const &s, uint32_t n) {
 		if (opt->simple_kernels || n > 0x7FFFFFFFu) return false;
 		use();
 		uint32_t const T = terra::CLD_THREADS, nb = (n + T - 1)/T;
-		run(terra::k_cloud_mark, dim3(nb), dim3(T), 0, c, nbr, n, (terra::cloud_tile_pod_t const *)state, (terra::cloud_pod_t const *)clouds, touched);
-		run(terra::k_cloud_tiles, dim3(nb), dim3(T), 0, c, tile_xy, nbr, n, (uint8_t const *)touched, state, clouds);
-		run(terra::k_cloud_tail, dim3(1), dim3(T), 0, c, tile_xy, nbr, n, (uint8_t const *)touched, order, state, clouds, total);
+		uint8_t *const touched = (uint8_t *)s.marks;
+		run(terra::k_cloud_mark, dim3(nb), dim3(T), 0, c, s.nbr, n, io.state, io.clouds, touched);
+		run(terra::k_cloud_tiles, dim3(nb), dim3(T), 0, c, s.txy, s.nbr, n, touched, io.state, io.clouds);
+		run(terra::k_cloud_tail, dim3(1), dim3(T), 0, c, s.txy, s.nbr, n, touched, s.order, io.state, io.clouds, io.total);
 		return true;
 	}
 	// the clouds' draw list: a lane per record slot, then every listed instance to its rank
-	bool tile_cloud_view(terra::cloud_view_consts_t const &c, terra::tree_place_consts_t const *consts, uint32_t n, terra_tile_stats const *stats, terra::cloud_tile_pod_t const *state,
-		terra::cloud_pod_t const *clouds, uint8_t *stage, terra::cloud_inst_pod_t *found, uint32_t *cnt, terra::cloud_inst_pod_t *list, uint32_t *list_count)
-	{
+	bool tile_cloud_view(terra::cloud_view_consts_t const &c, terra::cloud_view_io_t const &io, terra::cloud_view_scratch_t const &s, uint32_t n) {
 		if (opt->simple_kernels) return false;
 		use();
 		uint32_t const T = terra::CLD_THREADS, nrec = n*c.capacity, nb = (nrec + T - 1)/T;
-		run(terra::k_cloud_view, dim3(nb), dim3(T), 0, c, consts, nrec, stats, state, clouds, stage, found, cnt);
-		run(terra::k_cloud_rank, dim3(nb), dim3(T), 0, (terra::cloud_inst_pod_t const *)found, (uint32_t const *)cnt, list, list_count);
+		run(terra::k_cloud_view, dim3(nb), dim3(T), 0, c, s.tc, nrec, io.stats, io.state, io.clouds, io.stage, s.found, s.cnt);
+		run(terra::k_cloud_rank, dim3(nb), dim3(T), 0, s.found, s.cnt, io.list, io.list_count);
 		return true;
 	}
 	// sphere collisions and tree box tests: one wave per query, four to a workgroup (k_sphere_collide, k_cube_int_trees)

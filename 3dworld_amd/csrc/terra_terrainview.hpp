@@ -15,7 +15,10 @@
 // clipped by it, and a column s of o that is not zeroed and clips all four top points of the sub-box".  It does not depend on the order of the occluders.
 #pragma once
 #include "terra_view.hpp"
+#include "terra_stage.hpp"
 #include "../../include/terra.h"
+#include <stdexcept>
+#include <string>
 
 namespace terra {
 
@@ -251,5 +254,77 @@ TERRA_HD bool terrain_view_occluded(terrain_view_consts_t const &c, terrain_view
 TERRA_HD bool terrain_view_before(float da, uint32_t ia, float db, uint32_t ib) {return da < db || (!(db < da) && ia < ib);}
 
 TERRA_HD bool terrain_view_args_finite(terrain_view_args_pod_t const &a) {return isfinite(a.behind_sphere_mult) && isfinite(a.occluder_zmin);}
+
+// ---- the arrays of a call, in the order of terra_tiles_terrain_view[_dev] and terra_tiles_reflection_view[_dev] (reflect: the reflection view's, null in the terrain view)
+struct terrain_view_io_t {terrain_view_in_t in; uint8_t *status; float *dist; uint8_t *lod, *crack; uint32_t *draw_order, *occluded, *counts; uint8_t *not_drawn, *reflect;};
+// the argument rules of both views, behind their checks that need no array: throws what the call refuses; false: nothing to do (n == 0).  what: the pass's name; dev: the arrays are the device's
+inline bool terrain_view_io_check(char const *what, int32_t const *tile_xy, uint32_t n, terrain_view_io_t const &io, bool dev) {
+	if (n == 0) return false;
+	if (!tile_xy || !io.in.stats || !io.status || !io.dist || !io.lod || !io.crack || !io.draw_order || !io.occluded || !io.counts) throw std::invalid_argument(std::string(what) + ": null argument");
+	if (dev && (((uintptr_t)io.in.stats | (uintptr_t)io.in.min_normal_z | (uintptr_t)io.in.trmax | (uintptr_t)io.in.tile_zmax | (uintptr_t)io.dist | (uintptr_t)io.draw_order | (uintptr_t)io.occluded |
+	             (uintptr_t)io.counts) & 3u) != 0) throw std::invalid_argument(std::string(what) + ": d_stats, d_min_normal_z, d_trmax, d_tile_zmax, d_dist, d_draw_order, d_occluded and d_counts must be 4-byte aligned");
+	return true;
+}
+// ---- the scratch of both views: the coordinates and the neighbour table, the occluders of the batch in batch order with their count, the candidates that run the occlusion
+// test, and the (dist, batch index) keys of the drawn tiles in batch order for the order's second path.  The reflection view's alone, null in the terrain view: the constants for
+// k_reflect_walk, per tile what the walk reads of it, the marks of the walk (the start tile's index + 1), its work list, the provisional result of the occlusion test, the answer of :2869, last_occluded as the loop goes
+struct reflect_consts_t; struct reflect_tile_t;
+struct terrain_view_scratch_t {
+	int32_t *txy, *nbr; terrain_view_occluder_t *occ; uint32_t *nocc, *key_tile; uint8_t *test; float *keys;
+	reflect_consts_t *rc; reflect_tile_t *rt; uint32_t *mark; int32_t *work; uint8_t *prov, *refl, *state;
+};
+inline void terrain_view_scratch_add(stage_layout_t &lay, terrain_view_scratch_t &s, uint32_t n) {lay.add(s.occ, n); lay.add(s.txy, (size_t)n*2); lay.add(s.nbr, (size_t)n*9); lay.add(s.nocc, 4); lay.add(s.keys, n); lay.add(s.key_tile, n); lay.add(s.test, n);}
+// ---- the literal bodies of the simple form.  (1) a logical thread per tile: everything but the occlusion test, the cracks and the lists
+TERRA_HD terrain_view_tile_t terrain_view_tile_literal(terrain_view_consts_t const &c, terrain_view_io_t const &io, terrain_view_scratch_t const &s, size_t t) {
+	terrain_view_tile_t const o = terrain_view_tile(c, io.in, s.txy, t);
+	io.status[t] = (uint8_t)(o.status | (o.occluder ? TV_WAS_OCCLUDER : 0)); io.dist[t] = o.dist; io.lod[t] = o.lod; s.test[t] = o.test;
+	return o;
+}
+// (2) one thread: the occluders in batch order, as the loop of :2858-2861 leaves them; -> their number
+TERRA_HD uint32_t terrain_view_occluders_literal(terrain_view_consts_t const &c, terrain_view_io_t const &io, terrain_view_scratch_t const &s, uint32_t n) {
+	uint32_t m = 0;
+	for (uint32_t t = 0; t < n; ++t) {
+		if (!(io.status[t] & TV_WAS_OCCLUDER)) continue;
+		terrain_view_geom_t const g = terrain_view_geom_of(c, io.in, s.txy, t);
+		terrain_view_occluder_t &o = s.occ[m++];
+		terrain_view_mesh_box(g, io.in.stats[t].mzmin, io.in.stats[t].mzmax, o.bc);
+		for (uint32_t q = 0; q < 16; ++q) {terrain_view_occluder_column(c, g, io.in.stats[t], q, o.sub[q]);}
+		o.tile = (int32_t)t; o.pad = 0;
+	}
+	return *s.nocc = m;
+}
+// (3) a thread per tile: the loop of :2872-2908
+TERRA_HD void terrain_view_occlusion_literal(terrain_view_consts_t const &c, terrain_view_io_t const &io, terrain_view_scratch_t const &s, size_t t) {
+	uint32_t const nocc = *s.nocc;
+	if ((io.status[t] & TV_STATUS_MASK) != TV_DRAWN || !s.test[t] || nocc == 0) return;
+	bool const occluded = terrain_view_occluded(c, terrain_view_geom_of(c, io.in, s.txy, t), io.in.stats[t], s.occ, nocc, (int32_t)t);
+	if (occluded) {io.status[t] = (uint8_t)((io.status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
+	if (io.in.occl_state) {io.in.occl_state[t] = occluded ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED;} // set_last_occluded (:2906)
+}
+// the last step of both views, a thread per tile: its cracks, and its place in its list -- the rank of (dist, batch index) among the drawn tiles is where the sort of :2915 puts it
+TERRA_HD void terrain_view_lists_literal(terrain_view_io_t const &io, terrain_view_scratch_t const &s, uint32_t n, size_t t) {
+	uint32_t const me = io.status[t] & TV_STATUS_MASK;
+	for (uint32_t k = 0; k < 4; ++k) {
+		int32_t const u = s.nbr[t*9 + terrain_view_nbr_slot(k >> 1, k & 1u)];
+		bool const adj = me == TV_DRAWN && u >= 0 && (io.status[u] & TV_STATUS_MASK) != TV_ABSENT;
+		io.crack[t*4 + k] = adj ? (uint8_t)terrain_view_crack_index(k >> 1, k & 1u, io.lod[t], io.lod[u]) : TERRAIN_VIEW_NO_CRACK;
+	}
+	if (io.not_drawn) {io.not_drawn[t] = (me != TV_DRAWN) ? 1 : 0;}
+	if (me == TV_DRAWN) {
+		uint32_t rank = 0;
+		for (uint32_t u = 0; u < n; ++u) {rank += ((io.status[u] & TV_STATUS_MASK) == TV_DRAWN && terrain_view_before(io.dist[u], u, io.dist[t], (uint32_t)t)) ? 1u : 0u;}
+		io.draw_order[rank] = (uint32_t)t;
+	}
+	else if (me == TV_OCCLUDED) {
+		uint32_t rank = 0;
+		for (uint32_t u = 0; u < t; ++u) {rank += ((io.status[u] & TV_STATUS_MASK) == TV_OCCLUDED) ? 1u : 0u;}
+		io.occluded[rank] = (uint32_t)t;
+	}
+	if (t == 0) {
+		uint32_t nd = 0, no = 0;
+		for (uint32_t u = 0; u < n; ++u) {uint32_t const su = io.status[u] & TV_STATUS_MASK; nd += (su == TV_DRAWN) ? 1u : 0u; no += (su == TV_OCCLUDED) ? 1u : 0u;}
+		io.counts[0] = nd; io.counts[1] = no;
+	}
+}
 
 } // namespace terra

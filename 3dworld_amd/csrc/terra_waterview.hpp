@@ -169,4 +169,69 @@ TERRA_HD uint32_t water_view_caps(terrain_view_consts_t const &c, uint32_t w, ui
 
 TERRA_HD bool reflection_view_args_finite(reflection_view_args_pod_t const &a) {return terrain_view_args_finite(a.tv) && isfinite(a.zmax);}
 
+// ---- the reflection view: the terrain view's records (terrain_view_io_t, terrain_view_io_check, terrain_view_scratch_t), all of the scratch
+inline void reflection_view_scratch_add(stage_layout_t &lay, terrain_view_scratch_t &s, uint32_t n) {
+	lay.add(s.rc, 1); lay.add(s.rt, n); lay.add(s.occ, n); lay.add(s.txy, (size_t)n*2); lay.add(s.nbr, (size_t)n*9); lay.add(s.nocc, 4); lay.add(s.keys, n); lay.add(s.key_tile, n); lay.add(s.mark, n);
+	lay.add(s.work, n); lay.add(s.test, n); lay.add(s.prov, n); lay.add(s.refl, n); lay.add(s.state, n);
+}
+// the literal bodies of its simple form.  (1) a logical thread per tile: the terrain view's first step, and what the loop of :2863 reads of the tile
+TERRA_HD void reflection_view_tile_literal(terrain_view_consts_t const &c, terrain_view_io_t const &io, terrain_view_scratch_t const &s, size_t t) {
+	terrain_view_tile_t const o = terrain_view_tile_literal(c, io, s, t);
+	s.rt[t] = reflect_tile(c, io.in, s.txy, t, o.visible != 0);
+	s.state[t] = io.in.occl_state ? io.in.occl_state[t] : (uint8_t)TV_STATE_NONE; s.mark[t] = 0u;
+	if (io.reflect) {io.reflect[t] = RF_NOT_ASKED;}
+}
+// (2) one thread: the occluders in batch order, then the loop of :2863 as written, in batch order: a tile's walk sees what the turns before it left of last_occluded.  c: the
+// launch's own copy of rc.tv (as an alias of rc.tv the kernel reloaded n from its arguments in every skipped turn of the occluder loop: 3% at 4096 tiles)
+TERRA_HD void reflection_view_loop_literal(terrain_view_consts_t const &c, reflect_consts_t const &rc, terrain_view_io_t const &io, terrain_view_scratch_t const &s, uint32_t n) {
+	terrain_view_in_t const &in = io.in;
+	uint32_t const nocc = terrain_view_occluders_literal(c, io, s, n);
+	for (uint32_t t = 0; t < n; ++t) {
+		if ((io.status[t] & TV_STATUS_MASK) != TV_DRAWN) continue;
+		terrain_view_geom_t const g = terrain_view_geom_of(c, in, s.txy, t);
+		uint32_t r = reflect_without_walk(c, s.rt[t].flags);
+		if (r == RF_NOT_ASKED) {
+			reflect_corners_t const k = reflect_corners(c, g.bc, in.stats[t].mzmax);
+			auto seen = [&](uint32_t u) {bool const was = s.mark[u] == t + 1u; s.mark[u] = t + 1u; return was;};
+			auto occluded = [&](uint32_t u) {return s.state[u] == TV_STATE_OCCLUDED;};
+			r = reflect_walk(rc, in.stats, s.nbr, s.rt, t, k, s.work, n, seen, occluded, [](reflect_corners_t &) {}) ? RF_WALK_FOUND : RF_WALK_NOTHING;
+		}
+		if (io.reflect) {io.reflect[t] = (uint8_t)r;}
+		if (r < RF_HAS_WATER) {io.status[t] = (uint8_t)((io.status[t] & ~TV_STATUS_MASK) | TV_NO_REFLECTION); continue;} // :2869
+		if (!s.test[t] || nocc == 0) continue;
+		bool const occluded_now = terrain_view_occluded(c, g, in.stats[t], s.occ, nocc, (int32_t)t);
+		if (occluded_now) {io.status[t] = (uint8_t)((io.status[t] & ~TV_STATUS_MASK) | TV_OCCLUDED);}
+		s.state[t] = occluded_now ? TV_STATE_OCCLUDED : TV_STATE_UNOCCLUDED; // set_last_occluded (:2906)
+		if (in.occl_state) {in.occl_state[t] = s.state[t];}
+	}
+}
+
+// ---- the arrays of a water view call, in the order of terra_tiles_water_view[_dev] (in.min_normal_z and in.occl_state are not the pass's: null)
+struct water_view_io_t {terrain_view_in_t in; uint8_t const *status; uint32_t *water_list; uint8_t *cap_mask; uint32_t *counts;};
+// the argument rules of a call, behind water_view_check: throws what the call refuses; false: nothing to do (n == 0).  dev: the arrays are the device's
+inline bool water_view_io_check(int32_t const *tile_xy, uint32_t n, water_view_io_t const &io, bool dev) {
+	if ((io.status != nullptr) != (io.cap_mask != nullptr)) throw std::invalid_argument("tiles_water_view: status and cap_mask are both null or both given");
+	if (n == 0) return false;
+	if (!tile_xy || !io.in.stats || !io.water_list || !io.counts) throw std::invalid_argument("tiles_water_view: null argument");
+	if (dev && (((uintptr_t)io.in.stats | (uintptr_t)io.in.trmax | (uintptr_t)io.in.tile_zmax | (uintptr_t)io.water_list | (uintptr_t)io.counts) & 3u) != 0) throw std::invalid_argument(
+		"tiles_water_view: d_stats, d_trmax, d_tile_zmax, d_water_list and d_counts must be 4-byte aligned");
+	return true;
+}
+// scratch: the coordinates, the neighbour table, and what the pass keeps of a tile (WV_*)
+struct water_view_scratch_t {int32_t *txy, *nbr; uint8_t *wv;};
+inline void water_view_scratch_add(stage_layout_t &lay, water_view_scratch_t &s, uint32_t n) {lay.add(s.txy, (size_t)n*2); lay.add(s.nbr, (size_t)n*9); lay.add(s.wv, n);}
+// the literal body of the simple form's second step, one thread (the first is water_view_tile, a thread per tile): tile_draw_t::draw_water's loop in batch order, then the caps
+TERRA_HD void water_view_lists_literal(terrain_view_consts_t const &c, water_view_io_t const &io, water_view_scratch_t const &s, uint32_t n) {
+	uint32_t nw = 0, nc = 0;
+	for (uint32_t t = 0; t < n; ++t) {if (water_view_listed(s.wv[t])) {io.water_list[nw++] = t;}}
+	io.counts[0] = nw;
+	if (!io.status) return;
+	for (uint32_t t = 0; t < n; ++t) {
+		uint32_t const m = water_view_caps(c, s.wv[t], io.status[t], s.nbr, s.wv, t);
+		io.cap_mask[t] = (uint8_t)m;
+		nc += m ? 1u : 0u;
+	}
+	io.counts[1] = nc;
+}
+
 } // namespace terra

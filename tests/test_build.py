@@ -1,9 +1,10 @@
 import pytest
 
 
-@pytest.mark.parametrize("header", ["terra_grassview.hpp", "terra_treeview.hpp", "terra_sceneryview.hpp", "terra_decidview.hpp", "terra_lineintersect.hpp"])
+@pytest.mark.parametrize("header", ["terra_grassview.hpp", "terra_treeview.hpp", "terra_sceneryview.hpp", "terra_decidview.hpp", "terra_lineintersect.hpp", "terra_terrainview.hpp",
+                                    "terra_waterview.hpp", "terra_clouds.hpp", "terra_smapview.hpp"])
 def test_pass_header_stands_alone(header, tmp_path):
-    """A draw-list pass header holds the pass's records, constants, leaf functions and literal body, and the line-query header the leaf code the grass pass
+    """A pass header holds the pass's records, its argument rules, constants, leaf functions and literal bodies, and the line-query header the leaf code the grass pass
     shares with the line queries: a translation unit that includes nothing else compiles as plain C++17 -- nothing in them needs the driver."""
     import os, shutil, subprocess
     cxx = shutil.which(os.environ.get("CXX") or "g++")

@@ -41,7 +41,7 @@ def test_view_cases_host_form(pkg, gpu, orc, name):
     cc.run_view_case(pkg, gpu, orc, V_BY_NAME[name])
 
 
-@pytest.mark.parametrize("name", ["row_crossed_in_one_frame", "diagonal_against_order", "drop_at_ungenerated", "fed_before_turn", "holes_shuffled_s128"])
+@pytest.mark.parametrize("name", ["row_crossed_in_one_frame", "diagonal_against_order", "drop_at_ungenerated", "fed_before_turn", "holes_shuffled_s128", "overflow", "density_zero"])
 def test_update_cases_simple_form(pkg, gpu, orc, name):
     with simple_form(gpu):
         cc.run_update_case(pkg, gpu, orc, U_BY_NAME[name], dev=True)

@@ -34,7 +34,7 @@ def test_cases_host_form(pkg, gpu, orc, name):
     tc.run_case(pkg, gpu, orc, BY_NAME[name])
 
 
-@pytest.mark.parametrize("name", ["ridge_low_camera", "many_drawn_equal", "many_drawn_distinct", "lod_classes_s128", "cracks"])
+@pytest.mark.parametrize("name", ["ridge_low_camera", "many_drawn_equal", "many_drawn_distinct", "lod_classes_s128", "cracks", "state_in", "all_arrays"])
 def test_cases_simple_form(pkg, gpu, orc, name):
     with simple_form(gpu):
         tc.run_case(pkg, gpu, orc, BY_NAME[name], dev=True)

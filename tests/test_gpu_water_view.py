@@ -42,13 +42,13 @@ def test_water_cases_host_form(pkg, gpu, orc, name):
     wc.run_water_case(pkg, gpu, orc, W_BY_NAME[name])
 
 
-@pytest.mark.parametrize("name", ["reflect_values", "order_shuffled", "order_chain", "lod_pass1_s128"])
+@pytest.mark.parametrize("name", ["reflect_values", "order_shuffled", "order_chain", "lod_pass1_s128", "state_in_unoccluded", "all_arrays"])
 def test_reflection_cases_simple_form(pkg, gpu, orc, name):
     with simple_form(gpu):
         wc.run_case(pkg, gpu, orc, R_BY_NAME[name], dev=True)
 
 
-@pytest.mark.parametrize("name", ["caps_masks", "caps_distance"])
+@pytest.mark.parametrize("name", ["caps_masks", "caps_distance", "water_no_status"])
 def test_water_cases_simple_form(pkg, gpu, orc, name):
     with simple_form(gpu):
         wc.run_water_case(pkg, gpu, orc, W_BY_NAME[name], dev=True)
